@@ -12,6 +12,11 @@ the PCM when N > 1, inside the library: mis_comm_all_gather_pcm).  Inputs are re
   python bench.py --gpus 1 --steps 2 --warmup 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds, after the timed region, what the
+headline figure does not need: the frame-slot sampler run, the per-kernel roofline probes, the CPU baseline (--no-cpu-baseline
+leaves it out) and the other single-GPU configurations (--no-secondary leaves them out).  --dump-outputs DIR writes what the
+last timed step returned (dump_outputs) before any of that runs.
 """
 import argparse
 import json
@@ -319,6 +324,60 @@ def secondary_benches(device, orpheus=None):
     return out
 
 
+def dump_outputs(out_dir, pcm, lens, tokens):
+    """What a caller of the timed generate receives from its last step, as DIR/<name>.npy: `pcm` [rows, samples] float32 (zero past each
+    row's length; 25 MB at 32 rows - above 60 MB, a fixed seeded sample of the rows, listed in `pcm_rows`), `pcm_lengths` per row and
+    `generated_tokens` per row of this GPU (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pcm = pcm.cpu().numpy()
+    lens = np.asarray(lens, np.int64)
+    pcm = np.where(np.arange(pcm.shape[1])[None, :] < lens[:, None], pcm, 0.0).astype(np.float32)
+    max_rows = 60_000_000 // pcm[0].nbytes
+    if pcm.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(pcm.shape[0], max_rows, replace=False))
+        pcm = pcm[rows]
+        np.save(os.path.join(out_dir, "pcm_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "pcm.npy"), pcm)
+    np.save(os.path.join(out_dir, "pcm_lengths.npy"), lens.astype(np.float64))
+    np.save(os.path.join(out_dir, "generated_tokens.npy"), np.asarray(list(tokens), np.float64))
+
+
+def kernel_roofline(lm, timing):
+    """Roofline of the dominant kernel: the weight-streaming skinny GEMM (k_gemm_skinny); measured live with HIP events on the library's
+    stream, rotating over the 28 layers so the 256 MB Infinity Cache cannot serve the weights.  Dominant instance by bytes/step: gate+up
+    (42 % of the step's weight bytes)."""
+    names = ["qkv", "o_proj", "gate_up", "down", "lm_head", "attn_decode_ctx368", "reduce_residual_rmsnorm"]
+    kern = {}
+    for i, n in enumerate(names):
+        ms, by = lm.time_gemm(i, ROWS_PER_GPU, iters=56)
+        kern[n] = {"us": ms * 1e3, "GBps": by / ms / 1e6, "bytes": by}
+    dom = kern["gate_up"]
+    # HBM bytes per launch of the dominant kernel from the PMC passes of tools/pmc_traffic.sh (FETCH_SIZE / WRITE_SIZE in their own
+    # rocprofv3 runs, with the gfx950 corrections of tools/pmc_reduce.py); tagged with the kernel source it was measured on, so a stale
+    # figure is visible as such (VERDICT r01 weak 9)
+    traffic, traffic_src = None, None
+    for cand in ("r06_pmc", "r05_pmc", "r04_pmc", "r03_pmc", "r02_pmc", "r01_pmc"):
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", cand, "traffic.json")))
+            traffic = tj["gate_up"]["hbm_bytes_per_launch"]
+            traffic_src = {"file": f"profiles/{cand}/traffic.json", "measured_on_kernel_source": tj.get("kernel_source_sha1"),
+                           "current_kernel_source": kernel_source_sha1(),
+                           "matches_current_build": tj.get("kernel_source_sha1") == kernel_source_sha1()}
+            break
+        except Exception:
+            continue
+    step_ms = timing["step_ms_avg"]
+    step_GBps = timing["hbm_bytes_per_step"] / max(step_ms, 1e-9) / 1e6
+    return {"bound": "hbm", "kernel": "k_gemm_skinny<MT=2,R=4,silu_mul,KSB=4,U=3> (gate+up, 100.7 MB/launch)",
+            "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["GBps"] / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes": dom["bytes"],
+            "launch_us": dom["us"],
+            "kernels": {k: {"us": round(v["us"], 2), "GBps": round(v["GBps"], 1), "frac": round(v["GBps"] / HBM_PEAK_GBS, 3),
+                            "algorithmic_bytes": v["bytes"]} for k, v in kern.items()},
+            "step": {"ms": step_ms, "algorithmic_GB": timing["hbm_bytes_per_step"] / 1e9, "achieved_GBps": step_GBps,
+                     "frac": step_GBps / HBM_PEAK_GBS, "frac_of_measured_copy_6290": step_GBps / 6290.0}}
+
+
 def kernel_source_sha1():
     """Identity of the decode-step kernels a measurement belongs to (sha1 over the step chain's sources)."""
     import hashlib
@@ -339,7 +398,8 @@ def self_spawn(args):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup",
-           str(args.warmup)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+           str(args.warmup)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--full"] if args.full else []) + \
+          (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.run(cmd, env=env).returncode
@@ -350,9 +410,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (Whisper / Soprano / Qwen3-TTS) after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the frame-slot sampler, the per-kernel roofline probes, the CPU baseline and the "
+                         "secondary configurations")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configurations (Whisper / Soprano / Qwen3-TTS) after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_spawn(args))
 
@@ -441,13 +507,15 @@ def main():
     audio_s = float(alll.sum()) / 24000.0 * args.steps
     value = audio_s / elapsed
     timing = lm.last_timing()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, allp, alll, ntok)
     # The timed region above sends the WHOLE 156 940-id vocabulary through the sampler every step (frame_constrained = 2: every id
     # visited by k_samp_cluster, the ones outside the step's frame slot get zero mass - random weights must emit valid SNAC frames
     # for there to be audio to count).  That is the code path of a real, unconstrained checkpoint.  A checkpoint-specific shortcut
     # exists (frame_constrained = 1: only the 4096 ids of the slot are visited, k_samp_narrow); the same generate is run once more
-    # that way and reported beside the timed one as a secondary figure.
+    # that way and reported beside the timed one as a secondary figure (--full).
     narrow = None
-    if rank == 0:
+    if rank == 0 and args.full:
         gpn_ = mas.GenerateParameters(max_tokens=NEW_TOKENS, temperature=0.6, top_p=0.8, repetition_penalty=1.3,
                                       repetition_context_size=20, seed=2024, frame_constrained=True, row_offset=row0)
         gpn_c = gpn_.to_c()
@@ -461,41 +529,9 @@ def main():
 
     result = None
     if rank == 0:
-        # roofline of the dominant kernel: the weight-streaming skinny GEMM (k_gemm_skinny); measured live with
-        # HIP events on the library's stream, rotating over the 28 layers so the 256 MB Infinity Cache cannot
-        # serve the weights.  Dominant instance by bytes/step: gate+up (42 % of the step's weight bytes).
-        names = ["qkv", "o_proj", "gate_up", "down", "lm_head", "attn_decode_ctx368", "reduce_residual_rmsnorm"]
-        kern = {}
-        for i, n in enumerate(names):
-            ms, by = lm.time_gemm(i, ROWS_PER_GPU, iters=56)
-            kern[n] = {"us": ms * 1e3, "GBps": by / ms / 1e6, "bytes": by}
-        dom = kern["gate_up"]
-        # HBM bytes per launch of the dominant kernel from the PMC passes of tools/pmc_traffic.sh (FETCH_SIZE / WRITE_SIZE in their own
-        # rocprofv3 runs, gfx950 corrections of MI355X_MICROARCH.md); tagged with the kernel source it was measured on, so a stale
-        # figure is visible as such
-        traffic, traffic_src = None, None
-        for cand in ("r06_pmc", "r05_pmc", "r04_pmc", "r03_pmc", "r02_pmc", "r01_pmc"):
-            try:
-                tj = json.load(open(os.path.join(ROOT, "profiles", cand, "traffic.json")))
-                traffic = tj["gate_up"]["hbm_bytes_per_launch"]
-                traffic_src = {"file": f"profiles/{cand}/traffic.json", "measured_on_kernel_source": tj.get("kernel_source_sha1"),
-                               "current_kernel_source": kernel_source_sha1(),
-                               "matches_current_build": tj.get("kernel_source_sha1") == kernel_source_sha1()}
-                break
-            except Exception:
-                continue
-        step_ms = timing["step_ms_avg"]
-        step_GBps = timing["hbm_bytes_per_step"] / max(step_ms, 1e-9) / 1e6
-        roofline = {"bound": "hbm", "kernel": "k_gemm_skinny<MT=2,R=4,silu_mul,KSB=4,U=3> (gate+up, 100.7 MB/launch)",
-                    "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": dom["GBps"] / HBM_PEAK_GBS,
-                    "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes": dom["bytes"],
-                    "launch_us": dom["us"],
-                    "kernels": {k: {"us": round(v["us"], 2), "GBps": round(v["GBps"], 1), "frac": round(v["GBps"] / HBM_PEAK_GBS, 3),
-                                    "algorithmic_bytes": v["bytes"]} for k, v in kern.items()},
-                    "step": {"ms": step_ms, "algorithmic_GB": timing["hbm_bytes_per_step"] / 1e9, "achieved_GBps": step_GBps,
-                             "frac": step_GBps / HBM_PEAK_GBS, "frac_of_measured_copy_6290": step_GBps / 6290.0}}
+        roofline = kernel_roofline(lm, timing) if args.full else None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline({})
         result = {
             # BASELINE.json's metric is quoted per GPU; the bench contract wants `value` = the WHOLE-JOB aggregate over n_gpus (the
@@ -526,7 +562,7 @@ def main():
                                       "tokens per row %s" % (narrow["tokens_per_row_min"] if narrow else None)},
             "roofline": roofline, "cpu_baseline": cpu,
         }
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 result["secondary"] = secondary_benches(device, (lm_cfg, codec, flat, lens, gpc, pcm, n_samples, plens, ntok))
             except Exception as ex:                              # the headline line must not be lost to a secondary configuration

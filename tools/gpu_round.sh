@@ -4,6 +4,7 @@
 set -x
 cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p gpurun_out/final
+FINAL=$_                                   # the output folder just made
 export TMPDIR=/tmp
 rm -f gpurun_out/parity_observed.jsonl
 [ -n "$SKIP_TESTS" ] || { timeout 2400 python -m pytest tests -m gpu --runslow -q -rs --durations=8 2>&1 | grep -E "passed|failed|error|SKIPPED|s call|s setup" | tail -14 > gpurun_out/final/pytest_gpu.txt; cat gpurun_out/final/pytest_gpu.txt; }
@@ -13,7 +14,7 @@ cp gpurun_out/parity_observed.jsonl gpurun_out/final/ 2>/dev/null
 timeout 900 bash tools/pmc_traffic.sh final > gpurun_out/final/pmc.log 2>&1; cp gpurun_out/final_pmc/traffic.json gpurun_out/final/traffic.json
 rm -rf gpurun_out/final_pmc/fetch gpurun_out/final_pmc/write
 mkdir -p profiles/r06_pmc; [ -s gpurun_out/final/traffic.json ] && cp gpurun_out/final/traffic.json profiles/r06_pmc/traffic.json
-timeout 900 python bench.py > gpurun_out/final/bench.log 2>&1; tail -1 gpurun_out/final/bench.log > gpurun_out/final/bench.json
+timeout 900 python bench.py --full > "$FINAL/bench.log" 2>&1; tail -1 "$FINAL/bench.log" > "$FINAL/bench.json"
 rm -rf /tmp/ks; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > /tmp/ks.log 2>&1)
 cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) gpurun_out/final/bench_kernel_stats.csv
 timeout 120 python tools/samp_phases.py 32 2> gpurun_out/final/samp_phases.txt
