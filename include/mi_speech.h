@@ -638,7 +638,26 @@ mis_status mis_whisper_create(const mis_whisper_config*, int device, mis_whisper
  * WhisperModel.sanitize, WhisperModel.swift:321-478 */
 mis_status mis_whisper_set_tensor(mis_whisper*, const char* name, const void* data, mis_dtype dtype,
                                   const int64_t* shape, int ndim);
+/* the same keys in MLX's affine-quantised form (mlx-community whisper conversions; WhisperModel.fromDirectory quantises every Linear and
+ * decoder.embed_tokens, WhisperModel.swift:499-510): `name` is the `.weight` key (either layout), wq uint32 [N, K*bits/32], scales /
+ * biases [N, K/group_size] of dtype sb_dtype - the format and validation of mis_tts_set_tensor_quantized.  The reference keeps
+ * QuantizedLinear and never materialises the weight: quantizedMatmul applies scale and bias to float32 group sums.  So does the engine
+ * for the decoder matrices every step re-reads (self q|k|v, self out, cross q, cross out, fc1, fc2 and the tied vocab projection) when
+ * they arrive with 8 or 4 bits, group size 64 and bf16 or f16 scales (f16 read as stored): the codes are streamed (csrc/lm_qgemm.hip);
+ * a layer's q|k|v only if its three projections share bits and scale dtype.  The encoder matrices and the cross-attention K/V
+ * projections (run once per 30 s window at 1500 rows) are dequantised once at load into the bf16 layouts; so is the token-embedding
+ * gather (QuantizedEmbedding: dequantised rows).  Any other combination (2 bit, other group sizes, f32 scales, MIS_QUANT_NATIVE=0) is
+ * dequantised at load into the bf16 layout, which rounds s*q+b to bf16 per weight - a stated deviation for those cases only.
+ * proj_out.{weight,scales,biases} are ignored (tied). */
+mis_status mis_whisper_set_tensor_quantized(mis_whisper*, const char* name, const uint32_t* wq, const void* scales, const void* biases,
+                                            mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits);
+/* after finalize: bits a decoder matrix is streamed in (0 = dense bf16).  role 0 self q|k|v, 1 self out, 2 cross q, 3 cross out,
+ * 4 fc1, 5 fc2 of decoder layer `layer`; role 6 the tied vocab projection (layer ignored) */
+int        mis_whisper_native_quant_bits(const mis_whisper*, int layer, int role);
 mis_status mis_whisper_init_synthetic(mis_whisper*, uint64_t seed);
+/* benches: every Linear and the token embedding as a synthetic MLX-quantised matrix (bits 8 or 4, group 64, sb_dtype MIS_BF16 or
+ * MIS_F16) through the path of mis_whisper_set_tensor_quantized - no checkpoints offline */
+mis_status mis_whisper_init_synthetic_quantized(mis_whisper*, uint64_t seed, int bits, mis_dtype sb_dtype);
 mis_status mis_whisper_finalize(mis_whisper*);
 void       mis_whisper_destroy(mis_whisper*);
 /* WhisperEncoder (+ the cross-attention K/V of every decoder layer): features f32 [batch, 3000, n_mels];

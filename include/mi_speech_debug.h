@@ -30,6 +30,9 @@ mis_status mis_debug_occupy_wait(void);
 int32_t mis_debug_device_cus(int device);            /* compute units of a device (0 when it does not exist) */
 /* diagnostics / tests: launches of the one-launch sampler that reported a timed-out row barrier in this process so far */
 int32_t mis_debug_sampler_failures(void);
+/* tests: device bytes a finalized Whisper handle holds for its weights (the bf16 arena plus the code / scale tables of the natively
+ * streamed quantised decoder matrices) */
+int64_t mis_debug_whisper_weight_bytes(const mis_whisper* c);
 
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product

@@ -198,6 +198,9 @@ SYMBOLS = {
     "mis_whisper_create": (C.c_int, [C.POINTER(WhisperConfigC), C.c_int, C.POINTER(_P)]),
     "mis_whisper_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_whisper_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_whisper_set_tensor_quantized": (C.c_int, [_P, C.c_char_p, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mis_whisper_native_quant_bits": (C.c_int, [_P, C.c_int, C.c_int]),
+    "mis_whisper_init_synthetic_quantized": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_int]),
     "mis_whisper_finalize": (C.c_int, [_P]),
     "mis_whisper_destroy": (None, [_P]),
     "mis_whisper_encode": (C.c_int, [_P, _P, C.c_int, _P]),
@@ -288,6 +291,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_sampler_failures": (C.c_int32, []),
     "mis_debug_choose_split": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
 }
 
 _lib = None

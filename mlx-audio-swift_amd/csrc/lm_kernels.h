@@ -43,8 +43,9 @@ void launch_gemm_skinny_norm(int epi, int R, const bf16_t* Wp, const float* slab
 struct GemmArr { int R = 2, ksb = 4, U = 4, S = 1; };
 
 // the same on MLX affine-quantised weights (lm_qgemm.hip): Qp packed codes, SB packed bf16 scale/bias pairs, G = K/64 scale groups
+// sb_dtype (mis_dtype): the 16-bit format of the packed scales / biases, MIS_BF16 or MIS_F16 (f16: R = 2 launches only)
 void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, const bf16_t* SB, const bf16_t* X, void* out, int NT, int G,
-                          int S, int N_out, int Mpad, hipStream_t s, const bf16_t* bias = nullptr);
+                          int S, int N_out, int Mpad, hipStream_t s, const bf16_t* bias = nullptr, int sb_dtype = 2 /* MIS_BF16 */);
 void launch_pack_qweight(int bits, const uint32_t* wq, const bf16_t* scales, const bf16_t* biases, void* qdst, bf16_t* sbdst, int N, int K,
                          int tile_stride, int tile_offset, hipStream_t s);
 

@@ -15,6 +15,8 @@
 //   codes   [NT][KT][64 lanes][8 codes]: lane l = q*16 + i holds W[16nt + i][32kt + 8q .. +8) - the bf16 pack of lm_kernels.hip with
 //           codes instead of values: 8 bytes (uint2) per lane at 8 bit, 4 bytes at 4 bit (code e in bits [bits*e, bits*(e+1)))
 //   scales  [NT][G][2][16] bf16: scale then bias of rows 16nt .. 16nt+15 for scale group g (a lane reads its 4 C/D rows as 8 bytes)
+//           - or f16, as stored (mlx-whisper conversions keep float16 scales): k_pack_qweight moves the 16-bit payloads unchanged and
+//           the trailing template parameter SBT of the GEMMs (0 bf16, 1 f16) says how to widen them; f16 -> f32 is exact as well.
 // Work decomposition, epilogues and the in-block split-K combine are those of k_gemm_skinny; K ranges are cut at scale groups.
 #include "common.h"
 #include "lm_kernels.h"
@@ -47,6 +49,23 @@ __device__ __forceinline__ void unpack_bf16x4(uint2 v, float (&o)[4]) {
     o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
     o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
 }
+// one 16-bit scale / bias (low half of w) -> float32, exactly: SBT 0 = bf16, 1 = f16 (v_cvt_f32_f16)
+template <int SBT>
+__device__ __forceinline__ float sb_to_f32(uint32_t w) {
+    if (SBT == 1) return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
+    return __uint_as_float(w << 16);
+}
+template <int SBT>
+__device__ __forceinline__ void unpack_sb4(uint2 v, float (&o)[4]) {
+    if (SBT == 1) {
+        o[0] = sb_to_f32<1>(v.x); o[1] = sb_to_f32<1>(v.x >> 16);
+        o[2] = sb_to_f32<1>(v.y); o[3] = sb_to_f32<1>(v.y >> 16);
+    } else {
+        unpack_bf16x4(v, o);
+    }
+}
+
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }   // = lm_kernels.hip's
 
 // epilogues: identical arithmetic to gemm_epilogue of lm_kernels.hip (kept in step with it)
 template <int MT, int R, int EPI>
@@ -72,7 +91,7 @@ __device__ __forceinline__ void qgemm_epilogue(const f32x4_t (&acc)[R][MT], void
                     make_float4(acc[r][mt][0] + bv[0], acc[r][mt][1] + bv[1], acc[r][mt][2] + bv[2], acc[r][mt][3] + bv[3]);
             }
         }
-    } else if (EPI == EPI_BF16) {
+    } else if (EPI == EPI_BF16 || EPI == EPI_GELU_PACKED) {    // GELU_PACKED: T(gelu(T(xW + b))) in the packed layout fc2 reads
         bf16_t* o = reinterpret_cast<bf16_t*>(out);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -88,8 +107,12 @@ __device__ __forceinline__ void qgemm_epilogue(const f32x4_t (&acc)[R][MT], void
                 if (mt_only >= 0 && mt != mt_only) continue;
                 uint16_t res[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) res[e] = f32_to_bf16(acc[r][mt][e] + bv[e]);
-                size_t off = ((size_t)mt * 16 + ml) * N_out + tile * 16 + nl;
+                for (int e = 0; e < 4; ++e) {
+                    float v = acc[r][mt][e] + bv[e];
+                    if (EPI == EPI_GELU_PACKED) v = gelu_erf(bf16_round_f32(v));
+                    res[e] = f32_to_bf16(v);
+                }
+                size_t off = EPI == EPI_GELU_PACKED ? xpk_index(mt * 16 + ml, tile * 16 + nl, MT) : ((size_t)mt * 16 + ml) * N_out + tile * 16 + nl;
                 uint2 v;
                 v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
                 v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
@@ -130,7 +153,7 @@ __device__ __forceinline__ void qgemm_epilogue(const f32x4_t (&acc)[R][MT], void
 // x-fragment bytes + weight bytes alike (every wave re-reads its x fragments out of L2; R = 2 -> 4 took the bf16 gate+up from 19.4 to
 // 17.6 us) - and at 8 bit the x fragments are TWICE the code bytes at R = 2.  Four tiles per wave halve them; one scale group per
 // buffer keeps the wave under 256 registers.
-template <int MT, int R, int EPI, int KSB, int BITS, int QGEMM_U>
+template <int MT, int R, int EPI, int KSB, int BITS, int QGEMM_U, int SBT = 0>
 __global__ void __launch_bounds__(KSB == 8 ? 512 : 256, 2) k_gemm_skinny_q(const void* __restrict__ Qp, const bf16_t* __restrict__ SB, const bf16_t* __restrict__ X,
                                                        void* __restrict__ out, int NT, int G, int S, int n_items, int N_out, int Mpad,
                                                        const bf16_t* __restrict__ bias) {
@@ -243,8 +266,8 @@ __global__ void __launch_bounds__(KSB == 8 ? 512 : 256, 2) k_gemm_skinny_q(const
         }                                                                                           \
         _Pragma("unroll") for (int r = 0; r < R; ++r) {                                             \
             float sc[4], bi[4];                                                                     \
-            unpack_bf16x4(SBUF[U][r][0], sc);                                                       \
-            unpack_bf16x4(SBUF[U][r][1], bi);                                                       \
+            unpack_sb4<SBT>(SBUF[U][r][0], sc);                                                     \
+            unpack_sb4<SBT>(SBUF[U][r][1], bi);                                                     \
             _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                       \
                 _Pragma("unroll") for (int e = 0; e < 4; ++e)                                       \
                     acc[r][mt][e] += sc[e] * ag[r][mt][e] + bi[e] * sx[mt][e];                      \
@@ -330,7 +353,7 @@ __global__ void __launch_bounds__(KSB == 8 ? 512 : 256, 2) k_gemm_skinny_q(const
 // accumulators pass through LDS once at the end (a 16 x 16 float tile per (r, mt), written [m][n], read back as the streaming
 // kernel's lanes hold them), so the epilogues and the in-block split-K combine are shared; eight waves per item are possible here.
 // Per-element arithmetic is that of k_gemm_skinny_q; the in-block combine adds KSB partials in wave order.
-template <int MT, int R, int EPI, int KSB, int BITS, int U>
+template <int MT, int R, int EPI, int KSB, int BITS, int U, int SBT = 0>
 __global__ void __launch_bounds__(256, 2) k_gemm_skinny_q1(const void* Qp, const bf16_t* SB, const bf16_t* X,     // not __restrict__: see the
                                                                             void* __restrict__ out, int NT, int G, int S, int n_items, int N_out, int Mpad,   // fence below
                                                                             const bf16_t* __restrict__ bias) {
@@ -434,8 +457,8 @@ __global__ void __launch_bounds__(256, 2) k_gemm_skinny_q1(const void* Qp, const
             }
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const float sc = live ? __uint_as_float(sb[u][r][0] << 16) : 0.0f;
-                const float bi = live ? __uint_as_float(sb[u][r][1] << 16) : 0.0f;
+                const float sc = live ? sb_to_f32<SBT>(sb[u][r][0]) : 0.0f;
+                const float bi = live ? sb_to_f32<SBT>(sb[u][r][1]) : 0.0f;
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -474,62 +497,111 @@ __global__ void __launch_bounds__(256, 2) k_gemm_skinny_q1(const void* Qp, const
     }
 }
 
-template <int MT, int BITS, int U>
+template <int MT, int BITS, int U, int SBT>
 static void launch_qgemm1_mt(int epi, int R, int ksb, const void* Qp, const bf16_t* SB, const bf16_t* X, void* out, int NT, int G, int S,
                              int N_out, int Mpad, const bf16_t* bias, hipStream_t s) {
     int n_items = ((NT + R - 1) / R) * S;
     dim3 grid(n_items), block(256);
 #define QGEMM1_CASE(E, RR, KS)                                                                                      \
     if (epi == E && R == RR && ksb == KS) {                                                                         \
-        hipLaunchKernelGGL((k_gemm_skinny_q1<MT, RR, E, KS, BITS, U>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
+        hipLaunchKernelGGL((k_gemm_skinny_q1<MT, RR, E, KS, BITS, U, SBT>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
                            N_out, Mpad, bias);                                                                      \
         return;                                                                                                     \
     }
-    QGEMM1_CASE(EPI_PARTIAL, 1, 4)
-    QGEMM1_CASE(EPI_PARTIAL, 2, 4)
-    QGEMM1_CASE(EPI_BF16, 2, 4)
-    QGEMM1_CASE(EPI_SILU_MUL, 2, 4)
+    if constexpr (SBT == 0) {
+        QGEMM1_CASE(EPI_PARTIAL, 1, 4)
+        QGEMM1_CASE(EPI_BF16, 2, 4)
+        QGEMM1_CASE(EPI_SILU_MUL, 2, 4)
+    }
+    QGEMM1_CASE(EPI_PARTIAL, 2, 4)                 // Whisper's decoder roles (both scale dtypes): split-K slabs and fc1's GELU
+    QGEMM1_CASE(EPI_GELU_PACKED, 2, 4)
 #undef QGEMM1_CASE
     throw MisError(MIS_ERR_GENERATION_FAILED, "unsupported quantised GEMM variant");
 }
 
-template <int MT, int BITS, int U>
+template <int MT, int BITS, int U, int SBT>
 static void launch_qgemm_mt(int epi, int R, int ksb, const void* Qp, const bf16_t* SB, const bf16_t* X, void* out, int NT, int G, int S,
                             int N_out, int Mpad, const bf16_t* bias, hipStream_t s) {
     int n_items = ((NT + R - 1) / R) * S;
     dim3 grid(ksb == 1 ? (n_items + 3) / 4 : n_items), block(ksb == 8 ? 512 : 256);
 #define QGEMM_CASE(E, RR, KS)                                                                                       \
     if (epi == E && R == RR && ksb == KS) {                                                                         \
-        hipLaunchKernelGGL((k_gemm_skinny_q<MT, RR, E, KS, BITS, U>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
+        hipLaunchKernelGGL((k_gemm_skinny_q<MT, RR, E, KS, BITS, U, SBT>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
                            N_out, Mpad, bias);                                                                      \
         return;                                                                                                     \
     }
-    QGEMM_CASE(EPI_PARTIAL, 1, 4)
-    QGEMM_CASE(EPI_PARTIAL, 2, 1)
-    QGEMM_CASE(EPI_PARTIAL, 2, 4)
+    QGEMM_CASE(EPI_PARTIAL, 2, 4)                  // Whisper's decoder roles (both scale dtypes): split-K slabs, fc1's GELU, the vocab
+    QGEMM_CASE(EPI_GELU_PACKED, 2, 4)
     QGEMM_CASE(EPI_BF16, 2, 1)
-    QGEMM_CASE(EPI_BF16, 2, 4)
-    QGEMM_CASE(EPI_SILU_MUL, 2, 1)
-    QGEMM_CASE(EPI_SILU_MUL, 2, 4)
-    if constexpr (MT <= 2 && U == 1) {             // four n-tiles per wave: one scale group per buffer, <= 32 rows
-        QGEMM_CASE(EPI_SILU_MUL, 4, 4)
-        QGEMM_CASE(EPI_SILU_MUL, 4, 8)
-        QGEMM_CASE(EPI_BF16, 4, 4)
-        QGEMM_CASE(EPI_BF16, 4, 8)
-        QGEMM_CASE(EPI_PARTIAL, 4, 4)
-        QGEMM_CASE(EPI_PARTIAL, 4, 8)
-    }
-    if constexpr (MT <= 2 && U == 2) {
-        QGEMM_CASE(EPI_SILU_MUL, 2, 8)
-        QGEMM_CASE(EPI_BF16, 2, 8)
+    if constexpr (SBT == 0) {                      // the LM's roles: bf16 scales only
+        QGEMM_CASE(EPI_PARTIAL, 1, 4)
+        QGEMM_CASE(EPI_PARTIAL, 2, 1)
+        QGEMM_CASE(EPI_BF16, 2, 4)
+        QGEMM_CASE(EPI_SILU_MUL, 2, 1)
+        QGEMM_CASE(EPI_SILU_MUL, 2, 4)
+        if constexpr (MT <= 2 && U == 1) {         // four n-tiles per wave: one scale group per buffer, <= 32 rows
+            QGEMM_CASE(EPI_SILU_MUL, 4, 4)
+            QGEMM_CASE(EPI_SILU_MUL, 4, 8)
+            QGEMM_CASE(EPI_BF16, 4, 4)
+            QGEMM_CASE(EPI_BF16, 4, 8)
+            QGEMM_CASE(EPI_PARTIAL, 4, 4)
+            QGEMM_CASE(EPI_PARTIAL, 4, 8)
+        }
+        if constexpr (MT <= 2 && U == 2) {
+            QGEMM_CASE(EPI_SILU_MUL, 2, 8)
+            QGEMM_CASE(EPI_BF16, 2, 8)
+        }
     }
 #undef QGEMM_CASE
     throw MisError(MIS_ERR_GENERATION_FAILED, "unsupported quantised GEMM variant");
 }
 
-// Qp / SB: packed codes and scale/bias pairs (see the file header); G = K / 64 scale groups; otherwise as launch_gemm_skinny
+// f16 scales: the same arrangement choice as the bf16 launcher below, for the R = 2 launches of Whisper's decoder step
+static void launch_gemm_skinny_q_f16(int bits, int epi, int R, int ksb, const void* Qp, const bf16_t* SB, const bf16_t* X, void* out, int NT,
+                                     int G, int S, int N_out, int Mpad, hipStream_t s, const bf16_t* bias) {
+    MIS_REQUIRE(epi == EPI_PARTIAL || S == 1, MIS_ERR_GENERATION_FAILED, "split-K needs the partial epilogue");
+    MIS_REQUIRE(bits == 8 || bits == 4, MIS_ERR_GENERATION_FAILED, "quantised GEMM: 8 or 4 bits");
+    MIS_REQUIRE(S >= 1 && S <= G, MIS_ERR_GENERATION_FAILED, "quantised GEMM: %d K slices for %d scale groups", S, G);
+    MIS_REQUIRE(R == 2, MIS_ERR_GENERATION_FAILED, "quantised GEMM with f16 scales: two n-tiles per wave");
+    static const int v2 = getenv("MIS_QGEMM_V2") ? atoi(getenv("MIS_QGEMM_V2")) : 1;
+    if (v2 && Mpad / 16 <= 2) {
+        const int per_item = (G + S - 1) / S;
+        const int n = (per_item + ksb - 1) / ksb;
+        const int u2 = ksb == 1 ? 0 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 6 ? 6 : 0;
+#define QGEMM1_GO(M, UU)                                                                                             \
+        { if (bits == 8) launch_qgemm1_mt<M, 8, UU, 1>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);     \
+          else launch_qgemm1_mt<M, 4, UU, 1>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);               \
+          return; }
+#define QGEMM1_MT(M)                                                                                                 \
+        if (u2 == 2) QGEMM1_GO(M, 2)                                                                                 \
+        if (u2 == 4) QGEMM1_GO(M, 4)                                                                                 \
+        if (u2 == 6) QGEMM1_GO(M, 6)
+        if (u2) { if (Mpad / 16 == 1) { QGEMM1_MT(1) } else { QGEMM1_MT(2) } }
+#undef QGEMM1_MT
+#undef QGEMM1_GO
+    }
+#define QGEMM_MT(M, UU)                                                                                              \
+    if (bits == 8) launch_qgemm_mt<M, 8, UU, 1>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);        \
+    else launch_qgemm_mt<M, 4, UU, 1>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);
+    switch (Mpad / 16) {
+        case 1: { QGEMM_MT(1, 2) } break;
+        case 2: { QGEMM_MT(2, 2) } break;
+        case 3: { QGEMM_MT(3, 1) } break;
+        case 4: { QGEMM_MT(4, 1) } break;
+        default: throw MisError(MIS_ERR_INVALID_INPUT, "batch per GPU must be <= 64");
+    }
+#undef QGEMM_MT
+}
+
+// Qp / SB: packed codes and scale/bias pairs (see the file header); G = K / 64 scale groups; otherwise as launch_gemm_skinny.
+// sb_dtype (mis_dtype): MIS_BF16 or MIS_F16, the 16-bit format SB holds (f16: the R = 2 roles Whisper launches only).
 void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, const bf16_t* SB, const bf16_t* X, void* out, int NT, int G,
-                          int S, int N_out, int Mpad, hipStream_t s, const bf16_t* bias) {
+                          int S, int N_out, int Mpad, hipStream_t s, const bf16_t* bias, int sb_dtype) {
+    MIS_REQUIRE(sb_dtype == MIS_BF16 || sb_dtype == MIS_F16, MIS_ERR_GENERATION_FAILED, "quantised GEMM: bf16 or f16 scales");
+    if (sb_dtype == MIS_F16) {
+        launch_gemm_skinny_q_f16(bits, epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, s, bias);
+        return;
+    }
     MIS_REQUIRE(epi == EPI_PARTIAL || S == 1, MIS_ERR_GENERATION_FAILED, "split-K needs the partial epilogue");
     MIS_REQUIRE(bits == 8 || bits == 4, MIS_ERR_GENERATION_FAILED, "quantised GEMM: 8 or 4 bits");
     MIS_REQUIRE(S >= 1 && S <= G, MIS_ERR_GENERATION_FAILED, "quantised GEMM: %d K slices for %d scale groups", S, G);   // a wave may get none
@@ -541,8 +613,8 @@ void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, con
     if (R == 4 || ksb == 8) {                      // the wide roles' arrangement (streaming kernel only): R = 4 -> one group per buffer
         MIS_REQUIRE(Mpad / 16 <= 2, MIS_ERR_GENERATION_FAILED, "quantised GEMM: four n-tiles per wave / eight waves per item are built for <= 32 rows");
 #define QGEMM_R4(M, UU)                                                                                              \
-        { if (bits == 8) launch_qgemm_mt<M, 8, UU>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);         \
-          else launch_qgemm_mt<M, 4, UU>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);                   \
+        { if (bits == 8) launch_qgemm_mt<M, 8, UU, 0>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);         \
+          else launch_qgemm_mt<M, 4, UU, 0>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);                   \
           return; }
         if (R == 4) { if (Mpad / 16 == 1) QGEMM_R4(1, 1) else QGEMM_R4(2, 1) }
         else { if (Mpad / 16 == 1) QGEMM_R4(1, 2) else QGEMM_R4(2, 2) }
@@ -555,8 +627,8 @@ void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, con
         const int k2 = ksb, n = (per_item + ksb - 1) / ksb;
         const int u2 = ksb == 1 ? 0 : n <= 2 ? 2 : n <= 4 ? 4 : n <= 6 ? 6 : 0;       // one wave per item: the streaming kernel (long K shares)
 #define QGEMM1_GO(M, UU)                                                                                             \
-        { if (bits == 8) launch_qgemm1_mt<M, 8, UU>(epi, R, k2, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);         \
-          else launch_qgemm1_mt<M, 4, UU>(epi, R, k2, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);                   \
+        { if (bits == 8) launch_qgemm1_mt<M, 8, UU, 0>(epi, R, k2, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);         \
+          else launch_qgemm1_mt<M, 4, UU, 0>(epi, R, k2, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);                   \
           return; }
 #define QGEMM1_MT(M)                                                                                                 \
         if (u2 == 2) QGEMM1_GO(M, 2)                                                                                 \
@@ -567,8 +639,8 @@ void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, con
 #undef QGEMM1_GO
     }
 #define QGEMM_MT(M, UU)                                                                                              \
-    if (bits == 8) launch_qgemm_mt<M, 8, UU>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);           \
-    else launch_qgemm_mt<M, 4, UU>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);
+    if (bits == 8) launch_qgemm_mt<M, 8, UU, 0>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);           \
+    else launch_qgemm_mt<M, 4, UU, 0>(epi, R, ksb, Qp, SB, X, out, NT, G, S, N_out, Mpad, bias, s);
     switch (Mpad / 16) {
         case 1: { QGEMM_MT(1, 2) } break;
         case 2: { QGEMM_MT(2, 2) } break;
@@ -579,7 +651,8 @@ void launch_gemm_skinny_q(int bits, int epi, int R, int ksb, const void* Qp, con
 #undef QGEMM_MT
 }
 
-// ---- load-time packing: MLX layout (wq uint32 [N][K*bits/32], scales / biases bf16 [N][K/64]) -> the layouts above.
+// ---- load-time packing: MLX layout (wq uint32 [N][K*bits/32], scales / biases bf16 or f16 [N][K/64]) -> the layouts above.
+// Scales and biases are moved as 16-bit payloads, so f16 bits arrive in the table unchanged.
 // Tile placement as launch_pack_weight: source n-tile t lands at tile t*tile_stride + tile_offset of a matrix with KT = K/32.
 template <int BITS>
 __global__ void k_pack_qweight(const uint32_t* __restrict__ wq, const bf16_t* __restrict__ scales, const bf16_t* __restrict__ biases,

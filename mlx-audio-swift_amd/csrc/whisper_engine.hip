@@ -12,17 +12,33 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
+#include <array>
 #include <memory>
 
 struct WTensor {
     DevBuf<bf16_t> buf;
     std::vector<int64_t> shape;
 };
+// a matrix held in MLX's affine-quantised form until finalize: codes | scales | biases in one device buffer
+struct QRaw {
+    DevBuf<uint8_t> buf;
+    int64_t N = 0, K = 0;
+    int group = 0, bits = 0;
+    mis_dtype sbt = MIS_BF16;
+    size_t wb = 0, sb = 0;                   // byte offsets of scales and biases
+    const uint32_t* wq() const { return reinterpret_cast<const uint32_t*>(buf.p); }
+    const void* sc() const { return buf.p + wb; }
+    const void* bi() const { return buf.p + sb; }
+};
+// a decoder matrix streamed as codes (lm_qgemm.hip layouts); bits == 0: the bf16 packed copy is streamed instead
+struct QW { int bits = 0; int sbt = MIS_BF16; const void* q = nullptr; const bf16_t* sb = nullptr; };
+enum { WQ_SQKV = 0, WQ_SO = 1, WQ_CQ = 2, WQ_CO = 3, WQ_FC1 = 4, WQ_FC2 = 5, WQ_ROLES = 6 };   // mis_whisper_native_quant_bits roles
 
 struct EncLayer { bf16_t *wqkv, *bqkv, *wo, *bo, *fc1, *b1, *fc2, *b2, *ln1w, *ln1b, *ln2w, *ln2b; };
 struct DecLayer {
     bf16_t *sqkv, *sbqkv, *so, *sbo, *cq, *cbq, *ckv, *cbkv, *co, *cbo, *fc1, *b1, *fc2, *b2;
     bf16_t *ln1w, *ln1b, *ln2w, *ln2b, *ln3w, *ln3b;
+    QW qw[WQ_ROLES];
 };
 
 struct mis_whisper {
@@ -31,8 +47,11 @@ struct mis_whisper {
     mis_whisper_config cfg{};
     int d = 0, He = 0, Hd = 0, D = 0, V = 0, Vpad = 0, nmel = 0, K1 = 0;
     std::map<std::string, std::unique_ptr<WTensor>> raw;
+    std::map<std::string, std::unique_ptr<QRaw>> qraw;    // natively streamable quantised matrices (mis_whisper_set_tensor_quantized)
     bool finalized = false;
-    DevBuf<bf16_t> arena;                    // all assembled weights
+    DevBuf<bf16_t> arena;                    // all assembled weights (bf16)
+    DevBuf<uint8_t> qarena;                  // codes and scale / bias tables of the natively streamed decoder matrices
+    QW qvocab;                               // the tied vocab projection as codes (bits == 0: emb_packed)
     bf16_t *conv1w = nullptr, *conv1b = nullptr, *conv2w = nullptr, *conv2b = nullptr, *enc_pos = nullptr, *enc_lnw = nullptr,
            *enc_lnb = nullptr, *emb = nullptr, *emb_packed = nullptr, *dec_pos = nullptr, *dec_lnw = nullptr, *dec_lnb = nullptr;
     std::vector<EncLayer> enc;
@@ -126,20 +145,27 @@ static bool whisper_remap_mlx_key(const std::string& raw, std::string* out) {
     return false;
 }
 
+// checkpoint key -> the HF name the engine indexes by; "" = a key the engine ignores
+static std::string whisper_canonical_name(const std::string& raw_name) {
+    std::string name = raw_name;
+    if (name == "proj_out.weight" || name == "model.proj_out.weight") return "";              // tied, WhisperModel.swift:343-346
+    if (name == "alignment_heads") return "";                                                  // mlx-whisper extra (:371)
+    {   // mlx-whisper key layout -> HF names (WhisperModel.remapMlxWhisperKey / remapBlockSuffix, :393-478)
+        std::string mapped;
+        if (whisper_remap_mlx_key(name, &mapped)) name = mapped;
+    }
+    if (name.rfind("model.", 0) != 0 && (name.rfind("encoder.", 0) == 0 || name.rfind("decoder.", 0) == 0)) name = "model." + name;
+    return name;
+}
+
 extern "C" mis_status mis_whisper_set_tensor(mis_whisper* c, const char* name_, const void* data, mis_dtype dtype,
                                              const int64_t* shape, int ndim) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && name_ && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    std::string name = name_;
-    if (name == "proj_out.weight" || name == "model.proj_out.weight") return MIS_OK;          // tied, WhisperModel.swift:343-346
-    if (name == "alignment_heads") return MIS_OK;                                              // mlx-whisper extra (:371)
-    {   // mlx-whisper key layout -> HF names (WhisperModel.remapMlxWhisperKey / remapBlockSuffix, :393-478)
-        std::string mapped;
-        if (whisper_remap_mlx_key(name, &mapped)) name = mapped;
-    }
-    if (name.rfind("model.", 0) != 0 && (name.rfind("encoder.", 0) == 0 || name.rfind("decoder.", 0) == 0)) name = "model." + name;
+    const std::string name = whisper_canonical_name(name_);
+    if (name.empty()) return MIS_OK;
     HIP_CHECK(hipSetDevice(c->device));
     size_t n = 1;
     auto t = std::make_unique<WTensor>();
@@ -166,6 +192,71 @@ extern "C" mis_status mis_whisper_set_tensor(mis_whisper* c, const char* name_, 
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
     c->raw[name] = std::move(t);
+    c->qraw.erase(name);                                      // a dense tensor replaces an earlier quantised one of the same name
+    MIS_API_END
+}
+
+// the decoder matrices every step re-reads (and the tied vocab projection, through the embedding): the ones streamed as codes
+static bool whisper_streamed_matrix(const std::string& name) {
+    if (name == "model.decoder.embed_tokens.weight") return true;
+    const std::string pre = "model.decoder.layers.";
+    if (name.rfind(pre, 0) != 0) return false;
+    const size_t dot = name.find('.', pre.size());
+    if (dot == std::string::npos) return false;
+    const std::string rest = name.substr(dot + 1);
+    for (const char* r : {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.out_proj.weight",
+                          "encoder_attn.q_proj.weight", "encoder_attn.out_proj.weight", "fc1.weight", "fc2.weight"})
+        if (rest == r) return true;
+    return false;
+}
+
+// A Linear / Embedding in MLX's affine-quantised form (WhisperModel.fromDirectory quantises every Linear and decoder.embed_tokens,
+// WhisperModel.swift:499-510).  Decoder matrices with 8 / 4 bits, group 64 and bf16 / f16 scales are kept as codes for finalize to pack;
+// everything else is dequantised here into the bf16 form set_tensor produces.
+static void whisper_set_quantized(mis_whisper* c, const std::string& name_in, const uint32_t* wq, const void* scales, const void* biases,
+                                  mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits) {
+    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d (2, 4 or 8 bits)", bits);
+    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT,
+                "bad quantised shape for %s", name_in.c_str());
+    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
+    const std::string name = whisper_canonical_name(name_in);
+    if (name.empty()) return;                                                      // proj_out.{weight,scales,biases}: tied
+    MIS_REQUIRE(name.size() > 7 && name.compare(name.size() - 7, 7, ".weight") == 0, MIS_ERR_INVALID_INPUT,
+                "quantised tensor %s: expected the .weight key of a Linear / Embedding", name_in.c_str());
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    auto q = std::make_unique<QRaw>();
+    const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
+    q->N = N; q->K = K; q->group = group_size; q->bits = bits; q->sbt = sb_dtype;
+    q->wb = round_up(words * 4, 256); q->sb = q->wb + round_up(ng * esz, 256);
+    q->buf.alloc(q->sb + ng * esz);
+    HIP_CHECK(hipMemcpyAsync(q->buf.p, wq, words * 4, hipMemcpyDefault, s));
+    HIP_CHECK(hipMemcpyAsync(q->buf.p + q->wb, scales, ng * esz, hipMemcpyDefault, s));
+    HIP_CHECK(hipMemcpyAsync(q->buf.p + q->sb, biases, ng * esz, hipMemcpyDefault, s));
+    static const bool native = !(getenv("MIS_QUANT_NATIVE") && atoi(getenv("MIS_QUANT_NATIVE")) == 0);
+    if (native && (bits == 8 || bits == 4) && group_size == 64 && (sb_dtype == MIS_BF16 || sb_dtype == MIS_F16) && K % 64 == 0 &&
+        whisper_streamed_matrix(name)) {
+        c->qraw[name] = std::move(q);
+        c->raw.erase(name);
+    } else {
+        auto t = std::make_unique<WTensor>();
+        t->shape = {N, K};
+        t->buf.alloc((size_t)N * K);
+        launch_dequant_affine(q->wq(), q->sc(), q->bi(), (int)sb_dtype, t->buf.p, (int)N, (int)K, group_size, bits, s);
+        c->raw[name] = std::move(t);
+        c->qraw.erase(name);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
+extern "C" mis_status mis_whisper_set_tensor_quantized(mis_whisper* c, const char* name, const uint32_t* wq, const void* scales,
+                                                       const void* biases, mis_dtype sb_dtype, int64_t N, int64_t K, int group_size,
+                                                       int bits) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && name && wq && scales && biases, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
+    whisper_set_quantized(c, name, wq, scales, biases, sb_dtype, N, K, group_size, bits);
     MIS_API_END
 }
 
@@ -193,6 +284,51 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     hipStream_t s = c->stream;
     const int64_t d = c->d, fe = c->cfg.encoder_ffn_dim, fd = c->cfg.decoder_ffn_dim, V = c->V, nm = c->nmel;
     const int Le = c->cfg.encoder_layers, Ld = c->cfg.decoder_layers;
+    const std::string E = "model.encoder", Dd = "model.decoder";
+    // ---- which decoder matrices stream as codes.  A layer's q|k|v is one matrix: native only if all three projections share bits and
+    // scale dtype; otherwise (and for every matrix finalize does not stream) the quantised tensors are dequantised into the bf16 form.
+    auto qfind = [&](const std::string& name) -> QRaw* { auto it = c->qraw.find(name); return it == c->qraw.end() ? nullptr : it->second.get(); };
+    auto densify = [&](const std::string& name) {
+        QRaw* q = qfind(name);
+        if (!q || c->raw.count(name)) return;
+        auto t = std::make_unique<WTensor>();
+        t->shape = {q->N, q->K};
+        t->buf.alloc((size_t)q->N * q->K);
+        launch_dequant_affine(q->wq(), q->sc(), q->bi(), (int)q->sbt, t->buf.p, (int)q->N, (int)q->K, q->group, q->bits, s);
+        c->raw[name] = std::move(t);
+    };
+    static const char* const ROLE_NAMES[WQ_ROLES][3] = {
+        {".self_attn.q_proj.weight", ".self_attn.k_proj.weight", ".self_attn.v_proj.weight"}, {".self_attn.out_proj.weight", nullptr, nullptr},
+        {".encoder_attn.q_proj.weight", nullptr, nullptr}, {".encoder_attn.out_proj.weight", nullptr, nullptr}, {".fc1.weight", nullptr, nullptr},
+        {".fc2.weight", nullptr, nullptr}};
+    const int64_t role_N[WQ_ROLES] = {3 * d, d, d, d, fd, d}, role_K[WQ_ROLES] = {d, d, d, d, d, fd};
+    std::vector<std::array<int, WQ_ROLES>> rbits(Ld), rsbt(Ld);
+    size_t qbytes = 0, dense_saved = 0;
+    auto qsize = [](int64_t NT, int64_t K, int bits) { return round_up((size_t)NT * (K / 32) * 64 * bits, 256) + round_up((size_t)NT * (K / 64) * 64, 256); };
+    for (int li = 0; li < Ld; ++li) {
+        const std::string q = Dd + ".layers." + std::to_string(li);
+        for (int r = 0; r < WQ_ROLES; ++r) {
+            rbits[li][r] = 0; rsbt[li][r] = MIS_BF16;
+            const int parts = r == WQ_SQKV ? 3 : 1;
+            QRaw* first = qfind(q + ROLE_NAMES[r][0]);
+            bool ok = first != nullptr;
+            for (int j = 0; j < parts && ok; ++j) {
+                QRaw* x = qfind(q + ROLE_NAMES[r][j]);
+                ok = x && x->bits == first->bits && x->sbt == first->sbt && x->N == role_N[r] / parts && x->K == role_K[r];
+            }
+            if (ok) {
+                rbits[li][r] = first->bits; rsbt[li][r] = first->sbt;
+                qbytes += qsize(role_N[r] / 16, role_K[r], first->bits);
+                dense_saved += (size_t)role_N[r] * role_K[r];
+            } else {
+                for (int j = 0; j < parts; ++j) densify(q + ROLE_NAMES[r][j]);
+            }
+        }
+    }
+    QRaw* qemb = qfind(Dd + ".embed_tokens.weight");
+    const bool vocab_native = qemb && qemb->N == V && qemb->K == d;
+    if (vocab_native) { qbytes += qsize(c->Vpad / 16, d, qemb->bits); dense_saved += (size_t)c->Vpad * d; }
+    densify(Dd + ".embed_tokens.weight");                     // the gather table is always bf16 (QuantizedEmbedding: dequantised rows)
     // arena size
     size_t total = (size_t)d * c->K1 + d + (size_t)d * 3 * d + d + (size_t)1500 * d + 2 * d;
     total += (size_t)Le * ((size_t)3 * d * d + 3 * d + (size_t)d * d + d + (size_t)fe * d + fe + (size_t)d * fe + d + 4 * d);
@@ -200,6 +336,7 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     total += (size_t)Ld * ((size_t)3 * d * d + 3 * d + (size_t)d * d + d + (size_t)d * d + d + (size_t)2 * d * d + 2 * d +
                            (size_t)d * d + d + (size_t)fd * d + fd + (size_t)d * fd + d + 6 * d);
     total += 64 * (size_t)(Le * 12 + Ld * 20 + 16);
+    total -= dense_saved;                                     // natively streamed matrices keep no bf16 copy
     c->arena.alloc(total);
     HIP_CHECK(hipMemsetAsync(c->arena.p, 0, total * 2, s));
     size_t off = 0;
@@ -209,7 +346,23 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     auto pack = [&](const std::string& name, int64_t N, int64_t K, bf16_t* dst, int NT_total_offset_tiles) {
         launch_pack_weight(wneed(c, name, {N, K})->buf.p, dst, (int)N, (int)K, (int)(N / 16), 1, NT_total_offset_tiles, s);
     };
-    const std::string E = "model.encoder", Dd = "model.decoder";
+    // code arena: [codes][scale / bias pairs] per natively streamed matrix, zeroed (vocabulary padding rows: codes 0, scale 0, bias 0)
+    size_t qoff = 0;
+    if (qbytes) {
+        c->qarena.alloc(qbytes);
+        HIP_CHECK(hipMemsetAsync(c->qarena.p, 0, qbytes, s));
+    }
+    auto qtake = [&](QW& w, int bits, int sbt, int64_t NT, int64_t K) {
+        w.bits = bits; w.sbt = sbt;
+        w.q = c->qarena.p + qoff; qoff += round_up((size_t)NT * (K / 32) * 64 * bits, 256);
+        w.sb = reinterpret_cast<const bf16_t*>(c->qarena.p + qoff); qoff += round_up((size_t)NT * (K / 64) * 64, 256);
+        MIS_REQUIRE(qoff <= qbytes, MIS_ERR_GENERATION_FAILED, "code arena overflow");
+    };
+    auto qpack = [&](const QW& w, const std::string& name, int tile_offset) {
+        const QRaw* q = qfind(name);
+        launch_pack_qweight(q->bits, q->wq(), (const bf16_t*)q->sc(), (const bf16_t*)q->bi(), const_cast<void*>(w.q), const_cast<bf16_t*>(w.sb),
+                            (int)q->N, (int)q->K, 1, tile_offset, s);
+    };
     // ---- encoder
     c->conv1w = take((size_t)d * c->K1);
     hipLaunchKernelGGL(k_conv_w_reorder, dim3((unsigned)((d * c->K1 + 255) / 256)), dim3(256), 0, s,
@@ -259,35 +412,55 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     // ---- decoder
     c->emb = take((size_t)V * d);
     copy(c->emb, wneed(c, Dd + ".embed_tokens.weight", {V, d}));
-    c->emb_packed = take((size_t)c->Vpad * d);
-    launch_pack_weight(c->emb, c->emb_packed, (int)V, (int)d, c->Vpad / 16, 1, 0, s);        // projectToVocab: tied (:325-327)
+    c->qvocab = QW{};
+    if (vocab_native) {                                                                      // projectToVocab: tied (:325-327)
+        qtake(c->qvocab, qemb->bits, qemb->sbt, c->Vpad / 16, d);
+        qpack(c->qvocab, Dd + ".embed_tokens.weight", 0);
+    } else {
+        c->emb_packed = take((size_t)c->Vpad * d);
+        launch_pack_weight(c->emb, c->emb_packed, (int)V, (int)d, c->Vpad / 16, 1, 0, s);
+    }
     c->dec_pos = take((size_t)c->cfg.max_target_positions * d);
     copy(c->dec_pos, wneed(c, Dd + ".embed_positions.weight", {(int64_t)c->cfg.max_target_positions, d}));
     c->dec.resize(Ld);
     for (int li = 0; li < Ld; ++li) {
         std::string q = Dd + ".layers." + std::to_string(li);
         DecLayer& L = c->dec[li];
-        L.sqkv = take((size_t)3 * d * d);
-        pack(q + ".self_attn.q_proj.weight", d, d, L.sqkv, 0);
-        pack(q + ".self_attn.k_proj.weight", d, d, L.sqkv, (int)(d / 16));
-        pack(q + ".self_attn.v_proj.weight", d, d, L.sqkv, (int)(2 * d / 16));
+        L = DecLayer{};
+        for (int r = 0; r < WQ_ROLES; ++r)
+            if (rbits[li][r]) qtake(L.qw[r], rbits[li][r], rsbt[li][r], role_N[r] / 16, role_K[r]);
+        if (L.qw[WQ_SQKV].bits) {
+            qpack(L.qw[WQ_SQKV], q + ".self_attn.q_proj.weight", 0);
+            qpack(L.qw[WQ_SQKV], q + ".self_attn.k_proj.weight", (int)(d / 16));
+            qpack(L.qw[WQ_SQKV], q + ".self_attn.v_proj.weight", (int)(2 * d / 16));
+        } else {
+            L.sqkv = take((size_t)3 * d * d);
+            pack(q + ".self_attn.q_proj.weight", d, d, L.sqkv, 0);
+            pack(q + ".self_attn.k_proj.weight", d, d, L.sqkv, (int)(d / 16));
+            pack(q + ".self_attn.v_proj.weight", d, d, L.sqkv, (int)(2 * d / 16));
+        }
+        // one decoder matrix: codes, or the bf16 pack (the arena order of the all-dense model is unchanged)
+        auto mat = [&](int r, const std::string& name, int64_t N, int64_t K, bf16_t** dense) {
+            if (L.qw[r].bits) qpack(L.qw[r], name, 0);
+            else { *dense = take((size_t)N * K); pack(name, N, K, *dense, 0); }
+        };
         L.sbqkv = take(3 * d);
         copy(L.sbqkv, wneed(c, q + ".self_attn.q_proj.bias", {d}));
         copy(L.sbqkv + 2 * d, wneed(c, q + ".self_attn.v_proj.bias", {d}));
-        L.so = take((size_t)d * d); pack(q + ".self_attn.out_proj.weight", d, d, L.so, 0);
+        mat(WQ_SO, q + ".self_attn.out_proj.weight", d, d, &L.so);
         L.sbo = vec(q + ".self_attn.out_proj.bias", d);
-        L.cq = take((size_t)d * d); pack(q + ".encoder_attn.q_proj.weight", d, d, L.cq, 0);
+        mat(WQ_CQ, q + ".encoder_attn.q_proj.weight", d, d, &L.cq);
         L.cbq = vec(q + ".encoder_attn.q_proj.bias", d);
         L.ckv = take((size_t)2 * d * d);
         copy(L.ckv, wneed(c, q + ".encoder_attn.k_proj.weight", {d, d}));
         copy(L.ckv + (size_t)d * d, wneed(c, q + ".encoder_attn.v_proj.weight", {d, d}));
         L.cbkv = take(2 * d);
         copy(L.cbkv + d, wneed(c, q + ".encoder_attn.v_proj.bias", {d}));
-        L.co = take((size_t)d * d); pack(q + ".encoder_attn.out_proj.weight", d, d, L.co, 0);
+        mat(WQ_CO, q + ".encoder_attn.out_proj.weight", d, d, &L.co);
         L.cbo = vec(q + ".encoder_attn.out_proj.bias", d);
-        L.fc1 = take((size_t)fd * d); pack(q + ".fc1.weight", fd, d, L.fc1, 0);
+        mat(WQ_FC1, q + ".fc1.weight", fd, d, &L.fc1);
         L.b1 = vec(q + ".fc1.bias", fd);
-        L.fc2 = take((size_t)d * fd); pack(q + ".fc2.weight", d, fd, L.fc2, 0);
+        mat(WQ_FC2, q + ".fc2.weight", d, fd, &L.fc2);
         L.b2 = vec(q + ".fc2.bias", d);
         L.ln1w = vec(q + ".self_attn_layer_norm.weight", d); L.ln1b = vec(q + ".self_attn_layer_norm.bias", d);
         L.ln2w = vec(q + ".encoder_attn_layer_norm.weight", d); L.ln2b = vec(q + ".encoder_attn_layer_norm.bias", d);
@@ -297,18 +470,42 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
     c->raw.clear();
+    c->qraw.clear();
     c->finalized = true;
     MIS_API_END
 }
 
-// mis-synth-v1 weights, same key order / amplitudes as oracle/whisper.py make_synthetic_weights
-extern "C" mis_status mis_whisper_init_synthetic(mis_whisper* c, uint64_t seed) {
-    MIS_API_BEGIN
-    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+// benches: a synthetic MLX-quantised matrix (random codes, group scale ~ 2 amp / (2^bits - 1), bias ~ -amp: values within +-amp), group 64,
+// scales / biases in bf16 (sbt 2) or f16 (sbt 1)
+__global__ void k_whisper_synth_quant(uint32_t* __restrict__ wq, uint16_t* __restrict__ sc, uint16_t* __restrict__ bi, size_t words,
+                                      size_t groups, uint64_t key, float amp, int bits, int sbt) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < words) wq[i] = (uint32_t)(mis_splitmix64(key * 0x9E3779B97F4A7C15ull + i) >> 16);
+    if (i < groups) {
+        const float jitter = 1.0f + 0.25f * mis_synth_value(key ^ 0x5bd1e995ull, i, 1.0f);
+        const float sv = 2.0f * amp * jitter / (float)((1 << bits) - 1), bv = -amp * jitter;
+        sc[i] = sbt == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)sv) : f32_to_bf16(sv);
+        bi[i] = sbt == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)bv) : f32_to_bf16(bv);
+    }
+}
+
+// mis-synth-v1 weights, same key order / amplitudes as oracle/whisper.py make_synthetic_weights (bits == 0).  bits 8 / 4: every Linear
+// and the token embedding as a synthetic quantised matrix through the checkpoint path (mis_whisper_init_synthetic_quantized).
+static void whisper_synth(mis_whisper* c, uint64_t seed, int bits, mis_dtype sbt) {
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     uint64_t key = seed * 100000ull;
     const int64_t d = c->d, nm = c->nmel;
+    DevBuf<uint32_t> qw; DevBuf<uint16_t> qs, qb;
+    auto qmat = [&](const std::string& name, int64_t N, int64_t K, double amp) {
+        const size_t words = (size_t)N * K * bits / 32, groups = (size_t)N * (K / 64);
+        qw.alloc(words); qs.alloc(groups); qb.alloc(groups);
+        hipLaunchKernelGGL(k_whisper_synth_quant, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, qw.p, qs.p, qb.p, words, groups, ++key,
+                           (float)amp, bits, (int)sbt);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+        whisper_set_quantized(c, name, qw.p, qs.p, qb.p, sbt, N, K, 64, bits);
+    };
     auto put = [&](const std::string& name, std::vector<int64_t> shape, double amp, int plus_one) {
         auto t = std::make_unique<WTensor>();
         size_t n = 1;
@@ -319,7 +516,8 @@ extern "C" mis_status mis_whisper_init_synthetic(mis_whisper* c, uint64_t seed) 
         c->raw[name] = std::move(t);
     };
     auto lin = [&](const std::string& p, int64_t out_f, int64_t in_f, bool bias, double gain) {
-        put(p + ".weight", {out_f, in_f}, gain * sqrt(3.0 / (double)in_f), 0);
+        if (bits) qmat(p + ".weight", out_f, in_f, gain * sqrt(3.0 / (double)in_f));
+        else put(p + ".weight", {out_f, in_f}, gain * sqrt(3.0 / (double)in_f), 0);
         if (bias) put(p + ".bias", {out_f}, 0.05, 0);
     };
     auto lnp = [&](const std::string& p) { put(p + ".weight", {d}, 0.1, 2); put(p + ".bias", {d}, 0.05, 0); };
@@ -338,7 +536,8 @@ extern "C" mis_status mis_whisper_init_synthetic(mis_whisper* c, uint64_t seed) 
         lnp(q + ".final_layer_norm");
     }
     lnp(E + ".layer_norm");
-    put(Dd + ".embed_tokens.weight", {(int64_t)c->V, d}, 0.5, 0);
+    if (bits) qmat(Dd + ".embed_tokens.weight", (int64_t)c->V, d, 0.5);
+    else put(Dd + ".embed_tokens.weight", {(int64_t)c->V, d}, 0.5, 0);
     put(Dd + ".embed_positions.weight", {(int64_t)c->cfg.max_target_positions, d}, 0.3, 0);
     for (int li = 0; li < c->cfg.decoder_layers; ++li) {
         std::string q = Dd + ".layers." + std::to_string(li);
@@ -350,7 +549,36 @@ extern "C" mis_status mis_whisper_init_synthetic(mis_whisper* c, uint64_t seed) 
     lnp(Dd + ".layer_norm");
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
+}
+
+extern "C" mis_status mis_whisper_init_synthetic(mis_whisper* c, uint64_t seed) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+    whisper_synth(c, seed, 0, MIS_BF16);
     MIS_API_END
+}
+
+extern "C" mis_status mis_whisper_init_synthetic_quantized(mis_whisper* c, uint64_t seed, int bits, mis_dtype sb_dtype) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized && (bits == 4 || bits == 8) && (sb_dtype == MIS_BF16 || sb_dtype == MIS_F16), MIS_ERR_INVALID_INPUT,
+                "bad argument");
+    MIS_REQUIRE(c->d % 64 == 0 && c->cfg.encoder_ffn_dim % 64 == 0 && c->cfg.decoder_ffn_dim % 64 == 0, MIS_ERR_INVALID_INPUT,
+                "synthetic quantised weights need d_model and the ffn widths to be multiples of 64");
+    whisper_synth(c, seed, bits, sb_dtype);
+    MIS_API_END
+}
+
+// after finalize: bits a decoder matrix streams in (0 = dense bf16).  role 0 self q|k|v, 1 self out, 2 cross q, 3 cross out, 4 fc1, 5 fc2,
+// 6 the tied vocab projection (layer ignored)
+extern "C" int mis_whisper_native_quant_bits(const mis_whisper* c, int layer, int role) {
+    if (!c || !c->finalized) return 0;
+    if (role == WQ_ROLES) return c->qvocab.bits;
+    if (role < 0 || role >= WQ_ROLES || layer < 0 || layer >= (int)c->dec.size()) return 0;
+    return c->dec[layer].qw[role].bits;
+}
+
+extern "C" int64_t mis_debug_whisper_weight_bytes(const mis_whisper* c) {
+    return c ? (int64_t)(c->arena.bytes() + c->qarena.bytes()) : 0;
 }
 
 // ---------------------------------------------------------------------------- encoder
@@ -501,7 +729,16 @@ extern "C" mis_status mis_whisper_encode(mis_whisper* c, const float* features, 
 // kernel 5.0 -> 15.6 us against 9.6 saved; the variant is on file as c5_self_attention_qkv_fold_measured_variant.patch), and the ONE-SLAB
 // arrangement (profiles/r06/c9: every producer GEMM as eight-wave items over the whole K range writing one float32 slab, so that LayerNorm 1
 // could move into q|k|v's prologue as well - 7 launches per layer, parity green, transcribe 214 -> 224 ms: fc2 at 80 blocks 5.2 -> 8.5 us).
+// Quantised checkpoints: both folds read bf16 weights, so a layer whose cross query (fc1) streams as codes takes the separate launches
+// for it; bit 3 counts a fold lost that way as one that does not apply.
 #define WHISPER_FOLD_DEFAULT 20
+// one weight-streaming GEMM of the decoder step, R = 2: the packed codes where the matrix streams natively, else the bf16 pack.  The split
+// factors are the dense ones: gemm_choose_split caps S at KT / 8 = G / 4 k-slices, within the S <= G the quantised kernels need.
+static void whisper_gemm(const mis_whisper* c, const QW& w, const bf16_t* dense, int epi, int ksb, const bf16_t* X, void* out, int NT, int K,
+                         int S, int N_out, const bf16_t* bias) {
+    if (w.bits) launch_gemm_skinny_q(w.bits, epi, 2, ksb, w.q, w.sb, X, out, NT, K / 64, S, N_out, c->Mpad, c->stream, bias, w.sbt);
+    else launch_gemm_skinny(epi, 2, ksb, dense, X, out, NT, K / 32, S, N_out, c->Mpad, c->stream, bias);
+}
 static void enqueue_decoder_step(mis_whisper* c) {
     hipStream_t s = c->stream;
     const int d = c->d, fd = c->cfg.decoder_ffn_dim, Mpad = c->Mpad, H = c->Hd, D = c->D;
@@ -512,7 +749,9 @@ static void enqueue_decoder_step(mis_whisper* c) {
     probe.cross = 1; probe.cross_len = 1500; probe.D = D; probe.H = H; probe.Hkv = H; probe.qp_KT = d / 32; probe.qp_S = c->S_o;
     const bool f_cqa = (want & 16) && Mpad == 16 && attn_qp_ok(probe);
     const bool f_fc1 = (want & 4) && gemm_skinny_norm_ok(EPI_GELU_PACKED, 2, d / 32, 1, c->S_o, Mpad, c->batch);
-    MIS_REQUIRE(!(want & 8) || (f_cqa == !!(want & 16) && f_fc1 == !!(want & 4)), MIS_ERR_GENERATION_FAILED,
+    bool cq_dense = true, fc1_dense = true;
+    for (const DecLayer& L : c->dec) { cq_dense = cq_dense && !L.qw[WQ_CQ].bits; fc1_dense = fc1_dense && !L.qw[WQ_FC1].bits; }
+    MIS_REQUIRE(!(want & 8) || ((f_cqa && cq_dense) == !!(want & 16) && (f_fc1 && fc1_dense) == !!(want & 4)), MIS_ERR_GENERATION_FAILED,
                 "MIS_WHISPER_FOLD: the folded decoder step does not apply to this shape");
     bf16_t* hcur = c->h.p;
     bf16_t* hoth = c->h2.p;
@@ -521,7 +760,7 @@ static void enqueue_decoder_step(mis_whisper* c) {
     for (size_t li = 0; li < c->dec.size(); ++li) {
         const DecLayer& L = c->dec[li];
         // self attention (WhisperLayers.swift:202-214)
-        launch_gemm_skinny(EPI_PARTIAL, 2, 4, L.sqkv, c->x.p, c->qkv_part.p, 3 * d / 16, d / 32, c->S_qkv, 3 * d, Mpad, s, L.sbqkv);
+        whisper_gemm(c, L.qw[WQ_SQKV], L.sqkv, EPI_PARTIAL, 4, c->x.p, c->qkv_part.p, 3 * d / 16, d, c->S_qkv, 3 * d, L.sbqkv);
         AttnParams ap{};
         ap.qkv_part = c->qkv_part.p; ap.S = c->S_qkv; ap.Mpad = Mpad; ap.Nqkv = 3 * d;
         size_t ls = (size_t)c->batch * H * c->Smax * D;
@@ -529,17 +768,17 @@ static void enqueue_decoder_step(mis_whisper* c) {
         ap.pos = c->pos_cur.p; ap.active = c->active.p; ap.rope_cos = nullptr; ap.rope_sin = nullptr;
         ap.out = c->attn_out.p; ap.H = H; ap.Hkv = H; ap.D = D; ap.Smax = c->Smax; ap.scale = 1.0f / sqrtf((float)D);
         launch_attn_decode(ap, c->batch, s);
-        launch_gemm_skinny(EPI_PARTIAL, 2, 4, L.so, c->attn_out.p, c->part.p, d / 16, d / 32, c->S_o, d, Mpad, s, L.sbo);
+        whisper_gemm(c, L.qw[WQ_SO], L.so, EPI_PARTIAL, 4, c->attn_out.p, c->part.p, d / 16, d, c->S_o, d, L.sbo);
         // cross attention over the cached encoder K/V (:216-243)
         AttnParams cp{};
         cp.Mpad = Mpad;
-        if (f_cqa) {                                       // the launch below does h += self-attention output, LayerNorm 2 and q = W_q x + b itself
+        if (f_cqa && !L.qw[WQ_CQ].bits) {                  // the launch below does h += self-attention output, LayerNorm 2 and q = W_q x + b itself
             cp.qp_w = L.cq; cp.qp_bias = L.cbq; cp.qp_slabs = c->part.p; cp.qp_S = c->S_o; cp.qp_KT = d / 32; cp.qp_h_in = hcur; cp.qp_h_out = hoth;
             cp.qp_lnw = L.ln2w; cp.qp_lnb = L.ln2b; cp.qp_eps = LN_EPS;
             std::swap(hcur, hoth);
         } else {
             launch_reduce_residual_rmsnorm(c->part.p, c->S_o, Mpad, d, hcur, L.ln2w, c->x.p, LN_EPS, s, L.ln2b);
-            launch_gemm_skinny(EPI_PARTIAL, 2, 4, L.cq, c->x.p, c->qkv_part.p, d / 16, d / 32, c->S_cq, d, Mpad, s, L.cbq);
+            whisper_gemm(c, L.qw[WQ_CQ], L.cq, EPI_PARTIAL, 4, c->x.p, c->qkv_part.p, d / 16, d, c->S_cq, d, L.cbq);
             cp.qkv_part = c->qkv_part.p; cp.S = c->S_cq; cp.Nqkv = d;
         }
         size_t cs = (size_t)c->batch * H * c->Spad * D;
@@ -548,24 +787,24 @@ static void enqueue_decoder_step(mis_whisper* c) {
         cp.out = c->attn_out.p; cp.H = H; cp.Hkv = H; cp.D = D; cp.Smax = c->Spad; cp.scale = 1.0f / sqrtf((float)D);
         cp.cross = 1; cp.cross_len = 1500;
         launch_attn_decode(cp, c->batch, s);
-        launch_gemm_skinny(EPI_PARTIAL, 2, 4, L.co, c->attn_out.p, c->part.p, d / 16, d / 32, c->S_o, d, Mpad, s, L.cbo);
+        whisper_gemm(c, L.qw[WQ_CO], L.co, EPI_PARTIAL, 4, c->attn_out.p, c->part.p, d / 16, d, c->S_o, d, L.cbo);
         // MLP (:245-249)
-        if (f_fc1) {
+        if (f_fc1 && !L.qw[WQ_FC1].bits) {
             launch_gemm_skinny_norm(EPI_GELU_PACKED, 2, L.fc1, c->part.p, c->S_o, hcur, hoth, L.ln3w, L.ln3b, LN_EPS, c->batch, c->act.p, fd / 16, d / 32, 1,
                                     fd, Mpad, s, L.b1);
             std::swap(hcur, hoth);
         } else {
             launch_reduce_residual_rmsnorm(c->part.p, c->S_o, Mpad, d, hcur, L.ln3w, c->x.p, LN_EPS, s, L.ln3b);
-            launch_gemm_skinny(EPI_GELU_PACKED, 2, 4, L.fc1, c->x.p, c->act.p, fd / 16, d / 32, 1, fd, Mpad, s, L.b1);
+            whisper_gemm(c, L.qw[WQ_FC1], L.fc1, EPI_GELU_PACKED, 4, c->x.p, c->act.p, fd / 16, d, 1, fd, L.b1);
         }
-        launch_gemm_skinny(EPI_PARTIAL, 2, 4, L.fc2, c->act.p, c->part.p, d / 16, fd / 32, c->S_fc2, d, Mpad, s, L.b2);
+        whisper_gemm(c, L.qw[WQ_FC2], L.fc2, EPI_PARTIAL, 4, c->act.p, c->part.p, d / 16, fd, c->S_fc2, d, L.b2);
         const bf16_t* nw = (li + 1 < c->dec.size()) ? c->dec[li + 1].ln1w : c->dec_lnw;
         const bf16_t* nb = (li + 1 < c->dec.size()) ? c->dec[li + 1].ln1b : c->dec_lnb;
         launch_reduce_residual_rmsnorm(c->part.p, c->S_fc2, Mpad, d, hcur, nw, c->x.p, LN_EPS, s, nb);
     }
 }
 static void enqueue_vocab(mis_whisper* c) {
-    launch_gemm_skinny(EPI_BF16, 2, 1, c->emb_packed, c->x.p, c->logits.p, c->Vpad / 16, c->d / 32, 1, c->Vpad, c->Mpad, c->stream);
+    whisper_gemm(c, c->qvocab, c->emb_packed, EPI_BF16, 1, c->x.p, c->logits.p, c->Vpad / 16, c->d, 1, c->Vpad, nullptr);
 }
 
 __global__ void k_bf16_rows_to_f32_w(const bf16_t* __restrict__ src, int src_stride, float* __restrict__ dst, int cols, int rows) {

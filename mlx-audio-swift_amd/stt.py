@@ -85,6 +85,40 @@ class STTOutput:
     token_ids: list = field(default_factory=list)   # per chunk (the engine's raw output; text needs a tokenizer)
 
 
+WHISPER_QUANT_ROLES = ("self_qkv", "self_out", "cross_q", "cross_out", "fc1", "fc2")
+
+
+def whisper_checkpoint_plan(dtypes: dict, quantization: dict | None) -> list:
+    """How WhisperModel.from_model_directory sends a checkpoint's tensors to the engine (WhisperModel.fromDirectory, WhisperModel.swift:
+    499-510: a `quantization` entry in config.json makes every Linear and decoder.embed_tokens an MLX affine-quantised module).
+    dtypes: key -> safetensors dtype string ("BF16", "F16", "F32", "U32", ...); quantization: config.json's entry or None.
+    Returns, in key order, ("dense", key) and ("quantized", weight_key, scales_key, biases_key, group_size, bits) entries; the tied
+    proj_out.* keys are dropped.  A uint32 `.weight` without `.scales`, or `.scales` / `.biases` without a `quantization` entry (or without
+    their companions), raise AudioGenerationError."""
+    plan = []
+    q = quantization or {}
+    for k in sorted(dtypes):
+        if k.startswith("proj_out.") or k.startswith("model.proj_out."):
+            continue                                                     # tied to the token embedding (WhisperModel.swift:343-346)
+        for suf in (".scales", ".biases"):
+            if k.endswith(suf):
+                base = k[: -len(suf)]
+                if not quantization:
+                    raise AudioGenerationError(3, f"{k}: quantised tensor in a checkpoint whose config.json has no quantization entry")
+                if base + ".weight" not in dtypes or base + ".scales" not in dtypes or base + ".biases" not in dtypes:
+                    raise AudioGenerationError(3, f"{k}: quantised tensor without its .weight / .scales / .biases companions")
+                break
+        else:
+            if k.endswith(".weight") and k[: -len(".weight")] + ".scales" in dtypes:
+                base = k[: -len(".weight")]
+                plan.append(("quantized", k, base + ".scales", base + ".biases", int(q.get("group_size", 64)), int(q.get("bits", 4))))
+            elif dtypes[k] in ("U32", "I32", "U8"):
+                raise AudioGenerationError(3, f"{k}: integer tensor without .scales (a quantised checkpoint needs .scales / .biases)")
+            else:
+                plan.append(("dense", k))
+    return plan
+
+
 class WhisperModel:
     """STTGenerationModel conformance: default_generation_parameters, generate(audio, generation_parameters)."""
 
@@ -109,9 +143,17 @@ class WhisperModel:
         return m
 
     @classmethod
-    def synthetic(cls, config, device: int = 0, seed: int = 777) -> "WhisperModel":
+    def synthetic(cls, config, device: int = 0, seed: int = 777, quant_bits: int | None = None, scale_dtype: str = "bf16") -> "WhisperModel":
+        """mis-synth-v1 weights; quant_bits 8 / 4: every Linear and the token embedding as a synthetic group-64 quantised matrix with
+        scale_dtype ("bf16" or "f16") scales and biases."""
         m = cls(config, device)
-        check(_lib.lib().mis_whisper_init_synthetic(m._h, seed))
+        if quant_bits:
+            if scale_dtype not in ("bf16", "f16"):
+                raise AudioGenerationError(3, f"scale_dtype must be 'bf16' or 'f16', not {scale_dtype!r}")
+            sbt = _lib.MIS_BF16 if scale_dtype == "bf16" else _lib.MIS_F16
+            check(_lib.lib().mis_whisper_init_synthetic_quantized(m._h, seed, int(quant_bits), sbt))
+        else:
+            check(_lib.lib().mis_whisper_init_synthetic(m._h, seed))
         m.finalize()
         return m
 
@@ -120,15 +162,24 @@ class WhisperModel:
         """fromDirectory: config.json + *.safetensors (WhisperModel.swift:337-363) in either key layout - HF transformers
         ("model.encoder.layers.N.self_attn.q_proj.*") or OpenAI / mlx-whisper ("encoder.blocks.N.attn.query.*", MLX conv
         layout, no encoder positional embedding); the engine's set_tensor applies WhisperModel.sanitize (:321-478)."""
+        import torch
         from safetensors import safe_open
         with open(os.path.join(model_dir, "config.json")) as f:
-            cfg = WhisperConfig.from_dict(json.load(f))
+            cj = json.load(f)
+        cfg = WhisperConfig.from_dict(cj)
+        quant = cj.get("quantization") or cj.get("quantization_config")
         m = cls(cfg, device)
         for fn in sorted(os.listdir(model_dir)):
             if fn.endswith(".safetensors"):
                 with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
-                    for k in sf.keys():
-                        m.set_tensor(k, sf.get_tensor(k))
+                    plan = whisper_checkpoint_plan({k: sf.get_slice(k).get_dtype() for k in sf.keys()}, quant)
+                    for e in plan:
+                        if e[0] == "dense":
+                            m.set_tensor(e[1], sf.get_tensor(e[1]))
+                        else:
+                            _, kw, ks, kb, gs, bits = e
+                            wq = sf.get_tensor(kw).contiguous().view(torch.int32).numpy().view(np.uint32)
+                            m.set_quantized_tensor(kw, wq, sf.get_tensor(ks), sf.get_tensor(kb), gs, bits)
         m.finalize()
         gc = os.path.join(model_dir, "generation_config.json")
         if os.path.exists(gc):
@@ -141,8 +192,29 @@ class WhisperModel:
         sh = (C.c_int64 * len(shape))(*shape)
         check(_lib.lib().mis_whisper_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
 
+    def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
+        """A Linear / Embedding in MLX's affine-quantised form (`name` = its .weight key): wq uint32 [N, K*bits/32], scales / biases
+        [N, K/group_size] (bf16 / f16 / f32)."""
+        wq = np.ascontiguousarray(wq, dtype=np.uint32)
+        ks, ps, ds, ss = _tensor_args(scales)
+        kb, pb, db, sb = _tensor_args(biases)
+        if ds != db or tuple(ss) != tuple(sb) or len(ss) != 2:
+            raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
+        N, K = int(ss[0]), int(ss[1]) * group_size
+        check(_lib.lib().mis_whisper_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
+
     def finalize(self):
         check(_lib.lib().mis_whisper_finalize(self._h))
+
+    @property
+    def native_quant_bits(self) -> dict:
+        """after finalize: bits each decoder matrix streams in (0 = dense bf16): role -> [per decoder layer], plus "vocab" (the tied
+        projection) -> int"""
+        l = _lib.lib()
+        out = {r: [int(l.mis_whisper_native_quant_bits(self._h, li, i)) for li in range(self.config.decoder_layers)]
+               for i, r in enumerate(WHISPER_QUANT_ROLES)}
+        out["vocab"] = int(l.mis_whisper_native_quant_bits(self._h, 0, len(WHISPER_QUANT_ROLES)))
+        return out
 
     @property
     def default_generation_parameters(self) -> STTGenerateParameters:      # WhisperModel.swift:21-34
