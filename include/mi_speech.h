@@ -354,20 +354,31 @@ mis_status mis_soprano_create(const mis_soprano_config*, int device, mis_soprano
  * weights, everything else -> the token LM (model.* / lm_head.weight) */
 mis_status mis_soprano_set_tensor(mis_soprano*, const char* name, const void* data, mis_dtype dtype,
                                   const int64_t* shape, int ndim);
+/* A Linear in MLX's affine-quantised form (SopranoModel.fromPretrained quantises every module with a `.scales` companion,
+ * Soprano.swift:949-963), with the format and validation of mis_tts_set_tensor_quantized; `name` is the .weight key, sanitised as
+ * above.  LM keys go to the token LM, which streams a role's codes or dequantises them at load as mis_tts_set_tensor_quantized says.
+ * Decoder keys (decoder.decoder.convnext.N.pwconv1 / pwconv2, decoder.head.out) are dequantised once at load to float32 (s*q+b in
+ * float32) into the decoder's layouts: a stated deviation - the reference runs quantizedMatmul on float32 activations, this differs
+ * from it in summation order only. */
+mis_status mis_soprano_set_tensor_quantized(mis_soprano*, const char* name, const uint32_t* wq, const void* scales, const void* biases,
+                                            mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits);
 mis_status mis_soprano_finalize(mis_soprano*);
 void       mis_soprano_destroy(mis_soprano*);
 mis_tts*   mis_soprano_lm(mis_soprano*);                 /* borrowed handle of the token LM (taps, synthetic init) */
 int64_t    mis_soprano_num_samples(const mis_soprano*, int n_hidden);   /* (upscale*(n-1)) * hop_length */
 /* SopranoDecoder.callAsFunction: hidden f32 [batch, L, hidden_size] -> audio f32 [batch, num_samples(L)] */
 mis_status mis_soprano_decode(mis_soprano*, const float* hidden, int batch, int L, float* audio_out);
-/* generate for a batch of tokenised sentences: outputs as mis_tts_generate (pcm rows padded to the longest) */
+/* generate for a batch of tokenised sentences: outputs as mis_tts_generate (pcm rows padded to the longest).  One row runs on the batch-1
+ * token engine wherever mis_soprano_lm_path below says so - bf16 checkpoints and 8 / 4-bit quantised ones of the engine's widths alike. */
 mis_status mis_soprano_generate(mis_soprano*, const int32_t* prompt_ids, const int32_t* prompt_lens, int batch,
                                 const mis_gen_params* params, float** pcm_out, int64_t* pcm_stride, int64_t* pcm_lens,
                                 int32_t** tokens_out, int64_t* tokens_stride, int32_t* n_tokens);
 /* Which program ran the LM loop of the handle's LAST generate / generateStream call: 0 = the launch chain, chosen by rule; 1 = the batch-1
- * token engine (one persistent launch; chosen by rule: a ONE-row request - over all shards of a group call - on a bf16 checkpoint of
- * Soprano-80M's widths, device of 8 XCDs x 32 compute units not shared with another replica, prompt + max_tokens <= 1024,
- * repetition context <= 64; MIS_TOKEN_ENGINE=0 disables it); 2 = the launch chain AFTER the engine's workers could not be made
+ * token engine (one persistent launch; chosen by rule: a ONE-row request - over all shards of a group call - on a checkpoint of
+ * Soprano-80M's widths that is bf16 or MLX-quantised with q|k|v, o_proj, gate|up and down_proj all streamed as codes of ONE width,
+ * 8 or 4 bit (mis_tts_native_quant_bits; the output projection dense or of the same width), device of 8 XCDs x 32 compute units not
+ * shared with another replica, prompt + max_tokens <= 1024, repetition context <= 64; MIS_TOKEN_ENGINE=0 disables it); 2 = the launch
+ * chain AFTER the engine's workers could not be made
  * co-resident (another stream held compute units; also written to stderr).  The two programs round at the same points but sum in other
  * orders: ids can differ on near-ties, so the choice never depends on stream vs non-stream, only on the request (and, reported, on 2). */
 int32_t    mis_soprano_lm_path(const mis_soprano*);

@@ -212,6 +212,7 @@ SYMBOLS = {
                                                   C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_create": (C.c_int, [C.POINTER(SopranoConfigC), C.c_int, C.POINTER(_P)]),
     "mis_soprano_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_soprano_set_tensor_quantized": (C.c_int, [_P, C.c_char_p, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "mis_soprano_finalize": (C.c_int, [_P]),
     "mis_soprano_destroy": (None, [_P]),
     "mis_soprano_lm": (_P, [_P]),

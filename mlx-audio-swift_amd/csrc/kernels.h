@@ -51,11 +51,16 @@ void tts_internal_enqueue_layers(mis_tts* c, const bf16_t* table, int table_rows
 void tts_internal_enqueue_head(mis_tts* c, const bf16_t* head_packed);      // logits of the view; nullptr = own lm_head
 TtsView tts_internal_view(mis_tts* c);
 // the packed weights of a finalized handle, for engines that stream them in their own kernels (token_engine.hip)
+// (a role streamed as MLX-quantised codes: its dense pointer is null and its QRole view holds the packed codes / scale-bias pairs of
+// lm_qgemm.hip, layer strides in bytes / bf16 elements, and the bit width; bits 0 = dense)
+struct TtsQRoleView { const uint8_t* q; const bf16_t* sb; size_t q_layer, sb_layer; int bits; };
 struct TtsWeightsView {
     const bf16_t *emb, *wqkv, *wo, *wgu, *wdown, *head, *norms, *qknorm;
     int d, L, ff, H, Hkv, D, V, Vpad, Nqkv, device, finalized, qk_norm, rope_plain, quantised;
     float eps;
     hipStream_t stream;
+    TtsQRoleView q_qkv, q_o, q_gu, q_down, q_head;
+    int q_head_nt;                     // n-tiles of the code-streamed output projection (round_up(V, 16) / 16)
 };
 TtsWeightsView tts_internal_weights(mis_tts* c);
 // RoPE cos / sin tables [positions][D/2] for at least `max_context` positions (re-initialises the handle's per-batch state for one row)

@@ -1952,6 +1952,9 @@ TtsWeightsView tts_internal_weights(mis_tts* c) {
     v.device = c->device; v.finalized = c->finalized ? 1 : 0; v.qk_norm = c->cfg.qk_norm ? 1 : 0; v.rope_plain = c->cfg.rope_plain ? 1 : 0;
     v.quantised = (c->q_qkv.on || c->q_o.on || c->q_gu.on || c->q_down.on || c->q_head.on) ? 1 : 0;
     v.eps = c->cfg.rms_norm_eps; v.stream = c->stream;
+    auto qv = [](const mis_tts::QRole& R) { return R.on ? TtsQRoleView{R.q.p, R.sb.p, R.q_layer, R.sb_layer, R.bits} : TtsQRoleView{}; };
+    v.q_qkv = qv(c->q_qkv); v.q_o = qv(c->q_o); v.q_gu = qv(c->q_gu); v.q_down = qv(c->q_down); v.q_head = qv(c->q_head);
+    v.q_head_nt = c->q_head.on ? (int)(round_up(c->V, 16) / 16) : 0;
     return v;
 }
 void tts_internal_rope_tables(mis_tts* c, int max_context, const float** cos_out, const float** sin_out) {

@@ -20,40 +20,12 @@
 // Work decomposition, epilogues and the in-block split-K combine are those of k_gemm_skinny; K ranges are cut at scale groups.
 #include "common.h"
 #include "lm_kernels.h"
+#include "lm_qcodes.h"
 
 
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-template <int BITS> struct QTile;
-template <> struct QTile<8> { typedef u32x2_t type; };
-template <> struct QTile<4> { typedef unsigned int type; };
-
-// 8 codes -> 8 bf16 values (exact).  (float)(byte) is v_cvt_f32_ubyteN; the pair conversion is v_cvt_pk_bf16_f32.
-// (Measured alternative: v_perm_b32 placing byte k under the exponent of 2^23, one v_pk_add_f32 per pair, then the same pack - 16
-// instead of 12 instructions per fragment and no faster anywhere: profiles/r03/qgemm_loads_vs_math.jsonl.)
-__device__ __forceinline__ bf16x8_t dq_codes(u32x2_t w) {
-    bf16x8_t r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        r[e] = (short)f32_to_bf16((float)((w.x >> (8 * e)) & 0xffu));
-        r[4 + e] = (short)f32_to_bf16((float)((w.y >> (8 * e)) & 0xffu));
-    }
-    return r;
-}
-__device__ __forceinline__ bf16x8_t dq_codes(unsigned int w) {
-    bf16x8_t r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (short)f32_to_bf16((float)((w >> (4 * e)) & 0xfu));
-    return r;
-}
 __device__ __forceinline__ void unpack_bf16x4(uint2 v, float (&o)[4]) {
     o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
     o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-// one 16-bit scale / bias (low half of w) -> float32, exactly: SBT 0 = bf16, 1 = f16 (v_cvt_f32_f16)
-template <int SBT>
-__device__ __forceinline__ float sb_to_f32(uint32_t w) {
-    if (SBT == 1) return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
-    return __uint_as_float(w << 16);
 }
 template <int SBT>
 __device__ __forceinline__ void unpack_sb4(uint2 v, float (&o)[4]) {

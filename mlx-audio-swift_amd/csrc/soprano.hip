@@ -250,6 +250,52 @@ extern "C" mis_status mis_soprano_set_tensor(mis_soprano* c, const char* name_, 
     MIS_API_END
 }
 
+// A Linear in MLX's affine-quantised form (SopranoModel.fromPretrained quantises every module with a `.scales` companion,
+// Soprano.swift:949-963).  LM keys go to the LM handle (mis_tts_set_tensor_quantized: codes streamed or dequantised per role there);
+// decoder keys (decoder.decoder.convnext.N.pwconv1 / pwconv2, decoder.head.out) are dequantised once here to float32, s * q + b in
+// float32, into what mis_soprano_set_tensor stores - the reference runs quantizedMatmul on float32 activations, this differs from it in
+// summation order only.
+extern "C" mis_status mis_soprano_set_tensor_quantized(mis_soprano* c, const char* name_, const uint32_t* wq, const void* scales,
+                                                       const void* biases, mis_dtype sb_dtype, int64_t N, int64_t K, int group_size,
+                                                       int bits) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && name_ && wq && scales && biases, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
+    const std::string name = sop_sanitize(name_);
+    if (name.rfind("decoder.", 0) != 0) return mis_tts_set_tensor_quantized(c->lm, name.c_str(), wq, scales, biases, sb_dtype, N, K, group_size, bits);
+    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d (2, 4 or 8 bits)", bits);
+    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT,
+                "bad quantised shape for %s", name.c_str());
+    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
+    HIP_CHECK(hipSetDevice(c->device));
+    const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
+    std::vector<uint32_t> w(words);
+    std::vector<uint8_t> sraw(ng * esz), braw(ng * esz);
+    HIP_CHECK(hipMemcpy(w.data(), wq, words * 4, hipMemcpyDefault));
+    HIP_CHECK(hipMemcpy(sraw.data(), scales, ng * esz, hipMemcpyDefault));
+    HIP_CHECK(hipMemcpy(braw.data(), biases, ng * esz, hipMemcpyDefault));
+    auto widen = [&](const std::vector<uint8_t>& raw, size_t i) -> float {
+        if (sb_dtype == MIS_F32) { float f; memcpy(&f, raw.data() + 4 * i, 4); return f; }
+        const uint16_t h = reinterpret_cast<const uint16_t*>(raw.data())[i];
+        return sb_dtype == MIS_BF16 ? bf16_to_f32(h) : f16_to_f32_host(h);
+    };
+    // element k of row n: word k / (32 / bits) of the row, bits [bits (k % (32 / bits)), + bits) (mlx quantize)
+    std::vector<float> v((size_t)N * K);
+    const uint32_t mask = (1u << bits) - 1u;
+    const int epw = 32 / bits;
+    for (int64_t n = 0; n < N; ++n) {
+        const uint32_t* rw = w.data() + (size_t)n * (K / epw);
+        for (int64_t k = 0; k < K; ++k) {
+            const float q = (float)((rw[k / epw] >> (bits * (k % epw))) & mask);
+            const size_t gi = (size_t)n * (K / group_size) + (size_t)(k / group_size);
+            v[(size_t)n * K + k] = widen(sraw, gi) * q + widen(braw, gi);
+        }
+    }
+    c->raw[name] = std::move(v);
+    c->raw_shape[name] = {N, K};
+    MIS_API_END
+}
+
 static const std::vector<float>& sneed(mis_soprano* c, const std::string& name, std::initializer_list<int64_t> shape) {
     auto it = c->raw.find(name);
     MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "Soprano weight missing: %s", name.c_str());
@@ -427,8 +473,9 @@ static void soprano_generate_impl(mis_soprano* c, const int32_t* prompt_ids, con
     // Soprano.swift:877 - the reference's generate is itself built on streamGenerate, :801-885).
     // WHICH program runs the LM loop is a function of the request and the handle only: the engine iff the request is ONE
     // row (of a group call: one row over all shards), the checkpoint has the widths the engine is compiled for (TeShape: Soprano-80M,
-    // bf16 - other widths and MLX-quantised checkpoints, SopranoConfig.swift:167-190, take the launch chain at ~0.57 ms per token), the
-    // device is 8 XCDs x 32 compute units not shared with another replica, and the request fits the engine's context.
+    // bf16 or MLX-quantised with every layer role streamed as 8- or 4-bit codes of one width - token_engine_q.hip; other widths and
+    // mixed quantisations, SopranoConfig.swift:167-190, take the launch chain at ~0.57 ms per token), the device is 8 XCDs x 32 compute
+    // units not shared with another replica, and the request fits the engine's context.
     // MIS_TOKEN_ENGINE = 0 keeps the launch chain, 1 / 2 / 4 / 8 picks the number of XCDs.  The one run-time exception is reported, never
     // silent: if the engine's workers cannot be co-resident (another stream holds compute units: its bounded polls run out before the
     // first id) the request runs on the launch chain, mis_soprano_lm_path() returns 2 and a line goes to stderr - the launch chain's

@@ -8,6 +8,8 @@ whitespace collapse: it is string processing outside the accelerated path."""
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 import re
 from dataclasses import dataclass
 
@@ -51,6 +53,16 @@ class SopranoConfiguration:
         known = {f for f in cls.__dataclass_fields__}
         return cls(**{k: v for k, v in d.items() if k in known})
 
+    @classmethod
+    def from_model_config(cls, config_json: dict, repo: str) -> "SopranoConfiguration":
+        """config.json as SopranoModel.fromModelDirectory reads it: SopranoConfig.swift's defaults for absent keys, then the
+        pre-1.1 decoder (Soprano.swift:935-941) - decoder_dim 512, decoder_intermediate_dim 1536, input_kernel 3 - unless the
+        repo name contains "soprano-1.1"."""
+        cfg = cls.from_dict(config_json)
+        if "soprano-1.1" not in repo.lower():
+            cfg.decoder_dim, cfg.decoder_intermediate_dim, cfg.input_kernel = 512, 1536, 3
+        return cfg
+
     def lm_configuration(self) -> LlamaTTSConfiguration:
         return LlamaTTSConfiguration(hidden_size=self.hidden_size, num_hidden_layers=self.num_hidden_layers,
                                      intermediate_size=self.intermediate_size,
@@ -64,6 +76,59 @@ class SopranoConfiguration:
         return _lib.SopranoConfigC(self.lm_configuration().to_c(), self.decoder_num_layers, self.decoder_dim,
                                    self.decoder_intermediate_dim, self.hop_length, self.n_fft, self.upscale,
                                    self.input_kernel, self.dw_kernel, self.token_size, self.stop_token_id)
+
+
+def _sanitize_key(key: str) -> str:
+    """SopranoModel.sanitize's key map (Soprano.swift:314-360)."""
+    k = key[len("model."):] if key.startswith("model.") else key
+    if k.startswith("decoder."):
+        return k
+    if k.startswith("language_model.lm_head"):
+        return k.replace("language_model.", "")
+    if k.startswith("language_model."):
+        return k.replace("language_model.", "model.")
+    if k.startswith("lm_head"):
+        return k
+    return "model." + k
+
+
+def soprano_checkpoint_plan(dtypes: dict, quantization: dict | None, tie_word_embeddings: bool) -> list:
+    """How SopranoModel.from_model_directory sends a checkpoint's tensors to the engine (SopranoModel.fromModelDirectory,
+    Soprano.swift:905-979: sanitize :314-360, then every module with a `.scales` companion quantised with its per-layer entry of
+    `quantization` or the global one, :949-963).  dtypes: stored key -> safetensors dtype string; quantization: config.json's
+    `quantization` / `quantization_config` entry or None.  Returns, in key order, ("dense", src_key, dst_key, as_f32) and
+    ("quantized", w_key, scales_key, biases_key, dst_key, group_size, bits) entries (dst_key: the sanitized .weight key); decoder
+    tensors other than packed weights and their scales / biases are cast to float32; lm_head.weight is dropped under tied embeddings.
+    `.scales` / `.biases` without a quantization entry or without their companions, and a U32 / I32 weight without `.scales`, raise
+    AudioGenerationError."""
+    q = quantization or {}
+    plan = []
+    for k in sorted(dtypes):
+        dst = _sanitize_key(k)
+        if tie_word_embeddings and dst == "lm_head.weight":
+            continue
+        suf = next((s for s in (".scales", ".biases") if k.endswith(s)), None)
+        if suf is not None:
+            base = k[: -len(suf)]
+            if not quantization:
+                raise AudioGenerationError(3, f"{k}: quantised tensor in a checkpoint whose config.json has no quantization entry")
+            if base + ".weight" not in dtypes or base + ".scales" not in dtypes or base + ".biases" not in dtypes:
+                raise AudioGenerationError(3, f"{k}: quantised tensor without its .weight / .scales / .biases companions")
+            continue                                                     # (sent with its .weight)
+        if k.endswith(".weight") and k[: -len(".weight")] + ".scales" in dtypes:
+            base = k[: -len(".weight")]
+            if base + ".biases" not in dtypes:
+                raise AudioGenerationError(3, f"{k}: quantised weight without its .biases companion")
+            if not quantization:
+                raise AudioGenerationError(3, f"{k}: quantised tensor in a checkpoint whose config.json has no quantization entry")
+            layer = q.get(dst[: -len(".weight")])
+            src = layer if isinstance(layer, dict) else q
+            plan.append(("quantized", k, base + ".scales", base + ".biases", dst, int(src.get("group_size", 64)), int(src.get("bits", 4))))
+        elif dtypes[k] in ("U32", "I32"):
+            raise AudioGenerationError(3, f"{k}: integer tensor without .scales (a quantised checkpoint needs .scales / .biases)")
+        else:
+            plan.append(("dense", k, dst, dst.startswith("decoder.")))
+    return plan
 
 
 _SENT_SPLIT = re.compile(r"(?<=[.!?])\s+")
@@ -152,19 +217,80 @@ class SopranoModel:
         return m
 
     @classmethod
-    def synthetic(cls, config, device: int = 0, seed: int = 4321, decoder_seed: int = 99) -> "SopranoModel":
+    def synthetic(cls, config, device: int = 0, seed: int = 4321, decoder_seed: int = 99, quant_bits: int | None = None) -> "SopranoModel":
+        """mis-synth-v1 LM weights; quant_bits 8 / 4: every Linear of the LM as a synthetic group-64 quantised matrix (bf16 scales),
+        streamed as codes (mis_tts_init_synthetic_quantized)."""
         from .synthetic import soprano_decoder_synthetic_weights
         m = cls(config, device)
-        check(_lib.lib().mis_tts_init_synthetic(m.lm._h, seed))
+        if quant_bits:
+            check(_lib.lib().mis_tts_init_synthetic_quantized(m.lm._h, seed, int(quant_bits)))
+        else:
+            check(_lib.lib().mis_tts_init_synthetic(m.lm._h, seed))
         for k, v in soprano_decoder_synthetic_weights(config, decoder_seed).items():
             m.set_tensor(k, v)
         m.finalize()
         return m
 
+    @classmethod
+    def from_model_directory(cls, model_dir: str, repo: str | None = None, device: int = 0) -> "SopranoModel":
+        """SopranoModel.fromModelDirectory (Soprano.swift:926-979): config.json (SopranoConfiguration.from_model_config with `repo`,
+        default the directory's base name) and every *.safetensors in name order, later files overriding earlier keys
+        (loadSopranoWeights); soprano_checkpoint_plan says what goes to set_tensor and what to set_quantized_tensor.  The tokenizer is
+        not attached (it cannot be checked offline): set `tokenizer` before generate(text); the stop id is the configuration's."""
+        import torch
+        from safetensors import safe_open
+        with open(os.path.join(model_dir, "config.json")) as f:
+            cj = json.load(f)
+        repo = repo if repo is not None else os.path.basename(os.path.normpath(model_dir))
+        cfg = SopranoConfiguration.from_model_config(cj, repo)
+        quant = cj.get("quantization") or cj.get("quantization_config")
+        files = sorted(fn for fn in os.listdir(model_dir) if fn.endswith(".safetensors"))
+        where = {}                                                          # key -> file (the last one that holds it)
+        for fn in files:
+            with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
+                for k in sf.keys():
+                    where[k] = (fn, sf.get_slice(k).get_dtype())
+        plan = soprano_checkpoint_plan({k: v[1] for k, v in where.items()}, quant, cfg.tie_word_embeddings)
+        m = cls(cfg, device)
+        handles = {fn: safe_open(os.path.join(model_dir, fn), framework="pt") for fn in files}
+        try:
+            get = lambda k: handles[where[k][0]].get_tensor(k)
+            for e in plan:
+                if e[0] == "dense":
+                    _, src, dst, as_f32 = e
+                    v = get(src)
+                    m.set_tensor(dst, v.float() if as_f32 else v)
+                else:
+                    _, kw, ks, kb, dst, gs, bits = e
+                    wq = get(kw).contiguous().view(torch.int32).numpy().view(np.uint32)
+                    m.set_quantized_tensor(dst, wq, get(ks), get(kb), gs, bits)
+        finally:
+            handles.clear()
+        m.finalize()
+        return m
+
+    @classmethod
+    def from_pretrained(cls, model_repo: str, device: int = 0) -> "SopranoModel":
+        if os.path.isdir(model_repo):
+            return cls.from_model_directory(model_repo, device=device)
+        raise AudioGenerationError(1, f"model repo {model_repo!r} is not a local directory (no network access)")
+
     def set_tensor(self, name: str, arr):
         keep, ptr, dt, shape = _tensor_args(arr)
         sh = (C.c_int64 * len(shape))(*shape)
         check(_lib.lib().mis_soprano_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
+
+    def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
+        """A Linear in MLX's affine-quantised form (`name` = its .weight key, sanitised like set_tensor's): wq uint32
+        [N, K*bits/32], scales / biases [N, K/group_size] (bf16 / f16 / f32).  LM matrices go to the token LM (streamed as codes
+        where a whole role qualifies, see mis_tts_set_tensor_quantized); decoder matrices are dequantised to float32 at load."""
+        wq = np.ascontiguousarray(wq, dtype=np.uint32)
+        ks, ps, ds, ss = _tensor_args(scales)
+        kb, pb, db, sb = _tensor_args(biases)
+        if ds != db or tuple(ss) != tuple(sb) or len(ss) != 2:
+            raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
+        N, K = int(ss[0]), int(ss[1]) * group_size
+        check(_lib.lib().mis_soprano_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
 
     def finalize(self):
         check(_lib.lib().mis_soprano_finalize(self._h))
