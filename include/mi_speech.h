@@ -584,6 +584,48 @@ mis_status mis_encodec_debug_tap(mis_encodec*, const int32_t* codes, int batch, 
                                  int32_t* channels, int64_t* length);
 
 /* ------------------------------------------------------------------------------------------
+ * Mimi codec (Kyutai, 12.5 Hz codes, 24 kHz mono).  Replaces Mimi.decode / encode (Sources/MLXAudioCodecs/Mimi/Mimi.swift:168-186),
+ * MimiStreamingDecoder.decodeFrames (:207-232, decodeStep :196-204) and the modules behind them: SplitResidualVectorQuantizer
+ * (Quantization.swift), ConvTrUpsample1d / StreamableConv1d / StreamableConvTranspose1d (Conv.swift), the decoder transformer
+ * (Transformer.swift) and SeanetDecoder / SeanetEncoder (Seanet.swift).  Float32 throughout.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_mimi mis_mimi;
+typedef struct {                   /* MimiConfig of mimi_202407 (Mimi.swift:47-99); mis_mimi_202407 fills the defaults */
+    int32_t channels, sample_rate; float frame_rate;
+    /* SeanetConfig: dimension, filters, residual layers, ratios (decoder order), kernel sizes, dilation base, compress */
+    int32_t dimension, n_filters, n_residual_layers, n_ratios, ratios[8];
+    int32_t kernel_size, residual_kernel_size, last_kernel_size, dilation_base, compress;
+    /* TransformerConfig: layers, heads, feed-forward width, streaming attention context, RoPE max period, LayerNorm eps */
+    int32_t num_layers, num_heads, dim_feedforward, context;
+    float   max_period, norm_eps;
+    /* SplitResidualVectorQuantizer: codebooks (one semantic + nq - 1 acoustic), bins, codebook dimension */
+    int32_t num_quantizers, bins, quantizer_dim;
+} mis_mimi_config;
+void       mis_mimi_202407(int num_codebooks, mis_mimi_config* out);
+mis_status mis_mimi_create(const mis_mimi_config*, int device, mis_mimi** out);
+/* post-sanitize names and layouts (Mimi.sanitize :337-415): conv [out, k, in], convtr [out, k, in / groups], Linear [out, in],
+ * quantizer "*.output_proj.weight" / "*.input_proj.weight" [out, 1, in].  Missing keys fail at finalize.  The encoder is built when
+ * "encoder.*" / "encoder_transformer.*" / "downsample.*" / the input projections are present; the codebooks serve both directions. */
+mis_status mis_mimi_set_tensor(mis_mimi*, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim);
+mis_status mis_mimi_finalize(mis_mimi*);
+void       mis_mimi_destroy(mis_mimi*);
+int64_t    mis_mimi_num_samples(const mis_mimi*, int n_frames);            /* n_frames * 1920 for mimi_202407 */
+/* Mimi.decode: codes int32 [batch, n_q, T] (host or device), 2 <= n_q <= num_quantizers (else MIS_ERR_INVALID_INPUT) ->
+ * pcm f32 [batch, num_samples(T)].  Plain causal attention over the whole sequence. */
+mis_status mis_mimi_decode(mis_mimi*, const int32_t* codes, int batch, int n_q, int T, float* pcm_out);
+/* Mimi.encode: audio f32 [batch, n_samples] -> codes int32 [batch, n_q, encode_num_frames(n_samples)], 1 <= n_q <= num_quantizers;
+ * MIS_ERR_AUDIO_ENCODE without encoder tensors */
+int64_t    mis_mimi_encode_num_frames(const mis_mimi*, int64_t n_samples);
+mis_status mis_mimi_encode(mis_mimi*, const float* audio, int batch, int64_t n_samples, int n_q, int32_t* codes_out);
+/* MimiStreamingDecoder: begin opens (or resets) a session of `batch` independent rows; each step decodes the next n_frames frames of
+ * every row, codes int32 [batch, n_q, n_frames] -> pcm f32 [batch, n_frames * num_samples(1)], the result of n_frames decodeStep
+ * calls.  The attention of the step sees the last `context` keys before the frame (Transformer.swift:155-166); the stream has no
+ * length limit.  step without begin: MIS_ERR_NOT_INITIALIZED. */
+mis_status mis_mimi_decode_stream_begin(mis_mimi*, int batch);
+mis_status mis_mimi_decode_stream_step(mis_mimi*, const int32_t* codes, int n_q, int n_frames, float* pcm_out);
+mis_status mis_mimi_decode_stream_end(mis_mimi*);
+
+/* ------------------------------------------------------------------------------------------
  * Log-mel / STFT front end.  Replaces WhisperAudio.logMelSpectrogram / encoderFeatures
  * (Sources/MLXAudioSTT/Models/Whisper/WhisperAudio.swift:38-87) and computeMelSpectrogram
  * (Sources/MLXAudioCore/DSP.swift:230-273): reflect pad, window, rfft, |.|^2, mel filterbank

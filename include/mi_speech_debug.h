@@ -33,6 +33,10 @@ int32_t mis_debug_sampler_failures(void);
 /* tests: device bytes a finalized Whisper handle holds for its weights (the bf16 arena plus the code / scale tables of the natively
  * streamed quantised decoder matrices) */
 int64_t mis_debug_whisper_weight_bytes(const mis_whisper* c);
+/* tests: stage outputs of the Mimi decoder (whole sequence), out f32 [batch, C, T'].  stage 0 RVQ latent, 1 upsampled, 2 transformer,
+ * 3 init conv, 4 + i decoder layer i (ELU, transposed conv, residual blocks), 4 + n_ratios final (pcm, C = 1) */
+mis_status mis_debug_mimi_decoder_tap(mis_mimi* m, const int32_t* codes, int batch, int n_q, int T, int stage, float* out, int64_t capacity,
+                                      int32_t* channels, int64_t* length);
 
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product

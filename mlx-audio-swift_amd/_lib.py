@@ -95,6 +95,16 @@ class DacConfigC(C.Structure):
                 ("codebook_dim", C.c_int32), ("sample_rate", C.c_int32)]
 
 
+class MimiConfigC(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("sample_rate", C.c_int32), ("frame_rate", C.c_float),
+                ("dimension", C.c_int32), ("n_filters", C.c_int32), ("n_residual_layers", C.c_int32), ("n_ratios", C.c_int32),
+                ("ratios", C.c_int32 * 8), ("kernel_size", C.c_int32), ("residual_kernel_size", C.c_int32),
+                ("last_kernel_size", C.c_int32), ("dilation_base", C.c_int32), ("compress", C.c_int32),
+                ("num_layers", C.c_int32), ("num_heads", C.c_int32), ("dim_feedforward", C.c_int32), ("context", C.c_int32),
+                ("max_period", C.c_float), ("norm_eps", C.c_float),
+                ("num_quantizers", C.c_int32), ("bins", C.c_int32), ("quantizer_dim", C.c_int32)]
+
+
 class EncodecConfigC(C.Structure):
     _fields_ = [("audio_channels", C.c_int32), ("num_filters", C.c_int32), ("kernel_size", C.c_int32),
                 ("num_residual_layers", C.c_int32), ("dilation_growth_rate", C.c_int32), ("codebook_size", C.c_int32),
@@ -281,6 +291,18 @@ SYMBOLS = {
     "mis_encodec_decode_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_encodec_debug_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64)]),
+    "mis_mimi_202407": (None, [C.c_int, C.POINTER(MimiConfigC)]),
+    "mis_mimi_create": (C.c_int, [C.POINTER(MimiConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_mimi_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_mimi_finalize": (C.c_int, [_P]),
+    "mis_mimi_destroy": (None, [_P]),
+    "mis_mimi_num_samples": (C.c_int64, [_P, C.c_int]),
+    "mis_mimi_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_mimi_encode_num_frames": (C.c_int64, [_P, C.c_int64]),
+    "mis_mimi_encode": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, _P]),
+    "mis_mimi_decode_stream_begin": (C.c_int, [_P, C.c_int]),
+    "mis_mimi_decode_stream_step": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "mis_mimi_decode_stream_end": (C.c_int, [_P]),
 }
 
 # diagnostics / test scaffolding: include/mi_speech_debug.h (not part of the product surface)
@@ -293,6 +315,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_choose_split": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
+    "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int64)]),
 }
 
 _lib = None

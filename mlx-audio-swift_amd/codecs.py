@@ -472,3 +472,236 @@ class Encodec:
         ch = C.c_int32(); ln = C.c_int64()
         check(_lib.lib().mis_encodec_debug_tap(self._h, cd.ctypes.data, B, nq, T, stage, buf.ctypes.data, cap, C.byref(ch), C.byref(ln)))
         return buf[: B * ch.value * ln.value].reshape(B, ch.value, ln.value).copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Mimi (Sources/MLXAudioCodecs/Mimi/)
+@dataclass
+class MimiConfig:
+    """MimiConfig with the mimi_202407 defaults (Mimi.swift:47-99)."""
+    num_codebooks: int = 32
+    channels: int = 1
+    sample_rate: int = 24000
+    frame_rate: float = 12.5
+    dimension: int = 512
+    n_filters: int = 64
+    n_residual_layers: int = 1
+    ratios: list = field(default_factory=lambda: [8, 6, 5, 4])
+    kernel_size: int = 7
+    residual_kernel_size: int = 3
+    last_kernel_size: int = 3
+    dilation_base: int = 2
+    compress: int = 2
+    num_layers: int = 8
+    num_heads: int = 8
+    dim_feedforward: int = 2048
+    context: int = 250
+    max_period: float = 10000.0
+    norm_eps: float = 1e-5
+    bins: int = 2048
+    quantizer_dim: int = 256
+
+    @property
+    def stride(self) -> int:                          # downsampleStride (Mimi.swift:125-126)
+        return int(self.sample_rate / float(np.prod(self.ratios)) / self.frame_rate)
+
+    @property
+    def samples_per_frame(self) -> int:
+        return self.stride * int(np.prod(self.ratios))
+
+    def to_c(self) -> "_lib.MimiConfigC":
+        c = _lib.MimiConfigC()
+        c.channels, c.sample_rate, c.frame_rate = self.channels, self.sample_rate, self.frame_rate
+        c.dimension, c.n_filters, c.n_residual_layers = self.dimension, self.n_filters, self.n_residual_layers
+        c.n_ratios = len(self.ratios)
+        for i, r in enumerate(self.ratios):
+            c.ratios[i] = r
+        c.kernel_size, c.residual_kernel_size, c.last_kernel_size = self.kernel_size, self.residual_kernel_size, self.last_kernel_size
+        c.dilation_base, c.compress = self.dilation_base, self.compress
+        c.num_layers, c.num_heads, c.dim_feedforward, c.context = self.num_layers, self.num_heads, self.dim_feedforward, self.context
+        c.max_period, c.norm_eps = self.max_period, self.norm_eps
+        c.num_quantizers, c.bins, c.quantizer_dim = self.num_codebooks, self.bins, self.quantizer_dim
+        return c
+
+
+def _swap(v, a: int, b: int):
+    return v.transpose(a, b) if hasattr(v, "detach") else np.swapaxes(v, a, b)
+
+
+def _permute(v, axes):
+    return v.permute(*axes) if hasattr(v, "detach") else np.transpose(v, axes)
+
+
+def mimi_sanitize(key: str, arr):
+    """Mimi.sanitize (Mimi.swift:337-415) for one raw Kyutai (PyTorch) tensor -> (post-sanitize key, array in the MLX layout)."""
+    k = ".".join(seg[1:] if seg.startswith("_") else seg for seg in key.split("."))
+    if k.startswith("encoder.model."):
+        k = k.replace("encoder.model.", "encoder.")
+    if k.startswith("decoder.model."):
+        k = k.replace("decoder.model.", "decoder.")
+    if k.endswith(".in_proj_weight"):
+        k = k.replace(".in_proj_weight", ".in_proj.weight")
+    if k.endswith(".linear1.weight"):
+        k = k.replace(".linear1.weight", ".gating.linear1.weight")
+    if k.endswith(".linear2.weight"):
+        k = k.replace(".linear2.weight", ".gating.linear2.weight")
+    for li, di in enumerate((2, 5, 8, 11)):
+        k = k.replace(f"decoder.{di}.", f"decoder.layers.{li}.upsample.")
+        k = k.replace(f"decoder.{di + 1}.", f"decoder.layers.{li}.residuals.0.")
+    for li, ei in enumerate((1, 4, 7, 10)):
+        k = k.replace(f"encoder.{ei}.", f"encoder.layers.{li}.residuals.0.")
+        k = k.replace(f"encoder.{ei + 2}.", f"encoder.layers.{li}.downsample.")
+    k = k.replace("decoder.0.", "decoder.init_conv1d.")
+    k = k.replace("decoder.14.", "decoder.final_conv1d.")
+    k = k.replace("encoder.0.", "encoder.init_conv1d.")
+    k = k.replace("encoder.14.", "encoder.final_conv1d.")
+    k = k.replace(".block.1.", ".block.0.")
+    k = k.replace(".block.3.", ".block.1.")
+    v = arr
+    if (k.endswith(".conv.weight") or k.endswith(".output_proj.weight") or k.endswith(".input_proj.weight")) and v.ndim >= 2:
+        v = _swap(v, v.ndim - 1, v.ndim - 2)
+    if k.endswith(".convtr.weight") and v.ndim == 3:
+        v = _swap(v, 1, 2) if v.shape[1] == 1 else _permute(v, (1, 2, 0))   # depthwise [C, 1, k] -> [C, k, 1]; [in, out, k] -> [out, k, in]
+    return k, v
+
+
+class Mimi:
+    """extension Mimi: AudioCodecModel (Mimi.swift:426-437): codec_sample_rate, frame_rate, encode / encode_audio, decode /
+    decode_audio; loaders from_weights (post-sanitize names), from_model_directory / from_pretrained (raw Kyutai safetensors through
+    mimi_sanitize; local directories only) and synthetic.  Weights are computed in float32 whatever their stored dtype."""
+
+    def __init__(self, config: MimiConfig | None = None, device: int = 0):
+        self.config = config or MimiConfig()
+        self._h = C.c_void_p()
+        cc = self.config.to_c()
+        check(_lib.lib().mis_mimi_create(C.byref(cc), device, C.byref(self._h)))
+
+    def close(self):
+        """Release the handle now: its stream, device buffers and the encoder (otherwise at garbage collection)."""
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _lib.lib().mis_mimi_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                                # interpreter shutdown
+            pass
+
+    # -- loading -----------------------------------------------------------------------------------
+    @classmethod
+    def from_weights(cls, config: MimiConfig, weights: dict, device: int = 0) -> "Mimi":
+        m = cls(config, device)
+        for k, v in weights.items():
+            m.set_tensor(k, v)
+        check(_lib.lib().mis_mimi_finalize(m._h))
+        return m
+
+    @classmethod
+    def from_model_directory(cls, model_dir: str, config: MimiConfig | None = None, device: int = 0) -> "Mimi":
+        """Every *.safetensors of the directory (name order; the reference reads tokenizer-e351c8d8-checkpoint125.safetensors) through
+        mimi_sanitize."""
+        from .qwen3tts import read_safetensors
+        files = sorted(f for f in os.listdir(model_dir) if f.endswith(".safetensors"))
+        if not files:
+            raise AudioGenerationError(1, f"no .safetensors file in {model_dir!r}")
+        m = cls(config, device)
+        for fn in files:
+            for k, v in read_safetensors(os.path.join(model_dir, fn)).items():
+                if isinstance(v, np.ndarray):
+                    continue                                             # integer bookkeeping tensors
+                m.set_tensor(*mimi_sanitize(k, v))
+        check(_lib.lib().mis_mimi_finalize(m._h))
+        return m
+
+    @classmethod
+    def from_pretrained(cls, repo_id: str, config: MimiConfig | None = None, device: int = 0) -> "Mimi":
+        """fromPretrained (Mimi.swift:235-335): a local directory only (no network access)."""
+        if os.path.isdir(repo_id):
+            return cls.from_model_directory(repo_id, config, device)
+        raise AudioGenerationError(1, f"model repo {repo_id!r} is not a local directory (no network access)")
+
+    @classmethod
+    def synthetic(cls, config: MimiConfig | None = None, seed: int = 77, device: int = 0) -> "Mimi":
+        from .synthetic import mimi_synthetic_weights
+        config = config or MimiConfig()
+        return cls.from_weights(config, mimi_synthetic_weights(config, seed), device)
+
+    def set_tensor(self, name: str, arr):
+        keep, ptr, dt, shape = _tensor_args(arr)
+        sh = (C.c_int64 * len(shape))(*shape)
+        check(_lib.lib().mis_mimi_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
+
+    # -- AudioCodecModel -----------------------------------------------------------------------------
+    @property
+    def codec_sample_rate(self) -> float:
+        return float(self.config.sample_rate)
+
+    @property
+    def frame_rate(self) -> float:
+        return float(self.config.frame_rate)
+
+    def num_samples(self, n_frames: int) -> int:
+        return int(_lib.lib().mis_mimi_num_samples(self._h, n_frames))
+
+    def decode(self, codes) -> np.ndarray:
+        """Mimi.decode: codes [B, n_q, T] (or [n_q, T]) -> pcm float32 [B, 1, T * 1920]."""
+        cd = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
+        if cd.ndim == 2:
+            cd = cd[None]
+        B, nq, T = cd.shape
+        out = np.empty((B, 1, self.num_samples(T)), np.float32)
+        check(_lib.lib().mis_mimi_decode(self._h, cd.ctypes.data, B, nq, T, out.ctypes.data))
+        return out
+
+    def decode_audio(self, codes) -> np.ndarray:
+        return self.decode(codes)
+
+    def encode_num_frames(self, n_samples: int) -> int:
+        return int(_lib.lib().mis_mimi_encode_num_frames(self._h, n_samples))
+
+    def encode(self, audio, n_q: int | None = None) -> np.ndarray:
+        """Mimi.encode: audio [B, 1, n] (or [B, n] / [n]) -> codes int32 [B, n_q, frames]."""
+        a = np.ascontiguousarray(np.asarray(audio, np.float32))
+        a = a.reshape(1, -1) if a.ndim == 1 else a.reshape(a.shape[0], -1)
+        B, n = a.shape
+        nq = self.config.num_codebooks if n_q is None else int(n_q)
+        out = np.empty((B, nq, self.encode_num_frames(n)), np.int32)
+        check(_lib.lib().mis_mimi_encode(self._h, a.ctypes.data, B, n, nq, out.ctypes.data))
+        return out
+
+    def encode_audio(self, waveform) -> np.ndarray:
+        return self.encode(waveform)
+
+    def debug_tap(self, codes, stage: int) -> np.ndarray:
+        cd = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
+        B, nq, T = cd.shape
+        cap = B * max(self.config.dim_feedforward, 3 * self.config.dimension, self.config.n_filters << len(self.config.ratios)) * \
+            self.num_samples(T)
+        buf = np.empty(cap, np.float32)
+        ch, ln = C.c_int32(), C.c_int64()
+        check(_lib.lib().mis_debug_mimi_decoder_tap(self._h, cd.ctypes.data, B, nq, T, stage, buf.ctypes.data, cap, C.byref(ch), C.byref(ln)))
+        return buf[: B * ch.value * ln.value].reshape(B, ch.value, ln.value).copy()
+
+
+class MimiStreamingDecoder:
+    """MimiStreamingDecoder (Mimi.swift:207-232): reset() and decode_frames(codes [B, n_q, T] or [n_q, T]) -> pcm [B, 1, T * 1920]; the
+    state of every row is kept across calls, a call of several frames equals the same frames one call at a time."""
+
+    def __init__(self, mimi: Mimi, batch: int = 1):
+        self.mimi, self.batch = mimi, batch
+        self.reset()
+
+    def reset(self):
+        check(_lib.lib().mis_mimi_decode_stream_begin(self.mimi._h, self.batch))
+
+    def decode_frames(self, codes) -> np.ndarray:
+        cd = np.ascontiguousarray(np.asarray(codes), dtype=np.int32)
+        if cd.ndim == 2:
+            cd = cd[None]
+        B, nq, T = cd.shape
+        if B != self.batch:
+            raise AudioGenerationError(3, f"stream has {self.batch} rows, got {B}")
+        out = np.empty((B, 1, T * self.mimi.num_samples(1)), np.float32)
+        check(_lib.lib().mis_mimi_decode_stream_step(self.mimi._h, cd.ctypes.data, nq, T, out.ctypes.data))
+        return out

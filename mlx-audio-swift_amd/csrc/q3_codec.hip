@@ -198,26 +198,32 @@ __global__ void __launch_bounds__(64) k_q3_attn(Q3AttnArgs a) {
     for (int d = 0; d < D; ++d) o[d] = 0.0f;
     float m = -INFINITY, l = 0.0f;
     const int t_hi = a.pos0 + min(blockIdx.x * 64 + 63, a.Tq - 1);
-    for (int j0 = 0; j0 <= t_hi; j0 += 64) {
+    // window: lowest key of this query and of the block's first query (keys below a query's bound are skipped; the online softmax
+    // starts at its first valid key, so where the tiles start does not change a query's operation order)
+    auto key_lo = [&](int p) { return a.window > 0 ? max(0, (p / a.win_group) * a.win_group - a.window) : 0; };
+    const int lo = key_lo(t), j_first = (key_lo(a.pos0 + blockIdx.x * 64) / 64) * 64;
+    for (int j0 = j_first; j0 <= t_hi; j0 += 64) {
         __syncthreads();
         {   // thread tid stages key j0 + tid
             const int j = j0 + tid;
             const bool kin = j < Tk;
+            const int jc = a.ring ? j % a.ring : j;
 #pragma unroll
             for (int i = 0; i < D / 2; ++i) {
                 float inv = 1.0f / powf(a.theta, (float)(2 * i) / (float)D);
                 float ang = (float)j * inv, c = cosf(ang), s = sinf(ang);
-                float x1 = kin ? kb[(size_t)i * a.kv_ld + j] : 0.0f, x2 = kin ? kb[(size_t)(i + D / 2) * a.kv_ld + j] : 0.0f;
+                float x1 = kin ? kb[(size_t)i * a.kv_ld + jc] : 0.0f, x2 = kin ? kb[(size_t)(i + D / 2) * a.kv_ld + jc] : 0.0f;
                 Ks[i][tid] = x1 * c - x2 * s;
                 Ks[i + D / 2][tid] = x2 * c + x1 * s;
             }
 #pragma unroll
-            for (int d = 0; d < D; ++d) Vs[d][tid] = kin ? vb[(size_t)d * a.kv_ld + j] : 0.0f;
+            for (int d = 0; d < D; ++d) Vs[d][tid] = kin ? vb[(size_t)d * a.kv_ld + jc] : 0.0f;
         }
         __syncthreads();
         const int jn = min(64, t_hi - j0 + 1);
         for (int jj = 0; jj < jn; ++jj) {
             if (j0 + jj > t) break;                                   // causal
+            if (j0 + jj < lo) continue;                               // window
             float sc = 0.0f;
 #pragma unroll
             for (int d = 0; d < D; ++d) sc += q[d] * Ks[d][jj];

@@ -30,6 +30,9 @@ struct Q3AttnArgs {
     float* out; int64_t o_bs; int o_ld;
     int H, Hkv, Tq, pos0;
     float theta, scale;
+    // optional, zero = off (Mimi's streaming decoder): the query at position t sees keys from max(0, (t / win_group) * win_group - window)
+    // on (the per-step cache trim of Transformer.swift:155-166), and key j lives in column j % ring of k / v (a ring cache)
+    int window, win_group, ring;
 };
 void launch_q3_attn(const Q3AttnArgs& a, int head_dim /*16, 32, 64*/, int batch, hipStream_t s);
 // normalisation over the channel axis of [B][C][T] data (row stride ld); rms = 1: RMSNorm (bias unused), 0: LayerNorm
@@ -38,7 +41,8 @@ void launch_q3_norm_ct(const float* x, float* y, const float* w, const float* bi
 
 // q3_reference.hip: speaker encoder (ECAPA-TDNN) + speech-tokenizer encoder (Mimi) of the in-context voice-cloning path
 struct mis_q3ref;
-mis_q3ref* q3ref_create(const mis_qwen3tts_reference_config* cfg, int device, hipStream_t s);
+// enc_prefix: key prefix of the tokenizer-encoder tensors ("encoder_model." inside a Qwen3-TTS checkpoint, "" for a Mimi handle)
+mis_q3ref* q3ref_create(const mis_qwen3tts_reference_config* cfg, int device, hipStream_t s, const char* enc_prefix = "encoder_model.");
 void q3ref_destroy(mis_q3ref*);
 bool q3ref_owns(const char* name);                                   // "speaker_encoder.*" / "encoder_model.*"
 void q3ref_set_tensor(mis_q3ref*, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim);

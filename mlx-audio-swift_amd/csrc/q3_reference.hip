@@ -49,6 +49,7 @@ struct mis_q3ref {
     std::vector<TL> tlayers;
     struct VqGroup { Lin in_proj; size_t embT = 0, emb = 0, e2h = 0; int nq = 0; } vq[2];
     int ds_stride = 1;
+    std::string enc_prefix;
 };
 
 // ---------------------------------------------------------------------------- kernels
@@ -220,10 +221,10 @@ __global__ void __launch_bounds__(256) k_ref_rvq(const float* __restrict__ z, in
 }
 
 // ---------------------------------------------------------------------------- handle
-mis_q3ref* q3ref_create(const mis_qwen3tts_reference_config* cfg, int device, hipStream_t s) {
+mis_q3ref* q3ref_create(const mis_qwen3tts_reference_config* cfg, int device, hipStream_t s, const char* enc_prefix) {
     MIS_REQUIRE(cfg, MIS_ERR_INVALID_INPUT, "null reference config");
     mis_q3ref* r = new mis_q3ref();
-    r->device = device; r->s = s; r->cfg = *cfg;
+    r->device = device; r->s = s; r->cfg = *cfg; r->enc_prefix = enc_prefix ? enc_prefix : "";
     r->has_spk = cfg->spk_n_blocks > 0;
     r->has_enc = cfg->enc_num_filters > 0;
     try {
@@ -356,7 +357,7 @@ void q3ref_finalize(mis_q3ref* r) {
         r->spk_fc = matvec(P + "fc", cf.spk_enc_dim, 2 * ch[nb - 1]);
     }
     if (r->has_enc) {
-        const std::string P = "encoder_model.";
+        const std::string& P = r->enc_prefix;
         const int nf = cf.enc_num_filters;
         r->enc_init = conv(P + "encoder.init_conv1d.conv.conv", nf, cf.enc_kernel_size, cf.enc_audio_channels, 1, true);
         r->enc_layers.clear();

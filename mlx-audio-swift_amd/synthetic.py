@@ -324,3 +324,71 @@ def qwen3tts_reference_synthetic_weights(cfg, seed: int = 717):
                 usage = (1.0 + np.abs(t((en.codebook_size,), 1.0))).astype(np.float32)
                 yield q + ".cluster_usage", usage
                 yield q + ".embedding_sum", (t((en.codebook_size, en.codebook_dim), 1.0 / (i + 1)) * usage[:, None]).astype(np.float32)
+
+
+def mimi_synthetic_weights(cfg, seed: int = 77) -> dict:
+    """Synthetic Mimi checkpoint in the post-sanitize key layout (codecs.Mimi.from_weights): encoder, both transformers, the split
+    RVQ (codebooks, input and output projections), upsample and SEANet decoder.  cfg: codecs.MimiConfig.  name -> float32 array."""
+    W, key = {}, [seed * 100000]
+
+    def t(shape, amp):
+        key[0] += 1
+        return synth_tensor(key[0], shape, amp)
+
+    def conv(p, co, k, ci, bias=True, gain=1.0):
+        W[p + ".weight"] = t((co, k, ci), gain * math.sqrt(3.0 / (k * ci)))
+        if bias:
+            W[p + ".bias"] = t((co,), 0.05)
+
+    def transformer(P, D, I):
+        for li in range(cfg.num_layers):
+            p = f"{P}.transformer.layers.{li}"
+            for nm in ("norm1", "norm2"):
+                W[f"{p}.{nm}.weight"] = (1.0 + t((D,), 0.2)).astype(np.float32)
+                W[f"{p}.{nm}.bias"] = t((D,), 0.1)
+            W[p + ".self_attn.in_proj.weight"] = t((3 * D, D), math.sqrt(3.0 / D))
+            W[p + ".self_attn.out_proj.weight"] = t((D, D), math.sqrt(3.0 / D))
+            W[p + ".gating.linear1.weight"] = t((I, D), math.sqrt(3.0 / D))
+            W[p + ".gating.linear2.weight"] = t((D, I), math.sqrt(3.0 / I))
+            W[p + ".layer_scale_1.scale"] = (0.3 + t((D,), 0.1)).astype(np.float32)
+            W[p + ".layer_scale_2.scale"] = (0.3 + t((D,), 0.1)).astype(np.float32)
+    nf, mult, D, qd, bins = cfg.n_filters, 1, cfg.dimension, cfg.quantizer_dim, cfg.bins
+    conv("encoder.init_conv1d.conv.conv", nf, cfg.kernel_size, 1, gain=2.0)
+    for li, ratio in enumerate(reversed(cfg.ratios)):
+        p = f"encoder.layers.{li}"
+        dim = mult * nf
+        for ri in range(cfg.n_residual_layers):
+            conv(f"{p}.residuals.{ri}.block.0.conv.conv", dim // cfg.compress, cfg.residual_kernel_size, dim, gain=1.3)
+            conv(f"{p}.residuals.{ri}.block.1.conv.conv", dim, 1, dim // cfg.compress, gain=0.7)
+        conv(p + ".downsample.conv.conv", 2 * dim, 2 * ratio, dim, gain=1.3)
+        mult *= 2
+    conv("encoder.final_conv1d.conv.conv", D, cfg.last_kernel_size, mult * nf, gain=1.3)
+    transformer("encoder_transformer", D, cfg.dim_feedforward)
+    conv("downsample.conv.conv.conv", D, 2 * cfg.stride, D, bias=False)
+    for grp, nq in (("rvq_first", 1), ("rvq_rest", cfg.num_codebooks - 1)):
+        p = f"quantizer.{grp}"
+        W[p + ".input_proj.weight"] = t((qd, 1, D), math.sqrt(3.0 / D))
+        for i in range(nq):
+            q = f"{p}.vq.layers.{i}.codebook"
+            usage = (1.0 + np.abs(t((bins,), 1.0))).astype(np.float32)
+            W[q + ".cluster_usage"] = usage
+            W[q + ".embedding_sum"] = (t((bins, qd), 1.0 / (i + 1)) * usage[:, None]).astype(np.float32)
+    key[0] = seed * 100000 + 50000                                   # the decoder half
+    for grp in ("rvq_first", "rvq_rest"):
+        W[f"quantizer.{grp}.output_proj.weight"] = t((D, 1, qd), math.sqrt(3.0 / qd))
+    W["upsample.convtr.convtr.convtr.weight"] = t((D, 2 * cfg.stride, 1), 0.8)
+    transformer("decoder_transformer", D, cfg.dim_feedforward)
+    mult = 1 << len(cfg.ratios)
+    conv("decoder.init_conv1d.conv.conv", mult * nf, cfg.kernel_size, D, gain=1.3)
+    for li, r in enumerate(cfg.ratios):
+        p = f"decoder.layers.{li}"
+        cin = mult * nf
+        cout = cin // 2
+        conv(p + ".upsample.convtr.convtr", cout, 2 * r, cin, gain=1.3 * math.sqrt(r))
+        for ri in range(cfg.n_residual_layers):
+            q = f"{p}.residuals.{ri}"
+            conv(q + ".block.0.conv.conv", cout // cfg.compress, cfg.residual_kernel_size, cout, gain=1.3)
+            conv(q + ".block.1.conv.conv", cout, 1, cout // cfg.compress, gain=0.7)
+        mult //= 2
+    conv("decoder.final_conv1d.conv.conv", 1, cfg.last_kernel_size, nf)
+    return W
