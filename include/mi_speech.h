@@ -626,6 +626,62 @@ mis_status mis_mimi_decode_stream_step(mis_mimi*, const int32_t* codes, int n_q,
 mis_status mis_mimi_decode_stream_end(mis_mimi*);
 
 /* ------------------------------------------------------------------------------------------
+ * Marvis TTS (CSM): backbone LM + depth decoder over Mimi codes.  Replaces CSMModel.generateFrame
+ * (Sources/MLXAudioTTS/Models/Marvis/CSMModel.swift:467-526), CSMLlamaModel (CSMLlamaModel.swift) and the generate loop of
+ * MarvisTTSModel.swift:402-477.  Rows of a batch are independent utterances (the reference runs batch 1).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_marvis mis_marvis;
+typedef struct {
+    mis_lm_config backbone;        /* CSMLlamaConfiguration of the backbone; vocab_size / qk_norm / rope_* flags are set by the engine */
+    mis_lm_config decoder;         /* ... of the depth decoder */
+    int32_t text_vocab_size, audio_vocab_size, audio_num_codebooks;   /* K = audio_num_codebooks <= 32, audio_vocab_size <= 4096 */
+} mis_marvis_config;
+typedef struct {
+    int32_t  max_frames;           /* 0 = 750 (60 s at 12.5 Hz, MarvisTTSModel.swift:402); at most 750 */
+    int32_t  codebooks;            /* Cb = min(K, qualityLevel) (:17-22); 0 = K; outside 1..K: MIS_ERR_INVALID_INPUT */
+    float    temperature;          /* 0 => arg-max; the reference samples with TopPSampler(temperature 0.9, topP 0.8) (:429) */
+    float    top_p;
+    uint64_t seed;                 /* mis-sampler-v1 keyed by (seed, row_offset + row, frame * K + codebook) */
+    int64_t  row_offset;
+} mis_marvis_params;
+mis_status mis_marvis_create(const mis_marvis_config*, int device, mis_marvis** out);
+/* post-sanitize names (MarvisTTSModel.sanitize :225-262): model.backbone.layers.N.*, model.backbone.norm.weight, model.decoder.*,
+ * model.text_embeddings.weight [text_vocab, D], model.audio_embeddings.weight [audio_vocab * K, D], model.projection.weight [Dd, D],
+ * model.codebook0_head.weight [audio_vocab, D], model.audio_head [K - 1, Dd, audio_vocab].  q_proj / k_proj rows are de-interleaved per
+ * head when set (the engine rotates halves; CSM rotates pairs). */
+mis_status mis_marvis_set_tensor(mis_marvis*, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim);
+/* a module of an MLX-quantised checkpoint (`name` = its .weight key): Linear layers of both LMs and codebook0_head stream as 8 / 4-bit
+ * codes where the GEMMs take the format (group 64, bf16 / f16 scales; otherwise dequantised at load); the embeddings and projection are
+ * dequantised at load */
+mis_status mis_marvis_set_tensor_quantized(mis_marvis*, const char* name, const uint32_t* wq, const void* scales, const void* biases,
+                                           mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits);
+mis_status mis_marvis_init_synthetic(mis_marvis*, uint64_t seed);
+mis_status mis_marvis_init_synthetic_quantized(mis_marvis*, uint64_t seed, int bits);
+mis_status mis_marvis_finalize(mis_marvis*);
+void       mis_marvis_destroy(mis_marvis*);
+mis_tts*   mis_marvis_backbone(mis_marvis*);          /* borrowed: the two LM handles (introspection, e.g. mis_tts_native_quant_bits) */
+mis_tts*   mis_marvis_decoder(mis_marvis*);
+int        mis_marvis_launches_per_frame(const mis_marvis*);   /* nodes of the last call's captured frame graph (MIS_NO_GRAPH: the expected count) */
+/* Frames only.  tokens int32 [batch, P, K + 1] / mask u8 [batch, P, K + 1]: a text position has its id in the last column and mask
+ * there only, an audio position K codes and mask on those (:70-134); prompt_lens[batch] < 2048 - 750.  row_max_frames (may be NULL):
+ * per-row frame caps.  A frame whose Cb codes are all 0 ends its row and is not kept (:444-447).  Outputs: *codes_out (mis_free) int32
+ * [batch, *codes_stride, Cb]; n_frames[batch].  Bad lengths, Cb, or ids outside their tables: MIS_ERR_INVALID_INPUT before any launch. */
+mis_status mis_marvis_generate_codes(mis_marvis*, const int32_t* tokens, const uint8_t* mask, const int32_t* prompt_lens, int P, int batch,
+                                     const mis_marvis_params* params, const int32_t* row_max_frames, int32_t** codes_out,
+                                     int64_t* codes_stride, int32_t* n_frames);
+/* Frames + audio through a borrowed Mimi (same device; its decode-stream session must be closed; 2 <= Cb <= its quantizers).  *pcm_out
+ * (mis_free) f32 [batch, *pcm_stride], pcm_lens[batch] = n_frames * mis_mimi_num_samples(1).  A row's audio is the STREAMING decode of its
+ * frames in both forms, so they return identical samples.  on_event == NULL or chunk_frames <= 0: all frames, then the audio (one
+ * MIS_EVENT_AUDIO per row if on_event).  on_event and chunk_frames > 0 (streamingInterval * 12.5 frames, :403,464-470): Mimi's stream
+ * step of the whole batch runs on Mimi's stream while the frame loop continues; MIS_EVENT_TOKEN (payload: the frame's Cb codes) per
+ * frame, MIS_EVENT_AUDIO per row and chunk, MIS_EVENT_INFO per row when the loop ends, then the remainder.  cancel_flag is polled every
+ * 8 frames -> MIS_ERR_CANCELLED.  codes_out / codes_stride / n_frames may be NULL. */
+mis_status mis_marvis_generate(mis_marvis*, mis_mimi* mimi, const int32_t* tokens, const uint8_t* mask, const int32_t* prompt_lens, int P,
+                               int batch, const mis_marvis_params* params, const int32_t* row_max_frames, float** pcm_out,
+                               int64_t* pcm_stride, int64_t* pcm_lens, int32_t** codes_out, int64_t* codes_stride, int32_t* n_frames,
+                               int chunk_frames, mis_event_cb on_event, void* user, const volatile int* cancel_flag);
+
+/* ------------------------------------------------------------------------------------------
  * Log-mel / STFT front end.  Replaces WhisperAudio.logMelSpectrogram / encoderFeatures
  * (Sources/MLXAudioSTT/Models/Whisper/WhisperAudio.swift:38-87) and computeMelSpectrogram
  * (Sources/MLXAudioCore/DSP.swift:230-273): reflect pad, window, rfft, |.|^2, mel filterbank

@@ -53,6 +53,20 @@ mis_status mis_debug_mimi_decoder_tap(mis_mimi* m, const int32_t* codes, int bat
 mis_status mis_debug_token_engine(mis_tts* lm, const int32_t* prompt, int n_prompt, int n_new, int xcds, const mis_gen_params* sampling,
                                   int stop_id, int32_t* next_tokens, float* logits_out, float* hidden_out, int32_t* counts, double* ms_out);
 
+/* csrc/marvis.hip, tests.  forced_logits: the Marvis frame loop TEACHER-FORCED for F frames - the loop samples as usual but continues
+ * from forced int32 [batch, F, Cb] (Cb = params->codebooks, or all) - returning logits_out f32 [batch, F, Cb, audio_vocab] of every
+ * (frame, codebook) (frames past a row's end stay 0), sampled_out int32 [batch, F, Cb] (may be NULL: what the sampler chose) and
+ * n_frames[batch] under the end rule applied to the forced codes (an all-zero frame ends the row and is not counted).
+ * sample_logits: the loop's sampler (mis-sampler-v1, RNG step = frame * K + slot) on given logits f32 [batch, vocab] (rounded to bf16).
+ * rope_tables: cos / sin f32 [n_pos, head_dim / 2] of CSMLlama3ScaledRoPE (host arithmetic only: no GPU needed). */
+mis_status mis_debug_marvis_forced_logits(mis_marvis* c, const int32_t* tokens, const uint8_t* mask, const int32_t* prompt_lens, int P,
+                                          int batch, const mis_marvis_params* params, const int32_t* forced, int F, float* logits_out,
+                                          int32_t* sampled_out, int32_t* n_frames);
+mis_status mis_debug_marvis_sample_logits(int device, const float* logits, int batch, int vocab, float temperature, float top_p,
+                                          uint64_t seed, int64_t row_offset, int frame, int slot, int K, int32_t* tokens_out);
+mis_status mis_debug_marvis_rope_tables(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor,
+                                        float old_context_len, int n_pos, float* cos_out, float* sin_out);
+
 #ifdef __cplusplus
 }
 #endif

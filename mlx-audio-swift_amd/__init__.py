@@ -13,6 +13,7 @@ the Swift shim a maintainer would add):
     tts.LlamaTTSModel      <-> class LlamaTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Llama/LlamaTTS.swift)
     soprano.SopranoModel   <-> class SopranoModel : SpeechGenerationModel  (MLXAudioTTS/Models/Soprano/Soprano.swift)
     qwen3tts.Qwen3TTSModel <-> class Qwen3TTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Qwen3TTS/Qwen3TTS.swift)
+    marvis.MarvisTTSModel  <-> class MarvisTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Marvis/MarvisTTSModel.swift)
     stt.WhisperModel       <-> class WhisperModel : STTGenerationModel   (MLXAudioSTT/Models/Whisper/WhisperModel.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
@@ -32,6 +33,8 @@ from .orpheus import deinterleave, parse_output  # noqa: F401
 from .soprano import SopranoModel, SopranoConfiguration  # noqa: F401
 from .qwen3tts import (Qwen3TTSModel, Qwen3TTSConfiguration, Qwen3TTSDecoderConfiguration, Qwen3TTSGenerateParameters,  # noqa: F401
                        PreparedPrompt)
+from .marvis import (MarvisTTSModel, CSMModelArgs, CSMLlamaConfiguration, MarvisGenerateParameters, QualityLevel,  # noqa: F401
+                     marvis_sanitize, marvis_checkpoint_plan, tokenize_text_segment, tokenize_audio, tokenize_segment, text_pieces)
 from . import dsp  # noqa: F401
 from .stt import WhisperModel, WhisperConfig, STTGenerateParameters, STTOutput  # noqa: F401
 

@@ -105,6 +105,16 @@ class MimiConfigC(C.Structure):
                 ("num_quantizers", C.c_int32), ("bins", C.c_int32), ("quantizer_dim", C.c_int32)]
 
 
+class MarvisConfigC(C.Structure):
+    _fields_ = [("backbone", LmConfigC), ("decoder", LmConfigC), ("text_vocab_size", C.c_int32), ("audio_vocab_size", C.c_int32),
+                ("audio_num_codebooks", C.c_int32)]
+
+
+class MarvisParamsC(C.Structure):
+    _fields_ = [("max_frames", C.c_int32), ("codebooks", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float),
+                ("seed", C.c_uint64), ("row_offset", C.c_int64)]
+
+
 class EncodecConfigC(C.Structure):
     _fields_ = [("audio_channels", C.c_int32), ("num_filters", C.c_int32), ("kernel_size", C.c_int32),
                 ("num_residual_layers", C.c_int32), ("dilation_growth_rate", C.c_int32), ("codebook_size", C.c_int32),
@@ -303,6 +313,20 @@ SYMBOLS = {
     "mis_mimi_decode_stream_begin": (C.c_int, [_P, C.c_int]),
     "mis_mimi_decode_stream_step": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "mis_mimi_decode_stream_end": (C.c_int, [_P]),
+    "mis_marvis_create": (C.c_int, [C.POINTER(MarvisConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_marvis_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_marvis_set_tensor_quantized": (C.c_int, [_P, C.c_char_p, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mis_marvis_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_marvis_init_synthetic_quantized": (C.c_int, [_P, C.c_uint64, C.c_int]),
+    "mis_marvis_finalize": (C.c_int, [_P]),
+    "mis_marvis_destroy": (None, [_P]),
+    "mis_marvis_backbone": (_P, [_P]),
+    "mis_marvis_decoder": (_P, [_P]),
+    "mis_marvis_launches_per_frame": (C.c_int, [_P]),
+    "mis_marvis_generate_codes": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(MarvisParamsC), _P, C.POINTER(_P),
+                                            C.POINTER(C.c_int64), _P]),
+    "mis_marvis_generate": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(MarvisParamsC), _P, C.POINTER(_P),
+                                      C.POINTER(C.c_int64), _P, C.POINTER(_P), C.POINTER(C.c_int64), _P, C.c_int, _P, _P, _P]),
 }
 
 # diagnostics / test scaffolding: include/mi_speech_debug.h (not part of the product surface)
@@ -317,6 +341,10 @@ DEBUG_SYMBOLS = {
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int64)]),
+    "mis_debug_marvis_forced_logits": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(MarvisParamsC), _P, C.c_int, _P, _P, _P]),
+    "mis_debug_marvis_sample_logits": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_int,
+                                                 C.c_int, C.c_int, _P]),
+    "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 
 _lib = None

@@ -115,6 +115,21 @@ bool tts_internal_shared_device(const mis_tts* c);
 mis_tts* soprano_internal_lm(mis_soprano* c);
 void soprano_internal_set_group_batch(mis_soprano* c, int batch);   // group entry points: the request's batch over all shards (0 = leave)
 void tts_internal_set_decode_ms(mis_tts* c, double ms);
+// Marvis / CSM (marvis.hip): the handle's cos / sin tables come from marvis_rope_tables (CSMLlama3ScaledRoPE.ropeInit / applyScaling,
+// CSMLlamaModel.swift:69-104) instead of build_rope_tables - the two agree in exact arithmetic, not in float32.  Set before the first reset.
+void tts_internal_set_rope_csm(mis_tts* c, bool on);
+void marvis_rope_tables(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor, float old_context_len,
+                        int n_pos, float* cos_out /*[n_pos][head_dim/2]*/, float* sin_out);
+
+// mimi.hip hooks used by marvis.hip: the open stream session's next n_frames frames of every row, codes (b, q, t) at
+// codes_dev[b*cs_b + q*cs_q + t*cs_t] -> wav_dev[b*wav_stride + ...], enqueued on the handle's stream WITHOUT a host synchronisation
+struct mis_mimi;
+hipStream_t mimi_internal_stream(mis_mimi* m);
+int mimi_internal_device(const mis_mimi* m);
+int mimi_internal_num_quantizers(const mis_mimi* m);
+bool mimi_internal_stream_open(const mis_mimi* m);
+void mimi_internal_stream_step_device(mis_mimi* m, const int32_t* codes_dev, int64_t cs_b, int64_t cs_q, int64_t cs_t, int n_q, int n_frames,
+                                      float* wav_dev, int64_t wav_stride);
 int soprano_internal_device(const mis_soprano* c);
 int whisper_internal_device(const mis_whisper* c);
 void whisper_internal_set_shared_device(mis_whisper* c, bool shared);

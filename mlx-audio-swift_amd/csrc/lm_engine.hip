@@ -81,6 +81,7 @@ struct mis_tts {
     uint64_t graph_key = 0;
     bool use_graph = true;
     bool borrowed_stream = false;
+    bool rope_csm = false;           // cos / sin tables of CSMLlama3ScaledRoPE (tts_internal_set_rope_csm) instead of build_rope_tables' own
     int profiling = 0;
     mis_tts_timing timing{};
     SamplerParams sp{};
@@ -513,7 +514,8 @@ static void build_rope_tables(mis_tts* c) {
         inv[i] = 1.0f / ff;
     }
     std::vector<float> cs((size_t)c->Smax * half), sn((size_t)c->Smax * half);
-    for (int p = 0; p < c->Smax; ++p)
+    if (c->rope_csm) marvis_rope_tables(D, base, factor, low, high, old, c->Smax, cs.data(), sn.data());
+    else for (int p = 0; p < c->Smax; ++p)
         for (int i = 0; i < half; ++i) {
             float ang = (float)p * inv[i];
             cs[(size_t)p * half + i] = (float)cos((double)ang);
@@ -1941,6 +1943,9 @@ void tts_internal_prefill_rows(mis_tts* c, const bf16_t* rows, const int32_t* le
 void tts_internal_use_stream(mis_tts* c, hipStream_t s) {
     if (c->stream && !c->borrowed_stream && c->stream != s) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
     c->stream = s; c->borrowed_stream = true;
+}
+void tts_internal_set_rope_csm(mis_tts* c, bool on) {
+    if (c->rope_csm != on) { c->rope_csm = on; c->rope_cos.release(); c->rope_sin.release(); }      // rebuilt by the next reset
 }
 void tts_internal_enqueue_layers(mis_tts* c, const bf16_t* table, int table_rows, const int32_t* ids) { enqueue_layers(c, table, table_rows, ids); }
 void tts_internal_enqueue_head(mis_tts* c, const bf16_t* head_packed) { enqueue_lm_head(c, head_packed); }

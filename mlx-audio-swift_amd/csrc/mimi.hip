@@ -633,6 +633,24 @@ extern "C" mis_status mis_mimi_decode_stream_step(mis_mimi* m, const int32_t* co
     MIS_API_END
 }
 
+// hooks for marvis.hip (kernels.h): the open session's next frames from device codes, enqueued on the handle's stream, no synchronisation
+hipStream_t mimi_internal_stream(mis_mimi* m) { return m->stream; }
+int mimi_internal_device(const mis_mimi* m) { return m->device; }
+int mimi_internal_num_quantizers(const mis_mimi* m) { return m->cfg.num_quantizers; }
+bool mimi_internal_stream_open(const mis_mimi* m) { return m->st.open; }
+void mimi_internal_stream_step_device(mis_mimi* m, const int32_t* codes_dev, int64_t cs_b, int64_t cs_q, int64_t cs_t, int n_q, int n_frames,
+                                      float* wav_dev, int64_t wav_stride) {
+    MIS_REQUIRE(m && m->st.open, MIS_ERR_NOT_INITIALIZED, "no Mimi stream is open (mis_mimi_decode_stream_begin)");
+    mimi_check_codes(m, codes_dev, m->st.batch, n_q, n_frames, wav_dev);
+    HIP_CHECK(hipSetDevice(m->device));
+    const int64_t spf = mis_mimi_num_samples(m, 1);
+    for (int f0 = 0; f0 < n_frames; f0 += MIMI_CHUNK) {
+        const int Tn = std::min(MIMI_CHUNK, n_frames - f0);
+        int C; int64_t Tt;
+        mimi_run(m, codes_dev + (int64_t)f0 * cs_t, cs_b, cs_q, cs_t, n_q, m->st.batch, Tn, wav_dev + f0 * spf, wav_stride, 0, &C, &Tt, &m->st);
+    }
+}
+
 extern "C" mis_status mis_mimi_decode_stream_end(mis_mimi* m) {
     MIS_API_BEGIN
     MIS_REQUIRE(m, MIS_ERR_INVALID_INPUT, "null handle");
