@@ -792,6 +792,50 @@ mis_status mis_stt_whisper_generate_stream(mis_whisper*, const float* pcm, const
                                            int32_t** tokens_out, int64_t* tokens_stride, int32_t* n_tokens);
 
 /* ------------------------------------------------------------------------------------------
+ * Moonshine STT (Sources/MLXAudioSTT/Models/Moonshine/MoonshineModel.swift:112-411, MoonshineConfig.swift:3-125): raw 16 kHz samples ->
+ * strided conv stem -> encoder -> decoder with cached self / cross K/V -> greedy ids.  No mel front end: the work follows the audio
+ * length, and a batch is RAGGED - every row has its own frame count T3 = ((T1 - 7) / 3 + 1 - 3) / 2 + 1, T1 = (n - 127) / 64 + 1;
+ * samples past lens[b] never influence a result.  Rows shorter than 895 samples (T3 < 1) or longer than 480000 (30 s) and batches above
+ * 64 rows are MIS_ERR_INVALID_INPUT.  f32 through GroupNorm, bf16 storage / f32 accumulation behind it (f32 checkpoints are rounded to
+ * bf16 once, at finalize); logits f32.  hidden_size <= 512 (a multiple of 32), head_dim <= 64 (heads are zero-padded to 64 at load).
+ * Tokenizer and text stay on the host (MoonshineTokenizer, :7-69).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_moonshine mis_moonshine;
+/* MoonshineConfig.swift:3-25; *_hidden_act: 0 gelu, 1 silu (the decoder MLP is the SiLU gate whatever decoder_hidden_act says, :223-227;
+ * encoder_hidden_act 1 is not implemented) */
+typedef struct {
+    int32_t vocab_size, hidden_size, intermediate_size;
+    int32_t encoder_num_hidden_layers, decoder_num_hidden_layers, encoder_num_attention_heads, decoder_num_attention_heads;
+    int32_t encoder_num_key_value_heads, decoder_num_key_value_heads, encoder_hidden_act, decoder_hidden_act;
+    int32_t max_position_embeddings, attention_bias;
+    float   partial_rotary_factor, rope_theta;
+    int32_t bos_token_id, eos_token_id, decoder_start_token_id, tie_word_embeddings;
+} mis_moonshine_config;
+mis_status mis_moonshine_create(const mis_moonshine_config*, int device, mis_moonshine** out);
+/* published key layout ("model.encoder.conv1.weight" [d, 1, 127], conv weights [out, in, k], "proj_out.weight" ignored when tied);
+ * host pointers; MoonshineModel.sanitize, :443-459 */
+mis_status mis_moonshine_set_tensor(mis_moonshine*, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim);
+mis_status mis_moonshine_init_synthetic(mis_moonshine*, uint64_t seed);
+mis_status mis_moonshine_finalize(mis_moonshine*);
+void       mis_moonshine_destroy(mis_moonshine*);
+/* lens[batch] samples -> frames_out[batch] encoder frames T3 (0: too short).  Host arithmetic; the handle may be NULL. */
+mis_status mis_moonshine_frames(const mis_moonshine*, const int64_t* lens, int batch, int32_t* frames_out);
+/* MoonshineEncoder (+ the cross-attention K/V of every decoder layer): pcm f32 [batch, stride], lens[batch] valid samples (NULL =
+ * stride); enc_out f32 [batch, max T3, hidden] (zeros behind a row's own T3) or NULL.  Resets the decoder state. */
+mis_status mis_moonshine_encode(mis_moonshine*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* enc_out);
+/* empties the self-attention caches; max_positions: decoder positions to provide for (<= 2048; 0 = max_position_embeddings) */
+mis_status mis_moonshine_decoder_reset(mis_moonshine*, int max_positions);
+/* one teacher-forced decoder token per row through the caches (MoonshineDecoder with one new position); logits_out f32 [batch, vocab] or NULL */
+mis_status mis_moonshine_decoder_forward(mis_moonshine*, const int32_t* tokens, float* logits_out);
+/* kernel launches of one decoder step of the generate loop (8 per layer + vocabulary projection + arg-max) */
+int        mis_moonshine_launches_per_step(const mis_moonshine*);
+/* MoonshineModel.generate (:374-411) for a ragged batch: decoder_start_token_id, arg-max per step, eos_token_id ends a row and is not
+ * kept, at most max_tokens ids (<= 0: 200; <= 2047).  Only max_tokens and temperature of mis_stt_params are read; temperature > 0 is
+ * MIS_ERR_INVALID_INPUT (sampling is not mirrored).  *tokens_out (mis_free) int32 [batch, *tokens_stride], n_tokens[batch]. */
+mis_status mis_stt_moonshine_generate(mis_moonshine*, const float* pcm, const int64_t* lens, int batch, int64_t stride,
+                                      const mis_stt_params*, int32_t** tokens_out, int64_t* tokens_stride, int32_t* n_tokens);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

@@ -67,6 +67,12 @@ mis_status mis_debug_marvis_sample_logits(int device, const float* logits, int b
 mis_status mis_debug_marvis_rope_tables(int head_dim, float theta, float factor, float low_freq_factor, float high_freq_factor,
                                         float old_context_len, int n_pos, float* cos_out, float* sin_out);
 
+/* csrc/moonshine.hip, tests: stage outputs of the Moonshine stem for a ragged batch (arguments of mis_moonshine_encode).  stage 0 conv1 + tanh
+ * (f32), 1 GroupNorm, 2 gelu(conv2), 3 gelu(conv3).  dims[0] frames per row as the engine lays the batch out, dims[1] channels; out f32
+ * [batch, dims[0], dims[1]] (a row's own frames first) or NULL for the dims alone.  Leaves the handle without encoder output. */
+mis_status mis_debug_moonshine_stem_tap(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, int stage,
+                                        float* out, int64_t capacity, int64_t* dims);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ the Swift shim a maintainer would add):
     qwen3tts.Qwen3TTSModel <-> class Qwen3TTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Qwen3TTS/Qwen3TTS.swift)
     marvis.MarvisTTSModel  <-> class MarvisTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Marvis/MarvisTTSModel.swift)
     stt.WhisperModel       <-> class WhisperModel : STTGenerationModel   (MLXAudioSTT/Models/Whisper/WhisperModel.swift)
+    moonshine.MoonshineModel <-> class MoonshineModel : STTGenerationModel (MLXAudioSTT/Models/Moonshine/MoonshineModel.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -37,6 +38,8 @@ from .marvis import (MarvisTTSModel, CSMModelArgs, CSMLlamaConfiguration, Marvis
                      marvis_sanitize, marvis_checkpoint_plan, tokenize_text_segment, tokenize_audio, tokenize_segment, text_pieces)
 from . import dsp  # noqa: F401
 from .stt import WhisperModel, WhisperConfig, STTGenerateParameters, STTOutput  # noqa: F401
+from .moonshine import (MoonshineModel, MoonshineConfig, MoonshineTokenizer, moonshine_sanitize, moonshine_frames,  # noqa: F401
+                        moonshine_rotary_dim)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

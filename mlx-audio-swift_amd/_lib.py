@@ -137,6 +137,15 @@ class WhisperConfigC(C.Structure):
                                          "max_target_positions")]
 
 
+class MoonshineConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden_size", "intermediate_size", "encoder_num_hidden_layers",
+                                          "decoder_num_hidden_layers", "encoder_num_attention_heads", "decoder_num_attention_heads",
+                                          "encoder_num_key_value_heads", "decoder_num_key_value_heads", "encoder_hidden_act",
+                                          "decoder_hidden_act", "max_position_embeddings", "attention_bias")]
+                + [("partial_rotary_factor", C.c_float), ("rope_theta", C.c_float)]
+                + [(n, C.c_int32) for n in ("bos_token_id", "eos_token_id", "decoder_start_token_id", "tie_word_embeddings")])
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -253,6 +262,17 @@ SYMBOLS = {
     "mis_qwen3tts_group_generate": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(Qwen3TTSParamsC), _P,
                                               C.POINTER(_P), C.POINTER(C.c_int64), _P, C.POINTER(_P), C.POINTER(C.c_int64), _P,
                                               C.c_int, EVENT_CB, _P, _P]),
+    "mis_moonshine_create": (C.c_int, [C.POINTER(MoonshineConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_moonshine_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_moonshine_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_moonshine_finalize": (C.c_int, [_P]),
+    "mis_moonshine_destroy": (None, [_P]),
+    "mis_moonshine_frames": (C.c_int, [_P, _P, C.c_int, _P]),
+    "mis_moonshine_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
+    "mis_moonshine_decoder_reset": (C.c_int, [_P, C.c_int]),
+    "mis_moonshine_decoder_forward": (C.c_int, [_P, _P, _P]),
+    "mis_moonshine_launches_per_step": (C.c_int, [_P]),
+    "mis_stt_moonshine_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.POINTER(SttParamsC), C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -344,6 +364,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_marvis_forced_logits": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(MarvisParamsC), _P, C.c_int, _P, _P, _P]),
     "mis_debug_marvis_sample_logits": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_int,
                                                  C.c_int, C.c_int, _P]),
+    "mis_debug_moonshine_stem_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 

@@ -1,0 +1,959 @@
+// moonshine.hip - the Moonshine STT engine: raw 16 kHz samples -> strided conv stem -> encoder -> cached decoder -> greedy ids.
+//
+// Reference being replaced: MoonshineModel / MoonshineEncoder / MoonshineDecoder / MoonshineAttention
+// (Sources/MLXAudioSTT/Models/Moonshine/MoonshineModel.swift:112-411).  Tokenizer and text stay on the host (:7-69).
+//
+// Ragged batch.  A row of n samples has T1 = (n - 127) / 64 + 1 conv1 frames, T2 = (T1 - 7) / 3 + 1, T3 = (T2 - 3) / 2 + 1 (no padding in
+// any conv, :309-312).  The batch is laid out with T1pad = 6 * ceil(max T1 / 6), T2pad = T1pad / 3, T3pad = T2pad / 2 frames per row, so
+// that frame t2 of row b of conv2 is the CONTIGUOUS span of 7 d values starting at element 3 d (b T2pad + t2) of the GroupNorm output
+// (and likewise conv3 on conv2's output): both dense convs are one launch_gemm_big each with ldx = stride * C_in < K = k * C_in, no patch
+// matrix.  Frames past a row's own extent are written as zeros by the GroupNorm kernel, the statistics run over the row's own T1 d
+// values, and every attention masks keys >= T3[b]: samples past lens[b] never reach a value that is kept.
+//
+// Precision: f32 from the waveform through GroupNorm (conv1 + tanh, statistics, affine), one rounding to bf16 there; bf16 storage with
+// f32 accumulation from conv2 on, rounding at every primitive boundary as in the Whisper engine.  Logits stay f32.
+//
+// Head sizes 36 / 52 (hidden / heads): every head is zero-padded to 64 at load (rows of q/k/v, columns of o_proj), which leaves scores
+// and outputs unchanged; the scale stays head_dim^-0.5 of the real size and RoPE touches the first rotary_dim columns only (:142-147).
+//
+//   k_ms_conv1_tanh    [T1,127] x [127,d] on overlapping sample windows held in LDS (f32)
+//   k_ms_gn_partial    whole-row GroupNorm statistics, two passes over fixed 32768-element chunks (a row's result does not depend on the batch)
+//   k_ms_gn_apply      affine + the single rounding to bf16, zeros past T1[b]
+//   k_ms_rope_rows     partial interleaved RoPE on the q and k columns of the encoder's q|k|v rows
+//   k_ms_attn_enc      non-causal attention over the row's own T3 keys, one wave per query
+//   k_ms_gemv          decode-step GEMM for <= 64 rows: LayerNorm in the prologue, bias / residual / SiLU gate in the epilogue
+//   k_ms_attn_self     RoPE + cache append + causal attention of the new token;  k_ms_attn_cross  over the cached encoder K/V
+//   k_ms_argmax_embed  greedy choice, EOS rule, token bookkeeping and the next token's embedding in one launch
+#include "common.h"
+#include "whisper_kernels.h"
+
+#include <math.h>
+#include <string.h>
+#include <memory>
+
+#define MS_DP 64                 // padded head size
+#define MS_MAX_SAMPLES 480000    // per-row cap: 30 s at 16 kHz
+#define MS_MAX_KEYS 1280         // >= T3 of the cap (1248)
+#define MS_MAX_POS 2048          // decoder positions (start token + max_tokens)
+#define MS_MAX_BATCH 64
+#define MS_GN_CHUNK 32768
+static const float MS_EPS = 1e-5f;
+
+struct MsHostTensor { std::vector<float> v; std::vector<int64_t> shape; };
+struct MsEncLayer { bf16_t *ln1, *ln2, *wqkv, *bqkv, *wo, *fc1, *b1, *fc2, *b2; };
+struct MsDecLayer { bf16_t *ln1, *ln2, *ln3, *sqkv, *sbqkv, *so, *cq, *cbq, *ckv, *cbkv, *co, *fc1, *b1, *fc2, *b2; };
+
+struct mis_moonshine {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    mis_moonshine_config cfg{};
+    int d = 0, f = 0, V = 0, He = 0, Hke = 0, Hd = 0, Hkd = 0, hde = 0, hdd = 0, rote = 0, rotd = 0;
+    std::map<std::string, MsHostTensor> raw;
+    bool finalized = false;
+    DevBuf<bf16_t> arena;
+    DevBuf<float> farena;
+    float *conv1wT = nullptr, *gn_w = nullptr, *gn_b = nullptr, *cos_e = nullptr, *sin_e = nullptr, *cos_d = nullptr, *sin_d = nullptr;
+    bf16_t *conv2w = nullptr, *conv2b = nullptr, *conv3w = nullptr, *conv3b = nullptr, *enc_ln = nullptr, *zeros = nullptr, *emb = nullptr,
+           *proj = nullptr, *dec_norm = nullptr;
+    std::vector<MsEncLayer> enc;
+    std::vector<MsDecLayer> dec;
+    // state of the last encode
+    int batch = 0, T1pad = 0, T2pad = 0, T3pad = 0, T3max = 0, Smax = 0, pos = 0;
+    std::vector<int> hT1, hT3;
+    DevBuf<float> pcm, c1, gn_part0, gn_part1, gn_stats, logits;
+    DevBuf<int> T1, T3;
+    DevBuf<bf16_t> gn, c2, h, x, qkv, att, ff, enc_out, cross, self_k, self_v;
+    DevBuf<bf16_t> dh, dqkv, dq, datt, dact;
+    DevBuf<int32_t> ids, n_gen, tokens_out, done_count;
+    DevBuf<uint8_t> active;
+};
+
+// ---------------------------------------------------------------------------- frame counts
+static inline int ms_t1(int64_t n) { return n >= 127 ? (int)((n - 127) / 64 + 1) : 0; }
+static inline int ms_t2(int t1) { return t1 >= 7 ? (t1 - 7) / 3 + 1 : 0; }
+static inline int ms_t3(int t2) { return t2 >= 3 ? (t2 - 3) / 2 + 1 : 0; }
+
+// rotaryDim (MoonshineModel.swift:142-144)
+static int ms_rotary_dim(int head_dim, float factor) {
+    int r = (int)((float)head_dim * factor);
+    r -= r % 2;
+    return std::max(2, r);
+}
+
+extern "C" mis_status mis_moonshine_frames(const mis_moonshine*, const int64_t* lens, int batch, int32_t* frames_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(lens && frames_out && batch >= 1, MIS_ERR_INVALID_INPUT, "bad argument");
+    for (int b = 0; b < batch; ++b) frames_out[b] = ms_t3(ms_t2(ms_t1(lens[b])));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_moonshine_create(const mis_moonshine_config* cfg, int device, mis_moonshine** out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
+    int n = 0;
+    HIP_CHECK(hipGetDeviceCount(&n));
+    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
+    const int d = cfg->hidden_size;
+    MIS_REQUIRE(d > 0 && d % 32 == 0 && d <= 512, MIS_ERR_INVALID_INPUT, "hidden_size %d unsupported (a multiple of 32, at most 512)", d);
+    MIS_REQUIRE(cfg->intermediate_size > 0 && cfg->intermediate_size % 32 == 0, MIS_ERR_INVALID_INPUT, "intermediate_size must be a multiple of 32");
+    MIS_REQUIRE(cfg->vocab_size > 0 && cfg->encoder_num_hidden_layers > 0 && cfg->decoder_num_hidden_layers > 0, MIS_ERR_INVALID_INPUT, "bad dims");
+    const int He = cfg->encoder_num_attention_heads, Hd = cfg->decoder_num_attention_heads;
+    const int Hke = cfg->encoder_num_key_value_heads, Hkd = cfg->decoder_num_key_value_heads;
+    MIS_REQUIRE(He > 0 && Hd > 0 && d % He == 0 && d % Hd == 0, MIS_ERR_INVALID_INPUT, "bad head counts");
+    MIS_REQUIRE(Hke > 0 && Hkd > 0 && He % Hke == 0 && Hd % Hkd == 0, MIS_ERR_INVALID_INPUT, "bad key/value head counts");
+    MIS_REQUIRE(d / He <= MS_DP && d / Hd <= MS_DP && d / He >= 2 && d / Hd >= 2, MIS_ERR_INVALID_INPUT, "head_dim above %d unsupported", MS_DP);
+    MIS_REQUIRE(cfg->encoder_hidden_act == 0, MIS_ERR_INVALID_INPUT, "encoder_hidden_act: only gelu is implemented");
+    MIS_REQUIRE(cfg->partial_rotary_factor > 0.0f && cfg->partial_rotary_factor <= 1.0f && cfg->rope_theta > 0.0f, MIS_ERR_INVALID_INPUT, "bad rotary parameters");
+    MIS_REQUIRE(cfg->decoder_start_token_id >= 0 && cfg->decoder_start_token_id < cfg->vocab_size, MIS_ERR_INVALID_INPUT, "decoder_start_token_id outside the vocabulary");
+    HIP_CHECK(hipSetDevice(device));
+    auto c = std::make_unique<mis_moonshine>();
+    c->device = device; c->cfg = *cfg;
+    c->d = d; c->f = cfg->intermediate_size; c->V = cfg->vocab_size;
+    c->He = He; c->Hke = Hke; c->Hd = Hd; c->Hkd = Hkd; c->hde = d / He; c->hdd = d / Hd;
+    c->rote = ms_rotary_dim(c->hde, cfg->partial_rotary_factor);
+    c->rotd = ms_rotary_dim(c->hdd, cfg->partial_rotary_factor);
+    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    *out = c.release();
+    MIS_API_END
+}
+
+extern "C" void mis_moonshine_destroy(mis_moonshine* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
+    delete c;
+}
+
+// checkpoint key -> the name the engine indexes by (MoonshineModel.sanitize, :443-459: "model." stripped); "" = ignored
+static std::string ms_canonical_name(const mis_moonshine* c, const std::string& raw) {
+    std::string name = raw;
+    if (name.rfind("model.", 0) == 0) name = name.substr(6);
+    if (name.rfind("proj_out.", 0) == 0 && c->cfg.tie_word_embeddings) return "";
+    return name;
+}
+
+extern "C" mis_status mis_moonshine_set_tensor(mis_moonshine* c, const char* name_, const void* data, mis_dtype dtype, const int64_t* shape,
+                                               int ndim) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && name_ && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
+    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    const std::string name = ms_canonical_name(c, name_);
+    if (name.empty()) return MIS_OK;
+    MsHostTensor t;
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; t.shape.push_back(shape[i]); }
+    t.v.resize(n);
+    if (dtype == MIS_F32) memcpy(t.v.data(), data, n * 4);
+    else {
+        const uint16_t* s = static_cast<const uint16_t*>(data);
+        for (size_t i = 0; i < n; ++i) t.v[i] = dtype == MIS_F16 ? f16_to_f32_host(s[i]) : bf16_to_f32(s[i]);
+    }
+    c->raw[name] = std::move(t);
+    MIS_API_END
+}
+
+static const MsHostTensor& ms_need(mis_moonshine* c, const std::string& name, std::initializer_list<int64_t> shape) {
+    auto it = c->raw.find(name);
+    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "Moonshine weight missing: %s", name.c_str());
+    MIS_REQUIRE(it->second.shape == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Moonshine weight %s has the wrong shape", name.c_str());
+    return it->second;
+}
+
+extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+    HIP_CHECK(hipSetDevice(c->device));
+    const int64_t d = c->d, f = c->f, V = c->V;
+    const bool ab = c->cfg.attention_bias != 0;
+    std::vector<bf16_t> host;                           // the bf16 arena, assembled on the host: f32 checkpoints are rounded once, here
+    std::vector<float> fhost;
+    auto btake = [&](size_t n) { size_t off = host.size(); host.resize(off + round_up(n, 64), 0); return off; };
+    auto ftake = [&](size_t n) { size_t off = fhost.size(); fhost.resize(off + round_up(n, 64), 0.0f); return off; };
+    auto bvec = [&](const std::string& name, int64_t n) {
+        const MsHostTensor& t = ms_need(c, name, {n});
+        size_t off = btake(n);
+        for (int64_t i = 0; i < n; ++i) host[off + i] = f32_to_bf16(t.v[i]);
+        return off;
+    };
+    auto bmat = [&](const std::string& name, int64_t N, int64_t K) {
+        const MsHostTensor& t = ms_need(c, name, {N, K});
+        size_t off = btake((size_t)N * K);
+        for (size_t i = 0; i < (size_t)N * K; ++i) host[off + i] = f32_to_bf16(t.v[i]);
+        return off;
+    };
+    // projection rows [H hd][d] -> [H 64][d] at dst row0 (head h, column j -> row h 64 + j; the padding rows stay zero)
+    auto pad_rows = [&](const std::string& name, int H, int hd, size_t off, int64_t row0) {
+        const MsHostTensor& t = ms_need(c, name, {(int64_t)H * hd, d});
+        for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j) for (int64_t k = 0; k < d; ++k)
+            host[off + (size_t)(row0 + h * MS_DP + j) * d + k] = f32_to_bf16(t.v[(size_t)(h * hd + j) * d + k]);
+    };
+    auto pad_bias = [&](const std::string& name, int H, int hd, size_t off, int64_t row0) {
+        const MsHostTensor& t = ms_need(c, name, {(int64_t)H * hd});
+        for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j) host[off + row0 + h * MS_DP + j] = f32_to_bf16(t.v[h * hd + j]);
+    };
+    // o_proj [d][H hd] -> [d][H 64]
+    auto pad_cols = [&](const std::string& name, int H, int hd) {
+        const MsHostTensor& t = ms_need(c, name, {d, (int64_t)H * hd});
+        size_t off = btake((size_t)d * H * MS_DP);
+        for (int64_t n = 0; n < d; ++n) for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j)
+            host[off + (size_t)n * H * MS_DP + h * MS_DP + j] = f32_to_bf16(t.v[(size_t)n * H * hd + h * hd + j]);
+        return off;
+    };
+    // conv weight [out][in][k] (published layout) -> [out][k in] (the order of a contiguous span of k frames)
+    auto conv_w = [&](const std::string& name, int64_t O, int64_t I, int64_t K) {
+        const MsHostTensor& t = ms_need(c, name, {O, I, K});
+        size_t off = btake((size_t)O * I * K);
+        for (int64_t o = 0; o < O; ++o) for (int64_t k = 0; k < K; ++k) for (int64_t i = 0; i < I; ++i)
+            host[off + ((size_t)o * K + k) * I + i] = f32_to_bf16(t.v[((size_t)o * I + i) * K + k]);
+        return off;
+    };
+    const std::string E = "encoder", D = "decoder";
+    // ---- stem (f32 through GroupNorm)
+    const MsHostTensor& w1 = ms_need(c, E + ".conv1.weight", {d, 1, 127});
+    const size_t o_c1 = ftake((size_t)127 * d);
+    for (int64_t ch = 0; ch < d; ++ch) for (int k = 0; k < 127; ++k) fhost[o_c1 + (size_t)k * d + ch] = w1.v[(size_t)ch * 127 + k];
+    const size_t o_gw = ftake(d), o_gb = ftake(d);
+    { const MsHostTensor& gw = ms_need(c, E + ".groupnorm.weight", {d}); const MsHostTensor& gb = ms_need(c, E + ".groupnorm.bias", {d});
+      for (int64_t i = 0; i < d; ++i) { fhost[o_gw + i] = gw.v[i]; fhost[o_gb + i] = gb.v[i]; } }
+    // rotary tables [MS_MAX_POS][rot / 2] (MoonshineRotaryEmbedding, :88-110)
+    auto rope_tab = [&](int rot, size_t* oc, size_t* os) {
+        *oc = ftake((size_t)MS_MAX_POS * (rot / 2)); *os = ftake((size_t)MS_MAX_POS * (rot / 2));
+        for (int i = 0; i < rot / 2; ++i) {
+            const float inv = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / (float)rot);
+            for (int p = 0; p < MS_MAX_POS; ++p) {
+                const float a = (float)p * inv;
+                fhost[*oc + (size_t)p * (rot / 2) + i] = (float)cos((double)a);
+                fhost[*os + (size_t)p * (rot / 2) + i] = (float)sin((double)a);
+            }
+        }
+    };
+    size_t o_ce, o_se, o_cd, o_sd;
+    rope_tab(c->rote, &o_ce, &o_se);
+    rope_tab(c->rotd, &o_cd, &o_sd);
+    const size_t o_zero = btake(std::max<int64_t>(d, 64));
+    const size_t o_c2w = conv_w(E + ".conv2.weight", 2 * d, d, 7), o_c2b = bvec(E + ".conv2.bias", 2 * d);
+    const size_t o_c3w = conv_w(E + ".conv3.weight", d, 2 * d, 3), o_c3b = bvec(E + ".conv3.bias", d);
+    // ---- encoder layers
+    struct Off { size_t v[15]; };
+    std::vector<Off> eo(c->cfg.encoder_num_hidden_layers), dof(c->cfg.decoder_num_hidden_layers);
+    const int64_t NQe = (int64_t)(c->He + 2 * c->Hke) * MS_DP;
+    for (size_t li = 0; li < eo.size(); ++li) {
+        const std::string q = E + ".layers." + std::to_string(li);
+        Off& o = eo[li];
+        o.v[0] = bvec(q + ".input_layernorm.weight", d); o.v[1] = bvec(q + ".post_attention_layernorm.weight", d);
+        o.v[2] = btake((size_t)NQe * d);
+        pad_rows(q + ".self_attn.q_proj.weight", c->He, c->hde, o.v[2], 0);
+        pad_rows(q + ".self_attn.k_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)c->He * MS_DP);
+        pad_rows(q + ".self_attn.v_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)(c->He + c->Hke) * MS_DP);
+        o.v[3] = btake(NQe);
+        if (ab) {
+            pad_bias(q + ".self_attn.q_proj.bias", c->He, c->hde, o.v[3], 0);
+            pad_bias(q + ".self_attn.k_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)c->He * MS_DP);
+            pad_bias(q + ".self_attn.v_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)(c->He + c->Hke) * MS_DP);
+        }
+        o.v[4] = pad_cols(q + ".self_attn.o_proj.weight", c->He, c->hde);
+        o.v[5] = bmat(q + ".mlp.fc1.weight", f, d); o.v[6] = bvec(q + ".mlp.fc1.bias", f);
+        o.v[7] = bmat(q + ".mlp.fc2.weight", d, f); o.v[8] = bvec(q + ".mlp.fc2.bias", d);
+    }
+    const size_t o_eln = bvec(E + ".layer_norm.weight", d);
+    // ---- decoder
+    const size_t o_emb = bmat(D + ".embed_tokens.weight", V, d);
+    const size_t o_proj = c->cfg.tie_word_embeddings ? o_emb : bmat("proj_out.weight", V, d);
+    const int64_t NQd = (int64_t)(c->Hd + 2 * c->Hkd) * MS_DP, NKVd = (int64_t)2 * c->Hkd * MS_DP;
+    for (size_t li = 0; li < dof.size(); ++li) {
+        const std::string q = D + ".layers." + std::to_string(li);
+        Off& o = dof[li];
+        o.v[0] = bvec(q + ".input_layernorm.weight", d); o.v[1] = bvec(q + ".post_attention_layernorm.weight", d);
+        o.v[2] = bvec(q + ".final_layernorm.weight", d);
+        o.v[3] = btake((size_t)NQd * d);
+        pad_rows(q + ".self_attn.q_proj.weight", c->Hd, c->hdd, o.v[3], 0);
+        pad_rows(q + ".self_attn.k_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)c->Hd * MS_DP);
+        pad_rows(q + ".self_attn.v_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)(c->Hd + c->Hkd) * MS_DP);
+        o.v[4] = btake(NQd);
+        if (ab) {
+            pad_bias(q + ".self_attn.q_proj.bias", c->Hd, c->hdd, o.v[4], 0);
+            pad_bias(q + ".self_attn.k_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)c->Hd * MS_DP);
+            pad_bias(q + ".self_attn.v_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)(c->Hd + c->Hkd) * MS_DP);
+        }
+        o.v[5] = pad_cols(q + ".self_attn.o_proj.weight", c->Hd, c->hdd);
+        o.v[6] = btake((size_t)c->Hd * MS_DP * d);
+        pad_rows(q + ".encoder_attn.q_proj.weight", c->Hd, c->hdd, o.v[6], 0);
+        o.v[7] = btake((size_t)c->Hd * MS_DP);
+        if (ab) pad_bias(q + ".encoder_attn.q_proj.bias", c->Hd, c->hdd, o.v[7], 0);
+        o.v[8] = btake((size_t)NKVd * d);
+        pad_rows(q + ".encoder_attn.k_proj.weight", c->Hkd, c->hdd, o.v[8], 0);
+        pad_rows(q + ".encoder_attn.v_proj.weight", c->Hkd, c->hdd, o.v[8], (int64_t)c->Hkd * MS_DP);
+        o.v[9] = btake(NKVd);
+        if (ab) {
+            pad_bias(q + ".encoder_attn.k_proj.bias", c->Hkd, c->hdd, o.v[9], 0);
+            pad_bias(q + ".encoder_attn.v_proj.bias", c->Hkd, c->hdd, o.v[9], (int64_t)c->Hkd * MS_DP);
+        }
+        o.v[10] = pad_cols(q + ".encoder_attn.o_proj.weight", c->Hd, c->hdd);
+        o.v[11] = bmat(q + ".mlp.fc1.weight", 2 * f, d); o.v[12] = bvec(q + ".mlp.fc1.bias", 2 * f);
+        o.v[13] = bmat(q + ".mlp.fc2.weight", d, f); o.v[14] = bvec(q + ".mlp.fc2.bias", d);
+    }
+    const size_t o_dn = bvec(D + ".norm.weight", d);
+    // ---- upload
+    c->arena.alloc(host.size());
+    c->farena.alloc(fhost.size());
+    HIP_CHECK(hipMemcpy(c->arena.p, host.data(), host.size() * 2, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(c->farena.p, fhost.data(), fhost.size() * 4, hipMemcpyHostToDevice));
+    bf16_t* A = c->arena.p;
+    float* F = c->farena.p;
+    c->conv1wT = F + o_c1; c->gn_w = F + o_gw; c->gn_b = F + o_gb;
+    c->cos_e = F + o_ce; c->sin_e = F + o_se; c->cos_d = F + o_cd; c->sin_d = F + o_sd;
+    c->zeros = A + o_zero; c->conv2w = A + o_c2w; c->conv2b = A + o_c2b; c->conv3w = A + o_c3w; c->conv3b = A + o_c3b;
+    c->enc_ln = A + o_eln; c->emb = A + o_emb; c->proj = A + o_proj; c->dec_norm = A + o_dn;
+    c->enc.resize(eo.size());
+    for (size_t li = 0; li < eo.size(); ++li) {
+        const Off& o = eo[li];
+        c->enc[li] = MsEncLayer{A + o.v[0], A + o.v[1], A + o.v[2], ab ? A + o.v[3] : nullptr, A + o.v[4], A + o.v[5], A + o.v[6], A + o.v[7], A + o.v[8]};
+    }
+    c->dec.resize(dof.size());
+    for (size_t li = 0; li < dof.size(); ++li) {
+        const Off& o = dof[li];
+        c->dec[li] = MsDecLayer{A + o.v[0], A + o.v[1], A + o.v[2], A + o.v[3], ab ? A + o.v[4] : nullptr, A + o.v[5], A + o.v[6],
+                                ab ? A + o.v[7] : nullptr, A + o.v[8], ab ? A + o.v[9] : nullptr, A + o.v[10], A + o.v[11], A + o.v[12],
+                                A + o.v[13], A + o.v[14]};
+    }
+    c->raw.clear();
+    c->finalized = true;
+    MIS_API_END
+}
+
+// mis-synth-v1 weights (benches): every published key, amplitudes as the other engines' synthetic models
+extern "C" mis_status mis_moonshine_init_synthetic(mis_moonshine* c, uint64_t seed) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+    uint64_t key = seed * 100000ull;
+    const int64_t d = c->d, f = c->f;
+    auto put = [&](const std::string& name, std::vector<int64_t> shape, double amp, float plus) {
+        MsHostTensor t;
+        size_t n = 1;
+        for (auto v : shape) n *= (size_t)v;
+        t.shape = shape; t.v.resize(n);
+        ++key;
+        for (size_t i = 0; i < n; ++i) t.v[i] = plus + mis_synth_value(key, i, (float)amp);
+        c->raw[name] = std::move(t);
+    };
+    auto lin = [&](const std::string& p, int64_t o, int64_t i, bool bias, double gain) {
+        put(p + ".weight", {o, i}, gain * sqrt(3.0 / (double)i), 0.0f);
+        if (bias) put(p + ".bias", {o}, 0.05, 0.0f);
+    };
+    auto attn = [&](const std::string& p, int H, int Hk, int hd) {
+        const bool ab = c->cfg.attention_bias != 0;
+        lin(p + ".q_proj", (int64_t)H * hd, d, ab, 1.0); lin(p + ".k_proj", (int64_t)Hk * hd, d, ab, 1.0);
+        lin(p + ".v_proj", (int64_t)Hk * hd, d, ab, 1.0); lin(p + ".o_proj", d, (int64_t)H * hd, false, 0.5);
+    };
+    put("encoder.conv1.weight", {d, 1, 127}, sqrt(3.0 / 127.0) * 4.0, 0.0f);
+    put("encoder.groupnorm.weight", {d}, 0.1, 1.0f); put("encoder.groupnorm.bias", {d}, 0.05, 0.0f);
+    put("encoder.conv2.weight", {2 * d, d, 7}, sqrt(3.0 / (7.0 * d)), 0.0f); put("encoder.conv2.bias", {2 * d}, 0.05, 0.0f);
+    put("encoder.conv3.weight", {d, 2 * d, 3}, sqrt(3.0 / (6.0 * d)), 0.0f); put("encoder.conv3.bias", {d}, 0.05, 0.0f);
+    for (int li = 0; li < c->cfg.encoder_num_hidden_layers; ++li) {
+        const std::string q = "encoder.layers." + std::to_string(li);
+        attn(q + ".self_attn", c->He, c->Hke, c->hde);
+        put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
+        lin(q + ".mlp.fc1", f, d, true, 1.0); lin(q + ".mlp.fc2", d, f, true, 0.5);
+    }
+    put("encoder.layer_norm.weight", {d}, 0.1, 1.0f);
+    put("decoder.embed_tokens.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
+    for (int li = 0; li < c->cfg.decoder_num_hidden_layers; ++li) {
+        const std::string q = "decoder.layers." + std::to_string(li);
+        attn(q + ".self_attn", c->Hd, c->Hkd, c->hdd); attn(q + ".encoder_attn", c->Hd, c->Hkd, c->hdd);
+        put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
+        put(q + ".final_layernorm.weight", {d}, 0.1, 1.0f);
+        lin(q + ".mlp.fc1", 2 * f, d, true, 1.0); lin(q + ".mlp.fc2", d, f, true, 0.5);
+    }
+    put("decoder.norm.weight", {d}, 0.1, 1.0f);
+    if (!c->cfg.tie_word_embeddings) put("proj_out.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
+    MIS_API_END
+}
+
+// ============================================================================ stem kernels
+// tanh(conv1d(1 -> d, k 127, stride 64, no bias)) (:309,321): a block is 16 frames of one row - their 16 * 64 + 63 samples sit in LDS
+// once, a thread is a channel and reads its 127 taps once (weights transposed to [127][d]: coalesced) for all 16 frames.
+__global__ void __launch_bounds__(256) k_ms_conv1_tanh(const float* __restrict__ pcm, int64_t stride, const int* __restrict__ T1,
+                                                       const float* __restrict__ wT, float* __restrict__ out, int T1pad, int d) {
+    __shared__ float xs[16 * 64 + 64];
+    const int b = blockIdx.y, t0 = blockIdx.x * 16, n1 = T1[b];
+    const int64_t extent = n1 > 0 ? (int64_t)(n1 - 1) * 64 + 127 : 0;         // samples the row's own frames read (<= lens[b])
+    for (int i = threadIdx.x; i < 16 * 64 + 63; i += 256) {
+        const int64_t s = (int64_t)t0 * 64 + i;
+        xs[i] = s < extent ? pcm[(int64_t)b * stride + s] : 0.0f;
+    }
+    __syncthreads();
+    for (int ch = threadIdx.x; ch < d; ch += 256) {
+        float acc[16];
+#pragma unroll
+        for (int fidx = 0; fidx < 16; ++fidx) acc[fidx] = 0.0f;
+        for (int k = 0; k < 127; ++k) {
+            const float w = wT[(size_t)k * d + ch];
+#pragma unroll
+            for (int fidx = 0; fidx < 16; ++fidx) acc[fidx] = fmaf(w, xs[fidx * 64 + k], acc[fidx]);
+        }
+#pragma unroll
+        for (int fidx = 0; fidx < 16; ++fidx) {
+            const int t = t0 + fidx;
+            if (t < T1pad) out[((size_t)b * T1pad + t) * d + ch] = t < n1 ? tanhf(acc[fidx]) : 0.0f;
+        }
+    }
+}
+
+// GroupNorm(1 group) statistics over the row's own T1[b] * d values (:310,322; pytorchCompatible: biased variance).  Chunks of a fixed
+// 32768 elements, so that a row's sums are formed in the same order whatever the batch it travels in; PASS 1 reads the mean as the
+// ordered sum of the PASS 0 partials (chunks past the row's extent hold 0).
+template <int PASS>
+__global__ void __launch_bounds__(256) k_ms_gn_partial(const float* __restrict__ x, const int* __restrict__ T1, int T1pad, int d,
+                                                       const float* __restrict__ sums, float* __restrict__ out, int nch) {
+    __shared__ float red[4];
+    const int b = blockIdx.y, ch = blockIdx.x;
+    const size_t n = (size_t)T1[b] * d, lo = (size_t)ch * MS_GN_CHUNK, hi = lo + MS_GN_CHUNK < n ? lo + MS_GN_CHUNK : n;
+    float mean = 0.0f;
+    if (PASS == 1) {
+        float s = 0.0f;
+        for (int i = 0; i < nch; ++i) s += sums[b * nch + i];
+        mean = s / (float)n;
+    }
+    const float* xr = x + (size_t)b * T1pad * d;
+    float acc = 0.0f;
+    for (size_t i = lo + threadIdx.x; i < hi; i += 256) { const float v = xr[i] - mean; acc += PASS == 1 ? v * v : v; }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[b * nch + ch] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ void k_ms_gn_final(const float* __restrict__ sums, const float* __restrict__ sq, const int* __restrict__ T1, int d, int nch,
+                              float* __restrict__ stats, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float s = 0.0f, q = 0.0f;
+    for (int i = 0; i < nch; ++i) { s += sums[b * nch + i]; q += sq[b * nch + i]; }
+    const float n = (float)((size_t)T1[b] * d);
+    stats[2 * b] = s / n;
+    stats[2 * b + 1] = 1.0f / sqrtf(q / n + 1e-5f);
+}
+// y = T((x - mean) rstd gamma + beta) for t < T1[b], 0 behind it and in the tail the dense convs read past the last row
+__global__ void __launch_bounds__(256) k_ms_gn_apply(const float* __restrict__ x, const int* __restrict__ T1, const float* __restrict__ stats,
+                                                     const float* __restrict__ gw, const float* __restrict__ gb, bf16_t* __restrict__ y,
+                                                     int T1pad, int d, int B, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t row = i / d;
+    const int ch = (int)(i - row * d);
+    const size_t b = row / T1pad;
+    const int t = (int)(row - b * T1pad);
+    bf16_t v = 0;
+    if (b < (size_t)B && t < T1[b]) v = f32_to_bf16((x[i] - stats[2 * b]) * stats[2 * b + 1] * gw[ch] + gb[ch]);
+    y[i] = v;
+}
+
+// ============================================================================ attention
+// partial interleaved RoPE (:80-110,165-178): pairs (2i, 2i + 1) of the first `rot` columns of a head, T(x cos + rotate_half(x) sin)
+__device__ __forceinline__ float ms_rope(float x, int lane, int rot, const float* __restrict__ cs, const float* __restrict__ sn, int pos) {
+    const float partner = __shfl_xor(x, 1, 64);
+    if (lane >= rot) return x;
+    const float c = cs[(size_t)pos * (rot >> 1) + (lane >> 1)], s = sn[(size_t)pos * (rot >> 1) + (lane >> 1)];
+    return bf16_round_f32(x * c + ((lane & 1) ? partner : -partner) * s);
+}
+// rows [M][ld]: heads 0 .. nheads - 1 of 64 columns from column 0 (q heads, then k heads) are rotated in place at position m % Tpad
+__global__ void __launch_bounds__(256) k_ms_rope_rows(bf16_t* __restrict__ rows, int ld, int nheads, int Tpad, int rot,
+                                                      const float* __restrict__ cs, const float* __restrict__ sn, size_t M) {
+    const int lane = threadIdx.x & 63;
+    const size_t item = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= M * nheads) return;
+    const size_t m = item / nheads;
+    const int h = (int)(item - m * nheads);
+    bf16_t* p = rows + m * ld + h * MS_DP + lane;
+    const float r = ms_rope(bf16_to_f32(*p), lane, rot, cs, sn, (int)(m % Tpad));
+    if (lane < rot) *p = f32_to_bf16(r);
+}
+
+// one query against n keys: q (f32, in LDS, 64 wide), K / V rows of 64 bf16 with row strides ldk / ldv.  A lane is a key in the score
+// pass (the query is broadcast from LDS) and a column in the value pass; scores, softmax and the value sum in f32.  Returns the lane's
+// output column.  `cur_*`: one more key held in registers behind the n cached ones (the decoder's new token), cur_s = its score.
+__device__ __forceinline__ float ms_attend(const float* __restrict__ qs, float* __restrict__ sc, const bf16_t* __restrict__ K, size_t ldk,
+                                           const bf16_t* __restrict__ Vv, size_t ldv, int n, float scale, int lane, bool has_cur, float cur_s,
+                                           float cur_v) {
+    float mx = has_cur ? cur_s : -INFINITY;
+    for (int j = lane; j < n; j += 64) {
+        const uint4* kr = reinterpret_cast<const uint4*>(K + (size_t)j * ldk);
+        float dot = 0.0f;
+#pragma unroll
+        for (int c8 = 0; c8 < MS_DP / 8; ++c8) {
+            const uint4 u = kr[c8];
+            const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                dot = fmaf(bf16_to_f32((bf16_t)(w[e] & 0xffffu)), qs[c8 * 8 + 2 * e], dot);
+                dot = fmaf(bf16_to_f32((bf16_t)(w[e] >> 16)), qs[c8 * 8 + 2 * e + 1], dot);
+            }
+        }
+        const float s = dot * scale;
+        sc[j] = s;
+        mx = fmaxf(mx, s);
+    }
+    mx = wave_max(mx);
+    float sum = 0.0f;
+    for (int j = lane; j < n; j += 64) { const float e = __expf(sc[j] - mx); sc[j] = e; sum += e; }
+    sum = wave_sum(sum);
+    __syncthreads();                                              // the wave's own probabilities, written by other lanes
+    float acc = 0.0f;
+    for (int j = 0; j < n; ++j) acc = fmaf(sc[j], bf16_to_f32(Vv[(size_t)j * ldv + lane]), acc);
+    if (has_cur) { const float e = __expf(cur_s - mx); sum += e; acc = fmaf(e, cur_v, acc); }
+    return acc / sum;
+}
+
+// encoder self-attention, non-causal over the row's own T3[b] keys (:181-194).  grid (ceil(Tpad / 4), H, B): a wave is one query.
+__global__ void __launch_bounds__(256) k_ms_attn_enc(const bf16_t* __restrict__ qkv, int ld, int H, int Hkv, const int* __restrict__ T3,
+                                                     int Tpad, float scale, bf16_t* __restrict__ out, int ldo) {
+    __shared__ float sc[4][MS_MAX_KEYS];
+    __shared__ float qs[4][MS_DP];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.z, h = blockIdx.y, hk = h / (H / Hkv);
+    const int n = min(T3[b], MS_MAX_KEYS);
+    const int t = min(blockIdx.x * 4 + wave, Tpad - 1);           // (a clamped wave repeats the last row's work: uniform barriers)
+    const size_t row = (size_t)b * Tpad + t;
+    qs[wave][lane] = bf16_to_f32(qkv[row * ld + h * MS_DP + lane]);
+    __syncthreads();
+    const bf16_t* K = qkv + (size_t)b * Tpad * ld + (size_t)(H + hk) * MS_DP;
+    const bf16_t* Vv = qkv + (size_t)b * Tpad * ld + (size_t)(H + Hkv + hk) * MS_DP;
+    const float o = ms_attend(qs[wave], sc[wave], K, ld, Vv, ld, n, scale, lane, false, 0.0f, 0.0f);
+    if ((int)(blockIdx.x * 4 + wave) < Tpad) out[row * ldo + h * MS_DP + lane] = f32_to_bf16(t < n ? o : 0.0f);
+}
+
+// decoder self-attention of the token at position `pos` (causal, :155-194): RoPE on q and k, the new K / V rows appended to the caches
+// [B][Hkv][Smax][64] by the first head of each group, attention over positions 0 .. pos.  grid (H, B), one wave.
+__global__ void __launch_bounds__(64) k_ms_attn_self(const bf16_t* __restrict__ qkv, int H, int Hkv, bf16_t* __restrict__ kc,
+                                                     bf16_t* __restrict__ vc, int Smax, int pos, int rot, const float* __restrict__ cs,
+                                                     const float* __restrict__ sn, float scale, bf16_t* __restrict__ out) {
+    __shared__ float sc[MS_MAX_POS];
+    __shared__ float qs[MS_DP];
+    const int lane = threadIdx.x, h = blockIdx.x, b = blockIdx.y, group = H / Hkv, hk = h / group;
+    const size_t N = (size_t)(H + 2 * Hkv) * MS_DP;
+    const float q = ms_rope(bf16_to_f32(qkv[b * N + h * MS_DP + lane]), lane, rot, cs, sn, pos);
+    const float k = ms_rope(bf16_to_f32(qkv[b * N + (size_t)(H + hk) * MS_DP + lane]), lane, rot, cs, sn, pos);
+    const float v = bf16_to_f32(qkv[b * N + (size_t)(H + Hkv + hk) * MS_DP + lane]);
+    const size_t base = ((size_t)b * Hkv + hk) * Smax * MS_DP;
+    if (h % group == 0) { kc[base + (size_t)pos * MS_DP + lane] = f32_to_bf16(k); vc[base + (size_t)pos * MS_DP + lane] = f32_to_bf16(v); }
+    qs[lane] = q;
+    const float cur_s = wave_sum(q * k) * scale;
+    __syncthreads();
+    const float o = ms_attend(qs, sc, kc + base, MS_DP, vc + base, MS_DP, pos, scale, lane, true, cur_s, v);
+    out[(size_t)b * H * MS_DP + h * MS_DP + lane] = f32_to_bf16(o);
+}
+
+// decoder cross-attention over the row's cached encoder K / V (no RoPE, :165): kv rows [B Tpad][2 Hkv 64] (K heads, then V heads)
+__global__ void __launch_bounds__(64) k_ms_attn_cross(const bf16_t* __restrict__ q, int H, int Hkv, const bf16_t* __restrict__ kv,
+                                                      const int* __restrict__ T3, int Tpad, float scale, bf16_t* __restrict__ out) {
+    __shared__ float sc[MS_MAX_KEYS];
+    __shared__ float qs[MS_DP];
+    const int lane = threadIdx.x, h = blockIdx.x, b = blockIdx.y, hk = h / (H / Hkv);
+    const size_t ld = (size_t)2 * Hkv * MS_DP;
+    qs[lane] = bf16_to_f32(q[(size_t)b * H * MS_DP + h * MS_DP + lane]);
+    __syncthreads();
+    const bf16_t* K = kv + (size_t)b * Tpad * ld + (size_t)hk * MS_DP;
+    const bf16_t* Vv = kv + (size_t)b * Tpad * ld + (size_t)(Hkv + hk) * MS_DP;
+    const float o = ms_attend(qs, sc, K, ld, Vv, ld, min(T3[b], MS_MAX_KEYS), scale, lane, false, 0.0f, 0.0f);
+    out[(size_t)b * H * MS_DP + h * MS_DP + lane] = f32_to_bf16(o);
+}
+
+// ============================================================================ decode-step GEMM
+// out[b][n] = sum_k X[b][k] W[n][k] for B <= 64 rows: a wave is one output column (GATE: the pair n, n + F), lanes split K in pieces of
+// four, eight rows at a time in registers.  LN: X = T(LayerNorm(h) w) (weight only, eps 1e-5, :247,286-288) rebuilt per block into LDS
+// (K <= 512) - no separate LayerNorm launch.  Epilogues: MS_BF16 T(acc + bias); MS_RESID h = T(T(acc + bias) + h) in place (a column's
+// rows are read and written by the same lane only); MS_GATE T(T(silu(g)) a) with a = T(rows n), g = T(rows n + F) (:223-227);
+// MS_F32 the raw f32 sums (logits).
+enum { MS_BF16 = 0, MS_RESID = 1, MS_GATE = 2, MS_F32 = 3 };
+template <bool LN, int EPI>
+__global__ void __launch_bounds__(256) k_ms_gemv(const bf16_t* __restrict__ X, int K, const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ W,
+                                                 const bf16_t* __restrict__ bias, void* __restrict__ out, int N, int B, int F) {
+    extern __shared__ __attribute__((aligned(16))) bf16_t xn[];          // LN: [B][K]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (LN) {
+        for (int r = wave; r < B; r += 4) {
+            float s = 0.0f;
+            for (int i = lane; i < K; i += 64) s += bf16_to_f32(X[(size_t)r * K + i]);
+            const float mean = wave_sum(s) / (float)K;
+            float q = 0.0f;
+            for (int i = lane; i < K; i += 64) { const float t = bf16_to_f32(X[(size_t)r * K + i]) - mean; q += t * t; }
+            const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)K + 1e-5f);
+            for (int i = lane; i < K; i += 64)
+                xn[(size_t)r * K + i] = f32_to_bf16((bf16_to_f32(X[(size_t)r * K + i]) - mean) * rstd * bf16_to_f32(lnw[i]));
+        }
+        __syncthreads();
+    }
+    const int n = blockIdx.x * 4 + wave;
+    const int ncols = EPI == MS_GATE ? F : N;
+    if (n >= ncols) return;
+    const bf16_t* xsrc = LN ? xn : X;
+    const int K4 = K >> 2;
+    for (int r0 = 0; r0 < B; r0 += 8) {
+        float acc[8], accg[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) { acc[r] = 0.0f; accg[r] = 0.0f; }
+        for (int k4 = lane; k4 < K4; k4 += 64) {
+            const uint2 wu = *reinterpret_cast<const uint2*>(W + (size_t)n * K + k4 * 4);
+            const float w0 = bf16_to_f32((bf16_t)(wu.x & 0xffffu)), w1 = bf16_to_f32((bf16_t)(wu.x >> 16)),
+                        w2 = bf16_to_f32((bf16_t)(wu.y & 0xffffu)), w3 = bf16_to_f32((bf16_t)(wu.y >> 16));
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+            if (EPI == MS_GATE) {
+                const uint2 gu = *reinterpret_cast<const uint2*>(W + (size_t)(n + F) * K + k4 * 4);
+                g0 = bf16_to_f32((bf16_t)(gu.x & 0xffffu)); g1 = bf16_to_f32((bf16_t)(gu.x >> 16));
+                g2 = bf16_to_f32((bf16_t)(gu.y & 0xffffu)); g3 = bf16_to_f32((bf16_t)(gu.y >> 16));
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int row = min(r0 + r, B - 1);
+                const uint2 xu = *reinterpret_cast<const uint2*>(xsrc + (size_t)row * K + k4 * 4);
+                const float x0 = bf16_to_f32((bf16_t)(xu.x & 0xffffu)), x1 = bf16_to_f32((bf16_t)(xu.x >> 16)),
+                            x2 = bf16_to_f32((bf16_t)(xu.y & 0xffffu)), x3 = bf16_to_f32((bf16_t)(xu.y >> 16));
+                acc[r] = fmaf(x3, w3, fmaf(x2, w2, fmaf(x1, w1, fmaf(x0, w0, acc[r]))));
+                if (EPI == MS_GATE) accg[r] = fmaf(x3, g3, fmaf(x2, g2, fmaf(x1, g1, fmaf(x0, g0, accg[r]))));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const float a = wave_sum(acc[r]);
+            const float g = EPI == MS_GATE ? wave_sum(accg[r]) : 0.0f;
+            const int row = r0 + r;
+            if (lane != 0 || row >= B) continue;
+            if (EPI == MS_F32) { static_cast<float*>(out)[(size_t)row * N + n] = a; continue; }
+            float v = bf16_round_f32(a + (bias ? bf16_to_f32(bias[n]) : 0.0f));
+            bf16_t* o = static_cast<bf16_t*>(out);
+            if (EPI == MS_RESID) v = bf16_round_f32(v + bf16_to_f32(o[(size_t)row * N + n]));
+            if (EPI == MS_GATE) {
+                const float gg = bf16_round_f32(g + (bias ? bf16_to_f32(bias[n + F]) : 0.0f));
+                const float sg = bf16_round_f32(gg / (1.0f + __expf(-gg)));
+                o[(size_t)row * F + n] = f32_to_bf16(sg * v);
+                continue;
+            }
+            o[(size_t)row * N + n] = f32_to_bf16(v);
+        }
+    }
+}
+template <bool LN, int EPI>
+static void ms_gemv(const bf16_t* X, int K, const bf16_t* lnw, const bf16_t* W, const bf16_t* bias, void* out, int N, int B, int F, hipStream_t s) {
+    MIS_REQUIRE(K % 4 == 0 && B >= 1 && B <= MS_MAX_BATCH && (!LN || K <= 512), MIS_ERR_INVALID_INPUT, "decode GEMM: unsupported shape");
+    const int ncols = EPI == MS_GATE ? F : N;
+    hipLaunchKernelGGL((k_ms_gemv<LN, EPI>), dim3(cdiv(ncols, 4)), dim3(256), LN ? (size_t)B * K * 2 : 0, s, X, K, lnw, W, bias, out, N, B, F);
+}
+
+// h[b] = E[ids[b]] (:345)
+__global__ void __launch_bounds__(256) k_ms_embed(const bf16_t* __restrict__ emb, const int32_t* __restrict__ ids, bf16_t* __restrict__ h,
+                                                  int d, int vocab) {
+    int id = ids[blockIdx.x];
+    if (id < 0 || id >= vocab) id = 0;
+    for (int i = threadIdx.x; i < d; i += 256) h[(size_t)blockIdx.x * d + i] = emb[(size_t)id * d + i];
+}
+// greedy step of generate (:388-398): arg-max (lowest id on ties); EOS ends the row and is not kept; otherwise the id is appended and
+// becomes the next input, whose embedding is written here.  One block per row.
+__global__ void __launch_bounds__(256) k_ms_argmax_embed(const float* __restrict__ logits, int V, int eos, uint8_t* __restrict__ active,
+                                                         int32_t* __restrict__ n_gen, int32_t* __restrict__ tokens_out, int stride,
+                                                         int32_t* __restrict__ done_count, const bf16_t* __restrict__ emb,
+                                                         bf16_t* __restrict__ h, int d) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    __shared__ int chosen;
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = threadIdx.x; i < V; i += 256) {
+        const float v = logits[(size_t)b * V + i];
+        if (v > best || (v == best && i < idx)) { best = v; idx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if (lane == 0) { bv[wave] = best; bi[wave] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+        if (idx < 0 || idx >= V) idx = 0;                             // (a row of NaNs: no comparison holds)
+        if (active[b]) {
+            if (idx == eos) { active[b] = 0; atomicAdd(done_count, 1); }
+            else {
+                const int g = n_gen[b];
+                if (g < stride) tokens_out[(size_t)b * stride + g] = idx;
+                n_gen[b] = g + 1;
+            }
+        }
+        chosen = idx;
+    }
+    __syncthreads();
+    const int id = chosen;
+    for (int i = threadIdx.x; i < d; i += 256) h[(size_t)b * d + i] = emb[(size_t)id * d + i];
+}
+
+__global__ void k_ms_bf16_to_f32(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = bf16_to_f32(src[i]);
+}
+
+// ============================================================================ encoder pass
+static void ms_check_lens(const mis_moonshine* c, const int64_t* lens, int batch, int64_t stride, std::vector<int64_t>* hl) {
+    MIS_REQUIRE(c->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
+    MIS_REQUIRE(batch >= 1 && batch <= MS_MAX_BATCH, MIS_ERR_INVALID_INPUT, "batch per GPU must be 1..%d", MS_MAX_BATCH);
+    MIS_REQUIRE(stride >= 1, MIS_ERR_INVALID_INPUT, "bad stride");
+    hl->assign(batch, stride);
+    if (lens) memcpy(hl->data(), lens, batch * sizeof(int64_t));
+    for (int b = 0; b < batch; ++b) {
+        const int64_t n = (*hl)[b];
+        MIS_REQUIRE(n <= stride, MIS_ERR_INVALID_INPUT, "row %d: %lld samples exceed the row stride %lld", b, (long long)n, (long long)stride);
+        MIS_REQUIRE(ms_t3(ms_t2(ms_t1(n))) >= 1, MIS_ERR_INVALID_INPUT, "row %d: %lld samples give no encoder frame (at least 895 are needed)", b, (long long)n);
+        MIS_REQUIRE(n <= MS_MAX_SAMPLES, MIS_ERR_INVALID_INPUT, "row %d: %lld samples exceed the per-row cap of %d (30 s at 16 kHz)", b, (long long)n,
+                    MS_MAX_SAMPLES);
+    }
+}
+
+static void ms_decoder_reset(mis_moonshine* c, int max_positions) {
+    const int Smax = std::max(max_positions, 1);
+    MIS_REQUIRE(Smax <= MS_MAX_POS, MIS_ERR_INVALID_INPUT, "at most %d decoder positions", MS_MAX_POS);
+    const size_t n = (size_t)c->dec.size() * c->batch * c->Hkd * Smax * MS_DP;
+    c->Smax = Smax; c->pos = 0;
+    c->self_k.alloc(n); c->self_v.alloc(n);
+    HIP_CHECK(hipMemsetAsync(c->self_k.p, 0, n * 2, c->stream));
+    HIP_CHECK(hipMemsetAsync(c->self_v.p, 0, n * 2, c->stream));
+    const int B = c->batch;
+    c->dh.alloc((size_t)B * c->d); c->dqkv.alloc((size_t)B * (c->Hd + 2 * c->Hkd) * MS_DP); c->dq.alloc((size_t)B * c->Hd * MS_DP);
+    c->datt.alloc((size_t)B * c->Hd * MS_DP); c->dact.alloc((size_t)B * c->f); c->logits.alloc((size_t)B * c->V);
+    c->ids.alloc(B); c->n_gen.alloc(B); c->active.alloc(B); c->done_count.alloc(1);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// pcm_dev f32 [B][stride]; stop_stage < 0: the whole encoder and the cross K / V of every decoder layer; 0..3: stop behind conv1 + tanh,
+// GroupNorm, conv2, conv3 (the debug tap)
+static void ms_encode_device(mis_moonshine* c, const float* pcm_dev, const std::vector<int64_t>& hl, int batch, int64_t stride, int stop_stage) {
+    hipStream_t s = c->stream;
+    const int d = c->d, f = c->f, B = batch;
+    c->hT1.resize(B); c->hT3.resize(B);
+    int T1max = 0, T3max = 0;
+    for (int b = 0; b < B; ++b) {
+        c->hT1[b] = ms_t1(hl[b]); c->hT3[b] = ms_t3(ms_t2(c->hT1[b]));
+        T1max = std::max(T1max, c->hT1[b]); T3max = std::max(T3max, c->hT3[b]);
+    }
+    const int T1pad = (int)round_up(T1max, 6), T2pad = T1pad / 3, T3pad = T2pad / 2;
+    MIS_REQUIRE(T3max <= MS_MAX_KEYS && T3pad >= T3max, MIS_ERR_GENERATION_FAILED, "frame layout");
+    c->batch = B; c->T1pad = T1pad; c->T2pad = T2pad; c->T3pad = T3pad; c->T3max = T3max;
+    c->T1.alloc(B); c->T3.alloc(B);
+    HIP_CHECK(hipMemcpyAsync(c->T1.p, c->hT1.data(), B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->T3.p, c->hT3.data(), B * 4, hipMemcpyHostToDevice, s));
+    // ---- stem
+    const size_t n1 = (size_t)B * T1pad * d, tail = (size_t)8 * d;
+    c->c1.alloc(n1);
+    hipLaunchKernelGGL(k_ms_conv1_tanh, dim3(cdiv(T1pad, 16), B), dim3(256), 0, s, pcm_dev, stride, c->T1.p, c->conv1wT, c->c1.p, T1pad, d);
+    if (stop_stage == 0) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
+    const int nch = cdiv((int64_t)T1max * d, MS_GN_CHUNK);
+    c->gn_part0.alloc((size_t)B * nch); c->gn_part1.alloc((size_t)B * nch); c->gn_stats.alloc(2 * B);
+    hipLaunchKernelGGL((k_ms_gn_partial<0>), dim3(nch, B), dim3(256), 0, s, c->c1.p, c->T1.p, T1pad, d, nullptr, c->gn_part0.p, nch);
+    hipLaunchKernelGGL((k_ms_gn_partial<1>), dim3(nch, B), dim3(256), 0, s, c->c1.p, c->T1.p, T1pad, d, c->gn_part0.p, c->gn_part1.p, nch);
+    hipLaunchKernelGGL(k_ms_gn_final, dim3(1), dim3(64), 0, s, c->gn_part0.p, c->gn_part1.p, c->T1.p, d, nch, c->gn_stats.p, B);
+    c->gn.alloc(n1 + tail);
+    hipLaunchKernelGGL(k_ms_gn_apply, dim3((unsigned)((n1 + tail + 255) / 256)), dim3(256), 0, s, c->c1.p, c->T1.p, c->gn_stats.p, c->gn_w, c->gn_b,
+                       c->gn.p, T1pad, d, B, n1 + tail);
+    if (stop_stage == 1) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
+    // gelu(conv2), gelu(conv3) (:311-312,323-324): frame t of row b is the span of k C_in values at stride C_in * (b Tpad + t)
+    const int M2 = B * T2pad, M = B * T3pad;
+    const size_t n2 = (size_t)M2 * 2 * d;
+    c->c2.alloc(n2 + tail);
+    HIP_CHECK(hipMemsetAsync(c->c2.p + n2, 0, tail * 2, s));
+    BigGemmParams g{c->gn.p, c->conv2w, c->conv2b, nullptr, c->c2.p, M2, 2 * d, 7 * d, 3 * d, 0};
+    launch_gemm_big(BG_GELU, g, s);
+    if (stop_stage == 2) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
+    c->h.alloc((size_t)M * d);
+    g = BigGemmParams{c->c2.p, c->conv3w, c->conv3b, nullptr, c->h.p, M, d, 6 * d, 4 * d, 0};
+    launch_gemm_big(BG_GELU, g, s);
+    if (stop_stage == 3) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
+    // ---- encoder layers (:230-256)
+    const int NQ = (c->He + 2 * c->Hke) * MS_DP, NA = c->He * MS_DP;
+    c->x.alloc((size_t)M * d); c->qkv.alloc((size_t)M * NQ); c->att.alloc((size_t)M * NA); c->ff.alloc((size_t)M * f);
+    c->enc_out.alloc((size_t)M * d);
+    const float scale_e = 1.0f / sqrtf((float)c->hde);
+    for (const MsEncLayer& L : c->enc) {
+        launch_layernorm(c->h.p, c->x.p, L.ln1, c->zeros, M, d, MS_EPS, s);
+        g = BigGemmParams{c->x.p, L.wqkv, L.bqkv, nullptr, c->qkv.p, M, NQ, d, d, 0};
+        launch_gemm_big(BG_NONE, g, s);
+        const size_t items = (size_t)M * (c->He + c->Hke);
+        hipLaunchKernelGGL(k_ms_rope_rows, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, c->qkv.p, NQ, c->He + c->Hke, T3pad, c->rote,
+                           c->cos_e, c->sin_e, (size_t)M);
+        hipLaunchKernelGGL(k_ms_attn_enc, dim3(cdiv(T3pad, 4), c->He, B), dim3(256), 0, s, c->qkv.p, NQ, c->He, c->Hke, c->T3.p, T3pad, scale_e,
+                           c->att.p, NA);
+        g = BigGemmParams{c->att.p, L.wo, nullptr, c->h.p, c->h.p, M, d, NA, NA, 0};
+        launch_gemm_big(BG_RESID, g, s);
+        launch_layernorm(c->h.p, c->x.p, L.ln2, c->zeros, M, d, MS_EPS, s);
+        g = BigGemmParams{c->x.p, L.fc1, L.b1, nullptr, c->ff.p, M, f, d, d, 0};
+        launch_gemm_big(BG_GELU, g, s);
+        g = BigGemmParams{c->ff.p, L.fc2, L.b2, c->h.p, c->h.p, M, d, f, f, 0};
+        launch_gemm_big(BG_RESID, g, s);
+    }
+    launch_layernorm(c->h.p, c->enc_out.p, c->enc_ln, c->zeros, M, d, MS_EPS, s);
+    // cross-attention K / V of every decoder layer, once per request (:162-163 with encoderHiddenStates)
+    const int NKV = 2 * c->Hkd * MS_DP;
+    c->cross.alloc((size_t)c->dec.size() * M * NKV);
+    for (size_t li = 0; li < c->dec.size(); ++li) {
+        g = BigGemmParams{c->enc_out.p, c->dec[li].ckv, c->dec[li].cbkv, nullptr, c->cross.p + li * (size_t)M * NKV, M, NKV, d, d, 0};
+        launch_gemm_big(BG_NONE, g, s);
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    ms_decoder_reset(c, std::min(c->cfg.max_position_embeddings, MS_MAX_POS));
+}
+
+static void ms_upload_pcm(mis_moonshine* c, const float* pcm, int batch, int64_t stride) {
+    c->pcm.alloc((size_t)batch * stride);
+    HIP_CHECK(hipMemcpy(c->pcm.p, pcm, (size_t)batch * stride * 4, hipMemcpyDefault));
+}
+
+extern "C" mis_status mis_moonshine_encode(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* enc_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm, MIS_ERR_INVALID_INPUT, "null argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    std::vector<int64_t> hl;
+    ms_check_lens(c, lens, batch, stride, &hl);
+    ms_upload_pcm(c, pcm, batch, stride);
+    ms_encode_device(c, c->pcm.p, hl, batch, stride, -1);
+    if (enc_out) {                                            // [B][T3max][d], zeros behind a row's own T3
+        const size_t n = (size_t)batch * c->T3pad * c->d;
+        DevBuf<float> o;
+        o.alloc(n);
+        hipLaunchKernelGGL(k_ms_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->enc_out.p, o.p, n);
+        std::vector<float> hostv(n);
+        HIP_CHECK(hipMemcpyAsync(hostv.data(), o.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(hipStreamSynchronize(c->stream));
+        memset(enc_out, 0, (size_t)batch * c->T3max * c->d * 4);
+        for (int b = 0; b < batch; ++b)
+            memcpy(enc_out + (size_t)b * c->T3max * c->d, hostv.data() + (size_t)b * c->T3pad * c->d, (size_t)c->hT3[b] * c->d * 4);
+    }
+    MIS_API_END
+}
+
+// tests: stem stage outputs, out f32 [batch, dims[0], dims[1]] (frames as laid out by the engine: the row's own frames first, zeros or
+// padding-frame values behind them); out == NULL: dims only
+extern "C" mis_status mis_debug_moonshine_stem_tap(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, int stage,
+                                                   float* out, int64_t capacity, int64_t* dims) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm && dims && stage >= 0 && stage <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    std::vector<int64_t> hl;
+    ms_check_lens(c, lens, batch, stride, &hl);
+    ms_upload_pcm(c, pcm, batch, stride);
+    ms_encode_device(c, c->pcm.p, hl, batch, stride, stage);
+    const int64_t T = stage <= 1 ? c->T1pad : stage == 2 ? c->T2pad : c->T3pad, C = stage == 2 ? 2 * c->d : c->d;
+    dims[0] = T; dims[1] = C;
+    if (out) {
+        const size_t n = (size_t)batch * T * C;
+        MIS_REQUIRE((int64_t)n <= capacity, MIS_ERR_INVALID_INPUT, "output capacity too small");
+        if (stage == 0) HIP_CHECK(hipMemcpy(out, c->c1.p, n * 4, hipMemcpyDeviceToHost));
+        else {
+            DevBuf<float> o;
+            o.alloc(n);
+            const bf16_t* src = stage == 1 ? c->gn.p : stage == 2 ? c->c2.p : c->h.p;
+            hipLaunchKernelGGL(k_ms_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, src, o.p, n);
+            HIP_CHECK(hipStreamSynchronize(c->stream));
+            HIP_CHECK(hipMemcpy(out, o.p, n * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    c->batch = 0;                                             // no encoder output behind a tap: encode before decoding
+    MIS_API_END
+}
+
+// ============================================================================ decoder step
+// 8 launches per layer: [LN1 + q|k|v] [RoPE + append + self-attention] [o_proj + residual] [LN2 + cross q] [cross-attention]
+// [o_proj + residual] [LN3 + fc1 + SiLU gate] [fc2 + residual]   (:258-297); a single chain on one stream
+static int ms_launches_per_step(const mis_moonshine* c) { return 8 * (int)c->dec.size() + 2; }
+static void ms_enqueue_layers(mis_moonshine* c, int pos) {
+    hipStream_t s = c->stream;
+    const int d = c->d, f = c->f, B = c->batch, H = c->Hd, Hk = c->Hkd, NQ = (H + 2 * Hk) * MS_DP, NA = H * MS_DP, NKV = 2 * Hk * MS_DP;
+    const float scale = 1.0f / sqrtf((float)c->hdd);
+    const size_t M = (size_t)B * c->T3pad, ls = (size_t)B * Hk * c->Smax * MS_DP;
+    for (size_t li = 0; li < c->dec.size(); ++li) {
+        const MsDecLayer& L = c->dec[li];
+        ms_gemv<true, MS_BF16>(c->dh.p, d, L.ln1, L.sqkv, L.sbqkv, c->dqkv.p, NQ, B, 0, s);
+        hipLaunchKernelGGL(k_ms_attn_self, dim3(H, B), dim3(64), 0, s, c->dqkv.p, H, Hk, c->self_k.p + li * ls, c->self_v.p + li * ls, c->Smax, pos,
+                           c->rotd, c->cos_d, c->sin_d, scale, c->datt.p);
+        ms_gemv<false, MS_RESID>(c->datt.p, NA, nullptr, L.so, nullptr, c->dh.p, d, B, 0, s);
+        ms_gemv<true, MS_BF16>(c->dh.p, d, L.ln2, L.cq, L.cbq, c->dq.p, NA, B, 0, s);
+        hipLaunchKernelGGL(k_ms_attn_cross, dim3(H, B), dim3(64), 0, s, c->dq.p, H, Hk, c->cross.p + li * M * NKV, c->T3.p, c->T3pad, scale, c->datt.p);
+        ms_gemv<false, MS_RESID>(c->datt.p, NA, nullptr, L.co, nullptr, c->dh.p, d, B, 0, s);
+        ms_gemv<true, MS_GATE>(c->dh.p, d, L.ln3, L.fc1, L.b1, c->dact.p, 2 * f, B, f, s);
+        ms_gemv<false, MS_RESID>(c->dact.p, f, nullptr, L.fc2, L.b2, c->dh.p, d, B, 0, s);
+    }
+    // logitsForHidden(norm(x)) (:349,427-432): the final LayerNorm in the prologue of the vocabulary projection
+    ms_gemv<true, MS_F32>(c->dh.p, d, c->dec_norm, c->proj, nullptr, c->logits.p, c->V, B, 0, s);
+}
+
+extern "C" int mis_moonshine_launches_per_step(const mis_moonshine* c) { return c && c->finalized ? ms_launches_per_step(c) : 0; }
+
+extern "C" mis_status mis_moonshine_decoder_reset(mis_moonshine* c, int max_positions) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && c->batch > 0, MIS_ERR_NOT_INITIALIZED, "encode first");
+    HIP_CHECK(hipSetDevice(c->device));
+    ms_decoder_reset(c, max_positions > 0 ? max_positions : std::min(c->cfg.max_position_embeddings, MS_MAX_POS));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_moonshine_decoder_forward(mis_moonshine* c, const int32_t* tokens, float* logits_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && tokens, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(c->batch > 0, MIS_ERR_NOT_INITIALIZED, "encode first");
+    MIS_REQUIRE(c->pos < c->Smax, MIS_ERR_INVALID_INPUT, "decoder position %d beyond the %d the caches were reset for", c->pos, c->Smax);
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIP_CHECK(hipMemcpyAsync(c->ids.p, tokens, c->batch * 4, hipMemcpyDefault, s));
+    hipLaunchKernelGGL(k_ms_embed, dim3(c->batch), dim3(256), 0, s, c->emb, c->ids.p, c->dh.p, c->d, c->V);
+    ms_enqueue_layers(c, c->pos);
+    c->pos += 1;
+    if (logits_out) HIP_CHECK(hipMemcpyAsync(logits_out, c->logits.p, (size_t)c->batch * c->V * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    MIS_API_END
+}
+
+// MoonshineModel.generate (:374-411) for a ragged batch: start token, arg-max per step, EOS ends a row and is not kept, at most
+// max_tokens ids per row.  The reference recomputes the decoder over all tokens each step; the caches make that the same arithmetic.
+extern "C" mis_status mis_stt_moonshine_generate(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride,
+                                                 const mis_stt_params* sp, int32_t** tokens_out, int64_t* tokens_stride, int32_t* n_tokens) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm && sp && tokens_out && tokens_stride && n_tokens, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(!(sp->temperature > 0.0f), MIS_ERR_INVALID_INPUT, "Moonshine: temperature > 0 (categorical sampling) is not implemented; use temperature 0");
+    const int max_tokens = sp->max_tokens > 0 ? sp->max_tokens : 200;
+    MIS_REQUIRE(max_tokens + 1 <= MS_MAX_POS, MIS_ERR_INVALID_INPUT, "max_tokens above %d", MS_MAX_POS - 1);
+    HIP_CHECK(hipSetDevice(c->device));
+    std::vector<int64_t> hl;
+    ms_check_lens(c, lens, batch, stride, &hl);
+    ms_upload_pcm(c, pcm, batch, stride);
+    ms_encode_device(c, c->pcm.p, hl, batch, stride, -1);
+    ms_decoder_reset(c, max_tokens);
+    hipStream_t s = c->stream;
+    c->tokens_out.alloc((size_t)batch * max_tokens);
+    c->tokens_out.zero(s); c->n_gen.zero(s); c->done_count.zero(s);
+    HIP_CHECK(hipMemsetAsync(c->active.p, 1, batch, s));
+    std::vector<int32_t> start(batch, c->cfg.decoder_start_token_id);
+    HIP_CHECK(hipMemcpyAsync(c->ids.p, start.data(), batch * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ms_embed, dim3(batch), dim3(256), 0, s, c->emb, c->ids.p, c->dh.p, c->d, c->V);
+    PinnedBuf<int32_t> done(1);
+    *done.p = 0;
+    for (int step = 0; step < max_tokens; ++step) {
+        ms_enqueue_layers(c, step);
+        hipLaunchKernelGGL(k_ms_argmax_embed, dim3(batch), dim3(256), 0, s, c->logits.p, c->V, c->cfg.eos_token_id, c->active.p, c->n_gen.p,
+                           c->tokens_out.p, max_tokens, c->done_count.p, c->emb, c->dh.p, c->d);
+        if ((step & 7) == 7 || step + 1 == max_tokens) {          // the EOS check the loop needs, every 8 steps
+            HIP_CHECK(hipMemcpyAsync(done.p, c->done_count.p, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (*done.p >= batch) break;
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    PinnedBuf<int32_t> th((size_t)batch * max_tokens + 1);
+    HIP_CHECK(hipMemcpy(th.p, c->tokens_out.p, (size_t)batch * max_tokens * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(n_tokens, c->n_gen.p, batch * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; ++b) n_tokens[b] = std::min(n_tokens[b], max_tokens);
+    *tokens_out = th.release();
+    *tokens_stride = max_tokens;
+    MIS_API_END
+}
