@@ -836,6 +836,43 @@ mis_status mis_stt_moonshine_generate(mis_moonshine*, const float* pcm, const in
                                       const mis_stt_params*, int32_t** tokens_out, int64_t* tokens_stride, int32_t* n_tokens);
 
 /* ------------------------------------------------------------------------------------------
+ * Smart Turn endpoint detection (Sources/MLXAudioVAD/Models/SmartTurn/SmartTurn.swift:29-272, SmartTurnFeatures.swift:10-81,
+ * SmartTurnConfig.swift): has the speaker finished?  Every row is cut or left-padded with zeros to W = max_audio_seconds * sampling_rate
+ * samples, normalised to zero mean and unit deviation over the whole window (padding included), turned into F = W / hop_length log-mel
+ * frames (symmetric Hann, Slaney filters, last frame dropped) and run through a Whisper-style encoder of T = F / 2 positions, an
+ * attention pool and a small classifier.  Encoder in bf16 storage / f32 accumulation (an f32 checkpoint is rounded once, at finalize);
+ * prepare, features, pool and classifier in f32.  1..64 rows per call.  No step mixes rows, and every reduction runs in a fixed order,
+ * so a row's result is the same bit for bit in every batch whose encoder GEMMs run the same kernel; the GEMM launcher picks its
+ * 256 x 256 tile once a product has 200 or more such tiles (at the published shape: from about 22 rows), and across that switch the
+ * f32 summation order may differ, i.e. results agree to bf16 rounding only.
+ * Rejected with MIS_ERR_INVALID_INPUT before any launch: T > max_source_positions, odd F, head size other than 64 / 128, d_model or
+ * encoder_ffn_dim not a multiple of 32, n_fft / num_mel_bins outside what mis_mel_config takes; at a call, batch outside 1..64,
+ * lens[b] outside 1..stride, a null pointer, a handle that is not finalized.  A rejected call leaves the handle usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_smartturn mis_smartturn;
+/* SmartTurnEncoderConfig + SmartTurnProcessorConfig (SmartTurnConfig.swift:3-104); n_mels of the processor = num_mel_bins */
+typedef struct {
+    int32_t num_mel_bins, max_source_positions, d_model, encoder_attention_heads, encoder_layers, encoder_ffn_dim, k_proj_bias;
+    int32_t sampling_rate, max_audio_seconds, n_fft, hop_length, normalize_audio;
+    float   threshold;
+} mis_smartturn_config;
+mis_status mis_smartturn_create(const mis_smartturn_config*, int device, mis_smartturn** out);
+/* names as SmartTurnModel.sanitize leaves them (:274-324): encoder.conv{1,2}.weight [out, k, in], encoder.embed_positions.weight,
+ * encoder.layers.N.{self_attn_layer_norm,self_attn.{q,k,v,out}_proj,fc1,fc2,final_layer_norm}.*, encoder.layer_norm.*,
+ * pool_attention_{0,2}.*, classifier_{0,1,4,6}.*; host pointers.  finalize names a missing weight and checks every shape. */
+mis_status mis_smartturn_set_tensor(mis_smartturn*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_smartturn_init_synthetic(mis_smartturn*, uint64_t seed);
+mis_status mis_smartturn_finalize(mis_smartturn*);
+void       mis_smartturn_destroy(mis_smartturn*);
+/* kernel nodes of the last call's encoder + head chain: the node count of the replayed graph, or the launches made under MIS_NO_GRAPH */
+int        mis_smartturn_launches(const mis_smartturn*);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride); threshold < 0 = the config's.  Outputs caller-allocated [batch]; any may be NULL. */
+mis_status mis_smartturn_predict(mis_smartturn*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float threshold,
+                                 float* probability, float* logit, int32_t* prediction);
+/* already-prepared features f32 [batch, n_mels, F] (HF layout, SmartTurnModel.callAsFunction) */
+mis_status mis_smartturn_forward_features(mis_smartturn*, const float* features, int batch, float* probability, float* logit);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

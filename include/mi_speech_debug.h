@@ -73,6 +73,13 @@ mis_status mis_debug_marvis_rope_tables(int head_dim, float theta, float factor,
 mis_status mis_debug_moonshine_stem_tap(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, int stage,
                                         float* out, int64_t capacity, int64_t* dims);
 
+/* csrc/smartturn.hip, tests: tensors of the handle's last call, out f32 with room for `capacity` floats.  stage 0 prepared samples
+ * [B, W] (of the last predict), 1 features [B, F, n_mels], 2 encoder output [B, T, d], 3 pooled [B, d]. */
+mis_status mis_debug_smartturn_tap(mis_smartturn* c, int stage, float* out, int64_t capacity);
+/* measurements: device milliseconds of the last call, ms[3] = prepare + mel, encoder, head.  Inside a graph replay encoder and head
+ * are one interval: ms[1] holds it and ms[2] is -1. */
+mis_status mis_debug_smartturn_timing(const mis_smartturn* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ the Swift shim a maintainer would add):
     marvis.MarvisTTSModel  <-> class MarvisTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Marvis/MarvisTTSModel.swift)
     stt.WhisperModel       <-> class WhisperModel : STTGenerationModel   (MLXAudioSTT/Models/Whisper/WhisperModel.swift)
     moonshine.MoonshineModel <-> class MoonshineModel : STTGenerationModel (MLXAudioSTT/Models/Moonshine/MoonshineModel.swift)
+    smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -40,6 +41,8 @@ from . import dsp  # noqa: F401
 from .stt import WhisperModel, WhisperConfig, STTGenerateParameters, STTOutput  # noqa: F401
 from .moonshine import (MoonshineModel, MoonshineConfig, MoonshineTokenizer, moonshine_sanitize, moonshine_frames,  # noqa: F401
                         moonshine_rotary_dim)
+from .smartturn import (SmartTurnModel, SmartTurnConfig, SmartTurnEncoderConfig, SmartTurnProcessorConfig,  # noqa: F401
+                        SmartTurnEndpointOutput, smart_turn_sanitize, smart_turn_expected_keys, smart_turn_read_directory)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

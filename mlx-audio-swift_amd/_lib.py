@@ -146,6 +146,13 @@ class MoonshineConfigC(C.Structure):
                 + [(n, C.c_int32) for n in ("bos_token_id", "eos_token_id", "decoder_start_token_id", "tie_word_embeddings")])
 
 
+class SmartTurnConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_mel_bins", "max_source_positions", "d_model", "encoder_attention_heads", "encoder_layers",
+                                          "encoder_ffn_dim", "k_proj_bias", "sampling_rate", "max_audio_seconds", "n_fft", "hop_length",
+                                          "normalize_audio")]
+                + [("threshold", C.c_float)])
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -273,6 +280,14 @@ SYMBOLS = {
     "mis_moonshine_decoder_forward": (C.c_int, [_P, _P, _P]),
     "mis_moonshine_launches_per_step": (C.c_int, [_P]),
     "mis_stt_moonshine_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.POINTER(SttParamsC), C.POINTER(_P), C.POINTER(C.c_int64), _P]),
+    "mis_smartturn_create": (C.c_int, [C.POINTER(SmartTurnConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_smartturn_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_smartturn_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_smartturn_finalize": (C.c_int, [_P]),
+    "mis_smartturn_destroy": (None, [_P]),
+    "mis_smartturn_launches": (C.c_int, [_P]),
+    "mis_smartturn_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_float, _P, _P, _P]),
+    "mis_smartturn_forward_features": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -365,6 +380,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_marvis_sample_logits": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_int,
                                                  C.c_int, C.c_int, _P]),
     "mis_debug_moonshine_stem_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, _P]),
+    "mis_debug_smartturn_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
+    "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 
