@@ -38,6 +38,28 @@ int64_t mis_debug_whisper_weight_bytes(const mis_whisper* c);
 mis_status mis_debug_mimi_decoder_tap(mis_mimi* m, const int32_t* codes, int batch, int n_q, int T, int stage, float* out, int64_t capacity,
                                       int32_t* channels, int64_t* length);
 
+/* csrc/gemm_debug.hip, tests (tests/test_gpu_gemm_ops.py): ONE launch of a GEMM launcher on caller-supplied host data.  16-bit operands are
+ * passed as raw payloads (uint16).  Operands are packed by the product's load-time kernels; W2 (optional, same shape as W) is packed with
+ * tile stride 2 at offset 1 behind W at offset 0 - the gate / up interleave, twice the output columns.  The output is poisoned (NaN) before
+ * the launch and lies between poisoned guard bands: an element never written comes back as NaN, a changed guard word fails the call with
+ * MIS_ERR_GENERATION_FAILED; every input is followed by NaN (codes: 0xFF), so an over-read shows in the result.  An arrangement the
+ * launcher does not build returns the launcher's status and launches nothing.  report (may be NULL) int32[8]: the instantiation that ran -
+ * kernel (0 k_gemm_skinny, 1 k_gemm_skinny_q, 2 k_gemm_skinny_q1, 3 k_gemm_pf), MT, R, epilogue, KSB, U, bits (16 = bf16 weights), scale
+ * format (0 bf16, 1 f16).
+ *   gemm_skinny: W bf16 [N][K], X bf16 [M][K] (M <= 64; packed as Mpad = 16 ceil(M / 16) rows, rows >= M zero), bias bf16 [output columns]
+ *     or NULL, epi / R / ksb / U / S the arguments of launch_gemm_skinny (S > K / 32: MIS_ERR_INVALID_INPUT).  out f32: epilogue 0 (partial)
+ *     the raw slabs [S][Mpad][cols]; 1 (bf16) [Mpad][cols]; 2 (silu(gate) * up) [Mpad][cols / 2], 3 / 4 (gelu / silu, packed) [Mpad][cols] un-packed.
+ *   gemm_skinny_q: the same on MLX affine-quantised operands (group size 64): wq uint32 [N][K bits / 32], scales / biases 16-bit [N][K / 64]
+ *     of sb_dtype (MIS_BF16 / MIS_F16); the launcher picks the one-shot or the streaming kernel as in the product (MIS_QGEMM_V2).
+ *   gemm_pf: X bf16 [M][K] row-major, epi 0 f32 [M][cols], 1 h = T(h + T(x W^T)) on the given h bf16 [M][cols], 2 silu(gate) * up [M][cols / 2]. */
+mis_status mis_debug_gemm_skinny(int device, const uint16_t* W, const uint16_t* W2, const uint16_t* X, const uint16_t* bias, int M, int N, int K,
+                                 int epi, int R, int ksb, int U, int S, float* out, int64_t capacity, int32_t* report);
+mis_status mis_debug_gemm_skinny_q(int device, int bits, int sb_dtype, const uint32_t* wq, const uint16_t* scales, const uint16_t* biases,
+                                   const uint32_t* wq2, const uint16_t* scales2, const uint16_t* biases2, const uint16_t* X, const uint16_t* bias,
+                                   int M, int N, int K, int epi, int R, int ksb, int S, float* out, int64_t capacity, int32_t* report);
+mis_status mis_debug_gemm_pf(int device, const uint16_t* W, const uint16_t* W2, const uint16_t* X, const uint16_t* h, int M, int N, int K, int epi,
+                             float* out, int64_t capacity, int32_t* report);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -372,6 +372,11 @@ DEBUG_SYMBOLS = {
     "mis_debug_device_cus": (C.c_int32, [C.c_int]),
     "mis_debug_sampler_failures": (C.c_int32, []),
     "mis_debug_choose_split": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mis_debug_gemm_skinny": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                        C.c_int64, _P]),
+    "mis_debug_gemm_skinny_q": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, _P, C.c_int64, _P]),
+    "mis_debug_gemm_pf": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),

@@ -1,0 +1,218 @@
+// gemm_debug.hip - test scaffolding (include/mi_speech_debug.h): ONE launch of a GEMM launcher of lm_kernels.hip / lm_qgemm.hip /
+// lm_prefill.hip on caller-supplied host data, so that tests/test_gpu_gemm_ops.py can hold the kernels to an operator-level reference.
+//
+// Every call packs its operands with the product's own load-time kernels (launch_pack_weight / launch_pack_qweight, k_pf_pack_rows),
+// launches once and copies the result back as float.  What makes a silent error visible:
+//   - the output is allocated as [guard | body | guard] (a guard is at least one tile row, 16 output rows), all of it filled with the
+//     byte 0xFF (a NaN in float32 and in bf16) before the launch: an element the kernel never wrote comes back as NaN, and a guard
+//     byte that changed fails the call (MIS_ERR_GENERATION_FAILED);
+//   - every input the kernel reads is followed by a guard of NaN (16-bit inputs: quiet NaN of their format; codes: 0xFF bytes), so a
+//     read past the end lands in the result instead of in a neighbour's memory.
+#include <cstring>
+#include "common.h"
+#include "lm_kernels.h"
+
+namespace {
+
+constexpr size_t IN_GUARD = 4096;                          // trailing guard of every input, elements
+constexpr uint16_t BF16_NAN = 0x7FC0, F16_NAN = 0x7E00;
+
+// device bytes [guard | body | guard], all 0xFF until somebody writes
+struct GuardedOut {
+    DevBuf<uint8_t> buf;
+    size_t guard = 0, body = 0;
+    void alloc(size_t body_bytes, size_t guard_bytes) {
+        guard = round_up(guard_bytes, 256); body = body_bytes;
+        buf.alloc(2 * guard + body);
+        HIP_CHECK(hipMemset(buf.p, 0xFF, 2 * guard + body));
+    }
+    uint8_t* p() { return buf.p + guard; }
+    void check_guards() {
+        std::vector<uint8_t> g(guard);
+        for (int side = 0; side < 2; ++side) {
+            HIP_CHECK(hipMemcpy(g.data(), side ? buf.p + guard + body : buf.p, guard, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < guard; ++i)
+                MIS_REQUIRE(g[i] == 0xFF, MIS_ERR_GENERATION_FAILED, "the kernel wrote %s its output (guard byte %zu)", side ? "behind" : "before", i);
+        }
+    }
+};
+
+// n 16-bit elements followed by IN_GUARD elements of `nan`; src == nullptr leaves the body to a pack kernel (pre-filled with `nan` too)
+void alloc16(DevBuf<uint16_t>& d, const uint16_t* src, size_t n, uint16_t nan) {
+    std::vector<uint16_t> h(n + IN_GUARD, nan);
+    if (src) std::copy(src, src + n, h.begin());
+    d.alloc(h.size());
+    HIP_CHECK(hipMemcpy(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+}
+void alloc_bytes(DevBuf<uint8_t>& d, const void* src, size_t n) {           // codes: 0xFF guard
+    std::vector<uint8_t> h(n + IN_GUARD, 0xFF);
+    if (src) memcpy(h.data(), src, n);
+    d.alloc(h.size());
+    HIP_CHECK(hipMemcpy(d.p, h.data(), h.size(), hipMemcpyHostToDevice));
+}
+
+// X [M][K] host bf16 -> packed fragments [K/32][MT][64][8] through k_pf_pack_rows (rows >= M zero), NaN behind
+void pack_x(DevBuf<uint16_t>& xpk, const uint16_t* X, int M, int K, int Mpad) {
+    std::vector<uint16_t> rows((size_t)Mpad * K, 0);
+    std::copy(X, X + (size_t)M * K, rows.begin());
+    DevBuf<uint16_t> drows;
+    alloc16(drows, rows.data(), rows.size(), BF16_NAN);
+    alloc16(xpk, nullptr, (size_t)Mpad * K, BF16_NAN);
+    launch_pf_pack_rows(drows.p, xpk.p, Mpad, K, 0);
+    HIP_CHECK(hipDeviceSynchronize());
+}
+
+void pack_w(DevBuf<uint16_t>& wp, const uint16_t* W, const uint16_t* W2, int N, int K) {
+    const int nt = N / 16;
+    alloc16(wp, nullptr, (size_t)(W2 ? 2 : 1) * N * K, BF16_NAN);
+    DevBuf<uint16_t> src;
+    for (int h = 0; h < (W2 ? 2 : 1); ++h) {
+        alloc16(src, h ? W2 : W, (size_t)N * K, BF16_NAN);
+        launch_pack_weight(src.p, wp.p, N, K, nt, W2 ? 2 : 1, h, 0);
+        HIP_CHECK(hipDeviceSynchronize());
+    }
+}
+
+void report_launch(int32_t* report) {
+    if (!report) return;
+    const GemmLaunchInfo& g = g_gemm_last_launch;
+    const int32_t r[8] = {g.kernel, g.MT, g.R, g.epi, g.ksb, g.U, g.bits, g.sbt};
+    std::copy(r, r + 8, report);
+}
+
+// copies the result of a skinny launch back as float: EPI_PARTIAL [S][Mpad][ncols], EPI_BF16 [Mpad][ncols], packed epilogues un-packed
+// with xpk_index into [Mpad][F] (F = ncols, or ncols / 2 behind the gate * up product)
+void fetch_skinny(GuardedOut& o, int epi, int S, int Mpad, int ncols, float* out, int64_t capacity) {
+    const int MT = Mpad / 16;
+    if (epi == EPI_PARTIAL) {
+        const size_t n = (size_t)S * Mpad * ncols;
+        MIS_REQUIRE((int64_t)n <= capacity, MIS_ERR_INVALID_INPUT, "output needs %zu floats", n);
+        HIP_CHECK(hipMemcpy(out, o.p(), n * 4, hipMemcpyDeviceToHost));
+        return;
+    }
+    std::vector<uint16_t> h(o.body / 2);
+    HIP_CHECK(hipMemcpy(h.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    const int F = epi == EPI_SILU_MUL ? ncols / 2 : ncols;
+    MIS_REQUIRE((int64_t)Mpad * F <= capacity, MIS_ERR_INVALID_INPUT, "output needs %zu floats", (size_t)Mpad * F);
+    if (epi == EPI_BF16) {
+        for (size_t i = 0; i < (size_t)Mpad * F; ++i) out[i] = bf16_to_f32(h[i]);
+        return;
+    }
+    const int Fpad = (int)round_up(F, 32);
+    for (int m = 0; m < Mpad; ++m)
+        for (int k = 0; k < Fpad; ++k) {
+            const uint16_t v = h[xpk_index(m, k, MT)];
+            if (k < F) out[(size_t)m * F + k] = bf16_to_f32(v);
+            else MIS_REQUIRE(v == 0xFFFF, MIS_ERR_GENERATION_FAILED, "packed output: column %d past the %d features was written", k, F);
+        }
+}
+
+size_t skinny_out_bytes(int epi, int S, int Mpad, int ncols) {
+    if (epi == EPI_PARTIAL) return (size_t)S * Mpad * ncols * 4;
+    if (epi == EPI_BF16) return (size_t)Mpad * ncols * 2;
+    const int F = epi == EPI_SILU_MUL ? ncols / 2 : ncols;
+    return round_up(F, 32) * (size_t)Mpad * 2;
+}
+
+}  // namespace
+
+extern "C" mis_status mis_debug_gemm_skinny(int device, const uint16_t* W, const uint16_t* W2, const uint16_t* X, const uint16_t* bias, int M,
+                                            int N, int K, int epi, int R, int ksb, int U, int S, float* out, int64_t capacity, int32_t* report) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(W && X && out && M >= 1 && M <= 64 && N >= 16 && N % 16 == 0 && K >= 32 && K % 32 == 0 && S >= 1, MIS_ERR_INVALID_INPUT,
+                "dense GEMM: 1..64 rows, N a multiple of 16, K a multiple of 32");
+    MIS_REQUIRE(epi >= EPI_PARTIAL && epi <= EPI_SILU_PACKED, MIS_ERR_INVALID_INPUT, "unknown epilogue %d", epi);
+    const int KT = K / 32, NT = (W2 ? 2 : 1) * (N / 16), ncols = NT * 16, Mpad = (int)round_up(M, 16);
+    MIS_REQUIRE(S <= KT, MIS_ERR_INVALID_INPUT, "%d K slices for %d k-tiles", S, KT);
+    MIS_REQUIRE(epi != EPI_SILU_MUL || W2, MIS_ERR_INVALID_INPUT, "the gate * up epilogue needs the interleaved second matrix");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint16_t> wp, xpk, db;
+    pack_w(wp, W, W2, N, K);
+    pack_x(xpk, X, M, K, Mpad);
+    if (bias) alloc16(db, bias, ncols, BF16_NAN);
+    GuardedOut o;
+    o.alloc(skinny_out_bytes(epi, S, Mpad, ncols), (size_t)16 * ncols * 4);
+    g_gemm_last_launch = GemmLaunchInfo{};
+    launch_gemm_skinny(epi, R, ksb, wp.p, xpk.p, o.p(), NT, KT, S, ncols, Mpad, 0, bias ? db.p : nullptr, U);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    report_launch(report);
+    o.check_guards();
+    fetch_skinny(o, epi, S, Mpad, ncols, out, capacity);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_gemm_skinny_q(int device, int bits, int sb_dtype, const uint32_t* wq, const uint16_t* scales, const uint16_t* biases,
+                                              const uint32_t* wq2, const uint16_t* scales2, const uint16_t* biases2, const uint16_t* X,
+                                              const uint16_t* bias, int M, int N, int K, int epi, int R, int ksb, int S, float* out,
+                                              int64_t capacity, int32_t* report) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(wq && scales && biases && X && out && M >= 1 && M <= 64 && N >= 16 && N % 16 == 0 && K >= 64 && K % 64 == 0 && S >= 1,
+                MIS_ERR_INVALID_INPUT, "quantised GEMM: 1..64 rows, N a multiple of 16, K a multiple of 64");
+    MIS_REQUIRE((bits == 8 || bits == 4) && (sb_dtype == MIS_BF16 || sb_dtype == MIS_F16), MIS_ERR_INVALID_INPUT, "8 or 4 bits, bf16 or f16 scales");
+    MIS_REQUIRE(epi >= EPI_PARTIAL && epi <= EPI_GELU_PACKED, MIS_ERR_INVALID_INPUT, "unknown epilogue %d", epi);
+    const bool two = wq2 != nullptr;
+    MIS_REQUIRE(!two || (scales2 && biases2), MIS_ERR_INVALID_INPUT, "second matrix without scales / biases");
+    MIS_REQUIRE(epi != EPI_SILU_MUL || two, MIS_ERR_INVALID_INPUT, "the gate * up epilogue needs the interleaved second matrix");
+    const int G = K / 64, NT = (two ? 2 : 1) * (N / 16), ncols = NT * 16, Mpad = (int)round_up(M, 16);
+    const uint16_t nan = sb_dtype == MIS_F16 ? F16_NAN : BF16_NAN;
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint8_t> qp, dq;
+    DevBuf<uint16_t> sb, dsc, dbi, xpk, db;
+    const size_t code_bytes = (size_t)N * K * bits / 8;
+    alloc_bytes(qp, nullptr, (two ? 2 : 1) * code_bytes);
+    alloc16(sb, nullptr, (size_t)NT * G * 32, nan);
+    for (int h = 0; h < (two ? 2 : 1); ++h) {
+        alloc_bytes(dq, h ? wq2 : wq, code_bytes);
+        alloc16(dsc, h ? scales2 : scales, (size_t)N * G, nan);
+        alloc16(dbi, h ? biases2 : biases, (size_t)N * G, nan);
+        launch_pack_qweight(bits, reinterpret_cast<const uint32_t*>(dq.p), dsc.p, dbi.p, qp.p, sb.p, N, K, two ? 2 : 1, h, 0);
+        HIP_CHECK(hipDeviceSynchronize());
+    }
+    pack_x(xpk, X, M, K, Mpad);
+    if (bias) alloc16(db, bias, ncols, BF16_NAN);
+    GuardedOut o;
+    o.alloc(skinny_out_bytes(epi, S, Mpad, ncols), (size_t)16 * ncols * 4);
+    g_gemm_last_launch = GemmLaunchInfo{};
+    launch_gemm_skinny_q(bits, epi, R, ksb, qp.p, sb.p, xpk.p, o.p(), NT, G, S, ncols, Mpad, 0, bias ? db.p : nullptr, sb_dtype);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    report_launch(report);
+    o.check_guards();
+    fetch_skinny(o, epi, S, Mpad, ncols, out, capacity);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_gemm_pf(int device, const uint16_t* W, const uint16_t* W2, const uint16_t* X, const uint16_t* h, int M, int N, int K,
+                                        int epi, float* out, int64_t capacity, int32_t* report) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(W && X && out && M >= 1 && N >= 16 && N % 16 == 0 && K >= 32 && K % 32 == 0, MIS_ERR_INVALID_INPUT,
+                "prefill GEMM: N a multiple of 16, K a multiple of 32");
+    MIS_REQUIRE(epi >= PF_F32 && epi <= PF_SILU, MIS_ERR_INVALID_INPUT, "unknown prefill epilogue %d", epi);
+    MIS_REQUIRE(epi != PF_RESID || h, MIS_ERR_INVALID_INPUT, "the residual epilogue needs h");
+    MIS_REQUIRE(epi != PF_SILU || W2, MIS_ERR_INVALID_INPUT, "the gate * up epilogue needs the interleaved second matrix");
+    const int ncols = (W2 ? 2 : 1) * N, ocols = epi == PF_SILU ? ncols / 2 : ncols;
+    const size_t n_out = (size_t)M * ocols, esz = epi == PF_F32 ? 4 : 2;
+    MIS_REQUIRE((int64_t)n_out <= capacity, MIS_ERR_INVALID_INPUT, "output needs %zu floats", n_out);
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint16_t> wp, dx;
+    pack_w(wp, W, W2, N, K);
+    alloc16(dx, X, (size_t)M * K, BF16_NAN);
+    GuardedOut o;
+    o.alloc(n_out * esz, (size_t)128 * ocols * esz);             // a whole 128-row block tile of rows >= M would still land in it
+    if (epi == PF_RESID) HIP_CHECK(hipMemcpy(o.p(), h, n_out * 2, hipMemcpyHostToDevice));
+    g_gemm_last_launch = GemmLaunchInfo{};
+    launch_gemm_pf(epi, dx.p, wp.p, o.p(), M, ncols, K, 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    report_launch(report);
+    o.check_guards();
+    if (epi == PF_F32) {
+        HIP_CHECK(hipMemcpy(out, o.p(), n_out * 4, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<uint16_t> hb(n_out);
+        HIP_CHECK(hipMemcpy(hb.data(), o.p(), n_out * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n_out; ++i) out[i] = bf16_to_f32(hb[i]);
+    }
+    MIS_API_END
+}

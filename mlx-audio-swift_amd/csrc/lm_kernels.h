@@ -60,6 +60,12 @@ void launch_pf_rows_rmsnorm(const bf16_t* rows, int src_rows, const int32_t* len
 void launch_pf_rmsnorm(const bf16_t* h, const bf16_t* wnorm, bf16_t* x, int rows, int d, float eps, hipStream_t s);
 void launch_pf_pack_rows(const bf16_t* rows, bf16_t* xpk, int Mpad, int d, hipStream_t s);
 
+// the instantiation the GEMM launchers of lm_kernels.hip / lm_qgemm.hip / lm_prefill.hip launched last on this thread (host bookkeeping only): the
+// mis_debug_gemm_* entry points report it, so that tests/test_gpu_gemm_ops.py can assert that every arrangement of the launcher tables ran.
+// kernel: 0 k_gemm_skinny, 1 k_gemm_skinny_q (streaming), 2 k_gemm_skinny_q1 (one-shot), 3 k_gemm_pf; -1 nothing launched yet
+struct GemmLaunchInfo { int kernel = -1, MT = 0, R = 0, epi = 0, ksb = 0, U = 0, bits = 0, sbt = 0; };
+extern thread_local GemmLaunchInfo g_gemm_last_launch;
+
 // split-K factor of a weight-streaming GEMM (items = n-tile groups, KT = k-tiles, ksb = waves per item), see the definition
 int gemm_choose_split(int items, int KT, int ksb, int s_max);
 

@@ -862,6 +862,8 @@ __global__ void __launch_bounds__((KSB == 1 ? 4 : KSB) * 64, 2) k_gemm_skinny(co
     }
 }
 
+thread_local GemmLaunchInfo g_gemm_last_launch;
+
 template <int MT>
 static void launch_gemm_mt(int epi, int R, int ksb, int U, const bf16_t* Wp, const bf16_t* X, void* out, int NT, int KT, int S,
                            int N_out, int Mpad, const bf16_t* bias, hipStream_t s) {
@@ -869,6 +871,7 @@ static void launch_gemm_mt(int epi, int R, int ksb, int U, const bf16_t* Wp, con
     dim3 grid(ksb == 1 ? (n_items + 3) / 4 : n_items), block((ksb == 1 ? 4 : ksb) * 64);
 #define GEMM_CASE(E, RR, KS, UU)                                                                              \
     if (epi == E && R == RR && ksb == KS && U == UU) {                                                        \
+        g_gemm_last_launch = GemmLaunchInfo{0, MT, RR, E, KS, UU, 16, 0};                                     \
         hipLaunchKernelGGL((k_gemm_skinny<MT, RR, E, KS, UU>), grid, block, 0, s, Wp, X, out, NT, KT, S, n_items, \
                            N_out, Mpad, bias);                                                                    \
         return;                                                                                               \

@@ -235,6 +235,7 @@ void launch_gemm_pf(int epi, const bf16_t* X, const bf16_t* Wp, void* C, int M, 
     MIS_REQUIRE(epi != PF_SILU || N % 32 == 0, MIS_ERR_GENERATION_FAILED, "prefill GEMM: gate / up tiles come in pairs");
     PfGemmParams p{X, Wp, C, M, N, K};
     dim3 grid(cdiv(N, PF_BN), cdiv(M, PF_BM)), block(256);
+    g_gemm_last_launch = GemmLaunchInfo{3, 0, 0, epi, 0, 0, 16, 0};
     if (epi == PF_F32) hipLaunchKernelGGL((k_gemm_pf<PF_F32>), grid, block, 0, s, p);
     else if (epi == PF_RESID) hipLaunchKernelGGL((k_gemm_pf<PF_RESID>), grid, block, 0, s, p);
     else if (epi == PF_SILU) hipLaunchKernelGGL((k_gemm_pf<PF_SILU>), grid, block, 0, s, p);

@@ -476,6 +476,7 @@ static void launch_qgemm1_mt(int epi, int R, int ksb, const void* Qp, const bf16
     dim3 grid(n_items), block(256);
 #define QGEMM1_CASE(E, RR, KS)                                                                                      \
     if (epi == E && R == RR && ksb == KS) {                                                                         \
+        g_gemm_last_launch = GemmLaunchInfo{2, MT, RR, E, KS, U, BITS, SBT};                                        \
         hipLaunchKernelGGL((k_gemm_skinny_q1<MT, RR, E, KS, BITS, U, SBT>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
                            N_out, Mpad, bias);                                                                      \
         return;                                                                                                     \
@@ -498,6 +499,7 @@ static void launch_qgemm_mt(int epi, int R, int ksb, const void* Qp, const bf16_
     dim3 grid(ksb == 1 ? (n_items + 3) / 4 : n_items), block(ksb == 8 ? 512 : 256);
 #define QGEMM_CASE(E, RR, KS)                                                                                       \
     if (epi == E && R == RR && ksb == KS) {                                                                         \
+        g_gemm_last_launch = GemmLaunchInfo{1, MT, RR, E, KS, U, BITS, SBT};                                        \
         hipLaunchKernelGGL((k_gemm_skinny_q<MT, RR, E, KS, BITS, U, SBT>), grid, block, 0, s, Qp, SB, X, out, NT, G, S, n_items, \
                            N_out, Mpad, bias);                                                                      \
         return;                                                                                                     \
