@@ -60,6 +60,43 @@ mis_status mis_debug_gemm_skinny_q(int device, int bits, int sb_dtype, const uin
 mis_status mis_debug_gemm_pf(int device, const uint16_t* W, const uint16_t* W2, const uint16_t* X, const uint16_t* h, int M, int N, int K, int epi,
                              float* out, int64_t capacity, int32_t* report);
 
+/* csrc/attn_debug.hip, tests (tests/test_gpu_attn_ops.py): ONE call of launch_attn_decode (csrc/lm_kernels.hip: k_attn_decode<D, NIT, XS, QP>
+ * or k_attn_decode2<NS>) on caller-supplied host data.  The fields carry the names and meanings of AttnParams (csrc/lm_kernels.h); 16-bit
+ * operands are raw payloads (uint16), NULL where AttnParams allows null.  The K and V^T caches are passed as raw IMAGES in the kernels'
+ * tiled layout (K [rows][Hkv][Smax/32][2][D/32][64][8], V^T [rows][Hkv][Smax/32][D/16][64][8], rows = cache_rows or batch) and uploaded
+ * unchanged - the caller decides what sits past kv_len; kcache_out / vtcache_out receive the images after the launch.  qp_w (QP launches
+ * only) is the row-major W_q bf16 [H D][H D], packed by launch_pack_weight; qp_KT is passed to the launcher as given.
+ * The attention output, qp_h_out and both caches lie between guard bands of the byte 0xFF (a NaN in bf16), and the output and qp_h_out
+ * bodies are pre-filled with it: an element never written comes back as NaN, a changed guard byte fails the call with
+ * MIS_ERR_GENERATION_FAILED, and a key read behind row rows - 1 of a cache is a NaN.  Every other input is followed by NaN (pos and
+ * active, which have no NaN: zeros, i.e. inactive rows at position 0), both RoPE tables included.  A shape the launcher rejects returns
+ * the launcher's status and launches nothing.
+ *   out f32 [Mpad][H D]: the output, un-packed with xpk_index when out_ld == 0, else the first H D columns of each row of out_ld (>= H D;
+ *     the columns behind must stay untouched); rows the kernel did not write (inactive, >= batch, append_only) are NaN.
+ *   qp_h_out uint16 [batch][H D] (QP launches; 0xFFFF where never written).
+ *   report (may be NULL) int32[6]: kernel (0 k_attn_decode, 1 k_attn_decode2; -1 nothing launched), D, NIT, XS, QP, NS. */
+typedef struct mis_debug_attn_args {
+    int32_t batch, Mpad, S, Nqkv, H, Hkv, D, Smax;
+    int32_t cache_rows, append_only, first_schedule, cross, cross_len, out_ld, rope_in_dtype;
+    int32_t qp_S, qp_KT;
+    float scale, qk_eps, qp_eps;
+    const float* qkv_part;                       /* [S][Mpad][Nqkv] (NULL with qp_w) */
+    const int32_t* pos;                          /* [Mpad] */
+    const uint8_t* active;                       /* [Mpad] */
+    const float *rope_cos, *rope_sin;            /* [Smax][D/2] or NULL */
+    const uint16_t *qnorm_w, *knorm_w;           /* bf16 [D] or NULL */
+    const uint16_t* qp_w;                        /* bf16 [H D][H D] row-major or NULL */
+    const uint16_t* qp_bias;                     /* bf16 [H D] or NULL */
+    const float* qp_slabs;                       /* [qp_S][Mpad][H D] */
+    const uint16_t *qp_h_in, *qp_lnw, *qp_lnb;   /* bf16 [Mpad][H D], [H D], [H D] */
+    const uint16_t *kcache, *vtcache;            /* images, rows x Hkv x Smax x D elements each */
+    uint16_t *kcache_out, *vtcache_out;
+    float* out;
+    uint16_t* qp_h_out;
+    int32_t* report;
+} mis_debug_attn_args;
+mis_status mis_debug_attn_decode(int device, const mis_debug_attn_args* args);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

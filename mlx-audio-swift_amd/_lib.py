@@ -364,6 +364,15 @@ SYMBOLS = {
                                       C.POINTER(C.c_int64), _P, C.POINTER(_P), C.POINTER(C.c_int64), _P, C.c_int, _P, _P, _P]),
 }
 
+class AttnDebugArgsC(C.Structure):
+    """mis_debug_attn_args (include/mi_speech_debug.h): one launch_attn_decode call on host data"""
+    _fields_ = ([(n, C.c_int32) for n in ("batch", "Mpad", "S", "Nqkv", "H", "Hkv", "D", "Smax", "cache_rows", "append_only", "first_schedule",
+                                          "cross", "cross_len", "out_ld", "rope_in_dtype", "qp_S", "qp_KT")] +
+                [(n, C.c_float) for n in ("scale", "qk_eps", "qp_eps")] +
+                [(n, _P) for n in ("qkv_part", "pos", "active", "rope_cos", "rope_sin", "qnorm_w", "knorm_w", "qp_w", "qp_bias", "qp_slabs",
+                                   "qp_h_in", "qp_lnw", "qp_lnb", "kcache", "vtcache", "kcache_out", "vtcache_out", "out", "qp_h_out", "report")])
+
+
 # diagnostics / test scaffolding: include/mi_speech_debug.h (not part of the product surface)
 DEBUG_SYMBOLS = {
     "mis_debug_launch_floor": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
@@ -377,6 +386,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_gemm_skinny_q": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_gemm_pf": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    "mis_debug_attn_decode": (C.c_int, [C.c_int, C.POINTER(AttnDebugArgsC)]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),

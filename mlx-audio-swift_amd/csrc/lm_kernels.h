@@ -74,6 +74,8 @@ bool attn_qp_ok(const AttnParams& p);
 struct AttnParams {
     const float* qkv_part;   // [S][Mpad][Nqkv]
     int S, Mpad, Nqkv;
+    // CACHE CONTRACT: cache contents at positions >= kv_len of a row must be FINITE (the kernels multiply P = 0 with whatever the last
+    // tile holds past kv_len, and 0 * NaN is NaN); the engines zero them (lm_reset, k_scatter_kv).  Smax is a multiple of 32 (whole tiles).
     bf16_t* kcache;          // layer slice [B][Hkv][Smax][D]
     bf16_t* vtcache;         // layer slice [B][Hkv][D][Smax]
     const int* pos;          // [Mpad] position of the token being processed
@@ -108,6 +110,11 @@ struct AttnParams {
     int first_schedule;      // 1: never k_attn_decode2 - the prefill's two arrangements must give the same bits whatever the batch size
 };
 void launch_attn_decode(const AttnParams& p, int batch, hipStream_t s);
+// the instantiation launch_attn_decode launched last on this thread (host bookkeeping only, as g_gemm_last_launch): mis_debug_attn_decode
+// reports it, so that tests/test_gpu_attn_ops.py can assert which of the eleven instantiations a case reached.
+// kernel: 0 k_attn_decode<D, NIT, XS, QP>, 1 k_attn_decode2<NS>; -1 nothing launched yet
+struct AttnLaunchInfo { int kernel = -1, D = 0, NIT = 0, XS = 0, QP = 0, NS = 0; };
+extern thread_local AttnLaunchInfo g_attn_last_launch;
 
 #define SAMP_MAX_CHUNKS 64
 #define SAMP_CLUSTER_NB 8

@@ -1151,6 +1151,10 @@ int gemm_choose_split(int items, int KT, int ksb, int s_max) {
 // the score registers line up with the P.V A-operand, B = Q^T), online softmax in f32, O += P . V with
 // P split into bf16 hi + lo parts (f32-accurate probabilities) and V^T tiles as B operand.  Epilogue:
 // cross-wave log-sum-exp combine through LDS.   (LlamaTTS.swift:235-266; SDPA semantics: oracle/llama.py)
+// CACHE CONTRACT: cache contents at positions >= kv_len of a row must be FINITE; the engines zero them (lm_reset, k_scatter_kv).  The
+// mask sets the SCORE of such a key to -inf, so its probability is exactly 0 - but the P.V product still multiplies that 0 with whatever
+// the last tile holds past kv_len, and 0 * NaN (or 0 * inf) is NaN.  Tiles past the last one are never loaded.  Held by
+// tests/test_gpu_attn_ops.py (stale finite values past kv_len must not change a bit of the result).
 // Measured alternative (round 2, removed again): waves 1..7 request their first tile at once while WAVE 0 ALONE runs the whole
 // prologue barrier-free, the second tile of a pair requested after the single barrier (counted wait in front of the first tile's
 // math).  Parity-green (103 GPU tests) and slower: 14.24 -> 14.58 us at context 368, bench 173.9 -> 171.1 audio-s/s
@@ -1821,6 +1825,9 @@ __global__ void __launch_bounds__(512) k_attn_decode2(AttnParams p) {
         if constexpr (NS > 1) asm volatile("" : "+v"(sv[NS > 1 ? 1 : 0][0]), "+v"(sv[NS > 1 ? 1 : 0][1]), "+v"(sv[NS > 1 ? 1 : 0][2]));
         if constexpr (NS > 2) asm volatile("" : "+v"(sv[NS > 2 ? 2 : 0][0]), "+v"(sv[NS > 2 ? 2 : 0][1]), "+v"(sv[NS > 2 ? 2 : 0][2]));
         if constexpr (NS > 3) asm volatile("" : "+v"(sv[NS > 3 ? 3 : 0][0]), "+v"(sv[NS > 3 ? 3 : 0][1]), "+v"(sv[NS > 3 ? 3 : 0][2]));
+        // (The sum starts from slab 0 itself, where k_attn_decode starts from 0.0f: a -0.0 element of a SINGLE slab stays -0.0 here and
+        // becomes +0.0 there - the sign of a zero in the appended key / value is the one bit the two schedules do not share;
+        // tests/test_gpu_attn_ops.py::test_negative_zero_slab.)
         // slab sum (slab order 0, 1, ...: deterministic), T(), into the wave's strip in linear order (all 192 units are stored: rows
         // past G + 1 hold don't-care copies of unit 0 - a lane predicate here would be a branch)
 #pragma unroll
@@ -2051,6 +2058,8 @@ size_t attn_smem_bytes(int G, int D) {
 }
 
 // the cross-attention launches whose prologue can take the LayerNorm glue and the query projection (k_attn_decode<64, 2, true, QP>)
+thread_local AttnLaunchInfo g_attn_last_launch;
+
 bool attn_qp_ok(const AttnParams& p) {
     const char* xe = getenv("MIS_ATTN_XS");
     return !(xe && atoi(xe) == 0) && p.cross && p.D == 64 && p.H == p.Hkv && !p.append_only && !p.cache_rows && !p.rope_cos && !p.qnorm_w &&
@@ -2064,6 +2073,10 @@ void launch_attn_decode(const AttnParams& p, int batch, hipStream_t s) {
     MIS_REQUIRE(smem <= 64 * 1024, MIS_ERR_INVALID_INPUT, "attention LDS footprint too large");
     MIS_REQUIRE(p.qp_w || (p.S >= 1 && p.S <= 8), MIS_ERR_GENERATION_FAILED, "attention prologue reduces at most 8 split-K slabs (got %d)", p.S);
     MIS_REQUIRE(((uintptr_t)p.active & 3) == 0, MIS_ERR_GENERATION_FAILED, "attention: the active-flag array must be 4-byte aligned");
+    // (checked for every path: a launch that carries qp_w has no qkv_part for any other kernel to read)
+    MIS_REQUIRE(!p.qp_w || attn_qp_ok(p), MIS_ERR_GENERATION_FAILED, "attention: the query-projection prologue does not apply to this launch");
+    // both schedules address the caches in whole 32-key tiles (the engines round Smax to 64)
+    MIS_REQUIRE(p.Smax >= 32 && p.Smax % 32 == 0, MIS_ERR_INVALID_INPUT, "attention: %d cache positions are not a multiple of the 32-key tile", p.Smax);
     dim3 grid(p.Hkv, batch), block(512);
     const int n_el = (G + 2) * p.D;
     // second schedule (k_attn_decode2) where it applies: head_dim 128, RoPE tables, no q/k norm, <= 4 slabs, a decode step (the batched
@@ -2074,6 +2087,7 @@ void launch_attn_decode(const AttnParams& p, int batch, hipStream_t s) {
         // k_attn_decode2 is compiled for 0 .. ATT2_MAX_J key tiles per wave (its switch has no case beyond): the cache must not hold more
         MIS_REQUIRE((p.Smax / 32 + ATT_WAVES - 1) / ATT_WAVES <= ATT2_MAX_J, MIS_ERR_GENERATION_FAILED,
                     "attention: %d cache positions need more than %d key tiles per wave", p.Smax, ATT2_MAX_J);
+        g_attn_last_launch = AttnLaunchInfo{1, 128, 0, 0, 0, p.S <= 3 ? p.S : 4};
         switch (p.S) {
             case 1: hipLaunchKernelGGL((k_attn_decode2<1>), grid, block, sm2, s, p); break;
             case 2: hipLaunchKernelGGL((k_attn_decode2<2>), grid, block, sm2, s, p); break;
@@ -2092,23 +2106,26 @@ void launch_attn_decode(const AttnParams& p, int batch, hipStream_t s) {
 #endif
     const char* xe = getenv("MIS_ATTN_XS");                                                // 0: the pair-at-a-time loop for cross-attention too (A/B,
     const bool xs_on = !(xe && atoi(xe) == 0);                                             // parity tests: read per launch)
+    MIS_REQUIRE(p.D == 64 || p.D == 128, MIS_ERR_INVALID_INPUT, "head_dim must be 64 or 128");
+    g_attn_last_launch = AttnLaunchInfo{0, p.D, attn_nit(G, p.D), 0, 0, 0};          // (the XS / QP branch below completes it)
     if (p.D == 128 && n_el <= 1024) hipLaunchKernelGGL((k_attn_decode<128, 2>), grid, block, smem, s, p2);
     else if (p.D == 128) hipLaunchKernelGGL((k_attn_decode<128, 5>), grid, block, smem, s, p2);
     else if (p.D == 64 && n_el <= 1024 && p.cross && !p.append_only && !p.cache_rows && xs_on && (p.cross_len + 31) / 32 >= ATT_WAVES * ATT_XS_MIN_J &&
              (p.cross_len + 31) / 32 <= ATT_WAVES * ATT_XS_MAX_J)
     {
         if (p.qp_w) {                                                                       // LayerNorm + query projection in the prologue
-            MIS_REQUIRE(attn_qp_ok(p), MIS_ERR_GENERATION_FAILED, "attention: the query-projection prologue does not apply to this launch");
+            g_attn_last_launch = AttnLaunchInfo{0, 64, 2, 1, p.qp_S <= 4 ? 4 : 8, 0};
             AttnParams pq = p2;                            // (the kernel's unconditional dummy loads - norm weights, RoPE rows - read qkv_part[0])
             if (!pq.qkv_part) pq.qkv_part = pq.qp_slabs;
             const AttnParams& p2 = pq;
             const size_t smq = smem + ATT_QP_LDS;
             if (p.qp_S <= 4) hipLaunchKernelGGL((k_attn_decode<64, 2, true, 4>), grid, block, smq, s, p2);
             else hipLaunchKernelGGL((k_attn_decode<64, 2, true, 8>), grid, block, smq, s, p2);
-        } else
-        hipLaunchKernelGGL((k_attn_decode<64, 2, true>), grid, block, smem, s, p2);       // cross-attention: two pairs of tiles in flight
+        } else {
+            g_attn_last_launch.XS = 1;                                                      // cross-attention: two pairs of tiles in flight
+            hipLaunchKernelGGL((k_attn_decode<64, 2, true>), grid, block, smem, s, p2);
+        }
     }
     else if (p.D == 64 && n_el <= 1024) hipLaunchKernelGGL((k_attn_decode<64, 2>), grid, block, smem, s, p2);
-    else if (p.D == 64) hipLaunchKernelGGL((k_attn_decode<64, 3>), grid, block, smem, s, p2);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "head_dim must be 64 or 128");
+    else hipLaunchKernelGGL((k_attn_decode<64, 3>), grid, block, smem, s, p2);
 }

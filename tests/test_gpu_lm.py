@@ -242,9 +242,9 @@ def test_short_prompt_prefill_on_the_decode_step_kernels(lens, monkeypatch):
 def test_second_attention_schedule_matches_the_oracle():
     """k_attn_decode2 (wave-local prologue, counted waits, one tile in flight per wave while the previous one is multiplied) - the decode
     step's attention at head_dim 128 - against the oracle at contexts that give the waves 0 / 1 / 2 / 3 tiles each (<= 256, 257..512,
-    > 512 keys) and with the new key landing in every wave's last tile.  (Rounds 3-4 also held it to the first schedule through an
-    environment switch: bit-identical then, profiles/r04_parity_observed.json; the first schedule still serves the batched prefill, whose
-    tests compare the two on the same keys.)"""
+    > 512 keys) and with the new key landing in every wave's last tile.  (Its equality with the first schedule, bit for bit on the same
+    inputs, is held at the operator level: tests/test_gpu_attn_ops.py::test_second_schedule_and_its_equality_with_the_first, through
+    AttnParams::first_schedule.)"""
     from gpu_util import logits_errors, record
     cfg = ollama.LlamaConfig(**{**ollama.TINY.__dict__, "num_hidden_layers": 2})
     W, oracle, dev = lm_pair(cfg)
