@@ -11,6 +11,7 @@
 // with residual epilogue) then Snake + the stride-s conv (k = 2s, pad ceil(s/2)) as a 3-tap conv over the phase-split tensor, last
 // conv k3; residual VQ: in_proj GEMM, nearest code of the L2-normalised latent (first index on ties), residual -= the decode table row.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 
@@ -24,8 +25,7 @@ struct mis_dac {
     mis_dac_config cfg{};
     int latent = 0;
     hipStream_t stream = nullptr;
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"DAC"};
     bool finalized = false;
     DevBuf<float> arena;
     struct Lin { size_t w = 0, b = 0; int M = 0, K = 0; };
@@ -125,28 +125,11 @@ extern "C" mis_status mis_dac_set_tensor(mis_dac* c, const char* name_, const vo
         size_t pos;
         while ((pos = name.find(rep.first)) != std::string::npos) name.replace(pos, strlen(rep.first), rep.second);
     }
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(c->device));
-    size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((bf16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    c->raw[name] = std::move(v);
-    c->raw_shape[name] = sh;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    c->raw.put(name, host.data(), dtype, shape, ndim);
     MIS_API_END
-}
-
-static const std::vector<float>& dneed(mis_dac* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "DAC weight missing: %s", name.c_str());
-    MIS_REQUIRE(c->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "DAC weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 extern "C" mis_status mis_dac_finalize(mis_dac* c) {
@@ -159,8 +142,8 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
     auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
     // w = g * v / (||v|| + 1e-12), norm over all axes except `keep` (0: per output channel; 2: per input channel)
     auto wn = [&](const std::string& p, int64_t co, int64_t k, int64_t ci, int keep) {
-        const auto& v = dneed(c, p + ".weight_v", {co, k, ci});
-        const auto& g = keep == 0 ? dneed(c, p + ".weight_g", {co, 1, 1}) : dneed(c, p + ".weight_g", {1, 1, ci});
+        const auto& v = c->raw.need(p + ".weight_v", {co, k, ci}).v;
+        const auto& g = keep == 0 ? c->raw.need(p + ".weight_g", {co, 1, 1}).v : c->raw.need(p + ".weight_g", {1, 1, ci}).v;
         std::vector<float> w(v.size());
         const int64_t groups = keep == 0 ? co : ci;
         std::vector<double> nrm(groups, 0.0);
@@ -177,11 +160,11 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {              // -> A^T [(j*ci + c)][co]
         std::vector<float> w = wn(p, co, k, ci, 0), at((size_t)k * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t i = 0; i < ci; ++i) at[(j * ci + i) * co + o] = w[(o * k + j) * ci + i];
-        mis_dac::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(dneed(c, p + ".bias", {co}));
+        mis_dac::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(c->raw.need(p + ".bias", {co}).v);
         return L;
     };
     auto snake = [&](const std::string& p, int64_t C, size_t& a, size_t& ra) {
-        const auto& al = dneed(c, p, {1, 1, C});
+        const auto& al = c->raw.need(p, {1, 1, C}).v;
         std::vector<float> rv(C);
         for (int64_t i = 0; i < C; ++i) rv[i] = 1.0f / (al[i] + 1e-9f);
         a = push(al); ra = push(rv);
@@ -190,9 +173,9 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
         std::vector<float> tables((size_t)cf.n_codebooks * bins * D);
         for (int q = 0; q < cf.n_codebooks; ++q) {
             const std::string p = "quantizer.quantizers." + std::to_string(q);
-            const auto& cb = dneed(c, p + ".codebook.weight", {bins, cd});
+            const auto& cb = c->raw.need(p + ".codebook.weight", {bins, cd}).v;
             std::vector<float> w = wn(p + ".outProj", D, 1, cd, 0);
-            const auto& b = dneed(c, p + ".outProj.bias", {D});
+            const auto& b = c->raw.need(p + ".outProj.bias", {D}).v;
             for (int64_t v = 0; v < bins; ++v) for (int64_t o = 0; o < D; ++o) {
                 float acc = 0.0f;
                 for (int64_t k = 0; k < cd; ++k) acc += w[o * cd + k] * cb[v * cd + k];
@@ -213,7 +196,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
             std::vector<float> w = wn(p + ".1", cout, k, cin, 2), at((size_t)s * 2 * cin * cout);
             for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t i = 0; i < cin; ++i) for (int64_t o = 0; o < cout; ++o)
                 at[((ph * 2 + j) * cin + i) * cout + o] = w[(o * k + ((ph + pad) % s + s * j)) * cin + i];
-            B.ct.M = (int)cout; B.ct.K = (int)(2 * cin); B.ct.w = push(at); B.ct.b = push(dneed(c, p + ".1.bias", {cout}));
+            B.ct.M = (int)cout; B.ct.K = (int)(2 * cin); B.ct.w = push(at); B.ct.b = push(c->raw.need(p + ".1.bias", {cout}).v);
         }
         const int dils[3] = {1, 3, 9};
         for (int ri = 0; ri < 3; ++ri) {
@@ -233,19 +216,19 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
         snake("decoder.model." + std::to_string(n + 1) + ".alpha", cl, c->fin_a, c->fin_ra);
         std::vector<float> w = wn("decoder.model." + std::to_string(n + 2), 1, 7, cl, 0);
         c->fin_w = push(w);                                              // [1][7][C] == [7][C]
-        c->fin_b = dneed(c, "decoder.model." + std::to_string(n + 2) + ".bias", {1})[0];
+        c->fin_b = c->raw.need("decoder.model." + std::to_string(n + 2) + ".bias", {1}).v[0];
     }
     // ---- encoder (optional): dimensions are read off the tensors
     c->has_encoder = false;
     {
-        auto e0 = c->raw_shape.find("encoder.block.0.weight_v");
-        if (e0 != c->raw_shape.end()) {
-            MIS_REQUIRE(e0->second.size() == 3 && e0->second[1] == 7 && e0->second[2] == 1, MIS_ERR_INVALID_INPUT, "bad DAC encoder stem");
-            int64_t ch = e0->second[0];
+        const HostTensor* e0 = c->raw.find("encoder.block.0.weight_v");
+        if (e0) {
+            MIS_REQUIRE(e0->shape.size() == 3 && e0->shape[1] == 7 && e0->shape[2] == 1, MIS_ERR_INVALID_INPUT, "bad DAC encoder stem");
+            int64_t ch = e0->shape[0];
             c->enc_dim = (int)ch;
             {
                 std::vector<float> w = wn("encoder.block.0", ch, 7, 1, 0);          // [C][7][1] == [C][7]
-                c->enc_first_w = push(w); c->enc_first_b = push(dneed(c, "encoder.block.0.bias", {ch}));
+                c->enc_first_w = push(w); c->enc_first_b = push(c->raw.need("encoder.block.0.bias", {ch}).v);
             }
             c->enc_blocks.clear();
             c->hop = 1;
@@ -253,11 +236,11 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
             const int dils[3] = {1, 3, 9};
             for (;; ++li) {
                 const std::string p = "encoder.block." + std::to_string(li) + ".block";
-                auto dn = c->raw_shape.find(p + ".4.weight_v");
-                if (dn == c->raw_shape.end()) break;
-                MIS_REQUIRE(dn->second.size() == 3 && dn->second[2] == ch && dn->second[1] % 2 == 0, MIS_ERR_INVALID_INPUT, "bad DAC encoder block %d", li);
+                const HostTensor* dn = c->raw.find(p + ".4.weight_v");
+                if (!dn) break;
+                MIS_REQUIRE(dn->shape.size() == 3 && dn->shape[2] == ch && dn->shape[1] % 2 == 0, MIS_ERR_INVALID_INPUT, "bad DAC encoder block %d", li);
                 mis_dac::EncBlk E{};
-                E.cin = (int)ch; E.cout = (int)dn->second[0]; E.stride = (int)dn->second[1] / 2;
+                E.cin = (int)ch; E.cout = (int)dn->shape[0]; E.stride = (int)dn->shape[1] / 2;
                 for (int ri = 0; ri < 3; ++ri) {
                     const std::string q = p + "." + std::to_string(ri) + ".block";
                     snake(q + ".0.alpha", ch, E.ru[ri].a1, E.ru[ri].ra1);
@@ -280,7 +263,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
                                 for (int co = 0; co < E.cout; ++co)
                                     at[(((size_t)qi * ch * sdn) + (size_t)ci * sdn + r) * E.cout + co] = w[((size_t)co * K + j) * ch + ci];
                             }
-                    E.down.M = E.cout; E.down.K = 3 * sdn * (int)ch; E.down.w = push(at); E.down.b = push(dneed(c, p + ".4.bias", {E.cout}));
+                    E.down.M = E.cout; E.down.K = 3 * sdn * (int)ch; E.down.w = push(at); E.down.b = push(c->raw.need(p + ".4.bias", {E.cout}).v);
                 }
                 c->hop *= E.stride;
                 ch = E.cout;
@@ -294,7 +277,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
                 const std::string p = "quantizer.quantizers." + std::to_string(q);
                 mis_dac::VqEnc v{};
                 v.in_proj = conv(p + ".inProj", cd, 1, D);
-                const auto& cb = dneed(c, p + ".codebook.weight", {bins, cd});
+                const auto& cb = c->raw.need(p + ".codebook.weight", {bins, cd}).v;
                 std::vector<float> cn((size_t)bins * cd), cn2(bins);
                 for (int64_t k = 0; k < bins; ++k) {                         // descriptNormalize (DescriptQuantization.swift:8-11)
                     float n2 = 0.0f;
@@ -312,7 +295,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
     }
     c->arena.alloc(arena.size());
     HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    c->raw.clear(); c->raw_shape.clear();
+    c->raw.clear();
     c->finalized = true;
     MIS_API_END
 }

@@ -10,6 +10,7 @@
 // the hidden state is exchanged through global memory, one monotonic counter barrier per step (release fence -> atomic arrive;
 // agent-scope poll -> acquire fence), bounded spins so a lost block cannot hang the GPU.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 
@@ -22,8 +23,7 @@ struct mis_encodec {
     int device = 0;
     mis_encodec_config cfg{};
     hipStream_t stream = nullptr;
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"Encodec"};
     bool finalized = false;
     int n_q = 0, dim0 = 0;
     DevBuf<float> arena;
@@ -241,28 +241,11 @@ extern "C" mis_status mis_encodec_set_tensor(mis_encodec* c, const char* name_, 
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     std::string name = name_;
     if (name.rfind("encoder.", 0) == 0) return MIS_OK;                    // encode path: not built
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(c->device));
-    size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((bf16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    c->raw[name] = std::move(v);
-    c->raw_shape[name] = sh;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    c->raw.put(name, host.data(), dtype, shape, ndim);
     MIS_API_END
-}
-
-static const std::vector<float>& eneed(mis_encodec* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "Encodec weight missing: %s", name.c_str());
-    MIS_REQUIRE(c->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Encodec weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
@@ -273,18 +256,18 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
     std::vector<float> arena;
     auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {              // [co][k][ci] -> A^T [(j*ci + c)][co]
-        const auto& w = eneed(c, p + ".conv.weight", {co, k, ci});
+        const auto& w = c->raw.need(p + ".conv.weight", {co, k, ci}).v;
         std::vector<float> at((size_t)k * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t i = 0; i < ci; ++i) at[(j * ci + i) * co + o] = w[(o * k + j) * ci + i];
-        mis_encodec::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(eneed(c, p + ".conv.bias", {co}));
-        if (cf.group_norm) { L.nw = push(eneed(c, p + ".norm.weight", {co})); L.nb = push(eneed(c, p + ".norm.bias", {co})); }
+        mis_encodec::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(c->raw.need(p + ".conv.bias", {co}).v);
+        if (cf.group_norm) { L.nw = push(c->raw.need(p + ".norm.weight", {co}).v); L.nb = push(c->raw.need(p + ".norm.bias", {co}).v); }
         return L;
     };
     {
         const int64_t D = cf.codebook_dim;
         std::vector<float> tables((size_t)c->n_q * cf.codebook_size * D);
         for (int q = 0; q < c->n_q; ++q) {
-            const auto& e = eneed(c, "quantizer.layers." + std::to_string(q) + ".codebook.embed", {cf.codebook_size, D});
+            const auto& e = c->raw.need("quantizer.layers." + std::to_string(q) + ".codebook.embed", {cf.codebook_size, D}).v;
             memcpy(tables.data() + (size_t)q * cf.codebook_size * D, e.data(), e.size() * 4);
         }
         c->tables = push(tables);
@@ -296,11 +279,11 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
     for (int j = 0; j < cf.num_lstm_layers; ++j) {
         const std::string p = "decoder.layers.1.lstm." + std::to_string(j);
         mis_encodec::Lstm L;
-        const auto& wx = eneed(c, p + ".Wx", {4 * dim, dim});
+        const auto& wx = c->raw.need(p + ".Wx", {4 * dim, dim}).v;
         std::vector<float> at((size_t)dim * 4 * dim);
         for (int64_t o = 0; o < 4 * dim; ++o) for (int64_t i = 0; i < dim; ++i) at[i * 4 * dim + o] = wx[o * dim + i];
-        L.xproj.M = (int)(4 * dim); L.xproj.K = (int)dim; L.xproj.w = push(at); L.xproj.b = push(eneed(c, p + ".bias", {4 * dim}));
-        L.wh = push(eneed(c, p + ".Wh", {4 * dim, dim}));
+        L.xproj.M = (int)(4 * dim); L.xproj.K = (int)dim; L.xproj.w = push(at); L.xproj.b = push(c->raw.need(p + ".bias", {4 * dim}).v);
+        L.wh = push(c->raw.need(p + ".Wh", {4 * dim, dim}).v);
         c->lstm.push_back(L);
     }
     c->ups.clear();
@@ -311,12 +294,12 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
         U.s = (int)s; U.cin = (int)cin; U.cout = (int)cout;
         {   // causal transposed conv: out[s*n + ph] = sum_j sum_c W[co][ph + s*j][c] x[c][n - j]  (full conv, right trim k - s)
             const std::string p = "decoder.layers." + std::to_string(li + 1);
-            const auto& w = eneed(c, p + ".conv.weight", {cout, k, cin});
+            const auto& w = c->raw.need(p + ".conv.weight", {cout, k, cin}).v;
             std::vector<float> at((size_t)s * 2 * cin * cout);
             for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t i = 0; i < cin; ++i) for (int64_t o = 0; o < cout; ++o)
                 at[((ph * 2 + j) * cin + i) * cout + o] = w[(o * k + (ph + s * j)) * cin + i];
-            U.ct.M = (int)cout; U.ct.K = (int)(2 * cin); U.ct.w = push(at); U.ct.b = push(eneed(c, p + ".conv.bias", {cout}));
-            if (cf.group_norm) { U.ct.nw = push(eneed(c, p + ".norm.weight", {cout})); U.ct.nb = push(eneed(c, p + ".norm.bias", {cout})); }
+            U.ct.M = (int)cout; U.ct.K = (int)(2 * cin); U.ct.w = push(at); U.ct.b = push(c->raw.need(p + ".conv.bias", {cout}).v);
+            if (cf.group_norm) { U.ct.nw = push(c->raw.need(p + ".norm.weight", {cout}).v); U.ct.nb = push(c->raw.need(p + ".norm.bias", {cout}).v); }
         }
         li += 2;
         dim = cout;
@@ -338,7 +321,7 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
     c->last = conv("decoder.layers." + std::to_string(li + 1), cf.audio_channels, cf.last_kernel_size, dim);
     c->arena.alloc(arena.size());
     HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    c->raw.clear(); c->raw_shape.clear();
+    c->raw.clear();
     c->finalized = true;
     MIS_API_END
 }

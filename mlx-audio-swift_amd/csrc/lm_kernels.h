@@ -10,6 +10,7 @@ __host__ __device__ __forceinline__ size_t xpk_index(int m, int k, int MT) {
 enum { EPI_PARTIAL = 0, EPI_BF16 = 1, EPI_SILU_MUL = 2, EPI_GELU_PACKED = 3, EPI_SILU_PACKED = 4 };
 
 void launch_convert_to_bf16(const void* src, int dtype, bf16_t* dst, size_t n, hipStream_t s);
+void launch_bf16_to_f32(const bf16_t* src, float* dst, size_t n, hipStream_t s);      // flat, n > 0
 // MLX affine-quantised matrix (uint32 words, per-group scales / biases of dtype sb_dtype = mis_dtype) -> bf16 [N][K]
 void launch_dequant_affine(const uint32_t* wq, const void* scales, const void* biases, int sb_dtype, bf16_t* dst, int N, int K,
                            int group, int bits, hipStream_t s);

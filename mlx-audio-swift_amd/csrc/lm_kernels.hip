@@ -34,6 +34,11 @@ __global__ void k_convert_to_bf16(const void* __restrict__ src, int dtype, bf16_
     else dst[i] = ((const bf16_t*)src)[i];
 }
 
+__global__ void k_bf16_to_f32(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = bf16_to_f32(src[i]);
+}
+
 // row-major [N][K] bf16 -> packed tiles; destination tile index = nt * tile_stride + tile_offset
 // (gate/up interleave: stride 2, offset 0/1).  Rows >= N are zero.  One thread per 16-byte unit.
 __global__ void k_pack_weight(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst, int N, int K, int NT,
@@ -90,6 +95,9 @@ void launch_dequant_affine(const uint32_t* wq, const void* scales, const void* b
 void launch_convert_to_bf16(const void* src, int dtype, bf16_t* dst, size_t n, hipStream_t s) {
     if (!n) return;
     hipLaunchKernelGGL(k_convert_to_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dtype, dst, n);
+}
+void launch_bf16_to_f32(const bf16_t* src, float* dst, size_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
 }
 void launch_pack_weight(const bf16_t* src, bf16_t* dst, int N, int K, int NT, int tile_stride, int tile_offset,
                         hipStream_t s) {

@@ -20,6 +20,7 @@
 // bottom-right causal mask), RoPE at the absolute position.  Every output column runs the same instruction sequence in both modes, so
 // the stream is bitwise equal to whole decode while the window holds every key (frames 0 .. context/s).
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 #include "q3_kernels.h"
@@ -38,8 +39,7 @@ struct mis_mimi {
     hipStream_t stream = nullptr;
     mis_mimi_config cfg{};
     int up_s = 2;                        // upsample stride = encoder frame rate / frame rate
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"Mimi"};
     bool finalized = false;
     DevBuf<float> arena;
     struct Lin { size_t w = 0, b = (size_t)-1; int M = 0, K = 0; };
@@ -230,28 +230,11 @@ extern "C" mis_status mis_mimi_set_tensor(mis_mimi* m, const char* name, const v
     MIS_API_BEGIN
     MIS_REQUIRE(m && name && data && shape, MIS_ERR_INVALID_INPUT, "null argument");
     MIS_REQUIRE(!m->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(m->device));
-    const size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((bf16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    m->raw[name] = std::move(v);
-    m->raw_shape[name] = sh;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    m->raw.put(name, host.data(), dtype, shape, ndim);
     MIS_API_END
-}
-
-static const std::vector<float>& mneed(mis_mimi* m, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = m->raw.find(name);
-    MIS_REQUIRE(it != m->raw.end(), MIS_ERR_NOT_INITIALIZED, "Mimi weight missing: %s", name.c_str());
-    MIS_REQUIRE(m->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Mimi weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 static bool mimi_is_encoder_key(const std::string& k) {
@@ -276,22 +259,22 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
         return L;
     };
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {                      // [co][k][ci] -> A^T [(j ci + c)][co]
-        const auto& w = mneed(m, p + ".weight", {co, k, ci});
+        const auto& w = m->raw.need(p + ".weight", {co, k, ci}).v;
         mis_mimi::Lin L; L.M = (int)co; L.K = (int)(k * ci);
         std::vector<float> at((size_t)k * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
         L.w = push(at);
-        L.b = push(mneed(m, p + ".bias", {co}));
+        L.b = push(m->raw.need(p + ".bias", {co}).v);
         return L;
     };
     auto convT = [&](const std::string& p, int64_t co, int64_t r, int64_t ci) {                     // [co][2r][ci] -> [r][(j ci + c)][co], tap p + r j
-        const auto& w = mneed(m, p + ".weight", {co, 2 * r, ci});
+        const auto& w = m->raw.need(p + ".weight", {co, 2 * r, ci}).v;
         mis_mimi::Lin L; L.M = (int)co; L.K = (int)(2 * ci);
         std::vector<float> at((size_t)2 * r * ci * co);
         for (int64_t ph = 0; ph < r; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t c = 0; c < ci; ++c) for (int64_t o = 0; o < co; ++o)
             at[((ph * 2 + j) * ci + c) * co + o] = w[(o * 2 * r + (ph + r * j)) * ci + c];
         L.w = push(at);
-        L.b = push(mneed(m, p + ".bias", {co}));
+        L.b = push(m->raw.need(p + ".bias", {co}).v);
         return L;
     };
     m->zeros = push(std::vector<float>((size_t)std::max<int64_t>(D, (int64_t)cf.n_filters << cf.n_ratios), 0.0f));
@@ -300,9 +283,9 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
         for (int64_t q = 0; q < nq; ++q) {
             const std::string grp = q == 0 ? "rvq_first" : "rvq_rest";
             const std::string p = "quantizer." + grp + ".vq.layers." + std::to_string(q == 0 ? 0 : q - 1) + ".codebook";
-            const auto& es = mneed(m, p + ".embedding_sum", {bins, qd});
-            const auto& cu = mneed(m, p + ".cluster_usage", {bins});
-            const auto& pw = mneed(m, "quantizer." + grp + ".output_proj.weight", {D, 1, qd});
+            const auto& es = m->raw.need(p + ".embedding_sum", {bins, qd}).v;
+            const auto& cu = m->raw.need(p + ".cluster_usage", {bins}).v;
+            const auto& pw = m->raw.need("quantizer." + grp + ".output_proj.weight", {D, 1, qd}).v;
             std::vector<float> e((size_t)qd);
             for (int64_t v = 0; v < bins; ++v) {
                 const float den = std::max(cu[v], 1e-5f);
@@ -316,16 +299,16 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
         }
         m->rvq_tables = push(tables);
     }
-    m->up_w = push(mneed(m, "upsample.convtr.convtr.convtr.weight", {D, 2 * s, 1}));                   // [C][2s][1] == [C][2s]
+    m->up_w = push(m->raw.need("upsample.convtr.convtr.convtr.weight", {D, 2 * s, 1}).v);                   // [C][2s][1] == [C][2s]
     m->tl.clear();
     for (int li = 0; li < cf.num_layers; ++li) {
         const std::string p = "decoder_transformer.transformer.layers." + std::to_string(li);
         mis_mimi::TL L{};
-        L.n1w = push(mneed(m, p + ".norm1.weight", {D})); L.n1b = push(mneed(m, p + ".norm1.bias", {D}));
-        L.n2w = push(mneed(m, p + ".norm2.weight", {D})); L.n2b = push(mneed(m, p + ".norm2.bias", {D}));
-        L.ls1 = push(mneed(m, p + ".layer_scale_1.scale", {D})); L.ls2 = push(mneed(m, p + ".layer_scale_2.scale", {D}));
+        L.n1w = push(m->raw.need(p + ".norm1.weight", {D}).v); L.n1b = push(m->raw.need(p + ".norm1.bias", {D}).v);
+        L.n2w = push(m->raw.need(p + ".norm2.weight", {D}).v); L.n2b = push(m->raw.need(p + ".norm2.bias", {D}).v);
+        L.ls1 = push(m->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = push(m->raw.need(p + ".layer_scale_2.scale", {D}).v);
         {   // q / k rows of every head evens-then-odds (as q3_reference.hip): interleaved RoPE pairs become rotate-half pairs
-            const auto& w = mneed(m, p + ".self_attn.in_proj.weight", {3 * D, D});
+            const auto& w = m->raw.need(p + ".self_attn.in_proj.weight", {3 * D, D}).v;
             std::vector<float> pw(w.size());
             for (int part = 0; part < 3; ++part)
                 for (int64_t h = 0; h < H; ++h)
@@ -335,9 +318,9 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
                     }
             L.qkv = lin_t(pw, 3 * D, D);
         }
-        L.o = lin_t(mneed(m, p + ".self_attn.out_proj.weight", {D, D}), D, D);
-        L.f1 = lin_t(mneed(m, p + ".gating.linear1.weight", {I, D}), I, D);
-        L.f2 = lin_t(mneed(m, p + ".gating.linear2.weight", {D, I}), D, I);
+        L.o = lin_t(m->raw.need(p + ".self_attn.out_proj.weight", {D, D}).v, D, D);
+        L.f1 = lin_t(m->raw.need(p + ".gating.linear1.weight", {I, D}).v, I, D);
+        L.f2 = lin_t(m->raw.need(p + ".gating.linear2.weight", {D, I}).v, D, I);
         m->tl.push_back(L);
     }
     int64_t mult = (int64_t)1 << cf.n_ratios;
@@ -364,9 +347,9 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
     }
     m->fin_c = cf.n_filters;
     {
-        const auto& w = mneed(m, "decoder.final_conv1d.conv.conv.weight", {1, cf.last_kernel_size, cf.n_filters});   // [1][k][C] == [k][C]
+        const auto& w = m->raw.need("decoder.final_conv1d.conv.conv.weight", {1, cf.last_kernel_size, cf.n_filters}).v;   // [1][k][C] == [k][C]
         m->fin_w = push(w);
-        m->fin_b = mneed(m, "decoder.final_conv1d.conv.conv.bias", {1})[0];
+        m->fin_b = m->raw.need("decoder.final_conv1d.conv.conv.bias", {1}).v[0];
     }
     // the encoder: present when the checkpoint carries it
     if (m->raw.count("encoder.init_conv1d.conv.conv.weight")) {
@@ -386,8 +369,8 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
         try {
             for (auto& kv : m->raw) {
                 if (!mimi_is_encoder_key(kv.first)) continue;
-                const auto& sh = m->raw_shape[kv.first];
-                q3ref_set_tensor(e, kv.first.c_str(), kv.second.data(), MIS_F32, sh.data(), (int)sh.size());
+                const auto& sh = kv.second.shape;
+                q3ref_set_tensor(e, kv.first.c_str(), kv.second.v.data(), MIS_F32, sh.data(), (int)sh.size());
             }
             q3ref_finalize(e);
         } catch (...) { q3ref_destroy(e); throw; }
@@ -395,7 +378,7 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
     }
     m->arena.alloc(arena.size());
     HIP_CHECK(hipMemcpy(m->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    m->raw.clear(); m->raw_shape.clear();
+    m->raw.clear();
     m->finalized = true;
     MIS_API_END
 }

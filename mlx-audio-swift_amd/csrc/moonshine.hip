@@ -25,6 +25,8 @@
 //   k_ms_attn_self     RoPE + cache append + causal attention of the new token;  k_ms_attn_cross  over the cached encoder K/V
 //   k_ms_argmax_embed  greedy choice, EOS rule, token bookkeeping and the next token's embedding in one launch
 #include "common.h"
+#include "host_weights.h"
+#include "lm_kernels.h"
 #include "whisper_kernels.h"
 
 #include <math.h>
@@ -39,7 +41,6 @@
 #define MS_GN_CHUNK 32768
 static const float MS_EPS = 1e-5f;
 
-struct MsHostTensor { std::vector<float> v; std::vector<int64_t> shape; };
 struct MsEncLayer { bf16_t *ln1, *ln2, *wqkv, *bqkv, *wo, *fc1, *b1, *fc2, *b2; };
 struct MsDecLayer { bf16_t *ln1, *ln2, *ln3, *sqkv, *sbqkv, *so, *cq, *cbq, *ckv, *cbkv, *co, *fc1, *b1, *fc2, *b2; };
 
@@ -48,7 +49,7 @@ struct mis_moonshine {
     hipStream_t stream = nullptr;
     mis_moonshine_config cfg{};
     int d = 0, f = 0, V = 0, He = 0, Hke = 0, Hd = 0, Hkd = 0, hde = 0, hdd = 0, rote = 0, rotd = 0;
-    std::map<std::string, MsHostTensor> raw;
+    HostWeights raw{"Moonshine"};
     bool finalized = false;
     DevBuf<bf16_t> arena;
     DevBuf<float> farena;
@@ -140,24 +141,8 @@ extern "C" mis_status mis_moonshine_set_tensor(mis_moonshine* c, const char* nam
     MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
     const std::string name = ms_canonical_name(c, name_);
     if (name.empty()) return MIS_OK;
-    MsHostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; t.shape.push_back(shape[i]); }
-    t.v.resize(n);
-    if (dtype == MIS_F32) memcpy(t.v.data(), data, n * 4);
-    else {
-        const uint16_t* s = static_cast<const uint16_t*>(data);
-        for (size_t i = 0; i < n; ++i) t.v[i] = dtype == MIS_F16 ? f16_to_f32_host(s[i]) : bf16_to_f32(s[i]);
-    }
-    c->raw[name] = std::move(t);
+    c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
-}
-
-static const MsHostTensor& ms_need(mis_moonshine* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "Moonshine weight missing: %s", name.c_str());
-    MIS_REQUIRE(it->second.shape == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Moonshine weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
@@ -166,59 +151,46 @@ extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
     HIP_CHECK(hipSetDevice(c->device));
     const int64_t d = c->d, f = c->f, V = c->V;
     const bool ab = c->cfg.attention_bias != 0;
-    std::vector<bf16_t> host;                           // the bf16 arena, assembled on the host: f32 checkpoints are rounded once, here
-    std::vector<float> fhost;
-    auto btake = [&](size_t n) { size_t off = host.size(); host.resize(off + round_up(n, 64), 0); return off; };
-    auto ftake = [&](size_t n) { size_t off = fhost.size(); fhost.resize(off + round_up(n, 64), 0.0f); return off; };
-    auto bvec = [&](const std::string& name, int64_t n) {
-        const MsHostTensor& t = ms_need(c, name, {n});
-        size_t off = btake(n);
-        for (int64_t i = 0; i < n; ++i) host[off + i] = f32_to_bf16(t.v[i]);
-        return off;
-    };
-    auto bmat = [&](const std::string& name, int64_t N, int64_t K) {
-        const MsHostTensor& t = ms_need(c, name, {N, K});
-        size_t off = btake((size_t)N * K);
-        for (size_t i = 0; i < (size_t)N * K; ++i) host[off + i] = f32_to_bf16(t.v[i]);
-        return off;
-    };
+    HostArena a(c->raw);
+    std::vector<bf16_t>& host = a.host;                 // the packers below write through these
+    std::vector<float>& fhost = a.fhost;
     // projection rows [H hd][d] -> [H 64][d] at dst row0 (head h, column j -> row h 64 + j; the padding rows stay zero)
     auto pad_rows = [&](const std::string& name, int H, int hd, size_t off, int64_t row0) {
-        const MsHostTensor& t = ms_need(c, name, {(int64_t)H * hd, d});
+        const HostTensor& t = c->raw.need(name, {(int64_t)H * hd, d});
         for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j) for (int64_t k = 0; k < d; ++k)
             host[off + (size_t)(row0 + h * MS_DP + j) * d + k] = f32_to_bf16(t.v[(size_t)(h * hd + j) * d + k]);
     };
     auto pad_bias = [&](const std::string& name, int H, int hd, size_t off, int64_t row0) {
-        const MsHostTensor& t = ms_need(c, name, {(int64_t)H * hd});
+        const HostTensor& t = c->raw.need(name, {(int64_t)H * hd});
         for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j) host[off + row0 + h * MS_DP + j] = f32_to_bf16(t.v[h * hd + j]);
     };
     // o_proj [d][H hd] -> [d][H 64]
     auto pad_cols = [&](const std::string& name, int H, int hd) {
-        const MsHostTensor& t = ms_need(c, name, {d, (int64_t)H * hd});
-        size_t off = btake((size_t)d * H * MS_DP);
+        const HostTensor& t = c->raw.need(name, {d, (int64_t)H * hd});
+        size_t off = a.btake((size_t)d * H * MS_DP);
         for (int64_t n = 0; n < d; ++n) for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j)
             host[off + (size_t)n * H * MS_DP + h * MS_DP + j] = f32_to_bf16(t.v[(size_t)n * H * hd + h * hd + j]);
         return off;
     };
     // conv weight [out][in][k] (published layout) -> [out][k in] (the order of a contiguous span of k frames)
     auto conv_w = [&](const std::string& name, int64_t O, int64_t I, int64_t K) {
-        const MsHostTensor& t = ms_need(c, name, {O, I, K});
-        size_t off = btake((size_t)O * I * K);
+        const HostTensor& t = c->raw.need(name, {O, I, K});
+        size_t off = a.btake((size_t)O * I * K);
         for (int64_t o = 0; o < O; ++o) for (int64_t k = 0; k < K; ++k) for (int64_t i = 0; i < I; ++i)
             host[off + ((size_t)o * K + k) * I + i] = f32_to_bf16(t.v[((size_t)o * I + i) * K + k]);
         return off;
     };
     const std::string E = "encoder", D = "decoder";
     // ---- stem (f32 through GroupNorm)
-    const MsHostTensor& w1 = ms_need(c, E + ".conv1.weight", {d, 1, 127});
-    const size_t o_c1 = ftake((size_t)127 * d);
+    const HostTensor& w1 = c->raw.need(E + ".conv1.weight", {d, 1, 127});
+    const size_t o_c1 = a.ftake((size_t)127 * d);
     for (int64_t ch = 0; ch < d; ++ch) for (int k = 0; k < 127; ++k) fhost[o_c1 + (size_t)k * d + ch] = w1.v[(size_t)ch * 127 + k];
-    const size_t o_gw = ftake(d), o_gb = ftake(d);
-    { const MsHostTensor& gw = ms_need(c, E + ".groupnorm.weight", {d}); const MsHostTensor& gb = ms_need(c, E + ".groupnorm.bias", {d});
+    const size_t o_gw = a.ftake(d), o_gb = a.ftake(d);
+    { const HostTensor& gw = c->raw.need(E + ".groupnorm.weight", {d}); const HostTensor& gb = c->raw.need(E + ".groupnorm.bias", {d});
       for (int64_t i = 0; i < d; ++i) { fhost[o_gw + i] = gw.v[i]; fhost[o_gb + i] = gb.v[i]; } }
     // rotary tables [MS_MAX_POS][rot / 2] (MoonshineRotaryEmbedding, :88-110)
     auto rope_tab = [&](int rot, size_t* oc, size_t* os) {
-        *oc = ftake((size_t)MS_MAX_POS * (rot / 2)); *os = ftake((size_t)MS_MAX_POS * (rot / 2));
+        *oc = a.ftake((size_t)MS_MAX_POS * (rot / 2)); *os = a.ftake((size_t)MS_MAX_POS * (rot / 2));
         for (int i = 0; i < rot / 2; ++i) {
             const float inv = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / (float)rot);
             for (int p = 0; p < MS_MAX_POS; ++p) {
@@ -231,9 +203,9 @@ extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
     size_t o_ce, o_se, o_cd, o_sd;
     rope_tab(c->rote, &o_ce, &o_se);
     rope_tab(c->rotd, &o_cd, &o_sd);
-    const size_t o_zero = btake(std::max<int64_t>(d, 64));
-    const size_t o_c2w = conv_w(E + ".conv2.weight", 2 * d, d, 7), o_c2b = bvec(E + ".conv2.bias", 2 * d);
-    const size_t o_c3w = conv_w(E + ".conv3.weight", d, 2 * d, 3), o_c3b = bvec(E + ".conv3.bias", d);
+    const size_t o_zero = a.btake(std::max<int64_t>(d, 64));
+    const size_t o_c2w = conv_w(E + ".conv2.weight", 2 * d, d, 7), o_c2b = a.bvec(E + ".conv2.bias", 2 * d);
+    const size_t o_c3w = conv_w(E + ".conv3.weight", d, 2 * d, 3), o_c3b = a.bvec(E + ".conv3.bias", d);
     // ---- encoder layers
     struct Off { size_t v[15]; };
     std::vector<Off> eo(c->cfg.encoder_num_hidden_layers), dof(c->cfg.decoder_num_hidden_layers);
@@ -241,64 +213,61 @@ extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
     for (size_t li = 0; li < eo.size(); ++li) {
         const std::string q = E + ".layers." + std::to_string(li);
         Off& o = eo[li];
-        o.v[0] = bvec(q + ".input_layernorm.weight", d); o.v[1] = bvec(q + ".post_attention_layernorm.weight", d);
-        o.v[2] = btake((size_t)NQe * d);
+        o.v[0] = a.bvec(q + ".input_layernorm.weight", d); o.v[1] = a.bvec(q + ".post_attention_layernorm.weight", d);
+        o.v[2] = a.btake((size_t)NQe * d);
         pad_rows(q + ".self_attn.q_proj.weight", c->He, c->hde, o.v[2], 0);
         pad_rows(q + ".self_attn.k_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)c->He * MS_DP);
         pad_rows(q + ".self_attn.v_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)(c->He + c->Hke) * MS_DP);
-        o.v[3] = btake(NQe);
+        o.v[3] = a.btake(NQe);
         if (ab) {
             pad_bias(q + ".self_attn.q_proj.bias", c->He, c->hde, o.v[3], 0);
             pad_bias(q + ".self_attn.k_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)c->He * MS_DP);
             pad_bias(q + ".self_attn.v_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)(c->He + c->Hke) * MS_DP);
         }
         o.v[4] = pad_cols(q + ".self_attn.o_proj.weight", c->He, c->hde);
-        o.v[5] = bmat(q + ".mlp.fc1.weight", f, d); o.v[6] = bvec(q + ".mlp.fc1.bias", f);
-        o.v[7] = bmat(q + ".mlp.fc2.weight", d, f); o.v[8] = bvec(q + ".mlp.fc2.bias", d);
+        o.v[5] = a.bmat(q + ".mlp.fc1.weight", f, d); o.v[6] = a.bvec(q + ".mlp.fc1.bias", f);
+        o.v[7] = a.bmat(q + ".mlp.fc2.weight", d, f); o.v[8] = a.bvec(q + ".mlp.fc2.bias", d);
     }
-    const size_t o_eln = bvec(E + ".layer_norm.weight", d);
+    const size_t o_eln = a.bvec(E + ".layer_norm.weight", d);
     // ---- decoder
-    const size_t o_emb = bmat(D + ".embed_tokens.weight", V, d);
-    const size_t o_proj = c->cfg.tie_word_embeddings ? o_emb : bmat("proj_out.weight", V, d);
+    const size_t o_emb = a.bmat(D + ".embed_tokens.weight", V, d);
+    const size_t o_proj = c->cfg.tie_word_embeddings ? o_emb : a.bmat("proj_out.weight", V, d);
     const int64_t NQd = (int64_t)(c->Hd + 2 * c->Hkd) * MS_DP, NKVd = (int64_t)2 * c->Hkd * MS_DP;
     for (size_t li = 0; li < dof.size(); ++li) {
         const std::string q = D + ".layers." + std::to_string(li);
         Off& o = dof[li];
-        o.v[0] = bvec(q + ".input_layernorm.weight", d); o.v[1] = bvec(q + ".post_attention_layernorm.weight", d);
-        o.v[2] = bvec(q + ".final_layernorm.weight", d);
-        o.v[3] = btake((size_t)NQd * d);
+        o.v[0] = a.bvec(q + ".input_layernorm.weight", d); o.v[1] = a.bvec(q + ".post_attention_layernorm.weight", d);
+        o.v[2] = a.bvec(q + ".final_layernorm.weight", d);
+        o.v[3] = a.btake((size_t)NQd * d);
         pad_rows(q + ".self_attn.q_proj.weight", c->Hd, c->hdd, o.v[3], 0);
         pad_rows(q + ".self_attn.k_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)c->Hd * MS_DP);
         pad_rows(q + ".self_attn.v_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)(c->Hd + c->Hkd) * MS_DP);
-        o.v[4] = btake(NQd);
+        o.v[4] = a.btake(NQd);
         if (ab) {
             pad_bias(q + ".self_attn.q_proj.bias", c->Hd, c->hdd, o.v[4], 0);
             pad_bias(q + ".self_attn.k_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)c->Hd * MS_DP);
             pad_bias(q + ".self_attn.v_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)(c->Hd + c->Hkd) * MS_DP);
         }
         o.v[5] = pad_cols(q + ".self_attn.o_proj.weight", c->Hd, c->hdd);
-        o.v[6] = btake((size_t)c->Hd * MS_DP * d);
+        o.v[6] = a.btake((size_t)c->Hd * MS_DP * d);
         pad_rows(q + ".encoder_attn.q_proj.weight", c->Hd, c->hdd, o.v[6], 0);
-        o.v[7] = btake((size_t)c->Hd * MS_DP);
+        o.v[7] = a.btake((size_t)c->Hd * MS_DP);
         if (ab) pad_bias(q + ".encoder_attn.q_proj.bias", c->Hd, c->hdd, o.v[7], 0);
-        o.v[8] = btake((size_t)NKVd * d);
+        o.v[8] = a.btake((size_t)NKVd * d);
         pad_rows(q + ".encoder_attn.k_proj.weight", c->Hkd, c->hdd, o.v[8], 0);
         pad_rows(q + ".encoder_attn.v_proj.weight", c->Hkd, c->hdd, o.v[8], (int64_t)c->Hkd * MS_DP);
-        o.v[9] = btake(NKVd);
+        o.v[9] = a.btake(NKVd);
         if (ab) {
             pad_bias(q + ".encoder_attn.k_proj.bias", c->Hkd, c->hdd, o.v[9], 0);
             pad_bias(q + ".encoder_attn.v_proj.bias", c->Hkd, c->hdd, o.v[9], (int64_t)c->Hkd * MS_DP);
         }
         o.v[10] = pad_cols(q + ".encoder_attn.o_proj.weight", c->Hd, c->hdd);
-        o.v[11] = bmat(q + ".mlp.fc1.weight", 2 * f, d); o.v[12] = bvec(q + ".mlp.fc1.bias", 2 * f);
-        o.v[13] = bmat(q + ".mlp.fc2.weight", d, f); o.v[14] = bvec(q + ".mlp.fc2.bias", d);
+        o.v[11] = a.bmat(q + ".mlp.fc1.weight", 2 * f, d); o.v[12] = a.bvec(q + ".mlp.fc1.bias", 2 * f);
+        o.v[13] = a.bmat(q + ".mlp.fc2.weight", d, f); o.v[14] = a.bvec(q + ".mlp.fc2.bias", d);
     }
-    const size_t o_dn = bvec(D + ".norm.weight", d);
+    const size_t o_dn = a.bvec(D + ".norm.weight", d);
     // ---- upload
-    c->arena.alloc(host.size());
-    c->farena.alloc(fhost.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, host.data(), host.size() * 2, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(c->farena.p, fhost.data(), fhost.size() * 4, hipMemcpyHostToDevice));
+    a.upload(c->arena, c->farena);
     bf16_t* A = c->arena.p;
     float* F = c->farena.p;
     c->conv1wT = F + o_c1; c->gn_w = F + o_gw; c->gn_b = F + o_gb;
@@ -326,47 +295,34 @@ extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
 extern "C" mis_status mis_moonshine_init_synthetic(mis_moonshine* c, uint64_t seed) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
-    uint64_t key = seed * 100000ull;
+    SynthWeights sw{c->raw, seed * 100000ull};
     const int64_t d = c->d, f = c->f;
-    auto put = [&](const std::string& name, std::vector<int64_t> shape, double amp, float plus) {
-        MsHostTensor t;
-        size_t n = 1;
-        for (auto v : shape) n *= (size_t)v;
-        t.shape = shape; t.v.resize(n);
-        ++key;
-        for (size_t i = 0; i < n; ++i) t.v[i] = plus + mis_synth_value(key, i, (float)amp);
-        c->raw[name] = std::move(t);
-    };
-    auto lin = [&](const std::string& p, int64_t o, int64_t i, bool bias, double gain) {
-        put(p + ".weight", {o, i}, gain * sqrt(3.0 / (double)i), 0.0f);
-        if (bias) put(p + ".bias", {o}, 0.05, 0.0f);
-    };
     auto attn = [&](const std::string& p, int H, int Hk, int hd) {
         const bool ab = c->cfg.attention_bias != 0;
-        lin(p + ".q_proj", (int64_t)H * hd, d, ab, 1.0); lin(p + ".k_proj", (int64_t)Hk * hd, d, ab, 1.0);
-        lin(p + ".v_proj", (int64_t)Hk * hd, d, ab, 1.0); lin(p + ".o_proj", d, (int64_t)H * hd, false, 0.5);
+        sw.lin(p + ".q_proj", (int64_t)H * hd, d, ab, 1.0); sw.lin(p + ".k_proj", (int64_t)Hk * hd, d, ab, 1.0);
+        sw.lin(p + ".v_proj", (int64_t)Hk * hd, d, ab, 1.0); sw.lin(p + ".o_proj", d, (int64_t)H * hd, false, 0.5);
     };
-    put("encoder.conv1.weight", {d, 1, 127}, sqrt(3.0 / 127.0) * 4.0, 0.0f);
-    put("encoder.groupnorm.weight", {d}, 0.1, 1.0f); put("encoder.groupnorm.bias", {d}, 0.05, 0.0f);
-    put("encoder.conv2.weight", {2 * d, d, 7}, sqrt(3.0 / (7.0 * d)), 0.0f); put("encoder.conv2.bias", {2 * d}, 0.05, 0.0f);
-    put("encoder.conv3.weight", {d, 2 * d, 3}, sqrt(3.0 / (6.0 * d)), 0.0f); put("encoder.conv3.bias", {d}, 0.05, 0.0f);
+    sw.put("encoder.conv1.weight", {d, 1, 127}, sqrt(3.0 / 127.0) * 4.0, 0.0f);
+    sw.put("encoder.groupnorm.weight", {d}, 0.1, 1.0f); sw.put("encoder.groupnorm.bias", {d}, 0.05, 0.0f);
+    sw.put("encoder.conv2.weight", {2 * d, d, 7}, sqrt(3.0 / (7.0 * d)), 0.0f); sw.put("encoder.conv2.bias", {2 * d}, 0.05, 0.0f);
+    sw.put("encoder.conv3.weight", {d, 2 * d, 3}, sqrt(3.0 / (6.0 * d)), 0.0f); sw.put("encoder.conv3.bias", {d}, 0.05, 0.0f);
     for (int li = 0; li < c->cfg.encoder_num_hidden_layers; ++li) {
         const std::string q = "encoder.layers." + std::to_string(li);
         attn(q + ".self_attn", c->He, c->Hke, c->hde);
-        put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
-        lin(q + ".mlp.fc1", f, d, true, 1.0); lin(q + ".mlp.fc2", d, f, true, 0.5);
+        sw.put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); sw.put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
+        sw.lin(q + ".mlp.fc1", f, d, true, 1.0); sw.lin(q + ".mlp.fc2", d, f, true, 0.5);
     }
-    put("encoder.layer_norm.weight", {d}, 0.1, 1.0f);
-    put("decoder.embed_tokens.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
+    sw.put("encoder.layer_norm.weight", {d}, 0.1, 1.0f);
+    sw.put("decoder.embed_tokens.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
     for (int li = 0; li < c->cfg.decoder_num_hidden_layers; ++li) {
         const std::string q = "decoder.layers." + std::to_string(li);
         attn(q + ".self_attn", c->Hd, c->Hkd, c->hdd); attn(q + ".encoder_attn", c->Hd, c->Hkd, c->hdd);
-        put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
-        put(q + ".final_layernorm.weight", {d}, 0.1, 1.0f);
-        lin(q + ".mlp.fc1", 2 * f, d, true, 1.0); lin(q + ".mlp.fc2", d, f, true, 0.5);
+        sw.put(q + ".input_layernorm.weight", {d}, 0.1, 1.0f); sw.put(q + ".post_attention_layernorm.weight", {d}, 0.1, 1.0f);
+        sw.put(q + ".final_layernorm.weight", {d}, 0.1, 1.0f);
+        sw.lin(q + ".mlp.fc1", 2 * f, d, true, 1.0); sw.lin(q + ".mlp.fc2", d, f, true, 0.5);
     }
-    put("decoder.norm.weight", {d}, 0.1, 1.0f);
-    if (!c->cfg.tie_word_embeddings) put("proj_out.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
+    sw.put("decoder.norm.weight", {d}, 0.1, 1.0f);
+    if (!c->cfg.tie_word_embeddings) sw.put("proj_out.weight", {(int64_t)c->V, d}, 0.5, 0.0f);
     MIS_API_END
 }
 
@@ -689,11 +645,6 @@ __global__ void __launch_bounds__(256) k_ms_argmax_embed(const float* __restrict
     for (int i = threadIdx.x; i < d; i += 256) h[(size_t)b * d + i] = emb[(size_t)id * d + i];
 }
 
-__global__ void k_ms_bf16_to_f32(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = bf16_to_f32(src[i]);
-}
-
 // ============================================================================ encoder pass
 static void ms_check_lens(const mis_moonshine* c, const int64_t* lens, int batch, int64_t stride, std::vector<int64_t>* hl) {
     MIS_REQUIRE(c->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
@@ -820,7 +771,7 @@ extern "C" mis_status mis_moonshine_encode(mis_moonshine* c, const float* pcm, c
         const size_t n = (size_t)batch * c->T3pad * c->d;
         DevBuf<float> o;
         o.alloc(n);
-        hipLaunchKernelGGL(k_ms_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->enc_out.p, o.p, n);
+        launch_bf16_to_f32(c->enc_out.p, o.p, n, c->stream);
         std::vector<float> hostv(n);
         HIP_CHECK(hipMemcpyAsync(hostv.data(), o.p, n * 4, hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -852,7 +803,7 @@ extern "C" mis_status mis_debug_moonshine_stem_tap(mis_moonshine* c, const float
             DevBuf<float> o;
             o.alloc(n);
             const bf16_t* src = stage == 1 ? c->gn.p : stage == 2 ? c->c2.p : c->h.p;
-            hipLaunchKernelGGL(k_ms_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, src, o.p, n);
+            launch_bf16_to_f32(src, o.p, n, c->stream);
             HIP_CHECK(hipStreamSynchronize(c->stream));
             HIP_CHECK(hipMemcpy(out, o.p, n * 4, hipMemcpyDeviceToHost));
         }

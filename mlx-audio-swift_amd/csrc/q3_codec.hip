@@ -19,6 +19,7 @@
 // Activations are NCT ([B][C][T], time contiguous); dense convs are exact-f32 MFMA contractions over (tap, channel)
 // (k_snac_gemm modes TAPS / CONVT of snac.hip) with the SnakeBeta activation fused into the operand load.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 #include "q3_kernels.h"
@@ -31,8 +32,7 @@
 struct mis_q3dec {
     int device = 0;
     mis_qwen3tts_config cfg{};
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"speech tokenizer"};
     bool finalized = false;
     DevBuf<float> arena;
     size_t rvq_tables = 0, zeros = 0;
@@ -315,28 +315,11 @@ int q3dec_total_upsample(const mis_q3dec* d) {
 mis_status mis_q3dec_set_tensor(mis_q3dec* d, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
     MIS_REQUIRE(!d->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(d->device));
-    size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((bf16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    d->raw[name] = std::move(v);
-    d->raw_shape[name] = sh;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    d->raw.put(name, host.data(), dtype, shape, ndim);
     MIS_API_END
-}
-
-static const std::vector<float>& need(mis_q3dec* d, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = d->raw.find(name);
-    MIS_REQUIRE(it != d->raw.end(), MIS_ERR_NOT_INITIALIZED, "speech tokenizer weight missing: %s", name.c_str());
-    MIS_REQUIRE(d->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "speech tokenizer weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 mis_status mis_q3dec_finalize(mis_q3dec* d) {
@@ -367,7 +350,7 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         return at;
     };
     auto snake_pair = [&](const std::string& pa, const std::string& pb, int64_t C, size_t& a, size_t& ra) {
-        const auto& al = need(d, pa, {C}); const auto& be = need(d, pb, {C});
+        const auto& al = d->raw.need(pa, {C}).v; const auto& be = d->raw.need(pb, {C}).v;
         std::vector<float> av(C), rv(C);
         for (int64_t i = 0; i < C; ++i) { av[i] = expf(al[i]); rv[i] = 1.0f / (expf(be[i]) + 1e-9f); }   // SnakeBeta :236-254
         a = push(av); ra = push(rv);
@@ -379,9 +362,9 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
             const bool first = q < nsem;
             const std::string grp = first ? "rvq_first" : "rvq_rest";
             const std::string p = "decoder.quantizer." + grp + ".vq.layers." + std::to_string(first ? q : q - nsem) + ".codebook";
-            const auto& es = need(d, p + ".embedding_sum", {bins, half});
-            const auto& cu = need(d, p + ".cluster_usage", {bins});
-            const auto& pw = need(d, "decoder.quantizer." + grp + ".output_proj.weight", {Cd, 1, half});
+            const auto& es = d->raw.need(p + ".embedding_sum", {bins, half}).v;
+            const auto& cu = d->raw.need(p + ".cluster_usage", {bins}).v;
+            const auto& pw = d->raw.need("decoder.quantizer." + grp + ".output_proj.weight", {Cd, 1, half}).v;
             for (int64_t v = 0; v < bins; ++v) {
                 const float inv = 1.0f / std::max(cu[v], 1e-5f);
                 for (int64_t c = 0; c < Cd; ++c) {
@@ -395,42 +378,42 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
     }
     auto lin = [&](const std::string& p, int64_t out_f, int64_t in_f, bool bias) {
         mis_q3dec::Lin L; L.M = (int)out_f; L.K = (int)in_f;
-        L.w = push(lin_t(need(d, p + ".weight", {out_f, in_f}), out_f, in_f));
-        L.b = bias ? push(need(d, p + ".bias", {out_f})) : (size_t)-1;
+        L.w = push(lin_t(d->raw.need(p + ".weight", {out_f, in_f}).v, out_f, in_f));
+        L.b = bias ? push(d->raw.need(p + ".bias", {out_f}).v) : (size_t)-1;
         return L;
     };
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {
         mis_q3dec::Lin L; L.M = (int)co; L.K = (int)(k * ci);
-        L.w = push(conv_t(need(d, p + ".weight", {co, k, ci}), co, k, ci));
-        L.b = push(need(d, p + ".bias", {co}));
+        L.w = push(conv_t(d->raw.need(p + ".weight", {co, k, ci}).v, co, k, ci));
+        L.b = push(d->raw.need(p + ".bias", {co}).v);
         return L;
     };
     d->pre_conv = conv("decoder.pre_conv.conv", ld, 3, Cd);
     const std::string P = "decoder.pre_transformer";
     d->in_proj = lin(P + ".input_proj", hs, ld, true);
     d->out_proj = lin(P + ".output_proj", ld, hs, true);
-    d->tnorm = push(need(d, P + ".norm.weight", {hs}));
+    d->tnorm = push(d->raw.need(P + ".norm.weight", {hs}).v);
     d->layers.clear();
     for (int li = 0; li < cf.dec_num_layers; ++li) {
         const std::string p = P + ".layers." + std::to_string(li);
         mis_q3dec::Layer L{};
-        L.ln1 = push(need(d, p + ".input_layernorm.weight", {hs}));
-        L.ln2 = push(need(d, p + ".post_attention_layernorm.weight", {hs}));
-        L.ls1 = push(need(d, p + ".self_attn_layer_scale.scale", {hs}));
-        L.ls2 = push(need(d, p + ".mlp_layer_scale.scale", {hs}));
+        L.ln1 = push(d->raw.need(p + ".input_layernorm.weight", {hs}).v);
+        L.ln2 = push(d->raw.need(p + ".post_attention_layernorm.weight", {hs}).v);
+        L.ls1 = push(d->raw.need(p + ".self_attn_layer_scale.scale", {hs}).v);
+        L.ls2 = push(d->raw.need(p + ".mlp_layer_scale.scale", {hs}).v);
         {   // q, k, v rows concatenated: one GEMM
             std::vector<float> w;
             for (const char* nm : {"q_proj", "k_proj", "v_proj"}) {
                 int64_t rows = (std::string(nm) == "q_proj" ? H : Hkv) * D;
-                const auto& t = need(d, p + ".self_attn." + nm + ".weight", {rows, hs});
+                const auto& t = d->raw.need(p + ".self_attn." + nm + ".weight", {rows, hs}).v;
                 w.insert(w.end(), t.begin(), t.end());
             }
             L.qkv.M = (int)((H + 2 * Hkv) * D); L.qkv.K = (int)hs; L.qkv.w = push(lin_t(w, L.qkv.M, hs)); L.qkv.b = (size_t)-1;
         }
         L.o = lin(p + ".self_attn.o_proj", hs, H * D, false);
         {
-            std::vector<float> w = need(d, p + ".mlp.gate_proj.weight", {I, hs});
-            const auto& u = need(d, p + ".mlp.up_proj.weight", {I, hs});
+            std::vector<float> w = d->raw.need(p + ".mlp.gate_proj.weight", {I, hs}).v;
+            const auto& u = d->raw.need(p + ".mlp.up_proj.weight", {I, hs}).v;
             w.insert(w.end(), u.begin(), u.end());
             L.gu.M = (int)(2 * I); L.gu.K = (int)hs; L.gu.w = push(lin_t(w, 2 * I, hs)); L.gu.b = (size_t)-1;
         }
@@ -444,13 +427,13 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         mis_q3dec::Up U{};
         U.f = (int)f;
         U.ct.M = (int)ld; U.ct.K = (int)ld;
-        U.ct.w = push(convT_t(need(d, p + ".0.conv.weight", {ld, f, ld}), ld, f, ld, f));
-        U.ct.b = push(need(d, p + ".0.conv.bias", {ld}));
-        U.dw = push(need(d, p + ".1.dwconv.conv.weight", {ld, 7, 1})); U.dwb = push(need(d, p + ".1.dwconv.conv.bias", {ld}));
-        U.lnw = push(need(d, p + ".1.norm.weight", {ld})); U.lnb = push(need(d, p + ".1.norm.bias", {ld}));
+        U.ct.w = push(convT_t(d->raw.need(p + ".0.conv.weight", {ld, f, ld}).v, ld, f, ld, f));
+        U.ct.b = push(d->raw.need(p + ".0.conv.bias", {ld}).v);
+        U.dw = push(d->raw.need(p + ".1.dwconv.conv.weight", {ld, 7, 1}).v); U.dwb = push(d->raw.need(p + ".1.dwconv.conv.bias", {ld}).v);
+        U.lnw = push(d->raw.need(p + ".1.norm.weight", {ld}).v); U.lnb = push(d->raw.need(p + ".1.norm.bias", {ld}).v);
         U.p1 = lin(p + ".1.pwconv1", 4 * ld, ld, true);
         U.p2 = lin(p + ".1.pwconv2", ld, 4 * ld, true);
-        U.gamma = push(need(d, p + ".1.gamma", {ld}));
+        U.gamma = push(d->raw.need(p + ".1.gamma", {ld}).v);
         d->ups.push_back(U);
     }
     d->dec0 = conv("decoder.decoder.0.conv", dd, 7, ld);
@@ -462,8 +445,8 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         B.s = (int)s; B.cin = (int)cin; B.cout = (int)cout;
         snake_pair(p + ".0.alpha", p + ".0.beta", cin, B.a, B.ra);
         B.ct.M = (int)cout; B.ct.K = (int)(2 * cin);
-        B.ct.w = push(convT_t(need(d, p + ".1.conv.weight", {cout, 2 * s, cin}), cout, 2 * s, cin, s));
-        B.ct.b = push(need(d, p + ".1.conv.bias", {cout}));
+        B.ct.w = push(convT_t(d->raw.need(p + ".1.conv.weight", {cout, 2 * s, cin}).v, cout, 2 * s, cin, s));
+        B.ct.b = push(d->raw.need(p + ".1.conv.bias", {cout}).v);
         const int dils[3] = {1, 3, 9};
         for (int ri = 0; ri < 3; ++ri) {
             const std::string q = p + "." + std::to_string(ri + 2);
@@ -480,13 +463,13 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         const int64_t cl = dd >> n;
         d->fin_c = (int)cl;
         snake_pair("decoder.decoder." + std::to_string(n + 1) + ".alpha", "decoder.decoder." + std::to_string(n + 1) + ".beta", cl, d->fin_a, d->fin_ra);
-        const auto& w = need(d, "decoder.decoder." + std::to_string(n + 2) + ".conv.weight", {1, 7, cl});     // [1][k][C] == [k][C]
+        const auto& w = d->raw.need("decoder.decoder." + std::to_string(n + 2) + ".conv.weight", {1, 7, cl}).v;     // [1][k][C] == [k][C]
         d->fin_w = push(w);
-        d->fin_b = need(d, "decoder.decoder." + std::to_string(n + 2) + ".conv.bias", {1})[0];
+        d->fin_b = d->raw.need("decoder.decoder." + std::to_string(n + 2) + ".conv.bias", {1}).v[0];
     }
     d->arena.alloc(arena.size());
     HIP_CHECK(hipMemcpy(d->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    d->raw.clear(); d->raw_shape.clear();
+    d->raw.clear();
     d->finalized = true;
     MIS_API_END
 }

@@ -17,6 +17,7 @@
 // (q3_codec.hip; interleaved RoPE = rotate-half RoPE after permuting the q / k rows of every head to evens-then-odds, which leaves
 // q.k unchanged), and the residual VQ of a frame runs in one block that keeps the residual in LDS across all quantizer layers.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 #include "q3_kernels.h"
@@ -31,8 +32,7 @@ struct mis_q3ref {
     int device = 0;
     hipStream_t s = nullptr;
     mis_qwen3tts_reference_config cfg{};
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"reference front-end"};
     bool finalized = false, has_spk = false, has_enc = false;
     DevBuf<float> arena;
     struct Lin { size_t w = 0, b = (size_t)-1; int M = 0, K = 0, taps = 1, dil = 1, cin = 0; };
@@ -263,27 +263,10 @@ bool q3ref_owns(const char* name) { return !strncmp(name, "speaker_encoder.", 16
 
 void q3ref_set_tensor(mis_q3ref* r, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_REQUIRE(!r->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(r->device));
-    const size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((bf16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    r->raw[name] = std::move(v);
-    r->raw_shape[name] = sh;
-}
-
-static const std::vector<float>& rneed(mis_q3ref* r, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = r->raw.find(name);
-    MIS_REQUIRE(it != r->raw.end(), MIS_ERR_NOT_INITIALIZED, "reference front-end weight missing: %s", name.c_str());
-    MIS_REQUIRE(r->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "reference front-end weight %s has the wrong shape", name.c_str());
-    return it->second;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    r->raw.put(name, host.data(), dtype, shape, ndim);
 }
 
 void q3ref_finalize(mis_q3ref* r) {
@@ -294,29 +277,29 @@ void q3ref_finalize(mis_q3ref* r) {
     auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
     // conv weight [co][k][ci] (MLX layout) -> A^T [(j ci + c)][co]
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci, int dil, bool bias) {
-        const auto& w = rneed(r, p + ".weight", {co, k, ci});
+        const auto& w = r->raw.need(p + ".weight", {co, k, ci}).v;
         std::vector<float> at((size_t)k * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
         mis_q3ref::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.taps = (int)k; L.dil = dil; L.cin = (int)ci;
         L.w = push(at);
-        if (bias) L.b = push(rneed(r, p + ".bias", {co}));
+        if (bias) L.b = push(r->raw.need(p + ".bias", {co}).v);
         return L;
     };
     // strided conv k = 2 s: [co][2s][ci] -> two taps over the phase-split input: A^T [(j (ci s) + c s + ph)][co] = w[co][j s + ph][c]
     auto conv_strided = [&](const std::string& p, int64_t co, int64_t s, int64_t ci, bool bias) {
-        const auto& w = rneed(r, p + ".weight", {co, 2 * s, ci});
+        const auto& w = r->raw.need(p + ".weight", {co, 2 * s, ci}).v;
         std::vector<float> at((size_t)2 * s * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < 2; ++j) for (int64_t ph = 0; ph < s; ++ph) for (int64_t c = 0; c < ci; ++c)
             at[((j * ci * s) + c * s + ph) * co + o] = w[(o * 2 * s + j * s + ph) * ci + c];
         mis_q3ref::Lin L; L.M = (int)co; L.K = (int)(2 * s * ci); L.taps = 2; L.dil = 1; L.cin = (int)(ci * s);
         L.w = push(at);
-        if (bias) L.b = push(rneed(r, p + ".bias", {co}));
+        if (bias) L.b = push(r->raw.need(p + ".bias", {co}).v);
         return L;
     };
     auto matvec = [&](const std::string& p, int64_t co, int64_t ci) {      // 1x1 conv kept row-major [co][ci] for k_ref_matvec
         mis_q3ref::Lin L; L.M = (int)co; L.K = (int)ci;
-        L.w = push(rneed(r, p + ".weight", {co, 1, ci}));
-        L.b = push(rneed(r, p + ".bias", {co}));
+        L.w = push(r->raw.need(p + ".weight", {co, 1, ci}).v);
+        L.b = push(r->raw.need(p + ".bias", {co}).v);
         return L;
     };
     auto linear = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) {           // [out][in] -> A^T [in][out]
@@ -390,11 +373,11 @@ void q3ref_finalize(mis_q3ref* r) {
         for (int li = 0; li < cf.enc_num_layers; ++li) {
             const std::string p = P + "encoder_transformer.transformer.layers." + std::to_string(li);
             mis_q3ref::TL L{};
-            L.n1w = push(rneed(r, p + ".norm1.weight", {D})); L.n1b = push(rneed(r, p + ".norm1.bias", {D}));
-            L.n2w = push(rneed(r, p + ".norm2.weight", {D})); L.n2b = push(rneed(r, p + ".norm2.bias", {D}));
-            L.ls1 = push(rneed(r, p + ".layer_scale_1.scale", {D})); L.ls2 = push(rneed(r, p + ".layer_scale_2.scale", {D}));
+            L.n1w = push(r->raw.need(p + ".norm1.weight", {D}).v); L.n1b = push(r->raw.need(p + ".norm1.bias", {D}).v);
+            L.n2w = push(r->raw.need(p + ".norm2.weight", {D}).v); L.n2b = push(r->raw.need(p + ".norm2.bias", {D}).v);
+            L.ls1 = push(r->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = push(r->raw.need(p + ".layer_scale_2.scale", {D}).v);
             {   // q / k rows of every head reordered evens-then-odds: interleaved RoPE pairs (2i, 2i+1) become rotate-half pairs (i, i + hd/2)
-                const auto& w = rneed(r, p + ".self_attn.in_proj.weight", {3 * D, D});
+                const auto& w = r->raw.need(p + ".self_attn.in_proj.weight", {3 * D, D}).v;
                 std::vector<float> pw(w.size());
                 for (int part = 0; part < 3; ++part)
                     for (int h = 0; h < H; ++h)
@@ -404,9 +387,9 @@ void q3ref_finalize(mis_q3ref* r) {
                         }
                 L.qkv = linear(pw, 3 * D, D);
             }
-            L.o = linear(rneed(r, p + ".self_attn.out_proj.weight", {D, D}), D, D);
-            L.f1 = linear(rneed(r, p + ".gating.linear1.weight", {I, D}), I, D);
-            L.f2 = linear(rneed(r, p + ".gating.linear2.weight", {D, I}), D, I);
+            L.o = linear(r->raw.need(p + ".self_attn.out_proj.weight", {D, D}).v, D, D);
+            L.f1 = linear(r->raw.need(p + ".gating.linear1.weight", {I, D}).v, I, D);
+            L.f2 = linear(r->raw.need(p + ".gating.linear2.weight", {D, I}).v, D, I);
             r->tlayers.push_back(L);
         }
         r->enc_down = conv_strided(P + "downsample.conv.conv.conv", D, r->ds_stride, D, false);
@@ -418,14 +401,14 @@ void q3ref_finalize(mis_q3ref* r) {
             V.nq = g == 0 ? 1 : std::max(0, keep - 1);          // layers beyond the kept ones never influence the kept codes
             if (V.nq == 0) continue;
             {
-                const auto& w = rneed(r, p + ".input_proj.weight", {cd, 1, D});
+                const auto& w = r->raw.need(p + ".input_proj.weight", {cd, 1, D}).v;
                 V.in_proj = linear(w, cd, D);
             }
             std::vector<float> eT((size_t)V.nq * cd * bins), em((size_t)V.nq * bins * cd), e2((size_t)V.nq * bins);
             for (int q = 0; q < V.nq; ++q) {
                 const std::string cbk = p + ".vq.layers." + std::to_string(q) + ".codebook";
-                const auto& es = rneed(r, cbk + ".embedding_sum", {bins, cd});
-                const auto& cu = rneed(r, cbk + ".cluster_usage", {bins});
+                const auto& es = r->raw.need(cbk + ".embedding_sum", {bins, cd}).v;
+                const auto& cu = r->raw.need(cbk + ".cluster_usage", {bins}).v;
                 for (int v = 0; v < bins; ++v) {
                     const float den = std::max(cu[v], 1e-5f);                                    // Quantization.swift:24-27
                     float n2 = 0.0f;
@@ -443,7 +426,7 @@ void q3ref_finalize(mis_q3ref* r) {
     }
     r->arena.alloc(std::max<size_t>(arena.size(), 4));
     HIP_CHECK(hipMemcpy(r->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    r->raw.clear(); r->raw_shape.clear();
+    r->raw.clear();
     r->finalized = true;
 }
 

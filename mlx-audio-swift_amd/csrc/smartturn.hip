@@ -11,8 +11,8 @@
 //   k_st_prepare       the window itself: tail or left padding, (x - mean) / max(std, 1e-7)
 //   mel_spectrogram_device (mel.hip)  symmetric Hann, Slaney scale and norm, last frame dropped, per-row clamp
 //   k_st_patches       k = 3 patches of the f32 features, rounded to bf16, columns zero-padded to a multiple of 32
-//   launch_gemm_big / launch_layernorm / launch_im2col3_bf16 / launch_scatter_kv / launch_attn_prefill (whisper_kernels.hip): the encoder,
-//                      bf16 storage, f32 accumulation, one rounding per primitive
+//   whisper_encoder_enqueue (whisper_kernels.hip)  the encoder, the chain the Whisper engine runs: bf16 storage, f32 accumulation, one
+//                      rounding per primitive
 //   k_st_pool_scores   s_t = w2 . tanh(W0 h_t + b0) + b2 in f32, 8 positions per block (T / 8 blocks per row.  Chosen from the
 //                      arithmetic: at the published shape a row's scores are 400 x 384 x 256 = 39 M multiply-adds, which one
 //                      256-thread block would walk alone; one block per row was not measured.  Measured: scores + head together
@@ -24,7 +24,9 @@
 // As measured the replay is level with plain launches (0.484 vs 0.481 ms on the device at 1 row, 0.865 vs 0.875 ms per call).
 // Prepare and mel stay in front of it: the mel front end allocates and synchronises.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
+#include "lm_kernels.h"
 #include "whisper_kernels.h"
 
 #include <math.h>
@@ -38,8 +40,6 @@
 #define ST_TS 8                  // positions per k_st_pool_scores block
 #define ST_LN_EPS 1e-5f       // MLXNN.LayerNorm default
 
-struct StHostTensor { std::vector<float> v; std::vector<int64_t> shape; };
-struct StLayer { bf16_t *ln1w, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2w, *ln2b, *fc1, *b1, *fc2, *b2; };
 struct StGraph { hipGraphExec_t exec = nullptr; int nodes = 0; };
 
 struct mis_smartturn {
@@ -48,12 +48,11 @@ struct mis_smartturn {
     mis_smartturn_config cfg{};
     int W = 0, F = 0, T = 0, d = 0, H = 0, D = 0, ffn = 0, nmel = 0, K1 = 0, Spad = 0, nch = 0;
     mis_mel_config mel{};
-    std::map<std::string, StHostTensor> raw;
+    HostWeights raw{"Smart Turn", MIS_ERR_INVALID_INPUT};
     bool finalized = false;
     DevBuf<bf16_t> arena;
     DevBuf<float> farena;
-    bf16_t *conv1w = nullptr, *conv1b = nullptr, *conv2w = nullptr, *conv2b = nullptr, *pos = nullptr, *lnw = nullptr, *lnb = nullptr;
-    std::vector<StLayer> layers;
+    WhisperEncWeights enc;
     float *p0wT = nullptr, *p0b = nullptr, *p2w = nullptr, *p2b = nullptr, *c0wT = nullptr, *c0b = nullptr, *c1w = nullptr, *c1b = nullptr,
           *c4wT = nullptr, *c4b = nullptr, *c6w = nullptr, *c6b = nullptr;
     // work buffers for `cap` rows; the graphs hold their addresses and die with them
@@ -126,24 +125,8 @@ extern "C" mis_status mis_smartturn_set_tensor(mis_smartturn* c, const char* nam
     MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    StHostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; t.shape.push_back(shape[i]); }
-    t.v.resize(n);
-    if (dtype == MIS_F32) memcpy(t.v.data(), data, n * 4);
-    else {
-        const uint16_t* s = static_cast<const uint16_t*>(data);
-        for (size_t i = 0; i < n; ++i) t.v[i] = dtype == MIS_F16 ? f16_to_f32_host(s[i]) : bf16_to_f32(s[i]);
-    }
-    c->raw[name] = std::move(t);
+    c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
-}
-
-static const StHostTensor& st_need(mis_smartturn* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_INVALID_INPUT, "Smart Turn weight missing: %s", name.c_str());
-    MIS_REQUIRE(it->second.shape == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Smart Turn weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
@@ -151,31 +134,13 @@ extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
     HIP_CHECK(hipSetDevice(c->device));
     const int64_t d = c->d, f = c->ffn, nm = c->nmel, K1 = c->K1, T = c->T;
-    std::vector<bf16_t> host;                           // bf16 arena assembled on the host: an f32 checkpoint is rounded once, here
-    std::vector<float> fhost;                           // the f32 head
-    auto btake = [&](size_t n) { size_t off = host.size(); host.resize(off + round_up(n, 64), 0); return off; };
-    auto ftake = [&](size_t n) { size_t off = fhost.size(); fhost.resize(off + round_up(n, 64), 0.0f); return off; };
-    auto bvec = [&](const std::string& name, int64_t n) {
-        const StHostTensor& t = st_need(c, name, {n});
-        size_t off = btake(n);
-        for (int64_t i = 0; i < n; ++i) host[off + i] = f32_to_bf16(t.v[i]);
-        return off;
-    };
-    auto bmat_into = [&](const std::string& name, int64_t N, int64_t K, size_t off) {
-        const StHostTensor& t = st_need(c, name, {N, K});
-        for (size_t i = 0; i < (size_t)N * K; ++i) host[off + i] = f32_to_bf16(t.v[i]);
-    };
-    auto bmat = [&](const std::string& name, int64_t N, int64_t K) { size_t off = btake((size_t)N * K); bmat_into(name, N, K, off); return off; };
-    auto fvec = [&](const std::string& name, std::initializer_list<int64_t> shape, int64_t n) {
-        const StHostTensor& t = st_need(c, name, shape);
-        size_t off = ftake(n);
-        for (int64_t i = 0; i < n; ++i) fhost[off + i] = t.v[i];
-        return off;
-    };
+    HostArena a(c->raw);
+    std::vector<bf16_t>& host = a.host;                 // the packers below write through these
+    std::vector<float>& fhost = a.fhost;                // the f32 head
     // Linear.weight [N][K] -> [K][N]: a thread is an output unit, neighbouring threads read neighbouring floats
     auto fmatT = [&](const std::string& name, int64_t N, int64_t K) {
-        const StHostTensor& t = st_need(c, name, {N, K});
-        size_t off = ftake((size_t)N * K);
+        const HostTensor& t = c->raw.need(name, {N, K});
+        size_t off = a.ftake((size_t)N * K);
         for (int64_t n = 0; n < N; ++n) for (int64_t k = 0; k < K; ++k) fhost[off + (size_t)k * N + n] = t.v[(size_t)n * K + k];
         return off;
     };
@@ -183,22 +148,22 @@ extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
     // conv weights [out][k][in] (MLX layout after sanitize): the column order of the k = 3 patches; conv1's rows padded to K1 columns
     size_t o_c1w;
     {
-        const StHostTensor& t = st_need(c, E + ".conv1.weight", {d, 3, nm});
-        o_c1w = btake((size_t)d * K1);
+        const HostTensor& t = c->raw.need(E + ".conv1.weight", {d, 3, nm});
+        o_c1w = a.btake((size_t)d * K1);
         for (int64_t o = 0; o < d; ++o) for (int64_t k = 0; k < 3 * nm; ++k) host[o_c1w + (size_t)o * K1 + k] = f32_to_bf16(t.v[(size_t)o * 3 * nm + k]);
     }
-    const size_t o_c1b = bvec(E + ".conv1.bias", d);
+    const size_t o_c1b = a.bvec(E + ".conv1.bias", d);
     size_t o_c2w;
     {
-        const StHostTensor& t = st_need(c, E + ".conv2.weight", {d, 3, d});
-        o_c2w = btake((size_t)d * 3 * d);
+        const HostTensor& t = c->raw.need(E + ".conv2.weight", {d, 3, d});
+        o_c2w = a.btake((size_t)d * 3 * d);
         for (size_t i = 0; i < (size_t)d * 3 * d; ++i) host[o_c2w + i] = f32_to_bf16(t.v[i]);
     }
-    const size_t o_c2b = bvec(E + ".conv2.bias", d);
+    const size_t o_c2b = a.bvec(E + ".conv2.bias", d);
     size_t o_pos;
     {   // rows 0 .. T - 1 of the table (:141-142)
-        const StHostTensor& t = st_need(c, E + ".embed_positions.weight", {(int64_t)c->cfg.max_source_positions, d});
-        o_pos = btake((size_t)T * d);
+        const HostTensor& t = c->raw.need(E + ".embed_positions.weight", {(int64_t)c->cfg.max_source_positions, d});
+        o_pos = a.btake((size_t)T * d);
         for (size_t i = 0; i < (size_t)T * d; ++i) host[o_pos + i] = f32_to_bf16(t.v[i]);
     }
     struct Off { size_t v[12]; };
@@ -206,48 +171,47 @@ extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
     for (size_t li = 0; li < lo.size(); ++li) {
         const std::string q = E + ".layers." + std::to_string(li);
         Off& o = lo[li];
-        o.v[0] = bvec(q + ".self_attn_layer_norm.weight", d); o.v[1] = bvec(q + ".self_attn_layer_norm.bias", d);
-        o.v[2] = btake((size_t)3 * d * d);
-        bmat_into(q + ".self_attn.q_proj.weight", d, d, o.v[2]);
-        bmat_into(q + ".self_attn.k_proj.weight", d, d, o.v[2] + (size_t)d * d);
-        bmat_into(q + ".self_attn.v_proj.weight", d, d, o.v[2] + (size_t)2 * d * d);
-        o.v[3] = btake(3 * d);
+        o.v[0] = a.bvec(q + ".self_attn_layer_norm.weight", d); o.v[1] = a.bvec(q + ".self_attn_layer_norm.bias", d);
+        o.v[2] = a.btake((size_t)3 * d * d);
+        a.bmat_into(q + ".self_attn.q_proj.weight", d, d, o.v[2]);
+        a.bmat_into(q + ".self_attn.k_proj.weight", d, d, o.v[2] + (size_t)d * d);
+        a.bmat_into(q + ".self_attn.v_proj.weight", d, d, o.v[2] + (size_t)2 * d * d);
+        o.v[3] = a.btake(3 * d);
         {
-            const StHostTensor& qb = st_need(c, q + ".self_attn.q_proj.bias", {d});
-            const StHostTensor& vb = st_need(c, q + ".self_attn.v_proj.bias", {d});
+            const HostTensor& qb = c->raw.need(q + ".self_attn.q_proj.bias", {d});
+            const HostTensor& vb = c->raw.need(q + ".self_attn.v_proj.bias", {d});
             for (int64_t i = 0; i < d; ++i) { host[o.v[3] + i] = f32_to_bf16(qb.v[i]); host[o.v[3] + 2 * d + i] = f32_to_bf16(vb.v[i]); }
             if (c->cfg.k_proj_bias) {
-                const StHostTensor& kb = st_need(c, q + ".self_attn.k_proj.bias", {d});
+                const HostTensor& kb = c->raw.need(q + ".self_attn.k_proj.bias", {d});
                 for (int64_t i = 0; i < d; ++i) host[o.v[3] + d + i] = f32_to_bf16(kb.v[i]);
             }
         }
-        o.v[4] = bmat(q + ".self_attn.out_proj.weight", d, d); o.v[5] = bvec(q + ".self_attn.out_proj.bias", d);
-        o.v[6] = bvec(q + ".final_layer_norm.weight", d); o.v[7] = bvec(q + ".final_layer_norm.bias", d);
-        o.v[8] = bmat(q + ".fc1.weight", f, d); o.v[9] = bvec(q + ".fc1.bias", f);
-        o.v[10] = bmat(q + ".fc2.weight", d, f); o.v[11] = bvec(q + ".fc2.bias", d);
+        o.v[4] = a.bmat(q + ".self_attn.out_proj.weight", d, d); o.v[5] = a.bvec(q + ".self_attn.out_proj.bias", d);
+        o.v[6] = a.bvec(q + ".final_layer_norm.weight", d); o.v[7] = a.bvec(q + ".final_layer_norm.bias", d);
+        o.v[8] = a.bmat(q + ".fc1.weight", f, d); o.v[9] = a.bvec(q + ".fc1.bias", f);
+        o.v[10] = a.bmat(q + ".fc2.weight", d, f); o.v[11] = a.bvec(q + ".fc2.bias", d);
     }
-    const size_t o_lnw = bvec(E + ".layer_norm.weight", d), o_lnb = bvec(E + ".layer_norm.bias", d);
+    const size_t o_lnw = a.bvec(E + ".layer_norm.weight", d), o_lnb = a.bvec(E + ".layer_norm.bias", d);
     // ---- the head, f32 as stored
-    const size_t o_p0w = fmatT("pool_attention_0.weight", ST_POOL_HID, d), o_p0b = fvec("pool_attention_0.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_p2w = fvec("pool_attention_2.weight", {1, ST_POOL_HID}, ST_POOL_HID), o_p2b = fvec("pool_attention_2.bias", {1}, 1);
-    const size_t o_c0w = fmatT("classifier_0.weight", ST_POOL_HID, d), o_c0b = fvec("classifier_0.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_n1w = fvec("classifier_1.weight", {ST_POOL_HID}, ST_POOL_HID), o_n1b = fvec("classifier_1.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_c4w = fmatT("classifier_4.weight", ST_CLS_MID, ST_POOL_HID), o_c4b = fvec("classifier_4.bias", {ST_CLS_MID}, ST_CLS_MID);
-    const size_t o_c6w = fvec("classifier_6.weight", {1, ST_CLS_MID}, ST_CLS_MID), o_c6b = fvec("classifier_6.bias", {1}, 1);
+    const size_t o_p0w = fmatT("pool_attention_0.weight", ST_POOL_HID, d), o_p0b = a.fvec("pool_attention_0.bias", {ST_POOL_HID}, ST_POOL_HID);
+    const size_t o_p2w = a.fvec("pool_attention_2.weight", {1, ST_POOL_HID}, ST_POOL_HID), o_p2b = a.fvec("pool_attention_2.bias", {1}, 1);
+    const size_t o_c0w = fmatT("classifier_0.weight", ST_POOL_HID, d), o_c0b = a.fvec("classifier_0.bias", {ST_POOL_HID}, ST_POOL_HID);
+    const size_t o_n1w = a.fvec("classifier_1.weight", {ST_POOL_HID}, ST_POOL_HID), o_n1b = a.fvec("classifier_1.bias", {ST_POOL_HID}, ST_POOL_HID);
+    const size_t o_c4w = fmatT("classifier_4.weight", ST_CLS_MID, ST_POOL_HID), o_c4b = a.fvec("classifier_4.bias", {ST_CLS_MID}, ST_CLS_MID);
+    const size_t o_c6w = a.fvec("classifier_6.weight", {1, ST_CLS_MID}, ST_CLS_MID), o_c6b = a.fvec("classifier_6.bias", {1}, 1);
     // ---- upload (nothing of the handle has changed up to here: a rejected finalize can be repeated)
-    c->arena.alloc(host.size());
-    c->farena.alloc(fhost.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, host.data(), host.size() * 2, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(c->farena.p, fhost.data(), fhost.size() * 4, hipMemcpyHostToDevice));
+    a.upload(c->arena, c->farena);
     bf16_t* A = c->arena.p;
     float* P = c->farena.p;
-    c->conv1w = A + o_c1w; c->conv1b = A + o_c1b; c->conv2w = A + o_c2w; c->conv2b = A + o_c2b; c->pos = A + o_pos;
-    c->lnw = A + o_lnw; c->lnb = A + o_lnb;
-    c->layers.resize(lo.size());
+    WhisperEncWeights& w = c->enc;
+    w.conv1w = A + o_c1w; w.conv1b = A + o_c1b; w.conv2w = A + o_c2w; w.conv2b = A + o_c2b; w.pos = A + o_pos;
+    w.lnw = A + o_lnw; w.lnb = A + o_lnb;
+    w.d = c->d; w.H = c->H; w.D = c->D; w.ffn = c->ffn; w.K1 = c->K1; w.Spad = c->Spad;
+    w.layers.resize(lo.size());
     for (size_t li = 0; li < lo.size(); ++li) {
         const Off& o = lo[li];
-        c->layers[li] = StLayer{A + o.v[0], A + o.v[1], A + o.v[2], A + o.v[3], A + o.v[4], A + o.v[5], A + o.v[6], A + o.v[7], A + o.v[8], A + o.v[9],
-                                A + o.v[10], A + o.v[11]};
+        w.layers[li] = WhisperEncLayer{A + o.v[0], A + o.v[1], A + o.v[2], A + o.v[3], A + o.v[4], A + o.v[5], A + o.v[6], A + o.v[7], A + o.v[8],
+                                       A + o.v[9], A + o.v[10], A + o.v[11]};
     }
     c->p0wT = P + o_p0w; c->p0b = P + o_p0b; c->p2w = P + o_p2w; c->p2b = P + o_p2b; c->c0wT = P + o_c0w; c->c0b = P + o_c0b;
     c->c1w = P + o_n1w; c->c1b = P + o_n1b; c->c4wT = P + o_c4w; c->c4b = P + o_c4b; c->c6w = P + o_c6w; c->c6b = P + o_c6b;
@@ -260,36 +224,22 @@ extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
 extern "C" mis_status mis_smartturn_init_synthetic(mis_smartturn* c, uint64_t seed) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
-    uint64_t key = seed * 100000ull;
+    SynthWeights sw{c->raw, seed * 100000ull};
     const int64_t d = c->d, f = c->ffn, nm = c->nmel;
-    auto put = [&](const std::string& name, std::vector<int64_t> shape, double amp, float plus) {
-        StHostTensor t;
-        size_t n = 1;
-        for (auto v : shape) n *= (size_t)v;
-        t.shape = shape; t.v.resize(n);
-        ++key;
-        for (size_t i = 0; i < n; ++i) t.v[i] = plus + mis_synth_value(key, i, (float)amp);
-        c->raw[name] = std::move(t);
-    };
-    auto lin = [&](const std::string& p, int64_t o, int64_t i, bool bias, double gain) {
-        put(p + ".weight", {o, i}, gain * sqrt(3.0 / (double)i), 0.0f);
-        if (bias) put(p + ".bias", {o}, 0.05, 0.0f);
-    };
-    auto norm = [&](const std::string& p, int64_t n) { put(p + ".weight", {n}, 0.1, 1.0f); put(p + ".bias", {n}, 0.05, 0.0f); };
-    put("encoder.conv1.weight", {d, 3, nm}, sqrt(3.0 / (3.0 * nm)), 0.0f); put("encoder.conv1.bias", {d}, 0.05, 0.0f);
-    put("encoder.conv2.weight", {d, 3, d}, sqrt(3.0 / (3.0 * d)), 0.0f); put("encoder.conv2.bias", {d}, 0.05, 0.0f);
-    put("encoder.embed_positions.weight", {(int64_t)c->cfg.max_source_positions, d}, 0.1, 0.0f);
+    sw.put("encoder.conv1.weight", {d, 3, nm}, sqrt(3.0 / (3.0 * nm)), 0.0f); sw.put("encoder.conv1.bias", {d}, 0.05, 0.0f);
+    sw.put("encoder.conv2.weight", {d, 3, d}, sqrt(3.0 / (3.0 * d)), 0.0f); sw.put("encoder.conv2.bias", {d}, 0.05, 0.0f);
+    sw.put("encoder.embed_positions.weight", {(int64_t)c->cfg.max_source_positions, d}, 0.1, 0.0f);
     for (int li = 0; li < c->cfg.encoder_layers; ++li) {
         const std::string q = "encoder.layers." + std::to_string(li);
-        norm(q + ".self_attn_layer_norm", d); norm(q + ".final_layer_norm", d);
-        lin(q + ".self_attn.q_proj", d, d, true, 1.0); lin(q + ".self_attn.k_proj", d, d, c->cfg.k_proj_bias != 0, 1.0);
-        lin(q + ".self_attn.v_proj", d, d, true, 1.0); lin(q + ".self_attn.out_proj", d, d, true, 0.5);
-        lin(q + ".fc1", f, d, true, 1.0); lin(q + ".fc2", d, f, true, 0.5);
+        sw.norm(q + ".self_attn_layer_norm", d); sw.norm(q + ".final_layer_norm", d);
+        sw.lin(q + ".self_attn.q_proj", d, d, true, 1.0); sw.lin(q + ".self_attn.k_proj", d, d, c->cfg.k_proj_bias != 0, 1.0);
+        sw.lin(q + ".self_attn.v_proj", d, d, true, 1.0); sw.lin(q + ".self_attn.out_proj", d, d, true, 0.5);
+        sw.lin(q + ".fc1", f, d, true, 1.0); sw.lin(q + ".fc2", d, f, true, 0.5);
     }
-    norm("encoder.layer_norm", d);
-    lin("pool_attention_0", ST_POOL_HID, d, true, 1.0); lin("pool_attention_2", 1, ST_POOL_HID, true, 2.0);
-    lin("classifier_0", ST_POOL_HID, d, true, 1.0); norm("classifier_1", ST_POOL_HID);
-    lin("classifier_4", ST_CLS_MID, ST_POOL_HID, true, 2.0); lin("classifier_6", 1, ST_CLS_MID, true, 2.0);
+    sw.norm("encoder.layer_norm", d);
+    sw.lin("pool_attention_0", ST_POOL_HID, d, true, 1.0); sw.lin("pool_attention_2", 1, ST_POOL_HID, true, 2.0);
+    sw.lin("classifier_0", ST_POOL_HID, d, true, 1.0); sw.norm("classifier_1", ST_POOL_HID);
+    sw.lin("classifier_4", ST_CLS_MID, ST_POOL_HID, true, 2.0); sw.lin("classifier_6", 1, ST_CLS_MID, true, 2.0);
     MIS_API_END
 }
 
@@ -366,10 +316,6 @@ __global__ void __launch_bounds__(256) k_st_features_to_nlc(const float* __restr
     const int t = (int)(r % Fr);
     const size_t b = r / Fr;
     out[i] = in[(b * C + ch) * Fr + t];
-}
-__global__ void k_st_bf16_to_f32(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = bf16_to_f32(src[i]);
 }
 
 // ============================================================================ pool + classifier head (f32)
@@ -510,35 +456,17 @@ static void st_reserve(mis_smartturn* c, int batch) {
     c->cap = batch;
 }
 
-static int st_chain_launches(const mis_smartturn* c) { return 4 + 8 * (int)c->layers.size() + 1 + 2; }
+static int st_chain_launches(const mis_smartturn* c) { return 4 + 8 * (int)c->enc.layers.size() + 1 + 2; }
 
 // features f32 [B][F][nmel] in c->feat -> logits; `mark`: an event recorded between the encoder and the head (plain launches only)
 static void st_enqueue_chain(mis_smartturn* c, int B, hipEvent_t mark) {
     hipStream_t s = c->stream;
-    const int d = c->d, T = c->T, Fr = c->F, f = c->ffn, M1 = B * Fr, M = B * T;
-    const size_t n1 = (size_t)M1 * c->K1;
+    const int d = c->d, T = c->T, Fr = c->F;
+    const size_t n1 = (size_t)B * Fr * c->K1;
     hipLaunchKernelGGL(k_st_patches, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, c->feat.p, c->col1.p, Fr, c->nmel, c->K1, n1);
-    // gelu(conv1), gelu(conv2) + positions (:137-142)
-    BigGemmParams g{c->col1.p, c->conv1w, c->conv1b, nullptr, c->h1.p, M1, d, c->K1, c->K1, 0};
-    launch_gemm_big(BG_GELU, g, s);
-    launch_im2col3_bf16(c->h1.p, c->col2.p, B, Fr, d, T, 2, s);
-    g = BigGemmParams{c->col2.p, c->conv2w, c->conv2b, c->pos, c->h.p, M, d, 3 * d, 3 * d, T};
-    launch_gemm_big(BG_GELU_POS, g, s);
-    for (const StLayer& L : c->layers) {                              // pre-LN blocks (:86-97)
-        launch_layernorm(c->h.p, c->x.p, L.ln1w, L.ln1b, M, d, ST_LN_EPS, s);
-        g = BigGemmParams{c->x.p, L.wqkv, L.bqkv, nullptr, c->qkv.p, M, 3 * d, d, d, 0};
-        launch_gemm_big(BG_NONE, g, s);
-        launch_scatter_kv(c->qkv.p, 3 * d, d, 2 * d, c->kc.p, c->vc.p, B, T, c->H, c->D, c->Spad, s);
-        launch_attn_prefill(c->qkv.p, 3 * d, c->kc.p, c->vc.p, c->att.p, d, B, T, c->H, c->D, c->Spad, s);
-        g = BigGemmParams{c->att.p, L.wo, L.bo, c->h.p, c->h.p, M, d, d, d, 0};
-        launch_gemm_big(BG_RESID, g, s);
-        launch_layernorm(c->h.p, c->x.p, L.ln2w, L.ln2b, M, d, ST_LN_EPS, s);
-        g = BigGemmParams{c->x.p, L.fc1, L.b1, nullptr, c->ff.p, M, f, d, d, 0};
-        launch_gemm_big(BG_GELU, g, s);
-        g = BigGemmParams{c->ff.p, L.fc2, L.b2, c->h.p, c->h.p, M, d, f, f, 0};
-        launch_gemm_big(BG_RESID, g, s);
-    }
-    launch_layernorm(c->h.p, c->enc_out.p, c->lnw, c->lnb, M, d, ST_LN_EPS, s);
+    // the encoder (:86-97, 137-142)
+    const WhisperEncWork k{c->col1.p, c->h1.p, c->col2.p, c->h.p, c->x.p, c->qkv.p, c->att.p, c->ff.p, c->kc.p, c->vc.p};
+    whisper_encoder_enqueue(c->enc, k, B, Fr, T, c->enc_out.p, s);
     if (mark) HIP_CHECK(hipEventRecord(mark, s));
     hipLaunchKernelGGL(k_st_pool_scores, dim3(cdiv(T, ST_TS), B), dim3(ST_POOL_HID), (size_t)ST_TS * d * 4, s, c->enc_out.p, T, d, c->p0wT, c->p0b,
                        c->p2w, c->p2b, c->scores.p);
@@ -667,7 +595,7 @@ extern "C" mis_status mis_debug_smartturn_tap(mis_smartturn* c, int stage, float
     if (stage == 2) {
         DevBuf<float> o;
         o.alloc(n);
-        hipLaunchKernelGGL(k_st_bf16_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->enc_out.p, o.p, n);
+        launch_bf16_to_f32(c->enc_out.p, o.p, n, c->stream);
         HIP_CHECK(hipStreamSynchronize(c->stream));
         HIP_CHECK(hipMemcpy(out, o.p, n * 4, hipMemcpyDeviceToHost));
     } else {

@@ -13,6 +13,7 @@
 //                  bias / residual / NoiseBlock / transposed-conv-phase epilogues
 //   k_snac_final   Snake -> conv k7 (C -> 1) -> tanh
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 
@@ -707,11 +708,6 @@ __global__ void __launch_bounds__(256) k_snac_final(const float* __restrict__ X,
 
 // ============================================================================ host side
 
-struct HostTensor {
-    std::vector<float> v;
-    std::vector<int64_t> shape;
-};
-
 struct ConvW { size_t w = 0, b = 0; bool has_bias = false; };        // offsets into the weight arena (floats)
 struct SnakeW { size_t a = 0, ra = 0; };
 
@@ -719,7 +715,7 @@ struct mis_snac {
     int device = 0;
     hipStream_t stream = nullptr;
     mis_snac_config cfg{};
-    std::map<std::string, HostTensor> raw;
+    HostWeights raw{"SNAC"};
     bool finalized = false;
 
     DevBuf<float> arena;      // folded weights
@@ -774,16 +770,15 @@ int snac_device(const mis_snac* c) { return c->device; }
 const mis_snac_config* snac_config(const mis_snac* c) { return &c->cfg; }
 
 static const HostTensor& need(mis_snac* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "SNAC weight missing: %s", name.c_str());
+    const HostTensor& t = c->raw.need(name);
     std::vector<int64_t> want(shape);
-    if (it->second.shape != want) {
+    if (t.shape != want) {                                              // (SNAC's message names both shapes)
         std::string got, exp;
-        for (auto d : it->second.shape) got += std::to_string(d) + ",";
+        for (auto d : t.shape) got += std::to_string(d) + ",";
         for (auto d : want) exp += std::to_string(d) + ",";
         throw MisError(MIS_ERR_INVALID_INPUT, "SNAC weight " + name + " has shape [" + got + "] expected [" + exp + "]");
     }
-    return it->second;
+    return t;
 }
 
 // w = g * v / (||v||_(1,2) + eps)   (Layers.swift:35-42,102-103; eps = 0 for the transposed conv :166)
@@ -847,15 +842,9 @@ extern "C" mis_status mis_snac_set_tensor(mis_snac* c, const char* name, const v
     MIS_API_BEGIN
     MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 4, MIS_ERR_INVALID_INPUT, "bad argument");
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    HostTensor t;
-    size_t n = 1;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; t.shape.push_back(shape[i]); }
-    t.v.resize(n);
-    if (dtype == MIS_F32) memcpy(t.v.data(), data, n * 4);
-    else if (dtype == MIS_BF16) { const uint16_t* s = (const uint16_t*)data; for (size_t i = 0; i < n; ++i) t.v[i] = bf16_to_f32(s[i]); }
-    else if (dtype == MIS_F16) { const uint16_t* s = (const uint16_t*)data; for (size_t i = 0; i < n; ++i) t.v[i] = f16_to_f32_host(s[i]); }
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype for SNAC tensor");
-    c->raw[name] = std::move(t);
+    HostWeights::count(shape, ndim);                                     // a bad shape is reported before a bad dtype
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_BF16 || dtype == MIS_F16, MIS_ERR_INVALID_INPUT, "unsupported dtype for SNAC tensor");
+    c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -928,9 +917,9 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
         };
         m.qkv = push(lin_t(need(c, p + ".to_qkv.weight", {3 * dim, dim}), 3 * dim, dim));
         m.out = push(lin_t(need(c, p + ".to_out.weight", {dim, dim}), dim, dim));
-        auto fq = c->raw.find(p + ".rel_pos.inv_freq");
+        const HostTensor* fq = c->raw.find(p + ".rel_pos.inv_freq");
         std::vector<float> inv(32);
-        if (fq != c->raw.end() && fq->second.v.size() == 32) inv = fq->second.v;
+        if (fq && fq->v.size() == 32) inv = fq->v;
         else for (int j = 0; j < 32; ++j) inv[j] = 1.0f / powf(10000.0f, (float)(2 * j) / 64.0f);      // SinusoidalEmbeddings.init (:105-107)
         m.inv_freq = push(inv);
         return m;
@@ -991,11 +980,11 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
     // ---- encoder (optional): dimensions are read off the tensors (encoder_dim / encoder_rates are not part of mis_snac_config)
     c->has_encoder = false;
     const std::string E = "encoder.block.layers";
-    auto e0 = c->raw.find(E + ".0.weight_v");
-    if (e0 != c->raw.end()) {
+    const HostTensor* e0 = c->raw.find(E + ".0.weight_v");
+    if (e0) {
         MIS_REQUIRE(cf.depthwise, MIS_ERR_INVALID_INPUT, "SNAC encoder: only depthwise residual units are built");
-        MIS_REQUIRE(e0->second.shape.size() == 3 && e0->second.shape[1] == 7 && e0->second.shape[2] == 1, MIS_ERR_INVALID_INPUT, "bad encoder stem");
-        int64_t ch = e0->second.shape[0];
+        MIS_REQUIRE(e0->shape.size() == 3 && e0->shape[1] == 7 && e0->shape[2] == 1, MIS_ERR_INVALID_INPUT, "bad encoder stem");
+        int64_t ch = e0->shape[0];
         c->enc_dim = (int)ch;
         {
             std::vector<float> w = fold_weight_norm(need(c, E + ".0.weight_g", {ch, 1, 1}), need(c, E + ".0.weight_v", {ch, 7, 1}), 1e-12f);
@@ -1005,13 +994,13 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
         int li = 1;
         for (;; ++li) {
             const std::string b = E + "." + std::to_string(li) + ".block.layers";
-            auto dn = c->raw.find(b + ".4.weight_v");
-            if (dn == c->raw.end()) break;
+            const HostTensor* dn = c->raw.find(b + ".4.weight_v");
+            if (!dn) break;
             mis_snac::EncBlock eb;
             eb.cin = (int)ch;
-            MIS_REQUIRE(dn->second.shape.size() == 3 && dn->second.shape[2] == ch && dn->second.shape[1] % 2 == 0, MIS_ERR_INVALID_INPUT, "bad encoder block %d", li);
-            eb.cout = (int)dn->second.shape[0];
-            eb.stride = (int)dn->second.shape[1] / 2;
+            MIS_REQUIRE(dn->shape.size() == 3 && dn->shape[2] == ch && dn->shape[1] % 2 == 0, MIS_ERR_INVALID_INPUT, "bad encoder block %d", li);
+            eb.cout = (int)dn->shape[0];
+            eb.stride = (int)dn->shape[1] / 2;
             for (int j = 0; j < 3; ++j) {
                 const std::string r = b + "." + std::to_string(j) + ".block.layers";
                 eb.ru[j].s1 = push_snake(r + ".0.alpha", ch);

@@ -8,6 +8,7 @@
 // an exact-f32 MFMA contraction against a host-built inverse-DFT table and the overlap-add is one gather kernel.
 // Activations are NCT ([B][C][T], time contiguous) so the f32 codec kernels of snac.hip are reused unchanged.
 #include "common.h"
+#include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
 
@@ -20,8 +21,7 @@ struct mis_soprano {
     int device = 0;
     mis_soprano_config cfg{};
     mis_tts* lm = nullptr;
-    std::map<std::string, std::vector<float>> raw;
-    std::map<std::string, std::vector<int64_t>> raw_shape;
+    HostWeights raw{"Soprano"};
     bool finalized = false;
     DevBuf<float> arena;
     size_t embed_w = 0, embed_b = 0, norm_w = 0, norm_b = 0, fin_w = 0, fin_b = 0, head_w = 0, head_b = 0, idft = 0, window = 0;
@@ -233,20 +233,10 @@ extern "C" mis_status mis_soprano_set_tensor(mis_soprano* c, const char* name_, 
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     std::string name = sop_sanitize(name_);
     if (name.rfind("decoder.", 0) != 0) return mis_tts_set_tensor(c->lm, name.c_str(), data, dtype, shape, ndim);
-    size_t n = 1;
-    std::vector<int64_t> sh;
-    for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; sh.push_back(shape[i]); }
+    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
     HIP_CHECK(hipSetDevice(c->device));
-    size_t esz = dtype == MIS_F32 ? 4 : 2;
-    std::vector<uint8_t> host(n * esz);
-    HIP_CHECK(hipMemcpy(host.data(), data, n * esz, hipMemcpyDefault));
-    std::vector<float> v(n);                                         // decoder weights are float32 (Soprano.swift:332-339)
-    if (dtype == MIS_F32) memcpy(v.data(), host.data(), n * 4);
-    else if (dtype == MIS_BF16) for (size_t i = 0; i < n; ++i) v[i] = bf16_to_f32(((uint16_t*)host.data())[i]);
-    else if (dtype == MIS_F16) for (size_t i = 0; i < n; ++i) v[i] = f16_to_f32_host(((uint16_t*)host.data())[i]);
-    else throw MisError(MIS_ERR_INVALID_INPUT, "unsupported dtype");
-    c->raw[name] = std::move(v);
-    c->raw_shape[name] = sh;
+    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
+    c->raw.put(name, host.data(), dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -291,16 +281,8 @@ extern "C" mis_status mis_soprano_set_tensor_quantized(mis_soprano* c, const cha
             v[(size_t)n * K + k] = widen(sraw, gi) * q + widen(braw, gi);
         }
     }
-    c->raw[name] = std::move(v);
-    c->raw_shape[name] = {N, K};
+    c->raw.put(name, HostTensor{std::move(v), {N, K}});
     MIS_API_END
-}
-
-static const std::vector<float>& sneed(mis_soprano* c, const std::string& name, std::initializer_list<int64_t> shape) {
-    auto it = c->raw.find(name);
-    MIS_REQUIRE(it != c->raw.end(), MIS_ERR_NOT_INITIALIZED, "Soprano weight missing: %s", name.c_str());
-    MIS_REQUIRE(c->raw_shape[name] == std::vector<int64_t>(shape), MIS_ERR_INVALID_INPUT, "Soprano weight %s has the wrong shape", name.c_str());
-    return it->second;
 }
 
 extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
@@ -321,28 +303,28 @@ extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
     };
     const std::string P = "decoder.decoder";
     {   // embed conv: weight [d][ik][C] (MLX Conv1d) == [d][ik*C] row-major with column kk*C + c
-        const auto& w = sneed(c, P + ".embed.weight", {d, ik, C});
+        const auto& w = c->raw.need(P + ".embed.weight", {d, ik, C}).v;
         c->embed_w = push(transpose(w, d, ik * C));
-        c->embed_b = push(sneed(c, P + ".embed.bias", {d}));
+        c->embed_b = push(c->raw.need(P + ".embed.bias", {d}).v);
     }
-    c->norm_w = push(sneed(c, P + ".norm.weight", {d})); c->norm_b = push(sneed(c, P + ".norm.bias", {d}));
+    c->norm_w = push(c->raw.need(P + ".norm.weight", {d}).v); c->norm_b = push(c->raw.need(P + ".norm.bias", {d}).v);
     c->blocks.clear();
     for (int i = 0; i < cf.decoder_num_layers; ++i) {
         std::string q = P + ".convnext." + std::to_string(i);
         mis_soprano::Blk b{};
-        const auto& dw = sneed(c, q + ".dwconv.weight", {d, dk, 1});
+        const auto& dw = c->raw.need(q + ".dwconv.weight", {d, dk, 1}).v;
         std::vector<float> w7((size_t)d * 7, 0.0f);                    // centre the dk taps in a 7-tap kernel
         for (int64_t ch = 0; ch < d; ++ch) for (int64_t j = 0; j < dk; ++j) w7[ch * 7 + (3 - dk / 2) + j] = dw[ch * dk + j];
-        b.dw = push(w7); b.dwb = push(sneed(c, q + ".dwconv.bias", {d}));
-        b.lnw = push(sneed(c, q + ".norm.weight", {d})); b.lnb = push(sneed(c, q + ".norm.bias", {d}));
-        b.p1 = push(transpose(sneed(c, q + ".pwconv1.weight", {inter, d}), inter, d)); b.b1 = push(sneed(c, q + ".pwconv1.bias", {inter}));
-        b.p2 = push(transpose(sneed(c, q + ".pwconv2.weight", {d, inter}), d, inter)); b.b2 = push(sneed(c, q + ".pwconv2.bias", {d}));
-        b.gamma = push(sneed(c, q + ".gamma", {d}));
+        b.dw = push(w7); b.dwb = push(c->raw.need(q + ".dwconv.bias", {d}).v);
+        b.lnw = push(c->raw.need(q + ".norm.weight", {d}).v); b.lnb = push(c->raw.need(q + ".norm.bias", {d}).v);
+        b.p1 = push(transpose(c->raw.need(q + ".pwconv1.weight", {inter, d}).v, inter, d)); b.b1 = push(c->raw.need(q + ".pwconv1.bias", {inter}).v);
+        b.p2 = push(transpose(c->raw.need(q + ".pwconv2.weight", {d, inter}).v, d, inter)); b.b2 = push(c->raw.need(q + ".pwconv2.bias", {d}).v);
+        b.gamma = push(c->raw.need(q + ".gamma", {d}).v);
         c->blocks.push_back(b);
     }
-    c->fin_w = push(sneed(c, P + ".final_layer_norm.weight", {d})); c->fin_b = push(sneed(c, P + ".final_layer_norm.bias", {d}));
-    c->head_w = push(transpose(sneed(c, "decoder.head.out.weight", {nf + 2, d}), nf + 2, d));
-    c->head_b = push(sneed(c, "decoder.head.out.bias", {nf + 2}));
+    c->fin_w = push(c->raw.need(P + ".final_layer_norm.weight", {d}).v); c->fin_b = push(c->raw.need(P + ".final_layer_norm.bias", {d}).v);
+    c->head_w = push(transpose(c->raw.need("decoder.head.out.weight", {nf + 2, d}).v, nf + 2, d));
+    c->head_b = push(c->raw.need("decoder.head.out.bias", {nf + 2}).v);
     {   // irfft as a contraction: frames[n] = (1/N) sum_k c_k (Re_k cos(2 pi k n / N) - Im_k sin(2 pi k n / N)),
         // c_0 = c_{N/2} = 1, else 2; imaginary parts of DC / Nyquist are ignored (MLXFFT.irfft semantics)
         std::vector<float> at((size_t)2 * bins * nf);
@@ -363,7 +345,7 @@ extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
     }
     c->arena.alloc(arena.size());
     HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
-    c->raw.clear(); c->raw_shape.clear();
+    c->raw.clear();
     c->finalized = true;
     MIS_API_END
 }

@@ -1,5 +1,6 @@
-// whisper_engine.hip - host side of the Whisper STT engine: weights, encoder pass, cached cross K/V, the
-// per-token decoder chain (weight-streaming kernels of lm_kernels.hip) and the greedy generate loop.
+// whisper_engine.hip - host side of the Whisper STT engine: weights, encoder pass (the launches are whisper_encoder_enqueue,
+// whisper_kernels.hip, shared with smartturn.hip), cached cross K/V, the per-token decoder chain (weight-streaming kernels of
+// lm_kernels.hip) and the greedy generate loop.
 //
 // Reference being replaced: WhisperModel (Sources/MLXAudioSTT/Models/Whisper/WhisperModel.swift:36-309),
 // WhisperEncoder / WhisperDecoder (WhisperLayers.swift:110-328).  Tokenisation, prompt construction
@@ -34,7 +35,6 @@ struct QRaw {
 struct QW { int bits = 0; int sbt = MIS_BF16; const void* q = nullptr; const bf16_t* sb = nullptr; };
 enum { WQ_SQKV = 0, WQ_SO = 1, WQ_CQ = 2, WQ_CO = 3, WQ_FC1 = 4, WQ_FC2 = 5, WQ_ROLES = 6 };   // mis_whisper_native_quant_bits roles
 
-struct EncLayer { bf16_t *wqkv, *bqkv, *wo, *bo, *fc1, *b1, *fc2, *b2, *ln1w, *ln1b, *ln2w, *ln2b; };
 struct DecLayer {
     bf16_t *sqkv, *sbqkv, *so, *sbo, *cq, *cbq, *ckv, *cbkv, *co, *cbo, *fc1, *b1, *fc2, *b2;
     bf16_t *ln1w, *ln1b, *ln2w, *ln2b, *ln3w, *ln3b;
@@ -52,9 +52,8 @@ struct mis_whisper {
     DevBuf<bf16_t> arena;                    // all assembled weights (bf16)
     DevBuf<uint8_t> qarena;                  // codes and scale / bias tables of the natively streamed decoder matrices
     QW qvocab;                               // the tied vocab projection as codes (bits == 0: emb_packed)
-    bf16_t *conv1w = nullptr, *conv1b = nullptr, *conv2w = nullptr, *conv2b = nullptr, *enc_pos = nullptr, *enc_lnw = nullptr,
-           *enc_lnb = nullptr, *emb = nullptr, *emb_packed = nullptr, *dec_pos = nullptr, *dec_lnw = nullptr, *dec_lnb = nullptr;
-    std::vector<EncLayer> enc;
+    bf16_t *emb = nullptr, *emb_packed = nullptr, *dec_pos = nullptr, *dec_lnw = nullptr, *dec_lnb = nullptr;
+    WhisperEncWeights enc;                   // the encoder chain is whisper_encoder_enqueue (whisper_kernels.hip)
     std::vector<DecLayer> dec;
     // state
     int batch = 0, Mpad = 0, Smax = 0, Spad = 1536;
@@ -364,15 +363,17 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
                             (int)q->N, (int)q->K, 1, tile_offset, s);
     };
     // ---- encoder
-    c->conv1w = take((size_t)d * c->K1);
+    WhisperEncWeights& we = c->enc;
+    we.d = c->d; we.H = c->He; we.D = c->D; we.ffn = (int)fe; we.K1 = c->K1; we.Spad = c->Spad;
+    we.conv1w = take((size_t)d * c->K1);
     hipLaunchKernelGGL(k_conv_w_reorder, dim3((unsigned)((d * c->K1 + 255) / 256)), dim3(256), 0, s,
-                       wneed(c, E + ".conv1.weight", {d, nm, 3})->buf.p, c->conv1w, (int)d, (int)nm, c->K1);
-    c->conv1b = vec(E + ".conv1.bias", d);
-    c->conv2w = take((size_t)d * 3 * d);
+                       wneed(c, E + ".conv1.weight", {d, nm, 3})->buf.p, we.conv1w, (int)d, (int)nm, c->K1);
+    we.conv1b = vec(E + ".conv1.bias", d);
+    we.conv2w = take((size_t)d * 3 * d);
     hipLaunchKernelGGL(k_conv_w_reorder, dim3((unsigned)((d * 3 * d + 255) / 256)), dim3(256), 0, s,
-                       wneed(c, E + ".conv2.weight", {d, d, 3})->buf.p, c->conv2w, (int)d, (int)d, (int)(3 * d));
-    c->conv2b = vec(E + ".conv2.bias", d);
-    c->enc_pos = take((size_t)1500 * d);
+                       wneed(c, E + ".conv2.weight", {d, d, 3})->buf.p, we.conv2w, (int)d, (int)d, (int)(3 * d));
+    we.conv2b = vec(E + ".conv2.bias", d);
+    we.pos = take((size_t)1500 * d);
     if (!c->raw.count(E + ".embed_positions.weight")) {
         // mlx-whisper checkpoints omit the fixed sinusoid (WhisperModel.swift:376-392 synthesises it): [sin | cos] halves
         const int64_t half = d / 2;
@@ -384,14 +385,14 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
                 pe[pos * d + i] = f32_to_bf16((float)sin(st));
                 pe[pos * d + half + i] = f32_to_bf16((float)cos(st));
             }
-        HIP_CHECK(hipMemcpyAsync(c->enc_pos, pe.data(), pe.size() * 2, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(we.pos, pe.data(), pe.size() * 2, hipMemcpyHostToDevice, s));
         HIP_CHECK(hipStreamSynchronize(s));
     } else
-        copy(c->enc_pos, wneed(c, E + ".embed_positions.weight", {1500, d}));
-    c->enc.resize(Le);
+        copy(we.pos, wneed(c, E + ".embed_positions.weight", {1500, d}));
+    we.layers.resize(Le);
     for (int li = 0; li < Le; ++li) {
         std::string q = E + ".layers." + std::to_string(li);
-        EncLayer& L = c->enc[li];
+        WhisperEncLayer& L = we.layers[li];
         L.wqkv = take((size_t)3 * d * d);
         copy(L.wqkv, wneed(c, q + ".self_attn.q_proj.weight", {d, d}));
         copy(L.wqkv + (size_t)d * d, wneed(c, q + ".self_attn.k_proj.weight", {d, d}));
@@ -408,7 +409,7 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
         L.ln1w = vec(q + ".self_attn_layer_norm.weight", d); L.ln1b = vec(q + ".self_attn_layer_norm.bias", d);
         L.ln2w = vec(q + ".final_layer_norm.weight", d); L.ln2b = vec(q + ".final_layer_norm.bias", d);
     }
-    c->enc_lnw = vec(E + ".layer_norm.weight", d); c->enc_lnb = vec(E + ".layer_norm.bias", d);
+    we.lnw = vec(E + ".layer_norm.weight", d); we.lnb = vec(E + ".layer_norm.bias", d);
     // ---- decoder
     c->emb = take((size_t)V * d);
     copy(c->emb, wneed(c, Dd + ".embed_tokens.weight", {V, d}));
@@ -639,11 +640,10 @@ static void whisper_encode_device(mis_whisper* c, const float* features_dev, int
     HIP_CHECK(hipMemsetAsync(col1.p, 0, col1.bytes(), s));
     HIP_CHECK(hipMemsetAsync(kc.p, 0, kvn * 2, s));
     HIP_CHECK(hipMemsetAsync(vc.p, 0, kvn * 2, s));
+    const WhisperEncWork work{col1.p, h1.p, col2.p, h.p, x.p, qkv.p, att.p, ff.p, kc.p, vc.p};
     for (int b0 = 0; b0 < batch; b0 += SB) {
         const int nb = std::min(SB, batch - b0);
         const int m1 = nb * 3000, m = nb * 1500;
-        BigGemmParams g{};
-        // gelu(conv1), gelu(conv2) + positions     (WhisperLayers.swift:147-151)
         {   // conv1 patches with row stride K1 (zero padded columns)
             DevBuf<bf16_t> tight;
             tight.alloc((size_t)m1 * 3 * c->nmel);
@@ -652,32 +652,12 @@ static void whisper_encode_device(mis_whisper* c, const float* features_dev, int
                                        hipMemcpyDeviceToDevice, s));
             HIP_CHECK(hipStreamSynchronize(s));
         }
-        g = BigGemmParams{col1.p, c->conv1w, c->conv1b, nullptr, h1.p, m1, d, c->K1, c->K1, 0};
-        launch_gemm_big(BG_GELU, g, s);
-        launch_im2col3_bf16(h1.p, col2.p, nb, 3000, d, 1500, 2, s);
-        g = BigGemmParams{col2.p, c->conv2w, c->conv2b, c->enc_pos, h.p, m, d, 3 * d, 3 * d, 1500};
-        launch_gemm_big(BG_GELU_POS, g, s);
-        for (size_t li = 0; li < c->enc.size(); ++li) {
-            const EncLayer& L = c->enc[li];
-            launch_layernorm(h.p, x.p, L.ln1w, L.ln1b, m, d, LN_EPS, s);
-            g = BigGemmParams{x.p, L.wqkv, L.bqkv, nullptr, qkv.p, m, 3 * d, d, d, 0};
-            launch_gemm_big(BG_NONE, g, s);
-            launch_scatter_kv(qkv.p, 3 * d, d, 2 * d, kc.p, vc.p, nb, 1500, H, D, c->Spad, s);
-            launch_attn_prefill(qkv.p, 3 * d, kc.p, vc.p, att.p, d, nb, 1500, H, D, c->Spad, s);
-            g = BigGemmParams{att.p, L.wo, L.bo, h.p, h.p, m, d, d, d, 0};
-            launch_gemm_big(BG_RESID, g, s);                                   // h = h + out_proj(attn)
-            launch_layernorm(h.p, x.p, L.ln2w, L.ln2b, m, d, LN_EPS, s);
-            g = BigGemmParams{x.p, L.fc1, L.b1, nullptr, ff.p, m, fe, d, d, 0};
-            launch_gemm_big(BG_GELU, g, s);
-            g = BigGemmParams{ff.p, L.fc2, L.b2, h.p, h.p, m, d, fe, fe, 0};
-            launch_gemm_big(BG_RESID, g, s);
-        }
         bf16_t* eo = c->enc_out.p + (size_t)b0 * 1500 * d;
-        launch_layernorm(h.p, eo, c->enc_lnw, c->enc_lnb, m, d, LN_EPS, s);
+        whisper_encoder_enqueue(c->enc, work, nb, 3000, 1500, eo, s);
         // cross-attention K/V of every decoder layer, computed once per utterance (WhisperLayers.swift:216-243)
         for (size_t li = 0; li < c->dec.size(); ++li) {
             const DecLayer& L = c->dec[li];
-            g = BigGemmParams{eo, L.ckv, L.cbkv, nullptr, ckv.p, m, 2 * d, d, d, 0};
+            BigGemmParams g{eo, L.ckv, L.cbkv, nullptr, ckv.p, m, 2 * d, d, d, 0};
             launch_gemm_big(BG_NONE, g, s);
             size_t lstride = (size_t)c->batch * c->Hd * c->Spad * D;
             size_t boff = (size_t)b0 * c->Hd * c->Spad * D;
@@ -688,11 +668,6 @@ static void whisper_encode_device(mis_whisper* c, const float* features_dev, int
         HIP_CHECK(hipStreamSynchronize(s));
     }
     whisper_decoder_reset(c);
-}
-
-__global__ void k_bf16_to_f32_flat(const bf16_t* __restrict__ src, float* __restrict__ dst, size_t n) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = bf16_to_f32(src[i]);
 }
 
 extern "C" mis_status mis_whisper_encode(mis_whisper* c, const float* features, int batch, float* enc_out) {
@@ -709,7 +684,7 @@ extern "C" mis_status mis_whisper_encode(mis_whisper* c, const float* features, 
         size_t ne = (size_t)batch * 1500 * c->d;
         DevBuf<float> o;
         o.alloc(ne);
-        hipLaunchKernelGGL(k_bf16_to_f32_flat, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->stream, c->enc_out.p, o.p, ne);
+        launch_bf16_to_f32(c->enc_out.p, o.p, ne, c->stream);
         HIP_CHECK(hipStreamSynchronize(c->stream));
         HIP_CHECK(hipMemcpy(enc_out, o.p, ne * 4, hipMemcpyDefault));
     }

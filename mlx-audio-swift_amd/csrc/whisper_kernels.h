@@ -24,3 +24,16 @@ void launch_whisper_embed_ln(const bf16_t* emb, const bf16_t* pos_emb, const int
                              int max_pos, int batch, int Mpad, hipStream_t s);
 void launch_whisper_suppress(bf16_t* logits, int Vpad, int vocab, const int32_t* sup, int n_sup, const int32_t* bsup, int n_bsup,
                              const int32_t* n_gen, const uint8_t* active, int batch, hipStream_t s);
+
+// The Whisper encoder (WhisperEncoder, WhisperLayers.swift:110-160; Smart Turn's encoder is the same stack): weights as bf16 device
+// pointers, work buffers owned by the caller and sized for B rows.
+struct WhisperEncLayer { bf16_t *ln1w, *ln1b, *wqkv, *bqkv, *wo, *bo, *ln2w, *ln2b, *fc1, *b1, *fc2, *b2; };
+struct WhisperEncWeights {
+    bf16_t *conv1w = nullptr, *conv1b = nullptr, *conv2w = nullptr, *conv2b = nullptr, *pos = nullptr, *lnw = nullptr, *lnb = nullptr;
+    std::vector<WhisperEncLayer> layers;
+    int d = 0, H = 0, D = 0, ffn = 0, K1 = 0, Spad = 0;   // K1: columns of a conv1 patch row; Spad: key rows per head of kc / vc
+};
+struct WhisperEncWork { bf16_t *col1, *h1, *col2, *h, *x, *qkv, *att, *ff, *kc, *vc; };
+// col1 (k = 3 patches of B x frames feature rows, K1 columns) -> enc_out [B T][d], T = frames / 2.  Launches only - 4 + 8 per layer + 1 -
+// on s: no allocation, no synchronisation, so the chain can be captured into a graph.
+void whisper_encoder_enqueue(const WhisperEncWeights& w, const WhisperEncWork& k, int B, int frames, int T, bf16_t* enc_out, hipStream_t s);

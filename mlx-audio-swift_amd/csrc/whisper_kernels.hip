@@ -805,6 +805,33 @@ void launch_attn_prefill(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_
     else throw MisError(MIS_ERR_INVALID_INPUT, "head_dim must be 64 or 128");
 }
 
+// ============================================================================ the encoder chain
+void whisper_encoder_enqueue(const WhisperEncWeights& w, const WhisperEncWork& k, int B, int frames, int T, bf16_t* enc_out, hipStream_t s) {
+    const float eps = 1e-5f;                                          // MLXNN.LayerNorm default
+    const int d = w.d, f = w.ffn, M1 = B * frames, M = B * T;
+    // gelu(conv1), gelu(conv2) + positions     (WhisperLayers.swift:147-151)
+    BigGemmParams g{k.col1, w.conv1w, w.conv1b, nullptr, k.h1, M1, d, w.K1, w.K1, 0};
+    launch_gemm_big(BG_GELU, g, s);
+    launch_im2col3_bf16(k.h1, k.col2, B, frames, d, T, 2, s);
+    g = BigGemmParams{k.col2, w.conv2w, w.conv2b, w.pos, k.h, M, d, 3 * d, 3 * d, T};
+    launch_gemm_big(BG_GELU_POS, g, s);
+    for (const WhisperEncLayer& L : w.layers) {                       // pre-LN blocks
+        launch_layernorm(k.h, k.x, L.ln1w, L.ln1b, M, d, eps, s);
+        g = BigGemmParams{k.x, L.wqkv, L.bqkv, nullptr, k.qkv, M, 3 * d, d, d, 0};
+        launch_gemm_big(BG_NONE, g, s);
+        launch_scatter_kv(k.qkv, 3 * d, d, 2 * d, k.kc, k.vc, B, T, w.H, w.D, w.Spad, s);
+        launch_attn_prefill(k.qkv, 3 * d, k.kc, k.vc, k.att, d, B, T, w.H, w.D, w.Spad, s);
+        g = BigGemmParams{k.att, L.wo, L.bo, k.h, k.h, M, d, d, d, 0};
+        launch_gemm_big(BG_RESID, g, s);                              // h = h + out_proj(attn)
+        launch_layernorm(k.h, k.x, L.ln2w, L.ln2b, M, d, eps, s);
+        g = BigGemmParams{k.x, L.fc1, L.b1, nullptr, k.ff, M, f, d, d, 0};
+        launch_gemm_big(BG_GELU, g, s);
+        g = BigGemmParams{k.ff, L.fc2, L.b2, k.h, k.h, M, d, f, f, 0};
+        launch_gemm_big(BG_RESID, g, s);
+    }
+    launch_layernorm(k.h, enc_out, w.lnw, w.lnb, M, d, eps, s);
+}
+
 // ============================================================================ decoder step helpers
 // h = T(E[tok] + P[pos]) ; x = LayerNorm(h) packed ; advances positions like k_embed_rmsnorm
 __global__ void __launch_bounds__(256) k_whisper_embed_ln(const bf16_t* __restrict__ emb, const bf16_t* __restrict__ pos_emb,

@@ -1,0 +1,155 @@
+// Stand-alone check of csrc/host_weights.h (test_host_weights_cpu.py builds it with the address and undefined-behaviour sanitizers and
+// runs it).  Host code only: no HIP call is made, no device is opened.
+#include "../mlx-audio-swift_amd/csrc/host_weights.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+static int failures = 0;
+#define CHECK(cond)                                                             \
+    do {                                                                        \
+        if (!(cond)) { printf("FAILED line %d: %s\n", __LINE__, #cond); ++failures; } \
+    } while (0)
+
+static uint32_t bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static float from_bits(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+
+// what() and code of the MisError that f throws; code -1: nothing thrown
+template <typename F>
+static std::string thrown(F f, int* code) {
+    *code = -1;
+    try { f(); } catch (const MisError& e) { *code = (int)e.code; return e.what(); }
+    return "";
+}
+
+static void need_messages(const char* label, mis_status missing) {
+    HostWeights w(label, missing);
+    const float v[6] = {1, 2, 3, 4, 5, 6};
+    const int64_t sh[2] = {2, 3};
+    w.put("a.weight", v, MIS_F32, sh, 2);
+    const HostTensor& t = w.need("a.weight", {2, 3});
+    CHECK(t.shape == (std::vector<int64_t>{2, 3}) && t.v.size() == 6 && t.v[5] == 6.0f);
+    CHECK(&w.need("a.weight") == &t && w.find("a.weight") == &t && w.find("b") == nullptr && w.count("a.weight") == 1 && w.count("b") == 0);
+    int code;
+    std::string m = thrown([&] { w.need("b.bias", {3}); }, &code);
+    CHECK(code == (int)missing && m == std::string(label) + " weight missing: b.bias");
+    m = thrown([&] { w.need("b.bias"); }, &code);
+    CHECK(code == (int)missing && m == std::string(label) + " weight missing: b.bias");
+    for (auto wrong : {std::vector<int64_t>{3, 2}, std::vector<int64_t>{6}, std::vector<int64_t>{2, 3, 1}}) {
+        m = thrown([&] {
+            if (wrong.size() == 1) w.need("a.weight", {wrong[0]});
+            else if (wrong.size() == 2) w.need("a.weight", {wrong[0], wrong[1]});
+            else w.need("a.weight", {wrong[0], wrong[1], wrong[2]});
+        }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == std::string(label) + " weight a.weight has the wrong shape");
+    }
+    size_t n = 0;
+    for (auto& kv : w) { CHECK(kv.first == "a.weight"); ++n; }
+    CHECK(n == 1);
+    w.clear();
+    CHECK(w.find("a.weight") == nullptr && w.begin() == w.end());
+}
+
+int main() {
+    HostWeights w("DAC");
+    int code;
+    std::string m;
+    {   // f32 as stored; f16: zero, -zero, the smallest and the largest subnormal, +-inf, full mantissas; bf16
+        const float f[3] = {1.00390625f, -0.0f, 3.0e38f};
+        const int64_t s3[1] = {3};
+        w.put("f32", f, MIS_F32, s3, 1);
+        for (int i = 0; i < 3; ++i) CHECK(bits(w.need("f32", {3}).v[i]) == bits(f[i]));
+        const uint16_t h[10] = {0x0000, 0x8000, 0x0001, 0x03ff, 0x7c00, 0xfc00, 0x3fff, 0x7bff, 0xc248, 0x0400};
+        const uint32_t want[10] = {0x00000000u, 0x80000000u, 0x33800000u /* 2^-24 */, 0x387fc000u /* 1023 x 2^-24 */, 0x7f800000u, 0xff800000u,
+                                   0x3fffe000u /* 1.9990234375 */, 0x477fe000u /* 65504 */, 0xc0490000u /* -3.140625 */, 0x38800000u /* 2^-14 */};
+        const int64_t s10[2] = {2, 5};
+        w.put("f16", h, MIS_F16, s10, 2);
+        const HostTensor& t = w.need("f16", {2, 5});
+        for (int i = 0; i < 10; ++i) CHECK(bits(t.v[i]) == want[i]);
+        CHECK(t.v[2] == 5.9604644775390625e-08f && t.v[3] == 6.097555160522461e-05f && t.v[6] == 1.9990234375f && t.v[7] == 65504.0f);
+        CHECK(isinf(t.v[4]) && t.v[4] > 0 && isinf(t.v[5]) && t.v[5] < 0);
+        const uint16_t b[4] = {0x3f80, 0xc049, 0x0001, 0x7f80};
+        const uint32_t bwant[4] = {0x3f800000u, 0xc0490000u, 0x00010000u, 0x7f800000u};
+        const int64_t s4[3] = {1, 4, 1};
+        w.put("bf16", b, MIS_BF16, s4, 3);
+        for (int i = 0; i < 4; ++i) CHECK(bits(w.need("bf16", {1, 4, 1}).v[i]) == bwant[i]);
+        CHECK(w.need("bf16").v[1] == -3.140625f);
+        m = thrown([&] { w.put("bad", b, MIS_I32, s4, 3); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "unsupported dtype" && !w.find("bad"));
+    }
+    {   // a shape entry <= 0
+        const float f[2] = {1, 2};
+        const int64_t zero[2] = {2, 0}, neg[1] = {-1};
+        m = thrown([&] { w.put("z", f, MIS_F32, zero, 2); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "bad shape");
+        m = thrown([&] { w.put("z", f, MIS_F32, neg, 1); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "bad shape" && !w.find("z"));
+        m = thrown([&] { HostWeights::count(zero, 2); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT);
+        const int64_t ok[3] = {2, 3, 4};
+        CHECK(HostWeights::count(ok, 3) == 24);
+    }
+    {   // the second put of a name replaces the first, shape included
+        const float a[2] = {1, 2}, b[3] = {7, 8, 9};
+        const int64_t s2[1] = {2}, s3[2] = {3, 1};
+        w.put("r", a, MIS_F32, s2, 1);
+        w.put("r", b, MIS_F32, s3, 2);
+        CHECK(w.need("r", {3, 1}).v == (std::vector<float>{7, 8, 9}));
+        thrown([&] { w.need("r", {2}); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT);
+        w.put("r", HostTensor{{4.0f}, {1}});
+        CHECK(w.need("r", {1}).v[0] == 4.0f);
+    }
+    need_messages("Smart Turn", MIS_ERR_INVALID_INPUT);
+    need_messages("DAC", MIS_ERR_NOT_INITIALIZED);
+    {   // arena: offsets rounded up to 64 elements, zero fill, one round-to-nearest-even per element
+        // 1 + 2^-8: tie, even below; 1 + 3 x 2^-8: tie, even above; one ulp above and below the first tie; a negative tie
+        const float f[5] = {from_bits(0x3f808000u), from_bits(0x3f818000u), from_bits(0x3f808001u), from_bits(0x3f807fffu), from_bits(0xbf818000u)};
+        const uint16_t want[5] = {0x3f80, 0x3f82, 0x3f81, 0x3f80, 0xbf82};
+        const int64_t s5[1] = {5}, s23[2] = {2, 3};
+        const float g[6] = {0.5f, -2.0f, 3.0f, 65536.0f, 1e-3f, -0.0f};
+        w.put("v", f, MIS_F32, s5, 1);
+        w.put("m", g, MIS_F32, s23, 2);
+        HostArena a(w);
+        CHECK(a.btake(1) == 0 && a.host.size() == 64);
+        CHECK(a.btake(65) == 64 && a.host.size() == 192);
+        CHECK(a.btake(64) == 192 && a.host.size() == 256);
+        const size_t ov = a.bvec("v", 5);
+        CHECK(ov == 256 && a.host.size() == 320);
+        for (int i = 0; i < 5; ++i) CHECK(a.host[ov + i] == want[i]);
+        const size_t om = a.bmat("m", 2, 3);
+        CHECK(om == 320 && a.host.size() == 384);
+        for (int i = 0; i < 6; ++i) CHECK(a.host[om + i] == f32_to_bf16(g[i]));
+        CHECK(a.host[om + 1] == 0xc000 && a.host[om + 4] == 0x3a83 && a.host[om + 5] == 0x8000);
+        a.bmat_into("m", 2, 3, 10);
+        CHECK(a.host[10] == 0x3f00 && a.host[15] == 0x8000);
+        for (size_t i = 0; i < a.host.size(); ++i)
+            if (!(i >= 10 && i < 16) && !(i >= ov && i < ov + 5) && !(i >= om && i < om + 6)) CHECK(a.host[i] == 0);
+        CHECK(a.ftake(3) == 0 && a.fhost.size() == 64 && a.ftake(128) == 64 && a.fhost.size() == 192);
+        const size_t of = a.fvec("m", {2, 3}, 4);
+        CHECK(of == 192 && a.fhost.size() == 256);
+        for (size_t i = 0; i < a.fhost.size(); ++i) CHECK(bits(a.fhost[i]) == (i >= of && i < of + 4 ? bits(g[i - of]) : 0u));
+        m = thrown([&] { a.bvec("v", 4); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "DAC weight v has the wrong shape" && a.host.size() == 384);
+        m = thrown([&] { a.fvec("nope", {1}, 1); }, &code);
+        CHECK(code == (int)MIS_ERR_NOT_INITIALIZED && m == "DAC weight missing: nope");
+    }
+    {   // synthetic tensors: put k takes key seed + k
+        HostWeights s("Moonshine");
+        SynthWeights sw{s, 7 * 100000ull};
+        sw.lin("p", 2, 3, true, 0.5);
+        sw.norm("n", 2);
+        CHECK(sw.key == 700004ull);
+        const float amp = (float)(0.5 * sqrt(3.0 / 3.0));
+        for (int i = 0; i < 6; ++i) CHECK(s.need("p.weight", {2, 3}).v[i] == 0.0f + mis_synth_value(700001ull, i, amp));
+        for (int i = 0; i < 2; ++i) {
+            CHECK(s.need("p.bias", {2}).v[i] == 0.0f + mis_synth_value(700002ull, i, 0.05f));
+            CHECK(s.need("n.weight", {2}).v[i] == 1.0f + mis_synth_value(700003ull, i, 0.1f));
+            CHECK(s.need("n.bias", {2}).v[i] == 0.0f + mis_synth_value(700004ull, i, 0.05f));
+        }
+    }
+    if (failures) { printf("%d checks failed\n", failures); return 1; }
+    printf("host_weights ok\n");
+    return 0;
+}
