@@ -873,6 +873,53 @@ mis_status mis_smartturn_predict(mis_smartturn*, const float* pcm, const int64_t
 mis_status mis_smartturn_forward_features(mis_smartturn*, const float* features, int batch, float* probability, float* logit);
 
 /* ------------------------------------------------------------------------------------------
+ * Spoken language identification: ECAPA-TDNN over VoxLingua107 (Sources/MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift:13-195,
+ * EcapaTdnnLayers.swift:52-78, EcapaMelSpectrogram.swift:15-55, MLXAudioCodecs/EcapaTdnn/EcapaTdnnBackbone.swift:16-282 with zero padding
+ * and global context): which language is spoken?  16 kHz mono rows of differing lengths, 1..max_batch a call.  Row b of n_b samples has
+ * T_b = n_b / 160 + 1 frames: periodic Hamming window of 400, 200 zeros on each side, power spectrum, HTK filters without
+ * normalisation, 10 log10 max(., 1e-10) floored at the row's own maximum - 80, minus the per-mel mean over the row's own frames; then
+ * the backbone (BatchNorm after every ReLU, running statistics), attentive statistics pooling over the valid frames, and the
+ * BatchNorm / LeakyReLU classifier with log-softmax.  f32 weights and activations, contractions in exact f32 on the matrix cores.
+ * A row's result does not depend on the batch it travels in, on the longest row, or on what lies behind lens[b]: bit for bit.
+ * The workspace is sized once, at finalize, from max_batch and max_samples; a call allocates nothing.
+ * Rejected with MIS_ERR_INVALID_INPUT before any launch: kernel sizes other than 1 / 3 / 5, channels not a multiple of res2net_scale,
+ * sizes outside the ranges mis_ecapa_lid_create names, a tensor missing or misshapen at finalize; at a call, batch outside
+ * 1..max_batch, an empty row (the reference would return NaN), a row longer than stride or max_samples, a null pointer, a handle that
+ * is not finalized.  A rejected call leaves the handle usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_ecapa_lid mis_ecapa_lid;
+/* EcapaTdnnConfig (EcapaTdnnConfig.swift:8-89) + the sizes of the workspace */
+typedef struct {
+    int32_t n_mels, channels, kernel_sizes[5], dilations[5], attention_channels, res2net_scale, se_channels, embedding_dim,
+            classifier_hidden_dim, num_classes;
+    int32_t max_batch, max_samples;      /* 1..64 rows a call; samples per row (at most 120 s) */
+} mis_ecapa_lid_config;
+mis_status mis_ecapa_lid_create(const mis_ecapa_lid_config*, int device, mis_ecapa_lid** out);
+/* names as EcapaTdnn.sanitize leaves them (EcapaTdnnLID.swift:99-131): embedding_model.{block0,mfa,asp.tdnn}.{conv,norm}.*,
+ * embedding_model.blockN.{tdnn1,tdnn2,res2net_block.blocks.M}.{conv,norm}.*, embedding_model.blockN.se_block.conv{1,2}.*,
+ * embedding_model.{asp.conv,asp_bn,fc}.*, classifier.{norm,DNN.block_0.linear.w,DNN.block_0.norm,out.w}.*; conv weights [out, k, in],
+ * BatchNorm as weight / bias / running_mean / running_var; host pointers.  finalize names a missing weight and checks every shape. */
+mis_status mis_ecapa_lid_set_tensor(mis_ecapa_lid*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_ecapa_lid_init_synthetic(mis_ecapa_lid*, uint64_t seed);
+mis_status mis_ecapa_lid_finalize(mis_ecapa_lid*);
+void       mis_ecapa_lid_destroy(mis_ecapa_lid*);
+/* kernel launches of the last call */
+int        mis_ecapa_lid_launches(const mis_ecapa_lid*);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride).  top_k is clamped to 0..num_classes: k.  Outputs caller-allocated, any may be
+ * NULL: log_probs [batch, num_classes], embedding [batch, embedding_dim], top_idx / top_prob [batch, k], sorted on the device by
+ * descending probability, ties to the lower index. */
+mis_status mis_ecapa_lid_predict(mis_ecapa_lid*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int top_k,
+                                 float* log_probs, float* embedding, int32_t* top_idx, float* top_prob);
+/* already-computed mel dB f32 [batch, T, n_mels] with frames[batch] valid frames each (NULL = T): EcapaTdnn.callAsFunction, the
+ * sentence-mean step included */
+mis_status mis_ecapa_lid_forward_features(mis_ecapa_lid*, const float* mel, const int32_t* frames, int batch, int T, int top_k,
+                                          float* log_probs, float* embedding, int32_t* top_idx, float* top_prob);
+/* tensors of the last call, f32, zeros behind a row's own frames.  stage 0 mel dB [B, Ts, n_mels] (Ts: frames of the longest row),
+ * 1 normalised features, 2 block0 [B, Ts, C], 3-5 the SE-Res2Net blocks, 6 mfa [B, Ts, 3 C], 7 pooled [B, 1, 6 C], 8 embedding,
+ * 9 log-probabilities.  dims[3] receives B, Ts, width; out NULL for the dims alone, else room for `capacity` floats. */
+mis_status mis_ecapa_lid_tap(mis_ecapa_lid*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

@@ -139,6 +139,9 @@ mis_status mis_debug_smartturn_tap(mis_smartturn* c, int stage, float* out, int6
  * are one interval: ms[1] holds it and ms[2] is -1. */
 mis_status mis_debug_smartturn_timing(const mis_smartturn* c, float* ms);
 
+/* csrc/ecapa_lid.hip, measurements: device milliseconds of the last call, ms[2] = front end (0 after forward_features), model */
+mis_status mis_debug_ecapa_lid_timing(const mis_ecapa_lid* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ the Swift shim a maintainer would add):
     stt.WhisperModel       <-> class WhisperModel : STTGenerationModel   (MLXAudioSTT/Models/Whisper/WhisperModel.swift)
     moonshine.MoonshineModel <-> class MoonshineModel : STTGenerationModel (MLXAudioSTT/Models/Moonshine/MoonshineModel.swift)
     smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
+    lid.EcapaTdnnLID         <-> class EcapaTdnn (spoken language identification)  (MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -43,6 +44,8 @@ from .moonshine import (MoonshineModel, MoonshineConfig, MoonshineTokenizer, moo
                         moonshine_rotary_dim)
 from .smartturn import (SmartTurnModel, SmartTurnConfig, SmartTurnEncoderConfig, SmartTurnProcessorConfig,  # noqa: F401
                         SmartTurnEndpointOutput, smart_turn_sanitize, smart_turn_expected_keys, smart_turn_read_directory)
+from .lid import (EcapaTdnnLID, EcapaTdnnConfig, LanguagePrediction, LIDOutput, LIDError, ecapa_lid_sanitize,  # noqa: F401
+                  ecapa_lid_expected_shapes, ecapa_lid_labels, ecapa_lid_read_directory)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

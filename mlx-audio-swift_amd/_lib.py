@@ -153,6 +153,13 @@ class SmartTurnConfigC(C.Structure):
                 + [("threshold", C.c_float)])
 
 
+class EcapaLidConfigC(C.Structure):
+    _fields_ = [("n_mels", C.c_int32), ("channels", C.c_int32), ("kernel_sizes", C.c_int32 * 5), ("dilations", C.c_int32 * 5),
+                ("attention_channels", C.c_int32), ("res2net_scale", C.c_int32), ("se_channels", C.c_int32),
+                ("embedding_dim", C.c_int32), ("classifier_hidden_dim", C.c_int32), ("num_classes", C.c_int32),
+                ("max_batch", C.c_int32), ("max_samples", C.c_int32)]
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -288,6 +295,15 @@ SYMBOLS = {
     "mis_smartturn_launches": (C.c_int, [_P]),
     "mis_smartturn_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_float, _P, _P, _P]),
     "mis_smartturn_forward_features": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_ecapa_lid_create": (C.c_int, [C.POINTER(EcapaLidConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_ecapa_lid_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_ecapa_lid_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_ecapa_lid_finalize": (C.c_int, [_P]),
+    "mis_ecapa_lid_destroy": (None, [_P]),
+    "mis_ecapa_lid_launches": (C.c_int, [_P]),
+    "mis_ecapa_lid_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P]),
+    "mis_ecapa_lid_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "mis_ecapa_lid_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -397,6 +413,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_moonshine_stem_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_smartturn_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
+    "mis_debug_ecapa_lid_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 
