@@ -1,4 +1,7 @@
-// codec_kernels.h - f32 kernels shared by the codec back ends (SNAC decoder, Soprano / Vocos decoder); defined in snac.hip
+// codec_kernels.h - f32 kernels shared by the codec back ends.  Defined in snac.hip: the contractions (launch_gemm), the depthwise conv
+// and the encoder / VQ pieces.  Defined in codec_bf3.hip: the split-bf16 path.  Defined in codec_stream.hip: the RVQ gather-sum
+// (launch_codec_embed: DAC, EnCodec, Mimi, Qwen3-TTS), the streaming carry (launch_codec_hist) and the final activation + conv
+// (launch_codec_final) of the Mimi and Qwen3-TTS decoders.
 #pragma once
 #include "common.h"
 #include <vector>
@@ -86,3 +89,16 @@ void launch_enc_first(const float* audio, float* y, const float* w, const float*
 void launch_enc_phase_split(const float* x, float* y, const float* a, const float* ra, int batch, int C, int T, int stride, hipStream_t s);
 void launch_vq_nearest(const float* ze, const float* cn, const float* cn2, int32_t* codes, int batch, int CD, int CB, int Tm, hipStream_t s);
 void launch_vq_residual(float* r, const int32_t* codes, const float* table, int batch, int C, int T, int stride, hipStream_t s);
+
+// codes (element (b, q, t) at codes[b*cs_b + q*cs_q + t*cs_t]; dense [B][nq][T]: cs_b = nq*T, cs_q = T, cs_t = 1) -> h [B][C][ld]
+// (dense: ld = T): sum over q ascending of the folded tables [nq][bins][C]; codes are clamped to [0, bins).  Grid (T, batch)
+void launch_codec_embed(const int32_t* codes, int64_t cs_b, int64_t cs_q, int64_t cs_t, const float* tables, float* h, int nq, int bins, int C,
+                        int ld, int T, int batch, hipStream_t s);
+// streaming carry in front of a causal conv.  st [B][C][H] holds the last H columns this layer's input had before this chunk; x points
+// at column 0 of the chunk's [B][C][ld] input (Tn new columns, H columns of head room in front).  Columns [-H, 0) of x <- st, then
+// st <- the last H columns of [st | new].  H <= 64
+void launch_codec_hist(float* st, float* x, int C, int ld, int H, int Tn, int batch, hipStream_t s);
+// activation -> causal conv k (C -> 1, w [k][C], k <= 8) + bias over columns [0, T) of x [B][C][ld] (columns [x_lo, 0) hold carried
+// history, zero below) -> out [B][out_stride].  a != null: SnakeBeta (a, ra per channel), output clipped to [-1, 1]; a == null: ELU, no clip
+void launch_codec_final(const float* x, float* out, int64_t out_stride, const float* w, float bias, const float* a, const float* ra, int C, int T,
+                        int ld, int x_lo, int k, int batch, hipStream_t s);

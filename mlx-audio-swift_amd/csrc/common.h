@@ -89,6 +89,17 @@ struct PinnedBuf {
     T* release() { T* q = p; p = nullptr; return q; }
 };
 
+// create()'s device check: the device becomes current and gets a non-blocking stream of the handle's own
+static inline hipStream_t mis_open_stream(int device) {
+    int n = 0;
+    HIP_CHECK(hipGetDeviceCount(&n));
+    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
+    HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return s;
+}
+
 static inline size_t round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

@@ -28,7 +28,7 @@ struct mis_dac {
     HostWeights raw{"DAC"};
     bool finalized = false;
     DevBuf<float> arena;
-    struct Lin { size_t w = 0, b = 0; int M = 0, K = 0; };
+    typedef F32Lin Lin;
     struct RU { size_t a1, ra1, a2, ra2; Lin c1, c2; int dil; };
     struct Blk { size_t a, ra; Lin ct; int s, pad, cin, cout; RU ru[3]; };
     size_t tables = 0;
@@ -53,19 +53,6 @@ struct mis_dac {
     DevBuf<float> ebuf[3], vq_ze;
     DevBuf<int32_t> enc_codes;
 };
-
-__global__ void k_dac_embed(const int32_t* __restrict__ codes, const float* __restrict__ tables, float* __restrict__ z, int ncb, int bins,
-                            int C, int T) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float acc = 0.0f;
-        for (int q = 0; q < ncb; ++q) {
-            int code = min(max(codes[((size_t)b * ncb + q) * T + t], 0), bins - 1);
-            acc += tables[((size_t)q * bins + code) * C + c];
-        }
-        z[((size_t)b * C + c) * T + t] = acc;
-    }
-}
 
 // Snake -> conv k7 "same" (C -> 1) -> tanh   (DescriptDAC.swift:146-148)
 __global__ void k_dac_final(const float* __restrict__ x, float* __restrict__ out, int64_t out_stride, const float* __restrict__ w /*[7][C]*/,
@@ -92,13 +79,9 @@ extern "C" mis_status mis_dac_create(const mis_dac_config* cfg, int device, mis_
     MIS_REQUIRE(cfg->n_decoder_rates >= 1 && cfg->n_decoder_rates <= 8 && cfg->decoder_dim >> cfg->n_decoder_rates >= 1 && cfg->n_codebooks >= 1 &&
                     cfg->codebook_size >= 1 && cfg->codebook_dim >= 1 && cfg->latent_dim >= 1,
                 MIS_ERR_INVALID_INPUT, "bad DAC config");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_dac* c = new mis_dac();
-    c->device = device; c->cfg = *cfg; c->latent = cfg->latent_dim;
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->device = device; c->cfg = *cfg; c->latent = cfg->latent_dim; c->stream = stream;
     *out = c;
     MIS_API_END
 }
@@ -125,10 +108,7 @@ extern "C" mis_status mis_dac_set_tensor(mis_dac* c, const char* name_, const vo
         size_t pos;
         while ((pos = name.find(rep.first)) != std::string::npos) name.replace(pos, strlen(rep.first), rep.second);
     }
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    c->raw.put(name, host.data(), dtype, shape, ndim);
+    c->raw.put_staged(c->device, name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -138,8 +118,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
     HIP_CHECK(hipSetDevice(c->device));
     const mis_dac_config& cf = c->cfg;
     const int64_t D = c->latent, cd = cf.codebook_dim, bins = cf.codebook_size, dd = cf.decoder_dim;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
+    F32Arena arena;
     // w = g * v / (||v|| + 1e-12), norm over all axes except `keep` (0: per output channel; 2: per input channel)
     auto wn = [&](const std::string& p, int64_t co, int64_t k, int64_t ci, int keep) {
         const auto& v = c->raw.need(p + ".weight_v", {co, k, ci}).v;
@@ -157,17 +136,14 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
         }
         return w;
     };
-    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {              // -> A^T [(j*ci + c)][co]
-        std::vector<float> w = wn(p, co, k, ci, 0), at((size_t)k * ci * co);
-        for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t i = 0; i < ci; ++i) at[(j * ci + i) * co + o] = w[(o * k + j) * ci + i];
-        mis_dac::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(c->raw.need(p + ".bias", {co}).v);
-        return L;
+    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {
+        return arena.packed(conv_taps_t(wn(p, co, k, ci, 0), co, k, ci), co, k * ci, &c->raw.need(p + ".bias", {co}).v);
     };
     auto snake = [&](const std::string& p, int64_t C, size_t& a, size_t& ra) {
         const auto& al = c->raw.need(p, {1, 1, C}).v;
         std::vector<float> rv(C);
         for (int64_t i = 0; i < C; ++i) rv[i] = 1.0f / (al[i] + 1e-9f);
-        a = push(al); ra = push(rv);
+        a = arena.push(al); ra = arena.push(rv);
     };
     {   // fromCodes: sum_i outProj_i(codebook_i[code]) -> tables [n_cb][bins][D] (bias included once per codebook)
         std::vector<float> tables((size_t)cf.n_codebooks * bins * D);
@@ -176,13 +152,9 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
             const auto& cb = c->raw.need(p + ".codebook.weight", {bins, cd}).v;
             std::vector<float> w = wn(p + ".outProj", D, 1, cd, 0);
             const auto& b = c->raw.need(p + ".outProj.bias", {D}).v;
-            for (int64_t v = 0; v < bins; ++v) for (int64_t o = 0; o < D; ++o) {
-                float acc = 0.0f;
-                for (int64_t k = 0; k < cd; ++k) acc += w[o * cd + k] * cb[v * cd + k];
-                tables[((size_t)q * bins + v) * D + o] = acc + b[o];
-            }
+            fold_tables_into(&tables[(size_t)q * bins * D], w.data(), cb.data(), b.data(), D, cd, bins);
         }
-        c->tables = push(tables);
+        c->tables = arena.push(tables);
     }
     c->first = conv("decoder.model.0", dd, 7, D);
     c->blocks.clear();
@@ -192,12 +164,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
         mis_dac::Blk B{};
         B.s = (int)s; B.pad = (int)pad; B.cin = (int)cin; B.cout = (int)cout;
         snake(p + ".0.alpha", cin, B.a, B.ra);
-        {   // per output phase ph: o = s*n + ph takes taps kk = (ph + pad) % s + s*j from x[n + (ph + pad)/s - j]
-            std::vector<float> w = wn(p + ".1", cout, k, cin, 2), at((size_t)s * 2 * cin * cout);
-            for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t i = 0; i < cin; ++i) for (int64_t o = 0; o < cout; ++o)
-                at[((ph * 2 + j) * cin + i) * cout + o] = w[(o * k + ((ph + pad) % s + s * j)) * cin + i];
-            B.ct.M = (int)cout; B.ct.K = (int)(2 * cin); B.ct.w = push(at); B.ct.b = push(c->raw.need(p + ".1.bias", {cout}).v);
-        }
+        B.ct = arena.packed(convt_phases_t(wn(p + ".1", cout, k, cin, 2), cout, k, cin, s, pad, false), cout, 2 * cin, &c->raw.need(p + ".1.bias", {cout}).v);
         const int dils[3] = {1, 3, 9};
         for (int ri = 0; ri < 3; ++ri) {
             const std::string q = p + "." + std::to_string(ri + 2) + ".block";
@@ -215,7 +182,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
         c->fin_c = (int)cl;
         snake("decoder.model." + std::to_string(n + 1) + ".alpha", cl, c->fin_a, c->fin_ra);
         std::vector<float> w = wn("decoder.model." + std::to_string(n + 2), 1, 7, cl, 0);
-        c->fin_w = push(w);                                              // [1][7][C] == [7][C]
+        c->fin_w = arena.push(w);                                              // [1][7][C] == [7][C]
         c->fin_b = c->raw.need("decoder.model." + std::to_string(n + 2) + ".bias", {1}).v[0];
     }
     // ---- encoder (optional): dimensions are read off the tensors
@@ -228,7 +195,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
             c->enc_dim = (int)ch;
             {
                 std::vector<float> w = wn("encoder.block.0", ch, 7, 1, 0);          // [C][7][1] == [C][7]
-                c->enc_first_w = push(w); c->enc_first_b = push(c->raw.need("encoder.block.0.bias", {ch}).v);
+                c->enc_first_w = arena.push(w); c->enc_first_b = arena.push(c->raw.need("encoder.block.0.bias", {ch}).v);
             }
             c->enc_blocks.clear();
             c->hop = 1;
@@ -263,7 +230,7 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
                                 for (int co = 0; co < E.cout; ++co)
                                     at[(((size_t)qi * ch * sdn) + (size_t)ci * sdn + r) * E.cout + co] = w[((size_t)co * K + j) * ch + ci];
                             }
-                    E.down.M = E.cout; E.down.K = 3 * sdn * (int)ch; E.down.w = push(at); E.down.b = push(c->raw.need(p + ".4.bias", {E.cout}).v);
+                    E.down = arena.packed(at, E.cout, 3 * sdn * ch, &c->raw.need(p + ".4.bias", {E.cout}).v);
                 }
                 c->hop *= E.stride;
                 ch = E.cout;
@@ -287,14 +254,13 @@ extern "C" mis_status mis_dac_finalize(mis_dac* c) {
                     for (int64_t d2 = 0; d2 < cd; ++d2) { const float x = cb[k * cd + d2] * inv; cn[k * cd + d2] = x; s2 += x * x; }
                     cn2[k] = s2;
                 }
-                v.cn = push(cn); v.cn2 = push(cn2);
+                v.cn = arena.push(cn); v.cn2 = arena.push(cn2);
                 c->vq_enc.push_back(v);
             }
             c->has_encoder = true;
         }
     }
-    c->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    arena.upload(c->arena);
     c->raw.clear();
     c->finalized = true;
     MIS_API_END
@@ -402,7 +368,7 @@ static const float* dac_run(mis_dac* c, const int32_t* codes_dev, int batch, int
         g.AT = W + L.w; g.bias = W + L.b; g.X = X; g.Y = Y; g.M = L.M; g.K = L.K; g.N = N; g.Tin = Tin; g.Tout = Tout;
         return g;
     };
-    hipLaunchKernelGGL(k_dac_embed, dim3(T, batch), dim3(256), 0, s, codes_dev, W + c->tables, x, cf.n_codebooks, cf.codebook_size, c->latent, T);
+    launch_codec_embed(codes_dev, (int64_t)cf.n_codebooks * T, T, 1, W + c->tables, x, cf.n_codebooks, cf.codebook_size, c->latent, T, T, batch, s);
     {
         GemmParams g = gp(c->first, x, y, T, T, T);
         g.Cin = c->latent; g.taps = 7; g.dil = 1; g.pad = 3;

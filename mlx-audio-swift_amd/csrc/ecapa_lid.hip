@@ -407,15 +407,11 @@ extern "C" mis_status mis_ecapa_lid_create(const mis_ecapa_lid_config* cfg, int 
                 "embedding_dim / classifier_hidden_dim / num_classes unsupported (1..4096)");
     MIS_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= LID_MAX_BATCH, MIS_ERR_INVALID_INPUT, "max_batch must be 1..%d", LID_MAX_BATCH);
     MIS_REQUIRE(cfg->max_samples >= 1 && cfg->max_samples <= 16000 * 120, MIS_ERR_INVALID_INPUT, "max_samples must be 1..%d", 16000 * 120);
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     auto c = std::make_unique<mis_ecapa_lid>();
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->nm = cfg->n_mels; c->C = cfg->channels; c->A = cfg->attention_channels; c->SE = cfg->se_channels; c->E = cfg->embedding_dim;
     c->Hd = cfg->classifier_hidden_dim; c->N = cfg->num_classes; c->S = cfg->res2net_scale; c->Tcap = (int)(cfg->max_samples / LID_HOP + 1);
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END

@@ -27,7 +27,11 @@ struct mis_encodec {
     bool finalized = false;
     int n_q = 0, dim0 = 0;
     DevBuf<float> arena;
-    struct Lin { size_t w = 0, b = 0, nw = 0, nb = 0; int M = 0, K = 0; };      // nw / nb: GroupNorm weight / bias (group_norm models)
+    struct Lin : F32Lin {                                                        // nw / nb: GroupNorm weight / bias (group_norm models)
+        size_t nw = 0, nb = 0;
+        Lin() {}
+        Lin(const F32Lin& l) : F32Lin(l) {}
+    };
     size_t tables = 0, zeros = 0;
     Lin conv0, last;
     struct Lstm { Lin xproj; size_t wh = 0; };
@@ -43,19 +47,6 @@ struct mis_encodec {
 };
 
 // ---------------------------------------------------------------------------- kernels
-__global__ void k_encodec_embed(const int32_t* __restrict__ codes, const float* __restrict__ tables, float* __restrict__ z, int nq, int bins,
-                                int C, int T) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float acc = 0.0f;
-        for (int q = 0; q < nq; ++q) {
-            int code = min(max(codes[((size_t)b * nq + q) * T + t], 0), bins - 1);
-            acc += tables[((size_t)q * bins + code) * C + c];
-        }
-        z[((size_t)b * C + c) * T + t] = acc;
-    }
-}
-
 // y[c][i], i in [0, left + T + right): EncodecConv1d.pad1d (EncodecLayers.swift:130-171) then optional ELU (:340-350).
 // reflect: left sample i <- x[min(left - i, T-1)], right sample i <- x[max(T-2-i, 0)]; zero mode: zeros.
 __global__ void k_encodec_pad_act(const float* __restrict__ x, float* __restrict__ y, int C, int T, int left, int right, int reflect, int elu) {
@@ -211,14 +202,10 @@ extern "C" mis_status mis_encodec_create(const mis_encodec_config* cfg, int devi
                     cfg->codebook_size >= 1 && cfg->n_quantizers >= 1 && (cfg->audio_channels == 1 || cfg->audio_channels == 2) && cfg->compress >= 1,
                 MIS_ERR_INVALID_INPUT, "bad Encodec config (one or two audio channels)");
     MIS_REQUIRE(cfg->kernel_size <= 7 && cfg->last_kernel_size <= 7 && cfg->residual_kernel_size <= 7, MIS_ERR_INVALID_INPUT, "kernel sizes above 7 are not built");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_encodec* c = new mis_encodec();
-    c->device = device; c->cfg = *cfg; c->n_q = cfg->n_quantizers;
+    c->device = device; c->cfg = *cfg; c->n_q = cfg->n_quantizers; c->stream = stream;
     c->dim0 = cfg->num_filters << cfg->n_upsampling_ratios;
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     *out = c;
     MIS_API_END
 }
@@ -241,10 +228,7 @@ extern "C" mis_status mis_encodec_set_tensor(mis_encodec* c, const char* name_, 
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     std::string name = name_;
     if (name.rfind("encoder.", 0) == 0) return MIS_OK;                    // encode path: not built
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    c->raw.put(name, host.data(), dtype, shape, ndim);
+    c->raw.put_staged(c->device, name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -253,15 +237,15 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
     HIP_CHECK(hipSetDevice(c->device));
     const mis_encodec_config& cf = c->cfg;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
-    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {              // [co][k][ci] -> A^T [(j*ci + c)][co]
-        const auto& w = c->raw.need(p + ".conv.weight", {co, k, ci}).v;
-        std::vector<float> at((size_t)k * ci * co);
-        for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t i = 0; i < ci; ++i) at[(j * ci + i) * co + o] = w[(o * k + j) * ci + i];
-        mis_encodec::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.w = push(at); L.b = push(c->raw.need(p + ".conv.bias", {co}).v);
-        if (cf.group_norm) { L.nw = push(c->raw.need(p + ".norm.weight", {co}).v); L.nb = push(c->raw.need(p + ".norm.bias", {co}).v); }
+    F32Arena arena;
+    // p.conv.{weight, bias} re-laid-out by `at` (+ p.norm.{weight, bias} of the group_norm models) for co output channels
+    auto packed = [&](const std::string& p, const std::vector<float>& at, int64_t co, int64_t K) {
+        mis_encodec::Lin L = arena.packed(at, co, K, &c->raw.need(p + ".conv.bias", {co}).v);
+        if (cf.group_norm) { L.nw = arena.push(c->raw.need(p + ".norm.weight", {co}).v); L.nb = arena.push(c->raw.need(p + ".norm.bias", {co}).v); }
         return L;
+    };
+    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {
+        return packed(p, conv_taps_t(c->raw.need(p + ".conv.weight", {co, k, ci}).v, co, k, ci), co, k * ci);
     };
     {
         const int64_t D = cf.codebook_dim;
@@ -270,20 +254,17 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
             const auto& e = c->raw.need("quantizer.layers." + std::to_string(q) + ".codebook.embed", {cf.codebook_size, D}).v;
             memcpy(tables.data() + (size_t)q * cf.codebook_size * D, e.data(), e.size() * 4);
         }
-        c->tables = push(tables);
+        c->tables = arena.push(tables);
     }
     int64_t dim = c->dim0;
-    c->zeros = push(std::vector<float>((size_t)dim, 0.0f));
+    c->zeros = arena.zeros((size_t)dim);
     c->conv0 = conv("decoder.layers.0", dim, cf.kernel_size, cf.hidden_size);
     c->lstm.clear();
     for (int j = 0; j < cf.num_lstm_layers; ++j) {
         const std::string p = "decoder.layers.1.lstm." + std::to_string(j);
         mis_encodec::Lstm L;
-        const auto& wx = c->raw.need(p + ".Wx", {4 * dim, dim}).v;
-        std::vector<float> at((size_t)dim * 4 * dim);
-        for (int64_t o = 0; o < 4 * dim; ++o) for (int64_t i = 0; i < dim; ++i) at[i * 4 * dim + o] = wx[o * dim + i];
-        L.xproj.M = (int)(4 * dim); L.xproj.K = (int)dim; L.xproj.w = push(at); L.xproj.b = push(c->raw.need(p + ".bias", {4 * dim}).v);
-        L.wh = push(c->raw.need(p + ".Wh", {4 * dim, dim}).v);
+        L.xproj = arena.packed(lin_t(c->raw.need(p + ".Wx", {4 * dim, dim}).v, 4 * dim, dim), 4 * dim, dim, &c->raw.need(p + ".bias", {4 * dim}).v);
+        L.wh = arena.push(c->raw.need(p + ".Wh", {4 * dim, dim}).v);
         c->lstm.push_back(L);
     }
     c->ups.clear();
@@ -294,12 +275,7 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
         U.s = (int)s; U.cin = (int)cin; U.cout = (int)cout;
         {   // causal transposed conv: out[s*n + ph] = sum_j sum_c W[co][ph + s*j][c] x[c][n - j]  (full conv, right trim k - s)
             const std::string p = "decoder.layers." + std::to_string(li + 1);
-            const auto& w = c->raw.need(p + ".conv.weight", {cout, k, cin}).v;
-            std::vector<float> at((size_t)s * 2 * cin * cout);
-            for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t i = 0; i < cin; ++i) for (int64_t o = 0; o < cout; ++o)
-                at[((ph * 2 + j) * cin + i) * cout + o] = w[(o * k + (ph + s * j)) * cin + i];
-            U.ct.M = (int)cout; U.ct.K = (int)(2 * cin); U.ct.w = push(at); U.ct.b = push(c->raw.need(p + ".conv.bias", {cout}).v);
-            if (cf.group_norm) { U.ct.nw = push(c->raw.need(p + ".norm.weight", {cout}).v); U.ct.nb = push(c->raw.need(p + ".norm.bias", {cout}).v); }
+            U.ct = packed(p, convt_phases_t(c->raw.need(p + ".conv.weight", {cout, k, cin}).v, cout, k, cin, s, 0, false), cout, 2 * cin);
         }
         li += 2;
         dim = cout;
@@ -319,8 +295,7 @@ extern "C" mis_status mis_encodec_finalize(mis_encodec* c) {
         c->ups.push_back(U);
     }
     c->last = conv("decoder.layers." + std::to_string(li + 1), cf.audio_channels, cf.last_kernel_size, dim);
-    c->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    arena.upload(c->arena);
     c->raw.clear();
     c->finalized = true;
     MIS_API_END
@@ -371,7 +346,7 @@ static const float* encodec_run(mis_encodec* c, const int32_t* codes_dev, int nq
         if (gn) group_norm(Y, Tout, 0, Y, L, R, Tout);          // norm(conv(x)) (+ the residual, which the plain path adds in the GEMM epilogue)
         return Tout;
     };
-    hipLaunchKernelGGL(k_encodec_embed, dim3(T, batch), dim3(256), 0, s, codes_dev, W + c->tables, x, nq, cf.codebook_size, cf.codebook_dim, T);
+    launch_codec_embed(codes_dev, (int64_t)nq * T, T, 1, W + c->tables, x, nq, cf.codebook_size, cf.codebook_dim, T, T, batch, s);
     int Tc = conv1d(c->conv0, cf.hidden_size, cf.kernel_size, 1, x, y, T, 0, nullptr);
     std::swap(x, y);
     if (stage == 1) { *outC = H; *outT = Tc; return x; }

@@ -1,5 +1,6 @@
 // host_weights.h - a model's checkpoint tensors between set_tensor and finalize, widened to f32 on the host (HostWeights), and the
-// bf16 / f32 weight arenas that finalize assembles from them and uploads once (HostArena).
+// weight arenas that finalize assembles from them and uploads once: bf16 + f32 for the LM-shaped models (HostArena), exact f32 with
+// the codec re-layouts for the codec engines (F32Arena, lin_t / conv_taps_t / convt_phases_t / fold_tables_into).
 #pragma once
 #include "common.h"
 
@@ -36,6 +37,13 @@ public:
         put(name, std::move(t));
     }
     void put(const std::string& name, HostTensor&& t) { map_[name] = std::move(t); }
+    // set_tensor's staging copy: the caller's pointer may be a device one (of `device`)
+    void put_staged(int device, const std::string& name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
+        std::vector<uint8_t> host(count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
+        HIP_CHECK(hipSetDevice(device));
+        HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));
+        put(name, host.data(), dtype, shape, ndim);
+    }
 
     const HostTensor& need(const std::string& name) const {
         auto it = map_.find(name);
@@ -116,5 +124,85 @@ struct HostArena {
         farena.alloc(fhost.size());
         HIP_CHECK(hipMemcpy(arena.p, host.data(), host.size() * 2, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(farena.p, fhost.data(), fhost.size() * 4, hipMemcpyHostToDevice));
+    }
+};
+
+// ---------------------------------------------------------------------------- exact-f32 codec arenas
+// Re-layouts of checkpoint weights into the A^T operands of launch_gemm (codec_kernels.h); plain index arithmetic, no rounding.
+// Linear [out][in] -> A^T [in][out]
+static inline std::vector<float> lin_t(const std::vector<float>& w, int64_t out, int64_t in) {
+    std::vector<float> at((size_t)in * out);
+    for (int64_t o = 0; o < out; ++o) for (int64_t i = 0; i < in; ++i) at[i * out + o] = w[o * in + i];
+    return at;
+}
+// dense conv [co][k][ci] -> A^T [(j ci + c)][co]
+static inline std::vector<float> conv_taps_t(const std::vector<float>& w, int64_t co, int64_t k, int64_t ci) {
+    std::vector<float> at((size_t)k * ci * co);
+    for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
+    return at;
+}
+// transposed conv (k taps, stride s, k / s taps per output phase) [co][k][ci], or [ci][k][co] when in_major -> [s][(j ci + c)][co]:
+// output phase ph (o = s n + ph) takes tap ((ph + pad) % s) + s j from x[n + (ph + pad) / s - j]
+static inline std::vector<float> convt_phases_t(const std::vector<float>& w, int64_t co, int64_t k, int64_t ci, int64_t s, int64_t pad, bool in_major) {
+    const int64_t nt = k / s;
+    std::vector<float> at((size_t)s * nt * ci * co);
+    for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < nt; ++j) {
+        const int64_t tap = (ph + pad) % s + s * j;
+        for (int64_t c = 0; c < ci; ++c) for (int64_t o = 0; o < co; ++o)
+            at[((ph * nt + j) * ci + c) * co + o] = in_major ? w[(c * k + tap) * co + o] : w[(o * k + tap) * ci + c];
+    }
+    return at;
+}
+// folded quantiser table dst[code][c] = sum_d proj[c][d] codebook[code][d] (+ bias[c]): f32 accumulator, d ascending, bias after the
+// sum.  The codebook is taken as given: a caller that normalises it does so first, in its own arithmetic.
+static inline void fold_tables_into(float* dst, const float* proj, const float* codebook, const float* bias, int64_t C, int64_t cd, int64_t bins) {
+    for (int64_t v = 0; v < bins; ++v)
+        for (int64_t c = 0; c < C; ++c) {
+            float acc = 0.0f;
+            for (int64_t d = 0; d < cd; ++d) acc += proj[c * cd + d] * codebook[v * cd + d];
+            dst[v * C + c] = bias ? acc + bias[c] : acc;
+        }
+}
+
+// one contraction's operands in an F32Arena: A^T at w ([K][M]), bias at b (npos: none); offsets count floats
+struct F32Lin {
+    static constexpr size_t npos = (size_t)-1;
+    size_t w = 0, b = npos;
+    int M = 0, K = 0;
+};
+
+// The f32 arena of a codec engine, assembled on the host in push order.  Offsets count floats and are multiples of 4 (they feed 16-byte
+// loads): every push pads the arena with zeros to the next multiple.
+struct F32Arena {
+    std::vector<float> host;
+
+    size_t push(const std::vector<float>& v) {
+        const size_t o = host.size();
+        host.insert(host.end(), v.begin(), v.end());
+        host.resize(round_up(host.size(), 4), 0.0f);
+        return o;
+    }
+    size_t zeros(size_t n) { return push(std::vector<float>(n, 0.0f)); }
+    // a re-laid-out A^T [K][M] and its bias (nullptr: none)
+    F32Lin packed(const std::vector<float>& at, int64_t M, int64_t K, const std::vector<float>* bias) {
+        F32Lin L;
+        L.M = (int)M; L.K = (int)K;
+        L.w = push(at);
+        if (bias) L.b = push(*bias);
+        return L;
+    }
+    // prefix.weight [out][in] (+ prefix.bias [out])
+    F32Lin lin(const HostWeights& s, const std::string& prefix, int64_t out, int64_t in, bool bias) {
+        const std::vector<float> at = lin_t(s.need(prefix + ".weight", {out, in}).v, out, in);
+        return packed(at, out, in, bias ? &s.need(prefix + ".bias", {out}).v : nullptr);
+    }
+    // prefix.weight [co][k][ci], prefix.bias [co]
+    F32Lin conv(const HostWeights& s, const std::string& prefix, int64_t co, int64_t k, int64_t ci) {
+        const std::vector<float> at = conv_taps_t(s.need(prefix + ".weight", {co, k, ci}).v, co, k, ci);
+        return packed(at, co, k * ci, &s.need(prefix + ".bias", {co}).v);
+    }
+    void upload(DevBuf<float>& arena) const {
+        arena.alloc(host.size());
+        HIP_CHECK(hipMemcpy(arena.p, host.data(), host.size() * 4, hipMemcpyHostToDevice));
     }
 };

@@ -450,15 +450,11 @@ struct mis_mel_stream {
 extern "C" mis_status mis_mel_stream_create(int device, int sample_rate, int n_fft, int hop_length, int n_mels, mis_mel_stream** out) {
     MIS_API_BEGIN
     MIS_REQUIRE(out && n_fft >= 2 && hop_length >= 1 && hop_length <= n_fft && n_mels >= 1 && sample_rate >= 1, MIS_ERR_INVALID_INPUT, "bad argument");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_mel_stream* h = new mis_mel_stream();
-    h->device = device;
+    h->device = device; h->stream = stream;
     h->cfg.sample_rate = sample_rate; h->cfg.n_fft = n_fft; h->cfg.hop_length = hop_length; h->cfg.n_mels = n_mels;
     h->cfg.window = 1; h->cfg.mel_scale = 0; h->cfg.slaney_norm = 1; h->cfg.drop_last_frame = 0;      // hanningWindow + melFilters(norm: "slaney") (:54-60)
-    HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->rmax.alloc(1);
     *out = h;
     MIS_API_END

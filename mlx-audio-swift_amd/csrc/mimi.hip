@@ -13,7 +13,7 @@
 // shape pays, exact-f32 MFMA otherwise), the transformer on k_q3_norm_ct / k_q3_attn with the q / k rows of every head permuted
 // evens-then-odds (interleaved RoPE == rotate-half RoPE on the permuted rows).  ELU is a staging pass (k_mimi_elu) in front of the conv
 // that consumes it: the operand prologues of the shared GEMMs stay exactly as they are.
-// Streaming: work buffers carry MIMI_HP columns of head room in front of every row; k_q3_hist-style carries drop the last (k-1)*d
+// Streaming: work buffers carry MIMI_HP columns of head room in front of every row; launch_codec_hist carries drop the last (k-1)*d
 // inputs of every causal conv and the last input column of every transposed conv there (StreamableConvTranspose1d.step subtracts the
 // bias from its carried tail, Conv.swift:316, so the overlap-add is exact and nothing is added twice).  The transformer keeps K/V in a
 // per-layer ring; a step's queries see keys [max(0, s*f - context), p] (the cache trim of Transformer.swift:155-166 under MLX's
@@ -42,7 +42,7 @@ struct mis_mimi {
     HostWeights raw{"Mimi"};
     bool finalized = false;
     DevBuf<float> arena;
-    struct Lin { size_t w = 0, b = (size_t)-1; int M = 0, K = 0; };
+    typedef F32Lin Lin;
     size_t rvq_tables = 0, up_w = 0, zeros = 0;
     struct TL { size_t n1w, n1b, n2w, n2b, ls1, ls2; Lin qkv, o, f1, f2; };
     std::vector<TL> tl;
@@ -68,22 +68,6 @@ struct mis_mimi {
 };
 
 // ---------------------------------------------------------------------------- kernels
-// codes [B][nq][T] (element (b, q, t) at codes[b*cs_b + q*cs_q + t*cs_t]) -> h [B][C][ld]: sum over the given quantizers of the folded
-// tables [nq][bins][C] (table 0 = rvq_first.output_proj . codebook 0, table q >= 1 = rvq_rest.output_proj . codebook q)
-__global__ void k_mimi_rvq(const int32_t* __restrict__ codes, int64_t cs_b, int64_t cs_q, int64_t cs_t, const float* __restrict__ tables,
-                           float* __restrict__ h, int nq, int bins, int C, int ld) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float acc = 0.0f;
-        for (int q = 0; q < nq; ++q) {
-            int code = codes[(size_t)b * cs_b + (size_t)q * cs_q + (size_t)t * cs_t];
-            code = min(max(code, 0), bins - 1);
-            acc += tables[((size_t)q * bins + code) * C + c];
-        }
-        h[((size_t)b * C + c) * ld + t] = acc;
-    }
-}
-
 // ConvTrUpsample1d (depthwise, k = 2s, no bias, causal trim): y[c][s m + p] = x[c][m] w[c][p] + x[c][m-1] w[c][p+s]; column -1 of x is
 // the carried input when streaming (x_lo = -HP), zero otherwise.  w [C][2s]
 __global__ void k_mimi_upsample(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ w, int C, int Tin, int ldx,
@@ -106,58 +90,12 @@ __global__ void k_mimi_elu(const float* __restrict__ x, float* __restrict__ y, i
     y[o] = v > 0.0f ? v : expf(v) - 1.0f;
 }
 
-// streaming carry (as k_q3_hist): columns [-H, 0) of x <- st, then st <- the last H columns of [st | new]
-__global__ void __launch_bounds__(64) k_mimi_hist(float* __restrict__ st, float* __restrict__ x, int C, int ld, int H, int Tn) {
-    const int c = blockIdx.x, b = blockIdx.y, i = threadIdx.x;
-    float* sr = st + ((size_t)b * C + c) * H;
-    float* xr = x + ((size_t)b * C + c) * ld;
-    float old = 0.0f, nw = 0.0f;
-    if (i < H) {
-        old = sr[i];
-        const int src = Tn - H + i;
-        nw = src >= 0 ? xr[src] : sr[i + Tn];
-    }
-    __syncthreads();
-    if (i < H) { xr[i - H] = old; sr[i] = nw; }
-}
-
 // K and V rows of the fused q|k|v output (columns [0, Tn)) -> ring columns (pos0 + t) % ring
 __global__ void k_mimi_kv_ring(const float* __restrict__ qkv, int64_t q_bs, int q_ld, int row0, float* __restrict__ kv, int64_t kv_bs,
                                int ring, int pos0, int Tn) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y, b = blockIdx.z;
     if (t >= Tn) return;
     kv[(size_t)b * kv_bs + (size_t)r * ring + (pos0 + t) % ring] = qkv[(size_t)b * q_bs + (size_t)(row0 + r) * q_ld + t];
-}
-
-// ELU -> causal conv k (C -> 1) + bias (final_conv1d): 256 output columns per block, 16 channels at a time staged in LDS with the ELU
-// applied once per element; accumulation channel-major, tap-minor
-#define MIMI_F_TILE 256
-#define MIMI_F_CH 16
-__global__ void __launch_bounds__(256) k_mimi_final(const float* __restrict__ x, float* __restrict__ out, int64_t out_stride,
-                                                    const float* __restrict__ w /*[k][C]*/, float bias, int C, int T, int ld, int x_lo, int k) {
-    __shared__ float sx[MIMI_F_CH][MIMI_F_TILE + 8];
-    const int b = blockIdx.y, t0 = blockIdx.x * MIMI_F_TILE, tid = threadIdx.x;
-    const int halo = k - 1;                                              // k <= 8
-    float acc = bias;
-    for (int c0 = 0; c0 < C; c0 += MIMI_F_CH) {
-        __syncthreads();
-        for (int i = tid; i < MIMI_F_CH * (MIMI_F_TILE + halo); i += 256) {
-            const int cc = i / (MIMI_F_TILE + halo), j = i - cc * (MIMI_F_TILE + halo);
-            const int c = c0 + cc, t = t0 - halo + j;
-            float v = 0.0f;
-            if (c < C && t >= x_lo && t < T) {
-                v = x[((int64_t)b * C + c) * ld + t];
-                v = v > 0.0f ? v : expf(v) - 1.0f;
-            }
-            sx[cc][j] = v;
-        }
-        __syncthreads();
-        const int cmax = min(MIMI_F_CH, C - c0);
-        for (int cc = 0; cc < cmax; ++cc)
-            for (int j = 0; j < k; ++j) acc += w[j * C + c0 + cc] * sx[cc][tid + j];
-    }
-    const int t = t0 + tid;
-    if (t < T) out[(size_t)b * out_stride + t] = acc;
 }
 
 // ---------------------------------------------------------------------------- handle and weights
@@ -200,13 +138,9 @@ extern "C" mis_status mis_mimi_create(const mis_mimi_config* cfg, int device, mi
     const int s = (int)(enc_fps / (double)c.frame_rate);                                   // Mimi.swift:125-126
     MIS_REQUIRE(s >= 1 && s <= 8, MIS_ERR_INVALID_INPUT, "Mimi up/downsample stride %d unsupported", s);
     MIS_REQUIRE(((int64_t)(c.n_filters) << c.n_ratios) >= 1, MIS_ERR_INVALID_INPUT, "bad Mimi filters");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_mimi* m = new mis_mimi();
-    m->device = device; m->cfg = c; m->up_s = s;
-    HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    m->device = device; m->cfg = c; m->up_s = s; m->stream = stream;
     *out = m;
     MIS_API_END
 }
@@ -230,10 +164,7 @@ extern "C" mis_status mis_mimi_set_tensor(mis_mimi* m, const char* name, const v
     MIS_API_BEGIN
     MIS_REQUIRE(m && name && data && shape, MIS_ERR_INVALID_INPUT, "null argument");
     MIS_REQUIRE(!m->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(m->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    m->raw.put(name, host.data(), dtype, shape, ndim);
+    m->raw.put_staged(m->device, name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -249,35 +180,14 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
     const mis_mimi_config& cf = m->cfg;
     const int64_t D = cf.dimension, H = cf.num_heads, hd = D / H, I = cf.dim_feedforward, nq = cf.num_quantizers, bins = cf.bins,
                   qd = cf.quantizer_dim, s = m->up_s;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
-    auto lin_t = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) {                  // [out][in] -> A^T [in][out]
-        mis_mimi::Lin L; L.M = (int)out_f; L.K = (int)in_f;
-        std::vector<float> at((size_t)in_f * out_f);
-        for (int64_t o = 0; o < out_f; ++o) for (int64_t i = 0; i < in_f; ++i) at[i * out_f + o] = w[o * in_f + i];
-        L.w = push(at);
-        return L;
+    F32Arena arena;
+    auto linear = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) { return arena.packed(lin_t(w, out_f, in_f), out_f, in_f, nullptr); };
+    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) { return arena.conv(m->raw, p, co, k, ci); };
+    auto convT = [&](const std::string& p, int64_t co, int64_t r, int64_t ci) {                     // [co][2r][ci], causal: phase ph takes taps ph + r j
+        return arena.packed(convt_phases_t(m->raw.need(p + ".weight", {co, 2 * r, ci}).v, co, 2 * r, ci, r, 0, false), co, 2 * ci,
+                            &m->raw.need(p + ".bias", {co}).v);
     };
-    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {                      // [co][k][ci] -> A^T [(j ci + c)][co]
-        const auto& w = m->raw.need(p + ".weight", {co, k, ci}).v;
-        mis_mimi::Lin L; L.M = (int)co; L.K = (int)(k * ci);
-        std::vector<float> at((size_t)k * ci * co);
-        for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
-        L.w = push(at);
-        L.b = push(m->raw.need(p + ".bias", {co}).v);
-        return L;
-    };
-    auto convT = [&](const std::string& p, int64_t co, int64_t r, int64_t ci) {                     // [co][2r][ci] -> [r][(j ci + c)][co], tap p + r j
-        const auto& w = m->raw.need(p + ".weight", {co, 2 * r, ci}).v;
-        mis_mimi::Lin L; L.M = (int)co; L.K = (int)(2 * ci);
-        std::vector<float> at((size_t)2 * r * ci * co);
-        for (int64_t ph = 0; ph < r; ++ph) for (int64_t j = 0; j < 2; ++j) for (int64_t c = 0; c < ci; ++c) for (int64_t o = 0; o < co; ++o)
-            at[((ph * 2 + j) * ci + c) * co + o] = w[(o * 2 * r + (ph + r * j)) * ci + c];
-        L.w = push(at);
-        L.b = push(m->raw.need(p + ".bias", {co}).v);
-        return L;
-    };
-    m->zeros = push(std::vector<float>((size_t)std::max<int64_t>(D, (int64_t)cf.n_filters << cf.n_ratios), 0.0f));
+    m->zeros = arena.zeros((size_t)std::max<int64_t>(D, (int64_t)cf.n_filters << cf.n_ratios));
     {   // folded RVQ tables [nq][bins][D] = output_proj . (embedding_sum / max(cluster_usage, 1e-5))  (Quantization.swift:22-32)
         std::vector<float> tables((size_t)nq * bins * D);
         for (int64_t q = 0; q < nq; ++q) {
@@ -286,27 +196,23 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
             const auto& es = m->raw.need(p + ".embedding_sum", {bins, qd}).v;
             const auto& cu = m->raw.need(p + ".cluster_usage", {bins}).v;
             const auto& pw = m->raw.need("quantizer." + grp + ".output_proj.weight", {D, 1, qd}).v;
-            std::vector<float> e((size_t)qd);
+            std::vector<float> e((size_t)bins * qd);
             for (int64_t v = 0; v < bins; ++v) {
                 const float den = std::max(cu[v], 1e-5f);
-                for (int64_t k = 0; k < qd; ++k) e[k] = es[v * qd + k] / den;
-                for (int64_t c = 0; c < D; ++c) {
-                    float acc = 0.0f;
-                    for (int64_t k = 0; k < qd; ++k) acc += pw[c * qd + k] * e[k];
-                    tables[((size_t)q * bins + v) * D + c] = acc;
-                }
+                for (int64_t k = 0; k < qd; ++k) e[v * qd + k] = es[v * qd + k] / den;
             }
+            fold_tables_into(&tables[(size_t)q * bins * D], pw.data(), e.data(), nullptr, D, qd, bins);
         }
-        m->rvq_tables = push(tables);
+        m->rvq_tables = arena.push(tables);
     }
-    m->up_w = push(m->raw.need("upsample.convtr.convtr.convtr.weight", {D, 2 * s, 1}).v);                   // [C][2s][1] == [C][2s]
+    m->up_w = arena.push(m->raw.need("upsample.convtr.convtr.convtr.weight", {D, 2 * s, 1}).v);                   // [C][2s][1] == [C][2s]
     m->tl.clear();
     for (int li = 0; li < cf.num_layers; ++li) {
         const std::string p = "decoder_transformer.transformer.layers." + std::to_string(li);
         mis_mimi::TL L{};
-        L.n1w = push(m->raw.need(p + ".norm1.weight", {D}).v); L.n1b = push(m->raw.need(p + ".norm1.bias", {D}).v);
-        L.n2w = push(m->raw.need(p + ".norm2.weight", {D}).v); L.n2b = push(m->raw.need(p + ".norm2.bias", {D}).v);
-        L.ls1 = push(m->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = push(m->raw.need(p + ".layer_scale_2.scale", {D}).v);
+        L.n1w = arena.push(m->raw.need(p + ".norm1.weight", {D}).v); L.n1b = arena.push(m->raw.need(p + ".norm1.bias", {D}).v);
+        L.n2w = arena.push(m->raw.need(p + ".norm2.weight", {D}).v); L.n2b = arena.push(m->raw.need(p + ".norm2.bias", {D}).v);
+        L.ls1 = arena.push(m->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = arena.push(m->raw.need(p + ".layer_scale_2.scale", {D}).v);
         {   // q / k rows of every head evens-then-odds (as q3_reference.hip): interleaved RoPE pairs become rotate-half pairs
             const auto& w = m->raw.need(p + ".self_attn.in_proj.weight", {3 * D, D}).v;
             std::vector<float> pw(w.size());
@@ -316,11 +222,11 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
                         const int64_t src = part < 2 ? (i < hd / 2 ? 2 * i : 2 * (i - hd / 2) + 1) : i;
                         memcpy(&pw[((size_t)part * D + (size_t)h * hd + i) * D], &w[((size_t)part * D + (size_t)h * hd + src) * D], (size_t)D * 4);
                     }
-            L.qkv = lin_t(pw, 3 * D, D);
+            L.qkv = linear(pw, 3 * D, D);
         }
-        L.o = lin_t(m->raw.need(p + ".self_attn.out_proj.weight", {D, D}).v, D, D);
-        L.f1 = lin_t(m->raw.need(p + ".gating.linear1.weight", {I, D}).v, I, D);
-        L.f2 = lin_t(m->raw.need(p + ".gating.linear2.weight", {D, I}).v, D, I);
+        L.o = linear(m->raw.need(p + ".self_attn.out_proj.weight", {D, D}).v, D, D);
+        L.f1 = linear(m->raw.need(p + ".gating.linear1.weight", {I, D}).v, I, D);
+        L.f2 = linear(m->raw.need(p + ".gating.linear2.weight", {D, I}).v, D, I);
         m->tl.push_back(L);
     }
     int64_t mult = (int64_t)1 << cf.n_ratios;
@@ -348,7 +254,7 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
     m->fin_c = cf.n_filters;
     {
         const auto& w = m->raw.need("decoder.final_conv1d.conv.conv.weight", {1, cf.last_kernel_size, cf.n_filters}).v;   // [1][k][C] == [k][C]
-        m->fin_w = push(w);
+        m->fin_w = arena.push(w);
         m->fin_b = m->raw.need("decoder.final_conv1d.conv.conv.bias", {1}).v[0];
     }
     // the encoder: present when the checkpoint carries it
@@ -376,8 +282,7 @@ extern "C" mis_status mis_mimi_finalize(mis_mimi* m) {
         } catch (...) { q3ref_destroy(e); throw; }
         m->enc = e;
     }
-    m->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(m->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    arena.upload(m->arena);
     m->raw.clear();
     m->finalized = true;
     MIS_API_END
@@ -427,7 +332,7 @@ static const float* mimi_run(mis_mimi* m, const int32_t* codes_dev, int64_t cs_b
     float *a = m->buf[0].p + HP, *b = m->buf[1].p + HP, *t1 = m->buf[2].p + HP, *t2 = m->buf[3].p + HP;   // column 0 of row 0
     auto gemm = [&](const mis_mimi::Lin& L, const float* X, float* Y, int N, int Tin, int Tout, const float* R = nullptr, const float* scale = nullptr) {
         GemmParams g{};
-        g.AT = W + L.w; g.bias = L.b == (size_t)-1 ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale;
+        g.AT = W + L.w; g.bias = L.b == F32Lin::npos ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale;
         g.M = L.M; g.K = L.K; g.N = N; g.Tin = Tin; g.Tout = Tout;
         g.ldx = LD(Tin); g.ldy = LD(Tout); g.x_lo = -HP;
         return g;
@@ -436,14 +341,14 @@ static const float* mimi_run(mis_mimi* m, const int32_t* codes_dev, int64_t cs_b
     auto hist = [&](float* x, int C, int Tn, int Hc) {
         if (!st || Hc == 0) return;
         MIS_REQUIRE(Hc <= MIMI_HP && hist_cur + (size_t)batch * C * Hc <= st->hist_n, MIS_ERR_GENERATION_FAILED, "streaming history overflow");
-        hipLaunchKernelGGL(k_mimi_hist, dim3(C, batch), dim3(64), 0, s, st->hist.p + hist_cur, x, C, LD(Tn), Hc, Tn);
+        launch_codec_hist(st->hist.p + hist_cur, x, C, LD(Tn), Hc, Tn, batch, s);
         hist_cur += (size_t)batch * C * Hc;
     };
     auto elu = [&](const float* x, float* y, int C, int Tc) {
         hipLaunchKernelGGL(k_mimi_elu, dim3(cdiv(Tc, 256), C, batch), dim3(256), 0, s, x, y, C, Tc, LD(Tc));
     };
     const float* Z = W + m->zeros;
-    hipLaunchKernelGGL(k_mimi_rvq, dim3(T, batch), dim3(256), 0, s, codes_dev, cs_b, cs_q, cs_t, W + m->rvq_tables, a, n_q, cf.bins, D, LD(T));
+    launch_codec_embed(codes_dev, cs_b, cs_q, cs_t, W + m->rvq_tables, a, n_q, cf.bins, D, LD(T), T, batch, s);
     if (stop_after == 1) { *outC = D; *outT = T; return a; }
     // ConvTrUpsample1d
     const int Tt = T * us;
@@ -517,8 +422,7 @@ static const float* mimi_run(mis_mimi* m, const int32_t* codes_dev, int64_t cs_b
     }
     MIS_REQUIRE((int64_t)Tc == mis_mimi_num_samples(m, T), MIS_ERR_GENERATION_FAILED, "internal length mismatch");
     hist(x, m->fin_c, Tc, cf.last_kernel_size - 1);
-    hipLaunchKernelGGL(k_mimi_final, dim3(cdiv(Tc, MIMI_F_TILE), batch), dim3(256), 0, s, x, wav_dev, wav_stride, W + m->fin_w, m->fin_b, m->fin_c,
-                       Tc, LD(Tc), -HP, cf.last_kernel_size);
+    launch_codec_final(x, wav_dev, wav_stride, W + m->fin_w, m->fin_b, nullptr, nullptr, m->fin_c, Tc, LD(Tc), -HP, cf.last_kernel_size, batch, s);   // ELU
     HIP_CHECK(hipGetLastError());
     if (st) {
         MIS_REQUIRE(hist_cur == st->hist_n, MIS_ERR_GENERATION_FAILED, "streaming history bookkeeping mismatch");

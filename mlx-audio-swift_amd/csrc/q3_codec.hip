@@ -36,7 +36,7 @@ struct mis_q3dec {
     bool finalized = false;
     DevBuf<float> arena;
     size_t rvq_tables = 0, zeros = 0;
-    struct Lin { size_t w = 0, b = 0; int M = 0, K = 0; };
+    typedef F32Lin Lin;
     struct Layer { size_t ln1, ln2, ls1, ls2; Lin qkv, o, gu, down; };
     Lin pre_conv, in_proj, out_proj, dec0;
     size_t tnorm = 0;
@@ -64,38 +64,6 @@ struct mis_q3dec {
 #define Q3_HP 64                           // head-room columns in front of every work-buffer row (>= 6*9 = longest history)
 
 // ---------------------------------------------------------------------------- kernels
-// codes [B][nq][T] -> h [B][C][T]: sum over quantizers of the folded tables [nq][bins][C]
-// code (b, q, t) at codes[b*cs_b + q*cs_q + t*cs_t]: [B][nq][T] arrays and the generate loop's [B][frames][nq] store alike
-__global__ void k_q3_rvq(const int32_t* __restrict__ codes, int64_t cs_b, int64_t cs_q, int64_t cs_t, const float* __restrict__ tables,
-                         float* __restrict__ h, int nq, int bins, int C, int ld) {
-    const int t = blockIdx.x, b = blockIdx.y;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float acc = 0.0f;
-        for (int q = 0; q < nq; ++q) {
-            int code = codes[(size_t)b * cs_b + (size_t)q * cs_q + (size_t)t * cs_t];
-            code = min(max(code, 0), bins - 1);
-            acc += tables[((size_t)q * bins + code) * C + c];
-        }
-        h[((size_t)b * C + c) * ld + t] = acc;
-    }
-}
-
-// streaming: history columns in and out.  st [B][C][H] holds the last H columns this layer's input had before this chunk; x points
-// at column 0 of the chunk's [B][C][ld] input (Tn new columns).  Columns [-H, 0) of x <- st, then st <- the last H columns of
-// [st | new]  (CausalConv1d.step :201-210).  One block per row, H <= 64.
-__global__ void __launch_bounds__(64) k_q3_hist(float* __restrict__ st, float* __restrict__ x, int C, int ld, int H, int Tn) {
-    const int c = blockIdx.x, b = blockIdx.y, i = threadIdx.x;
-    float* sr = st + ((size_t)b * C + c) * H;
-    float* xr = x + ((size_t)b * C + c) * ld;
-    float old = 0.0f, nw = 0.0f;
-    if (i < H) {
-        old = sr[i];
-        const int src = Tn - H + i;
-        nw = src >= 0 ? xr[src] : sr[i + Tn];
-    }
-    __syncthreads();
-    if (i < H) { xr[i - H] = old; sr[i] = nw; }
-}
 // streaming: K and V rows of the fused q|k|v output (columns [0, Tn)) -> cache columns [pos0, pos0 + Tn)
 __global__ void k_q3_kv_append(const float* __restrict__ qkv, int64_t q_bs, int q_ld, int row0, float* __restrict__ kv, int64_t kv_bs,
                                int kv_ld, int rows, int pos0, int Tn) {
@@ -243,39 +211,6 @@ __global__ void __launch_bounds__(64) k_q3_attn(Q3AttnArgs a) {
     }
 }
 
-// SnakeBeta -> causal conv k (C -> 1) -> clip(-1, 1)   (DecoderOutputSnake / DecoderOutputConv :676-730, clip :945)
-// 256 output columns per block; 16 channels at a time are staged through LDS with the activation applied ONCE per element (the
-// per-thread version evaluated sin() k times per element and ran at 0.6 TB/s); accumulation order as before: channel-major, tap-minor
-#define Q3F_TILE 256
-#define Q3F_CH 16
-__global__ void __launch_bounds__(256) k_q3_final(const float* __restrict__ x, float* __restrict__ out, int64_t out_stride,
-                                                  const float* __restrict__ w /*[k][C]*/, float bias, const float* __restrict__ a,
-                                                  const float* __restrict__ ra, int C, int T, int ld, int x_lo, int k) {
-    __shared__ float sx[Q3F_CH][Q3F_TILE + 8];
-    const int b = blockIdx.y, t0 = blockIdx.x * Q3F_TILE, tid = threadIdx.x;
-    const int halo = k - 1;                                              // k <= 8
-    float acc = bias;
-    for (int c0 = 0; c0 < C; c0 += Q3F_CH) {
-        __syncthreads();
-        for (int i = tid; i < Q3F_CH * (Q3F_TILE + halo); i += 256) {
-            const int cc = i / (Q3F_TILE + halo), j = i - cc * (Q3F_TILE + halo);
-            const int c = c0 + cc, t = t0 - halo + j;
-            float v = 0.0f;
-            if (c < C && t >= x_lo && t < T) {
-                v = x[((int64_t)b * C + c) * ld + t];
-                v = fmaf(ra[c], mis_sin_sq(a[c] * v), v);
-            }
-            sx[cc][j] = v;
-        }
-        __syncthreads();
-        const int cmax = min(Q3F_CH, C - c0);
-        for (int cc = 0; cc < cmax; ++cc)
-            for (int j = 0; j < k; ++j) acc += w[j * C + c0 + cc] * sx[cc][tid + j];
-    }
-    const int t = t0 + tid;
-    if (t < T) out[(size_t)b * out_stride + t] = fminf(fmaxf(acc, -1.0f), 1.0f);
-}
-
 void launch_q3_attn(const Q3AttnArgs& a, int D, int batch, hipStream_t s) {
     dim3 ag(cdiv(a.Tq, 64), a.H, batch);
     if (D == 64) hipLaunchKernelGGL((k_q3_attn<64>), ag, dim3(64), 0, s, a);
@@ -315,10 +250,7 @@ int q3dec_total_upsample(const mis_q3dec* d) {
 mis_status mis_q3dec_set_tensor(mis_q3dec* d, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
     MIS_REQUIRE(!d->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(d->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    d->raw.put(name, host.data(), dtype, shape, ndim);
+    d->raw.put_staged(d->device, name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -330,32 +262,14 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
     const int64_t Cd = cf.dec_codebook_dim, half = Cd / 2, bins = cf.dec_codebook_size, nq = cf.dec_num_quantizers,
                   nsem = cf.dec_num_semantic_quantizers, ld = cf.dec_latent_dim, hs = cf.dec_hidden_size, I = cf.dec_intermediate_size,
                   H = cf.dec_num_heads, Hkv = cf.dec_num_kv_heads, D = cf.dec_head_dim, dd = cf.dec_decoder_dim;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
-    auto lin_t = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) {                  // [out][in] -> A^T [in][out]
-        std::vector<float> at((size_t)in_f * out_f);
-        for (int64_t o = 0; o < out_f; ++o) for (int64_t i = 0; i < in_f; ++i) at[i * out_f + o] = w[o * in_f + i];
-        return at;
-    };
-    auto conv_t = [&](const std::vector<float>& w, int64_t co, int64_t k, int64_t ci) {           // [co][k][ci] -> A^T [(j*ci + c)][co]
-        std::vector<float> at((size_t)k * ci * co);
-        for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
-        return at;
-    };
-    auto convT_t = [&](const std::vector<float>& w, int64_t co, int64_t k, int64_t ci, int64_t s) { // -> [s][(j*ci + c)][co], tap p + s*j
-        const int64_t nt = k / s;
-        std::vector<float> at((size_t)s * nt * ci * co);
-        for (int64_t p = 0; p < s; ++p) for (int64_t j = 0; j < nt; ++j) for (int64_t c = 0; c < ci; ++c) for (int64_t o = 0; o < co; ++o)
-            at[((p * nt + j) * ci + c) * co + o] = w[(o * k + (p + s * j)) * ci + c];
-        return at;
-    };
+    F32Arena arena;
     auto snake_pair = [&](const std::string& pa, const std::string& pb, int64_t C, size_t& a, size_t& ra) {
         const auto& al = d->raw.need(pa, {C}).v; const auto& be = d->raw.need(pb, {C}).v;
         std::vector<float> av(C), rv(C);
         for (int64_t i = 0; i < C; ++i) { av[i] = expf(al[i]); rv[i] = 1.0f / (expf(be[i]) + 1e-9f); }   // SnakeBeta :236-254
-        a = push(av); ra = push(rv);
+        a = arena.push(av); ra = arena.push(rv);
     };
-    d->zeros = push(std::vector<float>((size_t)std::max<int64_t>({ld, dd, Cd, 4}), 0.0f));
+    d->zeros = arena.zeros((size_t)std::max<int64_t>({ld, dd, Cd, 4}));
     {   // folded RVQ tables [nq][bins][Cd] = output_proj . (embedding_sum / max(cluster_usage, 1e-5))
         std::vector<float> tables((size_t)nq * bins * Cd);
         for (int64_t q = 0; q < nq; ++q) {
@@ -365,42 +279,35 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
             const auto& es = d->raw.need(p + ".embedding_sum", {bins, half}).v;
             const auto& cu = d->raw.need(p + ".cluster_usage", {bins}).v;
             const auto& pw = d->raw.need("decoder.quantizer." + grp + ".output_proj.weight", {Cd, 1, half}).v;
+            std::vector<float> e((size_t)bins * half);
             for (int64_t v = 0; v < bins; ++v) {
                 const float inv = 1.0f / std::max(cu[v], 1e-5f);
-                for (int64_t c = 0; c < Cd; ++c) {
-                    float acc = 0.0f;
-                    for (int64_t k = 0; k < half; ++k) acc += pw[c * half + k] * (es[v * half + k] * inv);
-                    tables[((size_t)q * bins + v) * Cd + c] = acc;
-                }
+                for (int64_t k = 0; k < half; ++k) e[v * half + k] = es[v * half + k] * inv;
             }
+            fold_tables_into(&tables[(size_t)q * bins * Cd], pw.data(), e.data(), nullptr, Cd, half, bins);
         }
-        d->rvq_tables = push(tables);
+        d->rvq_tables = arena.push(tables);
     }
-    auto lin = [&](const std::string& p, int64_t out_f, int64_t in_f, bool bias) {
-        mis_q3dec::Lin L; L.M = (int)out_f; L.K = (int)in_f;
-        L.w = push(lin_t(d->raw.need(p + ".weight", {out_f, in_f}).v, out_f, in_f));
-        L.b = bias ? push(d->raw.need(p + ".bias", {out_f}).v) : (size_t)-1;
-        return L;
-    };
-    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) {
-        mis_q3dec::Lin L; L.M = (int)co; L.K = (int)(k * ci);
-        L.w = push(conv_t(d->raw.need(p + ".weight", {co, k, ci}).v, co, k, ci));
-        L.b = push(d->raw.need(p + ".bias", {co}).v);
-        return L;
+    auto lin = [&](const std::string& p, int64_t out_f, int64_t in_f, bool bias) { return arena.lin(d->raw, p, out_f, in_f, bias); };
+    auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci) { return arena.conv(d->raw, p, co, k, ci); };
+    // causal transposed conv [co][k][ci], k / s taps per phase: phase ph takes taps ph + s j
+    auto convT = [&](const std::string& p, int64_t co, int64_t k, int64_t ci, int64_t s) {
+        return arena.packed(convt_phases_t(d->raw.need(p + ".weight", {co, k, ci}).v, co, k, ci, s, 0, false), co, k / s * ci,
+                            &d->raw.need(p + ".bias", {co}).v);
     };
     d->pre_conv = conv("decoder.pre_conv.conv", ld, 3, Cd);
     const std::string P = "decoder.pre_transformer";
     d->in_proj = lin(P + ".input_proj", hs, ld, true);
     d->out_proj = lin(P + ".output_proj", ld, hs, true);
-    d->tnorm = push(d->raw.need(P + ".norm.weight", {hs}).v);
+    d->tnorm = arena.push(d->raw.need(P + ".norm.weight", {hs}).v);
     d->layers.clear();
     for (int li = 0; li < cf.dec_num_layers; ++li) {
         const std::string p = P + ".layers." + std::to_string(li);
         mis_q3dec::Layer L{};
-        L.ln1 = push(d->raw.need(p + ".input_layernorm.weight", {hs}).v);
-        L.ln2 = push(d->raw.need(p + ".post_attention_layernorm.weight", {hs}).v);
-        L.ls1 = push(d->raw.need(p + ".self_attn_layer_scale.scale", {hs}).v);
-        L.ls2 = push(d->raw.need(p + ".mlp_layer_scale.scale", {hs}).v);
+        L.ln1 = arena.push(d->raw.need(p + ".input_layernorm.weight", {hs}).v);
+        L.ln2 = arena.push(d->raw.need(p + ".post_attention_layernorm.weight", {hs}).v);
+        L.ls1 = arena.push(d->raw.need(p + ".self_attn_layer_scale.scale", {hs}).v);
+        L.ls2 = arena.push(d->raw.need(p + ".mlp_layer_scale.scale", {hs}).v);
         {   // q, k, v rows concatenated: one GEMM
             std::vector<float> w;
             for (const char* nm : {"q_proj", "k_proj", "v_proj"}) {
@@ -408,14 +315,14 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
                 const auto& t = d->raw.need(p + ".self_attn." + nm + ".weight", {rows, hs}).v;
                 w.insert(w.end(), t.begin(), t.end());
             }
-            L.qkv.M = (int)((H + 2 * Hkv) * D); L.qkv.K = (int)hs; L.qkv.w = push(lin_t(w, L.qkv.M, hs)); L.qkv.b = (size_t)-1;
+            L.qkv = arena.packed(lin_t(w, (H + 2 * Hkv) * D, hs), (H + 2 * Hkv) * D, hs, nullptr);
         }
         L.o = lin(p + ".self_attn.o_proj", hs, H * D, false);
         {
             std::vector<float> w = d->raw.need(p + ".mlp.gate_proj.weight", {I, hs}).v;
             const auto& u = d->raw.need(p + ".mlp.up_proj.weight", {I, hs}).v;
             w.insert(w.end(), u.begin(), u.end());
-            L.gu.M = (int)(2 * I); L.gu.K = (int)hs; L.gu.w = push(lin_t(w, 2 * I, hs)); L.gu.b = (size_t)-1;
+            L.gu = arena.packed(lin_t(w, 2 * I, hs), 2 * I, hs, nullptr);
         }
         L.down = lin(p + ".mlp.down_proj", hs, I, false);
         d->layers.push_back(L);
@@ -426,14 +333,12 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         const std::string p = "decoder.upsample." + std::to_string(i) + ".layers";
         mis_q3dec::Up U{};
         U.f = (int)f;
-        U.ct.M = (int)ld; U.ct.K = (int)ld;
-        U.ct.w = push(convT_t(d->raw.need(p + ".0.conv.weight", {ld, f, ld}).v, ld, f, ld, f));
-        U.ct.b = push(d->raw.need(p + ".0.conv.bias", {ld}).v);
-        U.dw = push(d->raw.need(p + ".1.dwconv.conv.weight", {ld, 7, 1}).v); U.dwb = push(d->raw.need(p + ".1.dwconv.conv.bias", {ld}).v);
-        U.lnw = push(d->raw.need(p + ".1.norm.weight", {ld}).v); U.lnb = push(d->raw.need(p + ".1.norm.bias", {ld}).v);
+        U.ct = convT(p + ".0.conv", ld, f, ld, f);
+        U.dw = arena.push(d->raw.need(p + ".1.dwconv.conv.weight", {ld, 7, 1}).v); U.dwb = arena.push(d->raw.need(p + ".1.dwconv.conv.bias", {ld}).v);
+        U.lnw = arena.push(d->raw.need(p + ".1.norm.weight", {ld}).v); U.lnb = arena.push(d->raw.need(p + ".1.norm.bias", {ld}).v);
         U.p1 = lin(p + ".1.pwconv1", 4 * ld, ld, true);
         U.p2 = lin(p + ".1.pwconv2", ld, 4 * ld, true);
-        U.gamma = push(d->raw.need(p + ".1.gamma", {ld}).v);
+        U.gamma = arena.push(d->raw.need(p + ".1.gamma", {ld}).v);
         d->ups.push_back(U);
     }
     d->dec0 = conv("decoder.decoder.0.conv", dd, 7, ld);
@@ -444,9 +349,7 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         mis_q3dec::Blk B{};
         B.s = (int)s; B.cin = (int)cin; B.cout = (int)cout;
         snake_pair(p + ".0.alpha", p + ".0.beta", cin, B.a, B.ra);
-        B.ct.M = (int)cout; B.ct.K = (int)(2 * cin);
-        B.ct.w = push(convT_t(d->raw.need(p + ".1.conv.weight", {cout, 2 * s, cin}).v, cout, 2 * s, cin, s));
-        B.ct.b = push(d->raw.need(p + ".1.conv.bias", {cout}).v);
+        B.ct = convT(p + ".1.conv", cout, 2 * s, cin, s);
         const int dils[3] = {1, 3, 9};
         for (int ri = 0; ri < 3; ++ri) {
             const std::string q = p + "." + std::to_string(ri + 2);
@@ -464,11 +367,10 @@ mis_status mis_q3dec_finalize(mis_q3dec* d) {
         d->fin_c = (int)cl;
         snake_pair("decoder.decoder." + std::to_string(n + 1) + ".alpha", "decoder.decoder." + std::to_string(n + 1) + ".beta", cl, d->fin_a, d->fin_ra);
         const auto& w = d->raw.need("decoder.decoder." + std::to_string(n + 2) + ".conv.weight", {1, 7, cl}).v;     // [1][k][C] == [k][C]
-        d->fin_w = push(w);
+        d->fin_w = arena.push(w);
         d->fin_b = d->raw.need("decoder.decoder." + std::to_string(n + 2) + ".conv.bias", {1}).v[0];
     }
-    d->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(d->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    arena.upload(d->arena);
     d->raw.clear();
     d->finalized = true;
     MIS_API_END
@@ -515,7 +417,7 @@ static const float* q3dec_run(mis_q3dec* d, const int32_t* codes_dev, int64_t cs
     auto gemm = [&](const mis_q3dec::Lin& L, const float* X, float* Y, int N, int Tin, int Tout, const float* R = nullptr,
                     const float* scale = nullptr, const float* al = nullptr, const float* ral = nullptr) {
         GemmParams g{};
-        g.AT = W + L.w; g.bias = L.b == (size_t)-1 ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale; g.alpha = al; g.ralpha = ral;
+        g.AT = W + L.w; g.bias = L.b == F32Lin::npos ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale; g.alpha = al; g.ralpha = ral;
         g.M = L.M; g.K = L.K; g.N = N; g.Tin = Tin; g.Tout = Tout;
         g.ldx = LD(Tin); g.ldy = LD(Tout); g.x_lo = -HP;
         return g;
@@ -525,15 +427,14 @@ static const float* q3dec_run(mis_q3dec* d, const int32_t* codes_dev, int64_t cs
     auto hist = [&](float* x, int C, int Tn, int Hc) {
         if (!st) return;
         MIS_REQUIRE(Hc <= Q3_HP && hist_cur + (size_t)batch * C * Hc <= st->hist_n, MIS_ERR_GENERATION_FAILED, "streaming history overflow");
-        hipLaunchKernelGGL(k_q3_hist, dim3(C, batch), dim3(64), 0, s, st->hist.p + hist_cur, x, C, LD(Tn), Hc, Tn);
+        launch_codec_hist(st->hist.p + hist_cur, x, C, LD(Tn), Hc, Tn, batch, s);
         hist_cur += (size_t)batch * C * Hc;
     };
     const float* Z = W + d->zeros;
     dim3 tb(128);
     int Tc = T;
     const int pos0 = st ? st->pos : 0;
-    hipLaunchKernelGGL(k_q3_rvq, dim3(T, batch), dim3(256), 0, s, codes_dev, cs_b, cs_q, cs_t, W + d->rvq_tables, a, cf.dec_num_quantizers,
-                       cf.dec_codebook_size, Cd, LD(T));
+    launch_codec_embed(codes_dev, cs_b, cs_q, cs_t, W + d->rvq_tables, a, cf.dec_num_quantizers, cf.dec_codebook_size, Cd, LD(T), T, batch, s);
     if (stop_after == 1) { *outC = Cd; *outT = T; return a; }
     {   // pre_conv: causal k3
         hist(a, Cd, T, 2);
@@ -625,8 +526,7 @@ static const float* q3dec_run(mis_q3dec* d, const int32_t* codes_dev, int64_t cs
     }
     MIS_REQUIRE(Tc == (int64_t)T * up, MIS_ERR_GENERATION_FAILED, "internal length mismatch");
     hist(x, d->fin_c, Tc, 6);
-    hipLaunchKernelGGL(k_q3_final, dim3(cdiv(Tc, Q3F_TILE), batch), dim3(256), 0, s, x, wav_dev, wav_stride, W + d->fin_w, d->fin_b, W + d->fin_a,
-                       W + d->fin_ra, d->fin_c, Tc, LD(Tc), -HP, 7);
+    launch_codec_final(x, wav_dev, wav_stride, W + d->fin_w, d->fin_b, W + d->fin_a, W + d->fin_ra, d->fin_c, Tc, LD(Tc), -HP, 7, batch, s);
     HIP_CHECK(hipGetLastError());
     if (st) {
         MIS_REQUIRE(hist_cur == st->hist_n, MIS_ERR_GENERATION_FAILED, "streaming history bookkeeping mismatch");

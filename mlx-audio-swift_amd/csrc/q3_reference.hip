@@ -35,7 +35,11 @@ struct mis_q3ref {
     HostWeights raw{"reference front-end"};
     bool finalized = false, has_spk = false, has_enc = false;
     DevBuf<float> arena;
-    struct Lin { size_t w = 0, b = (size_t)-1; int M = 0, K = 0, taps = 1, dil = 1, cin = 0; };
+    struct Lin : F32Lin {
+        int taps = 1, dil = 1, cin = 0;
+        Lin() {}
+        Lin(const F32Lin& l, int taps_, int dil_, int cin_) : F32Lin(l), taps(taps_), dil(dil_), cin(cin_) {}
+    };
     // speaker encoder
     struct SeBlock { Lin tdnn1, tdnn2, se1, se2; std::vector<Lin> res; };
     Lin spk_first, spk_mfa, asp_tdnn, asp_conv, spk_fc;
@@ -263,27 +267,19 @@ bool q3ref_owns(const char* name) { return !strncmp(name, "speaker_encoder.", 16
 
 void q3ref_set_tensor(mis_q3ref* r, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_REQUIRE(!r->finalized && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad tensor %s", name);
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(r->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    r->raw.put(name, host.data(), dtype, shape, ndim);
+    r->raw.put_staged(r->device, name, data, dtype, shape, ndim);
 }
 
 void q3ref_finalize(mis_q3ref* r) {
     MIS_REQUIRE(!r->finalized, MIS_ERR_INVALID_INPUT, "already finalized");
     HIP_CHECK(hipSetDevice(r->device));
     const mis_qwen3tts_reference_config& cf = r->cfg;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
+    F32Arena arena;
+    auto bias_of = [&](const std::string& p, int64_t co, bool bias) { return bias ? &r->raw.need(p + ".bias", {co}).v : nullptr; };
     // conv weight [co][k][ci] (MLX layout) -> A^T [(j ci + c)][co]
     auto conv = [&](const std::string& p, int64_t co, int64_t k, int64_t ci, int dil, bool bias) {
-        const auto& w = r->raw.need(p + ".weight", {co, k, ci}).v;
-        std::vector<float> at((size_t)k * ci * co);
-        for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c) at[(j * ci + c) * co + o] = w[(o * k + j) * ci + c];
-        mis_q3ref::Lin L; L.M = (int)co; L.K = (int)(k * ci); L.taps = (int)k; L.dil = dil; L.cin = (int)ci;
-        L.w = push(at);
-        if (bias) L.b = push(r->raw.need(p + ".bias", {co}).v);
-        return L;
+        const std::vector<float> at = conv_taps_t(r->raw.need(p + ".weight", {co, k, ci}).v, co, k, ci);
+        return mis_q3ref::Lin(arena.packed(at, co, k * ci, bias_of(p, co, bias)), (int)k, dil, (int)ci);
     };
     // strided conv k = 2 s: [co][2s][ci] -> two taps over the phase-split input: A^T [(j (ci s) + c s + ph)][co] = w[co][j s + ph][c]
     auto conv_strided = [&](const std::string& p, int64_t co, int64_t s, int64_t ci, bool bias) {
@@ -291,23 +287,17 @@ void q3ref_finalize(mis_q3ref* r) {
         std::vector<float> at((size_t)2 * s * ci * co);
         for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < 2; ++j) for (int64_t ph = 0; ph < s; ++ph) for (int64_t c = 0; c < ci; ++c)
             at[((j * ci * s) + c * s + ph) * co + o] = w[(o * 2 * s + j * s + ph) * ci + c];
-        mis_q3ref::Lin L; L.M = (int)co; L.K = (int)(2 * s * ci); L.taps = 2; L.dil = 1; L.cin = (int)(ci * s);
-        L.w = push(at);
-        if (bias) L.b = push(r->raw.need(p + ".bias", {co}).v);
-        return L;
+        return mis_q3ref::Lin(arena.packed(at, co, 2 * s * ci, bias_of(p, co, bias)), 2, 1, (int)(ci * s));
     };
     auto matvec = [&](const std::string& p, int64_t co, int64_t ci) {      // 1x1 conv kept row-major [co][ci] for k_ref_matvec
-        mis_q3ref::Lin L; L.M = (int)co; L.K = (int)ci;
-        L.w = push(r->raw.need(p + ".weight", {co, 1, ci}).v);
-        L.b = push(r->raw.need(p + ".bias", {co}).v);
+        mis_q3ref::Lin L;                                                   // not an A^T: pushed as stored
+        L.M = (int)co; L.K = (int)ci;
+        L.w = arena.push(r->raw.need(p + ".weight", {co, 1, ci}).v);
+        L.b = arena.push(r->raw.need(p + ".bias", {co}).v);
         return L;
     };
     auto linear = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) {           // [out][in] -> A^T [in][out]
-        std::vector<float> at((size_t)in_f * out_f);
-        for (int64_t o = 0; o < out_f; ++o) for (int64_t i = 0; i < in_f; ++i) at[i * out_f + o] = w[o * in_f + i];
-        mis_q3ref::Lin L; L.M = (int)out_f; L.K = (int)in_f; L.cin = (int)in_f;
-        L.w = push(at);
-        return L;
+        return mis_q3ref::Lin(arena.packed(lin_t(w, out_f, in_f), out_f, in_f, nullptr), 1, 1, (int)in_f);
     };
     if (r->has_spk) {
         const std::string P = "speaker_encoder.";
@@ -373,9 +363,9 @@ void q3ref_finalize(mis_q3ref* r) {
         for (int li = 0; li < cf.enc_num_layers; ++li) {
             const std::string p = P + "encoder_transformer.transformer.layers." + std::to_string(li);
             mis_q3ref::TL L{};
-            L.n1w = push(r->raw.need(p + ".norm1.weight", {D}).v); L.n1b = push(r->raw.need(p + ".norm1.bias", {D}).v);
-            L.n2w = push(r->raw.need(p + ".norm2.weight", {D}).v); L.n2b = push(r->raw.need(p + ".norm2.bias", {D}).v);
-            L.ls1 = push(r->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = push(r->raw.need(p + ".layer_scale_2.scale", {D}).v);
+            L.n1w = arena.push(r->raw.need(p + ".norm1.weight", {D}).v); L.n1b = arena.push(r->raw.need(p + ".norm1.bias", {D}).v);
+            L.n2w = arena.push(r->raw.need(p + ".norm2.weight", {D}).v); L.n2b = arena.push(r->raw.need(p + ".norm2.bias", {D}).v);
+            L.ls1 = arena.push(r->raw.need(p + ".layer_scale_1.scale", {D}).v); L.ls2 = arena.push(r->raw.need(p + ".layer_scale_2.scale", {D}).v);
             {   // q / k rows of every head reordered evens-then-odds: interleaved RoPE pairs (2i, 2i+1) become rotate-half pairs (i, i + hd/2)
                 const auto& w = r->raw.need(p + ".self_attn.in_proj.weight", {3 * D, D}).v;
                 std::vector<float> pw(w.size());
@@ -421,11 +411,11 @@ void q3ref_finalize(mis_q3ref* r) {
                     e2[(size_t)q * bins + v] = n2 / 2.0f;
                 }
             }
-            V.embT = push(eT); V.emb = push(em); V.e2h = push(e2);
+            V.embT = arena.push(eT); V.emb = arena.push(em); V.e2h = arena.push(e2);
         }
     }
-    r->arena.alloc(std::max<size_t>(arena.size(), 4));
-    HIP_CHECK(hipMemcpy(r->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    if (arena.host.empty()) arena.zeros(4);
+    arena.upload(r->arena);
     r->raw.clear();
     r->finalized = true;
 }
@@ -435,7 +425,7 @@ static void ref_conv(const mis_q3ref* r, const mis_q3ref::Lin& L, int mode, cons
                      const float* R = nullptr, const float* scale = nullptr) {
     const float* W = r->arena.p;
     GemmParams g{};
-    g.AT = W + L.w; g.bias = L.b == (size_t)-1 ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale;
+    g.AT = W + L.w; g.bias = L.b == F32Lin::npos ? nullptr : W + L.b; g.X = X; g.Y = Y; g.R = R; g.scale = scale;
     g.M = L.M; g.K = L.K; g.N = N; g.Tin = Tin; g.Tout = N; g.ldx = ldx; g.ldy = ldy;
     g.Cin = L.cin; g.taps = L.taps; g.dil = L.dil; g.pad = pad;
     launch_gemm(mode, false, g, 1, r->s);

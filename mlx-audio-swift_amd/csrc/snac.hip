@@ -708,7 +708,7 @@ __global__ void __launch_bounds__(256) k_snac_final(const float* __restrict__ X,
 
 // ============================================================================ host side
 
-struct ConvW { size_t w = 0, b = 0; bool has_bias = false; };        // offsets into the weight arena (floats)
+typedef F32Lin ConvW;                                                // offsets into the weight arena (floats)
 struct SnakeW { size_t a = 0, ra = 0; };
 
 struct mis_snac {
@@ -814,14 +814,11 @@ extern "C" mis_status mis_snac_create(const mis_snac_config* cfg, int device, mi
         MIS_REQUIRE(cfg->decoder_rates[i] >= 1 && cfg->decoder_rates[i] <= 64, MIS_ERR_INVALID_INPUT, "bad decoder rate");
     MIS_REQUIRE(cfg->latent_dim > 0 && cfg->decoder_dim > 0 && cfg->codebook_size > 0 && cfg->codebook_dim > 0,
                 MIS_ERR_INVALID_INPUT, "bad dimensions");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_snac* c = new mis_snac();
     c->device = device;
     c->cfg = *cfg;
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    c->stream = stream;
     *out = c;
     MIS_API_END
 }
@@ -855,34 +852,27 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
     HIP_CHECK(hipSetDevice(c->device));
     const mis_snac_config& cf = c->cfg;
     const int64_t D = cf.latent_dim, CB = cf.codebook_size, CD = cf.codebook_dim;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
+    F32Arena arena;
     auto push_snake = [&](const std::string& name, int64_t C) {
         const HostTensor& a = need(c, name, {1, C, 1});
         std::vector<float> ra(C);
         for (int64_t i = 0; i < C; ++i) ra[i] = 1.0f / (a.v[i] + 1e-9f);
         SnakeW s;
-        s.a = push(a.v);
-        s.ra = push(ra);
+        s.a = arena.push(a.v);
+        s.ra = arena.push(ra);
         return s;
     };
+    auto bias_of = [&](const std::string& p, int64_t co) { return &need(c, p + ".bias", {co}).v; };
     // 1x1 conv -> A^T [K=cin][M=cout]
     auto push_pw = [&](const std::string& p, int64_t cout, int64_t cin, bool bias) {
         std::vector<float> w = fold_weight_norm(need(c, p + ".weight_g", {cout, 1, 1}), need(c, p + ".weight_v", {cout, 1, cin}), 1e-12f);
-        std::vector<float> at((size_t)cin * cout);
-        for (int64_t o = 0; o < cout; ++o) for (int64_t i = 0; i < cin; ++i) at[i * cout + o] = w[o * cin + i];
-        ConvW cw;
-        cw.w = push(at);
-        cw.has_bias = bias;
-        if (bias) cw.b = push(need(c, p + ".bias", {cout}).v);
-        return cw;
+        return arena.packed(lin_t(w, cout, cin), cout, cin, bias ? bias_of(p, cout) : nullptr);
     };
-    auto push_dw = [&](const std::string& p, int64_t C) {
+    auto push_dw = [&](const std::string& p, int64_t C) {                 // [C][7]
         std::vector<float> w = fold_weight_norm(need(c, p + ".weight_g", {C, 1, 1}), need(c, p + ".weight_v", {C, 7, 1}), 1e-12f);
-        ConvW cw;
-        cw.w = push(w);          // [C][7]
-        cw.has_bias = true;
-        cw.b = push(need(c, p + ".bias", {C}).v);
+        ConvW cw;                                                         // depthwise: no contraction, M / K stay unset
+        cw.w = arena.push(w);
+        cw.b = arena.push(*bias_of(p, C));
         return cw;
     };
 
@@ -894,34 +884,24 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
             const HostTensor& cb = need(c, p + ".codebook.weight", {CB, CD});
             std::vector<float> w = fold_weight_norm(need(c, p + ".out_proj.weight_g", {D, 1, 1}), need(c, p + ".out_proj.weight_v", {D, 1, CD}), 1e-12f);
             const HostTensor& bias = need(c, p + ".out_proj.bias", {D});
-            for (int64_t code = 0; code < CB; ++code)
-                for (int64_t ch = 0; ch < D; ++ch) {
-                    float acc = 0.0f;
-                    for (int64_t d = 0; d < CD; ++d) acc += w[ch * CD + d] * cb.v[code * CD + d];
-                    tables[((size_t)i * CB + code) * D + ch] = acc + bias.v[ch];
-                }
+            fold_tables_into(&tables[(size_t)i * CB * D], w.data(), cb.v.data(), bias.v.data(), D, CD, CB);
         }
-        c->tables_off = push(tables);
+        c->tables_off = arena.push(tables);
     }
     // LocalMHA parameters: norm.{weight,bias} [dim], to_qkv.weight [3 dim][dim], to_out.weight [dim][dim] (Linear, no bias), rel_pos.inv_freq [32]
     auto push_mha = [&](const std::string& p, int64_t dim) {
         mis_snac::MhaW m;
         MIS_REQUIRE(dim % MHA_D == 0, MIS_ERR_INVALID_INPUT, "LocalMHA width %lld is not a multiple of the head size 64", (long long)dim);
         m.on = true; m.dim = (int)dim;
-        m.ln_w = push(need(c, p + ".norm.weight", {dim}).v);
-        m.ln_b = push(need(c, p + ".norm.bias", {dim}).v);
-        auto lin_t = [&](const HostTensor& w, int64_t out_f, int64_t in_f) {            // Linear weight [out][in] -> A^T [in][out]
-            std::vector<float> at((size_t)in_f * out_f);
-            for (int64_t o = 0; o < out_f; ++o) for (int64_t i = 0; i < in_f; ++i) at[i * out_f + o] = w.v[o * in_f + i];
-            return at;
-        };
-        m.qkv = push(lin_t(need(c, p + ".to_qkv.weight", {3 * dim, dim}), 3 * dim, dim));
-        m.out = push(lin_t(need(c, p + ".to_out.weight", {dim, dim}), dim, dim));
+        m.ln_w = arena.push(need(c, p + ".norm.weight", {dim}).v);
+        m.ln_b = arena.push(need(c, p + ".norm.bias", {dim}).v);
+        m.qkv = arena.push(lin_t(need(c, p + ".to_qkv.weight", {3 * dim, dim}).v, 3 * dim, dim));
+        m.out = arena.push(lin_t(need(c, p + ".to_out.weight", {dim, dim}).v, dim, dim));
         const HostTensor* fq = c->raw.find(p + ".rel_pos.inv_freq");
         std::vector<float> inv(32);
         if (fq && fq->v.size() == 32) inv = fq->v;
         else for (int j = 0; j < 32; ++j) inv[j] = 1.0f / powf(10000.0f, (float)(2 * j) / 64.0f);      // SinusoidalEmbeddings.init (:105-107)
-        m.inv_freq = push(inv);
+        m.inv_freq = arena.push(inv);
         return m;
     };
     const std::string L = "decoder.model.layers";
@@ -943,17 +923,7 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
         {   // transposed conv, weight_v [in, 2s, out]; per phase p: AT[p][j*Cin+ci][co] = w[ci][((p+pad)%s) + j*s][co]
             int s = blk.stride, K = 2 * s;
             std::vector<float> w = fold_weight_norm(need(c, b + ".1.weight_g", {blk.cin, 1, 1}), need(c, b + ".1.weight_v", {blk.cin, K, blk.cout}), 0.0f);
-            std::vector<float> at((size_t)s * 2 * blk.cin * blk.cout);
-            for (int p = 0; p < s; ++p)
-                for (int j = 0; j < 2; ++j) {
-                    int k = ((p + blk.pad) % s) + j * s;
-                    for (int ci = 0; ci < blk.cin; ++ci)
-                        for (int co = 0; co < blk.cout; ++co)
-                            at[(((size_t)p * 2 + j) * blk.cin + ci) * blk.cout + co] = w[((size_t)ci * K + k) * blk.cout + co];
-                }
-            blk.convT.w = push(at);
-            blk.convT.has_bias = true;
-            blk.convT.b = push(need(c, b + ".1.bias", {blk.cout}).v);
+            blk.convT = arena.packed(convt_phases_t(w, blk.cout, K, blk.cin, s, blk.pad, true), blk.cout, 2 * blk.cin, bias_of(b + ".1", blk.cout));
         }
         int idx = 2;
         if (cf.noise) { blk.noise = push_pw(b + ".2.linear", blk.cout, blk.cout, false); idx = 3; }
@@ -974,7 +944,7 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
         std::vector<float> w = fold_weight_norm(need(c, p + ".weight_g", {1, 1, 1}), need(c, p + ".weight_v", {1, 7, cl}), 1e-12f);
         std::vector<float> wt((size_t)cl * 7);       // [C][7]
         for (int64_t k = 0; k < 7; ++k) for (int64_t ci = 0; ci < cl; ++ci) wt[ci * 7 + k] = w[k * cl + ci];
-        c->fin.w = push(wt);
+        c->fin.w = arena.push(wt);
         c->fin_bias = need(c, p + ".bias", {1}).v[0];
     }
     // ---- encoder (optional): dimensions are read off the tensors (encoder_dim / encoder_rates are not part of mis_snac_config)
@@ -988,7 +958,7 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
         c->enc_dim = (int)ch;
         {
             std::vector<float> w = fold_weight_norm(need(c, E + ".0.weight_g", {ch, 1, 1}), need(c, E + ".0.weight_v", {ch, 7, 1}), 1e-12f);
-            c->enc_first.w = push(w); c->enc_first.has_bias = true; c->enc_first.b = push(need(c, E + ".0.bias", {ch}).v);
+            c->enc_first.w = arena.push(w); c->enc_first.b = arena.push(*bias_of(E + ".0", ch));
         }
         c->enc_blocks.clear();
         int li = 1;
@@ -1022,7 +992,7 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
                             for (int co = 0; co < eb.cout; ++co)
                                 at[(((size_t)qi * ch * sdn) + (size_t)ci * sdn + r) * eb.cout + co] = w[((size_t)co * K + j) * ch + ci];
                         }
-                eb.down.w = push(at); eb.down.has_bias = true; eb.down.b = push(need(c, b + ".4.bias", {eb.cout}).v);
+                eb.down = arena.packed(at, eb.cout, 3 * sdn * ch, bias_of(b + ".4", eb.cout));
             }
             ch = eb.cout;
             c->enc_blocks.push_back(eb);
@@ -1046,13 +1016,12 @@ extern "C" mis_status mis_snac_finalize(mis_snac* c) {
                 for (int64_t d = 0; d < CD; ++d) { float x = cb.v[k * CD + d] * inv; cn[k * CD + d] = x; s2 += x * x; }
                 cn2[k] = s2;
             }
-            v.cn = push(cn); v.cn2 = push(cn2);
+            v.cn = arena.push(cn); v.cn2 = arena.push(cn2);
             c->vq_enc.push_back(v);
         }
         c->has_encoder = true;
     }
-    c->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * sizeof(float), hipMemcpyHostToDevice));
+    arena.upload(c->arena);
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

@@ -233,10 +233,7 @@ extern "C" mis_status mis_soprano_set_tensor(mis_soprano* c, const char* name_, 
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     std::string name = sop_sanitize(name_);
     if (name.rfind("decoder.", 0) != 0) return mis_tts_set_tensor(c->lm, name.c_str(), data, dtype, shape, ndim);
-    std::vector<uint8_t> host(HostWeights::count(shape, ndim) * (dtype == MIS_F32 ? 4 : 2));
-    HIP_CHECK(hipSetDevice(c->device));
-    HIP_CHECK(hipMemcpy(host.data(), data, host.size(), hipMemcpyDefault));      // the caller's pointer may be a device one
-    c->raw.put(name, host.data(), dtype, shape, ndim);
+    c->raw.put_staged(c->device, name, data, dtype, shape, ndim);
     MIS_API_END
 }
 
@@ -294,20 +291,14 @@ extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
     const mis_soprano_config& cf = c->cfg;
     const int64_t C = cf.lm.hidden_size, d = cf.decoder_dim, inter = cf.decoder_intermediate_dim, nf = cf.n_fft, bins = nf / 2 + 1;
     const int64_t ik = cf.input_kernel, dk = cf.dw_kernel;
-    std::vector<float> arena;
-    auto push = [&](const std::vector<float>& v) { size_t o = arena.size(); arena.insert(arena.end(), v.begin(), v.end()); while (arena.size() & 3) arena.push_back(0.f); return o; };
-    auto transpose = [&](const std::vector<float>& w, int64_t out_f, int64_t in_f) {       // [out][in] -> A^T [in][out]
-        std::vector<float> at((size_t)in_f * out_f);
-        for (int64_t o = 0; o < out_f; ++o) for (int64_t i = 0; i < in_f; ++i) at[i * out_f + o] = w[o * in_f + i];
-        return at;
-    };
+    F32Arena arena;
     const std::string P = "decoder.decoder";
     {   // embed conv: weight [d][ik][C] (MLX Conv1d) == [d][ik*C] row-major with column kk*C + c
         const auto& w = c->raw.need(P + ".embed.weight", {d, ik, C}).v;
-        c->embed_w = push(transpose(w, d, ik * C));
-        c->embed_b = push(c->raw.need(P + ".embed.bias", {d}).v);
+        c->embed_w = arena.push(lin_t(w, d, ik * C));
+        c->embed_b = arena.push(c->raw.need(P + ".embed.bias", {d}).v);
     }
-    c->norm_w = push(c->raw.need(P + ".norm.weight", {d}).v); c->norm_b = push(c->raw.need(P + ".norm.bias", {d}).v);
+    c->norm_w = arena.push(c->raw.need(P + ".norm.weight", {d}).v); c->norm_b = arena.push(c->raw.need(P + ".norm.bias", {d}).v);
     c->blocks.clear();
     for (int i = 0; i < cf.decoder_num_layers; ++i) {
         std::string q = P + ".convnext." + std::to_string(i);
@@ -315,16 +306,16 @@ extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
         const auto& dw = c->raw.need(q + ".dwconv.weight", {d, dk, 1}).v;
         std::vector<float> w7((size_t)d * 7, 0.0f);                    // centre the dk taps in a 7-tap kernel
         for (int64_t ch = 0; ch < d; ++ch) for (int64_t j = 0; j < dk; ++j) w7[ch * 7 + (3 - dk / 2) + j] = dw[ch * dk + j];
-        b.dw = push(w7); b.dwb = push(c->raw.need(q + ".dwconv.bias", {d}).v);
-        b.lnw = push(c->raw.need(q + ".norm.weight", {d}).v); b.lnb = push(c->raw.need(q + ".norm.bias", {d}).v);
-        b.p1 = push(transpose(c->raw.need(q + ".pwconv1.weight", {inter, d}).v, inter, d)); b.b1 = push(c->raw.need(q + ".pwconv1.bias", {inter}).v);
-        b.p2 = push(transpose(c->raw.need(q + ".pwconv2.weight", {d, inter}).v, d, inter)); b.b2 = push(c->raw.need(q + ".pwconv2.bias", {d}).v);
-        b.gamma = push(c->raw.need(q + ".gamma", {d}).v);
+        b.dw = arena.push(w7); b.dwb = arena.push(c->raw.need(q + ".dwconv.bias", {d}).v);
+        b.lnw = arena.push(c->raw.need(q + ".norm.weight", {d}).v); b.lnb = arena.push(c->raw.need(q + ".norm.bias", {d}).v);
+        b.p1 = arena.push(lin_t(c->raw.need(q + ".pwconv1.weight", {inter, d}).v, inter, d)); b.b1 = arena.push(c->raw.need(q + ".pwconv1.bias", {inter}).v);
+        b.p2 = arena.push(lin_t(c->raw.need(q + ".pwconv2.weight", {d, inter}).v, d, inter)); b.b2 = arena.push(c->raw.need(q + ".pwconv2.bias", {d}).v);
+        b.gamma = arena.push(c->raw.need(q + ".gamma", {d}).v);
         c->blocks.push_back(b);
     }
-    c->fin_w = push(c->raw.need(P + ".final_layer_norm.weight", {d}).v); c->fin_b = push(c->raw.need(P + ".final_layer_norm.bias", {d}).v);
-    c->head_w = push(transpose(c->raw.need("decoder.head.out.weight", {nf + 2, d}).v, nf + 2, d));
-    c->head_b = push(c->raw.need("decoder.head.out.bias", {nf + 2}).v);
+    c->fin_w = arena.push(c->raw.need(P + ".final_layer_norm.weight", {d}).v); c->fin_b = arena.push(c->raw.need(P + ".final_layer_norm.bias", {d}).v);
+    c->head_w = arena.push(lin_t(c->raw.need("decoder.head.out.weight", {nf + 2, d}).v, nf + 2, d));
+    c->head_b = arena.push(c->raw.need("decoder.head.out.bias", {nf + 2}).v);
     {   // irfft as a contraction: frames[n] = (1/N) sum_k c_k (Re_k cos(2 pi k n / N) - Im_k sin(2 pi k n / N)),
         // c_0 = c_{N/2} = 1, else 2; imaginary parts of DC / Nyquist are ignored (MLXFFT.irfft semantics)
         std::vector<float> at((size_t)2 * bins * nf);
@@ -336,15 +327,14 @@ extern "C" mis_status mis_soprano_finalize(mis_soprano* c) {
                 at[(size_t)(bins + k) * nf + n] = (k == 0 || k == nf / 2) ? 0.0f : (float)(-ck * sin(ang) / (double)nf);
             }
         }
-        c->idft = push(at);
+        c->idft = arena.push(at);
         std::vector<float> win(nf);
         float factor = (float)M_PI / (float)(nf - 1);                   // hanningWindow, SopranoDecoder.swift:209-217
         for (int64_t n = 0; n < nf; ++n) win[n] = 0.5f - 0.5f * cosf(2.0f * factor * (float)n);
         if (nf == 1) win[0] = 1.0f;
-        c->window = push(win);
+        c->window = arena.push(win);
     }
-    c->arena.alloc(arena.size());
-    HIP_CHECK(hipMemcpy(c->arena.p, arena.data(), arena.size() * 4, hipMemcpyHostToDevice));
+    arena.upload(c->arena);
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

@@ -1,5 +1,5 @@
 // Stand-alone check of csrc/host_weights.h (test_host_weights_cpu.py builds it with the address and undefined-behaviour sanitizers and
-// runs it).  Host code only: no HIP call is made, no device is opened.
+// runs it): the weight stash, the bf16 / f32 arena, the exact-f32 codec arena and its re-layouts, the synthetic tensors.  Host code only: no HIP call is made, no device is opened.
 #include "../mlx-audio-swift_amd/csrc/host_weights.h"
 
 #include <math.h>
@@ -134,6 +134,104 @@ int main() {
         CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "DAC weight v has the wrong shape" && a.host.size() == 384);
         m = thrown([&] { a.fvec("nope", {1}, 1); }, &code);
         CHECK(code == (int)MIS_ERR_NOT_INITIALIZED && m == "DAC weight missing: nope");
+    }
+    {   // F32Arena::push: offsets count floats, zero padding to a multiple of 4 after every push
+        F32Arena a;
+        const size_t len[5] = {1, 4, 5, 0, 7}, want[5] = {0, 4, 8, 16, 16};
+        for (int i = 0; i < 5; ++i) CHECK(a.push(std::vector<float>(len[i], -1.5f)) == want[i]);
+        CHECK(a.host.size() == 24);
+        const bool data[24] = {1, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 0};
+        for (int i = 0; i < 24; ++i) CHECK(bits(a.host[i]) == (data[i] ? bits(-1.5f) : 0u));
+        CHECK(a.zeros(6) == 24 && a.host.size() == 32);
+        for (int i = 24; i < 32; ++i) CHECK(bits(a.host[i]) == 0u);
+    }
+    {   // re-layouts against the index formulas of the engines, written out; distinct integers, no two equal dimensions
+        auto iota = [](size_t n) { std::vector<float> v(n); for (size_t i = 0; i < n; ++i) v[i] = (float)(i + 1); return v; };
+        {
+            const int64_t out = 3, in = 5;
+            const std::vector<float> w = iota(out * in), at = lin_t(w, out, in);
+            CHECK(at.size() == (size_t)(out * in));
+            for (int64_t o = 0; o < out; ++o) for (int64_t i = 0; i < in; ++i) CHECK(at[i * out + o] == w[o * in + i]);
+        }
+        for (int64_t k : {4, 1}) {
+            const int64_t co = 3, ci = 5;
+            const std::vector<float> w = iota(co * k * ci), at = conv_taps_t(w, co, k, ci);
+            CHECK(at.size() == (size_t)(co * k * ci));
+            for (int64_t o = 0; o < co; ++o) for (int64_t j = 0; j < k; ++j) for (int64_t c = 0; c < ci; ++c)
+                CHECK(at[(j * ci + c) * co + o] == w[(o * k + j) * ci + c]);
+        }
+        struct { int64_t k, s, pad; } cases[] = {{4, 2, 0}, {4, 2, 1}, {6, 2, 0}, {6, 2, 1}, {2, 2, 0}, {6, 3, 2}};
+        for (auto cs : cases)
+            for (bool in_major : {false, true}) {
+                const int64_t co = 3, ci = 5, k = cs.k, s = cs.s, pad = cs.pad, nt = k / s;
+                const std::vector<float> w = iota(co * k * ci), at = convt_phases_t(w, co, k, ci, s, pad, in_major);
+                CHECK(at.size() == (size_t)(s * nt * ci * co));
+                for (int64_t ph = 0; ph < s; ++ph) for (int64_t j = 0; j < nt; ++j) for (int64_t c = 0; c < ci; ++c) for (int64_t o = 0; o < co; ++o) {
+                    const int64_t tap = ((ph + pad) % s) + s * j;
+                    CHECK(at[((ph * nt + j) * ci + c) * co + o] == (in_major ? w[(c * k + tap) * co + o] : w[(o * k + tap) * ci + c]));
+                }
+            }
+    }
+    {   // fold_tables_into: f32 accumulator, d ascending, bias after the sum; the codebook is used as given
+        const int64_t C = 3, cd = 7, bins = 5;
+        std::vector<float> proj(C * cd), cb(bins * cd), bias(C);
+        for (size_t i = 0; i < proj.size(); ++i) proj[i] = mis_synth_value(11, i, 1.0f);
+        for (size_t i = 0; i < cb.size(); ++i) cb[i] = mis_synth_value(12, i, 3.0f) / 3.0f;       // pre-scaled by the caller, in its own arithmetic
+        for (size_t i = 0; i < bias.size(); ++i) bias[i] = mis_synth_value(13, i, 0.1f);
+        const std::vector<float> cb0 = cb;
+        bool inexact = false;
+        for (const float* b : {(const float*)nullptr, (const float*)bias.data()}) {
+            std::vector<float> got(bins * C + 1, 7.0f);
+            fold_tables_into(got.data(), proj.data(), cb.data(), b, C, cd, bins);
+            for (int64_t v = 0; v < bins; ++v) for (int64_t c = 0; c < C; ++c) {
+                float acc = 0.0f;
+                double exact = 0.0;
+                for (int64_t d = 0; d < cd; ++d) { acc += proj[c * cd + d] * cb[v * cd + d]; exact += (double)proj[c * cd + d] * (double)cb[v * cd + d]; }
+                inexact = inexact || (double)acc != exact;
+                CHECK(bits(got[v * C + c]) == bits(b ? acc + b[c] : acc));
+            }
+            CHECK(got[bins * C] == 7.0f);
+        }
+        CHECK(inexact && cb == cb0);
+    }
+    {   // arena.lin / arena.conv read prefix.weight / prefix.bias through need(): its shape message, npos without a bias
+        HostWeights s("Mimi");
+        const float wv[12] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12}, bv[2] = {0.5f, -0.5f};
+        const int64_t s26[2] = {2, 6}, s223[3] = {2, 2, 3}, s2[1] = {2};
+        s.put("l.weight", wv, MIS_F32, s26, 2);
+        s.put("l.bias", bv, MIS_F32, s2, 1);
+        s.put("c.weight", wv, MIS_F32, s223, 3);
+        s.put("c.bias", bv, MIS_F32, s2, 1);
+        s.put("n.weight", wv, MIS_F32, s26, 2);
+        F32Arena a;
+        const F32Lin L = a.lin(s, "l", 2, 6, true);
+        CHECK(L.w == 0 && L.b == 12 && L.M == 2 && L.K == 6 && a.host.size() == 16);
+        for (int o = 0; o < 2; ++o) for (int i = 0; i < 6; ++i) CHECK(a.host[L.w + i * 2 + o] == wv[o * 6 + i]);
+        CHECK(a.host[L.b] == 0.5f && a.host[L.b + 1] == -0.5f);
+        const F32Lin N = a.lin(s, "n", 2, 6, false);
+        CHECK(N.w == 16 && N.b == F32Lin::npos && N.b == (size_t)-1 && a.host.size() == 28);
+        const F32Lin Cv = a.conv(s, "c", 2, 2, 3);
+        CHECK(Cv.w == 28 && Cv.b == 40 && Cv.M == 2 && Cv.K == 6 && a.host.size() == 44);
+        for (int o = 0; o < 2; ++o) for (int j = 0; j < 2; ++j) for (int c2 = 0; c2 < 3; ++c2) CHECK(a.host[Cv.w + (j * 3 + c2) * 2 + o] == wv[(o * 2 + j) * 3 + c2]);
+        CHECK(F32Lin().b == F32Lin::npos);
+        m = thrown([&] { a.lin(s, "l", 6, 2, true); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "Mimi weight l.weight has the wrong shape");
+        m = thrown([&] { a.conv(s, "c", 2, 3, 2); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "Mimi weight c.weight has the wrong shape");
+        // a bias of the input's length, not the output's, is refused by lin and by conv themselves
+        const float b6[6] = {1, 2, 3, 4, 5, 6}, b3[3] = {1, 2, 3};
+        const int64_t s6[1] = {6}, s3[1] = {3};
+        s.put("lb.weight", wv, MIS_F32, s26, 2);
+        s.put("lb.bias", b6, MIS_F32, s6, 1);
+        s.put("cb.weight", wv, MIS_F32, s223, 3);
+        s.put("cb.bias", b3, MIS_F32, s3, 1);
+        m = thrown([&] { a.lin(s, "lb", 2, 6, true); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "Mimi weight lb.bias has the wrong shape");
+        m = thrown([&] { a.conv(s, "cb", 2, 2, 3); }, &code);
+        CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "Mimi weight cb.bias has the wrong shape");
+        CHECK(a.lin(s, "lb", 2, 6, false).b == F32Lin::npos);
+        m = thrown([&] { a.lin(s, "n", 2, 6, true); }, &code);
+        CHECK(code == (int)MIS_ERR_NOT_INITIALIZED && m == "Mimi weight missing: n.bias");
     }
     {   // synthetic tensors: put k takes key seed + k
         HostWeights s("Moonshine");

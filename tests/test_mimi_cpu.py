@@ -188,13 +188,17 @@ def test_package_synthetic_weights_are_the_oracle_weights():
 def usage():
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not installed")
+    # mimi.hip's own kernels and the ones it shares with the Qwen3-TTS decoder (codec_stream.hip: gather-sum, carry, final conv)
+    stderr = ""
     with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
-                            os.path.join(ROOT, "mlx-audio-swift_amd", "csrc", "mimi.hip"), "-o", os.path.join(td, "k.s"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
+        for src in ("mimi.hip", "codec_stream.hip"):
+            r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
+                                os.path.join(ROOT, "mlx-audio-swift_amd", "csrc", src), "-o", os.path.join(td, "k.s"),
+                                "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-2000:]
+            stderr += r.stderr
     use, cur = {}, None
-    for line in r.stderr.splitlines():
+    for line in stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = use.setdefault(m.group(1), {})
@@ -207,12 +211,13 @@ def usage():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m:
             cur["scratch"] = int(m.group(1))
-    return {k: v for k, v in use.items() if "k_mimi_" in k}
+    return {k: v for k, v in use.items() if "k_mimi_" in k or "k_codec_" in k}
 
 
 def test_mimi_kernels_do_not_spill(usage):
-    want = {"k_mimi_rvq", "k_mimi_upsample", "k_mimi_elu", "k_mimi_hist", "k_mimi_kv_ring", "k_mimi_final"}
-    assert {re.search(r"k_mimi_[a-z_]+?(?=P)", k).group(0) for k in usage} == want, sorted(usage)
+    want = {"k_codec_embed", "k_mimi_upsample", "k_mimi_elu", "k_codec_hist", "k_mimi_kv_ring", "k_codec_final"}
+    assert {re.search(r"k_(mimi|codec)_[a-z_]+?(?=P|I)", k).group(0) for k in usage} == want, sorted(usage)
+    assert sum("k_codec_final" in k for k in usage) == 2, sorted(usage)          # the ELU and the SnakeBeta instantiation
     for k, v in usage.items():
         assert v["scratch"] == 0, (k, v)
         assert v["vgprs"] <= 64, (k, v)
