@@ -97,6 +97,54 @@ typedef struct mis_debug_attn_args {
 } mis_debug_attn_args;
 mis_status mis_debug_attn_decode(int device, const mis_debug_attn_args* args);
 
+/* csrc/codec_debug.hip, tests (tests/test_gpu_codec_ops.py): ONE call of a codec launcher (csrc/codec_kernels.h) on caller-supplied host
+ * data; nothing is computed in the entry points.  Guards as for the GEMM and attention entry points above: every output lies between
+ * guard bands and is pre-filled with the byte 0xFF (a float NaN; code -1): an element never written comes back as that, a changed guard
+ * byte - or a changed padding column of a strided output - fails the call with MIS_ERR_GENERATION_FAILED.  Every input is followed (the
+ * activations: also preceded) by NaN, and the padding columns of a strided input are NaN, so an over-read shows in the result; codes are
+ * followed by 0xFF bytes.  The entry points refuse (MIS_ERR_INVALID_INPUT) what would make a KERNEL read or write out of bounds; what a
+ * launcher checks itself is left to it: its status is returned and nothing is launched.
+ *
+ * codec_gemm: launch_gemm(mode, snake, GemmParams, batch).  The fields carry the names and meanings of GemmParams; ldx / ldy 0 = dense.
+ *   mode 0 PLAIN, 1 RESID, 2 NOISE, 3 CONVT, 4 GELU, 5 TAPS.  use_pack 0: pack = NULL and no CodecPackScope (the exact-f32 kernels);
+ *   1: a fresh CodecPack owned by the call (the split-bf16 path where the launcher's shape rule and the MIS_BF3_* / MIS_CODEC_EXACT_F32
+ *   environment, read per launch, allow it).
+ *   X  [batch][Kx][hist + Tin] dense, hist = max(-x_lo, 0) history columns in front of column 0 (Kx = K; CONVT / TAPS: Cin); uploaded with
+ *      row stride ldx (>= hist + Tin), column 0 of every row 16-byte aligned when ldx is a multiple of 4, all other columns NaN.
+ *   R  [batch][M][Tout] dense or NULL, uploaded with row stride ldy (padding NaN).  noise [batch][N] or NULL; row_ids [batch] or NULL.
+ *   AT [K][M] (CONVT: [s][K][M]); bias, scale [M] or NULL; alpha, ralpha [Kx] or NULL.
+ *   Y  [batch][M][Tout] dense: the first Tout columns of every row of ldy.
+ *   report (may be NULL) int32[6]: kernel (0 k_snac_gemm, 1 k_conv_taps, 2 k_pw_fused, 3 k_bf3_gemm; -1 nothing launched), ntaps, NQ,
+ *   ksplit, Tp, Cp (the last four: split-bf16 launches only).
+ * codec_final: launch_codec_final.  x [batch][C][hist + T] dense (hist = max(-x_lo, 0)), uploaded with row stride ld; w [k][C]; a, ra [C] or
+ *   both NULL (ELU); out [batch][T]: the first T columns of every row of out_stride.
+ * codec_hist: launch_codec_hist.  st [batch][C][H] and the image x_img [batch][C][ld] (H columns of head room, then Tn new columns, then
+ *   padding: the launcher gets x_img + H) go in and come back (st_out, x_out) as the launch left them.
+ * codec_embed: launch_codec_embed.  codes int32 [n_codes] addressed through cs_b / cs_q / cs_t (>= 0); tables [nq][bins][C]; h [batch][C][T]:
+ *   the first T columns of every row of ld.
+ * codec_dw7: launch_dw7.  X, Y [batch][C][T]; w7 [C][7]; bias [C]; dil 1 .. 9 (the kernel's halo).
+ * codec_vq_nearest: launch_vq_nearest.  ze [batch][CD][Tm]; cn [CB][CD]; cn2 [CB]; codes_out int32 [batch][Tm]. */
+typedef struct mis_debug_codec_gemm_args {
+    int32_t mode, snake, batch, use_pack;
+    int32_t M, K, N, Tin, Tout, s, pad, Cin, ldx, ldy, x_lo, dup_bias_n0, split_k_ok, taps, dil, noise_rng;
+    uint64_t noise_key;
+    int64_t row_offset;
+    const float *AT, *bias, *X, *R, *scale, *noise, *alpha, *ralpha;
+    const int32_t* row_ids;
+    float* Y;
+    int32_t* report;
+} mis_debug_codec_gemm_args;
+mis_status mis_debug_codec_gemm(int device, const mis_debug_codec_gemm_args* args);
+mis_status mis_debug_codec_final(int device, const float* x, const float* w, float bias, const float* a, const float* ra, int C, int T, int ld,
+                                 int x_lo, int k, int batch, int64_t out_stride, float* out);
+mis_status mis_debug_codec_hist(int device, const float* st, const float* x_img, int C, int ld, int H, int Tn, int batch, float* st_out,
+                                float* x_out);
+mis_status mis_debug_codec_embed(int device, const int32_t* codes, int64_t n_codes, int64_t cs_b, int64_t cs_q, int64_t cs_t,
+                                 const float* tables, int nq, int bins, int C, int ld, int T, int batch, float* h);
+mis_status mis_debug_codec_dw7(int device, const float* X, const float* w7, const float* bias, int batch, int C, int T, int dil, float* Y);
+mis_status mis_debug_codec_vq_nearest(int device, const float* ze, const float* cn, const float* cn2, int batch, int CD, int CB, int Tm,
+                                      int32_t* codes_out);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -389,6 +389,14 @@ class AttnDebugArgsC(C.Structure):
                                    "qp_h_in", "qp_lnw", "qp_lnb", "kcache", "vtcache", "kcache_out", "vtcache_out", "out", "qp_h_out", "report")])
 
 
+class CodecGemmDebugArgsC(C.Structure):
+    """mis_debug_codec_gemm_args (include/mi_speech_debug.h): one launch_gemm call on host data"""
+    _fields_ = ([(n, C.c_int32) for n in ("mode", "snake", "batch", "use_pack", "M", "K", "N", "Tin", "Tout", "s", "pad", "Cin", "ldx", "ldy",
+                                          "x_lo", "dup_bias_n0", "split_k_ok", "taps", "dil", "noise_rng")] +
+                [("noise_key", C.c_uint64), ("row_offset", C.c_int64)] +
+                [(n, _P) for n in ("AT", "bias", "X", "R", "scale", "noise", "alpha", "ralpha", "row_ids", "Y", "report")])
+
+
 # diagnostics / test scaffolding: include/mi_speech_debug.h (not part of the product surface)
 DEBUG_SYMBOLS = {
     "mis_debug_launch_floor": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
@@ -403,6 +411,13 @@ DEBUG_SYMBOLS = {
                                           C.c_int, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_gemm_pf": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "mis_debug_attn_decode": (C.c_int, [C.c_int, C.POINTER(AttnDebugArgsC)]),
+    "mis_debug_codec_gemm": (C.c_int, [C.c_int, C.POINTER(CodecGemmDebugArgsC)]),
+    "mis_debug_codec_final": (C.c_int, [C.c_int, _P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P]),
+    "mis_debug_codec_hist": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_codec_embed": (C.c_int, [C.c_int, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, _P]),
+    "mis_debug_codec_dw7": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_codec_vq_nearest": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),

@@ -402,6 +402,9 @@ bool launch_gemm_bf3(int mode, bool snake, const GemmParams& p_in, int batch, hi
     if (one ? Cin < min_k1 : Cin < min_k) return false;
     if (mode == GEMM_CONVT && (int64_t)p.M * p.K < min_mk) return false;
     if (p.M < 32 || span > 64 || (ntaps != 1 && ntaps != 2 && ntaps != 7)) return false;
+    // the one- and two-tap bodies are built with the 144-column tile (NQ 9) only: a two-tap dense conv whose dilation exceeds 16 would
+    // read tile columns that were never staged, so it stays on the exact-f32 kernel
+    if (ntaps != 7 && span > 16) return false;
     const CodecPack::Entry& e = p.pack->get(p.AT, wtaps, Cin, p.M, s);
 
     const int nbx = (p.N + B3_BN - 1) / B3_BN;
@@ -433,6 +436,7 @@ bool launch_gemm_bf3(int mode, bool snake, const GemmParams& p_in, int batch, hi
         P.ksplit = ksplit; P.part = p.pack->part.p; P.batch = batch;
     }
     dim3 grid(nbx, (p.M + B3_BM - 1) / B3_BM, batch * phases * ksplit), block(B3_THREADS);
+    g_codec_last_launch = CodecLaunchInfo{3, ntaps, nq, ksplit, Tp, e.Cp};
     // MINW 3 = two blocks (ten waves) per CU: 168 registers; the 7-tap body then spills a few address temporaries (A/B by MIS_BF3_MINW)
     // MINW 3 = two blocks (ten waves) per CU, 168 registers: fits 1 and 2 taps; the 7-tap body would spill (measured 2.3x slower), so it
     // runs one block per CU (a persistent loop over column tiles was measured too: no gain, profiles/r02_codec/ab_record.json)

@@ -76,7 +76,13 @@ struct GemmParams {
     int taps, dil;        // TAPS: dense conv, K = taps*Cin, tap j reads x[:, n - pad + j*dil] (zero outside); A^T row j*Cin + c;
                           // pad = (taps-1)*dil: causal, (taps-1)*dil/2: "same"; optional R (+scale) residual epilogue
 };
-// snake: Snake prologue on the X rows (CONVT always runs it: pass alpha = ralpha = zeros for identity)
+// the kernel launch_gemm launched last on this thread (host bookkeeping only, as g_gemm_last_launch of lm_kernels.h): mis_debug_codec_gemm
+// reports it, so that tests/test_gpu_codec_ops.py can assert which kernel family a case reached.
+// kernel: 0 k_snac_gemm, 1 k_conv_taps, 2 k_pw_fused, 3 k_bf3_gemm (ntaps, NQ, ksplit, Tp, Cp of the split-bf16 launch); -1 nothing launched yet
+struct CodecLaunchInfo { int kernel = -1, ntaps = 0, NQ = 0, ksplit = 0, Tp = 0, Cp = 0; };
+extern thread_local CodecLaunchInfo g_codec_last_launch;
+// snake: Snake prologue on the X rows of the RESID, TAPS and CONVT modes (CONVT always runs it: pass alpha = ralpha = zeros for identity);
+// PLAIN, GELU and NOISE have none and ignore the flag
 void launch_gemm(int mode, bool snake, const GemmParams& p, int batch, hipStream_t s);
 // split-bf16 path; false = shape not eligible (or MIS_CODEC_EXACT_F32=1), nothing launched.  p must have ldx / ldy resolved
 bool launch_gemm_bf3(int mode, bool snake, const GemmParams& p, int batch, hipStream_t s);

@@ -1169,17 +1169,23 @@ void launch_vq_residual(float* r, const int32_t* codes, const float* table, int 
     hipLaunchKernelGGL(k_vq_residual, dim3(cdiv(T, 256), C, batch), dim3(256), 0, s, r, codes, table, C, T, stride);
 }
 
+thread_local CodecLaunchInfo g_codec_last_launch;
+
 void launch_gemm(int mode, bool snake, const GemmParams& p_in, int batch, hipStream_t s) {
     GemmParams p = p_in;
     if (!p.ldx) p.ldx = p.Tin;                                          // dense [B][C][T] tensors unless the caller says otherwise
     if (!p.ldy) p.ldy = p.Tout;
     MIS_REQUIRE(p.x_lo <= 0 && p.ldx >= p.Tin, MIS_ERR_GENERATION_FAILED, "bad codec GEMM strides");
+    // the Snake prologue belongs to the residual, dense-conv and transposed-conv modes: the plain, GELU and noise kernels have none, on
+    // either path (the split-bf16 pre-pass would otherwise apply one the exact-f32 kernels ignore)
+    if (mode == GEMM_PLAIN || mode == GEMM_GELU || mode == GEMM_NOISE) snake = false;
     if (mode == GEMM_RESID && snake && p.alpha && p.R && !p.scale && p.bias && p.M == p.K && ru_fused_enabled() &&
         (p.M == 64 || p.M == 96 || p.M == 128 || p.M == 192)) {           // narrow unit tails: whole channel range per block (k_pw_fused)
         PwFusedParams fp{};
         fp.X = p.X; fp.R = p.R; fp.Y = p.Y; fp.a2 = p.alpha; fp.ra2 = p.ralpha; fp.AT = p.AT; fp.b2 = p.bias;
         fp.T = p.N; fp.dil = 0; fp.ldx = p.ldx; fp.ldr = p.ldy; fp.ldy = p.ldy;
         dim3 fg(cdiv(p.N, RU_NT), batch);
+        g_codec_last_launch = CodecLaunchInfo{2, 1, 0, 0, 0, 0};
         if (p.M == 64) hipLaunchKernelGGL((k_pw_fused<64, false>), fg, dim3(256), 0, s, fp);
         else if (p.M == 96) hipLaunchKernelGGL((k_pw_fused<96, false>), fg, dim3(256), 0, s, fp);
         else if (p.M == 128) hipLaunchKernelGGL((k_pw_fused<128, false>), fg, dim3(256), 0, s, fp);
@@ -1189,6 +1195,7 @@ void launch_gemm(int mode, bool snake, const GemmParams& p_in, int batch, hipStr
     if (launch_gemm_bf3(mode, snake, p, batch, s)) return;
     int phases = (mode == GEMM_CONVT) ? p.s : 1;
     dim3 grid(cdiv(p.N, G_BN), cdiv(p.M, G_BM), batch * phases), block(256);
+    if (mode != GEMM_TAPS && (mode != GEMM_CONVT || snake)) g_codec_last_launch = CodecLaunchInfo{0, 1, 0, 0, 0, 0};
     if (mode == GEMM_PLAIN) hipLaunchKernelGGL((k_snac_gemm<GEMM_PLAIN, false>), grid, block, 0, s, p);
     else if (mode == GEMM_GELU) hipLaunchKernelGGL((k_snac_gemm<GEMM_GELU, false>), grid, block, 0, s, p);
     else if (mode == GEMM_RESID && snake) hipLaunchKernelGGL((k_snac_gemm<GEMM_RESID, true>), grid, block, 0, s, p);
@@ -1198,6 +1205,7 @@ void launch_gemm(int mode, bool snake, const GemmParams& p_in, int batch, hipStr
                     "dense conv: %d taps with dilation %d exceed the staged halo", p.taps, p.dil);
         GemmParams q = p;
         if (!snake) { q.alpha = nullptr; q.ralpha = nullptr; }
+        g_codec_last_launch = CodecLaunchInfo{1, p.taps, 0, 0, 0, 0};
         if (q.R) hipLaunchKernelGGL((k_conv_taps<true>), grid, block, 0, s, q);
         else hipLaunchKernelGGL((k_conv_taps<false>), grid, block, 0, s, q);
     }
