@@ -145,6 +145,45 @@ mis_status mis_debug_codec_dw7(int device, const float* X, const float* w7, cons
 mis_status mis_debug_codec_vq_nearest(int device, const float* ze, const float* cn, const float* cn2, int batch, int CD, int CB, int Tm,
                                       int32_t* codes_out);
 
+/* csrc/enc_debug.hip, tests (tests/test_gpu_enc_ops.py): ONE call of a launcher of csrc/whisper_kernels.h - the Whisper / Smart Turn encoder
+ * chain, Moonshine's encoder GEMMs, the decoders' cross-K/V projection - on caller-supplied host data; nothing is computed in the entry
+ * points.  16-bit operands and results are raw bf16 payloads (uint16).  Guards as above: every output lies between guard bands and is
+ * pre-filled with the byte 0xFF, so an element never written comes back as 0xFFFF, and a changed guard byte - or a changed padding column
+ * of a strided output - fails the call with MIS_ERR_GENERATION_FAILED; every input is followed by NaN and the columns of a strided input
+ * that the launch has no business with are NaN.  The entry points refuse (MIS_ERR_INVALID_INPUT) what would make a KERNEL read or write
+ * outside these buffers; what a launcher checks itself is left to it: its status is returned and nothing is launched.
+ *   gemm_big: launch_gemm_big(epi, BigGemmParams).  X is the IMAGE the kernels address, (M - 1) ldx + K elements with row m at m ldx - rows
+ *     overlap when ldx < K (Moonshine's conv2 / conv3), and with ldx > K the columns between two rows are replaced by NaN; exactly that many
+ *     elements are uploaded, which is also what the clamped staging rows of k_gemm_big2 / 3 reach.  W [N][K]; bias [N] or NULL; R [M][N]
+ *     (epi 2, BG_RESID) or [pos_rows][N] (epi 3, BG_GELU_POS); C_out [M][N].  report (may be NULL) int32[4]: kernel (0 k_gemm_big,
+ *     1 k_gemm_big2, 2 k_gemm_big3; -1 nothing launched), epilogue, wave grid WM, WN.  MIS_GEMM_BIG3 is read per launch.
+ *   enc_layernorm: launch_layernorm.  x, y_out [rows][d]; w, b [d].  report int32[1]: 0 k_layernorm, 1 k_layernorm8.
+ *   enc_im2col3: launch_im2col3_f32 / _bf16.  in [B][Tin][C] float (in_is_f32) or bf16; out [B Tout][3 C].
+ *   enc_scatter_kv: launch_scatter_kv.  src [B T][ld], of which only the K columns kcol0 .. + H D and the V columns vcol0 .. + H D are
+ *     uploaded (the others: NaN); kc_out / vc_out: the WHOLE images [B][H][Spad D], 0xFFFF where nothing was written.
+ *   enc_attn_prefill: launch_attn_prefill.  q [B T][H D] dense, uploaded with row stride ldq (a multiple of 8); kc_img / vc_img [B][H][Spad D]
+ *     uploaded unchanged, as mis_debug_attn_decode does - the caller decides what sits behind T; out [B T][H D]: the first H D columns of
+ *     every row of ldo.  report int32[2]: kernel (0 k_attn_prefill, 1 k_attn_prefill2), D.  MIS_ATTN_PREFILL_V1 is read per launch.
+ *   whisper_embed_ln: launch_whisper_embed_ln.  emb [vocab][d], pos_emb [max_pos][d], ids, active, pos_cur, pos_next [batch] (the two position
+ *     arrays go in and come back; pos_next >= 0), lw, lb [d]; h_out [Mpad][d], x_out the packed image of Mpad d elements (xpk layout; d a
+ *     multiple of 32, Mpad of 16).
+ *   whisper_suppress: launch_whisper_suppress.  logits [batch][Vpad] go in and come back; sup [n_sup], bsup [n_bsup], n_gen [batch], active
+ *     [batch] or NULL. */
+mis_status mis_debug_gemm_big(int device, int epi, const uint16_t* X, const uint16_t* W, const uint16_t* bias, const uint16_t* R, int M, int N, int K,
+                              int ldx, int pos_rows, uint16_t* C_out, int32_t* report);
+mis_status mis_debug_enc_layernorm(int device, const uint16_t* x, const uint16_t* w, const uint16_t* b, int rows, int d, float eps, uint16_t* y_out,
+                                   int32_t* report);
+mis_status mis_debug_enc_im2col3(int device, const void* in, int in_is_f32, int B, int Tin, int C, int Tout, int stride, uint16_t* out);
+mis_status mis_debug_enc_scatter_kv(int device, const uint16_t* src, int ld, int kcol0, int vcol0, int B, int T, int H, int D, int Spad,
+                                    uint16_t* kc_out, uint16_t* vc_out);
+mis_status mis_debug_enc_attn_prefill(int device, const uint16_t* q, int ldq, const uint16_t* kc_img, const uint16_t* vc_img, int B, int T, int H, int D,
+                                      int Spad, int ldo, uint16_t* out, int32_t* report);
+mis_status mis_debug_whisper_embed_ln(int device, const uint16_t* emb, const uint16_t* pos_emb, const int32_t* ids, const uint8_t* active,
+                                      int32_t* pos_cur, int32_t* pos_next, const uint16_t* lw, const uint16_t* lb, int d, int vocab, int max_pos,
+                                      int batch, int Mpad, uint16_t* h_out, uint16_t* x_out);
+mis_status mis_debug_whisper_suppress(int device, uint16_t* logits, int Vpad, int vocab, const int32_t* sup, int n_sup, const int32_t* bsup, int n_bsup,
+                                      const int32_t* n_gen, const uint8_t* active, int batch);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -418,6 +418,13 @@ DEBUG_SYMBOLS = {
                                         C.c_int, _P]),
     "mis_debug_codec_dw7": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_codec_vq_nearest": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_gemm_big": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_enc_layernorm": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
+    "mis_debug_enc_im2col3": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_enc_scatter_kv": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_enc_attn_prefill": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_whisper_embed_ln": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_whisper_suppress": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),

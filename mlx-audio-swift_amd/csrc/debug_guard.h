@@ -1,4 +1,4 @@
-// debug_guard.h - what the operator-level debug entry points (gemm_debug.hip, attn_debug.hip) share: poisoned, guarded device buffers.
+// debug_guard.h - what the operator-level debug entry points (gemm_debug.hip, attn_debug.hip, codec_debug.hip, enc_debug.hip) share: poisoned, guarded device buffers.
 #pragma once
 #include <algorithm>
 #include <cstring>

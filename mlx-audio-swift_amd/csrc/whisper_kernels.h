@@ -12,11 +12,22 @@ struct BigGemmParams {
     int M, N, K, ldx, pos_rows;
 };
 void launch_gemm_big(int epi, const BigGemmParams& p, hipStream_t s);
+// what launch_gemm_big / launch_layernorm / launch_attn_prefill launched last on this thread (host bookkeeping only, as
+// g_codec_last_launch of codec_kernels.h): the mis_debug_* entry points of enc_debug.hip report it
+struct EncLaunchInfo {
+    int gemm = -1, epi = 0, WM = 0, WN = 0;   // 0 k_gemm_big, 1 k_gemm_big2, 2 k_gemm_big3; the wave grid (m x n)
+    int ln = -1;                              // 0 k_layernorm, 1 k_layernorm8
+    int attn = -1, attn_D = 0;                // 0 k_attn_prefill, 1 k_attn_prefill2
+};
+extern thread_local EncLaunchInfo g_enc_last_launch;
 void launch_layernorm(const bf16_t* x, bf16_t* y, const bf16_t* w, const bf16_t* b, int rows, int d, float eps, hipStream_t s);
 void launch_im2col3_f32(const float* in, bf16_t* out, int B, int Tin, int C, int Tout, int stride, hipStream_t s);
 void launch_im2col3_bf16(const bf16_t* in, bf16_t* out, int B, int Tin, int C, int Tout, int stride, hipStream_t s);
 void launch_scatter_kv(const bf16_t* src, int ld, int kcol0, int vcol0, bf16_t* kc, bf16_t* vc, int B, int T, int H, int D,
                        int Spad, hipStream_t s);
+// Cache contract of launch_attn_prefill: kc / vc hold ceil(T / 32) tiles per (row, head) within Spad keys; keys T .. tile end of the
+// last tile must be ZERO in both images, as launch_scatter_kv leaves them - the kernels mask the scores there (p = 0) but still multiply
+// p by the stored values, so a NaN or Inf there reaches the output.  Tiles behind the last one are never read.  ldq must be a multiple of 8.
 void launch_attn_prefill(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_t* vc, bf16_t* out, int ldo, int B, int T,
                          int H, int D, int Spad, hipStream_t s);
 void launch_whisper_embed_ln(const bf16_t* emb, const bf16_t* pos_emb, const int32_t* ids, const uint8_t* active, int* pos_cur,

@@ -368,6 +368,7 @@ static bool launch_big3_one(const BigGemmParams& p, hipStream_t s) {
     static const bool ok = hipFuncSetAttribute((const void*)k_gemm_big3<EPI, WM, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); return false; }
     hipLaunchKernelGGL((k_gemm_big3<EPI, WM, WN>), dim3(cdiv(p.N, BG3_BN), cdiv(p.M, BG3_BM)), dim3(512), lds_bytes, s, p);
+    g_enc_last_launch.gemm = 2; g_enc_last_launch.epi = EPI; g_enc_last_launch.WM = WM; g_enc_last_launch.WN = WN;
     return true;
 }
 template <int EPI>
@@ -375,6 +376,8 @@ static bool launch_big3(const BigGemmParams& p, hipStream_t s) {
     // wave grid as measured: 2 (m) x 4 (n) for the wide / deep MLP shapes, 4 x 2 otherwise
     return (p.N >= 4096 || p.K >= 4096) ? launch_big3_one<EPI, 2, 4>(p, s) : launch_big3_one<EPI, 4, 2>(p, s);
 }
+
+thread_local EncLaunchInfo g_enc_last_launch;
 
 void launch_gemm_big(int epi, const BigGemmParams& p, hipStream_t s) {
     MIS_REQUIRE(p.K % BG_BK == 0 && p.ldx % 8 == 0 && p.N % 4 == 0, MIS_ERR_INVALID_INPUT, "big GEMM needs K %% 32 == 0");
@@ -396,6 +399,9 @@ void launch_gemm_big(int epi, const BigGemmParams& p, hipStream_t s) {
             if (done) return;
         }
     }
+    if (epi < BG_NONE || epi > BG_GELU_POS) throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
+    g_enc_last_launch.epi = epi; g_enc_last_launch.WM = 2; g_enc_last_launch.WN = 2;
+    g_enc_last_launch.gemm = (p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK) ? 1 : 0;
     if (p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK) {
         switch (epi) {
             case BG_NONE: hipLaunchKernelGGL((k_gemm_big2<BG_NONE>), grid, block, 0, s, p); return;
@@ -482,6 +488,7 @@ __global__ void __launch_bounds__(256) k_layernorm8(const bf16_t* __restrict__ x
 void launch_layernorm(const bf16_t* x, bf16_t* y, const bf16_t* w, const bf16_t* b, int rows, int d, float eps, hipStream_t s) {
     if (rows <= 0) return;
     const bool a16 = ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)w) | ((uintptr_t)b)) & 15) == 0;
+    g_enc_last_launch.ln = (d % 8 == 0 && d <= 2048 && a16) ? 1 : 0;
     if (d % 8 == 0 && d <= 2048 && a16) hipLaunchKernelGGL(k_layernorm8, dim3(rows), dim3(256), 0, s, x, y, w, b, d, eps);
     else hipLaunchKernelGGL(k_layernorm, dim3(rows), dim3(256), 0, s, x, y, w, b, d, eps);
 }
@@ -797,12 +804,14 @@ void launch_attn_prefill(const bf16_t* q, int ldq, const bf16_t* kc, const bf16_
     const bool v1 = ve && atoi(ve) != 0;
     if (D == 64 && !v1 && ((uintptr_t)kc & 15) == 0 && ((uintptr_t)vc & 15) == 0) {
         hipLaunchKernelGGL((k_attn_prefill2<64>), dim3(cdiv(T, 256), H, B), dim3(512), 0, s, q, ldq, kc, vc, out, ldo, T, H, Spad, scale);
+        g_enc_last_launch.attn = 1; g_enc_last_launch.attn_D = 64;
         return;
     }
     dim3 grid(cdiv(T, 64), H, B), block(256);
     if (D == 64) hipLaunchKernelGGL((k_attn_prefill<64>), grid, block, 0, s, q, ldq, kc, vc, out, ldo, T, H, Spad, scale);
     else if (D == 128) hipLaunchKernelGGL((k_attn_prefill<128>), grid, block, 0, s, q, ldq, kc, vc, out, ldo, T, H, Spad, scale);
     else throw MisError(MIS_ERR_INVALID_INPUT, "head_dim must be 64 or 128");
+    g_enc_last_launch.attn = 0; g_enc_last_launch.attn_D = D;
 }
 
 // ============================================================================ the encoder chain
