@@ -920,6 +920,64 @@ mis_status mis_ecapa_lid_forward_features(mis_ecapa_lid*, const float* mel, cons
 mis_status mis_ecapa_lid_tap(mis_ecapa_lid*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * LASR CTC speech-to-text (Sources/MLXAudioSTT/Models/LasrCTC/LasrCTCModel.swift:7-406, LasrCTCConfig.swift:3-193; front end
+ * ParakeetAudio.swift:6-62 with DSP.swift hanningWindow / stft(.constant) / melFilters(slaney, slaney); greedy CTC
+ * Wav2Vec2CTC.swift:520-542): 16 kHz mono rows of differing lengths, 1..max_batch a call.  Row b of n_b samples has F_b = 1 + n_b / 160
+ * feature frames (pre-emphasis 0.97, symmetric Hann window of 400 in 512, 256 zeros on each side, power spectrum, slaney filters,
+ * log(. + 2^-24), per-bin mean / unbiased variance over the row's own frames), T1_b = (F_b - k_s) / s + 1 and T2_b = (T1_b - k_s) / s + 1
+ * frames behind the two stem convs; then the macaron Conformer blocks (full non-causal attention with rotate-half RoPE over the row's
+ * own T2_b keys, GLU -> depthwise conv -> inference BatchNorm), out_norm, the CTC head and greedy CTC collapse on the device.
+ * f32 through the normalised features, bf16 storage with f32 accumulation behind them, f32 logits; the RoPE tables stay f32.
+ * A row's result does not depend on the batch it travels in, on the longest row, or on what lies behind lens[b]: bit for bit.
+ * The workspace is sized once, at finalize, from max_batch and max_seconds; a call allocates nothing.
+ * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: head size hidden_size / num_attention_heads = 64;
+ * hidden_size, intermediate_size, subsampling_conv_channels multiples of 32; num_key_value_heads divides num_attention_heads;
+ * conv_kernel_size 2..64; subsampling_conv_kernel_size 2..8; subsampling_conv_stride 1..4; vocab_size <= 65536 (any value: a vocabulary
+ * that is no multiple of 4 is padded inside the engine); num_mel_bins 8..256 (dense_0's K is zero-padded to a multiple of 32 at load);
+ * rope_type 0 ("default") only; max_batch 1..64; max_seconds 1..120.  At finalize: a tensor missing or misshapen.  At a call, before
+ * any launch: batch outside 1..max_batch, a row longer than stride or max_seconds, a row too short for the stem (F_b < k_s or
+ * T1_b < k_s), a null pointer.  A rejected call leaves the handle usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_lasr mis_lasr;
+/* LasrCTCConfig + LasrEncoderConfig; hidden_act 0 silu, 1 relu; rope_type 0 "default"; max_batch / max_seconds size the workspace */
+typedef struct {
+    int32_t vocab_size, hidden_size, num_hidden_layers, num_attention_heads, num_key_value_heads, intermediate_size, hidden_act,
+            conv_kernel_size, convolution_bias, num_mel_bins, subsampling_conv_channels, subsampling_conv_kernel_size,
+            subsampling_conv_stride, attention_bias, rope_type, pad_token_id, max_batch, max_seconds;
+    float layer_norm_eps, rope_theta, conv_residual_weights[2], feed_forward_residual_weights[2];
+} mis_lasr_config;
+mis_status mis_lasr_create(const mis_lasr_config*, int device, mis_lasr** out);
+/* names as LasrCTCModel.sanitize leaves them (:352-367): encoder.subsampler.{dense_0,conv_0,conv_1,dense_1}.*,
+ * encoder.layers.N.{feed_forward1,feed_forward2}.{linear1,linear2}.*, .self_attn.{q,k,v,o}_proj.*, .conv.{pointwise_conv1,depthwise_conv,
+ * pointwise_conv2}.*, .conv.norm.{weight,bias,running_mean,running_var}, .norm_{feed_forward1,self_att,conv,feed_forward2,out}.*,
+ * encoder.out_norm.*, ctc_head.*; conv weights [out, k, in]; host pointers.  finalize names a missing weight and checks every shape;
+ * only a LayerNorm's bias may be absent (zero, as the reference creates it: the published checkpoints carry none). */
+mis_status mis_lasr_set_tensor(mis_lasr*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_lasr_init_synthetic(mis_lasr*, uint64_t seed);
+mis_status mis_lasr_finalize(mis_lasr*);
+void       mis_lasr_destroy(mis_lasr*);
+/* kernel launches of the last call */
+int        mis_lasr_launches(const mis_lasr*);
+/* F_b and T2_b of rows of lens[b] samples (either output may be NULL; T2 0: too short for the stem) */
+mis_status mis_lasr_frames(const mis_lasr*, const int64_t* lens, int batch, int32_t* F_out, int32_t* T2_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> normalised features f32 [batch, Fmax, num_mel_bins], Fmax the longest row's
+ * frames, zeros behind a row's own F_b */
+mis_status mis_lasr_features(mis_lasr*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* feats_out);
+/* LasrCTCModel.callAsFunction on given features f32 [batch, F, num_mel_bins], frames[batch] valid frames each (NULL = F) ->
+ * logits f32 [batch, T2 of F, vocab_size], zeros behind a row's own T2_b */
+mis_status mis_lasr_forward_features(mis_lasr*, const float* feats, const int32_t* frames, int batch, int F, float* logits_out);
+/* front end + callAsFunction: logits f32 [batch, T2 of the longest row, vocab_size] */
+mis_status mis_lasr_forward(mis_lasr*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* logits_out);
+/* generate for a ragged batch: arg-max per frame (lowest index on ties), a token is kept when it differs from the previous frame's and
+ * is not pad_token_id.  tokens_out int32 [batch, tokens_stride] and n_tokens[batch] are the caller's; a row's ids behind tokens_stride
+ * are dropped (T2 of the longest row always suffices).  One synchronisation per call. */
+mis_status mis_stt_lasr_generate(mis_lasr*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int32_t* tokens_out,
+                                 int64_t tokens_stride, int32_t* n_tokens);
+/* tensors of the last call, f32 [B, T2max, hidden_size], zero rows behind a row's own T2_b: stage 0 the stem's output, 1..L that
+ * block's output, L + 1 out_norm.  dims[3] receives B, T2max, hidden_size; out NULL for the dims alone, else room for `capacity` floats. */
+mis_status mis_lasr_tap(mis_lasr*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

@@ -229,6 +229,10 @@ mis_status mis_debug_smartturn_timing(const mis_smartturn* c, float* ms);
 /* csrc/ecapa_lid.hip, measurements: device milliseconds of the last call, ms[2] = front end (0 after forward_features), model */
 mis_status mis_debug_ecapa_lid_timing(const mis_ecapa_lid* c, float* ms);
 
+/* csrc/lasr.hip, measurements: ms NULL switches the timestamps of mis_stt_lasr_generate on; else device milliseconds of the last
+ * generate, ms[3] = front end, encoder, tail */
+mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,8 @@ from .smartturn import (SmartTurnModel, SmartTurnConfig, SmartTurnEncoderConfig,
                         SmartTurnEndpointOutput, smart_turn_sanitize, smart_turn_expected_keys, smart_turn_read_directory)
 from .lid import (EcapaTdnnLID, EcapaTdnnConfig, LanguagePrediction, LIDOutput, LIDError, ecapa_lid_sanitize,  # noqa: F401
                   ecapa_lid_expected_shapes, ecapa_lid_labels, ecapa_lid_read_directory)
+from .lasr import (LasrCTCModel, LasrCTCConfig, LasrEncoderConfig, SentencePieceTokenizer, lasr_sanitize, lasr_expected_keys,  # noqa: F401
+                   greedy_ctc_tokens)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

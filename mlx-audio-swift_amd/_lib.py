@@ -160,6 +160,15 @@ class EcapaLidConfigC(C.Structure):
                 ("max_batch", C.c_int32), ("max_samples", C.c_int32)]
 
 
+class LasrConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads",
+                                          "intermediate_size", "hidden_act", "conv_kernel_size", "convolution_bias", "num_mel_bins",
+                                          "subsampling_conv_channels", "subsampling_conv_kernel_size", "subsampling_conv_stride",
+                                          "attention_bias", "rope_type", "pad_token_id", "max_batch", "max_seconds")]
+                + [("layer_norm_eps", C.c_float), ("rope_theta", C.c_float), ("conv_residual_weights", C.c_float * 2),
+                   ("feed_forward_residual_weights", C.c_float * 2)])
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -304,6 +313,18 @@ SYMBOLS = {
     "mis_ecapa_lid_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "mis_ecapa_lid_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mis_ecapa_lid_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_lasr_create": (C.c_int, [C.POINTER(LasrConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_lasr_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_lasr_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_lasr_finalize": (C.c_int, [_P]),
+    "mis_lasr_destroy": (None, [_P]),
+    "mis_lasr_launches": (C.c_int, [_P]),
+    "mis_lasr_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_lasr_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
+    "mis_lasr_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_lasr_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
+    "mis_stt_lasr_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P]),
+    "mis_lasr_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -436,6 +457,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_smartturn_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
     "mis_debug_ecapa_lid_timing": (C.c_int, [_P, _P]),
+    "mis_debug_lasr_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 

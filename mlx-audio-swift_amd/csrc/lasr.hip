@@ -1,0 +1,1044 @@
+// lasr.hip - the LASR CTC engine: raw 16 kHz samples -> NeMo-style log-mel -> strided conv stem -> RoPE Conformer -> CTC head -> greedy ids.
+//
+// Reference being replaced: LasrCTCModel / LasrEncoder / LasrEncoderBlock / LasrEncoderAttention / LasrEncoderConvolutionModule
+// (Sources/MLXAudioSTT/Models/LasrCTC/LasrCTCModel.swift:7-406), ParakeetAudio.logMelSpectrogram (ParakeetAudio.swift:6-62) with DSP.swift's
+// hanningWindow / stft(.constant) / melFilters(slaney, slaney), Wav2Vec2CTCModel.greedyCTCTokens (Wav2Vec2CTC.swift:520-542).
+// Tokenizer and text stay on the host.
+//
+// Ragged batch.  A row of n samples has F = 1 + n / 160 feature frames, T1 = (F - k_s) / s + 1 and T2 = (T1 - k_s) / s + 1 stem frames.
+// The batch is laid out with the longest row's Fp / T1p / T2p frames per row; every kernel takes the row's own count: the normalisation
+// statistics run over the row's F frames, the im2col writes zero patches behind T1[b] / T2[b], the depthwise conv reads zeros outside
+// 0 .. T2[b], attention masks keys >= T2[b], the LayerNorms that close a block write zero rows behind T2[b], the CTC scan stops there.
+// Samples behind lens[b] are never read.
+//
+// Precision: f32 from the waveform through the normalised features, one rounding to bf16 there; bf16 storage with f32 accumulation
+// behind it, one rounding per kernel output; f32 logits; f32 statistics in every LayerNorm; f32 RoPE tables (the reference casts them to
+// the activations' dtype); the depthwise conv with the BatchNorm folded into its taps accumulates in f32.
+//
+//   k_lasr_stft_mel    pre-emphasis, 512-point FFT of one frame in LDS, power, slaney mel, log
+//   k_lasr_norm        per-row per-bin mean / unbiased variance in two passes over the row's own frames, fixed summation order
+//   k_lasr_pack        f32 features -> the bf16 rows dense_0 multiplies (K padded to 32, zero rows behind F[b])
+//   k_lasr_im2col      k_s-tap strided patches with per-row valid counts
+//   k_lasr_gemm        C = X W^T on v_mfma_f32_16x16x32_bf16, 128 x 128 or 64 x 64 tiles; epilogues bias / ReLU / SiLU / a R + b acc / f32
+//   k_lasr_ln          LayerNorm with weight and bias, one wave per row, optional zero rows behind the row count
+//   k_lasr_rope        rotate-half RoPE over the whole 64-wide head on the q and k columns, in place, before attention
+//   k_lasr_attn        non-causal flash attention, 64 queries x head x row per block, K / V tiles staged through LDS, per-row key count
+//   k_lasr_glu_dwconv  GLU -> zero-padded depthwise conv (<= 64 taps) -> folded BatchNorm -> activation, a time tile + halo in LDS
+//   k_lasr_argmax      per-frame arg-max (lowest index on ties);  k_lasr_collapse  CTC collapse + compaction per row
+#include "common.h"
+#include "host_weights.h"
+
+#include <math.h>
+#include <string.h>
+#include <memory>
+
+#define LS_HD 64                 // head size
+#define LS_MAX_BATCH 64
+#define LS_MAX_SECONDS 120
+#define LS_NFFT 512
+#define LS_HOP 160
+#define LS_WIN 400
+#define LS_BINS 257
+#define LS_DW_TT 64              // depthwise conv: output frames per block
+#define LS_DW_MAXK 64
+
+struct LsLayer {
+    bf16_t *ln_ff1w, *ln_ff1b, *ff1_w1, *ff1_b1, *ff1_w2, *ff1_b2;
+    bf16_t *ln_attw, *ln_attb, *wqkv, *bqkv, *wo, *bo;
+    bf16_t *ln_cvw, *ln_cvb, *pw1, *pw1b, *pw2, *pw2b;
+    float *dw, *dwshift;         // [k][C] taps with the BatchNorm scale folded in; [C] shift
+    bf16_t *ln_ff2w, *ln_ff2b, *ff2_w1, *ff2_b1, *ff2_w2, *ff2_b2;
+    bf16_t *ln_outw, *ln_outb;
+};
+
+struct mis_lasr {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    mis_lasr_config cfg{};
+    int d = 0, f = 0, V = 0, H = 0, Hk = 0, L = 0, mels = 0, Kp = 0, cc = 0, ks = 0, st = 0, ck = 0;
+    HostWeights raw{"LASR", MIS_ERR_INVALID_INPUT};
+    bool finalized = false;
+    DevBuf<bf16_t> arena;
+    DevBuf<float> farena;
+    float *window = nullptr, *tw_cos = nullptr, *tw_sin = nullptr, *fb = nullptr, *rope_cos = nullptr, *rope_sin = nullptr;
+    int* fb_range = nullptr;
+    bf16_t *d0w = nullptr, *d0b = nullptr, *c0w = nullptr, *c0b = nullptr, *c1w = nullptr, *c1b = nullptr, *d1w = nullptr, *d1b = nullptr,
+           *onw = nullptr, *onb = nullptr, *headw = nullptr, *headb = nullptr;
+    std::vector<LsLayer> layers;
+    // workspace (sized at finalize)
+    int64_t maxN = 0;
+    int Fcap = 0, T1cap = 0, T2cap = 0;
+    DevBuf<float> pcm, melraw, feats, logits;
+    DevBuf<int> fbr, cntN, cntF, cnt1, cnt2, pred, tokens, ntok;
+    DevBuf<bf16_t> x0, h0, col, c0, c1, h, x, qkv, att, ff, enc_out;
+    PinnedBuf<int32_t> host_tokens;
+    // state of the last call
+    int batch = 0, Fp = 0, T1p = 0, T2p = 0, launches = 0;
+    std::vector<int> hN, hF, hT1, hT2;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = false;
+};
+
+#define LS_LAUNCH(c, kernel, grid, block, ...)                                  \
+    do {                                                                        \
+        hipLaunchKernelGGL(kernel, grid, block, 0, (c)->stream, __VA_ARGS__);   \
+        (c)->launches += 1;                                                     \
+    } while (0)
+
+// ---------------------------------------------------------------------------- frame counts
+static inline int ls_frames(int64_t n) { return (int)(1 + n / LS_HOP); }
+static inline int ls_conv_out(int t, int k, int s) { return t >= k ? (t - k) / s + 1 : 0; }
+
+extern "C" mis_status mis_lasr_frames(const mis_lasr* c, const int64_t* lens, int batch, int32_t* F_out, int32_t* T2_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && lens && batch >= 1, MIS_ERR_INVALID_INPUT, "bad argument");
+    for (int b = 0; b < batch; ++b) {
+        MIS_REQUIRE(lens[b] >= 0, MIS_ERR_INVALID_INPUT, "row %d: negative sample count", b);
+        const int F = ls_frames(lens[b]);
+        if (F_out) F_out[b] = F;
+        if (T2_out) T2_out[b] = ls_conv_out(ls_conv_out(F, c->ks, c->st), c->ks, c->st);
+    }
+    MIS_API_END
+}
+
+extern "C" mis_status mis_lasr_create(const mis_lasr_config* cfg, int device, mis_lasr** out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
+    const int d = cfg->hidden_size, H = cfg->num_attention_heads, Hk = cfg->num_key_value_heads;
+    MIS_REQUIRE(d > 0 && d % 32 == 0, MIS_ERR_INVALID_INPUT, "hidden_size %d unsupported (a positive multiple of 32)", d);
+    MIS_REQUIRE(H > 0 && d % H == 0 && d / H == LS_HD, MIS_ERR_INVALID_INPUT,
+                "num_attention_heads %d: head size hidden_size / num_attention_heads must be %d", H, LS_HD);
+    MIS_REQUIRE(Hk > 0 && H % Hk == 0, MIS_ERR_INVALID_INPUT, "num_key_value_heads %d must divide num_attention_heads %d", Hk, H);
+    MIS_REQUIRE(cfg->intermediate_size > 0 && cfg->intermediate_size % 32 == 0, MIS_ERR_INVALID_INPUT,
+                "intermediate_size %d unsupported (a positive multiple of 32)", cfg->intermediate_size);
+    MIS_REQUIRE(cfg->subsampling_conv_channels > 0 && cfg->subsampling_conv_channels % 32 == 0, MIS_ERR_INVALID_INPUT,
+                "subsampling_conv_channels %d unsupported (a positive multiple of 32)", cfg->subsampling_conv_channels);
+    MIS_REQUIRE(cfg->conv_kernel_size >= 2 && cfg->conv_kernel_size <= LS_DW_MAXK, MIS_ERR_INVALID_INPUT,
+                "conv_kernel_size %d outside 2..%d", cfg->conv_kernel_size, LS_DW_MAXK);
+    MIS_REQUIRE(cfg->subsampling_conv_kernel_size >= 2 && cfg->subsampling_conv_kernel_size <= 8, MIS_ERR_INVALID_INPUT,
+                "subsampling_conv_kernel_size %d outside 2..8", cfg->subsampling_conv_kernel_size);
+    MIS_REQUIRE(cfg->subsampling_conv_stride >= 1 && cfg->subsampling_conv_stride <= 4, MIS_ERR_INVALID_INPUT,
+                "subsampling_conv_stride %d outside 1..4", cfg->subsampling_conv_stride);
+    MIS_REQUIRE(cfg->vocab_size >= 1 && cfg->vocab_size <= 65536, MIS_ERR_INVALID_INPUT, "vocab_size %d outside 1..65536", cfg->vocab_size);
+    MIS_REQUIRE(cfg->num_mel_bins >= 8 && cfg->num_mel_bins <= 256, MIS_ERR_INVALID_INPUT, "num_mel_bins %d outside 8..256", cfg->num_mel_bins);
+    MIS_REQUIRE(cfg->num_hidden_layers >= 1, MIS_ERR_INVALID_INPUT, "num_hidden_layers %d must be positive", cfg->num_hidden_layers);
+    MIS_REQUIRE(cfg->rope_type == 0, MIS_ERR_INVALID_INPUT, "rope_type: only \"default\" is implemented");
+    MIS_REQUIRE(cfg->rope_theta > 0.0f, MIS_ERR_INVALID_INPUT, "rope_theta must be positive");
+    MIS_REQUIRE(cfg->hidden_act == 0 || cfg->hidden_act == 1, MIS_ERR_INVALID_INPUT, "hidden_act must be 0 (silu) or 1 (relu)");
+    MIS_REQUIRE(cfg->pad_token_id >= 0, MIS_ERR_INVALID_INPUT, "pad_token_id must not be negative");
+    MIS_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= LS_MAX_BATCH, MIS_ERR_INVALID_INPUT, "max_batch %d outside 1..%d", cfg->max_batch, LS_MAX_BATCH);
+    MIS_REQUIRE(cfg->max_seconds >= 1 && cfg->max_seconds <= LS_MAX_SECONDS, MIS_ERR_INVALID_INPUT, "max_seconds %d outside 1..%d", cfg->max_seconds,
+                LS_MAX_SECONDS);
+    auto c = std::make_unique<mis_lasr>();
+    c->stream = mis_open_stream(device);
+    c->device = device; c->cfg = *cfg;
+    c->d = d; c->f = cfg->intermediate_size; c->V = cfg->vocab_size; c->H = H; c->Hk = Hk; c->L = cfg->num_hidden_layers;
+    c->mels = cfg->num_mel_bins; c->Kp = (int)round_up(c->mels, 32); c->cc = cfg->subsampling_conv_channels;
+    c->ks = cfg->subsampling_conv_kernel_size; c->st = cfg->subsampling_conv_stride; c->ck = cfg->conv_kernel_size;
+    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
+    *out = c.release();
+    MIS_API_END
+}
+
+extern "C" void mis_lasr_destroy(mis_lasr* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
+    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
+    delete c;
+}
+
+extern "C" mis_status mis_lasr_set_tensor(mis_lasr* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
+    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    c->raw.put(name, data, dtype, shape, ndim);
+    MIS_API_END
+}
+
+// slaney mel scale (DSP.swift melFilters, melScale .slaney)
+static double ls_hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + log(f / 1000.0) / (log(6.4) / 27.0); }
+static double ls_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
+
+extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+    HIP_CHECK(hipSetDevice(c->device));
+    const int64_t d = c->d, f = c->f, V = c->V, cc = c->cc, ks = c->ks, ck = c->ck, mels = c->mels, Kp = c->Kp;
+    const bool ab = c->cfg.attention_bias != 0, cb = c->cfg.convolution_bias != 0;
+    HostArena a(c->raw);
+    std::vector<bf16_t>& host = a.host;
+    std::vector<float>& fhost = a.fhost;
+    const std::string E = "encoder.", S = "encoder.subsampler.";
+    // ---- front end tables (f32): window 400 -> 512, FFT twiddles, slaney filters [257][mels] and each filter's bin range
+    const size_t o_win = a.ftake(LS_NFFT), o_twc = a.ftake(LS_NFFT / 2), o_tws = a.ftake(LS_NFFT / 2);
+    for (int n = 0; n < LS_WIN; ++n)
+        fhost[o_win + (LS_NFFT - LS_WIN) / 2 + n] = 0.5f * (1.0f - (float)cos(2.0 * M_PI * (double)n / (double)(LS_WIN - 1)));
+    for (int k = 0; k < LS_NFFT / 2; ++k) {
+        fhost[o_twc + k] = (float)cos(2.0 * M_PI * (double)k / LS_NFFT);
+        fhost[o_tws + k] = (float)-sin(2.0 * M_PI * (double)k / LS_NFFT);
+    }
+    const size_t o_fb = a.ftake((size_t)LS_BINS * mels);
+    std::vector<int> ranges(2 * mels, 0);
+    {
+        const double mmax = ls_hz_to_mel(8000.0);
+        std::vector<double> fp(mels + 2);
+        for (int i = 0; i < mels + 2; ++i) fp[i] = ls_mel_to_hz((double)i * mmax / (double)(mels + 1));
+        for (int j = 0; j < mels; ++j) {
+            const double lo = fp[j], ce = fp[j + 1], hi = fp[j + 2], enorm = 2.0 / (hi - lo);
+            int first = LS_BINS, last = 0;
+            for (int i = 0; i < LS_BINS; ++i) {
+                const double fr = (double)i * 16000.0 / LS_NFFT;
+                double w = 0.0;
+                if (fr >= lo && fr < ce) w = (fr - lo) / (ce - lo);
+                else if (fr >= ce && fr <= hi) w = (hi - fr) / (hi - ce);
+                fhost[o_fb + (size_t)i * mels + j] = (float)(w * enorm);
+                if (w != 0.0) { first = std::min(first, i); last = std::max(last, i + 1); }
+            }
+            ranges[2 * j] = first < last ? first : 0; ranges[2 * j + 1] = first < last ? last : 0;
+        }
+    }
+    // ---- workspace extents and the rotary tables [T2cap][32] (LasrRotaryEmbedding, :23-42): f32, angle = pos * theta^(-2i/64)
+    c->maxN = (int64_t)c->cfg.max_seconds * 16000;
+    c->Fcap = ls_frames(c->maxN); c->T1cap = ls_conv_out(c->Fcap, c->ks, c->st); c->T2cap = ls_conv_out(c->T1cap, c->ks, c->st);
+    MIS_REQUIRE(c->T2cap >= 1, MIS_ERR_INVALID_INPUT, "max_seconds %d gives no encoder frame", c->cfg.max_seconds);
+    const size_t o_rc = a.ftake((size_t)c->T2cap * 32), o_rs = a.ftake((size_t)c->T2cap * 32);
+    for (int i = 0; i < 32; ++i) {
+        const float inv = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / (float)LS_HD);
+        for (int p = 0; p < c->T2cap; ++p) {
+            const float ang = (float)p * inv;
+            fhost[o_rc + (size_t)p * 32 + i] = (float)cos((double)ang);
+            fhost[o_rs + (size_t)p * 32 + i] = (float)sin((double)ang);
+        }
+    }
+    // ---- stem.  dense_0 [d][mels] -> [d][Kp] (zero columns); conv weights [O][k][I] are already the patch order k * I + i
+    const HostTensor& w0 = c->raw.need(S + "dense_0.weight", {d, mels});
+    const size_t o_d0w = a.btake((size_t)d * Kp);
+    for (int64_t n = 0; n < d; ++n) for (int64_t k = 0; k < mels; ++k) host[o_d0w + n * Kp + k] = f32_to_bf16(w0.v[n * mels + k]);
+    const size_t o_d0b = a.bvec(S + "dense_0.bias", d);
+    auto conv3 = [&](const std::string& name, int64_t O, int64_t K, int64_t I) {
+        const HostTensor& t = c->raw.need(name, {O, K, I});
+        const size_t off = a.btake((size_t)O * K * I);
+        for (size_t i = 0; i < (size_t)O * K * I; ++i) host[off + i] = f32_to_bf16(t.v[i]);
+        return off;
+    };
+    const size_t o_c0w = conv3(S + "conv_0.weight", d, ks, d), o_c0b = a.bvec(S + "conv_0.bias", d);
+    const size_t o_c1w = conv3(S + "conv_1.weight", cc, ks, d), o_c1b = a.bvec(S + "conv_1.bias", cc);
+    const size_t o_d1w = a.bmat(S + "dense_1.weight", d, cc), o_d1b = a.bvec(S + "dense_1.bias", d);
+    // ---- blocks.  A LayerNorm bias the checkpoint does not carry is zero, the value the reference's LayerNorm is created with (the
+    // published checkpoints have weight-only LayerNorms and the reference loads them with noUnusedKeys, :401)
+    auto ln_bias = [&](const std::string& name) { return c->raw.find(name) ? a.bvec(name, d) : a.btake(d); };
+    struct Off { size_t v[28]; size_t dw, sh; };
+    std::vector<Off> lo(c->L);
+    const size_t npos = (size_t)-1;
+    const int64_t NQ = (int64_t)(c->H + 2 * c->Hk) * LS_HD;
+    for (int li = 0; li < c->L; ++li) {
+        const std::string q = E + "layers." + std::to_string(li) + ".";
+        Off& o = lo[li];
+        auto norm = [&](const std::string& n, int i) { o.v[i] = a.bvec(q + n + ".weight", d); o.v[i + 1] = ln_bias(q + n + ".bias"); };
+        auto ffn = [&](const std::string& n, int i) {
+            o.v[i] = a.bmat(q + n + ".linear1.weight", f, d); o.v[i + 1] = ab ? a.bvec(q + n + ".linear1.bias", f) : npos;
+            o.v[i + 2] = a.bmat(q + n + ".linear2.weight", d, f); o.v[i + 3] = ab ? a.bvec(q + n + ".linear2.bias", d) : npos;
+        };
+        norm("norm_feed_forward1", 0); ffn("feed_forward1", 2);
+        norm("norm_self_att", 6);
+        o.v[8] = a.btake((size_t)NQ * d);
+        a.bmat_into(q + "self_attn.q_proj.weight", d, d, o.v[8]);
+        a.bmat_into(q + "self_attn.k_proj.weight", (int64_t)c->Hk * LS_HD, d, o.v[8] + (size_t)d * d);
+        a.bmat_into(q + "self_attn.v_proj.weight", (int64_t)c->Hk * LS_HD, d, o.v[8] + (size_t)(d + c->Hk * LS_HD) * d);
+        o.v[9] = npos;
+        if (ab) {
+            o.v[9] = a.btake(NQ);
+            const HostTensor& bq = c->raw.need(q + "self_attn.q_proj.bias", {d});
+            const HostTensor& bk = c->raw.need(q + "self_attn.k_proj.bias", {(int64_t)c->Hk * LS_HD});
+            const HostTensor& bv = c->raw.need(q + "self_attn.v_proj.bias", {(int64_t)c->Hk * LS_HD});
+            for (int64_t i = 0; i < d; ++i) host[o.v[9] + i] = f32_to_bf16(bq.v[i]);
+            for (int64_t i = 0; i < c->Hk * LS_HD; ++i) {
+                host[o.v[9] + d + i] = f32_to_bf16(bk.v[i]);
+                host[o.v[9] + d + c->Hk * LS_HD + i] = f32_to_bf16(bv.v[i]);
+            }
+        }
+        o.v[10] = a.bmat(q + "self_attn.o_proj.weight", d, d); o.v[11] = ab ? a.bvec(q + "self_attn.o_proj.bias", d) : npos;
+        norm("norm_conv", 12);
+        o.v[14] = conv3(q + "conv.pointwise_conv1.weight", 2 * d, 1, d); o.v[15] = cb ? a.bvec(q + "conv.pointwise_conv1.bias", 2 * d) : npos;
+        o.v[16] = conv3(q + "conv.pointwise_conv2.weight", d, 1, d); o.v[17] = cb ? a.bvec(q + "conv.pointwise_conv2.bias", d) : npos;
+        // inference BatchNorm (eps 1e-5, the MLXNN default) folded into the depthwise taps and a shift, in f32
+        const HostTensor& dw = c->raw.need(q + "conv.depthwise_conv.weight", {d, ck, 1});
+        const HostTensor* dwb = cb ? &c->raw.need(q + "conv.depthwise_conv.bias", {d}) : nullptr;
+        const HostTensor& bw = c->raw.need(q + "conv.norm.weight", {d}); const HostTensor& bb = c->raw.need(q + "conv.norm.bias", {d});
+        const HostTensor& bm = c->raw.need(q + "conv.norm.running_mean", {d}); const HostTensor& bvv = c->raw.need(q + "conv.norm.running_var", {d});
+        o.dw = a.ftake((size_t)ck * d); o.sh = a.ftake(d);
+        for (int64_t ch = 0; ch < d; ++ch) {
+            const float scale = bw.v[ch] / sqrtf(bvv.v[ch] + 1e-5f);
+            for (int64_t k = 0; k < ck; ++k) fhost[o.dw + k * d + ch] = dw.v[ch * ck + k] * scale;
+            fhost[o.sh + ch] = ((dwb ? dwb->v[ch] : 0.0f) - bm.v[ch]) * scale + bb.v[ch];
+        }
+        norm("norm_feed_forward2", 18); ffn("feed_forward2", 20);
+        norm("norm_out", 24);
+    }
+    const size_t o_onw = a.bvec(E + "out_norm.weight", d), o_onb = ln_bias(E + "out_norm.bias");
+    const size_t o_hw = a.bmat("ctc_head.weight", V, d), o_hb = a.bvec("ctc_head.bias", V);
+    // ---- upload
+    a.upload(c->arena, c->farena);
+    bf16_t* A = c->arena.p;
+    float* F = c->farena.p;
+    auto P = [&](size_t off) { return off == npos ? (bf16_t*)nullptr : A + off; };
+    c->window = F + o_win; c->tw_cos = F + o_twc; c->tw_sin = F + o_tws; c->fb = F + o_fb; c->rope_cos = F + o_rc; c->rope_sin = F + o_rs;
+    c->fbr.alloc(2 * mels);
+    HIP_CHECK(hipMemcpy(c->fbr.p, ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
+    c->fb_range = c->fbr.p;
+    c->d0w = A + o_d0w; c->d0b = A + o_d0b; c->c0w = A + o_c0w; c->c0b = A + o_c0b; c->c1w = A + o_c1w; c->c1b = A + o_c1b;
+    c->d1w = A + o_d1w; c->d1b = A + o_d1b; c->onw = A + o_onw; c->onb = A + o_onb; c->headw = A + o_hw; c->headb = A + o_hb;
+    c->layers.resize(c->L);
+    for (int li = 0; li < c->L; ++li) {
+        const Off& o = lo[li];
+        LsLayer& l = c->layers[li];
+        l.ln_ff1w = P(o.v[0]); l.ln_ff1b = P(o.v[1]); l.ff1_w1 = P(o.v[2]); l.ff1_b1 = P(o.v[3]); l.ff1_w2 = P(o.v[4]); l.ff1_b2 = P(o.v[5]);
+        l.ln_attw = P(o.v[6]); l.ln_attb = P(o.v[7]); l.wqkv = P(o.v[8]); l.bqkv = P(o.v[9]); l.wo = P(o.v[10]); l.bo = P(o.v[11]);
+        l.ln_cvw = P(o.v[12]); l.ln_cvb = P(o.v[13]); l.pw1 = P(o.v[14]); l.pw1b = P(o.v[15]); l.pw2 = P(o.v[16]); l.pw2b = P(o.v[17]);
+        l.dw = F + o.dw; l.dwshift = F + o.sh;
+        l.ln_ff2w = P(o.v[18]); l.ln_ff2b = P(o.v[19]); l.ff2_w1 = P(o.v[20]); l.ff2_b1 = P(o.v[21]); l.ff2_w2 = P(o.v[22]); l.ff2_b2 = P(o.v[23]);
+        l.ln_outw = P(o.v[24]); l.ln_outb = P(o.v[25]);
+    }
+    // ---- the workspace: every buffer a call touches, for max_batch rows of max_seconds
+    const size_t B = c->cfg.max_batch, Fc = c->Fcap, T1c = c->T1cap, M = B * c->T2cap;
+    c->pcm.alloc(B * c->maxN); c->melraw.alloc(B * Fc * mels); c->feats.alloc(B * Fc * mels); c->logits.alloc(M * V);
+    c->cntN.alloc(B); c->cntF.alloc(B); c->cnt1.alloc(B); c->cnt2.alloc(B); c->pred.alloc(M); c->tokens.alloc(M); c->ntok.alloc(B);
+    c->x0.alloc(B * Fc * Kp); c->h0.alloc(B * Fc * d); c->col.alloc(B * T1c * ks * d); c->c0.alloc(B * T1c * d); c->c1.alloc(M * cc);
+    c->h.alloc(M * d); c->x.alloc(M * d); c->qkv.alloc(M * NQ); c->att.alloc(M * d); c->ff.alloc(M * std::max<size_t>(f, 2 * d));
+    c->enc_out.alloc(M * d);
+    c->host_tokens.alloc(M + B);
+    c->raw.clear();
+    c->finalized = true;
+    MIS_API_END
+}
+
+// mis-synth-v1 weights (benches): every key of LasrCTCModel, amplitudes as the other engines' synthetic models
+extern "C" mis_status mis_lasr_init_synthetic(mis_lasr* c, uint64_t seed) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
+    SynthWeights sw{c->raw, seed * 100000ull};
+    const int64_t d = c->d, f = c->f, cc = c->cc, ks = c->ks, ck = c->ck;
+    const bool ab = c->cfg.attention_bias != 0, cb = c->cfg.convolution_bias != 0;
+    const std::string S = "encoder.subsampler.";
+    sw.lin(S + "dense_0", d, c->mels, true, 1.0);
+    sw.put(S + "conv_0.weight", {d, ks, d}, sqrt(3.0 / (double)(ks * d)), 0.0f); sw.put(S + "conv_0.bias", {d}, 0.05, 0.0f);
+    sw.put(S + "conv_1.weight", {cc, ks, d}, sqrt(3.0 / (double)(ks * d)), 0.0f); sw.put(S + "conv_1.bias", {cc}, 0.05, 0.0f);
+    sw.lin(S + "dense_1", d, cc, true, 1.0);
+    for (int li = 0; li < c->L; ++li) {
+        const std::string q = "encoder.layers." + std::to_string(li) + ".";
+        for (const char* n : {"norm_feed_forward1", "norm_self_att", "norm_conv", "norm_feed_forward2", "norm_out"}) sw.norm(q + n, d);
+        for (const char* n : {"feed_forward1", "feed_forward2"}) {
+            sw.lin(q + n + ".linear1", f, d, ab, 1.0); sw.lin(q + n + ".linear2", d, f, ab, 0.5);
+        }
+        sw.lin(q + "self_attn.q_proj", d, d, ab, 1.0); sw.lin(q + "self_attn.k_proj", (int64_t)c->Hk * LS_HD, d, ab, 1.0);
+        sw.lin(q + "self_attn.v_proj", (int64_t)c->Hk * LS_HD, d, ab, 1.0); sw.lin(q + "self_attn.o_proj", d, d, ab, 0.5);
+        sw.put(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, sqrt(3.0 / (double)d), 0.0f);
+        sw.put(q + "conv.pointwise_conv2.weight", {d, 1, d}, 0.5 * sqrt(3.0 / (double)d), 0.0f);
+        sw.put(q + "conv.depthwise_conv.weight", {d, ck, 1}, sqrt(3.0 / (double)ck), 0.0f);
+        if (cb) {
+            sw.put(q + "conv.pointwise_conv1.bias", {2 * d}, 0.05, 0.0f); sw.put(q + "conv.pointwise_conv2.bias", {d}, 0.05, 0.0f);
+            sw.put(q + "conv.depthwise_conv.bias", {d}, 0.05, 0.0f);
+        }
+        sw.put(q + "conv.norm.weight", {d}, 0.1, 1.0f); sw.put(q + "conv.norm.bias", {d}, 0.05, 0.0f);
+        sw.put(q + "conv.norm.running_mean", {d}, 0.05, 0.0f); sw.put(q + "conv.norm.running_var", {d}, 0.1, 1.0f);
+    }
+    sw.norm("encoder.out_norm", d);
+    sw.lin("ctc_head", c->V, d, true, 1.0);
+    MIS_API_END
+}
+
+// ============================================================================ front end
+// One frame of one row: samples t 160 - 256 .. + 511 of the zero-centred, pre-emphasised waveform (x[0] kept, y[i] = x[i] - 0.97 x[i-1];
+// skipped for n <= 1), window, 512-point radix-2 FFT in LDS, |.|^2, slaney filters over each filter's own bins, log(. + 2^-24).
+__global__ void __launch_bounds__(256) k_lasr_stft_mel(const float* __restrict__ pcm, int64_t stride, const int* __restrict__ N,
+                                                       const int* __restrict__ F, const float* __restrict__ window,
+                                                       const float* __restrict__ twc, const float* __restrict__ tws,
+                                                       const float* __restrict__ fb, const int* __restrict__ fbr, float* __restrict__ out,
+                                                       int Fp, int mels) {
+    __shared__ float re[LS_NFFT], im[LS_NFFT];
+    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    float* o = out + ((size_t)b * Fp + t) * mels;
+    if (t >= F[b]) { if (tid < mels) o[tid] = 0.0f; return; }
+    const int n = N[b];
+    const float* x = pcm + (size_t)b * stride;
+    for (int j = tid; j < LS_NFFT; j += 256) {
+        const float w = window[j];
+        const int64_t s = (int64_t)t * LS_HOP - LS_NFFT / 2 + j;
+        float v = 0.0f;
+        if (w != 0.0f && s >= 0 && s < n) v = (s == 0 || n <= 1) ? x[s] : __fsub_rn(x[s], __fmul_rn(0.97f, x[s - 1]));
+        const int r = (int)(__brev((unsigned)j) >> 23);
+        re[r] = __fmul_rn(v, w); im[r] = 0.0f;
+    }
+    __syncthreads();
+    for (int half = 1; half < LS_NFFT; half <<= 1) {
+        const int k = tid & (half - 1), i0 = ((tid - k) << 1) + k, i1 = i0 + half, ti = k * (LS_NFFT / 2 / half);
+        const float c = twc[ti], s = tws[ti];
+        const float xr = re[i1], xi = im[i1];
+        const float pr = xr * c - xi * s, pi = xr * s + xi * c;
+        const float ar = re[i0], ai = im[i0];
+        re[i0] = ar + pr; im[i0] = ai + pi; re[i1] = ar - pr; im[i1] = ai - pi;
+        __syncthreads();
+    }
+    for (int j = tid; j < LS_BINS; j += 256) { const float a = re[j], c = im[j]; re[j] = a * a + c * c; }
+    __syncthreads();
+    if (tid < mels) {
+        float acc = 0.0f;
+        for (int i = fbr[2 * tid]; i < fbr[2 * tid + 1]; ++i) acc = fmaf(re[i], fb[(size_t)i * mels + tid], acc);
+        o[tid] = logf(acc + 5.9604644775390625e-08f);
+    }
+}
+
+// per_feature normalisation (ParakeetAudio.swift:47-53): per mel bin, mean and unbiased variance (divisor max(F - 1, 1)) over the row's
+// own F frames in two passes, (x - mean) / (sqrt(var) + 1e-5); zeros behind F[b].  A thread owns one bin and every fourth frame; the
+// four partial sums are added in a fixed order, so a row's statistics depend on nothing but the row.
+__global__ void __launch_bounds__(256) k_lasr_norm(const float* __restrict__ raw, const int* __restrict__ F, float* __restrict__ out, int Fp,
+                                                   int mels) {
+    __shared__ float part[4][64];
+    const int b = blockIdx.y, ml = threadIdx.x & 63, fl = threadIdx.x >> 6, m = blockIdx.x * 64 + ml, n = F[b];
+    const bool live = m < mels;
+    const float* x = raw + (size_t)b * Fp * mels + (live ? m : 0);
+    float s = 0.0f;
+    for (int t = fl; t < n; t += 4) s += x[(size_t)t * mels];
+    part[fl][ml] = s;
+    __syncthreads();
+    const float mean = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)n;
+    __syncthreads();
+    float q = 0.0f;
+    for (int t = fl; t < n; t += 4) { const float v = x[(size_t)t * mels] - mean; q = fmaf(v, v, q); }
+    part[fl][ml] = q;
+    __syncthreads();
+    const float var = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)max(n - 1, 1);
+    const float den = sqrtf(var) + 1e-5f;
+    if (!live) return;
+    float* y = out + (size_t)b * Fp * mels + m;
+    for (int t = fl; t < Fp; t += 4) y[(size_t)t * mels] = t < n ? (x[(size_t)t * mels] - mean) / den : 0.0f;
+}
+
+// f32 features [B][Fp][mels] -> bf16 rows [B Fp][Kp] (the single rounding of the front end), zero behind F[b] and in the padding columns
+__global__ void __launch_bounds__(256) k_lasr_pack(const float* __restrict__ feats, const int* __restrict__ F, bf16_t* __restrict__ out, int Fp,
+                                                   int mels, int Kp, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t row = i / Kp;
+    const int k = (int)(i - row * Kp), b = (int)(row / Fp), t = (int)(row - (size_t)b * Fp);
+    out[i] = (k < mels && t < F[b]) ? f32_to_bf16(feats[row * mels + k]) : (bf16_t)0;
+}
+
+// ============================================================================ stem patches
+// out[(b Tout + t)][k C + c] = in[(b Tin + t s + k)][c] for t < cnt[b], zero behind it; eight values a thread
+__global__ void __launch_bounds__(256) k_lasr_im2col(const bf16_t* __restrict__ in, bf16_t* __restrict__ out, const int* __restrict__ cnt, int Tin,
+                                                     int Tout, int C, int ks, int st, size_t total8) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total8) return;
+    const int C8 = C >> 3;
+    const int c8 = (int)(i % C8);
+    size_t r = i / C8;
+    const int k = (int)(r % ks);
+    r /= ks;
+    const int t = (int)(r % Tout), b = (int)(r / Tout);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (t < cnt[b]) v = *reinterpret_cast<const uint4*>(in + ((size_t)b * Tin + (size_t)t * st + k) * C + c8 * 8);
+    reinterpret_cast<uint4*>(out)[i] = v;
+}
+
+// ============================================================================ GEMM
+// C[m][n] = sum_k X[m][k] W[n][k]: 2 x 2 waves, a wave holds TI x TI MFMA tiles (block tile 32 TI squared), BK = 32, the next k-slab in
+// registers while this one is multiplied.  One MFMA per 32 k in ascending order whatever TI: both tile sizes give the same bits.
+// Epilogues, v = T(acc + bias): LG_BIAS v; LG_RELU T(max(v, 0)); LG_SILU T(v sigmoid(v)); LG_AXPBY T(a R + b v) (R may be C);
+// LG_F32 acc + bias unrounded, f32, any N.  cnt != null: rows m with m % Tp >= cnt[m / Tp] are written as zero.
+enum { LG_BIAS = 0, LG_RELU = 1, LG_SILU = 2, LG_AXPBY = 3, LG_F32 = 4 };
+struct LasrGemm {
+    const bf16_t *X, *W, *bias, *R;
+    void* C;
+    int M, N, K, ldx;
+    float a, b;
+    const int* cnt;
+    int Tp;
+};
+#define LG_LD 40
+template <int EPI, int TI>
+__global__ void __launch_bounds__(256) k_lasr_gemm(LasrGemm p) {
+    constexpr int BT = 32 * TI, NCH = TI / 2;
+    __shared__ __attribute__((aligned(16))) bf16_t Ws[BT][LG_LD];
+    __shared__ __attribute__((aligned(16))) bf16_t Xs[BT][LG_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.x * BT, m0 = blockIdx.y * BT;
+    const int wn = wave >> 1, wm = wave & 1;
+    f32x4_t acc[TI][TI];
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < TI; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    const int r0 = tid >> 2, c0 = (tid & 3) * 8;
+    uint4 wreg[NCH], xreg[NCH];
+    auto load = [&](int k0) {
+#pragma unroll
+        for (int h = 0; h < NCH; ++h) {
+            const int row = r0 + 64 * h, n = n0 + row, m = m0 + row;
+            wreg[h] = (n < p.N) ? *reinterpret_cast<const uint4*>(p.W + (size_t)n * p.K + k0 + c0) : make_uint4(0, 0, 0, 0);
+            xreg[h] = (m < p.M) ? *reinterpret_cast<const uint4*>(p.X + (size_t)m * p.ldx + k0 + c0) : make_uint4(0, 0, 0, 0);
+        }
+    };
+    load(0);
+    for (int k0 = 0; k0 < p.K; k0 += 32) {
+        __syncthreads();
+#pragma unroll
+        for (int h = 0; h < NCH; ++h) {
+            *reinterpret_cast<uint4*>(&Ws[r0 + 64 * h][c0]) = wreg[h];
+            *reinterpret_cast<uint4*>(&Xs[r0 + 64 * h][c0]) = xreg[h];
+        }
+        __syncthreads();
+        if (k0 + 32 < p.K) load(k0 + 32);
+        bf16x8_t af[TI], bfr[TI];
+#pragma unroll
+        for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(&Ws[wn * 16 * TI + i * 16 + (lane & 15)][(lane >> 4) * 8]);
+#pragma unroll
+        for (int j = 0; j < TI; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(&Xs[wm * 16 * TI + j * 16 + (lane & 15)][(lane >> 4) * 8]);
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < TI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+    // C/D lane l, register e: n = 4 (l >> 4) + e (A rows), m = l & 15 (B columns)
+#pragma unroll
+    for (int i = 0; i < TI; ++i) {
+        const int n = n0 + wn * 16 * TI + i * 16 + (lane >> 4) * 4;
+        if (n >= p.N) continue;
+        float bv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (p.bias) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bv[e] = (n + e < p.N) ? bf16_to_f32(p.bias[n + e]) : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < TI; ++j) {
+            const int m = m0 + wm * 16 * TI + j * 16 + (lane & 15);
+            if (m >= p.M) continue;
+            const bool valid = !p.cnt || (m % p.Tp) < p.cnt[m / p.Tp];
+            if (EPI == LG_F32) {
+                float* o = static_cast<float*>(p.C) + (size_t)m * p.N + n;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (n + e < p.N) o[e] = valid ? acc[i][j][e] + bv[e] : 0.0f;
+                continue;
+            }
+            float rv[4] = {0.f, 0.f, 0.f, 0.f};
+            if (EPI == LG_AXPBY) {
+                const uint2 rq = *reinterpret_cast<const uint2*>(p.R + (size_t)m * p.N + n);
+                rv[0] = __uint_as_float(rq.x << 16); rv[1] = __uint_as_float(rq.x & 0xffff0000u);
+                rv[2] = __uint_as_float(rq.y << 16); rv[3] = __uint_as_float(rq.y & 0xffff0000u);
+            }
+            uint16_t res[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = bf16_round_f32(acc[i][j][e] + bv[e]);
+                if (EPI == LG_RELU) v = fmaxf(v, 0.0f);
+                if (EPI == LG_SILU) v = v / (1.0f + __expf(-v));
+                if (EPI == LG_AXPBY) v = fmaf(p.a, rv[e], p.b * v);
+                res[e] = valid ? f32_to_bf16(v) : (uint16_t)0;
+            }
+            uint2 v;
+            v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
+            v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
+            *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p.C) + (size_t)m * p.N + n) = v;      // (N % 4 == 0 for every bf16 output)
+        }
+    }
+}
+template <int EPI>
+static void ls_gemm_epi(mis_lasr* c, const LasrGemm& p) {
+    // the 128 x 128 tile once its grid fills the chip, the 64 x 64 tile (four times the blocks) below that
+    if ((long)cdiv(p.N, 128) * cdiv(p.M, 128) >= 256) LS_LAUNCH(c, (k_lasr_gemm<EPI, 4>), dim3(cdiv(p.N, 128), cdiv(p.M, 128)), dim3(256), p);
+    else LS_LAUNCH(c, (k_lasr_gemm<EPI, 2>), dim3(cdiv(p.N, 64), cdiv(p.M, 64)), dim3(256), p);
+}
+static void ls_gemm(mis_lasr* c, int epi, const bf16_t* X, int ldx, const bf16_t* W, const bf16_t* bias, void* C, int M, int N, int K,
+                    const bf16_t* R = nullptr, float ra = 0.0f, float rb = 0.0f, const int* cnt = nullptr, int Tp = 1) {
+    MIS_REQUIRE(K % 32 == 0 && ldx % 8 == 0 && (epi == LG_F32 || N % 4 == 0) && M >= 1, MIS_ERR_GENERATION_FAILED, "LASR GEMM: unsupported shape");
+    const LasrGemm p{X, W, bias, R, C, M, N, K, ldx, ra, rb, cnt, Tp};
+    switch (epi) {
+        case LG_BIAS: ls_gemm_epi<LG_BIAS>(c, p); break;
+        case LG_RELU: ls_gemm_epi<LG_RELU>(c, p); break;
+        case LG_SILU: ls_gemm_epi<LG_SILU>(c, p); break;
+        case LG_AXPBY: ls_gemm_epi<LG_AXPBY>(c, p); break;
+        case LG_F32: ls_gemm_epi<LG_F32>(c, p); break;
+        default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown LASR GEMM epilogue");
+    }
+}
+
+// ============================================================================ LayerNorm
+// y = T((x - mean) rstd w + b), f32 statistics in two passes, one wave per row; cnt != null: rows behind the row count are zero
+__global__ void __launch_bounds__(256) k_lasr_ln(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, const bf16_t* __restrict__ w,
+                                                 const bf16_t* __restrict__ bias, int d, float eps, int M, const int* __restrict__ cnt, int Tp) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const int d2 = d >> 1;
+    const uint32_t* xr = reinterpret_cast<const uint32_t*>(x + (size_t)row * d);
+    uint32_t* yr = reinterpret_cast<uint32_t*>(y + (size_t)row * d);
+    if (cnt && (row % Tp) >= cnt[row / Tp]) {
+        for (int i = lane; i < d2; i += 64) yr[i] = 0u;
+        return;
+    }
+    float s = 0.0f;
+    for (int i = lane; i < d2; i += 64) { const uint32_t u = xr[i]; s += __uint_as_float(u << 16) + __uint_as_float(u & 0xffff0000u); }
+    const float mean = wave_sum(s) / (float)d;
+    float q = 0.0f;
+    for (int i = lane; i < d2; i += 64) {
+        const uint32_t u = xr[i];
+        const float a = __uint_as_float(u << 16) - mean, b = __uint_as_float(u & 0xffff0000u) - mean;
+        q += a * a + b * b;
+    }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
+    const uint32_t* wr = reinterpret_cast<const uint32_t*>(w);
+    const uint32_t* br = reinterpret_cast<const uint32_t*>(bias);
+    for (int i = lane; i < d2; i += 64) {
+        const uint32_t u = xr[i], wu = wr[i], bu = br[i];
+        const float a = (__uint_as_float(u << 16) - mean) * rstd * __uint_as_float(wu << 16) + __uint_as_float(bu << 16);
+        const float b = (__uint_as_float(u & 0xffff0000u) - mean) * rstd * __uint_as_float(wu & 0xffff0000u) + __uint_as_float(bu & 0xffff0000u);
+        yr[i] = (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16);
+    }
+}
+
+// ============================================================================ attention
+// rotate-half RoPE over the whole head (:16-21,110-111): column i < 32 pairs with i + 32; T(x cos + rotate_half(x) sin) in f32 with one
+// rounding.  Heads 0 .. nheads - 1 of 64 columns from column 0 (q heads, then k heads) of rows [M][ld], position m % Tp, in place.
+__global__ void __launch_bounds__(256) k_lasr_rope(bf16_t* __restrict__ rows, int ld, int nheads, int Tp, const float* __restrict__ cs,
+                                                   const float* __restrict__ sn, size_t M) {
+    const int lane = threadIdx.x & 63;
+    const size_t item = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= M * nheads) return;
+    const size_t m = item / nheads;
+    const int h = (int)(item - m * nheads), pos = (int)(m % Tp);
+    bf16_t* p = rows + m * ld + h * LS_HD + lane;
+    const float x = bf16_to_f32(*p), partner = __shfl_xor(x, 32, 64);
+    const float c = cs[(size_t)pos * 32 + (lane & 31)], s = sn[(size_t)pos * 32 + (lane & 31)];
+    *p = f32_to_bf16(fmaf(x, c, (lane < 32 ? -partner : partner) * s));
+}
+
+// Non-causal attention over the row's own n = cnt[b] keys (:121-127).  grid (ceil(Tp / 64), H, B), 4 waves x 16 queries.  A 32-key tile
+// of the head's K and V columns of the q|k|v rows goes through LDS once per block (keys >= n are staged as ZERO, whatever the rows hold
+// there): K in row order, V transposed, so that both MFMA operands are single 16-byte LDS reads.  S^T = K Q^T with the K rows taken in
+// the order (0-3, 8-11, 16-19, 24-27 | 4-7, ...), which leaves lane (query j, group g) with the scores of keys 8 g .. 8 g + 7 - the A
+// operand of O += P V as it stands.  Online softmax in f32; P as bf16 hi + lo.  Queries >= n are written as zero.
+__global__ void __launch_bounds__(256) k_lasr_attn(const bf16_t* __restrict__ qkv, int ld, int H, int Hkv, const int* __restrict__ cnt, int Tp,
+                                                   float scale, bf16_t* __restrict__ out, int ldo) {
+    __shared__ __attribute__((aligned(16))) bf16_t ks[32][72];
+    __shared__ __attribute__((aligned(16))) bf16_t vt[LS_HD][40];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.z, h = blockIdx.y, hk = h / (H / Hkv), q0 = blockIdx.x * 64, n = min(cnt[b], Tp);
+    const size_t rowbase = (size_t)b * Tp;
+    if (q0 >= n) {                                                 // (uniform over the block)
+        for (int i = tid; i < 64 * LS_HD; i += 256) {
+            const int t = q0 + (i >> 6);
+            if (t < Tp) out[(rowbase + t) * ldo + h * LS_HD + (i & 63)] = 0;
+        }
+        return;
+    }
+    const int j = lane & 15, g4 = lane >> 4, t0 = q0 + wave * 16, tq = t0 + j;
+    bf16x8_t qf[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        if (tq < n) qf[c] = *reinterpret_cast<const bf16x8_t*>(qkv + (rowbase + tq) * ld + h * LS_HD + c * 32 + g4 * 8);
+        else qf[c] = (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    const bf16_t* Kg = qkv + rowbase * ld + (size_t)(H + hk) * LS_HD;
+    const bf16_t* Vg = qkv + rowbase * ld + (size_t)(H + Hkv + hk) * LS_HD;
+    const int sr = tid >> 3, sc8 = (tid & 7) * 8;                  // staging: key sr of the tile, columns sc8 .. + 8
+    const int pr0 = ((j >> 2) << 3) | (j & 3);
+    f32x4_t O[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) O[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.0f;
+    const int n_tiles = (n + 31) >> 5;
+    for (int tile = 0; tile < n_tiles; ++tile) {
+        const int kb = tile * 32;
+        __syncthreads();                                          // the previous tile's reads are done
+        {
+            const int key = kb + sr;
+            uint4 kv = make_uint4(0, 0, 0, 0), vv = kv;
+            if (key < n) {
+                kv = *reinterpret_cast<const uint4*>(Kg + (size_t)key * ld + sc8);
+                vv = *reinterpret_cast<const uint4*>(Vg + (size_t)key * ld + sc8);
+            }
+            *reinterpret_cast<uint4*>(&ks[sr][sc8]) = kv;
+            const uint32_t w[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { vt[sc8 + 2 * e][sr] = (bf16_t)(w[e] & 0xffffu); vt[sc8 + 2 * e + 1][sr] = (bf16_t)(w[e] >> 16); }
+        }
+        __syncthreads();
+        f32x4_t S0 = (f32x4_t){0.f, 0.f, 0.f, 0.f}, S1 = S0;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(&ks[pr0][c * 32 + g4 * 8]);
+            const bf16x8_t a1 = *reinterpret_cast<const bf16x8_t*>(&ks[pr0 | 4][c * 32 + g4 * 8]);
+            S0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[c], S0, 0, 0, 0);
+            S1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[c], S1, 0, 0, 0);
+        }
+        float sc[8], mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float v = (e < 4 ? S0[e] : S1[e - 4]) * scale;
+            v = (kb + g4 * 8 + e < n) ? v : -INFINITY;
+            sc[e] = v;
+            mx = fmaxf(mx, v);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);                     // finite: every tile holds a key < n
+        const float alpha = __expf(m_run - m_new);
+        float psum = 0.0f;
+        bf16x8_t ph, pl;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float pe = __expf(sc[e] - m_new);
+            psum += pe;
+            const bf16_t hi = f32_to_bf16(pe);
+            const bf16_t lo = f32_to_bf16(pe - bf16_to_f32(hi));
+            ph[e] = (short)hi;
+            pl[e] = (short)lo;
+        }
+        l_run = l_run * alpha + psum;
+        m_run = m_new;
+        float ar[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ar[r] = __shfl(alpha, g4 * 4 + r, 64);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x8_t vb = *reinterpret_cast<const bf16x8_t*>(&vt[dt * 16 + j][g4 * 8]);
+            f32x4_t o = O[dt];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] *= ar[r];
+            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vb, o, 0, 0, 0);
+            o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, vb, o, 0, 0, 0);
+            O[dt] = o;
+        }
+    }
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    // O[dt][r]: query 4 g + r, column 16 dt + j; the query's normaliser lives in lane 4 g + r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float lr = __shfl(l_run, g4 * 4 + r, 64);
+        const int tr = t0 + g4 * 4 + r;
+        if (tr < Tp) {
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                out[(rowbase + tr) * ldo + h * LS_HD + dt * 16 + j] = tr < n ? f32_to_bf16(O[dt][r] / lr) : (bf16_t)0;
+        }
+    }
+}
+
+// ============================================================================ conv module
+// pw [M][2C] (pointwise_conv1) -> out [M][C]: g = T(a sigmoid(b)) (a the first C columns, b the last, :172-173), zero padding of
+// (k - 1) / 2 frames in front and k - 1 - (k - 1) / 2 behind the row's own n = cnt[b] frames (:174), depthwise conv with the BatchNorm
+// folded in (taps [k][C], shift [C], f32), activation, one rounding.  A block is 64 output frames x 64 channels of one row: the tile's
+// 64 + k - 1 gated frames sit in LDS as f32; a wave is 16 frames, a lane a channel.
+template <int ACT>
+__global__ void __launch_bounds__(256) k_lasr_glu_dwconv(const bf16_t* __restrict__ pw, const float* __restrict__ taps,
+                                                         const float* __restrict__ shift, const int* __restrict__ cnt, bf16_t* __restrict__ out,
+                                                         int Tp, int C, int k) {
+    __shared__ float g[LS_DW_TT + LS_DW_MAXK - 1][64];
+    const int cl = threadIdx.x & 63, tl = threadIdx.x >> 6, ch = blockIdx.y * 64 + cl, b = blockIdx.z, t0 = blockIdx.x * LS_DW_TT;
+    const int n = min(cnt[b], Tp), padl = (k - 1) >> 1;
+    const bool live = ch < C;
+    const size_t rowbase = (size_t)b * Tp;
+    for (int r = tl; r < LS_DW_TT + k - 1; r += 4) {
+        const int t = t0 - padl + r;
+        float v = 0.0f;
+        if (live && t >= 0 && t < n) {
+            const bf16_t* row = pw + (rowbase + t) * 2 * C;
+            const float a = bf16_to_f32(row[ch]), gate = bf16_to_f32(row[C + ch]);
+            v = bf16_round_f32(a / (1.0f + __expf(-gate)));
+        }
+        g[r][cl] = v;
+    }
+    __syncthreads();
+    if (!live) return;
+    float acc[16];
+    const float sh = shift[ch];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = sh;
+    for (int kk = 0; kk < k; ++kk) {
+        const float w = taps[(size_t)kk * C + ch];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = fmaf(w, g[tl * 16 + i + kk][cl], acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int t = t0 + tl * 16 + i;
+        if (t >= Tp) continue;
+        float v = acc[i];
+        v = ACT == 1 ? fmaxf(v, 0.0f) : v / (1.0f + __expf(-v));
+        out[(rowbase + t) * C + ch] = t < n ? f32_to_bf16(v) : (bf16_t)0;
+    }
+}
+
+// ============================================================================ CTC tail
+// arg-max of a frame's V logits, lowest index on ties (MLX argMax); one wave per frame
+__global__ void __launch_bounds__(256) k_lasr_argmax(const float* __restrict__ logits, int V, int M, int* __restrict__ pred) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const float* x = logits + (size_t)row * V;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i = lane; i < V; i += 64) {
+        const float v = x[i];
+        if (v > best || (v == best && i < idx)) { best = v; idx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if (lane == 0) pred[row] = (idx < 0 || idx >= V) ? 0 : idx;    // (a frame of NaNs: no comparison holds)
+}
+// greedy CTC (Wav2Vec2CTC.swift:520-542): frame t < cnt[b] emits its token when it differs from frame t - 1's (-1 in front of frame 0)
+// and is not the blank; the kept tokens are compacted in frame order into tokens[b][0 .. ntok[b]).  One block per row.
+__global__ void __launch_bounds__(256) k_lasr_collapse(const int* __restrict__ pred, const int* __restrict__ cnt, int Tp, int blank,
+                                                       int* __restrict__ tokens, int* __restrict__ ntok) {
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = min(cnt[b], Tp);
+    const int* p = pred + (size_t)b * Tp;
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int t = c0 + tid;
+        int tok = 0;
+        bool keep = false;
+        if (t < n) { tok = p[t]; keep = tok != blank && tok != (t > 0 ? p[t - 1] : -1); }
+        const unsigned long long mask = __ballot(keep);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(mask);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        if (keep) tokens[(size_t)b * Tp + off + before] = tok;
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid == 0) ntok[b] = base;
+}
+
+// ============================================================================ the chain
+static void ls_check_ready(const mis_lasr* c, int batch) {
+    MIS_REQUIRE(c->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
+    MIS_REQUIRE(batch >= 1 && batch <= c->cfg.max_batch, MIS_ERR_INVALID_INPUT, "batch %d outside 1..%d (max_batch)", batch, c->cfg.max_batch);
+}
+// frame counts of every row from its feature frames; need_stem: rejects a row the stem cannot take (the front end alone takes any row)
+static void ls_set_frames(mis_lasr* c, const std::vector<int>& F, int Fp, bool need_stem) {
+    const int B = (int)F.size();
+    std::vector<int> t1(B), t2(B);
+    int Fmax = 0;
+    for (int b = 0; b < B; ++b) {
+        MIS_REQUIRE(F[b] >= 0 && F[b] <= Fp, MIS_ERR_INVALID_INPUT, "row %d: %d frames exceed the row stride %d", b, F[b], Fp);
+        t1[b] = ls_conv_out(F[b], c->ks, c->st); t2[b] = ls_conv_out(t1[b], c->ks, c->st);
+        MIS_REQUIRE(!need_stem || t2[b] >= 1, MIS_ERR_INVALID_INPUT, "row %d: %d feature frames are too short for the conv stem (kernel %d, stride %d)", b, F[b],
+                    c->ks, c->st);
+        Fmax = std::max(Fmax, F[b]);
+    }
+    MIS_REQUIRE(Fp <= c->Fcap, MIS_ERR_INVALID_INPUT, "%d feature frames exceed the workspace of %d (max_seconds %d)", Fp, c->Fcap, c->cfg.max_seconds);
+    c->hF = F; c->hT1 = t1; c->hT2 = t2;
+    c->batch = B; c->Fp = Fp; c->T1p = ls_conv_out(Fp, c->ks, c->st); c->T2p = ls_conv_out(c->T1p, c->ks, c->st);
+    hipStream_t s = c->stream;
+    HIP_CHECK(hipMemcpyAsync(c->cntF.p, c->hF.data(), B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->cnt1.p, c->hT1.data(), B * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->cnt2.p, c->hT2.data(), B * 4, hipMemcpyHostToDevice, s));
+}
+
+// pcm f32 [B][stride] (host or device) -> c->feats [B][Fp][mels]
+static void ls_front(mis_lasr* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, bool need_stem) {
+    MIS_REQUIRE(stride >= 1, MIS_ERR_INVALID_INPUT, "bad stride");
+    std::vector<int> N(batch), F(batch);
+    int Fp = 0;
+    for (int b = 0; b < batch; ++b) {
+        const int64_t n = lens ? lens[b] : stride;
+        MIS_REQUIRE(n >= 0 && n <= stride, MIS_ERR_INVALID_INPUT, "row %d: %lld samples exceed the row stride %lld", b, (long long)n, (long long)stride);
+        MIS_REQUIRE(n <= c->maxN, MIS_ERR_INVALID_INPUT, "row %d: %lld samples exceed the workspace of %d seconds (max_seconds)", b, (long long)n,
+                    c->cfg.max_seconds);
+        N[b] = (int)n; F[b] = ls_frames(n);
+        Fp = std::max(Fp, F[b]);
+    }
+    ls_set_frames(c, F, Fp, need_stem);
+    c->hN = N;
+    hipStream_t s = c->stream;
+    HIP_CHECK(hipMemcpyAsync(c->cntN.p, c->hN.data(), batch * 4, hipMemcpyHostToDevice, s));
+    // the rows are packed at the workspace's own stride: only a row's own samples travel
+    const int64_t ws = std::min<int64_t>(stride, c->maxN);
+    HIP_CHECK(hipMemcpy2DAsync(c->pcm.p, ws * 4, pcm, stride * 4, ws * 4, batch, hipMemcpyDefault, s));
+    if (c->timed) HIP_CHECK(hipEventRecord(c->ev[0], s));
+    LS_LAUNCH(c, k_lasr_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF.p, c->window, c->tw_cos, c->tw_sin, c->fb,
+              c->fb_range, c->melraw.p, Fp, c->mels);
+    LS_LAUNCH(c, k_lasr_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF.p, c->feats.p, Fp, c->mels);
+}
+
+// c->feats -> stem -> blocks -> out_norm (c->enc_out).  stop: -1 everything, 0 behind the stem, 1 .. L behind that block.
+static void ls_encoder(mis_lasr* c, int stop) {
+    const int B = c->batch, d = c->d, f = c->f, Fp = c->Fp, T1p = c->T1p, T2p = c->T2p, ks = c->ks, st = c->st, M = B * T2p;
+    const int NQ = (c->H + 2 * c->Hk) * LS_HD;
+    const int act = c->cfg.hidden_act == 1 ? LG_RELU : LG_SILU;
+    const float eps = c->cfg.layer_norm_eps, ffa = c->cfg.feed_forward_residual_weights[0], ffb = c->cfg.feed_forward_residual_weights[1],
+                cva = c->cfg.conv_residual_weights[0], cvb = c->cfg.conv_residual_weights[1];
+    // ---- stem (:67-72)
+    const size_t n0 = (size_t)B * Fp * c->Kp;
+    LS_LAUNCH(c, k_lasr_pack, dim3((unsigned)((n0 + 255) / 256)), dim3(256), c->feats.p, c->cntF.p, c->x0.p, Fp, c->mels, c->Kp, n0);
+    ls_gemm(c, LG_RELU, c->x0.p, c->Kp, c->d0w, c->d0b, c->h0.p, B * Fp, d, c->Kp);
+    size_t n8 = (size_t)B * T1p * ks * d / 8;
+    LS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->h0.p, c->col.p, c->cnt1.p, Fp, T1p, d, ks, st, n8);
+    ls_gemm(c, LG_RELU, c->col.p, ks * d, c->c0w, c->c0b, c->c0.p, B * T1p, d, ks * d);
+    n8 = (size_t)B * T2p * ks * d / 8;
+    LS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->c0.p, c->col.p, c->cnt2.p, T1p, T2p, d, ks, st, n8);
+    ls_gemm(c, LG_RELU, c->col.p, ks * d, c->c1w, c->c1b, c->c1.p, M, c->cc, ks * d);
+    ls_gemm(c, LG_BIAS, c->c1.p, c->cc, c->d1w, c->d1b, c->h.p, M, d, c->cc, nullptr, 0.0f, 0.0f, c->cnt2.p, T2p);
+    if (stop == 0) return;
+    // ---- blocks (:226-245), 16 launches each
+    const float scale = 1.0f / sqrtf((float)LS_HD);
+    auto ln = [&](const bf16_t* x, bf16_t* y, const bf16_t* w, const bf16_t* b, const int* cnt) {
+        LS_LAUNCH(c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), x, y, w, b, d, eps, M, cnt, T2p);
+    };
+    for (int li = 0; li < c->L; ++li) {
+        const LsLayer& l = c->layers[li];
+        ln(c->h.p, c->x.p, l.ln_ff1w, l.ln_ff1b, nullptr);
+        ls_gemm(c, act, c->x.p, d, l.ff1_w1, l.ff1_b1, c->ff.p, M, f, d);
+        ls_gemm(c, LG_AXPBY, c->ff.p, f, l.ff1_w2, l.ff1_b2, c->h.p, M, d, f, c->h.p, ffa, ffb);
+        ln(c->h.p, c->x.p, l.ln_attw, l.ln_attb, nullptr);
+        ls_gemm(c, LG_BIAS, c->x.p, d, l.wqkv, l.bqkv, c->qkv.p, M, NQ, d);
+        const size_t items = (size_t)M * (c->H + c->Hk);
+        LS_LAUNCH(c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), c->qkv.p, NQ, c->H + c->Hk, T2p, c->rope_cos, c->rope_sin, (size_t)M);
+        LS_LAUNCH(c, k_lasr_attn, dim3(cdiv(T2p, 64), c->H, B), dim3(256), c->qkv.p, NQ, c->H, c->Hk, c->cnt2.p, T2p, scale, c->att.p, d);
+        ls_gemm(c, LG_AXPBY, c->att.p, d, l.wo, l.bo, c->h.p, M, d, d, c->h.p, 1.0f, 1.0f);
+        ln(c->h.p, c->x.p, l.ln_cvw, l.ln_cvb, nullptr);
+        ls_gemm(c, LG_BIAS, c->x.p, d, l.pw1, l.pw1b, c->ff.p, M, 2 * d, d);
+        if (c->cfg.hidden_act == 1)
+            LS_LAUNCH(c, (k_lasr_glu_dwconv<1>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
+        else
+            LS_LAUNCH(c, (k_lasr_glu_dwconv<0>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
+        ls_gemm(c, LG_AXPBY, c->att.p, d, l.pw2, l.pw2b, c->h.p, M, d, d, c->h.p, cva, cvb);
+        ln(c->h.p, c->x.p, l.ln_ff2w, l.ln_ff2b, nullptr);
+        ls_gemm(c, act, c->x.p, d, l.ff2_w1, l.ff2_b1, c->ff.p, M, f, d);
+        ls_gemm(c, LG_AXPBY, c->ff.p, f, l.ff2_w2, l.ff2_b2, c->x.p, M, d, f, c->h.p, ffa, ffb);
+        ln(c->x.p, c->h.p, l.ln_outw, l.ln_outb, c->cnt2.p);
+        if (stop == li + 1) return;
+    }
+    ln(c->h.p, c->enc_out.p, c->onw, c->onb, c->cnt2.p);
+}
+
+static void ls_head(mis_lasr* c) {
+    ls_gemm(c, LG_F32, c->enc_out.p, c->d, c->headw, c->headb, c->logits.p, c->batch * c->T2p, c->V, c->d, nullptr, 0.0f, 0.0f, c->cnt2.p, c->T2p);
+}
+
+extern "C" int mis_lasr_launches(const mis_lasr* c) { return c ? c->launches : 0; }
+
+// copies [B][Tp][W] f32 device rows into out [B][Tp][W]
+static void ls_copy_out(mis_lasr* c, const float* dev, float* out, size_t n) {
+    HIP_CHECK(hipMemcpyAsync(out, dev, n * 4, hipMemcpyDeviceToHost, c->stream));
+}
+
+extern "C" mis_status mis_lasr_features(mis_lasr* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* feats_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm && feats_out, MIS_ERR_INVALID_INPUT, "null argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    ls_check_ready(c, batch);
+    c->launches = 0;
+    ls_front(c, pcm, lens, batch, stride, false);
+    ls_copy_out(c, c->feats.p, feats_out, (size_t)batch * c->Fp * c->mels);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_lasr_forward_features(mis_lasr* c, const float* feats, const int32_t* frames, int batch, int F, float* logits_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && feats && logits_out, MIS_ERR_INVALID_INPUT, "null argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    ls_check_ready(c, batch);
+    MIS_REQUIRE(F >= 1, MIS_ERR_INVALID_INPUT, "bad frame count");
+    std::vector<int> fr(batch, F);
+    if (frames) for (int b = 0; b < batch; ++b) fr[b] = frames[b];
+    c->launches = 0;
+    ls_set_frames(c, fr, F, true);
+    HIP_CHECK(hipMemcpyAsync(c->feats.p, feats, (size_t)batch * F * c->mels * 4, hipMemcpyDefault, c->stream));
+    ls_encoder(c, -1);
+    ls_head(c);
+    ls_copy_out(c, c->logits.p, logits_out, (size_t)batch * c->T2p * c->V);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_lasr_forward(mis_lasr* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* logits_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm && logits_out, MIS_ERR_INVALID_INPUT, "null argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    ls_check_ready(c, batch);
+    c->launches = 0;
+    ls_front(c, pcm, lens, batch, stride, true);
+    ls_encoder(c, -1);
+    ls_head(c);
+    ls_copy_out(c, c->logits.p, logits_out, (size_t)batch * c->T2p * c->V);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_stt_lasr_generate(mis_lasr* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, int32_t* tokens_out,
+                                            int64_t tokens_stride, int32_t* n_tokens) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && pcm && tokens_out && n_tokens && tokens_stride >= 1, MIS_ERR_INVALID_INPUT, "null argument");
+    HIP_CHECK(hipSetDevice(c->device));
+    ls_check_ready(c, batch);
+    c->launches = 0;
+    hipStream_t s = c->stream;
+    ls_front(c, pcm, lens, batch, stride, true);
+    if (c->timed) HIP_CHECK(hipEventRecord(c->ev[1], s));
+    ls_encoder(c, -1);
+    if (c->timed) HIP_CHECK(hipEventRecord(c->ev[2], s));
+    ls_head(c);
+    const int M = batch * c->T2p;
+    LS_LAUNCH(c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), c->logits.p, c->V, M, c->pred.p);
+    LS_LAUNCH(c, k_lasr_collapse, dim3(batch), dim3(256), c->pred.p, c->cnt2.p, c->T2p, c->cfg.pad_token_id, c->tokens.p, c->ntok.p);
+    if (c->timed) HIP_CHECK(hipEventRecord(c->ev[3], s));
+    int32_t* ht = c->host_tokens.p;
+    HIP_CHECK(hipMemcpyAsync(ht, c->tokens.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(ht + M, c->ntok.p, batch * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));                            // the call's one synchronisation
+    for (int b = 0; b < batch; ++b) {
+        const int n = (int)std::min<int64_t>(ht[M + b], tokens_stride);
+        n_tokens[b] = n;
+        memcpy(tokens_out + (size_t)b * tokens_stride, ht + (size_t)b * c->T2p, (size_t)n * 4);
+    }
+    MIS_API_END
+}
+
+// tensors of the last call, f32 [B][T2p][d], zero rows behind a row's own T2: stage 0 the stem's output, 1 .. L that block's output,
+// L + 1 out_norm.  The chain is deterministic and the call's features are still in the workspace: stages 0 .. L are recomputed from
+// them (the same bits as the call produced), out_norm is read where the call left it.
+extern "C" mis_status mis_lasr_tap(mis_lasr* c, int stage, float* out, int64_t capacity, int64_t* dims) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c && dims, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(c->finalized && c->batch > 0, MIS_ERR_NOT_INITIALIZED, "no call to tap");
+    MIS_REQUIRE(stage >= 0 && stage <= c->L + 1, MIS_ERR_INVALID_INPUT, "stage %d outside 0..%d", stage, c->L + 1);
+    HIP_CHECK(hipSetDevice(c->device));
+    dims[0] = c->batch; dims[1] = c->T2p; dims[2] = c->d;
+    if (!out) return MIS_OK;
+    const size_t n = (size_t)c->batch * c->T2p * c->d;
+    MIS_REQUIRE((int64_t)n <= capacity, MIS_ERR_INVALID_INPUT, "output capacity too small");
+    const int kept = c->launches;
+    if (stage <= c->L) ls_encoder(c, stage);
+    c->launches = kept;
+    const bf16_t* src = stage <= c->L ? c->h.p : c->enc_out.p;
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    std::vector<bf16_t> hostv(n);
+    HIP_CHECK(hipMemcpy(hostv.data(), src, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = bf16_to_f32(hostv[i]);
+    MIS_API_END
+}
+
+// benches: device milliseconds of the next / last mis_stt_lasr_generate: front end, encoder, tail
+extern "C" mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c, MIS_ERR_INVALID_INPUT, "null argument");
+    if (!ms) { c->timed = true; return MIS_OK; }
+    MIS_REQUIRE(c->timed && c->batch > 0, MIS_ERR_NOT_INITIALIZED, "no timed generate");
+    for (int i = 0; i < 3; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    MIS_API_END
+}
