@@ -978,6 +978,61 @@ mis_status mis_stt_lasr_generate(mis_lasr*, const float* pcm, const int64_t* len
 mis_status mis_lasr_tap(mis_lasr*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * FSMN voice activity detection (Sources/MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift): mono rows of differing lengths at the model's
+ * sample rate, 1..max_batch a call, of ANY length.  Row b of n_b samples has T_b = 1 + (n_b - win) / hop fbank frames (0 below one
+ * window; win / hop = sample_rate x frame_length / frame_shift / 1000) and R_b = (T_b + (lfr_m - 1) / 2 + lfr_n - 1) / lfr_n LFR rows.
+ * Front end: x 32768, minus the frame mean, pre-emphasis 0.97 with the frame's first sample kept, symmetric Hamming, 512-point power
+ * spectrum, HTK triangles from 20 Hz to Nyquist (unnormalised, none on the Nyquist bin), log max(., 1e-8); per frame also
+ * decibel = 10 log10(sum x^2 + 1e-6) of the raw samples.  LFR row o, slot i = fbank frame clamp(o lfr_n + i - (lfr_m - 1) / 2, 0, T - 1);
+ * (x + shift) scale when cmvn.shift / cmvn.scale of input_dim values are loaded.  Encoder: in_linear1, ReLU(in_linear2), fsmn_layers x
+ * {linear, p + depthwise causal conv of lorder taps, ReLU(affine)}, out_linear1, softmax(out_linear2).  All of it exact f32.
+ * The encoder is causal with a reach of fsmn_layers (lorder - 1) rows: a call walks the LFR rows in chunks of chunk_frames, recomputing
+ * that halo, inside one workspace sized at finalize for max_batch rows of chunk_frames (+ halo) - a call allocates nothing and
+ * synchronises once.  A row's result does not depend on the batch it travels in, on what lies behind lens[b], or on chunk_frames:
+ * bit for bit.  The serial post-processing that turns the two per-frame floats into segments is host work (vad.py).
+ * Rejected with MIS_ERR_INVALID_INPUT at create: lstride != 1, lfr_n > lfr_m, input_dim != n_mels x lfr_m, a window outside 257..512
+ * samples, output_dim > 256, sizes outside the ranges the messages name; at finalize a tensor missing or misshapen; at a call batch
+ * outside 1..max_batch, a row longer than stride, too little room in an output, a null pointer, a handle that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_fsmn_vad mis_fsmn_vad;
+/* FSMNVADEncoderConfig + the front-end fields of FSMNVADConfig + sil_pdf_ids (the first n_sil entries) + the sizes of the workspace */
+typedef struct {
+    int32_t input_dim, input_affine_dim, fsmn_layers, linear_dim, proj_dim, lorder, rorder, lstride, rstride, output_affine_dim, output_dim;
+    int32_t sample_rate, n_mels, frame_length, frame_shift, lfr_m, lfr_n;
+    int32_t n_sil, sil_pdf_ids[16];
+    int32_t max_batch, chunk_frames;     /* 1..64 rows a call; LFR rows a chunk */
+} mis_fsmn_vad_config;
+mis_status mis_fsmn_vad_create(const mis_fsmn_vad_config*, int device, mis_fsmn_vad** out);
+/* names with the "encoder." prefix stripped: in_linear{1,2}.{weight,bias}, fsmn.N.linear.weight, fsmn.N.fsmn_block.conv_left.weight
+ * [proj, lorder, 1], fsmn.N.affine.{weight,bias}, out_linear{1,2}.{weight,bias}; optional cmvn.shift / cmvn.scale (ignored unless both
+ * hold input_dim values, as the reference ignores them); host pointers.  finalize names a missing weight and checks every shape. */
+mis_status mis_fsmn_vad_set_tensor(mis_fsmn_vad*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_fsmn_vad_init_synthetic(mis_fsmn_vad*, uint64_t seed);
+mis_status mis_fsmn_vad_finalize(mis_fsmn_vad*);
+void       mis_fsmn_vad_destroy(mis_fsmn_vad*);
+/* kernel launches of the last call: 5 + 2 fsmn_layers per chunk from pcm (13 at the published depth), one less from features */
+int        mis_fsmn_vad_launches(const mis_fsmn_vad*);
+/* T_b and R_b of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_fsmn_vad_frames(const mis_fsmn_vad*, const int64_t* lens, int batch, int32_t* frames_out, int32_t* rows_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> LFR + CMVN features f32 [batch, rows, input_dim]; rows >= the longest row's
+ * R_b, zeros behind a row's own.  A batch of rows below one window launches nothing and writes nothing. */
+mis_status mis_fsmn_vad_features(mis_fsmn_vad*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* features_out,
+                                 int rows);
+/* FSMNVAD.callAsFunction on given features f32 [batch, rows, input_dim], counts[batch] valid rows each (NULL = rows) -> scores f32
+ * [batch, rows, output_dim], zeros behind a row's own */
+mis_status mis_fsmn_vad_forward_features(mis_fsmn_vad*, const float* features, const int32_t* counts, int batch, int rows, float* scores_out);
+/* front end + encoder: scores f32 [batch, rows, output_dim] */
+mis_status mis_fsmn_vad_forward(mis_fsmn_vad*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* scores_out, int rows);
+/* what the post-processing reads: silence f32 [batch, rows] = the sum of the scores over sil_pdf_ids in their order, decibel f32
+ * [batch, frames]; rows >= the longest R_b, frames >= the longest T_b */
+mis_status mis_fsmn_vad_detect_raw(mis_fsmn_vad*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* silence_out,
+                                   int rows, float* decibel_out, int frames);
+/* tensors of the last chunk of the last call, f32, zeros behind a row's own rows.  stage 0 fbank [B, F, n_mels], 1 decibel [B, F, 1],
+ * 2 features [B, R, input_dim], 3 in_linear1, 4 in_linear2, 5 + 2 i layer i's projection, 6 + 2 i its output, 5 + 2 L out_linear1,
+ * 6 + 2 L scores, 7 + 2 L the silence sum [B, R, 1].  dims[3] receives B, rows, width; out NULL for the dims alone. */
+mis_status mis_fsmn_vad_tap(mis_fsmn_vad*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

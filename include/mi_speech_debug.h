@@ -233,6 +233,10 @@ mis_status mis_debug_ecapa_lid_timing(const mis_ecapa_lid* c, float* ms);
  * generate, ms[3] = front end, encoder, tail */
 mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms);
 
+/* csrc/fsmn_vad.hip, measurements: device milliseconds of the last call summed over its first 128 chunks, ms[2] = front end (copy in +
+ * fbank), encoder (+ copy out) */
+mis_status mis_debug_fsmn_vad_timing(const mis_fsmn_vad* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

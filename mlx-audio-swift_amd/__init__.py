@@ -18,6 +18,7 @@ the Swift shim a maintainer would add):
     moonshine.MoonshineModel <-> class MoonshineModel : STTGenerationModel (MLXAudioSTT/Models/Moonshine/MoonshineModel.swift)
     smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
     lid.EcapaTdnnLID         <-> class EcapaTdnn (spoken language identification)  (MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift)
+    vad.FSMNVAD              <-> class FSMNVAD (voice activity detection)  (MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -48,6 +49,9 @@ from .lid import (EcapaTdnnLID, EcapaTdnnConfig, LanguagePrediction, LIDOutput, 
                   ecapa_lid_expected_shapes, ecapa_lid_labels, ecapa_lid_read_directory)
 from .lasr import (LasrCTCModel, LasrCTCConfig, LasrEncoderConfig, SentencePieceTokenizer, lasr_sanitize, lasr_expected_keys,  # noqa: F401
                    greedy_ctc_tokens)
+from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitize, fsmn_vad_expected_shapes,  # noqa: F401
+                  fsmn_vad_check_weights, fsmn_vad_read_directory, fsmn_vad_read_cmvn, fsmn_vad_postprocess, parse_kaldi_cmvn,
+                  chunks_from_segments)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

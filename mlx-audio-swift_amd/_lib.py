@@ -160,6 +160,13 @@ class EcapaLidConfigC(C.Structure):
                 ("max_batch", C.c_int32), ("max_samples", C.c_int32)]
 
 
+class FsmnVadConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("input_dim", "input_affine_dim", "fsmn_layers", "linear_dim", "proj_dim", "lorder", "rorder",
+                                          "lstride", "rstride", "output_affine_dim", "output_dim", "sample_rate", "n_mels", "frame_length",
+                                          "frame_shift", "lfr_m", "lfr_n", "n_sil")]
+                + [("sil_pdf_ids", C.c_int32 * 16), ("max_batch", C.c_int32), ("chunk_frames", C.c_int32)])
+
+
 class LasrConfigC(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads",
                                           "intermediate_size", "hidden_act", "conv_kernel_size", "convolution_bias", "num_mel_bins",
@@ -313,6 +320,18 @@ SYMBOLS = {
     "mis_ecapa_lid_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, _P]),
     "mis_ecapa_lid_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mis_ecapa_lid_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_fsmn_vad_create": (C.c_int, [C.POINTER(FsmnVadConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_fsmn_vad_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_fsmn_vad_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_fsmn_vad_finalize": (C.c_int, [_P]),
+    "mis_fsmn_vad_destroy": (None, [_P]),
+    "mis_fsmn_vad_launches": (C.c_int, [_P]),
+    "mis_fsmn_vad_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_fsmn_vad_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
+    "mis_fsmn_vad_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_fsmn_vad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
+    "mis_fsmn_vad_detect_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int]),
+    "mis_fsmn_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_lasr_create": (C.c_int, [C.POINTER(LasrConfigC), C.c_int, C.POINTER(_P)]),
     "mis_lasr_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_lasr_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -458,6 +477,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
     "mis_debug_ecapa_lid_timing": (C.c_int, [_P, _P]),
     "mis_debug_lasr_timing": (C.c_int, [_P, _P]),
+    "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 
