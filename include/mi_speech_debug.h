@@ -184,6 +184,52 @@ mis_status mis_debug_whisper_embed_ln(int device, const uint16_t* emb, const uin
 mis_status mis_debug_whisper_suppress(int device, uint16_t* logits, int Vpad, int vocab, const int32_t* sup, int n_sup, const int32_t* bsup, int n_bsup,
                                       const int32_t* n_gen, const uint8_t* active, int batch);
 
+/* csrc/glue_debug.hip, tests (tests/test_gpu_glue_ops.py): ONE call of a launcher of the LM glue (csrc/lm_kernels.h) on caller-supplied host
+ * data; nothing is computed in the entry points.  16-bit operands and results are raw bf16 payloads (uint16).  Guards as above: every output
+ * lies between guard bands and is pre-filled with the byte 0xFF (0xFFFF in bf16, -1 as an integer), a changed guard byte fails the call with
+ * MIS_ERR_GENERATION_FAILED; every input is followed by NaN (ids: 0x7FFFFFFF; prompts and lens: zeros; bytes: 0xFF).  The entry points
+ * refuse (MIS_ERR_INVALID_INPUT) only what would make a KERNEL read or write outside these buffers; what a launcher refuses is returned as
+ * its status and nothing is launched.
+ *   lm_embed_rmsnorm: launch_embed_rmsnorm.  emb [vocab][d], ids, active, pos_cur, pos_next [batch] (the two position arrays go in and come
+ *     back), wnorm [d]; h_out [Mpad][d]; x_out the packed image (xpk layout) of Mpad round_up(d, 32) elements.
+ *     TOKEN IDS: an id outside 0 .. vocab - 1 is not part of any model's contract - every host entry point that takes ids (mis_tts_generate,
+ *     mis_lm_prefill, mis_lm_forward, the token engine) rejects it with MIS_ERR_INVALID_INPUT before a launch, so neither kernel meets one
+ *     in the product.  What the kernels do with one is therefore only a memory-safety rule, pinned as it is: k_embed_rmsnorm reads
+ *     embedding row 0 (as it does for the rows batch .. Mpad - 1), k_pf_embed_rmsnorm writes a zero row.
+ *   lm_glue: launch_reduce_residual_rmsnorm.  slabs f32 [S][Mpad][N]; h [Mpad][N] goes in and comes back; wnorm [N]; ln_bias [N] or NULL
+ *     (RMSNorm); x_out the packed image of Mpad round_up(N, 32) elements - the columns N .. of the last k-tile are never written (0xFFFF).
+ *     report (may be NULL) int32[4]: kernel (0 k_reduce_residual_rmsnorm, 1 k_glue4, 2 k_glue_cpt; -1 nothing launched), SG, CPT, threads per block.
+ *   gemm_skinny_norm: launch_gemm_skinny_norm at Mpad = 16.  W bf16 [N_out][K] row-major, packed by launch_pack_weight; slabs f32
+ *     [S_in][16][K]; h_in [16][K]; wnorm, ln_bias (NULL: RMSNorm) [K]; bias [N_out] or NULL.  out f32 as mis_debug_gemm_skinny returns it
+ *     (packed epilogues un-packed into [16][N_out]); h_out [16][K] is a buffer of its own, pre-filled: rows >= nrows stay 0xFFFF;
+ *     h_in_after (may be NULL) [16][K]: h_in as the launch left it.  report int32[5]: kernel (3 k_gemm_skinny_norm; -1 nothing launched),
+ *     epilogue, LN, SG, KW.  gemm_skinny_norm_ok: the launcher's capability check (1 / 0).
+ *   pf_rows: mode 0 launch_pf_embed_rmsnorm (table = emb [vocab][d], prompt [batch][Lmax] left padded, lens [batch]), 1 launch_pf_rows_rmsnorm
+ *     (table = rows [Lmax][src_rows][d]), 2 launch_pf_rmsnorm (h [Tc Mpad][d] -> x), 3 launch_pf_add_resid (h [n] += part [n]),
+ *     4 launch_pf_pack_rows (h [Mpad][d] -> x the packed image of Mpad round_up(d, 32) elements).  Modes 0 / 1 write h, x [Tc Mpad][d] and
+ *     pos_tab (int32), act_tab (uint8) [Tc Mpad] for the chunk t0 .. t0 + Tc - 1 (inside 0 .. Lmax; 0 <= lens <= Lmax).  h, x, pos_tab and
+ *     act_tab come back whole; arguments a mode does not use may be NULL / 0.
+ *   prefill_feed: launch_prefill_feed.  step_counter int32[1] goes in and comes back; ids_out int32 [batch], active_out uint8 [batch].
+ *   convert_to_bf16: launch_convert_to_bf16, src of dtype (mis_dtype) MIS_F32 / MIS_F16 / MIS_BF16, n elements.
+ *   dequant_affine: launch_dequant_affine.  wq uint32 [N][K bits / 32]; scales, biases [N][K / group] of sb_dtype MIS_F32 / MIS_F16 / MIS_BF16;
+ *     dst_out bf16 [N][K]. */
+mis_status mis_debug_lm_embed_rmsnorm(int device, const uint16_t* emb, const int32_t* ids, const uint8_t* active, int32_t* pos_cur, int32_t* pos_next,
+                                      const uint16_t* wnorm, int d, int vocab, float eps, int batch, int Mpad, uint16_t* h_out, uint16_t* x_out);
+mis_status mis_debug_lm_glue(int device, const float* slabs, int S, int Mpad, int N, uint16_t* h, const uint16_t* wnorm, const uint16_t* ln_bias,
+                             float eps, uint16_t* x_out, int32_t* report);
+int32_t mis_debug_gemm_skinny_norm_ok(int epi, int R, int KT, int S, int S_in, int Mpad, int nrows, int layer_norm);
+mis_status mis_debug_gemm_skinny_norm(int device, const uint16_t* W, const float* slabs, int S_in, const uint16_t* h_in, const uint16_t* wnorm,
+                                      const uint16_t* ln_bias, float eps, int nrows, int epi, int R, int S, const uint16_t* bias, int N_out, int K,
+                                      float* out, int64_t capacity, uint16_t* h_out, uint16_t* h_in_after, int32_t* report);
+mis_status mis_debug_pf_rows(int device, int mode, const uint16_t* table, const int32_t* prompt, const int32_t* lens, int Lmax, int t0, int Tc, int batch,
+                             int Mpad, int vocab, int src_rows, const uint16_t* wnorm, const float* part, int64_t n, int d, float eps, uint16_t* h,
+                             uint16_t* x, int32_t* pos_tab, uint8_t* act_tab);
+mis_status mis_debug_prefill_feed(int device, const int32_t* prompt, const int32_t* lens, int Lmax, int32_t* step_counter, int batch, int32_t* ids_out,
+                                  uint8_t* active_out);
+mis_status mis_debug_convert_to_bf16(int device, const void* src, int dtype, int64_t n, uint16_t* dst_out);
+mis_status mis_debug_dequant_affine(int device, const uint32_t* wq, const void* scales, const void* biases, int sb_dtype, int N, int K, int group, int bits,
+                                    uint16_t* dst_out);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

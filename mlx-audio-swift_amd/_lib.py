@@ -465,6 +465,16 @@ DEBUG_SYMBOLS = {
     "mis_debug_enc_attn_prefill": (C.c_int, [C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_whisper_embed_ln": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_whisper_suppress": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int]),
+    "mis_debug_lm_embed_rmsnorm": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_lm_glue": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P, _P]),
+    "mis_debug_gemm_skinny_norm_ok": (C.c_int32, [C.c_int] * 8),
+    "mis_debug_gemm_skinny_norm": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
+                                             _P, C.c_int64, _P, _P, _P]),
+    "mis_debug_pf_rows": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int64,
+                                    C.c_int, C.c_float, _P, _P, _P, _P]),
+    "mis_debug_prefill_feed": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P]),
+    "mis_debug_convert_to_bf16": (C.c_int, [C.c_int, _P, C.c_int, C.c_int64, _P]),
+    "mis_debug_dequant_affine": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_token_engine": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "mis_debug_whisper_weight_bytes": (C.c_int64, [_P]),
     "mis_debug_mimi_decoder_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),

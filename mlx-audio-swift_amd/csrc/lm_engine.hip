@@ -961,6 +961,12 @@ extern "C" mis_status mis_lm_forward_hidden(mis_tts* c, const int32_t* ids, cons
         for (int b = 0; b < c->batch; ++b)
             MIS_REQUIRE(!act[b] || pn[b] < c->Smax, MIS_ERR_INVALID_INPUT, "row %d exceeds max_context %d", b, c->Smax);
     }
+    {   // an id outside the vocabulary is rejected here, as in mis_lm_prefill / mis_tts_generate: k_embed_rmsnorm would read row 0 for it
+        std::vector<int32_t> hi(c->batch);
+        HIP_CHECK(hipMemcpy(hi.data(), ids, c->batch * 4, hipMemcpyDefault));
+        for (int b = 0; b < c->batch; ++b)
+            MIS_REQUIRE(!act[b] || (hi[b] >= 0 && hi[b] < c->V), MIS_ERR_INVALID_INPUT, "token %d of row %d outside the vocabulary", hi[b], b);
+    }
     HIP_CHECK(hipMemcpyAsync(c->ids.p, ids, c->batch * 4, hipMemcpyDefault, s));
     HIP_CHECK(hipMemcpyAsync(c->active.p, act.data(), c->batch, hipMemcpyHostToDevice, s));
     enqueue_layers(c);

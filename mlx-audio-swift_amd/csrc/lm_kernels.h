@@ -35,8 +35,10 @@ void launch_gemm_skinny(int epi, int R, int ksb, const bf16_t* Wp, const bf16_t*
                         int N_out, int Mpad, hipStream_t s, const bf16_t* bias = nullptr, int U = 0);
 // The same GEMM with the residual add + LayerNorm / RMSNorm glue in its prologue (<= 16 rows, K <= 1280; see k_gemm_skinny_norm): X is rebuilt per
 // block from the producer's S_in split-K slabs [S_in][16][K] and the residual stream h_in [16][K]; h_new is written to h_out (!= h_in).
-// ln_bias == nullptr: RMSNorm.  R = 2, eight waves per item.
-bool gemm_skinny_norm_ok(int epi, int R, int KT, int S, int S_in, int Mpad, int nrows);
+// ln_bias == nullptr: RMSNorm.  R = 2, eight waves per item.  gemm_skinny_norm_ok answers true for exactly the arrangements the launcher
+// instantiates (the GELU epilogue behind a LayerNorm, S = 1, S_in <= 8); everything else the launcher refuses with MIS_ERR_GENERATION_FAILED
+// before anything is launched.
+bool gemm_skinny_norm_ok(int epi, int R, int KT, int S, int S_in, int Mpad, int nrows, bool layer_norm = true);
 void launch_gemm_skinny_norm(int epi, int R, const bf16_t* Wp, const float* slabs, int S_in, const bf16_t* h_in, bf16_t* h_out, const bf16_t* wnorm,
                              const bf16_t* ln_bias, float eps, int nrows, void* out, int NT, int KT, int S, int N_out, int Mpad, hipStream_t s,
                              const bf16_t* bias = nullptr);
@@ -66,6 +68,12 @@ void launch_pf_pack_rows(const bf16_t* rows, bf16_t* xpk, int Mpad, int d, hipSt
 // kernel: 0 k_gemm_skinny, 1 k_gemm_skinny_q (streaming), 2 k_gemm_skinny_q1 (one-shot), 3 k_gemm_pf; -1 nothing launched yet
 struct GemmLaunchInfo { int kernel = -1, MT = 0, R = 0, epi = 0, ksb = 0, U = 0, bits = 0, sbt = 0; };
 extern thread_local GemmLaunchInfo g_gemm_last_launch;
+
+// the glue instantiation launch_reduce_residual_rmsnorm / launch_gemm_skinny_norm launched last on this thread (host bookkeeping only, as
+// g_gemm_last_launch): mis_debug_lm_glue and mis_debug_gemm_skinny_norm report it, so that tests/test_gpu_glue_ops.py can assert the dispatch.
+// kernel: 0 k_reduce_residual_rmsnorm<SG>, 1 k_glue4<SG, LN>, 2 k_glue_cpt<SG, CPT, LN>, 3 k_gemm_skinny_norm<2, epi, LN, SG, KW, 5>; -1 nothing yet
+struct GlueLaunchInfo { int kernel = -1, SG = 0, CPT = 0, threads = 0, epi = 0, LN = 0, KW = 0; };
+extern thread_local GlueLaunchInfo g_glue_last_launch;
 
 // split-K factor of a weight-streaming GEMM (items = n-tile groups, KT = k-tiles, ksb = waves per item), see the definition
 int gemm_choose_split(int items, int KT, int ksb, int s_max);

@@ -581,9 +581,12 @@ __global__ void __launch_bounds__(256) k_glue_cpt(const float* __restrict__ slab
         }
     }
 }
+thread_local GlueLaunchInfo g_glue_last_launch;
+
 template <int CPT, bool LN>
 static void launch_glue_cpt(const float* slabs, int S, int Mpad, int N, bf16_t* h, const bf16_t* wnorm, bf16_t* x, float eps, const bf16_t* ln_bias, hipStream_t s) {
     const int nth = N / (4 * CPT);
+    g_glue_last_launch = GlueLaunchInfo{2, S <= 2 ? 2 : S <= 4 ? 4 : 8, CPT, nth, 0, LN ? 1 : 0, 0};
     if (S <= 2) hipLaunchKernelGGL((k_glue_cpt<2, CPT, LN>), dim3(Mpad), dim3(nth), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
     else if (S <= 4) hipLaunchKernelGGL((k_glue_cpt<4, CPT, LN>), dim3(Mpad), dim3(nth), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
     else hipLaunchKernelGGL((k_glue_cpt<8, CPT, LN>), dim3(Mpad), dim3(nth), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
@@ -598,8 +601,10 @@ void launch_reduce_residual_rmsnorm(const float* slabs, int S, int Mpad, int N, 
     // c15_ab.json); every other width up to 4096 -> one group of four columns per thread (k_glue4); beyond that, or more than 8 slabs, the
     // general kernel.
     if (!ln_bias && N == 3072 && S <= 8) { launch_glue_cpt<3, false>(slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias, s); return; }
+    const int sg = S <= 2 ? 2 : S <= 4 ? 4 : 8;
     if (N % 4 == 0 && N / 4 <= 1024 && S <= 8) {
         const int nth = ((N / 4 + 63) / 64) * 64;
+        g_glue_last_launch = GlueLaunchInfo{1, sg, 1, nth, 0, ln_bias ? 1 : 0, 0};
         if (ln_bias) {
             if (S <= 2) hipLaunchKernelGGL((k_glue4<2, true>), dim3(Mpad), dim3(nth), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
             else if (S <= 4) hipLaunchKernelGGL((k_glue4<4, true>), dim3(Mpad), dim3(nth), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
@@ -611,6 +616,7 @@ void launch_reduce_residual_rmsnorm(const float* slabs, int S, int Mpad, int N, 
         }
         return;
     }
+    g_glue_last_launch = GlueLaunchInfo{0, sg, 0, RR_THREADS, 0, ln_bias ? 1 : 0, 0};
     if (S <= 2) hipLaunchKernelGGL((k_reduce_residual_rmsnorm<2>), dim3(Mpad), dim3(RR_THREADS), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
     else if (S <= 4) hipLaunchKernelGGL((k_reduce_residual_rmsnorm<4>), dim3(Mpad), dim3(RR_THREADS), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
     else hipLaunchKernelGGL((k_reduce_residual_rmsnorm<8>), dim3(Mpad), dim3(RR_THREADS), 0, s, slabs, S, Mpad, N, h, wnorm, x, eps, ln_bias);
@@ -1094,16 +1100,16 @@ __global__ void __launch_bounds__(512, 1) k_gemm_skinny_norm(const bf16_t* __res
     }
 }
 
-bool gemm_skinny_norm_ok(int epi, int R, int KT, int S, int S_in, int Mpad, int nrows) {
-    const int N = KT * 32;
-    return Mpad == 16 && nrows >= 1 && nrows <= 16 && R == 2 && (epi == EPI_PARTIAL || epi == EPI_GELU_PACKED) && N % 4 == 0 && N <= 1280 && S_in >= 1 &&
-           S_in <= 8 && S >= 1 && S <= KT && ((KT + S - 1) / S + 7) / 8 <= 5;
+bool gemm_skinny_norm_ok(int epi, int R, int KT, int S, int S_in, int Mpad, int nrows, bool layer_norm) {
+    // exactly what the launcher below instantiates: the GELU epilogue behind a LayerNorm, one K slice, up to 8 producer slabs, K <= 1280
+    // (five k-tiles per wave, five column groups per lane)
+    return Mpad == 16 && nrows >= 1 && nrows <= 16 && R == 2 && epi == EPI_GELU_PACKED && layer_norm && KT >= 1 && KT * 32 <= 1280 && S_in >= 1 &&
+           S_in <= 8 && S == 1;
 }
 void launch_gemm_skinny_norm(int epi, int R, const bf16_t* Wp, const float* slabs, int S_in, const bf16_t* h_in, bf16_t* h_out, const bf16_t* wnorm,
                              const bf16_t* ln_bias, float eps, int nrows, void* out, int NT, int KT, int S, int N_out, int Mpad, hipStream_t s,
                              const bf16_t* bias) {
-    MIS_REQUIRE(gemm_skinny_norm_ok(epi, R, KT, S, S_in, Mpad, nrows), MIS_ERR_GENERATION_FAILED, "unsupported norm-in-prologue GEMM shape");
-    MIS_REQUIRE(epi == EPI_PARTIAL || S == 1, MIS_ERR_GENERATION_FAILED, "split-K needs the partial epilogue");
+    MIS_REQUIRE(gemm_skinny_norm_ok(epi, R, KT, S, S_in, Mpad, nrows, ln_bias != nullptr), MIS_ERR_GENERATION_FAILED, "unsupported norm-in-prologue GEMM shape");
     const int n_items = ((NT + R - 1) / R) * S;
     const int len_max = (KT + S - 1) / S;                 // k-tiles of the longest block range
     const int kw = (len_max + 7) / 8;                     // k-tiles of the longest wave range
@@ -1111,6 +1117,7 @@ void launch_gemm_skinny_norm(int epi, int R, const bf16_t* Wp, const float* slab
     const bool ln = ln_bias != nullptr;
 #define GN_CASE(E, LNB, SGv, KWv)                                                                                                         \
     if (epi == E && ln == LNB && S_in <= SGv && kw <= KWv) {                                                                              \
+        g_glue_last_launch = GlueLaunchInfo{3, SGv, 0, 512, E, LNB ? 1 : 0, KWv};                                                         \
         hipLaunchKernelGGL((k_gemm_skinny_norm<2, E, LNB, SGv, KWv, 5>), dim3(n_items), dim3(512), lds, s, Wp, slabs, S_in, h_in, h_out, wnorm,  \
                            ln_bias, eps, nrows, out, NT, KT, S, n_items, N_out, bias);                                                    \
         return;                                                                                                                           \
