@@ -10,6 +10,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from ._handle import NativeHandle, _tensor_args  # noqa: F401  (other modules import _tensor_args from here)
 from .generation import AudioGenerationError, check
 
 
@@ -52,42 +53,18 @@ class SNACConfig:
         return c
 
 
-_NP_DTYPES = {np.dtype(np.float32): _lib.MIS_F32, np.dtype(np.float16): _lib.MIS_F16}
-
-
-def _tensor_args(arr):
-    """numpy / torch tensor -> (keepalive, data pointer, mis dtype, shape)."""
-    try:
-        import torch
-        if isinstance(arr, torch.Tensor):
-            t = arr.detach().contiguous()
-            if t.dtype == torch.bfloat16:
-                return t, t.data_ptr(), _lib.MIS_BF16, tuple(t.shape)
-            if t.dtype == torch.float16:
-                return t, t.data_ptr(), _lib.MIS_F16, tuple(t.shape)
-            t = t.to(torch.float32).contiguous()
-            return t, t.data_ptr(), _lib.MIS_F32, tuple(t.shape)
-    except ImportError:
-        pass
-    a = np.ascontiguousarray(arr)
-    if a.dtype not in _NP_DTYPES:
-        a = a.astype(np.float32)
-    return a, a.ctypes.data, _NP_DTYPES[a.dtype], a.shape
-
-
-class SNAC:
+class SNAC(NativeHandle):
     """AudioCodecModel conformance (AudioCodecModel.swift:15-27): codec_sample_rate, encode_audio (SNACDecoder.swift:120-125, on
     mis_snac_encode; a handle loaded without encoder tensors raises audioEncodingFailed), decode_audio."""
+
+    _prefix = "mis_snac"
 
     def __init__(self, config: SNACConfig, device: int = 0, _handle=None):
         self.config = config
         self.device = device
         self._h = _handle
         if self._h is None:
-            h = C.c_void_p()
-            cfg = config.to_c()
-            check(_lib.lib().mis_snac_create(C.byref(cfg), device, C.byref(h)))
-            self._h = h
+            self._create(config.to_c(), device)
         self.sampling_rate = config.sampling_rate
         self.hop_length = int(np.prod(config.encoder_rates))
 
@@ -115,14 +92,6 @@ class SNAC:
             m.set_tensor(name, arr)                  # "encoder.*" / "*.in_proj.*" enable the encode path when present
         m.finalize()
         return m
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_snac_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_snac_finalize(self._h))
 
     def set_noise(self, null_noise_is_zero: bool, seed: int = 0):
         check(_lib.lib().mis_snac_set_noise(self._h, 1 if null_noise_is_zero else 0, seed))
@@ -201,17 +170,6 @@ class SNAC:
         check(_lib.lib().mis_snac_debug_tap(self._h, name.encode(), buf.ctypes.data, cap, C.byref(ch), C.byref(ln)))
         return buf[: batch * ch.value * ln.value].reshape(batch, ch.value, ln.value).copy()
 
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_snac_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 @dataclass
 class DescriptDACConfig:
@@ -235,29 +193,22 @@ class DescriptDACConfig:
                                self.n_codebooks, self.codebook_size, self.codebook_dim, self.sample_rate)
 
 
-class DescriptDAC:
+class DescriptDAC(NativeHandle):
     """class DescriptDAC (Descript/DescriptDAC.swift:172-245,334-352): preprocess / encode / encode_audio / decode_from_codes /
     decode_audio.  The encoder needs the checkpoint's encoder.* and in_proj tensors (error 5 otherwise)."""
 
+    _prefix = "mis_dac"
+
     def __init__(self, config: DescriptDACConfig, device: int = 0):
         self.config = config
-        self._h = C.c_void_p()
-        cc = config.to_c()
-        check(_lib.lib().mis_dac_create(C.byref(cc), device, C.byref(self._h)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _lib.lib().mis_dac_destroy(h)
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0) -> "DescriptDAC":
         m = cls(config, device)
         for k, v in weights.items():
-            keep, ptr, dt, shape = _tensor_args(v)
-            sh = (C.c_int64 * len(shape))(*shape)
-            check(_lib.lib().mis_dac_set_tensor(m._h, k.encode(), ptr, dt, sh, len(shape)))
-        check(_lib.lib().mis_dac_finalize(m._h))
+            m.set_tensor(k, v)
+        m.finalize()
         return m
 
     @property
@@ -384,29 +335,22 @@ class EncodecConfig:
                                    1 if self.norm_type == "time_group_norm" else 0)
 
 
-class Encodec:
+class Encodec(NativeHandle):
     """Decode side of class Encodec (Encodec/Encodec.swift:179-398): decode(audio_codes, audio_scales); the 24 kHz (mono, causal,
     plain convs) and the 48 kHz (stereo, non-causal, GroupNorm) model families."""
 
+    _prefix = "mis_encodec"
+
     def __init__(self, config: EncodecConfig, device: int = 0):
         self.config = config
-        self._h = C.c_void_p()
-        cc = config.to_c()
-        check(_lib.lib().mis_encodec_create(C.byref(cc), device, C.byref(self._h)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _lib.lib().mis_encodec_destroy(h)
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0) -> "Encodec":
         m = cls(config, device)
         for k, v in weights.items():
-            keep, ptr, dt, shape = _tensor_args(v)
-            sh = (C.c_int64 * len(shape))(*shape)
-            check(_lib.lib().mis_encodec_set_tensor(m._h, k.encode(), ptr, dt, sh, len(shape)))
-        check(_lib.lib().mis_encodec_finalize(m._h))
+            m.set_tensor(k, v)
+        m.finalize()
         return m
 
     @property
@@ -565,28 +509,16 @@ def mimi_sanitize(key: str, arr):
     return k, v
 
 
-class Mimi:
+class Mimi(NativeHandle):
     """extension Mimi: AudioCodecModel (Mimi.swift:426-437): codec_sample_rate, frame_rate, encode / encode_audio, decode /
     decode_audio; loaders from_weights (post-sanitize names), from_model_directory / from_pretrained (raw Kyutai safetensors through
     mimi_sanitize; local directories only) and synthetic.  Weights are computed in float32 whatever their stored dtype."""
 
+    _prefix = "mis_mimi"
+
     def __init__(self, config: MimiConfig | None = None, device: int = 0):
         self.config = config or MimiConfig()
-        self._h = C.c_void_p()
-        cc = self.config.to_c()
-        check(_lib.lib().mis_mimi_create(C.byref(cc), device, C.byref(self._h)))
-
-    def close(self):
-        """Release the handle now: its stream, device buffers and the encoder (otherwise at garbage collection)."""
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _lib.lib().mis_mimi_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                                # interpreter shutdown
-            pass
+        self._create(self.config.to_c(), device)
 
     # -- loading -----------------------------------------------------------------------------------
     @classmethod
@@ -594,7 +526,7 @@ class Mimi:
         m = cls(config, device)
         for k, v in weights.items():
             m.set_tensor(k, v)
-        check(_lib.lib().mis_mimi_finalize(m._h))
+        m.finalize()
         return m
 
     @classmethod
@@ -611,7 +543,7 @@ class Mimi:
                 if isinstance(v, np.ndarray):
                     continue                                             # integer bookkeeping tensors
                 m.set_tensor(*mimi_sanitize(k, v))
-        check(_lib.lib().mis_mimi_finalize(m._h))
+        m.finalize()
         return m
 
     @classmethod
@@ -626,11 +558,6 @@ class Mimi:
         from .synthetic import mimi_synthetic_weights
         config = config or MimiConfig()
         return cls.from_weights(config, mimi_synthetic_weights(config, seed), device)
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_mimi_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
 
     # -- AudioCodecModel -----------------------------------------------------------------------------
     @property

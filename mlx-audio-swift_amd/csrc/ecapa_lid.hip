@@ -24,6 +24,7 @@
 //   k_lid_asp_pool  softmax over the valid frames, weighted mean, sqrt(max(sum a x^2 - mean^2, 1e-9)) (EcapaTdnnBackbone.swift:275-280)
 //   k_lid_tail / k_lid_head   asp_bn + fc; LeakyReLU -> BN -> Linear -> LeakyReLU -> BN -> Linear -> log-softmax -> top-k by rank
 //
+// The block-wide maximum and sum of k_lid_clamp and k_lid_head are common.h's block_max_256 / block_sum_256.
 // The Res2Net chain runs as scale - 1 launches of k_lid_gemm per block (chunk 0 is stored twice by tdnn1's epilogue): 49 launches a call
 // at the published depth.  No allocation and no synchronisation between the copy in and the copy out.
 #include "common.h"
@@ -133,22 +134,6 @@ __global__ void __launch_bounds__(256) k_lid_gemm(LidGemm p) {
     }
 }
 
-// sums / maxima over the block's 256 threads in a fixed order; every thread gets the result.  `red` holds 4 floats.
-__device__ __forceinline__ float lid_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float lid_block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // mel [B][Ts][nm] in place: floor at (the row's maximum over t < T_b and all mels) - 80; one block per row
 __global__ void __launch_bounds__(256) k_lid_clamp(float* __restrict__ mel, const int32_t* __restrict__ T, int Ts, int nm) {
     __shared__ float red[4];
@@ -156,7 +141,7 @@ __global__ void __launch_bounds__(256) k_lid_clamp(float* __restrict__ mel, cons
     float* row = mel + (size_t)b * Ts * nm;
     float mx = -INFINITY;
     for (int i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, row[i]);
-    mx = lid_block_max(mx, red);
+    mx = block_max_256(mx, red);
     const float floor_db = mx - 80.0f;
     for (int i = threadIdx.x; i < n; i += 256) row[i] = fmaxf(row[i], floor_db);
 }
@@ -339,10 +324,10 @@ __global__ void __launch_bounds__(256) k_lid_head(LidHead p) {
     __syncthreads();
     float mx = -INFINITY;
     for (int n = threadIdx.x; n < p.N; n += 256) mx = fmaxf(mx, lg[n]);
-    mx = lid_block_max(mx, red);
+    mx = block_max_256(mx, red);
     float s = 0.0f;
     for (int n = threadIdx.x; n < p.N; n += 256) s += expf(lg[n] - mx);
-    s = lid_block_sum(s, red);
+    s = block_sum_256(s, red);
     const float lse = mx + logf(s);
     for (int n = threadIdx.x; n < p.N; n += 256) { const float v = lg[n] - lse; lg[n] = v; p.logp[(size_t)b * p.N + n] = v; }
     __syncthreads();

@@ -15,7 +15,7 @@
 //
 //   k_fvad_fbank   one frame per block: x 32768, minus the frame mean, pre-emphasis 0.97 with the first sample kept (:838-843), symmetric
 //                  Hamming, 512-point radix-2 FFT in LDS, power, the sparse HTK triangles (each filter over its own bins, the Nyquist
-//                  bin never read), log max(., 1e-8); and the frame's 10 log10(sum x^2 + 1e-6) over the raw samples
+//                  bin never read), log max(., 1e-8); and the frame's 10 log10(sum x^2 + 1e-6) over the raw samples (block_sum_256)
 //   k_fvad_lfr     the stacked, CMVN-ed features as a tensor (features / tap only: the forward pass gathers them in in_linear1's load)
 //   k_fvad_gemm    the one contraction, exact f32 on v_mfma_f32_32x32x2_f32, every dimension guarded.  Loads: activations, the LFR + CMVN
 //                  gather from the fbank, or the memory block p + depthwise_causal_conv(p) formed from a time tile + lorder - 1 rows of
@@ -24,6 +24,7 @@
 // A chunk is 5 + 2 fsmn_layers launches (13 at the published depth): fbank, in_linear1 (LFR load), in_linear2, per layer linear and
 // affine (memory-block load), out_linear1, out_linear2 + softmax.  No allocation and one synchronisation per call.
 #include "common.h"
+#include "audio_front.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -63,15 +64,6 @@ __device__ __forceinline__ float fv_lfr_value(const FvLfr& q, const FvGeom& g, i
     return v;
 }
 
-// sums over the block's 256 threads in a fixed order; every thread gets the result.  `red` holds 4 floats.
-__device__ __forceinline__ float fv_block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 struct FvFront {
     const float* pcm; int64_t pcm_stride;                   // the chunk's samples: [B][pcm_stride], sample 0 is frame fa's first
     const float *win, *twc, *tws, *fb; const int32_t* fbr;  // window [wlen], twiddles [256], filters [256][nm], bin range per filter
@@ -91,8 +83,8 @@ __global__ void __launch_bounds__(256) k_fvad_fbank(FvFront p) {
     const float* x = p.pcm + (size_t)b * p.pcm_stride + (size_t)f * p.hop;
     const float v0 = tid < p.wlen ? x[tid] : 0.0f, v1 = tid + 256 < p.wlen ? x[tid + 256] : 0.0f;
     const float s0 = v0 * 32768.0f, s1 = v1 * 32768.0f;
-    const float energy = fv_block_sum(fmaf(v1, v1, v0 * v0), red);
-    const float mean = fv_block_sum(s0 + s1, red) / (float)p.wlen;
+    const float energy = block_sum_256(fmaf(v1, v1, v0 * v0), red);
+    const float mean = block_sum_256(s0 + s1, red) / (float)p.wlen;
     im[tid] = s0 - mean; im[tid + 256] = s1 - mean;
     __syncthreads();
     for (int j = tid; j < FV_NFFT; j += 256) {
@@ -396,26 +388,20 @@ extern "C" mis_status mis_fsmn_vad_finalize(mis_fsmn_vad* c) {
     const size_t o_win = a.ftake(c->wlen), o_twc = a.ftake(FV_NFFT / 2), o_tws = a.ftake(FV_NFFT / 2), o_fb = a.ftake((size_t)FV_BINS * nm);
     const double PI = 3.14159265358979323846;
     for (int i = 0; i < c->wlen; ++i) fh[o_win + i] = (float)(0.54 - 0.46 * cos(2.0 * PI * i / (double)(c->wlen - 1)));
-    for (int i = 0; i < FV_NFFT / 2; ++i) {
-        fh[o_twc + i] = (float)cos(2.0 * PI * i / FV_NFFT);
-        fh[o_tws + i] = (float)-sin(2.0 * PI * i / FV_NFFT);
-    }
+    fft512_twiddles(&fh[o_twc], &fh[o_tws]);
     std::vector<int32_t> ih((size_t)round_up(2 * nm, 64) + 64, 0);
     {
         const float nyquist = 0.5f * (float)c->cfg.sample_rate, width = (float)c->cfg.sample_rate / (float)FV_NFFT;
         const float mel_low = fv_kaldi_mel(20.0f), mel_high = fv_kaldi_mel(0.0f + nyquist), delta = (mel_high - mel_low) / (float)(nm + 1);
         for (int j = 0; j < nm; ++j) {
             const float left = mel_low + (float)j * delta, center = mel_low + (float)(j + 1) * delta, right = mel_low + (float)(j + 2) * delta;
-            int lo = FV_BINS, hi = 0;
             for (int i = 0; i < FV_BINS; ++i) {
                 const float mel = fv_kaldi_mel(width * (float)i);
                 const float up = (mel - left) / (center - left), down = (right - mel) / (right - center);
-                const float v = std::max(0.0f, std::min(up, down));
-                fh[o_fb + (size_t)i * nm + j] = v;
-                if (v != 0.0f) { lo = std::min(lo, i); hi = std::max(hi, i + 1); }
+                fh[o_fb + (size_t)i * nm + j] = std::max(0.0f, std::min(up, down));
             }
-            ih[2 * j] = lo < hi ? lo : 0; ih[2 * j + 1] = lo < hi ? hi : 0;
         }
+        filter_bin_ranges(&fh[o_fb], FV_BINS, (int)nm, ih.data());
     }
     const size_t o_sil = round_up(2 * nm, 64);
     for (int i = 0; i < c->cfg.n_sil; ++i) ih[o_sil + i] = c->cfg.sil_pdf_ids[i];

@@ -26,6 +26,7 @@
 //   k_lasr_glu_dwconv  GLU -> zero-padded depthwise conv (<= 64 taps) -> folded BatchNorm -> activation, a time tile + halo in LDS
 //   k_lasr_argmax      per-frame arg-max (lowest index on ties);  k_lasr_collapse  CTC collapse + compaction per row
 #include "common.h"
+#include "audio_front.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -175,10 +176,7 @@ extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
     const size_t o_win = a.ftake(LS_NFFT), o_twc = a.ftake(LS_NFFT / 2), o_tws = a.ftake(LS_NFFT / 2);
     for (int n = 0; n < LS_WIN; ++n)
         fhost[o_win + (LS_NFFT - LS_WIN) / 2 + n] = 0.5f * (1.0f - (float)cos(2.0 * M_PI * (double)n / (double)(LS_WIN - 1)));
-    for (int k = 0; k < LS_NFFT / 2; ++k) {
-        fhost[o_twc + k] = (float)cos(2.0 * M_PI * (double)k / LS_NFFT);
-        fhost[o_tws + k] = (float)-sin(2.0 * M_PI * (double)k / LS_NFFT);
-    }
+    fft512_twiddles(&fhost[o_twc], &fhost[o_tws]);
     const size_t o_fb = a.ftake((size_t)LS_BINS * mels);
     std::vector<int> ranges(2 * mels, 0);
     {
@@ -187,17 +185,15 @@ extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
         for (int i = 0; i < mels + 2; ++i) fp[i] = ls_mel_to_hz((double)i * mmax / (double)(mels + 1));
         for (int j = 0; j < mels; ++j) {
             const double lo = fp[j], ce = fp[j + 1], hi = fp[j + 2], enorm = 2.0 / (hi - lo);
-            int first = LS_BINS, last = 0;
             for (int i = 0; i < LS_BINS; ++i) {
                 const double fr = (double)i * 16000.0 / LS_NFFT;
                 double w = 0.0;
                 if (fr >= lo && fr < ce) w = (fr - lo) / (ce - lo);
                 else if (fr >= ce && fr <= hi) w = (hi - fr) / (hi - ce);
                 fhost[o_fb + (size_t)i * mels + j] = (float)(w * enorm);
-                if (w != 0.0) { first = std::min(first, i); last = std::max(last, i + 1); }
             }
-            ranges[2 * j] = first < last ? first : 0; ranges[2 * j + 1] = first < last ? last : 0;
         }
+        filter_bin_ranges(&fhost[o_fb], LS_BINS, (int)mels, ranges.data());
     }
     // ---- workspace extents and the rotary tables [T2cap][32] (LasrRotaryEmbedding, :23-42): f32, angle = pos * theta^(-2i/64)
     c->maxN = (int64_t)c->cfg.max_seconds * 16000;

@@ -95,9 +95,6 @@ static size_t layer_down_elems(const mis_tts* c) { return (size_t)c->d * c->ff; 
 extern "C" mis_status mis_tts_create(const mis_lm_config* cfg, mis_snac* codec, int device, mis_tts** out) {
     MIS_API_BEGIN
     MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
     MIS_REQUIRE(!codec || snac_device(codec) == device, MIS_ERR_INVALID_INPUT, "codec lives on another device");
     const int d = cfg->hidden_size, H = cfg->num_attention_heads, Hkv = cfg->num_key_value_heads;
     const int D = cfg->head_dim > 0 ? cfg->head_dim : (H > 0 ? d / H : 0);
@@ -107,9 +104,9 @@ extern "C" mis_status mis_tts_create(const mis_lm_config* cfg, mis_snac* codec, 
     MIS_REQUIRE(H % Hkv == 0 && H / Hkv <= 16, MIS_ERR_INVALID_INPUT, "unsupported GQA grouping %d/%d", H, Hkv);
     MIS_REQUIRE(d % 32 == 0 && cfg->intermediate_size % 32 == 0 && (H * D) % 32 == 0, MIS_ERR_INVALID_INPUT,
                 "hidden/intermediate sizes must be multiples of 32");
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_tts* c = new mis_tts();
-    c->device = device;
+    c->device = device; c->stream = stream;
     c->cfg = *cfg;
     c->cfg.head_dim = D;
     if (c->cfg.rope_factor <= 0) c->cfg.rope_factor = 32.0f;            // LlamaTTS.swift:181-184 defaults
@@ -121,7 +118,6 @@ extern "C" mis_status mis_tts_create(const mis_lm_config* cfg, mis_snac* codec, 
     c->codec = codec;
     c->d = d; c->L = cfg->num_hidden_layers; c->ff = cfg->intermediate_size; c->H = H; c->Hkv = Hkv; c->D = D;
     c->V = cfg->vocab_size; c->Vpad = (int)round_up(c->V, 16); c->Nqkv = (H + 2 * Hkv) * D;
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->emb.alloc((size_t)c->V * d);
     c->lm_head.alloc((size_t)c->Vpad * d);
     c->wqkv.alloc(layer_qkv_elems(c) * c->L);

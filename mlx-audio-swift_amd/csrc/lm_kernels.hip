@@ -149,7 +149,8 @@ void launch_prefill_feed(const int32_t* prompt, const int32_t* lens, int Lmax, i
 
 // ============================================================================ embed + RMSNorm
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
+// (its own order and barriers: red[0] + red[1] + red[2] + red[3], not common.h's block_sum_256)
+__device__ __forceinline__ float lm_block_sum_256(float v, float* red) {
     v = wave_sum(v);
     int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) red[w] = v;
@@ -206,7 +207,7 @@ __global__ void __launch_bounds__(256) k_embed_rmsnorm(const bf16_t* __restrict_
             }
         }
     }
-    float tot = block_sum_256(ss, red);
+    float tot = lm_block_sum_256(ss, red);
     float inv = 1.0f / sqrtf(tot / (float)d + eps);
     const int MT = gridDim.x >> 4;
 #pragma unroll

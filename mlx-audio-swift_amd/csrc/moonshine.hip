@@ -91,9 +91,6 @@ extern "C" mis_status mis_moonshine_frames(const mis_moonshine*, const int64_t* 
 extern "C" mis_status mis_moonshine_create(const mis_moonshine_config* cfg, int device, mis_moonshine** out) {
     MIS_API_BEGIN
     MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
     const int d = cfg->hidden_size;
     MIS_REQUIRE(d > 0 && d % 32 == 0 && d <= 512, MIS_ERR_INVALID_INPUT, "hidden_size %d unsupported (a multiple of 32, at most 512)", d);
     MIS_REQUIRE(cfg->intermediate_size > 0 && cfg->intermediate_size % 32 == 0, MIS_ERR_INVALID_INPUT, "intermediate_size must be a multiple of 32");
@@ -106,14 +103,13 @@ extern "C" mis_status mis_moonshine_create(const mis_moonshine_config* cfg, int 
     MIS_REQUIRE(cfg->encoder_hidden_act == 0, MIS_ERR_INVALID_INPUT, "encoder_hidden_act: only gelu is implemented");
     MIS_REQUIRE(cfg->partial_rotary_factor > 0.0f && cfg->partial_rotary_factor <= 1.0f && cfg->rope_theta > 0.0f, MIS_ERR_INVALID_INPUT, "bad rotary parameters");
     MIS_REQUIRE(cfg->decoder_start_token_id >= 0 && cfg->decoder_start_token_id < cfg->vocab_size, MIS_ERR_INVALID_INPUT, "decoder_start_token_id outside the vocabulary");
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     auto c = std::make_unique<mis_moonshine>();
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->d = d; c->f = cfg->intermediate_size; c->V = cfg->vocab_size;
     c->He = He; c->Hke = Hke; c->Hd = Hd; c->Hkd = Hkd; c->hde = d / He; c->hdd = d / Hd;
     c->rote = ms_rotary_dim(c->hde, cfg->partial_rotary_factor);
     c->rotd = ms_rotary_dim(c->hdd, cfg->partial_rotary_factor);
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     *out = c.release();
     MIS_API_END
 }

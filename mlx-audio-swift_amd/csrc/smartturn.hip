@@ -91,18 +91,14 @@ extern "C" mis_status mis_smartturn_create(const mis_smartturn_config* cfg, int 
     MIS_REQUIRE(H > 0 && d % H == 0 && (d / H == 64 || d / H == 128), MIS_ERR_INVALID_INPUT, "head size %d unsupported (64 or 128)", H > 0 ? d / H : 0);
     MIS_REQUIRE(cfg->encoder_layers >= 1 && cfg->encoder_layers <= 64, MIS_ERR_INVALID_INPUT, "bad encoder_layers");
     MIS_REQUIRE(cfg->threshold >= 0.0f && cfg->threshold <= 1.0f, MIS_ERR_INVALID_INPUT, "threshold outside [0, 1]");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     auto c = std::make_unique<mis_smartturn>();
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->W = (int)W; c->F = F; c->T = T; c->d = d; c->H = H; c->D = d / H; c->ffn = cfg->encoder_ffn_dim; c->nmel = cfg->num_mel_bins;
     c->K1 = (int)round_up((size_t)3 * c->nmel, 32); c->Spad = (int)round_up(T, 32); c->nch = cdiv(W, ST_CHUNK);
     c->mel.sample_rate = cfg->sampling_rate; c->mel.n_fft = cfg->n_fft; c->mel.hop_length = cfg->hop_length; c->mel.n_mels = c->nmel;
     c->mel.window = 1; c->mel.mel_scale = 1; c->mel.slaney_norm = 1; c->mel.drop_last_frame = 1;      // SmartTurnFeatures.swift:56-72
     MIS_REQUIRE(mis_mel_num_frames(&c->mel, W) == F, MIS_ERR_INVALID_INPUT, "frame count of the front end differs from W / hop_length");
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END

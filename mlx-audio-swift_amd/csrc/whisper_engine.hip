@@ -72,9 +72,6 @@ static const float LN_EPS = 1e-5f;
 extern "C" mis_status mis_whisper_create(const mis_whisper_config* cfg, int device, mis_whisper** out) {
     MIS_API_BEGIN
     MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
-    int n = 0;
-    HIP_CHECK(hipGetDeviceCount(&n));
-    MIS_REQUIRE(device >= 0 && device < n, MIS_ERR_DEVICE, "device %d not available (%d GPUs visible)", device, n);
     const int d = cfg->d_model;
     MIS_REQUIRE(d > 0 && cfg->encoder_layers > 0 && cfg->decoder_layers > 0 && cfg->vocab_size > 0, MIS_ERR_INVALID_INPUT, "bad dims");
     MIS_REQUIRE(cfg->encoder_attention_heads > 0 && d % cfg->encoder_attention_heads == 0 &&
@@ -85,13 +82,12 @@ extern "C" mis_status mis_whisper_create(const mis_whisper_config* cfg, int devi
                 "d_model / ffn dims must be multiples of 32");
     MIS_REQUIRE(cfg->num_mel_bins == 80 || cfg->num_mel_bins == 128, MIS_ERR_INVALID_INPUT, "num_mel_bins must be 80 or 128");
     MIS_REQUIRE(cfg->max_source_positions == 1500, MIS_ERR_INVALID_INPUT, "max_source_positions must be 1500");
-    HIP_CHECK(hipSetDevice(device));
+    hipStream_t stream = mis_open_stream(device);
     mis_whisper* c = new mis_whisper();
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->d = d; c->He = cfg->encoder_attention_heads; c->Hd = cfg->decoder_attention_heads; c->D = D;
     c->V = cfg->vocab_size; c->Vpad = (int)round_up(c->V, 16); c->nmel = cfg->num_mel_bins;
     c->K1 = (int)round_up(3 * c->nmel, 32);
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     *out = c;
     MIS_API_END
 }

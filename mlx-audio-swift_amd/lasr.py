@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 from .stt import STTGenerateParameters, STTOutput
 
@@ -214,16 +214,13 @@ def greedy_ctc_tokens(logits, blank_token_id: int = 0, frames=None) -> list:
     return rows
 
 
-class LasrCTCModel:
+class LasrCTCModel(NativeHandle):
     """generate / generateStream / callAsFunction of the reference class, plus ragged batches; one handle, 1..max_batch rows a call."""
+    _prefix = "mis_lasr"
 
     def __init__(self, config: LasrCTCConfig, tokenizer: SentencePieceTokenizer | None = None, device: int = 0):
         self.config, self.tokenizer, self.device = config, tokenizer, device
-        self._h = None
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_lasr_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     default_generation_parameters = STTGenerateParameters(max_tokens=0, temperature=0.0, language=None)      # :282-284
     sanitize = staticmethod(lasr_sanitize)
@@ -257,28 +254,11 @@ class LasrCTCModel:
                 tokenizer = SentencePieceTokenizer.from_tokenizer_json(tpath)
             except Exception:                                     # `try?`: a tokenizer that does not load is no error
                 tokenizer = None
-        files = sorted(fn for fn in os.listdir(model_dir) if fn.endswith(".safetensors"))
-        if not files:
-            raise AudioGenerationError(2, f"No safetensors files found in {model_dir}")
-        from safetensors import safe_open
-        weights = {}
-        for fn in files:
-            with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
-                for k in sf.keys():
-                    weights[k] = sf.get_tensor(k)
-        weights = lasr_sanitize(weights)
+        weights = lasr_sanitize(read_safetensors_dir(model_dir, missing_code=(2, f"No safetensors files found in {model_dir}")))
         unknown = sorted(set(weights) - lasr_expected_keys(config))
         if unknown:
             raise AudioGenerationError(3, f"LASR checkpoint: unused keys {unknown[:4]}")
         return cls.from_weights(config, weights, tokenizer, device)
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_lasr_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_lasr_finalize(self._h))
 
     @property
     def launches(self) -> int:
@@ -297,13 +277,7 @@ class LasrCTCModel:
         rows = [np.asarray(w, np.float32) for w in audios]
         if not rows or any(r.ndim != 1 for r in rows):
             raise AudioGenerationError(3, "LASR: a non-empty list of one-dimensional waveforms is expected")
-        stride = max(1, max(len(r) for r in rows))
-        pcm = np.zeros((len(rows), stride), np.float32) if junk is None else np.full((len(rows), stride), junk, np.float32)
-        lens = np.zeros(len(rows), np.int64)
-        for i, r in enumerate(rows):
-            pcm[i, : len(r)] = r
-            lens[i] = len(r)
-        return pcm, lens
+        return pack_rows(rows, junk)
 
     def features(self, audios, junk=None) -> np.ndarray:
         """Normalised log-mel features [B, Fmax, mels] of a ragged list of waveforms, zeros behind a row's own frames; `junk` fills the
@@ -416,14 +390,3 @@ class LasrCTCModel:
         ms = (C.c_float * 3)()
         check(_lib.lib().mis_debug_lasr_timing(self._h, ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_lasr_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

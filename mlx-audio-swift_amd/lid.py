@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 
 SAMPLE_RATE, HOP_LENGTH = 16000, 160                              # EcapaMelSpectrogram.swift:5-9
@@ -159,16 +159,8 @@ def ecapa_lid_read_directory(model_dir: str, **workspace):
         cfg = EcapaTdnnConfig.from_dict(json.load(f), **workspace)
     if cfg.id2label is None:
         raise LIDError("noLabels", "No id2label mapping found in config")
-    files = sorted(fn for fn in os.listdir(model_dir) if fn.endswith(".safetensors"))
-    if not files:
-        raise LIDError("weightsNotFound", "No .safetensors files found in model directory")
-    from safetensors import safe_open
-    weights = {}
-    for fn in files:
-        with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
-            for k in sf.keys():
-                weights[k] = sf.get_tensor(k)
-    weights = ecapa_lid_sanitize(weights)
+    missing = LIDError("weightsNotFound", "No .safetensors files found in model directory")
+    weights = ecapa_lid_sanitize(read_safetensors_dir(model_dir, missing_code=missing))
     want = ecapa_lid_expected_shapes(cfg)
     unknown, missing = sorted(set(weights) - set(want)), sorted(set(want) - set(weights))
     if unknown or missing:
@@ -179,18 +171,15 @@ def ecapa_lid_read_directory(model_dir: str, **workspace):
     return cfg, weights
 
 
-class EcapaTdnnLID:
+class EcapaTdnnLID(NativeHandle):
     """predict / callAsFunction of the reference class, plus ragged batches; one handle, 1..max_batch rows a call."""
+    _prefix = "mis_ecapa_lid"
 
     def __init__(self, config: EcapaTdnnConfig, device: int = 0):
         self.config = config
         self.device = device
         self.id2label = ecapa_lid_labels(config.id2label)
-        self._h = None
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_ecapa_lid_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config: EcapaTdnnConfig, weights: dict, device: int = 0) -> "EcapaTdnnLID":
@@ -215,14 +204,6 @@ class EcapaTdnnLID:
 
     sanitize = staticmethod(ecapa_lid_sanitize)
 
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_ecapa_lid_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_ecapa_lid_finalize(self._h))
-
     @property
     def launches(self) -> int:
         return int(_lib.lib().mis_ecapa_lid_launches(self._h))
@@ -237,12 +218,8 @@ class EcapaTdnnLID:
         rows = [np.asarray(w, np.float32) for w in waveforms]
         if not rows or any(r.ndim != 1 for r in rows):
             raise AudioGenerationError(3, "ECAPA LID: a non-empty list of one-dimensional waveforms is expected")
-        B, stride = len(rows), max(1, max(len(r) for r in rows))
-        pcm = np.zeros((B, stride), np.float32) if junk is None else np.full((B, stride), junk, np.float32)
-        lens = np.zeros(B, np.int64)
-        for i, r in enumerate(rows):
-            pcm[i, : len(r)] = r
-            lens[i] = len(r)
+        pcm, lens = pack_rows(rows, junk)
+        B, stride = pcm.shape
         return self._run(lambda *o: _lib.lib().mis_ecapa_lid_predict(self._h, pcm.ctypes.data, lens.ctypes.data, B, stride, *o), B, top_k)
 
     def _run(self, call, B, top_k):
@@ -301,14 +278,3 @@ class EcapaTdnnLID:
         ms = (C.c_float * 2)()
         check(_lib.lib().mis_debug_ecapa_lid_timing(self._h, ms))
         return float(ms[0]), float(ms[1])
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_ecapa_lid_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle
 from .generation import AudioGenerationError, check, decode_audio_event, stream_events
 
 MAX_SEQ_LEN = 2048
@@ -271,27 +271,16 @@ class MarvisGenerateParameters:
     row_offset: int = 0
 
 
-class MarvisTTSModel:
+class MarvisTTSModel(NativeHandle):
     """MarvisTTSModel : SpeechGenerationModel.  A handle owns the two LMs and the CSM tables; the Mimi codec is BORROWED per call and
     stays the caller's."""
+
+    _prefix = "mis_marvis"
 
     def __init__(self, args: CSMModelArgs, device: int = 0):
         self.args = args
         self.device = device
-        self._h = C.c_void_p()
-        cc = args.to_c()
-        check(_lib.lib().mis_marvis_create(C.byref(cc), device, C.byref(self._h)))
-
-    def close(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _lib.lib().mis_marvis_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                                # interpreter shutdown
-            pass
+        self._create(args.to_c(), device)
 
     # -- loading -------------------------------------------------------------------------------------
     @classmethod
@@ -355,23 +344,6 @@ class MarvisTTSModel:
         if os.path.isdir(model_repo):
             return cls.from_model_directory(model_repo, device)
         raise AudioGenerationError(1, f"model repo {model_repo!r} is not a local directory (no network access)")
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_marvis_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
-        wq = np.ascontiguousarray(wq, dtype=np.uint32)
-        ks, ps, ds, ss = _tensor_args(scales)
-        kb, pb, db, sb = _tensor_args(biases)
-        if ds != db or tuple(ss) != tuple(sb) or len(ss) != 2:
-            raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
-        N, K = int(ss[0]), int(ss[1]) * group_size
-        check(_lib.lib().mis_marvis_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
-
-    def finalize(self):
-        check(_lib.lib().mis_marvis_finalize(self._h))
 
     # -- protocol surface ----------------------------------------------------------------------------
     @property

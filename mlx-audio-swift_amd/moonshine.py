@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 from .stt import STTGenerateParameters, STTOutput
 
@@ -140,17 +140,15 @@ def moonshine_sanitize(weights: dict, tie_word_embeddings: bool = True) -> dict:
     return out
 
 
-class MoonshineModel:
+class MoonshineModel(NativeHandle):
     """STTGenerationModel conformance: default_generation_parameters, generate, generate_stream."""
+    _prefix = "mis_moonshine"
 
     def __init__(self, config: MoonshineConfig, device: int = 0, tokenizer: MoonshineTokenizer | None = None):
         self.config = config
         self.device = device
         self.tokenizer = tokenizer
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_moonshine_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0, tokenizer=None) -> "MoonshineModel":
@@ -171,26 +169,20 @@ class MoonshineModel:
     def from_model_directory(cls, model_dir: str, device: int = 0) -> "MoonshineModel":
         """fromModelDirectory (:483-495): config.json, an optional tokenizer.json, every *.safetensors in name order.  The reference
         updates with noUnusedKeys and has no quantisation branch: an MLX-quantised directory (.scales keys) is rejected."""
-        from safetensors import safe_open
         with open(os.path.join(model_dir, "config.json")) as f:
             cfg = MoonshineConfig.from_dict(json.load(f))
         try:
             tok = MoonshineTokenizer(model_dir)                   # `try?`: a missing or unusable tokenizer.json is not an error
         except (OSError, ValueError, AudioGenerationError):
             tok = None
-        files = sorted(fn for fn in os.listdir(model_dir) if fn.endswith(".safetensors"))
-        if not files:
-            raise AudioGenerationError(1, f"No safetensors files found in {model_dir}")
-        weights = {}
-        for fn in files:
-            with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
-                keys = list(sf.keys())
-                quant = [k for k in keys if k.endswith(".scales") or k.endswith(".biases")]
-                if quant:
-                    raise AudioGenerationError(3, f"{fn}: MLX-quantised Moonshine checkpoints are not supported ({quant[0]}): the "
-                                                  "reference loads Moonshine without a quantisation branch")
-                for k in keys:
-                    weights[k] = sf.get_tensor(k)
+
+        def no_quant(fn, keys):
+            quant = [k for k in keys if k.endswith(".scales") or k.endswith(".biases")]
+            if quant:
+                raise AudioGenerationError(3, f"{fn}: MLX-quantised Moonshine checkpoints are not supported ({quant[0]}): the "
+                                              "reference loads Moonshine without a quantisation branch")
+
+        weights = read_safetensors_dir(model_dir, missing_code=(1, f"No safetensors files found in {model_dir}"), on_keys=no_quant)
         return cls.from_weights(cfg, weights, device, tok)
 
     @classmethod
@@ -200,14 +192,6 @@ class MoonshineModel:
         if not os.path.isdir(path):
             raise AudioGenerationError(3, f"Moonshine: {model_name!r} is not a local model directory (downloads are not supported)")
         return cls.from_model_directory(path, device)
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_moonshine_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_moonshine_finalize(self._h))
 
     @property
     def default_generation_parameters(self) -> STTGenerateParameters:      # :361-363
@@ -220,14 +204,8 @@ class MoonshineModel:
     # -- batching helpers ---------------------------------------------------------------------------
     @staticmethod
     def _pack(rows, junk: float | None = None):
-        rows = [np.asarray(r, np.float32).reshape(-1) for r in rows]
-        stride = max(1, max(len(r) for r in rows))
-        pcm = np.zeros((len(rows), stride), np.float32) if junk is None else np.full((len(rows), stride), junk, np.float32)
-        lens = np.zeros(len(rows), np.int64)
-        for i, r in enumerate(rows):
-            pcm[i, : len(r)] = r
-            lens[i] = len(r)
-        return pcm, lens, stride
+        pcm, lens = pack_rows([np.asarray(r, np.float32).reshape(-1) for r in rows], junk)
+        return pcm, lens, pcm.shape[1]
 
     def frames(self, lens) -> np.ndarray:
         l = np.ascontiguousarray(lens, dtype=np.int64)
@@ -321,14 +299,3 @@ class MoonshineModel:
         if out.text:
             yield ("token", out.text)
         yield ("result", out)
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_moonshine_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, _tensor_args
 from .generation import (AudioEvent, AudioGenerationError, InfoEvent, TokenEvent, check, decode_audio_event,  # noqa: F401
                          stream_events)
 from .tts import LlamaTTSConfiguration
@@ -405,24 +405,19 @@ class PreparedPrompt:
     reference: object = None            # ReferenceAudioContext of an in-context prompt (its rows live on the model handle)
 
 
-class Qwen3TTSModel:
+class Qwen3TTSModel(NativeHandle):
+    _prefix = "mis_qwen3tts"
+
     def __init__(self, config: Qwen3TTSConfiguration, device: int = 0):
         self.configuration = config
         self.device = device
         self.tokenizer = None
-        self._h = C.c_void_p()
-        cc = config.to_c()
-        check(_lib.lib().mis_qwen3tts_create(C.byref(cc), device, C.byref(self._h)))
+        self._create(config.to_c(), device)
         self._ref_cache = None              # cachedReferenceAudioContext (Qwen3TTS.swift:268-300): one entry, keyed by the array object
         self._ref_log = []                  # every context registered on the handle, in row order (replayed onto replicas)
         if config.speaker_encoder is not None or config.tokenizer_encoder is not None:
             rc = config.reference_to_c()
             check(_lib.lib().mis_qwen3tts_enable_reference(self._h, C.byref(rc)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            _lib.lib().mis_qwen3tts_destroy(h)
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0) -> "Qwen3TTSModel":
@@ -494,11 +489,6 @@ class Qwen3TTSModel:
             return cls.from_model_directory(model_repo, device)
         raise AudioGenerationError(1, f"model repo {model_repo!r} is not a local directory (no network access)")
 
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_qwen3tts_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
     def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 8):
         """A tensor of a quantised checkpoint: wq uint32 [N, K*bits/32], scales / biases [N, K/group_size]."""
         wq = np.ascontiguousarray(wq, dtype=np.uint32)
@@ -508,9 +498,6 @@ class Qwen3TTSModel:
             raise AudioGenerationError(3, "scales and biases must share dtype and shape")
         N, K = int(ss[0]), int(ss[1]) * group_size
         check(_lib.lib().mis_qwen3tts_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
-
-    def finalize(self):
-        check(_lib.lib().mis_qwen3tts_finalize(self._h))
 
     # -- protocol surface ------------------------------------------------------------------------------
     @property

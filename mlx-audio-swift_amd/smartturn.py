@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 
 
@@ -158,21 +158,15 @@ def smart_turn_expected_keys(config: SmartTurnConfig) -> set:
 def smart_turn_read_directory(model_dir: str):
     """config.json and every *.safetensors of a model directory (fromModelDirectory, :339-358) -> (SmartTurnConfig, sanitized weights).
     No device is touched.  MLX-quantised directories and keys the model does not have are errors."""
-    from safetensors import safe_open
     with open(os.path.join(model_dir, "config.json")) as f:
         cfg = SmartTurnConfig.from_dict(json.load(f))
-    files = sorted(fn for fn in os.listdir(model_dir) if fn.endswith(".safetensors"))
-    if not files:
-        raise AudioGenerationError(1, f"No safetensors files found in {model_dir}")
-    weights = {}
-    for fn in files:
-        with safe_open(os.path.join(model_dir, fn), framework="pt") as sf:
-            keys = list(sf.keys())
-            quant = [k for k in keys if k.endswith(".scales") or k.endswith(".biases")]
-            if quant:
-                raise AudioGenerationError(3, f"{fn}: MLX-quantised Smart Turn checkpoints are not supported ({quant[0]})")
-            for k in keys:
-                weights[k] = sf.get_tensor(k)
+
+    def no_quant(fn, keys):
+        quant = [k for k in keys if k.endswith(".scales") or k.endswith(".biases")]
+        if quant:
+            raise AudioGenerationError(3, f"{fn}: MLX-quantised Smart Turn checkpoints are not supported ({quant[0]})")
+
+    weights = read_safetensors_dir(model_dir, missing_code=(1, f"No safetensors files found in {model_dir}"), on_keys=no_quant)
     weights = smart_turn_sanitize(weights)
     unknown = sorted(set(weights) - smart_turn_expected_keys(cfg))
     if unknown:
@@ -180,18 +174,15 @@ def smart_turn_read_directory(model_dir: str):
     return cfg, weights
 
 
-class SmartTurnModel:
+class SmartTurnModel(NativeHandle):
     """predict_endpoint / predict_endpoints / prepare_input_features / __call__ of the reference class; one handle, 1..64 rows a call."""
+    _prefix = "mis_smartturn"
 
     def __init__(self, config: SmartTurnConfig, device: int = 0):
         self.config = config
         self.device = device
-        self._h = None
         self._last_batch = 0
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_smartturn_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config: SmartTurnConfig, weights: dict, device: int = 0) -> "SmartTurnModel":
@@ -222,14 +213,6 @@ class SmartTurnModel:
             raise AudioGenerationError(3, f"Smart Turn: {model_name!r} is not a local model directory (downloads are not supported)")
         return cls.from_model_directory(path, device)
 
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_smartturn_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_smartturn_finalize(self._h))
-
     @property
     def launches(self) -> int:
         return int(_lib.lib().mis_smartturn_launches(self._h))
@@ -247,13 +230,8 @@ class SmartTurnModel:
 
     @staticmethod
     def _pack(rows, junk: float | None = None):
-        stride = max(1, max(len(r) for r in rows))
-        pcm = np.zeros((len(rows), stride), np.float32) if junk is None else np.full((len(rows), stride), junk, np.float32)
-        lens = np.zeros(len(rows), np.int64)
-        for i, r in enumerate(rows):
-            pcm[i, : len(r)] = r
-            lens[i] = len(r)
-        return pcm, lens, stride
+        pcm, lens = pack_rows(rows, junk)
+        return pcm, lens, pcm.shape[1]
 
     # -- calls ---------------------------------------------------------------------------------------
     def predict_raw(self, rows, sample_rate=None, threshold=None, junk: float | None = None):
@@ -314,14 +292,3 @@ class SmartTurnModel:
         ms = (C.c_float * 3)()
         check(_lib.lib().mis_debug_smartturn_timing(self._h, ms))
         return tuple(float(v) for v in ms)
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_smartturn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

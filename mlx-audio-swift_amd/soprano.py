@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle
 from .generation import (AudioEvent, AudioGenerationError, AudioGenerationInfo, GenerateParameters, InfoEvent, TokenEvent, check,
                          decode_audio_event, stream_events)
 from .tts import MAX_BATCH, LlamaTTSConfiguration, LlamaTTSModel
@@ -187,26 +187,24 @@ def split_prompt(text: str, split_pattern: str = "\n") -> list[str]:
     return [c for c in out if c]
 
 
-class SopranoModel:
+class SopranoModel(NativeHandle):
+    _prefix = "mis_soprano"
+
     def __init__(self, config: SopranoConfiguration, device: int = 0):
         self.configuration = config
         self.device = device
         self.tokenizer = None
         self.clean_text = None
-        self._h = C.c_void_p()
-        cc = config.to_c()
-        check(_lib.lib().mis_soprano_create(C.byref(cc), device, C.byref(self._h)))
+        self._create(config.to_c(), device)
         # borrowed LM handle: taps (lm_forward / reset) for tests and synthetic init
         self.lm = LlamaTTSModel(config.lm_configuration(), None, device,
                                 _handle=C.c_void_p(_lib.lib().mis_soprano_lm(self._h)))
         self.lm._borrowed = True
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            if getattr(self, "lm", None) is not None:
-                self.lm._h = None
-            _lib.lib().mis_soprano_destroy(h)
+    def close(self):
+        if getattr(self, "lm", None) is not None:
+            self.lm._h = None                                            # borrowed: it dies with this handle
+        super().close()
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0) -> "SopranoModel":
@@ -274,26 +272,6 @@ class SopranoModel:
         if os.path.isdir(model_repo):
             return cls.from_model_directory(model_repo, device=device)
         raise AudioGenerationError(1, f"model repo {model_repo!r} is not a local directory (no network access)")
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_soprano_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
-        """A Linear in MLX's affine-quantised form (`name` = its .weight key, sanitised like set_tensor's): wq uint32
-        [N, K*bits/32], scales / biases [N, K/group_size] (bf16 / f16 / f32).  LM matrices go to the token LM (streamed as codes
-        where a whole role qualifies, see mis_tts_set_tensor_quantized); decoder matrices are dequantised to float32 at load."""
-        wq = np.ascontiguousarray(wq, dtype=np.uint32)
-        ks, ps, ds, ss = _tensor_args(scales)
-        kb, pb, db, sb = _tensor_args(biases)
-        if ds != db or tuple(ss) != tuple(sb) or len(ss) != 2:
-            raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
-        N, K = int(ss[0]), int(ss[1]) * group_size
-        check(_lib.lib().mis_soprano_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
-
-    def finalize(self):
-        check(_lib.lib().mis_soprano_finalize(self._h))
 
     # -- protocol surface ------------------------------------------------------------------------------
     @property

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle
 from .generation import AudioGenerationError, InfoEvent, TokenEvent, check, decode_audio_event, stream_events
 
 SAMPLE_RATE, CHUNK_SAMPLES = 16000, 480000          # WhisperAudioConfig, WhisperConfig.swift:188-193
@@ -119,8 +119,10 @@ def whisper_checkpoint_plan(dtypes: dict, quantization: dict | None) -> list:
     return plan
 
 
-class WhisperModel:
+class WhisperModel(NativeHandle):
     """STTGenerationModel conformance: default_generation_parameters, generate(audio, generation_parameters)."""
+
+    _prefix = "mis_whisper"
 
     def __init__(self, config: WhisperConfig, device: int = 0):
         self.config = config
@@ -129,10 +131,7 @@ class WhisperModel:
         # timestamp_begin_id, is_multilingual, language_to_id (WhisperTokenizer.swift)
         self.tokenizer = None
         self.generation_config = None    # optional dict: suppress_tokens / begin_suppress_tokens (generation_config.json)
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_whisper_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config, weights: dict, device: int = 0) -> "WhisperModel":
@@ -186,25 +185,6 @@ class WhisperModel:
             with open(gc) as f:
                 m.generation_config = json.load(f)
         return m
-
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_whisper_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
-        """A Linear / Embedding in MLX's affine-quantised form (`name` = its .weight key): wq uint32 [N, K*bits/32], scales / biases
-        [N, K/group_size] (bf16 / f16 / f32)."""
-        wq = np.ascontiguousarray(wq, dtype=np.uint32)
-        ks, ps, ds, ss = _tensor_args(scales)
-        kb, pb, db, sb = _tensor_args(biases)
-        if ds != db or tuple(ss) != tuple(sb) or len(ss) != 2:
-            raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
-        N, K = int(ss[0]), int(ss[1]) * group_size
-        check(_lib.lib().mis_whisper_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
-
-    def finalize(self):
-        check(_lib.lib().mis_whisper_finalize(self._h))
 
     @property
     def native_quant_bits(self) -> dict:
@@ -387,14 +367,3 @@ class WhisperModel:
         n_prompt, n_gen = len(prompt_ids) * len(chunks), sum(len(t) for t in ids)
         yield ("result", STTOutput(" ".join(texts), segments or None, self._prompt_language(prompt_ids, gp.language), n_prompt, n_gen,
                                    n_prompt + n_gen, n_prompt / el if el > 0 else 0.0, n_gen / el if el > 0 else 0.0, el, 0.0, ids))
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_whisper_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -12,7 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .codecs import SNAC, _tensor_args
+from ._handle import NativeHandle, _tensor_args
+from .codecs import SNAC
 from .generation import (AudioEvent, AudioGenerationError, AudioGenerationInfo, GenerateParameters, InfoEvent,
                          TokenEvent, check, decode_audio_event, stream_events)
 
@@ -159,10 +160,12 @@ class LlamaTTSConfiguration:
                               self.codec_chunk_groups)
 
 
-class LlamaTTSModel:
+class LlamaTTSModel(NativeHandle):
     """SpeechGenerationModel conformance: sample_rate, default_generation_parameters, generate,
     generate_stream (Generation.swift:8-39).  Batch methods (`generate_batch`) are the new capability
     (the reference is batch-1, LlamaTTS.swift:683-688); row r of a batch equals the B=1 result."""
+
+    _prefix = "mis_tts"
 
     def __init__(self, config: LlamaTTSConfiguration, codec: SNAC | None = None, device: int = 0, _handle=None):
         self.configuration = config
@@ -171,10 +174,7 @@ class LlamaTTSModel:
         self.tokenizer = None
         self._h = _handle
         if self._h is None:
-            h = C.c_void_p()
-            cfg = config.to_c()
-            check(_lib.lib().mis_tts_create(C.byref(cfg), codec._h if codec else None, device, C.byref(h)))
-            self._h = h
+            self._create(config.to_c(), codec._h if codec else None, device)
 
     # -- loading (LlamaTTS.swift:915-993) ---------------------------------------------------------
     @classmethod
@@ -216,11 +216,6 @@ class LlamaTTSModel:
         """Per role, the bit width of the quantised form it is streamed in (0 = dense bf16)."""
         return {r: int(_lib.lib().mis_tts_native_quant_bits(self._h, i)) for i, r in enumerate(("qkv", "o", "gate_up", "down", "lm_head"))}
 
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_tts_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
     def set_quantized_tensor(self, name: str, wq, scales, biases, group_size: int = 64, bits: int = 4):
         """A matrix in MLX's affine-quantised form: wq uint32 [N, K*bits/32], scales / biases [N, K/group_size]."""
         wq = np.ascontiguousarray(wq, dtype=np.uint32)
@@ -230,9 +225,6 @@ class LlamaTTSModel:
             raise AudioGenerationError(3, "scales and biases must share dtype and shape")
         N, K = int(ss[0]), int(ss[1]) * group_size
         check(_lib.lib().mis_tts_set_tensor_quantized(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
-
-    def finalize(self):
-        check(_lib.lib().mis_tts_finalize(self._h))
 
     # -- protocol surface --------------------------------------------------------------------------
     @property
@@ -403,16 +395,9 @@ class LlamaTTSModel:
         return (C.c_void_p * len(keep))(*[n.ctypes.data for n in keep]), keep
 
     def close(self):
-        if self._h is not None:
-            if not getattr(self, "_borrowed", False):      # SopranoModel owns its LM handle
-                _lib.lib().mis_tts_destroy(self._h)
+        if getattr(self, "_borrowed", False):              # SopranoModel owns its LM handle
             self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 def sample_logits(logits, window, window_len, params: GenerateParameters, step: int, lo: int = 0, hi: int = 0,

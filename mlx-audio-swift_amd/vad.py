@@ -11,7 +11,7 @@ from dataclasses import dataclass, field, fields
 import numpy as np
 
 from . import _lib
-from .codecs import _tensor_args
+from ._handle import NativeHandle, pack_rows
 from .generation import AudioGenerationError, check
 
 _F = np.float32
@@ -409,18 +409,15 @@ def chunks_from_segments(segments_ms, n_samples: int, sample_rate: int, merge_ga
 
 
 # ------------------------------------------------------------------------------------------------------------ the model
-class FSMNVAD:
+class FSMNVAD(NativeHandle):
     """extractFeatures / callAsFunction / detect of the reference class, plus ragged batches; one handle, 1..max_batch rows a call, rows
     of any length (the engine walks them in chunks of chunk_frames)."""
+    _prefix = "mis_fsmn_vad"
 
     def __init__(self, config: FSMNVADConfig, device: int = 0):
         self.config = config
         self.device = device
-        self._h = None
-        h = C.c_void_p()
-        cfg = config.to_c()
-        check(_lib.lib().mis_fsmn_vad_create(C.byref(cfg), device, C.byref(h)))
-        self._h = h
+        self._create(config.to_c(), device)
 
     @classmethod
     def from_weights(cls, config: FSMNVADConfig, weights: dict, cmvn=None, device: int = 0) -> "FSMNVAD":
@@ -457,14 +454,6 @@ class FSMNVAD:
 
     sanitize = staticmethod(fsmn_vad_sanitize)
 
-    def set_tensor(self, name: str, arr):
-        keep, ptr, dt, shape = _tensor_args(arr)
-        sh = (C.c_int64 * len(shape))(*shape)
-        check(_lib.lib().mis_fsmn_vad_set_tensor(self._h, name.encode(), ptr, dt, sh, len(shape)))
-
-    def finalize(self):
-        check(_lib.lib().mis_fsmn_vad_finalize(self._h))
-
     @property
     def launches(self) -> int:
         return int(_lib.lib().mis_fsmn_vad_launches(self._h))
@@ -484,13 +473,8 @@ class FSMNVAD:
         rows = [self._row(w, sample_rate) for w in waveforms]
         if not rows:
             raise AudioGenerationError(3, "FSMN VAD: no rows")
-        B, stride = len(rows), max(1, max(len(r) for r in rows))
-        pcm = np.zeros((B, stride), _F) if junk is None else np.full((B, stride), junk, _F)
-        lens = np.zeros(B, np.int64)
-        for i, r in enumerate(rows):
-            pcm[i, : len(r)] = r
-            lens[i] = len(r)
-        return pcm, lens, B, stride
+        pcm, lens = pack_rows(rows, junk)
+        return pcm, lens, *pcm.shape
 
     def frames(self, lens):
         """Sample counts -> (fbank frames T, LFR rows R), int32 arrays."""
@@ -577,14 +561,3 @@ class FSMNVAD:
         ms = (C.c_float * 2)()
         check(_lib.lib().mis_debug_fsmn_vad_timing(self._h, ms))
         return float(ms[0]), float(ms[1])
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().mis_fsmn_vad_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
