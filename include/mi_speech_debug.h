@@ -230,6 +230,45 @@ mis_status mis_debug_convert_to_bf16(int device, const void* src, int dtype, int
 mis_status mis_debug_dequant_affine(int device, const uint32_t* wq, const void* scales, const void* biases, int sb_dtype, int N, int K, int group, int bits,
                                     uint16_t* dst_out);
 
+/* csrc/lasr.hip, tests (tests/test_gpu_lasr_ops.py): ONE call of ls_gemm, or one launch line of the LASR chain (k_lasr_ln, k_lasr_rope,
+ * k_lasr_attn, k_lasr_glu_dwconv, k_lasr_im2col, k_lasr_pack, k_lasr_argmax, k_lasr_collapse - the kernels are private to csrc/lasr.hip, so
+ * the entry points live at its end), on caller-supplied host data; nothing is computed in the entry points.  16-bit operands and results
+ * are raw bf16 payloads (uint16).  Guards as above: every output lies between guard bands and is pre-filled with the byte 0xFF (0xFFFF in
+ * bf16, -1 as an integer), a changed guard byte - or a changed padding column of a strided output - fails the call with
+ * MIS_ERR_GENERATION_FAILED; every input is followed by NaN (ints and row counts: 0x7FFFFFFF).  The entry points refuse
+ * (MIS_ERR_INVALID_INPUT) only what would make a KERNEL read or write outside these buffers; a shape ls_gemm refuses is returned as its
+ * status (MIS_ERR_GENERATION_FAILED) and nothing is launched.  Row counts: cnt[r] frames of every Tp rows are live, NULL = all.
+ *   lasr_gemm: ls_gemm.  epi 0 LG_BIAS, 1 LG_RELU, 2 LG_SILU, 3 LG_AXPBY, 4 LG_F32.  X is the IMAGE the kernel addresses, (M - 1) ldx + K
+ *     elements with row m at m ldx; with ldx > K the columns between two rows are replaced by NaN.  W [N][K]; bias [N] or NULL; R [M][N]
+ *     (LG_AXPBY) or NULL; cnt [ceil(M / Tp)] or NULL.  in_place (LG_AXPBY): the output buffer is loaded with R and passed as the residual too,
+ *     as the chain's FF1 / attention / conv calls do; else R is a buffer of its own (the FF2 call) and R_after (may be NULL) [M][N] receives
+ *     it as the launch left it.  tile 0: the launcher's rule, 2 / 4: the 64- / 128-tile whatever the grid.  C_out bf16 [M][N], LG_F32: float
+ *     [M][N].  report (may be NULL) int32[2]: epilogue (-1: nothing launched), TI (2 / 4).
+ *   lasr_ln: x, y_out [M][d] (d even), w, b [d]; cnt [ceil(M / Tp)] or NULL.
+ *   lasr_rope: rows [M][ld] go in and come back whole; heads 0 .. nheads - 1 of 64 columns are rotated with row m % Tp of cs / sn [Tp][32].
+ *   lasr_attn: qkv [B Tp][ld] uploaded as given (q heads | k heads | v heads from column 0; the caller decides what sits behind cnt[b] and
+ *     in the padding columns; ld a multiple of 8); out [B Tp][H 64]: the first H 64 columns of every row of ldo.
+ *   lasr_glu_dwconv: act 0 SiLU, 1 ReLU.  pw [B Tp][2 C], taps [k][C], shift [C], cnt [B], 1 <= k <= 64; out [B Tp][C].  report int32[1]: act.
+ *   lasr_im2col: in [B][Tin][C] (C a multiple of 8), cnt [B]; out [B Tout][ks C].  A live frame must read inside its own row:
+ *     (min(cnt[b], Tout) - 1) st + ks <= Tin.
+ *   lasr_pack: feats float [B][Fp][mels], F [B]; out [B Fp][Kp], Kp >= mels.
+ *   lasr_argmax: logits float [M][V]; pred int32 [M].
+ *   lasr_collapse: pred [B][Tp], cnt [B]; tokens int32 [B][Tp] comes back whole (-1: never written), ntok [B]. */
+mis_status mis_debug_lasr_gemm(int device, int epi, const uint16_t* X, const uint16_t* W, const uint16_t* bias, const uint16_t* R, float a, float b,
+                               const int32_t* cnt, int Tp, int in_place, int tile, int M, int N, int K, int ldx, void* C_out, uint16_t* R_after,
+                               int32_t* report);
+mis_status mis_debug_lasr_ln(int device, const uint16_t* x, const uint16_t* w, const uint16_t* b, int M, int d, float eps, const int32_t* cnt, int Tp,
+                             uint16_t* y_out);
+mis_status mis_debug_lasr_rope(int device, uint16_t* rows, int M, int ld, int nheads, int Tp, const float* cs, const float* sn);
+mis_status mis_debug_lasr_attn(int device, const uint16_t* qkv, int ld, int H, int Hkv, const int32_t* cnt, int B, int Tp, float scale, int ldo,
+                               uint16_t* out);
+mis_status mis_debug_lasr_glu_dwconv(int device, int act, const uint16_t* pw, const float* taps, const float* shift, const int32_t* cnt, int B, int Tp,
+                                     int C, int k, uint16_t* out, int32_t* report);
+mis_status mis_debug_lasr_im2col(int device, const uint16_t* in, const int32_t* cnt, int B, int Tin, int Tout, int C, int ks, int st, uint16_t* out);
+mis_status mis_debug_lasr_pack(int device, const float* feats, const int32_t* F, int B, int Fp, int mels, int Kp, uint16_t* out);
+mis_status mis_debug_lasr_argmax(int device, const float* logits, int M, int V, int32_t* pred);
+mis_status mis_debug_lasr_collapse(int device, const int32_t* pred, const int32_t* cnt, int B, int Tp, int blank, int32_t* tokens, int32_t* ntok);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

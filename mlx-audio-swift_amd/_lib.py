@@ -487,6 +487,16 @@ DEBUG_SYMBOLS = {
     "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
     "mis_debug_ecapa_lid_timing": (C.c_int, [_P, _P]),
     "mis_debug_lasr_timing": (C.c_int, [_P, _P]),
+    "mis_debug_lasr_gemm": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, _P, _P, _P]),
+    "mis_debug_lasr_ln": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P]),
+    "mis_debug_lasr_rope": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_lasr_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "mis_debug_lasr_glu_dwconv": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_lasr_im2col": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_lasr_pack": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_lasr_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P]),
+    "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }

@@ -540,22 +540,25 @@ __global__ void __launch_bounds__(256) k_lasr_gemm(LasrGemm p) {
         }
     }
 }
+// tile: 0 the rule below, 2 / 4 that tile whatever the grid (tests); returns the TI that ran
 template <int EPI>
-static void ls_gemm_epi(mis_lasr* c, const LasrGemm& p) {
+static int ls_gemm_epi(mis_lasr* c, const LasrGemm& p, int tile) {
     // the 128 x 128 tile once its grid fills the chip, the 64 x 64 tile (four times the blocks) below that
-    if ((long)cdiv(p.N, 128) * cdiv(p.M, 128) >= 256) LS_LAUNCH(c, (k_lasr_gemm<EPI, 4>), dim3(cdiv(p.N, 128), cdiv(p.M, 128)), dim3(256), p);
+    const bool big = tile ? tile == 4 : (long)cdiv(p.N, 128) * cdiv(p.M, 128) >= 256;
+    if (big) LS_LAUNCH(c, (k_lasr_gemm<EPI, 4>), dim3(cdiv(p.N, 128), cdiv(p.M, 128)), dim3(256), p);
     else LS_LAUNCH(c, (k_lasr_gemm<EPI, 2>), dim3(cdiv(p.N, 64), cdiv(p.M, 64)), dim3(256), p);
+    return big ? 4 : 2;
 }
-static void ls_gemm(mis_lasr* c, int epi, const bf16_t* X, int ldx, const bf16_t* W, const bf16_t* bias, void* C, int M, int N, int K,
-                    const bf16_t* R = nullptr, float ra = 0.0f, float rb = 0.0f, const int* cnt = nullptr, int Tp = 1) {
+static int ls_gemm(mis_lasr* c, int epi, const bf16_t* X, int ldx, const bf16_t* W, const bf16_t* bias, void* C, int M, int N, int K,
+                   const bf16_t* R = nullptr, float ra = 0.0f, float rb = 0.0f, const int* cnt = nullptr, int Tp = 1, int tile = 0) {
     MIS_REQUIRE(K % 32 == 0 && ldx % 8 == 0 && (epi == LG_F32 || N % 4 == 0) && M >= 1, MIS_ERR_GENERATION_FAILED, "LASR GEMM: unsupported shape");
     const LasrGemm p{X, W, bias, R, C, M, N, K, ldx, ra, rb, cnt, Tp};
     switch (epi) {
-        case LG_BIAS: ls_gemm_epi<LG_BIAS>(c, p); break;
-        case LG_RELU: ls_gemm_epi<LG_RELU>(c, p); break;
-        case LG_SILU: ls_gemm_epi<LG_SILU>(c, p); break;
-        case LG_AXPBY: ls_gemm_epi<LG_AXPBY>(c, p); break;
-        case LG_F32: ls_gemm_epi<LG_F32>(c, p); break;
+        case LG_BIAS: return ls_gemm_epi<LG_BIAS>(c, p, tile);
+        case LG_RELU: return ls_gemm_epi<LG_RELU>(c, p, tile);
+        case LG_SILU: return ls_gemm_epi<LG_SILU>(c, p, tile);
+        case LG_AXPBY: return ls_gemm_epi<LG_AXPBY>(c, p, tile);
+        case LG_F32: return ls_gemm_epi<LG_F32>(c, p, tile);
         default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown LASR GEMM epilogue");
     }
 }
@@ -1036,5 +1039,269 @@ extern "C" mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms) {
     if (!ms) { c->timed = true; return MIS_OK; }
     MIS_REQUIRE(c->timed && c->batch > 0, MIS_ERR_NOT_INITIALIZED, "no timed generate");
     for (int i = 0; i < 3; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    MIS_API_END
+}
+
+// ============================================================================ test scaffolding (include/mi_speech_debug.h)
+// ONE call of ls_gemm, or one launch line of ls_encoder / mis_stt_lasr_generate, on caller-supplied host data, so that
+// tests/test_gpu_lasr_ops.py can hold the kernels above to an operator-level reference.  Nothing is computed here: the operands are
+// uploaded as given and what the launch wrote is copied back.  Guards as gemm_debug.hip, attn_debug.hip, codec_debug.hip and
+// enc_debug.hip (debug_guard.h): every output is [guard | body | guard], all of it the byte 0xFF before the launch (an output that
+// also goes IN - the rotated rows, the in-place residual - holds the caller's data instead); a changed guard byte or padding column
+// fails the call; every input is followed by IN_GUARD NaNs (ints: 0x7FFFFFFF).  The entry points refuse what would make a KERNEL leave
+// these buffers; what ls_gemm refuses is returned as its status and nothing is launched.  The launches run on a bare mis_lasr (device
+// and the null stream, no weights, no workspace): the launchers need nothing else of it.
+#include "debug_guard.h"
+#include "../../include/mi_speech_debug.h"
+
+namespace {
+
+constexpr int64_t LSD_MAX_ELEMS = (int64_t)1 << 28;          // per tensor
+
+void lsd_sync(const mis_lasr& c) {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    MIS_REQUIRE(c.launches == 1, MIS_ERR_GENERATION_FAILED, "%d launches where one was meant", c.launches);
+}
+void lsd_open(mis_lasr& c, int device) {
+    HIP_CHECK(hipSetDevice(device));
+    c.device = device;
+}
+// counts [n] followed by 0x7FFFFFFF (a row count that masks nothing)
+void lsd_counts(DevBuf<uint32_t>& d, const int32_t* cnt, size_t n) { alloc32(d, cnt, n, 0x7FFFFFFFu); }
+const int* lsd_int(const DevBuf<uint32_t>& d) { return reinterpret_cast<const int*>(d.p); }
+// the body of a guarded output
+void lsd_fetch(GuardedOut& o, void* out) {
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+}
+// rows of ld with `cols` live columns -> the live columns; the columns behind must still hold the fill
+void lsd_fetch16_rows(GuardedOut& o, size_t rows, size_t ld, size_t cols, uint16_t* out) {
+    o.check_guards();
+    std::vector<uint16_t> h(o.body / 2);
+    HIP_CHECK(hipMemcpy(h.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        std::copy(h.begin() + r * ld, h.begin() + r * ld + cols, out + r * cols);
+        for (size_t c = cols; c < ld; ++c)
+            MIS_REQUIRE(h[r * ld + c] == 0xFFFF, MIS_ERR_GENERATION_FAILED, "the kernel wrote column %zu of row %zu behind its %zu columns", c, r, cols);
+    }
+}
+
+}  // namespace
+
+extern "C" mis_status mis_debug_lasr_gemm(int device, int epi, const uint16_t* X, const uint16_t* W, const uint16_t* bias, const uint16_t* R, float a,
+                                          float b, const int32_t* cnt, int Tp, int in_place, int tile, int M, int N, int K, int ldx, void* C_out,
+                                          uint16_t* R_after, int32_t* report) {
+    MIS_API_BEGIN
+    if (report) { report[0] = -1; report[1] = 0; }
+    MIS_REQUIRE(X && W && C_out && M >= 1 && N >= 1 && K >= 1 && ldx >= 1, MIS_ERR_INVALID_INPUT, "LASR GEMM: X, W, C_out and positive M, N, K, ldx are required");
+    MIS_REQUIRE((int64_t)M * N <= LSD_MAX_ELEMS && (int64_t)N * K <= LSD_MAX_ELEMS && (int64_t)(M - 1) * ldx + K <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "LASR GEMM: tensor too large");
+    MIS_REQUIRE(epi != LG_AXPBY || R, MIS_ERR_INVALID_INPUT, "LASR GEMM: the epilogue needs R");
+    MIS_REQUIRE(!in_place || epi == LG_AXPBY, MIS_ERR_INVALID_INPUT, "LASR GEMM: in_place is the residual epilogue's");
+    MIS_REQUIRE(!cnt || Tp >= 1, MIS_ERR_INVALID_INPUT, "LASR GEMM: row counts need Tp >= 1");
+    MIS_REQUIRE(tile == 0 || tile == 2 || tile == 4, MIS_ERR_INVALID_INPUT, "LASR GEMM: tile 0 (the launcher's rule), 2 or 4");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint16_t> dX, dW, dB, dR;
+    DevBuf<uint32_t> dcnt;
+    {   // the image the kernel addresses: row m at m ldx, K columns; with ldx > K the columns between the rows are NaN
+        const size_t n = (size_t)(M - 1) * ldx + K;
+        std::vector<uint16_t> h(X, X + n);
+        if (ldx > K)
+            for (int m = 0; m + 1 < M; ++m) std::fill(h.begin() + (size_t)m * ldx + K, h.begin() + (size_t)(m + 1) * ldx, BF16_NAN);
+        alloc16(dX, h.data(), n, BF16_NAN);
+    }
+    alloc16(dW, W, (size_t)N * K, BF16_NAN);
+    if (bias) alloc16(dB, bias, N, BF16_NAN);
+    const bool sep = epi == LG_AXPBY && !in_place;
+    if (sep) alloc16(dR, R, (size_t)M * N, BF16_NAN);
+    if (cnt) lsd_counts(dcnt, cnt, (size_t)cdiv(M, Tp));
+    const size_t es = epi == LG_F32 ? 4 : 2;
+    GuardedOut o;
+    o.alloc((size_t)M * N * es, (size_t)128 * N * es);             // a guard is one 128-row tile of output
+    if (in_place) HIP_CHECK(hipMemcpy(o.p(), R, o.body, hipMemcpyHostToDevice));
+    const bf16_t* Rp = in_place ? reinterpret_cast<const bf16_t*>(o.p()) : sep ? dR.p : nullptr;
+    const int ti = ls_gemm(&c, epi, dX.p, ldx, dW.p, bias ? dB.p : nullptr, o.p(), M, N, K, Rp, a, b, cnt ? lsd_int(dcnt) : nullptr, Tp, tile);
+    lsd_sync(c);
+    if (report) { report[0] = epi; report[1] = ti; }
+    lsd_fetch(o, C_out);
+    if (sep && R_after) HIP_CHECK(hipMemcpy(R_after, dR.p, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_ln(int device, const uint16_t* x, const uint16_t* w, const uint16_t* b, int M, int d, float eps, const int32_t* cnt,
+                                        int Tp, uint16_t* y_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && w && b && y_out && M >= 1 && d >= 2 && d % 2 == 0 && (int64_t)M * d <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "LASR LayerNorm: x, w, b, y_out, M >= 1 and an even d (the kernel moves 32-bit pairs) are required");
+    MIS_REQUIRE(!cnt || Tp >= 1, MIS_ERR_INVALID_INPUT, "LASR LayerNorm: row counts need Tp >= 1");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint16_t> dx, dw, db;
+    DevBuf<uint32_t> dcnt;
+    alloc16(dx, x, (size_t)M * d, BF16_NAN);
+    alloc16(dw, w, d, BF16_NAN);
+    alloc16(db, b, d, BF16_NAN);
+    if (cnt) lsd_counts(dcnt, cnt, (size_t)cdiv(M, Tp));
+    GuardedOut y;
+    y.alloc((size_t)M * d * 2, (size_t)4 * d * 2);
+    LS_LAUNCH(&c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), dx.p, reinterpret_cast<bf16_t*>(y.p()), dw.p, db.p, d, eps, M, cnt ? lsd_int(dcnt) : nullptr, Tp);
+    lsd_sync(c);
+    lsd_fetch(y, y_out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_rope(int device, uint16_t* rows, int M, int ld, int nheads, int Tp, const float* cs, const float* sn) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(rows && cs && sn && M >= 1 && nheads >= 1 && Tp >= 1 && (int64_t)nheads * LS_HD <= ld, MIS_ERR_INVALID_INPUT,
+                "LASR RoPE: rows, both tables, M, Tp >= 1 and 1 <= nheads <= ld / 64 are required");
+    MIS_REQUIRE((int64_t)M * ld <= LSD_MAX_ELEMS && (int64_t)Tp * 32 <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "LASR RoPE: tensor too large");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint32_t> dc, ds;
+    alloc32(dc, cs, (size_t)Tp * 32, F32_NAN);
+    alloc32(ds, sn, (size_t)Tp * 32, F32_NAN);
+    GuardedOut r;
+    r.alloc((size_t)M * ld * 2, (size_t)4 * ld * 2);
+    HIP_CHECK(hipMemcpy(r.p(), rows, r.body, hipMemcpyHostToDevice));
+    const size_t items = (size_t)M * nheads;
+    LS_LAUNCH(&c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), reinterpret_cast<bf16_t*>(r.p()), ld, nheads, Tp,
+              reinterpret_cast<const float*>(dc.p), reinterpret_cast<const float*>(ds.p), (size_t)M);
+    lsd_sync(c);
+    lsd_fetch(r, rows);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_attn(int device, const uint16_t* qkv, int ld, int H, int Hkv, const int32_t* cnt, int B, int Tp, float scale, int ldo,
+                                          uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(qkv && cnt && out && B >= 1 && Tp >= 1 && H >= 1 && Hkv >= 1 && H % Hkv == 0, MIS_ERR_INVALID_INPUT,
+                "LASR attention: qkv, cnt, out, B, Tp >= 1 and Hkv dividing H are required");
+    MIS_REQUIRE(ld % 8 == 0 && (int64_t)(H + 2 * Hkv) * LS_HD <= ld && (int64_t)H * LS_HD <= ldo, MIS_ERR_INVALID_INPUT,
+                "LASR attention: ld >= (H + 2 Hkv) 64 in 16-byte rows, ldo >= H 64");
+    MIS_REQUIRE((int64_t)B * Tp * ld <= LSD_MAX_ELEMS && (int64_t)B * Tp * ldo <= LSD_MAX_ELEMS && B <= 65535 && H <= 65535, MIS_ERR_INVALID_INPUT,
+                "LASR attention: tensor too large");
+    mis_lasr c;
+    lsd_open(c, device);
+    const size_t rows = (size_t)B * Tp;
+    DevBuf<uint16_t> dq;
+    DevBuf<uint32_t> dcnt;
+    alloc16(dq, qkv, rows * ld, BF16_NAN);
+    lsd_counts(dcnt, cnt, B);
+    GuardedOut o;
+    o.alloc(rows * ldo * 2, (size_t)64 * ldo * 2);
+    LS_LAUNCH(&c, k_lasr_attn, dim3(cdiv(Tp, 64), H, B), dim3(256), dq.p, ld, H, Hkv, lsd_int(dcnt), Tp, scale, reinterpret_cast<bf16_t*>(o.p()), ldo);
+    lsd_sync(c);
+    lsd_fetch16_rows(o, rows, ldo, (size_t)H * LS_HD, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_glu_dwconv(int device, int act, const uint16_t* pw, const float* taps, const float* shift, const int32_t* cnt, int B,
+                                                int Tp, int C, int k, uint16_t* out, int32_t* report) {
+    MIS_API_BEGIN
+    if (report) report[0] = -1;
+    MIS_REQUIRE(pw && taps && shift && cnt && out && B >= 1 && Tp >= 1 && C >= 1 && (act == 0 || act == 1), MIS_ERR_INVALID_INPUT,
+                "LASR GLU + depthwise conv: every pointer, B, Tp, C >= 1 and act 0 / 1 are required");
+    MIS_REQUIRE(k >= 1 && k <= LS_DW_MAXK, MIS_ERR_INVALID_INPUT, "LASR GLU + depthwise conv: k %d outside 1..%d (the LDS tile)", k, LS_DW_MAXK);
+    MIS_REQUIRE((int64_t)B * Tp * 2 * C <= LSD_MAX_ELEMS && B <= 65535 && cdiv(C, 64) <= 65535, MIS_ERR_INVALID_INPUT, "LASR GLU + depthwise conv: tensor too large");
+    mis_lasr c;
+    lsd_open(c, device);
+    const size_t rows = (size_t)B * Tp;
+    DevBuf<uint16_t> dp;
+    DevBuf<uint32_t> dt, ds, dcnt;
+    alloc16(dp, pw, rows * 2 * C, BF16_NAN);
+    alloc32(dt, taps, (size_t)k * C, F32_NAN);
+    alloc32(ds, shift, C, F32_NAN);
+    lsd_counts(dcnt, cnt, B);
+    GuardedOut o;
+    o.alloc(rows * C * 2, (size_t)LS_DW_TT * C * 2);
+    const float *tp = reinterpret_cast<const float*>(dt.p), *sp = reinterpret_cast<const float*>(ds.p);
+    bf16_t* op = reinterpret_cast<bf16_t*>(o.p());
+    if (act == 1) LS_LAUNCH(&c, (k_lasr_glu_dwconv<1>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
+    else LS_LAUNCH(&c, (k_lasr_glu_dwconv<0>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
+    lsd_sync(c);
+    if (report) report[0] = act;
+    lsd_fetch(o, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_im2col(int device, const uint16_t* in, const int32_t* cnt, int B, int Tin, int Tout, int C, int ks, int st,
+                                            uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(in && cnt && out && B >= 1 && Tin >= 1 && Tout >= 1 && C >= 8 && C % 8 == 0 && ks >= 1 && st >= 1, MIS_ERR_INVALID_INPUT,
+                "LASR im2col: in, cnt, out, positive B, Tin, Tout, ks, st and C a multiple of 8 are required");
+    MIS_REQUIRE((int64_t)B * Tin * C <= LSD_MAX_ELEMS && (int64_t)B * Tout * ks * C <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "LASR im2col: tensor too large");
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = std::min(cnt[b], Tout);
+        MIS_REQUIRE(n <= 0 || (n - 1) * st + ks <= Tin, MIS_ERR_INVALID_INPUT, "LASR im2col: row %d: frame %lld reads behind the row's %d input frames", b,
+                    (long long)(n - 1), Tin);
+    }
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint16_t> di;
+    DevBuf<uint32_t> dcnt;
+    alloc16(di, in, (size_t)B * Tin * C, BF16_NAN);
+    lsd_counts(dcnt, cnt, B);
+    GuardedOut o;
+    const size_t n = (size_t)B * Tout * ks * C, n8 = n / 8;
+    o.alloc(n * 2, (size_t)4 * ks * C * 2);
+    LS_LAUNCH(&c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), di.p, reinterpret_cast<bf16_t*>(o.p()), lsd_int(dcnt), Tin, Tout, C, ks, st, n8);
+    lsd_sync(c);
+    lsd_fetch(o, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_pack(int device, const float* feats, const int32_t* F, int B, int Fp, int mels, int Kp, uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(feats && F && out && B >= 1 && Fp >= 1 && mels >= 1 && Kp >= mels, MIS_ERR_INVALID_INPUT,
+                "LASR pack: feats, F, out, positive B, Fp and 1 <= mels <= Kp are required");
+    MIS_REQUIRE((int64_t)B * Fp * Kp <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "LASR pack: tensor too large");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint32_t> df, dcnt;
+    alloc32(df, feats, (size_t)B * Fp * mels, F32_NAN);
+    lsd_counts(dcnt, F, B);
+    GuardedOut o;
+    const size_t n = (size_t)B * Fp * Kp;
+    o.alloc(n * 2, (size_t)4 * Kp * 2);
+    LS_LAUNCH(&c, k_lasr_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), reinterpret_cast<const float*>(df.p), lsd_int(dcnt), reinterpret_cast<bf16_t*>(o.p()), Fp,
+              mels, Kp, n);
+    lsd_sync(c);
+    lsd_fetch(o, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_argmax(int device, const float* logits, int M, int V, int32_t* pred) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(logits && pred && M >= 1 && V >= 1 && (int64_t)M * V <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "LASR arg-max: logits, pred and positive M, V are required");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint32_t> dl;
+    alloc32(dl, logits, (size_t)M * V, F32_NAN);
+    GuardedOut o;
+    o.alloc((size_t)M * 4, 256);
+    LS_LAUNCH(&c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), reinterpret_cast<const float*>(dl.p), V, M, reinterpret_cast<int*>(o.p()));
+    lsd_sync(c);
+    lsd_fetch(o, pred);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_lasr_collapse(int device, const int32_t* pred, const int32_t* cnt, int B, int Tp, int blank, int32_t* tokens, int32_t* ntok) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pred && cnt && tokens && ntok && B >= 1 && Tp >= 1 && (int64_t)B * Tp <= LSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "LASR CTC collapse: pred, cnt, tokens, ntok and positive B, Tp are required");
+    mis_lasr c;
+    lsd_open(c, device);
+    DevBuf<uint32_t> dp, dcnt;
+    alloc32(dp, pred, (size_t)B * Tp, 0x7FFFFFFFu);
+    lsd_counts(dcnt, cnt, B);
+    GuardedOut t, n;
+    t.alloc((size_t)B * Tp * 4, (size_t)Tp * 4);
+    n.alloc((size_t)B * 4, 256);
+    LS_LAUNCH(&c, k_lasr_collapse, dim3(B), dim3(256), lsd_int(dp), lsd_int(dcnt), Tp, blank, reinterpret_cast<int*>(t.p()), reinterpret_cast<int*>(n.p()));
+    lsd_sync(c);
+    lsd_fetch(t, tokens);
+    lsd_fetch(n, ntok);
     MIS_API_END
 }
