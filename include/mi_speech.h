@@ -1033,6 +1033,66 @@ mis_status mis_fsmn_vad_detect_raw(mis_fsmn_vad*, const float* pcm, const int64_
 mis_status mis_fsmn_vad_tap(mis_fsmn_vad*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * MossFormer2-SE speech enhancement (csrc/mossformer2.hip; MLXAudioSTS/Models/MossFormer2SE): noisy waveform -> enhanced waveform.
+ * Row b of n_b samples has T_b = n_b < win_len ? 0 : 1 + (n_b - win_len) / win_inc frames and (T_b - 1) win_inc + min(win_len, fft_len)
+ * output samples (0 without a frame).  Front end: x 32768, per frame minus its mean, pre-emphasis (first sample x0 - c x0), symmetric
+ * Hamming / Hann window, FFT of nextpow2(win_len) points, power, Hz triangles from 20 Hz to Nyquist (the Nyquist bin included,
+ * unnormalised), log max(., 1e-10); features = [fbank | delta | delta-delta], the 5-tap filter with edge padding.  Mask network:
+ * GlobalLayerNorm over the row, conv1d_encoder, scaled sinusoidal positions, num_blocks x (FLASH layer, GatedFSMNBlock), two LayerNorms
+ * + skip, PReLU, conv1d_out (speaker 0: the first out_channels outputs, all the reference returns), tanh(output) x sigmoid(output_gate),
+ * conv1_decoder, ReLU.  Synthesis: windowed frames of the x 32768 waveform, fft_len-point transform (any even length), x mask,
+ * inverse transform, x window, overlap-add, / max(sum w^2, 1e-8), / 32768.  All of it exact f32.  One workspace is sized at finalize
+ * for max_batch rows of max_samples: a call allocates nothing and synchronises once; a row's result does not depend on the batch it
+ * travels in or on what lies behind lens[b], bit for bit.
+ * Rejected with MIS_ERR_INVALID_INPUT at create: win_len outside 33..2048, win_inc > win_len, an odd fft_len, out_channels_final !=
+ * fft_len / 2 + 1, in_channels != 3 num_mels, out_channels no multiple of 16, sizes outside the ranges the messages name; at finalize
+ * a tensor missing or misshapen; at a call batch outside 1..max_batch, a row longer than stride or max_samples, too little room in an
+ * output, a null pointer, a handle that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_mossformer2 mis_mossformer2;
+/* the fields of MossFormer2SEConfig the engine reads + the sizes of the workspace */
+typedef struct {
+    int32_t sample_rate, win_len, win_inc, fft_len, num_mels, win_hann, in_channels, out_channels, out_channels_final, num_blocks;
+    int32_t max_batch;                   /* 1..64 rows a call */
+    float   preemphasis;
+    int64_t max_samples;                 /* the longest row a call may carry */
+} mis_mossformer2_config;
+mis_status mis_mossformer2_create(const mis_mossformer2_config*, int device, mis_mossformer2** out);
+/* names below "model.mossformer." of a sanitized checkpoint (norm.weight, conv1d_encoder.weight, pos_enc.inv_freq,
+ * mdl.intra_mdl.mossformerM.layers.N.to_hidden.linear.weight, ...); conv weights [out, 1, in], depthwise taps [C, 17, 1] and [C, 39, 1, 1],
+ * scalars as [1]; host pointers; f32 / f16 / bf16, widened to f32.  finalize names a missing weight and checks every shape. */
+mis_status mis_mossformer2_set_tensor(mis_mossformer2*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_mossformer2_init_synthetic(mis_mossformer2*, uint64_t seed);
+mis_status mis_mossformer2_finalize(mis_mossformer2*);
+void       mis_mossformer2_destroy(mis_mossformer2*);
+/* kernel launches of the last call: enhance 11 + 18 num_blocks, mask 8 + 18 num_blocks, mask_features 6 + 18 num_blocks, features 2,
+ * synthesize 3; 0 when no row had a frame */
+int        mis_mossformer2_launches(const mis_mossformer2*);
+/* T_b and the output length of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_mossformer2_frames(const mis_mossformer2*, const int64_t* lens, int batch, int32_t* frames_out, int64_t* out_lens);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> features f32 [batch, rows, 3 num_mels]; rows >= the longest row's T_b, zeros
+ * behind a row's own.  A batch of rows below one window launches nothing and writes nothing. */
+mis_status mis_mossformer2_features(mis_mossformer2*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* features_out,
+                                    int rows);
+/* the mask network on given features f32 [batch, rows, in_channels], counts[batch] valid rows each (NULL = rows) -> mask f32
+ * [batch, rows, out_channels_final], zeros behind a row's own */
+mis_status mis_mossformer2_mask_features(mis_mossformer2*, const float* features, const int32_t* counts, int batch, int rows, float* mask_out);
+/* front end + mask network: mask f32 [batch, rows, out_channels_final] */
+mis_status mis_mossformer2_mask(mis_mossformer2*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* mask_out, int rows);
+/* MossFormer2SEModel.enhance for a ragged batch: out f32 [batch, out_stride], out_lens[batch] (may be NULL); zeros behind a row's own */
+mis_status mis_mossformer2_enhance(mis_mossformer2*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* out,
+                                   int64_t out_stride, int64_t* out_lens);
+/* the synthesis alone with a given mask f32 [batch, rows, out_channels_final], rows = the longest row's T_b */
+mis_status mis_mossformer2_synthesize(mis_mossformer2*, const float* pcm, const int64_t* lens, int batch, int64_t stride, const float* mask,
+                                      int rows, float* out, int64_t out_stride, int64_t* out_lens);
+/* tensors of the last call, f32 [B, rows, width], zeros behind a row's own rows.  With L = num_blocks: stage 0 fbank, 1 features,
+ * 2 GlobalLayerNorm, 3 encoder + positions, 4 + 2 i FLASH layer i, 5 + 2 i GatedFSMNBlock i; from base = 4 + 2 L: + 0 LayerNorms + skip +
+ * PReLU, + 1 conv1d_out (speaker 0), + 2 tanh(output) | sigmoid(output_gate), + 3 mask, + 4 spectrum [re | im], + 5 windowed
+ * synthesis frames, + 6 waveform [B, samples, 1]; base + 7 + k, k = 0..12: the last block's inner stages (csrc/mossformer2.hip lists
+ * them).  dims[3] receives B, rows, width; out NULL for the dims alone. */
+mis_status mis_mossformer2_tap(mis_mossformer2*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

@@ -322,6 +322,10 @@ mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms);
  * fbank), encoder (+ copy out) */
 mis_status mis_debug_fsmn_vad_timing(const mis_fsmn_vad* c, float* ms);
 
+/* csrc/mossformer2.hip, measurements: device milliseconds of the last call, ms[3] = front end (copy in + fbank + deltas), mask network,
+ * synthesis (+ copy out) */
+mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

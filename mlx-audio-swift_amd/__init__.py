@@ -19,6 +19,7 @@ the Swift shim a maintainer would add):
     smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
     lid.EcapaTdnnLID         <-> class EcapaTdnn (spoken language identification)  (MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift)
     vad.FSMNVAD              <-> class FSMNVAD (voice activity detection)  (MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift)
+    sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -52,6 +53,9 @@ from .lasr import (LasrCTCModel, LasrCTCConfig, LasrEncoderConfig, SentencePiece
 from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitize, fsmn_vad_expected_shapes,  # noqa: F401
                   fsmn_vad_check_weights, fsmn_vad_read_directory, fsmn_vad_read_cmvn, fsmn_vad_postprocess, parse_kaldi_cmvn,
                   chunks_from_segments)
+from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSModelError, mossformer2_sanitize,  # noqa: F401
+                  mossformer2_normalized_key, mossformer2_expected_shapes, mossformer2_check_weights, resolve_sts_model_type,
+                  load_sts_model)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

@@ -167,6 +167,12 @@ class FsmnVadConfigC(C.Structure):
                 + [("sil_pdf_ids", C.c_int32 * 16), ("max_batch", C.c_int32), ("chunk_frames", C.c_int32)])
 
 
+class MossFormer2ConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("sample_rate", "win_len", "win_inc", "fft_len", "num_mels", "win_hann", "in_channels",
+                                          "out_channels", "out_channels_final", "num_blocks", "max_batch")]
+                + [("preemphasis", C.c_float), ("max_samples", C.c_int64)])
+
+
 class LasrConfigC(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads",
                                           "intermediate_size", "hidden_act", "conv_kernel_size", "convolution_bias", "num_mel_bins",
@@ -332,6 +338,19 @@ SYMBOLS = {
     "mis_fsmn_vad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
     "mis_fsmn_vad_detect_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int]),
     "mis_fsmn_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_mossformer2_create": (C.c_int, [C.POINTER(MossFormer2ConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_mossformer2_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_mossformer2_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_mossformer2_finalize": (C.c_int, [_P]),
+    "mis_mossformer2_destroy": (None, [_P]),
+    "mis_mossformer2_launches": (C.c_int, [_P]),
+    "mis_mossformer2_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_mossformer2_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
+    "mis_mossformer2_mask_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_mossformer2_mask": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
+    "mis_mossformer2_enhance": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P]),
+    "mis_mossformer2_synthesize": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int64, _P]),
+    "mis_mossformer2_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_lasr_create": (C.c_int, [C.POINTER(LasrConfigC), C.c_int, C.POINTER(_P)]),
     "mis_lasr_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_lasr_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -498,6 +517,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_lasr_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P]),
     "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
+    "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 

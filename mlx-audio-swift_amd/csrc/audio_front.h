@@ -19,6 +19,15 @@ static inline void fft512_twiddles(float* c, float* s) {
     }
 }
 
+// c[k] = cos(2 pi k / 2048), s[k] = -sin(2 pi k / 2048), k < 1024, formed in double and rounded once (mossformer2.hip).  A shorter
+// power-of-two transform of n points reads every (2048 / n)-th entry: the same angles, the same values.
+static inline void fft2048_twiddles(float* c, float* s) {
+    for (int k = 0; k < 1024; ++k) {
+        c[k] = (float)cos(2.0 * 3.14159265358979323846 * (double)k / 2048);
+        s[k] = (float)-sin(2.0 * 3.14159265358979323846 * (double)k / 2048);
+    }
+}
+
 // ranges[2 m], ranges[2 m + 1] = [first, last) non-zero bin of filter m in the finished fb [bins][nm]; 0, 0 for an all-zero filter
 static inline void filter_bin_ranges(const float* fb, int bins, int nm, int* ranges) {
     for (int m = 0; m < nm; ++m) {
