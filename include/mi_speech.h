@@ -1093,6 +1093,80 @@ mis_status mis_mossformer2_synthesize(mis_mossformer2*, const float* pcm, const 
 mis_status mis_mossformer2_tap(mis_mossformer2*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * Sortformer speaker diarization (csrc/sortformer.hip; Sources/MLXAudioVAD/Models/Sortformer/Sortformer.swift, SortformerConfig.swift,
+ * SortformerFeatures.swift): "who spoke when" for up to num_speakers speakers.  16 kHz mono rows of differing lengths, 1..max_batch a
+ * call.  Row b of n_b samples has F_b = 1 + n_b / 160 feature frames (per-call options: peak normalisation x / (max|x| + 1e-3);
+ * pre-emphasis, symmetric Hann window of 400 in 512, 256 zeros on each side, power spectrum, slaney filters, log(. + 2^-24);
+ * normalize: per-bin mean / unbiased variance over the row's own frames, (x - mean) / (std + 1e-5); pad_to: zero frames appended after
+ * the normalisation up to a multiple of it, which count as frames of the row), then T_b = the three-fold floor((L - 1) / 2) + 1 of F_b
+ * diarization frames behind the depthwise-striding Conv2d stem, the FastConformer blocks (Transformer-XL relative-position attention
+ * with bias_u / bias_v and a per-layer relative_k_proj over the row's own T_b keys; GLU -> depthwise conv -> inference BatchNorm ->
+ * SiLU), encoder_proj + embed_positions, the post-LN BART layers (keys limited to the row's own count) and the speaker sigmoids.
+ * All of it exact f32.  A row's result does not depend on the batch it travels in, on the longest row, or on what lies behind
+ * lens[b]: bit for bit.  The workspace is sized once, at finalize, from max_batch and max_seconds; a call allocates nothing and
+ * synchronises once.  The streaming state (speaker cache, FIFO, compression) is host work (sortformer.py) over pre_encode and
+ * encode_embeddings.
+ * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: sampling_rate / n_fft / hop_length / win_length 16000 / 512 /
+ * 160 / 400; num_mel_bins 8..256; subsampling_factor / subsampling_conv_kernel_size / subsampling_conv_stride 8 / 3 / 2;
+ * subsampling_conv_channels 1..1024; hidden_size and d_model 8..4096; both head sizes whole numbers up to 64; num_key_value_heads =
+ * num_attention_heads; intermediate_size, encoder_ffn_dim 1..16384; both depths 1..64; conv_kernel_size odd, 3..31; fc_d_model /
+ * tf_d_model of the modules equal to hidden_size / d_model; num_speakers 1..64; max_batch 1..64; max_seconds 1..120.  At finalize: a
+ * tensor missing or misshapen.  At a call, before any launch: batch outside 1..max_batch, a row longer than stride or max_seconds,
+ * more frames than the workspace or max_source_positions hold, a count outside 1..the row stride, pad_to not 0 or a divisor of 16, a
+ * null pointer.  A rejected call leaves the handle usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_sortformer mis_sortformer;
+/* FCEncoderConfig, TFEncoderConfig, ModulesConfig (fc_d_model, tf_d_model_modules = its tf_d_model, num_speakers) and ProcessorConfig
+ * fields the engine reads; max_batch / max_seconds size the workspace */
+typedef struct {
+    int32_t hidden_size, num_hidden_layers, num_attention_heads, num_key_value_heads, intermediate_size, num_mel_bins, conv_kernel_size,
+            subsampling_factor, subsampling_conv_channels, subsampling_conv_kernel_size, subsampling_conv_stride, attention_bias, scale_input;
+    int32_t tf_d_model, encoder_layers, encoder_attention_heads, encoder_ffn_dim, max_source_positions, k_proj_bias;
+    int32_t num_speakers, fc_d_model, tf_d_model_modules;
+    int32_t sampling_rate, hop_length, n_fft, win_length;
+    int32_t max_batch, max_seconds;
+    float   layer_norm_eps, preemphasis;
+} mis_sortformer_config;
+mis_status mis_sortformer_create(const mis_sortformer_config*, int device, mis_sortformer** out);
+/* names as SortformerModel.sanitize leaves them: fc_encoder.subsampling.{layers_0,layers_2,layers_3,layers_5,layers_6,linear}.*,
+ * fc_encoder.layers.N.{feed_forward1,feed_forward2}.{linear1,linear2}.*, .self_attn.{q,k,v,o}_proj.*, .self_attn.relative_k_proj.weight,
+ * .self_attn.{bias_u,bias_v}, .conv.{pointwise_conv1,depthwise_conv,pointwise_conv2}.*, .conv.norm.{weight,bias,running_mean,running_var},
+ * .norm_{feed_forward1,self_att,conv,feed_forward2,out}.*, tf_encoder.embed_positions.weight, tf_encoder.layers.N.self_attn.{q,k,v,out}_proj.*,
+ * .{self_attn_layer_norm,final_layer_norm}.*, .{fc1,fc2}.*, sortformer_modules.{encoder_proj,first_hidden_to_hidden,single_hidden_to_spks,
+ * hidden_to_spks}.*; Conv2d weights [out, 3, 3, in / groups], Conv1d weights [out, k, in / groups]; host pointers.  finalize names a
+ * missing weight and checks every shape (hidden_to_spks too, which nothing reads, as in the reference). */
+mis_status mis_sortformer_set_tensor(mis_sortformer*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_sortformer_init_synthetic(mis_sortformer*, uint64_t seed);
+mis_status mis_sortformer_finalize(mis_sortformer*);
+void       mis_sortformer_destroy(mis_sortformer*);
+/* kernel launches of the last call, with L_fc = num_hidden_layers and L_tf = encoder_layers: forward 11 + 15 L_fc + 7 L_tf,
+ * forward_features 8 + 15 L_fc + 7 L_tf, encode_embeddings 4 + 15 L_fc + 7 L_tf, pre_encode 4, features 3 */
+int        mis_sortformer_launches(const mis_sortformer*);
+/* F_b (pad_to applied) and T_b of rows of lens[b] samples (either output may be NULL); pad_to and a row beyond max_seconds are
+ * rejected as by the calls below */
+mis_status mis_sortformer_frames(const mis_sortformer*, const int64_t* lens, int batch, int pad_to, int32_t* F_out, int32_t* T_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> features f32 [batch, Fmax, num_mel_bins], Fmax the longest row's frames,
+ * zeros behind a row's own F_b */
+mis_status mis_sortformer_features(mis_sortformer*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int peak_normalize,
+                                   int normalize, int pad_to, float* feats_out);
+/* SortformerModel.callAsFunction on given features f32 [batch, F, num_mel_bins], frames[batch] valid frames each (NULL = F) ->
+ * probabilities f32 [batch, T of F, num_speakers], zeros behind a row's own T_b */
+mis_status mis_sortformer_forward_features(mis_sortformer*, const float* feats, const int32_t* frames, int batch, int F, float* probs_out);
+/* front end + callAsFunction: probabilities f32 [batch, T of the longest row, num_speakers].  One synchronisation per call. */
+mis_status mis_sortformer_forward(mis_sortformer*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int peak_normalize,
+                                  int normalize, int pad_to, float* probs_out);
+/* fcEncoder.preEncode: features as above -> the stem's embeddings f32 [batch, T of F, hidden_size] (not scaled by sqrt(hidden_size)) */
+mis_status mis_sortformer_pre_encode(mis_sortformer*, const float* feats, const int32_t* frames, int batch, int F, float* emb_out);
+/* fcEncoder.encode onward, what streamingStep runs on [spkcache, fifo, left, chunk, right]: embeddings f32 [batch, T, hidden_size],
+ * counts[batch] valid frames each (NULL = T) -> probabilities f32 [batch, T, num_speakers] */
+mis_status mis_sortformer_encode_embeddings(mis_sortformer*, const float* emb, const int32_t* counts, int batch, int T, float* probs_out);
+/* tensors of the last call - forward, forward_features, pre_encode or encode_embeddings; after features alone, which leaves no
+ * embeddings, the tap is rejected with MIS_ERR_NOT_INITIALIZED - f32, zero rows behind a row's own T_b.  With L = num_hidden_layers, Lt = encoder_layers: stage 0 the stem's
+ * embeddings [B, T, hidden_size], 1..L that Conformer block, L + 1 encoder_proj + positions [B, T, d_model], L + 2 .. L + 1 + Lt that BART
+ * layer, L + 2 + Lt the probabilities [B, T, num_speakers].  dims[3] receives B, T, width; out NULL for the dims alone. */
+mis_status mis_sortformer_tap(mis_sortformer*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

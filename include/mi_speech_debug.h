@@ -326,6 +326,11 @@ mis_status mis_debug_fsmn_vad_timing(const mis_fsmn_vad* c, float* ms);
  * synthesis (+ copy out) */
 mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);
 
+/* csrc/sortformer.hip, measurements: ms NULL switches the timestamps of mis_sortformer_forward on; else device milliseconds of the
+ * last call, which must have been mis_sortformer_forward (MIS_ERR_NOT_INITIALIZED otherwise): ms[4] = front end, stem, Conformer blocks,
+ * projection + BART layers + head */
+mis_status mis_debug_sortformer_timing(mis_sortformer* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

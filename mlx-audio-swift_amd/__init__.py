@@ -19,6 +19,7 @@ the Swift shim a maintainer would add):
     smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
     lid.EcapaTdnnLID         <-> class EcapaTdnn (spoken language identification)  (MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift)
     vad.FSMNVAD              <-> class FSMNVAD (voice activity detection)  (MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift)
+    sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
     sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
@@ -56,6 +57,9 @@ from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitiz
 from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSModelError, mossformer2_sanitize,  # noqa: F401
                   mossformer2_normalized_key, mossformer2_expected_shapes, mossformer2_check_weights, resolve_sts_model_type,
                   load_sts_model)
+from .sortformer import (SortformerModel, SortformerConfig, FCEncoderConfig, TFEncoderConfig, ModulesConfig, ProcessorConfig,  # noqa: F401
+                         DiarizationSegment, DiarizationOutput, StreamingState, sortformer_sanitize, sortformer_expected_keys,
+                         preds_to_segments, trim_silence, maybe_compress_state)
 
 __all__ = ["SNAC", "SNACConfig", "LlamaTTSModel", "LlamaTTSConfiguration", "OrpheusTokens", "GenerateParameters",
            "AudioGenerationError", "AudioGenerationInfo", "TokenEvent", "InfoEvent", "AudioEvent", "deinterleave",

@@ -182,6 +182,16 @@ class LasrConfigC(C.Structure):
                    ("feed_forward_residual_weights", C.c_float * 2)])
 
 
+class SortformerConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads", "intermediate_size",
+                                          "num_mel_bins", "conv_kernel_size", "subsampling_factor", "subsampling_conv_channels",
+                                          "subsampling_conv_kernel_size", "subsampling_conv_stride", "attention_bias", "scale_input",
+                                          "tf_d_model", "encoder_layers", "encoder_attention_heads", "encoder_ffn_dim", "max_source_positions",
+                                          "k_proj_bias", "num_speakers", "fc_d_model", "tf_d_model_modules", "sampling_rate", "hop_length",
+                                          "n_fft", "win_length", "max_batch", "max_seconds")]
+                + [("layer_norm_eps", C.c_float), ("preemphasis", C.c_float)])
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -363,6 +373,19 @@ SYMBOLS = {
     "mis_lasr_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
     "mis_stt_lasr_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P]),
     "mis_lasr_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_sortformer_create": (C.c_int, [C.POINTER(SortformerConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_sortformer_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_sortformer_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_sortformer_finalize": (C.c_int, [_P]),
+    "mis_sortformer_destroy": (None, [_P]),
+    "mis_sortformer_launches": (C.c_int, [_P]),
+    "mis_sortformer_frames": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "mis_sortformer_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_sortformer_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_sortformer_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_sortformer_pre_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_sortformer_encode_embeddings": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_sortformer_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -518,6 +541,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
+    "mis_debug_sortformer_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 
