@@ -2,10 +2,10 @@
 // range of non-zero bins.  Both engines promise results that are bit for bit independent of the batch, and both kernels read these
 // tables, so they are formed in one place; tests/test_gpu_front_bits.py holds the engines' outputs to recorded hashes.
 //
-// The kernels themselves (k_lasr_stft_mel, k_fvad_fbank) keep their own copy of the butterfly loop and of the filter dot: moved into
-// shared __forceinline__ functions, the compiler scheduled and allocated both kernels differently (other SGPR / VGPR counts), and the
-// engines are held to an unchanged instruction stream.  A third fbank engine starts from these tables and from block_sum_256 /
-// block_max_256 in common.h.
+// A shared device piece is held to what these engines promise a caller: a row's bits in any batch (the recorded hashes), and the
+// time, measured against the parent (f32_tile.h is shared on those terms; DESIGN.md has what was measured).  The FFT kernels keep
+// their own copy of the butterfly loop and of the filter dot: ten lines each, and the kernels differ around them.  A further fbank
+// engine starts from these tables and from block_sum_256 / block_max_256 in common.h.
 #pragma once
 #include <math.h>
 #include <algorithm>

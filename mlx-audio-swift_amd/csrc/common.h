@@ -206,6 +206,29 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// mean and 1 / sqrt(variance + eps) of one frame of n values x(c), one wave over the frame; every lane gets both.  Two passes in
+// lane-strided order, each met in wave_sum's fixed order: the sum, then the squared distances to the mean.
+template <class Val>
+__device__ __forceinline__ void wave_mean_rstd_of(Val x, int n, float eps, float& mean, float& rstd) {
+    const int lane = threadIdx.x & 63;
+    float s = 0.0f;
+    for (int c = lane; c < n; c += 64) s += x(c);
+    mean = wave_sum(s) / (float)n;
+    float q = 0.0f;
+    for (int c = lane; c < n; c += 64) { const float v = x(c) - mean; q = fmaf(v, v, q); }
+    rstd = 1.0f / sqrtf(wave_sum(q) / (float)n + eps);
+}
+__device__ __forceinline__ void wave_mean_rstd(const float* x, int n, float eps, float& mean, float& rstd) {
+    wave_mean_rstd_of([x](int c) { return x[c]; }, n, eps, mean, rstd);
+}
+
+// a launch on the handle's stream that counts itself (the engines that report launches per call)
+#define MIS_LAUNCH(c, kernel, grid, block, ...)                                 \
+    do {                                                                        \
+        hipLaunchKernelGGL(kernel, grid, block, 0, (c)->stream, __VA_ARGS__);   \
+        (c)->launches += 1;                                                     \
+    } while (0)
+
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));

@@ -15,7 +15,7 @@
 //                   every dimension guarded (60 mels, C / 8 channels per Res2Net chunk).  Loads: activations (optionally the sum of two, the
 //                   Res2Net chunk + previous output), windowed frames of the zero-padded signal (the DFT as a 400 -> 402 product), or the
 //                   power of a spectrum (the mel filters).  Epilogues: plain, BN(ReLU(. + bias)), tanh of that, 10 log10 max(., 1e-10);
-//                   a per-row bias carries the broadcast mean / std columns of the pooling's attention input.
+//                   a per-row bias carries the broadcast mean / std columns of the pooling's attention input. (On f32_tile.h.)
 //   k_lid_clamp     the row's maximum over its own frames and all mels, minus 80 dB, as a floor (powerToDB topDB, DSP.swift:68-70)
 //   k_lid_meannorm  sentenceMeanNormalize (EcapaTdnnLID.swift:84-86)
 //   k_lid_time_stats  per-row, per-channel mean over the valid frames (SE squeeze) and sqrt(population variance + 1e-9) (pooling context)
@@ -28,6 +28,7 @@
 // The Res2Net chain runs as scale - 1 launches of k_lid_gemm per block (chunk 0 is stored twice by tdnn1's epilogue): 49 launches a call
 // at the published depth.  No allocation and no synchronisation between the copy in and the copy out.
 #include "common.h"
+#include "f32_tile.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -38,9 +39,6 @@
 #define LID_NFFT 400
 #define LID_HOP 160
 #define LID_NBIN 201
-#define LID_TT 64
-#define LID_TC 64
-#define LID_KC 32
 #define LID_BN_EPS 1e-5           // MLXNN.BatchNorm default
 
 enum { LID_EPI_PLAIN = 0, LID_EPI_RELU_BN = 1, LID_EPI_RELU_BN_TANH = 2, LID_EPI_DB = 3 };
@@ -58,31 +56,25 @@ struct LidGemm {
 };
 
 __global__ void __launch_bounds__(256) k_lid_gemm(LidGemm p) {
-    __shared__ float As[LID_TT][LID_KC + 1];
-    __shared__ float Bs[LID_TC][LID_KC + 1];
-    const int b = blockIdx.z, t0 = blockIdx.x * LID_TT, c0 = blockIdx.y * LID_TC;
+    constexpr int TT = F32_TILE, TC = F32_TILE;
+    __shared__ float As[TT][F32_KC + 1];
+    __shared__ float Bs[TC][F32_KC + 1];
+    const int b = blockIdx.z, t0 = blockIdx.x * TT, c0 = blockIdx.y * TC;
     const int Tb = p.T[b], tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t row0 = (size_t)b * p.Ts;
     if (t0 >= Tb) {                                                   // nothing of the row here: the padding is written as zeros
-        for (int i = tid; i < LID_TT * LID_TC; i += 256) {
-            const int t = t0 + (i >> 6), co = c0 + (i & 63);
-            if (t < p.Ts && co < p.Cout) {
-                p.Y[(row0 + t) * p.ldy + co] = 0.0f;
-                if (p.Y2 && co < p.y2_cols) p.Y2[(row0 + t) * p.ldy2 + co] = 0.0f;
-            }
-        }
+        f32_tile_zero<TT, TC>(p.Y, p.ldy, row0, t0, c0, p.Ts, p.Cout);
+        if (p.Y2) f32_tile_zero<TT, TC>(p.Y2, p.ldy2, row0, t0, c0, p.Ts, min(p.Cout, p.y2_cols));
         return;
     }
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    const int wt = (wave & 1) * 32, wc = (wave >> 1) * 32, half = (p.taps - 1) / 2, kh = lane >> 5, l31 = lane & 31;
+    f32x16_t acc[1] = {};
+    const int wt = (wave & 1) * 32, wc = (wave >> 1) * 32, kh = lane >> 5, l31 = lane & 31, half = (p.taps - 1) / 2;
     const int64_t ns = p.load == LID_LOAD_FRAMES ? p.nsamp[b] : 0;
     for (int j = 0; j < p.taps; ++j) {
         const int shift = (j - half) * p.dil;
-        for (int ci0 = 0; ci0 < p.Cin; ci0 += LID_KC) {
+        for (int ci0 = 0; ci0 < p.Cin; ci0 += F32_KC) {
 #pragma unroll
-            for (int n = 0; n < LID_TT * LID_KC / 256; ++n) {
+            for (int n = 0; n < TT * F32_KC / 256; ++n) {
                 const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), t = t0 + r + shift;
                 float v = 0.0f;
                 if (ci < p.Cin && t >= 0 && t < Tb) {
@@ -100,28 +92,25 @@ __global__ void __launch_bounds__(256) k_lid_gemm(LidGemm p) {
                 As[r][i & 31] = v;
             }
 #pragma unroll
-            for (int n = 0; n < LID_TC * LID_KC / 256; ++n) {
+            for (int n = 0; n < TC * F32_KC / 256; ++n) {
                 const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), co = c0 + r;
                 Bs[r][i & 31] = (co < p.Cout && ci < p.Cin) ? p.W[(size_t)co * p.ldw + (size_t)j * p.Cin + ci] : 0.0f;
             }
             __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < LID_KC; kk += 2)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wt + l31][kk + kh], Bs[wc + l31][kk + kh], acc, 0, 0, 0);
+            f32_tile_mfma(As, Bs, wt + l31, wc + l31, kh, acc);
             __syncthreads();
         }
     }
-    // C/D: column (output channel) = lane & 31, row (frame) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int co = c0 + wc + l31;
+    const int co = c0 + wc + l31;                                   // C/D: column = lane & 31, row = f32_tile_row(r, lane >> 5)
     if (co >= p.Cout) return;
     float add = p.bias ? p.bias[co] : 0.0f;
     if (p.rowbias) add += p.rowbias[(size_t)b * p.Cout + co];
     const float s = p.bn_s ? p.bn_s[co] : 1.0f, sh = p.bn_b ? p.bn_b[co] : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int t = t0 + wt + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int t = t0 + wt + f32_tile_row(r, kh);
         if (t >= p.Ts) continue;
-        float v = acc[r] + add;
+        float v = acc[0][r] + add;
         if (p.epi == LID_EPI_RELU_BN || p.epi == LID_EPI_RELU_BN_TANH) {
             v = fmaxf(v, 0.0f) * s + sh;
             if (p.epi == LID_EPI_RELU_BN_TANH) v = tanhf(v);
@@ -588,7 +577,7 @@ extern "C" mis_status mis_ecapa_lid_init_synthetic(mis_ecapa_lid* c, uint64_t se
 static int lid_launch_gemm(mis_ecapa_lid* c, LidGemm g, int B, int Ts) {
     g.T = c->frames.p; g.Ts = Ts;
     if (!g.ldw) g.ldw = g.taps * g.Cin;
-    hipLaunchKernelGGL(k_lid_gemm, dim3(cdiv(Ts, LID_TT), cdiv(g.Cout, LID_TC), B), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(k_lid_gemm, dim3(cdiv(Ts, F32_TILE), cdiv(g.Cout, F32_TILE), B), dim3(256), 0, c->stream, g);
     return 1;
 }
 static LidGemm lid_tdnn_gemm(const LidTdnn& t, const float* X, int ldx, float* Y, int ldy) {

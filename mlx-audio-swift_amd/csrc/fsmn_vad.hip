@@ -19,12 +19,13 @@
 //   k_fvad_lfr     the stacked, CMVN-ed features as a tensor (features / tap only: the forward pass gathers them in in_linear1's load)
 //   k_fvad_gemm    the one contraction, exact f32 on v_mfma_f32_32x32x2_f32, every dimension guarded.  Loads: activations, the LFR + CMVN
 //                  gather from the fbank, or the memory block p + depthwise_causal_conv(p) formed from a time tile + lorder - 1 rows of
-//                  halo in LDS.  Epilogues: bias / none, ReLU, or (256-column tile) bias + softmax + the silence sum.
+//                  halo in LDS.  Epilogues: bias / none, ReLU, or (256-column tile) bias + softmax + the silence sum. (On f32_tile.h.)
 //
 // A chunk is 5 + 2 fsmn_layers launches (13 at the published depth): fbank, in_linear1 (LFR load), in_linear2, per layer linear and
 // affine (memory-block load), out_linear1, out_linear2 + softmax.  No allocation and one synchronisation per call.
 #include "common.h"
 #include "audio_front.h"
+#include "f32_tile.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -34,7 +35,6 @@
 #define FV_MAX_BATCH 64
 #define FV_NFFT 512
 #define FV_BINS 256               // bins 0..255 carry filters; the reference's loop never reaches the Nyquist bin (:943)
-#define FV_KC 32
 #define FV_LMAX 64                // lorder
 #define FV_MAX_SIL 16
 #define FV_TIMED_CHUNKS 128
@@ -142,42 +142,35 @@ template <int WT, int CT>
 __global__ void __launch_bounds__(256) k_fvad_gemm(FvGemm p) {
     constexpr int WCW = 4 / WT, TT = 32 * WT, TC = 32 * WCW * CT;
     constexpr bool WIDE = CT > 1;
-    __shared__ float As[TT][FV_KC + 1];
-    __shared__ float Bs[TC][FV_KC + 1];
-    __shared__ float Hs[WIDE ? 1 : TT + FV_LMAX - 1][FV_KC + 1];
-    __shared__ float Ws[WIDE ? 1 : FV_KC][FV_LMAX + 1];
+    __shared__ float As[TT][F32_KC + 1];
+    __shared__ float Bs[TC][F32_KC + 1];
+    __shared__ float Hs[WIDE ? 1 : TT + FV_LMAX - 1][F32_KC + 1];
+    __shared__ float Ws[WIDE ? 1 : F32_KC][FV_LMAX + 1];
     const int b = blockIdx.z, t0 = blockIdx.x * TT, c0 = blockIdx.y * TC, nr = p.g.nr;
     const int cnt = fv_count(p.g, b), tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t row0 = (size_t)b * nr;
     if (t0 >= cnt) {                                                  // nothing of the row here: zeros
-        for (int i = tid; i < TT * TC; i += 256) {
-            const int t = t0 + i / TC, co = c0 + i % TC;
-            if (t < nr && co < p.Cout) p.Y[(row0 + t) * p.ldy + co] = 0.0f;
-        }
+        f32_tile_zero<TT, TC>(p.Y, p.ldy, row0, t0, c0, nr, p.Cout);
         if (p.epi == FV_EPI_SOFTMAX && tid < TT && t0 + tid < nr) p.sil[row0 + t0 + tid] = 0.0f;
         return;
     }
-    f32x16_t acc[CT];
-#pragma unroll
-    for (int a = 0; a < CT; ++a)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][r] = 0.0f;
+    f32x16_t acc[CT] = {};
     const int wt = (wave % WT) * 32, wc = (wave / WT) * CT * 32, kh = lane >> 5, l31 = lane & 31;
-    for (int ci0 = 0; ci0 < p.Cin; ci0 += FV_KC) {
+    for (int ci0 = 0; ci0 < p.Cin; ci0 += F32_KC) {
         if constexpr (!WIDE) {
             if (p.load == FV_LOAD_MEM) {
                 const int L = p.lorder, nh = TT + L - 1;
-                for (int i = tid; i < nh * FV_KC; i += 256) {
+                for (int i = tid; i < nh * F32_KC; i += 256) {
                     const int h = i >> 5, ci = ci0 + (i & 31), t = t0 - (L - 1) + h;
                     Hs[h][i & 31] = (ci < p.Cin && t >= 0 && t < cnt) ? p.X[(row0 + t) * p.ldx + ci] : 0.0f;
                 }
-                for (int i = tid; i < FV_KC * L; i += 256) {
+                for (int i = tid; i < F32_KC * L; i += 256) {
                     const int c = i / L, j = i - c * L;
                     Ws[c][j] = ci0 + c < p.Cin ? p.dw[(size_t)(ci0 + c) * L + j] : 0.0f;
                 }
                 __syncthreads();
 #pragma unroll
-                for (int n = 0; n < TT * FV_KC / 256; ++n) {          // x[t] + sum_j w[j] x[t + j - (L - 1)], taps ascending
+                for (int n = 0; n < TT * F32_KC / 256; ++n) {          // x[t] + sum_j w[j] x[t + j - (L - 1)], taps ascending
                     const int i = tid + n * 256, r = i >> 5, cc = i & 31;
                     float a = 0.0f;
                     for (int j = 0; j < L; ++j) a = fmaf(Ws[cc][j], Hs[r + j][cc], a);
@@ -187,7 +180,7 @@ __global__ void __launch_bounds__(256) k_fvad_gemm(FvGemm p) {
         }
         if (WIDE || p.load != FV_LOAD_MEM) {
 #pragma unroll
-            for (int n = 0; n < TT * FV_KC / 256; ++n) {
+            for (int n = 0; n < TT * F32_KC / 256; ++n) {
                 const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), t = t0 + r;
                 float v = 0.0f;
                 if (ci < p.Cin && t < cnt) v = p.load == FV_LOAD_LFR ? fv_lfr_value(p.lfr, p.g, b, t, ci) : p.X[(row0 + t) * p.ldx + ci];
@@ -195,20 +188,15 @@ __global__ void __launch_bounds__(256) k_fvad_gemm(FvGemm p) {
             }
         }
 #pragma unroll
-        for (int n = 0; n < TC * FV_KC / 256; ++n) {
+        for (int n = 0; n < TC * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), co = c0 + r;
             Bs[r][i & 31] = (co < p.Cout && ci < p.Cin) ? p.W[(size_t)co * p.Cin + ci] : 0.0f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < FV_KC; kk += 2) {
-            const float a = As[wt + l31][kk + kh];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[wc + ct * 32 + l31][kk + kh], acc[ct], 0, 0, 0);
-        }
+        f32_tile_mfma(As, Bs, wt + l31, wc + l31, kh, acc);
         __syncthreads();
     }
-    // C/D: column (output channel) = lane & 31, row (frame) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // C/D: column (output channel) = lane & 31, row (frame) = f32_tile_row(r, lane >> 5)
     if constexpr (WIDE) {
         if (p.epi == FV_EPI_SOFTMAX) {                                // (one block column: c0 = 0, Cout <= TC)
             float* Ls = &Bs[0][0];                                    // logits [TT][TC + 1]
@@ -217,7 +205,7 @@ __global__ void __launch_bounds__(256) k_fvad_gemm(FvGemm p) {
                 const int co = wc + ct * 32 + l31;
                 const float add = (co < p.Cout && p.bias) ? p.bias[co] : 0.0f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) Ls[((r & 3) + 8 * (r >> 2) + 4 * kh) * (TC + 1) + co] = acc[ct][r] + add;
+                for (int r = 0; r < 16; ++r) Ls[f32_tile_row(r, kh) * (TC + 1) + co] = acc[ct][r] + add;
             }
             __syncthreads();
             for (int rr = wave; rr < TT; rr += 4) {                   // a wave per frame; the 64 partial maxima / sums meet in a fixed order
@@ -248,7 +236,7 @@ __global__ void __launch_bounds__(256) k_fvad_gemm(FvGemm p) {
         const float add = p.bias ? p.bias[co] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int t = t0 + wt + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            const int t = t0 + wt + f32_tile_row(r, kh);
             if (t >= nr) continue;
             float v = acc[ct][r] + add;
             if (p.epi == FV_EPI_RELU) v = fmaxf(v, 0.0f);

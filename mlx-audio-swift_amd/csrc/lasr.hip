@@ -80,12 +80,6 @@ struct mis_lasr {
     bool timed = false;
 };
 
-#define LS_LAUNCH(c, kernel, grid, block, ...)                                  \
-    do {                                                                        \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (c)->stream, __VA_ARGS__);   \
-        (c)->launches += 1;                                                     \
-    } while (0)
-
 // ---------------------------------------------------------------------------- frame counts
 static inline int ls_frames(int64_t n) { return (int)(1 + n / LS_HOP); }
 static inline int ls_conv_out(int t, int k, int s) { return t >= k ? (t - k) / s + 1 : 0; }
@@ -545,8 +539,8 @@ template <int EPI>
 static int ls_gemm_epi(mis_lasr* c, const LasrGemm& p, int tile) {
     // the 128 x 128 tile once its grid fills the chip, the 64 x 64 tile (four times the blocks) below that
     const bool big = tile ? tile == 4 : (long)cdiv(p.N, 128) * cdiv(p.M, 128) >= 256;
-    if (big) LS_LAUNCH(c, (k_lasr_gemm<EPI, 4>), dim3(cdiv(p.N, 128), cdiv(p.M, 128)), dim3(256), p);
-    else LS_LAUNCH(c, (k_lasr_gemm<EPI, 2>), dim3(cdiv(p.N, 64), cdiv(p.M, 64)), dim3(256), p);
+    if (big) MIS_LAUNCH(c, (k_lasr_gemm<EPI, 4>), dim3(cdiv(p.N, 128), cdiv(p.M, 128)), dim3(256), p);
+    else MIS_LAUNCH(c, (k_lasr_gemm<EPI, 2>), dim3(cdiv(p.N, 64), cdiv(p.M, 64)), dim3(256), p);
     return big ? 4 : 2;
 }
 static int ls_gemm(mis_lasr* c, int epi, const bf16_t* X, int ldx, const bf16_t* W, const bf16_t* bias, void* C, int M, int N, int K,
@@ -863,9 +857,9 @@ static void ls_front(mis_lasr* c, const float* pcm, const int64_t* lens, int bat
     const int64_t ws = std::min<int64_t>(stride, c->maxN);
     HIP_CHECK(hipMemcpy2DAsync(c->pcm.p, ws * 4, pcm, stride * 4, ws * 4, batch, hipMemcpyDefault, s));
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[0], s));
-    LS_LAUNCH(c, k_lasr_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF.p, c->window, c->tw_cos, c->tw_sin, c->fb,
+    MIS_LAUNCH(c, k_lasr_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF.p, c->window, c->tw_cos, c->tw_sin, c->fb,
               c->fb_range, c->melraw.p, Fp, c->mels);
-    LS_LAUNCH(c, k_lasr_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF.p, c->feats.p, Fp, c->mels);
+    MIS_LAUNCH(c, k_lasr_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF.p, c->feats.p, Fp, c->mels);
 }
 
 // c->feats -> stem -> blocks -> out_norm (c->enc_out).  stop: -1 everything, 0 behind the stem, 1 .. L behind that block.
@@ -877,20 +871,20 @@ static void ls_encoder(mis_lasr* c, int stop) {
                 cva = c->cfg.conv_residual_weights[0], cvb = c->cfg.conv_residual_weights[1];
     // ---- stem (:67-72)
     const size_t n0 = (size_t)B * Fp * c->Kp;
-    LS_LAUNCH(c, k_lasr_pack, dim3((unsigned)((n0 + 255) / 256)), dim3(256), c->feats.p, c->cntF.p, c->x0.p, Fp, c->mels, c->Kp, n0);
+    MIS_LAUNCH(c, k_lasr_pack, dim3((unsigned)((n0 + 255) / 256)), dim3(256), c->feats.p, c->cntF.p, c->x0.p, Fp, c->mels, c->Kp, n0);
     ls_gemm(c, LG_RELU, c->x0.p, c->Kp, c->d0w, c->d0b, c->h0.p, B * Fp, d, c->Kp);
     size_t n8 = (size_t)B * T1p * ks * d / 8;
-    LS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->h0.p, c->col.p, c->cnt1.p, Fp, T1p, d, ks, st, n8);
+    MIS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->h0.p, c->col.p, c->cnt1.p, Fp, T1p, d, ks, st, n8);
     ls_gemm(c, LG_RELU, c->col.p, ks * d, c->c0w, c->c0b, c->c0.p, B * T1p, d, ks * d);
     n8 = (size_t)B * T2p * ks * d / 8;
-    LS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->c0.p, c->col.p, c->cnt2.p, T1p, T2p, d, ks, st, n8);
+    MIS_LAUNCH(c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), c->c0.p, c->col.p, c->cnt2.p, T1p, T2p, d, ks, st, n8);
     ls_gemm(c, LG_RELU, c->col.p, ks * d, c->c1w, c->c1b, c->c1.p, M, c->cc, ks * d);
     ls_gemm(c, LG_BIAS, c->c1.p, c->cc, c->d1w, c->d1b, c->h.p, M, d, c->cc, nullptr, 0.0f, 0.0f, c->cnt2.p, T2p);
     if (stop == 0) return;
     // ---- blocks (:226-245), 16 launches each
     const float scale = 1.0f / sqrtf((float)LS_HD);
     auto ln = [&](const bf16_t* x, bf16_t* y, const bf16_t* w, const bf16_t* b, const int* cnt) {
-        LS_LAUNCH(c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), x, y, w, b, d, eps, M, cnt, T2p);
+        MIS_LAUNCH(c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), x, y, w, b, d, eps, M, cnt, T2p);
     };
     for (int li = 0; li < c->L; ++li) {
         const LsLayer& l = c->layers[li];
@@ -900,15 +894,15 @@ static void ls_encoder(mis_lasr* c, int stop) {
         ln(c->h.p, c->x.p, l.ln_attw, l.ln_attb, nullptr);
         ls_gemm(c, LG_BIAS, c->x.p, d, l.wqkv, l.bqkv, c->qkv.p, M, NQ, d);
         const size_t items = (size_t)M * (c->H + c->Hk);
-        LS_LAUNCH(c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), c->qkv.p, NQ, c->H + c->Hk, T2p, c->rope_cos, c->rope_sin, (size_t)M);
-        LS_LAUNCH(c, k_lasr_attn, dim3(cdiv(T2p, 64), c->H, B), dim3(256), c->qkv.p, NQ, c->H, c->Hk, c->cnt2.p, T2p, scale, c->att.p, d);
+        MIS_LAUNCH(c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), c->qkv.p, NQ, c->H + c->Hk, T2p, c->rope_cos, c->rope_sin, (size_t)M);
+        MIS_LAUNCH(c, k_lasr_attn, dim3(cdiv(T2p, 64), c->H, B), dim3(256), c->qkv.p, NQ, c->H, c->Hk, c->cnt2.p, T2p, scale, c->att.p, d);
         ls_gemm(c, LG_AXPBY, c->att.p, d, l.wo, l.bo, c->h.p, M, d, d, c->h.p, 1.0f, 1.0f);
         ln(c->h.p, c->x.p, l.ln_cvw, l.ln_cvb, nullptr);
         ls_gemm(c, LG_BIAS, c->x.p, d, l.pw1, l.pw1b, c->ff.p, M, 2 * d, d);
         if (c->cfg.hidden_act == 1)
-            LS_LAUNCH(c, (k_lasr_glu_dwconv<1>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
+            MIS_LAUNCH(c, (k_lasr_glu_dwconv<1>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
         else
-            LS_LAUNCH(c, (k_lasr_glu_dwconv<0>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
+            MIS_LAUNCH(c, (k_lasr_glu_dwconv<0>), dim3(cdiv(T2p, LS_DW_TT), cdiv(d, 64), B), dim3(256), c->ff.p, l.dw, l.dwshift, c->cnt2.p, c->att.p, T2p, d, c->ck);
         ls_gemm(c, LG_AXPBY, c->att.p, d, l.pw2, l.pw2b, c->h.p, M, d, d, c->h.p, cva, cvb);
         ln(c->h.p, c->x.p, l.ln_ff2w, l.ln_ff2b, nullptr);
         ls_gemm(c, act, c->x.p, d, l.ff2_w1, l.ff2_b1, c->ff.p, M, f, d);
@@ -991,8 +985,8 @@ extern "C" mis_status mis_stt_lasr_generate(mis_lasr* c, const float* pcm, const
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[2], s));
     ls_head(c);
     const int M = batch * c->T2p;
-    LS_LAUNCH(c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), c->logits.p, c->V, M, c->pred.p);
-    LS_LAUNCH(c, k_lasr_collapse, dim3(batch), dim3(256), c->pred.p, c->cnt2.p, c->T2p, c->cfg.pad_token_id, c->tokens.p, c->ntok.p);
+    MIS_LAUNCH(c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), c->logits.p, c->V, M, c->pred.p);
+    MIS_LAUNCH(c, k_lasr_collapse, dim3(batch), dim3(256), c->pred.p, c->cnt2.p, c->T2p, c->cfg.pad_token_id, c->tokens.p, c->ntok.p);
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[3], s));
     int32_t* ht = c->host_tokens.p;
     HIP_CHECK(hipMemcpyAsync(ht, c->tokens.p, (size_t)M * 4, hipMemcpyDeviceToHost, s));
@@ -1146,7 +1140,7 @@ extern "C" mis_status mis_debug_lasr_ln(int device, const uint16_t* x, const uin
     if (cnt) lsd_counts(dcnt, cnt, (size_t)cdiv(M, Tp));
     GuardedOut y;
     y.alloc((size_t)M * d * 2, (size_t)4 * d * 2);
-    LS_LAUNCH(&c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), dx.p, reinterpret_cast<bf16_t*>(y.p()), dw.p, db.p, d, eps, M, cnt ? lsd_int(dcnt) : nullptr, Tp);
+    MIS_LAUNCH(&c, k_lasr_ln, dim3(cdiv(M, 4)), dim3(256), dx.p, reinterpret_cast<bf16_t*>(y.p()), dw.p, db.p, d, eps, M, cnt ? lsd_int(dcnt) : nullptr, Tp);
     lsd_sync(c);
     lsd_fetch(y, y_out);
     MIS_API_END
@@ -1166,7 +1160,7 @@ extern "C" mis_status mis_debug_lasr_rope(int device, uint16_t* rows, int M, int
     r.alloc((size_t)M * ld * 2, (size_t)4 * ld * 2);
     HIP_CHECK(hipMemcpy(r.p(), rows, r.body, hipMemcpyHostToDevice));
     const size_t items = (size_t)M * nheads;
-    LS_LAUNCH(&c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), reinterpret_cast<bf16_t*>(r.p()), ld, nheads, Tp,
+    MIS_LAUNCH(&c, k_lasr_rope, dim3((unsigned)((items + 3) / 4)), dim3(256), reinterpret_cast<bf16_t*>(r.p()), ld, nheads, Tp,
               reinterpret_cast<const float*>(dc.p), reinterpret_cast<const float*>(ds.p), (size_t)M);
     lsd_sync(c);
     lsd_fetch(r, rows);
@@ -1191,7 +1185,7 @@ extern "C" mis_status mis_debug_lasr_attn(int device, const uint16_t* qkv, int l
     lsd_counts(dcnt, cnt, B);
     GuardedOut o;
     o.alloc(rows * ldo * 2, (size_t)64 * ldo * 2);
-    LS_LAUNCH(&c, k_lasr_attn, dim3(cdiv(Tp, 64), H, B), dim3(256), dq.p, ld, H, Hkv, lsd_int(dcnt), Tp, scale, reinterpret_cast<bf16_t*>(o.p()), ldo);
+    MIS_LAUNCH(&c, k_lasr_attn, dim3(cdiv(Tp, 64), H, B), dim3(256), dq.p, ld, H, Hkv, lsd_int(dcnt), Tp, scale, reinterpret_cast<bf16_t*>(o.p()), ldo);
     lsd_sync(c);
     lsd_fetch16_rows(o, rows, ldo, (size_t)H * LS_HD, out);
     MIS_API_END
@@ -1218,8 +1212,8 @@ extern "C" mis_status mis_debug_lasr_glu_dwconv(int device, int act, const uint1
     o.alloc(rows * C * 2, (size_t)LS_DW_TT * C * 2);
     const float *tp = reinterpret_cast<const float*>(dt.p), *sp = reinterpret_cast<const float*>(ds.p);
     bf16_t* op = reinterpret_cast<bf16_t*>(o.p());
-    if (act == 1) LS_LAUNCH(&c, (k_lasr_glu_dwconv<1>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
-    else LS_LAUNCH(&c, (k_lasr_glu_dwconv<0>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
+    if (act == 1) MIS_LAUNCH(&c, (k_lasr_glu_dwconv<1>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
+    else MIS_LAUNCH(&c, (k_lasr_glu_dwconv<0>), dim3(cdiv(Tp, LS_DW_TT), cdiv(C, 64), B), dim3(256), dp.p, tp, sp, lsd_int(dcnt), op, Tp, C, k);
     lsd_sync(c);
     if (report) report[0] = act;
     lsd_fetch(o, out);
@@ -1246,7 +1240,7 @@ extern "C" mis_status mis_debug_lasr_im2col(int device, const uint16_t* in, cons
     GuardedOut o;
     const size_t n = (size_t)B * Tout * ks * C, n8 = n / 8;
     o.alloc(n * 2, (size_t)4 * ks * C * 2);
-    LS_LAUNCH(&c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), di.p, reinterpret_cast<bf16_t*>(o.p()), lsd_int(dcnt), Tin, Tout, C, ks, st, n8);
+    MIS_LAUNCH(&c, k_lasr_im2col, dim3((unsigned)((n8 + 255) / 256)), dim3(256), di.p, reinterpret_cast<bf16_t*>(o.p()), lsd_int(dcnt), Tin, Tout, C, ks, st, n8);
     lsd_sync(c);
     lsd_fetch(o, out);
     MIS_API_END
@@ -1265,7 +1259,7 @@ extern "C" mis_status mis_debug_lasr_pack(int device, const float* feats, const 
     GuardedOut o;
     const size_t n = (size_t)B * Fp * Kp;
     o.alloc(n * 2, (size_t)4 * Kp * 2);
-    LS_LAUNCH(&c, k_lasr_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), reinterpret_cast<const float*>(df.p), lsd_int(dcnt), reinterpret_cast<bf16_t*>(o.p()), Fp,
+    MIS_LAUNCH(&c, k_lasr_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), reinterpret_cast<const float*>(df.p), lsd_int(dcnt), reinterpret_cast<bf16_t*>(o.p()), Fp,
               mels, Kp, n);
     lsd_sync(c);
     lsd_fetch(o, out);
@@ -1281,7 +1275,7 @@ extern "C" mis_status mis_debug_lasr_argmax(int device, const float* logits, int
     alloc32(dl, logits, (size_t)M * V, F32_NAN);
     GuardedOut o;
     o.alloc((size_t)M * 4, 256);
-    LS_LAUNCH(&c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), reinterpret_cast<const float*>(dl.p), V, M, reinterpret_cast<int*>(o.p()));
+    MIS_LAUNCH(&c, k_lasr_argmax, dim3(cdiv(M, 4)), dim3(256), reinterpret_cast<const float*>(dl.p), V, M, reinterpret_cast<int*>(o.p()));
     lsd_sync(c);
     lsd_fetch(o, pred);
     MIS_API_END
@@ -1299,7 +1293,7 @@ extern "C" mis_status mis_debug_lasr_collapse(int device, const int32_t* pred, c
     GuardedOut t, n;
     t.alloc((size_t)B * Tp * 4, (size_t)Tp * 4);
     n.alloc((size_t)B * 4, 256);
-    LS_LAUNCH(&c, k_lasr_collapse, dim3(B), dim3(256), lsd_int(dp), lsd_int(dcnt), Tp, blank, reinterpret_cast<int*>(t.p()), reinterpret_cast<int*>(n.p()));
+    MIS_LAUNCH(&c, k_lasr_collapse, dim3(B), dim3(256), lsd_int(dp), lsd_int(dcnt), Tp, blank, reinterpret_cast<int*>(t.p()), reinterpret_cast<int*>(n.p()));
     lsd_sync(c);
     lsd_fetch(t, tokens);
     lsd_fetch(n, ntok);

@@ -17,10 +17,10 @@
 //                  or the tail LayerNorm o LayerNorm + skip + PReLU
 //   k_mf2_gemm     the one contraction, exact f32 on v_mfma_f32_32x32x2_f32, 64 x 64 tile, every dimension guarded.  Loads: activations,
 //                  token shift, LayerNorm, the product of the two gate halves, windowed frames of the waveform, spectrum x mask.  Epilogue: row scale,
-//                  bias, SiLU / ReLU / PReLU / tanh | sigmoid, column scale, residual, positional table
+//                  bias, SiLU / ReLU / PReLU / tanh | sigmoid, column scale, residual, positional table (on f32_tile.h)
 //   k_mf2_dwconv   y + depthwise(y) from a time tile + halo in LDS, 17 taps (FFConvM; the qk channels go on through OffsetScale and
 //                  RoPE; to_out adds the layer's input) or 39 (UniDeepFsmn, fused with the gate xv (.) + residual)
-//   k_mf2_linkv    linK^T [V | U] of one group of 256 frames: the linear attention's partials
+//   k_mf2_linkv    linK^T [V | U] of one group of 256 frames: the linear attention's partials (its own transposed staging)
 //   k_mf2_linsum   the partials summed once in group order, / n
 //   k_mf2_attn     relu(Q K^T / 256)^2 [V | U] inside the group + linQ x that sum, then the gate
 //   k_mf2_ola      overlap-add as a gather, / max(sum w^2, 1e-8), / 32768
@@ -28,6 +28,7 @@
 // Launches: enhance 11 + 18 num_blocks; mask 8 + 18 num_blocks; mask_features 6 + 18 num_blocks; features 2; synthesize 3.
 #include "common.h"
 #include "audio_front.h"
+#include "f32_tile.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -35,7 +36,6 @@
 #include <memory>
 
 #define MF_MAX_BATCH 64
-#define MF_KC 32
 #define MF_GROUP 256              // constants of the reference: group size, query / key width, FSMN inner width, lorder, taps
 #define MF_QK 128
 #define MF_INNER 256
@@ -187,34 +187,25 @@ __global__ void __launch_bounds__(256) k_mf2_row(MfRow p) {
         if (p.stats && lane == 0) { p.stats[2 * row] = 0.0f; p.stats[2 * row + 1] = 0.0f; }
         return;
     }
-    float s = 0.0f;
-    for (int c = lane; c < C; c += 64) s += x[c];
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.0f;
-    for (int c = lane; c < C; c += 64) { const float d = x[c] - mean; q = fmaf(d, d, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + p.eps);
+    float mean, rstd, m2, r2;
+    wave_mean_rstd(x, C, p.eps, mean, rstd);
+    const auto ln1 = [&](int c) { return fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]); };
     if (p.mode == MF_ROW_CLN) {
-        float s2 = 0.0f;
-        for (int c = lane; c < C; c += 64) { const float v = fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]); y[c] = v; s2 += v; }
+        float s2 = 0.0f;                                            // (the sum rides on the pass that writes y: not wave_mean_rstd)
+        for (int c = lane; c < C; c += 64) { const float v = ln1(c); y[c] = v; s2 += v; }
         if (!p.stats) return;
-        const float m2 = wave_sum(s2) / (float)C;                    // the LayerNorm in front of to_u / to_v reads these
+        m2 = wave_sum(s2) / (float)C;                                // the LayerNorm in front of to_u / to_v reads these
         float q2 = 0.0f;
-        for (int c = lane; c < C; c += 64) { const float d = fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]) - m2; q2 = fmaf(d, d, q2); }
+        for (int c = lane; c < C; c += 64) { const float d = ln1(c) - m2; q2 = fmaf(d, d, q2); }
         q2 = wave_sum(q2);
         if (lane == 0) { p.stats[2 * row] = m2; p.stats[2 * row + 1] = 1.0f / sqrtf(q2 / (float)C + p.eps_next); }
         return;
     }
     // tail: LayerNorm (intra_mdl.norm), LayerNorm (intra_norm), + the network's input, PReLU
-    float s2 = 0.0f;
-    for (int c = lane; c < C; c += 64) s2 += fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]);
-    const float m2 = wave_sum(s2) / (float)C;
-    float q2 = 0.0f;
-    for (int c = lane; c < C; c += 64) { const float d = fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]) - m2; q2 = fmaf(d, d, q2); }
-    const float r2 = 1.0f / sqrtf(wave_sum(q2) / (float)C + p.eps);
+    wave_mean_rstd_of(ln1, C, p.eps, m2, r2);
     const float a = p.slope[0];
     for (int c = lane; c < C; c += 64) {
-        const float v1 = fmaf((x[c] - mean) * rstd, p.w1[c], p.b1[c]);
-        const float v = fmaf((v1 - m2) * r2, p.w2[c], p.b2[c]) + p.R[row * p.ldr + c];
+        const float v = fmaf((ln1(c) - m2) * r2, p.w2[c], p.b2[c]) + p.R[row * p.ldr + c];
         y[c] = fmaxf(v, 0.0f) + a * fminf(v, 0.0f);
     }
 }
@@ -251,41 +242,31 @@ __device__ __forceinline__ float mf_load(const MfGemm& p, int b, size_t row, int
 }
 
 __global__ void __launch_bounds__(256) k_mf2_gemm(MfGemm p) {
-    constexpr int TT = 64, TC = 64;
-    __shared__ float As[TT][MF_KC + 1];
-    __shared__ float Bs[TC][MF_KC + 1];
+    constexpr int TT = F32_TILE, TC = F32_TILE;
+    __shared__ float As[TT][F32_KC + 1];
+    __shared__ float Bs[TC][F32_KC + 1];
     const int b = blockIdx.z, t0 = blockIdx.x * TT, c0 = blockIdx.y * TC, nr = p.nr;
     const int T = min(p.cnt[b], nr), tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t row0 = (size_t)b * nr;
-    if (t0 >= T) {
-        for (int i = tid; i < TT * TC; i += 256) {
-            const int t = t0 + i / TC, co = c0 + i % TC;
-            if (t < nr && co < p.Cout) p.Y[(row0 + t) * p.ldy + co] = 0.0f;
-        }
-        return;
-    }
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    if (t0 >= T) { f32_tile_zero<TT, TC>(p.Y, p.ldy, row0, t0, c0, nr, p.Cout); return; }
+    f32x16_t acc[1] = {};
     const int wt = (wave & 1) * 32, wc = (wave >> 1) * 32, kh = lane >> 5, l31 = lane & 31;
-    for (int ci0 = 0; ci0 < p.Cin; ci0 += MF_KC) {
+    for (int ci0 = 0; ci0 < p.Cin; ci0 += F32_KC) {
 #pragma unroll
-        for (int n = 0; n < TT * MF_KC / 256; ++n) {
+        for (int n = 0; n < TT * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), t = t0 + r;
             As[r][i & 31] = (ci < p.Cin && t < T) ? mf_load(p, b, row0 + t, t, T, ci) : 0.0f;
         }
 #pragma unroll
-        for (int n = 0; n < TC * MF_KC / 256; ++n) {
+        for (int n = 0; n < TC * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), co = c0 + r;
             Bs[r][i & 31] = (co < p.Cout && ci < p.Cin) ? p.W[(size_t)co * p.ldw + ci] : 0.0f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < MF_KC; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wt + l31][kk + kh], Bs[wc + l31][kk + kh], acc, 0, 0, 0);
+        f32_tile_mfma(As, Bs, wt + l31, wc + l31, kh, acc);
         __syncthreads();
     }
-    // C/D: column (output channel) = lane & 31, row (frame) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int co = c0 + wc + l31;
+    const int co = c0 + wc + l31;                                   // C/D: column = lane & 31, row = f32_tile_row(r, lane >> 5)
     if (co >= p.Cout) return;
     const float add = p.bias ? p.bias[co] : 0.0f;
     const float g = p.g0 ? (co < p.gsplit ? p.g0[0] : p.g1[0]) : 1.0f;
@@ -293,10 +274,10 @@ __global__ void __launch_bounds__(256) k_mf2_gemm(MfGemm p) {
     const float slope = p.act == MF_ACT_PRELU ? p.slope[0] : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int t = t0 + wt + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int t = t0 + wt + f32_tile_row(r, kh);
         if (t >= nr) continue;
         const size_t row = row0 + t;
-        float v = acc[r];
+        float v = acc[0][r];
         if (t < T) {
             if (p.g0) v *= p.stats[2 * row] * g;
             v += add;
@@ -392,34 +373,31 @@ __global__ void __launch_bounds__(256) k_mf2_dwconv(MfDw p) {
 struct MfLinKV { const float* qk4; const float* vu; float* P; const int32_t* cnt; int nr, G, N; };   // N = 4 dim, the width of vu
 
 __global__ void __launch_bounds__(256) k_mf2_linkv(MfLinKV p) {
-    __shared__ float As[64][MF_KC + 1];
-    __shared__ float Bs[64][MF_KC + 1];
+    __shared__ float As[F32_TILE][F32_KC + 1];
+    __shared__ float Bs[F32_TILE][F32_KC + 1];
     const int g = blockIdx.z % p.G, b = blockIdx.z / p.G, d0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const int T = min(p.cnt[b], p.nr), tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t row0 = (size_t)b * p.nr;
     const int ta = g * MF_GROUP, tb = min(T, ta + MF_GROUP);
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    f32x16_t acc[1] = {};
     const int wd = (wave & 1) * 32, wc = (wave >> 1) * 32, kh = lane >> 5, l31 = lane & 31;
-    for (int k0 = ta; k0 < tb; k0 += MF_KC) {
+    for (int k0 = ta; k0 < tb; k0 += F32_KC) {                        // (frames are the K index here: both operands are staged transposed)
 #pragma unroll
-        for (int n = 0; n < 64 * MF_KC / 256; ++n) {
+        for (int n = 0; n < F32_TILE * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i & 63, kk = i >> 6, t = k0 + kk;
             As[r][kk] = t < tb ? p.qk4[((row0 + t) * 4 + 3) * MF_QK + d0 + r] : 0.0f;
             Bs[r][kk] = (t < tb && c0 + r < p.N) ? p.vu[(row0 + t) * p.N + c0 + r] : 0.0f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < MF_KC; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wd + l31][kk + kh], Bs[wc + l31][kk + kh], acc, 0, 0, 0);
+        f32_tile_mfma(As, Bs, wd + l31, wc + l31, kh, acc);
         __syncthreads();
     }
     const int c = c0 + wc + l31;
     if (c >= p.N) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int d = d0 + wd + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        p.P[(((size_t)b * p.G + g) * MF_QK + d) * p.N + c] = acc[r];
+        const int d = d0 + wd + f32_tile_row(r, kh);
+        p.P[(((size_t)b * p.G + g) * MF_QK + d) * p.N + c] = acc[0][r];
     }
 }
 

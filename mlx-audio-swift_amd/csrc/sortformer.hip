@@ -1,6 +1,6 @@
 // sortformer.hip - Sortformer speaker diarization: 16 kHz samples -> NeMo log-mel -> depthwise-striding Conv2d stem (factor 8) ->
 // FastConformer blocks with Transformer-XL relative-position attention -> encoder_proj + learned positions -> post-LN BART layers ->
-// speaker sigmoids.  Exact f32 on v_mfma_f32_32x32x2_f32 throughout, as ecapa_lid.hip, fsmn_vad.hip and mossformer2.hip.
+// speaker sigmoids.  Exact f32 on v_mfma_f32_32x32x2_f32 throughout, as ecapa_lid.hip, fsmn_vad.hip and mossformer2.hip (f32_tile.h).
 //
 // Reference being replaced: SortformerModel (Sources/MLXAudioVAD/Models/Sortformer/Sortformer.swift: ConvSubsampling :16-87,
 // RelPositionalEncoding :90-116, RelPositionMultiHeadAttention :119-196, ConformerConvolution :237-278, ConformerLayer :281-329,
@@ -19,11 +19,11 @@
 //                  slaney filters over each filter's own bins, log(. + 2^-24)
 //   k_sf_norm      per bin mean / unbiased variance over the row's own frames, (x - mean) / (std + 1e-5), or the copy (normalize off)
 //   k_sf_conv0     Conv2d 1 -> C, 3 x 3, stride 2, pad 1, ReLU; channels last [B][T1][F1][C]
-//   k_sf_gemm      the one contraction: 64 x 64 tile, every dimension guarded.  Loads: plain, LayerNorm (statistics from k_sf_stats),
+//   k_sf_gemm      the one contraction (on f32_tile.h): 64 x 64 tile, every dimension guarded.  Loads: plain, LayerNorm (statistics from k_sf_stats),
 //                  ReLU, and the stem's depthwise 3 x 3 stride-2 conv FOLDED into the operand load of the pointwise GEMM that follows
 //                  it (nine taps of a channels-last tensor are nine coalesced reads; its own kernel would write and re-read the
 //                  largest tensors of the model).  Epilogue: bias, SiLU / ReLU / sigmoid, R + a v, positional table, zero rows behind T
-//   k_sf_stats     mean and 1 / sqrt(var + eps) of a frame, one wave per frame
+//   k_sf_stats     mean and 1 / sqrt(var + eps) of a frame, one wave per frame (wave_mean_rstd of common.h)
 //   k_sf_ln        LayerNorm with weight and bias (norm_out, the BART post-norms), zero rows behind T
 //   k_sf_intake    x sqrt(hidden) (scale_input) of the stem's embeddings, zero rows behind T
 //   k_sf_attn      flash attention, 64 queries x head x row per block (two waves of 32), 32-key tiles through LDS, online softmax in
@@ -42,6 +42,7 @@
 // encode_embeddings 4 + 15 L_fc + 7 L_tf; pre_encode 4; features 3.
 #include "common.h"
 #include "audio_front.h"
+#include "f32_tile.h"
 #include "host_weights.h"
 
 #include <math.h>
@@ -54,18 +55,11 @@
 #define SF_HOP 160
 #define SF_WIN 400
 #define SF_BINS 257
-#define SF_KC 32
 #define SF_DW_TT 64
 #define SF_DW_MAXK 31
 
 enum { SF_LOAD_ACT = 0, SF_LOAD_LN, SF_LOAD_RELU, SF_LOAD_DW };
 enum { SF_ACT_NONE = 0, SF_ACT_SILU, SF_ACT_RELU, SF_ACT_SIGMOID };
-
-#define SF_LAUNCH(c, kernel, grid, block, ...)                                  \
-    do {                                                                        \
-        hipLaunchKernelGGL(kernel, grid, block, 0, (c)->stream, __VA_ARGS__);   \
-        (c)->launches += 1;                                                     \
-    } while (0)
 
 // ============================================================================ front end
 __global__ void __launch_bounds__(256) k_sf_peak(const float* __restrict__ pcm, int64_t stride, const int* __restrict__ N, int on,
@@ -226,51 +220,41 @@ __device__ __forceinline__ float sf_load(const SfGemm& p, int b, size_t row, int
 
 template <int LOAD>
 __global__ void __launch_bounds__(256) k_sf_gemm(SfGemm p) {
-    constexpr int TT = 64, TC = 64;
-    __shared__ float As[TT][SF_KC + 1];
-    __shared__ float Bs[TC][SF_KC + 1];
+    constexpr int TT = F32_TILE, TC = F32_TILE;
+    __shared__ float As[TT][F32_KC + 1];
+    __shared__ float Bs[TC][F32_KC + 1];
     const int b = blockIdx.z, t0 = blockIdx.x * TT, c0 = blockIdx.y * TC, nr = p.Tp * p.rowmul;
     const int T = (p.cnt ? min(p.cnt[b], p.Tp) : p.Tp) * p.rowmul, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const size_t row0 = (size_t)b * nr;
-    if (t0 >= T) {
-        for (int i = tid; i < TT * TC; i += 256) {
-            const int t = t0 + i / TC, co = c0 + i % TC;
-            if (t < nr && co < p.N) p.Y[(row0 + t) * p.ldy + co] = 0.0f;
-        }
-        return;
-    }
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    if (t0 >= T) { f32_tile_zero<TT, TC>(p.Y, p.ldy, row0, t0, c0, nr, p.N); return; }
+    f32x16_t acc[1] = {};
     const int wt = (wave & 1) * 32, wc = (wave >> 1) * 32, kh = lane >> 5, l31 = lane & 31;
-    for (int ci0 = 0; ci0 < p.K; ci0 += SF_KC) {
+    for (int ci0 = 0; ci0 < p.K; ci0 += F32_KC) {
 #pragma unroll
-        for (int n = 0; n < TT * SF_KC / 256; ++n) {
+        for (int n = 0; n < TT * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), t = t0 + r;
             As[r][i & 31] = (ci < p.K && t < T) ? sf_load<LOAD>(p, b, row0 + t, t, ci) : 0.0f;
         }
 #pragma unroll
-        for (int n = 0; n < TC * SF_KC / 256; ++n) {
+        for (int n = 0; n < TC * F32_KC / 256; ++n) {
             const int i = tid + n * 256, r = i >> 5, ci = ci0 + (i & 31), co = c0 + r;
             Bs[r][i & 31] = (co < p.N && ci < p.K) ? p.W[(size_t)co * p.K + ci] : 0.0f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < SF_KC; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[wt + l31][kk + kh], Bs[wc + l31][kk + kh], acc, 0, 0, 0);
+        f32_tile_mfma(As, Bs, wt + l31, wc + l31, kh, acc);
         __syncthreads();
     }
-    // C/D: column (output channel) = lane & 31, row (frame) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int co = c0 + wc + l31;
+    const int co = c0 + wc + l31;                                   // C/D: column = lane & 31, row = f32_tile_row(r, lane >> 5)
     if (co >= p.N) return;
     const float add = p.bias ? p.bias[co] : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int t = t0 + wt + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int t = t0 + wt + f32_tile_row(r, kh);
         if (t >= nr) continue;
         const size_t row = row0 + t;
         float v = 0.0f;
         if (t < T) {
-            v = acc[r] + add;
+            v = acc[0][r] + add;
             if (p.act == SF_ACT_SILU) v = v / (1.0f + expf(-v));
             else if (p.act == SF_ACT_RELU) v = fmaxf(v, 0.0f);
             else if (p.act == SF_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
@@ -285,14 +269,9 @@ __global__ void __launch_bounds__(256) k_sf_gemm(SfGemm p) {
 __global__ void __launch_bounds__(256) k_sf_stats(const float* __restrict__ X, float* __restrict__ stats, int d, float eps, int M) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    const float* x = X + (size_t)row * d;
-    float s = 0.0f;
-    for (int c = lane; c < d; c += 64) s += x[c];
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.0f;
-    for (int c = lane; c < d; c += 64) { const float v = x[c] - mean; q = fmaf(v, v, q); }
-    q = wave_sum(q);
-    if (lane == 0) { stats[2 * (size_t)row] = mean; stats[2 * (size_t)row + 1] = 1.0f / sqrtf(q / (float)d + eps); }
+    float mean, rstd;
+    wave_mean_rstd(X + (size_t)row * d, d, eps, mean, rstd);
+    if (lane == 0) { stats[2 * (size_t)row] = mean; stats[2 * (size_t)row + 1] = rstd; }
 }
 
 __global__ void __launch_bounds__(256) k_sf_ln(const float* X, float* Y, const float* __restrict__ w,
@@ -305,12 +284,8 @@ __global__ void __launch_bounds__(256) k_sf_ln(const float* X, float* Y, const f
         for (int c = lane; c < d; c += 64) y[c] = 0.0f;
         return;
     }
-    float s = 0.0f;
-    for (int c = lane; c < d; c += 64) s += x[c];
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.0f;
-    for (int c = lane; c < d; c += 64) { const float v = x[c] - mean; q = fmaf(v, v, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
+    float mean, rstd;
+    wave_mean_rstd(x, d, eps, mean, rstd);
     for (int c = lane; c < d; c += 64) y[c] = fmaf((x[c] - mean) * rstd, w[c], bias[c]);
 }
 
@@ -626,10 +601,10 @@ static double sf_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 100
 static void sf_gemm(mis_sortformer* c, SfGemm p, int B) {
     const dim3 grid(cdiv((int64_t)p.Tp * p.rowmul, 64), cdiv(p.N, 64), B);
     switch (p.load) {
-        case SF_LOAD_LN: SF_LAUNCH(c, k_sf_gemm<SF_LOAD_LN>, grid, dim3(256), p); break;
-        case SF_LOAD_RELU: SF_LAUNCH(c, k_sf_gemm<SF_LOAD_RELU>, grid, dim3(256), p); break;
-        case SF_LOAD_DW: SF_LAUNCH(c, k_sf_gemm<SF_LOAD_DW>, grid, dim3(256), p); break;
-        default: SF_LAUNCH(c, k_sf_gemm<SF_LOAD_ACT>, grid, dim3(256), p); break;
+        case SF_LOAD_LN: MIS_LAUNCH(c, k_sf_gemm<SF_LOAD_LN>, grid, dim3(256), p); break;
+        case SF_LOAD_RELU: MIS_LAUNCH(c, k_sf_gemm<SF_LOAD_RELU>, grid, dim3(256), p); break;
+        case SF_LOAD_DW: MIS_LAUNCH(c, k_sf_gemm<SF_LOAD_DW>, grid, dim3(256), p); break;
+        default: MIS_LAUNCH(c, k_sf_gemm<SF_LOAD_ACT>, grid, dim3(256), p); break;
     }
 }
 // plain rows [B Tp][K] x lin -> Y [B Tp][N]
@@ -920,17 +895,17 @@ static void sf_front(mis_sortformer* c, const float* pcm, const int64_t* lens, i
     const int64_t ws = std::min<int64_t>(stride, c->maxN);
     HIP_CHECK(hipMemcpy2DAsync(c->pcm.p, ws * 4, pcm, stride * 4, ws * 4, batch, hipMemcpyDefault, s));
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[0], s));
-    SF_LAUNCH(c, k_sf_peak, dim3(batch), dim3(256), c->pcm.p, ws, c->cntN.p, peak, c->scale.p);
-    SF_LAUNCH(c, k_sf_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF0.p, c->scale.p, c->cfg.preemphasis, c->window, c->twc, c->tws,
+    MIS_LAUNCH(c, k_sf_peak, dim3(batch), dim3(256), c->pcm.p, ws, c->cntN.p, peak, c->scale.p);
+    MIS_LAUNCH(c, k_sf_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF0.p, c->scale.p, c->cfg.preemphasis, c->window, c->twc, c->tws,
               c->fb, c->fbr.p, c->melraw.p, Fp, c->mels);
-    SF_LAUNCH(c, k_sf_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF0.p, c->feats.p, Fp, c->mels, normalize);
+    MIS_LAUNCH(c, k_sf_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF0.p, c->feats.p, Fp, c->mels, normalize);
 }
 
 // c->feats -> c->emb [B][Tp][d] (ConvSubsampling), 4 launches
 static void sf_stem(mis_sortformer* c) {
     const int B = c->batch, C = c->C, F1 = c->F1, F2 = c->F2, F3 = c->F3;
     const size_t n0 = (size_t)B * c->T1p * F1 * C;
-    SF_LAUNCH(c, k_sf_conv0, dim3((unsigned)((n0 + 255) / 256)), dim3(256), c->feats.p, c->cntF.p, c->cnt1.p, c->c0w, c->c0b, c->s0.p, c->Fp, c->mels, c->T1p,
+    MIS_LAUNCH(c, k_sf_conv0, dim3((unsigned)((n0 + 255) / 256)), dim3(256), c->feats.p, c->cntF.p, c->cnt1.p, c->c0w, c->c0b, c->s0.p, c->Fp, c->mels, c->T1p,
               F1, C, n0);
     auto dwpw = [&](const float* in, const int* cin, int Tin, int Fin, const float* dww, const float* dwb, const SfLin& pw, float* out, const int* cout,
                     int Tout, int Fout) {
@@ -948,8 +923,8 @@ static void sf_stem(mis_sortformer* c) {
 template <bool REL>
 static void sf_attn(mis_sortformer* c, const SfAttn& p, int heads, int hd) {
     const dim3 grid(cdiv(c->Tp, 64), heads, c->batch);
-    if (hd <= 32) SF_LAUNCH(c, (k_sf_attn<1, REL>), grid, dim3(128), p);
-    else SF_LAUNCH(c, (k_sf_attn<2, REL>), grid, dim3(128), p);
+    if (hd <= 32) MIS_LAUNCH(c, (k_sf_attn<1, REL>), grid, dim3(128), p);
+    else MIS_LAUNCH(c, (k_sf_attn<2, REL>), grid, dim3(128), p);
 }
 
 // c->emb -> Conformer blocks -> projection -> BART layers -> c->probs.  stop: -1 everything; 1 .. L behind that block (c->h);
@@ -959,9 +934,9 @@ static void sf_encoder(mis_sortformer* c, int stop) {
     const int* cnt = c->cnt3.p;
     hipStream_t s = c->stream;
     const size_t nd = (size_t)M * d;
-    SF_LAUNCH(c, k_sf_intake, dim3((unsigned)((nd + 255) / 256)), dim3(256), c->emb.p, c->h.p, cnt, Tp, d,
+    MIS_LAUNCH(c, k_sf_intake, dim3((unsigned)((nd + 255) / 256)), dim3(256), c->emb.p, c->h.p, cnt, Tp, d,
               c->cfg.scale_input ? sqrtf((float)d) : 1.0f, nd);
-    auto stats = [&](const float* x) { SF_LAUNCH(c, k_sf_stats, dim3(cdiv(M, 4)), dim3(256), x, c->stats.p, d, 1e-5f, M); };
+    auto stats = [&](const float* x) { MIS_LAUNCH(c, k_sf_stats, dim3(cdiv(M, 4)), dim3(256), x, c->stats.p, d, 1e-5f, M); };
     auto ln_lin = [&](const float* x, const float* w, const float* b, const SfLin& l, float* y, int N, int act) {
         SfGemm p = sf_lin(x, d, l, y, N, cnt, Tp, act);
         p.load = SF_LOAD_LN; p.stats = c->stats.p; p.lnw = w; p.lnb = b;
@@ -984,12 +959,12 @@ static void sf_encoder(mis_sortformer* c, int stop) {
         res_lin(c->att.p, d, l.o, c->h.p, d, 1.0f);
         stats(c->h.p);
         ln_lin(c->h.p, l.lncw, l.lncb, l.pw1, c->big.p, 2 * d, SF_ACT_NONE);
-        SF_LAUNCH(c, k_sf_glu_dwconv, dim3(cdiv(Tp, SF_DW_TT), cdiv(d, 64), B), dim3(256), c->big.p, l.dw, l.dwshift, cnt, c->att.p, Tp, d, c->ck);
+        MIS_LAUNCH(c, k_sf_glu_dwconv, dim3(cdiv(Tp, SF_DW_TT), cdiv(d, 64), B), dim3(256), c->big.p, l.dw, l.dwshift, cnt, c->att.p, Tp, d, c->ck);
         res_lin(c->att.p, d, l.pw2, c->h.p, d, 1.0f);
         stats(c->h.p);
         ln_lin(c->h.p, l.ln2w, l.ln2b, l.ff2a, c->big.p, f, SF_ACT_SILU);
         res_lin(c->big.p, f, l.ff2b, c->h.p, d, 0.5f);
-        SF_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->h.p, c->h.p, l.lnow, l.lnob, d, 1e-5f, M, cnt, Tp);
+        MIS_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->h.p, c->h.p, l.lnow, l.lnob, d, 1e-5f, M, cnt, Tp);
         if (stop == li + 1) return;
     }
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[3], s));
@@ -1010,14 +985,14 @@ static void sf_encoder(mis_sortformer* c, int stop) {
             p.R = c->g.p; p.ldr = dt; p.ra = 1.0f;
             sf_gemm(c, p, B);
         }
-        SF_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->gx.p, c->g.p, l.ln1w, l.ln1b, dt, eps, M, cnt, Tp);
+        MIS_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->gx.p, c->g.p, l.ln1w, l.ln1b, dt, eps, M, cnt, Tp);
         sf_gemm(c, sf_lin(c->g.p, dt, l.fc1, c->gf.p, ft, cnt, Tp, SF_ACT_RELU), B);
         {
             SfGemm p = sf_lin(c->gf.p, ft, l.fc2, c->gx.p, dt, cnt, Tp);
             p.R = c->g.p; p.ldr = dt; p.ra = 1.0f;
             sf_gemm(c, p, B);
         }
-        SF_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->gx.p, c->g.p, l.ln2w, l.ln2b, dt, eps, M, cnt, Tp);
+        MIS_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->gx.p, c->g.p, l.ln2w, l.ln2b, dt, eps, M, cnt, Tp);
         if (stop == L + 2 + li) return;
     }
     {   // ReLU -> first_hidden_to_hidden -> ReLU -> single_hidden_to_spks -> sigmoid

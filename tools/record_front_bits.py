@@ -13,6 +13,16 @@ The shapes are the smallest that reach every path of the front ends and of the e
              longest row spans two chunks and both GEMM tiles and the softmax epilogue run
   ecapa_lid  log_probs / embedding, 60 mels (the edge guards of the GEMM); rows of 160, 1700 and 4000 samples
   moonshine  encode, rows of 895 and 3000 samples
+  mossformer2  one block at out_channels 16 (the smallest width the config check takes), otherwise the smallest model of
+             tests/test_gpu_mossformer2.py: 16 kHz, window 320, hop 64, 20 mels, so the feature width 60 runs the K guard and 161 bins the N
+             guard.  Rows of 319, 320 and 320 + 256 x 64 samples: no frame, one, and 257, which is two groups of k_mf2_linkv and five row
+             tiles, whose last four are zero tiles for the short rows.  enhance passes through the six loads (activations, token shift,
+             LayerNorm, gate, frame, masked) and the row-scale, column-scale, PReLU and tanh | sigmoid epilogues; mask and features are
+             digested on the way
+  sortformer   one Conformer block (48 / 2 heads / 80, stem 24 channels, 80 mels) and one BART layer (40 / 2 heads / 72), 4 speakers: no width
+             is a multiple of 32.  Rows of 0, 3000 and 81920 samples at pad_to 0: F = 1, 19, 513 and T = 1, 3, 65, so the encoder GEMMs have
+             a second row tile that is a zero tile for the short rows.  forward runs the plain, LayerNorm and ReLU loads and the R + a v and
+             positional epilogues; pre_encode of the features runs the depthwise-conv load with rowmul > 1 rows
 The waveforms come from integer arithmetic alone, so they are the same bytes on every machine."""
 import argparse
 import hashlib
@@ -97,7 +107,40 @@ def moonshine() -> dict:
         m.close()
 
 
-ENGINES = dict(lasr=lasr, fsmn_vad=fsmn_vad, ecapa_lid=ecapa_lid, moonshine=moonshine)
+def mossformer2() -> dict:
+    import mlx_audio_swift_amd as mas
+    cfg = mas.MossFormer2SEConfig(sample_rate=16000, win_len=320, win_inc=64, fft_len=320, num_mels=20, in_channels=60, out_channels=16,
+                                  out_channels_final=161, num_blocks=1, max_batch=4, max_seconds=1.1)
+    m = mas.MossFormer2SE.synthetic(cfg, seed=SEED)
+    try:
+        r = rows([319, 320, 320 + 256 * 64])
+        feats, T = m.features_raw(r)
+        mask, _ = m.mask_raw(r)
+        out = {f"enhance_row{b}": digest(o) for b, o in enumerate(m.enhance_batch(r))}
+        return dict(out, features=digest(feats), mask=digest(mask), frames=digest(T))
+    finally:
+        m.close()
+
+
+def sortformer() -> dict:
+    import mlx_audio_swift_amd as mas
+    e = mas.FCEncoderConfig(hidden_size=48, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=2, intermediate_size=80,
+                            num_mel_bins=80, subsampling_conv_channels=24)
+    t = mas.TFEncoderConfig(d_model=40, encoder_layers=1, encoder_attention_heads=2, encoder_ffn_dim=72)
+    cfg = mas.SortformerConfig(fc_encoder_config=e, tf_encoder_config=t, modules_config=mas.ModulesConfig(num_speakers=4, fc_d_model=48, tf_d_model=40),
+                               processor_config=mas.ProcessorConfig(feature_size=80), max_batch=4, max_seconds=6)
+    m = mas.SortformerModel.synthetic(cfg, seed=SEED)
+    try:
+        r = rows([0, 3000, 81920])
+        F, T = m.frames([len(x) for x in r], 0)
+        feats = m.features(r, pad_to=0)
+        return dict(forward=digest(m.forward(r, pad_to=0)), features=digest(feats), pre_encode=digest(m.pre_encode(feats, F)),
+                    feature_frames=digest(F), frames=digest(T))
+    finally:
+        m.close()
+
+
+ENGINES = dict(lasr=lasr, fsmn_vad=fsmn_vad, ecapa_lid=ecapa_lid, moonshine=moonshine, mossformer2=mossformer2, sortformer=sortformer)
 
 
 def main():
