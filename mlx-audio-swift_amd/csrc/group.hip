@@ -11,6 +11,7 @@
 //              library still loads on hosts without RCCL.
 #include "common.h"
 #include "kernels.h"
+#include "step_loop.h"
 
 #include <dlfcn.h>
 #include <string.h>
@@ -122,20 +123,15 @@ extern "C" mis_status mis_comm_all_gather_pcm(mis_comm* c, const float* pcm_loca
     hipStream_t s = c->stream;
     c->lens_local.alloc(rows_local); c->lens_all.alloc((size_t)rows_local * c->world);
     HIP_CHECK(hipMemcpyAsync(c->lens_local.p, lens_local, (size_t)rows_local * 8, hipMemcpyDefault, s));
-    struct EventPair {                             // released on every exit path (RCCL_CHECK / HIP_CHECK throw)
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    } ev;
-    HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-    hipEvent_t e0 = ev.a, e1 = ev.b;
-    HIP_CHECK(hipEventRecord(e0, s));
+    HipEvents<2> ev;                               // released on every exit path (RCCL_CHECK / HIP_CHECK throw)
+    HIP_CHECK(hipEventRecord(ev[0], s));
     RCCL_CHECK(rccl()->AllGather(pcm_local_dev, pcm_all_dev, (size_t)rows_local * stride, RCCL_FLOAT32, c->comm, s));
     RCCL_CHECK(rccl()->AllGather(c->lens_local.p, c->lens_all.p, (size_t)rows_local, RCCL_INT64, c->comm, s));
-    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventRecord(ev[1], s));
     HIP_CHECK(hipMemcpyAsync(lens_all, c->lens_all.p, (size_t)rows_local * c->world * 8, hipMemcpyDefault, s));
     HIP_CHECK(hipStreamSynchronize(s));
     float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     c->last_gather_ms = ms;
     if (gather_ms) *gather_ms = ms;
     MIS_API_END

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lm_kernels.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -76,7 +77,7 @@ struct mis_tts {
     DevBuf<int32_t> pf_pos;
     DevBuf<uint8_t> pf_on;
     DevBuf<SamplerScratch> samp_scratch;
-    hipGraphExec_t g_prefill = nullptr, g_decode = nullptr;
+    StepGraph g_prefill, g_decode;
     bool shared_device = false;      // another replica's streams run on this device (group.hip): never a kernel that waits for co-resident blocks
     uint64_t graph_key = 0;
     bool use_graph = true;
@@ -135,8 +136,7 @@ extern "C" void mis_tts_destroy(mis_tts* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->g_prefill) (void)hipGraphExecDestroy(c->g_prefill);
-    if (c->g_decode) (void)hipGraphExecDestroy(c->g_decode);
+    c->g_prefill.reset(); c->g_decode.reset();
     if (c->stream && !c->borrowed_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -485,10 +485,7 @@ static int choose_split(int items, int KT, int ksb, const char* env, int s_max =
     return std::max(1, std::min(env_int(env, gemm_choose_split(items, KT, ksb, s_max)), 16));
 }
 
-static void destroy_graphs(mis_tts* c) {
-    if (c->g_prefill) { (void)hipGraphExecDestroy(c->g_prefill); c->g_prefill = nullptr; }
-    if (c->g_decode) { (void)hipGraphExecDestroy(c->g_decode); c->g_decode = nullptr; }
-}
+static void destroy_graphs(mis_tts* c) { c->g_prefill.reset(); c->g_decode.reset(); }
 
 static void build_rope_tables(mis_tts* c) {
     // Llama3ScaledRoPE freqs, LlamaTTS.swift:126-156, float32 arithmetic; angle = pos / freqs[i]
@@ -1100,15 +1097,14 @@ extern "C" mis_status mis_sample_logits(int device, const float* logits, int bat
     launch_sampler(sp, batch, 0);
     HIP_CHECK(hipGetLastError());
     if (want_dbg) {
-        hipEvent_t e0, e1;
-        HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+        HipEvents<2> ev;
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipEventRecord(e0, 0));
+        HIP_CHECK(hipEventRecord(ev[0], 0));
         for (int i = 0; i < 20; ++i) launch_sampler(sp, batch, 0);         // (stamps of the last launch stay; timing of 20 back to back)
-        HIP_CHECK(hipEventRecord(e1, 0));
-        HIP_CHECK(hipEventSynchronize(e1));
+        HIP_CHECK(hipEventRecord(ev[1], 0));
+        HIP_CHECK(hipEventSynchronize(ev[1]));
         float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
         unsigned long long st[48];
         HIP_CHECK(hipMemcpy(st, dbg.p, sizeof(st), hipMemcpyDeviceToHost));
         fprintf(stderr, "SAMP_DBG us_per_launch %.2f stamps", ms * 1e3 / 20);
@@ -1119,7 +1115,6 @@ extern "C" mis_status mis_sample_logits(int device, const float* logits, int bat
         for (int cb = 0; cb < 8; ++cb) fprintf(stderr, " [%llu %llu %llu %llu]", st[16 + 4 * cb] - t0w, st[17 + 4 * cb] - t0w, st[18 + 4 * cb] - t0w,
                                                st[19 + 4 * cb] ? st[19 + 4 * cb] - t0w : 0ull);
         fprintf(stderr, "\n");
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     }
     if (sampler_check_failed(scratch.p, batch, 0)) {
         // a row barrier of the one-launch sampler timed out (its 8 x batch blocks were not co-resident: another stream holds CUs).  This
@@ -1314,17 +1309,8 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         enqueue_layers(c);
         collect(0);
     };
-    auto capture = [&](hipGraphExec_t* exec, auto&& body) {
-        hipGraph_t g = nullptr;
-        HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        try { body(); } catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(s, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-        HIP_CHECK(hipStreamEndCapture(s, &g));
-        HIP_CHECK(hipGraphInstantiate(exec, g, nullptr, nullptr, 0));
-        HIP_CHECK(hipGraphDestroy(g));
-    };
 
-    hipEvent_t ev[4];
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    HipEvents<4> ev;
     auto t_host0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipEventRecord(ev[0], s));
     // ---- prefill: Lmax steps of the ragged, left-padded batch (prefill :711)
@@ -1332,9 +1318,9 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         prefill_batched(c, c->prompt_mat.p, c->prompt_lens.p, lens, Lmax);
         collect(1);
     } else {
-        if (c->use_graph && !c->g_prefill) capture(&c->g_prefill, prefill_body);
+        if (c->use_graph && !c->g_prefill) c->g_prefill.capture(s, prefill_body);
         for (int j = 0; j < Lmax; ++j) {
-            if (c->use_graph) HIP_CHECK(hipGraphLaunch(c->g_prefill, s)); else prefill_body();
+            if (c->use_graph) c->g_prefill.launch(s); else prefill_body();
         }
     }
     HIP_CHECK(hipEventRecord(ev[1], s));
@@ -1345,7 +1331,7 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         HIP_CHECK(hipStreamSynchronize(s));
     }
     // ---- decode loop (:714-744)
-    if (c->use_graph && !c->g_decode) capture(&c->g_decode, decode_body);
+    if (c->use_graph && !c->g_decode) c->g_decode.capture(s, decode_body);
     // (Several decode steps per graph launch were measured and removed: between two hipGraphLaunch calls of the one-step graph the
     // device idles for 8.2 us - profiles/r04/c1_gaps.json - and yet eight steps per graph are SLOWER, 2.1047 against 2.0953 ms per step
     // over five A/B runs, profiles/r04/c2_ab.json: a 1376-node graph costs more per node than its seven removed seams save.)
@@ -1360,7 +1346,7 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
     while (steps < max_tokens) {
         int chunk = std::min(poll, max_tokens - steps);
         for (int i = 0; i < chunk; ++i) {
-            if (c->use_graph) HIP_CHECK(hipGraphLaunch(c->g_decode, s)); else decode_body();
+            if (c->use_graph) c->g_decode.launch(s); else decode_body();
         }
         steps += chunk;
         HIP_CHECK(hipMemcpyAsync(done_host, c->done_count.p, 4, hipMemcpyDeviceToHost, s));
@@ -1376,7 +1362,6 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
             // k_samp_cluster).  The reference's loop cannot fail for lack of free compute units (LlamaTTS.swift:714-744): the caller
             // runs the request again on kernels that do not wait for each other.
             sampler_note_failure(c->samp_scratch.p, batch, s);
-            for (auto& e : ev) (void)hipEventDestroy(e);
             throw SamplerTimeout{};
         }
         if (cb) {
@@ -1391,10 +1376,7 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         if (*done_host >= batch) break;
     }
     HIP_CHECK(hipEventRecord(ev[2], s));
-    if (cancelled) {
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        throw MisError(MIS_ERR_CANCELLED, "generation cancelled");
-    }
+    if (cancelled) throw MisError(MIS_ERR_CANCELLED, "generation cancelled");
 
     if (hidden_mode) {
         hm->n_hidden.resize(batch);
@@ -1415,7 +1397,6 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         c->timing.codec_ms = 0;
         c->timing.steps = steps;
         c->timing.step_ms_avg = steps ? c->timing.decode_ms / steps : 0;
-        for (auto& e2 : ev) (void)hipEventDestroy(e2);
         return;
     }
     // ---- parseOutput (:749-752) + de-interleave (:41-64) + SNAC decode (:759)
@@ -1571,7 +1552,6 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         double kvb = (double)batch * mean_ctx * c->L * 2.0 * c->Hkv * c->D * 2.0;
         c->timing.hbm_bytes_per_step = w + kvb;
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
 }
 
 // generate = one attempt on the fastest kernels; if the one-launch sampler could not get its blocks co-resident (the only kernel of
@@ -1762,18 +1742,14 @@ extern "C" mis_status mis_tts_time_gemm(mis_tts* c, int which, int batch, int it
         default: b = wbytes(c->q_head, c->V, d); break;
     }
     run(0);   // warm
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, s));
+    HipEvents<2> ev;
+    HIP_CHECK(hipEventRecord(ev[0], s));
     for (int i = 0; i < iters; ++i) run(i + 1);
-    HIP_CHECK(hipEventRecord(e1, s));
+    HIP_CHECK(hipEventRecord(ev[1], s));
     HIP_CHECK(hipStreamSynchronize(s));
     HIP_CHECK(hipGetLastError());
-    *avg_ms = ms_between(e0, e1) / iters;
+    *avg_ms = ms_between(ev[0], ev[1]) / iters;
     *bytes = b;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     MIS_API_END
 }
 
@@ -1889,28 +1865,24 @@ extern "C" mis_status mis_debug_launch_floor(int device, int n_kernels, int mode
     a.alloc(n); b.alloc(n);
     HIP_CHECK(hipMemset(a.p, 0, n * 4));
     dim3 grid(mode == 0 ? 1 : (mode == 1 ? 32 : 1024)), block(mode == 0 ? 64 : (mode == 1 ? 1024 : 256));
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < n_kernels; ++i) {
-        const float* src = (i & 1) ? b.p : a.p;
-        float* dst = (i & 1) ? a.p : b.p;
-        hipLaunchKernelGGL(k_floor_probe, grid, block, 0, s, src, dst, n);
+    {
+        StepGraph ge;
+        ge.capture(s, [&]() {
+            for (int i = 0; i < n_kernels; ++i) {
+                const float* src = (i & 1) ? b.p : a.p;
+                float* dst = (i & 1) ? a.p : b.p;
+                hipLaunchKernelGGL(k_floor_probe, grid, block, 0, s, src, dst, n);
+            }
+        });
+        ge.launch(s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        HipEvents<2> ev;
+        HIP_CHECK(hipEventRecord(ev[0], s));
+        for (int r = 0; r < reps; ++r) ge.launch(s);
+        HIP_CHECK(hipEventRecord(ev[1], s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        *us_per_kernel = ms_between(ev[0], ev[1]) * 1e3 / ((double)reps * n_kernels);
     }
-    HIP_CHECK(hipStreamEndCapture(s, &g));
-    HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    HIP_CHECK(hipGraphLaunch(ge, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, s));
-    for (int r = 0; r < reps; ++r) HIP_CHECK(hipGraphLaunch(ge, s));
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    *us_per_kernel = ms_between(e0, e1) * 1e3 / ((double)reps * n_kernels);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
     (void)hipStreamDestroy(s);
     MIS_API_END
 }

@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "lm_kernels.h"
 #include "sampler_math.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -624,13 +625,6 @@ extern "C" int mis_marvis_launches_per_frame(const mis_marvis* c) { return c ? c
 #define MV_MAX_SEQ 2048
 #define MV_MAX_AUDIO_FRAMES 750            // Int(60000 / 80.0), MarvisTTSModel.swift:402
 
-struct MvStreamHook {
-    int chunk_frames = 0;
-    std::function<void(int f0, int fn)> on_boundary;    // frames [f0, f0 + fn) were just enqueued on c->s
-    std::function<void(int f)> pre_sync;                // f frames enqueued; the loop is about to synchronise with the host
-    std::function<void(int f)> poll;                    // ... and has
-    std::function<void()> loop_done;                    // every row has ended (before the frames after the last full chunk go out)
-};
 struct MvDebug {                                        // teacher forcing (mis_debug_marvis_forced_logits)
     const int32_t* forced = nullptr;                    // host [batch][F][Cb]
     int F = 0;
@@ -650,7 +644,7 @@ static void mv_check_params(const mis_marvis* c, const mis_marvis_params* gp, in
 
 static void mv_generate_codes(mis_marvis* c, const int32_t* tokens, const uint8_t* mask, const int32_t* prompt_lens, int P, int batch,
                               const mis_marvis_params* gp, const int32_t* row_max_frames, std::vector<int32_t>& codes_host,
-                              std::vector<int32_t>& n_frames_host, int* stride_out, const volatile int* cancel, MvStreamHook* hook = nullptr,
+                              std::vector<int32_t>& n_frames_host, int* stride_out, const volatile int* cancel, FrameStreamHook* hook = nullptr,
                               MvDebug* dbg = nullptr) {
     int Cb = 0, max_frames = 0;
     mv_check_params(c, gp, &Cb, &max_frames);
@@ -701,8 +695,8 @@ static void mv_generate_codes(mis_marvis* c, const int32_t* tokens, const uint8_
         c->sampled.zero(s); c->logits_dbg.zero(s);
     }
     const bool use_graph = getenv("MIS_NO_GRAPH") == nullptr;
-    hipGraphExec_t g_frame = nullptr;
-    try {
+    {
+        StepGraph g_frame;
         // ---- prefill: the right-aligned prompt matrix, all positions at once where lm_prefill.hip applies, else one position a launch chain
         if (tts_internal_prefill_rows_ok(c->bb, Lmax)) {
             c->pf_rows.alloc((size_t)Lmax * Mpad * d);
@@ -757,50 +751,23 @@ static void mv_generate_codes(mis_marvis* c, const int32_t* tokens, const uint8_
             tts_internal_enqueue_layers(c->bb, c->in_emb.p, Mpad, c->iota.p);       // the next frame's backbone position
         };
         if (use_graph) {
-            hipGraph_t g = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            try { frame_body(); } catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(s, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-            HIP_CHECK(hipStreamEndCapture(s, &g));
-            size_t n_nodes = 0;
-            HIP_CHECK(hipGraphGetNodes(g, nullptr, &n_nodes));         // what the graph really holds (the formula above is the expectation)
-            c->last_launches = (int)n_nodes;
-            HIP_CHECK(hipGraphInstantiate(&g_frame, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
+            g_frame.capture(s, frame_body);
+            c->last_launches = g_frame.nodes();                        // what the graph really holds (the formula above is the expectation)
         }
         PinnedBuf<int32_t> done_pin(1);
-        int32_t* done_host = done_pin.p;
-        *done_host = 0;
-        const int loop_frames = dbg ? dbg->F : max_frames;
-        int f = 0, last_boundary = 0;
-        const int poll = 8;
-        while (f < loop_frames) {
-            int chunk = std::min(poll, loop_frames - f);
-            if (hook) chunk = std::min(chunk, last_boundary + hook->chunk_frames - f);
-            for (int i = 0; i < chunk; ++i) { if (use_graph) HIP_CHECK(hipGraphLaunch(g_frame, s)); else frame_body(); }
-            f += chunk;
-            if (hook && f - last_boundary == hook->chunk_frames) { hook->on_boundary(last_boundary, f - last_boundary); last_boundary = f; }
-            HIP_CHECK(hipMemcpyAsync(done_host, c->done.p, 4, hipMemcpyDeviceToHost, s));
-            if (hook) hook->pre_sync(f);
-            HIP_CHECK(hipStreamSynchronize(s));
-            if (hook) hook->poll(f);
-            if (*done_host >= batch) break;
-            if (cancel && *cancel) throw MisError(MIS_ERR_CANCELLED, "generation cancelled");
-        }
-        HIP_CHECK(hipGetLastError());
-        if (hook) {   // the frames after the last full chunk: rows still running there have <= f - last_boundary of them
-            n_frames_host.resize(batch);
-            HIP_CHECK(hipMemcpyAsync(n_frames_host.data(), c->n_frames.p, batch * 4, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            int longest = 0;
-            for (int b = 0; b < batch; ++b) longest = std::max(longest, n_frames_host[b]);
-            hook->loop_done();
-            if (longest > last_boundary) hook->on_boundary(last_boundary, longest - last_boundary);
-        }
-    } catch (...) {
-        if (g_frame) (void)hipGraphExecDestroy(g_frame);
-        throw;
+        *done_pin.p = 0;
+        run_frame_loop(dbg ? dbg->F : max_frames, batch, cancel, hook,
+                       [&]() { if (use_graph) g_frame.launch(s); else frame_body(); },
+                       [&]() { HIP_CHECK(hipMemcpyAsync(done_pin.p, c->done.p, 4, hipMemcpyDeviceToHost, s)); },
+                       [&]() { HIP_CHECK(hipStreamSynchronize(s)); return (int)*done_pin.p; },
+                       [&]() { HIP_CHECK(hipGetLastError()); },
+                       [&]() {
+                           n_frames_host.resize(batch);
+                           HIP_CHECK(hipMemcpyAsync(n_frames_host.data(), c->n_frames.p, batch * 4, hipMemcpyDeviceToHost, s));
+                           HIP_CHECK(hipStreamSynchronize(s));
+                           return *std::max_element(n_frames_host.begin(), n_frames_host.end());
+                       });
     }
-    if (g_frame) (void)hipGraphExecDestroy(g_frame);
     codes_host.resize((size_t)batch * max_frames * Cb);
     n_frames_host.resize(batch);
     HIP_CHECK(hipMemcpyAsync(codes_host.data(), c->codes.p, codes_host.size() * 4, hipMemcpyDeviceToHost, s));
@@ -901,93 +868,31 @@ extern "C" mis_status mis_marvis_generate(mis_marvis* c, mis_mimi* mimi, const i
     std::vector<int32_t> codes, nf;
     int stride = 0;
 
-    struct Chunk { int f0, fn; PinnedBuf<float> wav; PinnedBuf<int32_t> nf; hipEvent_t done = nullptr; bool emitted = false; };
-    std::deque<std::unique_ptr<Chunk>> chunks;
+    struct Session {                                     // Mimi's decode-stream session while THIS call holds it
+        mis_mimi* m = nullptr;
+        ~Session() { if (m) (void)mis_mimi_decode_stream_end(m); }
+    } session;
+    std::unique_ptr<ChunkedAudio> pipe;
     DevBuf<float> wav_dev;
-    hipEvent_t ev_lm = nullptr;
-    bool own_session = false;
-    auto cleanup = [&]() {
-        if (ev_lm) { (void)hipEventDestroy(ev_lm); ev_lm = nullptr; }
-        for (auto& ch : chunks) if (ch->done) { (void)hipEventDestroy(ch->done); ch->done = nullptr; }
-        if (own_session) { (void)mis_mimi_decode_stream_end(mimi); own_session = false; }
-    };
-    auto emit_ready = [&](bool wait) {
-        for (auto& ch : chunks) {
-            if (ch->emitted) continue;
-            if (wait) HIP_CHECK(hipEventSynchronize(ch->done));
-            else if (hipEventQuery(ch->done) != hipSuccess) { (void)hipGetLastError(); break; }     // chunks finish in order
-            for (int b = 0; b < batch; ++b) {
-                const int valid = std::min(std::max(ch->nf.p[b] - ch->f0, 0), ch->fn);
-                if (valid > 0) on_event(user, b, MIS_EVENT_AUDIO, ch->wav.p + (size_t)b * ch->fn * up, (int64_t)valid * up);
-            }
-            ch->emitted = true;
-        }
-    };
-    MvStreamHook hook;
-    PinnedBuf<int32_t> tok_codes, tok_nf;
-    int tok_f = 0, tok_pending_f = 0;
+    FrameStreamHook hook;
     const auto t_start = std::chrono::steady_clock::now();
     try {
         HIP_CHECK(hipSetDevice(c->device));
         if (streaming) {
-            const int cap = max_frames, cf = std::min(chunk_frames, cap);
             MIS_REQUIRE(mis_mimi_decode_stream_begin(mimi, batch) == MIS_OK, MIS_ERR_GENERATION_FAILED, "Mimi stream: %s", mis_last_error());
-            own_session = true;
-            wav_dev.alloc((size_t)batch * cf * up);
-            HIP_CHECK(hipEventCreateWithFlags(&ev_lm, hipEventDisableTiming));
-            hook.chunk_frames = chunk_frames;
-            hook.on_boundary = [&](int f0, int fn) {
-                auto ch = std::make_unique<Chunk>();
-                ch->f0 = f0; ch->fn = fn;
-                ch->wav.alloc((size_t)batch * fn * up);
-                ch->nf.alloc(batch);
-                HIP_CHECK(hipEventCreateWithFlags(&ch->done, hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(ev_lm, c->s));                  // frames < f0 + fn are final once this fires
-                HIP_CHECK(hipStreamWaitEvent(s_mimi, ev_lm, 0));
-                // the loop's code store is [B][max_frames][Cb]: no transposition, the quantizer kernel takes the strides
-                mimi_internal_stream_step_device(mimi, c->codes.p + (size_t)f0 * Cb, (int64_t)max_frames * Cb, 1, Cb, Cb, fn, wav_dev.p, (int64_t)fn * up);
-                HIP_CHECK(hipMemcpyAsync(ch->wav.p, wav_dev.p, (size_t)batch * fn * up * 4, hipMemcpyDeviceToHost, s_mimi));
-                HIP_CHECK(hipMemcpyAsync(ch->nf.p, c->n_frames.p, (size_t)batch * 4, hipMemcpyDeviceToHost, s_mimi));
-                HIP_CHECK(hipEventRecord(ch->done, s_mimi));
-                chunks.push_back(std::move(ch));
+            session.m = mimi;
+            pipe = std::make_unique<ChunkedAudio>(batch, Cb, max_frames, chunk_frames, up, c->s, s_mimi, &c->codes, &c->n_frames, on_event, user, Cb);
+            pipe->t_start = t_start; pipe->prompt_lens = prompt_lens;
+            // the loop's code store is [B][max_frames][Cb]: no transposition, the quantizer kernel takes the strides
+            pipe->decode = [&](int f0, int fn, float* wav, int64_t row_stride) {
+                mimi_internal_stream_step_device(mimi, c->codes.p + (size_t)f0 * Cb, (int64_t)max_frames * Cb, 1, Cb, Cb, fn, wav, row_stride);
             };
-            tok_codes.alloc((size_t)batch * 8 * Cb);
-            tok_nf.alloc(batch);
-            hook.pre_sync = [&](int f) {
-                MIS_REQUIRE(f - tok_f <= 8, MIS_ERR_GENERATION_FAILED, "token window");
-                if (f > tok_f)
-                    HIP_CHECK(hipMemcpy2DAsync(tok_codes.p, (size_t)8 * Cb * 4, c->codes.p + (size_t)tok_f * Cb, (size_t)max_frames * Cb * 4,
-                                               (size_t)(f - tok_f) * Cb * 4, batch, hipMemcpyDeviceToHost, c->s));
-                HIP_CHECK(hipMemcpyAsync(tok_nf.p, c->n_frames.p, (size_t)batch * 4, hipMemcpyDeviceToHost, c->s));
-                tok_pending_f = f;
-            };
-            hook.poll = [&](int) {
-                for (int b = 0; b < batch; ++b)
-                    for (int i = tok_f; i < std::min(tok_nf.p[b], tok_pending_f); ++i)
-                        on_event(user, b, MIS_EVENT_TOKEN, &tok_codes.p[((size_t)b * 8 + (i - tok_f)) * Cb], Cb);
-                tok_f = tok_pending_f;
-                emit_ready(false);
-            };
-            hook.loop_done = [&]() {
-                const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-                size_t free_b = 0, total_b = 0;
-                (void)hipMemGetInfo(&free_b, &total_b);
-                for (int b = 0; b < batch; ++b) {
-                    mis_gen_info info{};
-                    info.prompt_token_count = prompt_lens[b];
-                    info.generation_token_count = tok_nf.p[b];
-                    info.generate_time = secs;
-                    info.tokens_per_second = secs > 0 ? tok_nf.p[b] / secs : 0;
-                    info.peak_memory_gb = (double)(total_b - free_b) / 1e9;
-                    on_event(user, b, MIS_EVENT_INFO, &info, 1);
-                }
-            };
+            hook = pipe->hook(chunk_frames);
         }
         mv_generate_codes(c, tokens, mask, prompt_lens, P, batch, params, row_max_frames, codes, nf, &stride, cancel_flag, streaming ? &hook : nullptr);
-        if (streaming) emit_ready(true);
+        if (streaming) pipe->emit_ready(true);
     } catch (...) {
         (void)hipStreamSynchronize(s_mimi);
-        cleanup();
         throw;
     }
     int64_t longest = 0;
@@ -998,16 +903,12 @@ extern "C" mis_status mis_marvis_generate(mis_marvis* c, mis_mimi* mimi, const i
     memset(host, 0, (size_t)std::max<int64_t>(longest, 1) * batch * 4);
     try {
         if (streaming) {
-            for (auto& ch : chunks)
-                for (int b = 0; b < batch; ++b) {
-                    const int valid = std::min(std::max(nf[b] - ch->f0, 0), ch->fn);
-                    if (valid > 0) memcpy(host + (size_t)b * longest + (size_t)ch->f0 * up, ch->wav.p + (size_t)b * ch->fn * up, (size_t)valid * up * 4);
-                }
+            pipe->gather(host, longest, nf);
         } else if (longest_f > 0) {
             // one session over the frames of every row (rows right-padded with zero codes: every layer is causal, a row's samples do not
             // depend on what follows them), in sub-steps that bound the staging buffer
             MIS_REQUIRE(mis_mimi_decode_stream_begin(mimi, batch) == MIS_OK, MIS_ERR_GENERATION_FAILED, "Mimi stream: %s", mis_last_error());
-            own_session = true;
+            session.m = mimi;
             const int sub = 64;
             wav_dev.alloc((size_t)batch * std::min(sub, longest_f) * up);
             HIP_CHECK(hipStreamSynchronize(c->s));
@@ -1029,11 +930,8 @@ extern "C" mis_status mis_marvis_generate(mis_marvis* c, mis_mimi* mimi, const i
         }
     } catch (...) {
         (void)hipStreamSynchronize(s_mimi);
-        cleanup();
         throw;
     }
-    cleanup();
-    chunks.clear();
     if (codes_out) {
         PinnedBuf<int32_t> ch(codes.size() + 1);
         memcpy(ch.p, codes.data(), codes.size() * 4);

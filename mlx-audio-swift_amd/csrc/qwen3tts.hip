@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "lm_kernels.h"
 #include "q3_kernels.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -412,16 +413,7 @@ extern "C" mis_status mis_qwen3tts_finalize(mis_qwen3tts* c) {
 }
 
 // ---------------------------------------------------------------------------- generate (codes)
-// generateStream: the frame loop tells the caller whenever another `chunk_frames` frames of every row are final on the loop's
-// stream (Qwen3TTS.swift:492-505), and lets it look for finished work after every host synchronisation.
-struct Q3StreamHook {
-    int chunk_frames = 0;
-    std::function<void(int f0, int fn)> on_boundary;    // frames [f0, f0 + fn) were just enqueued on c->s
-    std::function<void(int f)> pre_sync;                // f frames enqueued; the loop is about to synchronise with the host
-    std::function<void(int f)> poll;                    // ... and has
-    std::function<void()> loop_done;                    // every row has ended (before the frames after the last full chunk go out)
-};
-
+// generateStream: the hook of the frame loop (step_loop.h) is Qwen3TTS.swift:492-505, its tail :537-546
 static void q3_text_projection(mis_qwen3tts* c, const std::vector<int32_t>& text_ids) {
     // textProjection(textEmbedding(ids)) for every text id of the call (ResizeMLP, Qwen3TTSTalker.swift:212-225), 64 rows a time
     const int n = (int)text_ids.size();
@@ -442,7 +434,7 @@ static void q3_text_projection(mis_qwen3tts* c, const std::vector<int32_t>& text
 void q3_generate_codes(mis_qwen3tts* c, const int32_t* text_ids, const int32_t* codec_ids, const int32_t* prefill_lens, int P,
                        const int32_t* trailing_ids, const int32_t* trailing_lens, int Tt, int batch, const mis_qwen3tts_params* gp,
                        const int32_t* row_max_frames, std::vector<int32_t>& codes_host, std::vector<int32_t>& n_frames_host,
-                       int* stride_out, const volatile int* cancel, Q3StreamHook* hook = nullptr) {
+                       int* stride_out, const volatile int* cancel, FrameStreamHook* hook = nullptr) {
     MIS_REQUIRE(c->finalized, MIS_ERR_NOT_INITIALIZED, "Qwen3-TTS model not finalized");
     MIS_REQUIRE(batch >= 1 && batch <= 64 && P >= 1 && Tt >= 0, MIS_ERR_INVALID_INPUT, "bad batch / prompt sizes");
     MIS_REQUIRE(gp->max_frames >= 1, MIS_ERR_INVALID_INPUT, "max_frames must be positive");
@@ -499,14 +491,6 @@ void q3_generate_codes(mis_qwen3tts* c, const int32_t* text_ids, const int32_t* 
     ptabs_dev.alloc(G - 1);
     HIP_CHECK(hipMemcpyAsync(ptabs_dev.p, ptabs.data(), (G - 1) * sizeof(void*), hipMemcpyHostToDevice, s));
 
-    auto capture = [&](hipGraphExec_t* exec, auto&& body) {
-        hipGraph_t g = nullptr;
-        HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        try { body(); } catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(s, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-        HIP_CHECK(hipStreamEndCapture(s, &g));
-        HIP_CHECK(hipGraphInstantiate(exec, g, nullptr, nullptr, 0));
-        HIP_CHECK(hipGraphDestroy(g));
-    };
     const bool use_graph = getenv("MIS_NO_GRAPH") == nullptr;
 
     // ---- prefill: one talker position per replay over the right-aligned prompt matrix
@@ -516,8 +500,8 @@ void q3_generate_codes(mis_qwen3tts* c, const int32_t* text_ids, const int32_t* 
         hipLaunchKernelGGL(k_q3_bump, dim3(1), dim3(64), 0, s, c->step_counter.p);
         tts_internal_enqueue_layers(c->talker, c->in_emb.p, Mpad, c->iota.p);
     };
-    hipGraphExec_t g_prefill = nullptr, g_frame = nullptr;
-    try {
+    {
+        StepGraph g_prefill, g_frame;
         if (tts_internal_prefill_rows_ok(c->talker, Lmax)) {
             // all prompt positions through the talker at once (lm_prefill.hip: [positions x rows] GEMMs on the packed weights); the
             // position-by-position graph below remains for quantised roles, odd widths and MIS_PREFILL_SEQ=1
@@ -526,8 +510,8 @@ void q3_generate_codes(mis_qwen3tts* c, const int32_t* text_ids, const int32_t* 
                                c->codec_emb.p, c->Vc, c->ref_rows.p, c->n_ref_rows, c->pf_rows.p, d, batch, Mpad);
             tts_internal_prefill_rows(c->talker, c->pf_rows.p, prefill_lens, Lmax);
         } else {
-            if (use_graph) capture(&g_prefill, prefill_body);
-            for (int j = 0; j < Lmax; ++j) { if (use_graph) HIP_CHECK(hipGraphLaunch(g_prefill, s)); else prefill_body(); }
+            if (use_graph) g_prefill.capture(s, prefill_body);
+            for (int j = 0; j < Lmax; ++j) { if (use_graph) g_prefill.launch(s); else prefill_body(); }
         }
         {
             std::vector<uint8_t> ones(Mpad, 0);
@@ -577,42 +561,21 @@ void q3_generate_codes(mis_qwen3tts* c, const int32_t* text_ids, const int32_t* 
             // the next frame's talker position
             tts_internal_enqueue_layers(c->talker, c->in_emb.p, Mpad, c->iota.p);
         };
-        if (use_graph) capture(&g_frame, frame_body);
+        if (use_graph) g_frame.capture(s, frame_body);
         PinnedBuf<int32_t> done_pin(1);
-        int32_t* done_host = done_pin.p;
-        *done_host = 0;
-        int f = 0, last_boundary = 0;
-        const int poll = 8;
-        while (f < max_frames) {
-            int chunk = std::min(poll, max_frames - f);
-            if (hook) chunk = std::min(chunk, last_boundary + hook->chunk_frames - f);
-            for (int i = 0; i < chunk; ++i) { if (use_graph) HIP_CHECK(hipGraphLaunch(g_frame, s)); else frame_body(); }
-            f += chunk;
-            if (hook && f - last_boundary == hook->chunk_frames) { hook->on_boundary(last_boundary, f - last_boundary); last_boundary = f; }
-            HIP_CHECK(hipMemcpyAsync(done_host, c->done.p, 4, hipMemcpyDeviceToHost, s));
-            if (hook) hook->pre_sync(f);
-            HIP_CHECK(hipStreamSynchronize(s));
-            if (hook) hook->poll(f);
-            if (*done_host >= batch) break;
-            if (cancel && *cancel) throw MisError(MIS_ERR_CANCELLED, "generation cancelled");
-        }
-        HIP_CHECK(hipGetLastError());
-        if (hook) {   // the frames after the last full chunk (:537-546): rows still running there have <= f - last_boundary of them
-            n_frames_host.resize(batch);
-            HIP_CHECK(hipMemcpyAsync(n_frames_host.data(), c->n_frames.p, batch * 4, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            int longest = 0;
-            for (int b = 0; b < batch; ++b) longest = std::max(longest, n_frames_host[b]);
-            hook->loop_done();
-            if (longest > last_boundary) hook->on_boundary(last_boundary, longest - last_boundary);
-        }
-    } catch (...) {
-        if (g_prefill) (void)hipGraphExecDestroy(g_prefill);
-        if (g_frame) (void)hipGraphExecDestroy(g_frame);
-        throw;
+        *done_pin.p = 0;
+        run_frame_loop(max_frames, batch, cancel, hook,
+                       [&]() { if (use_graph) g_frame.launch(s); else frame_body(); },
+                       [&]() { HIP_CHECK(hipMemcpyAsync(done_pin.p, c->done.p, 4, hipMemcpyDeviceToHost, s)); },
+                       [&]() { HIP_CHECK(hipStreamSynchronize(s)); return (int)*done_pin.p; },
+                       [&]() { HIP_CHECK(hipGetLastError()); },
+                       [&]() {
+                           n_frames_host.resize(batch);
+                           HIP_CHECK(hipMemcpyAsync(n_frames_host.data(), c->n_frames.p, batch * 4, hipMemcpyDeviceToHost, s));
+                           HIP_CHECK(hipStreamSynchronize(s));
+                           return *std::max_element(n_frames_host.begin(), n_frames_host.end());
+                       });
     }
-    if (g_prefill) (void)hipGraphExecDestroy(g_prefill);
-    if (g_frame) (void)hipGraphExecDestroy(g_frame);
     codes_host.resize((size_t)batch * max_frames * G);
     n_frames_host.resize(batch);
     HIP_CHECK(hipMemcpyAsync(codes_host.data(), c->codes.p, codes_host.size() * 4, hipMemcpyDeviceToHost, s));
@@ -854,33 +817,13 @@ extern "C" mis_status mis_qwen3tts_generate(mis_qwen3tts* c, const int32_t* text
     const bool streaming = on_event && chunk_frames > 0;
     MIS_REQUIRE(G == c->cfg.dec_num_quantizers, MIS_ERR_INVALID_INPUT, "num_code_groups (%d) != decoder quantizers (%d)", G, c->cfg.dec_num_quantizers);
 
-    struct Chunk { int f0, fn; PinnedBuf<float> wav; PinnedBuf<int32_t> nf; hipEvent_t done = nullptr; bool emitted = false; };
-    std::deque<std::unique_ptr<Chunk>> chunks;
-    DevBuf<float> wav_dev;
-    hipEvent_t ev_lm = nullptr;
-    bool own_session = false;                       // the decode-stream session of the handle was opened by THIS call
-    auto cleanup = [&]() {
-        if (ev_lm) { (void)hipEventDestroy(ev_lm); ev_lm = nullptr; }
-        for (auto& ch : chunks) if (ch->done) { (void)hipEventDestroy(ch->done); ch->done = nullptr; }
-        if (own_session) { q3dec_stream_end(c->dec); own_session = false; }      // never a session the host opened itself
-    };
-    auto emit_ready = [&](bool wait) {
-        for (auto& ch : chunks) {
-            if (ch->emitted) continue;
-            if (wait) HIP_CHECK(hipEventSynchronize(ch->done));
-            else if (hipEventQuery(ch->done) != hipSuccess) { (void)hipGetLastError(); break; }     // chunks finish in order
-            for (int b = 0; b < batch; ++b) {
-                const int valid = std::min(std::max(ch->nf.p[b] - ch->f0, 0), ch->fn);
-                if (valid > 0) on_event(user, b, MIS_EVENT_AUDIO, ch->wav.p + (size_t)b * ch->fn * up, (int64_t)valid * up);
-            }
-            ch->emitted = true;
-        }
-    };
-    Q3StreamHook hook;
-    // MIS_EVENT_TOKEN: code 0 of every frame as the host learns of it (onToken, :484), the EOS id included when a row ends on it
-    PinnedBuf<int32_t> tok_codes, tok_nf;
+    struct Session {                                     // the handle's decode-stream session while THIS call holds it:
+        mis_q3dec* d = nullptr;                          // never a session the host opened itself
+        ~Session() { if (d) q3dec_stream_end(d); }
+    } session;
+    std::unique_ptr<ChunkedAudio> pipe;
+    FrameStreamHook hook;
     std::vector<char> eos_sent(batch, 0);
-    int tok_f = 0, tok_pending_f = 0;
     const auto t_start = std::chrono::steady_clock::now();
     try {
         if (streaming) {
@@ -890,72 +833,30 @@ extern "C" mis_status mis_qwen3tts_generate(mis_qwen3tts* c, const int32_t* text
             MIS_REQUIRE(q3dec_stream_pos(c->dec) < 0, MIS_ERR_INVALID_INPUT,
                         "generateStream needs the handle's decode-stream session, but the host has one open (mis_qwen3tts_decode_stream_end first)");
             q3dec_stream_begin(c->dec, batch, cap, std::min(chunk_frames, cap), !c->stream_exact, c->s_dec);
-            own_session = true;
-            wav_dev.alloc((size_t)batch * std::min(chunk_frames, cap) * up);
-            HIP_CHECK(hipEventCreateWithFlags(&ev_lm, hipEventDisableTiming));
-            hook.chunk_frames = chunk_frames;
-            hook.on_boundary = [&](int f0, int fn) {
-                auto ch = std::make_unique<Chunk>();
-                ch->f0 = f0; ch->fn = fn;
-                ch->wav.alloc((size_t)batch * fn * up);
-                ch->nf.alloc(batch);
-                HIP_CHECK(hipEventCreateWithFlags(&ch->done, hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(ev_lm, c->s));                  // frames < f0 + fn are final once this fires
-                HIP_CHECK(hipStreamWaitEvent(c->s_dec, ev_lm, 0));
-                // the loop's code store is [B][max_frames][G]: no transposition, the quantizer kernel takes the strides
-                q3dec_stream_step(c->dec, c->codes.p + (size_t)f0 * G, (int64_t)params->max_frames * G, 1, G, fn, wav_dev.p, (int64_t)fn * up,
-                                  c->s_dec);
-                HIP_CHECK(hipMemcpyAsync(ch->wav.p, wav_dev.p, (size_t)batch * fn * up * 4, hipMemcpyDeviceToHost, c->s_dec));
-                // rows that ended inside / before this chunk keep their count; running rows have >= f0 + fn (clipped at emission)
-                HIP_CHECK(hipMemcpyAsync(ch->nf.p, c->n_frames.p, (size_t)batch * 4, hipMemcpyDeviceToHost, c->s_dec));
-                HIP_CHECK(hipEventRecord(ch->done, c->s_dec));
-                chunks.push_back(std::move(ch));
+            session.d = c->dec;
+            // MIS_EVENT_TOKEN: code 0 of every frame as the host learns of it (onToken, :484), the EOS id included when a row ends on it;
+            // MIS_EVENT_INFO: AudioGenerationInfo (:524-534), one per row
+            pipe = std::make_unique<ChunkedAudio>(batch, G, cap, chunk_frames, up, c->s, c->s_dec, &c->codes, &c->n_frames, on_event, user, 1);
+            pipe->t_start = t_start;
+            // the loop's code store is [B][max_frames][G]: no transposition, the quantizer kernel takes the strides
+            pipe->decode = [&](int f0, int fn, float* wav, int64_t row_stride) {
+                q3dec_stream_step(c->dec, c->codes.p + (size_t)f0 * G, (int64_t)cap * G, 1, G, fn, wav, row_stride, c->s_dec);
             };
-            tok_codes.alloc((size_t)batch * 8 * G);
-            tok_nf.alloc(batch);
-            hook.pre_sync = [&](int f) {
-                MIS_REQUIRE(f - tok_f <= 8, MIS_ERR_GENERATION_FAILED, "token window");
-                if (f > tok_f)
-                    HIP_CHECK(hipMemcpy2DAsync(tok_codes.p, (size_t)8 * G * 4, c->codes.p + (size_t)tok_f * G, (size_t)params->max_frames * G * 4,
-                                               (size_t)(f - tok_f) * G * 4, batch, hipMemcpyDeviceToHost, c->s));
-                HIP_CHECK(hipMemcpyAsync(tok_nf.p, c->n_frames.p, (size_t)batch * 4, hipMemcpyDeviceToHost, c->s));
-                tok_pending_f = f;
-            };
-            hook.poll = [&](int f) {
-                for (int b = 0; b < batch; ++b) {
-                    const int cap = row_max_frames ? std::max(1, std::min(row_max_frames[b], params->max_frames)) : params->max_frames;
-                    for (int i = tok_f; i < std::min(tok_nf.p[b], tok_pending_f); ++i)
-                        on_event(user, b, MIS_EVENT_TOKEN, &tok_codes.p[((size_t)b * 8 + (i - tok_f)) * G], 1);
-                    if (!eos_sent[b] && tok_nf.p[b] < std::min(tok_pending_f, cap)) {
-                        const int32_t eos = c->cfg.codec_eos_token_id;
-                        on_event(user, b, MIS_EVENT_TOKEN, &eos, 1);
-                        eos_sent[b] = 1;
-                    }
-                }
-                tok_f = tok_pending_f;
-                (void)f;
-                emit_ready(false);
-            };
-            hook.loop_done = [&]() {                                   // AudioGenerationInfo (:524-534): one per row
-                const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-                size_t free_b = 0, total_b = 0;
-                (void)hipMemGetInfo(&free_b, &total_b);
-                for (int b = 0; b < batch; ++b) {
-                    mis_gen_info info{};
-                    info.generation_token_count = tok_nf.p[b];
-                    info.generate_time = secs;
-                    info.tokens_per_second = secs > 0 ? tok_nf.p[b] / secs : 0;
-                    info.peak_memory_gb = (double)(total_b - free_b) / 1e9;
-                    on_event(user, b, MIS_EVENT_INFO, &info, 1);
+            pipe->row_polled = [&](int b, int nf_b, int f) {
+                const int row_cap = row_max_frames ? std::max(1, std::min(row_max_frames[b], cap)) : cap;
+                if (!eos_sent[b] && nf_b < std::min(f, row_cap)) {
+                    const int32_t eos = c->cfg.codec_eos_token_id;
+                    on_event(user, b, MIS_EVENT_TOKEN, &eos, 1);
+                    eos_sent[b] = 1;
                 }
             };
+            hook = pipe->hook(chunk_frames);
         }
         q3_generate_codes(c, text_ids, codec_ids, prefill_lens, P, trailing_ids, trailing_lens, Tt, batch, params, row_max_frames, codes, nf,
                           &stride, cancel_flag, streaming ? &hook : nullptr);
-        if (streaming) emit_ready(true);
+        if (streaming) pipe->emit_ready(true);
     } catch (...) {
         (void)hipStreamSynchronize(c->s_dec);
-        cleanup();
         throw;
     }
     // in-context voice cloning, non-streaming tail (Qwen3TTS.swift:547-563): a row whose prompt holds reference frame rows decodes
@@ -1015,13 +916,7 @@ extern "C" mis_status mis_qwen3tts_generate(mis_qwen3tts* c, const int32_t* text
     float* host = host_pin.p;
     memset(host, 0, (size_t)std::max<int64_t>(longest, 1) * batch * 4);
     if (streaming) {
-        for (auto& ch : chunks)
-            for (int b = 0; b < batch; ++b) {
-                const int valid = std::min(std::max(nf[b] - ch->f0, 0), ch->fn);
-                if (valid > 0) memcpy(host + (size_t)b * longest + (size_t)ch->f0 * up, ch->wav.p + (size_t)b * ch->fn * up, (size_t)valid * up * 4);
-            }
-        cleanup();
-        chunks.clear();
+        pipe->gather(host, longest, nf);
     } else {
         DevBuf<float> wav;
         DevBuf<int32_t> dcodes_dev;

@@ -25,6 +25,7 @@
 // Prepare and mel stay in front of it: the mel front end allocates and synchronises.
 #include "common.h"
 #include "host_weights.h"
+#include "step_loop.h"
 #include "kernels.h"
 #include "lm_kernels.h"
 #include "whisper_kernels.h"
@@ -39,8 +40,6 @@
 #define ST_CLS_MID 64
 #define ST_TS 8                  // positions per k_st_pool_scores block
 #define ST_LN_EPS 1e-5f       // MLXNN.LayerNorm default
-
-struct StGraph { hipGraphExec_t exec = nullptr; int nodes = 0; };
 
 struct mis_smartturn {
     int device = 0;
@@ -61,15 +60,10 @@ struct mis_smartturn {
     DevBuf<int64_t> lens;
     DevBuf<int32_t> pred;
     DevBuf<bf16_t> col1, h1, col2, h, x, qkv, att, ff, kc, vc, enc_out;
-    std::map<int, StGraph> graphs;
+    std::map<int, StepGraph> graphs;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float ms_prepare = 0.0f, ms_encoder = 0.0f, ms_head = 0.0f;
 };
-
-static void st_drop_graphs(mis_smartturn* c) {
-    for (auto& kv : c->graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    c->graphs.clear();
-}
 
 extern "C" mis_status mis_smartturn_create(const mis_smartturn_config* cfg, int device, mis_smartturn** out) {
     MIS_API_BEGIN
@@ -108,7 +102,7 @@ extern "C" void mis_smartturn_destroy(mis_smartturn* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    st_drop_graphs(c);
+    c->graphs.clear();
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -437,7 +431,7 @@ __global__ void __launch_bounds__(ST_POOL_HID) k_st_pool_head(StHeadParams p) {
 static void st_reserve(mis_smartturn* c, int batch) {
     if (batch <= c->cap) return;
     HIP_CHECK(hipStreamSynchronize(c->stream));
-    st_drop_graphs(c);                                                // they hold the old addresses
+    c->graphs.clear();                                                // they hold the old addresses
     const size_t B = batch, M1 = B * c->F, M = B * c->T, d = c->d;
     c->prep.alloc(B * c->W); c->part0.alloc(B * c->nch); c->part1.alloc(B * c->nch); c->feat.alloc(M1 * c->nmel);
     c->lens.alloc(ST_MAX_BATCH); c->thr.alloc(1);
@@ -486,27 +480,16 @@ static void st_run_chain(mis_smartturn* c, int B, float threshold) {
         HIP_CHECK(hipGetLastError());
         c->last_launches = st_chain_launches(c);
     } else {
-        StGraph& g = c->graphs[B];
-        if (!g.exec) {
+        StepGraph& g = c->graphs[B];
+        if (!g) {
             st_enqueue_chain(c, B, nullptr);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipStreamSynchronize(s));
-            hipGraph_t graph = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            try { st_enqueue_chain(c, B, nullptr); }
-            catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(s, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-            HIP_CHECK(hipStreamEndCapture(s, &graph));
-            size_t n_nodes = 0;
-            HIP_CHECK(hipGraphGetNodes(graph, nullptr, &n_nodes));
-            hipGraphExec_t exec = nullptr;
-            const hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HIP_CHECK(e);
-            g.exec = exec; g.nodes = (int)n_nodes;
+            g.capture(s, [&]() { st_enqueue_chain(c, B, nullptr); });
             HIP_CHECK(hipEventRecord(c->ev[1], s));
         }
-        HIP_CHECK(hipGraphLaunch(g.exec, s));
-        c->last_launches = g.nodes;
+        g.launch(s);
+        c->last_launches = g.nodes();
     }
     HIP_CHECK(hipEventRecord(c->ev[3], s));
     HIP_CHECK(hipStreamSynchronize(s));

@@ -36,6 +36,7 @@
 // Tests: tests/test_gpu_token_engine.py (oracle and launch-chain logits, sampler bit-exact on its own logits, hidden rows, stop id,
 // long contexts, 1 / 2 / 4 / 8 XCDs), tests/test_gpu_soprano.py, tests/test_isa_cpu.py (register budget).
 #include "token_engine_impl.h"
+#include "step_loop.h"
 #include <string.h>
 #include <chrono>
 #include <mutex>
@@ -273,11 +274,6 @@ TokenEngineScratch* token_engine_scratch_create() { return new TokenEngineScratc
 void token_engine_scratch_destroy(TokenEngineScratch* s) { delete s; }
 
 namespace {
-struct TeEvents {                      // (destroyed on every path)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    TeEvents() { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); }
-    ~TeEvents() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
 // 8 XCDs x 32 compute units (SPX mode of an MI355X): the worker set is "blocks with index mod 8 below xcds" of a 256-block grid, one block
 // per compute unit.  Other partition modes / parts keep the launch chain.
 bool te_device_ok(int device) {
@@ -421,8 +417,8 @@ void token_engine_run(mis_tts* lm, const TokenEngineRequest& rq, TokenEngineResu
     else if (xcds == 2) HIP_CHECK(hipFuncSetAttribute((const void*)k_token_engine<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad));
     else if (xcds == 4) HIP_CHECK(hipFuncSetAttribute((const void*)k_token_engine<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad));
     else HIP_CHECK(hipFuncSetAttribute((const void*)k_token_engine<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad));
-    TeEvents ev;
-    HIP_CHECK(hipEventRecord(ev.e0, s));
+    HipEvents<2> ev;
+    HIP_CHECK(hipEventRecord(ev[0], s));
     if (qkernel) {
         void* args[] = {&p, &qp};
         HIP_CHECK(hipLaunchKernel(qkernel, dim3(grid), dim3(TE_NT), args, pad, s));
@@ -430,7 +426,7 @@ void token_engine_run(mis_tts* lm, const TokenEngineRequest& rq, TokenEngineResu
     else if (xcds == 2) hipLaunchKernelGGL(k_token_engine<2>, dim3(grid), dim3(TE_NT), pad, s, p);
     else if (xcds == 4) hipLaunchKernelGGL(k_token_engine<4>, dim3(grid), dim3(TE_NT), pad, s, p);
     else hipLaunchKernelGGL(k_token_engine<8>, dim3(grid), dim3(TE_NT), pad, s, p);
-    HIP_CHECK(hipEventRecord(ev.e1, s));
+    HIP_CHECK(hipEventRecord(ev[1], s));
     HIP_CHECK(hipGetLastError());
     // ---- while the launch runs: the ids it has chosen so far, in order, to the caller; the caller's cancel flag to the launch
     bool cancelled = false;
@@ -446,7 +442,7 @@ void token_engine_run(mis_tts* lm, const TokenEngineRequest& rq, TokenEngineResu
     };
     if (rq.on_token || rq.cancel) {
         for (;;) {
-            const hipError_t q = hipEventQuery(ev.e1);
+            const hipError_t q = hipEventQuery(ev[1]);
             if (q == hipSuccess) break;
             if (q != hipErrorNotReady) HIP_CHECK(q);
             drain();
@@ -456,7 +452,7 @@ void token_engine_run(mis_tts* lm, const TokenEngineRequest& rq, TokenEngineResu
     }
     HIP_CHECK(hipStreamSynchronize(s));
     float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
     unsigned failed = 0;
     HIP_CHECK(hipMemcpy(&failed, sc.sync.p + 32, 4, hipMemcpyDeviceToHost));
     MIS_REQUIRE(!failed, MIS_ERR_GENERATION_FAILED, "token engine: an edge timed out (its workers were not co-resident)");

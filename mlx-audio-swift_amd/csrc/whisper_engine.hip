@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lm_kernels.h"
+#include "step_loop.h"
 #include "whisper_kernels.h"
 
 #include <math.h>
@@ -898,23 +899,16 @@ static void whisper_generate_impl(mis_whisper* c, const float* pcm, const int64_
             launch_sampler(q, batch, s);
             enqueue_decoder_step(c);
     };
-    hipGraphExec_t gexec = nullptr;
     const bool use_graph = getenv("MIS_NO_GRAPH") == nullptr;
-    try {
-        if (use_graph) {
-            hipGraph_t g = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            try { step_body(); } catch (...) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(s, &dead); if (dead) (void)hipGraphDestroy(dead); throw; }
-            HIP_CHECK(hipStreamEndCapture(s, &g));
-            HIP_CHECK(hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-        }
+    {
+        StepGraph gexec;
+        if (use_graph) gexec.capture(s, step_body);
         // stream form: the ids sampled since the last poll are announced in step order per row (the reference decodes them to a
         // text delta per step, WhisperModel.swift:242-254; detokenisation stays with the host); EOT is never announced (:238)
         std::vector<int32_t> h_ng(batch), h_tok;
         const int poll = on_event ? 3 : 7;
         for (int step = 0; step < max_tokens; ++step) {
-            if (use_graph) HIP_CHECK(hipGraphLaunch(gexec, s)); else step_body();
+            if (use_graph) gexec.launch(s); else step_body();
             if ((step & poll) == poll || step + 1 == max_tokens) {
                 HIP_CHECK(hipMemcpyAsync(done_host, c->done_count.p, 4, hipMemcpyDeviceToHost, s));
                 sampler_fail_flags_async(c->scratch.p, batch, fail_pin.p, s);
@@ -935,11 +929,7 @@ static void whisper_generate_impl(mis_whisper* c, const float* pcm, const int64_
                 if (*done_host >= batch) break;
             }
         }
-    } catch (...) {
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        throw;
     }
-    if (gexec) (void)hipGraphExecDestroy(gexec);
     HIP_CHECK(hipGetLastError());
     if (sampler_failed) sampler_note_failure(c->scratch.p, batch, s);
     return !sampler_failed;
