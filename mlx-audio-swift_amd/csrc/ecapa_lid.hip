@@ -30,6 +30,7 @@
 #include "common.h"
 #include "f32_tile.h"
 #include "host_weights.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -357,7 +358,7 @@ struct mis_ecapa_lid {
           *att = nullptr, *sc = nullptr, *mean = nullptr, *sd = nullptr, *gate = nullptr, *rb = nullptr, *pooled = nullptr, *emb = nullptr,
           *logp = nullptr, *top_prob = nullptr;
     int last_batch = 0, last_Ts = 0, last_launches = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    HipEvents<3> ev;
     float ms_front = 0.0f, ms_model = 0.0f;
 };
 
@@ -386,7 +387,6 @@ extern "C" mis_status mis_ecapa_lid_create(const mis_ecapa_lid_config* cfg, int 
     c->device = device; c->cfg = *cfg; c->stream = stream;
     c->nm = cfg->n_mels; c->C = cfg->channels; c->A = cfg->attention_channels; c->SE = cfg->se_channels; c->E = cfg->embedding_dim;
     c->Hd = cfg->classifier_hidden_dim; c->N = cfg->num_classes; c->S = cfg->res2net_scale; c->Tcap = (int)(cfg->max_samples / LID_HOP + 1);
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -395,7 +395,6 @@ extern "C" void mis_ecapa_lid_destroy(mis_ecapa_lid* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -404,9 +403,7 @@ extern "C" void mis_ecapa_lid_destroy(mis_ecapa_lid* c) {
 extern "C" mis_status mis_ecapa_lid_set_tensor(mis_ecapa_lid* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape,
                                                int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 3, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
@@ -438,47 +435,55 @@ extern "C" mis_status mis_ecapa_lid_finalize(mis_ecapa_lid* c) {
     HostArena a(c->raw);
     std::vector<float>& fh = a.fhost;
     // BatchNorm in eval mode as scale and shift: y = x s + b, s = weight / sqrt(running_var + eps), b = bias - running_mean s
-    auto bn = [&](const std::string& p, int64_t n, size_t off[2]) {
+    auto bn = [&](const std::string& p, int64_t n, LidBN& dst) {
         const HostTensor &w = c->raw.need(p + ".weight", {n}), &b = c->raw.need(p + ".bias", {n}), &m = c->raw.need(p + ".running_mean", {n}),
                          &v = c->raw.need(p + ".running_var", {n});
-        off[0] = a.ftake(n); off[1] = a.ftake(n);
+        const size_t os = a.ftake(n, dst.s), ob = a.ftake(n, dst.b);
         for (int64_t i = 0; i < n; ++i) {
             const double s = (double)w.v[i] / sqrt((double)v.v[i] + LID_BN_EPS);
-            fh[off[0] + i] = (float)s;
-            fh[off[1] + i] = (float)((double)b.v[i] - (double)m.v[i] * s);
+            fh[os + i] = (float)s;
+            fh[ob + i] = (float)((double)b.v[i] - (double)m.v[i] * s);
         }
     };
-    auto whole = [&](const std::string& name, std::initializer_list<int64_t> shape) {
+    auto whole = [&](const std::string& name, std::initializer_list<int64_t> shape, const float*& dst) {
         int64_t n = 1;
         for (auto d : shape) n *= d;
-        return a.fvec(name, shape, n);
+        a.fvec(name, shape, n, dst);
     };
-    struct TOff { size_t w, b, bn[2]; };
+    // the handle's TDNN blocks in the order of the specs
+    std::vector<LidTdnn*> tdnn{&c->block0};
+    for (LidBlock& bl : c->blocks) {
+        bl.res.assign(c->S - 1, LidTdnn{});
+        tdnn.push_back(&bl.tdnn1);
+        for (LidTdnn& r : bl.res) tdnn.push_back(&r);
+        tdnn.push_back(&bl.tdnn2);
+    }
+    tdnn.push_back(&c->mfa); tdnn.push_back(&c->asp_tdnn);
     const std::vector<LidTdnnSpec> specs = lid_tdnn_specs(c);
-    std::vector<TOff> toff(specs.size());
     for (size_t i = 0; i < specs.size(); ++i) {
         const LidTdnnSpec& s = specs[i];
-        toff[i].w = whole(s.name + ".conv.weight", {s.cout, s.k, s.cin});
-        toff[i].b = whole(s.name + ".conv.bias", {s.cout});
-        bn(s.name + ".norm", s.cout, toff[i].bn);
+        LidTdnn& t = *tdnn[i];
+        t = LidTdnn{nullptr, nullptr, LidBN{}, s.cin, s.cout, s.k, s.dil};
+        whole(s.name + ".conv.weight", {s.cout, s.k, s.cin}, t.w);
+        whole(s.name + ".conv.bias", {s.cout}, t.bias);
+        bn(s.name + ".norm", s.cout, t.bn);
     }
-    size_t se_off[3][4];
     for (int i = 1; i <= 3; ++i) {
         const std::string q = "embedding_model.block" + std::to_string(i) + ".se_block.";
-        se_off[i - 1][0] = whole(q + "conv1.weight", {SE, 1, C}); se_off[i - 1][1] = whole(q + "conv1.bias", {SE});
-        se_off[i - 1][2] = whole(q + "conv2.weight", {C, 1, SE}); se_off[i - 1][3] = whole(q + "conv2.bias", {C});
+        LidBlock& bl = c->blocks[i - 1];
+        whole(q + "conv1.weight", {SE, 1, C}, bl.se_w1); whole(q + "conv1.bias", {SE}, bl.se_b1);
+        whole(q + "conv2.weight", {C, 1, SE}, bl.se_w2); whole(q + "conv2.bias", {C}, bl.se_b2);
     }
-    const size_t o_aw = whole("embedding_model.asp.conv.weight", {3 * C, 1, A}), o_ab = whole("embedding_model.asp.conv.bias", {3 * C});
-    size_t o_abn[2], o_n0[2], o_n1[2];
-    bn("embedding_model.asp_bn", 6 * C, o_abn);
-    const size_t o_fw = whole("embedding_model.fc.weight", {E, 1, 6 * C}), o_fb = whole("embedding_model.fc.bias", {E});
-    bn("classifier.norm", E, o_n0);
-    const size_t o_w1 = whole("classifier.DNN.block_0.linear.w.weight", {Hd, E}), o_b1 = whole("classifier.DNN.block_0.linear.w.bias", {Hd});
-    bn("classifier.DNN.block_0.norm", Hd, o_n1);
-    const size_t o_w2 = whole("classifier.out.w.weight", {N, Hd}), o_b2 = whole("classifier.out.w.bias", {N});
+    whole("embedding_model.asp.conv.weight", {3 * C, 1, A}, c->asp_w); whole("embedding_model.asp.conv.bias", {3 * C}, c->asp_b);
+    bn("embedding_model.asp_bn", 6 * C, c->asp_bn);
+    whole("embedding_model.fc.weight", {E, 1, 6 * C}, c->fc_w); whole("embedding_model.fc.bias", {E}, c->fc_b);
+    bn("classifier.norm", E, c->n0);
+    whole("classifier.DNN.block_0.linear.w.weight", {Hd, E}, c->w1); whole("classifier.DNN.block_0.linear.w.bias", {Hd}, c->b1);
+    bn("classifier.DNN.block_0.norm", Hd, c->n1);
+    whole("classifier.out.w.weight", {N, Hd}, c->w2); whole("classifier.out.w.bias", {N}, c->b2);
     // front end: periodic Hamming window (DSP.swift:25-42), the real DFT as [402][400] (cos rows, then sin rows), HTK filters without
     // normalisation as [n_mels][201] (:76-168), all formed in double
-    const size_t o_win = a.ftake(LID_NFFT), o_dft = a.ftake((size_t)2 * LID_NBIN * LID_NFFT), o_filt = a.ftake((size_t)nm * LID_NBIN);
+    const size_t o_win = a.ftake(LID_NFFT, c->win), o_dft = a.ftake((size_t)2 * LID_NBIN * LID_NFFT, c->dft), o_filt = a.ftake((size_t)nm * LID_NBIN, c->filt);
     const double PI = 3.14159265358979323846;
     for (int n = 0; n < LID_NFFT; ++n) fh[o_win + n] = (float)(0.54 - 0.46 * cos(2.0 * PI * n / LID_NFFT));
     for (int f = 0; f < LID_NBIN; ++f)
@@ -500,7 +505,7 @@ extern "C" mis_status mis_ecapa_lid_finalize(mis_ecapa_lid* c) {
                 fh[o_filt + (size_t)j * LID_NBIN + i] = (float)v;
             }
     }
-    // ---- the workspace, sized once (nothing of the handle has changed up to here: a rejected finalize can be repeated)
+    // ---- the workspace, sized once (no call reads the handle before finalized is set: a rejected finalize can be repeated)
     const size_t rows = (size_t)c->cfg.max_batch * c->Tcap, B = c->cfg.max_batch;
     const size_t per_frame = 2 * LID_NBIN + 2 * nm + 4 * C + 9 * C + A, per_row = 3 * C + 3 * C + C + A + 6 * C + E + 2 * N;
     const size_t total = rows * per_frame + B * per_row + 64 * 32;
@@ -518,25 +523,6 @@ extern "C" mis_status mis_ecapa_lid_finalize(mis_ecapa_lid* c) {
     c->r = take(rows * C); c->q = take(rows * C); c->u = take(rows * C); c->mf = take(rows * 3 * C); c->att = take(rows * A);
     c->sc = take(rows * 3 * C); c->mean = take(B * 3 * C); c->sd = take(B * 3 * C); c->gate = take(B * C); c->rb = take(B * A);
     c->pooled = take(B * 6 * C); c->emb = take(B * E); c->logp = take(B * N); c->top_prob = take(B * N);
-    const float* P = c->farena.p;
-    auto tdnn = [&](size_t i) {
-        return LidTdnn{P + toff[i].w, P + toff[i].b, LidBN{P + toff[i].bn[0], P + toff[i].bn[1]}, specs[i].cin, specs[i].cout, specs[i].k, specs[i].dil};
-    };
-    size_t i = 0;
-    c->block0 = tdnn(i++);
-    for (int bi = 0; bi < 3; ++bi) {
-        LidBlock& bl = c->blocks[bi];
-        bl.tdnn1 = tdnn(i++);
-        bl.res.clear();
-        for (int j = 0; j < c->S - 1; ++j) bl.res.push_back(tdnn(i++));
-        bl.tdnn2 = tdnn(i++);
-        bl.se_w1 = P + se_off[bi][0]; bl.se_b1 = P + se_off[bi][1]; bl.se_w2 = P + se_off[bi][2]; bl.se_b2 = P + se_off[bi][3];
-    }
-    c->mfa = tdnn(i++);
-    c->asp_tdnn = tdnn(i++);
-    c->asp_w = P + o_aw; c->asp_b = P + o_ab; c->asp_bn = LidBN{P + o_abn[0], P + o_abn[1]}; c->fc_w = P + o_fw; c->fc_b = P + o_fb;
-    c->n0 = LidBN{P + o_n0[0], P + o_n0[1]}; c->w1 = P + o_w1; c->b1 = P + o_b1; c->n1 = LidBN{P + o_n1[0], P + o_n1[1]};
-    c->w2 = P + o_w2; c->b2 = P + o_b2; c->win = P + o_win; c->dft = P + o_dft; c->filt = P + o_filt;
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

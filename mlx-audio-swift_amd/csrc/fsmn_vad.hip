@@ -27,6 +27,7 @@
 #include "audio_front.h"
 #include "f32_tile.h"
 #include "host_weights.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -270,7 +271,7 @@ struct mis_fsmn_vad {
     FvGeom last{};                                          // the last chunk of the last call (tap)
     int last_batch = 0, last_launches = 0;
     bool last_front = false;
-    std::vector<hipEvent_t> ev;
+    HipEvents<3 * FV_TIMED_CHUNKS> ev;
     float ms_front = 0.0f, ms_model = 0.0f;
 };
 
@@ -313,8 +314,6 @@ extern "C" mis_status mis_fsmn_vad_create(const mis_fsmn_vad_config* cfg, int de
     c->Ao = cfg->output_affine_dim; c->O = cfg->output_dim; c->nm = cfg->n_mels; c->wlen = (int)wlen; c->hop = (int)hop;
     c->m = cfg->lfr_m; c->n = cfg->lfr_n; c->lp = (cfg->lfr_m - 1) / 2; c->halo = cfg->fsmn_layers * (cfg->lorder - 1);
     c->Rc = cfg->chunk_frames + c->halo; c->Fc = c->Rc * c->n + c->m; c->Sc = (int64_t)c->Fc * c->hop + c->wlen;
-    c->ev.resize(3 * FV_TIMED_CHUNKS, nullptr);
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -323,7 +322,6 @@ extern "C" void mis_fsmn_vad_destroy(mis_fsmn_vad* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -332,9 +330,7 @@ extern "C" void mis_fsmn_vad_destroy(mis_fsmn_vad* c) {
 // [proj, lorder, 1], fsmn.N.affine.{weight,bias}, out_linear{1,2}.{weight,bias}; optional cmvn.shift / cmvn.scale; host pointers
 extern "C" mis_status mis_fsmn_vad_set_tensor(mis_fsmn_vad* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 3, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
@@ -348,32 +344,31 @@ extern "C" mis_status mis_fsmn_vad_finalize(mis_fsmn_vad* c) {
     const int64_t D = c->D, A = c->A, Ld = c->Ld, P = c->P, L = c->L, Ao = c->Ao, O = c->O, nm = c->nm;
     HostArena a(c->raw);
     std::vector<float>& fh = a.fhost;
-    struct LOff { size_t w, b; bool bias; int cin, cout; };
-    auto lin = [&](const std::string& p, int64_t cout, int64_t cin, bool bias) {
-        LOff o{a.fvec(p + ".weight", {cout, cin}, cout * cin), 0, bias, (int)cin, (int)cout};
-        if (bias) o.b = a.fvec(p + ".bias", {cout}, cout);
-        return o;
+    auto lin = [&](const std::string& p, int64_t cout, int64_t cin, bool bias, FvLin& l) {
+        l = FvLin{nullptr, nullptr, (int)cin, (int)cout};
+        a.fvec(p + ".weight", {cout, cin}, cout * cin, l.w);
+        if (bias) a.fvec(p + ".bias", {cout}, cout, l.b);
     };
-    const LOff o_in1 = lin("in_linear1", A, D, true), o_in2 = lin("in_linear2", Ld, A, true);
-    std::vector<LOff> o_lin, o_aff;
-    std::vector<size_t> o_dw;
+    lin("in_linear1", A, D, true, c->in1); lin("in_linear2", Ld, A, true, c->in2);
+    c->layers.assign(c->NL, FvLayer{});
     for (int i = 0; i < c->NL; ++i) {
         const std::string q = "fsmn." + std::to_string(i);
-        o_lin.push_back(lin(q + ".linear", P, Ld, false));
-        o_dw.push_back(a.fvec(q + ".fsmn_block.conv_left.weight", {P, L, 1}, P * L));
-        o_aff.push_back(lin(q + ".affine", Ld, P, true));
+        lin(q + ".linear", P, Ld, false, c->layers[i].linear);
+        a.fvec(q + ".fsmn_block.conv_left.weight", {P, L, 1}, P * L, c->layers[i].dw);
+        lin(q + ".affine", Ld, P, true, c->layers[i].affine);
     }
-    const LOff o_out1 = lin("out_linear1", Ao, Ld, true), o_out2 = lin("out_linear2", O, Ao, true);
+    lin("out_linear1", Ao, Ld, true, c->out1); lin("out_linear2", O, Ao, true, c->out2);
     // CMVN: applied only when both tensors have the feature width (FSMNVAD.swift:736)
     const HostTensor *sh = c->raw.find("cmvn.shift"), *sc = c->raw.find("cmvn.scale");
     const bool cmvn = sh && sc && (int64_t)sh->v.size() == D && (int64_t)sc->v.size() == D;
-    size_t o_shift = 0, o_scale = 0;
+    c->shift = c->scale = nullptr;
     if (cmvn) {
-        o_shift = a.ftake(D); o_scale = a.ftake(D);
+        const size_t o_shift = a.ftake(D, c->shift), o_scale = a.ftake(D, c->scale);
         for (int64_t i = 0; i < D; ++i) { fh[o_shift + i] = sh->v[i]; fh[o_scale + i] = sc->v[i]; }
     }
     // front end: symmetric Hamming window, twiddles, and the filters in the reference's own f32 arithmetic (:923-955), [bin][mel]
-    const size_t o_win = a.ftake(c->wlen), o_twc = a.ftake(FV_NFFT / 2), o_tws = a.ftake(FV_NFFT / 2), o_fb = a.ftake((size_t)FV_BINS * nm);
+    const size_t o_win = a.ftake(c->wlen, c->win), o_twc = a.ftake(FV_NFFT / 2, c->twc), o_tws = a.ftake(FV_NFFT / 2, c->tws),
+                 o_fb = a.ftake((size_t)FV_BINS * nm, c->fb);
     const double PI = 3.14159265358979323846;
     for (int i = 0; i < c->wlen; ++i) fh[o_win + i] = (float)(0.54 - 0.46 * cos(2.0 * PI * i / (double)(c->wlen - 1)));
     fft512_twiddles(&fh[o_twc], &fh[o_tws]);
@@ -393,7 +388,7 @@ extern "C" mis_status mis_fsmn_vad_finalize(mis_fsmn_vad* c) {
     }
     const size_t o_sil = round_up(2 * nm, 64);
     for (int i = 0; i < c->cfg.n_sil; ++i) ih[o_sil + i] = c->cfg.sil_pdf_ids[i];
-    // ---- the workspace, sized once (nothing of the handle has changed up to here: a rejected finalize can be repeated)
+    // ---- the workspace, sized once (no call reads the handle before finalized is set: a rejected finalize can be repeated)
     const size_t B = c->cfg.max_batch, rows = B * (size_t)c->Rc, frames = B * (size_t)c->Fc;
     const size_t per_row = D + A + Ld + (size_t)c->NL * (P + Ld) + Ao + O + 1;
     const size_t total = frames * (nm + 1) + rows * per_row + 64 * 32;
@@ -413,14 +408,7 @@ extern "C" mis_status mis_fsmn_vad_finalize(mis_fsmn_vad* c) {
     c->pbuf.clear(); c->hbuf.clear();
     for (int i = 0; i < c->NL; ++i) { c->pbuf.push_back(take(rows * P)); c->hbuf.push_back(take(rows * Ld)); }
     c->ao = take(rows * Ao); c->scores = take(rows * O); c->sil = take(rows);
-    const float* Pw = c->farena.p;
-    auto mk = [&](const LOff& o) { return FvLin{Pw + o.w, o.bias ? Pw + o.b : nullptr, o.cin, o.cout}; };
-    c->in1 = mk(o_in1); c->in2 = mk(o_in2); c->out1 = mk(o_out1); c->out2 = mk(o_out2);
-    c->layers.clear();
-    for (int i = 0; i < c->NL; ++i) c->layers.push_back(FvLayer{mk(o_lin[i]), mk(o_aff[i]), Pw + o_dw[i]});
     c->has_cmvn = cmvn;
-    c->shift = cmvn ? Pw + o_shift : nullptr; c->scale = cmvn ? Pw + o_scale : nullptr;
-    c->win = Pw + o_win; c->twc = Pw + o_twc; c->tws = Pw + o_tws; c->fb = Pw + o_fb;
     c->fbr = c->iarena.p; c->sil_ids = c->iarena.p + o_sil;
     c->raw.clear();
     c->finalized = true;

@@ -1,6 +1,7 @@
 // host_weights.h - a model's checkpoint tensors between set_tensor and finalize, widened to f32 on the host (HostWeights), and the
-// weight arenas that finalize assembles from them and uploads once: bf16 + f32 for the LM-shaped models (HostArena), exact f32 with
-// the codec re-layouts for the codec engines (F32Arena, lin_t / conv_taps_t / convt_phases_t / fold_tables_into).
+// weight arenas that finalize assembles from them and uploads once: bf16 + f32 for the LM-shaped and the small audio models (HostArena:
+// one pass, every take bound to the pointer that will address it; fold_bn_dwconv), exact f32 with the codec re-layouts for the codec
+// engines (F32Arena, lin_t / conv_taps_t / convt_phases_t / fold_tables_into).  set_tensor_check is the preamble of every set_tensor.
 #pragma once
 #include "common.h"
 
@@ -71,6 +72,14 @@ private:
     std::map<std::string, HostTensor> map_;
 };
 
+// what every engine's set_tensor asks before it stores a tensor: arguments, not finalized yet, a dtype put() can widen
+static inline void set_tensor_check(const void* handle, const char* name, const void* data, const int64_t* shape, int ndim, int max_ndim, bool finalized,
+                                    mis_dtype dtype) {
+    MIS_REQUIRE(handle && name && data && shape && ndim >= 1 && ndim <= max_ndim, MIS_ERR_INVALID_INPUT, "bad argument");
+    MIS_REQUIRE(!finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+}
+
 // mis-synth-v1 tensors (oracle/synth.py) for init_synthetic: every put takes the next key, value i is plus + synth(key, i, amp)
 struct SynthWeights {
     HostWeights& w;
@@ -91,13 +100,26 @@ struct SynthWeights {
     void norm(const std::string& p, int64_t n) { put(p + ".weight", {n}, 0.1, 1.0f); put(p + ".bias", {n}, 0.05, 0.0f); }
 };
 
-// The bf16 arena and the f32 arena of a model, assembled on the host: an f32 checkpoint is rounded to bf16 once, here.  Offsets count
-// elements and are multiples of 64; what nobody writes stays zero.  A model's own packers write through `host` / `fhost`.
+// The bf16 arena and the f32 arena of a model, assembled on the host in ONE pass: an f32 checkpoint is rounded to bf16 once, here.
+// Offsets count elements and are multiples of 64; what nobody writes stays zero.  A model's own packers write through `host` / `fhost`.
+//
+// Every take can name the pointer that will address it on the device (bf16_t*&, float*& or const float*&): the arena keeps (address
+// of the pointer, offset) and resolve() - which upload() calls once the device buffers exist - writes base + offset into each.  THE
+// RULE: a destination stays at its address until upload() returns.  Size the vectors of layer structs before the loop that binds into
+// them; members of the handle and locals of finalize are fine.  An offset may be bound more than once (tied weights); a pointer nobody
+// binds keeps its value (nullptr: an absent bias).
 struct HostArena {
     const HostWeights& w;
     std::vector<bf16_t> host;
     std::vector<float> fhost;
     explicit HostArena(const HostWeights& weights) : w(weights) {}
+    HostArena(const HostArena&) = delete;
+    HostArena& operator=(const HostArena&) = delete;
+
+    // offsets a model's own packers filled
+    void bind(bf16_t*& dst, size_t off) { binds_.push_back({&dst, off, BF16}); }
+    void bind(float*& dst, size_t off) { binds_.push_back({&dst, off, F32}); }
+    void bind(const float*& dst, size_t off) { binds_.push_back({&dst, off, CF32}); }
 
     size_t btake(size_t n) { size_t off = host.size(); host.resize(off + round_up(n, 64), 0); return off; }
     size_t ftake(size_t n) { size_t off = fhost.size(); fhost.resize(off + round_up(n, 64), 0.0f); return off; }
@@ -119,13 +141,46 @@ struct HostArena {
         for (int64_t i = 0; i < n; ++i) fhost[off + i] = t.v[i];
         return off;
     }
+    // the same takes, bound to their destination
+    size_t btake(size_t n, bf16_t*& dst) { return bound(dst, btake(n)); }
+    size_t bmat(const std::string& name, int64_t N, int64_t K, bf16_t*& dst) { return bound(dst, bmat(name, N, K)); }
+    size_t bvec(const std::string& name, int64_t n, bf16_t*& dst) { return bound(dst, bvec(name, n)); }
+    template <class F> size_t ftake(size_t n, F*& dst) { return bound(dst, ftake(n)); }
+    template <class F> size_t fvec(const std::string& name, std::initializer_list<int64_t> shape, int64_t n, F*& dst) { return bound(dst, fvec(name, shape, n)); }
+
+    // host only: every bound pointer = its arena's base + its offset
+    void resolve(bf16_t* A, float* F) const {
+        for (const Bind& b : binds_) {
+            if (b.kind == BF16) *static_cast<bf16_t**>(b.dst) = A + b.off;
+            else if (b.kind == F32) *static_cast<float**>(b.dst) = F + b.off;
+            else *static_cast<const float**>(b.dst) = F + b.off;
+        }
+    }
     void upload(DevBuf<bf16_t>& arena, DevBuf<float>& farena) const {
         arena.alloc(host.size());
         farena.alloc(fhost.size());
         HIP_CHECK(hipMemcpy(arena.p, host.data(), host.size() * 2, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(farena.p, fhost.data(), fhost.size() * 4, hipMemcpyHostToDevice));
+        resolve(arena.p, farena.p);
     }
+
+private:
+    enum Kind { BF16, F32, CF32 };
+    struct Bind { void* dst; size_t off; Kind kind; };
+    std::vector<Bind> binds_;
+    template <class T> size_t bound(T*& dst, size_t off) { bind(dst, off); return off; }
 };
+
+// Inference BatchNorm (eps 1e-5, the MLXNN default) folded into depthwise taps dw [d][k] (+ bias [d], or null) in f32:
+// taps_out [k][d] = dw scale, shift_out [d] = (bias - mean) scale + bn_b, scale = bn_w / sqrt(var + eps).  Both Conformer engines.
+static inline void fold_bn_dwconv(float* taps_out, float* shift_out, const float* dw, const float* dw_bias, const float* bn_w, const float* bn_b,
+                                  const float* mean, const float* var, int64_t d, int64_t k) {
+    for (int64_t ch = 0; ch < d; ++ch) {
+        const float scale = bn_w[ch] / sqrtf(var[ch] + 1e-5f);
+        for (int64_t j = 0; j < k; ++j) taps_out[j * d + ch] = dw[ch * k + j] * scale;
+        shift_out[ch] = ((dw_bias ? dw_bias[ch] : 0.0f) - mean[ch]) * scale + bn_b[ch];
+    }
+}
 
 // ---------------------------------------------------------------------------- exact-f32 codec arenas
 // Re-layouts of checkpoint weights into the A^T operands of launch_gemm (codec_kernels.h); plain index arithmetic, no rounding.

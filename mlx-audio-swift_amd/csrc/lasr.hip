@@ -15,8 +15,8 @@
 // behind it, one rounding per kernel output; f32 logits; f32 statistics in every LayerNorm; f32 RoPE tables (the reference casts them to
 // the activations' dtype); the depthwise conv with the BatchNorm folded into its taps accumulates in f32.
 //
-//   k_lasr_stft_mel    pre-emphasis, 512-point FFT of one frame in LDS, power, slaney mel, log
-//   k_lasr_norm        per-row per-bin mean / unbiased variance in two passes over the row's own frames, fixed summation order
+//   k_nemo_log_mel     pre-emphasis, 512-point FFT of one frame in LDS, power, slaney mel, log      (audio_front.h: the front end
+//   k_nemo_norm        per-row per-bin mean / unbiased variance in two passes over the row's own frames   shared with sortformer.hip)
 //   k_lasr_pack        f32 features -> the bf16 rows dense_0 multiplies (K padded to 32, zero rows behind F[b])
 //   k_lasr_im2col      k_s-tap strided patches with per-row valid counts
 //   k_lasr_gemm        C = X W^T on v_mfma_f32_16x16x32_bf16, 128 x 128 or 64 x 64 tiles; epilogues bias / ReLU / SiLU / a R + b acc / f32
@@ -26,8 +26,10 @@
 //   k_lasr_glu_dwconv  GLU -> zero-padded depthwise conv (<= 64 taps) -> folded BatchNorm -> activation, a time tile + halo in LDS
 //   k_lasr_argmax      per-frame arg-max (lowest index on ties);  k_lasr_collapse  CTC collapse + compaction per row
 #include "common.h"
+#define AUDIO_FRONT_NEMO_KERNELS
 #include "audio_front.h"
 #include "host_weights.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -36,10 +38,6 @@
 #define LS_HD 64                 // head size
 #define LS_MAX_BATCH 64
 #define LS_MAX_SECONDS 120
-#define LS_NFFT 512
-#define LS_HOP 160
-#define LS_WIN 400
-#define LS_BINS 257
 #define LS_DW_TT 64              // depthwise conv: output frames per block
 #define LS_DW_MAXK 64
 
@@ -76,12 +74,12 @@ struct mis_lasr {
     // state of the last call
     int batch = 0, Fp = 0, T1p = 0, T2p = 0, launches = 0;
     std::vector<int> hN, hF, hT1, hT2;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    HipEvents<4> ev;
     bool timed = false;
 };
 
 // ---------------------------------------------------------------------------- frame counts
-static inline int ls_frames(int64_t n) { return (int)(1 + n / LS_HOP); }
+static inline int ls_frames(int64_t n) { return (int)(1 + n / NEMO_HOP); }
 static inline int ls_conv_out(int t, int k, int s) { return t >= k ? (t - k) / s + 1 : 0; }
 
 extern "C" mis_status mis_lasr_frames(const mis_lasr* c, const int64_t* lens, int batch, int32_t* F_out, int32_t* T2_out) {
@@ -124,13 +122,12 @@ extern "C" mis_status mis_lasr_create(const mis_lasr_config* cfg, int device, mi
     MIS_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= LS_MAX_BATCH, MIS_ERR_INVALID_INPUT, "max_batch %d outside 1..%d", cfg->max_batch, LS_MAX_BATCH);
     MIS_REQUIRE(cfg->max_seconds >= 1 && cfg->max_seconds <= LS_MAX_SECONDS, MIS_ERR_INVALID_INPUT, "max_seconds %d outside 1..%d", cfg->max_seconds,
                 LS_MAX_SECONDS);
+    hipStream_t stream = mis_open_stream(device);      // first: the handle's events belong to this device
     auto c = std::make_unique<mis_lasr>();
-    c->stream = mis_open_stream(device);
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->d = d; c->f = cfg->intermediate_size; c->V = cfg->vocab_size; c->H = H; c->Hk = Hk; c->L = cfg->num_hidden_layers;
     c->mels = cfg->num_mel_bins; c->Kp = (int)round_up(c->mels, 32); c->cc = cfg->subsampling_conv_channels;
     c->ks = cfg->subsampling_conv_kernel_size; c->st = cfg->subsampling_conv_stride; c->ck = cfg->conv_kernel_size;
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -139,22 +136,15 @@ extern "C" void mis_lasr_destroy(mis_lasr* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
 extern "C" mis_status mis_lasr_set_tensor(mis_lasr* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 3, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
-
-// slaney mel scale (DSP.swift melFilters, melScale .slaney)
-static double ls_hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + log(f / 1000.0) / (log(6.4) / 27.0); }
-static double ls_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
 
 extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
     MIS_API_BEGIN
@@ -167,33 +157,17 @@ extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
     std::vector<float>& fhost = a.fhost;
     const std::string E = "encoder.", S = "encoder.subsampler.";
     // ---- front end tables (f32): window 400 -> 512, FFT twiddles, slaney filters [257][mels] and each filter's bin range
-    const size_t o_win = a.ftake(LS_NFFT), o_twc = a.ftake(LS_NFFT / 2), o_tws = a.ftake(LS_NFFT / 2);
-    for (int n = 0; n < LS_WIN; ++n)
-        fhost[o_win + (LS_NFFT - LS_WIN) / 2 + n] = 0.5f * (1.0f - (float)cos(2.0 * M_PI * (double)n / (double)(LS_WIN - 1)));
+    const size_t o_win = a.ftake(NEMO_NFFT, c->window), o_twc = a.ftake(NEMO_NFFT / 2, c->tw_cos), o_tws = a.ftake(NEMO_NFFT / 2, c->tw_sin);
+    hann_padded(&fhost[o_win], NEMO_WIN, NEMO_NFFT);
     fft512_twiddles(&fhost[o_twc], &fhost[o_tws]);
-    const size_t o_fb = a.ftake((size_t)LS_BINS * mels);
+    const size_t o_fb = a.ftake((size_t)NEMO_BINS * mels, c->fb);
     std::vector<int> ranges(2 * mels, 0);
-    {
-        const double mmax = ls_hz_to_mel(8000.0);
-        std::vector<double> fp(mels + 2);
-        for (int i = 0; i < mels + 2; ++i) fp[i] = ls_mel_to_hz((double)i * mmax / (double)(mels + 1));
-        for (int j = 0; j < mels; ++j) {
-            const double lo = fp[j], ce = fp[j + 1], hi = fp[j + 2], enorm = 2.0 / (hi - lo);
-            for (int i = 0; i < LS_BINS; ++i) {
-                const double fr = (double)i * 16000.0 / LS_NFFT;
-                double w = 0.0;
-                if (fr >= lo && fr < ce) w = (fr - lo) / (ce - lo);
-                else if (fr >= ce && fr <= hi) w = (hi - fr) / (hi - ce);
-                fhost[o_fb + (size_t)i * mels + j] = (float)(w * enorm);
-            }
-        }
-        filter_bin_ranges(&fhost[o_fb], LS_BINS, (int)mels, ranges.data());
-    }
+    slaney_filterbank(&fhost[o_fb], ranges.data(), NEMO_BINS, (int)mels, 16000.0, NEMO_NFFT);
     // ---- workspace extents and the rotary tables [T2cap][32] (LasrRotaryEmbedding, :23-42): f32, angle = pos * theta^(-2i/64)
     c->maxN = (int64_t)c->cfg.max_seconds * 16000;
     c->Fcap = ls_frames(c->maxN); c->T1cap = ls_conv_out(c->Fcap, c->ks, c->st); c->T2cap = ls_conv_out(c->T1cap, c->ks, c->st);
     MIS_REQUIRE(c->T2cap >= 1, MIS_ERR_INVALID_INPUT, "max_seconds %d gives no encoder frame", c->cfg.max_seconds);
-    const size_t o_rc = a.ftake((size_t)c->T2cap * 32), o_rs = a.ftake((size_t)c->T2cap * 32);
+    const size_t o_rc = a.ftake((size_t)c->T2cap * 32, c->rope_cos), o_rs = a.ftake((size_t)c->T2cap * 32, c->rope_sin);
     for (int i = 0; i < 32; ++i) {
         const float inv = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / (float)LS_HD);
         for (int p = 0; p < c->T2cap; ++p) {
@@ -204,93 +178,69 @@ extern "C" mis_status mis_lasr_finalize(mis_lasr* c) {
     }
     // ---- stem.  dense_0 [d][mels] -> [d][Kp] (zero columns); conv weights [O][k][I] are already the patch order k * I + i
     const HostTensor& w0 = c->raw.need(S + "dense_0.weight", {d, mels});
-    const size_t o_d0w = a.btake((size_t)d * Kp);
+    const size_t o_d0w = a.btake((size_t)d * Kp, c->d0w);
     for (int64_t n = 0; n < d; ++n) for (int64_t k = 0; k < mels; ++k) host[o_d0w + n * Kp + k] = f32_to_bf16(w0.v[n * mels + k]);
-    const size_t o_d0b = a.bvec(S + "dense_0.bias", d);
-    auto conv3 = [&](const std::string& name, int64_t O, int64_t K, int64_t I) {
+    a.bvec(S + "dense_0.bias", d, c->d0b);
+    auto conv3 = [&](const std::string& name, int64_t O, int64_t K, int64_t I, bf16_t*& dst) {
         const HostTensor& t = c->raw.need(name, {O, K, I});
-        const size_t off = a.btake((size_t)O * K * I);
+        const size_t off = a.btake((size_t)O * K * I, dst);
         for (size_t i = 0; i < (size_t)O * K * I; ++i) host[off + i] = f32_to_bf16(t.v[i]);
-        return off;
     };
-    const size_t o_c0w = conv3(S + "conv_0.weight", d, ks, d), o_c0b = a.bvec(S + "conv_0.bias", d);
-    const size_t o_c1w = conv3(S + "conv_1.weight", cc, ks, d), o_c1b = a.bvec(S + "conv_1.bias", cc);
-    const size_t o_d1w = a.bmat(S + "dense_1.weight", d, cc), o_d1b = a.bvec(S + "dense_1.bias", d);
+    conv3(S + "conv_0.weight", d, ks, d, c->c0w); a.bvec(S + "conv_0.bias", d, c->c0b);
+    conv3(S + "conv_1.weight", cc, ks, d, c->c1w); a.bvec(S + "conv_1.bias", cc, c->c1b);
+    a.bmat(S + "dense_1.weight", d, cc, c->d1w); a.bvec(S + "dense_1.bias", d, c->d1b);
     // ---- blocks.  A LayerNorm bias the checkpoint does not carry is zero, the value the reference's LayerNorm is created with (the
-    // published checkpoints have weight-only LayerNorms and the reference loads them with noUnusedKeys, :401)
-    auto ln_bias = [&](const std::string& name) { return c->raw.find(name) ? a.bvec(name, d) : a.btake(d); };
-    struct Off { size_t v[28]; size_t dw, sh; };
-    std::vector<Off> lo(c->L);
-    const size_t npos = (size_t)-1;
+    // published checkpoints have weight-only LayerNorms and the reference loads them with noUnusedKeys, :401).  A linear or conv bias
+    // the configuration turns off stays nullptr.
+    auto ln_bias = [&](const std::string& name, bf16_t*& dst) { if (c->raw.find(name)) a.bvec(name, d, dst); else a.btake(d, dst); };
     const int64_t NQ = (int64_t)(c->H + 2 * c->Hk) * LS_HD;
+    c->layers.assign(c->L, LsLayer{});
     for (int li = 0; li < c->L; ++li) {
         const std::string q = E + "layers." + std::to_string(li) + ".";
-        Off& o = lo[li];
-        auto norm = [&](const std::string& n, int i) { o.v[i] = a.bvec(q + n + ".weight", d); o.v[i + 1] = ln_bias(q + n + ".bias"); };
-        auto ffn = [&](const std::string& n, int i) {
-            o.v[i] = a.bmat(q + n + ".linear1.weight", f, d); o.v[i + 1] = ab ? a.bvec(q + n + ".linear1.bias", f) : npos;
-            o.v[i + 2] = a.bmat(q + n + ".linear2.weight", d, f); o.v[i + 3] = ab ? a.bvec(q + n + ".linear2.bias", d) : npos;
+        LsLayer& l = c->layers[li];
+        auto norm = [&](const std::string& n, bf16_t*& w, bf16_t*& b) { a.bvec(q + n + ".weight", d, w); ln_bias(q + n + ".bias", b); };
+        auto ffn = [&](const std::string& n, bf16_t*& w1, bf16_t*& b1, bf16_t*& w2, bf16_t*& b2) {
+            a.bmat(q + n + ".linear1.weight", f, d, w1); if (ab) a.bvec(q + n + ".linear1.bias", f, b1);
+            a.bmat(q + n + ".linear2.weight", d, f, w2); if (ab) a.bvec(q + n + ".linear2.bias", d, b2);
         };
-        norm("norm_feed_forward1", 0); ffn("feed_forward1", 2);
-        norm("norm_self_att", 6);
-        o.v[8] = a.btake((size_t)NQ * d);
-        a.bmat_into(q + "self_attn.q_proj.weight", d, d, o.v[8]);
-        a.bmat_into(q + "self_attn.k_proj.weight", (int64_t)c->Hk * LS_HD, d, o.v[8] + (size_t)d * d);
-        a.bmat_into(q + "self_attn.v_proj.weight", (int64_t)c->Hk * LS_HD, d, o.v[8] + (size_t)(d + c->Hk * LS_HD) * d);
-        o.v[9] = npos;
+        norm("norm_feed_forward1", l.ln_ff1w, l.ln_ff1b); ffn("feed_forward1", l.ff1_w1, l.ff1_b1, l.ff1_w2, l.ff1_b2);
+        norm("norm_self_att", l.ln_attw, l.ln_attb);
+        const size_t o_qkv = a.btake((size_t)NQ * d, l.wqkv);
+        a.bmat_into(q + "self_attn.q_proj.weight", d, d, o_qkv);
+        a.bmat_into(q + "self_attn.k_proj.weight", (int64_t)c->Hk * LS_HD, d, o_qkv + (size_t)d * d);
+        a.bmat_into(q + "self_attn.v_proj.weight", (int64_t)c->Hk * LS_HD, d, o_qkv + (size_t)(d + c->Hk * LS_HD) * d);
         if (ab) {
-            o.v[9] = a.btake(NQ);
+            const size_t o_b = a.btake(NQ, l.bqkv);
             const HostTensor& bq = c->raw.need(q + "self_attn.q_proj.bias", {d});
             const HostTensor& bk = c->raw.need(q + "self_attn.k_proj.bias", {(int64_t)c->Hk * LS_HD});
             const HostTensor& bv = c->raw.need(q + "self_attn.v_proj.bias", {(int64_t)c->Hk * LS_HD});
-            for (int64_t i = 0; i < d; ++i) host[o.v[9] + i] = f32_to_bf16(bq.v[i]);
+            for (int64_t i = 0; i < d; ++i) host[o_b + i] = f32_to_bf16(bq.v[i]);
             for (int64_t i = 0; i < c->Hk * LS_HD; ++i) {
-                host[o.v[9] + d + i] = f32_to_bf16(bk.v[i]);
-                host[o.v[9] + d + c->Hk * LS_HD + i] = f32_to_bf16(bv.v[i]);
+                host[o_b + d + i] = f32_to_bf16(bk.v[i]);
+                host[o_b + d + c->Hk * LS_HD + i] = f32_to_bf16(bv.v[i]);
             }
         }
-        o.v[10] = a.bmat(q + "self_attn.o_proj.weight", d, d); o.v[11] = ab ? a.bvec(q + "self_attn.o_proj.bias", d) : npos;
-        norm("norm_conv", 12);
-        o.v[14] = conv3(q + "conv.pointwise_conv1.weight", 2 * d, 1, d); o.v[15] = cb ? a.bvec(q + "conv.pointwise_conv1.bias", 2 * d) : npos;
-        o.v[16] = conv3(q + "conv.pointwise_conv2.weight", d, 1, d); o.v[17] = cb ? a.bvec(q + "conv.pointwise_conv2.bias", d) : npos;
-        // inference BatchNorm (eps 1e-5, the MLXNN default) folded into the depthwise taps and a shift, in f32
+        a.bmat(q + "self_attn.o_proj.weight", d, d, l.wo); if (ab) a.bvec(q + "self_attn.o_proj.bias", d, l.bo);
+        norm("norm_conv", l.ln_cvw, l.ln_cvb);
+        conv3(q + "conv.pointwise_conv1.weight", 2 * d, 1, d, l.pw1); if (cb) a.bvec(q + "conv.pointwise_conv1.bias", 2 * d, l.pw1b);
+        conv3(q + "conv.pointwise_conv2.weight", d, 1, d, l.pw2); if (cb) a.bvec(q + "conv.pointwise_conv2.bias", d, l.pw2b);
+        // inference BatchNorm folded into the depthwise taps and a shift
         const HostTensor& dw = c->raw.need(q + "conv.depthwise_conv.weight", {d, ck, 1});
         const HostTensor* dwb = cb ? &c->raw.need(q + "conv.depthwise_conv.bias", {d}) : nullptr;
         const HostTensor& bw = c->raw.need(q + "conv.norm.weight", {d}); const HostTensor& bb = c->raw.need(q + "conv.norm.bias", {d});
         const HostTensor& bm = c->raw.need(q + "conv.norm.running_mean", {d}); const HostTensor& bvv = c->raw.need(q + "conv.norm.running_var", {d});
-        o.dw = a.ftake((size_t)ck * d); o.sh = a.ftake(d);
-        for (int64_t ch = 0; ch < d; ++ch) {
-            const float scale = bw.v[ch] / sqrtf(bvv.v[ch] + 1e-5f);
-            for (int64_t k = 0; k < ck; ++k) fhost[o.dw + k * d + ch] = dw.v[ch * ck + k] * scale;
-            fhost[o.sh + ch] = ((dwb ? dwb->v[ch] : 0.0f) - bm.v[ch]) * scale + bb.v[ch];
-        }
-        norm("norm_feed_forward2", 18); ffn("feed_forward2", 20);
-        norm("norm_out", 24);
+        const size_t o_dw = a.ftake((size_t)ck * d, l.dw), o_sh = a.ftake(d, l.dwshift);
+        fold_bn_dwconv(&fhost[o_dw], &fhost[o_sh], dw.v.data(), dwb ? dwb->v.data() : nullptr, bw.v.data(), bb.v.data(), bm.v.data(), bvv.v.data(), d, ck);
+        norm("norm_feed_forward2", l.ln_ff2w, l.ln_ff2b); ffn("feed_forward2", l.ff2_w1, l.ff2_b1, l.ff2_w2, l.ff2_b2);
+        norm("norm_out", l.ln_outw, l.ln_outb);
     }
-    const size_t o_onw = a.bvec(E + "out_norm.weight", d), o_onb = ln_bias(E + "out_norm.bias");
-    const size_t o_hw = a.bmat("ctc_head.weight", V, d), o_hb = a.bvec("ctc_head.bias", V);
-    // ---- upload
+    a.bvec(E + "out_norm.weight", d, c->onw); ln_bias(E + "out_norm.bias", c->onb);
+    a.bmat("ctc_head.weight", V, d, c->headw); a.bvec("ctc_head.bias", V, c->headb);
+    // ---- upload: every pointer bound above now addresses the device arenas
     a.upload(c->arena, c->farena);
-    bf16_t* A = c->arena.p;
-    float* F = c->farena.p;
-    auto P = [&](size_t off) { return off == npos ? (bf16_t*)nullptr : A + off; };
-    c->window = F + o_win; c->tw_cos = F + o_twc; c->tw_sin = F + o_tws; c->fb = F + o_fb; c->rope_cos = F + o_rc; c->rope_sin = F + o_rs;
     c->fbr.alloc(2 * mels);
     HIP_CHECK(hipMemcpy(c->fbr.p, ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
     c->fb_range = c->fbr.p;
-    c->d0w = A + o_d0w; c->d0b = A + o_d0b; c->c0w = A + o_c0w; c->c0b = A + o_c0b; c->c1w = A + o_c1w; c->c1b = A + o_c1b;
-    c->d1w = A + o_d1w; c->d1b = A + o_d1b; c->onw = A + o_onw; c->onb = A + o_onb; c->headw = A + o_hw; c->headb = A + o_hb;
-    c->layers.resize(c->L);
-    for (int li = 0; li < c->L; ++li) {
-        const Off& o = lo[li];
-        LsLayer& l = c->layers[li];
-        l.ln_ff1w = P(o.v[0]); l.ln_ff1b = P(o.v[1]); l.ff1_w1 = P(o.v[2]); l.ff1_b1 = P(o.v[3]); l.ff1_w2 = P(o.v[4]); l.ff1_b2 = P(o.v[5]);
-        l.ln_attw = P(o.v[6]); l.ln_attb = P(o.v[7]); l.wqkv = P(o.v[8]); l.bqkv = P(o.v[9]); l.wo = P(o.v[10]); l.bo = P(o.v[11]);
-        l.ln_cvw = P(o.v[12]); l.ln_cvb = P(o.v[13]); l.pw1 = P(o.v[14]); l.pw1b = P(o.v[15]); l.pw2 = P(o.v[16]); l.pw2b = P(o.v[17]);
-        l.dw = F + o.dw; l.dwshift = F + o.sh;
-        l.ln_ff2w = P(o.v[18]); l.ln_ff2b = P(o.v[19]); l.ff2_w1 = P(o.v[20]); l.ff2_b1 = P(o.v[21]); l.ff2_w2 = P(o.v[22]); l.ff2_b2 = P(o.v[23]);
-        l.ln_outw = P(o.v[24]); l.ln_outb = P(o.v[25]);
-    }
     // ---- the workspace: every buffer a call touches, for max_batch rows of max_seconds
     const size_t B = c->cfg.max_batch, Fc = c->Fcap, T1c = c->T1cap, M = B * c->T2cap;
     c->pcm.alloc(B * c->maxN); c->melraw.alloc(B * Fc * mels); c->feats.alloc(B * Fc * mels); c->logits.alloc(M * V);
@@ -340,72 +290,7 @@ extern "C" mis_status mis_lasr_init_synthetic(mis_lasr* c, uint64_t seed) {
 }
 
 // ============================================================================ front end
-// One frame of one row: samples t 160 - 256 .. + 511 of the zero-centred, pre-emphasised waveform (x[0] kept, y[i] = x[i] - 0.97 x[i-1];
-// skipped for n <= 1), window, 512-point radix-2 FFT in LDS, |.|^2, slaney filters over each filter's own bins, log(. + 2^-24).
-__global__ void __launch_bounds__(256) k_lasr_stft_mel(const float* __restrict__ pcm, int64_t stride, const int* __restrict__ N,
-                                                       const int* __restrict__ F, const float* __restrict__ window,
-                                                       const float* __restrict__ twc, const float* __restrict__ tws,
-                                                       const float* __restrict__ fb, const int* __restrict__ fbr, float* __restrict__ out,
-                                                       int Fp, int mels) {
-    __shared__ float re[LS_NFFT], im[LS_NFFT];
-    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    float* o = out + ((size_t)b * Fp + t) * mels;
-    if (t >= F[b]) { if (tid < mels) o[tid] = 0.0f; return; }
-    const int n = N[b];
-    const float* x = pcm + (size_t)b * stride;
-    for (int j = tid; j < LS_NFFT; j += 256) {
-        const float w = window[j];
-        const int64_t s = (int64_t)t * LS_HOP - LS_NFFT / 2 + j;
-        float v = 0.0f;
-        if (w != 0.0f && s >= 0 && s < n) v = (s == 0 || n <= 1) ? x[s] : __fsub_rn(x[s], __fmul_rn(0.97f, x[s - 1]));
-        const int r = (int)(__brev((unsigned)j) >> 23);
-        re[r] = __fmul_rn(v, w); im[r] = 0.0f;
-    }
-    __syncthreads();
-    for (int half = 1; half < LS_NFFT; half <<= 1) {
-        const int k = tid & (half - 1), i0 = ((tid - k) << 1) + k, i1 = i0 + half, ti = k * (LS_NFFT / 2 / half);
-        const float c = twc[ti], s = tws[ti];
-        const float xr = re[i1], xi = im[i1];
-        const float pr = xr * c - xi * s, pi = xr * s + xi * c;
-        const float ar = re[i0], ai = im[i0];
-        re[i0] = ar + pr; im[i0] = ai + pi; re[i1] = ar - pr; im[i1] = ai - pi;
-        __syncthreads();
-    }
-    for (int j = tid; j < LS_BINS; j += 256) { const float a = re[j], c = im[j]; re[j] = a * a + c * c; }
-    __syncthreads();
-    if (tid < mels) {
-        float acc = 0.0f;
-        for (int i = fbr[2 * tid]; i < fbr[2 * tid + 1]; ++i) acc = fmaf(re[i], fb[(size_t)i * mels + tid], acc);
-        o[tid] = logf(acc + 5.9604644775390625e-08f);
-    }
-}
-
-// per_feature normalisation (ParakeetAudio.swift:47-53): per mel bin, mean and unbiased variance (divisor max(F - 1, 1)) over the row's
-// own F frames in two passes, (x - mean) / (sqrt(var) + 1e-5); zeros behind F[b].  A thread owns one bin and every fourth frame; the
-// four partial sums are added in a fixed order, so a row's statistics depend on nothing but the row.
-__global__ void __launch_bounds__(256) k_lasr_norm(const float* __restrict__ raw, const int* __restrict__ F, float* __restrict__ out, int Fp,
-                                                   int mels) {
-    __shared__ float part[4][64];
-    const int b = blockIdx.y, ml = threadIdx.x & 63, fl = threadIdx.x >> 6, m = blockIdx.x * 64 + ml, n = F[b];
-    const bool live = m < mels;
-    const float* x = raw + (size_t)b * Fp * mels + (live ? m : 0);
-    float s = 0.0f;
-    for (int t = fl; t < n; t += 4) s += x[(size_t)t * mels];
-    part[fl][ml] = s;
-    __syncthreads();
-    const float mean = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)n;
-    __syncthreads();
-    float q = 0.0f;
-    for (int t = fl; t < n; t += 4) { const float v = x[(size_t)t * mels] - mean; q = fmaf(v, v, q); }
-    part[fl][ml] = q;
-    __syncthreads();
-    const float var = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)max(n - 1, 1);
-    const float den = sqrtf(var) + 1e-5f;
-    if (!live) return;
-    float* y = out + (size_t)b * Fp * mels + m;
-    for (int t = fl; t < Fp; t += 4) y[(size_t)t * mels] = t < n ? (x[(size_t)t * mels] - mean) / den : 0.0f;
-}
-
+// k_nemo_log_mel (pre-emphasis 0.97, no scale) and k_nemo_norm of audio_front.h; then
 // f32 features [B][Fp][mels] -> bf16 rows [B Fp][Kp] (the single rounding of the front end), zero behind F[b] and in the padding columns
 __global__ void __launch_bounds__(256) k_lasr_pack(const float* __restrict__ feats, const int* __restrict__ F, bf16_t* __restrict__ out, int Fp,
                                                    int mels, int Kp, size_t total) {
@@ -857,9 +742,9 @@ static void ls_front(mis_lasr* c, const float* pcm, const int64_t* lens, int bat
     const int64_t ws = std::min<int64_t>(stride, c->maxN);
     HIP_CHECK(hipMemcpy2DAsync(c->pcm.p, ws * 4, pcm, stride * 4, ws * 4, batch, hipMemcpyDefault, s));
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[0], s));
-    MIS_LAUNCH(c, k_lasr_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF.p, c->window, c->tw_cos, c->tw_sin, c->fb,
-              c->fb_range, c->melraw.p, Fp, c->mels);
-    MIS_LAUNCH(c, k_lasr_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF.p, c->feats.p, Fp, c->mels);
+    MIS_LAUNCH(c, k_nemo_log_mel<false>, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF.p, nullptr, 0.97f, c->window, c->tw_cos,
+              c->tw_sin, c->fb, c->fb_range, c->melraw.p, Fp, c->mels);
+    MIS_LAUNCH(c, k_nemo_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF.p, c->feats.p, Fp, c->mels, 1);
 }
 
 // c->feats -> stem -> blocks -> out_norm (c->enc_out).  stop: -1 everything, 0 behind the stem, 1 .. L behind that block.

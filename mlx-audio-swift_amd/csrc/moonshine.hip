@@ -132,9 +132,7 @@ static std::string ms_canonical_name(const mis_moonshine* c, const std::string& 
 extern "C" mis_status mis_moonshine_set_tensor(mis_moonshine* c, const char* name_, const void* data, mis_dtype dtype, const int64_t* shape,
                                                int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name_ && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name_, data, shape, ndim, 3, c && c->finalized, dtype);
     const std::string name = ms_canonical_name(c, name_);
     if (name.empty()) return MIS_OK;
     c->raw.put(name, data, dtype, shape, ndim);
@@ -161,127 +159,90 @@ extern "C" mis_status mis_moonshine_finalize(mis_moonshine* c) {
         for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j) host[off + row0 + h * MS_DP + j] = f32_to_bf16(t.v[h * hd + j]);
     };
     // o_proj [d][H hd] -> [d][H 64]
-    auto pad_cols = [&](const std::string& name, int H, int hd) {
+    auto pad_cols = [&](const std::string& name, int H, int hd, bf16_t*& dst) {
         const HostTensor& t = c->raw.need(name, {d, (int64_t)H * hd});
-        size_t off = a.btake((size_t)d * H * MS_DP);
+        size_t off = a.btake((size_t)d * H * MS_DP, dst);
         for (int64_t n = 0; n < d; ++n) for (int h = 0; h < H; ++h) for (int j = 0; j < hd; ++j)
             host[off + (size_t)n * H * MS_DP + h * MS_DP + j] = f32_to_bf16(t.v[(size_t)n * H * hd + h * hd + j]);
-        return off;
     };
     // conv weight [out][in][k] (published layout) -> [out][k in] (the order of a contiguous span of k frames)
-    auto conv_w = [&](const std::string& name, int64_t O, int64_t I, int64_t K) {
+    auto conv_w = [&](const std::string& name, int64_t O, int64_t I, int64_t K, bf16_t*& dst) {
         const HostTensor& t = c->raw.need(name, {O, I, K});
-        size_t off = a.btake((size_t)O * I * K);
+        size_t off = a.btake((size_t)O * I * K, dst);
         for (int64_t o = 0; o < O; ++o) for (int64_t k = 0; k < K; ++k) for (int64_t i = 0; i < I; ++i)
             host[off + ((size_t)o * K + k) * I + i] = f32_to_bf16(t.v[((size_t)o * I + i) * K + k]);
-        return off;
     };
     const std::string E = "encoder", D = "decoder";
     // ---- stem (f32 through GroupNorm)
     const HostTensor& w1 = c->raw.need(E + ".conv1.weight", {d, 1, 127});
-    const size_t o_c1 = a.ftake((size_t)127 * d);
+    const size_t o_c1 = a.ftake((size_t)127 * d, c->conv1wT);
     for (int64_t ch = 0; ch < d; ++ch) for (int k = 0; k < 127; ++k) fhost[o_c1 + (size_t)k * d + ch] = w1.v[(size_t)ch * 127 + k];
-    const size_t o_gw = a.ftake(d), o_gb = a.ftake(d);
+    const size_t o_gw = a.ftake(d, c->gn_w), o_gb = a.ftake(d, c->gn_b);
     { const HostTensor& gw = c->raw.need(E + ".groupnorm.weight", {d}); const HostTensor& gb = c->raw.need(E + ".groupnorm.bias", {d});
       for (int64_t i = 0; i < d; ++i) { fhost[o_gw + i] = gw.v[i]; fhost[o_gb + i] = gb.v[i]; } }
     // rotary tables [MS_MAX_POS][rot / 2] (MoonshineRotaryEmbedding, :88-110)
-    auto rope_tab = [&](int rot, size_t* oc, size_t* os) {
-        *oc = a.ftake((size_t)MS_MAX_POS * (rot / 2)); *os = a.ftake((size_t)MS_MAX_POS * (rot / 2));
+    auto rope_tab = [&](int rot, float*& cos_t, float*& sin_t) {
+        const size_t oc = a.ftake((size_t)MS_MAX_POS * (rot / 2), cos_t), os = a.ftake((size_t)MS_MAX_POS * (rot / 2), sin_t);
         for (int i = 0; i < rot / 2; ++i) {
             const float inv = 1.0f / powf(c->cfg.rope_theta, (float)(2 * i) / (float)rot);
             for (int p = 0; p < MS_MAX_POS; ++p) {
                 const float a = (float)p * inv;
-                fhost[*oc + (size_t)p * (rot / 2) + i] = (float)cos((double)a);
-                fhost[*os + (size_t)p * (rot / 2) + i] = (float)sin((double)a);
+                fhost[oc + (size_t)p * (rot / 2) + i] = (float)cos((double)a);
+                fhost[os + (size_t)p * (rot / 2) + i] = (float)sin((double)a);
             }
         }
     };
-    size_t o_ce, o_se, o_cd, o_sd;
-    rope_tab(c->rote, &o_ce, &o_se);
-    rope_tab(c->rotd, &o_cd, &o_sd);
-    const size_t o_zero = a.btake(std::max<int64_t>(d, 64));
-    const size_t o_c2w = conv_w(E + ".conv2.weight", 2 * d, d, 7), o_c2b = a.bvec(E + ".conv2.bias", 2 * d);
-    const size_t o_c3w = conv_w(E + ".conv3.weight", d, 2 * d, 3), o_c3b = a.bvec(E + ".conv3.bias", d);
+    rope_tab(c->rote, c->cos_e, c->sin_e);
+    rope_tab(c->rotd, c->cos_d, c->sin_d);
+    a.btake(std::max<int64_t>(d, 64), c->zeros);
+    conv_w(E + ".conv2.weight", 2 * d, d, 7, c->conv2w); a.bvec(E + ".conv2.bias", 2 * d, c->conv2b);
+    conv_w(E + ".conv3.weight", d, 2 * d, 3, c->conv3w); a.bvec(E + ".conv3.bias", d, c->conv3b);
+    // fused q | k | v rows and their bias.  The bias buffer is taken whether or not the checkpoint has one (the arena's layout does
+    // not depend on attention_bias); without one it stays zero and unbound: the pointer is nullptr
+    auto qkv = [&](const std::string& p, const char* const* names, const int* heads, int n, int hd, bf16_t*& w, bf16_t*& b) {
+        int64_t rows = 0;
+        for (int i = 0; i < n; ++i) rows += (int64_t)heads[i] * MS_DP;
+        const size_t ow = a.btake((size_t)rows * d, w), ob = ab ? a.btake(rows, b) : a.btake(rows);
+        int64_t row0 = 0;
+        for (int i = 0; i < n; row0 += (int64_t)heads[i++] * MS_DP) pad_rows(p + names[i] + ".weight", heads[i], hd, ow, row0);
+        row0 = 0;
+        for (int i = 0; ab && i < n; row0 += (int64_t)heads[i++] * MS_DP) pad_bias(p + names[i] + ".bias", heads[i], hd, ob, row0);
+    };
+    static const char* const QKV[3] = {".q_proj", ".k_proj", ".v_proj"};
     // ---- encoder layers
-    struct Off { size_t v[15]; };
-    std::vector<Off> eo(c->cfg.encoder_num_hidden_layers), dof(c->cfg.decoder_num_hidden_layers);
-    const int64_t NQe = (int64_t)(c->He + 2 * c->Hke) * MS_DP;
-    for (size_t li = 0; li < eo.size(); ++li) {
+    c->enc.assign(c->cfg.encoder_num_hidden_layers, MsEncLayer{});
+    for (size_t li = 0; li < c->enc.size(); ++li) {
         const std::string q = E + ".layers." + std::to_string(li);
-        Off& o = eo[li];
-        o.v[0] = a.bvec(q + ".input_layernorm.weight", d); o.v[1] = a.bvec(q + ".post_attention_layernorm.weight", d);
-        o.v[2] = a.btake((size_t)NQe * d);
-        pad_rows(q + ".self_attn.q_proj.weight", c->He, c->hde, o.v[2], 0);
-        pad_rows(q + ".self_attn.k_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)c->He * MS_DP);
-        pad_rows(q + ".self_attn.v_proj.weight", c->Hke, c->hde, o.v[2], (int64_t)(c->He + c->Hke) * MS_DP);
-        o.v[3] = a.btake(NQe);
-        if (ab) {
-            pad_bias(q + ".self_attn.q_proj.bias", c->He, c->hde, o.v[3], 0);
-            pad_bias(q + ".self_attn.k_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)c->He * MS_DP);
-            pad_bias(q + ".self_attn.v_proj.bias", c->Hke, c->hde, o.v[3], (int64_t)(c->He + c->Hke) * MS_DP);
-        }
-        o.v[4] = pad_cols(q + ".self_attn.o_proj.weight", c->He, c->hde);
-        o.v[5] = a.bmat(q + ".mlp.fc1.weight", f, d); o.v[6] = a.bvec(q + ".mlp.fc1.bias", f);
-        o.v[7] = a.bmat(q + ".mlp.fc2.weight", d, f); o.v[8] = a.bvec(q + ".mlp.fc2.bias", d);
+        MsEncLayer& l = c->enc[li];
+        a.bvec(q + ".input_layernorm.weight", d, l.ln1); a.bvec(q + ".post_attention_layernorm.weight", d, l.ln2);
+        const int he[3] = {c->He, c->Hke, c->Hke};
+        qkv(q + ".self_attn", QKV, he, 3, c->hde, l.wqkv, l.bqkv);
+        pad_cols(q + ".self_attn.o_proj.weight", c->He, c->hde, l.wo);
+        a.bmat(q + ".mlp.fc1.weight", f, d, l.fc1); a.bvec(q + ".mlp.fc1.bias", f, l.b1);
+        a.bmat(q + ".mlp.fc2.weight", d, f, l.fc2); a.bvec(q + ".mlp.fc2.bias", d, l.b2);
     }
-    const size_t o_eln = a.bvec(E + ".layer_norm.weight", d);
-    // ---- decoder
-    const size_t o_emb = a.bmat(D + ".embed_tokens.weight", V, d);
-    const size_t o_proj = c->cfg.tie_word_embeddings ? o_emb : a.bmat("proj_out.weight", V, d);
-    const int64_t NQd = (int64_t)(c->Hd + 2 * c->Hkd) * MS_DP, NKVd = (int64_t)2 * c->Hkd * MS_DP;
-    for (size_t li = 0; li < dof.size(); ++li) {
+    a.bvec(E + ".layer_norm.weight", d, c->enc_ln);
+    // ---- decoder; a tied proj is the embedding's offset bound a second time
+    const size_t o_emb = a.bmat(D + ".embed_tokens.weight", V, d, c->emb);
+    if (c->cfg.tie_word_embeddings) a.bind(c->proj, o_emb); else a.bmat("proj_out.weight", V, d, c->proj);
+    c->dec.assign(c->cfg.decoder_num_hidden_layers, MsDecLayer{});
+    for (size_t li = 0; li < c->dec.size(); ++li) {
         const std::string q = D + ".layers." + std::to_string(li);
-        Off& o = dof[li];
-        o.v[0] = a.bvec(q + ".input_layernorm.weight", d); o.v[1] = a.bvec(q + ".post_attention_layernorm.weight", d);
-        o.v[2] = a.bvec(q + ".final_layernorm.weight", d);
-        o.v[3] = a.btake((size_t)NQd * d);
-        pad_rows(q + ".self_attn.q_proj.weight", c->Hd, c->hdd, o.v[3], 0);
-        pad_rows(q + ".self_attn.k_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)c->Hd * MS_DP);
-        pad_rows(q + ".self_attn.v_proj.weight", c->Hkd, c->hdd, o.v[3], (int64_t)(c->Hd + c->Hkd) * MS_DP);
-        o.v[4] = a.btake(NQd);
-        if (ab) {
-            pad_bias(q + ".self_attn.q_proj.bias", c->Hd, c->hdd, o.v[4], 0);
-            pad_bias(q + ".self_attn.k_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)c->Hd * MS_DP);
-            pad_bias(q + ".self_attn.v_proj.bias", c->Hkd, c->hdd, o.v[4], (int64_t)(c->Hd + c->Hkd) * MS_DP);
-        }
-        o.v[5] = pad_cols(q + ".self_attn.o_proj.weight", c->Hd, c->hdd);
-        o.v[6] = a.btake((size_t)c->Hd * MS_DP * d);
-        pad_rows(q + ".encoder_attn.q_proj.weight", c->Hd, c->hdd, o.v[6], 0);
-        o.v[7] = a.btake((size_t)c->Hd * MS_DP);
-        if (ab) pad_bias(q + ".encoder_attn.q_proj.bias", c->Hd, c->hdd, o.v[7], 0);
-        o.v[8] = a.btake((size_t)NKVd * d);
-        pad_rows(q + ".encoder_attn.k_proj.weight", c->Hkd, c->hdd, o.v[8], 0);
-        pad_rows(q + ".encoder_attn.v_proj.weight", c->Hkd, c->hdd, o.v[8], (int64_t)c->Hkd * MS_DP);
-        o.v[9] = a.btake(NKVd);
-        if (ab) {
-            pad_bias(q + ".encoder_attn.k_proj.bias", c->Hkd, c->hdd, o.v[9], 0);
-            pad_bias(q + ".encoder_attn.v_proj.bias", c->Hkd, c->hdd, o.v[9], (int64_t)c->Hkd * MS_DP);
-        }
-        o.v[10] = pad_cols(q + ".encoder_attn.o_proj.weight", c->Hd, c->hdd);
-        o.v[11] = a.bmat(q + ".mlp.fc1.weight", 2 * f, d); o.v[12] = a.bvec(q + ".mlp.fc1.bias", 2 * f);
-        o.v[13] = a.bmat(q + ".mlp.fc2.weight", d, f); o.v[14] = a.bvec(q + ".mlp.fc2.bias", d);
+        MsDecLayer& l = c->dec[li];
+        a.bvec(q + ".input_layernorm.weight", d, l.ln1); a.bvec(q + ".post_attention_layernorm.weight", d, l.ln2);
+        a.bvec(q + ".final_layernorm.weight", d, l.ln3);
+        const int hd3[3] = {c->Hd, c->Hkd, c->Hkd};
+        qkv(q + ".self_attn", QKV, hd3, 3, c->hdd, l.sqkv, l.sbqkv);
+        pad_cols(q + ".self_attn.o_proj.weight", c->Hd, c->hdd, l.so);
+        qkv(q + ".encoder_attn", QKV, hd3, 1, c->hdd, l.cq, l.cbq);
+        qkv(q + ".encoder_attn", QKV + 1, hd3 + 1, 2, c->hdd, l.ckv, l.cbkv);
+        pad_cols(q + ".encoder_attn.o_proj.weight", c->Hd, c->hdd, l.co);
+        a.bmat(q + ".mlp.fc1.weight", 2 * f, d, l.fc1); a.bvec(q + ".mlp.fc1.bias", 2 * f, l.b1);
+        a.bmat(q + ".mlp.fc2.weight", d, f, l.fc2); a.bvec(q + ".mlp.fc2.bias", d, l.b2);
     }
-    const size_t o_dn = a.bvec(D + ".norm.weight", d);
-    // ---- upload
+    a.bvec(D + ".norm.weight", d, c->dec_norm);
+    // ---- upload: every pointer bound above now addresses the device arenas
     a.upload(c->arena, c->farena);
-    bf16_t* A = c->arena.p;
-    float* F = c->farena.p;
-    c->conv1wT = F + o_c1; c->gn_w = F + o_gw; c->gn_b = F + o_gb;
-    c->cos_e = F + o_ce; c->sin_e = F + o_se; c->cos_d = F + o_cd; c->sin_d = F + o_sd;
-    c->zeros = A + o_zero; c->conv2w = A + o_c2w; c->conv2b = A + o_c2b; c->conv3w = A + o_c3w; c->conv3b = A + o_c3b;
-    c->enc_ln = A + o_eln; c->emb = A + o_emb; c->proj = A + o_proj; c->dec_norm = A + o_dn;
-    c->enc.resize(eo.size());
-    for (size_t li = 0; li < eo.size(); ++li) {
-        const Off& o = eo[li];
-        c->enc[li] = MsEncLayer{A + o.v[0], A + o.v[1], A + o.v[2], ab ? A + o.v[3] : nullptr, A + o.v[4], A + o.v[5], A + o.v[6], A + o.v[7], A + o.v[8]};
-    }
-    c->dec.resize(dof.size());
-    for (size_t li = 0; li < dof.size(); ++li) {
-        const Off& o = dof[li];
-        c->dec[li] = MsDecLayer{A + o.v[0], A + o.v[1], A + o.v[2], A + o.v[3], ab ? A + o.v[4] : nullptr, A + o.v[5], A + o.v[6],
-                                ab ? A + o.v[7] : nullptr, A + o.v[8], ab ? A + o.v[9] : nullptr, A + o.v[10], A + o.v[11], A + o.v[12],
-                                A + o.v[13], A + o.v[14]};
-    }
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

@@ -30,6 +30,7 @@
 #include "audio_front.h"
 #include "f32_tile.h"
 #include "host_weights.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -575,7 +576,7 @@ struct mis_mossformer2 {
     int last_batch = 0, last_nr = 0, last_launches = 0;
     int64_t last_out = 0;
     bool last_front = false, last_net = false, last_synth = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    HipEvents<4> ev;
     float ms[3] = {0.0f, 0.0f, 0.0f};
 };
 
@@ -612,7 +613,6 @@ extern "C" mis_status mis_mossformer2_create(const mis_mossformer2_config* cfg, 
     while (c->nfft < c->wlen) { c->nfft <<= 1; ++c->log2n; }
     c->Tcap = mf_frames_of(c.get(), cfg->max_samples); c->Gcap = cdiv(c->Tcap, MF_GROUP);
     c->out_cap = (int64_t)(c->Tcap - 1) * c->hop + c->W;
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -621,7 +621,6 @@ extern "C" void mis_mossformer2_destroy(mis_mossformer2* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -630,9 +629,7 @@ extern "C" void mis_mossformer2_destroy(mis_mossformer2* c) {
 extern "C" mis_status mis_mossformer2_set_tensor(mis_mossformer2* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape,
                                                  int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 4, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 4, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
@@ -648,49 +645,50 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
     const double PI = 3.14159265358979323846;
     HostArena a(c->raw);
     std::vector<float>& fh = a.fhost;
-    struct LOff { size_t w, b; bool bias; int cin, cout; };
-    auto lin = [&](const std::string& p, std::initializer_list<int64_t> shape, int64_t cout, int64_t cin, bool bias) {
-        LOff o{a.fvec(p + ".weight", shape, cout * cin), 0, bias, (int)cin, (int)cout};
-        if (bias) o.b = a.fvec(p + ".bias", {cout}, cout);
-        return o;
+    auto lin = [&](const std::string& p, std::initializer_list<int64_t> shape, int64_t cout, int64_t cin, bool bias, MfLin& l) {
+        l = MfLin{nullptr, nullptr, (int)cin, (int)cout};
+        a.fvec(p + ".weight", shape, cout * cin, l.w);
+        if (bias) a.fvec(p + ".bias", {cout}, cout, l.b);
     };
-    auto vec = [&](const std::string& name, std::initializer_list<int64_t> shape, int64_t n) { return a.fvec(name, shape, n); };
-    const size_t o_glw = vec("norm.weight", {Ci, 1}, Ci), o_glb = vec("norm.bias", {Ci, 1}, Ci);
-    const LOff o_enc = lin("conv1d_encoder", {D, 1, Ci}, D, Ci, false);
-    struct FOff { LOff hq, out; size_t gh, gqk, gout, dwhq, dwout, gamma, beta; };
-    struct SOff { LOff conv1, uv, lin, proj, conv2; size_t prelu, n1w, n1b, n2w, n2b, dwuv, dw39; };
-    std::vector<FOff> fo;
-    std::vector<SOff> so;
+    // a weight [cout][cin] at ow and a bias [cout] at ob for a packer below to fill
+    auto packed = [&](int64_t cout, int64_t cin, MfLin& l, size_t& ow, size_t& ob) {
+        l = MfLin{nullptr, nullptr, (int)cin, (int)cout};
+        ow = a.ftake((size_t)cout * cin, l.w); ob = a.ftake(cout, l.b);
+    };
+    auto vec = [&](const std::string& name, std::initializer_list<int64_t> shape, int64_t n, const float*& dst) { a.fvec(name, shape, n, dst); };
+    vec("norm.weight", {Ci, 1}, Ci, c->gln_w); vec("norm.bias", {Ci, 1}, Ci, c->gln_b);
+    lin("conv1d_encoder", {D, 1, Ci}, D, Ci, false, c->enc);
+    c->flash.assign(c->NB, MfFlash{}); c->fsmn.assign(c->NB, MfFsmn{});
+    size_t ow, ob;
     for (int i = 0; i < c->NB; ++i) {
         const std::string q = mf_layer(i);
-        FOff f{};
+        MfFlash& f = c->flash[i];
         // to_hidden and to_qk read the same shifted, scale-normed frame: one weight [4 D + 128][D], one bias, one set of taps
-        f.hq = LOff{a.ftake((size_t)(4 * D + Q) * D), a.ftake(4 * D + Q), true, (int)D, (int)(4 * D + Q)};
+        packed(4 * D + Q, D, f.hq, ow, ob);
         {
             const HostTensor &wh = c->raw.need(q + ".to_hidden.linear.weight", {4 * D, D}), &wq = c->raw.need(q + ".to_qk.linear.weight", {Q, D});
             const HostTensor &bh = c->raw.need(q + ".to_hidden.linear.bias", {4 * D}), &bq = c->raw.need(q + ".to_qk.linear.bias", {Q});
-            std::copy(wh.v.begin(), wh.v.end(), fh.begin() + f.hq.w); std::copy(wq.v.begin(), wq.v.end(), fh.begin() + f.hq.w + 4 * D * D);
-            std::copy(bh.v.begin(), bh.v.end(), fh.begin() + f.hq.b); std::copy(bq.v.begin(), bq.v.end(), fh.begin() + f.hq.b + 4 * D);
+            std::copy(wh.v.begin(), wh.v.end(), fh.begin() + ow); std::copy(wq.v.begin(), wq.v.end(), fh.begin() + ow + 4 * D * D);
+            std::copy(bh.v.begin(), bh.v.end(), fh.begin() + ob); std::copy(bq.v.begin(), bq.v.end(), fh.begin() + ob + 4 * D);
             const HostTensor &dh = c->raw.need(q + ".to_hidden.conv_module.weight", {4 * D, MF_FF_TAPS, 1}),
                              &dq = c->raw.need(q + ".to_qk.conv_module.weight", {Q, MF_FF_TAPS, 1});
-            f.dwhq = a.ftake((size_t)(4 * D + Q) * MF_FF_TAPS);
-            std::copy(dh.v.begin(), dh.v.end(), fh.begin() + f.dwhq); std::copy(dq.v.begin(), dq.v.end(), fh.begin() + f.dwhq + 4 * D * MF_FF_TAPS);
+            const size_t o_dw = a.ftake((size_t)(4 * D + Q) * MF_FF_TAPS, f.dw_hq);
+            std::copy(dh.v.begin(), dh.v.end(), fh.begin() + o_dw); std::copy(dq.v.begin(), dq.v.end(), fh.begin() + o_dw + 4 * D * MF_FF_TAPS);
         }
-        f.gh = vec(q + ".to_hidden.norm.g", {1}, 1); f.gqk = vec(q + ".to_qk.norm.g", {1}, 1); f.gout = vec(q + ".to_out.norm.g", {1}, 1);
-        f.gamma = vec(q + ".qk_offset_scale.gamma", {4, Q}, 4 * Q); f.beta = vec(q + ".qk_offset_scale.beta", {4, Q}, 4 * Q);
-        f.out = lin(q + ".to_out.linear", {D, 2 * D}, D, 2 * D, true);
-        f.dwout = vec(q + ".to_out.conv_module.weight", {D, MF_FF_TAPS, 1}, D * MF_FF_TAPS);
-        fo.push_back(f);
+        vec(q + ".to_hidden.norm.g", {1}, 1, f.g_h); vec(q + ".to_qk.norm.g", {1}, 1, f.g_qk); vec(q + ".to_out.norm.g", {1}, 1, f.g_out);
+        vec(q + ".qk_offset_scale.gamma", {4, Q}, 4 * Q, f.gamma); vec(q + ".qk_offset_scale.beta", {4, Q}, 4 * Q, f.beta);
+        lin(q + ".to_out.linear", {D, 2 * D}, D, 2 * D, true, f.out);
+        vec(q + ".to_out.conv_module.weight", {D, MF_FF_TAPS, 1}, D * MF_FF_TAPS, f.dw_out);
         const std::string s = mf_fsmn(i), gq = s + ".gated_fsmn";
-        SOff z{};
-        z.conv1 = lin(s + ".conv1", {I, 1, D}, I, D, true);
-        z.prelu = vec(s + ".prelu.weight", {1}, 1);
-        z.n1w = vec(s + ".norm1.weight", {I}, I); z.n1b = vec(s + ".norm1.bias", {I}, I);
-        z.n2w = vec(s + ".norm2.weight", {I}, I); z.n2b = vec(s + ".norm2.bias", {I}, I);
+        MfFsmn& z = c->fsmn[i];
+        lin(s + ".conv1", {I, 1, D}, I, D, true, z.conv1);
+        vec(s + ".prelu.weight", {1}, 1, z.prelu);
+        vec(s + ".norm1.weight", {I}, I, z.n1w); vec(s + ".norm1.bias", {I}, I, z.n1b);
+        vec(s + ".norm2.weight", {I}, I, z.n2w); vec(s + ".norm2.bias", {I}, I, z.n2b);
         // to_u | to_v: the LayerNorm's weight and bias are folded into the Linear (formed in double, rounded once); the kernel
         // normalises on load
-        z.uv = LOff{a.ftake((size_t)2 * I * I), a.ftake(2 * I), true, (int)I, (int)(2 * I)};
-        z.dwuv = a.ftake((size_t)2 * I * MF_FF_TAPS);
+        packed(2 * I, I, z.uv, ow, ob);
+        const size_t o_dwuv = a.ftake((size_t)2 * I * MF_FF_TAPS, z.dw_uv);
         for (int h = 0; h < 2; ++h) {
             const std::string t = gq + (h ? ".to_v" : ".to_u");
             const HostTensor &w = c->raw.need(t + ".linear.weight", {I, I}), &bl = c->raw.need(t + ".linear.bias", {I});
@@ -699,35 +697,35 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
             for (int64_t o = 0; o < I; ++o) {
                 double acc = bl.v[o];
                 for (int64_t k = 0; k < I; ++k) {
-                    fh[z.uv.w + (h * I + o) * I + k] = (float)((double)w.v[o * I + k] * (double)nw.v[k]);
+                    fh[ow + (h * I + o) * I + k] = (float)((double)w.v[o * I + k] * (double)nw.v[k]);
                     acc += (double)w.v[o * I + k] * (double)nb.v[k];
                 }
-                fh[z.uv.b + h * I + o] = (float)acc;
+                fh[ob + h * I + o] = (float)acc;
             }
-            std::copy(dw.v.begin(), dw.v.end(), fh.begin() + z.dwuv + h * I * MF_FF_TAPS);
+            std::copy(dw.v.begin(), dw.v.end(), fh.begin() + o_dwuv + h * I * MF_FF_TAPS);
         }
-        z.lin = lin(gq + ".fsmn.linear", {I, I}, I, I, true);
-        z.proj = lin(gq + ".fsmn.project", {I, I}, I, I, false);
-        z.dw39 = vec(gq + ".fsmn.conv1.weight", {I, MF_FSMN_TAPS, 1, 1}, I * MF_FSMN_TAPS);
-        z.conv2 = lin(s + ".conv2", {D, 1, I}, D, I, true);
-        so.push_back(z);
+        lin(gq + ".fsmn.linear", {I, I}, I, I, true, z.lin);
+        lin(gq + ".fsmn.project", {I, I}, I, I, false, z.proj);
+        vec(gq + ".fsmn.conv1.weight", {I, MF_FSMN_TAPS, 1, 1}, I * MF_FSMN_TAPS, z.dw39);
+        lin(s + ".conv2", {D, 1, I}, D, I, true, z.conv2);
     }
-    const size_t o_l1w = vec("mdl.intra_mdl.norm.weight", {D}, D), o_l1b = vec("mdl.intra_mdl.norm.bias", {D}, D);
-    const size_t o_l2w = vec("mdl.intra_norm.weight", {D}, D), o_l2b = vec("mdl.intra_norm.bias", {D}, D);
-    const size_t o_prelu = vec("prelu.weight", {1}, 1);
+    vec("mdl.intra_mdl.norm.weight", {D}, D, c->ln1w); vec("mdl.intra_mdl.norm.bias", {D}, D, c->ln1b);
+    vec("mdl.intra_norm.weight", {D}, D, c->ln2w); vec("mdl.intra_norm.bias", {D}, D, c->ln2b);
+    vec("prelu.weight", {1}, 1, c->prelu);
     // speaker 0 is the first out_channels outputs of conv1d_out; the reference returns nothing of the second speaker
-    const LOff o_co{a.fvec("conv1d_out.weight", {2 * D, 1, D}, D * D), a.fvec("conv1d_out.bias", {2 * D}, D), true, (int)D, (int)D};
-    LOff o_og{a.ftake((size_t)2 * D * D), a.ftake(2 * D), true, (int)D, (int)(2 * D)};
+    c->cout0 = MfLin{nullptr, nullptr, (int)D, (int)D};
+    a.fvec("conv1d_out.weight", {2 * D, 1, D}, D * D, c->cout0.w); a.fvec("conv1d_out.bias", {2 * D}, D, c->cout0.b);
+    packed(2 * D, D, c->og, ow, ob);
     {
         const HostTensor &wo = c->raw.need("output.weight", {D, 1, D}), &wg = c->raw.need("output_gate.weight", {D, 1, D});
         const HostTensor &bo = c->raw.need("output.bias", {D}), &bg = c->raw.need("output_gate.bias", {D});
-        std::copy(wo.v.begin(), wo.v.end(), fh.begin() + o_og.w); std::copy(wg.v.begin(), wg.v.end(), fh.begin() + o_og.w + D * D);
-        std::copy(bo.v.begin(), bo.v.end(), fh.begin() + o_og.b); std::copy(bg.v.begin(), bg.v.end(), fh.begin() + o_og.b + D);
+        std::copy(wo.v.begin(), wo.v.end(), fh.begin() + ow); std::copy(wg.v.begin(), wg.v.end(), fh.begin() + ow + D * D);
+        std::copy(bo.v.begin(), bo.v.end(), fh.begin() + ob); std::copy(bg.v.begin(), bg.v.end(), fh.begin() + ob + D);
     }
-    const LOff o_dec = lin("conv1_decoder", {F, 1, D}, F, D, false);
+    lin("conv1_decoder", {F, 1, D}, F, D, false, c->dec);
     // ---- tables
     const HostTensor &pscale = c->raw.need("pos_enc.scale", {1}), &pfreq = c->raw.need("pos_enc.inv_freq", {D / 2});
-    const size_t o_pos = a.ftake((size_t)Tc * D), o_rc = a.ftake((size_t)Tc * (MF_ROPE / 2)), o_rs = a.ftake((size_t)Tc * (MF_ROPE / 2));
+    const size_t o_pos = a.ftake((size_t)Tc * D, c->pos), o_rc = a.ftake((size_t)Tc * (MF_ROPE / 2), c->rc), o_rs = a.ftake((size_t)Tc * (MF_ROPE / 2), c->rs);
     for (int64_t t = 0; t < Tc; ++t) {
         for (int64_t i = 0; i < D / 2; ++i) {                          // [sin | cos] scale; the angle is the f32 product the reference forms
             const float th = (float)t * pfreq.v[i];
@@ -740,7 +738,7 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
         }
     }
     const int bins = c->nfft / 2 + 1;
-    const size_t o_win = a.ftake(c->wlen), o_twc = a.ftake(1024), o_tws = a.ftake(1024), o_fb = a.ftake((size_t)bins * nm);
+    const size_t o_win = a.ftake(c->wlen, c->win), o_twc = a.ftake(1024, c->twc), o_tws = a.ftake(1024, c->tws), o_fb = a.ftake((size_t)bins * nm, c->fb);
     for (int i = 0; i < c->wlen; ++i) {                                // the reference's own f32 arithmetic (hammingWindow / hannWindow)
         const float phase = 2.0f * (float)M_PI * (float)i / (float)(c->wlen - 1);
         fh[o_win + i] = c->cfg.win_hann ? 0.5f - 0.5f * (float)cos((double)phase) : 0.54f - 0.46f * (float)cos((double)phase);
@@ -767,7 +765,7 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
         filter_bin_ranges(&fh[o_fb], bins, (int)nm, ih.data());
     }
     // the transform pair as tables formed in double: rows [cos | -sin] over the W samples a frame keeps, and the inverse's weights
-    const size_t o_dft = a.ftake((size_t)2 * F * W), o_idft = a.ftake((size_t)W * 2 * F);
+    const size_t o_dft = a.ftake((size_t)2 * F * W, c->dft), o_idft = a.ftake((size_t)W * 2 * F, c->idft);
     for (int64_t k = 0; k < F; ++k)
         for (int64_t n = 0; n < W; ++n) {
             const double ang = 2.0 * PI * (double)((k * n) % N) / (double)N;
@@ -776,7 +774,7 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
             fh[o_idft + n * 2 * F + k] = (float)((edge ? 1.0 : 2.0) * cos(ang) / (double)N);
             fh[o_idft + n * 2 * F + F + k] = edge ? 0.0f : (float)(-2.0 * sin(ang) / (double)N);
         }
-    // ---- the workspace, sized once.  Nothing of the handle has changed up to here: a finalize rejected for a missing or misshapen
+    // ---- the workspace, sized once.  No call reads the handle before finalized is set: a finalize rejected for a missing or misshapen
     // tensor or for its size can be repeated.  A failed device allocation below is not recoverable: destroy the handle.
     const size_t B = c->cfg.max_batch, rows = B * (size_t)Tc;
     const size_t per_row = nm + 2 * Ci + (2 * c->NB + 1) * D + (4 * D + Q) + 4 * D + 4 * Q + 2 * D + D + 2 * I + 2 * 2 * I + 4 * I + 4 + D + D
@@ -803,20 +801,7 @@ extern "C" mis_status mis_mossformer2_finalize(mis_mossformer2* c) {
     c->tail = take(rows * D); c->co = take(rows * D); c->ogb = take(rows * 2 * D); c->mask = take(rows * F); c->spec = take(rows * 2 * F);
     c->fr = take(rows * W); c->P = take(B * (size_t)c->Gcap * Q * 4 * D); c->S = take(B * (size_t)Q * 4 * D); c->wave = take(B * (size_t)c->out_cap);
     MIS_REQUIRE((size_t)(w - c->work.p) <= total, MIS_ERR_GENERATION_FAILED, "workspace layout exceeds its size");
-    const float* Pw = c->farena.p;
-    auto mk = [&](const LOff& o) { return MfLin{Pw + o.w, o.bias ? Pw + o.b : nullptr, o.cin, o.cout}; };
-    c->enc = mk(o_enc); c->cout0 = mk(o_co); c->og = mk(o_og); c->dec = mk(o_dec);
-    c->flash.clear(); c->fsmn.clear();
-    for (int i = 0; i < c->NB; ++i) {
-        const FOff& f = fo[i];
-        c->flash.push_back(MfFlash{mk(f.hq), mk(f.out), Pw + f.gh, Pw + f.gqk, Pw + f.gout, Pw + f.dwhq, Pw + f.dwout, Pw + f.gamma, Pw + f.beta});
-        const SOff& z = so[i];
-        c->fsmn.push_back(MfFsmn{mk(z.conv1), mk(z.uv), mk(z.lin), mk(z.proj), mk(z.conv2), Pw + z.prelu, Pw + z.n1w, Pw + z.n1b, Pw + z.n2w,
-                                 Pw + z.n2b, Pw + z.dwuv, Pw + z.dw39});
-    }
-    c->gln_w = Pw + o_glw; c->gln_b = Pw + o_glb; c->ln1w = Pw + o_l1w; c->ln1b = Pw + o_l1b; c->ln2w = Pw + o_l2w; c->ln2b = Pw + o_l2b;
-    c->prelu = Pw + o_prelu; c->pos = Pw + o_pos; c->rc = Pw + o_rc; c->rs = Pw + o_rs; c->win = Pw + o_win; c->twc = Pw + o_twc;
-    c->tws = Pw + o_tws; c->fb = Pw + o_fb; c->dft = Pw + o_dft; c->idft = Pw + o_idft; c->fbr = c->iarena.p;
+    c->fbr = c->iarena.p;
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

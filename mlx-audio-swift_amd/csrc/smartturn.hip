@@ -61,7 +61,7 @@ struct mis_smartturn {
     DevBuf<int32_t> pred;
     DevBuf<bf16_t> col1, h1, col2, h, x, qkv, att, ff, kc, vc, enc_out;
     std::map<int, StepGraph> graphs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    HipEvents<4> ev;
     float ms_prepare = 0.0f, ms_encoder = 0.0f, ms_head = 0.0f;
 };
 
@@ -93,7 +93,6 @@ extern "C" mis_status mis_smartturn_create(const mis_smartturn_config* cfg, int 
     c->mel.sample_rate = cfg->sampling_rate; c->mel.n_fft = cfg->n_fft; c->mel.hop_length = cfg->hop_length; c->mel.n_mels = c->nmel;
     c->mel.window = 1; c->mel.mel_scale = 1; c->mel.slaney_norm = 1; c->mel.drop_last_frame = 1;      // SmartTurnFeatures.swift:56-72
     MIS_REQUIRE(mis_mel_num_frames(&c->mel, W) == F, MIS_ERR_INVALID_INPUT, "frame count of the front end differs from W / hop_length");
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -103,7 +102,6 @@ extern "C" void mis_smartturn_destroy(mis_smartturn* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->graphs.clear();
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -112,9 +110,7 @@ extern "C" void mis_smartturn_destroy(mis_smartturn* c) {
 extern "C" mis_status mis_smartturn_set_tensor(mis_smartturn* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape,
                                                int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 3, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 3, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
@@ -128,83 +124,66 @@ extern "C" mis_status mis_smartturn_finalize(mis_smartturn* c) {
     std::vector<bf16_t>& host = a.host;                 // the packers below write through these
     std::vector<float>& fhost = a.fhost;                // the f32 head
     // Linear.weight [N][K] -> [K][N]: a thread is an output unit, neighbouring threads read neighbouring floats
-    auto fmatT = [&](const std::string& name, int64_t N, int64_t K) {
+    auto fmatT = [&](const std::string& name, int64_t N, int64_t K, float*& dst) {
         const HostTensor& t = c->raw.need(name, {N, K});
-        size_t off = a.ftake((size_t)N * K);
+        size_t off = a.ftake((size_t)N * K, dst);
         for (int64_t n = 0; n < N; ++n) for (int64_t k = 0; k < K; ++k) fhost[off + (size_t)k * N + n] = t.v[(size_t)n * K + k];
-        return off;
     };
     const std::string E = "encoder";
+    WhisperEncWeights& w = c->enc;
     // conv weights [out][k][in] (MLX layout after sanitize): the column order of the k = 3 patches; conv1's rows padded to K1 columns
-    size_t o_c1w;
     {
         const HostTensor& t = c->raw.need(E + ".conv1.weight", {d, 3, nm});
-        o_c1w = a.btake((size_t)d * K1);
-        for (int64_t o = 0; o < d; ++o) for (int64_t k = 0; k < 3 * nm; ++k) host[o_c1w + (size_t)o * K1 + k] = f32_to_bf16(t.v[(size_t)o * 3 * nm + k]);
+        const size_t o = a.btake((size_t)d * K1, w.conv1w);
+        for (int64_t n = 0; n < d; ++n) for (int64_t k = 0; k < 3 * nm; ++k) host[o + (size_t)n * K1 + k] = f32_to_bf16(t.v[(size_t)n * 3 * nm + k]);
     }
-    const size_t o_c1b = a.bvec(E + ".conv1.bias", d);
-    size_t o_c2w;
+    a.bvec(E + ".conv1.bias", d, w.conv1b);
     {
         const HostTensor& t = c->raw.need(E + ".conv2.weight", {d, 3, d});
-        o_c2w = a.btake((size_t)d * 3 * d);
-        for (size_t i = 0; i < (size_t)d * 3 * d; ++i) host[o_c2w + i] = f32_to_bf16(t.v[i]);
+        const size_t o = a.btake((size_t)d * 3 * d, w.conv2w);
+        for (size_t i = 0; i < (size_t)d * 3 * d; ++i) host[o + i] = f32_to_bf16(t.v[i]);
     }
-    const size_t o_c2b = a.bvec(E + ".conv2.bias", d);
-    size_t o_pos;
+    a.bvec(E + ".conv2.bias", d, w.conv2b);
     {   // rows 0 .. T - 1 of the table (:141-142)
         const HostTensor& t = c->raw.need(E + ".embed_positions.weight", {(int64_t)c->cfg.max_source_positions, d});
-        o_pos = a.btake((size_t)T * d);
-        for (size_t i = 0; i < (size_t)T * d; ++i) host[o_pos + i] = f32_to_bf16(t.v[i]);
+        const size_t o = a.btake((size_t)T * d, w.pos);
+        for (size_t i = 0; i < (size_t)T * d; ++i) host[o + i] = f32_to_bf16(t.v[i]);
     }
-    struct Off { size_t v[12]; };
-    std::vector<Off> lo(c->cfg.encoder_layers);
-    for (size_t li = 0; li < lo.size(); ++li) {
+    w.layers.assign(c->cfg.encoder_layers, WhisperEncLayer{});
+    for (size_t li = 0; li < w.layers.size(); ++li) {
         const std::string q = E + ".layers." + std::to_string(li);
-        Off& o = lo[li];
-        o.v[0] = a.bvec(q + ".self_attn_layer_norm.weight", d); o.v[1] = a.bvec(q + ".self_attn_layer_norm.bias", d);
-        o.v[2] = a.btake((size_t)3 * d * d);
-        a.bmat_into(q + ".self_attn.q_proj.weight", d, d, o.v[2]);
-        a.bmat_into(q + ".self_attn.k_proj.weight", d, d, o.v[2] + (size_t)d * d);
-        a.bmat_into(q + ".self_attn.v_proj.weight", d, d, o.v[2] + (size_t)2 * d * d);
-        o.v[3] = a.btake(3 * d);
+        WhisperEncLayer& l = w.layers[li];
+        a.bvec(q + ".self_attn_layer_norm.weight", d, l.ln1w); a.bvec(q + ".self_attn_layer_norm.bias", d, l.ln1b);
+        const size_t ow = a.btake((size_t)3 * d * d, l.wqkv);
+        a.bmat_into(q + ".self_attn.q_proj.weight", d, d, ow);
+        a.bmat_into(q + ".self_attn.k_proj.weight", d, d, ow + (size_t)d * d);
+        a.bmat_into(q + ".self_attn.v_proj.weight", d, d, ow + (size_t)2 * d * d);
+        const size_t ob = a.btake(3 * d, l.bqkv);
         {
             const HostTensor& qb = c->raw.need(q + ".self_attn.q_proj.bias", {d});
             const HostTensor& vb = c->raw.need(q + ".self_attn.v_proj.bias", {d});
-            for (int64_t i = 0; i < d; ++i) { host[o.v[3] + i] = f32_to_bf16(qb.v[i]); host[o.v[3] + 2 * d + i] = f32_to_bf16(vb.v[i]); }
+            for (int64_t i = 0; i < d; ++i) { host[ob + i] = f32_to_bf16(qb.v[i]); host[ob + 2 * d + i] = f32_to_bf16(vb.v[i]); }
             if (c->cfg.k_proj_bias) {
                 const HostTensor& kb = c->raw.need(q + ".self_attn.k_proj.bias", {d});
-                for (int64_t i = 0; i < d; ++i) host[o.v[3] + d + i] = f32_to_bf16(kb.v[i]);
+                for (int64_t i = 0; i < d; ++i) host[ob + d + i] = f32_to_bf16(kb.v[i]);
             }
         }
-        o.v[4] = a.bmat(q + ".self_attn.out_proj.weight", d, d); o.v[5] = a.bvec(q + ".self_attn.out_proj.bias", d);
-        o.v[6] = a.bvec(q + ".final_layer_norm.weight", d); o.v[7] = a.bvec(q + ".final_layer_norm.bias", d);
-        o.v[8] = a.bmat(q + ".fc1.weight", f, d); o.v[9] = a.bvec(q + ".fc1.bias", f);
-        o.v[10] = a.bmat(q + ".fc2.weight", d, f); o.v[11] = a.bvec(q + ".fc2.bias", d);
+        a.bmat(q + ".self_attn.out_proj.weight", d, d, l.wo); a.bvec(q + ".self_attn.out_proj.bias", d, l.bo);
+        a.bvec(q + ".final_layer_norm.weight", d, l.ln2w); a.bvec(q + ".final_layer_norm.bias", d, l.ln2b);
+        a.bmat(q + ".fc1.weight", f, d, l.fc1); a.bvec(q + ".fc1.bias", f, l.b1);
+        a.bmat(q + ".fc2.weight", d, f, l.fc2); a.bvec(q + ".fc2.bias", d, l.b2);
     }
-    const size_t o_lnw = a.bvec(E + ".layer_norm.weight", d), o_lnb = a.bvec(E + ".layer_norm.bias", d);
+    a.bvec(E + ".layer_norm.weight", d, w.lnw); a.bvec(E + ".layer_norm.bias", d, w.lnb);
     // ---- the head, f32 as stored
-    const size_t o_p0w = fmatT("pool_attention_0.weight", ST_POOL_HID, d), o_p0b = a.fvec("pool_attention_0.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_p2w = a.fvec("pool_attention_2.weight", {1, ST_POOL_HID}, ST_POOL_HID), o_p2b = a.fvec("pool_attention_2.bias", {1}, 1);
-    const size_t o_c0w = fmatT("classifier_0.weight", ST_POOL_HID, d), o_c0b = a.fvec("classifier_0.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_n1w = a.fvec("classifier_1.weight", {ST_POOL_HID}, ST_POOL_HID), o_n1b = a.fvec("classifier_1.bias", {ST_POOL_HID}, ST_POOL_HID);
-    const size_t o_c4w = fmatT("classifier_4.weight", ST_CLS_MID, ST_POOL_HID), o_c4b = a.fvec("classifier_4.bias", {ST_CLS_MID}, ST_CLS_MID);
-    const size_t o_c6w = a.fvec("classifier_6.weight", {1, ST_CLS_MID}, ST_CLS_MID), o_c6b = a.fvec("classifier_6.bias", {1}, 1);
-    // ---- upload (nothing of the handle has changed up to here: a rejected finalize can be repeated)
+    fmatT("pool_attention_0.weight", ST_POOL_HID, d, c->p0wT); a.fvec("pool_attention_0.bias", {ST_POOL_HID}, ST_POOL_HID, c->p0b);
+    a.fvec("pool_attention_2.weight", {1, ST_POOL_HID}, ST_POOL_HID, c->p2w); a.fvec("pool_attention_2.bias", {1}, 1, c->p2b);
+    fmatT("classifier_0.weight", ST_POOL_HID, d, c->c0wT); a.fvec("classifier_0.bias", {ST_POOL_HID}, ST_POOL_HID, c->c0b);
+    a.fvec("classifier_1.weight", {ST_POOL_HID}, ST_POOL_HID, c->c1w); a.fvec("classifier_1.bias", {ST_POOL_HID}, ST_POOL_HID, c->c1b);
+    fmatT("classifier_4.weight", ST_CLS_MID, ST_POOL_HID, c->c4wT); a.fvec("classifier_4.bias", {ST_CLS_MID}, ST_CLS_MID, c->c4b);
+    a.fvec("classifier_6.weight", {1, ST_CLS_MID}, ST_CLS_MID, c->c6w); a.fvec("classifier_6.bias", {1}, 1, c->c6b);
+    // ---- upload (no call reads the handle before finalized is set: a rejected finalize can be repeated)
     a.upload(c->arena, c->farena);
-    bf16_t* A = c->arena.p;
-    float* P = c->farena.p;
-    WhisperEncWeights& w = c->enc;
-    w.conv1w = A + o_c1w; w.conv1b = A + o_c1b; w.conv2w = A + o_c2w; w.conv2b = A + o_c2b; w.pos = A + o_pos;
-    w.lnw = A + o_lnw; w.lnb = A + o_lnb;
     w.d = c->d; w.H = c->H; w.D = c->D; w.ffn = c->ffn; w.K1 = c->K1; w.Spad = c->Spad;
-    w.layers.resize(lo.size());
-    for (size_t li = 0; li < lo.size(); ++li) {
-        const Off& o = lo[li];
-        w.layers[li] = WhisperEncLayer{A + o.v[0], A + o.v[1], A + o.v[2], A + o.v[3], A + o.v[4], A + o.v[5], A + o.v[6], A + o.v[7], A + o.v[8],
-                                       A + o.v[9], A + o.v[10], A + o.v[11]};
-    }
-    c->p0wT = P + o_p0w; c->p0b = P + o_p0b; c->p2w = P + o_p2w; c->p2b = P + o_p2b; c->c0wT = P + o_c0w; c->c0b = P + o_c0b;
-    c->c1w = P + o_n1w; c->c1b = P + o_n1b; c->c4wT = P + o_c4w; c->c4b = P + o_c4b; c->c6w = P + o_c6w; c->c6b = P + o_c6b;
     c->raw.clear();
     c->finalized = true;
     MIS_API_END

@@ -15,9 +15,9 @@
 // zero rows behind T.  Each output element is one fixed-order sum over data of its own row: bit for bit the same in any batch.
 //
 //   k_sf_peak      scale[b] = 1 / (max|x| + 1e-3) over the row's own samples (1 when the option is off)
-//   k_sf_stft_mel  scale, pre-emphasis, 512-point FFT of one frame in LDS (the butterfly loop is this file's own copy), power,
-//                  slaney filters over each filter's own bins, log(. + 2^-24)
-//   k_sf_norm      per bin mean / unbiased variance over the row's own frames, (x - mean) / (std + 1e-5), or the copy (normalize off)
+//   k_nemo_log_mel<true>  scale, pre-emphasis, 512-point FFT of one frame in LDS, power, slaney filters over each filter's own bins,
+//                  log(. + 2^-24)                                                          (audio_front.h: the front end shared
+//   k_nemo_norm    per bin mean / unbiased variance over the row's own frames, (x - mean) / (std + 1e-5), or the copy    with lasr.hip)
 //   k_sf_conv0     Conv2d 1 -> C, 3 x 3, stride 2, pad 1, ReLU; channels last [B][T1][F1][C]
 //   k_sf_gemm      the one contraction (on f32_tile.h): 64 x 64 tile, every dimension guarded.  Loads: plain, LayerNorm (statistics from k_sf_stats),
 //                  ReLU, and the stem's depthwise 3 x 3 stride-2 conv FOLDED into the operand load of the pointwise GEMM that follows
@@ -41,9 +41,11 @@
 // Launches (derived from the chain below): forward 11 + 15 L_fc + 7 L_tf; forward_features 8 + 15 L_fc + 7 L_tf;
 // encode_embeddings 4 + 15 L_fc + 7 L_tf; pre_encode 4; features 3.
 #include "common.h"
+#define AUDIO_FRONT_NEMO_KERNELS
 #include "audio_front.h"
 #include "f32_tile.h"
 #include "host_weights.h"
+#include "step_loop.h"
 
 #include <math.h>
 #include <string.h>
@@ -51,10 +53,6 @@
 
 #define SF_MAX_BATCH 64
 #define SF_MAX_SECONDS 120
-#define SF_NFFT 512
-#define SF_HOP 160
-#define SF_WIN 400
-#define SF_BINS 257
 #define SF_DW_TT 64
 #define SF_DW_MAXK 31
 
@@ -73,77 +71,7 @@ __global__ void __launch_bounds__(256) k_sf_peak(const float* __restrict__ pcm, 
     if (threadIdx.x == 0) scale[b] = on ? 1.0f / (m + 1e-3f) : 1.0f;
 }
 
-// One frame of one row: samples t 160 - 256 .. + 511 of the scaled, zero-centred, pre-emphasised waveform (y[0] = x[0],
-// y[i] = x[i] - c x[i - 1]), window, 512-point radix-2 FFT in LDS, |.|^2, slaney filters, log(. + 2^-24).
-__global__ void __launch_bounds__(256) k_sf_stft_mel(const float* __restrict__ pcm, int64_t stride, const int* __restrict__ N,
-                                                     const int* __restrict__ F0, const float* __restrict__ scale, float preemph,
-                                                     const float* __restrict__ window, const float* __restrict__ twc,
-                                                     const float* __restrict__ tws, const float* __restrict__ fb, const int* __restrict__ fbr,
-                                                     float* __restrict__ out, int Fp, int mels) {
-    __shared__ float re[SF_NFFT], im[SF_NFFT];
-    const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    float* o = out + ((size_t)b * Fp + t) * mels;
-    if (t >= F0[b]) { if (tid < mels) o[tid] = 0.0f; return; }
-    const int n = N[b];
-    const float g = scale[b];
-    const float* x = pcm + (size_t)b * stride;
-    for (int j = tid; j < SF_NFFT; j += 256) {
-        const float w = window[j];
-        const int64_t s = (int64_t)t * SF_HOP - SF_NFFT / 2 + j;
-        float v = 0.0f;
-        if (w != 0.0f && s >= 0 && s < n) {
-            const float cur = __fmul_rn(g, x[s]);
-            v = s == 0 ? cur : __fsub_rn(cur, __fmul_rn(preemph, __fmul_rn(g, x[s - 1])));
-        }
-        const int r = (int)(__brev((unsigned)j) >> 23);
-        re[r] = __fmul_rn(v, w); im[r] = 0.0f;
-    }
-    __syncthreads();
-    for (int half = 1; half < SF_NFFT; half <<= 1) {
-        const int k = tid & (half - 1), i0 = ((tid - k) << 1) + k, i1 = i0 + half, ti = k * (SF_NFFT / 2 / half);
-        const float c = twc[ti], s = tws[ti];
-        const float xr = re[i1], xi = im[i1];
-        const float pr = xr * c - xi * s, pi = xr * s + xi * c;
-        const float ar = re[i0], ai = im[i0];
-        re[i0] = ar + pr; im[i0] = ai + pi; re[i1] = ar - pr; im[i1] = ai - pi;
-        __syncthreads();
-    }
-    for (int j = tid; j < SF_BINS; j += 256) { const float a = re[j], c = im[j]; re[j] = a * a + c * c; }
-    __syncthreads();
-    if (tid < mels) {
-        float acc = 0.0f;
-        for (int i = fbr[2 * tid]; i < fbr[2 * tid + 1]; ++i) acc = fmaf(re[i], fb[(size_t)i * mels + tid], acc);
-        o[tid] = logf(acc + 5.9604644775390625e-08f);
-    }
-}
-
-// per_feature normalisation over the row's own F0 computed frames (divisor max(F0 - 1, 1)), or the copy; frames F0 .. F (pad_to) and
-// everything behind are zero.  A thread owns one bin and every fourth frame; the four partial sums are added in a fixed order.
-__global__ void __launch_bounds__(256) k_sf_norm(const float* __restrict__ raw, const int* __restrict__ F0, float* __restrict__ out, int Fp,
-                                                 int mels, int normalize) {
-    __shared__ float part[4][64];
-    const int b = blockIdx.y, ml = threadIdx.x & 63, fl = threadIdx.x >> 6, m = blockIdx.x * 64 + ml, n = F0[b];
-    const bool live = m < mels;
-    const float* x = raw + (size_t)b * Fp * mels + (live ? m : 0);
-    float mean = 0.0f, den = 1.0f;
-    if (normalize) {
-        float s = 0.0f;
-        for (int t = fl; t < n; t += 4) s += x[(size_t)t * mels];
-        part[fl][ml] = s;
-        __syncthreads();
-        mean = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)n;
-        __syncthreads();
-        float q = 0.0f;
-        for (int t = fl; t < n; t += 4) { const float v = x[(size_t)t * mels] - mean; q = fmaf(v, v, q); }
-        part[fl][ml] = q;
-        __syncthreads();
-        const float var = ((part[0][ml] + part[1][ml]) + (part[2][ml] + part[3][ml])) / (float)max(n - 1, 1);
-        den = sqrtf(var) + 1e-5f;
-    }
-    if (!live) return;
-    float* y = out + (size_t)b * Fp * mels + m;
-    for (int t = fl; t < Fp; t += 4) y[(size_t)t * mels] = t < n ? (normalize ? (x[(size_t)t * mels] - mean) / den : x[(size_t)t * mels]) : 0.0f;
-}
+// k_nemo_log_mel<true> (every sample times scale[b]) and k_nemo_norm of audio_front.h follow it.
 
 // ============================================================================ stem
 // out[b][t][f][c] = ReLU(bias[c] + sum_ij w[3 i + j][c] feats[b][2 t + i - 1][2 f + j - 1]) for t < T1[b]; the features are zero outside
@@ -501,7 +429,7 @@ struct mis_sortformer {
     // state of the last call
     int batch = 0, Fp = 0, T1p = 0, T2p = 0, Tp = 0, launches = 0;
     std::vector<int> hN, hF0, hF, hT1, hT2, hT3;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    HipEvents<5> ev;
     bool timed = false;
     bool has_emb = false;        // the last call left the stem's embeddings of ITS rows in emb
     bool timed_done = false;     // the last call was a timed forward: all five events are recorded
@@ -509,7 +437,7 @@ struct mis_sortformer {
 
 static inline int sf_half(int t) { return t >= 1 ? (t - 1) / 2 + 1 : 0; }
 static inline int sf_frames(int64_t n, int pad_to) {
-    const int F = (int)(1 + n / SF_HOP);
+    const int F = (int)(1 + n / NEMO_HOP);
     return pad_to > 0 ? (int)round_up(F, pad_to) : F;
 }
 
@@ -536,7 +464,7 @@ extern "C" mis_status mis_sortformer_create(const mis_sortformer_config* cfg, in
     MIS_API_BEGIN
     MIS_REQUIRE(cfg && out, MIS_ERR_INVALID_INPUT, "null argument");
     const int d = cfg->hidden_size, H = cfg->num_attention_heads, dt = cfg->tf_d_model, Ht = cfg->encoder_attention_heads;
-    MIS_REQUIRE(cfg->sampling_rate == 16000 && cfg->n_fft == SF_NFFT && cfg->hop_length == SF_HOP && cfg->win_length == SF_WIN, MIS_ERR_INVALID_INPUT,
+    MIS_REQUIRE(cfg->sampling_rate == 16000 && cfg->n_fft == NEMO_NFFT && cfg->hop_length == NEMO_HOP && cfg->win_length == NEMO_WIN, MIS_ERR_INVALID_INPUT,
                 "sampling_rate / n_fft / hop_length / win_length: only 16000 / 512 / 160 / 400 are implemented");
     MIS_REQUIRE(cfg->preemphasis >= 0.0f && cfg->preemphasis <= 1.0f, MIS_ERR_INVALID_INPUT, "preemphasis outside 0..1");
     MIS_REQUIRE(cfg->num_mel_bins >= 8 && cfg->num_mel_bins <= 256, MIS_ERR_INVALID_INPUT, "num_mel_bins %d outside 8..256", cfg->num_mel_bins);
@@ -566,14 +494,13 @@ extern "C" mis_status mis_sortformer_create(const mis_sortformer_config* cfg, in
     MIS_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= SF_MAX_BATCH, MIS_ERR_INVALID_INPUT, "max_batch %d outside 1..%d", cfg->max_batch, SF_MAX_BATCH);
     MIS_REQUIRE(cfg->max_seconds >= 1 && cfg->max_seconds <= SF_MAX_SECONDS, MIS_ERR_INVALID_INPUT, "max_seconds %d outside 1..%d", cfg->max_seconds,
                 SF_MAX_SECONDS);
+    hipStream_t stream = mis_open_stream(device);      // first: the handle's events belong to this device
     auto c = std::make_unique<mis_sortformer>();
-    c->stream = mis_open_stream(device);
-    c->device = device; c->cfg = *cfg;
+    c->device = device; c->cfg = *cfg; c->stream = stream;
     c->mels = cfg->num_mel_bins; c->C = cfg->subsampling_conv_channels; c->d = d; c->H = H; c->hd = d / H; c->f = cfg->intermediate_size;
     c->L = cfg->num_hidden_layers; c->ck = cfg->conv_kernel_size; c->dt = dt; c->Ht = Ht; c->hdt = dt / Ht; c->ft = cfg->encoder_ffn_dim;
     c->Lt = cfg->encoder_layers; c->S = cfg->num_speakers;
     c->F1 = sf_half(c->mels); c->F2 = sf_half(c->F1); c->F3 = sf_half(c->F2);
-    for (auto& e : c->ev) HIP_CHECK(hipEventCreate(&e));
     *out = c.release();
     MIS_API_END
 }
@@ -582,21 +509,15 @@ extern "C" void mis_sortformer_destroy(mis_sortformer* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
 extern "C" mis_status mis_sortformer_set_tensor(mis_sortformer* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
-    MIS_REQUIRE(c && name && data && shape && ndim >= 1 && ndim <= 4, MIS_ERR_INVALID_INPUT, "bad argument");
-    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
+    set_tensor_check(c, name, data, shape, ndim, 4, c && c->finalized, dtype);
     c->raw.put(name, data, dtype, shape, ndim);
     MIS_API_END
 }
-
-static double sf_hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + log(f / 1000.0) / (log(6.4) / 27.0); }
-static double sf_mel_to_hz(double m) { return m < 15.0 ? (200.0 / 3.0) * m : 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)); }
 
 static void sf_gemm(mis_sortformer* c, SfGemm p, int B) {
     const dim3 grid(cdiv((int64_t)p.Tp * p.rowmul, 64), cdiv(p.N, 64), B);
@@ -622,122 +543,100 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
     const bool ab = c->cfg.attention_bias != 0, kb = c->cfg.k_proj_bias != 0;
     HostArena a(c->raw);
     std::vector<float>& fh = a.fhost;
-    const size_t npos = (size_t)-1;
     // ---- front end tables: window 400 -> 512, FFT twiddles, slaney filters [257][mels] and each filter's bin range
-    const size_t o_win = a.ftake(SF_NFFT), o_twc = a.ftake(SF_NFFT / 2), o_tws = a.ftake(SF_NFFT / 2);
-    for (int n = 0; n < SF_WIN; ++n) fh[o_win + (SF_NFFT - SF_WIN) / 2 + n] = 0.5f * (1.0f - (float)cos(2.0 * M_PI * (double)n / (double)(SF_WIN - 1)));
+    const size_t o_win = a.ftake(NEMO_NFFT, c->window), o_twc = a.ftake(NEMO_NFFT / 2, c->twc), o_tws = a.ftake(NEMO_NFFT / 2, c->tws);
+    hann_padded(&fh[o_win], NEMO_WIN, NEMO_NFFT);
     fft512_twiddles(&fh[o_twc], &fh[o_tws]);
-    const size_t o_fb = a.ftake((size_t)SF_BINS * mels);
+    const size_t o_fb = a.ftake((size_t)NEMO_BINS * mels, c->fb);
     std::vector<int> ranges(2 * mels, 0);
-    {
-        const double mmax = sf_hz_to_mel(8000.0);
-        std::vector<double> fp(mels + 2);
-        for (int i = 0; i < mels + 2; ++i) fp[i] = sf_mel_to_hz((double)i * mmax / (double)(mels + 1));
-        for (int j = 0; j < mels; ++j) {
-            const double lo = fp[j], ce = fp[j + 1], hi = fp[j + 2], enorm = 2.0 / (hi - lo);
-            for (int i = 0; i < SF_BINS; ++i) {
-                const double fr = (double)i * 16000.0 / SF_NFFT;
-                double w = 0.0;
-                if (fr >= lo && fr < ce) w = (fr - lo) / (ce - lo);
-                else if (fr >= ce && fr <= hi) w = (hi - fr) / (hi - ce);
-                fh[o_fb + (size_t)i * mels + j] = (float)(w * enorm);
-            }
-        }
-        filter_bin_ranges(&fh[o_fb], SF_BINS, (int)mels, ranges.data());
-    }
+    slaney_filterbank(&fh[o_fb], ranges.data(), NEMO_BINS, (int)mels, 16000.0, NEMO_NFFT);
     // ---- workspace extents
     c->maxN = (int64_t)c->cfg.max_seconds * 16000;
     c->Fcap = sf_frames(c->maxN, 16); c->T1cap = sf_half(c->Fcap); c->T2cap = sf_half(c->T1cap); c->Tcap = sf_half(c->T2cap);
     const int Tc = c->Tcap, NP = 2 * Tc - 1;
-    // ---- weights
-    struct LOff { size_t w, b; };
-    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias) {
-        LOff o{a.fvec(p + ".weight", {N, K}, N * K), npos};
-        if (bias) o.b = a.fvec(p + ".bias", {N}, N);
-        return o;
+    // ---- weights; an absent bias stays nullptr
+    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l) {
+        l = SfLin{};
+        a.fvec(p + ".weight", {N, K}, N * K, l.w);
+        if (bias) a.fvec(p + ".bias", {N}, N, l.b);
     };
     // three linears over the same input as one [N0 + N1 + N2][K]; an absent bias is zero
-    auto lin3 = [&](const std::string& p, const char* n0, const char* n1, const char* n2, int64_t N, bool b0, bool b1, bool b2) {
-        LOff o{a.ftake((size_t)3 * N * N), a.ftake(3 * N)};
+    auto lin3 = [&](const std::string& p, const char* n0, const char* n1, const char* n2, int64_t N, bool b0, bool b1, bool b2, SfLin& l) {
+        const size_t ow = a.ftake((size_t)3 * N * N, l.w), ob = a.ftake(3 * N, l.b);
         const char* names[3] = {n0, n1, n2};
         const bool has[3] = {b0, b1, b2};
         for (int i = 0; i < 3; ++i) {
             const HostTensor& w = c->raw.need(p + names[i] + ".weight", {N, N});
-            std::copy(w.v.begin(), w.v.end(), fh.begin() + o.w + (size_t)i * N * N);
-            if (has[i]) { const HostTensor& bb = c->raw.need(p + names[i] + ".bias", {N}); std::copy(bb.v.begin(), bb.v.end(), fh.begin() + o.b + (size_t)i * N); }
+            std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * N * N);
+            if (has[i]) { const HostTensor& bb = c->raw.need(p + names[i] + ".bias", {N}); std::copy(bb.v.begin(), bb.v.end(), fh.begin() + ob + (size_t)i * N); }
         }
-        return o;
     };
-    auto norm = [&](const std::string& p, int64_t n, size_t& w, size_t& b) { w = a.fvec(p + ".weight", {n}, n); b = a.fvec(p + ".bias", {n}, n); };
+    auto norm = [&](const std::string& p, int64_t n, const float*& w, const float*& b) { a.fvec(p + ".weight", {n}, n, w); a.fvec(p + ".bias", {n}, n, b); };
     const std::string SUB = "fc_encoder.subsampling.";
     // conv taps [C][3][3][1] -> [9][C]
-    auto taps9 = [&](const std::string& name) {
+    auto taps9 = [&](const std::string& name, const float*& dst) {
         const HostTensor& t = c->raw.need(name, {C, 3, 3, 1});
-        const size_t off = a.ftake(9 * C);
+        const size_t off = a.ftake(9 * C, dst);
         for (int64_t ch = 0; ch < C; ++ch) for (int k = 0; k < 9; ++k) fh[off + k * C + ch] = t.v[ch * 9 + k];
-        return off;
     };
-    const size_t o_c0w = taps9(SUB + "layers_0.weight"), o_c0b = a.fvec(SUB + "layers_0.bias", {C}, C);
-    const size_t o_d2w = taps9(SUB + "layers_2.weight"), o_d2b = a.fvec(SUB + "layers_2.bias", {C}, C);
-    const LOff o_p3{a.fvec(SUB + "layers_3.weight", {C, 1, 1, C}, C * C), a.fvec(SUB + "layers_3.bias", {C}, C)};
-    const size_t o_d5w = taps9(SUB + "layers_5.weight"), o_d5b = a.fvec(SUB + "layers_5.bias", {C}, C);
-    const LOff o_p6{a.fvec(SUB + "layers_6.weight", {C, 1, 1, C}, C * C), a.fvec(SUB + "layers_6.bias", {C}, C)};
+    taps9(SUB + "layers_0.weight", c->c0w); a.fvec(SUB + "layers_0.bias", {C}, C, c->c0b);
+    taps9(SUB + "layers_2.weight", c->dw2w); a.fvec(SUB + "layers_2.bias", {C}, C, c->dw2b);
+    a.fvec(SUB + "layers_3.weight", {C, 1, 1, C}, C * C, c->pw3.w); a.fvec(SUB + "layers_3.bias", {C}, C, c->pw3.b);
+    taps9(SUB + "layers_5.weight", c->dw5w); a.fvec(SUB + "layers_5.bias", {C}, C, c->dw5b);
+    a.fvec(SUB + "layers_6.weight", {C, 1, 1, C}, C * C, c->pw6.w); a.fvec(SUB + "layers_6.bias", {C}, C, c->pw6.b);
     // linear [d][C F3] reads the flattening (c, f); the stem keeps channels last, so its columns are re-ordered to (f, c) once, here
-    LOff o_lin{a.ftake((size_t)d * C * F3), a.fvec(SUB + "linear.bias", {d}, d)};
     {
+        const size_t ow = a.ftake((size_t)d * C * F3, c->lin.w);
+        a.fvec(SUB + "linear.bias", {d}, d, c->lin.b);
         const HostTensor& w = c->raw.need(SUB + "linear.weight", {d, C * F3});
         for (int64_t n = 0; n < d; ++n) for (int64_t ch = 0; ch < C; ++ch) for (int64_t fq = 0; fq < F3; ++fq)
-            fh[o_lin.w + (n * F3 + fq) * C + ch] = w.v[n * C * F3 + ch * F3 + fq];
+            fh[ow + (n * F3 + fq) * C + ch] = w.v[n * C * F3 + ch * F3 + fq];
     }
-    struct FcOff { size_t n[10], u, v, rk, dw, sh; LOff ff1a, ff1b, qkv, o, pw1, pw2, ff2a, ff2b; };
-    std::vector<FcOff> fo(c->L);
+    c->fc.assign(c->L, SfFcLayer{});
+    std::vector<SfLin> rk(c->L);                         // relative_k_proj: used once, below
     for (int li = 0; li < c->L; ++li) {
         const std::string q = "fc_encoder.layers." + std::to_string(li) + ".";
-        FcOff& o = fo[li];
-        norm(q + "norm_feed_forward1", d, o.n[0], o.n[1]);
-        o.ff1a = lin(q + "feed_forward1.linear1", f, d, true); o.ff1b = lin(q + "feed_forward1.linear2", d, f, true);
-        norm(q + "norm_self_att", d, o.n[2], o.n[3]);
-        o.qkv = lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", d, ab, ab, ab);
-        o.o = lin(q + "self_attn.o_proj", d, d, ab);
-        o.rk = a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d);
-        o.u = a.fvec(q + "self_attn.bias_u", {H, hd}, d); o.v = a.fvec(q + "self_attn.bias_v", {H, hd}, d);
-        norm(q + "norm_conv", d, o.n[4], o.n[5]);
-        o.pw1 = LOff{a.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d), a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d)};
-        o.pw2 = LOff{a.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d), a.fvec(q + "conv.pointwise_conv2.bias", {d}, d)};
-        // inference BatchNorm (eps 1e-5) folded into the depthwise taps and a shift
+        SfFcLayer& l = c->fc[li];
+        norm(q + "norm_feed_forward1", d, l.ln1w, l.ln1b);
+        lin(q + "feed_forward1.linear1", f, d, true, l.ff1a); lin(q + "feed_forward1.linear2", d, f, true, l.ff1b);
+        norm(q + "norm_self_att", d, l.lnaw, l.lnab);
+        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", d, ab, ab, ab, l.qkv);
+        lin(q + "self_attn.o_proj", d, d, ab, l.o);
+        a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, rk[li].w);
+        a.fvec(q + "self_attn.bias_u", {H, hd}, d, l.u); a.fvec(q + "self_attn.bias_v", {H, hd}, d, l.v);
+        norm(q + "norm_conv", d, l.lncw, l.lncb);
+        a.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w); a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d, l.pw1.b);
+        a.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w); a.fvec(q + "conv.pointwise_conv2.bias", {d}, d, l.pw2.b);
+        // inference BatchNorm folded into the depthwise taps and a shift
         const HostTensor& dw = c->raw.need(q + "conv.depthwise_conv.weight", {d, ck, 1});
         const HostTensor& dwb = c->raw.need(q + "conv.depthwise_conv.bias", {d});
         const HostTensor& bw = c->raw.need(q + "conv.norm.weight", {d}); const HostTensor& bb = c->raw.need(q + "conv.norm.bias", {d});
         const HostTensor& bm = c->raw.need(q + "conv.norm.running_mean", {d}); const HostTensor& bv = c->raw.need(q + "conv.norm.running_var", {d});
-        o.dw = a.ftake((size_t)ck * d); o.sh = a.ftake(d);
-        for (int64_t ch = 0; ch < d; ++ch) {
-            const float scale = bw.v[ch] / sqrtf(bv.v[ch] + 1e-5f);
-            for (int64_t k = 0; k < ck; ++k) fh[o.dw + k * d + ch] = dw.v[ch * ck + k] * scale;
-            fh[o.sh + ch] = (dwb.v[ch] - bm.v[ch]) * scale + bb.v[ch];
-        }
-        norm(q + "norm_feed_forward2", d, o.n[6], o.n[7]);
-        o.ff2a = lin(q + "feed_forward2.linear1", f, d, true); o.ff2b = lin(q + "feed_forward2.linear2", d, f, true);
-        norm(q + "norm_out", d, o.n[8], o.n[9]);
+        const size_t o_dw = a.ftake((size_t)ck * d, l.dw), o_sh = a.ftake(d, l.dwshift);
+        fold_bn_dwconv(&fh[o_dw], &fh[o_sh], dw.v.data(), dwb.v.data(), bw.v.data(), bb.v.data(), bm.v.data(), bv.v.data(), d, ck);
+        norm(q + "norm_feed_forward2", d, l.ln2w, l.ln2b);
+        lin(q + "feed_forward2.linear1", f, d, true, l.ff2a); lin(q + "feed_forward2.linear2", d, f, true, l.ff2b);
+        norm(q + "norm_out", d, l.lnow, l.lnob);
     }
     const int64_t msp = c->cfg.max_source_positions;
-    const size_t o_pos = a.fvec("tf_encoder.embed_positions.weight", {msp, dt}, msp * dt);
-    struct TfOff { LOff qkv, o, fc1, fc2; size_t n[4]; };
-    std::vector<TfOff> to(c->Lt);
+    a.fvec("tf_encoder.embed_positions.weight", {msp, dt}, msp * dt, c->pos);
+    c->tf.assign(c->Lt, SfTfLayer{});
     for (int li = 0; li < c->Lt; ++li) {
         const std::string q = "tf_encoder.layers." + std::to_string(li) + ".";
-        TfOff& o = to[li];
-        o.qkv = lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", dt, true, kb, true);
-        o.o = lin(q + "self_attn.out_proj", dt, dt, true);
-        norm(q + "self_attn_layer_norm", dt, o.n[0], o.n[1]);
-        o.fc1 = lin(q + "fc1", ft, dt, true); o.fc2 = lin(q + "fc2", dt, ft, true);
-        norm(q + "final_layer_norm", dt, o.n[2], o.n[3]);
+        SfTfLayer& l = c->tf[li];
+        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", dt, true, kb, true, l.qkv);
+        lin(q + "self_attn.out_proj", dt, dt, true, l.o);
+        norm(q + "self_attn_layer_norm", dt, l.ln1w, l.ln1b);
+        lin(q + "fc1", ft, dt, true, l.fc1); lin(q + "fc2", dt, ft, true, l.fc2);
+        norm(q + "final_layer_norm", dt, l.ln2w, l.ln2b);
     }
     const std::string SM = "sortformer_modules.";
-    const LOff o_proj = lin(SM + "encoder_proj", dt, d, true), o_h2h = lin(SM + "first_hidden_to_hidden", dt, dt, true),
-               o_spk = lin(SM + "single_hidden_to_spks", S, dt, true);
+    lin(SM + "encoder_proj", dt, d, true, c->proj); lin(SM + "first_hidden_to_hidden", dt, dt, true, c->h2h);
+    lin(SM + "single_hidden_to_spks", S, dt, true, c->spk);
     c->raw.need(SM + "hidden_to_spks.weight", {S, 2 * dt}); c->raw.need(SM + "hidden_to_spks.bias", {S});   // loaded and checked, unused
     // ---- the sinusoid table by distance: row d + Tcap - 1, columns interleaved sin, cos; formed in double, rounded once
-    const size_t o_tab = a.ftake((size_t)NP * d);
+    const float* tab = nullptr;
+    const size_t o_tab = a.ftake((size_t)NP * d, tab);
     for (int r = 0; r < NP; ++r) {
         const double dist = (double)(r - (Tc - 1));
         for (int64_t k = 0; 2 * k < d; ++k) {
@@ -746,37 +645,17 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
             if (2 * k + 1 < d) fh[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
         }
     }
-    // ---- upload
+    // ---- upload: every pointer bound above now addresses the device arena
     DevBuf<bf16_t> none;
     a.upload(none, c->farena);
-    const float* A = c->farena.p;
-    auto P = [&](size_t off) { return off == npos ? (const float*)nullptr : A + off; };
-    auto LN = [&](const LOff& o) { SfLin l; l.w = P(o.w); l.b = P(o.b); return l; };
-    c->window = P(o_win); c->twc = P(o_twc); c->tws = P(o_tws); c->fb = P(o_fb);
     c->fbr.alloc(2 * mels);
     HIP_CHECK(hipMemcpy(c->fbr.p, ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
-    c->c0w = P(o_c0w); c->c0b = P(o_c0b); c->dw2w = P(o_d2w); c->dw2b = P(o_d2b); c->dw5w = P(o_d5w); c->dw5b = P(o_d5b); c->pos = P(o_pos);
-    c->pw3 = LN(o_p3); c->pw6 = LN(o_p6); c->lin = LN(o_lin); c->proj = LN(o_proj); c->h2h = LN(o_h2h); c->spk = LN(o_spk);
+    // each layer's relative_k_proj of the table: one GEMM, once
     c->ptab.alloc((size_t)c->L * NP * d);
-    c->fc.resize(c->L);
     for (int li = 0; li < c->L; ++li) {
-        const FcOff& o = fo[li];
-        SfFcLayer& l = c->fc[li];
-        l.ln1w = P(o.n[0]); l.ln1b = P(o.n[1]); l.lnaw = P(o.n[2]); l.lnab = P(o.n[3]); l.lncw = P(o.n[4]); l.lncb = P(o.n[5]);
-        l.ln2w = P(o.n[6]); l.ln2b = P(o.n[7]); l.lnow = P(o.n[8]); l.lnob = P(o.n[9]); l.u = P(o.u); l.v = P(o.v); l.dw = P(o.dw); l.dwshift = P(o.sh);
-        l.ff1a = LN(o.ff1a); l.ff1b = LN(o.ff1b); l.qkv = LN(o.qkv); l.o = LN(o.o); l.pw1 = LN(o.pw1); l.pw2 = LN(o.pw2); l.ff2a = LN(o.ff2a); l.ff2b = LN(o.ff2b);
-        // this layer's relative_k_proj of the table: one GEMM, once
         float* dst = c->ptab.p + (size_t)li * NP * d;
-        SfLin rk; rk.w = P(o.rk);
-        sf_gemm(c, sf_lin(P(o_tab), (int)d, rk, dst, (int)d, nullptr, NP), 1);
-        l.P = dst;
-    }
-    c->tf.resize(c->Lt);
-    for (int li = 0; li < c->Lt; ++li) {
-        const TfOff& o = to[li];
-        SfTfLayer& l = c->tf[li];
-        l.qkv = LN(o.qkv); l.o = LN(o.o); l.fc1 = LN(o.fc1); l.fc2 = LN(o.fc2);
-        l.ln1w = P(o.n[0]); l.ln1b = P(o.n[1]); l.ln2w = P(o.n[2]); l.ln2b = P(o.n[3]);
+        sf_gemm(c, sf_lin(tab, (int)d, rk[li], dst, (int)d, nullptr, NP), 1);
+        c->fc[li].P = dst;
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -896,9 +775,9 @@ static void sf_front(mis_sortformer* c, const float* pcm, const int64_t* lens, i
     HIP_CHECK(hipMemcpy2DAsync(c->pcm.p, ws * 4, pcm, stride * 4, ws * 4, batch, hipMemcpyDefault, s));
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[0], s));
     MIS_LAUNCH(c, k_sf_peak, dim3(batch), dim3(256), c->pcm.p, ws, c->cntN.p, peak, c->scale.p);
-    MIS_LAUNCH(c, k_sf_stft_mel, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF0.p, c->scale.p, c->cfg.preemphasis, c->window, c->twc, c->tws,
+    MIS_LAUNCH(c, k_nemo_log_mel<true>, dim3(Fp, batch), dim3(256), c->pcm.p, ws, c->cntN.p, c->cntF0.p, c->scale.p, c->cfg.preemphasis, c->window, c->twc, c->tws,
               c->fb, c->fbr.p, c->melraw.p, Fp, c->mels);
-    MIS_LAUNCH(c, k_sf_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF0.p, c->feats.p, Fp, c->mels, normalize);
+    MIS_LAUNCH(c, k_nemo_norm, dim3(cdiv(c->mels, 64), batch), dim3(256), c->melraw.p, c->cntF0.p, c->feats.p, Fp, c->mels, normalize);
 }
 
 // c->feats -> c->emb [B][Tp][d] (ConvSubsampling), 4 launches

@@ -1,6 +1,8 @@
 // Stand-alone check of csrc/host_weights.h (test_host_weights_cpu.py builds it with the address and undefined-behaviour sanitizers and
-// runs it): the weight stash, the bf16 / f32 arena, the exact-f32 codec arena and its re-layouts, the synthetic tensors.  Host code only: no HIP call is made, no device is opened.
+// runs it): the weight stash, the bf16 / f32 arena and its bindings, the BatchNorm fold, the exact-f32 codec arena and its re-layouts, the
+// synthetic tensors; the host tables of the NeMo front end (csrc/audio_front.h).  Host code only: no HIP call is made, no device is opened.
 #include "../mlx-audio-swift_amd/csrc/host_weights.h"
+#include "../mlx-audio-swift_amd/csrc/audio_front.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -134,6 +136,82 @@ int main() {
         CHECK(code == (int)MIS_ERR_INVALID_INPUT && m == "DAC weight v has the wrong shape" && a.host.size() == 384);
         m = thrown([&] { a.fvec("nope", {1}, 1); }, &code);
         CHECK(code == (int)MIS_ERR_NOT_INITIALIZED && m == "DAC weight missing: nope");
+    }
+    {   // bindings: resolve() writes base + offset into every bound pointer, each arena from its own base; the takes are the plain ones
+        HostArena a(w);
+        struct { bf16_t *v = nullptr, *m = nullptr, *pad = nullptr, *tied = nullptr, *absent = nullptr; float* f = nullptr; const float *cf = nullptr, *cabs = nullptr; } dst;
+        float* local = nullptr;
+        CHECK(a.btake(1, dst.pad) == 0 && a.bvec("v", 5, dst.v) == 64 && a.btake(3) == 128 && a.bmat("m", 2, 3, dst.m) == 192 && a.host.size() == 256);
+        a.bind(dst.tied, 64);                                      // one offset, two destinations
+        CHECK(a.ftake(65, dst.f) == 0 && a.fvec("m", {2, 3}, 4, dst.cf) == 128 && a.ftake(2, local) == 192 && a.fhost.size() == 256);
+        CHECK(a.host[64] == 0x3f80 && a.host[192] == f32_to_bf16(0.5f) && bits(a.fhost[129]) == bits(-2.0f));
+        for (size_t i = 0; i < a.host.size(); ++i) if (!(i >= 64 && i < 69) && !(i >= 192 && i < 198)) CHECK(a.host[i] == 0);
+        for (size_t i = 0; i < a.fhost.size(); ++i) if (!(i >= 128 && i < 132)) CHECK(bits(a.fhost[i]) == 0u);
+        CHECK(!dst.v && !dst.f && !local);                          // nothing is written before resolve
+        std::vector<bf16_t> A(256);
+        std::vector<float> F(256);
+        a.resolve(A.data(), F.data());
+        CHECK(dst.pad == A.data() && dst.v == A.data() + 64 && dst.tied == A.data() + 64 && dst.m == A.data() + 192);
+        CHECK(dst.f == F.data() && dst.cf == F.data() + 128 && local == F.data() + 192);
+        CHECK(dst.absent == nullptr && dst.cabs == nullptr);
+        std::vector<bf16_t> A2(256);
+        a.resolve(A2.data(), F.data() + 7);                         // the two bases are independent
+        CHECK(dst.v == A2.data() + 64 && dst.cf == F.data() + 7 + 128 && local == F.data() + 7 + 192 && dst.absent == nullptr);
+        static_assert(!std::is_copy_constructible<HostArena>::value && !std::is_copy_assignable<HostArena>::value, "HostArena holds addresses");
+    }
+    for (bool with_bias : {false, true}) {   // fold_bn_dwconv against its formula: f32, eps 1e-5
+        const int64_t d = 5, k = 3;
+        std::vector<float> dw(d * k), db(d), bw(d), bb(d), mu(d), var(d), taps(k * d + 1, 7.0f), shift(d + 1, 7.0f);
+        for (int64_t i = 0; i < d * k; ++i) dw[i] = mis_synth_value(21, i, 1.0f);
+        for (int64_t i = 0; i < d; ++i) {
+            db[i] = mis_synth_value(22, i, 0.1f); bw[i] = 1.0f + mis_synth_value(23, i, 0.1f); bb[i] = mis_synth_value(24, i, 0.1f);
+            mu[i] = mis_synth_value(25, i, 0.1f); var[i] = 1.0f + mis_synth_value(26, i, 0.3f);
+        }
+        fold_bn_dwconv(taps.data(), shift.data(), dw.data(), with_bias ? db.data() : nullptr, bw.data(), bb.data(), mu.data(), var.data(), d, k);
+        for (int64_t ch = 0; ch < d; ++ch) {
+            const float scale = bw[ch] / sqrtf(var[ch] + 1e-5f);
+            for (int64_t j = 0; j < k; ++j) CHECK(bits(taps[j * d + ch]) == bits(dw[ch * k + j] * scale));
+            CHECK(bits(shift[ch]) == bits(((with_bias ? db[ch] : 0.0f) - mu[ch]) * scale + bb[ch]));
+        }
+        CHECK(taps[k * d] == 7.0f && shift[d] == 7.0f);
+    }
+    {   // the NeMo front end's tables against their formulas, in double: Hann 400 in 512, slaney filters for 80 and 128 mels
+        std::vector<float> win(513, 7.0f);
+        hann_padded(win.data(), 400, 512);
+        for (int n = 0; n < 512; ++n) {
+            const int i = n - 56;
+            const float want = (i >= 0 && i < 400) ? 0.5f * (1.0f - (float)cos(2.0 * 3.14159265358979323846 * (double)i / 399.0)) : 0.0f;
+            CHECK(bits(win[n]) == bits(want));
+        }
+        CHECK(win[512] == 7.0f && win[56] == 0.0f && win[455] == 0.0f && win[57] > 0.0f && win[256] > 0.9999f);
+        for (int mels : {80, 128}) {
+            const int bins = 257;
+            std::vector<float> fb((size_t)bins * mels + 1, 7.0f);
+            std::vector<int> ranges(2 * mels + 1, -5), want_ranges(2 * mels, -5);
+            slaney_filterbank(fb.data(), ranges.data(), bins, mels, 16000.0, 512);
+            auto h2m = [](double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + 27.0 * log(f / 1000.0) / log(6.4); };
+            auto m2h = [](double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * exp(log(6.4) * (m - 15.0) / 27.0); };
+            double worst = 0.0;
+            for (int j = 0; j < mels; ++j) {
+                const double lo = m2h(j * h2m(8000.0) / (mels + 1)), ce = m2h((j + 1) * h2m(8000.0) / (mels + 1)), hi = m2h((j + 2) * h2m(8000.0) / (mels + 1));
+                double area = 0.0;
+                for (int i = 0; i < bins; ++i) {
+                    const double fr = i * 31.25, tri = std::max(0.0, std::min((fr - lo) / (ce - lo), (hi - fr) / (hi - ce))), want = tri * 2.0 / (hi - lo);
+                    const double got = fb[(size_t)i * mels + j];
+                    worst = std::max(worst, fabs(got - want) / std::max(want, 1e-30) * (want > 1e-12 ? 1.0 : 0.0));
+                    CHECK(fabs(got - want) <= 1e-6 * want + 1e-12);           // one rounding to f32 (2^-24) and a few ulps of double
+                    CHECK((got != 0.0) == (fr > lo && fr < hi));
+                    area += got * 31.25;
+                }
+                // slaney normalisation: unit area up to the sampling of the triangle at 31.25 Hz (exact for an integrand linear between
+                // the bins; the kinks at lo, ce and hi cost at most three trapezoid corners)
+                CHECK(fabs(area - 1.0) < 3.0 * 31.25 / (hi - lo) + 1e-5);
+            }
+            CHECK(worst < 1e-6 && fb[(size_t)bins * mels] == 7.0f && ranges[2 * mels] == -5);
+            filter_bin_ranges(fb.data(), bins, mels, want_ranges.data());
+            for (int i = 0; i < 2 * mels; ++i) CHECK(ranges[i] == want_ranges[i]);
+            for (int j = 0; j < mels; ++j) CHECK(ranges[2 * j] >= 1 && ranges[2 * j] < ranges[2 * j + 1] && ranges[2 * j + 1] <= bins);
+        }
     }
     {   // F32Arena::push: offsets count floats, zero padding to a multiple of 4 after every push
         F32Arena a;

@@ -1,7 +1,10 @@
 """csrc/host_weights.h - the host weight stash every codec / STT / VAD engine stages its checkpoint in, the host arena builder and the
 synthetic-tensor helper - checked by a stand-alone program (tests/host_weights_main.cpp) built with the address and undefined-behaviour
 sanitizers: dtype widening against constants, need()'s statuses and messages, shape rejection, replacement, arena offsets / zero fill /
-round-to-nearest-even, the synthetic key sequence; the codec engines' F32Arena (offsets, zero padding, lin / conv and their messages) and
+round-to-nearest-even, the arena's bindings (resolve() against fake bases: base + offset for every bound pointer, nullptr for an
+unbound one, one offset bound twice, the two arenas independently), fold_bn_dwconv with and without a conv bias, the NeMo front end's
+host tables of csrc/audio_front.h (hann_padded, slaney_filterbank at 80 and 128 mels against the formulas in double, the ranges against
+filter_bin_ranges), the synthetic key sequence; the codec engines' F32Arena (offsets, zero padding, lin / conv and their messages) and
 the weight re-layouts and quantiser-table fold, each against its index formula written out.  Host code only; no device is opened."""
 import os
 import shutil

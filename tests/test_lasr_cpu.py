@@ -234,13 +234,13 @@ def usage():
 
 
 def test_lasr_kernels_do_not_spill(usage):
-    """No kernel of lasr.hip uses scratch.  The attention kernel stays within 128 VGPRs (four of its 256-thread blocks' waves per SIMD),
-    the GLU + depthwise kernel within 64 (its 16 accumulators, not its up to 64 taps, live in registers) with the 32.5 KB tile + halo
-    in LDS."""
-    names = {re.search(r"k_lasr_[a-z_0-9]+?(?=I|P)", k).group(0) for k in usage if "k_lasr_" in k}
-    assert {"k_lasr_attn", "k_lasr_glu_dwconv", "k_lasr_gemm", "k_lasr_stft_mel", "k_lasr_norm", "k_lasr_collapse"} <= names, names
+    """No kernel of lasr.hip uses scratch, the log-mel front end it shares with sortformer.hip (k_nemo_*, csrc/audio_front.h) included.
+    The attention kernel stays within 128 VGPRs (four of its 256-thread blocks' waves per SIMD), the GLU + depthwise kernel within 64
+    (its 16 accumulators, not its up to 64 taps, live in registers) with the 32.5 KB tile + halo in LDS."""
+    names = {re.search(r"k_(lasr|nemo)_[a-z_0-9]+?(?=I|P)", k).group(0) for k in usage if "k_lasr_" in k or "k_nemo_" in k}
+    assert {"k_lasr_attn", "k_lasr_glu_dwconv", "k_lasr_gemm", "k_nemo_log_mel", "k_nemo_norm", "k_lasr_collapse"} <= names, names
     for k, v in usage.items():
-        if "k_lasr_" in k:
+        if "k_lasr_" in k or "k_nemo_" in k:
             assert v["scratch"] == 0, (k, v)
     attn = [v for k, v in usage.items() if "k_lasr_attn" in k]
     dw = [v for k, v in usage.items() if "k_lasr_glu_dwconv" in k]

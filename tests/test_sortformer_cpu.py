@@ -338,9 +338,10 @@ def usage():
 
 
 def test_kernel_resources(usage):
-    """No kernel of sortformer.hip uses scratch.  Every instance of the attention kernel stays within 128 VGPRs, and its LDS within the
+    """No kernel of sortformer.hip uses scratch, the log-mel front end it shares with lasr.hip (k_nemo_*, csrc/audio_front.h) included.  Every instance of the attention kernel stays within 128 VGPRs, and its LDS within the
     figure the file's header derives for head size 64 with the band: (64 x 65 + 2 x 32 x 65 + 2 x 64 + 96 x 65) floats = 58752 bytes."""
-    mine = {k: v for k, v in usage.items() if "k_sf_" in k}
+    mine = {k: v for k, v in usage.items() if "k_sf_" in k or "k_nemo_" in k}
+    assert sum("k_nemo_" in k for k in mine) == 2, mine
     assert len(mine) >= 15 and all(v["scratch"] == 0 for v in mine.values()), mine
     attn = {k: v for k, v in mine.items() if "k_sf_attn" in k}
     assert len(attn) == 4 and all(v["vgprs"] <= 128 for v in attn.values()), attn
