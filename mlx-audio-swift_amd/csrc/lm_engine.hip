@@ -12,11 +12,11 @@
 #include "kernels.h"
 #include "lm_kernels.h"
 #include "step_loop.h"
+#include "lm_request.h"
 
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <chrono>
 #include <functional>
 #include <set>
 
@@ -1171,7 +1171,9 @@ __global__ void k_collect_hidden(const bf16_t* __restrict__ x, const uint8_t* __
 struct HiddenMode {            // Soprano: collect model.norm(h) per step instead of decoding SNAC frames
     bool on = false;
     int stop_id = -1;
-    DevBuf<float>* hidden = nullptr;      // [batch][max_tokens + 1][d]
+    DevBuf<float>* hidden = nullptr;      // [batch][rows = max_tokens + 1][d]
+    DevBuf<int32_t> count;                // [batch] slots filled
+    int64_t rows = 0;
     std::vector<int32_t> n_hidden;
 };
 
@@ -1179,103 +1181,91 @@ struct HiddenMode {            // Soprano: collect model.norm(h) per step instea
 // holds compute units).  Thrown at the poll that sees the flag, before any token of that poll interval reaches the callback.
 struct SamplerTimeout {};
 
-// One attempt of generate.  `multi_launch_only`: the sampler's multi-launch kernels (no kernel of the step waits for another block).
-// `emitted[b]`: tokens of row b already announced to the callback - by this attempt or by the one before it (the request is
-// deterministic: prompts, seeds and the RNG counter are the same, so a second attempt reproduces them and continues behind them).
-static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const int32_t* prompt_lens, int batch,
-                                 const mis_gen_params* gp, const float* const* snac_noise, float* pcm_dev, int64_t pcm_stride,
-                                 bool want_tokens, mis_event_cb cb, void* user, const volatile int* cancel, GenOutputs& out,
-                                 HiddenMode* hm, bool multi_launch_only, std::vector<int32_t>& emitted) {
-    MIS_REQUIRE(c && c->finalized, MIS_ERR_NOT_INITIALIZED, "model not initialized");
-    const bool hidden_mode = hm && hm->on;
-    MIS_REQUIRE(hidden_mode || c->codec, MIS_ERR_NOT_INITIALIZED, "SNAC model not loaded");            // LlamaTTS.swift:672-674
-    MIS_REQUIRE(prompt_ids && prompt_lens && gp, MIS_ERR_INVALID_INPUT, "null argument");
-    MIS_REQUIRE(batch >= 1 && batch <= 64, MIS_ERR_INVALID_INPUT, "batch per GPU must be 1..64");
-    const mis_snac_config* sc = hidden_mode ? nullptr : snac_config(c->codec);
-    MIS_REQUIRE(hidden_mode || (sc->n_codebooks == 3 && sc->vq_strides[0] == 4 && sc->vq_strides[1] == 2 &&
-                                sc->vq_strides[2] == 1 && sc->codebook_size == 4096),
-                MIS_ERR_INVALID_INPUT, "Orpheus framing needs a 3-level 4/2/1 SNAC codec with 4096-entry codebooks");
-    HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int max_tokens = gp->max_tokens > 0 ? gp->max_tokens : 1200;
-    std::vector<int32_t> lens(batch);
-    HIP_CHECK(hipMemcpy(lens.data(), prompt_lens, batch * 4, hipMemcpyDefault));
-    int Lmax = 0;
-    size_t total = 0;
-    for (int b = 0; b < batch; ++b) {
-        MIS_REQUIRE(lens[b] >= 1, MIS_ERR_INVALID_INPUT, "empty prompt in row %d", b);
-        Lmax = std::max(Lmax, lens[b]);
-        total += lens[b];
-    }
-    std::vector<int32_t> flat(total);
-    HIP_CHECK(hipMemcpy(flat.data(), prompt_ids, total * 4, hipMemcpyDefault));
-    for (auto t : flat) MIS_REQUIRE(t >= 0 && t < c->V, MIS_ERR_INVALID_INPUT, "prompt token %d outside the vocabulary", t);
-    const int ctx = std::max(gp->repetition_context, 0);
-    const int all_stride = Lmax + max_tokens;
-    lm_reset(c, batch, Lmax + max_tokens + 1);
+static int default_max_tokens(const mis_gen_params* gp) { return gp->max_tokens > 0 ? gp->max_tokens : 1200; }
 
-    // host-built state: left-padded prompt matrix, all_ids (prompt, left-aligned), repetition windows
-    std::vector<int32_t> pm((size_t)batch * Lmax, 0), all((size_t)batch * all_stride, 0), win((size_t)batch * std::max(ctx, 1), 0),
-        wl(batch, 0), alen(batch);
-    {
-        size_t off = 0;
-        for (int b = 0; b < batch; ++b) {
-            for (int j = 0; j < lens[b]; ++j) {
-                pm[(size_t)b * Lmax + (Lmax - lens[b]) + j] = flat[off + j];
-                all[(size_t)b * all_stride + j] = flat[off + j];
-            }
-            int w = std::min(ctx, lens[b]);                 // processor.prompt(promptTokens), LlamaTTS.swift:695-696
-            if (gp->sampler_flavor == 1) w = 0;             // Soprano penalises generated tokens only (Soprano.swift:833-848)
-            for (int j = 0; j < w; ++j) win[(size_t)b * ctx + (ctx - w) + j] = flat[off + lens[b] - w + j];
-            wl[b] = w;
-            alen[b] = lens[b];
-            off += lens[b];
-        }
-    }
-    c->prompt_mat.alloc(pm.size()); c->prompt_lens.alloc(batch); c->step_counter.alloc(1);
-    c->window.alloc(win.size()); c->window_len.alloc(batch); c->n_gen.alloc(batch);
-    c->tokens_out.alloc((size_t)batch * max_tokens); c->all_ids.alloc(all.size()); c->all_len.alloc(batch);
+// prompt_lens (host or device memory) on the host: once per entry point, handed down from there
+static std::vector<int32_t> host_prompt_lens(const int32_t* prompt_lens, int batch) {
+    MIS_REQUIRE(prompt_lens && batch >= 1, MIS_ERR_INVALID_INPUT, "null argument");
+    std::vector<int32_t> lens(batch);
+    HIP_CHECK(hipMemcpy(lens.data(), prompt_lens, (size_t)batch * 4, hipMemcpyDefault));
+    return lens;
+}
+
+// the request's device state: ten buffers, six uploads, four cleared; host arrays may be dropped when it returns
+static void upload_request(mis_tts* c, const LmRequest& req, const std::vector<int32_t>& lens, int max_tokens) {
+    const int batch = (int)lens.size();
+    hipStream_t s = c->stream;
+    c->prompt_mat.alloc(req.pm.size()); c->prompt_lens.alloc(batch); c->step_counter.alloc(1);
+    c->window.alloc(req.win.size()); c->window_len.alloc(batch); c->n_gen.alloc(batch);
+    c->tokens_out.alloc((size_t)batch * max_tokens); c->all_ids.alloc(req.all.size()); c->all_len.alloc(batch);
     c->done_count.alloc(1);
-    HIP_CHECK(hipMemcpyAsync(c->prompt_mat.p, pm.data(), pm.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->prompt_mat.p, req.pm.data(), req.pm.size() * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(c->prompt_lens.p, lens.data(), batch * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(c->window.p, win.data(), win.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(c->window_len.p, wl.data(), batch * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(c->all_ids.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(c->all_len.p, alen.data(), batch * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->window.p, req.win.data(), req.win.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->window_len.p, req.wl.data(), batch * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->all_ids.p, req.all.data(), req.all.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->all_len.p, req.alen.data(), batch * 4, hipMemcpyHostToDevice, s));
     c->step_counter.zero(s); c->n_gen.zero(s); c->done_count.zero(s); c->tokens_out.zero(s);
     HIP_CHECK(hipStreamSynchronize(s));
+}
 
+// sp: value-initialised by the caller (the graph key hashes its bytes, padding included)
+static void make_sampler_params(mis_tts* c, const mis_gen_params* gp, const LmRequest& req, int batch, int max_tokens,
+                                const HiddenMode* hm, bool multi_launch_only, SamplerParams& sp) {
     c->samp_scratch.alloc(batch);
-    sampler_scratch_init(c->samp_scratch.p, batch, s);
-    SamplerParams sp{};
+    sampler_scratch_init(c->samp_scratch.p, batch, c->stream);
     sp.scratch = c->samp_scratch.p;
     sampler_plan(c->V, &sp.n_chunks, &sp.chunk_w);
     sp.logits = c->logits.p; sp.e_buf = c->e_buf.p; sp.Vpad = c->Vpad; sp.vocab = c->V;
-    sp.active_in = c->active.p; sp.window = ctx > 0 ? c->window.p : nullptr; sp.window_len = c->window_len.p; sp.ctx = ctx;
+    sp.active_in = c->active.p; sp.window = req.ctx > 0 ? c->window.p : nullptr; sp.window_len = c->window_len.p; sp.ctx = req.ctx;
     sp.n_gen = c->n_gen.p; sp.tokens_out = c->tokens_out.p; sp.tokens_stride = max_tokens;
-    sp.all_ids = c->all_ids.p; sp.all_len = c->all_len.p; sp.all_stride = all_stride;
+    sp.all_ids = c->all_ids.p; sp.all_len = c->all_len.p; sp.all_stride = req.all_stride;
     sp.next_ids = c->ids.p; sp.active = c->active.p; sp.done_count = c->done_count.p;
     sp.temperature = gp->temperature; sp.top_p = gp->top_p; sp.penalty = gp->repetition_penalty;
     sp.seed = gp->seed; sp.row_offset = gp->row_offset; sp.frame_constrained = gp->frame_constrained;
     sp.lo = 0; sp.hi = 0; sp.max_tokens = max_tokens;
-    sp.eos_id = hidden_mode ? hm->stop_id : (c->cfg.end_of_speech_id > 0 ? c->cfg.end_of_speech_id : ORPHEUS_END_OF_SPEECH);
+    sp.eos_id = hm ? hm->stop_id : (c->cfg.end_of_speech_id > 0 ? c->cfg.end_of_speech_id : ORPHEUS_END_OF_SPEECH);
     sp.audio_offset = c->cfg.audio_token_offset;
     if (gp->sampler_flavor == 1) {
         c->samp_l32.alloc((size_t)c->Mpad * c->Vpad);
         sp.penalty_flavor = 1; sp.top_p = 1.0f; sp.logits32 = c->samp_l32.p;
     }
-    DevBuf<int32_t> hid_count;
-    int64_t hid_rows = max_tokens + 1;
-    if (hidden_mode) {
-        hm->hidden->alloc((size_t)batch * hid_rows * c->d);
-        hid_count.alloc(batch);
-        std::vector<int32_t> ones_i(batch, 1);           // slot 0 = last prompt token (Soprano.swift:824-825)
-        HIP_CHECK(hipMemcpyAsync(hid_count.p, ones_i.data(), batch * 4, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-    }
     sampler_resolve(sp, multi_launch_only);              // (environment switches read once per call; part of the graph key through sp)
-    c->sp = sp;
-    {   // the captured graphs bake in every pointer and scalar below: re-capture when any of them changes
+}
+
+static void start_hidden(mis_tts* c, HiddenMode* hm, int batch, int max_tokens) {
+    hm->rows = max_tokens + 1;
+    hm->hidden->alloc((size_t)batch * hm->rows * c->d);
+    hm->count.alloc(batch);
+    std::vector<int32_t> ones_i(batch, 1);               // slot 0 = last prompt token (Soprano.swift:824-825)
+    HIP_CHECK(hipMemcpyAsync(hm->count.p, ones_i.data(), batch * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
+// The two bodies that are captured into graphs, and the key of everything they bake in.  The bodies and key() belong together: every
+// pointer and scalar that a body - or a launcher it calls - reads from the handle must be mixed into the key, or a stale graph is
+// replayed after that value has changed.
+struct GenStep {
+    mis_tts* c;
+    int batch, Lmax, max_tokens;
+    const HiddenMode* hm;                                // null: no hidden-state collection
+    void collect(int prefill) const {
+        if (hm)
+            hipLaunchKernelGGL(k_collect_hidden, dim3(batch), dim3(256), 0, c->stream, c->x.p, c->active.p, hm->count.p, hm->hidden->p,
+                               hm->rows, c->d, c->Mpad / 16, prefill);
+    }
+    void prefill() const {
+        launch_prefill_feed(c->prompt_mat.p, c->prompt_lens.p, Lmax, c->step_counter.p, c->ids.p, c->active.p, batch, c->stream);
+        enqueue_layers(c);
+        collect(1);
+    }
+    void decode() const {
+        enqueue_lm_head(c);
+        launch_sampler(c->sp, batch, c->stream);
+        enqueue_layers(c);
+        collect(0);
+    }
+    uint64_t key(const SamplerParams& sp) const {        // FNV-1a; sp: what c->sp was copied from
         uint64_t key = 1469598103934665603ull;
         auto mix = [&](const void* p, size_t n) { const unsigned char* q = (const unsigned char*)p; for (size_t i = 0; i < n; ++i) { key ^= q[i]; key *= 1099511628211ull; } };
         mix(&sp, sizeof(sp));
@@ -1283,44 +1273,37 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
                               c->attn_out.p, c->act.p, c->logits.p, c->qkv_part.p, c->part.p, c->kcache.p, c->vtcache.p,
                               c->rope_cos.p, c->rope_sin.p, c->pos_cur.p, c->pos_next.p};
         mix(ptrs, sizeof(ptrs));
-        int ints[] = {batch, Lmax, max_tokens, c->Mpad, c->Smax, c->S_qkv, c->S_o, c->S_down, hidden_mode ? 1 : 0,
+        int ints[] = {batch, Lmax, max_tokens, c->Mpad, c->Smax, c->S_qkv, c->S_o, c->S_down, hm ? 1 : 0,
                       c->a_qkv.R, c->a_qkv.ksb, c->a_qkv.U, c->a_o.R, c->a_o.ksb, c->a_o.U, c->a_down.R, c->a_down.ksb, c->a_down.U,
                       c->a_head.R, c->a_head.ksb, c->a_head.U, c->r_gu, c->ksb_gu, c->qa_gu.R, c->qa_gu.ksb, c->qa_head.R, c->qa_head.ksb};
         mix(ints, sizeof(ints));
-        const void* hp[] = {hidden_mode ? (const void*)hm->hidden->p : nullptr, hidden_mode ? (const void*)hid_count.p : nullptr};
+        const void* hp[] = {hm ? (const void*)hm->hidden->p : nullptr, hm ? (const void*)hm->count.p : nullptr};
         mix(hp, sizeof(hp));
-        if (key != c->graph_key) destroy_graphs(c);
-        c->graph_key = key;
+        return key;
     }
+};
 
-    auto collect = [&](int prefill) {
-        if (hidden_mode)
-            hipLaunchKernelGGL(k_collect_hidden, dim3(batch), dim3(256), 0, s, c->x.p, c->active.p, hid_count.p, hm->hidden->p,
-                               hid_rows, c->d, c->Mpad / 16, prefill);
-    };
-    auto prefill_body = [&]() {
-        launch_prefill_feed(c->prompt_mat.p, c->prompt_lens.p, Lmax, c->step_counter.p, c->ids.p, c->active.p, batch, s);
-        enqueue_layers(c);
-        collect(1);
-    };
-    auto decode_body = [&]() {
-        enqueue_lm_head(c);
-        launch_sampler(c->sp, batch, s);
-        enqueue_layers(c);
-        collect(0);
-    };
+// the loop's pinned read-backs; the attempt owns them, so they are freed behind the codec tail (hipHostFree waits for the device)
+struct PollPins {
+    PinnedBuf<int32_t> done;
+    PinnedBuf<unsigned> fail;                            // the one-launch sampler's per-row time-out flags, read back with every poll
+};
 
-    HipEvents<4> ev;
-    auto t_host0 = std::chrono::steady_clock::now();
+// Prefill and the polled decode loop; ev[0..2] are recorded around them.  `emitted[b]`: tokens of row b already announced to the
+// callback - by this attempt or by the one before it.  Returns the decode steps enqueued.
+static int run_decode_loop(mis_tts* c, const GenStep& step, const std::vector<int32_t>& lens, const HipEvents<4>& ev, PollPins& pins,
+                           mis_event_cb cb, void* user, const volatile int* cancel, std::vector<int32_t>& emitted) {
+    hipStream_t s = c->stream;
+    const int batch = step.batch, max_tokens = step.max_tokens;
     HIP_CHECK(hipEventRecord(ev[0], s));
     // ---- prefill: Lmax steps of the ragged, left-padded batch (prefill :711)
-    if (prefill_batched_ok(c, Lmax)) {
-        prefill_batched(c, c->prompt_mat.p, c->prompt_lens.p, lens, Lmax);
-        collect(1);
+    if (prefill_batched_ok(c, step.Lmax)) {
+        prefill_batched(c, c->prompt_mat.p, c->prompt_lens.p, lens, step.Lmax);
+        step.collect(1);
     } else {
-        if (c->use_graph && !c->g_prefill) c->g_prefill.capture(s, prefill_body);
-        for (int j = 0; j < Lmax; ++j) {
-            if (c->use_graph) c->g_prefill.launch(s); else prefill_body();
+        if (c->use_graph && !c->g_prefill) c->g_prefill.capture(s, [&]() { step.prefill(); });
+        for (int j = 0; j < step.Lmax; ++j) {
+            if (c->use_graph) c->g_prefill.launch(s); else step.prefill();
         }
     }
     HIP_CHECK(hipEventRecord(ev[1], s));
@@ -1331,7 +1314,7 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
         HIP_CHECK(hipStreamSynchronize(s));
     }
     // ---- decode loop (:714-744)
-    if (c->use_graph && !c->g_decode) c->g_decode.capture(s, decode_body);
+    if (c->use_graph && !c->g_decode) c->g_decode.capture(s, [&]() { step.decode(); });
     // (Several decode steps per graph launch were measured and removed: between two hipGraphLaunch calls of the one-step graph the
     // device idles for 8.2 us - profiles/r04/c1_gaps.json - and yet eight steps per graph are SLOWER, 2.1047 against 2.0953 ms per step
     // over five A/B runs, profiles/r04/c2_ab.json: a 1376-node graph costs more per node than its seven removed seams save.)
@@ -1339,25 +1322,25 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
     const int poll = cb ? 8 : 32;
     std::vector<int32_t> host_ngen(batch, 0), host_tok;
     bool cancelled = false;
-    PinnedBuf<int32_t> done_pin(1);
-    PinnedBuf<unsigned> fail_pin(batch);                 // the one-launch sampler's per-row time-out flags, read back with every poll
-    int32_t* done_host = done_pin.p;
+    pins.done.alloc(1);
+    pins.fail.alloc(batch);
+    int32_t* done_host = pins.done.p;
     *done_host = 0;
     while (steps < max_tokens) {
         int chunk = std::min(poll, max_tokens - steps);
         for (int i = 0; i < chunk; ++i) {
-            if (c->use_graph) c->g_decode.launch(s); else decode_body();
+            if (c->use_graph) c->g_decode.launch(s); else step.decode();
         }
         steps += chunk;
         HIP_CHECK(hipMemcpyAsync(done_host, c->done_count.p, 4, hipMemcpyDeviceToHost, s));
-        sampler_fail_flags_async(c->samp_scratch.p, batch, fail_pin.p, s);
+        sampler_fail_flags_async(c->samp_scratch.p, batch, pins.fail.p, s);
         if (cb) {
             host_tok.resize((size_t)batch * max_tokens);
             HIP_CHECK(hipMemcpyAsync(host_ngen.data(), c->n_gen.p, batch * 4, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipMemcpyAsync(host_tok.data(), c->tokens_out.p, host_tok.size() * 4, hipMemcpyDeviceToHost, s));
         }
         HIP_CHECK(hipStreamSynchronize(s));
-        if (sampler_fail_flags_any(fail_pin.p, batch)) {
+        if (sampler_fail_flags_any(pins.fail.p, batch)) {
             // nothing of this poll interval has been announced; the steps queued behind the failed one ended at once (sticky flag,
             // k_samp_cluster).  The reference's loop cannot fail for lack of free compute units (LlamaTTS.swift:714-744): the caller
             // runs the request again on kernels that do not wait for each other.
@@ -1368,7 +1351,7 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
             for (int b = 0; b < batch; ++b)
                 for (; emitted[b] < host_ngen[b]; ++emitted[b]) {
                     int32_t t = host_tok[(size_t)b * max_tokens + emitted[b]];
-                    if (hidden_mode && t == hm->stop_id) continue;             // Soprano: [STOP] ends the row unannounced (Soprano.swift:855-857)
+                    if (step.hm && t == step.hm->stop_id) continue;            // Soprano: [STOP] ends the row unannounced (Soprano.swift:855-857)
                     cb(user, b, MIS_EVENT_TOKEN, &t, 1);                       // .token(id), LlamaTTS.swift:862
                 }
         }
@@ -1377,29 +1360,78 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
     }
     HIP_CHECK(hipEventRecord(ev[2], s));
     if (cancelled) throw MisError(MIS_ERR_CANCELLED, "generation cancelled");
+    return steps;
+}
 
-    if (hidden_mode) {
-        hm->n_hidden.resize(batch);
-        out.n_tokens.resize(batch);
-        HIP_CHECK(hipMemcpyAsync(hm->n_hidden.data(), hid_count.p, batch * 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(out.n_tokens.data(), c->n_gen.p, batch * 4, hipMemcpyDeviceToHost, s));
-        if (want_tokens) {
-            out.tokens.resize((size_t)batch * max_tokens);
-            out.tokens_stride = max_tokens;
-            HIP_CHECK(hipMemcpyAsync(out.tokens.data(), c->tokens_out.p, out.tokens.size() * 4, hipMemcpyDeviceToHost, s));
-        }
-        HIP_CHECK(hipStreamSynchronize(s));
-        // the graphs reference hid_count / hidden: never reuse them after this call
-        destroy_graphs(c);
-        c->graph_key = 0;
-        c->timing.prefill_ms = ms_between(ev[0], ev[1]);
-        c->timing.decode_ms = ms_between(ev[1], ev[2]);
-        c->timing.codec_ms = 0;
-        c->timing.steps = steps;
-        c->timing.step_ms_avg = steps ? c->timing.decode_ms / steps : 0;
-        return;
+static void copy_tokens_async(mis_tts* c, int batch, int max_tokens, GenOutputs& out) {
+    out.tokens.resize((size_t)batch * max_tokens);
+    out.tokens_stride = max_tokens;
+    HIP_CHECK(hipMemcpyAsync(out.tokens.data(), c->tokens_out.p, out.tokens.size() * 4, hipMemcpyDeviceToHost, c->stream));
+}
+
+static void finish_hidden(mis_tts* c, HiddenMode* hm, int batch, int max_tokens, bool want_tokens, GenOutputs& out) {
+    hipStream_t s = c->stream;
+    hm->n_hidden.resize(batch);
+    out.n_tokens.resize(batch);
+    HIP_CHECK(hipMemcpyAsync(hm->n_hidden.data(), hm->count.p, batch * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(out.n_tokens.data(), c->n_gen.p, batch * 4, hipMemcpyDeviceToHost, s));
+    if (want_tokens) copy_tokens_async(c, batch, max_tokens, out);
+    HIP_CHECK(hipStreamSynchronize(s));
+    // the graphs reference the slot counts / hidden: never reuse them after this call
+    destroy_graphs(c);
+    c->graph_key = 0;
+}
+
+// the caller's explicit SNAC noise on the device ([batch] rows of gmax groups per decoder block), and the staging of a sub-batch's slices
+struct CodecNoise {
+    int gmax = 0;
+    DevBuf<float> full[8], stage[8];
+    std::vector<const float*> full_ptrs, stage_ptrs;
+};
+
+// One gathered sub-batch: de-interleave the step's rows at its code offset, decode them together, scatter the PCM rows to its sample
+// offset.  The chunk index is folded into the seed of the internal noise (the reference draws fresh noise per chunk); explicit noise
+// (only ever with rows of equal length) is sliced at the chunk's offset.
+static void decode_gathered_rows(mis_tts* c, const mis_gen_params* gp, const SnacDecodeStep& st, int batch, int all_stride, int64_t hop,
+                                 CodecNoise* noise, float* pcm_dev, int64_t pcm_stride) {
+    hipStream_t s = c->stream;
+    const int gc = st.gc, nsub = (int)st.rows.size();
+    c->pcm_tmp.alloc((size_t)nsub * gc * hop);
+    for (int k = 0; k < nsub; ++k) {
+        const int b = st.rows[k];
+        int32_t *l0 = c->l0.p + (size_t)k * gc, *l1 = c->l1.p + (size_t)k * gc * 2, *l2 = c->l2.p + (size_t)k * gc * 4;
+        if (st.chunked)             // exactly the chunk's 7 * gc codes
+            launch_orpheus_deinterleave(c->codes.p + (size_t)b * all_stride + st.code_off, 7 * gc, 1, gc, l0, l1, l2, gc, s);
+        else                        // the whole row, its code count read on the device, codes clamped into the codebook
+            launch_orpheus_deinterleave_ragged(c->codes.p + (size_t)b * all_stride, all_stride, c->n_codes.p + b, 1, l0, l1, l2, gc, s);
     }
-    // ---- parseOutput (:749-752) + de-interleave (:41-64) + SNAC decode (:759)
+    const int32_t* cp[3] = {c->l0.p, c->l1.p, c->l2.p};
+    if (noise) {
+        noise->stage_ptrs.clear();
+        for (size_t i = 0; i < noise->full_ptrs.size(); ++i) {
+            const size_t full = mis_snac_noise_len(c->codec, (int)i, noise->gmax), per_group = full / noise->gmax, len = per_group * gc;
+            noise->stage[i].alloc((size_t)nsub * len);
+            for (int k = 0; k < nsub; ++k)
+                HIP_CHECK(hipMemcpyAsync(noise->stage[i].p + (size_t)k * len,
+                                         noise->full[i].p + (size_t)st.rows[k] * full + (size_t)st.group_off * per_group, len * 4,
+                                         hipMemcpyDeviceToDevice, s));
+            noise->stage_ptrs.push_back(noise->stage[i].p);
+        }
+    }
+    c->row_map.alloc(batch);
+    HIP_CHECK(hipMemcpyAsync(c->row_map.p, st.rows.data(), nsub * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    snac_decode_device(c->codec, cp, nsub, gc, noise ? noise->stage_ptrs.data() : nullptr, 1,
+                       gp->seed + 0x9E3779B97F4A7C15ull * (uint64_t)st.ci, c->row_map.p, gp->row_offset, c->pcm_tmp.p, (int64_t)gc * hop, s);
+    for (int k = 0; k < nsub; ++k)
+        HIP_CHECK(hipMemcpyAsync(pcm_dev + (size_t)st.rows[k] * pcm_stride + (size_t)st.group_off * hop, c->pcm_tmp.p + (size_t)k * gc * hop,
+                                 (size_t)gc * hop * 4, hipMemcpyDeviceToDevice, s));
+}
+
+// parseOutput (:749-752) + de-interleave (:41-64) + SNAC decode (:759): the sub-batches of snac_decode_plan (lm_request.h), in its order;
+// `decoded` is recorded behind the last of them
+static void decode_codes_to_pcm(mis_tts* c, const mis_gen_params* gp, const float* const* snac_noise, int batch, int all_stride,
+                                float* pcm_dev, int64_t pcm_stride, GenOutputs& out, hipEvent_t decoded) {
+    hipStream_t s = c->stream;
     c->codes.alloc((size_t)batch * all_stride); c->n_codes.alloc(batch);
     {
         SpeechTokenIds tk{c->cfg.start_of_speech_id, c->cfg.end_of_speech_id, c->cfg.audio_token_offset, c->cfg.start_of_ai_id > 0 ? c->cfg.start_of_ai_id : -1};
@@ -1411,167 +1443,123 @@ static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const in
     HIP_CHECK(hipMemcpyAsync(ncodes.data(), c->n_codes.p, batch * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(out.n_tokens.data(), c->n_gen.p, batch * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    int gmax = 0, gany = 0;
-    for (int b = 0; b < batch; ++b) { gmax = std::max(gmax, ncodes[b] / 7); gany += ncodes[b] > 0; }
-    MIS_REQUIRE(gany > 0, MIS_ERR_GENERATION_FAILED, "No audio codes generated");          // :754-756
+    const auto mm = std::minmax_element(ncodes.begin(), ncodes.end());
+    const int nc_min = *mm.first, nc_max = *mm.second, gmax = nc_max / 7;
+    MIS_REQUIRE(nc_max > 0, MIS_ERR_GENERATION_FAILED, "No audio codes generated");        // :754-756
     const int64_t hop = mis_snac_num_samples(c->codec, 1);
     out.pcm_lens.assign(batch, 0);
     for (int b = 0; b < batch; ++b) out.pcm_lens[b] = (int64_t)(ncodes[b] / 7) * hop;
-    int64_t need = (int64_t)gmax * hop;
-    DevBuf<float> own;   // (only used when the caller gave no device buffer)
-    (void)own;
+    const int64_t need = (int64_t)gmax * hop;
     MIS_REQUIRE(pcm_dev && pcm_stride >= need, MIS_ERR_INVALID_INPUT, "pcm buffer too small (%lld needed per row)", (long long)need);
     out.pcm_dev = pcm_dev; out.pcm_stride = pcm_stride;
-    // rows with equal group counts decode together; padding a short row would change its tail samples
-    std::vector<int> order(batch);
-    for (int b = 0; b < batch; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return ncodes[a] < ncodes[b2]; });
-    bool all_equal = ncodes[order.front()] == ncodes[order.back()];
-    MIS_REQUIRE(!snac_noise || all_equal, MIS_ERR_INVALID_INPUT,
+    MIS_REQUIRE(!snac_noise || nc_min == nc_max, MIS_ERR_INVALID_INPUT,
                 "explicit SNAC noise requires all rows to produce the same number of frames");
     c->l0.alloc((size_t)batch * gmax); c->l1.alloc((size_t)batch * gmax * 2); c->l2.alloc((size_t)batch * gmax * 4);
-    std::vector<const float*> dnoise;
-    DevBuf<float> noise_dev[8];
+    CodecNoise noise;
+    noise.gmax = gmax;
     if (snac_noise) {
-        for (int i = 0; i < sc->n_decoder_rates; ++i) {
+        for (int i = 0; i < snac_config(c->codec)->n_decoder_rates; ++i) {
             size_t n = (size_t)batch * mis_snac_noise_len(c->codec, i, gmax);
-            noise_dev[i].alloc(n);
-            HIP_CHECK(hipMemcpyAsync(noise_dev[i].p, snac_noise[i], n * 4, hipMemcpyDefault, s));
-            dnoise.push_back(noise_dev[i].p);
+            noise.full[i].alloc(n);
+            HIP_CHECK(hipMemcpyAsync(noise.full[i].p, snac_noise[i], n * 4, hipMemcpyDefault, s));
+            noise.full_ptrs.push_back(noise.full[i].p);
         }
     }
-    const int chunk = c->cfg.codec_chunk_groups;
-    if (chunk > 0 && gmax > chunk) {
-        // VyvoTTS decodeAudioFromCodes (Qwen3.swift:47-83): rows longer than `chunk` groups are decoded as INDEPENDENT chunks of
-        // `chunk` groups (the last one shorter) whose samples are concatenated; shorter rows are a single chunk.  Per chunk index
-        // the rows are grouped by their chunk length, gathered, decoded together and scattered to sample offset ci*chunk*hop.
-        // Explicit noise: the caller's per-row tensors (sized for the whole utterance) are sliced at the same offsets; internal
-        // noise: the chunk index is folded into the seed (the reference draws fresh noise per chunk).
-        DevBuf<float> noise_stage[8];
-        const int n_ch = (gmax + chunk - 1) / chunk;
-        for (int ci = 0; ci < n_ch; ++ci) {
-            std::vector<std::pair<int, int>> part;                      // (chunk length in groups, row)
-            for (int b = 0; b < batch; ++b) {
-                int g = ncodes[b] / 7;
-                if (g > ci * chunk) part.push_back({std::min(chunk, g - ci * chunk), b});
-            }
-            std::stable_sort(part.begin(), part.end());
-            size_t j0 = 0;
-            while (j0 < part.size()) {
-                size_t j1 = j0;
-                while (j1 < part.size() && part[j1].first == part[j0].first) ++j1;
-                const int gc = part[j0].first, nsub = (int)(j1 - j0);
-                c->pcm_tmp.alloc((size_t)nsub * gc * hop);
-                std::vector<int32_t> rows(nsub);
-                for (int k = 0; k < nsub; ++k) {
-                    const int b = part[j0 + k].second;
-                    rows[k] = b;
-                    launch_orpheus_deinterleave(c->codes.p + (size_t)b * all_stride + (size_t)ci * chunk * 7, 7 * gc, 1, gc,
-                                                c->l0.p + (size_t)k * gc, c->l1.p + (size_t)k * gc * 2, c->l2.p + (size_t)k * gc * 4, gc, s);
-                }
-                const int32_t* cp[3] = {c->l0.p, c->l1.p, c->l2.p};
-                std::vector<const float*> nz;
-                if (snac_noise) {                                       // all rows have gmax groups here (checked above)
-                    for (int i = 0; i < sc->n_decoder_rates; ++i) {
-                        const size_t full = mis_snac_noise_len(c->codec, i, gmax), per_group = full / gmax, len = per_group * gc;
-                        noise_stage[i].alloc((size_t)nsub * len);
-                        for (int k = 0; k < nsub; ++k)
-                            HIP_CHECK(hipMemcpyAsync(noise_stage[i].p + (size_t)k * len,
-                                                     noise_dev[i].p + (size_t)rows[k] * full + (size_t)ci * chunk * per_group, len * 4,
-                                                     hipMemcpyDeviceToDevice, s));
-                        nz.push_back(noise_stage[i].p);
-                    }
-                }
-                c->row_map.alloc(batch);
-                HIP_CHECK(hipMemcpyAsync(c->row_map.p, rows.data(), nsub * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                snac_decode_device(c->codec, cp, nsub, gc, snac_noise ? nz.data() : nullptr, 1,
-                                   gp->seed + 0x9E3779B97F4A7C15ull * (uint64_t)ci, c->row_map.p, gp->row_offset, c->pcm_tmp.p,
-                                   (int64_t)gc * hop, s);
-                for (int k = 0; k < nsub; ++k)
-                    HIP_CHECK(hipMemcpyAsync(pcm_dev + (size_t)rows[k] * pcm_stride + (size_t)ci * chunk * hop,
-                                             c->pcm_tmp.p + (size_t)k * gc * hop, (size_t)gc * hop * 4, hipMemcpyDeviceToDevice, s));
-                HIP_CHECK(hipStreamSynchronize(s));                     // `rows` / staging are reused by the next sub-batch
-                j0 = j1;
-            }
+    for (const SnacDecodeStep& st : snac_decode_plan(ncodes, c->cfg.codec_chunk_groups)) {
+        if (st.all_rows) {
+            launch_orpheus_deinterleave_ragged(c->codes.p, all_stride, c->n_codes.p, batch, c->l0.p, c->l1.p, c->l2.p, st.gc, s);
+            const int32_t* cp[3] = {c->l0.p, c->l1.p, c->l2.p};
+            snac_decode_device(c->codec, cp, batch, st.gc, snac_noise ? noise.full_ptrs.data() : nullptr, 1, gp->seed, nullptr,
+                               gp->row_offset, pcm_dev, pcm_stride, s);
+        } else {
+            decode_gathered_rows(c, gp, st, batch, all_stride, hop, snac_noise ? &noise : nullptr, pcm_dev, pcm_stride);
+            if (st.chunked) HIP_CHECK(hipStreamSynchronize(s));         // (kept: the chunked walk has always waited here before it reuses the staging)
         }
-        order.clear();                                                  // the whole-utterance path below has nothing left to do
-    }
-    size_t i0 = 0;
-    while (i0 < order.size()) {
-        size_t i1 = i0;
-        while (i1 < order.size() && ncodes[order[i1]] == ncodes[order[i0]]) ++i1;
-        int g = ncodes[order[i0]] / 7, nsub = (int)(i1 - i0);
-        if (g > 0) {
-            if (all_equal) {
-                launch_orpheus_deinterleave_ragged(c->codes.p, all_stride, c->n_codes.p, batch, c->l0.p, c->l1.p, c->l2.p, g, s);
-                const int32_t* cp[3] = {c->l0.p, c->l1.p, c->l2.p};
-                snac_decode_device(c->codec, cp, batch, g, snac_noise ? dnoise.data() : nullptr, 1, gp->seed, nullptr,
-                                   gp->row_offset, pcm_dev, pcm_stride, s);
-            } else {
-                // gather the subset row by row (rare path: ragged EOS); decode the subset; scatter PCM rows
-                c->pcm_tmp.alloc((size_t)nsub * g * hop);
-                for (int k = 0; k < nsub; ++k) {
-                    int b = order[i0 + k];
-                    launch_orpheus_deinterleave_ragged(c->codes.p + (size_t)b * all_stride, all_stride, c->n_codes.p + b, 1,
-                                                       c->l0.p + (size_t)k * g, c->l1.p + (size_t)k * g * 2,
-                                                       c->l2.p + (size_t)k * g * 4, g, s);
-                }
-                const int32_t* cp[3] = {c->l0.p, c->l1.p, c->l2.p};
-                c->row_map.alloc(batch);
-                HIP_CHECK(hipMemcpyAsync(c->row_map.p, order.data() + i0, nsub * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                snac_decode_device(c->codec, cp, nsub, g, nullptr, 1, gp->seed, c->row_map.p, gp->row_offset, c->pcm_tmp.p,
-                                   (int64_t)g * hop, s);
-                for (int k = 0; k < nsub; ++k)
-                    HIP_CHECK(hipMemcpyAsync(pcm_dev + (size_t)order[i0 + k] * pcm_stride, c->pcm_tmp.p + (size_t)k * g * hop,
-                                             (size_t)g * hop * 4, hipMemcpyDeviceToDevice, s));
-            }
-        }
-        i0 = i1;
     }
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[3], s));
-    if (want_tokens) {
-        out.tokens.resize((size_t)batch * max_tokens);
-        out.tokens_stride = max_tokens;
-        HIP_CHECK(hipMemcpyAsync(out.tokens.data(), c->tokens_out.p, out.tokens.size() * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    auto t_host1 = std::chrono::steady_clock::now();
-    (void)t_host0; (void)t_host1;
+    HIP_CHECK(hipEventRecord(decoded, s));               // (before the explicit noise is freed: hipFree waits for the device)
+}
+
+static void record_timing(mis_tts* c, const HipEvents<4>& ev, int steps, int batch, int Lmax, bool codec) {
     c->timing.prefill_ms = ms_between(ev[0], ev[1]);
     c->timing.decode_ms = ms_between(ev[1], ev[2]);
-    c->timing.codec_ms = ms_between(ev[2], ev[3]);
+    c->timing.codec_ms = codec ? ms_between(ev[2], ev[3]) : 0;
     c->timing.steps = steps;
     c->timing.step_ms_avg = steps ? c->timing.decode_ms / steps : 0;
-    {
-        // bytes per weight element as streamed: 2 (bf16) or bits / 8 + 4 / 64 (codes + a bf16 scale and bias per 64 codes)
-        auto bpe = [](const mis_tts::QRole& q) { return q.on ? q.bits / 8.0 + 4.0 / 64.0 : 2.0; };
-        double w = (double)c->L * (bpe(c->q_qkv) * c->Nqkv * c->d + bpe(c->q_o) * c->d * c->H * c->D + bpe(c->q_gu) * 2.0 * c->ff * c->d +
-                                   bpe(c->q_down) * c->ff * c->d) + bpe(c->q_head) * c->V * c->d;
-        double mean_ctx = Lmax + steps / 2.0;
-        double kvb = (double)batch * mean_ctx * c->L * 2.0 * c->Hkv * c->D * 2.0;
-        c->timing.hbm_bytes_per_step = w + kvb;
+    if (!codec) return;                                  // (hidden mode leaves the traffic model of the last codec call)
+    // bytes per weight element as streamed: 2 (bf16) or bits / 8 + 4 / 64 (codes + a bf16 scale and bias per 64 codes)
+    auto bpe = [](const mis_tts::QRole& q) { return q.on ? q.bits / 8.0 + 4.0 / 64.0 : 2.0; };
+    double w = (double)c->L * (bpe(c->q_qkv) * c->Nqkv * c->d + bpe(c->q_o) * c->d * c->H * c->D + bpe(c->q_gu) * 2.0 * c->ff * c->d +
+                               bpe(c->q_down) * c->ff * c->d) + bpe(c->q_head) * c->V * c->d;
+    double mean_ctx = Lmax + steps / 2.0;
+    double kvb = (double)batch * mean_ctx * c->L * 2.0 * c->Hkv * c->D * 2.0;
+    c->timing.hbm_bytes_per_step = w + kvb;
+}
+
+// One attempt of generate: request -> device state -> sampler -> graphs -> prefill and decode loop -> hidden states or codec.
+// `multi_launch_only`: the sampler's multi-launch kernels (no kernel of the step waits for another block).  `emitted`: see
+// run_decode_loop (the request is deterministic: prompts, seeds and the RNG counter are the same, so a second attempt reproduces the
+// tokens of the first and continues behind them).
+static void run_generate_attempt(mis_tts* c, const int32_t* prompt_ids, const std::vector<int32_t>& lens, const mis_gen_params* gp,
+                                 const float* const* snac_noise, float* pcm_dev, int64_t pcm_stride, bool want_tokens, mis_event_cb cb,
+                                 void* user, const volatile int* cancel, GenOutputs& out, HiddenMode* hm, bool multi_launch_only,
+                                 std::vector<int32_t>& emitted) {
+    const int batch = (int)lens.size();
+    MIS_REQUIRE(c && c->finalized, MIS_ERR_NOT_INITIALIZED, "model not initialized");
+    if (hm && !hm->on) hm = nullptr;
+    MIS_REQUIRE(hm || c->codec, MIS_ERR_NOT_INITIALIZED, "SNAC model not loaded");            // LlamaTTS.swift:672-674
+    MIS_REQUIRE(prompt_ids && gp, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(batch >= 1 && batch <= 64, MIS_ERR_INVALID_INPUT, "batch per GPU must be 1..64");
+    const mis_snac_config* sc = hm ? nullptr : snac_config(c->codec);
+    MIS_REQUIRE(hm || (sc->n_codebooks == 3 && sc->vq_strides[0] == 4 && sc->vq_strides[1] == 2 && sc->vq_strides[2] == 1 &&
+                       sc->codebook_size == 4096),
+                MIS_ERR_INVALID_INPUT, "Orpheus framing needs a 3-level 4/2/1 SNAC codec with 4096-entry codebooks");
+    HIP_CHECK(hipSetDevice(c->device));
+    const int max_tokens = default_max_tokens(gp);
+    std::vector<int32_t> flat(lm_prompt_tokens(lens));
+    HIP_CHECK(hipMemcpy(flat.data(), prompt_ids, flat.size() * 4, hipMemcpyDefault));
+    const LmRequest req = build_lm_request(lens, flat, c->V, max_tokens, gp->repetition_context, gp->sampler_flavor);
+    lm_reset(c, batch, req.Lmax + max_tokens + 1);
+    upload_request(c, req, lens, max_tokens);
+    SamplerParams sp{};
+    make_sampler_params(c, gp, req, batch, max_tokens, hm, multi_launch_only, sp);
+    c->sp = sp;
+    if (hm) start_hidden(c, hm, batch, max_tokens);
+    const GenStep step{c, batch, req.Lmax, max_tokens, hm};
+    const uint64_t key = step.key(sp);                   // the captured graphs bake all of it in: re-capture when any of it changes
+    if (key != c->graph_key) destroy_graphs(c);
+    c->graph_key = key;
+
+    HipEvents<4> ev;
+    PollPins pins;
+    const int steps = run_decode_loop(c, step, lens, ev, pins, cb, user, cancel, emitted);
+    if (hm) {
+        finish_hidden(c, hm, batch, max_tokens, want_tokens, out);
+        record_timing(c, ev, steps, batch, req.Lmax, false);
+        return;
     }
+    decode_codes_to_pcm(c, gp, snac_noise, batch, req.all_stride, pcm_dev, pcm_stride, out, ev[3]);
+    if (want_tokens) copy_tokens_async(c, batch, max_tokens, out);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    record_timing(c, ev, steps, batch, req.Lmax, true);
 }
 
 // generate = one attempt on the fastest kernels; if the one-launch sampler could not get its blocks co-resident (the only kernel of
 // the step that needs that), the whole request once more on the multi-launch sampler - the request is deterministic, the second
 // attempt's tokens are the ones the first would have produced, and the callback continues behind what it has already been told.
 // A handle that shares its device with another replica's streams never takes the one-launch path in the first place.
-static void run_generate(mis_tts* c, const int32_t* prompt_ids, const int32_t* prompt_lens, int batch,
-                         const mis_gen_params* gp, const float* const* snac_noise, float* pcm_dev, int64_t pcm_stride,
-                         bool want_tokens, mis_event_cb cb, void* user, const volatile int* cancel, GenOutputs& out,
-                         HiddenMode* hm = nullptr) {
-    std::vector<int32_t> emitted(std::max(batch, 1), 0);
+static void run_generate(mis_tts* c, const int32_t* prompt_ids, const std::vector<int32_t>& lens, const mis_gen_params* gp,
+                         const float* const* snac_noise, float* pcm_dev, int64_t pcm_stride, bool want_tokens, mis_event_cb cb, void* user,
+                         const volatile int* cancel, GenOutputs& out, HiddenMode* hm = nullptr) {
+    std::vector<int32_t> emitted(lens.size(), 0);
     const bool multi_first = c && c->shared_device;
     try {
-        run_generate_attempt(c, prompt_ids, prompt_lens, batch, gp, snac_noise, pcm_dev, pcm_stride, want_tokens, cb, user, cancel, out, hm,
-                             multi_first, emitted);
+        run_generate_attempt(c, prompt_ids, lens, gp, snac_noise, pcm_dev, pcm_stride, want_tokens, cb, user, cancel, out, hm, multi_first,
+                             emitted);
     } catch (const SamplerTimeout&) {
         MIS_REQUIRE(!multi_first, MIS_ERR_GENERATION_FAILED, "sampler: time-out flag raised on the multi-launch path");   // (cannot happen: nothing spins there)
         out = GenOutputs{};
-        run_generate_attempt(c, prompt_ids, prompt_lens, batch, gp, snac_noise, pcm_dev, pcm_stride, want_tokens, cb, user, cancel, out, hm,
-                             true, emitted);
+        run_generate_attempt(c, prompt_ids, lens, gp, snac_noise, pcm_dev, pcm_stride, want_tokens, cb, user, cancel, out, hm, true, emitted);
     }
 }
 void tts_internal_set_shared_device(mis_tts* c, bool shared) { if (c) c->shared_device = shared; }
@@ -1588,8 +1576,9 @@ extern "C" mis_status mis_tts_generate_device(mis_tts* c, const int32_t* prompt_
     MIS_API_BEGIN
     MIS_REQUIRE(c, MIS_ERR_INVALID_INPUT, "null handle");
     default_params_check(params);
+    HIP_CHECK(hipSetDevice(c->device));
     GenOutputs out;
-    run_generate(c, prompt_ids, prompt_lens, batch, params, snac_noise, pcm_dev, pcm_stride, false, nullptr, nullptr, nullptr, out);
+    run_generate(c, prompt_ids, host_prompt_lens(prompt_lens, batch), params, snac_noise, pcm_dev, pcm_stride, false, nullptr, nullptr, nullptr, out);
     if (pcm_lens) for (int b = 0; b < batch; ++b) pcm_lens[b] = out.pcm_lens[b];
     if (n_tokens) for (int b = 0; b < batch; ++b) n_tokens[b] = out.n_tokens[b];
     MIS_API_END
@@ -1597,14 +1586,9 @@ extern "C" mis_status mis_tts_generate_device(mis_tts* c, const int32_t* prompt_
 
 // Upper bound of the audio one row can decode to.  parseOutput (LlamaTTS.swift:749-752) keeps everything after the LAST
 // start-of-speech marker - or the whole sequence, prompt included, when the prompt carries none - so the prompt length counts.
-static int64_t max_pcm_per_row(mis_tts* c, const mis_gen_params* p, const int32_t* prompt_lens, int batch) {
-    MIS_REQUIRE(prompt_lens && batch >= 1, MIS_ERR_INVALID_INPUT, "null argument");
-    std::vector<int32_t> lens(batch);
-    HIP_CHECK(hipMemcpy(lens.data(), prompt_lens, (size_t)batch * 4, hipMemcpyDefault));
-    int lmax = 0;
-    for (int b = 0; b < batch; ++b) lmax = std::max(lmax, lens[b]);
-    int mt = p->max_tokens > 0 ? p->max_tokens : 1200;
-    return mis_snac_num_samples(c->codec, std::max(1, (mt + lmax) / 7 + 1));
+static int64_t max_pcm_per_row(mis_tts* c, const mis_gen_params* p, const std::vector<int32_t>& lens) {
+    const int lmax = std::max(0, *std::max_element(lens.begin(), lens.end()));
+    return mis_snac_num_samples(c->codec, std::max(1, (default_max_tokens(p) + lmax) / 7 + 1));
 }
 
 extern "C" mis_status mis_tts_generate(mis_tts* c, const int32_t* prompt_ids, const int32_t* prompt_lens, int batch,
@@ -1616,12 +1600,13 @@ extern "C" mis_status mis_tts_generate(mis_tts* c, const int32_t* prompt_ids, co
     MIS_REQUIRE(c->codec, MIS_ERR_NOT_INITIALIZED, "SNAC model not loaded");
     default_params_check(params);
     HIP_CHECK(hipSetDevice(c->device));
-    int64_t cap = max_pcm_per_row(c, params, prompt_lens, batch);
+    const std::vector<int32_t> lens = host_prompt_lens(prompt_lens, batch);
+    int64_t cap = max_pcm_per_row(c, params, lens);
     DevBuf<float> pcm;
     pcm.alloc((size_t)batch * cap);
     HIP_CHECK(hipMemsetAsync(pcm.p, 0, (size_t)batch * cap * 4, c->stream));
     GenOutputs out;
-    run_generate(c, prompt_ids, prompt_lens, batch, params, snac_noise, pcm.p, cap, tokens_out != nullptr, nullptr, nullptr, nullptr, out);
+    run_generate(c, prompt_ids, lens, params, snac_noise, pcm.p, cap, tokens_out != nullptr, nullptr, nullptr, nullptr, out);
     int64_t longest = 0;
     for (int b = 0; b < batch; ++b) longest = std::max(longest, out.pcm_lens[b]);
     PinnedBuf<float> host((size_t)batch * std::max<int64_t>(longest, 1));
@@ -1646,13 +1631,12 @@ extern "C" mis_status mis_tts_generate_stream(mis_tts* c, const int32_t* prompt_
     MIS_REQUIRE(c->codec, MIS_ERR_NOT_INITIALIZED, "SNAC model not loaded");
     default_params_check(params);
     HIP_CHECK(hipSetDevice(c->device));
-    int64_t cap = max_pcm_per_row(c, params, prompt_lens, batch);
+    const std::vector<int32_t> lens = host_prompt_lens(prompt_lens, batch);
+    int64_t cap = max_pcm_per_row(c, params, lens);
     DevBuf<float> pcm;
     pcm.alloc((size_t)batch * cap);
     GenOutputs out;
-    run_generate(c, prompt_ids, prompt_lens, batch, params, snac_noise, pcm.p, cap, false, on_event, user, cancel_flag, out);
-    std::vector<int32_t> lens(batch);
-    HIP_CHECK(hipMemcpy(lens.data(), prompt_lens, batch * 4, hipMemcpyDefault));
+    run_generate(c, prompt_ids, lens, params, snac_noise, pcm.p, cap, false, on_event, user, cancel_flag, out);
     std::vector<float> host;
     for (int b = 0; b < batch; ++b) {
         mis_gen_info info{};
@@ -1899,7 +1883,8 @@ void tts_generate_hidden(mis_tts* c, const int32_t* prompt_ids, const int32_t* p
     HiddenMode hm;
     hm.on = true; hm.stop_id = stop_id; hm.hidden = &hidden;
     GenOutputs out;
-    run_generate(c, prompt_ids, prompt_lens, batch, gp, nullptr, nullptr, 0, true, cb, user, cancel, out, &hm);
+    HIP_CHECK(hipSetDevice(c->device));
+    run_generate(c, prompt_ids, host_prompt_lens(prompt_lens, batch), gp, nullptr, nullptr, 0, true, cb, user, cancel, out, &hm);
     n_hidden = hm.n_hidden; n_tokens = out.n_tokens; tokens = out.tokens; tokens_stride = out.tokens_stride;
 }
 

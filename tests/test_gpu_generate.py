@@ -177,9 +177,7 @@ def test_prompt_without_speech_marker_counts_towards_the_audio(stack):
     assert len(pcm[0]) == (frames + 1) * hop
 
 
-def test_vyvotts_token_ids_drive_the_same_loop():
-    # VyvoTTS = Qwen3-style LM + SNAC with its own token ids (Qwen3.swift:19-29): EOS, frame-constrained range and parse use them
-    ocfg_s, osn, dsn = snac_pair(SNAC_SMALL)
+def _vyvo_lm(codec, codec_chunk_groups=0):
     V = mas.VyvoTokens
     lcfg = ollama.LlamaConfig(hidden_size=256, num_hidden_layers=1, intermediate_size=512, num_attention_heads=2, num_key_value_heads=1,
                               head_dim=128, vocab_size=V.audio_token_offset + 7 * 4096, rope_theta=1e6, rope_scaling=None,
@@ -188,7 +186,16 @@ def test_vyvotts_token_ids_drive_the_same_loop():
     hc = lm_host_config(lcfg)
     hc.start_of_speech_id, hc.end_of_speech_id, hc.audio_token_offset, hc.start_of_ai_id = (V.start_of_speech, V.end_of_speech,
                                                                                            V.audio_token_offset, V.start_of_ai)
-    lm = mas.LlamaTTSModel.synthetic(hc, codec=dsn, seed=99)
+    if codec_chunk_groups:
+        hc.codec_chunk_groups = codec_chunk_groups
+    return mas.LlamaTTSModel.synthetic(hc, codec=codec, seed=99)
+
+
+def test_vyvotts_token_ids_drive_the_same_loop():
+    # VyvoTTS = Qwen3-style LM + SNAC with its own token ids (Qwen3.swift:19-29): EOS, frame-constrained range and parse use them
+    ocfg_s, osn, dsn = snac_pair(SNAC_SMALL)
+    V = mas.VyvoTokens
+    lm = _vyvo_lm(dsn)
     prompt = np.asarray([V.start_of_human, 11, 12, V.end_of_text, V.end_of_human, V.start_of_ai, V.start_of_speech], np.int32)
     gp = mas.GenerateParameters(max_tokens=14, temperature=0.0, repetition_penalty=0.0, frame_constrained=True)
     zeros = [np.zeros((1, n), np.float32) for n in dsn.noise_lengths(2)]
@@ -205,15 +212,7 @@ def test_vyvotts_decodes_snac_in_independent_chunks():
     # an independent SNAC decode; explicit noise is sliced at the chunk offsets
     ocfg_s, osn, dsn = snac_pair(SNAC_SMALL)
     V = mas.VyvoTokens
-    lcfg = ollama.LlamaConfig(hidden_size=256, num_hidden_layers=1, intermediate_size=512, num_attention_heads=2, num_key_value_heads=1,
-                              head_dim=128, vocab_size=V.audio_token_offset + 7 * 4096, rope_theta=1e6, rope_scaling=None,
-                              tie_word_embeddings=True, qk_norm=True, rope_plain=True, rms_norm_eps=1e-6)
-    from gpu_util import lm_host_config
-    hc = lm_host_config(lcfg)
-    hc.start_of_speech_id, hc.end_of_speech_id, hc.audio_token_offset, hc.start_of_ai_id = (V.start_of_speech, V.end_of_speech,
-                                                                                           V.audio_token_offset, V.start_of_ai)
-    hc.codec_chunk_groups = 3
-    lm = mas.LlamaTTSModel.synthetic(hc, codec=dsn, seed=99)
+    lm = _vyvo_lm(dsn, codec_chunk_groups=3)
     rng = np.random.default_rng(21)
     prompts = [np.asarray([V.start_of_human, 11 + r, 12, V.end_of_text, V.end_of_human, V.start_of_ai, V.start_of_speech], np.int32)
                for r in range(2)]
@@ -229,10 +228,59 @@ def test_vyvotts_decodes_snac_in_independent_chunks():
         assert rms(pcm[r], ref) < 1e-4
         whole.append(oc.decode_audio_from_codes_chunked(codes, osn, chunk_groups=50, noises=[z[r:r + 1] for z in noise]))
     assert rms(pcm[0], whole[0]) > 1e-3                                         # NOT the single-decode waveform
-    # internal noise: runs, deterministic, and rows of different length (EOS) take the ragged sub-batches
+    # internal noise: runs and is deterministic (rows of different length: test_vyvotts_ragged_rows_decode_in_chunked_sub_batches)
     a = lm.generate_batch(prompts, gp)
     b = lm.generate_batch(prompts, gp)
     assert all(np.array_equal(x, y) for x, y in zip(a, b)) and len(a[0]) == groups * 2048
+
+
+def test_ragged_rows_decode_in_gathered_sub_batches(stack):
+    """Rows with different code counts and a successful decode: the whole-utterance codec path gathers the rows of one length,
+    decodes them together and scatters the PCM.  Audio-only prompts count towards the audio (see above), so prompts of 1 and 3 frames
+    plus one generated frame give 14 and 28 codes - two sub-batches of one row each.  Internal noise is keyed by the global row, so
+    the row map must reach it: each row equals, bit for bit, the same row generated alone with its row offset."""
+    ocfg_s, osn, dsn, olm, dlm = stack
+    rng = np.random.default_rng(6)
+    prompts = [np.asarray([oc.AUDIO_TOKEN_OFFSET + (j % 7) * 4096 + int(rng.integers(0, 4096)) for j in range(7 * f)], np.int32)
+               for f in (1, 3)]
+    hop = int(np.prod(SNAC_SMALL["decoder_rates"])) * SNAC_SMALL["vq_strides"][0]
+    gp = mas.GenerateParameters(max_tokens=7, temperature=0.0, repetition_penalty=0.0, frame_constrained=True)
+    pcm, toks = dlm.generate_batch(prompts, gp, return_tokens=True)
+    assert [len(t) for t in toks] == [7, 7] and [len(p) for p in pcm] == [2 * hop, 4 * hop]
+    for r in range(2):
+        gp1 = mas.GenerateParameters(max_tokens=7, temperature=0.0, repetition_penalty=0.0, frame_constrained=True, row_offset=r)
+        p1, t1 = dlm.generate_batch([prompts[r]], gp1, return_tokens=True)
+        assert np.array_equal(t1[0], toks[r]) and np.array_equal(p1[0], pcm[r]), r
+    # a codec without the noise branch: every row against the oracle decode of the engine's own tokens
+    _, osn0, dsn0 = snac_pair(dict(SNAC_SMALL, noise=False))
+    _, _, dlm0 = lm_pair(LM_SMALL, codec=dsn0)
+    pcm0, toks0 = dlm0.generate_batch(prompts, gp, return_tokens=True)
+    assert [len(p) for p in pcm0] == [2 * hop, 4 * hop]
+    for r in range(2):
+        l0, l1, l2 = oc.deinterleave(oc.parse_output_row(list(prompts[r]) + list(toks0[r])))
+        ref = osn0.decode([l0[None], l1[None], l2[None]], None)[0, 0]
+        assert rms(pcm0[r], ref) < 1e-4, r
+
+
+def test_vyvotts_ragged_rows_decode_in_chunked_sub_batches():
+    """The chunked codec path with rows of different length: audio tokens behind the prompt's start-of-speech count, so 0 and 3
+    prompt frames plus two generated ones give 2 and 5 groups with chunks of 3 - chunk 0 decodes row 0 (2 groups) and row 1
+    (3 groups) apart, chunk 1 only row 1 (2 groups)."""
+    _, osn0, dsn0 = snac_pair(dict(SNAC_SMALL, noise=False))
+    V = mas.VyvoTokens
+    lm = _vyvo_lm(dsn0, codec_chunk_groups=3)
+    rng = np.random.default_rng(22)
+    head = [V.start_of_human, 11, 12, V.end_of_text, V.end_of_human, V.start_of_ai, V.start_of_speech]
+    prompts = [np.asarray(head + [V.audio_token_offset + (j % 7) * 4096 + int(rng.integers(0, 4096)) for j in range(7 * f)], np.int32)
+               for f in (0, 3)]
+    gp = mas.GenerateParameters(max_tokens=14, temperature=0.0, repetition_penalty=0.0, frame_constrained=True)
+    pcm, toks = lm.generate_batch(prompts, gp, return_tokens=True)
+    for r, groups in enumerate((2, 5)):
+        assert len(toks[r]) == 14 and len(pcm[r]) == groups * 2048
+        codes = oc.parse_output_row_vyvo(list(prompts[r]) + list(toks[r]))
+        assert len(codes) == 7 * groups
+        ref = oc.decode_audio_from_codes_chunked(codes, osn0, chunk_groups=3)
+        assert rms(pcm[r], ref) < 1e-4, r
 
 
 def test_device_group_two_logical_shards_equal_the_unsharded_call_bitwise(stack):
