@@ -13,6 +13,8 @@
 #include "lm_kernels.h"
 #include "step_loop.h"
 #include "lm_request.h"
+#include "lm_tensor_roles.h"
+#include "quant_intake.h"
 
 #include <math.h>
 #include <string.h>
@@ -141,89 +143,55 @@ extern "C" void mis_tts_destroy(mis_tts* c) {
     delete c;
 }
 
+// ---------------------------------------------------------------------------- weights: every key is named by lm_tensor_roles.h
+static LmDims lm_dims(const mis_tts* c) {
+    return {c->d, c->L, c->ff, c->H, c->Hkv, c->D, c->V, c->cfg.tie_word_embeddings != 0, c->cfg.qk_norm != 0};
+}
+static DevBuf<bf16_t>& dense_role(mis_tts* c, LmPack p) {
+    DevBuf<bf16_t>* const b[5] = {&c->wqkv, &c->wo, &c->wgu, &c->wdown, &c->lm_head};
+    return *b[p];
+}
+static mis_tts::QRole& code_role(mis_tts* c, LmPack p) {
+    mis_tts::QRole* const R[5] = {&c->q_qkv, &c->q_o, &c->q_gu, &c->q_down, &c->q_head};
+    return *R[p];
+}
+
 // staging (row-major bf16 [N][K]) -> destination by tensor role
-static void place_matrix(mis_tts* c, const std::string& name, int64_t N, int64_t K) {
+static void place_matrix(mis_tts* c, const LmTensorRole& r, const std::string& name, int64_t N, int64_t K) {
     hipStream_t s = c->stream;
-    auto starts = [&](const char* p) { return name.rfind(p, 0) == 0; };
-    if (name == "model.embed_tokens.weight") {
-        MIS_REQUIRE(N == c->V && K == c->d, MIS_ERR_INVALID_INPUT, "embed_tokens shape mismatch");
+    MIS_REQUIRE(r.error != LM_NAME_BAD, MIS_ERR_INVALID_INPUT, "bad tensor name %s", name.c_str());
+    MIS_REQUIRE(r.error != LM_NAME_LAYER_RANGE, MIS_ERR_INVALID_INPUT, "layer index out of range in %s", name.c_str());
+    MIS_REQUIRE(r.is_matrix(), MIS_ERR_INVALID_INPUT, "unexpected tensor %s", name.c_str());
+    MIS_REQUIRE(N == r.N && K == r.K, MIS_ERR_INVALID_INPUT, "%s shape mismatch",
+                r.kind == LM_EMBEDDING ? "embed_tokens" : r.kind == LM_HEAD ? "lm_head" : name.c_str());
+    if (r.kind == LM_EMBEDDING) {
         HIP_CHECK(hipMemcpyAsync(c->emb.p, c->staging.p, (size_t)N * K * 2, hipMemcpyDeviceToDevice, s));
         return;
     }
-    if (name == "lm_head.weight") {
-        MIS_REQUIRE(N == c->V && K == c->d, MIS_ERR_INVALID_INPUT, "lm_head shape mismatch");
-        launch_pack_weight(c->staging.p, c->lm_head.p, c->V, c->d, c->Vpad / 16, 1, 0, s);
-        c->have_lm_head = true;
-        return;
-    }
-    MIS_REQUIRE(starts("model.layers."), MIS_ERR_INVALID_INPUT, "unexpected tensor %s", name.c_str());
-    size_t p1 = strlen("model.layers.");
-    size_t p2 = name.find('.', p1);
-    MIS_REQUIRE(p2 != std::string::npos, MIS_ERR_INVALID_INPUT, "bad tensor name %s", name.c_str());
-    int li = atoi(name.substr(p1, p2 - p1).c_str());
-    MIS_REQUIRE(li >= 0 && li < c->L, MIS_ERR_INVALID_INPUT, "layer index out of range in %s", name.c_str());
-    std::string rest = name.substr(p2 + 1);
-    const int HD = c->H * c->D, KD = c->Hkv * c->D;
-    if (rest == "self_attn.q_proj.weight") {
-        MIS_REQUIRE(N == HD && K == c->d, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        bf16_t* dst = c->wqkv.p + layer_qkv_elems(c) * li;
-        launch_pack_weight(c->staging.p, dst, HD, c->d, HD / 16, 1, 0, s);
-    } else if (rest == "self_attn.k_proj.weight") {
-        MIS_REQUIRE(N == KD && K == c->d, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        bf16_t* dst = c->wqkv.p + layer_qkv_elems(c) * li;
-        launch_pack_weight(c->staging.p, dst, KD, c->d, KD / 16, 1, HD / 16, s);
-    } else if (rest == "self_attn.v_proj.weight") {
-        MIS_REQUIRE(N == KD && K == c->d, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        bf16_t* dst = c->wqkv.p + layer_qkv_elems(c) * li;
-        launch_pack_weight(c->staging.p, dst, KD, c->d, KD / 16, 1, (HD + KD) / 16, s);
-    } else if (rest == "self_attn.o_proj.weight") {
-        MIS_REQUIRE(N == c->d && K == HD, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        launch_pack_weight(c->staging.p, c->wo.p + layer_o_elems(c) * li, c->d, HD, c->d / 16, 1, 0, s);
-    } else if (rest == "mlp.gate_proj.weight" || rest == "mlp.up_proj.weight") {
-        MIS_REQUIRE(N == c->ff && K == c->d, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        launch_pack_weight(c->staging.p, c->wgu.p + layer_gu_elems(c) * li, c->ff, c->d, c->ff / 16, 2,
-                           rest == "mlp.gate_proj.weight" ? 0 : 1, s);
-    } else if (rest == "mlp.down_proj.weight") {
-        MIS_REQUIRE(N == c->d && K == c->ff, MIS_ERR_INVALID_INPUT, "%s shape mismatch", name.c_str());
-        launch_pack_weight(c->staging.p, c->wdown.p + layer_down_elems(c) * li, c->d, c->ff, c->d / 16, 1, 0, s);
-    } else {
-        throw MisError(MIS_ERR_INVALID_INPUT, "unexpected tensor " + name);
-    }
+    bf16_t* dst = dense_role(c, r.pack).p + (size_t)r.total_rows * r.K * r.layer;
+    launch_pack_weight(c->staging.p, dst, (int)N, (int)K, (int)(round_up(N, 16) / 16), r.tile_stride, r.tile_offset, s);
+    if (r.kind == LM_HEAD) c->have_lm_head = true;
 }
 
-// the same matrix in its quantised form (device pointers: MLX layout) -> the role's packed code / scale buffers
-static void place_qmatrix(mis_tts* c, const std::string& name, int64_t N, int64_t K, int bits, const uint32_t* wq, const bf16_t* sc,
-                          const bf16_t* bi) {
+// the same matrix in its quantised form (MLX layout, staged on the device) -> the role's packed code / scale buffers
+static void place_qmatrix(mis_tts* c, const LmTensorRole& r, const std::string& name, const QuantStaged& q) {
+    if (r.pack == LM_PACK_NONE) return;                                          // the embedding is gathered: bf16 rows only
     hipStream_t s = c->stream;
-    const int HD = c->H * c->D, KD = c->Hkv * c->D;
-    auto put = [&](mis_tts::QRole& R, int li, int n_layers, int64_t Ntot, int tile_stride, int tile_offset) {
-        if (R.bits && R.bits != bits) { R.bad = true; return; }
-        const size_t NTtot = round_up(Ntot, 16) / 16, KT = K / 32, G = K / 64;
-        const size_t q_layer = NTtot * KT * 64 * bits, sb_layer = NTtot * G * 32;
-        if (!R.bits) {
-            R.bits = bits; R.q_layer = q_layer; R.sb_layer = sb_layer;
-            R.q.alloc(q_layer * n_layers); R.sb.alloc(sb_layer * n_layers);
-            HIP_CHECK(hipMemsetAsync(R.q.p, 0, q_layer * n_layers, s));          // rows past N (vocabulary padding) decode to 0
-            HIP_CHECK(hipMemsetAsync(R.sb.p, 0, sb_layer * n_layers * 2, s));
-        }
-        if (R.q_layer != q_layer) { R.bad = true; return; }
-        launch_pack_qweight(bits, wq, sc, bi, R.q.p + q_layer * li, R.sb.p + sb_layer * li, (int)N, (int)K, tile_stride, tile_offset, s);
-        R.names.insert(name);
-    };
-    if (name == "lm_head.weight") { put(c->q_head, 0, 1, c->V, 1, 0); return; }
-    if (name.rfind("model.layers.", 0) != 0) return;
-    size_t p1 = strlen("model.layers."), p2 = name.find('.', p1);
-    if (p2 == std::string::npos) return;
-    const int li = atoi(name.substr(p1, p2 - p1).c_str());
-    if (li < 0 || li >= c->L) return;
-    const std::string rest = name.substr(p2 + 1);
-    if (rest == "self_attn.q_proj.weight") put(c->q_qkv, li, c->L, c->Nqkv, 1, 0);
-    else if (rest == "self_attn.k_proj.weight") put(c->q_qkv, li, c->L, c->Nqkv, 1, HD / 16);
-    else if (rest == "self_attn.v_proj.weight") put(c->q_qkv, li, c->L, c->Nqkv, 1, (HD + KD) / 16);
-    else if (rest == "self_attn.o_proj.weight") put(c->q_o, li, c->L, c->d, 1, 0);
-    else if (rest == "mlp.gate_proj.weight") put(c->q_gu, li, c->L, 2 * c->ff, 2, 0);
-    else if (rest == "mlp.up_proj.weight") put(c->q_gu, li, c->L, 2 * c->ff, 2, 1);
-    else if (rest == "mlp.down_proj.weight") put(c->q_down, li, c->L, c->d, 1, 0);
+    mis_tts::QRole& R = code_role(c, r.pack);
+    const int bits = q.bits, n_layers = r.pack == LM_PACK_HEAD ? 1 : c->L;
+    if (R.bits && R.bits != bits) { R.bad = true; return; }
+    const size_t NTtot = round_up(r.total_rows, 16) / 16, KT = q.K / 32, G = q.K / 64;
+    const size_t q_layer = NTtot * KT * 64 * bits, sb_layer = NTtot * G * 32;
+    if (!R.bits) {
+        R.bits = bits; R.q_layer = q_layer; R.sb_layer = sb_layer;
+        R.q.alloc(q_layer * n_layers); R.sb.alloc(sb_layer * n_layers);
+        HIP_CHECK(hipMemsetAsync(R.q.p, 0, q_layer * n_layers, s));          // rows past N (vocabulary padding) decode to 0
+        HIP_CHECK(hipMemsetAsync(R.sb.p, 0, sb_layer * n_layers * 2, s));
+    }
+    if (R.q_layer != q_layer) { R.bad = true; return; }
+    launch_pack_qweight(bits, q.wq(), (const bf16_t*)q.sc(), (const bf16_t*)q.bi(), R.q.p + q_layer * r.layer, R.sb.p + sb_layer * r.layer,
+                        (int)q.N, (int)q.K, r.tile_stride, r.tile_offset, s);
+    R.names.insert(name);
 }
 
 // a matrix that arrives in a form the code-streaming kernels cannot take (dense set_tensor, 2 bit, other group sizes / scale dtypes)
@@ -233,20 +201,15 @@ static void mark_dense_override(mis_tts* c, const std::string& name) {
         if (R->names.count(name)) R->bad = true;
 }
 
-static bf16_t* norm_slot(mis_tts* c, const std::string& name) {
-    if (name == "model.norm.weight") return c->norms.p + (size_t)2 * c->L * c->d;
-    size_t p1 = strlen("model.layers.");
-    if (name.rfind("model.layers.", 0) != 0) return nullptr;
-    size_t p2 = name.find('.', p1);
-    if (p2 == std::string::npos) return nullptr;
-    int li = atoi(name.substr(p1, p2 - p1).c_str());
-    if (li < 0 || li >= c->L) return nullptr;
-    std::string rest = name.substr(p2 + 1);
-    if (c->cfg.qk_norm && rest == "self_attn.q_norm.weight") return c->qknorm.p + (size_t)(2 * li) * c->D;
-    if (c->cfg.qk_norm && rest == "self_attn.k_norm.weight") return c->qknorm.p + (size_t)(2 * li + 1) * c->D;
-    if (rest == "input_layernorm.weight") return c->norms.p + (size_t)(2 * li) * c->d;
-    if (rest == "post_attention_layernorm.weight") return c->norms.p + (size_t)(2 * li + 1) * c->d;
-    return nullptr;
+static bf16_t* norm_slot(mis_tts* c, const LmTensorRole& r) {
+    switch (r.kind) {
+    case LM_FINAL_NORM: return c->norms.p + (size_t)2 * c->L * c->d;
+    case LM_INPUT_NORM: return c->norms.p + (size_t)(2 * r.layer) * c->d;
+    case LM_POST_NORM: return c->norms.p + (size_t)(2 * r.layer + 1) * c->d;
+    case LM_Q_NORM: return c->qknorm.p + (size_t)(2 * r.layer) * c->D;
+    case LM_K_NORM: return c->qknorm.p + (size_t)(2 * r.layer + 1) * c->D;
+    default: return nullptr;
+    }
 }
 
 extern "C" mis_status mis_tts_set_tensor(mis_tts* c, const char* name_, const void* data, mis_dtype dtype,
@@ -256,8 +219,8 @@ extern "C" mis_status mis_tts_set_tensor(mis_tts* c, const char* name_, const vo
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_F16 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported dtype");
     std::string name = name_;
-    if (name.find("rotary_emb.inv_freq") != std::string::npos) return MIS_OK;      // sanitize, LlamaTTS.swift:584-586
-    if (name == "lm_head.weight" && c->cfg.tie_word_embeddings) return MIS_OK;     // :588-590
+    const LmTensorRole r = lm_tensor_role(lm_dims(c), name);
+    if (r.kind == LM_IGNORED) return MIS_OK;
     HIP_CHECK(hipSetDevice(c->device));
     size_t n = 1;
     for (int i = 0; i < ndim; ++i) { MIS_REQUIRE(shape[i] > 0, MIS_ERR_INVALID_INPUT, "bad shape"); n *= (size_t)shape[i]; }
@@ -266,14 +229,13 @@ extern "C" mis_status mis_tts_set_tensor(mis_tts* c, const char* name_, const vo
     c->staging.alloc(n);
     HIP_CHECK(hipMemcpyAsync(c->raw_staging.p, data, n * esz, hipMemcpyDefault, c->stream));
     if (ndim == 1) {
-        bf16_t* slot = norm_slot(c, name);
-        bool is_qk = name.find("_norm.weight") != std::string::npos && name.find("self_attn.") != std::string::npos;
-        MIS_REQUIRE(slot && (int64_t)n == (is_qk ? c->D : c->d), MIS_ERR_INVALID_INPUT, "unexpected 1-D tensor %s", name.c_str());
+        bf16_t* slot = norm_slot(c, r);
+        MIS_REQUIRE(slot && (int64_t)n == r.N, MIS_ERR_INVALID_INPUT, "unexpected 1-D tensor %s", name.c_str());
         launch_convert_to_bf16(c->raw_staging.p, dtype, slot, n, c->stream);
     } else {
         MIS_REQUIRE(ndim == 2, MIS_ERR_INVALID_INPUT, "tensor %s must be 1-D or 2-D", name.c_str());
         launch_convert_to_bf16(c->raw_staging.p, dtype, c->staging.p, n, c->stream);
-        place_matrix(c, name, shape[0], shape[1]);
+        place_matrix(c, r, name, shape[0], shape[1]);
         mark_dense_override(c, name);
     }
     HIP_CHECK(hipGetLastError());
@@ -282,33 +244,21 @@ extern "C" mis_status mis_tts_set_tensor(mis_tts* c, const char* name_, const vo
     MIS_API_END
 }
 
-// A Linear / Embedding stored in MLX's affine-quantised form (`weight` uint32 [N, K*bits/32], `scales` / `biases` [N, K/group],
-// written by mlx quantize; the reference re-creates QuantizedLinear modules for every path that has `.scales`,
-// LlamaTTS.swift:958-968).  The matrix is dequantised once at load into the engine's bf16 layouts.
+// A Linear / Embedding stored in MLX's affine-quantised form (quant_intake.h; the reference re-creates QuantizedLinear modules for every
+// path that has `.scales`, LlamaTTS.swift:958-968).  The matrix is dequantised once at load into the engine's bf16 layouts.
 static void set_quantized_any(mis_tts* c, const std::string& name, const uint32_t* wq, const void* scales, const void* biases,
                               mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits) {
-    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d (2, 4 or 8 bits)", bits);
-    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT,
-                "bad quantised shape for %s", name.c_str());
-    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
-    if (name == "lm_head.weight" && c->cfg.tie_word_embeddings) return;
+    quant_check_args(name.c_str(), sb_dtype, N, K, group_size, bits);
+    const LmTensorRole r = lm_tensor_role(lm_dims(c), name);
+    if (r.kind == LM_IGNORED && name == "lm_head.weight") return;                  // tied (inv_freq has no quantised form: refused below)
     HIP_CHECK(hipSetDevice(c->device));
-    const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
-    const size_t wb = round_up(words * 4, 16), sb = round_up(ng * esz, 16);
-    c->raw_staging.alloc(wb + 2 * sb);
-    uint8_t* p = c->raw_staging.p;
-    uint8_t* ps = p + wb;
-    uint8_t* pb = ps + sb;
-    HIP_CHECK(hipMemcpyAsync(p, wq, words * 4, hipMemcpyDefault, c->stream));
-    HIP_CHECK(hipMemcpyAsync(ps, scales, ng * esz, hipMemcpyDefault, c->stream));
-    HIP_CHECK(hipMemcpyAsync(pb, biases, ng * esz, hipMemcpyDefault, c->stream));
+    QuantStaged q;
+    q.stage(wq, scales, biases, sb_dtype, N, K, group_size, bits, c->stream);
     c->staging.alloc((size_t)N * K);
-    launch_dequant_affine((const uint32_t*)p, ps, pb, (int)sb_dtype, c->staging.p, (int)N, (int)K, group_size, bits, c->stream);
-    place_matrix(c, name, N, K);
+    q.dequantise(c->staging.p, c->stream);
+    place_matrix(c, r, name, N, K);
     // native form (see QRole): bf16 scales are exact in the kernel's float32 arithmetic; anything else keeps the bf16 copy only
-    static const bool native = !(getenv("MIS_QUANT_NATIVE") && atoi(getenv("MIS_QUANT_NATIVE")) == 0);
-    if (native && (bits == 8 || bits == 4) && group_size == 64 && sb_dtype == MIS_BF16 && K % 64 == 0 && (N % 16 == 0 || name == "lm_head.weight"))
-        place_qmatrix(c, name, N, K, bits, (const uint32_t*)p, (const bf16_t*)ps, (const bf16_t*)pb);
+    if (quant_streamable(bits, group_size, K, sb_dtype, QUANT_SB_BF16) && (N % 16 == 0 || r.kind == LM_HEAD)) place_qmatrix(c, r, name, q);
     else mark_dense_override(c, name);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -332,103 +282,47 @@ extern "C" int mis_tts_native_quant_bits(const mis_tts* c, int role) {
     return (role >= 0 && role < 5 && R[role]->on) ? R[role]->bits : 0;
 }
 
-// benches: every Linear as a synthetic MLX-quantised matrix (random codes, group scale ~ 2 amp / (2^bits - 1), bias ~ -amp), group 64,
-// bf16 scales - there are no checkpoints offline.  The embedding stays dense.
-__global__ void k_synth_quant(uint32_t* __restrict__ wq, bf16_t* __restrict__ sc, bf16_t* __restrict__ bi, size_t words, size_t groups,
-                              uint64_t key, float amp, int bits) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < words) wq[i] = (uint32_t)(mis_splitmix64(key * 0x9E3779B97F4A7C15ull + i) >> 16);
-    if (i < groups) {
-        const float jitter = 1.0f + 0.25f * mis_synth_value(key ^ 0x5bd1e995ull, i, 1.0f);
-        sc[i] = f32_to_bf16(2.0f * amp * jitter / (float)((1 << bits) - 1));
-        bi[i] = f32_to_bf16(-amp * jitter);
+// benches: mis-synth-v1 weights, keys / amplitudes of oracle/llama.py make_synthetic_weights (lm_required_tensors).  bits 8 / 4: every
+// Linear as a synthetic MLX-quantised matrix (launch_synth_quant: group 64, bf16 scales) through the checkpoint path - there are no
+// checkpoints offline.  The embedding stays dense.
+static void tts_synth(mis_tts* c, uint64_t seed, int bits) {
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const LmDims dims = lm_dims(c);
+    const uint64_t base = seed * 100000ull;
+    DevBuf<uint32_t> wq; DevBuf<bf16_t> sc, bi;
+    const std::vector<LmRequiredTensor> tensors = lm_required_tensors(dims);
+    size_t big = 0;                          // one staging buffer for every matrix: fills and packs queue up behind each other on s
+    for (const LmRequiredTensor& t : tensors) { const LmTensorRole r = lm_tensor_role(dims, t.name); big = std::max(big, (size_t)(r.N * r.K)); }
+    c->staging.alloc(big);
+    for (const LmRequiredTensor& t : tensors) {
+        const LmTensorRole r = lm_tensor_role(dims, t.name);
+        if (r.is_vector()) {
+            launch_synth_fill_bf16(norm_slot(c, r), (size_t)r.N, base + t.key, (float)t.amp, t.plus_one, s);
+        } else if (bits && r.kind != LM_EMBEDDING) {
+            const size_t words = (size_t)r.N * r.K * bits / 32, groups = (size_t)r.N * (r.K / 64);
+            wq.alloc(words); sc.alloc(groups); bi.alloc(groups);
+            launch_synth_quant(wq.p, sc.p, bi.p, words, groups, base + t.key, (float)t.amp, bits, MIS_BF16, s);
+            set_quantized_any(c, t.name, wq.p, sc.p, bi.p, MIS_BF16, r.N, r.K, 64, bits);
+        } else {
+            launch_synth_fill_bf16(c->staging.p, (size_t)r.N * r.K, base + t.key, (float)t.amp, 0, s);
+            place_matrix(c, r, t.name, r.N, r.K);
+        }
+        c->loaded.insert(t.name);
     }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 extern "C" mis_status mis_tts_init_synthetic_quantized(mis_tts* c, uint64_t seed, int bits) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && !c->finalized && (bits == 4 || bits == 8), MIS_ERR_INVALID_INPUT, "bad argument");
-    HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int d = c->d, ff = c->ff, HD = c->H * c->D, KD = c->Hkv * c->D;
-    const uint64_t base = seed * 100000ull;
-    DevBuf<uint32_t> wq; DevBuf<bf16_t> sc, bi;
-    auto mat = [&](const std::string& name, uint64_t key, int64_t N, int64_t K, double amp) {
-        const size_t words = (size_t)N * K * bits / 32, groups = (size_t)N * (K / 64);
-        wq.alloc(words); sc.alloc(groups); bi.alloc(groups);
-        hipLaunchKernelGGL(k_synth_quant, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, wq.p, sc.p, bi.p, words, groups, base + key, (float)amp, bits);
-        HIP_CHECK(hipStreamSynchronize(s));
-        set_quantized_any(c, name, wq.p, sc.p, bi.p, MIS_BF16, N, K, 64, bits);
-    };
-    auto vec = [&](const std::string& name, uint64_t key) {
-        bool is_qk = name.find("self_attn.") != std::string::npos;
-        launch_synth_fill_bf16(norm_slot(c, name), (size_t)(is_qk ? c->D : d), base + key, 0.1f, 1, s);
-        c->loaded.insert(name);
-    };
-    c->staging.alloc((size_t)c->V * d);
-    launch_synth_fill_bf16(c->staging.p, (size_t)c->V * d, base + 1, (float)(0.5 * sqrt(3.0)), 0, s);
-    place_matrix(c, "model.embed_tokens.weight", c->V, d);
-    c->loaded.insert("model.embed_tokens.weight");
-    HIP_CHECK(hipStreamSynchronize(s));
-    vec("model.norm.weight", 2);
-    if (!c->cfg.tie_word_embeddings) mat("lm_head.weight", 3, c->V, d, sqrt(3.0 / d) * 2.0);
-    for (int li = 0; li < c->L; ++li) {
-        std::string p = "model.layers." + std::to_string(li);
-        uint64_t k = 100 + (uint64_t)li * 16;
-        vec(p + ".input_layernorm.weight", k + 0);
-        vec(p + ".post_attention_layernorm.weight", k + 1);
-        mat(p + ".self_attn.q_proj.weight", k + 2, HD, d, sqrt(3.0 / d) * 1.5);
-        mat(p + ".self_attn.k_proj.weight", k + 3, KD, d, sqrt(3.0 / d) * 1.5);
-        mat(p + ".self_attn.v_proj.weight", k + 4, KD, d, sqrt(3.0 / d));
-        mat(p + ".self_attn.o_proj.weight", k + 5, d, HD, sqrt(3.0 / HD) * 0.5);
-        mat(p + ".mlp.gate_proj.weight", k + 6, ff, d, sqrt(3.0 / d));
-        mat(p + ".mlp.up_proj.weight", k + 7, ff, d, sqrt(3.0 / d));
-        mat(p + ".mlp.down_proj.weight", k + 8, d, ff, sqrt(3.0 / ff) * 0.5);
-        if (c->cfg.qk_norm) { vec(p + ".self_attn.q_norm.weight", k + 9); vec(p + ".self_attn.k_norm.weight", k + 10); }
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(s));
+    tts_synth(c, seed, bits);
     MIS_API_END
 }
-
 extern "C" mis_status mis_tts_init_synthetic(mis_tts* c, uint64_t seed) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
-    HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const int d = c->d, ff = c->ff, HD = c->H * c->D, KD = c->Hkv * c->D;
-    const uint64_t base = seed * 100000ull;
-    size_t big = std::max((size_t)c->V * d, (size_t)ff * d);
-    c->staging.alloc(big);
-    // keys / amplitudes: oracle/llama.py make_synthetic_weights
-    auto mat = [&](const std::string& name, uint64_t key, int64_t N, int64_t K, double amp) {
-        launch_synth_fill_bf16(c->staging.p, (size_t)N * K, base + key, (float)amp, 0, s);
-        place_matrix(c, name, N, K);
-        c->loaded.insert(name);
-    };
-    auto vec = [&](const std::string& name, uint64_t key) {
-        bool is_qk = name.find("self_attn.") != std::string::npos;
-        launch_synth_fill_bf16(norm_slot(c, name), (size_t)(is_qk ? c->D : d), base + key, 0.1f, 1, s);
-        c->loaded.insert(name);
-    };
-    mat("model.embed_tokens.weight", 1, c->V, d, 0.5 * sqrt(3.0));
-    vec("model.norm.weight", 2);
-    if (!c->cfg.tie_word_embeddings) mat("lm_head.weight", 3, c->V, d, sqrt(3.0 / d) * 2.0);
-    for (int li = 0; li < c->L; ++li) {
-        std::string p = "model.layers." + std::to_string(li);
-        uint64_t k = 100 + (uint64_t)li * 16;
-        vec(p + ".input_layernorm.weight", k + 0);
-        vec(p + ".post_attention_layernorm.weight", k + 1);
-        mat(p + ".self_attn.q_proj.weight", k + 2, HD, d, sqrt(3.0 / d) * 1.5);
-        mat(p + ".self_attn.k_proj.weight", k + 3, KD, d, sqrt(3.0 / d) * 1.5);
-        mat(p + ".self_attn.v_proj.weight", k + 4, KD, d, sqrt(3.0 / d));
-        mat(p + ".self_attn.o_proj.weight", k + 5, d, HD, sqrt(3.0 / HD) * 0.5);
-        mat(p + ".mlp.gate_proj.weight", k + 6, ff, d, sqrt(3.0 / d));
-        mat(p + ".mlp.up_proj.weight", k + 7, ff, d, sqrt(3.0 / d));
-        mat(p + ".mlp.down_proj.weight", k + 8, d, ff, sqrt(3.0 / ff) * 0.5);
-        if (c->cfg.qk_norm) { vec(p + ".self_attn.q_norm.weight", k + 9); vec(p + ".self_attn.k_norm.weight", k + 10); }
-    }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(s));
+    tts_synth(c, seed, 0);
     MIS_API_END
 }
 
@@ -437,20 +331,8 @@ extern "C" mis_status mis_tts_finalize(mis_tts* c) {
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
     HIP_CHECK(hipSetDevice(c->device));
     // update(parameters:verify:.all), LlamaTTS.swift:971: every parameter must be present
-    std::vector<std::string> want = {"model.embed_tokens.weight", "model.norm.weight"};
-    if (!c->cfg.tie_word_embeddings) want.push_back("lm_head.weight");
-    const char* per_layer[] = {"input_layernorm.weight", "post_attention_layernorm.weight", "self_attn.q_proj.weight",
-                               "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
-                               "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight"};
-    for (int li = 0; li < c->L; ++li) {
-        for (const char* r : per_layer) want.push_back("model.layers." + std::to_string(li) + "." + r);
-        if (c->cfg.qk_norm) {
-            want.push_back("model.layers." + std::to_string(li) + ".self_attn.q_norm.weight");
-            want.push_back("model.layers." + std::to_string(li) + ".self_attn.k_norm.weight");
-        }
-    }
-    for (auto& w : want)
-        MIS_REQUIRE(c->loaded.count(w), MIS_ERR_NOT_INITIALIZED, "LM weight missing: %s", w.c_str());
+    for (const LmRequiredTensor& t : lm_required_tensors(lm_dims(c)))
+        MIS_REQUIRE(c->loaded.count(t.name), MIS_ERR_NOT_INITIALIZED, "LM weight missing: %s", t.name.c_str());
     if (c->cfg.tie_word_embeddings)        // embedTokens.asLinear, LlamaTTS.swift:563
         launch_pack_weight(c->emb.p, c->lm_head.p, c->V, c->d, c->Vpad / 16, 1, 0, c->stream);
     HIP_CHECK(hipGetLastError());

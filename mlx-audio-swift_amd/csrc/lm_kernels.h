@@ -17,6 +17,9 @@ void launch_dequant_affine(const uint32_t* wq, const void* scales, const void* b
 void launch_pack_weight(const bf16_t* src, bf16_t* dst, int N, int K, int NT, int tile_stride, int tile_offset,
                         hipStream_t s);
 void launch_synth_fill_bf16(bf16_t* dst, size_t n, uint64_t key, float amp, int plus_one, hipStream_t s);
+// a synthetic MLX-quantised matrix: words code words, groups (= N * K / 64) scales and biases of sb_dtype MIS_BF16 / MIS_F16
+void launch_synth_quant(uint32_t* wq, uint16_t* scales, uint16_t* biases, size_t words, size_t groups, uint64_t key, float amp, int bits,
+                        int sb_dtype, hipStream_t s);
 
 void launch_prefill_feed(const int32_t* prompt, const int32_t* lens, int Lmax, int* step_counter, int32_t* ids,
                          uint8_t* active, int batch, hipStream_t s);

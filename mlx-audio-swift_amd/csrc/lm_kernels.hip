@@ -110,6 +110,25 @@ void launch_synth_fill_bf16(bf16_t* dst, size_t n, uint64_t key, float amp, int 
     hipLaunchKernelGGL(k_synth_fill_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, n, key, amp, plus_one);
 }
 
+// benches: a synthetic MLX-quantised matrix (random codes, group scale ~ 2 amp / (2^bits - 1), bias ~ -amp: values within +-amp), group 64,
+// scales / biases in bf16 or f16 (sb_dtype MIS_BF16 / MIS_F16)
+__global__ void k_synth_quant(uint32_t* __restrict__ wq, uint16_t* __restrict__ sc, uint16_t* __restrict__ bi, size_t words, size_t groups,
+                              uint64_t key, float amp, int bits, int sb_dtype) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < words) wq[i] = (uint32_t)(mis_splitmix64(key * 0x9E3779B97F4A7C15ull + i) >> 16);
+    if (i < groups) {
+        const float jitter = 1.0f + 0.25f * mis_synth_value(key ^ 0x5bd1e995ull, i, 1.0f);
+        const float sv = 2.0f * amp * jitter / (float)((1 << bits) - 1), bv = -amp * jitter;
+        sc[i] = sb_dtype == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)sv) : f32_to_bf16(sv);
+        bi[i] = sb_dtype == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)bv) : f32_to_bf16(bv);
+    }
+}
+void launch_synth_quant(uint32_t* wq, uint16_t* scales, uint16_t* biases, size_t words, size_t groups, uint64_t key, float amp, int bits,
+                        int sb_dtype, hipStream_t s) {
+    if (!words) return;
+    hipLaunchKernelGGL(k_synth_quant, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, wq, scales, biases, words, groups, key, amp, bits, sb_dtype);
+}
+
 // (Round 3, measured and removed again: reading the NEXT launches' weights into the 256 MB Infinity Cache ahead of time.  As a forked
 // branch of the step graph every fork cost ~16 us on ROCm 7.2 (step 2.13 -> 2.95..4.1 ms); as extra blocks of the chain's own launches
 // - glue, split-K GEMMs, the attention waves that run out of key tiles - every schedule was slower too (2.144 -> 2.17..2.35 ms): the

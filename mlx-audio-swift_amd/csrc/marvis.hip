@@ -29,6 +29,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lm_kernels.h"
+#include "quant_intake.h"
 #include "sampler_math.h"
 #include "step_loop.h"
 
@@ -516,9 +517,7 @@ extern "C" mis_status mis_marvis_set_tensor_quantized(mis_marvis* c, const char*
     MIS_API_BEGIN
     MIS_REQUIRE(c && name_ && wq && scales && biases, MIS_ERR_INVALID_INPUT, "null argument");
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
-    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d", bits);
-    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT, "bad quantised shape for %s", name_);
-    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
+    quant_check_args(name_, sb_dtype, N, K, group_size, bits);
     const std::string name = name_;
     HIP_CHECK(hipSetDevice(c->device));
     mis_tts* lm = nullptr;
@@ -541,15 +540,11 @@ extern "C" mis_status mis_marvis_set_tensor_quantized(mis_marvis* c, const char*
         c->loaded.insert(name);
         return MIS_OK;
     }
-    const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
-    DevBuf<uint8_t> raw;
+    QuantStaged q;
     DevBuf<bf16_t> rows;
-    const size_t wb = round_up(words * 4, 16), sb = round_up(ng * esz, 16);
-    raw.alloc(wb + 2 * sb); rows.alloc((size_t)N * K);
-    HIP_CHECK(hipMemcpyAsync(raw.p, wq, words * 4, hipMemcpyDefault, c->s));
-    HIP_CHECK(hipMemcpyAsync(raw.p + wb, scales, ng * esz, hipMemcpyDefault, c->s));
-    HIP_CHECK(hipMemcpyAsync(raw.p + wb + sb, biases, ng * esz, hipMemcpyDefault, c->s));
-    launch_dequant_affine((const uint32_t*)raw.p, raw.p + wb, raw.p + wb + sb, (int)sb_dtype, rows.p, (int)N, (int)K, group_size, bits, c->s);
+    q.stage(wq, scales, biases, sb_dtype, N, K, group_size, bits, c->s);
+    rows.alloc((size_t)N * K);
+    q.dequantise(rows.p, c->s);
     HIP_CHECK(hipStreamSynchronize(c->s));
     const int64_t shape[2] = {N, K};
     return mis_marvis_set_tensor(c, name_, rows.p, MIS_BF16, shape, 2);

@@ -8,6 +8,7 @@
 // an exact-f32 MFMA contraction against a host-built inverse-DFT table and the overlap-add is one gather kernel.
 // Activations are NCT ([B][C][T], time contiguous) so the f32 codec kernels of snac.hip are reused unchanged.
 #include "common.h"
+#include "quant_intake.h"
 #include "host_weights.h"
 #include "kernels.h"
 #include "codec_kernels.h"
@@ -250,10 +251,7 @@ extern "C" mis_status mis_soprano_set_tensor_quantized(mis_soprano* c, const cha
     MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_tensor after finalize");
     const std::string name = sop_sanitize(name_);
     if (name.rfind("decoder.", 0) != 0) return mis_tts_set_tensor_quantized(c->lm, name.c_str(), wq, scales, biases, sb_dtype, N, K, group_size, bits);
-    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d (2, 4 or 8 bits)", bits);
-    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT,
-                "bad quantised shape for %s", name.c_str());
-    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
+    quant_check_args(name.c_str(), sb_dtype, N, K, group_size, bits);
     HIP_CHECK(hipSetDevice(c->device));
     const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
     std::vector<uint32_t> w(words);

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "lm_kernels.h"
+#include "quant_intake.h"
 #include "step_loop.h"
 #include "whisper_kernels.h"
 
@@ -20,17 +21,6 @@
 struct WTensor {
     DevBuf<bf16_t> buf;
     std::vector<int64_t> shape;
-};
-// a matrix held in MLX's affine-quantised form until finalize: codes | scales | biases in one device buffer
-struct QRaw {
-    DevBuf<uint8_t> buf;
-    int64_t N = 0, K = 0;
-    int group = 0, bits = 0;
-    mis_dtype sbt = MIS_BF16;
-    size_t wb = 0, sb = 0;                   // byte offsets of scales and biases
-    const uint32_t* wq() const { return reinterpret_cast<const uint32_t*>(buf.p); }
-    const void* sc() const { return buf.p + wb; }
-    const void* bi() const { return buf.p + sb; }
 };
 // a decoder matrix streamed as codes (lm_qgemm.hip layouts); bits == 0: the bf16 packed copy is streamed instead
 struct QW { int bits = 0; int sbt = MIS_BF16; const void* q = nullptr; const bf16_t* sb = nullptr; };
@@ -48,7 +38,7 @@ struct mis_whisper {
     mis_whisper_config cfg{};
     int d = 0, He = 0, Hd = 0, D = 0, V = 0, Vpad = 0, nmel = 0, K1 = 0;
     std::map<std::string, std::unique_ptr<WTensor>> raw;
-    std::map<std::string, std::unique_ptr<QRaw>> qraw;    // natively streamable quantised matrices (mis_whisper_set_tensor_quantized)
+    std::map<std::string, std::unique_ptr<QuantStaged>> qraw;    // matrices held as codes until finalize (mis_whisper_set_tensor_quantized)
     bool finalized = false;
     DevBuf<bf16_t> arena;                    // all assembled weights (bf16)
     DevBuf<uint8_t> qarena;                  // codes and scale / bias tables of the natively streamed decoder matrices
@@ -211,34 +201,23 @@ static bool whisper_streamed_matrix(const std::string& name) {
 // everything else is dequantised here into the bf16 form set_tensor produces.
 static void whisper_set_quantized(mis_whisper* c, const std::string& name_in, const uint32_t* wq, const void* scales, const void* biases,
                                   mis_dtype sb_dtype, int64_t N, int64_t K, int group_size, int bits) {
-    MIS_REQUIRE(bits == 2 || bits == 4 || bits == 8, MIS_ERR_INVALID_INPUT, "unsupported quantisation width %d (2, 4 or 8 bits)", bits);
-    MIS_REQUIRE(group_size >= 1 && N >= 1 && K >= 1 && K % group_size == 0 && K % (32 / bits) == 0, MIS_ERR_INVALID_INPUT,
-                "bad quantised shape for %s", name_in.c_str());
-    MIS_REQUIRE(sb_dtype == MIS_F32 || sb_dtype == MIS_F16 || sb_dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "unsupported scale dtype");
+    quant_check_args(name_in.c_str(), sb_dtype, N, K, group_size, bits);
     const std::string name = whisper_canonical_name(name_in);
     if (name.empty()) return;                                                      // proj_out.{weight,scales,biases}: tied
     MIS_REQUIRE(name.size() > 7 && name.compare(name.size() - 7, 7, ".weight") == 0, MIS_ERR_INVALID_INPUT,
                 "quantised tensor %s: expected the .weight key of a Linear / Embedding", name_in.c_str());
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    auto q = std::make_unique<QRaw>();
-    const size_t words = (size_t)N * K * bits / 32, ng = (size_t)N * (K / group_size), esz = sb_dtype == MIS_F32 ? 4 : 2;
-    q->N = N; q->K = K; q->group = group_size; q->bits = bits; q->sbt = sb_dtype;
-    q->wb = round_up(words * 4, 256); q->sb = q->wb + round_up(ng * esz, 256);
-    q->buf.alloc(q->sb + ng * esz);
-    HIP_CHECK(hipMemcpyAsync(q->buf.p, wq, words * 4, hipMemcpyDefault, s));
-    HIP_CHECK(hipMemcpyAsync(q->buf.p + q->wb, scales, ng * esz, hipMemcpyDefault, s));
-    HIP_CHECK(hipMemcpyAsync(q->buf.p + q->sb, biases, ng * esz, hipMemcpyDefault, s));
-    static const bool native = !(getenv("MIS_QUANT_NATIVE") && atoi(getenv("MIS_QUANT_NATIVE")) == 0);
-    if (native && (bits == 8 || bits == 4) && group_size == 64 && (sb_dtype == MIS_BF16 || sb_dtype == MIS_F16) && K % 64 == 0 &&
-        whisper_streamed_matrix(name)) {
+    auto q = std::make_unique<QuantStaged>();
+    q->stage(wq, scales, biases, sb_dtype, N, K, group_size, bits, s);
+    if (quant_streamable(bits, group_size, K, sb_dtype, QUANT_SB_BF16 | QUANT_SB_F16) && whisper_streamed_matrix(name)) {
         c->qraw[name] = std::move(q);
         c->raw.erase(name);
     } else {
         auto t = std::make_unique<WTensor>();
         t->shape = {N, K};
         t->buf.alloc((size_t)N * K);
-        launch_dequant_affine(q->wq(), q->sc(), q->bi(), (int)sb_dtype, t->buf.p, (int)N, (int)K, group_size, bits, s);
+        q->dequantise(t->buf.p, s);
         c->raw[name] = std::move(t);
         c->qraw.erase(name);
     }
@@ -283,14 +262,14 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     const std::string E = "model.encoder", Dd = "model.decoder";
     // ---- which decoder matrices stream as codes.  A layer's q|k|v is one matrix: native only if all three projections share bits and
     // scale dtype; otherwise (and for every matrix finalize does not stream) the quantised tensors are dequantised into the bf16 form.
-    auto qfind = [&](const std::string& name) -> QRaw* { auto it = c->qraw.find(name); return it == c->qraw.end() ? nullptr : it->second.get(); };
+    auto qfind = [&](const std::string& name) -> QuantStaged* { auto it = c->qraw.find(name); return it == c->qraw.end() ? nullptr : it->second.get(); };
     auto densify = [&](const std::string& name) {
-        QRaw* q = qfind(name);
+        QuantStaged* q = qfind(name);
         if (!q || c->raw.count(name)) return;
         auto t = std::make_unique<WTensor>();
         t->shape = {q->N, q->K};
         t->buf.alloc((size_t)q->N * q->K);
-        launch_dequant_affine(q->wq(), q->sc(), q->bi(), (int)q->sbt, t->buf.p, (int)q->N, (int)q->K, q->group, q->bits, s);
+        q->dequantise(t->buf.p, s);
         c->raw[name] = std::move(t);
     };
     static const char* const ROLE_NAMES[WQ_ROLES][3] = {
@@ -306,10 +285,10 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
         for (int r = 0; r < WQ_ROLES; ++r) {
             rbits[li][r] = 0; rsbt[li][r] = MIS_BF16;
             const int parts = r == WQ_SQKV ? 3 : 1;
-            QRaw* first = qfind(q + ROLE_NAMES[r][0]);
+            QuantStaged* first = qfind(q + ROLE_NAMES[r][0]);
             bool ok = first != nullptr;
             for (int j = 0; j < parts && ok; ++j) {
-                QRaw* x = qfind(q + ROLE_NAMES[r][j]);
+                QuantStaged* x = qfind(q + ROLE_NAMES[r][j]);
                 ok = x && x->bits == first->bits && x->sbt == first->sbt && x->N == role_N[r] / parts && x->K == role_K[r];
             }
             if (ok) {
@@ -321,7 +300,7 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
             }
         }
     }
-    QRaw* qemb = qfind(Dd + ".embed_tokens.weight");
+    QuantStaged* qemb = qfind(Dd + ".embed_tokens.weight");
     const bool vocab_native = qemb && qemb->N == V && qemb->K == d;
     if (vocab_native) { qbytes += qsize(c->Vpad / 16, d, qemb->bits); dense_saved += (size_t)c->Vpad * d; }
     densify(Dd + ".embed_tokens.weight");                     // the gather table is always bf16 (QuantizedEmbedding: dequantised rows)
@@ -355,7 +334,7 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
         MIS_REQUIRE(qoff <= qbytes, MIS_ERR_GENERATION_FAILED, "code arena overflow");
     };
     auto qpack = [&](const QW& w, const std::string& name, int tile_offset) {
-        const QRaw* q = qfind(name);
+        const QuantStaged* q = qfind(name);
         launch_pack_qweight(q->bits, q->wq(), (const bf16_t*)q->sc(), (const bf16_t*)q->bi(), const_cast<void*>(w.q), const_cast<bf16_t*>(w.sb),
                             (int)q->N, (int)q->K, 1, tile_offset, s);
     };
@@ -473,20 +452,6 @@ extern "C" mis_status mis_whisper_finalize(mis_whisper* c) {
     MIS_API_END
 }
 
-// benches: a synthetic MLX-quantised matrix (random codes, group scale ~ 2 amp / (2^bits - 1), bias ~ -amp: values within +-amp), group 64,
-// scales / biases in bf16 (sbt 2) or f16 (sbt 1)
-__global__ void k_whisper_synth_quant(uint32_t* __restrict__ wq, uint16_t* __restrict__ sc, uint16_t* __restrict__ bi, size_t words,
-                                      size_t groups, uint64_t key, float amp, int bits, int sbt) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < words) wq[i] = (uint32_t)(mis_splitmix64(key * 0x9E3779B97F4A7C15ull + i) >> 16);
-    if (i < groups) {
-        const float jitter = 1.0f + 0.25f * mis_synth_value(key ^ 0x5bd1e995ull, i, 1.0f);
-        const float sv = 2.0f * amp * jitter / (float)((1 << bits) - 1), bv = -amp * jitter;
-        sc[i] = sbt == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)sv) : f32_to_bf16(sv);
-        bi[i] = sbt == MIS_F16 ? __builtin_bit_cast(uint16_t, (_Float16)bv) : f32_to_bf16(bv);
-    }
-}
-
 // mis-synth-v1 weights, same key order / amplitudes as oracle/whisper.py make_synthetic_weights (bits == 0).  bits 8 / 4: every Linear
 // and the token embedding as a synthetic quantised matrix through the checkpoint path (mis_whisper_init_synthetic_quantized).
 static void whisper_synth(mis_whisper* c, uint64_t seed, int bits, mis_dtype sbt) {
@@ -498,10 +463,7 @@ static void whisper_synth(mis_whisper* c, uint64_t seed, int bits, mis_dtype sbt
     auto qmat = [&](const std::string& name, int64_t N, int64_t K, double amp) {
         const size_t words = (size_t)N * K * bits / 32, groups = (size_t)N * (K / 64);
         qw.alloc(words); qs.alloc(groups); qb.alloc(groups);
-        hipLaunchKernelGGL(k_whisper_synth_quant, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, qw.p, qs.p, qb.p, words, groups, ++key,
-                           (float)amp, bits, (int)sbt);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(s));
+        launch_synth_quant(qw.p, qs.p, qb.p, words, groups, ++key, (float)amp, bits, (int)sbt, s);
         whisper_set_quantized(c, name, qw.p, qs.p, qb.p, sbt, N, K, 64, bits);
     };
     auto put = [&](const std::string& name, std::vector<int64_t> shape, double amp, int plus_one) {
