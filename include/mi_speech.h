@@ -1190,6 +1190,54 @@ mis_status mis_qwen3tts_group_generate(mis_qwen3tts* const* replicas, int n, con
                                        int32_t* n_frames, int chunk_frames, mis_event_cb on_event, void* user,
                                        const volatile int* cancel_flag);
 
+/* ------------------------------------------------------------------------------------------
+ * BigVGAN vocoder (csrc/bigvgan.hip; Sources/MLXAudioCodecs/BigVGAN): mel [batch, num_mels, frames] -> waveform, hop = the product of
+ * upsample_rates samples a frame.  conv_pre (7 taps); per stage a weight-normalised transposed conv (kernel 2 x stride, pad stride / 2)
+ * and the mean of num_kernels AMP blocks (resblock 1: x + convs2(act(convs1(act(x)))) per dilation; 2: x + convs(act(x))); then
+ * activation_post, conv_post (7 taps -> 1 channel) and tanh or clip(-1, 1).  Every act is the anti-aliased Activation1d: 2 x Kaiser-sinc
+ * up-sampling with edge padding (12 taps, cutoff 0.25, half width 0.3), Snake / SnakeBeta, 2 x low-pass down-sampling with edge padding.
+ * All of it exact f32, weight norm folded at finalize in double.  1..max_batch ragged rows a call, each of 1..max_frames frames, inside
+ * one workspace sized at finalize: a call allocates nothing and synchronises once.  A row's waveform does not depend on the batch it
+ * travels in or on what lies behind its own frames: bit for bit.
+ * Rejected with MIS_ERR_INVALID_INPUT at create: upsample_kernel_sizes[i] != 2 upsample_rates[i], an odd or out-of-range rate, an even
+ * resblock kernel or one above 11 taps, a dilation above 5, sizes outside the ranges the messages name; at finalize a tensor missing or
+ * misshapen; at a call batch outside 1..max_batch, a stride above max_frames, a frame count outside 1..stride, a null pointer, a handle
+ * that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_bigvgan mis_bigvgan;
+/* BigVGANConfig's eleven fields (lists with their counts) + the sizes of the workspace */
+typedef struct {
+    int32_t num_mels;
+    int32_t n_upsamples, upsample_rates[8];
+    int32_t n_upsample_kernel_sizes, upsample_kernel_sizes[8];
+    int32_t upsample_initial_channel;
+    int32_t resblock;                                       /* 1 or 2 */
+    int32_t n_resblock_kernels, resblock_kernel_sizes[8];
+    int32_t n_resblock_dilations[8], resblock_dilation_sizes[8][8];
+    int32_t activation;                                     /* 0 snake, 1 snakebeta */
+    int32_t snake_logscale, use_bias_at_final, use_tanh_at_final;
+    int32_t max_batch, max_frames;                          /* 1..64 rows a call; mel frames a row */
+} mis_bigvgan_config;
+mis_status mis_bigvgan_create(const mis_bigvgan_config*, int device, mis_bigvgan** out);
+/* the reference's keys and MLX layouts: conv_pre.{weight_g [out, 1, 1], weight_v [out, k, in], bias}, ups.N.0.{weight_g [1, 1, in],
+ * weight_v [out, k, in], bias}, resblocks.N.{convs1,convs2}.M.* (resblock 1) or resblocks.N.convs.M.* (2),
+ * resblocks.N.activations.M.act.{alpha, beta} [channels], activation_post.act.*, conv_post.* (no bias without use_bias_at_final); beta
+ * only for snakebeta; host pointers.  finalize names a missing or misshapen tensor. */
+mis_status mis_bigvgan_set_tensor(mis_bigvgan*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_bigvgan_init_synthetic(mis_bigvgan*, uint64_t seed);
+mis_status mis_bigvgan_finalize(mis_bigvgan*);
+void       mis_bigvgan_destroy(mis_bigvgan*);
+int        mis_bigvgan_hop(const mis_bigvgan*);           /* samples a mel frame: the product of the rates */
+/* kernel launches of the last call: 3 + sum over stages of (2 + sum over AMP blocks of 4 (resblock 1) or 2 (resblock 2) per dilation) */
+int        mis_bigvgan_launches(const mis_bigvgan*);
+/* mel f32 [batch, num_mels, stride] and frames[batch] (1..stride each; NULL = stride), host -> wav f32 [batch, stride x hop], host;
+ * zeros behind a row's own frames[b] x hop samples */
+mis_status mis_bigvgan_decode(mis_bigvgan*, const float* mel, const int32_t* frames, int batch, int64_t stride, float* wav_out);
+/* tensors of the last call, f32 [B, C, stride x up-sampling so far], zeros behind a row's own samples.  stage 0 conv_pre; with
+ * n = num_kernels, 1 + i (n + 2) stage i's transposed conv, + 1 + j its AMP block j, + n + 1 the stage mean; 1 + stages x (n + 2)
+ * activation_post.  dims[3] receives B, C, length; out NULL for the dims alone. */
+mis_status mis_bigvgan_tap(mis_bigvgan*, int stage, float* out, int64_t capacity, int64_t* dims);
+
 /* Diagnostics and test scaffolding (launch floor, split-factor model, CU spinner, failure counters) are NOT part of the product
  * surface: include/mi_speech_debug.h. */
 

@@ -331,6 +331,15 @@ mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);
  * projection + BART layers + head */
 mis_status mis_debug_sortformer_timing(mis_sortformer* c, float* ms);
 
+/* csrc/bigvgan.hip, measurements: device milliseconds of the last decode's kernels (behind the copy in, before the copy out), ms[1] */
+mis_status mis_debug_bigvgan_timing(const mis_bigvgan* c, float* ms);
+/* csrc/bigvgan.hip, tests (tests/test_gpu_bigvgan.py): ONE launch of the anti-aliased activation k_bv_aa_act on host data.  x f32
+ * [batch][channels][stride], counts[batch] columns of each row (1..stride), alpha / beta [channels] as the activation uses them (after
+ * any exp(); 1 / (beta + 1e-9) is folded here as finalize folds it) -> out f32 [batch][channels][stride], zeros behind a row's own
+ * columns.  Inputs are followed by NaN and the poisoned output lies between guard bands, as for the other operator entry points. */
+mis_status mis_debug_bigvgan_aa_act(int device, const float* x, const int32_t* counts, int batch, int channels, int64_t stride,
+                                    const float* alpha, const float* beta, float* out);
+
 #ifdef __cplusplus
 }
 #endif

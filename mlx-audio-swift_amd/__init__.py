@@ -10,6 +10,7 @@ the Swift shim a maintainer would add):
     codecs.DescriptDAC     <-> class DescriptDAC (decode side)         (MLXAudioCodecs/Descript/DescriptDAC.swift)
     codecs.Encodec         <-> class Encodec (decode side)             (MLXAudioCodecs/Encodec/Encodec.swift)
     codecs.Mimi            <-> class Mimi : AudioCodecModel + MimiStreamingDecoder  (MLXAudioCodecs/Mimi/Mimi.swift)
+    codecs.BigVGAN         <-> class BigVGAN : AudioDecoderModel (mel -> waveform vocoder)  (MLXAudioCodecs/BigVGAN/BigVGAN.swift)
     tts.LlamaTTSModel      <-> class LlamaTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Llama/LlamaTTS.swift)
     soprano.SopranoModel   <-> class SopranoModel : SpeechGenerationModel  (MLXAudioTTS/Models/Soprano/Soprano.swift)
     qwen3tts.Qwen3TTSModel <-> class Qwen3TTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Qwen3TTS/Qwen3TTS.swift)
@@ -33,6 +34,7 @@ from .generation import (AudioGenerationError, AudioGenerationInfo, GeneratePara
                          AudioEvent)
 from .codecs import SNAC, SNACConfig, DescriptDAC, DescriptDACConfig, Encodec, EncodecConfig  # noqa: F401
 from .codecs import Mimi, MimiConfig, MimiStreamingDecoder, mimi_sanitize  # noqa: F401
+from .codecs import BigVGAN, BigVGANConfig, bigvgan_sanitize, bigvgan_expected_shapes, bigvgan_aa_act  # noqa: F401
 from .tts import (LlamaTTSModel, LlamaTTSConfiguration, OrpheusTokens, VyvoTokens, interleave_snac_codes,  # noqa: F401
                   orpheus_prompt_rows, padded_prompt_batch)
 from .orpheus import deinterleave, parse_output  # noqa: F401

@@ -167,6 +167,15 @@ class FsmnVadConfigC(C.Structure):
                 + [("sil_pdf_ids", C.c_int32 * 16), ("max_batch", C.c_int32), ("chunk_frames", C.c_int32)])
 
 
+class BigVGANConfigC(C.Structure):
+    _fields_ = [("num_mels", C.c_int32), ("n_upsamples", C.c_int32), ("upsample_rates", C.c_int32 * 8),
+                ("n_upsample_kernel_sizes", C.c_int32), ("upsample_kernel_sizes", C.c_int32 * 8), ("upsample_initial_channel", C.c_int32),
+                ("resblock", C.c_int32), ("n_resblock_kernels", C.c_int32), ("resblock_kernel_sizes", C.c_int32 * 8),
+                ("n_resblock_dilations", C.c_int32 * 8), ("resblock_dilation_sizes", (C.c_int32 * 8) * 8), ("activation", C.c_int32),
+                ("snake_logscale", C.c_int32), ("use_bias_at_final", C.c_int32), ("use_tanh_at_final", C.c_int32),
+                ("max_batch", C.c_int32), ("max_frames", C.c_int32)]
+
+
 class MossFormer2ConfigC(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("sample_rate", "win_len", "win_inc", "fft_len", "num_mels", "win_hann", "in_channels",
                                           "out_channels", "out_channels_final", "num_blocks", "max_batch")]
@@ -348,6 +357,15 @@ SYMBOLS = {
     "mis_fsmn_vad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
     "mis_fsmn_vad_detect_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int]),
     "mis_fsmn_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_bigvgan_create": (C.c_int, [C.POINTER(BigVGANConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_bigvgan_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_bigvgan_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_bigvgan_finalize": (C.c_int, [_P]),
+    "mis_bigvgan_destroy": (None, [_P]),
+    "mis_bigvgan_hop": (C.c_int, [_P]),
+    "mis_bigvgan_launches": (C.c_int, [_P]),
+    "mis_bigvgan_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
+    "mis_bigvgan_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_mossformer2_create": (C.c_int, [C.POINTER(MossFormer2ConfigC), C.c_int, C.POINTER(_P)]),
     "mis_mossformer2_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_mossformer2_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -541,6 +559,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
+    "mis_debug_bigvgan_timing": (C.c_int, [_P, _P]),
+    "mis_debug_bigvgan_aa_act": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "mis_debug_sortformer_timing": (C.c_int, [_P, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }

@@ -632,3 +632,235 @@ class MimiStreamingDecoder:
         out = np.empty((B, 1, T * self.mimi.num_samples(1)), np.float32)
         check(_lib.lib().mis_mimi_decode_stream_step(self.mimi._h, cd.ctypes.data, nq, T, out.ctypes.data))
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------ BigVGAN
+@dataclass
+class BigVGANConfig:
+    """BigVGANConfig (BigVGANConfig.swift:13-65): the eleven fields under their coding keys, resblock as "1" / "2", activation as
+    "snake" / "snakebeta".  max_batch / max_frames size the engine's workspace (rows a call, mel frames a row)."""
+    num_mels: int
+    upsample_rates: list
+    upsample_kernel_sizes: list
+    upsample_initial_channel: int
+    resblock: str
+    resblock_kernel_sizes: list
+    resblock_dilation_sizes: list
+    activation: str
+    snake_logscale: bool
+    use_bias_at_final: bool = True
+    use_tanh_at_final: bool = True
+    max_batch: int = 8
+    max_frames: int = 1024
+
+    _KEYS = ("num_mels", "upsample_rates", "upsample_kernel_sizes", "upsample_initial_channel", "resblock", "resblock_kernel_sizes",
+             "resblock_dilation_sizes", "activation", "snake_logscale")
+
+    def __post_init__(self):
+        self.resblock = str(self.resblock)
+        if self.resblock not in ("1", "2"):
+            raise AudioGenerationError(3, f"BigVGAN: resblock {self.resblock!r} (\"1\" or \"2\")")
+        if self.activation not in ("snake", "snakebeta"):
+            raise AudioGenerationError(3, f"BigVGAN: activation {self.activation!r} (\"snake\" or \"snakebeta\")")
+
+    @classmethod
+    def from_dict(cls, d: dict, **workspace) -> "BigVGANConfig":
+        missing = [k for k in cls._KEYS if k not in d]
+        if missing:
+            raise AudioGenerationError(3, f"BigVGAN: config misses {missing}")
+        kw = {k: d[k] for k in cls._KEYS}
+        for k in ("use_bias_at_final", "use_tanh_at_final"):
+            if k in d:
+                kw[k] = bool(d[k])
+        return cls(**kw, **workspace)
+
+    @property
+    def hop_length(self) -> int:
+        return int(np.prod(self.upsample_rates, dtype=np.int64))
+
+    def to_c(self) -> "_lib.BigVGANConfigC":
+        c = _lib.BigVGANConfigC()
+        if (len(self.upsample_rates) > 8 or len(self.upsample_kernel_sizes) > 8 or len(self.resblock_kernel_sizes) > 8
+                or len(self.resblock_dilation_sizes) != len(self.resblock_kernel_sizes) or any(len(d) > 8 for d in self.resblock_dilation_sizes)):
+            raise AudioGenerationError(3, "BigVGAN: at most 8 stages, 8 resblock kernels with a dilation list each, 8 dilations a block")
+        c.num_mels, c.upsample_initial_channel = self.num_mels, self.upsample_initial_channel
+        c.n_upsamples, c.n_upsample_kernel_sizes = len(self.upsample_rates), len(self.upsample_kernel_sizes)
+        for i, v in enumerate(self.upsample_rates):
+            c.upsample_rates[i] = v
+        for i, v in enumerate(self.upsample_kernel_sizes):
+            c.upsample_kernel_sizes[i] = v
+        c.resblock, c.n_resblock_kernels = int(self.resblock), len(self.resblock_kernel_sizes)
+        for i, (k, dil) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
+            c.resblock_kernel_sizes[i], c.n_resblock_dilations[i] = k, len(dil)
+            for j, v in enumerate(dil):
+                c.resblock_dilation_sizes[i][j] = v
+        c.activation, c.snake_logscale = int(self.activation == "snakebeta"), int(self.snake_logscale)
+        c.use_bias_at_final, c.use_tanh_at_final = int(self.use_bias_at_final), int(self.use_tanh_at_final)
+        c.max_batch, c.max_frames = self.max_batch, self.max_frames
+        return c
+
+
+def bigvgan_expected_shapes(config: BigVGANConfig) -> dict:
+    """name -> shape of every parameter of BigVGAN(config) in the reference's (MLX) layouts: conv weight_v [out, k, in] with weight_g
+    [out, 1, 1], transposed conv weight_v [out, k, in] with weight_g [1, 1, in] (BigVGANLayers.swift:113-225); act.beta only for
+    snakebeta; conv_post.bias only with use_bias_at_final."""
+    s = {}
+
+    def conv(p, out, k, cin, bias=True):
+        s[p + ".weight_g"], s[p + ".weight_v"] = (out, 1, 1), (out, k, cin)
+        if bias:
+            s[p + ".bias"] = (out,)
+
+    def act(p, ch):
+        s[p + ".act.alpha"] = (ch,)
+        if config.activation == "snakebeta":
+            s[p + ".act.beta"] = (ch,)
+
+    c0, nk = config.upsample_initial_channel, len(config.resblock_kernel_sizes)
+    conv("conv_pre", c0, 7, config.num_mels)
+    for i, (rate, ks) in enumerate(zip(config.upsample_rates, config.upsample_kernel_sizes)):
+        cin, ch = c0 >> i, c0 >> (i + 1)
+        u = f"ups.{i}.0"
+        s[u + ".weight_g"], s[u + ".weight_v"], s[u + ".bias"] = (1, 1, cin), (ch, ks, cin), (ch,)
+        for j, (k, dil) in enumerate(zip(config.resblock_kernel_sizes, config.resblock_dilation_sizes)):
+            q = f"resblocks.{i * nk + j}"
+            for d in range(len(dil)):
+                if config.resblock == "1":
+                    conv(f"{q}.convs1.{d}", ch, k, ch)
+                    conv(f"{q}.convs2.{d}", ch, k, ch)
+                    act(f"{q}.activations.{2 * d}", ch)
+                    act(f"{q}.activations.{2 * d + 1}", ch)
+                else:
+                    conv(f"{q}.convs.{d}", ch, k, ch)
+                    act(f"{q}.activations.{d}", ch)
+    cf = c0 >> len(config.upsample_rates)
+    act("activation_post", cf)
+    conv("conv_post", 1, 7, cf, config.use_bias_at_final)
+    return s
+
+
+def bigvgan_sanitize(config: BigVGANConfig, weights: dict) -> dict:
+    """BigVGAN.sanitize (BigVGAN.swift:190-217): num_batches_tracked keys are dropped; a 3-D conv / ups. tensor whose shape differs from
+    the parameter's is transposed - ups. with (1, 2, 0) (torch [in, out, k] -> [out, k, in]), any other conv with (0, 2, 1) (torch
+    [out, in, k] -> [out, k, in]); a tensor that already has the expected shape, and a key the model does not have, pass untouched."""
+    want = bigvgan_expected_shapes(config)
+    out = {}
+    for key, v in weights.items():
+        if "num_batches_tracked" in key:
+            continue
+        if key in want and ("conv" in key or "ups." in key) and v.ndim == 3 and tuple(v.shape) != want[key]:
+            v = _permute(v, (1, 2, 0)) if "ups." in key else _permute(v, (0, 2, 1))
+        out[key] = v
+    return out
+
+
+class BigVGAN(NativeHandle):
+    """BigVGAN (BigVGAN.swift:92-228): a mel -> waveform vocoder, extension BigVGAN: AudioDecoderModel.  __call__ / decode_audio take
+    [B, num_mels, T] and return [B, 1, T hop]; decode takes a ragged batch with per-row frame counts.  Loaders: from_weights
+    (sanitized names, all of them and no others), from_model_directory (config.json + *.safetensors through sanitize), synthetic."""
+    _prefix = "mis_bigvgan"
+
+    def __init__(self, config: BigVGANConfig, device: int = 0):
+        self.config = config
+        self.device = device
+        self._create(config.to_c(), device)
+
+    @classmethod
+    def from_weights(cls, config: BigVGANConfig, weights: dict, device: int = 0) -> "BigVGAN":
+        want = bigvgan_expected_shapes(config)
+        unknown, missing = sorted(set(weights) - set(want)), sorted(set(want) - set(weights))
+        if unknown or missing:
+            raise AudioGenerationError(3, f"BigVGAN checkpoint: unexpected keys {unknown[:4]}, missing keys {missing[:4]}")
+        m = cls(config, device)
+        for name, arr in weights.items():
+            m.set_tensor(name, arr)
+        m.finalize()
+        return m
+
+    @classmethod
+    def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "BigVGAN":
+        from ._handle import read_safetensors_dir
+        path = os.path.join(model_dir, "config.json")
+        if not os.path.exists(path):
+            raise AudioGenerationError(3, "BigVGAN: config.json not found in model directory")
+        with open(path) as f:
+            cfg = BigVGANConfig.from_dict(json.load(f), **workspace)
+        weights = read_safetensors_dir(model_dir, missing_code=(3, "BigVGAN: no .safetensors file in model directory"))
+        return cls.from_weights(cfg, bigvgan_sanitize(cfg, weights), device)
+
+    @classmethod
+    def synthetic(cls, config: BigVGANConfig, device: int = 0, seed: int = 777) -> "BigVGAN":
+        m = cls(config, device)
+        check(_lib.lib().mis_bigvgan_init_synthetic(m._h, seed))
+        m.finalize()
+        return m
+
+    def sanitize(self, weights: dict) -> dict:
+        return bigvgan_sanitize(self.config, weights)
+
+    # -- AudioDecoderModel ---------------------------------------------------------------------------
+    @property
+    def codec_sample_rate(self):
+        return None                                                      # BigVGAN.swift:223
+
+    @property
+    def hop_length(self) -> int:
+        return int(_lib.lib().mis_bigvgan_hop(self._h))
+
+    def num_samples(self, frames: int) -> int:
+        return int(frames) * self.hop_length
+
+    @property
+    def launches(self) -> int:
+        return int(_lib.lib().mis_bigvgan_launches(self._h))
+
+    def decode(self, mel, frames=None) -> np.ndarray:
+        """mel [B, num_mels, T] (or [num_mels, T]) with frames[B] valid frames a row (None: T) -> waveform [B, T hop]; the columns
+        behind a row's own frames[b] hop samples are zero."""
+        m = np.ascontiguousarray(mel, dtype=np.float32)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[1] != self.config.num_mels:
+            raise AudioGenerationError(3, f"BigVGAN: mel of shape {m.shape}, expected [batch, {self.config.num_mels}, frames]")
+        B, _, T = m.shape
+        fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+        if fr is not None and fr.shape != (B,):
+            raise AudioGenerationError(3, "BigVGAN: one frame count per batch row is expected")
+        out = np.zeros((B, T * self.hop_length), np.float32)
+        check(_lib.lib().mis_bigvgan_decode(self._h, m.ctypes.data, None if fr is None else fr.ctypes.data, B, T, out.ctypes.data))
+        return out
+
+    def __call__(self, mel) -> np.ndarray:
+        """callAsFunction (BigVGAN.swift:169-188): [B, num_mels, T] -> [B, 1, T hop]."""
+        return self.decode(mel)[:, None, :]
+
+    def decode_audio(self, mel) -> np.ndarray:
+        return self(mel)
+
+    def debug_tap(self, stage: int) -> np.ndarray:
+        """Tensors of the last call [B, C, length]: 0 conv_pre; with n = num_kernels, 1 + i (n + 2) stage i's transposed conv, + 1 + j its
+        AMP block j, + n + 1 the stage mean; 1 + stages (n + 2) activation_post."""
+        dims = (C.c_int64 * 3)()
+        check(_lib.lib().mis_bigvgan_tap(self._h, stage, None, 0, dims))
+        out = np.zeros(tuple(int(d) for d in dims), np.float32)
+        check(_lib.lib().mis_bigvgan_tap(self._h, stage, out.ctypes.data, out.size, dims))
+        return out
+
+    def timing(self) -> float:
+        """Device milliseconds of the last decode's kernels."""
+        ms = (C.c_float * 1)()
+        check(_lib.lib().mis_debug_bigvgan_timing(self._h, ms))
+        return float(ms[0])
+
+
+def bigvgan_aa_act(x, counts, alpha, beta, device: int = 0) -> np.ndarray:
+    """One launch of the anti-aliased activation kernel (tests): x [B, C, T], counts[B], alpha / beta [C] as the activation uses them."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    B, Cn, T = x.shape
+    cn, al, be = (np.ascontiguousarray(counts, dtype=np.int32), np.ascontiguousarray(alpha, dtype=np.float32),
+                  np.ascontiguousarray(beta, dtype=np.float32))
+    if cn.shape != (B,) or al.shape != (Cn,) or be.shape != (Cn,):
+        raise AudioGenerationError(3, "BigVGAN: counts [B] and alpha / beta [C] are expected")
+    out = np.zeros_like(x)
+    check(_lib.lib().mis_debug_bigvgan_aa_act(device, x.ctypes.data, cn.ctypes.data, B, Cn, T, al.ctypes.data, be.ctypes.data, out.ctypes.data))
+    return out
