@@ -26,6 +26,7 @@
 //   k_lasr_glu_dwconv  GLU -> zero-padded depthwise conv (<= 64 taps) -> folded BatchNorm -> activation, a time tile + halo in LDS
 //   k_lasr_argmax      per-frame arg-max (lowest index on ties);  k_lasr_collapse  CTC collapse + compaction per row
 #include "common.h"
+#include "bf16_tile.h"
 #define AUDIO_FRONT_NEMO_KERNELS
 #include "audio_front.h"
 #include "host_weights.h"
@@ -332,50 +333,16 @@ struct LasrGemm {
     const int* cnt;
     int Tp;
 };
-#define LG_LD 40
 template <int EPI, int TI>
 __global__ void __launch_bounds__(256) k_lasr_gemm(LasrGemm p) {
-    constexpr int BT = 32 * TI, NCH = TI / 2;
-    __shared__ __attribute__((aligned(16))) bf16_t Ws[BT][LG_LD];
-    __shared__ __attribute__((aligned(16))) bf16_t Xs[BT][LG_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int BT = 32 * TI;
+    __shared__ __attribute__((aligned(16))) bf16_t Ws[BT][BF16_LD];
+    __shared__ __attribute__((aligned(16))) bf16_t Xs[BT][BF16_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n0 = blockIdx.x * BT, m0 = blockIdx.y * BT;
     const int wn = wave >> 1, wm = wave & 1;
     f32x4_t acc[TI][TI];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TI; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    const int r0 = tid >> 2, c0 = (tid & 3) * 8;
-    uint4 wreg[NCH], xreg[NCH];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int h = 0; h < NCH; ++h) {
-            const int row = r0 + 64 * h, n = n0 + row, m = m0 + row;
-            wreg[h] = (n < p.N) ? *reinterpret_cast<const uint4*>(p.W + (size_t)n * p.K + k0 + c0) : make_uint4(0, 0, 0, 0);
-            xreg[h] = (m < p.M) ? *reinterpret_cast<const uint4*>(p.X + (size_t)m * p.ldx + k0 + c0) : make_uint4(0, 0, 0, 0);
-        }
-    };
-    load(0);
-    for (int k0 = 0; k0 < p.K; k0 += 32) {
-        __syncthreads();
-#pragma unroll
-        for (int h = 0; h < NCH; ++h) {
-            *reinterpret_cast<uint4*>(&Ws[r0 + 64 * h][c0]) = wreg[h];
-            *reinterpret_cast<uint4*>(&Xs[r0 + 64 * h][c0]) = xreg[h];
-        }
-        __syncthreads();
-        if (k0 + 32 < p.K) load(k0 + 32);
-        bf16x8_t af[TI], bfr[TI];
-#pragma unroll
-        for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf16x8_t*>(&Ws[wn * 16 * TI + i * 16 + (lane & 15)][(lane >> 4) * 8]);
-#pragma unroll
-        for (int j = 0; j < TI; ++j) bfr[j] = *reinterpret_cast<const bf16x8_t*>(&Xs[wm * 16 * TI + j * 16 + (lane & 15)][(lane >> 4) * 8]);
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    bf16_tile_contract<TI>(p.W, p.X, p.ldx, p.M, p.N, p.K, n0, m0, Ws, Xs, acc);
     // C/D lane l, register e: n = 4 (l >> 4) + e (A rows), m = l & 15 (B columns)
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
@@ -398,11 +365,7 @@ __global__ void __launch_bounds__(256) k_lasr_gemm(LasrGemm p) {
                 continue;
             }
             float rv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (EPI == LG_AXPBY) {
-                const uint2 rq = *reinterpret_cast<const uint2*>(p.R + (size_t)m * p.N + n);
-                rv[0] = __uint_as_float(rq.x << 16); rv[1] = __uint_as_float(rq.x & 0xffff0000u);
-                rv[2] = __uint_as_float(rq.y << 16); rv[3] = __uint_as_float(rq.y & 0xffff0000u);
-            }
+            if (EPI == LG_AXPBY) bf16x4_unpack(*reinterpret_cast<const uint2*>(p.R + (size_t)m * p.N + n), rv);
             uint16_t res[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -412,10 +375,7 @@ __global__ void __launch_bounds__(256) k_lasr_gemm(LasrGemm p) {
                 if (EPI == LG_AXPBY) v = fmaf(p.a, rv[e], p.b * v);
                 res[e] = valid ? f32_to_bf16(v) : (uint16_t)0;
             }
-            uint2 v;
-            v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
-            v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
-            *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p.C) + (size_t)m * p.N + n) = v;      // (N % 4 == 0 for every bf16 output)
+            *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p.C) + (size_t)m * p.N + n) = bf16x4_pack(res[0], res[1], res[2], res[3]);      // (N % 4 == 0 for every bf16 output)
         }
     }
 }

@@ -6,13 +6,18 @@
 // weight-streaming kernels of lm_kernels.hip.  bf16 storage, f32 accumulation, rounding at every MLX
 // primitive boundary (oracle/whisper.py).
 //
-//   k_gemm_big      C[M][N] = X[M][K] W[N][K]^T on v_mfma_f32_16x16x32_bf16, 128x128x32 LDS tiles, fused
-//                   bias / exact-erf GELU / residual / positional-embedding epilogues (M = batch*1500 rows)
-//   k_layernorm     row LayerNorm (f32 statistics)
+//   k_gemm_big      C[M][N] = X[M][K] W[N][K]^T on v_mfma_f32_16x16x32_bf16, 128x128x32 LDS tiles staged through registers (the
+//                   contraction of bf16_tile.h), any K % 32 == 0; fused bias / erf-form GELU / residual / positional-embedding
+//                   epilogues (M = batch*1500 rows)
+//   k_gemm_big2     the same tile with global -> LDS DMA staging, 64-wide k-tiles, two LDS buffers (K % 64 == 0, K >= 128)
+//   k_gemm_big3     256x256x64 tiles on eight waves, asm fragment reads with counted waits, where the grid fills the chip
+//                   all three end in bg_epilogue<EPI>; launch_gemm_big chooses among them
+//   k_layernorm, k_layernorm8     row LayerNorm (f32 statistics)
 //   k_im2col3       k=3 convolution patches (stride 1 / 2) so both stem convs run on k_gemm_big
 //   k_scatter_kv    [M][*] K and V columns -> the tiled MFMA-fragment cache layouts of lm_kernels.hip
 //   k_attn_prefill  non-causal flash attention over the tiled K/V, 16 query rows per wave
 #include "common.h"
+#include "bf16_tile.h"
 #include "whisper_kernels.h"
 #include <type_traits>
 
@@ -37,56 +42,39 @@ __device__ __forceinline__ float gelu_erf_w(float x) {
 // ============================================================================ big GEMM
 #define BG_BM 128
 #define BG_BN 128
-#define BG_BK 32
-#define BG_LD 40          // padded LDS row (bf16 elements): 80 B rows keep 16-B fragments aligned
 
+// The one epilogue of the three kernels, on the C/D quad acc of row m, columns n .. n + 3 (bv: their bias).  The loops over a wave's
+// tiles and the edge skips stay in the kernels.  T(xW^T + b), then T(gelu()), then T(+ the residual row m or the positional row
+// m % pos_rows): a rounding after each.
+template <int EPI>
+__device__ __forceinline__ void bg_epilogue(const BigGemmParams& p, const f32x4_t& acc, const float (&bv)[4], int n, int m) {
+    uint16_t res[4];
+    float rv[4] = {0.f, 0.f, 0.f, 0.f};                                     // residual / positional row: ONE 8-byte load (N % 4 == 0)
+    if (EPI == BG_RESID || EPI == BG_GELU_POS) {
+        const size_t rrow = EPI == BG_RESID ? (size_t)m : (size_t)(m % p.pos_rows);
+        bf16x4_unpack(*reinterpret_cast<const uint2*>(p.R + rrow * p.N + n), rv);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float v = bf16_round_f32(acc[e] + bv[e]);                             // T(xW^T + b)
+        if (EPI == BG_GELU || EPI == BG_GELU_POS) v = bf16_round_f32(gelu_erf_w(v));
+        if (EPI == BG_RESID || EPI == BG_GELU_POS) v = bf16_round_f32(v + rv[e]);
+        res[e] = f32_to_bf16(v);
+    }
+    // launch_gemm_big requires N % 4 == 0, so with n < N the four columns exist: one 8-byte store, no scalar tail
+    *reinterpret_cast<uint2*>(p.C + (size_t)m * p.N + n) = bf16x4_pack(res[0], res[1], res[2], res[3]);
+}
+
+// the TI = 4 instance of the register-staged contraction of bf16_tile.h
 template <int EPI>
 __global__ void __launch_bounds__(256) k_gemm_big(BigGemmParams p) {
-    __shared__ __attribute__((aligned(16))) bf16_t Ws[BG_BN][BG_LD];
-    __shared__ __attribute__((aligned(16))) bf16_t Xs[BG_BM][BG_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ __attribute__((aligned(16))) bf16_t Ws[BG_BN][BF16_LD];
+    __shared__ __attribute__((aligned(16))) bf16_t Xs[BG_BM][BF16_LD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n0 = blockIdx.x * BG_BN, m0 = blockIdx.y * BG_BM;
     const int wn = wave >> 1, wm = wave & 1;            // wave tile: 64 n x 64 m
     f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    // staging: 128 rows x 32 k = 512 chunks of 16 B per operand, two per thread
-    const int r0 = tid >> 2, c0 = (tid & 3) * 8;
-    uint4 wreg[2], xreg[2];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int row = r0 + 64 * h;
-            int n = n0 + row, m = m0 + row;
-            wreg[h] = (n < p.N) ? *reinterpret_cast<const uint4*>(p.W + (size_t)n * p.K + k0 + c0) : make_uint4(0, 0, 0, 0);
-            xreg[h] = (m < p.M) ? *reinterpret_cast<const uint4*>(p.X + (size_t)m * p.ldx + k0 + c0) : make_uint4(0, 0, 0, 0);
-        }
-    };
-    load(0);
-    for (int k0 = 0; k0 < p.K; k0 += BG_BK) {
-        __syncthreads();
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            *reinterpret_cast<uint4*>(&Ws[r0 + 64 * h][c0]) = wreg[h];
-            *reinterpret_cast<uint4*>(&Xs[r0 + 64 * h][c0]) = xreg[h];
-        }
-        __syncthreads();
-        if (k0 + BG_BK < p.K) load(k0 + BG_BK);
-        bf16x8_t a[4], b[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            a[i] = *reinterpret_cast<const bf16x8_t*>(&Ws[wn * 64 + i * 16 + (lane & 15)][(lane >> 4) * 8]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            b[j] = *reinterpret_cast<const bf16x8_t*>(&Xs[wm * 64 + j * 16 + (lane & 15)][(lane >> 4) * 8]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
+    bf16_tile_contract<4>(p.W, p.X, p.ldx, p.M, p.N, p.K, n0, m0, Ws, Xs, acc);
     // epilogue: C/D lane l, reg r: n = (l>>4)*4 + r (A rows), m = l&15 (B cols) -> 4 consecutive n per lane
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -101,24 +89,7 @@ __global__ void __launch_bounds__(256) k_gemm_big(BigGemmParams p) {
         for (int j = 0; j < 4; ++j) {
             int m = m0 + wm * 64 + j * 16 + (lane & 15);
             if (m >= p.M) continue;
-            uint16_t res[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = bf16_round_f32(acc[i][j][e] + bv[e]);                       // T(xW^T + b)
-                if (EPI == BG_GELU || EPI == BG_GELU_POS) v = bf16_round_f32(gelu_erf_w(v));
-                if (EPI == BG_RESID) v = bf16_round_f32(v + bf16_to_f32(p.R[(size_t)m * p.N + n + e]));
-                if (EPI == BG_GELU_POS) v = bf16_round_f32(v + bf16_to_f32(p.R[(size_t)(m % p.pos_rows) * p.N + n + e]));
-                res[e] = f32_to_bf16(v);
-            }
-            bf16_t* o = p.C + (size_t)m * p.N + n;
-            if (n + 3 < p.N) {
-                uint2 v;
-                v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
-                v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
-                *reinterpret_cast<uint2*>(o) = v;
-            } else {
-                for (int e = 0; e < 4 && n + e < p.N; ++e) o[e] = res[e];
-            }
+            bg_epilogue<EPI>(p, acc[i][j], bv, n, m);
         }
     }
 }
@@ -196,7 +167,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_big2(BigGemmParams p) {
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
     }
-    // epilogue: as k_gemm_big
+    // the C/D quads of the wave's 4 x 4 tiles, as in k_gemm_big
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
@@ -210,24 +181,7 @@ __global__ void __launch_bounds__(256, 2) k_gemm_big2(BigGemmParams p) {
         for (int j = 0; j < 4; ++j) {
             int m = m0 + wm * 64 + j * 16 + (lane & 15);
             if (m >= p.M) continue;
-            uint16_t res[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = bf16_round_f32(acc[i][j][e] + bv[e]);                       // T(xW^T + b)
-                if (EPI == BG_GELU || EPI == BG_GELU_POS) v = bf16_round_f32(gelu_erf_w(v));
-                if (EPI == BG_RESID) v = bf16_round_f32(v + bf16_to_f32(p.R[(size_t)m * p.N + n + e]));
-                if (EPI == BG_GELU_POS) v = bf16_round_f32(v + bf16_to_f32(p.R[(size_t)(m % p.pos_rows) * p.N + n + e]));
-                res[e] = f32_to_bf16(v);
-            }
-            bf16_t* o = p.C + (size_t)m * p.N + n;
-            if (n + 3 < p.N) {
-                uint2 v;
-                v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
-                v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
-                *reinterpret_cast<uint2*>(o) = v;
-            } else {
-                for (int e = 0; e < 4 && n + e < p.N; ++e) o[e] = res[e];
-            }
+            bg_epilogue<EPI>(p, acc[i][j], bv, n, m);
         }
     }
 }
@@ -325,7 +279,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm_big3(BigGemmParams p) {
                 for (int j = 0; j < TM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
         }
     }
-    // epilogue: as k_gemm_big2 (C/D lane = column m (l & 15), rows n = 4 (l >> 4) + e)
+    // the C/D quads of the wave's TN x TM tiles (C/D lane = column m (l & 15), rows n = 4 (l >> 4) + e)
 #pragma unroll
     for (int i = 0; i < TN; ++i) {
         const int n = n0 + wn * (BG3_BN / WN) + i * 16 + (lane >> 4) * 4;
@@ -339,26 +293,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm_big3(BigGemmParams p) {
         for (int j = 0; j < TM; ++j) {
             const int m = m0 + wm * (BG3_BM / WM) + j * 16 + (lane & 15);
             if (m >= p.M) continue;
-            uint16_t res[4];
-            float rv[4] = {0.f, 0.f, 0.f, 0.f};                                     // residual / positional row: ONE 8-byte load (N % 4 == 0)
-            if (EPI == BG_RESID || EPI == BG_GELU_POS) {
-                const size_t rrow = EPI == BG_RESID ? (size_t)m : (size_t)(m % p.pos_rows);
-                const uint2 rq = *reinterpret_cast<const uint2*>(p.R + rrow * p.N + n);
-                rv[0] = __uint_as_float(rq.x << 16); rv[1] = __uint_as_float(rq.x & 0xffff0000u);
-                rv[2] = __uint_as_float(rq.y << 16); rv[3] = __uint_as_float(rq.y & 0xffff0000u);
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = bf16_round_f32(acc[i][j][e] + bv[e]);                       // T(xW^T + b)
-                if (EPI == BG_GELU || EPI == BG_GELU_POS) v = bf16_round_f32(gelu_erf_w(v));
-                if (EPI == BG_RESID || EPI == BG_GELU_POS) v = bf16_round_f32(v + rv[e]);
-                res[e] = f32_to_bf16(v);
-            }
-            bf16_t* o = p.C + (size_t)m * p.N + n;
-            uint2 v;
-            v.x = (uint32_t)res[0] | ((uint32_t)res[1] << 16);
-            v.y = (uint32_t)res[2] | ((uint32_t)res[3] << 16);
-            *reinterpret_cast<uint2*>(o) = v;                                       // (n < N and N % 4 == 0: the four columns exist)
+            bg_epilogue<EPI>(p, acc[i][j], bv, n, m);
         }
     }
 }
@@ -379,45 +314,35 @@ static bool launch_big3(const BigGemmParams& p, hipStream_t s) {
 
 thread_local EncLaunchInfo g_enc_last_launch;
 
+// the run-time epilogue as a compile-time constant: f(std::integral_constant<int, EPI>); an unknown one throws before anything is launched
+template <typename F>
+static void with_big_epilogue(int epi, F f) {
+    switch (epi) {
+        case BG_NONE: f(std::integral_constant<int, BG_NONE>{}); break;
+        case BG_GELU: f(std::integral_constant<int, BG_GELU>{}); break;
+        case BG_RESID: f(std::integral_constant<int, BG_RESID>{}); break;
+        case BG_GELU_POS: f(std::integral_constant<int, BG_GELU_POS>{}); break;
+        default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
+    }
+}
+
 void launch_gemm_big(int epi, const BigGemmParams& p, hipStream_t s) {
-    MIS_REQUIRE(p.K % BG_BK == 0 && p.ldx % 8 == 0 && p.N % 4 == 0, MIS_ERR_INVALID_INPUT, "big GEMM needs K %% 32 == 0");
-    dim3 grid(cdiv(p.N, BG_BN), cdiv(p.M, BG_BM)), block(256);
-    {   // the 256 x 256 tile where its grid still fills most of the chip (out_proj of 8 windows: 235 blocks, 52.0 -> 44.6 us); below that the
+    MIS_REQUIRE(p.K % BF16_BK == 0 && p.ldx % 8 == 0 && p.N % 4 == 0, MIS_ERR_INVALID_INPUT, "big GEMM needs K %% 32 == 0");
+    with_big_epilogue(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        const bool dma = p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK;                 // the LDS-DMA kernels: 64-wide k-tiles, at least two
+        // the 256 x 256 tile where its grid still fills most of the chip (out_proj of 8 windows: 235 blocks, 52.0 -> 44.6 us); below that the
         // 128 x 128 kernel has four times the blocks.  MIS_GEMM_BIG3=0: never (A/B); =2: whenever the shape allows (parity tests)
         const char* e3 = getenv("MIS_GEMM_BIG3");
         const int mode = e3 ? atoi(e3) : 1;
         const long blocks3 = (long)cdiv(p.N, BG3_BN) * cdiv(p.M, BG3_BM);
-        if (mode != 0 && p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK && (mode == 2 || blocks3 >= 200)) {
-            bool done = false;
-            switch (epi) {
-                case BG_NONE: done = launch_big3<BG_NONE>(p, s); break;
-                case BG_GELU: done = launch_big3<BG_GELU>(p, s); break;
-                case BG_RESID: done = launch_big3<BG_RESID>(p, s); break;
-                case BG_GELU_POS: done = launch_big3<BG_GELU_POS>(p, s); break;
-                default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
-            }
-            if (done) return;
-        }
-    }
-    if (epi < BG_NONE || epi > BG_GELU_POS) throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
-    g_enc_last_launch.epi = epi; g_enc_last_launch.WM = 2; g_enc_last_launch.WN = 2;
-    g_enc_last_launch.gemm = (p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK) ? 1 : 0;
-    if (p.K % BG2_BK == 0 && p.K >= 2 * BG2_BK) {
-        switch (epi) {
-            case BG_NONE: hipLaunchKernelGGL((k_gemm_big2<BG_NONE>), grid, block, 0, s, p); return;
-            case BG_GELU: hipLaunchKernelGGL((k_gemm_big2<BG_GELU>), grid, block, 0, s, p); return;
-            case BG_RESID: hipLaunchKernelGGL((k_gemm_big2<BG_RESID>), grid, block, 0, s, p); return;
-            case BG_GELU_POS: hipLaunchKernelGGL((k_gemm_big2<BG_GELU_POS>), grid, block, 0, s, p); return;
-            default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
-        }
-    }
-    switch (epi) {
-        case BG_NONE: hipLaunchKernelGGL((k_gemm_big<BG_NONE>), grid, block, 0, s, p); break;
-        case BG_GELU: hipLaunchKernelGGL((k_gemm_big<BG_GELU>), grid, block, 0, s, p); break;
-        case BG_RESID: hipLaunchKernelGGL((k_gemm_big<BG_RESID>), grid, block, 0, s, p); break;
-        case BG_GELU_POS: hipLaunchKernelGGL((k_gemm_big<BG_GELU_POS>), grid, block, 0, s, p); break;
-        default: throw MisError(MIS_ERR_GENERATION_FAILED, "unknown big GEMM epilogue");
-    }
+        if (mode != 0 && dma && (mode == 2 || blocks3 >= 200) && launch_big3<EPI>(p, s)) return;
+        const dim3 grid(cdiv(p.N, BG_BN), cdiv(p.M, BG_BM)), block(256);
+        g_enc_last_launch.epi = EPI; g_enc_last_launch.WM = 2; g_enc_last_launch.WN = 2;
+        g_enc_last_launch.gemm = dma ? 1 : 0;
+        if (dma) hipLaunchKernelGGL((k_gemm_big2<EPI>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((k_gemm_big<EPI>), grid, block, 0, s, p);
+    });
 }
 
 // ============================================================================ LayerNorm over rows
