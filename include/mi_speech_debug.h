@@ -303,6 +303,42 @@ mis_status mis_debug_marvis_rope_tables(int head_dim, float theta, float factor,
  * [batch, dims[0], dims[1]] (a row's own frames first) or NULL for the dims alone.  Leaves the handle without encoder output. */
 mis_status mis_debug_moonshine_stem_tap(mis_moonshine* c, const float* pcm, const int64_t* lens, int batch, int64_t stride, int stage,
                                         float* out, int64_t capacity, int64_t* dims);
+/* csrc/moonshine.hip, tests (tests/test_gpu_moonshine_ops.py): ONE launch of a private kernel of the Moonshine engine (GroupNorm: its chain of
+ * four), through the launcher the engine itself calls, on caller-supplied host data; nothing is computed in the entry points.  16-bit operands
+ * and results are raw bf16 payloads (uint16).  Guards as above: every output lies between guard bands and is pre-filled with the byte 0xFF, a
+ * changed guard byte - or a changed padding column of a strided output - fails the call with MIS_ERR_GENERATION_FAILED; every input is followed
+ * by NaN (ints: 0x7FFFFFFF).  What the kernels' contract excludes is refused with MIS_ERR_INVALID_INPUT and nothing is launched: K % 4, B > 64,
+ * LayerNorm with K > 512, more than 1280 keys (MS_MAX_KEYS) or keys behind Tpad, pos >= Smax, Smax > 2048 (MS_MAX_POS), H % Hkv, a
+ * cross-attention row without a key, a GroupNorm row without a frame, a conv1 frame that reads behind the row's stride.
+ *   conv1: k_ms_conv1_tanh.  pcm float [B][stride], T1 [B] (0 .. T1pad), wT float [127][d]; out float [B][T1pad][d].
+ *   groupnorm: k_ms_gn_partial<0>, <1>, k_ms_gn_final, k_ms_gn_apply as ms_encode_device chains them.  x float [B][T1pad][d] (the frames behind
+ *     T1[b] are replaced by NaN), gw, gb float [d].  stage 0 stops behind pass 0, 1 behind pass 1, 2 runs the chain.  part0, part1 float
+ *     [B][*nch_out] (room for ceil(T1pad d / 32768) chunks a row), stats float [2 B] (mean, rstd), y [B T1pad d + 8 d].
+ *   rope: k_ms_rope_rows.  rows [M][ld] go in and come back whole; heads 0 .. nheads - 1 of 64 columns: the first rot columns are rotated
+ *     with row m % Tpad of cs / sn float [Tpad][rot / 2].
+ *   attn: kind 0 k_ms_attn_enc: q = qkv [B Tpad][ld] (q heads | k heads | v heads, ld a multiple of 8), out [B Tpad][H 64]: the first H 64
+ *     columns of every row of ldo.  kind 1 k_ms_attn_self: q = qkv [B][(H + 2 Hkv) 64] of the new token, kc / vc [B][Hkv][Smax][64] go in
+ *     and come back whole, cs / sn float [Smax][rot / 2]; out [B][H 64].  kind 2 k_ms_attn_cross: q [B][H 64], kv [B Tpad][2 Hkv 64] (K heads,
+ *     then V heads); out [B][H 64].  T3 [B] (kinds 0, 2); arguments a kind does not use may be NULL / 0.
+ *   gemv: k_ms_gemv<ln, epi>, epi 0 MS_BF16, 1 MS_RESID, 2 MS_GATE, 3 MS_F32; only the decoder's four instantiations (1, 0), (0, 1), (1, 2),
+ *     (1, 3).  X [B][K], lnw [K], W [N][K] (MS_GATE: N = 2 F), bias [N] or NULL; out bf16 [B][N] (MS_RESID: goes in as h and comes back;
+ *     MS_GATE: [B][F]; MS_F32: float).  report (may be NULL) int32[2]: (ln, epi) of the instantiation that ran, -1 when nothing was launched.
+ *   embed: k_ms_embed.  emb [vocab][d], ids [B]; h [B][d].
+ *   argmax_embed: k_ms_argmax_embed.  logits float [B][V]; active uint8 [B], n_gen [B], tokens [B][stride] and done_count [1] go in and come
+ *     back; emb [V][d]; h [B][d]. */
+mis_status mis_debug_moonshine_conv1(int device, const float* pcm, int64_t stride, const int32_t* T1, int B, int T1pad, int d, const float* wT,
+                                     float* out);
+mis_status mis_debug_moonshine_groupnorm(int device, const float* x, const int32_t* T1, int B, int T1pad, int d, const float* gw, const float* gb,
+                                         int stage, float* part0, float* part1, float* stats, uint16_t* y, int32_t* nch_out);
+mis_status mis_debug_moonshine_rope(int device, uint16_t* rows, int M, int ld, int nheads, int Tpad, int rot, const float* cs, const float* sn);
+mis_status mis_debug_moonshine_attn(int device, int kind, const uint16_t* q, const uint16_t* kv, int ld, int H, int Hkv, const int32_t* T3, int B,
+                                    int Tpad, float scale, int ldo, uint16_t* kc, uint16_t* vc, int Smax, int pos, int rot, const float* cs,
+                                    const float* sn, uint16_t* out);
+mis_status mis_debug_moonshine_gemv(int device, int ln, int epi, const uint16_t* X, const uint16_t* lnw, const uint16_t* W, const uint16_t* bias, int B,
+                                    int K, int N, int F, void* out, int32_t* report);
+mis_status mis_debug_moonshine_embed(int device, const uint16_t* emb, const int32_t* ids, int B, int d, int vocab, uint16_t* h);
+mis_status mis_debug_moonshine_argmax_embed(int device, const float* logits, int B, int V, int eos, uint8_t* active, int32_t* n_gen, int32_t* tokens,
+                                            int stride, int32_t* done_count, const uint16_t* emb, int d, uint16_t* h);
 
 /* csrc/smartturn.hip, tests: tensors of the handle's last call, out f32 with room for `capacity` floats.  stage 0 prepared samples
  * [B, W] (of the last predict), 1 features [B, F, n_mels], 2 encoder output [B, T, d], 3 pooled [B, d]. */

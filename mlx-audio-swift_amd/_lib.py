@@ -543,6 +543,14 @@ DEBUG_SYMBOLS = {
     "mis_debug_marvis_sample_logits": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_int,
                                                  C.c_int, C.c_int, _P]),
     "mis_debug_moonshine_stem_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int64, _P]),
+    "mis_debug_moonshine_conv1": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_moonshine_groupnorm": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_debug_moonshine_rope": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_moonshine_attn": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P,
+                                           C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "mis_debug_moonshine_gemv": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_moonshine_embed": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_moonshine_argmax_embed": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "mis_debug_smartturn_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "mis_debug_smartturn_timing": (C.c_int, [_P, _P]),
     "mis_debug_ecapa_lid_timing": (C.c_int, [_P, _P]),

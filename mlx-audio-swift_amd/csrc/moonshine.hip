@@ -313,6 +313,10 @@ __global__ void __launch_bounds__(256) k_ms_conv1_tanh(const float* __restrict__
     }
 }
 
+static void ms_launch_conv1(const float* pcm, int64_t stride, const int* T1, const float* wT, float* out, int T1pad, int d, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_conv1_tanh, dim3(cdiv(T1pad, 16), B), dim3(256), 0, s, pcm, stride, T1, wT, out, T1pad, d);
+}
+
 // GroupNorm(1 group) statistics over the row's own T1[b] * d values (:310,322; pytorchCompatible: biased variance).  Chunks of a fixed
 // 32768 elements, so that a row's sums are formed in the same order whatever the batch it travels in; PASS 1 reads the mean as the
 // ordered sum of the PASS 0 partials (chunks past the row's extent hold 0).
@@ -361,6 +365,23 @@ __global__ void __launch_bounds__(256) k_ms_gn_apply(const float* __restrict__ x
     y[i] = v;
 }
 
+// the four GroupNorm launches: chunks of the longest row, PASS 0 / 1 partials [B][nch], the per-row statistics, the affine
+static int ms_gn_chunks(int T1max, int d) { return cdiv((int64_t)T1max * d, MS_GN_CHUNK); }
+static void ms_launch_gn_partial(int pass, const float* x, const int* T1, int T1pad, int d, const float* sums, float* out, int nch, int B, hipStream_t s) {
+    if (pass == 0) hipLaunchKernelGGL((k_ms_gn_partial<0>), dim3(nch, B), dim3(256), 0, s, x, T1, T1pad, d, nullptr, out, nch);
+    else hipLaunchKernelGGL((k_ms_gn_partial<1>), dim3(nch, B), dim3(256), 0, s, x, T1, T1pad, d, sums, out, nch);
+}
+static void ms_launch_gn_final(const float* sums, const float* sq, const int* T1, int d, int nch, float* stats, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_gn_final, dim3(1), dim3(64), 0, s, sums, sq, T1, d, nch, stats, B);
+}
+// y holds B T1pad d elements and the tail of 8 d the dense convs read past the last row
+static size_t ms_gn_tail(int d) { return (size_t)8 * d; }
+static void ms_launch_gn_apply(const float* x, const int* T1, const float* stats, const float* gw, const float* gb, bf16_t* y, int T1pad, int d, int B,
+                               hipStream_t s) {
+    const size_t total = (size_t)B * T1pad * d + ms_gn_tail(d);
+    hipLaunchKernelGGL(k_ms_gn_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, T1, stats, gw, gb, y, T1pad, d, B, total);
+}
+
 // ============================================================================ attention
 // partial interleaved RoPE (:80-110,165-178): pairs (2i, 2i + 1) of the first `rot` columns of a head, T(x cos + rotate_half(x) sin)
 __device__ __forceinline__ float ms_rope(float x, int lane, int rot, const float* __restrict__ cs, const float* __restrict__ sn, int pos) {
@@ -380,6 +401,11 @@ __global__ void __launch_bounds__(256) k_ms_rope_rows(bf16_t* __restrict__ rows,
     bf16_t* p = rows + m * ld + h * MS_DP + lane;
     const float r = ms_rope(bf16_to_f32(*p), lane, rot, cs, sn, (int)(m % Tpad));
     if (lane < rot) *p = f32_to_bf16(r);
+}
+
+static void ms_launch_rope_rows(bf16_t* rows, int ld, int nheads, int Tpad, int rot, const float* cs, const float* sn, size_t M, hipStream_t s) {
+    const size_t items = M * nheads;
+    hipLaunchKernelGGL(k_ms_rope_rows, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, rows, ld, nheads, Tpad, rot, cs, sn, M);
 }
 
 // one query against n keys: q (f32, in LDS, 64 wide), K / V rows of 64 bf16 with row strides ldk / ldv.  A lane is a key in the score
@@ -471,6 +497,17 @@ __global__ void __launch_bounds__(64) k_ms_attn_cross(const bf16_t* __restrict__
     out[(size_t)b * H * MS_DP + h * MS_DP + lane] = f32_to_bf16(o);
 }
 
+static void ms_launch_attn_enc(const bf16_t* qkv, int ld, int H, int Hkv, const int* T3, int Tpad, float scale, bf16_t* out, int ldo, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_attn_enc, dim3(cdiv(Tpad, 4), H, B), dim3(256), 0, s, qkv, ld, H, Hkv, T3, Tpad, scale, out, ldo);
+}
+static void ms_launch_attn_self(const bf16_t* qkv, int H, int Hkv, bf16_t* kc, bf16_t* vc, int Smax, int pos, int rot, const float* cs, const float* sn,
+                                float scale, bf16_t* out, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_attn_self, dim3(H, B), dim3(64), 0, s, qkv, H, Hkv, kc, vc, Smax, pos, rot, cs, sn, scale, out);
+}
+static void ms_launch_attn_cross(const bf16_t* q, int H, int Hkv, const bf16_t* kv, const int* T3, int Tpad, float scale, bf16_t* out, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_attn_cross, dim3(H, B), dim3(64), 0, s, q, H, Hkv, kv, T3, Tpad, scale, out);
+}
+
 // ============================================================================ decode-step GEMM
 // out[b][n] = sum_k X[b][k] W[n][k] for B <= 64 rows: a wave is one output column (GATE: the pair n, n + F), lanes split K in pieces of
 // four, eight rows at a time in registers.  LN: X = T(LayerNorm(h) w) (weight only, eps 1e-5, :247,286-288) rebuilt per block into LDS
@@ -545,11 +582,13 @@ __global__ void __launch_bounds__(256) k_ms_gemv(const bf16_t* __restrict__ X, i
         }
     }
 }
+// returns the instantiation that ran: 4 LN + EPI
 template <bool LN, int EPI>
-static void ms_gemv(const bf16_t* X, int K, const bf16_t* lnw, const bf16_t* W, const bf16_t* bias, void* out, int N, int B, int F, hipStream_t s) {
+static int ms_gemv(const bf16_t* X, int K, const bf16_t* lnw, const bf16_t* W, const bf16_t* bias, void* out, int N, int B, int F, hipStream_t s) {
     MIS_REQUIRE(K % 4 == 0 && B >= 1 && B <= MS_MAX_BATCH && (!LN || K <= 512), MIS_ERR_INVALID_INPUT, "decode GEMM: unsupported shape");
     const int ncols = EPI == MS_GATE ? F : N;
     hipLaunchKernelGGL((k_ms_gemv<LN, EPI>), dim3(cdiv(ncols, 4)), dim3(256), LN ? (size_t)B * K * 2 : 0, s, X, K, lnw, W, bias, out, N, B, F);
+    return (LN ? 4 : 0) + EPI;
 }
 
 // h[b] = E[ids[b]] (:345)
@@ -602,6 +641,14 @@ __global__ void __launch_bounds__(256) k_ms_argmax_embed(const float* __restrict
     for (int i = threadIdx.x; i < d; i += 256) h[(size_t)b * d + i] = emb[(size_t)id * d + i];
 }
 
+static void ms_launch_embed(const bf16_t* emb, const int32_t* ids, bf16_t* h, int d, int vocab, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_embed, dim3(B), dim3(256), 0, s, emb, ids, h, d, vocab);
+}
+static void ms_launch_argmax_embed(const float* logits, int V, int eos, uint8_t* active, int32_t* n_gen, int32_t* tokens_out, int stride, int32_t* done_count,
+                                   const bf16_t* emb, bf16_t* h, int d, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_ms_argmax_embed, dim3(B), dim3(256), 0, s, logits, V, eos, active, n_gen, tokens_out, stride, done_count, emb, h, d);
+}
+
 // ============================================================================ encoder pass
 static void ms_check_lens(const mis_moonshine* c, const int64_t* lens, int batch, int64_t stride, std::vector<int64_t>* hl) {
     MIS_REQUIRE(c->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
@@ -651,18 +698,17 @@ static void ms_encode_device(mis_moonshine* c, const float* pcm_dev, const std::
     HIP_CHECK(hipMemcpyAsync(c->T1.p, c->hT1.data(), B * 4, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(c->T3.p, c->hT3.data(), B * 4, hipMemcpyHostToDevice, s));
     // ---- stem
-    const size_t n1 = (size_t)B * T1pad * d, tail = (size_t)8 * d;
+    const size_t n1 = (size_t)B * T1pad * d, tail = ms_gn_tail(d);
     c->c1.alloc(n1);
-    hipLaunchKernelGGL(k_ms_conv1_tanh, dim3(cdiv(T1pad, 16), B), dim3(256), 0, s, pcm_dev, stride, c->T1.p, c->conv1wT, c->c1.p, T1pad, d);
+    ms_launch_conv1(pcm_dev, stride, c->T1.p, c->conv1wT, c->c1.p, T1pad, d, B, s);
     if (stop_stage == 0) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
-    const int nch = cdiv((int64_t)T1max * d, MS_GN_CHUNK);
+    const int nch = ms_gn_chunks(T1max, d);
     c->gn_part0.alloc((size_t)B * nch); c->gn_part1.alloc((size_t)B * nch); c->gn_stats.alloc(2 * B);
-    hipLaunchKernelGGL((k_ms_gn_partial<0>), dim3(nch, B), dim3(256), 0, s, c->c1.p, c->T1.p, T1pad, d, nullptr, c->gn_part0.p, nch);
-    hipLaunchKernelGGL((k_ms_gn_partial<1>), dim3(nch, B), dim3(256), 0, s, c->c1.p, c->T1.p, T1pad, d, c->gn_part0.p, c->gn_part1.p, nch);
-    hipLaunchKernelGGL(k_ms_gn_final, dim3(1), dim3(64), 0, s, c->gn_part0.p, c->gn_part1.p, c->T1.p, d, nch, c->gn_stats.p, B);
+    ms_launch_gn_partial(0, c->c1.p, c->T1.p, T1pad, d, nullptr, c->gn_part0.p, nch, B, s);
+    ms_launch_gn_partial(1, c->c1.p, c->T1.p, T1pad, d, c->gn_part0.p, c->gn_part1.p, nch, B, s);
+    ms_launch_gn_final(c->gn_part0.p, c->gn_part1.p, c->T1.p, d, nch, c->gn_stats.p, B, s);
     c->gn.alloc(n1 + tail);
-    hipLaunchKernelGGL(k_ms_gn_apply, dim3((unsigned)((n1 + tail + 255) / 256)), dim3(256), 0, s, c->c1.p, c->T1.p, c->gn_stats.p, c->gn_w, c->gn_b,
-                       c->gn.p, T1pad, d, B, n1 + tail);
+    ms_launch_gn_apply(c->c1.p, c->T1.p, c->gn_stats.p, c->gn_w, c->gn_b, c->gn.p, T1pad, d, B, s);
     if (stop_stage == 1) { HIP_CHECK(hipGetLastError()); HIP_CHECK(hipStreamSynchronize(s)); return; }
     // gelu(conv2), gelu(conv3) (:311-312,323-324): frame t of row b is the span of k C_in values at stride C_in * (b Tpad + t)
     const int M2 = B * T2pad, M = B * T3pad;
@@ -685,11 +731,8 @@ static void ms_encode_device(mis_moonshine* c, const float* pcm_dev, const std::
         launch_layernorm(c->h.p, c->x.p, L.ln1, c->zeros, M, d, MS_EPS, s);
         g = BigGemmParams{c->x.p, L.wqkv, L.bqkv, nullptr, c->qkv.p, M, NQ, d, d, 0};
         launch_gemm_big(BG_NONE, g, s);
-        const size_t items = (size_t)M * (c->He + c->Hke);
-        hipLaunchKernelGGL(k_ms_rope_rows, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, c->qkv.p, NQ, c->He + c->Hke, T3pad, c->rote,
-                           c->cos_e, c->sin_e, (size_t)M);
-        hipLaunchKernelGGL(k_ms_attn_enc, dim3(cdiv(T3pad, 4), c->He, B), dim3(256), 0, s, c->qkv.p, NQ, c->He, c->Hke, c->T3.p, T3pad, scale_e,
-                           c->att.p, NA);
+        ms_launch_rope_rows(c->qkv.p, NQ, c->He + c->Hke, T3pad, c->rote, c->cos_e, c->sin_e, (size_t)M, s);
+        ms_launch_attn_enc(c->qkv.p, NQ, c->He, c->Hke, c->T3.p, T3pad, scale_e, c->att.p, NA, B, s);
         g = BigGemmParams{c->att.p, L.wo, nullptr, c->h.p, c->h.p, M, d, NA, NA, 0};
         launch_gemm_big(BG_RESID, g, s);
         launch_layernorm(c->h.p, c->x.p, L.ln2, c->zeros, M, d, MS_EPS, s);
@@ -781,11 +824,10 @@ static void ms_enqueue_layers(mis_moonshine* c, int pos) {
     for (size_t li = 0; li < c->dec.size(); ++li) {
         const MsDecLayer& L = c->dec[li];
         ms_gemv<true, MS_BF16>(c->dh.p, d, L.ln1, L.sqkv, L.sbqkv, c->dqkv.p, NQ, B, 0, s);
-        hipLaunchKernelGGL(k_ms_attn_self, dim3(H, B), dim3(64), 0, s, c->dqkv.p, H, Hk, c->self_k.p + li * ls, c->self_v.p + li * ls, c->Smax, pos,
-                           c->rotd, c->cos_d, c->sin_d, scale, c->datt.p);
+        ms_launch_attn_self(c->dqkv.p, H, Hk, c->self_k.p + li * ls, c->self_v.p + li * ls, c->Smax, pos, c->rotd, c->cos_d, c->sin_d, scale, c->datt.p, B, s);
         ms_gemv<false, MS_RESID>(c->datt.p, NA, nullptr, L.so, nullptr, c->dh.p, d, B, 0, s);
         ms_gemv<true, MS_BF16>(c->dh.p, d, L.ln2, L.cq, L.cbq, c->dq.p, NA, B, 0, s);
-        hipLaunchKernelGGL(k_ms_attn_cross, dim3(H, B), dim3(64), 0, s, c->dq.p, H, Hk, c->cross.p + li * M * NKV, c->T3.p, c->T3pad, scale, c->datt.p);
+        ms_launch_attn_cross(c->dq.p, H, Hk, c->cross.p + li * M * NKV, c->T3.p, c->T3pad, scale, c->datt.p, B, s);
         ms_gemv<false, MS_RESID>(c->datt.p, NA, nullptr, L.co, nullptr, c->dh.p, d, B, 0, s);
         ms_gemv<true, MS_GATE>(c->dh.p, d, L.ln3, L.fc1, L.b1, c->dact.p, 2 * f, B, f, s);
         ms_gemv<false, MS_RESID>(c->dact.p, f, nullptr, L.fc2, L.b2, c->dh.p, d, B, 0, s);
@@ -812,7 +854,7 @@ extern "C" mis_status mis_moonshine_decoder_forward(mis_moonshine* c, const int3
     HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIP_CHECK(hipMemcpyAsync(c->ids.p, tokens, c->batch * 4, hipMemcpyDefault, s));
-    hipLaunchKernelGGL(k_ms_embed, dim3(c->batch), dim3(256), 0, s, c->emb, c->ids.p, c->dh.p, c->d, c->V);
+    ms_launch_embed(c->emb, c->ids.p, c->dh.p, c->d, c->V, c->batch, s);
     ms_enqueue_layers(c, c->pos);
     c->pos += 1;
     if (logits_out) HIP_CHECK(hipMemcpyAsync(logits_out, c->logits.p, (size_t)c->batch * c->V * 4, hipMemcpyDeviceToHost, s));
@@ -842,13 +884,13 @@ extern "C" mis_status mis_stt_moonshine_generate(mis_moonshine* c, const float* 
     HIP_CHECK(hipMemsetAsync(c->active.p, 1, batch, s));
     std::vector<int32_t> start(batch, c->cfg.decoder_start_token_id);
     HIP_CHECK(hipMemcpyAsync(c->ids.p, start.data(), batch * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ms_embed, dim3(batch), dim3(256), 0, s, c->emb, c->ids.p, c->dh.p, c->d, c->V);
+    ms_launch_embed(c->emb, c->ids.p, c->dh.p, c->d, c->V, batch, s);
     PinnedBuf<int32_t> done(1);
     *done.p = 0;
     for (int step = 0; step < max_tokens; ++step) {
         ms_enqueue_layers(c, step);
-        hipLaunchKernelGGL(k_ms_argmax_embed, dim3(batch), dim3(256), 0, s, c->logits.p, c->V, c->cfg.eos_token_id, c->active.p, c->n_gen.p,
-                           c->tokens_out.p, max_tokens, c->done_count.p, c->emb, c->dh.p, c->d);
+        ms_launch_argmax_embed(c->logits.p, c->V, c->cfg.eos_token_id, c->active.p, c->n_gen.p, c->tokens_out.p, max_tokens, c->done_count.p, c->emb,
+                               c->dh.p, c->d, batch, s);
         if ((step & 7) == 7 || step + 1 == max_tokens) {          // the EOS check the loop needs, every 8 steps
             HIP_CHECK(hipMemcpyAsync(done.p, c->done_count.p, 4, hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
@@ -863,5 +905,284 @@ extern "C" mis_status mis_stt_moonshine_generate(mis_moonshine* c, const float* 
     for (int b = 0; b < batch; ++b) n_tokens[b] = std::min(n_tokens[b], max_tokens);
     *tokens_out = th.release();
     *tokens_stride = max_tokens;
+    MIS_API_END
+}
+
+// ============================================================================ test scaffolding (include/mi_speech_debug.h)
+// ONE launch of a private kernel above (GroupNorm: its chain of four), through the launcher the engine calls, on caller-supplied host
+// data, so that tests/test_gpu_moonshine_ops.py can hold the kernels to an operator-level reference.  Nothing is computed here: the
+// operands are uploaded as given and what the launch wrote is copied back.  Guards as the other operator entry points (debug_guard.h):
+// every output is [guard | body | guard], all of it the byte 0xFF before the launch (an output that also goes IN - the rotated rows, the
+// caches, the in-place residual, the token bookkeeping - holds the caller's data instead); a changed guard byte or padding column fails
+// the call; every input is followed by IN_GUARD NaNs (ints: 0x7FFFFFFF).  The entry points refuse what the kernels' contract excludes
+// (MIS_ERR_INVALID_INPUT, nothing launched).  The launches run on the null stream.
+#include "debug_guard.h"
+#include "../../include/mi_speech_debug.h"
+
+namespace {
+
+constexpr int64_t MSD_MAX_ELEMS = (int64_t)1 << 28;          // per tensor
+
+void msd_sync() {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+}
+const int* msd_int(const DevBuf<uint32_t>& d) { return reinterpret_cast<const int*>(d.p); }
+const float* msd_f32(const DevBuf<uint32_t>& d) { return reinterpret_cast<const float*>(d.p); }
+void msd_fetch(GuardedOut& o, void* out) {
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+}
+// an output that also goes in
+void msd_inout(GuardedOut& o, const void* src, size_t bytes, size_t guard_bytes) {
+    o.alloc(bytes, guard_bytes);
+    HIP_CHECK(hipMemcpy(o.p(), src, bytes, hipMemcpyHostToDevice));
+}
+// rows of ld with `cols` live columns -> the live columns; the columns behind must still hold the fill
+void msd_fetch16_rows(GuardedOut& o, size_t rows, size_t ld, size_t cols, uint16_t* out) {
+    o.check_guards();
+    std::vector<uint16_t> h(o.body / 2);
+    HIP_CHECK(hipMemcpy(h.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        std::copy(h.begin() + r * ld, h.begin() + r * ld + cols, out + r * cols);
+        for (size_t c = cols; c < ld; ++c)
+            MIS_REQUIRE(h[r * ld + c] == 0xFFFF, MIS_ERR_GENERATION_FAILED, "the kernel wrote column %zu of row %zu behind its %zu columns", c, r, cols);
+    }
+}
+
+}  // namespace
+
+extern "C" mis_status mis_debug_moonshine_conv1(int device, const float* pcm, int64_t stride, const int32_t* T1, int B, int T1pad, int d, const float* wT,
+                                                float* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pcm && T1 && wT && out && B >= 1 && B <= 65535 && T1pad >= 1 && d >= 1 && stride >= 1, MIS_ERR_INVALID_INPUT,
+                "Moonshine conv1: every pointer and positive B, T1pad, d, stride are required");
+    MIS_REQUIRE((int64_t)B * stride <= MSD_MAX_ELEMS && (int64_t)B * T1pad * d <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Moonshine conv1: tensor too large");
+    for (int b = 0; b < B; ++b)
+        MIS_REQUIRE(T1[b] >= 0 && T1[b] <= T1pad && (T1[b] == 0 || (int64_t)(T1[b] - 1) * 64 + 127 <= stride), MIS_ERR_INVALID_INPUT,
+                    "Moonshine conv1: row %d: %d frames outside 0..T1pad or reading behind the row's %lld samples", b, T1[b], (long long)stride);
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint32_t> dp, dw, dT;
+    alloc32(dp, pcm, (size_t)B * stride, F32_NAN);
+    alloc32(dw, wT, (size_t)127 * d, F32_NAN);
+    alloc32(dT, T1, B, 0x7FFFFFFFu);
+    GuardedOut o;
+    o.alloc((size_t)B * T1pad * d * 4, (size_t)16 * d * 4);
+    ms_launch_conv1(msd_f32(dp), stride, msd_int(dT), msd_f32(dw), reinterpret_cast<float*>(o.p()), T1pad, d, B, nullptr);
+    msd_sync();
+    msd_fetch(o, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_groupnorm(int device, const float* x, const int32_t* T1, int B, int T1pad, int d, const float* gw, const float* gb,
+                                                    int stage, float* part0, float* part1, float* stats, uint16_t* y, int32_t* nch_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && T1 && gw && gb && nch_out && B >= 1 && B <= MS_MAX_BATCH && T1pad >= 1 && d >= 1 && stage >= 0 && stage <= 2, MIS_ERR_INVALID_INPUT,
+                "Moonshine GroupNorm: x, T1, gw, gb, nch_out, 1 <= B <= 64, positive T1pad, d and stage 0..2 are required");
+    MIS_REQUIRE(part0 && (stage < 1 || part1) && (stage < 2 || (stats && y)), MIS_ERR_INVALID_INPUT, "Moonshine GroupNorm: the stage's outputs are required");
+    MIS_REQUIRE((int64_t)B * T1pad * d + 8 * (int64_t)d <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Moonshine GroupNorm: tensor too large");
+    int T1max = 0;
+    for (int b = 0; b < B; ++b) {
+        MIS_REQUIRE(T1[b] >= 1 && T1[b] <= T1pad, MIS_ERR_INVALID_INPUT, "Moonshine GroupNorm: row %d: %d frames outside 1..T1pad", b, T1[b]);
+        T1max = std::max(T1max, T1[b]);
+    }
+    HIP_CHECK(hipSetDevice(device));
+    const size_t n1 = (size_t)B * T1pad * d;
+    const int nch = ms_gn_chunks(T1max, d);
+    *nch_out = nch;
+    DevBuf<uint32_t> dx, dT, dgw, dgb;
+    {   // frames behind a row's own count: NaN
+        std::vector<float> h(x, x + n1);
+        for (int b = 0; b < B; ++b)
+            for (size_t i = ((size_t)b * T1pad + T1[b]) * d; i < (size_t)(b + 1) * T1pad * d; ++i) memcpy(&h[i], &F32_NAN, 4);
+        alloc32(dx, h.data(), n1, F32_NAN);
+    }
+    alloc32(dT, T1, B, 0x7FFFFFFFu);
+    alloc32(dgw, gw, d, F32_NAN);
+    alloc32(dgb, gb, d, F32_NAN);
+    GuardedOut p0, p1, st, o;
+    p0.alloc((size_t)B * nch * 4, 256);                            // only what the stage launches into
+    if (stage >= 1) p1.alloc((size_t)B * nch * 4, 256);
+    if (stage >= 2) { st.alloc((size_t)2 * B * 4, 256); o.alloc((n1 + ms_gn_tail(d)) * 2, (size_t)4 * d * 2); }
+    float *f0 = reinterpret_cast<float*>(p0.p()), *f1 = reinterpret_cast<float*>(p1.p());
+    ms_launch_gn_partial(0, msd_f32(dx), msd_int(dT), T1pad, d, nullptr, f0, nch, B, nullptr);
+    if (stage >= 1) ms_launch_gn_partial(1, msd_f32(dx), msd_int(dT), T1pad, d, f0, f1, nch, B, nullptr);
+    if (stage >= 2) {
+        float* fs = reinterpret_cast<float*>(st.p());
+        ms_launch_gn_final(f0, f1, msd_int(dT), d, nch, fs, B, nullptr);
+        ms_launch_gn_apply(msd_f32(dx), msd_int(dT), fs, msd_f32(dgw), msd_f32(dgb), reinterpret_cast<bf16_t*>(o.p()), T1pad, d, B, nullptr);
+    }
+    msd_sync();
+    msd_fetch(p0, part0);
+    if (stage >= 1) msd_fetch(p1, part1);
+    if (stage >= 2) { msd_fetch(st, stats); msd_fetch(o, y); }
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_rope(int device, uint16_t* rows, int M, int ld, int nheads, int Tpad, int rot, const float* cs, const float* sn) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(rows && cs && sn && M >= 1 && nheads >= 1 && Tpad >= 1 && (int64_t)nheads * MS_DP <= ld, MIS_ERR_INVALID_INPUT,
+                "Moonshine RoPE: rows, both tables, M, Tpad >= 1 and 1 <= nheads <= ld / 64 are required");
+    MIS_REQUIRE(rot >= 2 && rot <= MS_DP && rot % 2 == 0, MIS_ERR_INVALID_INPUT, "Moonshine RoPE: rot %d is not an even number in 2..64", rot);
+    MIS_REQUIRE((int64_t)M * ld <= MSD_MAX_ELEMS && (int64_t)Tpad * (rot / 2) <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Moonshine RoPE: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint32_t> dc, ds;
+    alloc32(dc, cs, (size_t)Tpad * (rot / 2), F32_NAN);
+    alloc32(ds, sn, (size_t)Tpad * (rot / 2), F32_NAN);
+    GuardedOut r;
+    msd_inout(r, rows, (size_t)M * ld * 2, (size_t)4 * ld * 2);
+    ms_launch_rope_rows(reinterpret_cast<bf16_t*>(r.p()), ld, nheads, Tpad, rot, msd_f32(dc), msd_f32(ds), (size_t)M, nullptr);
+    msd_sync();
+    msd_fetch(r, rows);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_attn(int device, int kind, const uint16_t* q, const uint16_t* kv, int ld, int H, int Hkv, const int32_t* T3, int B,
+                                               int Tpad, float scale, int ldo, uint16_t* kc, uint16_t* vc, int Smax, int pos, int rot, const float* cs,
+                                               const float* sn, uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(kind >= 0 && kind <= 2 && q && out && B >= 1 && B <= 65535 && H >= 1 && H <= 65535 && Hkv >= 1, MIS_ERR_INVALID_INPUT,
+                "Moonshine attention: kind 0..2, q, out and positive B, H, Hkv are required");
+    MIS_REQUIRE(H % Hkv == 0, MIS_ERR_INVALID_INPUT, "Moonshine attention: %d kv heads do not divide %d heads", Hkv, H);
+    const size_t NA = (size_t)H * MS_DP, NQ = (size_t)(H + 2 * Hkv) * MS_DP, NKV = (size_t)2 * Hkv * MS_DP;
+    if (kind != 1) {
+        MIS_REQUIRE(T3 && Tpad >= 1 && (int64_t)B * Tpad * std::max<int64_t>(ld, NKV) <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                    "Moonshine attention: T3 and Tpad >= 1 are required (or the tensor is too large)");
+        for (int b = 0; b < B; ++b)
+            MIS_REQUIRE(T3[b] >= (kind == 2 ? 1 : 0) && T3[b] <= MS_MAX_KEYS && T3[b] <= Tpad, MIS_ERR_INVALID_INPUT,
+                        "Moonshine attention: row %d: %d keys outside %d..min(Tpad, %d)", b, T3[b], kind == 2 ? 1 : 0, MS_MAX_KEYS);
+    }
+    if (kind == 0)
+        MIS_REQUIRE(ld % 8 == 0 && (int64_t)NQ <= ld && (int64_t)NA <= ldo && (int64_t)B * Tpad * ldo <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                    "Moonshine encoder attention: ld >= (H + 2 Hkv) 64 in 16-byte rows, ldo >= H 64");
+    if (kind == 2) MIS_REQUIRE(kv, MIS_ERR_INVALID_INPUT, "Moonshine cross-attention: kv is required");
+    if (kind == 1) {
+        MIS_REQUIRE(kc && vc && cs && sn && Smax >= 1 && Smax <= MS_MAX_POS && pos >= 0 && pos < Smax, MIS_ERR_INVALID_INPUT,
+                    "Moonshine self-attention: both caches and tables, 1 <= Smax <= %d and 0 <= pos < Smax are required", MS_MAX_POS);
+        MIS_REQUIRE(rot >= 2 && rot <= MS_DP && rot % 2 == 0, MIS_ERR_INVALID_INPUT, "Moonshine self-attention: rot %d is not an even number in 2..64", rot);
+        MIS_REQUIRE((int64_t)B * Hkv * Smax * MS_DP <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Moonshine self-attention: tensor too large");
+    }
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint16_t> dq, dkv;
+    DevBuf<uint32_t> dT, dc, ds;
+    GuardedOut o;
+    bf16_t* op = nullptr;
+    if (kind == 0) {
+        const size_t rows = (size_t)B * Tpad;
+        alloc16(dq, q, rows * ld, BF16_NAN);
+        alloc32(dT, T3, B, 0x7FFFFFFFu);
+        o.alloc(rows * ldo * 2, (size_t)4 * ldo * 2);
+        op = reinterpret_cast<bf16_t*>(o.p());
+        ms_launch_attn_enc(dq.p, ld, H, Hkv, msd_int(dT), Tpad, scale, op, ldo, B, nullptr);
+        msd_sync();
+        msd_fetch16_rows(o, rows, ldo, NA, out);
+    } else if (kind == 2) {
+        alloc16(dq, q, (size_t)B * NA, BF16_NAN);
+        alloc16(dkv, kv, (size_t)B * Tpad * NKV, BF16_NAN);
+        alloc32(dT, T3, B, 0x7FFFFFFFu);
+        o.alloc((size_t)B * NA * 2, NA * 2);
+        op = reinterpret_cast<bf16_t*>(o.p());
+        ms_launch_attn_cross(dq.p, H, Hkv, dkv.p, msd_int(dT), Tpad, scale, op, B, nullptr);
+        msd_sync();
+        msd_fetch(o, out);
+    } else {
+        const size_t nc = (size_t)B * Hkv * Smax * MS_DP;
+        alloc16(dq, q, (size_t)B * NQ, BF16_NAN);
+        alloc32(dc, cs, (size_t)Smax * (rot / 2), F32_NAN);
+        alloc32(ds, sn, (size_t)Smax * (rot / 2), F32_NAN);
+        GuardedOut gk, gv;
+        msd_inout(gk, kc, nc * 2, (size_t)Smax * MS_DP * 2);
+        msd_inout(gv, vc, nc * 2, (size_t)Smax * MS_DP * 2);
+        o.alloc((size_t)B * NA * 2, NA * 2);
+        op = reinterpret_cast<bf16_t*>(o.p());
+        ms_launch_attn_self(dq.p, H, Hkv, reinterpret_cast<bf16_t*>(gk.p()), reinterpret_cast<bf16_t*>(gv.p()), Smax, pos, rot, msd_f32(dc), msd_f32(ds), scale,
+                            op, B, nullptr);
+        msd_sync();
+        msd_fetch(o, out);
+        msd_fetch(gk, kc);
+        msd_fetch(gv, vc);
+    }
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_gemv(int device, int ln, int epi, const uint16_t* X, const uint16_t* lnw, const uint16_t* W, const uint16_t* bias,
+                                               int B, int K, int N, int F, void* out, int32_t* report) {
+    MIS_API_BEGIN
+    if (report) { report[0] = -1; report[1] = -1; }
+    MIS_REQUIRE(X && W && out && B >= 1 && K >= 1 && N >= 1 && (ln == 0 || ln == 1) && (!ln || lnw), MIS_ERR_INVALID_INPUT,
+                "Moonshine decode GEMM: X, W, out, positive B, K, N and ln 0 / 1 (with lnw) are required");
+    MIS_REQUIRE(K % 4 == 0 && B <= MS_MAX_BATCH && (!ln || K <= 512), MIS_ERR_INVALID_INPUT,
+                "Moonshine decode GEMM: K %% 4, B <= %d and K <= 512 under LayerNorm are the kernel's contract", MS_MAX_BATCH);
+    const int inst = 4 * ln + epi;
+    MIS_REQUIRE(inst == 4 + MS_BF16 || inst == MS_RESID || inst == 4 + MS_GATE || inst == 4 + MS_F32, MIS_ERR_INVALID_INPUT,
+                "Moonshine decode GEMM: (ln %d, epi %d) is not one of the decoder's four instantiations", ln, epi);
+    MIS_REQUIRE(epi != MS_GATE || (F >= 1 && N == 2 * F), MIS_ERR_INVALID_INPUT, "Moonshine decode GEMM: the gate epilogue needs N == 2 F");
+    MIS_REQUIRE((int64_t)N * K <= MSD_MAX_ELEMS && (int64_t)B * N <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Moonshine decode GEMM: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint16_t> dX, dl, dW, db;
+    alloc16(dX, X, (size_t)B * K, BF16_NAN);
+    if (ln) alloc16(dl, lnw, K, BF16_NAN);
+    alloc16(dW, W, (size_t)N * K, BF16_NAN);
+    if (bias) alloc16(db, bias, N, BF16_NAN);
+    const size_t cols = epi == MS_GATE ? F : N, es = epi == MS_F32 ? 4 : 2;
+    GuardedOut o;
+    if (epi == MS_RESID) msd_inout(o, out, (size_t)B * cols * es, (size_t)8 * cols * es);          // a guard is one eight-row register group
+    else o.alloc((size_t)B * cols * es, (size_t)8 * cols * es);
+    const bf16_t *lp = ln ? dl.p : nullptr, *bp = bias ? db.p : nullptr;
+    int ran = -1;
+    if (inst == 4 + MS_BF16) ran = ms_gemv<true, MS_BF16>(dX.p, K, lp, dW.p, bp, o.p(), N, B, F, nullptr);
+    else if (inst == MS_RESID) ran = ms_gemv<false, MS_RESID>(dX.p, K, lp, dW.p, bp, o.p(), N, B, F, nullptr);
+    else if (inst == 4 + MS_GATE) ran = ms_gemv<true, MS_GATE>(dX.p, K, lp, dW.p, bp, o.p(), N, B, F, nullptr);
+    else ran = ms_gemv<true, MS_F32>(dX.p, K, lp, dW.p, bp, o.p(), N, B, F, nullptr);
+    msd_sync();
+    if (report) { report[0] = ran / 4; report[1] = ran % 4; }
+    msd_fetch(o, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_embed(int device, const uint16_t* emb, const int32_t* ids, int B, int d, int vocab, uint16_t* h) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(emb && ids && h && B >= 1 && d >= 1 && vocab >= 1 && (int64_t)vocab * d <= MSD_MAX_ELEMS && (int64_t)B * d <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Moonshine embed: emb, ids, h and positive B, d, vocab are required");
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint16_t> de;
+    DevBuf<uint32_t> di;
+    alloc16(de, emb, (size_t)vocab * d, BF16_NAN);
+    alloc32(di, ids, B, 0x7FFFFFFFu);
+    GuardedOut o;
+    o.alloc((size_t)B * d * 2, (size_t)d * 2);
+    ms_launch_embed(de.p, msd_int(di), reinterpret_cast<bf16_t*>(o.p()), d, vocab, B, nullptr);
+    msd_sync();
+    msd_fetch(o, h);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_moonshine_argmax_embed(int device, const float* logits, int B, int V, int eos, uint8_t* active, int32_t* n_gen, int32_t* tokens,
+                                                       int stride, int32_t* done_count, const uint16_t* emb, int d, uint16_t* h) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(logits && active && n_gen && tokens && done_count && emb && h && B >= 1 && V >= 1 && stride >= 1 && d >= 1, MIS_ERR_INVALID_INPUT,
+                "Moonshine arg-max + embed: every pointer and positive B, V, stride, d are required");
+    MIS_REQUIRE((int64_t)B * V <= MSD_MAX_ELEMS && (int64_t)V * d <= MSD_MAX_ELEMS && (int64_t)B * stride <= MSD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Moonshine arg-max + embed: tensor too large");
+    for (int b = 0; b < B; ++b) MIS_REQUIRE(n_gen[b] >= 0, MIS_ERR_INVALID_INPUT, "Moonshine arg-max + embed: row %d: negative token count", b);
+    HIP_CHECK(hipSetDevice(device));
+    DevBuf<uint32_t> dl;
+    DevBuf<uint16_t> de;
+    alloc32(dl, logits, (size_t)B * V, F32_NAN);
+    alloc16(de, emb, (size_t)V * d, BF16_NAN);
+    GuardedOut ga, gn, gt, gd, o;
+    msd_inout(ga, active, B, 256);
+    msd_inout(gn, n_gen, (size_t)B * 4, 256);
+    msd_inout(gt, tokens, (size_t)B * stride * 4, (size_t)stride * 4);
+    msd_inout(gd, done_count, 4, 256);
+    o.alloc((size_t)B * d * 2, (size_t)d * 2);
+    ms_launch_argmax_embed(msd_f32(dl), V, eos, ga.p(), reinterpret_cast<int32_t*>(gn.p()), reinterpret_cast<int32_t*>(gt.p()), stride,
+                           reinterpret_cast<int32_t*>(gd.p()), de.p, reinterpret_cast<bf16_t*>(o.p()), d, B, nullptr);
+    msd_sync();
+    msd_fetch(ga, active);
+    msd_fetch(gn, n_gen);
+    msd_fetch(gt, tokens);
+    msd_fetch(gd, done_count);
+    msd_fetch(o, h);
     MIS_API_END
 }
