@@ -1033,6 +1033,58 @@ mis_status mis_fsmn_vad_detect_raw(mis_fsmn_vad*, const float* pcm, const int64_
 mis_status mis_fsmn_vad_tap(mis_fsmn_vad*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * Silero voice activity detection (Sources/MLXAudioVAD/Models/SileroVAD/SileroVAD.swift): mono rows of differing lengths at 16 kHz or
+ * 8 kHz (two branches with their own weights), 1..max_batch a call, of ANY length -> one speech probability per chunk of chunk_size
+ * samples (32 ms).  Row b of n_b samples has ceil(n_b / chunk_size) chunks; chunk j's window is samples [j chunk - context, (j + 1) chunk)
+ * of the row, zeros before sample 0 and behind sample n_b, then `pad` samples reflected on the right (padded[n + i] = w[n - 2 - i], NOT
+ * torch's reflect).  Per window: stft_conv (1 -> 2 cutoff, kernel filter_length, stride hop_length) + magnitude, conv1..conv4 (k3; strides
+ * 1, 2, 2, 1; zero-padded inside the chunk) + ReLU, LSTM 128 -> 128 (gates i, f, g, o) carrying (h, c) from the previous chunk,
+ * sigmoid(final_conv(relu(h))) averaged over the chunk's LSTM steps (one at the published branches).  All of it exact f32.
+ * The chunks of a call are walked in passes of max_chunks inside one workspace sized at finalize, with the state carried on the device -
+ * a call allocates nothing and synchronises once.  A row's probabilities and final state do not depend on the batch it travels in, on
+ * what lies behind lens[b], on max_chunks, or on whether it came through predict or chunk by chunk through forward: bit for bit.
+ * The thresholding into timestamps and segments is host work (vad.py).
+ * Rejected with MIS_ERR_INVALID_INPUT at create: a window (context + chunk) no longer than pad, a padded window shorter than the filter,
+ * sizes outside the ranges the messages name; at set_tensor an unknown name, a second tensor of a name, a wrong shape; at finalize a
+ * missing tensor; at a call a sample rate other than 16000 / 8000, batch outside 1..max_batch, a row longer than stride, too little
+ * room in an output, a null pointer, a handle that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_silero_vad mis_silero_vad;
+/* SileroVADBranchConfig */
+typedef struct {
+    int32_t sample_rate, filter_length, hop_length, pad, cutoff, context_size, chunk_size;
+} mis_silero_vad_branch_config;
+typedef struct {
+    mis_silero_vad_branch_config branch16k, branch8k;   /* served at sample_rate 16000 / 8000 */
+    int32_t max_batch, max_chunks;                      /* 1..64 rows a call; chunks a pass (1..65536) */
+} mis_silero_vad_config;
+mis_status mis_silero_vad_create(const mis_silero_vad_config*, int device, mis_silero_vad** out);
+/* names as SileroVAD.sanitize leaves them: branch16k. / branch8k. + stft_conv.weight [2 cutoff, filter_length, 1], conv1.weight
+ * [128, 3, cutoff], conv2.weight [64, 3, 128], conv3.weight [64, 3, 64], conv4.weight [128, 3, 64], convN.bias, lstm.Wx / lstm.Wh
+ * [512, 128], lstm.bias [512], final_conv.weight [1, 1, 128], final_conv.bias [1]; host pointers.  Every name is set exactly once and
+ * its shape is checked at the call; finalize names a missing one. */
+mis_status mis_silero_vad_set_tensor(mis_silero_vad*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_silero_vad_init_synthetic(mis_silero_vad*, uint64_t seed);
+mis_status mis_silero_vad_finalize(mis_silero_vad*);
+void       mis_silero_vad_destroy(mis_silero_vad*);
+/* kernel launches of the last call: 7 a pass (STFT + magnitude, conv1..conv4, Wx, the recurrence) */
+int        mis_silero_vad_launches(const mis_silero_vad*);
+/* chunks of rows of lens[b] samples at that sample rate */
+mis_status mis_silero_vad_chunks(const mis_silero_vad*, const int64_t* lens, int batch, int sample_rate, int32_t* chunks_out);
+/* predictProba of a ragged batch: pcm f32 [batch, stride], lens[batch] (NULL = stride) -> probs f32 [batch, cols], cols >= the longest
+ * row's chunks, zeros behind a row's own.  state f32 [2, batch, 128] (h, c): state_in NULL = zeros, state_out NULL = not returned.  A
+ * batch of empty rows launches nothing and passes the state through. */
+mis_status mis_silero_vad_predict(mis_silero_vad*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int sample_rate,
+                                  float* probs_out, int cols, const float* state_in, float* state_out);
+/* SileroVAD.callAsFunction, one chunk: windows f32 [batch, context_size + chunk_size] -> probs f32 [batch] and the new state */
+mis_status mis_silero_vad_forward(mis_silero_vad*, const float* windows, int batch, int sample_rate, const float* state_in, float* probs_out,
+                                  float* state_out);
+/* tensors of the last pass of the last call, f32, zeros behind a row's own chunks.  stage 0 magnitude [B, P F, cutoff], 1 conv1
+ * [B, P F, 128], 2 conv2 [B, P F2, 64], 3 conv3 [B, P F3, 64], 4 conv4 [B, P F3, 128], 5 the gate pre-activations Wx x + bias
+ * [B, P S, 512], 6 the probabilities [B, P, 1]; P the pass's chunks.  dims[3] receives B, rows, width; out NULL for the dims alone. */
+mis_status mis_silero_vad_tap(mis_silero_vad*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * MossFormer2-SE speech enhancement (csrc/mossformer2.hip; MLXAudioSTS/Models/MossFormer2SE): noisy waveform -> enhanced waveform.
  * Row b of n_b samples has T_b = n_b < win_len ? 0 : 1 + (n_b - win_len) / win_inc frames and (T_b - 1) win_inc + min(win_len, fft_len)
  * output samples (0 without a frame).  Front end: x 32768, per frame minus its mean, pre-emphasis (first sample x0 - c x0), symmetric

@@ -358,6 +358,10 @@ mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms);
  * fbank), encoder (+ copy out) */
 mis_status mis_debug_fsmn_vad_timing(const mis_fsmn_vad* c, float* ms);
 
+/* csrc/silero_vad.hip, measurements: device milliseconds of the last call summed over its first 64 passes, ms[2] = front end (copy in +
+ * the six contractions), recurrence */
+mis_status mis_debug_silero_vad_timing(const mis_silero_vad* c, float* ms);
+
 /* csrc/mossformer2.hip, measurements: device milliseconds of the last call, ms[3] = front end (copy in + fbank + deltas), mask network,
  * synthesis (+ copy out) */
 mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);

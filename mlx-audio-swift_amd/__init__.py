@@ -20,6 +20,8 @@ the Swift shim a maintainer would add):
     smartturn.SmartTurnModel <-> class SmartTurnModel (endpoint detection)  (MLXAudioVAD/Models/SmartTurn/SmartTurn.swift)
     lid.EcapaTdnnLID         <-> class EcapaTdnn (spoken language identification)  (MLXAudioLID/Models/EcapaTdnn/EcapaTdnnLID.swift)
     vad.FSMNVAD              <-> class FSMNVAD (voice activity detection)  (MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift)
+    vad.SileroVAD            <-> class SileroVAD (voice activity detection) (MLXAudioVAD/Models/SileroVAD/SileroVAD.swift)
+    vad.segment_speech       <-> func segmentSpeech (VAD -> STT chunker)    (MLXAudioVAD/SpeechSegmenter.swift)
     sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
     sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
@@ -55,7 +57,10 @@ from .lasr import (LasrCTCModel, LasrCTCConfig, LasrEncoderConfig, SentencePiece
                    greedy_ctc_tokens)
 from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitize, fsmn_vad_expected_shapes,  # noqa: F401
                   fsmn_vad_check_weights, fsmn_vad_read_directory, fsmn_vad_read_cmvn, fsmn_vad_postprocess, parse_kaldi_cmvn,
-                  chunks_from_segments)
+                  chunks_from_segments, merge_runs, SileroVAD, SileroVADConfig, SileroVADBranchConfig, SileroVADError,
+                  SileroVADStreamingState, SpeechSegmentConfig, silero_vad_sanitize, silero_vad_expected_shapes, silero_vad_check_weights,
+                  silero_vad_read_directory, silero_vad_probs_to_timestamps, silero_vad_chunk_samples, speech_runs_from_probs,
+                  detect_speech_runs, segment_speech)
 from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSModelError, mossformer2_sanitize,  # noqa: F401
                   mossformer2_normalized_key, mossformer2_expected_shapes, mossformer2_check_weights, resolve_sts_model_type,
                   load_sts_model)

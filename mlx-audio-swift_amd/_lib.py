@@ -167,6 +167,15 @@ class FsmnVadConfigC(C.Structure):
                 + [("sil_pdf_ids", C.c_int32 * 16), ("max_batch", C.c_int32), ("chunk_frames", C.c_int32)])
 
 
+class SileroVadBranchConfigC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "filter_length", "hop_length", "pad", "cutoff", "context_size", "chunk_size")]
+
+
+class SileroVadConfigC(C.Structure):
+    _fields_ = [("branch16k", SileroVadBranchConfigC), ("branch8k", SileroVadBranchConfigC), ("max_batch", C.c_int32),
+                ("max_chunks", C.c_int32)]
+
+
 class BigVGANConfigC(C.Structure):
     _fields_ = [("num_mels", C.c_int32), ("n_upsamples", C.c_int32), ("upsample_rates", C.c_int32 * 8),
                 ("n_upsample_kernel_sizes", C.c_int32), ("upsample_kernel_sizes", C.c_int32 * 8), ("upsample_initial_channel", C.c_int32),
@@ -357,6 +366,16 @@ SYMBOLS = {
     "mis_fsmn_vad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
     "mis_fsmn_vad_detect_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int]),
     "mis_fsmn_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_silero_vad_create": (C.c_int, [C.POINTER(SileroVadConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_silero_vad_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_silero_vad_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_silero_vad_finalize": (C.c_int, [_P]),
+    "mis_silero_vad_destroy": (None, [_P]),
+    "mis_silero_vad_launches": (C.c_int, [_P]),
+    "mis_silero_vad_chunks": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "mis_silero_vad_predict": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, C.c_int, _P, _P]),
+    "mis_silero_vad_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "mis_silero_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_bigvgan_create": (C.c_int, [C.POINTER(BigVGANConfigC), C.c_int, C.POINTER(_P)]),
     "mis_bigvgan_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_bigvgan_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -566,6 +585,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_lasr_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P]),
     "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
+    "mis_debug_silero_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_aa_act": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),

@@ -1,6 +1,8 @@
-"""FSMN voice activity detection, host mirror of `FSMNVAD` (Sources/MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift).  Configuration,
-checkpoint and CMVN loading, the ragged-batch packing and the serial post-processing (:239-701) stay on the host; the Kaldi-style fbank,
-LFR stacking + CMVN and the FSMN encoder run in libmi_speech.so (csrc/fsmn_vad.hip), for rows of any length."""
+"""Voice activity detection, host mirrors of `FSMNVAD` (Sources/MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift), `SileroVAD`
+(Models/SileroVAD/SileroVAD.swift) and `segmentSpeech` (SpeechSegmenter.swift).  Configuration, checkpoint and CMVN loading, the
+ragged-batch packing and the serial post-processing stay on the host; the Kaldi-style fbank, LFR stacking + CMVN and the FSMN encoder
+(csrc/fsmn_vad.hip), and Silero's chunk-parallel front end and LSTM recurrence (csrc/silero_vad.hip) run in libmi_speech.so, for rows of
+any length."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +13,7 @@ from dataclasses import dataclass, field, fields
 import numpy as np
 
 from . import _lib
-from ._handle import NativeHandle, pack_rows
+from ._handle import NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 
 _F = np.float32
@@ -390,6 +392,12 @@ def chunks_from_segments(segments_ms, n_samples: int, sample_rate: int, merge_ga
             runs.append((s0, e0))
     if not runs:
         return [(0, int(n_samples), 0.0)]
+    return [(a, b, a / float(sample_rate)) for a, b in merge_runs(runs, sample_rate, merge_gap_s, max_chunk_s)]
+
+
+def merge_runs(runs, sample_rate: int, merge_gap_s: float = 1.0, max_chunk_s: float = 30.0) -> list:
+    """mergeRuns / splitLong (SpeechSegmenter.swift:115-155) on a non-empty list of (start_sample, end_sample): what
+    chunks_from_segments and segment_speech share.  The two limits are formed in float32 as the Swift forms them."""
     max_chunk = max(1, int(_F(max_chunk_s) * _F(sample_rate)))
     max_gap = int(_F(merge_gap_s) * _F(sample_rate))
 
@@ -405,7 +413,7 @@ def chunks_from_segments(segments_ms, n_samples: int, sample_rate: int, merge_ga
             merged[-1] = (p0, b)
         else:
             merged.extend(split(a, b))
-    return [(a, b, a / float(sample_rate)) for a, b in merged]
+    return merged
 
 
 # ------------------------------------------------------------------------------------------------------------ the model
@@ -561,3 +569,460 @@ class FSMNVAD(NativeHandle):
         ms = (C.c_float * 2)()
         check(_lib.lib().mis_debug_fsmn_vad_timing(self._h, ms))
         return float(ms[0]), float(ms[1])
+
+
+# ============================================================================================================ Silero VAD
+class SileroVADError(AudioGenerationError):
+    """SileroVADError (SileroVAD.swift:29-48): `.kind` holds the Swift case name, the message its errorDescription."""
+
+    def __init__(self, kind: str, message: str):
+        self.kind = kind
+        super().__init__(3, message)
+
+    @classmethod
+    def invalid_repository_id(cls, repo):
+        return cls("invalidRepositoryID", f"Invalid repository ID: {repo}")
+
+    @classmethod
+    def unsupported_sample_rate(cls, sr):
+        return cls("unsupportedSampleRate", f"Silero VAD supports 8000 Hz and 16000 Hz audio (got {sr})")
+
+    @classmethod
+    def state_sample_rate_mismatch(cls, expected, got):
+        return cls("stateSampleRateMismatch", f"Streaming state is for {expected} Hz, got {got} Hz")
+
+    @classmethod
+    def unexpected_chunk_size(cls, expected, got):
+        return cls("unexpectedChunkSize", f"Expected {expected} samples per chunk, got {got}")
+
+    @classmethod
+    def insufficient_reflect_pad_input(cls, samples, pad):
+        return cls("insufficientReflectPadInput", f"Reflect padding of {pad} requires more than {pad} samples (got {samples})")
+
+
+@dataclass
+class SileroVADBranchConfig:
+    """SileroVADBranchConfig (SileroVADConfig.swift:3-50): every field, default and JSON key."""
+    sample_rate: int = 16000
+    filter_length: int = 256
+    hop_length: int = 128
+    pad: int = 64
+    cutoff: int = 129
+    context_size: int = 64
+    chunk_size: int = 512
+
+    @classmethod
+    def default_16k(cls) -> "SileroVADBranchConfig":
+        return cls()
+
+    @classmethod
+    def default_8k(cls) -> "SileroVADBranchConfig":
+        return cls(sample_rate=8000, filter_length=128, hop_length=64, pad=32, cutoff=65, context_size=32, chunk_size=256)
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "SileroVADBranchConfig":
+        """The synthesized Codable init: every key is required."""
+        names = [f.name for f in fields(cls)]
+        missing = [k for k in names if k not in d]
+        if missing:
+            raise AudioGenerationError(3, f"Silero VAD: branch config misses {missing}")
+        return cls(**{k: int(d[k]) for k in names})
+
+    @property
+    def window(self) -> int:
+        return self.context_size + self.chunk_size
+
+    def to_c(self) -> "_lib.SileroVadBranchConfigC":
+        return _lib.SileroVadBranchConfigC(self.sample_rate, self.filter_length, self.hop_length, self.pad, self.cutoff, self.context_size,
+                                           self.chunk_size)
+
+
+_SILERO_KEYS = ("model_type", "architecture", "dtype", "threshold", "min_speech_duration_ms", "min_silence_duration_ms", "speech_pad_ms")
+
+
+@dataclass
+class SileroVADConfig:
+    """SileroVADConfig (SileroVADConfig.swift:52-109): every field and default; the JSON keys of the branches are branch_16k / branch_8k.
+    max_batch / max_chunks size the engine's workspace (rows a call, chunks a pass) and are not part of a checkpoint."""
+    model_type: str = "silero_vad"
+    architecture: str = "silero_vad"
+    dtype: str = "float32"
+    threshold: float = 0.5
+    min_speech_duration_ms: int = 250
+    min_silence_duration_ms: int = 100
+    speech_pad_ms: int = 30
+    branch16k: SileroVADBranchConfig = field(default_factory=SileroVADBranchConfig.default_16k)
+    branch8k: SileroVADBranchConfig = field(default_factory=SileroVADBranchConfig.default_8k)
+    max_batch: int = 8
+    max_chunks: int = 1024
+
+    @classmethod
+    def from_dict(cls, d: dict, **workspace) -> "SileroVADConfig":
+        """init(from:) (:97-108): missing or null keys take the defaults, unknown keys are ignored."""
+        kw = {k: d[k] for k in _SILERO_KEYS if d.get(k) is not None}
+        if d.get("branch_16k") is not None:
+            kw["branch16k"] = SileroVADBranchConfig.from_dict(d["branch_16k"])
+        if d.get("branch_8k") is not None:
+            kw["branch8k"] = SileroVADBranchConfig.from_dict(d["branch_8k"])
+        return cls(**kw, **workspace)
+
+    def branch(self, sample_rate: int) -> SileroVADBranchConfig:
+        """branch(forSampleRate:) (SileroVAD.swift:145-151)."""
+        if int(sample_rate) == 16000:
+            return self.branch16k
+        if int(sample_rate) == 8000:
+            return self.branch8k
+        raise SileroVADError.unsupported_sample_rate(sample_rate)
+
+    def to_c(self) -> "_lib.SileroVadConfigC":
+        return _lib.SileroVadConfigC(self.branch16k.to_c(), self.branch8k.to_c(), self.max_batch, self.max_chunks)
+
+
+def silero_vad_sanitize(weights: dict) -> dict:
+    """sanitize (SileroVAD.swift:331-344): val_* dropped, vad_16k. -> branch16k., vad_8k. -> branch8k."""
+    out = {}
+    for k, v in weights.items():
+        if k.startswith("val_"):
+            continue
+        if k.startswith("vad_16k."):
+            k = "branch16k." + k[len("vad_16k."):]
+        elif k.startswith("vad_8k."):
+            k = "branch8k." + k[len("vad_8k."):]
+        out[k] = v
+    return out
+
+
+def silero_vad_expected_shapes(config: SileroVADConfig) -> dict:
+    """name -> shape of every parameter of SileroVAD(config): what update(parameters:verify: .all) accepts (:374).  MLX conv weights are
+    [out, kernel, in]."""
+    s = {}
+    for prefix, b in (("branch16k.", config.branch16k), ("branch8k.", config.branch8k)):
+        s[prefix + "stft_conv.weight"] = (2 * b.cutoff, b.filter_length, 1)
+        for i, (cin, cout) in enumerate(((b.cutoff, 128), (128, 64), (64, 64), (64, 128)), 1):
+            s[f"{prefix}conv{i}.weight"], s[f"{prefix}conv{i}.bias"] = (cout, 3, cin), (cout,)
+        s[prefix + "lstm.Wx"], s[prefix + "lstm.Wh"], s[prefix + "lstm.bias"] = (512, 128), (512, 128), (512,)
+        s[prefix + "final_conv.weight"], s[prefix + "final_conv.bias"] = (1, 1, 128), (1,)
+    return s
+
+
+def silero_vad_check_weights(config: SileroVADConfig, weights: dict):
+    want = silero_vad_expected_shapes(config)
+    unknown, missing = sorted(set(weights) - set(want)), sorted(set(want) - set(weights))
+    if unknown or missing:
+        raise AudioGenerationError(3, f"Silero VAD checkpoint: unexpected keys {unknown[:4]}, missing keys {missing[:4]}")
+    bad = [k for k in want if tuple(weights[k].shape) != want[k]]
+    if bad:
+        raise AudioGenerationError(3, f"Silero VAD checkpoint: {bad[0]} has shape {tuple(weights[bad[0]].shape)}, expected {want[bad[0]]}")
+
+
+def silero_vad_read_directory(model_dir: str, **workspace):
+    """config.json and every *.safetensors of a model directory (fromModelDirectory, :357-377) -> (SileroVADConfig, sanitized weights),
+    all keys verified.  No device is touched."""
+    path = os.path.join(model_dir, "config.json")
+    if not os.path.isfile(path):
+        raise AudioGenerationError(3, "Silero VAD: config.json not found in model directory")
+    with open(path) as f:
+        cfg = SileroVADConfig.from_dict(json.load(f), **workspace)
+    weights = silero_vad_sanitize(read_safetensors_dir(model_dir, missing_code=(3, "Silero VAD: no *.safetensors in model directory")))
+    silero_vad_check_weights(cfg, weights)
+    return cfg, weights
+
+
+def silero_vad_chunk_samples(sample_rate: int) -> int:
+    """The chunk the host-side thresholding assumes (probsToTimestamps :276, detectSpeechRuns :47): 512 at 16 kHz, else 256."""
+    return 512 if int(sample_rate) == 16000 else 256
+
+
+def silero_vad_probs_to_timestamps(probabilities, audio_len: int, sample_rate: int, threshold: float, min_speech_duration_ms: int,
+                                   min_silence_duration_ms: int, speech_pad_ms: int) -> list:
+    """probsToTimestamps (SileroVAD.swift:265-329) -> [(start_sample, end_sample)]; a 2-D input gives its first row.  The thresholds and
+    the minimum durations are numpy.float32 where the Swift uses Float."""
+    probs = np.asarray(probabilities, _F)
+    if probs.ndim == 2:
+        probs = probs[0]
+    chunk = silero_vad_chunk_samples(sample_rate)
+    thr = _F(threshold)
+    min_speech = _F(sample_rate) * _F(min_speech_duration_ms) / _F(1000)
+    min_silence = _F(sample_rate) * _F(min_silence_duration_ms) / _F(1000)
+    pad = int(_F(sample_rate) * _F(speech_pad_ms) / _F(1000))
+    neg = max(thr - _F(0.15), _F(0.01))
+    speeches, triggered, start, temp_end = [], False, 0, 0
+    for idx, p in enumerate(probs):
+        at = idx * chunk
+        if p >= thr and not triggered:
+            triggered, start, temp_end = True, at, 0
+            continue
+        if triggered and p >= thr:
+            temp_end = 0
+            continue
+        if triggered and p < neg:
+            if temp_end == 0:
+                temp_end = at
+            if _F(at - temp_end) >= min_silence:
+                if _F(temp_end - start) >= min_speech:
+                    speeches.append((start, temp_end))
+                triggered, temp_end = False, 0
+    if triggered:
+        end = min(int(audio_len), len(probs) * chunk)
+        if _F(end - start) >= min_speech:
+            speeches.append((start, end))
+    out = []
+    for a, b in speeches:
+        a, b = max(0, a - pad), min(int(audio_len), b + pad)
+        if out and a <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], b))
+        else:
+            out.append((a, b))
+    return out
+
+
+@dataclass
+class SileroVADStreamingState:
+    """SileroVADStreamingState (SileroVAD.swift:17-27): lstm_state f32 [2, batch, 128] or None, context f32 [batch, context_size]."""
+    lstm_state: np.ndarray | None
+    context: np.ndarray
+    sample_rate: int
+
+
+class SileroVAD(NativeHandle):
+    """callAsFunction / initialState / feed / predictProba / getSpeechTimestamps of the reference class, plus ragged batches; one handle,
+    1..max_batch rows a call, rows of any length (the engine walks them in passes of max_chunks with the LSTM state kept on the device)."""
+    _prefix = "mis_silero_vad"
+    STAGES = ("magnitude", "conv1", "conv2", "conv3", "conv4", "gates", "probs")
+
+    def __init__(self, config: SileroVADConfig | None = None, device: int = 0):
+        self.config = config if config is not None else SileroVADConfig()
+        self.device = device
+        self._create(self.config.to_c(), device)
+
+    @classmethod
+    def from_weights(cls, config: SileroVADConfig, weights: dict, device: int = 0) -> "SileroVAD":
+        """weights: sanitized names (what silero_vad_sanitize returns), all of them and no others."""
+        silero_vad_check_weights(config, weights)
+        m = cls(config, device)
+        for name, arr in weights.items():
+            m.set_tensor(name, arr)
+        m.finalize()
+        return m
+
+    @classmethod
+    def synthetic(cls, config: SileroVADConfig | None = None, device: int = 0, seed: int = 777) -> "SileroVAD":
+        m = cls(config, device)
+        check(_lib.lib().mis_silero_vad_init_synthetic(m._h, seed))
+        m.finalize()
+        return m
+
+    @classmethod
+    def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "SileroVAD":
+        cfg, weights = silero_vad_read_directory(model_dir, **workspace)
+        return cls.from_weights(cfg, weights, device)
+
+    @classmethod
+    def from_pretrained(cls, path: str, device: int = 0, **workspace) -> "SileroVAD":
+        """fromPretrained (:346-355) for a local path; this package downloads nothing."""
+        p = os.path.expanduser(path)
+        if not os.path.isdir(p):
+            raise SileroVADError.invalid_repository_id(f"{path} (no local model directory; nothing is downloaded)")
+        return cls.from_model_directory(p, device, **workspace)
+
+    sanitize = staticmethod(silero_vad_sanitize)
+    probs_to_timestamps = staticmethod(silero_vad_probs_to_timestamps)
+
+    @property
+    def launches(self) -> int:
+        return int(_lib.lib().mis_silero_vad_launches(self._h))
+
+    # -- one chunk -----------------------------------------------------------------------------------
+    def _state_arg(self, state, batch):
+        if state is None:
+            return None
+        st = np.ascontiguousarray(state, _F)
+        if st.shape != (2, batch, 128):
+            raise AudioGenerationError(3, f"Silero VAD: expected state shape (2, {batch}, 128), got {st.shape}")
+        return st
+
+    def __call__(self, x, state=None, sample_rate: int = 16000):
+        """callAsFunction (:153-160): windows [n] or [batch, n], n = context_size + chunk_size, state [2, batch, 128] or None ->
+        (prob [batch, 1], new state [2, batch, 128])."""
+        b = self.config.branch(sample_rate)
+        w = np.ascontiguousarray(x, _F)
+        if w.ndim == 1:
+            w = w[None]
+        if w.ndim != 2:
+            raise AudioGenerationError(3, f"Silero VAD: windows must be [batch, samples], got shape {w.shape}")
+        if w.shape[1] <= b.pad:
+            raise SileroVADError.insufficient_reflect_pad_input(w.shape[1], b.pad)
+        if w.shape[1] != b.window:
+            raise AudioGenerationError(3, f"Silero VAD: a window of {w.shape[1]} samples; the engine serves context_size + chunk_size = {b.window}")
+        B = w.shape[0]
+        st = self._state_arg(state, B)
+        prob, new = np.zeros((B, 1), _F), np.zeros((2, B, 128), _F)
+        check(_lib.lib().mis_silero_vad_forward(self._h, w.ctypes.data, B, int(sample_rate), None if st is None else st.ctypes.data,
+                                                prob.ctypes.data, new.ctypes.data))
+        return prob, new
+
+    def initial_state(self, batch_size: int = 1, sample_rate: int = 16000) -> SileroVADStreamingState:
+        b = self.config.branch(sample_rate)
+        return SileroVADStreamingState(None, np.zeros((batch_size, b.context_size), _F), int(sample_rate))
+
+    def feed(self, chunk, state: SileroVADStreamingState | None = None, sample_rate: int = 16000):
+        """feed (:168-190): chunk [chunk_size] or [batch, chunk_size] -> (prob [batch, 1], the next streaming state)."""
+        b = self.config.branch(sample_rate)
+        c = np.asarray(chunk, _F)
+        if c.ndim == 1:
+            c = c[None]
+        if c.shape[-1] != b.chunk_size:
+            raise SileroVADError.unexpected_chunk_size(b.chunk_size, c.shape[-1])
+        st = state if state is not None else self.initial_state(c.shape[0], sample_rate)
+        if st.sample_rate != int(sample_rate):
+            raise SileroVADError.state_sample_rate_mismatch(st.sample_rate, int(sample_rate))
+        prob, lstm = self(np.concatenate([st.context, c], axis=-1), st.lstm_state, sample_rate)
+        return prob, SileroVADStreamingState(lstm, c[:, c.shape[-1] - b.context_size:].copy(), int(sample_rate))
+
+    # -- whole rows ----------------------------------------------------------------------------------
+    def chunks(self, lens, sample_rate: int = 16000) -> np.ndarray:
+        lens = np.ascontiguousarray(lens, np.int64)
+        out = np.zeros(len(lens), np.int32)
+        check(_lib.lib().mis_silero_vad_chunks(self._h, lens.ctypes.data, len(lens), int(sample_rate), out.ctypes.data))
+        return out
+
+    def predict_proba_batch(self, waveforms, sample_rate: int = 16000, state=None, junk: float | None = None, return_state: bool = False):
+        """Ragged list of 1-D waveforms -> one float32 array of probabilities per row (an empty row gives an empty array); with
+        return_state also the LSTM state [2, B, 128] behind every row's last chunk.  state: the state to start from, or None."""
+        self.config.branch(sample_rate)
+        rows = [np.asarray(w, _F) for w in waveforms]
+        if not rows or any(r.ndim != 1 for r in rows):
+            raise AudioGenerationError(3, "Silero VAD: a non-empty list of one-dimensional waveforms is expected")
+        pcm, lens = pack_rows(rows, junk)
+        B, stride = pcm.shape
+        st = self._state_arg(state, B)
+        nc = self.chunks(lens, sample_rate) if B <= self.config.max_batch else np.zeros(B, np.int32)
+        cols = max(1, int(nc.max()))
+        probs, new = np.zeros((B, cols), _F), np.zeros((2, B, 128), _F)
+        check(_lib.lib().mis_silero_vad_predict(self._h, pcm.ctypes.data, lens.ctypes.data, B, stride, int(sample_rate), probs.ctypes.data, cols,
+                                                None if st is None else st.ctypes.data, new.ctypes.data))
+        out = [probs[b, : nc[b]].copy() for b in range(B)]
+        return (out, new) if return_state else out
+
+    def predict_proba(self, audio, sample_rate: int = 16000) -> np.ndarray:
+        """predictProba (:192-241): audio [n] -> [chunks], audio [B, n] -> [B, chunks]; no samples give no chunks."""
+        self.config.branch(sample_rate)
+        a = np.asarray(audio, _F)
+        if a.ndim not in (1, 2):
+            raise AudioGenerationError(3, f"Silero VAD: audio must be [samples] or [batch, samples], got shape {a.shape}")
+        if a.shape[-1] == 0:
+            return np.zeros(a.shape, _F)
+        out = np.stack(self.predict_proba_batch(list(a[None] if a.ndim == 1 else a), sample_rate))
+        return out[0] if a.ndim == 1 else out
+
+    def get_speech_timestamps(self, audio, sample_rate: int = 16000, threshold=None, min_speech_duration_ms=None, min_silence_duration_ms=None,
+                              speech_pad_ms=None) -> list:
+        """getSpeechTimestamps (:243-263) -> [(start_sample, end_sample)]."""
+        a = np.asarray(audio, _F)
+        c = self.config
+        return silero_vad_probs_to_timestamps(
+            self.predict_proba(a, sample_rate), a.shape[-1], sample_rate, c.threshold if threshold is None else threshold,
+            c.min_speech_duration_ms if min_speech_duration_ms is None else min_speech_duration_ms,
+            c.min_silence_duration_ms if min_silence_duration_ms is None else min_silence_duration_ms,
+            c.speech_pad_ms if speech_pad_ms is None else speech_pad_ms)
+
+    def tap(self, stage) -> np.ndarray:
+        """Tensors of the last pass of the last call, [B, P, frames, width] (P the pass's chunks; zeros behind a row's own): 0 magnitude,
+        1..4 conv1..conv4, 5 gate pre-activations Wx x + bias, 6 probabilities [B, P].  A stage may be given by its name in STAGES."""
+        stage = self.STAGES.index(stage) if isinstance(stage, str) else int(stage)
+        dims = (C.c_int64 * 3)()
+        check(_lib.lib().mis_silero_vad_tap(self._h, stage, None, 0, dims))
+        out = np.zeros(tuple(int(d) for d in dims), _F)
+        check(_lib.lib().mis_silero_vad_tap(self._h, stage, out.ctypes.data, out.size, dims))
+        if stage == 6:
+            return out[:, :, 0]
+        P = self.tap(6).shape[1]
+        return out.reshape(out.shape[0], P, out.shape[1] // P, out.shape[2])
+
+    def timing(self):
+        """Device milliseconds of the last call: (front end, recurrence)."""
+        ms = (C.c_float * 2)()
+        check(_lib.lib().mis_debug_silero_vad_timing(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
+
+# ------------------------------------------------------------------------------------------------------------ segmentSpeech
+@dataclass
+class SpeechSegmentConfig:
+    """SpeechSegmentConfig (SpeechSegmenter.swift:6-29)."""
+    threshold: float = 0.5
+    min_speech_ms: int = 250
+    min_silence_ms: int = 100
+    speech_pad_ms: int = 30
+    merge_gap_s: float = 1.0
+    max_chunk_s: float = 30.0
+
+
+_BLOCKS_PER_256MS = 8
+
+
+def speech_runs_from_probs(probs, n_samples: int, sample_rate: int, config: SpeechSegmentConfig | None = None) -> list:
+    """The part of detectSpeechRuns (SpeechSegmenter.swift:47-112) behind predictProba: per-chunk probabilities -> [(start_sample,
+    end_sample)].  Eight chunks form a ~256 ms block of probability 1 - prod(1 - p) in float32; the minimum durations round UP."""
+    cfg = config if config is not None else SpeechSegmentConfig()
+    p32 = np.asarray(probs, _F).ravel()
+    block_samples = silero_vad_chunk_samples(sample_rate) * _BLOCKS_PER_256MS
+    block_s = _F(block_samples) / _F(sample_rate)
+    nb = len(p32) // _BLOCKS_PER_256MS
+    if nb == 0:
+        return []
+    one = _F(1.0)
+    p256 = np.zeros(nb, _F)
+    for i in range(nb):
+        prod = one
+        for k in range(_BLOCKS_PER_256MS):
+            prod = _F(prod * _F(one - p32[i * _BLOCKS_PER_256MS + k]))
+        p256[i] = one - prod
+    pad_blocks = max(0, int(_F(cfg.speech_pad_ms) / _F(1000) / block_s))
+    min_speech = max(1, int(np.ceil(_F(cfg.min_speech_ms) / _F(1000) / block_s)))
+    min_silence = max(1, int(np.ceil(_F(cfg.min_silence_ms) / _F(1000) / block_s)))
+    thr = _F(cfg.threshold)
+    runs, in_speech, seg_start, last_speech, silent = [], False, 0, -1, 0
+
+    def close(seg_end):
+        if seg_end - seg_start >= min_speech:
+            s, e = seg_start * block_samples, min(seg_end * block_samples, int(n_samples))
+            if s < e:
+                runs.append((s, e))
+
+    for idx, p in enumerate(p256):
+        if p >= thr:
+            if not in_speech:
+                seg_start, in_speech = max(0, idx - pad_blocks), True
+            last_speech, silent = idx, 0
+        elif in_speech:
+            silent += 1
+            if silent >= min_silence:
+                close(min(last_speech + 1 + pad_blocks, nb))
+                in_speech, silent, last_speech = False, 0, -1
+    if in_speech:
+        close(min(nb, last_speech + 1 + pad_blocks))
+    return runs
+
+
+def _mono(audio) -> np.ndarray:
+    a = np.asarray(audio, _F)
+    return a.mean(axis=-1, dtype=_F) if a.ndim > 1 else a
+
+
+def detect_speech_runs(audio, sample_rate: int, vad_model, config: SpeechSegmentConfig | None = None) -> list:
+    """detectSpeechRuns (SpeechSegmenter.swift:38-113): vad_model.predict_proba, then speech_runs_from_probs."""
+    a = _mono(audio)
+    return speech_runs_from_probs(vad_model.predict_proba(a, sample_rate), len(a), sample_rate, config)
+
+
+def segment_speech(audio, sample_rate: int, vad_model, config: SpeechSegmentConfig | None = None) -> list:
+    """segmentSpeech (SpeechSegmenter.swift:162-183) -> [(segment, offset_s)]: silence dropped, runs within merge_gap_s merged, long runs
+    cut at max_chunk_s (merge_runs, shared with chunks_from_segments); the whole buffer at offset 0 when no speech is found.  audio with
+    more than one dimension is averaged over its last."""
+    cfg = config if config is not None else SpeechSegmentConfig()
+    a = _mono(audio)
+    raw = detect_speech_runs(a, sample_rate, vad_model, cfg)
+    if not raw:
+        return [(a, 0.0)]
+    return [(a[s:e], float(_F(s) / _F(sample_rate))) for s, e in merge_runs(raw, sample_rate, cfg.merge_gap_s, cfg.max_chunk_s)]
