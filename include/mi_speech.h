@@ -1145,6 +1145,68 @@ mis_status mis_mossformer2_synthesize(mis_mossformer2*, const float* pcm, const 
 mis_status mis_mossformer2_tap(mis_mossformer2*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * DeepFilterNet V2 / V3 speech enhancement, offline (csrc/deepfilternet.hip; MLXAudioSTS/Models/DeepFilterNet): noisy waveform ->
+ * enhanced waveform of the same length.  Row b of n_b samples is padded with hop_size zeros in front and fft_size zeros behind (in the
+ * operand load) and has T_b = 1 + (hop_size + n_b) / hop_size frames.  Analysis: Vorbis window, fft_size-point transform, x wnorm =
+ * 2 hop / fft^2.  Features: ERB energies (erb_fb [freq_bins, nb_erb] as a contraction when the checkpoint has it, else band means over
+ * erb_widths), 10 log10(. + 1e-10), and the two exponential normalisations as the recurrence s_t = a s_(t-1) + (1 - a) x_t (band mean:
+ * state linspace(-60, -90), / 40; complex unit norm of the first nb_df bins: state linspace(1e-3, 1e-4), / sqrt(max(s, 1e-12))).
+ * Network: the look-ahead shift, causal convs (time kernel 1..5, frequency kernel 1 or 3, grouped / depthwise in the operand load of
+ * their pointwise conv, BatchNorm folded at finalize), three squeezed GRUs (grouped linear_in, every GRU layer the checkpoint has, one
+ * launch a layer for all frames of all rows; linear_out where present), ERB decoder -> mask [T, nb_erb], DF decoder -> coefficients
+ * [T, nb_df, df_order, 2], lsnr.  Synthesis: bins >= nb_df: spec x (mask @ erb_inv_fb); bins < nb_df: the deep filter of the unmasked
+ * spec; / wnorm, inverse transform, window, overlap-add / max(sum w^2, 1e-8), the first fft_size - hop_size samples dropped, n_b
+ * samples kept, clip to [-1, 1].  All of it exact f32.  One workspace is sized at finalize for max_batch rows of max_samples: a call
+ * allocates nothing and synchronises once; a row's result does not depend on the batch it travels in or on what lies behind lens[b],
+ * bit for bit.  Not served: DeepFilterNet (V1), enc_concat, streaming.
+ * Rejected with MIS_ERR_INVALID_INPUT at create: sizes outside the ranges the messages name, a hidden size other than 32 / 64 / 128 /
+ * 256 (the recurrence kernel's instantiations), erb_widths that do not sum to freq_bins; at finalize a tensor missing or misshapen, a
+ * kernel size outside the served ones; at a call batch outside 1..max_batch, a row longer than stride or max_samples, too little room
+ * in an output, a null pointer, a handle that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_deepfilternet mis_deepfilternet;
+/* the fields of DeepFilterNetConfig the engine reads + the sizes of the workspace.  emb_num_layers .. df_pathway_kernel_size_t only
+ * shape init_synthetic's weights: a checkpoint's layer counts, groups and kernel sizes are taken from its tensors. */
+typedef struct {
+    int32_t sample_rate, fft_size, hop_size, nb_erb, nb_df, df_order, df_lookahead, conv_lookahead, conv_ch, emb_hidden_dim, df_hidden_dim;
+    int32_t lsnr_max, lsnr_min;
+    int32_t emb_num_layers, df_num_layers, linear_groups, enc_linear_groups, conv_kernel[2], convt_kernel[2], conv_kernel_inp[2],
+            df_pathway_kernel_size_t;
+    int32_t gru_kr;                      /* columns of Wh a thread keeps in registers at hidden size 256: 64, 96, 128; 0 = the default */
+    int32_t max_batch;                   /* 1..64 rows a call */
+    float   norm_alpha;                  /* computeNormAlpha(hop_size, sample_rate) */
+    int32_t erb_widths[128];             /* the first nb_erb: bins of every band, summing to fft_size / 2 + 1 */
+    int64_t max_samples;                 /* the longest row a call may carry */
+} mis_deepfilternet_config;
+mis_status mis_deepfilternet_create(const mis_deepfilternet_config*, int device, mis_deepfilternet** out);
+/* names as the reference reads them (mask.erb_inv_fb, erb_fb, enc.erb_conv0.1.weight, enc.emb_gru.gru.weight_hh_l0,
+ * df_dec.df_out.0.weight, ...) in the torch layouts: Conv2d [out, in / groups, kT, kF], ConvTranspose2d [in, out / groups, kT, kF],
+ * grouped linears [groups, in / groups, out / groups], GRU [3 H, in] with gates r | z | n; host pointers; f32 / f16 / bf16, widened
+ * to f32.  finalize names a missing weight and checks every shape. */
+mis_status mis_deepfilternet_set_tensor(mis_deepfilternet*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_deepfilternet_init_synthetic(mis_deepfilternet*, uint64_t seed);
+mis_status mis_deepfilternet_finalize(mis_deepfilternet*);
+void       mis_deepfilternet_destroy(mis_deepfilternet*);
+/* kernel launches of the last call: 26 + [erb_fb] + [df_skip] + [enc linear_out] + [erb_dec linear_out] + 2 L_enc + L_erb + L_df +
+ * (emb_hidden_dim == df_hidden_dim ? max(L_erb, L_df) : L_erb + L_df), L_. the GRU layers of the three chains */
+int        mis_deepfilternet_launches(const mis_deepfilternet*);
+/* T_b and the output length (= lens[b]) of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_deepfilternet_frames(const mis_deepfilternet*, const int64_t* lens, int batch, int32_t* frames_out, int64_t* out_lens);
+/* DeepFilterNetModel.enhance for a ragged batch: pcm f32 [batch, stride], lens[batch] (NULL = stride) -> out f32 [batch, out_stride]
+ * (out_stride >= the longest row, at least 1), out_lens[batch] (may be NULL), lsnr f32 [batch, lsnr_rows] per frame (may be NULL;
+ * lsnr_rows >= the longest row's T_b); zeros behind a row's own */
+mis_status mis_deepfilternet_enhance(mis_deepfilternet*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* out,
+                                     int64_t out_stride, int64_t* out_lens, float* lsnr_out, int lsnr_rows);
+/* tensors of the last call, f32 [B, rows, width], zeros behind a row's own rows; width = frequency x channel, channel fastest.
+ * stage 0 spec [re F | im F], 1 ERB feature [nb_erb], 2 complex feature [nb_df, 2], 3..6 e0..e3, 7 c0, 8 c1, 9 emb in front of the
+ * encoder GRU, 10 emb behind it (after linear_out), 11 lsnr, 12 the ERB decoder's squeezed GRU (after linear_out), 13 relu(conv3p) +
+ * that, 14 convt3, 15 relu(conv2p) + 14, 16 convt2, 17 relu(conv1p) + 16, 18 convt1, 19 relu(conv0p) + 18, 20 mask [nb_erb], 21 the DF
+ * decoder's GRU output (+ df_skip), 22 c0p [nb_df, 2 df_order], 23 coefficients [nb_df, df_order, 2], 24 enhanced spec / wnorm
+ * [re F | im F], 25 waveform [B, samples, 1], 26 ERB energies in dB (with erb_fb only); 32 + 16 chain + 0 linear_in, + 1 + l GRU layer
+ * l, chain 0 enc.emb_gru, 1 erb_dec.emb_gru, 2 df_dec.df_gru.  dims[3] receives B, rows, width; out NULL for the dims alone. */
+mis_status mis_deepfilternet_tap(mis_deepfilternet*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Sortformer speaker diarization (csrc/sortformer.hip; Sources/MLXAudioVAD/Models/Sortformer/Sortformer.swift, SortformerConfig.swift,
  * SortformerFeatures.swift): "who spoke when" for up to num_speakers speakers.  16 kHz mono rows of differing lengths, 1..max_batch a
  * call.  Row b of n_b samples has F_b = 1 + n_b / 160 feature frames (per-call options: peak normalisation x / (max|x| + 1e-3);

@@ -366,6 +366,10 @@ mis_status mis_debug_silero_vad_timing(const mis_silero_vad* c, float* ms);
  * synthesis (+ copy out) */
 mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);
 
+/* csrc/deepfilternet.hip, measurements: device milliseconds of the last call, ms[4] = front end (copy in + STFT + features), network
+ * without the recurrences, the recurrence launches, synthesis (+ copy out) */
+mis_status mis_debug_deepfilternet_timing(const mis_deepfilternet* c, float* ms);
+
 /* csrc/sortformer.hip, measurements: ms NULL switches the timestamps of mis_sortformer_forward on; else device milliseconds of the
  * last call, which must have been mis_sortformer_forward (MIS_ERR_NOT_INITIALIZED otherwise): ms[4] = front end, stem, Conformer blocks,
  * projection + BART layers + head */

@@ -191,6 +191,15 @@ class MossFormer2ConfigC(C.Structure):
                 + [("preemphasis", C.c_float), ("max_samples", C.c_int64)])
 
 
+class DeepFilterNetConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("sample_rate", "fft_size", "hop_size", "nb_erb", "nb_df", "df_order", "df_lookahead", "conv_lookahead",
+                                          "conv_ch", "emb_hidden_dim", "df_hidden_dim", "lsnr_max", "lsnr_min", "emb_num_layers",
+                                          "df_num_layers", "linear_groups", "enc_linear_groups")]
+                + [("conv_kernel", C.c_int32 * 2), ("convt_kernel", C.c_int32 * 2), ("conv_kernel_inp", C.c_int32 * 2),
+                   ("df_pathway_kernel_size_t", C.c_int32), ("gru_kr", C.c_int32), ("max_batch", C.c_int32), ("norm_alpha", C.c_float),
+                   ("erb_widths", C.c_int32 * 128), ("max_samples", C.c_int64)])
+
+
 class LasrConfigC(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "num_key_value_heads",
                                           "intermediate_size", "hidden_act", "conv_kernel_size", "convolution_bias", "num_mel_bins",
@@ -398,6 +407,15 @@ SYMBOLS = {
     "mis_mossformer2_enhance": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P]),
     "mis_mossformer2_synthesize": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int64, _P]),
     "mis_mossformer2_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_deepfilternet_create": (C.c_int, [C.POINTER(DeepFilterNetConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_deepfilternet_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_deepfilternet_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_deepfilternet_finalize": (C.c_int, [_P]),
+    "mis_deepfilternet_destroy": (None, [_P]),
+    "mis_deepfilternet_launches": (C.c_int, [_P]),
+    "mis_deepfilternet_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_deepfilternet_enhance": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int]),
+    "mis_deepfilternet_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_lasr_create": (C.c_int, [C.POINTER(LasrConfigC), C.c_int, C.POINTER(_P)]),
     "mis_lasr_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_lasr_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -587,6 +605,7 @@ DEBUG_SYMBOLS = {
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_silero_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
+    "mis_debug_deepfilternet_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_aa_act": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "mis_debug_sortformer_timing": (C.c_int, [_P, _P]),

@@ -1,4 +1,5 @@
-"""MossFormer2-SE speech enhancement, host mirror of `MossFormer2SEModel` (Sources/MLXAudioSTS/Models/MossFormer2SE) and of the
+"""MossFormer2-SE and DeepFilterNet speech enhancement, host mirrors of `MossFormer2SEModel` (Sources/MLXAudioSTS/Models/MossFormer2SE),
+`DeepFilterNetModel` (Sources/MLXAudioSTS/Models/DeepFilterNet; csrc/deepfilternet.hip) and of the
 `STS.loadModel` factory (Sources/MLXAudioSTS/STSModel.swift).  Configuration, checkpoint loading and the ragged-batch packing stay on
 the host; the Kaldi-style fbank + deltas, the mask network and the STFT / inverse STFT run in libmi_speech.so (csrc/mossformer2.hip)."""
 from __future__ import annotations
@@ -352,8 +353,473 @@ class MossFormer2SE(NativeHandle):
         return float(ms[0]), float(ms[1]), float(ms[2])
 
 
+# ------------------------------------------------------------------------------------------------------------ DeepFilterNet
+class DeepFilterNetError(AudioGenerationError):
+    """DeepFilterNetError (DeepFilterNetModel.swift:8-37): `.sts_case` is modelPathNotFound, missingConfig, missingWeights,
+    missingWeightKey, invalidAudioShape or streamingNotSupportedForModelVersion.  invalidRepoID cannot be reached: nothing is downloaded."""
+
+    def __init__(self, sts_case: str, message: str):
+        self.sts_case = sts_case
+        super().__init__(3, message)
+
+
+_DFN_KEYS = ("sample_rate", "fft_size", "hop_size", "min_nb_erb_freqs", "nb_erb", "nb_df", "df_order", "df_lookahead", "conv_lookahead",
+             "conv_ch", "conv_k_enc", "conv_k_dec", "conv_width_factor", "emb_hidden_dim", "emb_num_layers", "df_hidden_dim", "df_num_layers",
+             "gru_groups", "linear_groups", "enc_linear_groups", "group_shuffle", "enc_concat", "df_gru_skip", "conv_kernel", "convt_kernel",
+             "conv_kernel_inp", "df_pathway_kernel_size_t", "lsnr_max", "lsnr_min", "model_version", "erb_widths")
+
+
+def compute_norm_alpha(hop_size: int, sample_rate: int) -> float:
+    """computeNormAlpha (DeepFilterNetDSP.swift:102-112) in float32: exp(-hop / sr) rounded to the fewest decimals (from 3) below 1."""
+    a_raw = np.exp(-_F(hop_size) / _F(sample_rate), dtype=_F)
+    precision, a = 3, _F(1.0)
+    while a >= 1.0:
+        scale = _F(10.0) ** _F(precision)
+        a = _F(np.floor(np.abs(a_raw * scale) + _F(0.5)) * np.sign(a_raw)) / scale      # .rounded(): half away from zero
+        precision += 1
+    return float(a)
+
+
+def libdf_erb_band_widths(sample_rate: int, fft_size: int, nb_bands: int, min_nb_freqs: int) -> list:
+    """libdfErbBandWidths (DeepFilterNetDSP.swift:159-201) in float32."""
+    if sample_rate <= 0 or fft_size <= 0 or nb_bands <= 0:
+        return []
+    f2e = lambda f: _F(9.265) * np.log1p(_F(f) / (_F(24.7) * _F(9.265)), dtype=_F)
+    e2f = lambda e: _F(24.7) * _F(9.265) * (np.exp(_F(e) / _F(9.265), dtype=_F) - _F(1.0))
+    nyq, freq_width = sample_rate // 2, _F(sample_rate) / _F(fft_size)
+    erb_low, erb_high = f2e(0), f2e(nyq)
+    step = (erb_high - erb_low) / _F(nb_bands)
+    widths, prev, over, min_bins = [0] * nb_bands, 0, 0, max(1, min_nb_freqs)
+    for i in range(1, nb_bands + 1):
+        q = e2f(erb_low + _F(i) * step) / freq_width
+        fb = int(np.floor(q + _F(0.5)))
+        nb = fb - prev - over
+        if nb < min_bins:
+            over, nb = min_bins - nb, min_bins
+        else:
+            over = 0
+        widths[i - 1] = max(1, nb)
+        prev = fb
+    widths[-1] += 1
+    widths[-1] += fft_size // 2 + 1 - sum(widths)
+    return widths
+
+
+@dataclass
+class DeepFilterNetConfig:
+    """DeepFilterNetConfig (DeepFilterNetConfig.swift): every field, default and snake_case key.  max_batch / max_seconds size the
+    engine's workspace, gru_kr picks the register columns of the recurrence kernel (0: the default); none is part of a checkpoint."""
+    sample_rate: int = 48000
+    fft_size: int = 960
+    hop_size: int = 480
+    min_nb_erb_freqs: int = 2
+    nb_erb: int = 32
+    nb_df: int = 96
+    df_order: int = 5
+    df_lookahead: int = 2
+    conv_lookahead: int = 2
+    conv_ch: int = 64
+    conv_k_enc: int = 1
+    conv_k_dec: int = 1
+    conv_width_factor: int = 1
+    emb_hidden_dim: int = 256
+    emb_num_layers: int = 3
+    df_hidden_dim: int = 256
+    df_num_layers: int = 2
+    gru_groups: int = 8
+    linear_groups: int = 16
+    enc_linear_groups: int = 32
+    group_shuffle: bool = False
+    enc_concat: bool = False
+    df_gru_skip: str = "groupedlinear"
+    conv_kernel: tuple = (1, 3)
+    convt_kernel: tuple = (1, 3)
+    conv_kernel_inp: tuple = (3, 3)
+    df_pathway_kernel_size_t: int = 5
+    lsnr_max: int = 35
+    lsnr_min: int = -15
+    model_version: str = "DeepFilterNet3"
+    erb_widths: list | None = None
+    max_batch: int = 8
+    max_seconds: float = 60.0
+    gru_kr: int = 0
+
+    def __post_init__(self):
+        if not self.model_version:
+            self.model_version = "DeepFilterNet3"
+
+    @classmethod
+    def from_dict(cls, d: dict, **workspace) -> "DeepFilterNetConfig":
+        """init(from:): missing or null keys take the defaults, unknown keys are ignored; an empty model_version is DeepFilterNet3."""
+        return cls(**{k: d[k] for k in _DFN_KEYS if d.get(k) is not None}, **workspace)
+
+    @property
+    def freq_bins(self) -> int:
+        return self.fft_size // 2 + 1
+
+    @property
+    def model_type(self) -> str:
+        v = self.model_version.lower()
+        return v if v in ("deepfilternet", "deepfilternet2") else "deepfilternet3"
+
+    @property
+    def max_samples(self) -> int:
+        return max(1, int(round(self.max_seconds * self.sample_rate)))
+
+    @property
+    def norm_alpha(self) -> float:
+        return compute_norm_alpha(self.hop_size, self.sample_rate)
+
+    @property
+    def wnorm(self) -> float:
+        return float(_F(1.0) / _F(self.fft_size * self.fft_size) * _F(2 * self.hop_size))
+
+    @property
+    def erb_band_widths(self) -> list:
+        """The initialiser's rule: the config's widths when they sum to freq_bins, else libdfErbBandWidths."""
+        if self.erb_widths is not None and sum(self.erb_widths) == self.freq_bins:
+            return [int(w) for w in self.erb_widths]
+        return libdf_erb_band_widths(self.sample_rate, self.fft_size, self.nb_erb, max(1, self.min_nb_erb_freqs))
+
+    def check_served(self):
+        if self.model_version.lower() == "deepfilternet":
+            raise AudioGenerationError(3, "DeepFilterNet: model_version 'DeepFilterNet' (V1) is not served: its graph (grouped GRUs, "
+                                          "clc_* decoder, alpha blend) differs from V2 / V3; use a DeepFilterNet2 or DeepFilterNet3 checkpoint")
+        if self.enc_concat:
+            raise AudioGenerationError(3, "DeepFilterNet: enc_concat = true is not served (the encoder adds its two embeddings)")
+
+    def to_c(self) -> "_lib.DeepFilterNetConfigC":
+        self.check_served()
+        w = self.erb_band_widths
+        if not 1 <= self.nb_erb <= 128 or len(w) != self.nb_erb:
+            raise AudioGenerationError(3, f"DeepFilterNet: nb_erb {self.nb_erb} with {len(w)} band widths (1..128 bands are served)")
+        c = _lib.DeepFilterNetConfigC()
+        for k in ("sample_rate", "fft_size", "hop_size", "nb_erb", "nb_df", "df_order", "df_lookahead", "conv_lookahead", "conv_ch",
+                  "emb_hidden_dim", "df_hidden_dim", "lsnr_max", "lsnr_min", "emb_num_layers", "df_num_layers", "linear_groups",
+                  "enc_linear_groups", "df_pathway_kernel_size_t", "gru_kr", "max_batch"):
+            setattr(c, k, int(getattr(self, k)))
+        for k in ("conv_kernel", "convt_kernel", "conv_kernel_inp"):
+            v = list(getattr(self, k))
+            if len(v) != 2:
+                raise AudioGenerationError(3, f"DeepFilterNet: {k} must hold two sizes")
+            setattr(c, k, (C.c_int32 * 2)(*v))
+        c.norm_alpha = self.norm_alpha
+        c.erb_widths = (C.c_int32 * 128)(*w)
+        c.max_samples = self.max_samples
+        return c
+
+
+_DFN_OPTIONAL = ("erb_fb", "df_dec.df_skip.weight", "enc.emb_gru.linear_out.0.weight", "erb_dec.emb_gru.linear_out.0.weight")
+
+
+def deepfilternet_expected_shapes(config: DeepFilterNetConfig, weights: dict) -> dict:
+    """name -> shape of every tensor the V2 / V3 chain reads from `weights`, in the order the reference asks for them
+    (mask.erb_inv_fb first, as its initialiser does).  GRU layer counts, groups and conv kernel sizes are the tensors' own; erb_fb,
+    df_dec.df_skip.weight and the linear_outs are optional.  A missing required key raises missingWeightKey naming it; a shape that
+    does not fit the chain raises with both shapes."""
+    C_, E, D, O, F = config.conv_ch, config.nb_erb, config.nb_df, config.df_order, config.freq_bins
+    want = {}
+
+    def need(key, shape=None):
+        if key not in weights:
+            raise DeepFilterNetError("missingWeightKey", f"Missing DeepFilterNet weight key: {key}")
+        got = tuple(weights[key].shape)
+        if shape is not None:
+            if len(got) != len(shape) or any(s is not None and s != g for s, g in zip(shape, got)):
+                raise AudioGenerationError(3, f"DeepFilterNet checkpoint: {key} has shape {got}, expected "
+                                              f"{tuple('*' if s is None else s for s in shape)}")
+        want[key] = got
+        return got
+
+    def bn(p, n):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            need(f"{p}.{k}", (n,))
+
+    def conv(p, main, pw, bnidx, cin, cout=None, transposed=False):
+        m = need(f"{p}.{main}.weight", (cin, None, None, None) if transposed else (None, None, None, None))
+        mid = cin * m[1] if transposed else m[0]
+        if pw is not None:
+            mid = need(f"{p}.{pw}.weight", (cout, mid, 1, 1))[0]
+        elif cout is not None and mid != cout:
+            raise AudioGenerationError(3, f"DeepFilterNet checkpoint: {p}.{main}.weight has shape {m}, expected {cout} outputs")
+        bn(f"{p}.{bnidx}", mid)
+        return mid
+
+    def squeezed(p, din, hidden, dout):
+        g = need(f"{p}.linear_in.0.weight", (None, None, None))
+        if g[0] * g[1] != din or g[0] * g[2] != hidden:
+            raise AudioGenerationError(3, f"DeepFilterNet checkpoint: {p}.linear_in.0.weight has shape {g}, expected [groups, "
+                                          f"{din} / groups, {hidden} / groups]")
+        n = 0
+        while f"{p}.gru.weight_ih_l{n}" in weights:
+            need(f"{p}.gru.weight_ih_l{n}", (3 * hidden, hidden)), need(f"{p}.gru.weight_hh_l{n}", (3 * hidden, hidden))
+            need(f"{p}.gru.bias_ih_l{n}", (3 * hidden,)), need(f"{p}.gru.bias_hh_l{n}", (3 * hidden,))
+            n += 1
+        if n == 0:
+            need(f"{p}.gru.weight_ih_l0")
+        if dout and f"{p}.linear_out.0.weight" in weights:
+            g = need(f"{p}.linear_out.0.weight", (None, None, None))
+            if g[0] * g[1] != hidden or g[0] * g[2] != dout:
+                raise AudioGenerationError(3, f"DeepFilterNet checkpoint: {p}.linear_out.0.weight has shape {g}, expected [groups, "
+                                              f"{hidden} / groups, {dout} / groups]")
+            return dout
+        return hidden
+
+    need("mask.erb_inv_fb", (E, F))
+    if "erb_fb" in weights:
+        want["erb_fb"] = tuple(weights["erb_fb"].shape)                  # used only when it is [freq_bins, nb_erb] (erbEnergies)
+    conv("enc.erb_conv0", 1, None, 2, 1, C_)
+    for i in (1, 2, 3):
+        conv(f"enc.erb_conv{i}", 0, 1, 2, C_, C_)
+    conv("enc.df_conv0", 1, 2, 3, 2, C_)
+    conv("enc.df_conv1", 0, 1, 2, C_, C_)
+    emb = C_ * (E // 4)
+    g = need("enc.df_fc_emb.0.weight", (None, None, None))
+    if g[0] * g[1] != C_ * (D // 2) or g[0] * g[2] != emb:
+        raise AudioGenerationError(3, f"DeepFilterNet checkpoint: enc.df_fc_emb.0.weight has shape {g}, expected [groups, "
+                                      f"{C_ * (D // 2)} / groups, {emb} / groups]")
+    e_out = squeezed("enc.emb_gru", emb, config.emb_hidden_dim, emb)
+    need("enc.lsnr_fc.0.weight", (1, e_out)), need("enc.lsnr_fc.0.bias", (1,))
+    d_out = squeezed("erb_dec.emb_gru", e_out, config.emb_hidden_dim, emb)
+    if d_out != emb:
+        raise AudioGenerationError(3, f"DeepFilterNet checkpoint: erb_dec.emb_gru gives {d_out} values a frame, the decoder needs {emb}")
+    for i in (3, 2, 1, 0):
+        conv(f"erb_dec.conv{i}p", 0, None, 1, C_, C_)
+    conv("erb_dec.convt3", 0, 1, 2, C_, C_)
+    conv("erb_dec.convt2", 0, 1, 2, C_, C_, transposed=True)
+    conv("erb_dec.convt1", 0, 1, 2, C_, C_, transposed=True)
+    conv("erb_dec.conv0_out", 0, None, 1, C_, 1)
+    squeezed("df_dec.df_gru", e_out, config.df_hidden_dim, 0)
+    if "df_dec.df_skip.weight" in weights:
+        g = need("df_dec.df_skip.weight", (None, None, None))
+        if g[0] * g[1] != e_out or g[0] * g[2] != config.df_hidden_dim:
+            raise AudioGenerationError(3, f"DeepFilterNet checkpoint: df_dec.df_skip.weight has shape {g}")
+    conv("df_dec.df_convp", 1, 2, 3, C_, 2 * O)
+    g = need("df_dec.df_out.0.weight", (None, None, None))
+    if g[0] * g[1] != config.df_hidden_dim or g[0] * g[2] != D * O * 2:
+        raise AudioGenerationError(3, f"DeepFilterNet checkpoint: df_dec.df_out.0.weight has shape {g}, expected [groups, "
+                                      f"{config.df_hidden_dim} / groups, {D * O * 2} / groups]")
+    return want
+
+
+def deepfilternet_synthetic_weights(config: DeepFilterNetConfig, seed: int = 777, layers=None, erb_fb=True, df_skip=True) -> dict:
+    """Random float32 weights at the shapes the configuration implies, in the checkpoint's names and layouts.  layers = GRU layers of
+    (enc, erb_dec, df_dec); default DeepFilterNet3's (1, emb_num_layers - 1, df_num_layers)."""
+    import math
+    rng = np.random.default_rng(seed)
+    C_, E, D, O, F, H, Hd = (config.conv_ch, config.nb_erb, config.nb_df, config.df_order, config.freq_bins, config.emb_hidden_dim,
+                             config.df_hidden_dim)
+    G, Ge, emb = config.linear_groups, config.enc_linear_groups, config.conv_ch * (config.nb_erb // 4)
+    Le, Lr, Ld = layers if layers is not None else (1, max(1, config.emb_num_layers - 1), max(1, config.df_num_layers))
+    W = {}
+    u = lambda shape, amp: rng.uniform(-amp, amp, shape).astype(_F)
+
+    def bn(p, n):
+        W[p + ".weight"], W[p + ".bias"] = 1 + u((n,), 0.1), u((n,), 0.05)
+        W[p + ".running_mean"], W[p + ".running_var"] = u((n,), 0.05), 1 + u((n,), 0.1)
+
+    def conv(name, o, i, kt, kf, gain=1.0):
+        W[name] = u((o, i, kt, kf), gain * math.sqrt(3.0 / (i * kt * kf)))
+
+    def glin(name, g, din, dout):
+        W[name] = u((g, din // g, dout // g), math.sqrt(3.0 / (din // g)))
+
+    def sgru(p, din, h, n, dout):
+        glin(p + ".linear_in.0.weight", G, din, h)
+        for l in range(n):
+            W[f"{p}.gru.weight_ih_l{l}"], W[f"{p}.gru.weight_hh_l{l}"] = u((3 * h, h), math.sqrt(3.0 / h)), u((3 * h, h), math.sqrt(3.0 / h))
+            W[f"{p}.gru.bias_ih_l{l}"], W[f"{p}.gru.bias_hh_l{l}"] = u((3 * h,), 0.05), u((3 * h,), 0.05)
+        if dout:
+            glin(p + ".linear_out.0.weight", G, h, dout)
+
+    (ki0, ki1), (k0, k1), (t0, t1) = config.conv_kernel_inp, config.conv_kernel, config.convt_kernel
+    conv("enc.erb_conv0.1.weight", C_, 1, ki0, ki1), bn("enc.erb_conv0.2", C_)
+    for i in (1, 2, 3):
+        conv(f"enc.erb_conv{i}.0.weight", C_, 1, k0, k1), conv(f"enc.erb_conv{i}.1.weight", C_, C_, 1, 1, 1.4), bn(f"enc.erb_conv{i}.2", C_)
+    conv("enc.df_conv0.1.weight", C_, 1, ki0, ki1), conv("enc.df_conv0.2.weight", C_, C_, 1, 1, 1.4), bn("enc.df_conv0.3", C_)
+    conv("enc.df_conv1.0.weight", C_, 1, k0, k1), conv("enc.df_conv1.1.weight", C_, C_, 1, 1, 1.4), bn("enc.df_conv1.2", C_)
+    glin("enc.df_fc_emb.0.weight", Ge, C_ * (D // 2), emb)
+    sgru("enc.emb_gru", emb, H, Le, emb)
+    W["enc.lsnr_fc.0.weight"], W["enc.lsnr_fc.0.bias"] = u((1, emb), math.sqrt(3.0 / emb)), u((1,), 0.05)
+    sgru("erb_dec.emb_gru", emb, H, Lr, emb)
+    for i in (0, 1, 2, 3):
+        conv(f"erb_dec.conv{i}p.0.weight", C_, 1, 1, 1), bn(f"erb_dec.conv{i}p.1", C_)
+    conv("erb_dec.convt3.0.weight", C_, 1, k0, k1), conv("erb_dec.convt3.1.weight", C_, C_, 1, 1, 1.4), bn("erb_dec.convt3.2", C_)
+    for i in (1, 2):
+        conv(f"erb_dec.convt{i}.0.weight", C_, 1, t0, t1), conv(f"erb_dec.convt{i}.1.weight", C_, C_, 1, 1, 1.4), bn(f"erb_dec.convt{i}.2", C_)
+    conv("erb_dec.conv0_out.0.weight", 1, C_, k0, k1), bn("erb_dec.conv0_out.1", 1)
+    sgru("df_dec.df_gru", emb, Hd, Ld, 0)
+    if df_skip:
+        glin("df_dec.df_skip.weight", G, emb, Hd)
+    gc = math.gcd(C_, 2 * O)
+    conv("df_dec.df_convp.1.weight", 2 * O, C_ // gc, config.df_pathway_kernel_size_t, 1)
+    conv("df_dec.df_convp.2.weight", 2 * O, 2 * O, 1, 1, 1.4), bn("df_dec.df_convp.3", 2 * O)
+    glin("df_dec.df_out.0.weight", G, Hd, D * O * 2)
+    fb, inv, f = np.zeros((F, E), _F), np.zeros((E, F), _F), 0
+    for e, w in enumerate(config.erb_band_widths):
+        fb[f: f + w, e], inv[e, f: f + w], f = _F(1.0) / _F(w), 1.0, f + w
+    W["mask.erb_inv_fb"] = inv
+    if erb_fb:
+        W["erb_fb"] = fb
+    return W
+
+
+class DeepFilterNet(NativeHandle):
+    """DeepFilterNetModel.enhance (V2 / V3, offline) for ragged batches: one handle, 1..max_batch rows a call, each at most
+    max_seconds long.  The hop-by-hop streamer (enhanceStreaming) is not offered."""
+    _prefix = "mis_deepfilternet"
+
+    def __init__(self, config: DeepFilterNetConfig, device: int = 0):
+        self.config = config
+        self.device = device
+        self.model_version = config.model_version
+        self.layers = None
+        self._create(config.to_c(), device)
+
+    @property
+    def sample_rate(self) -> int:
+        return self.config.sample_rate
+
+    supports_streaming = False
+
+    @classmethod
+    def from_weights(cls, config: DeepFilterNetConfig, weights: dict, device: int = 0) -> "DeepFilterNet":
+        """weights: the checkpoint's names; every tensor the chain reads (deepfilternet_expected_shapes) is staged as f32, whatever the
+        checkpoint's dtype; other keys (num_batches_tracked, ...) are ignored."""
+        config.check_served()
+        want = deepfilternet_expected_shapes(config, weights)
+        m = cls(config, device)
+        for name in want:
+            arr = weights[name]
+            try:
+                import torch
+                if isinstance(arr, torch.Tensor):
+                    arr = arr.detach().to(torch.float32).cpu().numpy()
+            except ImportError:
+                pass
+            m.set_tensor(name, np.ascontiguousarray(arr, dtype=_F))
+        m.finalize()
+        m.layers = tuple(sum(1 for k in want if k.startswith(p + ".gru.weight_ih_l"))
+                         for p in ("enc.emb_gru", "erb_dec.emb_gru", "df_dec.df_gru"))
+        return m
+
+    @classmethod
+    def synthetic(cls, config: DeepFilterNetConfig, device: int = 0, seed: int = 777) -> "DeepFilterNet":
+        config.check_served()
+        m = cls(config, device)
+        check(_lib.lib().mis_deepfilternet_init_synthetic(m._h, seed))
+        m.finalize()
+        m.layers = (1, max(1, config.emb_num_layers - 1), max(1, config.df_num_layers))
+        return m
+
+    @classmethod
+    def from_local(cls, directory: str, subfolder: str | None = None, device: int = 0, **workspace) -> "DeepFilterNet":
+        """fromLocal (:280-312): the directory itself when it holds config.json, else its subfolder; model.safetensors first, else the
+        first *.safetensors in name order."""
+        model_dir = os.path.expanduser(directory)
+        if not os.path.exists(os.path.join(model_dir, "config.json")) and subfolder:
+            model_dir = os.path.join(model_dir, subfolder)
+        cfg_path = os.path.join(model_dir, "config.json")
+        if not os.path.exists(cfg_path):
+            raise DeepFilterNetError("missingConfig", f"Missing config.json in model directory: {model_dir}")
+        with open(cfg_path) as f:
+            config = DeepFilterNetConfig.from_dict(json.load(f), **workspace)
+        files = sorted(fn for fn in os.listdir(model_dir) if fn.lower().endswith(".safetensors"))
+        if not files:
+            raise DeepFilterNetError("missingWeights", f"Missing .safetensors weights in model directory: {model_dir}")
+        name = "model.safetensors" if "model.safetensors" in files else files[0]
+        config.check_served()
+        from safetensors import safe_open
+        with safe_open(os.path.join(model_dir, name), framework="pt") as sf:
+            weights = {k: sf.get_tensor(k) for k in sf.keys()}
+        m = cls.from_weights(config, weights, device)
+        m.model_directory = model_dir
+        return m
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: str | None = "v3", device: int = 0, **workspace) -> "DeepFilterNet":
+        """fromPretrained (:244-268) for local paths: a directory goes to from_local with the subfolder, a file means its directory.
+        Nothing is downloaded: any other path is modelPathNotFound."""
+        local = os.path.abspath(os.path.expanduser(path))
+        if os.path.isdir(local):
+            return cls.from_local(local, subfolder, device, **workspace)
+        if os.path.exists(local):
+            return cls.from_local(os.path.dirname(local), None, device, **workspace)
+        raise DeepFilterNetError("modelPathNotFound", f"Model path not found: {path} (this package downloads nothing)")
+
+    @property
+    def launches(self) -> int:
+        return int(_lib.lib().mis_deepfilternet_launches(self._h))
+
+    def expected_launches(self, erb_fb: bool, df_skip: bool, enc_linear_out: bool = True, erb_linear_out: bool = True) -> int:
+        """The launch count of a call as the chain gives it."""
+        le, lr, ld = self.layers
+        paired = max(lr, ld) if self.config.emb_hidden_dim == self.config.df_hidden_dim else lr + ld
+        return 26 + int(erb_fb) + int(df_skip) + int(enc_linear_out) + int(erb_linear_out) + 2 * le + lr + ld + paired
+
+    def _row(self, audio, sample_rate) -> np.ndarray:
+        a = np.asarray(audio)
+        if a.ndim != 1:
+            raise DeepFilterNetError("invalidAudioShape", f"Expected mono 1D audio array, got shape: {list(a.shape)}")
+        a = a.astype(_F, copy=False)
+        rate = self.config.sample_rate
+        if sample_rate is not None and int(sample_rate) != rate:
+            raise AudioGenerationError(3, f"DeepFilterNet: audio at {sample_rate} Hz, the model takes {rate} Hz; this package has no "
+                                          "resampler - resample before the call")
+        if len(a) > self.config.max_samples:
+            raise AudioGenerationError(3, f"DeepFilterNet: a row of {len(a)} samples, the workspace holds {self.config.max_samples} "
+                                          "(max_seconds)")
+        return a
+
+    def frames(self, lens):
+        """Sample counts -> (frames T, output samples), int32 / int64 arrays."""
+        lens = np.ascontiguousarray(lens, np.int64)
+        T, n = np.zeros(len(lens), np.int32), np.zeros(len(lens), np.int64)
+        check(_lib.lib().mis_deepfilternet_frames(self._h, lens.ctypes.data, len(lens), T.ctypes.data, n.ctypes.data))
+        return T, n
+
+    def enhance_raw(self, waveforms, sample_rate=None, junk: float | None = None):
+        """Ragged list of waveforms -> (waveforms, lsnr): one float32 array of the row's own length and one of its T frames per row."""
+        rows = [self._row(w, sample_rate) for w in waveforms]
+        if not rows:
+            raise AudioGenerationError(3, "DeepFilterNet: no rows")
+        pcm, lens = pack_rows(rows, junk)
+        B, stride = pcm.shape
+        T, _ = self.frames(lens)
+        out, got, lsnr = np.zeros((B, stride), _F), np.zeros(B, np.int64), np.zeros((B, int(T.max())), _F)
+        check(_lib.lib().mis_deepfilternet_enhance(self._h, pcm.ctypes.data, lens.ctypes.data, B, stride, out.ctypes.data, stride,
+                                                   got.ctypes.data, lsnr.ctypes.data, lsnr.shape[1]))
+        return [out[b, : int(got[b])].copy() for b in range(B)], [lsnr[b, : int(T[b])].copy() for b in range(B)]
+
+    def enhance_batch(self, waveforms, sample_rate=None, junk: float | None = None) -> list:
+        return self.enhance_raw(waveforms, sample_rate, junk)[0]
+
+    def enhance(self, waveform, sample_rate: int = 48000) -> np.ndarray:
+        """enhance (:323-418): one waveform -> the enhanced waveform of the same length."""
+        return self.enhance_batch([waveform], sample_rate)[0]
+
+    def enhance_streaming(self, *a, **kw):
+        raise DeepFilterNetError("streamingNotSupportedForModelVersion",
+                                 f"Streaming is not supported for model version {self.model_version}. Use offline enhancement instead.")
+
+    def tap(self, stage: int) -> np.ndarray:
+        """Tensors of the last call (include/mi_speech.h lists the stages), [B, rows, width]; the waveform stage as [B, samples]."""
+        dims = (C.c_int64 * 3)()
+        check(_lib.lib().mis_deepfilternet_tap(self._h, stage, None, 0, dims))
+        out = np.zeros(tuple(int(d) for d in dims), _F)
+        check(_lib.lib().mis_deepfilternet_tap(self._h, stage, out.ctypes.data, out.size, dims))
+        return out[:, :, 0] if stage == 25 else out
+
+    def timing(self):
+        """Device milliseconds of the last call: (front end, network without the recurrences, recurrences, synthesis)."""
+        ms = (C.c_float * 4)()
+        check(_lib.lib().mis_debug_deepfilternet_timing(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+
 # ------------------------------------------------------------------------------------------------------------ the factory
 _MOSSFORMER_TYPES = ("mossformer2_se", "mossformer2", "mossformer")
+_DEEPFILTERNET_TYPES = ("deepfilternet", "deepfilternet2", "deepfilternet3", "dfn")
 
 
 def _infer_model_type(path: str):
@@ -392,8 +858,11 @@ def resolve_sts_model_type(path: str, model_type=None):
 
 
 def load_sts_model(path: str, model_type=None, device: int = 0, **workspace):
-    """STS.loadModel for a local directory; this package downloads nothing.  Serves mossformer2_se / mossformer2 / mossformer."""
+    """STS.loadModel for a local directory; this package downloads nothing.  Serves mossformer2_se / mossformer2 / mossformer, and
+    deepfilternet / deepfilternet2 / deepfilternet3 / dfn when the path is an existing directory."""
     resolved = resolve_sts_model_type(path, model_type)
+    if resolved in _DEEPFILTERNET_TYPES and os.path.isdir(os.path.expanduser(path)):
+        return DeepFilterNet.from_local(os.path.expanduser(path), "v3", device, **workspace)
     if resolved not in _MOSSFORMER_TYPES:
         raise STSModelError(resolved if resolved is not None else model_type)
     p = os.path.expanduser(path)
