@@ -269,6 +269,47 @@ mis_status mis_debug_lasr_pack(int device, const float* feats, const int32_t* F,
 mis_status mis_debug_lasr_argmax(int device, const float* logits, int M, int V, int32_t* pred);
 mis_status mis_debug_lasr_collapse(int device, const int32_t* pred, const int32_t* cnt, int B, int Tp, int blank, int32_t* tokens, int32_t* ntok);
 
+/* csrc/sortformer.hip, tests (tests/test_gpu_sortformer_ops.py): ONE call of sf_gemm / sf_attn - the launchers the chain itself calls -, or
+ * one launch line of the Sortformer chain (k_sf_conv0, k_sf_stats, k_sf_ln, k_sf_intake, k_sf_glu_dwconv, k_sf_peak - private to
+ * csrc/sortformer.hip, so the entry points live at its end), on caller-supplied host data; nothing is computed in the entry points.  Every
+ * tensor is float32; outputs come back as the launch left them, so a word nobody wrote is still 0xFFFFFFFF.  Guards as above: every output
+ * lies between guard bands and is pre-filled with the byte 0xFF, a changed guard byte - or a changed padding column of a strided output -
+ * fails the call with MIS_ERR_GENERATION_FAILED; every input is followed by NaN (row counts: 0x7FFFFFFF) and uploaded UNCHANGED: the
+ * caller decides what sits in padding columns, behind a row's count and in unused table rows.  The entry points refuse
+ * (MIS_ERR_INVALID_INPUT, nothing launched) only what would make a KERNEL read or write outside these buffers.
+ *   sortformer_gemm: the fields of SfGemm plus batch.  load 0 plain, 1 LayerNorm, 2 ReLU, 3 depthwise 3 x 3 stride 2; act 0 none, 1 SiLU,
+ *     2 ReLU, 3 sigmoid.  rows = batch Tp rowmul.  X is the IMAGE the kernel addresses: (rows - 1) ldx + K elements (load 3:
+ *     [batch][Tin][Fin][K] channels last, ldx unused).  W [N][K]; bias [N] or NULL; cnt [batch] or NULL (every row live); stats [rows][2],
+ *     lnw, lnb [K] (load 1); pos [Tp][N] or NULL; cnt_in [batch], dww [9][K], dwb [K] (load 3).  R NULL: no residual.  in_place: R dense
+ *     [rows][N] is loaded into the output buffer, which is passed as the residual too (the Conformer calls); else R is the image
+ *     (rows - 1) ldr + N of a buffer of its own (the BART calls) and R_after (may be NULL) receives it as the launch left it.  Y_out
+ *     [rows][N]: the first N columns of every row of ldy.  report (may be NULL) int32[1]: load (-1: nothing launched).
+ *   sortformer_attn: the fields of SfAttn plus heads and batch; rel 0 / 1 picks k_sf_attn<ND, false / true>.  qkv [batch Tp][ld]: q of head
+ *     h at column h hd, k at koff + h hd, v at voff + h hd.  u, v [heads hd], P [2 Tcap - 1][ldp] (rel).  hd 1 .. 64.  out [batch Tp][heads hd]:
+ *     the first columns of every row of ldo.  report int32[2]: ND (1 iff hd <= 32), REL; -1: nothing launched.
+ *   sortformer_conv0: feats [batch][Fp][mels], F, T1 [batch], w [9][C], bias [C]; out [batch][T1p][F1][C].
+ *   sortformer_stats: x [M][d]; stats_out [M][2] = mean, 1 / sqrt(var + eps).
+ *   sortformer_ln: x, y_out [M][d], w, b [d], cnt [ceil(M / Tp)]; in_place: x is loaded into the output buffer and normalised there.
+ *   sortformer_intake: x, y_out [batch Tp][d], cnt [batch]: y = x g.
+ *   sortformer_glu_dwconv: pw [batch Tp][2 C], taps [k][C], shift [C], cnt [batch], 1 <= k <= 31; out [batch Tp][C].
+ *   sortformer_peak: pcm [batch][stride], N [batch] (each <= stride); scale_out [batch]. */
+mis_status mis_debug_sortformer_gemm(int device, int load, int act, const float* X, int ldx, const float* W, const float* bias, const int32_t* cnt, int batch,
+                                     int Tp, int rowmul, int K, int N, int ldy, const float* stats, const float* lnw, const float* lnb, const float* R,
+                                     int ldr, float ra, int in_place, const float* pos, const int32_t* cnt_in, int Tin, int Fin, int Fout, const float* dww,
+                                     const float* dwb, float* Y_out, float* R_after, int32_t* report);
+mis_status mis_debug_sortformer_attn(int device, int rel, const float* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads,
+                                     int hd, float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int Tcap, int ldo, float* out,
+                                     int32_t* report);
+mis_status mis_debug_sortformer_conv0(int device, const float* feats, const int32_t* F, const int32_t* T1, const float* w, const float* bias, int batch,
+                                      int Fp, int mels, int T1p, int F1, int C, float* out);
+mis_status mis_debug_sortformer_stats(int device, const float* x, int M, int d, float eps, float* stats_out);
+mis_status mis_debug_sortformer_ln(int device, const float* x, const float* w, const float* b, int M, int d, float eps, const int32_t* cnt, int Tp,
+                                   int in_place, float* y_out);
+mis_status mis_debug_sortformer_intake(int device, const float* x, const int32_t* cnt, int batch, int Tp, int d, float g, float* y_out);
+mis_status mis_debug_sortformer_glu_dwconv(int device, const float* pw, const float* taps, const float* shift, const int32_t* cnt, int batch, int Tp, int C,
+                                           int k, float* out);
+mis_status mis_debug_sortformer_peak(int device, const float* pcm, int64_t stride, const int32_t* N, int batch, int on, float* scale_out);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

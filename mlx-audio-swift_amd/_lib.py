@@ -609,6 +609,16 @@ DEBUG_SYMBOLS = {
     "mis_debug_bigvgan_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_aa_act": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "mis_debug_sortformer_timing": (C.c_int, [_P, _P]),
+    "mis_debug_sortformer_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                            _P, C.c_int, C.c_float, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_debug_sortformer_attn": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P,
+                                            _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_sortformer_conv0": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_sortformer_stats": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "mis_debug_sortformer_ln": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, C.c_int, C.c_int, _P]),
+    "mis_debug_sortformer_intake": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
+    "mis_debug_sortformer_glu_dwconv": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_sortformer_peak": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, _P]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 

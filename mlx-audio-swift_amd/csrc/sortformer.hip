@@ -519,7 +519,9 @@ extern "C" mis_status mis_sortformer_set_tensor(mis_sortformer* c, const char* n
     MIS_API_END
 }
 
-static void sf_gemm(mis_sortformer* c, SfGemm p, int B) {
+// c: whatever carries the stream and the launch counter (the handle; the debug entry points' bare context)
+template <class Ctx>
+static void sf_gemm(Ctx* c, SfGemm p, int B) {
     const dim3 grid(cdiv((int64_t)p.Tp * p.rowmul, 64), cdiv(p.N, 64), B);
     switch (p.load) {
         case SF_LOAD_LN: MIS_LAUNCH(c, k_sf_gemm<SF_LOAD_LN>, grid, dim3(256), p); break;
@@ -799,9 +801,9 @@ static void sf_stem(mis_sortformer* c) {
     c->has_emb = true;
 }
 
-template <bool REL>
-static void sf_attn(mis_sortformer* c, const SfAttn& p, int heads, int hd) {
-    const dim3 grid(cdiv(c->Tp, 64), heads, c->batch);
+template <bool REL, class Ctx>
+static void sf_attn(Ctx* c, const SfAttn& p, int heads, int hd, int batch) {
+    const dim3 grid(cdiv(p.Tp, 64), heads, batch);
     if (hd <= 32) MIS_LAUNCH(c, (k_sf_attn<1, REL>), grid, dim3(128), p);
     else MIS_LAUNCH(c, (k_sf_attn<2, REL>), grid, dim3(128), p);
 }
@@ -834,7 +836,7 @@ static void sf_encoder(mis_sortformer* c, int stop) {
         stats(c->h.p);
         ln_lin(c->h.p, l.lnaw, l.lnab, l.qkv, c->qkv.p, 3 * d, SF_ACT_NONE);
         SfAttn ap{c->qkv.p, 3 * d, d, 2 * d, c->att.p, d, cnt, Tp, c->hd, 1.0f, sqrtf((float)c->hd), l.u, l.v, l.P, d, c->Tcap};
-        sf_attn<true>(c, ap, c->H, c->hd);
+        sf_attn<true>(c, ap, c->H, c->hd, B);
         res_lin(c->att.p, d, l.o, c->h.p, d, 1.0f);
         stats(c->h.p);
         ln_lin(c->h.p, l.lncw, l.lncb, l.pw1, c->big.p, 2 * d, SF_ACT_NONE);
@@ -858,7 +860,7 @@ static void sf_encoder(mis_sortformer* c, int stop) {
         const SfTfLayer& l = c->tf[li];
         sf_gemm(c, sf_lin(c->g.p, dt, l.qkv, c->gq.p, 3 * dt, cnt, Tp), B);
         SfAttn ap{c->gq.p, 3 * dt, dt, 2 * dt, c->ga.p, dt, cnt, Tp, c->hdt, powf((float)c->hdt, -0.5f), 1.0f, nullptr, nullptr, nullptr, 0, 0};
-        sf_attn<false>(c, ap, c->Ht, c->hdt);
+        sf_attn<false>(c, ap, c->Ht, c->hdt, B);
         {
             SfGemm p = sf_lin(c->ga.p, dt, l.o, c->gx.p, dt, cnt, Tp);
             p.R = c->g.p; p.ldr = dt; p.ra = 1.0f;
@@ -1001,5 +1003,267 @@ extern "C" mis_status mis_debug_sortformer_timing(mis_sortformer* c, float* ms) 
     if (!ms) { c->timed = true; return MIS_OK; }
     MIS_REQUIRE(c->timed && c->timed_done, MIS_ERR_NOT_INITIALIZED, "no timed forward: the last call must be mis_sortformer_forward");
     for (int i = 0; i < 4; ++i) HIP_CHECK(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    MIS_API_END
+}
+
+// ============================================================================ test scaffolding (include/mi_speech_debug.h)
+// ONE call of sf_gemm / sf_attn, or one launch line of sf_front / sf_stem / sf_encoder, on caller-supplied host data, so that
+// tests/test_gpu_sortformer_ops.py can hold the kernels above to an operator-level reference.  Nothing is computed here: the operands are
+// uploaded as given and what the launch wrote is copied back.  Guards as the LASR entry points (debug_guard.h): every output is
+// [guard | body | guard], all of it the byte 0xFF before the launch (an output that also goes IN - the in-place residual, the in-place
+// LayerNorm - holds the caller's data instead); a changed guard byte or padding column fails the call; every input is followed by
+// IN_GUARD NaNs (ints: 0x7FFFFFFF).  The entry points refuse only what would make a KERNEL leave these buffers.  The launches run on a
+// bare context (the null stream and a launch counter): the launchers need nothing else of the handle.
+#include "debug_guard.h"
+#include "../../include/mi_speech_debug.h"
+
+namespace {
+
+constexpr int64_t SFD_MAX_ELEMS = (int64_t)1 << 28;          // per tensor
+
+struct SfdCtx { hipStream_t stream = nullptr; int launches = 0; };
+
+void sfd_sync(const SfdCtx& c) {
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    MIS_REQUIRE(c.launches == 1, MIS_ERR_GENERATION_FAILED, "%d launches where one was meant", c.launches);
+}
+void sfd_f32(DevBuf<uint32_t>& d, const float* src, size_t n) { alloc32(d, src, n, F32_NAN); }
+// counts [n] followed by 0x7FFFFFFF (a row count that masks nothing)
+void sfd_counts(DevBuf<uint32_t>& d, const int32_t* cnt, size_t n) { alloc32(d, cnt, n, 0x7FFFFFFFu); }
+const float* sfd_fp(const DevBuf<uint32_t>& d) { return reinterpret_cast<const float*>(d.p); }
+const int* sfd_ip(const DevBuf<uint32_t>& d) { return reinterpret_cast<const int*>(d.p); }
+float* sfd_out(GuardedOut& o) { return reinterpret_cast<float*>(o.p()); }
+// rows of ld words with `cols` live columns -> the live columns, as bits; the columns behind must still hold the fill
+void sfd_fetch_rows(GuardedOut& o, size_t rows, size_t ld, size_t cols, float* out) {
+    o.check_guards();
+    std::vector<uint32_t> h(o.body / 4);
+    HIP_CHECK(hipMemcpy(h.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        memcpy(out + r * cols, h.data() + r * ld, cols * 4);
+        for (size_t c = cols; c < ld; ++c)
+            MIS_REQUIRE(h[r * ld + c] == 0xFFFFFFFFu, MIS_ERR_GENERATION_FAILED, "the kernel wrote column %zu of row %zu behind its %zu columns", c, r, cols);
+    }
+}
+// dense rows [rows][cols] into the body of an output of row stride ld; the padding columns keep the fill
+void sfd_put_rows(GuardedOut& o, size_t rows, size_t ld, size_t cols, const float* src) {
+    HIP_CHECK(hipMemcpy2D(o.p(), ld * 4, src, cols * 4, cols * 4, rows, hipMemcpyHostToDevice));
+}
+
+}  // namespace
+
+extern "C" mis_status mis_debug_sortformer_gemm(int device, int load, int act, const float* X, int ldx, const float* W, const float* bias, const int32_t* cnt,
+                                                int batch, int Tp, int rowmul, int K, int N, int ldy, const float* stats, const float* lnw, const float* lnb,
+                                                const float* R, int ldr, float ra, int in_place, const float* pos, const int32_t* cnt_in, int Tin, int Fin,
+                                                int Fout, const float* dww, const float* dwb, float* Y_out, float* R_after, int32_t* report) {
+    MIS_API_BEGIN
+    if (report) report[0] = -1;
+    MIS_REQUIRE(X && W && Y_out && batch >= 1 && Tp >= 1 && rowmul >= 1 && K >= 1 && N >= 1 && ldy >= N, MIS_ERR_INVALID_INPUT,
+                "Sortformer GEMM: X, W, Y_out, positive batch, Tp, rowmul, K, N and ldy >= N are required");
+    MIS_REQUIRE(load >= SF_LOAD_ACT && load <= SF_LOAD_DW && act >= SF_ACT_NONE && act <= SF_ACT_SIGMOID, MIS_ERR_INVALID_INPUT, "Sortformer GEMM: load 0..3, act 0..3");
+    const int64_t rows = (int64_t)batch * Tp * rowmul;
+    MIS_REQUIRE(rows * ldy <= SFD_MAX_ELEMS && (int64_t)N * K <= SFD_MAX_ELEMS && batch <= 65535 && cdiv(N, 64) <= 65535, MIS_ERR_INVALID_INPUT,
+                "Sortformer GEMM: tensor too large");
+    MIS_REQUIRE(load != SF_LOAD_LN || (stats && lnw && lnb), MIS_ERR_INVALID_INPUT, "Sortformer GEMM: the LayerNorm load needs stats, lnw and lnb");
+    MIS_REQUIRE(!in_place || R, MIS_ERR_INVALID_INPUT, "Sortformer GEMM: in_place needs R");
+    MIS_REQUIRE(!R || in_place || ldr >= N, MIS_ERR_INVALID_INPUT, "Sortformer GEMM: ldr >= N");
+    size_t nx;
+    if (load == SF_LOAD_DW) {
+        MIS_REQUIRE(cnt_in && dww && dwb && Tin >= 1 && Fin >= 1 && Fout >= 1 && (int64_t)batch * Tin * Fin * K <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                    "Sortformer GEMM: the depthwise load needs cnt_in, dww, dwb and positive Tin, Fin, Fout");
+        nx = (size_t)batch * Tin * Fin * K;
+    } else {
+        MIS_REQUIRE(ldx >= K && (rows - 1) * ldx + K <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Sortformer GEMM: ldx >= K");
+        nx = (size_t)(rows - 1) * ldx + K;
+    }
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    DevBuf<uint32_t> dX, dW, dB, dcnt, dst, dlw, dlb, dR, dpos, dcin, ddw, ddb;
+    sfd_f32(dX, X, nx);
+    sfd_f32(dW, W, (size_t)N * K);
+    if (bias) sfd_f32(dB, bias, N);
+    if (cnt) sfd_counts(dcnt, cnt, batch);
+    if (load == SF_LOAD_LN) { sfd_f32(dst, stats, (size_t)rows * 2); sfd_f32(dlw, lnw, K); sfd_f32(dlb, lnb, K); }
+    if (load == SF_LOAD_DW) { sfd_counts(dcin, cnt_in, batch); sfd_f32(ddw, dww, (size_t)9 * K); sfd_f32(ddb, dwb, K); }
+    if (pos) sfd_f32(dpos, pos, (size_t)Tp * N);
+    const bool sep = R && !in_place;
+    const size_t nr = sep ? (size_t)(rows - 1) * ldr + N : 0;
+    if (sep) sfd_f32(dR, R, nr);
+    GuardedOut o;
+    o.alloc((size_t)rows * ldy * 4, (size_t)64 * ldy * 4);         // a guard is one 64-row tile of output
+    if (in_place) sfd_put_rows(o, rows, ldy, N, R);
+    SfGemm p{};
+    p.X = sfd_fp(dX); p.ldx = ldx; p.W = sfd_fp(dW); p.bias = bias ? sfd_fp(dB) : nullptr; p.Y = sfd_out(o); p.ldy = ldy;
+    p.cnt = cnt ? sfd_ip(dcnt) : nullptr; p.Tp = Tp; p.rowmul = rowmul; p.K = K; p.N = N; p.load = load; p.act = act;
+    if (load == SF_LOAD_LN) { p.stats = sfd_fp(dst); p.lnw = sfd_fp(dlw); p.lnb = sfd_fp(dlb); }
+    if (in_place) { p.R = sfd_out(o); p.ldr = ldy; p.ra = ra; }
+    else if (sep) { p.R = sfd_fp(dR); p.ldr = ldr; p.ra = ra; }
+    p.pos = pos ? sfd_fp(dpos) : nullptr;
+    if (load == SF_LOAD_DW) { p.cnt_in = sfd_ip(dcin); p.Tin = Tin; p.Fin = Fin; p.Fout = Fout; p.dww = sfd_fp(ddw); p.dwb = sfd_fp(ddb); }
+    sf_gemm(&c, p, batch);
+    sfd_sync(c);
+    if (report) report[0] = load;
+    sfd_fetch_rows(o, rows, ldy, N, Y_out);
+    if (sep && R_after) HIP_CHECK(hipMemcpy(R_after, dR.p, nr * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_attn(int device, int rel, const float* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp,
+                                                int heads, int hd, float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int Tcap,
+                                                int ldo, float* out, int32_t* report) {
+    MIS_API_BEGIN
+    if (report) { report[0] = -1; report[1] = -1; }
+    MIS_REQUIRE(qkv && cnt && out && batch >= 1 && Tp >= 1 && heads >= 1 && hd >= 1 && hd <= 64, MIS_ERR_INVALID_INPUT,
+                "Sortformer attention: qkv, cnt, out, positive batch, Tp, heads and a head size of 1..64 (the LDS tiles) are required");
+    const int64_t width = (int64_t)heads * hd;
+    MIS_REQUIRE(koff >= 0 && voff >= 0 && width <= ld && koff + width <= ld && voff + width <= ld && width <= ldo, MIS_ERR_INVALID_INPUT,
+                "Sortformer attention: q, k and v must lie inside a row of ld columns, the output inside ldo");
+    MIS_REQUIRE((int64_t)batch * Tp * ld <= SFD_MAX_ELEMS && (int64_t)batch * Tp * ldo <= SFD_MAX_ELEMS && batch <= 65535 && heads <= 65535, MIS_ERR_INVALID_INPUT,
+                "Sortformer attention: tensor too large");
+    MIS_REQUIRE(!rel || (u && v && P && Tcap >= 1 && ldp >= width && (int64_t)(2 * (int64_t)Tcap - 1) * ldp <= SFD_MAX_ELEMS), MIS_ERR_INVALID_INPUT,
+                "Sortformer attention: relative positions need u, v, P, Tcap >= 1 and ldp >= heads hd");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint32_t> dq, dcnt, du, dv, dP;
+    sfd_f32(dq, qkv, rows * ld);
+    sfd_counts(dcnt, cnt, batch);
+    if (rel) { sfd_f32(du, u, width); sfd_f32(dv, v, width); sfd_f32(dP, P, (size_t)(2 * Tcap - 1) * ldp); }
+    GuardedOut o;
+    o.alloc(rows * ldo * 4, (size_t)64 * ldo * 4);
+    SfAttn p{sfd_fp(dq), ld, koff, voff, sfd_out(o), ldo, sfd_ip(dcnt), Tp, hd, qscale, sdk, rel ? sfd_fp(du) : nullptr, rel ? sfd_fp(dv) : nullptr,
+             rel ? sfd_fp(dP) : nullptr, rel ? ldp : 0, rel ? Tcap : 0};
+    if (rel) sf_attn<true>(&c, p, heads, hd, batch);
+    else sf_attn<false>(&c, p, heads, hd, batch);
+    sfd_sync(c);
+    if (report) { report[0] = hd <= 32 ? 1 : 2; report[1] = rel ? 1 : 0; }
+    sfd_fetch_rows(o, rows, ldo, width, out);
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_conv0(int device, const float* feats, const int32_t* F, const int32_t* T1, const float* w, const float* bias, int batch,
+                                                 int Fp, int mels, int T1p, int F1, int C, float* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(feats && F && T1 && w && bias && out && batch >= 1 && Fp >= 1 && mels >= 1 && T1p >= 1 && F1 >= 1 && C >= 1, MIS_ERR_INVALID_INPUT,
+                "Sortformer conv0: every pointer and positive batch, Fp, mels, T1p, F1, C are required");
+    const int64_t n = (int64_t)batch * T1p * F1 * C;
+    MIS_REQUIRE(n <= SFD_MAX_ELEMS && (int64_t)batch * Fp * mels <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Sortformer conv0: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    DevBuf<uint32_t> df, dF, dT, dw, db;
+    sfd_f32(df, feats, (size_t)batch * Fp * mels);
+    sfd_counts(dF, F, batch);
+    sfd_counts(dT, T1, batch);
+    sfd_f32(dw, w, (size_t)9 * C);
+    sfd_f32(db, bias, C);
+    GuardedOut o;
+    o.alloc((size_t)n * 4, (size_t)F1 * C * 4);
+    MIS_LAUNCH(&c, k_sf_conv0, dim3((unsigned)((n + 255) / 256)), dim3(256), sfd_fp(df), sfd_ip(dF), sfd_ip(dT), sfd_fp(dw), sfd_fp(db), sfd_out(o), Fp, mels, T1p, F1,
+              C, (size_t)n);
+    sfd_sync(c);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_stats(int device, const float* x, int M, int d, float eps, float* stats_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && stats_out && M >= 1 && d >= 1 && (int64_t)M * d <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Sortformer stats: x, stats_out and positive M, d are required");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    DevBuf<uint32_t> dx;
+    sfd_f32(dx, x, (size_t)M * d);
+    GuardedOut o;
+    o.alloc((size_t)M * 2 * 4, 256);
+    MIS_LAUNCH(&c, k_sf_stats, dim3(cdiv(M, 4)), dim3(256), sfd_fp(dx), sfd_out(o), d, eps, M);
+    sfd_sync(c);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(stats_out, o.p(), o.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_ln(int device, const float* x, const float* w, const float* b, int M, int d, float eps, const int32_t* cnt, int Tp,
+                                              int in_place, float* y_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && w && b && cnt && y_out && M >= 1 && d >= 1 && Tp >= 1 && (int64_t)M * d <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Sortformer LayerNorm: x, w, b, cnt, y_out and positive M, d, Tp are required");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    DevBuf<uint32_t> dx, dw, db, dcnt;
+    if (!in_place) sfd_f32(dx, x, (size_t)M * d);
+    sfd_f32(dw, w, d);
+    sfd_f32(db, b, d);
+    sfd_counts(dcnt, cnt, (size_t)cdiv(M, Tp));
+    GuardedOut y;
+    y.alloc((size_t)M * d * 4, (size_t)4 * d * 4);
+    if (in_place) HIP_CHECK(hipMemcpy(y.p(), x, y.body, hipMemcpyHostToDevice));
+    MIS_LAUNCH(&c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), in_place ? sfd_out(y) : sfd_fp(dx), sfd_out(y), sfd_fp(dw), sfd_fp(db), d, eps, M, sfd_ip(dcnt), Tp);
+    sfd_sync(c);
+    y.check_guards();
+    HIP_CHECK(hipMemcpy(y_out, y.p(), y.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_intake(int device, const float* x, const int32_t* cnt, int batch, int Tp, int d, float g, float* y_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && cnt && y_out && batch >= 1 && Tp >= 1 && d >= 1 && (int64_t)batch * Tp * d <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Sortformer intake: x, cnt, y_out and positive batch, Tp, d are required");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    const size_t n = (size_t)batch * Tp * d;
+    DevBuf<uint32_t> dx, dcnt;
+    sfd_f32(dx, x, n);
+    sfd_counts(dcnt, cnt, batch);
+    GuardedOut o;
+    o.alloc(n * 4, (size_t)d * 4);
+    MIS_LAUNCH(&c, k_sf_intake, dim3((unsigned)((n + 255) / 256)), dim3(256), sfd_fp(dx), sfd_out(o), sfd_ip(dcnt), Tp, d, g, n);
+    sfd_sync(c);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(y_out, o.p(), o.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_glu_dwconv(int device, const float* pw, const float* taps, const float* shift, const int32_t* cnt, int batch, int Tp,
+                                                      int C, int k, float* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pw && taps && shift && cnt && out && batch >= 1 && Tp >= 1 && C >= 1, MIS_ERR_INVALID_INPUT,
+                "Sortformer GLU + depthwise conv: every pointer and positive batch, Tp, C are required");
+    MIS_REQUIRE(k >= 1 && k <= SF_DW_MAXK, MIS_ERR_INVALID_INPUT, "Sortformer GLU + depthwise conv: k %d outside 1..%d (the LDS tile)", k, SF_DW_MAXK);
+    MIS_REQUIRE((int64_t)batch * Tp * 2 * C <= SFD_MAX_ELEMS && batch <= 65535 && cdiv(C, 64) <= 65535, MIS_ERR_INVALID_INPUT,
+                "Sortformer GLU + depthwise conv: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint32_t> dp, dt, ds, dcnt;
+    sfd_f32(dp, pw, rows * 2 * C);
+    sfd_f32(dt, taps, (size_t)k * C);
+    sfd_f32(ds, shift, C);
+    sfd_counts(dcnt, cnt, batch);
+    GuardedOut o;
+    o.alloc(rows * C * 4, (size_t)SF_DW_TT * C * 4);
+    MIS_LAUNCH(&c, k_sf_glu_dwconv, dim3(cdiv(Tp, SF_DW_TT), cdiv(C, 64), batch), dim3(256), sfd_fp(dp), sfd_fp(dt), sfd_fp(ds), sfd_ip(dcnt), sfd_out(o), Tp, C, k);
+    sfd_sync(c);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+extern "C" mis_status mis_debug_sortformer_peak(int device, const float* pcm, int64_t stride, const int32_t* N, int batch, int on, float* scale_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pcm && N && scale_out && batch >= 1 && stride >= 1 && batch * stride <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Sortformer peak: pcm, N, scale_out and positive batch, stride are required");
+    for (int b = 0; b < batch; ++b)
+        MIS_REQUIRE(N[b] <= stride, MIS_ERR_INVALID_INPUT, "Sortformer peak: row %d: %d samples exceed the row stride %lld", b, N[b], (long long)stride);
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    DevBuf<uint32_t> dx, dn;
+    sfd_f32(dx, pcm, (size_t)batch * stride);
+    sfd_counts(dn, N, batch);
+    GuardedOut o;
+    o.alloc((size_t)batch * 4, 256);
+    MIS_LAUNCH(&c, k_sf_peak, dim3(batch), dim3(256), sfd_fp(dx), stride, sfd_ip(dn), on, sfd_out(o));
+    sfd_sync(c);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(scale_out, o.p(), o.body, hipMemcpyDeviceToHost));
     MIS_API_END
 }
