@@ -1158,7 +1158,7 @@ mis_status mis_mossformer2_tap(mis_mossformer2*, int stage, float* out, int64_t 
  * spec; / wnorm, inverse transform, window, overlap-add / max(sum w^2, 1e-8), the first fft_size - hop_size samples dropped, n_b
  * samples kept, clip to [-1, 1].  All of it exact f32.  One workspace is sized at finalize for max_batch rows of max_samples: a call
  * allocates nothing and synchronises once; a row's result does not depend on the batch it travels in or on what lies behind lens[b],
- * bit for bit.  Not served: DeepFilterNet (V1), enc_concat, streaming.
+ * bit for bit.  Not served: DeepFilterNet (V1), enc_concat.  Hop-by-hop streaming: mis_deepfilternet_stream_* below.
  * Rejected with MIS_ERR_INVALID_INPUT at create: sizes outside the ranges the messages name, a hidden size other than 32 / 64 / 128 /
  * 256 (the recurrence kernel's instantiations), erb_widths that do not sum to freq_bins; at finalize a tensor missing or misshapen, a
  * kernel size outside the served ones; at a call batch outside 1..max_batch, a row longer than stride or max_samples, too little room
@@ -1205,6 +1205,46 @@ mis_status mis_deepfilternet_enhance(mis_deepfilternet*, const float* pcm, const
  * [re F | im F], 25 waveform [B, samples, 1], 26 ERB energies in dB (with erb_fb only); 32 + 16 chain + 0 linear_in, + 1 + l GRU layer
  * l, chain 0 enc.emb_gru, 1 erb_dec.emb_gru, 2 df_dec.df_gru.  dims[3] receives B, rows, width; out NULL for the dims alone. */
 mis_status mis_deepfilternet_tap(mis_deepfilternet*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* DeepFilterNet hop by hop (csrc/deepfilternet_stream.hip; DeepFilterNetStreamer.processChunk / flush / reset of the reference):
+ * 1..max_batch streams on one finalized model, with a workspace of their own (mis_deepfilternet_enhance and feeds may interleave; the
+ * model outlives its streams).  Semantics, the engine's own:
+ *   Framing.  A stream is a sequence of whole hops.  After h hops the frames 0..h-1 exist; frame k is hops k-1, k, with zeros for hop
+ *   -1: offline frame k of the same samples.  With L = conv_lookahead, target frame t is computed once frame t + L exists.
+ *   Emission.  Target t emits its hop_size finished overlap-add samples (padded samples [t hop, (t + 1) hop): the first target's are the
+ *   fft_size - hop_size samples the offline call drops) through the offline expression: partial sums in frame order, / max(sum w^2,
+ *   1e-8), clip to [-1, 1].  The reference's processChunk neither divides nor clips; for the Vorbis window at fft = 2 hop the divisor is
+ *   sin^2 + cos^2 = 1 up to rounding, and its enhanceStreaming clips the concatenation.
+ *   State, on the device per stream: the last fft - hop input samples; both normalisation states (nb_erb + nb_df floats, from the
+ *   linspace expressions above at hop 0); kT - 1 input frames of every conv with a time kernel above 1; h of every GRU layer; the
+ *   unmasked spec frames t - (df_order - df_lookahead - 1) .. t + L (the deep filter's reach and the frames waiting for their
+ *   look-ahead); the last synthesis frame (the overlap-add tail).  The hop counter is kept by the host.
+ *   Yardstick.  After H hops in any chunking a stream has returned (H - L) hop samples (0 when negative) and H - L lsnr values.  With
+ *   x the samples fed, returned sample hop + s equals mis_deepfilternet_enhance(x)[s], and lsnr value t the offline lsnr of frame t,
+ *   bit for bit: every output element is the same fixed-order sum, zero history equals zero padding, and a sum continued from a
+ *   carried partial has the order of the offline sum.  A stream's result does not depend on its slot, on what the other streams bring
+ *   or on what lies behind its hops in pcm; a stream that brings 0 hops is untouched.
+ * A feed allocates nothing and synchronises once.  Feeds whose longest stream has at most 4 targets run the recurrence in its
+ * short-chunk form (every column of Wh streamed from the transposed copy, no register slice to fill), longer ones in the offline form:
+ * the same accumulation order, the same bits.
+ * Rejected with MIS_ERR_INVALID_INPUT at create: a model that is not finalized, streams outside 1..max_batch, max_hops outside 1..256,
+ * fft_size != 2 hop_size (the offline frame grid and the streamer's analysis memory coincide at this ratio only), df_lookahead >
+ * conv_lookahead (the deep filter would read frames that have not arrived); at a feed a null pointer, hops outside 0..max_hops, too
+ * little room in pcm, out or lsnr. */
+typedef struct mis_deepfilternet_stream mis_deepfilternet_stream;
+mis_status mis_deepfilternet_stream_create(mis_deepfilternet*, int streams, int max_hops, mis_deepfilternet_stream** out);
+void       mis_deepfilternet_stream_destroy(mis_deepfilternet_stream*);
+/* stream 0..streams-1, or -1 for all: zero history, hop counter 0 */
+mis_status mis_deepfilternet_stream_reset(mis_deepfilternet_stream*, int stream);
+/* pcm f32 [streams, stride], stream b brings hops[b] whole hops (0..max_hops) -> out f32 [streams, out_stride], out_lens[streams] (hop_size
+ * samples for every target that became ready), lsnr f32 [streams, lsnr_rows] and lsnr_counts[streams] (both NULL, or both given) */
+mis_status mis_deepfilternet_stream_feed(mis_deepfilternet_stream*, const float* pcm, const int32_t* hops, int64_t stride, float* out,
+                                         int64_t out_stride, int64_t* out_lens, float* lsnr_out, int lsnr_rows, int32_t* lsnr_counts);
+/* kernel launches of the last feed: the offline count + 1 (the history roll); launches without a row are skipped (no targets yet: the
+ * front end and the roll only); 0 when no stream brought a hop */
+int        mis_deepfilternet_stream_launches(const mis_deepfilternet_stream*);
+/* hops a stream has been fed since create or its last reset (-1: bad argument) */
+int64_t    mis_deepfilternet_stream_hops_seen(const mis_deepfilternet_stream*, int stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sortformer speaker diarization (csrc/sortformer.hip; Sources/MLXAudioVAD/Models/Sortformer/Sortformer.swift, SortformerConfig.swift,

@@ -410,6 +410,11 @@ mis_status mis_debug_mossformer2_timing(const mis_mossformer2* c, float* ms);
 /* csrc/deepfilternet.hip, measurements: device milliseconds of the last call, ms[4] = front end (copy in + STFT + features), network
  * without the recurrences, the recurrence launches, synthesis (+ copy out) */
 mis_status mis_debug_deepfilternet_timing(const mis_deepfilternet* c, float* ms);
+/* csrc/deepfilternet_stream.hip, measurements: device milliseconds of the last feed, ms[2] = the whole feed (copies included), its
+ * recurrence launches */
+mis_status mis_debug_deepfilternet_stream_timing(const mis_deepfilternet_stream* s, float* ms);
+/* feeds of at most `frames` targets run the short-chunk recurrence (0: never; negative: the default, 4) */
+mis_status mis_debug_deepfilternet_stream_gru_step_frames(mis_deepfilternet_stream* s, int frames);
 
 /* csrc/sortformer.hip, measurements: ms NULL switches the timestamps of mis_sortformer_forward on; else device milliseconds of the
  * last call, which must have been mis_sortformer_forward (MIS_ERR_NOT_INITIALIZED otherwise): ms[4] = front end, stem, Conformer blocks,

@@ -25,6 +25,7 @@ the Swift shim a maintainer would add):
     sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
     sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     sts.DeepFilterNet        <-> class DeepFilterNetModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/DeepFilterNet)
+    sts.DeepFilterNetStreamer <-> class DeepFilterNetStreamer (hop-by-hop enhancement)  (DeepFilterNet/DeepFilterNetStreamer.swift)
     dsp.*                  <-> computeMelSpectrogram (MLXAudioCore/DSP.swift) / WhisperAudio.encoderFeatures
     generation.*           <-> AudioGeneration / AudioGenerationInfo / AudioGenerationError /
                                GenerateParameters                (MLXAudioCore/Generation/GenerationTypes.swift)
@@ -65,7 +66,9 @@ from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitiz
 from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSModelError, mossformer2_sanitize,  # noqa: F401
                   mossformer2_normalized_key, mossformer2_expected_shapes, mossformer2_check_weights, resolve_sts_model_type,
                   load_sts_model, DeepFilterNet, DeepFilterNetConfig, DeepFilterNetError, deepfilternet_expected_shapes,
-                  deepfilternet_synthetic_weights, compute_norm_alpha, libdf_erb_band_widths)
+                  deepfilternet_synthetic_weights, compute_norm_alpha, libdf_erb_band_widths, DeepFilterNetStreamingConfig,
+                  DeepFilterNetStreamer, deepfilternet_enhance_streaming, deepfilternet_stream_chunks,
+                  deepfilternet_stream_check_served)
 from .sortformer import (SortformerModel, SortformerConfig, FCEncoderConfig, TFEncoderConfig, ModulesConfig, ProcessorConfig,  # noqa: F401
                          DiarizationSegment, DiarizationOutput, StreamingState, sortformer_sanitize, sortformer_expected_keys,
                          preds_to_segments, trim_silence, maybe_compress_state)

@@ -416,6 +416,12 @@ SYMBOLS = {
     "mis_deepfilternet_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "mis_deepfilternet_enhance": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int64, _P, _P, C.c_int]),
     "mis_deepfilternet_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_deepfilternet_stream_create": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
+    "mis_deepfilternet_stream_destroy": (None, [_P]),
+    "mis_deepfilternet_stream_reset": (C.c_int, [_P, C.c_int]),
+    "mis_deepfilternet_stream_feed": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, _P]),
+    "mis_deepfilternet_stream_launches": (C.c_int, [_P]),
+    "mis_deepfilternet_stream_hops_seen": (C.c_int64, [_P, C.c_int]),
     "mis_lasr_create": (C.c_int, [C.POINTER(LasrConfigC), C.c_int, C.POINTER(_P)]),
     "mis_lasr_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_lasr_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -606,6 +612,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_silero_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
     "mis_debug_deepfilternet_timing": (C.c_int, [_P, _P]),
+    "mis_debug_deepfilternet_stream_timing": (C.c_int, [_P, _P]),
+    "mis_debug_deepfilternet_stream_gru_step_frames": (C.c_int, [_P, C.c_int]),
     "mis_debug_bigvgan_timing": (C.c_int, [_P, _P]),
     "mis_debug_bigvgan_aa_act": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "mis_debug_sortformer_timing": (C.c_int, [_P, _P]),

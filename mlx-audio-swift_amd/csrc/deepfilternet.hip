@@ -25,300 +25,10 @@
 //
 // Launches of a call: 26 + [erb_fb] + [df_skip] + [enc linear_out] + [erb_dec linear_out] + 2 L_enc + L_erb + L_df
 // + (H_emb == H_df ? max(L_erb, L_df) : L_erb + L_df).
-#include "common.h"
-#include "f32_tile.h"
-#include "host_weights.h"
-#include "step_loop.h"
-
-#include <math.h>
-#include <string.h>
-#include <memory>
-
-#define DF_MAX_BATCH 64
-#define DF_MAX_ERB 128
-#define DF_MAX_REC 16             // recurrence launches a call that get their own pair of events
-
-enum { DF_LOAD_LIN = 0, DF_LOAD_FRAME, DF_LOAD_MAGSQ, DF_LOAD_IM2COL, DF_LOAD_GCONV, DF_LOAD_GCONVT };
-enum { DF_ACT_NONE = 0, DF_ACT_RELU, DF_ACT_SIGMOID, DF_ACT_TANH, DF_ACT_LOG10, DF_ACT_LSNR };
-enum { DF_PH_FRONT = 0, DF_PH_NET, DF_PH_REC, DF_PH_SYNTH };
-
-__device__ __forceinline__ float df_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// ---------------------------------------------------------------------------- the contraction
-struct DfGemm {
-    const int32_t* cnt; int nr, Fo, load;                   // a row's frames; positions a frame (m = t Fo + fo); the operand load
-    const float* W; int K, N, gws, ghs;                     // [N][gws]: row co holds the gws inputs of its group co / ghs (dense: gws = K)
-    const float* X; int ldx;                                // LIN / MAGSQ: [frame][ldx]; convs: [frame][Fin][Cin]
-    int Fin, Cin, kT, kF, fs, tshift;                       // conv geometry; tshift: the look-ahead (applied when T > tshift)
-    const float* Wm; int ipg, opg;                          // GCONV [K][ipg][kT][kF], GCONVT [Cin][opg][1][kF] (torch layouts)
-    const float* pcm; int64_t pcm_stride; const int32_t* lens; int hop; const float* win;   // FRAME
-    const float *scale, *bias; int act; float mul, s0, s1;  // epilogue: acc mul scale[co] + bias[co], activation (LSNR: sigmoid s0 + s1)
-    const float* cscale; const float* R; int ldr;           // column scale, residual (after the activation)
-    float* Y; int ldy;
-};
-
-__device__ __forceinline__ float df_conv_in(const DfGemm& p, size_t row0, int T, int t, int f, int ci) {
-    if (t < 0 || f < 0 || f >= p.Fin) return 0.0f;                        // the conv's own zero padding
-    if (T > p.tshift) t += p.tshift;                                      // applyLookahead: zero-filled from the row's own last frame
-    if (t >= T) return 0.0f;
-    return p.X[((row0 + t) * p.Fin + f) * p.Cin + ci];
-}
-
-__device__ __forceinline__ float df_load(const DfGemm& p, int b, size_t row0, int T, int m, int k) {
-    const int t = m / p.Fo, fo = m - t * p.Fo;
-    switch (p.load) {
-        case DF_LOAD_FRAME: {                                             // hop zeros in front of the row, zeros behind it
-            const int64_t s = (int64_t)t * p.hop + k - p.hop;
-            return (s >= 0 && s < p.lens[b]) ? __fmul_rn(p.pcm[(size_t)b * p.pcm_stride + s], p.win[k]) : 0.0f;
-        }
-        case DF_LOAD_MAGSQ: {
-            const float re = p.X[(row0 + t) * p.ldx + k], im = p.X[(row0 + t) * p.ldx + p.K + k];
-            return __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im));
-        }
-        case DF_LOAD_IM2COL: {                                            // k = (dt kF + df) Cin + ci
-            const int tap = k / p.Cin, ci = k - tap * p.Cin, dt = tap / p.kF, df = tap - dt * p.kF;
-            return df_conv_in(p, row0, T, t - (p.kT - 1) + dt, fo * p.fs - p.kF / 2 + df, ci);
-        }
-        case DF_LOAD_GCONV: {                                             // mid channel k of the grouped conv, taps (ci, dt, df) ascending
-            const int g = k / p.opg;
-            const float* w = p.Wm + (size_t)k * p.ipg * p.kT * p.kF;
-            float a = 0.0f;
-            for (int ci = 0; ci < p.ipg; ++ci)
-                for (int dt = 0; dt < p.kT; ++dt)
-                    for (int df = 0; df < p.kF; ++df)
-                        a = fmaf(df_conv_in(p, row0, T, t - (p.kT - 1) + dt, fo * p.fs - p.kF / 2 + df, g * p.ipg + ci),
-                                 w[(ci * p.kT + dt) * p.kF + df], a);
-            return a;
-        }
-        case DF_LOAD_GCONVT: {                                            // y[fo] = sum over fi fs - kF / 2 + j == fo of x[fi] w[j], j ascending
-            const int g = k / p.opg;
-            const float* w = p.Wm + (size_t)k * p.kF;
-            float a = 0.0f;
-            for (int j = 0; j < p.kF; ++j) {
-                const int q = fo + p.kF / 2 - j;
-                if (q >= 0 && q % p.fs == 0) a = fmaf(df_conv_in(p, row0, T, t, q / p.fs, g), w[j], a);
-            }
-            return a;
-        }
-        default: return p.X[(row0 + t) * p.ldx + k];
-    }
-}
-
-__global__ void __launch_bounds__(256) k_dfn_gemm(DfGemm p) {
-    constexpr int TT = F32_TILE, TC = F32_TILE;
-    __shared__ float As[TT][F32_KC + 1];
-    __shared__ float Bs[TC][F32_KC + 1];
-    const int b = blockIdx.z, m0 = blockIdx.x * TT, c0 = blockIdx.y * TC, nr = p.nr;
-    const int T = min(p.cnt[b], nr), M = T * p.Fo, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const size_t row0 = (size_t)b * nr;
-    if (m0 >= M) { f32_tile_zero<TT, TC>(p.Y, p.ldy, row0 * p.Fo, m0, c0, nr * p.Fo, p.N); return; }
-    f32x16_t acc[1] = {};
-    const int wt = (wave & 1) * 32, wc = (wave >> 1) * 32, kh = lane >> 5, l31 = lane & 31;
-    // a grouped linear reads the K range of the groups its 64 columns belong to
-    const int klo = (c0 / p.ghs) * p.gws, khi = min(p.K, (min(p.N - 1, c0 + TC - 1) / p.ghs + 1) * p.gws);
-    for (int k0 = klo; k0 < khi; k0 += F32_KC) {
-#pragma unroll
-        for (int n = 0; n < TT * F32_KC / 256; ++n) {
-            const int i = tid + n * 256, r = i >> 5, k = k0 + (i & 31), m = m0 + r;
-            As[r][i & 31] = (k < khi && m < M) ? df_load(p, b, row0, T, m, k) : 0.0f;
-        }
-#pragma unroll
-        for (int n = 0; n < TC * F32_KC / 256; ++n) {
-            const int i = tid + n * 256, r = i >> 5, k = k0 + (i & 31), co = c0 + r;
-            float v = 0.0f;
-            if (co < p.N && k < khi) {
-                const int kg = k - (co / p.ghs) * p.gws;
-                if (kg >= 0 && kg < p.gws) v = p.W[(size_t)co * p.gws + kg];
-            }
-            Bs[r][i & 31] = v;
-        }
-        __syncthreads();
-        f32_tile_mfma(As, Bs, wt + l31, wc + l31, kh, acc);
-        __syncthreads();
-    }
-    const int co = c0 + wc + l31;                                   // C/D: column = lane & 31, row = f32_tile_row(r, lane >> 5)
-    if (co >= p.N) return;
-    const float sc = p.scale ? p.scale[co] : 1.0f, add = p.bias ? p.bias[co] : 0.0f, cs = p.cscale ? p.cscale[co] : 1.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wt + f32_tile_row(r, kh);
-        if (m >= nr * p.Fo) continue;
-        const size_t at = row0 * p.Fo + m;
-        float v = 0.0f;
-        if (m < M) {
-            v = __fadd_rn(__fmul_rn(__fmul_rn(acc[0][r], p.mul), sc), add);
-            if (p.act == DF_ACT_RELU) v = fmaxf(v, 0.0f);
-            else if (p.act == DF_ACT_SIGMOID) v = df_sigmoid(v);
-            else if (p.act == DF_ACT_TANH) v = tanhf(v);
-            else if (p.act == DF_ACT_LOG10) v = __fmul_rn(10.0f, log10f(__fadd_rn(v, 1e-10f)));
-            else if (p.act == DF_ACT_LSNR) v = __fadd_rn(__fmul_rn(df_sigmoid(v), p.s0), p.s1);
-            if (p.cscale) v = __fmul_rn(v, cs);
-            if (p.R) v = __fadd_rn(v, p.R[at * p.ldr + co]);
-        }
-        p.Y[at * p.ldy + co] = v;
-    }
-}
-
-// ---------------------------------------------------------------------------- features
-struct DfNorm {
-    const float* spec; int F;                               // [frame][2 F], re | im
-    const float* erb;                                       // [frame][E] in dB (erb_fb), or null: band means over widths
-    const int32_t* wlo;                                     // [E + 1] first bin of every band
-    float *feat_erb, *feat_spec;                            // [frame][E], [frame][D][2]
-    const int32_t* cnt; int nr, E, D; float a;
-};
-
-__device__ __forceinline__ float df_magsq(const float* s, int F, int f) { return __fadd_rn(__fmul_rn(s[f], s[f]), __fmul_rn(s[F + f], s[F + f])); }
-
-__global__ void __launch_bounds__(256) k_dfn_norm(DfNorm p) {
-    const int b = blockIdx.x, T = min(p.cnt[b], p.nr);
-    const size_t row0 = (size_t)b * p.nr;
-    const float a = p.a, oma = __fsub_rn(1.0f, p.a);
-    for (int item = threadIdx.x; item < p.E + p.D; item += 256) {
-        const bool erb = item < p.E;
-        const int i = erb ? item : item - p.E, n = erb ? p.E : p.D;
-        // linspace(start, end, n): start + i (end - start) / (n - 1)
-        const float lo = erb ? -60.0f : 0.001f, hi = erb ? -90.0f : 0.0001f;
-        float s = n > 1 ? __fadd_rn(lo, __fmul_rn((float)i, __fdiv_rn(__fsub_rn(hi, lo), (float)(n - 1)))) : lo;
-        for (int t0 = 0; t0 < T; t0 += 8) {
-            float x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {                                 // the loads of eight frames, then their serial chain
-                const int t = t0 + j;
-                x[j] = 0.0f;
-                if (t >= T) continue;
-                const float* sp = p.spec + (row0 + t) * 2 * p.F;
-                if (!erb) x[j] = __fsqrt_rn(df_magsq(sp, p.F, i));
-                else if (p.erb) x[j] = p.erb[(row0 + t) * p.E + i];
-                else {
-                    float acc = 0.0f;
-                    for (int f = p.wlo[i]; f < p.wlo[i + 1]; ++f) acc = __fadd_rn(acc, df_magsq(sp, p.F, f));
-                    const int w = p.wlo[i + 1] - p.wlo[i];
-                    x[j] = __fmul_rn(10.0f, log10f(__fadd_rn(w > 0 ? __fdiv_rn(acc, (float)w) : 0.0f, 1e-10f)));
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int t = t0 + j;
-                if (t >= T) continue;
-                s = __fadd_rn(__fmul_rn(x[j], oma), __fmul_rn(s, a));
-                if (erb) p.feat_erb[(row0 + t) * p.E + i] = __fdiv_rn(__fsub_rn(x[j], s), 40.0f);
-                else {
-                    const float* sp = p.spec + (row0 + t) * 2 * p.F;
-                    const float den = __fsqrt_rn(fmaxf(s, 1e-12f));
-                    p.feat_spec[((row0 + t) * p.D + i) * 2] = __fdiv_rn(sp[i], den);
-                    p.feat_spec[((row0 + t) * p.D + i) * 2 + 1] = __fdiv_rn(sp[p.F + i], den);
-                }
-            }
-        }
-        for (int t = T; t < p.nr; ++t) {
-            if (erb) p.feat_erb[(row0 + t) * p.E + i] = 0.0f;
-            else { p.feat_spec[((row0 + t) * p.D + i) * 2] = 0.0f; p.feat_spec[((row0 + t) * p.D + i) * 2 + 1] = 0.0f; }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------- the recurrence
-struct DfGruChain {
-    const float* gx;                                        // [frame][3 H]: Wx x + b_ih, gates r | z | n
-    const float* Wh;                                        // [3 H][H]: thread t's register slice is the head of row t
-    const float* WhT;                                       // [H][3 H]: the streamed remainder, column k at WhT + k 3 H
-    const float* bhh;                                       // [3 H]
-    float* out;                                             // [frame][H]
-};
-struct DfGru { DfGruChain ch[2]; const int32_t* cnt; int nr; };
-
-template <int H, int KR>
-__global__ void __launch_bounds__(3 * H) k_dfn_gru(DfGru p) {
-    static_assert(KR % 4 == 0 && KR <= H && H % 4 == 0, "KR and H are multiples of 4");
-    __shared__ __attribute__((aligned(16))) float hs[H];
-    __shared__ float gs[3 * H];
-    const int b = blockIdx.x, t = threadIdx.x, T = min(p.cnt[b], p.nr);
-    const DfGruChain c = p.ch[blockIdx.y];
-    const size_t row0 = (size_t)b * p.nr;
-    float w[KR];
-    {
-        const float4* src = reinterpret_cast<const float4*>(c.Wh + (size_t)t * H);
-#pragma unroll
-        for (int q = 0; q < KR / 4; ++q) { const float4 v = src[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-    }
-    const float* wt = c.WhT + t;
-    const float bh = c.bhh[t];
-    float h = 0.0f;
-    if (t < H) hs[t] = 0.0f;
-    __syncthreads();
-    const float4* h4 = reinterpret_cast<const float4*>(hs);
-    for (int s = 0; s < T; ++s) {                                         // T is the row's own count: every barrier is block-uniform
-        float xr = 0.0f, xz = 0.0f, xn = 0.0f;
-        if (t < H) { const float* g = c.gx + (row0 + s) * 3 * H + t; xr = g[0]; xz = g[H]; xn = g[2 * H]; }
-        float a = 0.0f;                                                   // columns ascending: registers first, then the streamed part
-#pragma unroll
-        for (int q = 0; q < KR / 4; ++q) {
-            const float4 v = h4[q];
-            a = fmaf(w[4 * q], v.x, a); a = fmaf(w[4 * q + 1], v.y, a); a = fmaf(w[4 * q + 2], v.z, a); a = fmaf(w[4 * q + 3], v.w, a);
-        }
-        if constexpr (KR < H) {
-            constexpr int SC = KR > 96 ? 4 : 8;                            // loads in flight: what the registers beside w[] leave room for
-#pragma unroll 1
-            for (int k = KR; k < H; k += SC) {
-                float u[SC];
-#pragma unroll
-                for (int j = 0; j < SC; ++j) u[j] = wt[(size_t)(k + j) * 3 * H];
-#pragma unroll
-                for (int j = 0; j < SC; j += 4) {
-                    const float4 v = h4[(k + j) / 4];
-                    a = fmaf(u[j], v.x, a); a = fmaf(u[j + 1], v.y, a); a = fmaf(u[j + 2], v.z, a); a = fmaf(u[j + 3], v.w, a);
-                }
-            }
-        }
-        gs[t] = __fadd_rn(a, bh);
-        __syncthreads();
-        if (t < H) {
-            const float r = df_sigmoid(__fadd_rn(xr, gs[t])), z = df_sigmoid(__fadd_rn(xz, gs[H + t]));
-            const float n = tanhf(__fadd_rn(xn, __fmul_rn(r, gs[2 * H + t])));
-            h = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, z), n), __fmul_rn(z, h));
-            hs[t] = h;
-            c.out[(row0 + s) * H + t] = h;
-        }
-        __syncthreads();
-    }
-    for (int i = T * H + t; i < p.nr * H; i += 3 * H) c.out[row0 * H + i] = 0.0f;
-}
-
-// ---------------------------------------------------------------------------- synthesis
-struct DfEnh {
-    const float *spec, *mask, *coef, *inv;                  // [frame][2 F], [frame][E], [frame][D][order][2], erb_inv_fb [E][F]
-    float* enh;                                             // [frame][2 F]
-    const int32_t* cnt; int nr, F, E, D, order, pad_left; float wnorm; size_t total;
-};
-
-__global__ void __launch_bounds__(256) k_dfn_enh(DfEnh p) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.total) return;
-    const int f = (int)(i % p.F);
-    const size_t row = i / p.F;
-    const int t = (int)(row % p.nr), b = (int)(row / p.nr), T = min(p.cnt[b], p.nr);
-    float re = 0.0f, im = 0.0f;
-    if (t < T) {
-        if (f >= p.D) {
-            float g = 0.0f;
-            for (int e = 0; e < p.E; ++e) g = fmaf(p.mask[row * p.E + e], p.inv[(size_t)e * p.F + f], g);
-            re = __fmul_rn(p.spec[row * 2 * p.F + f], g); im = __fmul_rn(p.spec[row * 2 * p.F + p.F + f], g);
-        } else {
-            const float* cf = p.coef + (row * p.D + f) * p.order * 2;
-            for (int k = 0; k < p.order; ++k) {
-                const int tt = t + k - p.pad_left;
-                if (tt < 0 || tt >= T) continue;                          // (adds of + 0 in the reference)
-                const float* sp = p.spec + (row - t + tt) * 2 * p.F;
-                const float sr = sp[f], si = sp[p.F + f], cr = cf[2 * k], ci = cf[2 * k + 1];
-                re = __fadd_rn(re, __fsub_rn(__fmul_rn(sr, cr), __fmul_rn(si, ci)));
-                im = __fadd_rn(im, __fadd_rn(__fmul_rn(sr, ci), __fmul_rn(si, cr)));
-            }
-        }
-        re = __fdiv_rn(re, p.wnorm); im = __fdiv_rn(im, p.wnorm);
-    }
-    p.enh[row * 2 * p.F + f] = re; p.enh[row * 2 * p.F + p.F + f] = im;
-}
+//
+// The kernels and the handle live in deepfilternet_kernels.h, shared with the hop-by-hop streamer (deepfilternet_stream.hip); this file
+// instantiates their offline form (S = false).
+#include "deepfilternet_kernels.h"
 
 // out[b][s] = sum over the frames f covering padded sample s + fft - hop, in frame order, / max(sum w^2, 1e-8), clipped; 0 from lens[b] on
 __global__ void __launch_bounds__(256) k_dfn_ola(const float* __restrict__ fr, const float* __restrict__ win, float* __restrict__ out,
@@ -330,49 +40,10 @@ __global__ void __launch_bounds__(256) k_dfn_ola(const float* __restrict__ fr, c
     if (s < lens[b]) {
         const int64_t q = s + W - hop, lo = q - W + 1;
         const int fa = lo <= 0 ? 0 : (int)((lo + hop - 1) / hop), fb = q / hop > T - 1 ? T - 1 : (int)(q / hop);
-        float acc = 0.0f, ws = 0.0f;
-        for (int f = fa; f <= fb; ++f) {
-            const int j = (int)(q - (int64_t)f * hop);
-            acc = __fadd_rn(acc, fr[((size_t)b * nr + f) * W + j]);
-            ws = __fadd_rn(ws, __fmul_rn(win[j], win[j]));
-        }
-        v = fminf(fmaxf(__fdiv_rn(acc, fmaxf(ws, 1e-8f)), -1.0f), 1.0f);
+        v = df_ola_at(fr + (size_t)b * nr * W, 0, win, q, fa, fb, W, hop);
     }
     out[(size_t)b * out_stride + s] = v;
 }
-
-// ============================================================================ host
-struct DfBuf { float* p = nullptr; int F = 1, C = 0; size_t off = 0; };       // [B Tcap][F][C] at work + off
-struct DfOp {
-    int kind = 0, phase = DF_PH_NET;                                          // 0 gemm, 1 norm, 2 gru, 3 enh, 4 ola
-    DfGemm g{}; DfNorm n{}; DfGru r{}; DfEnh e{};
-    int H = 0, chains = 1;                                                    // recurrence: hidden size, chains of the launch
-    int in = -1, res = -1, out = -1;                                          // buffers, resolved once the workspace exists
-};
-struct DfTap { int stage; int buf; };
-
-struct mis_deepfilternet {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    mis_deepfilternet_config cfg{};
-    int F = 0, E = 0, D = 0, N = 0, hop = 0, Tcap = 0, KR = 0;
-    float wnorm = 0.0f;
-    HostWeights raw{"DeepFilterNet", MIS_ERR_INVALID_INPUT};
-    bool finalized = false;
-    DevBuf<float> farena, work, pcm;
-    DevBuf<int32_t> counts, iarena;                          // counts: T[64] | lens[64]
-    std::vector<int32_t> h_counts;
-    std::vector<DfOp> ops;
-    std::vector<DfBuf> bufs;
-    std::vector<DfTap> taps;
-    const float *win = nullptr, *idft = nullptr;
-    const int32_t* wlo = nullptr;
-    int b_wave = -1, b_fr = -1, b_lsnr = -1;
-    int last_batch = 0, last_nr = 0, last_launches = 0;
-    int64_t last_out = 0;
-    HipEvents<4 + 2 * DF_MAX_REC> ev;
-    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-};
 
 static int64_t df_frames_of(const mis_deepfilternet* c, int64_t n) { return 1 + (c->hop + n) / c->hop; }
 static bool df_gru_served(int H) { return H == 32 || H == 64 || H == 128 || H == 256; }
@@ -648,6 +319,7 @@ extern "C" mis_status mis_deepfilternet_finalize(mis_deepfilternet* c) {
         DfOp& op = B.new_op(1, DF_PH_FRONT);
         op.n.F = (int)F; op.n.E = (int)E; op.n.D = (int)D; op.n.a = cfg.norm_alpha;
         op.in = b_spec; op.res = b_erb;
+        c->b_spec = b_spec; c->b_ferb = b_ferb; c->b_fspec = b_fspec;
         B.tap(1, b_ferb); B.tap(2, b_fspec);
     }
     // ---- 3. encoder
@@ -752,6 +424,7 @@ extern "C" mis_status mis_deepfilternet_finalize(mis_deepfilternet* c) {
     const int coef = B.linear("df_dec.df_out.0.weight", true, nullptr, DF_ACT_TANH, cdf, c0p, 23);
     // ---- 6. synthesis
     const int b_enh = B.new_buf(1, (int)(2 * F));
+    c->b_enh = b_enh;
     {
         DfOp& op = B.new_op(3, DF_PH_SYNTH);
         op.e.F = (int)F; op.e.E = (int)E; op.e.D = (int)D; op.e.order = (int)O; op.e.pad_left = (int)O - 1 - cfg.df_lookahead; op.e.wnorm = c->wnorm;
@@ -811,6 +484,7 @@ extern "C" mis_status mis_deepfilternet_finalize(mis_deepfilternet* c) {
     }
     for (const RecFix& f : fix) {
         DfGruChain& q = c->ops[f.op].r.ch[f.slot];
+        c->ops[f.op].rgx[f.slot] = f.gx; c->ops[f.op].rout[f.slot] = f.out;
         q.gx = c->bufs[f.gx].p; q.Wh = gw[f.gw].Wh; q.WhT = gw[f.gw].WhT; q.bhh = gw[f.gw].bhh; q.out = c->bufs[f.out].p;
     }
     c->raw.clear();
@@ -903,7 +577,7 @@ extern "C" mis_status mis_deepfilternet_frames(const mis_deepfilternet* c, const
 // ---------------------------------------------------------------------------- a call
 template <int H, int KR>
 static void df_launch_gru(mis_deepfilternet* c, const DfOp& op, int B) {
-    hipLaunchKernelGGL((k_dfn_gru<H, KR>), dim3(B, op.chains), dim3(3 * H), 0, c->stream, op.r);
+    hipLaunchKernelGGL((k_dfn_gru<H, KR, false>), dim3(B, op.chains), dim3(3 * H), 0, c->stream, op.r);
 }
 
 static void df_run(mis_deepfilternet* c, const float* pcm, int64_t stride, int B, int nr, int64_t nmax, float* out, int64_t out_stride, float* lsnr,
@@ -925,10 +599,10 @@ static void df_run(mis_deepfilternet* c, const float* pcm, int64_t stride, int B
         }
         if (op.kind == 0) {
             op.g.nr = nr; op.g.pcm_stride = ns;
-            hipLaunchKernelGGL(k_dfn_gemm, dim3(cdiv((int64_t)nr * op.g.Fo, 64), cdiv(op.g.N, 64), B), dim3(256), 0, s, op.g);
+            hipLaunchKernelGGL(k_dfn_gemm<false>, dim3(cdiv((int64_t)nr * op.g.Fo, 64), cdiv(op.g.N, 64), B), dim3(256), 0, s, op.g);
         } else if (op.kind == 1) {
             op.n.nr = nr;
-            hipLaunchKernelGGL(k_dfn_norm, dim3(B), dim3(256), 0, s, op.n);
+            hipLaunchKernelGGL(k_dfn_norm<false>, dim3(B), dim3(256), 0, s, op.n);
         } else if (op.kind == 2) {
             op.r.nr = nr;
             HIP_CHECK(hipEventRecord(c->ev[4 + 2 * nrec], s));
@@ -942,7 +616,7 @@ static void df_run(mis_deepfilternet* c, const float* pcm, int64_t stride, int B
             ++nrec;
         } else if (op.kind == 3) {
             op.e.nr = nr; op.e.total = (size_t)B * nr * c->F;
-            hipLaunchKernelGGL(k_dfn_enh, dim3((unsigned)((op.e.total + 255) / 256)), dim3(256), 0, s, op.e);
+            hipLaunchKernelGGL(k_dfn_enh<false>, dim3((unsigned)((op.e.total + 255) / 256)), dim3(256), 0, s, op.e);
         } else {
             hipLaunchKernelGGL(k_dfn_ola, dim3((unsigned)((ns + 255) / 256), B), dim3(256), 0, s, c->bufs[c->b_fr].p, c->win, c->bufs[c->b_wave].p,
                                c->counts.p, c->counts.p + DF_MAX_BATCH, nr, c->N, c->hop, ns);

@@ -666,7 +666,9 @@ def deepfilternet_synthetic_weights(config: DeepFilterNetConfig, seed: int = 777
 
 class DeepFilterNet(NativeHandle):
     """DeepFilterNetModel.enhance (V2 / V3, offline) for ragged batches: one handle, 1..max_batch rows a call, each at most
-    max_seconds long.  The hop-by-hop streamer (enhanceStreaming) is not offered."""
+    max_seconds long.  Hop by hop: DeepFilterNetStreamer(model) (createStreamer), deepfilternet_enhance_streaming(model, audio) and
+    deepfilternet_stream_chunks(model, audio) (the two enhanceStreaming overloads); the method enhance_streaming of this class still
+    raises, as it did before the streamer existed."""
     _prefix = "mis_deepfilternet"
 
     def __init__(self, config: DeepFilterNetConfig, device: int = 0):
@@ -815,6 +817,222 @@ class DeepFilterNet(NativeHandle):
         ms = (C.c_float * 4)()
         check(_lib.lib().mis_debug_deepfilternet_timing(self._h, ms))
         return tuple(float(v) for v in ms)
+
+
+# ------------------------------------------------------------------------------------------------------------ DeepFilterNet, hop by hop
+@dataclass
+class DeepFilterNetStreamingConfig:
+    """DeepFilterNetStreamingConfig (DeepFilterNetModel.swift:40-82): every field and default.  Stage skipping is refused by the
+    streamer (its thresholds stay so that the fields round-trip); the profiling fields and materialize_every_hops are accepted and
+    ignored: they steer the reference's lazy evaluation, which this engine does not have."""
+    pad_end_frames: int = 3
+    compensate_delay: bool = True
+    enable_stage_skipping: bool = False
+    min_db_thresh: float = -10.0
+    max_db_erb_thresh: float = 30.0
+    max_db_df_thresh: float = 20.0
+    enable_profiling: bool = False
+    profiling_force_eval_per_stage: bool = False
+    materialize_every_hops: int = 512
+
+
+def deepfilternet_stream_check_served(config: DeepFilterNetConfig, streaming: "DeepFilterNetStreamingConfig"):
+    """What the streamer refuses before the device is touched (csrc/deepfilternet_stream.hip refuses the two shapes again)."""
+    config.check_served()
+    if streaming.enable_stage_skipping:
+        raise AudioGenerationError(3, "DeepFilterNet streaming: enable_stage_skipping = true is not served: the reference lets the decoder "
+                                      "GRUs stand still on skipped frames, which needs one host decision a hop; every stage runs on every hop")
+    if config.fft_size != 2 * config.hop_size:
+        raise AudioGenerationError(3, f"DeepFilterNet streaming: fft_size {config.fft_size} with hop_size {config.hop_size} is not served "
+                                      "(fft_size == 2 hop_size: the offline frame grid and the analysis memory coincide at this ratio only)")
+    if config.df_lookahead > config.conv_lookahead:
+        raise AudioGenerationError(3, f"DeepFilterNet streaming: df_lookahead {config.df_lookahead} above conv_lookahead "
+                                      f"{config.conv_lookahead} is not served (the deep filter would read frames that have not arrived)")
+    if streaming.pad_end_frames < 0:
+        raise AudioGenerationError(3, "DeepFilterNet streaming: pad_end_frames is negative")
+
+
+class DeepFilterNetStreamer:
+    """DeepFilterNetStreamer (DeepFilterNetStreamer.swift) for 1..max_batch streams on one model: process_chunk / flush / reset for
+    stream 0, process_chunks for all slots at once.  The host keeps what processChunk keeps, a stream's pending remainder below one hop,
+    the delay counter and the end padding; whole hops go to mis_deepfilternet_stream_feed, at most max_hops a stream and feed.  Fed any
+    chunking and flushed, a stream returns count = (H - conv_lookahead) hop - (fft - hop) samples for its H whole hops (compensate_delay;
+    fft - hop more without), bit for bit the first count samples of model.enhance on the same zero-extended samples.
+
+    _feed (tests): a callable (list of float32 arrays of whole hops, one a slot) -> (list of outputs, list of lsnr) in place of the device."""
+
+    def __init__(self, model, config: DeepFilterNetStreamingConfig | None = None, streams: int = 1, max_hops: int = 16, _feed=None):
+        self.model = model
+        self.config = config if config is not None else DeepFilterNetStreamingConfig()
+        deepfilternet_stream_check_served(model.config, self.config)
+        self.streams, self.max_hops = int(streams), int(max_hops)
+        self.hop, self.delay = model.config.hop_size, model.config.fft_size - model.config.hop_size
+        self._h, self._fake = None, _feed
+        if _feed is None:
+            h = C.c_void_p()
+            check(_lib.lib().mis_deepfilternet_stream_create(model._h, self.streams, self.max_hops, C.byref(h)))
+            self._h = h
+        elif not (1 <= self.streams and 1 <= self.max_hops):
+            raise AudioGenerationError(3, "DeepFilterNet streaming: streams and max_hops start at 1")
+        self._seen = [0] * self.streams
+        self._pending = [np.zeros(0, _F) for _ in range(self.streams)]
+        self._dropped = [0] * self.streams
+        self.last_lsnr = [np.zeros(0, _F) for _ in range(self.streams)]
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            _lib.lib().mis_deepfilternet_stream_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                                # interpreter shutdown
+            pass
+
+    @property
+    def launches(self) -> int:
+        """Kernel launches of the last feed."""
+        return int(_lib.lib().mis_deepfilternet_stream_launches(self._h)) if self._h else 0
+
+    def expected_launches(self, targets: bool, erb_fb: bool, df_skip: bool, enc_linear_out: bool = True, erb_linear_out: bool = True) -> int:
+        """The launch count of a feed: with targets the offline chain + the roll; before the look-ahead has filled, the
+        front end (analysis [+ erb_fb] + features) + the roll."""
+        return self.model.expected_launches(erb_fb, df_skip, enc_linear_out, erb_linear_out) + 1 if targets else 3 + int(erb_fb)
+
+    @property
+    def hops_seen(self):
+        """Hops every stream has been fed since its last reset; an int for a single stream."""
+        seen = [int(_lib.lib().mis_deepfilternet_stream_hops_seen(self._h, b)) for b in range(self.streams)] if self._h else list(self._seen)
+        return seen[0] if self.streams == 1 else seen
+
+    def timing(self):
+        """Device milliseconds of the last feed: (the whole feed, its recurrence launches)."""
+        ms = (C.c_float * 2)()
+        check(_lib.lib().mis_debug_deepfilternet_stream_timing(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
+    def set_gru_step_frames(self, frames: int):
+        """Measurements and tests: feeds of at most `frames` targets run the short-chunk recurrence (0 never, negative the default)."""
+        check(_lib.lib().mis_debug_deepfilternet_stream_gru_step_frames(self._h, int(frames)))
+
+    def reset(self, stream: int | None = None):
+        """reset(): one stream (None: all) back to the state after create."""
+        if stream is not None and not 0 <= stream < self.streams:
+            raise AudioGenerationError(3, f"DeepFilterNet streaming: stream {stream} outside 0..{self.streams - 1}")
+        if self._h:
+            check(_lib.lib().mis_deepfilternet_stream_reset(self._h, -1 if stream is None else int(stream)))
+        for b in range(self.streams) if stream is None else (stream,):
+            self._seen[b], self._pending[b], self._dropped[b], self.last_lsnr[b] = 0, np.zeros(0, _F), 0, np.zeros(0, _F)
+
+    # ---- whole hops to the device
+    def feed_hops(self, rows, junk=None):
+        """rows: a float32 array of whole hops (at most max_hops; may be empty) for every slot -> (outputs, lsnr), one array each a slot.
+        The raw device interface: no pending remainder, no delay drop."""
+        rows = [np.ascontiguousarray(r, _F) for r in rows]
+        if len(rows) != self.streams or any(r.ndim != 1 or len(r) % self.hop for r in rows):
+            raise AudioGenerationError(3, f"DeepFilterNet streaming: a feed takes {self.streams} rows of whole hops")
+        for b, r in enumerate(rows):
+            self._seen[b] += len(r) // self.hop
+        if self._fake is not None:
+            return self._fake(rows)
+        pcm, lens = pack_rows(rows, junk)
+        hops = np.ascontiguousarray(lens // self.hop, np.int32)
+        B, room = self.streams, max(1, self.max_hops * self.hop)
+        out, got = np.zeros((B, room), _F), np.zeros(B, np.int64)
+        lsnr, lc = np.zeros((B, self.max_hops), _F), np.zeros(B, np.int32)
+        check(_lib.lib().mis_deepfilternet_stream_feed(self._h, pcm.ctypes.data, hops.ctypes.data, pcm.shape[1], out.ctypes.data, room,
+                                                       got.ctypes.data, lsnr.ctypes.data, lsnr.shape[1], lc.ctypes.data))
+        return [out[b, : int(got[b])].copy() for b in range(B)], [lsnr[b, : int(lc[b])].copy() for b in range(B)]
+
+    def _run(self, chunks, last):
+        """processChunk for every slot: chunks[b] an array or None (the slot is left alone), last[b] its isLast."""
+        hop, B = self.hop, self.streams
+        todo = [np.zeros(0, _F)] * B
+        for b, ch in enumerate(chunks):
+            if ch is None:
+                continue
+            a = np.asarray(ch)
+            if a.ndim != 1:
+                raise DeepFilterNetError("invalidAudioShape", f"Expected mono 1D audio array, got shape: {list(a.shape)}")
+            p = np.concatenate([self._pending[b], a.astype(_F, copy=False)])
+            n = len(p) // hop * hop
+            whole, p = p[:n], p[n:]
+            if last[b] and self.config.pad_end_frames > 0:               # the remainder stays in front of the padding, as in the reference
+                p = np.concatenate([p, np.zeros(self.config.pad_end_frames * hop, _F)])
+                n = len(p) // hop * hop
+                whole, p = np.concatenate([whole, p[:n]]), p[n:]
+            todo[b], self._pending[b] = whole, p
+        outs, lsnrs = [[] for _ in range(B)], [[] for _ in range(B)]
+        step = self.max_hops * hop
+        for at in range(0, max(len(t) for t in todo), step):             # a chunk above max_hops hops is walked in several feeds
+            o, l = self.feed_hops([t[at: at + step] for t in todo])
+            for b in range(B):
+                outs[b].append(o[b]), lsnrs[b].append(l[b])
+        res = []
+        for b in range(B):
+            if chunks[b] is None:
+                res.append(None)
+                continue
+            y = np.concatenate(outs[b]) if outs[b] else np.zeros(0, _F)
+            self.last_lsnr[b] = np.concatenate(lsnrs[b]) if lsnrs[b] else np.zeros(0, _F)
+            if self.config.compensate_delay and self._dropped[b] < self.delay:
+                drop = min(self.delay - self._dropped[b], len(y))
+                y, self._dropped[b] = y[drop:], self._dropped[b] + drop
+            res.append(y)
+        return res
+
+    def process_chunks(self, chunks, is_last=False) -> list:
+        """One chunk (1-D array) or None for every stream slot -> one output array, or None, a slot.  is_last: one flag, or one a slot."""
+        chunks = list(chunks)
+        if len(chunks) != self.streams:
+            raise AudioGenerationError(3, f"DeepFilterNet streaming: {len(chunks)} chunks for {self.streams} streams")
+        last = list(is_last) if isinstance(is_last, (list, tuple)) else [bool(is_last)] * self.streams
+        return self._run(chunks, last)
+
+    def process_chunk(self, chunk, is_last: bool = False) -> np.ndarray:
+        """processChunk (:282-359) for stream 0: enhanced samples, possibly none while the look-ahead fills.  The per-frame lsnr of the
+        targets it ran is in last_lsnr[0]."""
+        return self._run([chunk] + [None] * (self.streams - 1), [is_last] + [False] * (self.streams - 1))[0]
+
+    def flush(self) -> np.ndarray:
+        """flush (:374-381): the end padding and what it releases."""
+        return self.process_chunk(np.zeros(0, _F), True)
+
+
+def deepfilternet_stream_chunks(model, audio, chunk_samples=None, config: DeepFilterNetStreamingConfig | None = None, max_hops: int = 16):
+    """enhanceStreaming as a stream of chunks (DeepFilterNetModel.swift:496-547): yields (audio, chunk_index, is_last_chunk) for every
+    non-empty output; chunk_samples is floored at one hop."""
+    a = np.asarray(audio)
+    if a.ndim != 1:
+        raise DeepFilterNetError("invalidAudioShape", f"Expected mono 1D audio array, got shape: {list(a.shape)}")
+    a = a.astype(_F, copy=False)
+    st = DeepFilterNetStreamer(model, config, 1, max_hops)
+    try:
+        step = max(model.config.hop_size, int(chunk_samples) if chunk_samples is not None else model.config.hop_size)
+        index = 0
+        for at in range(0, len(a), step):
+            out = st.process_chunk(a[at: at + step])
+            if len(out):
+                yield out, index, False
+                index += 1
+        tail = st.flush()
+        if len(tail):
+            yield tail, index, True
+    finally:
+        st.close()
+
+
+def deepfilternet_enhance_streaming(model, audio, chunk_samples=None, config: DeepFilterNetStreamingConfig | None = None) -> np.ndarray:
+    """enhanceStreaming (DeepFilterNetModel.swift:448-487): the clipped concatenation of the streamer's outputs; empty audio gives
+    empty audio."""
+    a = np.asarray(audio)
+    if a.ndim != 1:
+        raise DeepFilterNetError("invalidAudioShape", f"Expected mono 1D audio array, got shape: {list(a.shape)}")
+    if a.size == 0:
+        return np.zeros(0, _F)
+    parts = [out for out, _, _ in deepfilternet_stream_chunks(model, a, chunk_samples, config)]
+    return np.clip(np.concatenate(parts), -1.0, 1.0).astype(_F) if parts else np.zeros(0, _F)
 
 
 # ------------------------------------------------------------------------------------------------------------ the factory
