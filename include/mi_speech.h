@@ -552,10 +552,13 @@ mis_status mis_dac_debug_tap(mis_dac*, const int32_t* codes, int batch, int T, i
                              int32_t* channels, int64_t* length);
 
 /* ------------------------------------------------------------------------------------------
- * EnCodec decoder.  Replaces Encodec.decodeFrame / EncodecDecoder (Sources/MLXAudioCodecs/Encodec/Encodec.swift:94-170,295-302)
+ * EnCodec decoder and encoder.  Replaces Encodec.decodeFrame / EncodecDecoder (Sources/MLXAudioCodecs/Encodec/Encodec.swift:94-170,295-302)
  * incl. the 2-layer LSTM (EncodecLayers.swift:15-80) and EncodecResidualVectorQuantizer.decode (EncodecQuantization.swift:117-133).
  * norm_type "weight_norm" models (no GroupNorm), mono, causal.  Chunked decode = decode_frame per chunk + the host
  * linearOverlapAdd of the reference (Encodec.swift:304-355; mirrored in the Python host layer).
+ * Encode: Encodec.encodeFrame (Encodec.swift:212-238) = loudness normalisation (config.normalize), EncodecEncoder (:17-89) and
+ * EncodecResidualVectorQuantizer.encode (EncodecQuantization.swift:22-32,100-114); the chunk walk of Encodec.encode (:248-291) is host
+ * work (mirrored in the Python host layer), which folds all chunks of all batch rows into the rows of one encode_frame call.
  * ---------------------------------------------------------------------------------------- */
 typedef struct mis_encodec mis_encodec;
 typedef struct {                   /* EncodecConfig.swift:64-89 */
@@ -568,11 +571,14 @@ typedef struct {                   /* EncodecConfig.swift:64-89 */
     int32_t sampling_rate;
     int32_t group_norm;            /* 1: norm_type "time_group_norm" (the 48 kHz model): GroupNorm(1 group) after every conv, in the
                                       transposed-conv layer before the trim (EncodecLayers.swift:128-131,203-212,244-262); 0: plain convs */
+    int32_t normalize;             /* 1: encode divides every row by its loudness and returns it as the row's scale (Encodec.swift:227-233) */
 } mis_encodec_config;
 mis_status mis_encodec_create(const mis_encodec_config*, int device, mis_encodec** out);
 /* module-tree keys: quantizer.layers.N.codebook.embed, decoder.layers.N.conv.{weight [out,k,in],bias},
  * decoder.layers.1.lstm.N.{Wx,Wh,bias}, decoder.layers.N.{block.1,block.3,shortcut}.conv.*, with group_norm also
- * <conv prefix>.norm.{weight,bias} [out]; "encoder.*" ignored */
+ * <conv prefix>.norm.{weight,bias} [out].  Optional, all or none: the same key forms under encoder.layers.N (EncodecEncoder numbering:
+ * 0 conv, then per reversed ratio [resnet x num_residual_layers, ELU, strided conv], LSTM block, ELU, last conv).  A checkpoint
+ * without them finalizes and decodes; encoding with it returns MIS_ERR_AUDIO_ENCODE */
 mis_status mis_encodec_set_tensor(mis_encodec*, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim);
 mis_status mis_encodec_finalize(mis_encodec*);
 void       mis_encodec_destroy(mis_encodec*);
@@ -582,6 +588,13 @@ mis_status mis_encodec_decode_frame(mis_encodec*, const int32_t* codes, int batc
 /* stage 1 conv0, 2 LSTM block, 3 + i upsampling block i: out f32 [batch, C, T'] */
 mis_status mis_encodec_debug_tap(mis_encodec*, const int32_t* codes, int batch, int n_q, int T, int stage, float* out, int64_t capacity,
                                  int32_t* channels, int64_t* length);
+int        mis_encodec_has_encoder(const mis_encodec*);          /* 1: finalized with the encoder.layers.* tensors */
+int64_t    mis_encodec_encode_num_frames(const mis_encodec*, int64_t L);   /* frames of L samples: a ceil per strided conv */
+/* encodeFrame of rows = chunks x batch independent rows: audio f32 [rows][channels][L], mask u8 [rows][L] or NULL (all ones; read by
+ * normalize models only) -> codes_out i32 [rows][n_q][F], F = encode_num_frames(L); scales_out f32 [rows] or NULL (written by
+ * normalize models only).  Host or device pointers.  A row's codes and scale do not depend on the other rows of the call */
+mis_status mis_encodec_encode_frame(mis_encodec*, const float* audio, const uint8_t* mask, int rows, int64_t L, int n_q, int32_t* codes_out,
+                                    float* scales_out);
 
 /* ------------------------------------------------------------------------------------------
  * Mimi codec (Kyutai, 12.5 Hz codes, 24 kHz mono).  Replaces Mimi.decode / encode (Sources/MLXAudioCodecs/Mimi/Mimi.swift:168-186),

@@ -37,6 +37,14 @@ int64_t mis_debug_whisper_weight_bytes(const mis_whisper* c);
  * 3 init conv, 4 + i decoder layer i (ELU, transposed conv, residual blocks), 4 + n_ratios final (pcm, C = 1) */
 mis_status mis_debug_mimi_decoder_tap(mis_mimi* m, const int32_t* codes, int batch, int n_q, int T, int stage, float* out, int64_t capacity,
                                       int32_t* channels, int64_t* length);
+/* tests (tests/test_gpu_encodec_encode.py): the EnCodec encode chain.  stage >= 0: `in` is audio f32 [rows][channels][L] (+ mask u8
+ * [rows][L] or NULL); out f32 [rows][C][T'] is that stage's output: 0 normalised input, 1 conv0, 2 + i down block i (resnets, ELU, strided
+ * conv), 2 + n_ratios LSTM block, 3 + n_ratios embeddings.  stage -1: ONE launch of the residual-VQ search on caller-supplied embeddings
+ * `in` f32 [rows][D][L] (L frames): codes_out i32 [rows][n_q][L] and out f32 [n_q + 1][rows][D][L], the residual before every quantizer
+ * and after the last.  Inputs are followed by NaN (mask: 0xFF); the RVQ outputs lie between guard bands, a changed guard byte fails the
+ * call with MIS_ERR_GENERATION_FAILED */
+mis_status mis_debug_encodec_encode_tap(mis_encodec* c, const float* in, const uint8_t* mask, int rows, int64_t L, int n_q, int stage, float* out,
+                                        int64_t capacity, int32_t* codes_out, int32_t* channels, int64_t* length);
 
 /* csrc/gemm_debug.hip, tests (tests/test_gpu_gemm_ops.py): ONE launch of a GEMM launcher on caller-supplied host data.  16-bit operands are
  * passed as raw payloads (uint16).  Operands are packed by the product's load-time kernels; W2 (optional, same shape as W) is packed with

@@ -8,7 +8,7 @@ the Swift shim a maintainer would add):
 
     codecs.SNAC            <-> class SNAC : AudioCodecModel       (MLXAudioCodecs/SNAC/SNACDecoder.swift)
     codecs.DescriptDAC     <-> class DescriptDAC (decode side)         (MLXAudioCodecs/Descript/DescriptDAC.swift)
-    codecs.Encodec         <-> class Encodec (decode side)             (MLXAudioCodecs/Encodec/Encodec.swift)
+    codecs.Encodec         <-> class Encodec (encode and decode)       (MLXAudioCodecs/Encodec/Encodec.swift)
     codecs.Mimi            <-> class Mimi : AudioCodecModel + MimiStreamingDecoder  (MLXAudioCodecs/Mimi/Mimi.swift)
     codecs.BigVGAN         <-> class BigVGAN : AudioDecoderModel (mel -> waveform vocoder)  (MLXAudioCodecs/BigVGAN/BigVGAN.swift)
     tts.LlamaTTSModel      <-> class LlamaTTSModel : SpeechGenerationModel  (MLXAudioTTS/Models/Llama/LlamaTTS.swift)
@@ -37,6 +37,7 @@ from . import _lib  # noqa: F401
 from .generation import (AudioGenerationError, AudioGenerationInfo, GenerateParameters, TokenEvent, InfoEvent,  # noqa: F401
                          AudioEvent)
 from .codecs import SNAC, SNACConfig, DescriptDAC, DescriptDACConfig, Encodec, EncodecConfig  # noqa: F401
+from .codecs import EncodecEncodedAudio, preprocess_encodec_audio  # noqa: F401
 from .codecs import Mimi, MimiConfig, MimiStreamingDecoder, mimi_sanitize  # noqa: F401
 from .codecs import BigVGAN, BigVGANConfig, bigvgan_sanitize, bigvgan_expected_shapes, bigvgan_aa_act  # noqa: F401
 from .tts import (LlamaTTSModel, LlamaTTSConfiguration, OrpheusTokens, VyvoTokens, interleave_snac_codes,  # noqa: F401

@@ -122,7 +122,8 @@ class EncodecConfigC(C.Structure):
                 ("residual_kernel_size", C.c_int32), ("use_causal_conv", C.c_int32), ("pad_reflect", C.c_int32),
                 ("last_kernel_size", C.c_int32), ("compress", C.c_int32), ("use_conv_shortcut", C.c_int32),
                 ("trim_right_ratio", C.c_float), ("n_upsampling_ratios", C.c_int32), ("upsampling_ratios", C.c_int32 * 8),
-                ("n_quantizers", C.c_int32), ("sampling_rate", C.c_int32), ("group_norm", C.c_int32)]
+                ("n_quantizers", C.c_int32), ("sampling_rate", C.c_int32), ("group_norm", C.c_int32),
+                ("normalize", C.c_int32)]
 
 
 class MelConfigC(C.Structure):
@@ -495,6 +496,9 @@ SYMBOLS = {
     "mis_encodec_decode_frame": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_encodec_debug_tap": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64)]),
+    "mis_encodec_has_encoder": (C.c_int, [_P]),
+    "mis_encodec_encode_num_frames": (C.c_int64, [_P, C.c_int64]),
+    "mis_encodec_encode_frame": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, _P, _P]),
     "mis_mimi_202407": (None, [C.c_int, C.POINTER(MimiConfigC)]),
     "mis_mimi_create": (C.c_int, [C.POINTER(MimiConfigC), C.c_int, C.POINTER(_P)]),
     "mis_mimi_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
@@ -627,6 +631,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_sortformer_intake": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "mis_debug_sortformer_glu_dwconv": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_sortformer_peak": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, _P]),
+    "mis_debug_encodec_encode_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int64)]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
 }
 

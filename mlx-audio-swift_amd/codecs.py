@@ -302,16 +302,37 @@ class EncodecConfig:
     chunk_length_s: float | None = None
     overlap: float | None = None
     use_conv_shortcut: bool = True
+    normalize: bool = False
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "EncodecConfig":
+        """config.json keys of EncodecConfig.swift:37-62 (model_type and keys the reference does not decode are ignored)"""
+        kw = {k: d[k] for k in cls.__dataclass_fields__ if k in d}
+        for k in ("upsampling_ratios", "target_bandwidths"):
+            if k in kw:
+                kw[k] = tuple(kw[k])
+        return cls(**kw)
 
     @property
     def hop_length(self) -> int:
         return int(np.prod(self.upsampling_ratios))
 
     @property
-    def num_quantizers(self) -> int:              # EncodecQuantization.swift:60-64
+    def frame_rate(self) -> int:                  # EncodecQuantization.swift:78-79
         import math
-        frame_rate = int(math.ceil(self.sampling_rate / self.hop_length))
-        return int(1000 * max(self.target_bandwidths) / (frame_rate * 10))
+        return int(math.ceil(self.sampling_rate / self.hop_length))
+
+    @property
+    def num_quantizers(self) -> int:              # EncodecQuantization.swift:60-64
+        return int(1000 * max(self.target_bandwidths) / (self.frame_rate * 10))
+
+    def num_quantizers_for_bandwidth(self, bandwidth: float | None) -> int:
+        """getNumQuantizersForBandwidth (EncodecQuantization.swift:90-97), in the reference's float32"""
+        n = self.num_quantizers
+        if bandwidth is not None and bandwidth > 0.0:
+            bw_per_q = np.float32(np.log2(np.float32(self.codebook_size))) * np.float32(self.frame_rate)
+            n = max(1, int(np.floor(np.float32(bandwidth) * np.float32(1000) / bw_per_q)))
+        return n
 
     @property
     def chunk_length(self):                       # Encodec.swift:196-201
@@ -332,12 +353,87 @@ class EncodecConfig:
                                    1 if self.pad_mode == "reflect" else 0, self.last_kernel_size, self.compress,
                                    1 if self.use_conv_shortcut else 0, float(self.trim_right_ratio), len(self.upsampling_ratios),
                                    (C.c_int32 * 8)(*self.upsampling_ratios), self.num_quantizers, self.sampling_rate,
-                                   1 if self.norm_type == "time_group_norm" else 0)
+                                   1 if self.norm_type == "time_group_norm" else 0, 1 if self.normalize else 0)
+
+
+@dataclass
+class EncodecEncodedAudio:
+    """EncodecEncodedAudio (Encodec.swift:441-450): decode needs both the codes [chunks, B, n_q, frames] and the per-chunk scales"""
+    codes: np.ndarray
+    scales: list
+
+
+def encodec_expected_shapes(config: EncodecConfig, encoder: bool = True) -> dict:
+    """Module-tree key -> shape of an EnCodec checkpoint (EncodecEncoder / EncodecDecoder / EncodecResidualVectorQuantizer,
+    Encodec.swift:17-167, EncodecQuantization.swift:75-87; key suffixes of EncodecLayers.swift)."""
+    cfg, want = config, {}
+    gn = cfg.norm_type == "time_group_norm"
+
+    def conv(p, co, k, ci):
+        want[p + ".conv.weight"], want[p + ".conv.bias"] = (co, k, ci), (co,)
+        if gn:
+            want[p + ".norm.weight"], want[p + ".norm.bias"] = (co,), (co,)
+
+    def resnet(p, dim):
+        conv(p + ".block.1", dim // cfg.compress, cfg.residual_kernel_size, dim)
+        conv(p + ".block.3", dim, 1, dim // cfg.compress)
+        if cfg.use_conv_shortcut:
+            conv(p + ".shortcut", dim, 1, dim)
+
+    def lstm(p, dim):
+        for j in range(cfg.num_lstm_layers):
+            want[f"{p}.lstm.{j}.Wx"], want[f"{p}.lstm.{j}.Wh"], want[f"{p}.lstm.{j}.bias"] = (4 * dim, dim), (4 * dim, dim), (4 * dim,)
+
+    for i in range(cfg.num_quantizers):
+        want[f"quantizer.layers.{i}.codebook.embed"] = (cfg.codebook_size, cfg.codebook_dim)
+    dim = cfg.num_filters << len(cfg.upsampling_ratios)
+    conv("decoder.layers.0", dim, cfg.kernel_size, cfg.hidden_size)
+    lstm("decoder.layers.1", dim)
+    li = 2
+    for ratio in cfg.upsampling_ratios:
+        conv(f"decoder.layers.{li + 1}", dim // 2, 2 * ratio, dim)
+        li, dim = li + 2, dim // 2
+        for _ in range(cfg.num_residual_layers):
+            resnet(f"decoder.layers.{li}", dim)
+            li += 1
+    conv(f"decoder.layers.{li + 1}", cfg.audio_channels, cfg.last_kernel_size, dim)
+    if encoder:
+        dim = cfg.num_filters
+        conv("encoder.layers.0", dim, cfg.kernel_size, cfg.audio_channels)
+        li = 1
+        for ratio in reversed(cfg.upsampling_ratios):
+            for _ in range(cfg.num_residual_layers):
+                resnet(f"encoder.layers.{li}", dim)
+                li += 1
+            conv(f"encoder.layers.{li + 1}", 2 * dim, 2 * ratio, dim)
+            li, dim = li + 2, 2 * dim
+        lstm(f"encoder.layers.{li}", dim)
+        conv(f"encoder.layers.{li + 2}", cfg.hidden_size, cfg.last_kernel_size, dim)
+    return want
+
+
+def preprocess_encodec_audio(raw_audio, sampling_rate: int = 24000, chunk_length: int | None = None, chunk_stride: int | None = None):
+    """preprocessEncodecAudio (Encodec.swift:478-515): a list of [L] or [L, channels] waveforms -> (inputs float32 [B, max_length,
+    channels], masks bool [B, max_length]), right-padded with zeros; with chunking max_length grows by chunk - (max_length % stride)."""
+    audio = [np.asarray(x, np.float32) for x in raw_audio]
+    audio = [x[:, None] if x.ndim == 1 else x for x in audio]
+    max_length = max((x.shape[0] for x in audio), default=0)
+    if chunk_length is not None and chunk_stride is not None:
+        max_length += chunk_length - (max_length % chunk_stride)
+    inputs = np.zeros((len(audio), max_length, audio[0].shape[1] if audio else 1), np.float32)
+    masks = np.zeros((len(audio), max_length), bool)
+    for i, x in enumerate(audio):
+        inputs[i, : x.shape[0]] = x
+        masks[i, : x.shape[0]] = True
+    return inputs, masks
 
 
 class Encodec(NativeHandle):
-    """Decode side of class Encodec (Encodec/Encodec.swift:179-398): decode(audio_codes, audio_scales); the 24 kHz (mono, causal,
-    plain convs) and the 48 kHz (stereo, non-causal, GroupNorm) model families."""
+    """class Encodec (Encodec/Encodec.swift:172-465): encode(input_values, padding_mask, bandwidth) / decode(audio_codes, audio_scales)
+    and the AudioCodecModel surface encode_audio / decode_audio / reconstruct; the 24 kHz (mono, causal, plain convs) and the 48 kHz
+    (stereo, non-causal, GroupNorm, normalize, chunked) model families.  Loaders: from_weights, from_model_directory / from_pretrained
+    (config.json + model.safetensors, unknown keys rejected), synthetic.  Encoding needs the checkpoint's encoder.* tensors (error 5
+    otherwise)."""
 
     _prefix = "mis_encodec"
 
@@ -353,9 +449,143 @@ class Encodec(NativeHandle):
         m.finalize()
         return m
 
+    @classmethod
+    def from_model_directory(cls, model_dir: str, device: int = 0) -> "Encodec":
+        """fromModelDirectory (Encodec.swift:423-438): config.json + model.safetensors; a key the model does not have is an error
+        (verify: .noUnusedKeys).  The encoder tensors may be absent as a whole (a decoder-only export)."""
+        path = os.path.join(model_dir, "config.json")
+        if not os.path.exists(path):
+            raise AudioGenerationError(1, f"Encodec: config.json not found in {model_dir!r}")
+        with open(path) as f:
+            cfg = EncodecConfig.from_dict(json.load(f))
+        wpath = os.path.join(model_dir, "model.safetensors")
+        if not os.path.exists(wpath):
+            raise AudioGenerationError(1, f"Encodec: model.safetensors not found in {model_dir!r}")
+        from safetensors import safe_open
+        with safe_open(wpath, framework="pt") as sf:
+            weights = {k: sf.get_tensor(k) for k in sf.keys()}
+        unused = sorted(set(weights) - set(encodec_expected_shapes(cfg)))
+        if unused:
+            raise AudioGenerationError(3, f"Encodec checkpoint: unused keys {unused[:4]}")
+        return cls.from_weights(cfg, weights, device)
+
+    @classmethod
+    def from_pretrained(cls, path_or_repo: str, device: int = 0) -> "Encodec":
+        """fromPretrained (Encodec.swift:402-421).  No network here: the repo id must resolve to a local directory."""
+        if os.path.isdir(path_or_repo):
+            return cls.from_model_directory(path_or_repo, device)
+        raise AudioGenerationError(1, f"model repo {path_or_repo!r} is not a local directory (no network access)")
+
+    @classmethod
+    def synthetic(cls, config: EncodecConfig, seed: int = 909, device: int = 0) -> "Encodec":
+        """A full model (encoder, decoder, codebooks) with mis-synth-v1 weights in checkpoint order (measurement tools)."""
+        from .synthetic import encodec_synthetic_weights
+        return cls.from_weights(config, encodec_synthetic_weights(config, seed), device)
+
     @property
     def codec_sample_rate(self) -> float:
         return float(self.config.sampling_rate)
+
+    @property
+    def has_encoder(self) -> bool:
+        return bool(_lib.lib().mis_encodec_has_encoder(self._h))
+
+    def num_frames(self, length: int) -> int:
+        """frames of `length` samples: a ceil per strided conv of the encoder"""
+        return int(_lib.lib().mis_encodec_encode_num_frames(self._h, int(length)))
+
+    def encode_rows(self, rows, masks=None, n_q: int | None = None):
+        """encodeFrame (Encodec.swift:212-238) of independent rows: rows float32 [R, L, channels], masks bool [R, L] or None ->
+        (codes int32 [R, n_q, frames], scales float32 [R] or None without config.normalize).  One device pass."""
+        a = np.ascontiguousarray(np.transpose(np.asarray(rows, np.float32), (0, 2, 1)))            # [R, channels, L]
+        R, ch, L = a.shape
+        if ch != self.config.audio_channels:
+            raise AudioGenerationError(3, f"Encodec: {ch} input channels, the model has {self.config.audio_channels}")
+        if self.config.chunk_length_s is not None and L / self.config.sampling_rate > 1e-5 + self.config.chunk_length_s:
+            raise AudioGenerationError(3, f"Duration of frame ({L / self.config.sampling_rate}) is longer than chunk {self.config.chunk_length_s}")
+        nq = self.config.num_quantizers if n_q is None else int(n_q)
+        if not 1 <= nq <= self.config.num_quantizers:
+            raise AudioGenerationError(3, f"{nq} quantizers asked of a model with {self.config.num_quantizers}")
+        m = None if masks is None else np.ascontiguousarray(np.asarray(masks).astype(np.uint8))
+        codes = np.zeros((R, nq, self.num_frames(L)), np.int32)
+        scales = np.zeros(R, np.float32) if self.config.normalize else None
+        check(_lib.lib().mis_encodec_encode_frame(self._h, a.ctypes.data, None if m is None else m.ctypes.data, R, L, nq, codes.ctypes.data,
+                                                  None if scales is None else scales.ctypes.data))
+        return codes, scales
+
+    def encode(self, input_values, padding_mask=None, bandwidth: float | None = None):
+        """encode (Encodec.swift:248-291): input_values [B, L, channels] (or [B, L]) -> (codes int32 [chunks, B, n_q, frames], scales:
+        one float32 [B] per chunk, or None without config.normalize).  Chunks are independent, so all of them go through one device pass."""
+        cfg = self.config
+        bw = cfg.target_bandwidths[0] if bandwidth is None else bandwidth
+        if bw not in cfg.target_bandwidths:
+            raise AudioGenerationError(3, f"This model doesn't support bandwidth {bw}. Select one of {list(cfg.target_bandwidths)}")
+        x = np.asarray(input_values, np.float32)
+        if x.ndim == 2:
+            x = x[:, :, None]
+        if x.ndim != 3:
+            raise AudioGenerationError(3, "input_values must be [batch, samples, channels]")
+        B, L, ch = x.shape
+        if not 1 <= ch <= 2:
+            raise AudioGenerationError(3, f"Number of audio channels must be 1 or 2, but got {ch}")
+        chunk_len = cfg.chunk_length if cfg.chunk_length is not None else L
+        stride = cfg.chunk_stride if cfg.chunk_stride is not None else L
+        mask = np.ones((B, L), bool) if padding_mask is None else np.asarray(padding_mask).astype(bool)
+        step = chunk_len - stride
+        offsets, offset = [], 0
+        while offset < L - step:
+            offsets.append(offset)
+            offset += stride
+        if not offsets:
+            raise AudioGenerationError(3, "input shorter than one chunk step")
+        lens = {min(L, o + chunk_len) - o for o in offsets}
+        if len(lens) != 1:                                                    # stacked(encodedFrames) needs equal frame counts
+            raise AudioGenerationError(3, "chunks of unequal length: pad the input with preprocess_encodec_audio")
+        n = lens.pop()
+        rows = np.stack([x[:, o:o + n] for o in offsets]).reshape(len(offsets) * B, n, ch)
+        masks = np.stack([mask[:, o:o + n] for o in offsets]).reshape(len(offsets) * B, n)
+        codes, scales = self.encode_rows(rows, masks, cfg.num_quantizers_for_bandwidth(bw))
+        codes = codes.reshape(len(offsets), B, codes.shape[1], codes.shape[2])
+        return codes, [None if scales is None else scales[i * B:(i + 1) * B].copy() for i in range(len(offsets))]
+
+    def encode_audio(self, waveform) -> EncodecEncodedAudio:
+        """AudioCodecModel.encodeAudio (Encodec.swift:457-460)"""
+        codes, scales = self.encode(waveform)
+        return EncodecEncodedAudio(codes, scales)
+
+    def decode_audio(self, encoded: EncodecEncodedAudio) -> np.ndarray:
+        """AudioCodecModel.decodeAudio (Encodec.swift:462-464)"""
+        return self.decode(encoded.codes, encoded.scales)
+
+    def reconstruct(self, waveform) -> np.ndarray:
+        """AudioCodecModel.reconstruct: decode_audio(encode_audio(waveform)), cut to the input's length"""
+        n = np.asarray(waveform).shape[1]
+        return self.decode_audio(self.encode_audio(waveform))[..., :n]
+
+    def encode_tap(self, rows, stage: int, masks=None) -> np.ndarray:
+        """Stage output of the encode chain on rows [R, L, channels] -> [R, C, T'] (mis_debug_encodec_encode_tap)"""
+        a = np.ascontiguousarray(np.transpose(np.asarray(rows, np.float32), (0, 2, 1)))
+        R, ch, L = a.shape
+        m = None if masks is None else np.ascontiguousarray(np.asarray(masks).astype(np.uint8))
+        cap = R * max(self.config.num_filters << len(self.config.upsampling_ratios), self.config.hidden_size, ch) * (L + 8)
+        buf = np.zeros(cap, np.float32)
+        cch = C.c_int32(); ln = C.c_int64()
+        check(_lib.lib().mis_debug_encodec_encode_tap(self._h, a.ctypes.data, None if m is None else m.ctypes.data, R, L, 0, stage,
+                                                      buf.ctypes.data, cap, None, C.byref(cch), C.byref(ln)))
+        return buf[: R * cch.value * ln.value].reshape(R, cch.value, ln.value).copy()
+
+    def rvq_tap(self, embeddings, n_q: int):
+        """ONE launch of the residual-VQ search on embeddings [R, D, F] -> (codes int32 [R, n_q, F], residuals float32 [n_q + 1, R, D, F])"""
+        e = np.ascontiguousarray(embeddings, dtype=np.float32)
+        R, D, F = e.shape
+        if D != self.config.codebook_dim:
+            raise AudioGenerationError(3, "embeddings must be [rows, codebook_dim, frames]")
+        codes = np.zeros((R, n_q, F), np.int32)
+        res = np.zeros((n_q + 1, R, D, F), np.float32)
+        cch = C.c_int32(); ln = C.c_int64()
+        check(_lib.lib().mis_debug_encodec_encode_tap(self._h, e.ctypes.data, None, R, F, n_q, -1, res.ctypes.data, res.size, codes.ctypes.data,
+                                                      C.byref(cch), C.byref(ln)))
+        return codes, res
 
     def decode_frame(self, codes, scale=None) -> np.ndarray:
         """decodeFrame (Encodec.swift:295-302): codes int [B, n_q, T] -> [B, T * hop] (mono) or [B, channels, T * hop]"""

@@ -75,6 +75,7 @@ struct GemmParams {
                           // whatever batch it shares); float32 slabs summed in slice order by a second launch that applies the epilogue
     int taps, dil;        // TAPS: dense conv, K = taps*Cin, tap j reads x[:, n - pad + j*dil] (zero outside); A^T row j*Cin + c;
                           // pad = (taps-1)*dil: causal, (taps-1)*dil/2: "same"; optional R (+scale) residual epilogue
+    int two_level;        // TAPS on the exact-f32 kernel: blocked summation, one partial sum per staged chunk of 16 channels x taps
 };
 // the kernel launch_gemm launched last on this thread (host bookkeeping only, as g_gemm_last_launch of lm_kernels.h): mis_debug_codec_gemm
 // reports it, so that tests/test_gpu_codec_ops.py can assert which kernel family a case reached.

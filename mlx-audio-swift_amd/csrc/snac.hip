@@ -565,10 +565,13 @@ __global__ void k_vq_residual(float* __restrict__ r, const int32_t* __restrict__
 // float4 loads, Snake applied on the way in) and every tap reads it from LDS at a column offset, so x is fetched once instead
 // of `taps` times and never with scalar loads; the `taps` weight tiles of the chunk are staged together (2 barriers per chunk
 // for taps*16 MFMA steps).  A^T row (j*Cin + c), as for the other modes.
+// TWO_LEVEL (GemmParams.two_level): every chunk's taps*16 products are summed into a zeroed accumulator of their own, which is then
+// added to the running sum - a blocked float32 summation whose rounding error grows with sqrt(chunks) + sqrt(chunk) instead of
+// sqrt(K).  For contractions whose result feeds a discrete decision (the EnCodec encoder in front of its codebook search: K = 7 * 512).
 #define CT_XS 224                     // staged columns per row: G_BN + halo (<= 92) + alignment slack (<= 3)
 #define CT_MAXT 7
 #define CT_BK 16                      // input channels per staged chunk (7 tap tiles of 16 x 64 + the halo tile: 43 KB of LDS)
-template <bool RESID>
+template <bool RESID, bool TWO_LEVEL = false>
 __device__ __forceinline__ void conv_taps_body(const GemmParams& p, const float* __restrict__ pX, const float* __restrict__ pR,
                                                float* __restrict__ pY, const float* __restrict__ pbias, const float* __restrict__ pscale) {
     __shared__ float As[CT_MAXT][CT_BK][G_BM];
@@ -643,6 +646,29 @@ __device__ __forceinline__ void conv_taps_body(const GemmParams& p, const float*
         }
         __syncthreads();
         if (cc + 1 < nchunks) load_chunk((cc + 1) * CT_BK);
+        if constexpr (TWO_LEVEL) {
+            f32x16_t part[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) part[t][r] = 0.0f;
+            for (int j = 0; j < p.taps; ++j) {
+                const int xo = off + j * p.dil + wn * 64 + (lane & 31);
+#pragma unroll
+                for (int kk = 0; kk < CT_BK; kk += 2) {
+                    float a = As[j][kk + (lane >> 5)][wm * 32 + (lane & 31)];
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        float bv = Xs[kk + (lane >> 5)][xo + t * 32];
+                        part[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, part[t], 0, 0, 0);
+                    }
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] += part[t][r];
+        } else {
         for (int j = 0; j < p.taps; ++j) {
             const int xo = off + j * p.dil + wn * 64 + (lane & 31);
 #pragma unroll
@@ -654,6 +680,7 @@ __device__ __forceinline__ void conv_taps_body(const GemmParams& p, const float*
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc[t], 0, 0, 0);
                 }
             }
+        }
         }
     }
 #pragma unroll
@@ -672,8 +699,8 @@ __device__ __forceinline__ void conv_taps_body(const GemmParams& p, const float*
         }
     }
 }
-template <bool RESID>
-__global__ void __launch_bounds__(256) k_conv_taps(GemmParams p) { conv_taps_body<RESID>(p, p.X, p.R, p.Y, p.bias, p.scale); }
+template <bool RESID, bool TWO_LEVEL = false>
+__global__ void __launch_bounds__(256) k_conv_taps(GemmParams p) { conv_taps_body<RESID, TWO_LEVEL>(p, p.X, p.R, p.Y, p.bias, p.scale); }
 
 // ---- final Snake -> conv k7 (C -> 1) -> tanh ----------------------------------------------------------
 #define FIN_TILE 256
@@ -1206,7 +1233,9 @@ void launch_gemm(int mode, bool snake, const GemmParams& p_in, int batch, hipStr
         GemmParams q = p;
         if (!snake) { q.alpha = nullptr; q.ralpha = nullptr; }
         g_codec_last_launch = CodecLaunchInfo{1, p.taps, 0, 0, 0, 0};
-        if (q.R) hipLaunchKernelGGL((k_conv_taps<true>), grid, block, 0, s, q);
+        if (q.two_level && q.R) hipLaunchKernelGGL((k_conv_taps<true, true>), grid, block, 0, s, q);
+        else if (q.two_level) hipLaunchKernelGGL((k_conv_taps<false, true>), grid, block, 0, s, q);
+        else if (q.R) hipLaunchKernelGGL((k_conv_taps<true>), grid, block, 0, s, q);
         else hipLaunchKernelGGL((k_conv_taps<false>), grid, block, 0, s, q);
     }
     else if (mode == GEMM_NOISE) hipLaunchKernelGGL((k_snac_gemm<GEMM_NOISE, false>), grid, block, 0, s, p);

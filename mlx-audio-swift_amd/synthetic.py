@@ -392,3 +392,24 @@ def mimi_synthetic_weights(cfg, seed: int = 77) -> dict:
         mult //= 2
     conv("decoder.final_conv1d.conv.conv", 1, cfg.last_kernel_size, nf)
     return W
+
+
+def encodec_synthetic_weights(cfg, seed: int = 909) -> dict:
+    """cfg: codecs.EncodecConfig.  Every tensor of a full EnCodec checkpoint (encoder, decoder, codebooks) in key order: variance-
+    preserving uniform conv / LSTM weights, bias U(+-0.05), GroupNorm weight 1 + U(+-0.3), codebooks of unit variance over the sum of
+    all quantizers."""
+    from .codecs import encodec_expected_shapes
+    W, key = {}, seed * 100000
+    for name, shape in encodec_expected_shapes(cfg).items():
+        key += 1
+        if name.endswith("codebook.embed"):
+            W[name] = synth_tensor(key, shape, math.sqrt(3.0 / cfg.num_quantizers))
+        elif name.endswith(".conv.weight"):
+            W[name] = synth_tensor(key, shape, math.sqrt(3.0 / (shape[1] * shape[2])))
+        elif name.endswith((".Wx", ".Wh")):
+            W[name] = synth_tensor(key, shape, math.sqrt(3.0 / shape[1]))
+        elif name.endswith(".norm.weight"):
+            W[name] = (1.0 + synth_tensor(key, shape, 0.3)).astype(np.float32)
+        else:
+            W[name] = synth_tensor(key, shape, 0.05)
+    return W
