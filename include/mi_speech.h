@@ -1046,6 +1046,72 @@ mis_status mis_fsmn_vad_detect_raw(mis_fsmn_vad*, const float* pcm, const int64_
 mis_status mis_fsmn_vad_tap(mis_fsmn_vad*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * SenseVoice speech-to-text (Sources/MLXAudioSTT/Models/SenseVoice/SenseVoiceModel.swift, SenseVoiceAudio.swift; DSP.swift melFilters /
+ * hammingWindow / hanningWindow): a non-autoregressive CTC recogniser that also returns the language, emotion and audio event of a
+ * clip.  Mono rows of differing lengths at the model's sample rate, 1..max_batch a call.  Row b of n_b samples has F_b = 1 + (n_b - win)
+ * / hop fbank frames (0 below one window) and T_b = 4 + ceil(F_b / lfr_n) sequence rows; a row without frames is its four query rows.
+ * Front end: x 32768 iff the row's own max |x| <= 1, minus the frame mean, pre-emphasis 0.97 (first sample x0 - 0.97 x0), symmetric
+ * Hamming (Hann when window_hann), 512-point power spectrum over 257 bins, unnormalised HTK triangles from 20 Hz, log max(., 1e-10).
+ * Sequence row 0 embed[lid], rows 1, 2 embed[1], embed[2], row 3 embed[textnorm], row r >= 4 the fbank frames
+ * clamp((r - 4) lfr_n + i - (lfr_m - 1) / 2, 0, F_b - 1), i < lfr_m, then (x + shift) scale when cmvn.shift / cmvn.scale are loaded; all of
+ * it x sqrt(output_size) + the sinusoid of position r + 1.  Encoder: L = 1 + max(num_blocks - 1, 0) + tp_blocks SAN-M layers
+ * {LayerNorm, linear_q_k_v, attention over the row's own T_b keys, linear_out + v + depthwise_conv(v) [+ residual, not in layer 0],
+ * LayerNorm, w_2(relu(w_1)), + residual}, after_norm behind the first stack, tp_norm at the end; head ctc_lo.  All of it exact f32.
+ * The workspace is sized once, at finalize, from max_batch, max_seconds and head_rows; a call allocates nothing and generate
+ * synchronises once.  A row's result does not depend on the batch it travels in or on what lies behind lens[b]: bit for bit.
+ * Rejected with MIS_ERR_INVALID_INPUT at create: a head size above 128, kernel_size above 32, n_mels above 128, input_size !=
+ * n_mels x lfr_m, a window outside 257..512 samples (the next power of two must be 512), sizes outside the ranges the messages name;
+ * at finalize a tensor missing or misshapen; at a call batch outside 1..max_batch, a row longer than stride or than max_seconds (rows are
+ * never truncated), query ids outside 0..15, a null pointer, a handle that is not finalized.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_sensevoice mis_sensevoice;
+/* SenseVoiceConfig + SenseVoiceEncoderConfig + SenseVoiceFrontendConfig; window_hann: the window's name contains "hann"; max_batch /
+ * max_seconds size the workspace, head_rows the logits scratch of forward (frames a chunk) */
+typedef struct {
+    int32_t vocab_size, input_size, output_size, attention_heads, linear_units, num_blocks, tp_blocks, kernel_size, sanm_shift, normalize_before;
+    int32_t sample_rate, n_mels, frame_length, frame_shift, lfr_m, lfr_n, window_hann;
+    int32_t max_batch, max_seconds, head_rows;
+} mis_sensevoice_config;
+mis_status mis_sensevoice_create(const mis_sensevoice_config*, int device, mis_sensevoice** out);
+/* names as SenseVoiceModel.sanitize leaves them: embed.weight [16, input_size]; encoder.{encoders0.0, encoders.N, tp_encoders.N}.
+ * {self_attn.linear_q_k_v, self_attn.linear_out, feed_forward.w_1, feed_forward.w_2, norm1, norm2}.{weight,bias} and
+ * .self_attn.fsmn_block.weight [output_size, kernel_size, 1] (the torch layout [output_size, 1, kernel_size] holds the same values in the
+ * same order and is taken as well); encoder.after_norm / encoder.tp_norm.{weight,bias}; ctc_lo.{weight,bias}; optional cmvn.shift /
+ * cmvn.scale of input_size values; host pointers.  finalize names a missing weight and checks every shape. */
+mis_status mis_sensevoice_set_tensor(mis_sensevoice*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_sensevoice_init_synthetic(mis_sensevoice*, uint64_t seed);
+mis_status mis_sensevoice_finalize(mis_sensevoice*);
+void       mis_sensevoice_destroy(mis_sensevoice*);
+/* kernel launches of the last call: generate 7 + 5 L (peak, fbank, intake, five a layer - LayerNorm + linear_q_k_v; attention; linear_out
+ * + memory block + residual; LayerNorm + w_1 + ReLU; w_2 + residual - after_norm, tp_norm, head + arg-max, decode); forward 5 + 5 L + 2 per
+ * chunk of head_rows; forward_features 3 + 5 L + 2 per chunk; features 3 */
+int        mis_sensevoice_launches(const mis_sensevoice*);
+/* F_b and T_b of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_sensevoice_frames(const mis_sensevoice*, const int64_t* lens, int batch, int32_t* frames_out, int32_t* rows_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> the LFR + CMVN features extractFeatures returns, f32 [batch, rows, input_size];
+ * rows >= max(1, the longest row's T_b - 4), zeros behind a row's own */
+mis_status mis_sensevoice_features(mis_sensevoice*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* features_out, int rows);
+/* callAsFunction on given features f32 [batch, rows, input_size], counts[batch] valid rows each (NULL = rows); lid / textnorm: rows of
+ * the embedding (language 0 auto, 3 zh, 4 en, 7 yue, 11 ja, 12 ko, 13 nospeech; 14 with ITN, 15 without) -> log-probabilities f32
+ * [batch, 4 + rows, vocab_size], zeros behind a row's own.  Walks the (row, frame) space in chunks of head_rows frames. */
+mis_status mis_sensevoice_forward_features(mis_sensevoice*, const float* features, const int32_t* counts, int batch, int rows, int lid, int textnorm,
+                                           float* logp_out);
+/* front end + callAsFunction: log-probabilities f32 [batch, Tmax, vocab_size], Tmax the longest row's T_b */
+mis_status mis_sensevoice_forward(mis_sensevoice*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int lid, int textnorm,
+                                  float* logp_out);
+/* generate for a ragged batch.  The head's epilogue reduces every 64-column tile to (max, lowest index attaining it) per frame - no
+ * logit reaches memory - and one kernel combines the tiles in tile order (ties to the lower index), reads frames 0, 1, 2 as the
+ * language, emotion and event ids (rich_out int32 [batch, 3]) and collapses frames 4.. : a token is kept when it differs from the
+ * previous frame's and is not blank 0.  tokens_out int32 [batch, tokens_stride] and n_tokens[batch] are the caller's; a row's ids behind
+ * tokens_stride are dropped (Tmax - 4 always suffices).  One synchronisation per call. */
+mis_status mis_stt_sensevoice_generate(mis_sensevoice*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int lid, int textnorm,
+                                       int32_t* tokens_out, int64_t tokens_stride, int32_t* n_tokens, int32_t* rich_out);
+/* tensors of the last call, f32, zeros behind a row's own rows.  stage 0 fbank [B, Fmax, n_mels] (a call from pcm), 1 the intake
+ * [B, Tmax, input_size], 2 + i the stages of the encoder in the order they run, [B, Tmax, output_size]: the layers of the first stack,
+ * after_norm, the tp layers, tp_norm (stages 2 .. 3 + L).  dims[3] receives B, rows, width; out NULL for the dims alone. */
+mis_status mis_sensevoice_tap(mis_sensevoice*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Silero voice activity detection (Sources/MLXAudioVAD/Models/SileroVAD/SileroVAD.swift): mono rows of differing lengths at 16 kHz or
  * 8 kHz (two branches with their own weights), 1..max_batch a call, of ANY length -> one speech probability per chunk of chunk_size
  * samples (32 ms).  Row b of n_b samples has ceil(n_b / chunk_size) chunks; chunk j's window is samples [j chunk - context, (j + 1) chunk)

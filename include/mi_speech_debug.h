@@ -407,6 +407,24 @@ mis_status mis_debug_lasr_timing(mis_lasr* c, float* ms);
  * fbank), encoder (+ copy out) */
 mis_status mis_debug_fsmn_vad_timing(const mis_fsmn_vad* c, float* ms);
 
+/* csrc/sensevoice.hip, measurements: device milliseconds of the last generate / forward, ms[3] = front end (copy in + peak + fbank +
+ * intake; 0 for forward_features), encoder, head (generate: the fused head + arg-max and the decode; forward: the head GEMM +
+ * log-softmax summed over its first 64 chunks, copies excluded) */
+mis_status mis_debug_sensevoice_timing(const mis_sensevoice* c, float* ms);
+/* csrc/sensevoice.hip, tests (tests/test_gpu_sensevoice.py): ONE launch each on host data; inputs are followed by NaN (counts: 0x7FFFFFFF)
+ * and every poisoned output lies between guard bands, as for the other operator entry points.
+ *   sensevoice_attn: k_sv_attn<1 | 2 | 4> (hd <= 32 | 64 | 128).  qkv [batch Tp][ld]: q of head h at column h hd, k at koff + h hd, v at
+ *     voff + h hd; cnt [batch] keys (= queries) of each row; q is multiplied by `scale` at the load.  out [batch Tp][ldo].
+ *   sensevoice_head_argmax: k_sv_gemm<SV_ARGMAX> on X [batch Tp][K], W [N][K], bias [N] or NULL, cnt [batch] -> pmax_out / pidx_out
+ *     [batch Tp][ceil(N / 64)]: per frame and 64-column tile the maximum and the lowest column attaining it (frames behind cnt stay
+ *     0xFFFFFFFF).  A second launch, k_sv_decode, then combines what the first wrote: pred_out [batch Tp], tokens_out [batch Tp],
+ *     ntok_out [batch], rich_out [batch 3] as mis_stt_sensevoice_generate forms them. */
+mis_status mis_debug_sensevoice_attn(int device, const float* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads,
+                                     int hd, float scale, int ldo, float* out);
+mis_status mis_debug_sensevoice_head_argmax(int device, const float* X, const float* W, const float* bias, const int32_t* cnt, int batch, int Tp,
+                                            int K, int N, float* pmax_out, int32_t* pidx_out, int32_t* pred_out, int32_t* tokens_out,
+                                            int32_t* ntok_out, int32_t* rich_out);
+
 /* csrc/silero_vad.hip, measurements: device milliseconds of the last call summed over its first 64 passes, ms[2] = front end (copy in +
  * the six contractions), recurrence */
 mis_status mis_debug_silero_vad_timing(const mis_silero_vad* c, float* ms);

@@ -58,6 +58,9 @@ from .lid import (EcapaTdnnLID, EcapaTdnnConfig, LanguagePrediction, LIDOutput, 
                   ecapa_lid_expected_shapes, ecapa_lid_labels, ecapa_lid_read_directory)
 from .lasr import (LasrCTCModel, LasrCTCConfig, LasrEncoderConfig, SentencePieceTokenizer, lasr_sanitize, lasr_expected_keys,  # noqa: F401
                    greedy_ctc_tokens)
+from .sensevoice import (SenseVoiceModel, SenseVoiceConfig, SenseVoiceEncoderConfig, SenseVoiceFrontendConfig,  # noqa: F401
+                         SenseVoiceTokenizer, sensevoice_sanitize, sensevoice_expected_keys, sensevoice_expected_shapes,
+                         sensevoice_check_weights, sensevoice_layer_prefixes, sensevoice_read_directory, read_sentencepiece_pieces)
 from .vad import (FSMNVAD, FSMNVADConfig, FSMNVADEncoderConfig, fsmn_vad_sanitize, fsmn_vad_expected_shapes,  # noqa: F401
                   fsmn_vad_check_weights, fsmn_vad_read_directory, fsmn_vad_read_cmvn, fsmn_vad_postprocess, parse_kaldi_cmvn,
                   chunks_from_segments, merge_runs, SileroVAD, SileroVADConfig, SileroVADBranchConfig, SileroVADError,

@@ -168,6 +168,12 @@ class FsmnVadConfigC(C.Structure):
                 + [("sil_pdf_ids", C.c_int32 * 16), ("max_batch", C.c_int32), ("chunk_frames", C.c_int32)])
 
 
+class SenseVoiceConfigC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "input_size", "output_size", "attention_heads", "linear_units", "num_blocks", "tp_blocks",
+                                         "kernel_size", "sanm_shift", "normalize_before", "sample_rate", "n_mels", "frame_length", "frame_shift",
+                                         "lfr_m", "lfr_n", "window_hann", "max_batch", "max_seconds", "head_rows")]
+
+
 class SileroVadBranchConfigC(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sample_rate", "filter_length", "hop_length", "pad", "cutoff", "context_size", "chunk_size")]
 
@@ -376,6 +382,18 @@ SYMBOLS = {
     "mis_fsmn_vad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
     "mis_fsmn_vad_detect_raw": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int, _P, C.c_int]),
     "mis_fsmn_vad_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_sensevoice_create": (C.c_int, [C.POINTER(SenseVoiceConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_sensevoice_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_sensevoice_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_sensevoice_finalize": (C.c_int, [_P]),
+    "mis_sensevoice_destroy": (None, [_P]),
+    "mis_sensevoice_launches": (C.c_int, [_P]),
+    "mis_sensevoice_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_sensevoice_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, C.c_int]),
+    "mis_sensevoice_forward_features": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_sensevoice_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
+    "mis_stt_sensevoice_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "mis_sensevoice_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_silero_vad_create": (C.c_int, [C.POINTER(SileroVadConfigC), C.c_int, C.POINTER(_P)]),
     "mis_silero_vad_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_silero_vad_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -613,6 +631,9 @@ DEBUG_SYMBOLS = {
     "mis_debug_lasr_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, _P]),
     "mis_debug_lasr_collapse": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "mis_debug_fsmn_vad_timing": (C.c_int, [_P, _P]),
+    "mis_debug_sensevoice_timing": (C.c_int, [_P, _P]),
+    "mis_debug_sensevoice_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "mis_debug_sensevoice_head_argmax": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "mis_debug_silero_vad_timing": (C.c_int, [_P, _P]),
     "mis_debug_mossformer2_timing": (C.c_int, [_P, _P]),
     "mis_debug_deepfilternet_timing": (C.c_int, [_P, _P]),

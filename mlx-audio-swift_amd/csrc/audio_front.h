@@ -1,5 +1,5 @@
 // audio_front.h - what the filter-bank front ends share.  Host tables of the 512-point FFT front ends (lasr.hip, sortformer.hip,
-// fsmn_vad.hip) and of mossformer2.hip: the twiddles and each filter's range of non-zero bins.  And the whole NeMo log-mel front end of
+// fsmn_vad.hip, sensevoice.hip) and of mossformer2.hip: the twiddles and each filter's range of non-zero bins.  And the whole NeMo log-mel front end of
 // lasr.hip and sortformer.hip, which is ONE front end: the Hann window of 400 in 512, the slaney filters, the log-mel kernel and the
 // per-feature normalisation (below, behind AUDIO_FRONT_NEMO_KERNELS).  The engines promise results that are bit for bit independent of
 // the batch, and their kernels read these tables, so they are formed in one place; tests/test_gpu_front_bits.py holds the engines'

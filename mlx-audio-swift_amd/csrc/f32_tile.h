@@ -1,4 +1,4 @@
-// f32_tile.h - what the exact-f32 contractions of the f32 audio engines (ecapa_lid.hip, fsmn_vad.hip, mossformer2.hip, sortformer.hip)
+// f32_tile.h - what the exact-f32 contractions of the f32 audio engines (ecapa_lid.hip, fsmn_vad.hip, sensevoice.hip, mossformer2.hip, sortformer.hip)
 // share: device code only.  A block of 256 threads (four waves) forms a tile of C = A B^T on v_mfma_f32_32x32x2_f32, K staged F32_KC
 // at a time through As[rows][F32_KC + 1] / Bs[cols][F32_KC + 1] in LDS.  An engine keeps what differs: its parameter struct, its
 // staging loops with their operand loads, and its epilogue arithmetic.
