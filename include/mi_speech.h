@@ -1400,6 +1400,56 @@ mis_status mis_sortformer_encode_embeddings(mis_sortformer*, const float* emb, c
 mis_status mis_sortformer_tap(mis_sortformer*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * Parakeet TDT speech-to-text (csrc/parakeet.hip; Sources/MLXAudioSTT/Models/Parakeet/ParakeetModel.swift, ParakeetConformer.swift,
+ * Sources/MLXAudioSTT/Models/Nemo/): 16 kHz mono rows of differing lengths, 1..max_batch a call.  Row b of n_b samples has F_b =
+ * 1 + n_b / 160 log-mel frames (Sortformer's front end without the peak normalisation; normalize: per-feature) and T_b = the three-fold
+ * floor((L - 1) / 2) + 1 of F_b encoder frames behind Sortformer's stem and FastConformer blocks (head sizes up to 128: up to 64 its own
+ * attention kernel, 65..128 k_pk_attn), keys limited to the row's own T_b.  joint.enc is applied to every frame by one GEMM; the greedy
+ * TDT loop of a row (token and duration arg-max, ties to the lower index; a blank leaves the LSTM state; NemoDecodingLogic.tdtStep's
+ * advance, with max_symbols emissions a frame) runs in one block of ONE launch.  All of it exact f32; bf16 / f16 tensors are widened at
+ * set_tensor.  A row's encoder output, tokens, frames and durations do not depend on the batch it travels in or on what lies behind
+ * lens[b]: bit for bit.  The workspace is sized once, at finalize; a call allocates nothing and synchronises once.
+ * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: sampling_rate / n_fft / hop_length / win_length 16000 / 512 /
+ * 160 / 400; num_mel_bins 8..256; subsampling_factor 8; subsampling_conv_channels 1..1024; hidden_size 8..4096; the head size a whole
+ * number up to 128; intermediate_size 1..16384; num_hidden_layers 1..64; conv_kernel_size odd, 3..31; pred_rnn_layers 2; pred_hidden and
+ * joint_hidden 1..1024; vocab_size 1..65535; num_durations 1..8, each 0..64; max_symbols 1..64; max_batch 1..64; max_seconds 1..120;
+ * max_tokens (the output capacity of a row) 1..65536.  A rejected call leaves the handle usable.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_parakeet mis_parakeet;
+typedef struct {
+    int32_t hidden_size, num_hidden_layers, num_attention_heads, intermediate_size, num_mel_bins, conv_kernel_size, subsampling_factor,
+            subsampling_conv_channels, attention_bias, scale_input;
+    int32_t pred_hidden, pred_rnn_layers, joint_hidden, vocab_size, num_durations, max_symbols, durations[8];
+    int32_t sampling_rate, hop_length, n_fft, win_length, normalize;
+    int32_t max_batch, max_seconds, max_tokens;
+    float   preemphasis;
+} mis_parakeet_config;
+mis_status mis_parakeet_create(const mis_parakeet_config*, int device, mis_parakeet** out);
+/* names: encoder.subsampling.* and encoder.layers.N.* as Sortformer's fc_encoder.* (attention_bias 0: no Linear / Conv1d bias anywhere in
+ * a block); decoder.prediction.embed.weight [vocab + 1, pred_hidden] (the blank's row is never read: a blank feeds zeros);
+ * decoder.prediction.dec_rnn.lstm.{weight_ih,weight_hh,bias_ih,bias_hh}_l{0,1} (torch.nn.LSTM: gates i, f, g, o; both biases added);
+ * joint.{enc,pred}.{weight,bias}; joint.joint_net.{weight,bias} [vocab + 1 + num_durations, joint_hidden]; host pointers */
+mis_status mis_parakeet_set_tensor(mis_parakeet*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_parakeet_init_synthetic(mis_parakeet*, uint64_t seed);
+mis_status mis_parakeet_finalize(mis_parakeet*);
+void       mis_parakeet_destroy(mis_parakeet*);
+/* kernel launches of the last call, L = num_hidden_layers: generate 9 + 15 L = 2 (front end) + 4 (stem) + 1 (intake) + 15 L (Sortformer's
+ * block chain) + 1 (joint.enc) + 1 (decode); encode 7 + 15 L */
+int        mis_parakeet_launches(const mis_parakeet*);
+/* F_b and T_b of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_parakeet_frames(const mis_parakeet*, const int64_t* lens, int batch, int32_t* F_out, int32_t* T_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> the encoder's output f32 [batch, Tmax, hidden_size], zero rows behind T_b */
+mis_status mis_parakeet_encode(mis_parakeet*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* out);
+/* -> per row: tokens / frames / durations int32 [batch, max_tokens] (the first counts[b] entries of a row are written: token id, the
+ * encoder frame it was emitted at, the duration chosen with it), counts[batch], flags[batch] (1: the row stopped at max_tokens),
+ * steps[batch] (joint evaluations; may be NULL).  One synchronisation per call. */
+mis_status mis_parakeet_generate(mis_parakeet*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int32_t* tokens, int32_t* frames,
+                                 int32_t* durations, int32_t* counts, int32_t* flags, int32_t* steps);
+/* tensors of the last encode / generate, f32, zero rows behind T_b: stage 0 the stem's embeddings [B, T, hidden_size], 1..L that Conformer
+ * block, L + 1 joint.enc of the last block [B, T, joint_hidden].  dims[3] receives B, T, width; out NULL for the dims alone. */
+mis_status mis_parakeet_tap(mis_parakeet*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

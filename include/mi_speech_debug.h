@@ -318,6 +318,21 @@ mis_status mis_debug_sortformer_glu_dwconv(int device, const float* pw, const fl
                                            int k, float* out);
 mis_status mis_debug_sortformer_peak(int device, const float* pcm, int64_t stride, const int32_t* N, int batch, int on, float* scale_out);
 
+/* csrc/parakeet.hip: ONE launch of a new kernel on caller-supplied host data, and the device intervals of a generate.
+ *   parakeet_attn: k_pk_attn, head sizes 65..128; arguments as mis_debug_sortformer_attn with rel = 1 (qkv [batch Tp][ld], cnt [batch],
+ *     u, v [heads][hd], P [2 Tcap - 1][ldp] the projected table by distance); out [batch Tp][heads hd]; guards as there.
+ *   parakeet_tdt: k_pk_tdt on projected frames encp [batch][Tp][J] (joint.enc applied), cnt [batch], and the decoder's tensors as a
+ *     checkpoint holds them: embed [vocab + 1][P], wih / whh [2] x [4 P][P], bih / bhh [2] x [4 P], wp [J][P], bp [J], wo [vocab + 1 + D][J],
+ *     bo; outputs tokens / frames / durs [batch][cap] (entries behind a row's count: -1), counts / flags / steps [batch].
+ *   parakeet_timing: ms NULL arms the events; then ms[3] = front end, stem + blocks + joint.enc, decode of the last mis_parakeet_generate. */
+mis_status mis_debug_parakeet_attn(int device, const float* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads, int hd,
+                                   float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int Tcap, int ldo, float* out);
+mis_status mis_debug_parakeet_tdt(int device, const float* encp, const int32_t* cnt, int batch, int Tp, int J, int P, int vocab, int D,
+                                  const int32_t* durations, int max_symbols, int cap, const float* embed, const float* const* wih, const float* const* whh,
+                                  const float* const* bih, const float* const* bhh, const float* wp, const float* bp, const float* wo, const float* bo,
+                                  int32_t* tokens, int32_t* frames, int32_t* durs, int32_t* counts, int32_t* flags, int32_t* steps);
+mis_status mis_debug_parakeet_timing(mis_parakeet*, float* ms);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -22,6 +22,7 @@ the Swift shim a maintainer would add):
     vad.FSMNVAD              <-> class FSMNVAD (voice activity detection)  (MLXAudioVAD/Models/FSMNVAD/FSMNVAD.swift)
     vad.SileroVAD            <-> class SileroVAD (voice activity detection) (MLXAudioVAD/Models/SileroVAD/SileroVAD.swift)
     vad.segment_speech       <-> func segmentSpeech (VAD -> STT chunker)    (MLXAudioVAD/SpeechSegmenter.swift)
+    parakeet.ParakeetModel <-> class ParakeetModel (TDT speech-to-text)  (MLXAudioSTT/Models/Parakeet/ParakeetModel.swift)
     sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
     sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     sts.DeepFilterNet        <-> class DeepFilterNetModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/DeepFilterNet)
@@ -73,6 +74,8 @@ from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSMod
                   deepfilternet_synthetic_weights, compute_norm_alpha, libdf_erb_band_widths, DeepFilterNetStreamingConfig,
                   DeepFilterNetStreamer, deepfilternet_enhance_streaming, deepfilternet_stream_chunks,
                   deepfilternet_stream_check_served)
+from .parakeet import (ParakeetModel, ParakeetConfig, ParakeetResult, ParakeetToken, parakeet_sanitize,  # noqa: F401
+                       parakeet_expected_keys)
 from .sortformer import (SortformerModel, SortformerConfig, FCEncoderConfig, TFEncoderConfig, ModulesConfig, ProcessorConfig,  # noqa: F401
                          DiarizationSegment, DiarizationOutput, StreamingState, sortformer_sanitize, sortformer_expected_keys,
                          preds_to_segments, trim_silence, maybe_compress_state)
