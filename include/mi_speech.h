@@ -1450,6 +1450,60 @@ mis_status mis_parakeet_generate(mis_parakeet*, const float* pcm, const int64_t*
 mis_status mis_parakeet_tap(mis_parakeet*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * Nemotron ASR speech-to-text, offline (csrc/nemotron.hip; Sources/MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift decode,
+ * NemotronASRConformer.swift, Sources/MLXAudioSTT/Models/Nemo/): the cache-aware FastConformer + RNN-T recogniser.  16 kHz mono rows of
+ * differing lengths, 1..max_batch a call.  Row b of n_b samples has F_b = 1 + n_b / 160 log-mel frames and T_b = the three-fold
+ * floor(n / 2) + 1 of F_b encoder frames behind the CAUSAL stem (pad (2, 1) in time and frequency).  A block is Parakeet's with two
+ * differences: attention follows the chunked-limited rule of the call's context (left, right) - query q sees key k iff
+ * 0 <= q / C - k / C <= L, C = right + 1, L = left / C, left < 0 unlimited - walking only the key tiles the rule lets a query tile see and a
+ * projected distance table of the rows -(C - 1) .. L C + C - 1 alone, so nothing but the walk grows with T; and the conv module pads
+ * (conv_pad_left, conv_pad_right) and normalises with a LayerNorm over channels.  The prompt kernel (prompt_hidden > 0) conditions every
+ * frame on the row's own language index; joint.enc is one GEMM; the greedy RNN-T loop of a row (ties to the lower index; a blank
+ * leaves the LSTM state and advances; NemoDecodingLogic.rnntStep's max_symbols rule, max_symbols 0: none) runs in one block of ONE
+ * launch.  All of it exact f32.  A row's encoder output, tokens and frames do not depend on the batch it travels in or on what lies
+ * behind lens[b]: bit for bit.  The workspace is sized once, at finalize; a call allocates nothing and synchronises once.
+ * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: as Parakeet's, but the head size 65..128; conv_kernel_size
+ * 2..31 with conv_pad_left + conv_pad_right = conv_kernel_size - 1; 1..8 contexts, right >= 0 (att_context_style regular: one context
+ * (0, 2^30), a single chunk); num_prompts 1..4096 and prompt_hidden 1..16384, or both 0; pred_rnn_layers 1 or 2; max_symbols 0..64;
+ * max_seconds 1..1200.  A call's context must lie inside the distances the listed contexts cover.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_nemotron mis_nemotron;
+typedef struct {
+    int32_t hidden_size, num_hidden_layers, num_attention_heads, intermediate_size, num_mel_bins, conv_kernel_size, subsampling_factor,
+            subsampling_conv_channels, attention_bias, scale_input;
+    int32_t conv_pad_left, conv_pad_right, num_contexts, att_context[8][2], num_prompts, prompt_hidden;
+    int32_t pred_hidden, pred_rnn_layers, joint_hidden, vocab_size, max_symbols;
+    int32_t sampling_rate, hop_length, n_fft, win_length, normalize;
+    int32_t max_batch, max_seconds, max_tokens;
+    float   preemphasis;
+} mis_nemotron_config;
+mis_status mis_nemotron_create(const mis_nemotron_config*, int device, mis_nemotron** out);
+/* names: encoder.subsampling.*, encoder.layers.N.* as Parakeet's, with conv.norm.{weight,bias} a LayerNorm and (attention_bias)
+ * conv.depthwise_conv.bias; prompt_kernel.linear0.{weight,bias} [prompt_hidden, hidden_size + num_prompts], prompt_kernel.linear2
+ * [hidden_size, prompt_hidden]; decoder.prediction.embed.weight [vocab + 1, pred_hidden]; decoder.prediction.dec_rnn.lstm.* per layer;
+ * joint.{enc,pred}.{weight,bias}; joint.joint_net.{weight,bias} [vocab + 1, joint_hidden]; host pointers */
+mis_status mis_nemotron_set_tensor(mis_nemotron*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_nemotron_init_synthetic(mis_nemotron*, uint64_t seed);
+mis_status mis_nemotron_finalize(mis_nemotron*);
+void       mis_nemotron_destroy(mis_nemotron*);
+/* kernel launches of the last call, L = num_hidden_layers, p = 1 with a prompt kernel: generate 9 + 15 L + 2 p = 2 (front end) + 4 (stem)
+ * + 1 (intake) + 15 L + 2 p + 1 (joint.enc) + 1 (decode); encode 7 + 15 L */
+int        mis_nemotron_launches(const mis_nemotron*);
+/* F_b and T_b of rows of lens[b] samples (either output may be NULL) */
+mis_status mis_nemotron_frames(const mis_nemotron*, const int64_t* lens, int batch, int32_t* F_out, int32_t* T_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride), the context -> the encoder's output f32 [batch, Tmax, hidden_size] */
+mis_status mis_nemotron_encode(mis_nemotron*, const float* pcm, const int64_t* lens, int batch, int64_t stride, int left, int right, float* out);
+/* langs[batch]: the rows' prompt indices (NULL: 0; ignored without a prompt kernel) -> per row: tokens / frames int32 [batch, max_tokens]
+ * (the first counts[b] entries of a row are written: token id, the encoder frame it was emitted at), counts[batch], flags[batch] (1: the
+ * row stopped at max_tokens), steps[batch] (joint evaluations; may be NULL).  One synchronisation per call. */
+mis_status mis_nemotron_generate(mis_nemotron*, const float* pcm, const int64_t* lens, const int32_t* langs, int batch, int64_t stride, int left, int right,
+                                 int32_t* tokens, int32_t* frames, int32_t* counts, int32_t* flags, int32_t* steps);
+/* tensors of the last encode / generate, f32, zero rows behind T_b: stage 0 the stem's embeddings [B, T, hidden_size], 1..L that Conformer
+ * block, L + 1 the prompt kernel's output (without one: block L), L + 2 joint.enc of it [B, T, joint_hidden].  dims[3] receives B, T,
+ * width; out NULL for the dims alone. */
+mis_status mis_nemotron_tap(mis_nemotron*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous
  * blocks (mis_shard_rows), every replica runs its block on its own worker thread through the single-device entry point - with

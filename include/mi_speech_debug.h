@@ -333,6 +333,30 @@ mis_status mis_debug_parakeet_tdt(int device, const float* encp, const int32_t* 
                                   int32_t* tokens, int32_t* frames, int32_t* durs, int32_t* counts, int32_t* flags, int32_t* steps);
 mis_status mis_debug_parakeet_timing(mis_parakeet*, float* ms);
 
+/* csrc/nemotron.hip: ONE launch of a new kernel on caller-supplied host data (inputs followed by NaNs, outputs guarded), and the device
+ * intervals of a generate.
+ *   nemotron_attn: k_nm_attn as parakeet_attn, under the context (left, right) of a model of Tcap frames; P [prow][ldp] holds the
+ *     distances -poff .. prow - 1 - poff and must cover -(C - 1) .. min(L C + C - 1, Tcap - 1).  repeat > 1 and ms_out: the mean device
+ *     milliseconds of `repeat` further launches (benches).
+ *   nemotron_dwconv_ln: k_nm_glu_dwconv_ln, pw [batch Tp][2 C], taps [k][C], bias [C] or NULL, padl zero frames before the row ->
+ *     out [batch Tp][C] (before the LayerNorm), stats [batch Tp][2] = mean, rstd over the C channels.
+ *   nemotron_stem: stage 0 k_nm_conv0 on x [batch][Tin][Fin]; stage 1 the pad-(2, 1) depthwise operand load + pointwise conv + ReLU on
+ *     x [batch][Tin][Fin][C]; w9 [9][C], b9 [C], pw [C][C], pwb [C]; out [batch][Tin / 2 + 1][Fin / 2 + 1][C].
+ *   nemotron_rnnt: k_nm_rnnt as parakeet_tdt without durations; wih / whh / bih / bhh [layers]; wo [vocab + 1][J]; max_symbols 0: none.
+ *   nemotron_timing: as parakeet_timing. */
+mis_status mis_debug_nemotron_attn(int device, const float* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads, int hd,
+                                   float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int prow, int poff, int left, int right,
+                                   int Tcap, int ldo, float* out, int repeat, float* ms_out);
+mis_status mis_debug_nemotron_dwconv_ln(int device, const float* pw, const float* taps, const float* bias, const int32_t* cnt, int batch, int Tp, int C, int k,
+                                        int padl, float* out, float* stats);
+mis_status mis_debug_nemotron_stem(int device, int stage, const float* x, const int32_t* cnt_in, int batch, int Tin, int Fin, int C, const float* w9,
+                                   const float* b9, const float* pw, const float* pwb, float* out);
+mis_status mis_debug_nemotron_rnnt(int device, const float* encp, const int32_t* cnt, int batch, int Tp, int J, int P, int vocab, int layers, int max_symbols,
+                                   int cap, const float* embed, const float* const* wih, const float* const* whh, const float* const* bih,
+                                   const float* const* bhh, const float* wp, const float* bp, const float* wo, const float* bo, int32_t* tokens,
+                                   int32_t* frames, int32_t* counts, int32_t* flags, int32_t* steps);
+mis_status mis_debug_nemotron_timing(mis_nemotron*, float* ms);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

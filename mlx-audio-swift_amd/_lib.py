@@ -235,6 +235,16 @@ class ParakeetConfigC(C.Structure):
                 + [("preemphasis", C.c_float)])
 
 
+class NemotronConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "num_mel_bins",
+                                          "conv_kernel_size", "subsampling_factor", "subsampling_conv_channels", "attention_bias", "scale_input",
+                                          "conv_pad_left", "conv_pad_right", "num_contexts")]
+                + [("att_context", (C.c_int32 * 2) * 8)]
+                + [(n, C.c_int32) for n in ("num_prompts", "prompt_hidden", "pred_hidden", "pred_rnn_layers", "joint_hidden", "vocab_size", "max_symbols",
+                                            "sampling_rate", "hop_length", "n_fft", "win_length", "normalize", "max_batch", "max_seconds", "max_tokens")]
+                + [("preemphasis", C.c_float)])
+
+
 class SttParamsC(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64), ("eot_id", C.c_int32),
                 ("timestamp_begin", C.c_int32), ("suppress", C.c_void_p), ("n_suppress", C.c_int32),
@@ -485,6 +495,16 @@ SYMBOLS = {
     "mis_parakeet_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
     "mis_parakeet_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "mis_parakeet_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_nemotron_create": (C.c_int, [C.POINTER(NemotronConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_nemotron_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_nemotron_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_nemotron_finalize": (C.c_int, [_P]),
+    "mis_nemotron_destroy": (None, [_P]),
+    "mis_nemotron_launches": (C.c_int, [_P]),
+    "mis_nemotron_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_nemotron_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P]),
+    "mis_nemotron_generate": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_nemotron_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_whisper_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, C.c_int, C.POINTER(SttParamsC),
                                              C.POINTER(_P), C.POINTER(C.c_int64), _P]),
     "mis_soprano_group_generate": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.POINTER(GenParamsC), C.POINTER(_P), C.POINTER(C.c_int64),
@@ -676,6 +696,13 @@ DEBUG_SYMBOLS = {
     "mis_debug_parakeet_tdt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "mis_debug_parakeet_timing": (C.c_int, [_P, _P]),
+    "mis_debug_nemotron_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "mis_debug_nemotron_dwconv_ln": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_nemotron_stem": (C.c_int, [C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_debug_nemotron_rnnt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _P, _P, _P]),
+    "mis_debug_nemotron_timing": (C.c_int, [_P, _P]),
     "mis_debug_encodec_encode_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int64)]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),
