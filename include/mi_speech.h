@@ -1503,6 +1503,47 @@ mis_status mis_nemotron_generate(mis_nemotron*, const float* pcm, const int64_t*
  * width; out NULL for the dims alone. */
 mis_status mis_nemotron_tap(mis_nemotron*, int stage, float* out, int64_t capacity, int64_t* dims);
 
+/* Nemotron ASR, the cache-aware stream session (csrc/nemotron_stream.hip; NemotronASRStreaming.swift streamEncodeChunks,
+ * NemotronASRStreamSession.swift step / finish): 1..64 streams on one finalized model, with a workspace and a state of their own (feeds and
+ * offline calls may interleave; the model outlives its sessions).  Yardstick: after any split of a stream's samples into feeds, the encoder
+ * frames, the prompt kernel's output, the joint.enc rows, the tokens and their ABSOLUTE frame indices are those of mis_nemotron_encode /
+ * _generate on the whole audio at the same (left, right), bit for bit, whatever the slot and whatever the other streams do.
+ *   State, on the device per stream: per block a ring of the projected K and V addressed by absolute frame % R (R = left + the pass
+ *   capacity + 32, rounded up to 32) and the last conv_kernel_size - 1 gated frames of the conv module; 16 mel frames; the decoder's proposal
+ *   (h', c' per LSTM layer, joint.pred of it), the token count and the capacity flag.  On the host: the stream's sample tail (at most n_fft +
+ *   one chunk + one feed samples) and its counters.
+ *   A chunk is C = right + 1 encoder frames = 8 C mel frames.  Mid-stream only frozen mel frames are used (m hop + n_fft / 2 <= samples
+ *   seen), each computed once, and only whole chunks run; final[b] flushes the rest and ends the stream (the offline right pad).  A feed is
+ *   walked in passes of at most max_pass_frames / C chunks a stream; a stream without a whole chunk does no work and keeps its state.  A
+ *   feed allocates nothing and synchronises once (a feed of more than 8 passes waits for the device every 8).
+ * Rejected with MIS_ERR_INVALID_INPUT at create: streams outside 1..64; normalize per_feature (requires NA mel normalization); left < 0 or
+ * left % (right + 1) != 0; a context outside the distances of the listed contexts; a conv pad that is not causal; max_pass_frames below C. */
+typedef struct mis_nemotron_stream mis_nemotron_stream;
+mis_status mis_nemotron_stream_create(mis_nemotron*, int streams, int left, int right, int max_pass_frames, mis_nemotron_stream** out);
+void       mis_nemotron_stream_destroy(mis_nemotron_stream*);
+/* stream 0..streams-1, or -1 for all: zero state, counters 0, the prompt index of its next utterance; the other streams are untouched */
+mis_status mis_nemotron_stream_reset(mis_nemotron_stream*, int stream, int lang);
+/* pcm f32 [streams, stride], stream b brings n[b] >= 0 samples and final[b] (final NULL: none) -> the NEW tokens / absolute encoder frames
+ * int32 [streams, out_stride], counts[streams], flags[streams] (1: the stream reached max_tokens and ignores further frames).  out_stride
+ * >= max_tokens always suffices. */
+mis_status mis_nemotron_stream_feed(mis_nemotron_stream*, const float* pcm, const int64_t* n, const int32_t* final, int64_t stride, int32_t* tokens,
+                                    int32_t* frames, int64_t out_stride, int32_t* counts, int32_t* flags);
+/* kernel launches of the last feed: passes x (9 + 16 L + 2 p) = 1 (mel) + 4 (stem) + 1 (intake) + 16 L (the offline block's 15 + the ring
+ * put) + 2 p (prompt kernel) + 1 (joint.enc) + 1 (decode) + 1 (mel cache); 0 when no stream had a whole chunk */
+int        mis_nemotron_stream_launches(const mis_nemotron_stream*);
+/* the session's frame bookkeeping as a pure function (no device; a feed runs exactly this per stream): the passes a stream runs once it
+ * has seen `seen` samples (final: all of it) at chunk_frames = right + 1 and max_chunks = max_pass_frames / chunk_frames, from state[3] =
+ * mel frames consumed, encoder frames emitted, mel frames cached (zeros: a fresh stream; advanced).  passes[2 i], passes[2 i + 1] = the
+ * first absolute encoder frame and the frame count of pass i (the first max_passes are written), *n_passes = how many there are.  A feed
+ * runs max over its streams of n_passes passes. */
+mis_status mis_nemotron_stream_plan(int64_t seen, int final, int chunk_frames, int max_chunks, int32_t* state, int32_t* passes, int max_passes,
+                                    int32_t* n_passes);
+/* encoder frames a stream has emitted since create or its last reset (-1: bad argument) */
+int64_t    mis_nemotron_stream_frames_seen(const mis_nemotron_stream*, int stream);
+/* the frames the last feed brought, stages as mis_nemotron_tap's: out f32 [streams, kept, width], counts[streams].  The first call (out
+ * NULL, capacity = frames a stream may bring in one feed) allocates and turns the taps on; dims[3] receives streams, kept, width. */
+mis_status mis_nemotron_stream_tap(mis_nemotron_stream*, int stage, float* out, int64_t capacity, int64_t* dims, int32_t* counts);
+
 /* ------------------------------------------------------------------------------------------
  * Device groups for the other families ("Whisper (30 s chunks), Soprano (sentence prompts) and Qwen3-TTS rows shard the
  * same way").  replicas[n]: one finalized handle per GPU holding the same weights.  The rows of the call are split into n contiguous

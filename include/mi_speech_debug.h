@@ -357,6 +357,23 @@ mis_status mis_debug_nemotron_rnnt(int device, const float* encp, const int32_t*
                                    int32_t* frames, int32_t* counts, int32_t* flags, int32_t* steps);
 mis_status mis_debug_nemotron_timing(mis_nemotron*, float* ms);
 
+/* csrc/nemotron_stream.hip: ONE launch of a stream kernel on caller-supplied host data, and the device time of the last feed.
+ *   nemotron_attn_stream: k_nm_attn_stream; q [streams][Tp][heads hd] holds cnt[b] queries at the absolute frames pos[b] .., ring
+ *     [streams][R][2 heads hd] the projected k | v of frame f in row f % R (R % 32 == 0, R >= left + Tp + 32; the queries' own frames
+ *     included); the table as nemotron_attn's; left % (right + 1) == 0.  repeat / ms_out as nemotron_attn's.
+ *   nemotron_rnnt_stream: k_nm_rnnt_stream on a pass of cnt[b] frames at pos[b] .., resumed from and stored back to state
+ *     [streams][4 P + J] and ist [streams][4] = started, tokens, flag, joint evaluations (zeros: a fresh stream); the pass's tokens /
+ *     frames land in [streams][cap] at index (token count - tok0[b]).
+ *   nemotron_stream_timing: device milliseconds of the last feed, copies included. */
+mis_status mis_debug_nemotron_attn_stream(int device, const float* q, const float* ring, int R, const int32_t* cnt, const int32_t* pos, int streams, int Tp,
+                                          int heads, int hd, float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int prow,
+                                          int poff, int left, int right, float* out, int repeat, float* ms_out);
+mis_status mis_debug_nemotron_rnnt_stream(int device, const float* encp, const int32_t* cnt, const int32_t* pos, const int32_t* tok0, int streams, int Tp, int J,
+                                          int P, int vocab, int layers, int max_symbols, int cap, const float* embed, const float* const* wih,
+                                          const float* const* whh, const float* const* bih, const float* const* bhh, const float* wp, const float* bp,
+                                          const float* wo, const float* bo, float* state, int32_t* ist, int32_t* tokens, int32_t* frames);
+mis_status mis_debug_nemotron_stream_timing(mis_nemotron_stream*, float* ms);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -24,6 +24,7 @@ the Swift shim a maintainer would add):
     vad.segment_speech       <-> func segmentSpeech (VAD -> STT chunker)    (MLXAudioVAD/SpeechSegmenter.swift)
     parakeet.ParakeetModel <-> class ParakeetModel (TDT speech-to-text)  (MLXAudioSTT/Models/Parakeet/ParakeetModel.swift)
     nemotron.NemotronASR   <-> class NemotronASRModel (RNN-T speech-to-text, offline)  (MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift)
+    nemotron.NemotronStreamSession <-> class NemotronASRStreamSession (cache-aware streaming)  (.../NemotronASR/NemotronASRStreamSession.swift)
     sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
     sts.MossFormer2SE        <-> class MossFormer2SEModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/MossFormer2SE)
     sts.DeepFilterNet        <-> class DeepFilterNetModel : STSModel (speech enhancement)  (MLXAudioSTS/Models/DeepFilterNet)
@@ -77,7 +78,8 @@ from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSMod
                   deepfilternet_stream_check_served)
 from .parakeet import (ParakeetModel, ParakeetConfig, ParakeetResult, ParakeetToken, parakeet_sanitize,  # noqa: F401
                        parakeet_expected_keys)
-from .nemotron import NemotronASR, NemotronConfig, nemotron_sanitize, nemotron_expected_keys  # noqa: F401
+from .nemotron import (NemotronASR, NemotronConfig, NemotronStreamSession, Delta, StreamFrames, chunk_context, nemo_tokens_to_sentences,  # noqa: F401
+                       nemotron_sanitize, nemotron_expected_keys)
 from .sortformer import (SortformerModel, SortformerConfig, FCEncoderConfig, TFEncoderConfig, ModulesConfig, ProcessorConfig,  # noqa: F401
                          DiarizationSegment, DiarizationOutput, StreamingState, sortformer_sanitize, sortformer_expected_keys,
                          preds_to_segments, trim_silence, maybe_compress_state)

@@ -1,11 +1,12 @@
-"""Nemotron ASR speech-to-text (offline), host mirror of `NemotronASRModel` (Sources/MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift,
+"""Nemotron ASR speech-to-text (offline, and the cache-aware stream session), host mirror of `NemotronASRModel` (Sources/MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift,
 NemotronASRConfig.swift, NemotronASRTokenizer.swift): the cache-aware FastConformer + RNN-T recogniser.  Configuration, checkpoint key
 handling, the language -> prompt index resolution, the piece list and the token times stay on the host; the log-mel front end, the causal
 stem, the chunked-limited FastConformer encoder, the prompt kernel, the joint's enc projection and the whole greedy RNN-T loop run in
-libmi_speech.so (csrc/nemotron.hip).
+libmi_speech.so (csrc/nemotron.hip; the stream session NemotronStreamSession: csrc/nemotron_stream.hip).
 
 Refused, not approximated: quantised checkpoints, conv_norm_type other than layer_norm, att_context_style other than chunked_limited /
-regular, non-causal downsampling, beam search, the cache-aware stream session and rows beyond max_seconds."""
+regular, non-causal downsampling, beam search, rows beyond max_seconds; by the stream session also per_feature normalisation, a left context that is
+no multiple of right + 1 and a conv pad that is not causal."""
 from __future__ import annotations
 
 import ctypes as C
@@ -378,7 +379,226 @@ class NemotronASR(NativeHandle):
                 yield at + i, r
 
     def stream_session(self, *args, **kwargs):
-        """NemotronASRStreamSession (carried attention and conv caches) is not built."""
+        """Not a method of the offline class: the cache-aware session is its own class, NemotronStreamSession (make_stream_session), as
+        DeepFilterNetStreamer is; this name keeps refusing."""
         raise _bad("the cache-aware stream session is not implemented (offline decode only)")
 
     create_stream_session = stream_session
+
+    def make_stream_session(self, language=None, chunk_ms=None, streams: int = 1, att_context_size=None) -> "NemotronStreamSession":
+        """makeStreamSession"""
+        return NemotronStreamSession(self, streams, language, att_context_size, chunk_ms)
+
+    def transcribe_streaming(self, audio, language=None, chunk_ms: int = 480, on_delta=None) -> ParakeetResult:
+        """transcribeStreaming: the audio through a session at the model's native chunk, fed chunk_ms at a time as a live caller would;
+        on_delta receives every non-empty new fragment."""
+        wave = np.asarray(audio, np.float32)
+        wave = wave.mean(axis=-1, dtype=np.float32) if wave.ndim > 1 else wave
+        chunk = max(1, self.config.sampling_rate * chunk_ms // 1000)
+        s = self.make_stream_session(language)
+        start = time.perf_counter()
+        for at in list(range(0, len(wave), chunk)) + [None]:
+            delta = s.finish() if at is None else s.step(wave[at: at + chunk])
+            if delta.text and on_delta is not None:
+                on_delta(delta.text)
+        out = ParakeetResult(s.text.strip(), list(s.tokens), False, time.perf_counter() - start)
+        s.close()
+        return out
+
+
+@dataclass
+class Delta:
+    """NemotronASRStreamSession.Delta: what one step / finish decoded"""
+    text: str = ""
+    token_ids: list = field(default_factory=list)
+
+
+def chunk_context(chunk_ms, default_context):
+    """makeStreamSession's rounding on the 80 ms encoder frame: chunk_frames = max(1, round(chunk_ms / 80)), right = chunk_frames - 1, left
+    from the default context (80 -> (56, 0), 160 -> (56, 1), 320 -> (56, 3), 560 -> (56, 6), 1120 -> (56, 13)); None: the default context"""
+    if chunk_ms is None:
+        return tuple(default_context)
+    return int(default_context[0]), max(1, int(np.floor(chunk_ms / 80.0 + 0.5))) - 1
+
+
+def nemo_tokens_to_sentences(tokens) -> list:
+    """NemoAlignment.tokensToSentences + sentencesToResult(...).segments: a sentence closes behind a token that holds ! ? or their CJK forms,
+    or a . that ends the tokens or is followed by a token holding a space -> [dict(text, start, end)]"""
+    out, cur = [], []
+
+    def close():
+        by_start = sorted(cur, key=lambda t: t.start)
+        out.append(dict(text="".join(t.text for t in cur), start=by_start[0].start, end=by_start[-1].start + by_start[-1].duration))
+        cur.clear()
+
+    for i, t in enumerate(tokens):
+        cur.append(t)
+        if any(c in t.text for c in "!?。？！") or ("." in t.text and (i == len(tokens) - 1 or " " in tokens[i + 1].text)):
+            close()
+    if cur:
+        close()
+    return out
+
+
+@dataclass
+class StreamFrames:
+    """The frame bookkeeping of one stream: the pure function the device session itself runs per stream and pass (mis_nemotron_stream_plan
+    in csrc/nemotron_stream.hip: streamEncodeChunks + frozenMelFrames, with up to max_chunks whole chunks a pass).  Needs no device."""
+    chunk: int                                                            # C = right + 1 encoder frames
+    max_chunks: int = 1
+    consumed: int = 0                                                     # mel frames
+    emitted: int = 0                                                      # encoder frames
+    cache: int = 0                                                        # mel frames carried in front of the next window
+
+    def advance(self, seen: int, final: bool) -> list:
+        """-> the passes [(first absolute encoder frame, count)] that `seen` samples (final: all of the stream) let run"""
+        state, n = (C.c_int32 * 3)(self.consumed, self.emitted, self.cache), C.c_int32(0)
+        room = 2 + (1 + seen // 160) // (8 * self.chunk)
+        passes = (C.c_int32 * (2 * room))()
+        check(_lib.lib().mis_nemotron_stream_plan(seen, int(bool(final)), self.chunk, self.max_chunks, state, passes, room, C.byref(n)))
+        self.consumed, self.emitted, self.cache = (int(v) for v in state)
+        return [(int(passes[2 * i]), int(passes[2 * i + 1])) for i in range(n.value)]
+
+
+class NemotronStreamSession:
+    """NemotronASRStreamSession for 1..64 concurrent streams on one model (csrc/nemotron_stream.hip): step / step_batch feed samples and
+    return what they decoded, finish flushes a stream's tail; the transcript equals the offline generate of the whole audio at the same
+    context, token for token and frame for frame.  att_context_size / chunk_ms choose the context (chunk_context); left must be a multiple
+    of right + 1.  text / tokens / segments / is_finished speak of stream 0, as the reference's one-stream session; sentences(stream), raw(stream)
+    of any."""
+    _h = None
+
+    def __init__(self, model: NemotronASR, streams: int = 1, language=None, att_context_size=None, chunk_ms=None, max_pass_frames=None):
+        self.model, self.streams = model, int(streams)
+        if att_context_size is not None and chunk_ms is not None:
+            raise _bad("att_context_size and chunk_ms both choose the context: give one")
+        self.context = model._context(att_context_size) if att_context_size is not None else chunk_context(chunk_ms, model.config.default_context)
+        left, right = (int(v) for v in self.context)
+        mp, h, cap = int(max_pass_frames or 3 * (right + 1)), C.c_void_p(), model.config.max_tokens
+        check(_lib.lib().mis_nemotron_stream_create(model._h, self.streams, left, right, mp, C.byref(h)))
+        self._h, self._plan = h, (right + 1, max(1, mp // (right + 1)))
+        self._out = [np.zeros((self.streams, cap), np.int32) for _ in range(2)]      # a feed's tokens and frames
+        self._passes = 0
+        langs = language if isinstance(language, (list, tuple)) else [language] * self.streams
+        self._state = [None] * self.streams
+        for b in range(self.streams):
+            self.reset(b, langs[b])
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            _lib.lib().mis_nemotron_stream_destroy(h)
+
+    __del__ = close
+
+    def reset(self, stream: int = 0, language=None):
+        """stream -1: all of them"""
+        check(_lib.lib().mis_nemotron_stream_reset(self._h, stream, self.model.resolve_prompt_index(language)))
+        for b in range(self.streams) if stream < 0 else [stream]:
+            self._state[b] = dict(ids=[], frames=[], tokens=[], text="", done=False, truncated=False, seen=0, plan=StreamFrames(*self._plan))
+
+    @property
+    def launches(self) -> int:
+        return int(_lib.lib().mis_nemotron_stream_launches(self._h))
+
+    @property
+    def expected_launches_per_pass(self) -> int:
+        return 9 + 16 * self.model.config.num_hidden_layers + (2 if self.model.config.prompt_hidden else 0)
+
+    @property
+    def expected_launches(self) -> int:
+        """of the last feed: passes x (9 + 16 L + 2 p); a feed runs as many passes as the stream that needs the most (StreamFrames)"""
+        return self._passes * self.expected_launches_per_pass
+
+    def frames_seen(self, stream: int = 0) -> int:
+        return int(_lib.lib().mis_nemotron_stream_frames_seen(self._h, stream))
+
+    def feed_raw(self, chunks, final=None):
+        """One device call: chunks[b] the samples of stream b (None / empty: nothing), final[b] ends it -> per stream (token ids, frames)"""
+        S, cap = self.streams, self.model.config.max_tokens
+        rows = [np.zeros(0, np.float32) if c is None else np.ascontiguousarray(c, np.float32).reshape(-1) for c in chunks]
+        if len(rows) != S:
+            raise _bad(f"{len(rows)} chunks for {S} streams")
+        stride = max(1, max(len(r) for r in rows))
+        pcm = np.zeros((S, stride), np.float32)
+        for b, r in enumerate(rows):
+            pcm[b, :len(r)] = r
+        n = np.asarray([len(r) for r in rows], np.int64)
+        fin = np.asarray([bool(f) for f in (final or [False] * S)], np.int32)
+        tok, frm = self._out
+        cnt, flg = (np.zeros(S, np.int32) for _ in range(2))
+        self._passes = 0
+        for b, st in enumerate(self._state):
+            if not st["done"]:
+                st["seen"] += int(n[b])
+                self._passes = max(self._passes, len(st["plan"].advance(st["seen"], bool(fin[b]))))
+        check(_lib.lib().mis_nemotron_stream_feed(self._h, pcm.ctypes.data, n.ctypes.data, fin.ctypes.data, stride, tok.ctypes.data, frm.ctypes.data, cap,
+                                                  cnt.ctypes.data, flg.ctypes.data))
+        for b in range(S):
+            self._state[b]["truncated"] = bool(flg[b])
+        return [(tok[b, :cnt[b]].copy(), frm[b, :cnt[b]].copy()) for b in range(S)]
+
+    def _delta(self, b, ids, frames) -> Delta:
+        """advance()'s tail: special tokens leave the text, not the decoder state; the delta is the text's new suffix"""
+        st, m, vocab, new = self._state[b], self.model, self.model.config.vocabulary, []
+        st["ids"] += [int(t) for t in ids]; st["frames"] += [int(f) for f in frames]
+        for t, f in zip(ids, frames):
+            piece = vocab[t] if t < len(vocab) else f"<{t}>"
+            if t < len(vocab) and _is_special(piece):
+                continue
+            new.append(ParakeetToken(int(t), piece.replace("▁", " "), m.frame_seconds(int(f)), m.frame_seconds(1)))
+        st["tokens"] += new
+        full = "".join(t.text for t in st["tokens"])
+        delta = full[len(st["text"]):] if full.startswith(st["text"]) else full
+        st["text"] = full
+        return Delta(delta, [t.id for t in new])
+
+    def step_batch(self, chunks, final=None) -> list:
+        final = list(final or [False] * self.streams)
+        live = [not self._state[b]["done"] for b in range(self.streams)]
+        raws = self.feed_raw([c if live[b] else None for b, c in enumerate(chunks)], [f and live[b] for b, f in enumerate(final)])
+        out = [self._delta(b, *raws[b]) if live[b] else Delta() for b in range(self.streams)]
+        for b, f in enumerate(final):
+            self._state[b]["done"] |= bool(f)
+        return out
+
+    def step(self, samples, stream: int = 0) -> Delta:
+        return self.step_batch([samples if b == stream else None for b in range(self.streams)])[stream]
+
+    def finish(self, stream: int = 0) -> Delta:
+        """Flushes the trailing partial chunk; a second finish returns an empty delta."""
+        if self._state[stream]["done"]:
+            return Delta()
+        return self.step_batch([None] * self.streams, [b == stream for b in range(self.streams)])[stream]
+
+    def enable_taps(self, frames: int):
+        dims = (C.c_int64 * 3)()
+        check(_lib.lib().mis_nemotron_stream_tap(self._h, 0, None, frames, dims, None))
+
+    def tap(self, stage: int) -> list:
+        """The frames the last feed brought, per stream [n_b, width]; stages as NemotronASR.tap's.  enable_taps() first."""
+        dims, cnt = (C.c_int64 * 3)(), np.zeros(self.streams, np.int32)
+        check(_lib.lib().mis_nemotron_stream_tap(self._h, stage, None, 0, dims, None))
+        out = np.zeros(tuple(int(d) for d in dims), np.float32)
+        check(_lib.lib().mis_nemotron_stream_tap(self._h, stage, out.ctypes.data, out.size, dims, cnt.ctypes.data))
+        return [out[b, :cnt[b]].copy() for b in range(self.streams)]
+
+    def timing(self) -> float:
+        """Device milliseconds of the last feed, copies included."""
+        ms = C.c_float()
+        check(_lib.lib().mis_debug_nemotron_stream_timing(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    text = property(lambda self: self._state[0]["text"])
+    tokens = property(lambda self: self._state[0]["tokens"])
+    is_finished = property(lambda self: self._state[0]["done"])
+    segments = property(lambda self: self.sentences(0))
+
+    def sentences(self, stream: int = 0) -> list:
+        """NemoAlignedResult.segments of what the stream has decoded: [dict(text, start, end)]"""
+        return nemo_tokens_to_sentences(self._state[stream]["tokens"])
+
+    def raw(self, stream: int = 0) -> dict:
+        """every token id (specials included) and its absolute encoder frame, as decode_raw's"""
+        st = self._state[stream]
+        return dict(tokens=np.asarray(st["ids"], np.int32), frames=np.asarray(st["frames"], np.int32), truncated=st["truncated"])
