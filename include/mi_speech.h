@@ -1450,6 +1450,57 @@ mis_status mis_parakeet_generate(mis_parakeet*, const float* pcm, const int64_t*
 mis_status mis_parakeet_tap(mis_parakeet*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------
+ * Canary speech-to-text and translation (csrc/canary.hip; Sources/MLXAudioSTT/Models/Canary/CanaryModel.swift, CanaryConfig.swift): the
+ * attention-encoder-decoder recogniser of the NeMo family.  The encoder is Parakeet's, field for field (scale_input = xscaling,
+ * attention_bias = use_bias, per-feature normalisation), followed by encoder.projection when hidden_size != enc_output_dim.  The decoder
+ * is a pre-LN Transformer of width h = enc_output_dim (self attention, cross attention over the row's own T_b encoder frames, ReLU FFN,
+ * a vocabulary head); dec_hidden_size must equal h.  Where the reference re-runs the whole prefix at every token, a step here costs one
+ * token: the cross-attention K | V of every layer are formed once per call over all frames, self-attention K | V are cached, the head is
+ * fused with the arg-max (ties to the lower index) and the token bookkeeping stays on the device - generate synchronises once per eight
+ * steps.  A step is one captured graph per batch size (MIS_NO_GRAPH=1: plain launches).  All of it exact f32; a row's encoder output and
+ * tokens do not depend on the batch it travels in or on what lies behind lens[b]: bit for bit.
+ * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: the encoder's as Parakeet's; enc_output_dim 8..4096; dec_layers
+ * 1..32; the decoder head size a whole number up to 128; dec_inner_size 1..16384; vocab_size 2..65536; max_tokens 1..4096; max_prompt
+ * 1..256; the cross K/V store max_batch x T(max_seconds) x dec_layers x 2 h floats at most 4 GiB (the message names max_seconds).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct mis_canary mis_canary;
+typedef struct {
+    int32_t hidden_size, num_hidden_layers, num_attention_heads, intermediate_size, num_mel_bins, conv_kernel_size, subsampling_factor,
+            subsampling_conv_channels, attention_bias, scale_input;                       /* the encoder, as mis_parakeet_config */
+    int32_t enc_output_dim, dec_layers, dec_hidden_size, dec_heads, dec_inner_size, vocab_size;
+    int32_t sampling_rate, hop_length, n_fft, win_length, normalize;
+    int32_t max_batch, max_seconds, max_tokens, max_prompt;
+    float   preemphasis;
+} mis_canary_config;
+mis_status mis_canary_create(const mis_canary_config*, int device, mis_canary** out);
+/* names: encoder.subsampling.* and encoder.layers.N.* as Parakeet's; encoder.projection.{weight,bias} [h, hidden_size] when the widths
+ * differ; decoder.embedding.weight [vocab, h]; decoder.embedding_layer_norm, decoder.final_norm, decoder.blocks.N.{self_attn_norm,
+ * cross_attn_norm,ff_norm}.{weight,bias}; decoder.blocks.N.{self_attn,cross_attn}.{q_proj,k_proj,v_proj,out_proj}.{weight,bias} [h, h];
+ * decoder.blocks.N.ff1 [inner, h], ff2 [h, inner]; decoder.output_proj [vocab, h]; host pointers */
+mis_status mis_canary_set_tensor(mis_canary*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
+mis_status mis_canary_init_synthetic(mis_canary*, uint64_t seed);
+mis_status mis_canary_finalize(mis_canary*);
+void       mis_canary_destroy(mis_canary*);
+/* kernel launches of the last call: encode 7 + 15 L_enc (+ 1 with a projection); generate that + L_dec (cross K/V) + 1 (the first input)
+ * + steps x (11 L_dec + 2), steps as generate returned them */
+int        mis_canary_launches(const mis_canary*);
+mis_status mis_canary_frames(const mis_canary*, const int64_t* lens, int batch, int32_t* F_out, int32_t* T_out);
+/* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> the encoder's output behind the projection f32 [batch, Tmax, h] */
+mis_status mis_canary_encode(mis_canary*, const float* pcm, const int64_t* lens, int batch, int64_t stride, float* out);
+/* prompt ids int32 [batch, Pmax] of which plen[b] >= 1 are row b's, fed teacher-forced; then greedy tokens until the arg-max is eos (not
+ * appended) or max_tokens were generated.  -> tokens int32 [batch, max_tokens] (the first counts[b] of a row are written), counts[batch],
+ * flags[batch] (1: the row did not end inside the step bound), *steps (decode steps enqueued; may be NULL). */
+mis_status mis_canary_generate(mis_canary*, const float* pcm, const int64_t* lens, int batch, int64_t stride, const int32_t* prompt, const int32_t* plen,
+                               int Pmax, int eos, int max_tokens, int32_t* tokens, int32_t* counts, int32_t* flags, int32_t* steps);
+/* the decoder teacher-forced over per-row prompts against the cross K/V of the last encode / generate: logits f32 [B, vocab] behind each
+ * row's last prompt token (the first decoded step) and, unless NULL, the hidden state [B, h] in front of final_norm at that step */
+mis_status mis_canary_forward(mis_canary*, const int32_t* prompt, const int32_t* plen, int Pmax, float* logits, float* hidden);
+/* tensors of the last encode / generate, f32, zero rows behind T_b: stage 0 the stem's embeddings [B, T, hidden_size], 1..L_enc that
+ * Conformer block, L_enc + 1 the encoder's output behind the projection [B, T, h], L_enc + 2 + l the cross K | V of decoder layer l
+ * [B, T, 2 h].  dims[3] receives B, T, width; out NULL for the dims alone. */
+mis_status mis_canary_tap(mis_canary*, int stage, float* out, int64_t capacity, int64_t* dims);
+
+/* ------------------------------------------------------------------------------------------
  * Nemotron ASR speech-to-text, offline (csrc/nemotron.hip; Sources/MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift decode,
  * NemotronASRConformer.swift, Sources/MLXAudioSTT/Models/Nemo/): the cache-aware FastConformer + RNN-T recogniser.  16 kHz mono rows of
  * differing lengths, 1..max_batch a call.  Row b of n_b samples has F_b = 1 + n_b / 160 log-mel frames and T_b = the three-fold

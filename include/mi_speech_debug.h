@@ -374,6 +374,21 @@ mis_status mis_debug_nemotron_rnnt_stream(int device, const float* encp, const i
                                           const float* wo, const float* bo, float* state, int32_t* ist, int32_t* tokens, int32_t* frames);
 mis_status mis_debug_nemotron_stream_timing(mis_nemotron_stream*, float* ms);
 
+/* csrc/canary.hip: the decode step's kernels on caller-supplied host data (every input followed by NaNs, every output guarded).
+ *   canary_lin: k_cn_lin with S forced by the caller.  X [Mrows, K] of which the first M (1..64) rows are live, W [N, K], bias [N] or NULL.
+ *     S = 1: ONE launch, bias and optional ReLU in the epilogue.  S = 2 / 4 / 8: the partial launch [S, M, N] and the k_cn_rows that
+ *     reduces it in ascending s onto x = 0 with the bias (no ReLU, N <= 4096).  out [M, N].
+ *   canary_attn_step: ONE launch of k_cn_attn_step.  q [B, heads hd], kv [B, cap, 2 heads hd] (K | V of a position side by side), cnt[B]
+ *     keys a row (1..cap), scale hd^-0.5 -> out [B, heads hd].
+ *   canary_head_argmax: ONE launch of k_cn_lin as the head runs it; the per-tile pairs are combined by k_cn_select's rule.  logits [M, V]
+ *     may be NULL (then no logit reaches memory); index [M]; value [M] may be NULL.
+ *   canary_timing: NULL arms it; else device milliseconds of the last generate: front end, stem + encoder + projection, cross K/V, steps. */
+mis_status mis_debug_canary_lin(int device, const float* X, int Mrows, int M, int K, int N, const float* W, const float* bias, int relu, int S, float* out);
+mis_status mis_debug_canary_attn_step(int device, const float* q, const float* kv, const int32_t* cnt, int batch, int cap, int heads, int hd, float* out);
+mis_status mis_debug_canary_head_argmax(int device, const float* xn, int M, int K, int V, const float* W, const float* bias, float* logits, int32_t* index,
+                                        float* value);
+mis_status mis_debug_canary_timing(mis_canary*, float* ms);
+
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,
  * streaming the handle's own packed weights; compiled for Soprano-80M's LM widths (other shapes: MIS_ERR_INVALID_INPUT).  The product
  * reaches it through mis_soprano_generate at batch 1; this entry point is for tests and measurements.

@@ -23,6 +23,7 @@ the Swift shim a maintainer would add):
     vad.SileroVAD            <-> class SileroVAD (voice activity detection) (MLXAudioVAD/Models/SileroVAD/SileroVAD.swift)
     vad.segment_speech       <-> func segmentSpeech (VAD -> STT chunker)    (MLXAudioVAD/SpeechSegmenter.swift)
     parakeet.ParakeetModel <-> class ParakeetModel (TDT speech-to-text)  (MLXAudioSTT/Models/Parakeet/ParakeetModel.swift)
+    canary.CanaryModel     <-> class CanaryModel (speech-to-text and translation)  (MLXAudioSTT/Models/Canary/CanaryModel.swift)
     nemotron.NemotronASR   <-> class NemotronASRModel (RNN-T speech-to-text, offline)  (MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift)
     nemotron.NemotronStreamSession <-> class NemotronASRStreamSession (cache-aware streaming)  (.../NemotronASR/NemotronASRStreamSession.swift)
     sortformer.SortformerModel <-> class SortformerModel (speaker diarization)  (MLXAudioVAD/Models/Sortformer/Sortformer.swift)
@@ -78,6 +79,8 @@ from .sts import (MossFormer2SE, MossFormer2SEConfig, MossFormer2SEError, STSMod
                   deepfilternet_stream_check_served)
 from .parakeet import (ParakeetModel, ParakeetConfig, ParakeetResult, ParakeetToken, parakeet_sanitize,  # noqa: F401
                        parakeet_expected_keys)
+from .canary import (CanaryModel, CanaryConfig, CanaryEncoderConfig, CanaryDecoderConfig, CanaryPreprocessConfig, CanaryTokenizer,  # noqa: F401
+                     canary_sanitize, canary_reference_keys, canary_expected_keys)
 from .nemotron import (NemotronASR, NemotronConfig, NemotronStreamSession, Delta, StreamFrames, chunk_context, nemo_tokens_to_sentences,  # noqa: F401
                        nemotron_sanitize, nemotron_expected_keys)
 from .sortformer import (SortformerModel, SortformerConfig, FCEncoderConfig, TFEncoderConfig, ModulesConfig, ProcessorConfig,  # noqa: F401

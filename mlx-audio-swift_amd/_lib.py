@@ -235,6 +235,15 @@ class ParakeetConfigC(C.Structure):
                 + [("preemphasis", C.c_float)])
 
 
+class CanaryConfigC(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "num_mel_bins",
+                                          "conv_kernel_size", "subsampling_factor", "subsampling_conv_channels", "attention_bias", "scale_input",
+                                          "enc_output_dim", "dec_layers", "dec_hidden_size", "dec_heads", "dec_inner_size", "vocab_size",
+                                          "sampling_rate", "hop_length", "n_fft", "win_length", "normalize", "max_batch", "max_seconds",
+                                          "max_tokens", "max_prompt")]
+                + [("preemphasis", C.c_float)])
+
+
 class NemotronConfigC(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size", "num_mel_bins",
                                           "conv_kernel_size", "subsampling_factor", "subsampling_conv_channels", "attention_bias", "scale_input",
@@ -495,6 +504,17 @@ SYMBOLS = {
     "mis_parakeet_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
     "mis_parakeet_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "mis_parakeet_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
+    "mis_canary_create": (C.c_int, [C.POINTER(CanaryConfigC), C.c_int, C.POINTER(_P)]),
+    "mis_canary_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "mis_canary_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_canary_finalize": (C.c_int, [_P]),
+    "mis_canary_destroy": (None, [_P]),
+    "mis_canary_launches": (C.c_int, [_P]),
+    "mis_canary_frames": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "mis_canary_encode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P]),
+    "mis_canary_generate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "mis_canary_forward": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+    "mis_canary_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_nemotron_create": (C.c_int, [C.POINTER(NemotronConfigC), C.c_int, C.POINTER(_P)]),
     "mis_nemotron_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_nemotron_init_synthetic": (C.c_int, [_P, C.c_uint64]),
@@ -704,6 +724,10 @@ DEBUG_SYMBOLS = {
     "mis_debug_parakeet_tdt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "mis_debug_parakeet_timing": (C.c_int, [_P, _P]),
+    "mis_debug_canary_lin": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "mis_debug_canary_attn_step": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "mis_debug_canary_head_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_debug_canary_timing": (C.c_int, [_P, _P]),
     "mis_debug_nemotron_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "mis_debug_nemotron_dwconv_ln": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
