@@ -1414,6 +1414,19 @@ mis_status mis_sortformer_tap(mis_sortformer*, int stage, float* out, int64_t ca
  * number up to 128; intermediate_size 1..16384; num_hidden_layers 1..64; conv_kernel_size odd, 3..31; pred_rnn_layers 2; pred_hidden and
  * joint_hidden 1..1024; vocab_size 1..65535; num_durations 1..8, each 0..64; max_symbols 1..64; max_batch 1..64; max_seconds 1..120;
  * max_tokens (the output capacity of a row) 1..65536.  A rejected call leaves the handle usable.
+ *
+ * bf16 encoder (opt-in, mis_parakeet_set_encoder_dtype / mis_canary_set_encoder_dtype with MIS_BF16 before finalize; csrc/
+ * parakeet_encoder_bf16.h).  The Conformer blocks run on v_mfma_f32_16x16x32_bf16; front end, stem, joint.enc and the decode stay f32, the
+ * launch counts do not change, and the f32 mode keeps its bits.  Precision contract.  f32: the residual stream, the LayerNorm statistics,
+ * biases, LayerNorm parameters, bias_u / bias_v, the folded depthwise taps, every accumulation, the softmax and every epilogue computation.
+ * Rounded to bf16, to nearest even, once, at each of these points: the eight block matrices (both feed-forward pairs, q | k | v, o, the two
+ * pointwise convolutions) and each layer's projected distance table (projected in f32, then rounded); the operand a contraction stages
+ * (LayerNorm(h) is formed in f32 and rounded as it is staged); the activations between the launches of a block, which are bf16 buffers in
+ * this mode; inside attention q + bias_u and q + bias_v (summed in f32, rounded once) and the probabilities in front of P V - the row sum
+ * adds the unrounded probabilities.  As in f32 mode a row's output is bit-identical whatever its batch or the padding behind lens[b]: tile
+ * shapes depend on the layer widths only, partial sums have one fixed order, no float atomics.  Resident encoder weights halve: the block
+ * matrices and tables exist on the device as bf16 only.  Requires hidden_size % 32 == 0 and intermediate_size % 32 == 0
+ * (MIS_ERR_INVALID_INPUT naming the field); any dtype but MIS_F32 / MIS_BF16 and a call after finalize are refused, the handle stays usable.
  * ---------------------------------------------------------------------------------------- */
 typedef struct mis_parakeet mis_parakeet;
 typedef struct {
@@ -1431,6 +1444,8 @@ mis_status mis_parakeet_create(const mis_parakeet_config*, int device, mis_parak
  * joint.{enc,pred}.{weight,bias}; joint.joint_net.{weight,bias} [vocab + 1 + num_durations, joint_hidden]; host pointers */
 mis_status mis_parakeet_set_tensor(mis_parakeet*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
 mis_status mis_parakeet_init_synthetic(mis_parakeet*, uint64_t seed);
+/* MIS_F32 (the default) or MIS_BF16: the encoder's Conformer blocks (the contract above); before finalize */
+mis_status mis_parakeet_set_encoder_dtype(mis_parakeet*, mis_dtype);
 mis_status mis_parakeet_finalize(mis_parakeet*);
 void       mis_parakeet_destroy(mis_parakeet*);
 /* kernel launches of the last call, L = num_hidden_layers: generate 9 + 15 L = 2 (front end) + 4 (stem) + 1 (intake) + 15 L (Sortformer's
@@ -1479,6 +1494,8 @@ mis_status mis_canary_create(const mis_canary_config*, int device, mis_canary** 
  * decoder.blocks.N.ff1 [inner, h], ff2 [h, inner]; decoder.output_proj [vocab, h]; host pointers */
 mis_status mis_canary_set_tensor(mis_canary*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
 mis_status mis_canary_init_synthetic(mis_canary*, uint64_t seed);
+/* MIS_F32 (the default) or MIS_BF16: the encoder's Conformer blocks, Parakeet's contract; the decoder is f32 in both modes; before finalize */
+mis_status mis_canary_set_encoder_dtype(mis_canary*, mis_dtype);
 mis_status mis_canary_finalize(mis_canary*);
 void       mis_canary_destroy(mis_canary*);
 /* kernel launches of the last call: encode 7 + 15 L_enc (+ 1 with a projection); generate that + L_dec (cross K/V) + 1 (the first input)

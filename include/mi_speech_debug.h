@@ -332,6 +332,22 @@ mis_status mis_debug_parakeet_tdt(int device, const float* encp, const int32_t* 
                                   const float* const* bih, const float* const* bhh, const float* wp, const float* bp, const float* wo, const float* bo,
                                   int32_t* tokens, int32_t* frames, int32_t* durs, int32_t* counts, int32_t* flags, int32_t* steps);
 mis_status mis_debug_parakeet_timing(mis_parakeet*, float* ms);
+/* csrc/parakeet_encoder_bf16.h: ONE launch of a kernel of the bf16 encoder on caller-supplied host data; every input is followed by NaNs
+ * (counts: 0x7FFFFFFF), the output is guarded.  bf16 tensors are raw bits.  With ms != NULL the same launch is then repeated `repeat` times
+ * between two events and *ms receives the milliseconds of one launch.
+ *   parakeet_gemm_bf16: k_pk_gemm_bf16.  load 0: x bf16 [batch Tp][K]; 1: x f32 through the LayerNorm prologue, stats [batch Tp][2] = mean,
+ *     rstd, lnw, lnb [K].  w bf16 [N][K], bias f32 [N] or NULL.  epi 0 none / 1 SiLU: out bf16 [batch Tp][N]; 2: out f32 = R + ra v, R f32
+ *     [batch Tp][N].  rule 0: 64 x 64 block tile, 1: 32 x 32.  K % 32 == 0, N % 8 == 0.  Rows behind cnt[b] come back zero.
+ *   parakeet_attn_bf16: k_pk_attn_bf16, head sizes 1..128; the arguments of parakeet_attn with bf16 qkv and table, out bf16.
+ *   parakeet_glu_dwconv_bf16: k_pk_glu_dwconv_bf16; pw bf16 [batch Tp][2 C], taps f32 [k][C], shift f32 [C] -> out bf16 [batch Tp][C]. */
+mis_status mis_debug_parakeet_gemm_bf16(int device, int load, int epi, int rule, const void* x, const float* stats, const float* lnw, const float* lnb,
+                                        const uint16_t* w, const float* bias, const float* R, float ra, const int32_t* cnt, int batch, int Tp, int K, int N,
+                                        void* out, int repeat, float* ms);
+mis_status mis_debug_parakeet_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads, int hd,
+                                        float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp, int Tcap, int ldo, uint16_t* out,
+                                        int repeat, float* ms);
+mis_status mis_debug_parakeet_glu_dwconv_bf16(int device, const uint16_t* pw, const float* taps, const float* shift, const int32_t* cnt, int batch, int Tp, int C,
+                                              int k, uint16_t* out);
 
 /* csrc/nemotron.hip: ONE launch of a new kernel on caller-supplied host data (inputs followed by NaNs, outputs guarded), and the device
  * intervals of a generate.

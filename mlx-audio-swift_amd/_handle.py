@@ -11,6 +11,7 @@ from . import _lib
 from .generation import AudioGenerationError, check
 
 _NP_DTYPES = {np.dtype(np.float32): _lib.MIS_F32, np.dtype(np.float16): _lib.MIS_F16}
+_ENCODER_DTYPES = {"float32": _lib.MIS_F32, "bfloat16": _lib.MIS_BF16}
 
 
 def _tensor_args(arr):
@@ -63,6 +64,12 @@ class NativeHandle:
             raise AudioGenerationError(3, "scales and biases must be 2-D and share dtype and shape")
         N, K = int(ss[0]), int(ss[1]) * group_size
         check(self._fn("set_tensor_quantized")(self._h, name.encode(), wq.ctypes.data, ps, pb, ds, N, K, group_size, bits))
+
+    def set_encoder_dtype(self, name: str):
+        """"float32" (the default) or "bfloat16", before finalize; only the engines that export <prefix>_set_encoder_dtype take it."""
+        if name not in _ENCODER_DTYPES:
+            raise AudioGenerationError(3, f"encoder_dtype {name!r}: only {sorted(_ENCODER_DTYPES)} are implemented")
+        check(self._fn("set_encoder_dtype")(self._h, _ENCODER_DTYPES[name]))
 
     def finalize(self):
         check(self._fn("finalize")(self._h))

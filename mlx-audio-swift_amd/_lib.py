@@ -497,6 +497,7 @@ SYMBOLS = {
     "mis_parakeet_create": (C.c_int, [C.POINTER(ParakeetConfigC), C.c_int, C.POINTER(_P)]),
     "mis_parakeet_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_parakeet_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_parakeet_set_encoder_dtype": (C.c_int, [_P, C.c_int]),
     "mis_parakeet_finalize": (C.c_int, [_P]),
     "mis_parakeet_destroy": (None, [_P]),
     "mis_parakeet_launches": (C.c_int, [_P]),
@@ -507,6 +508,7 @@ SYMBOLS = {
     "mis_canary_create": (C.c_int, [C.POINTER(CanaryConfigC), C.c_int, C.POINTER(_P)]),
     "mis_canary_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_canary_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_canary_set_encoder_dtype": (C.c_int, [_P, C.c_int]),
     "mis_canary_finalize": (C.c_int, [_P]),
     "mis_canary_destroy": (None, [_P]),
     "mis_canary_launches": (C.c_int, [_P]),
@@ -724,6 +726,11 @@ DEBUG_SYMBOLS = {
     "mis_debug_parakeet_tdt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "mis_debug_parakeet_timing": (C.c_int, [_P, _P]),
+    "mis_debug_parakeet_gemm_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, _P, C.c_int, _P]),
+    "mis_debug_parakeet_attn_bf16": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P,
+                                                 _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "mis_debug_parakeet_glu_dwconv_bf16": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_canary_lin": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "mis_debug_canary_attn_step": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_canary_head_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),

@@ -11,7 +11,7 @@ import ctypes as C
 import json
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -100,6 +100,7 @@ class CanaryConfig:
     max_seconds: int = 30
     max_tokens: int = 200
     max_prompt: int = 16
+    encoder_dtype: str = "float32"   # "bfloat16": the encoder's Conformer blocks in bf16 (csrc/parakeet_encoder_bf16.h); not part of a checkpoint
 
     @classmethod
     def from_dict(cls, d: dict, **workspace) -> "CanaryConfig":
@@ -361,21 +362,23 @@ class CanaryModel(NativeHandle):
     def __init__(self, config: CanaryConfig, tokenizer: CanaryTokenizer | None = None, device: int = 0):
         self.config, self.tokenizer, self.device = config, tokenizer, device
         self._create(config.to_c(), device)
+        if config.encoder_dtype != "float32":
+            self.set_encoder_dtype(config.encoder_dtype)
 
     sanitize = staticmethod(canary_sanitize)
 
     @classmethod
-    def from_weights(cls, config: CanaryConfig, weights: dict, tokenizer=None, device: int = 0) -> "CanaryModel":
-        """weights: the engine's names (what canary_sanitize returns)."""
-        m = cls(config, tokenizer, device)
+    def from_weights(cls, config: CanaryConfig, weights: dict, tokenizer=None, device: int = 0, encoder_dtype: str | None = None) -> "CanaryModel":
+        """weights: the engine's names (what canary_sanitize returns); encoder_dtype overrides the config's."""
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, tokenizer, device)
         for name, arr in weights.items():
             m.set_tensor(name, arr)
         m.finalize()
         return m
 
     @classmethod
-    def synthetic(cls, config: CanaryConfig, device: int = 0, seed: int = 777) -> "CanaryModel":
-        m = cls(config, None, device)
+    def synthetic(cls, config: CanaryConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None) -> "CanaryModel":
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, None, device)
         check(_lib.lib().mis_canary_init_synthetic(m._h, seed))
         m.finalize()
         return m

@@ -1,7 +1,8 @@
 // canary.hip - Canary speech-to-text and translation: 16 kHz samples -> Parakeet's encoder (parakeet_encoder.h: NeMo log-mel, dw-striding
 // stem, FastConformer blocks) -> optional projection -> the cross-attention K and V of every decoder layer, once -> a pre-LN Transformer
 // decoder run ONE TOKEN A STEP over cached K/V, with the vocabulary head fused with the arg-max and the token bookkeeping on the device.
-// Exact f32 throughout.
+// Exact f32 throughout, unless mis_canary_set_encoder_dtype(MIS_BF16) selects the bf16 form of the encoder's Conformer blocks
+// (parakeet_encoder_bf16.h); the decoder is f32 in both modes.
 //
 // Reference being replaced: CanaryModel (Sources/MLXAudioSTT/Models/Canary/CanaryModel.swift generate :385-432, CanaryDecoder :288-329,
 // CanaryDecoderBlock :245-286, CanaryAttention :200-243, CanaryFixedPositionalEncoding :166-198).  The reference re-runs the whole prefix
@@ -34,6 +35,7 @@
 #include "step_loop.h"
 #include "sortformer_kernels.h"
 #include "parakeet_encoder.h"
+#include "parakeet_encoder_bf16.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -414,6 +416,12 @@ extern "C" mis_status mis_canary_set_tensor(mis_canary* c, const char* name, con
     MIS_API_END
 }
 
+extern "C" mis_status mis_canary_set_encoder_dtype(mis_canary* c, mis_dtype dtype) {
+    MIS_API_BEGIN
+    pk_set_encoder_dtype(c, dtype);
+    MIS_API_END
+}
+
 static const char* const CN_ATT[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 
 extern "C" mis_status mis_canary_finalize(mis_canary* c) {
@@ -465,8 +473,7 @@ extern "C" mis_status mis_canary_finalize(mis_canary* c) {
                 if (ch + 1 < h) fh[o + (size_t)r * h + ch + 1] = (float)(cos(ang) * rs);
             }
     }
-    DevBuf<bf16_t> none;
-    a.upload(none, c->farena);
+    a.upload(c->warena, c->farena);
     pk_encoder_workspace(c);
     const size_t B = c->cfg.max_batch, M = B * c->Tcap;
     if (d != h) c->encp.alloc(M * h);

@@ -1,6 +1,7 @@
 // parakeet.hip - Parakeet TDT speech-to-text: 16 kHz samples -> NeMo log-mel (per-feature normalisation) -> depthwise-striding Conv2d stem
 // (factor 8) -> FastConformer blocks with relative-position attention -> joint.enc over every frame -> greedy TDT decode (embedding, two
-// LSTM layers, joint, token and duration arg-max) in ONE launch.  Exact f32 throughout.
+// LSTM layers, joint, token and duration arg-max) in ONE launch.  Exact f32 throughout, unless mis_parakeet_set_encoder_dtype(MIS_BF16)
+// selects the bf16 form of the Conformer blocks (parakeet_encoder_bf16.h holds its kernels and its precision contract).
 //
 // Reference being replaced: ParakeetModel (Sources/MLXAudioSTT/Models/Parakeet/ParakeetModel.swift decodeTDTSerial :389-479,
 // makeCompiledTDTStep :894-931, ParakeetConformer.swift), NemoDecodingLogic.tdtStep (Nemo/NemoDecodingLogic.swift:41-67), NemoPredictNetwork /
@@ -34,6 +35,7 @@
 #include "step_loop.h"
 #include "sortformer_kernels.h"
 #include "parakeet_encoder.h"
+#include "parakeet_encoder_bf16.h"
 
 #include <math.h>
 #include <string.h>
@@ -248,6 +250,12 @@ extern "C" mis_status mis_parakeet_set_tensor(mis_parakeet* c, const char* name,
     MIS_API_END
 }
 
+extern "C" mis_status mis_parakeet_set_encoder_dtype(mis_parakeet* c, mis_dtype dtype) {
+    MIS_API_BEGIN
+    pk_set_encoder_dtype(c, dtype);
+    MIS_API_END
+}
+
 static const char* const PK_LSTM = "decoder.prediction.dec_rnn.lstm.";
 
 extern "C" mis_status mis_parakeet_finalize(mis_parakeet* c) {
@@ -268,8 +276,7 @@ extern "C" mis_status mis_parakeet_finalize(mis_parakeet* c) {
     }
     s.wp = c->raw.need("joint.pred.weight", {J, P}).v.data(); s.bp = c->raw.need("joint.pred.bias", {J}).v.data();
     s.wo = c->raw.need("joint.joint_net.weight", {NL, J}).v.data(); s.bo = c->raw.need("joint.joint_net.bias", {NL}).v.data();
-    DevBuf<bf16_t> none;
-    a.upload(none, c->farena);
+    a.upload(c->warena, c->farena);
     pk_pack_decoder(s, (int)P, (int)J, (int)V, (int)NL, c->dec, c->tdt);
     pk_encoder_workspace(c);
     const size_t B = c->cfg.max_batch, M = B * c->Tcap;
@@ -485,5 +492,127 @@ extern "C" mis_status mis_debug_parakeet_tdt(int device, const float* encp, cons
     HIP_CHECK(hipMemcpy(counts, p.count, batch * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(flags, p.flag, batch * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(steps, p.steps, batch * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ---------------------------------------------------------------------------- the bf16 encoder's kernels (parakeet_encoder_bf16.h)
+namespace {
+// the ONE checked launch; then, with ms, `repeat` more of the same launch between two events: *ms = milliseconds a launch
+template <class F>
+void pkd_run(PkdCtx& c, F launch, int repeat, float* ms) {
+    launch();
+    pkd_sync(c);
+    if (!ms) return;
+    MIS_REQUIRE(repeat >= 1 && repeat <= 10000, MIS_ERR_INVALID_INPUT, "repeat %d outside 1..10000", repeat);
+    HipEvents<2> ev;
+    HIP_CHECK(hipEventRecord(ev[0], c.stream));
+    for (int r = 0; r < repeat; ++r) launch();
+    HIP_CHECK(hipEventRecord(ev[1], c.stream));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipEventElapsedTime(ms, ev[0], ev[1]));
+    *ms /= (float)repeat;
+}
+// rows x width elements of `es` bytes out of a guarded [rows][ld] body; the columns behind width must be untouched
+void pkd_rows_out(GuardedOut& o, void* out, size_t rows, size_t width, size_t ld, size_t es) {
+    o.check_guards();
+    std::vector<uint8_t> hbuf(o.body);
+    HIP_CHECK(hipMemcpy(hbuf.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        memcpy(static_cast<uint8_t*>(out) + r * width * es, hbuf.data() + r * ld * es, width * es);
+        for (size_t i = width * es; i < ld * es; ++i)
+            MIS_REQUIRE(hbuf[r * ld * es + i] == 0xFF, MIS_ERR_GENERATION_FAILED, "the kernel wrote behind the %zu columns of row %zu", width, r);
+    }
+}
+}  // namespace
+
+// ONE launch of k_pk_gemm_bf16.  load PKB_LOAD_BF16 (0): x bf16 [batch Tp][K]; PKB_LOAD_LN (1): x f32 with stats [batch Tp][2], lnw, lnb [K].
+// epi 0 none / 1 SiLU: out bf16 [batch Tp][N]; 2: out f32 = R + ra v, R f32 [batch Tp][N].  rule 0: 64 x 64 tile, 1: 32 x 32.
+extern "C" mis_status mis_debug_parakeet_gemm_bf16(int device, int load, int epi, int rule, const void* x, const float* stats, const float* lnw, const float* lnb,
+                                                   const uint16_t* w, const float* bias, const float* R, float ra, const int32_t* cnt, int batch, int Tp, int K,
+                                                   int N, void* out, int repeat, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && w && cnt && out && batch >= 1 && batch <= 65535 && Tp >= 1 && K >= 32 && K % 32 == 0 && N >= 8 && N % 8 == 0, MIS_ERR_INVALID_INPUT,
+                "Parakeet bf16 GEMM: pointers, positive batch and Tp, K a multiple of 32 and N a multiple of 8 are required");
+    MIS_REQUIRE((load == PKB_LOAD_BF16 || (load == PKB_LOAD_LN && stats && lnw && lnb)) && epi >= PKB_EPI_NONE && epi <= PKB_EPI_RES && (epi != PKB_EPI_RES || R) &&
+                    (rule == PKB_TILE64 || rule == PKB_TILE32), MIS_ERR_INVALID_INPUT, "Parakeet bf16 GEMM: unknown load / epilogue / rule, or a missing operand");
+    const size_t rows = (size_t)batch * Tp;
+    MIS_REQUIRE((int64_t)rows * K <= PKD_MAX_ELEMS && (int64_t)rows * N <= PKD_MAX_ELEMS && (int64_t)N * K <= PKD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Parakeet bf16 GEMM: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    PkdCtx c;
+    DevBuf<uint16_t> dxb, dw;
+    DevBuf<uint32_t> dxf, dst, dlw, dlb, dbias, dR, dcnt;
+    PkbGemm p{};
+    if (load == PKB_LOAD_LN) {
+        alloc32(dxf, x, rows * K, F32_NAN); alloc32(dst, stats, rows * 2, F32_NAN); alloc32(dlw, lnw, K, F32_NAN); alloc32(dlb, lnb, K, F32_NAN);
+        p.Xf = pkd_fp(dxf); p.stats = pkd_fp(dst); p.lnw = pkd_fp(dlw); p.lnb = pkd_fp(dlb);
+    } else {
+        alloc16(dxb, static_cast<const uint16_t*>(x), rows * K, BF16_NAN);
+        p.Xb = dxb.p;
+    }
+    alloc16(dw, w, (size_t)N * K, BF16_NAN);
+    alloc32(dcnt, cnt, batch, 0x7FFFFFFFu);
+    if (bias) { alloc32(dbias, bias, N, F32_NAN); p.bias = pkd_fp(dbias); }
+    if (epi == PKB_EPI_RES) { alloc32(dR, R, rows * N, F32_NAN); p.R = pkd_fp(dR); p.ldr = N; p.ra = ra; }
+    const size_t es = epi == PKB_EPI_RES ? 4 : 2;
+    GuardedOut o;
+    o.alloc(rows * N * es, (size_t)64 * N * es);
+    p.Yf = reinterpret_cast<float*>(o.p()); p.Yb = reinterpret_cast<bf16_t*>(o.p());
+    p.ldx = K; p.W = dw.p; p.ldy = N; p.cnt = reinterpret_cast<const int*>(dcnt.p); p.Tp = Tp; p.K = K; p.N = N; p.epi = epi;
+    pkd_run(c, [&] { pkb_gemm_launch(&c, p, load, rule, batch); c.launches = 1; }, repeat, ms);
+    pkd_rows_out(o, out, rows, N, N, es);
+    MIS_API_END
+}
+
+// ONE launch of k_pk_attn_bf16: the arguments of mis_debug_parakeet_attn with bf16 qkv and table, head sizes 1..128; out bf16 [batch Tp][heads hd]
+extern "C" mis_status mis_debug_parakeet_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads,
+                                                   int hd, float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp, int Tcap, int ldo,
+                                                   uint16_t* out, int repeat, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(qkv && cnt && out && u && v && P && batch >= 1 && Tp >= 1 && heads >= 1 && hd >= 1 && hd <= 128 && Tcap >= 1, MIS_ERR_INVALID_INPUT,
+                "Parakeet bf16 attention: every pointer, positive batch, Tp, heads, Tcap and a head size of 1..128 are required");
+    const int64_t width = (int64_t)heads * hd;
+    MIS_REQUIRE(koff >= 0 && voff >= 0 && width <= ld && koff + width <= ld && voff + width <= ld && width <= ldo && ldp >= width, MIS_ERR_INVALID_INPUT,
+                "Parakeet bf16 attention: q, k and v must lie inside a row of ld columns, the output inside ldo, the table inside ldp");
+    MIS_REQUIRE((int64_t)batch * Tp * ld <= PKD_MAX_ELEMS && (int64_t)batch * Tp * ldo <= PKD_MAX_ELEMS && (2 * (int64_t)Tcap - 1) * ldp <= PKD_MAX_ELEMS &&
+                    batch <= 65535 && heads <= 65535, MIS_ERR_INVALID_INPUT, "Parakeet bf16 attention: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    PkdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint16_t> dq, dP;
+    DevBuf<uint32_t> dcnt, du, dv;
+    alloc16(dq, qkv, rows * ld, BF16_NAN); alloc16(dP, P, (size_t)(2 * Tcap - 1) * ldp, BF16_NAN);
+    alloc32(dcnt, cnt, batch, 0x7FFFFFFFu);
+    alloc32(du, u, width, F32_NAN); alloc32(dv, v, width, F32_NAN);
+    GuardedOut o;
+    o.alloc(rows * ldo * 2, (size_t)64 * ldo * 2);
+    PkbAttn p{dq.p, ld, koff, voff, reinterpret_cast<bf16_t*>(o.p()), ldo, reinterpret_cast<const int*>(dcnt.p), Tp, hd, qscale, sdk, pkd_fp(du), pkd_fp(dv),
+              dP.p, ldp, Tcap};
+    pkd_run(c, [&] { pkb_attn(&c, p, heads, hd, batch); c.launches = 1; }, repeat, ms);
+    pkd_rows_out(o, out, rows, width, ldo, 2);
+    MIS_API_END
+}
+
+// ONE launch of k_pk_glu_dwconv_bf16: pw bf16 [batch Tp][2 C], taps f32 [k][C], shift f32 [C] -> out bf16 [batch Tp][C]
+extern "C" mis_status mis_debug_parakeet_glu_dwconv_bf16(int device, const uint16_t* pw, const float* taps, const float* shift, const int32_t* cnt, int batch, int Tp,
+                                                         int C, int k, uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pw && taps && shift && cnt && out && batch >= 1 && batch <= 65535 && Tp >= 1 && C >= 1 && k >= 3 && k <= SF_DW_MAXK && k % 2 == 1,
+                MIS_ERR_INVALID_INPUT, "Parakeet bf16 GLU / depthwise: pointers, positive batch, Tp, C and an odd k of 3..%d are required", SF_DW_MAXK);
+    const size_t rows = (size_t)batch * Tp;
+    MIS_REQUIRE((int64_t)rows * 2 * C <= PKD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Parakeet bf16 GLU / depthwise: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    PkdCtx c;
+    DevBuf<uint16_t> dpw;
+    DevBuf<uint32_t> dt, dsh, dcnt;
+    alloc16(dpw, pw, rows * 2 * C, BF16_NAN);
+    alloc32(dt, taps, (size_t)k * C, F32_NAN); alloc32(dsh, shift, C, F32_NAN); alloc32(dcnt, cnt, batch, 0x7FFFFFFFu);
+    GuardedOut o;
+    o.alloc(rows * C * 2, (size_t)64 * C * 2);
+    MIS_LAUNCH(&c, k_pk_glu_dwconv_bf16, dim3(cdiv(Tp, SF_DW_TT), cdiv(C, 64), batch), dim3(256), dpw.p, pkd_fp(dt), pkd_fp(dsh),
+               reinterpret_cast<const int*>(dcnt.p), reinterpret_cast<bf16_t*>(o.p()), Tp, C, k);
+    pkd_sync(c);
+    pkd_rows_out(o, out, rows, C, C, 2);
     MIS_API_END
 }

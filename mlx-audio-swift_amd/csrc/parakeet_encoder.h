@@ -4,7 +4,10 @@
 // sortformer.hip: each including file gets its own copy (the anonymous namespace), the functions take the owning handle as a template
 // parameter.  The handle derives from PkEncoder and supplies: device, stream, cfg (the encoder fields of mis_parakeet_config by name, and
 // max_batch / max_seconds / preemphasis / normalize / scale_input / attention_bias), raw (HostWeights), finalized, timed, timed_done, ev.
-// Include common.h, audio_front.h (AUDIO_FRONT_NEMO_KERNELS), f32_tile.h, host_weights.h, step_loop.h and sortformer_kernels.h first.
+// Include common.h, audio_front.h (AUDIO_FRONT_NEMO_KERNELS), f32_tile.h, host_weights.h, step_loop.h and sortformer_kernels.h first, and
+// parakeet_encoder_bf16.h behind it: the opt-in bf16 form of the block chain (enc_bf16; its precision contract stands there).  With
+// enc_bf16 the eight block matrices go to the bf16 arena instead of the f32 one, each layer's table is projected by pk_bf16_tables, big /
+// qkv / att are bf16 buffers and pk_encoder hands over to pk_encoder_bf16; everything else here is shared by both modes.
 #pragma once
 
 #include <math.h>
@@ -168,10 +171,30 @@ struct PkEncoder {
     int batch = 0, Fp = 0, T1p = 0, T2p = 0, Tp = 0, launches = 0;
     std::vector<int> hN, hF, hT1, hT2, hT3;
     bool has_emb = false;
+    // bf16 mode (parakeet_encoder_bf16.h): the block matrices [N][K] and the rounded tables [2 Tcap - 1][d]; Layer keeps the f32 members
+    int enc_bf16 = 0;
+    struct Layer16 { bf16_t *ff1a, *ff1b, *qkv, *o, *pw1, *pw2, *ff2a, *ff2b, *P; };
+    std::vector<Layer16> fc16;
+    DevBuf<bf16_t> warena, ptab16, big16, qkv16, att16;
 };
+
+template <class Ctx> static void pk_bf16_tables(Ctx* c);
+template <class Ctx> static void pk_encoder_bf16(Ctx* c, int stop);
 
 static inline int pk_half(int t) { return t >= 1 ? (t - 1) / 2 + 1 : 0; }
 static inline int pk_frames(int64_t n) { return (int)(1 + n / NEMO_HOP); }
+
+// the sinusoid table by distance [2 Tc - 1][d]: row dist + Tc - 1, columns interleaved sin, cos; formed in double, rounded once
+static void pk_postab(float* tab, int Tc, int64_t d) {
+    for (int r = 0; r < 2 * Tc - 1; ++r) {
+        const double dist = (double)(r - (Tc - 1));
+        for (int64_t k = 0; 2 * k < d; ++k) {
+            const double ang = dist * exp(-(double)(2 * k) * log(10000.0) / (double)d);
+            tab[(size_t)r * d + 2 * k] = (float)sin(ang);
+            if (2 * k + 1 < d) tab[(size_t)r * d + 2 * k + 1] = (float)cos(ang);
+        }
+    }
+}
 
 // what create asks of the encoder's fields
 template <class Cfg>
@@ -220,9 +243,17 @@ static void pk_encoder_weights(Ctx* c, HostArena& a) {
     c->maxN = (int64_t)c->cfg.max_seconds * 16000;
     c->Fcap = pk_frames(c->maxN); c->T1cap = pk_half(c->Fcap); c->T2cap = pk_half(c->T1cap); c->Tcap = pk_half(c->T2cap);
     const int Tc = c->Tcap, NP = 2 * Tc - 1;
-    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l) {
+    const bool b16 = c->enc_bf16 != 0;
+    // a block matrix: the f32 arena, or rounded once into the bf16 arena
+    auto mat = [&](const std::string& name, std::initializer_list<int64_t> shape, int64_t N, int64_t K, const float*& wf, bf16_t*& wb) {
+        if (!b16) { a.fvec(name, shape, N * K, wf); return; }
+        const HostTensor& t = c->raw.need(name, shape);
+        const size_t off = a.btake((size_t)N * K, wb);
+        for (int64_t i = 0; i < N * K; ++i) a.host[off + i] = f32_to_bf16(t.v[i]);
+    };
+    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l, bf16_t*& wb) {
         l = SfLin{};
-        a.fvec(p + ".weight", {N, K}, N * K, l.w);
+        mat(p + ".weight", {N, K}, N, K, l.w, wb);
         if (bias) a.fvec(p + ".bias", {N}, N, l.b);
     };
     auto norm = [&](const std::string& p, int64_t n, const float*& w, const float*& b) { a.fvec(p + ".weight", {n}, n, w); a.fvec(p + ".bias", {n}, n, b); };
@@ -245,28 +276,32 @@ static void pk_encoder_weights(Ctx* c, HostArena& a) {
             fh[ow + (n * F3 + fq) * C + ch] = w.v[n * C * F3 + ch * F3 + fq];
     }
     c->fc.assign(c->L, PkEncoder::Layer{});
+    c->fc16.assign(c->L, PkEncoder::Layer16{});
     c->rk.assign(c->L, SfLin{});
     for (int li = 0; li < c->L; ++li) {
         const std::string q = "encoder.layers." + std::to_string(li) + ".";
         PkEncoder::Layer& l = c->fc[li];
+        PkEncoder::Layer16& l16 = c->fc16[li];
         norm(q + "norm_feed_forward1", d, l.ln1w, l.ln1b);
-        lin(q + "feed_forward1.linear1", f, d, ab, l.ff1a); lin(q + "feed_forward1.linear2", d, f, ab, l.ff1b);
+        lin(q + "feed_forward1.linear1", f, d, ab, l.ff1a, l16.ff1a); lin(q + "feed_forward1.linear2", d, f, ab, l.ff1b, l16.ff1b);
         norm(q + "norm_self_att", d, l.lnaw, l.lnab);
         {   // q, k, v over the same input as one [3 d][d]; an absent bias is zero
-            const size_t ow = a.ftake((size_t)3 * d * d, l.qkv.w), ob = a.ftake(3 * d, l.qkv.b);
+            const size_t ow = b16 ? a.btake((size_t)3 * d * d, l16.qkv) : a.ftake((size_t)3 * d * d, l.qkv.w), ob = a.ftake(3 * d, l.qkv.b);
             const char* names[3] = {"q_proj", "k_proj", "v_proj"};
             for (int i = 0; i < 3; ++i) {
                 const HostTensor& w = c->raw.need(q + "self_attn." + names[i] + ".weight", {d, d});
-                std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * d * d);
+                if (b16) for (int64_t j = 0; j < d * d; ++j) a.host[ow + (size_t)i * d * d + j] = f32_to_bf16(w.v[j]);
+                else std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * d * d);
                 if (ab) { const HostTensor& bb = c->raw.need(q + "self_attn." + names[i] + ".bias", {d}); std::copy(bb.v.begin(), bb.v.end(), fh.begin() + ob + (size_t)i * d); }
             }
         }
-        lin(q + "self_attn.o_proj", d, d, ab, l.o);
-        a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, c->rk[li].w);
+        lin(q + "self_attn.o_proj", d, d, ab, l.o, l16.o);
+        if (b16) c->raw.need(q + "self_attn.relative_k_proj.weight", {d, d});       // uploaded by pk_bf16_tables, for the projection only
+        else a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, c->rk[li].w);
         a.fvec(q + "self_attn.bias_u", {H, hd}, d, l.u); a.fvec(q + "self_attn.bias_v", {H, hd}, d, l.v);
         norm(q + "norm_conv", d, l.lncw, l.lncb);
-        a.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w);
-        a.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w);
+        mat(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d, d, l.pw1.w, l16.pw1);
+        mat(q + "conv.pointwise_conv2.weight", {d, 1, d}, d, d, l.pw2.w, l16.pw2);
         if (ab) { a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d, l.pw1.b); a.fvec(q + "conv.pointwise_conv2.bias", {d}, d, l.pw2.b); }
         const HostTensor& dw = c->raw.need(q + "conv.depthwise_conv.weight", {d, ck, 1});
         const HostTensor* dwb = ab ? &c->raw.need(q + "conv.depthwise_conv.bias", {d}) : nullptr;
@@ -275,19 +310,12 @@ static void pk_encoder_weights(Ctx* c, HostArena& a) {
         const size_t o_dw = a.ftake((size_t)ck * d, l.dw), o_sh = a.ftake(d, l.dwshift);
         fold_bn_dwconv(&fh[o_dw], &fh[o_sh], dw.v.data(), dwb ? dwb->v.data() : nullptr, bw.v.data(), bb.v.data(), bm.v.data(), bv.v.data(), d, ck);
         norm(q + "norm_feed_forward2", d, l.ln2w, l.ln2b);
-        lin(q + "feed_forward2.linear1", f, d, ab, l.ff2a); lin(q + "feed_forward2.linear2", d, f, ab, l.ff2b);
+        lin(q + "feed_forward2.linear1", f, d, ab, l.ff2a, l16.ff2a); lin(q + "feed_forward2.linear2", d, f, ab, l.ff2b, l16.ff2b);
         norm(q + "norm_out", d, l.lnow, l.lnob);
     }
-    // the sinusoid table by distance: row dist + Tcap - 1, columns interleaved sin, cos; formed in double, rounded once
+    if (b16) return;                                                // the table is pk_bf16_tables' in bf16 mode
     const size_t o_tab = a.ftake((size_t)NP * d, c->postab);
-    for (int r = 0; r < NP; ++r) {
-        const double dist = (double)(r - (Tc - 1));
-        for (int64_t k = 0; 2 * k < d; ++k) {
-            const double ang = dist * exp(-(double)(2 * k) * log(10000.0) / (double)d);
-            fh[o_tab + (size_t)r * d + 2 * k] = (float)sin(ang);
-            if (2 * k + 1 < d) fh[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
-        }
-    }
+    pk_postab(&fh[o_tab], Tc, d);
 }
 
 // finalize, second half (the arena is uploaded): each layer's relative_k_proj of the table, one GEMM each, once; the workspace
@@ -297,19 +325,24 @@ static void pk_encoder_workspace(Ctx* c) {
     const int Tc = c->Tcap, NP = 2 * Tc - 1;
     c->fbr.alloc(2 * mels);
     HIP_CHECK(hipMemcpy(c->fbr.p, c->fb_ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
-    c->ptab.alloc((size_t)c->L * NP * d);
-    for (int li = 0; li < c->L; ++li) {
-        float* dst = c->ptab.p + (size_t)li * NP * d;
-        sf_gemm(c, sf_lin(c->postab, (int)d, c->rk[li], dst, (int)d, nullptr, NP), 1);
-        c->fc[li].P = dst;
+    if (c->enc_bf16) pk_bf16_tables(c);
+    else {
+        c->ptab.alloc((size_t)c->L * NP * d);
+        for (int li = 0; li < c->L; ++li) {
+            float* dst = c->ptab.p + (size_t)li * NP * d;
+            sf_gemm(c, sf_lin(c->postab, (int)d, c->rk[li], dst, (int)d, nullptr, NP), 1);
+            c->fc[li].P = dst;
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(c->stream));
     c->launches = 0;
     const size_t B = c->cfg.max_batch, M = B * Tc;
     c->pcm.alloc(B * c->maxN); c->melraw.alloc(B * c->Fcap * mels); c->feats.alloc(B * c->Fcap * mels);
     c->s0.alloc(B * c->T1cap * c->F1 * C); c->s1.alloc(B * c->T2cap * c->F2 * C); c->s2.alloc(M * F3 * C); c->emb.alloc(M * d);
-    c->h.alloc(M * d); c->stats.alloc(M * 2); c->big.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d);
+    c->h.alloc(M * d); c->stats.alloc(M * 2);
+    if (c->enc_bf16) { c->big16.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv16.alloc(M * 3 * d); c->att16.alloc(M * d); }
+    else { c->big.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d); }
     c->cntN.alloc(B); c->cntF.alloc(B); c->cnt1.alloc(B); c->cnt2.alloc(B); c->cnt3.alloc(B);
 }
 
@@ -395,6 +428,7 @@ static void pk_front_stem(Ctx* c, const float* pcm, const int64_t* lens, int bat
 // c->emb -> the Conformer blocks -> c->h (1 + 15 L launches); stop: -1 all, 1 .. L behind that block
 template <class Ctx>
 static void pk_encoder(Ctx* c, int stop) {
+    if (c->enc_bf16) { pk_encoder_bf16(c, stop); return; }
     const int B = c->batch, Tp = c->Tp, d = c->d, f = c->f, M = B * Tp;
     const int* cnt = c->cnt3.p;
     const size_t nd = (size_t)M * d;

@@ -11,7 +11,7 @@ import ctypes as C
 import json
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -59,6 +59,7 @@ class ParakeetConfig:
     max_batch: int = 8
     max_seconds: int = 30
     max_tokens: int = 1024
+    encoder_dtype: str = "float32"   # "bfloat16": the Conformer blocks in bf16 (csrc/parakeet_encoder_bf16.h); not part of a checkpoint
 
     @classmethod
     def from_dict(cls, d: dict, **workspace) -> "ParakeetConfig":
@@ -223,28 +224,31 @@ class ParakeetModel(NativeHandle):
     def __init__(self, config: ParakeetConfig, device: int = 0):
         self.config, self.device = config, device
         self._create(config.to_c(), device)
+        if config.encoder_dtype != "float32":
+            self.set_encoder_dtype(config.encoder_dtype)
 
     sanitize = staticmethod(parakeet_sanitize)
 
     @classmethod
-    def from_weights(cls, config: ParakeetConfig, weights: dict, device: int = 0) -> "ParakeetModel":
-        """weights: the engine's names (what parakeet_sanitize returns)."""
-        m = cls(config, device)
+    def from_weights(cls, config: ParakeetConfig, weights: dict, device: int = 0, encoder_dtype: str | None = None) -> "ParakeetModel":
+        """weights: the engine's names (what parakeet_sanitize returns); encoder_dtype overrides the config's."""
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         for name, arr in weights.items():
             m.set_tensor(name, arr)
         m.finalize()
         return m
 
     @classmethod
-    def synthetic(cls, config: ParakeetConfig, device: int = 0, seed: int = 777) -> "ParakeetModel":
-        m = cls(config, device)
+    def synthetic(cls, config: ParakeetConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None) -> "ParakeetModel":
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         check(_lib.lib().mis_parakeet_init_synthetic(m._h, seed))
         m.finalize()
         return m
 
     @classmethod
     def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "ParakeetModel":
-        """fromDirectory (:946-1052): config.json, every *.safetensors; the vocabulary of config.json, else the first *.model's pieces."""
+        """fromDirectory (:946-1052): config.json, every *.safetensors; the vocabulary of config.json, else the first *.model's pieces.
+        workspace: max_batch / max_seconds / max_tokens / encoder_dtype."""
         with open(os.path.join(model_dir, "config.json")) as f:
             text = f.read()
         for tok in ("-Infinity", "Infinity", "NaN"):                     # normalizedConfigData (:934-944)

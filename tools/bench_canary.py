@@ -26,11 +26,12 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--enc-layers", type=int, default=32)
+    ap.add_argument("--encoder-dtype", default="float32", choices=["float32", "bfloat16"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "canary", "bench.jsonl"))
     a = ap.parse_args()
     batches = [int(b) for b in a.batches.split(",")]
     cfg = mas.CanaryConfig(encoder=mas.CanaryEncoderConfig(n_layers=a.enc_layers), max_batch=max(batches), max_seconds=int(np.ceil(a.seconds)),
-                           max_tokens=a.tokens, max_prompt=16)
+                           max_tokens=a.tokens, max_prompt=16, encoder_dtype=a.encoder_dtype)
     m = mas.CanaryModel.synthetic(cfg, seed=11)
     m.enable_timing()
     d, h = cfg.decoder, cfg.enc_output_dim
@@ -54,7 +55,7 @@ def main():
                 copies.append(ev[0].elapsed_time(ev[1]))
         med = lambda i: statistics.median(r[i] for r in rows)
         steps = rows[0][4]
-        rec = dict(batch=B, seconds=a.seconds, enc_layers=a.enc_layers, graph=os.environ.get("MIS_NO_GRAPH") is None, front_ms=med(0), encoder_ms=med(1),
+        rec = dict(batch=B, encoder_dtype=a.encoder_dtype, seconds=a.seconds, enc_layers=a.enc_layers, graph=os.environ.get("MIS_NO_GRAPH") is None, front_ms=med(0), encoder_ms=med(1),
                    cross_kv_ms=med(2), steps=steps, step_ms=med(3) / steps, launches_per_step=11 * d.num_layers + 2, launches=rows[0][5],
                    step_weight_bytes=4 * step_floats, d2d_copy_ms=statistics.median(copies), S_out_proj=8 if h <= 1024 else 4 if h <= 2048 else 2)
         rec["step_over_copy"] = rec["step_ms"] / rec["d2d_copy_ms"]
