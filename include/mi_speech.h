@@ -1477,6 +1477,21 @@ mis_status mis_parakeet_tap(mis_parakeet*, int stage, float* out, int64_t capaci
  * Limits, MIS_ERR_INVALID_INPUT at create with a message naming the field: the encoder's as Parakeet's; enc_output_dim 8..4096; dec_layers
  * 1..32; the decoder head size a whole number up to 128; dec_inner_size 1..16384; vocab_size 2..65536; max_tokens 1..4096; max_prompt
  * 1..256; the cross K/V store max_batch x T(max_seconds) x dec_layers x 2 h floats at most 4 GiB (the message names max_seconds).
+ *
+ * bf16 decoder (opt-in, mis_canary_set_decoder_dtype with MIS_BF16 before finalize, whatever the encoder's dtype; f32 stays the default
+ * with its bits and launch counts).  The step streams its weights as bf16 on v_mfma_f32_16x16x32_bf16 (k_cn_lin_bf16) and attends over
+ * bf16 K | V stores (k_cn_attn_step_bf16).  Precision contract.  Rounded to bf16, to nearest even, once: the six step matrices of every
+ * layer (q | k | v stacked, self out_proj, cross q_proj, cross out_proj, ff1, ff2) and decoder.output_proj; the operand a step contraction
+ * stages (the f32 xn / att / ff row, rounded as it is written to LDS); every K and V value as it is stored, in the self cache and the
+ * cross store.  The cross k | v matrix is NOT rounded: each layer's K | V is projected once a call by the f32 GEMM from the f32 encoder
+ * output, then rounded into the store.  f32 as in the default mode: the residual stream x, LayerNorm statistics and parameters, biases,
+ * every accumulation, the split-K partials and their ascending-s reduction, the query, the scores, the softmax and its probabilities
+ * (the attention step uses no MFMA: nothing there is rounded), the embedding table, the sinusoid table and the head's (max, lowest
+ * index) reduction.  A row's tokens and forward outputs stay bit-identical whatever its batch or the padding behind lens[b]: no float
+ * atomics, every add order fixed, tile shapes from the widths and the row bucket (<= 16 / 32 / 64) only, and a row's sums do not depend
+ * on the bucket.  Resident memory: the rounded matrices exist on the device as bf16 only - L_dec (6 h^2 + 2 h inner) + vocab h values
+ * of 2 bytes in place of 4.  Requires enc_output_dim % 32 == 0 and dec_inner_size % 32 == 0 (MIS_ERR_INVALID_INPUT naming the field);
+ * any dtype but MIS_F32 / MIS_BF16 and a call after finalize are refused, the handle stays usable.
  * ---------------------------------------------------------------------------------------- */
 typedef struct mis_canary mis_canary;
 typedef struct {
@@ -1494,12 +1509,15 @@ mis_status mis_canary_create(const mis_canary_config*, int device, mis_canary** 
  * decoder.blocks.N.ff1 [inner, h], ff2 [h, inner]; decoder.output_proj [vocab, h]; host pointers */
 mis_status mis_canary_set_tensor(mis_canary*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
 mis_status mis_canary_init_synthetic(mis_canary*, uint64_t seed);
-/* MIS_F32 (the default) or MIS_BF16: the encoder's Conformer blocks, Parakeet's contract; the decoder is f32 in both modes; before finalize */
+/* MIS_F32 (the default) or MIS_BF16: the encoder's Conformer blocks, Parakeet's contract; the decoder has its own switch; before finalize */
 mis_status mis_canary_set_encoder_dtype(mis_canary*, mis_dtype);
+/* MIS_F32 (the default) or MIS_BF16: the decoder's step (the contract above), independent of the encoder's dtype; before finalize */
+mis_status mis_canary_set_decoder_dtype(mis_canary*, mis_dtype);
 mis_status mis_canary_finalize(mis_canary*);
 void       mis_canary_destroy(mis_canary*);
 /* kernel launches of the last call: encode 7 + 15 L_enc (+ 1 with a projection); generate that + L_dec (cross K/V) + 1 (the first input)
- * + steps x (11 L_dec + 2), steps as generate returned them */
+ * + steps x (11 L_dec + 2), steps as generate returned them.  With the bf16 decoder the cross K/V is the f32 projection plus one rounding
+ * launch a layer into the bf16 store: generate counts 2 L_dec there (L_dec more); the step stays 11 L_dec + 2 */
 int        mis_canary_launches(const mis_canary*);
 mis_status mis_canary_frames(const mis_canary*, const int64_t* lens, int batch, int32_t* F_out, int32_t* T_out);
 /* pcm f32 [batch, stride], lens[batch] (NULL = stride) -> the encoder's output behind the projection f32 [batch, Tmax, h] */
@@ -1514,7 +1532,7 @@ mis_status mis_canary_generate(mis_canary*, const float* pcm, const int64_t* len
 mis_status mis_canary_forward(mis_canary*, const int32_t* prompt, const int32_t* plen, int Pmax, float* logits, float* hidden);
 /* tensors of the last encode / generate, f32, zero rows behind T_b: stage 0 the stem's embeddings [B, T, hidden_size], 1..L_enc that
  * Conformer block, L_enc + 1 the encoder's output behind the projection [B, T, h], L_enc + 2 + l the cross K | V of decoder layer l
- * [B, T, 2 h].  dims[3] receives B, T, width; out NULL for the dims alone. */
+ * [B, T, 2 h] (the bf16 decoder: the stored bf16 values, widened).  dims[3] receives B, T, width; out NULL for the dims alone. */
 mis_status mis_canary_tap(mis_canary*, int stage, float* out, int64_t capacity, int64_t* dims);
 
 /* ------------------------------------------------------------------------------------------

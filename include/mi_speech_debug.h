@@ -398,11 +398,18 @@ mis_status mis_debug_nemotron_stream_timing(mis_nemotron_stream*, float* ms);
  *     keys a row (1..cap), scale hd^-0.5 -> out [B, heads hd].
  *   canary_head_argmax: ONE launch of k_cn_lin as the head runs it; the per-tile pairs are combined by k_cn_select's rule.  logits [M, V]
  *     may be NULL (then no logit reaches memory); index [M]; value [M] may be NULL.
+ *   canary_lin_bf16: k_cn_lin_bf16 (the bf16 decoder) as canary_lin, W given as bf16 bits [N, K], K % 32 == 0.  index NULL: S = 1 one
+ *     launch, S = 2 / 4 / 8 the partial launch and k_cn_rows.  index [M] given (S = 1): the launch as the head runs it, the pairs combined
+ *     by k_cn_select's rule; out may then be NULL (no logit reaches memory).
+ *   canary_attn_step_bf16: ONE launch of k_cn_attn_step_bf16: canary_attn_step with kv given as bf16 bits.
  *   canary_timing: NULL arms it; else device milliseconds of the last generate: front end, stem + encoder + projection, cross K/V, steps. */
 mis_status mis_debug_canary_lin(int device, const float* X, int Mrows, int M, int K, int N, const float* W, const float* bias, int relu, int S, float* out);
 mis_status mis_debug_canary_attn_step(int device, const float* q, const float* kv, const int32_t* cnt, int batch, int cap, int heads, int hd, float* out);
 mis_status mis_debug_canary_head_argmax(int device, const float* xn, int M, int K, int V, const float* W, const float* bias, float* logits, int32_t* index,
                                         float* value);
+mis_status mis_debug_canary_lin_bf16(int device, const float* X, int Mrows, int M, int K, int N, const uint16_t* W, const float* bias, int relu, int S,
+                                     float* out, int32_t* index);
+mis_status mis_debug_canary_attn_step_bf16(int device, const float* q, const uint16_t* kv, const int32_t* cnt, int batch, int cap, int heads, int hd, float* out);
 mis_status mis_debug_canary_timing(mis_canary*, float* ms);
 
 /* csrc/token_engine.hip (round 5): a whole batch-1 request in ONE persistent launch on the compute units of `xcds` (1, 2, 4 or 8) XCDs,

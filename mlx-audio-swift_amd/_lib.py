@@ -509,6 +509,7 @@ SYMBOLS = {
     "mis_canary_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_canary_init_synthetic": (C.c_int, [_P, C.c_uint64]),
     "mis_canary_set_encoder_dtype": (C.c_int, [_P, C.c_int]),
+    "mis_canary_set_decoder_dtype": (C.c_int, [_P, C.c_int]),
     "mis_canary_finalize": (C.c_int, [_P]),
     "mis_canary_destroy": (None, [_P]),
     "mis_canary_launches": (C.c_int, [_P]),
@@ -734,6 +735,8 @@ DEBUG_SYMBOLS = {
     "mis_debug_canary_lin": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "mis_debug_canary_attn_step": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_canary_head_argmax": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mis_debug_canary_lin_bf16": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_canary_attn_step_bf16": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_canary_timing": (C.c_int, [_P, _P]),
     "mis_debug_nemotron_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),

@@ -16,7 +16,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._handle import NativeHandle, pack_rows, read_safetensors_dir
+from ._handle import _ENCODER_DTYPES, NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 from .lasr import SentencePieceTokenizer
 from .parakeet import parakeet_sanitize, _perm
@@ -101,6 +101,7 @@ class CanaryConfig:
     max_tokens: int = 200
     max_prompt: int = 16
     encoder_dtype: str = "float32"   # "bfloat16": the encoder's Conformer blocks in bf16 (csrc/parakeet_encoder_bf16.h); not part of a checkpoint
+    decoder_dtype: str = "float32"   # "bfloat16": the step's matrices and K/V stores in bf16 (mi_speech.h's contract); not part of a checkpoint
 
     @classmethod
     def from_dict(cls, d: dict, **workspace) -> "CanaryConfig":
@@ -364,28 +365,45 @@ class CanaryModel(NativeHandle):
         self._create(config.to_c(), device)
         if config.encoder_dtype != "float32":
             self.set_encoder_dtype(config.encoder_dtype)
+        if config.decoder_dtype != "float32":
+            self.set_decoder_dtype(config.decoder_dtype)
 
     sanitize = staticmethod(canary_sanitize)
 
+    def set_decoder_dtype(self, name: str):
+        """"float32" (the default) or "bfloat16", before finalize; independent of the encoder's dtype."""
+        if name not in _ENCODER_DTYPES:
+            raise _bad(f"decoder_dtype {name!r}: only {sorted(_ENCODER_DTYPES)} are implemented")
+        check(_lib.lib().mis_canary_set_decoder_dtype(self._h, _ENCODER_DTYPES[name]))
+        self.config = replace(self.config, decoder_dtype=name)
+
+    @staticmethod
+    def _with_dtypes(config, encoder_dtype, decoder_dtype):
+        kw = {k: v for k, v in (("encoder_dtype", encoder_dtype), ("decoder_dtype", decoder_dtype)) if v}
+        return replace(config, **kw) if kw else config
+
     @classmethod
-    def from_weights(cls, config: CanaryConfig, weights: dict, tokenizer=None, device: int = 0, encoder_dtype: str | None = None) -> "CanaryModel":
-        """weights: the engine's names (what canary_sanitize returns); encoder_dtype overrides the config's."""
-        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, tokenizer, device)
+    def from_weights(cls, config: CanaryConfig, weights: dict, tokenizer=None, device: int = 0, encoder_dtype: str | None = None,
+                     decoder_dtype: str | None = None) -> "CanaryModel":
+        """weights: the engine's names (what canary_sanitize returns); encoder_dtype / decoder_dtype override the config's."""
+        m = cls(cls._with_dtypes(config, encoder_dtype, decoder_dtype), tokenizer, device)
         for name, arr in weights.items():
             m.set_tensor(name, arr)
         m.finalize()
         return m
 
     @classmethod
-    def synthetic(cls, config: CanaryConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None) -> "CanaryModel":
-        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, None, device)
+    def synthetic(cls, config: CanaryConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None,
+                  decoder_dtype: str | None = None) -> "CanaryModel":
+        m = cls(cls._with_dtypes(config, encoder_dtype, decoder_dtype), None, device)
         check(_lib.lib().mis_canary_init_synthetic(m._h, seed))
         m.finalize()
         return m
 
     @classmethod
     def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "CanaryModel":
-        """fromModelDirectory (:510-533): config.json, the tokenizer files, every *.safetensors; keys the model does not have are rejected."""
+        """fromModelDirectory (:510-533): config.json, the tokenizer files, every *.safetensors; keys the model does not have are rejected.
+        workspace: max_batch / max_seconds / max_tokens / max_prompt / encoder_dtype / decoder_dtype."""
         with open(os.path.join(model_dir, "config.json")) as f:
             config = CanaryConfig.from_dict(json.load(f), **workspace)
 
@@ -415,7 +433,8 @@ class CanaryModel(NativeHandle):
     def expected_launches(self, steps: int = 0) -> dict:
         c = self.config
         enc = 7 + 15 * c.encoder.n_layers + int(c.encoder.d_model != c.enc_output_dim)
-        return dict(encode=enc, generate=enc + c.decoder.num_layers + 1 + steps * (11 * c.decoder.num_layers + 2))
+        cross = c.decoder.num_layers * (2 if c.decoder_dtype == "bfloat16" else 1)      # bf16: the f32 projection + the rounding into the store
+        return dict(encode=enc, generate=enc + cross + 1 + steps * (11 * c.decoder.num_layers + 2))
 
     def frames(self, lens):
         n = np.ascontiguousarray(lens, dtype=np.int64)

@@ -2,7 +2,8 @@
 // stem, FastConformer blocks) -> optional projection -> the cross-attention K and V of every decoder layer, once -> a pre-LN Transformer
 // decoder run ONE TOKEN A STEP over cached K/V, with the vocabulary head fused with the arg-max and the token bookkeeping on the device.
 // Exact f32 throughout, unless mis_canary_set_encoder_dtype(MIS_BF16) selects the bf16 form of the encoder's Conformer blocks
-// (parakeet_encoder_bf16.h); the decoder is f32 in both modes.
+// (parakeet_encoder_bf16.h) and mis_canary_set_decoder_dtype(MIS_BF16) the bf16 form of the decoder's step: the step matrices and both
+// K | V stores as bf16, k_cn_lin_bf16 and k_cn_attn_step_bf16 in place of k_cn_lin and k_cn_attn_step (precision contract: mi_speech.h).
 //
 // Reference being replaced: CanaryModel (Sources/MLXAudioSTT/Models/Canary/CanaryModel.swift generate :385-432, CanaryDecoder :288-329,
 // CanaryDecoderBlock :245-286, CanaryAttention :200-243, CanaryFixedPositionalEncoding :166-198).  The reference re-runs the whole prefix
@@ -27,6 +28,7 @@
 //                   -> x, then layer 0's self_attn_norm -> xn.
 //
 // Launches: encode = 7 + 15 L_enc (+ 1 with a projection); generate = that + L_dec (cross K/V) + 1 (first input) + steps (11 L_dec + 2).
+// The bf16 decoder keeps the f32 projection of the cross K/V and rounds each layer into its bf16 store: 2 L_dec there, the step unchanged.
 #include "common.h"
 #define AUDIO_FRONT_NEMO_KERNELS
 #include "audio_front.h"
@@ -58,6 +60,7 @@ struct CnLin {
     int relu;
     float* kv; const int* pos; int cap, kvoff;                       // columns >= kvoff -> kv[(m cap + pos[m]) (N - kvoff) + n - kvoff]
     float* amv; int* ami; int nt;                                    // the head: per row and tile (max, lowest index) [M][nt]
+    const bf16_t* Wb; bf16_t* kvb;                                   // the bf16 decoder (k_cn_lin_bf16): W and the self K/V cache as bf16
 };
 
 template <int MT>
@@ -137,6 +140,141 @@ __global__ void __launch_bounds__(256) k_cn_lin(CnLin p) {
     }
 }
 
+// ---------------------------------------------------------------------------- the same contraction with bf16 weights (the bf16 decoder)
+// Y[M, N] = bf16(X)[M, K] Wb[N, K]^T on v_mfma_f32_16x16x32_bf16, f32 accumulators; the outer shape is k_cn_lin's (32 columns a block,
+// grid (ceil(N / 32), S), slabs of 128, wave w owns the slab's columns 32 w .. 32 w + 31 = one MFMA k-step) and so are cn_split_for, part,
+// k_cn_rows, the pairs and k_cn_select.  W is the A operand: lane (n = lane & 15, kq = lane >> 4) loads the 8 bf16
+// W[n0 + 16 t + n][k0 + 32 w + 8 kq ..] of tile t = 0, 1 as one 16-byte load, straight into registers, the next slab's while this one is
+// contracted: every weight byte is read once, by one wave.  X is the B operand: the block stages X[0..16 MT)[slab] through LDS, rounded to
+// bf16 as it is staged (row stride 136 elements = 272 bytes: 16-byte fragments stay aligned and the 16 rows of one kq start 4 banks apart),
+// and both column tiles share the fragment.  C/D: lane l, element e = column 16 t + 4 (l >> 4) + e of row 16 mt + (l & 15): four
+// consecutive n of one row, so Y, part and cache stores are 16 (bf16: 8) bytes along n.  Waves 1..3 hand their accumulators to wave 0
+// through LDS; wave 0 adds them in wave order and runs k_cn_lin's epilogue.  K % 32 == 0; N, M and the last slab are guarded.
+#define CNB_LDX 136
+
+__device__ __forceinline__ uint32_t cnb_pack2(float a, float b) { return (uint32_t)f32_to_bf16(a) | ((uint32_t)f32_to_bf16(b) << 16); }
+
+template <int MT>
+__global__ void __launch_bounds__(256) k_cn_lin_bf16(CnLin p) {
+    __shared__ f32x4_t Red[3 * 2 * MT * 64];                         // first the staged slab (4352 MT of its 6144 MT bytes), then the accumulators of waves 1..3
+    bf16_t* Xs = reinterpret_cast<bf16_t*>(Red);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, kq = lane >> 4;
+    const int n0 = blockIdx.x * 32, s = blockIdx.y, kl = 32 * wave + 8 * kq;
+    const bf16_t* wrow[2];
+    bool wlive[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int nrow = n0 + 16 * t + l15;
+        wlive[t] = nrow < p.N;
+        wrow[t] = p.Wb + (size_t)(wlive[t] ? nrow : 0) * p.K + kl;
+    }
+    f32x4_t acc[2][MT];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[t][mt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+    const int ns = (p.K + CN_KS - 1) / CN_KS, sl0 = s * p.sps, sl1 = min((s + 1) * p.sps, ns);
+    bf16x8_t wn[2];
+    auto loadw = [&](int sl) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            wn[t] = (wlive[t] && sl * CN_KS + kl + 8 <= p.K) ? *reinterpret_cast<const bf16x8_t*>(wrow[t] + (size_t)sl * CN_KS) : (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+    };
+    if (sl0 < sl1) loadw(sl0);
+    for (int sl = sl0; sl < sl1; ++sl) {
+        const int k0 = sl * CN_KS;
+        __syncthreads();                                             // the previous slab's reads are done
+        for (int i = tid; i < MT * 16 * (CN_KS / 4); i += 256) {     // four floats a thread -> four bf16, rounded here, once
+            const int r = i >> 5, cc = (i & 31) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < p.M && k0 + cc < p.K) v = *reinterpret_cast<const float4*>(p.X + (size_t)r * p.ldx + k0 + cc);
+            *reinterpret_cast<uint2*>(Xs + r * CNB_LDX + cc) = make_uint2(cnb_pack2(v.x, v.y), cnb_pack2(v.z, v.w));
+        }
+        __syncthreads();
+        const bf16x8_t w0 = wn[0], w1 = wn[1];
+        if (sl + 1 < sl1) loadw(sl + 1);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8_t x = *reinterpret_cast<const bf16x8_t*>(Xs + (mt * 16 + l15) * CNB_LDX + kl);
+            acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, x, acc[0][mt], 0, 0, 0);
+            acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x, acc[1][mt], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    if (wave > 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) Red[(((wave - 1) * 2 + t) * MT + mt) * 64 + lane] = acc[t][mt];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int w = 1; w < 4; ++w)                                      // wave 0 + 1 + 2 + 3, in that order
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const f32x4_t o = Red[(((w - 1) * 2 + t) * MT + mt) * 64 + lane];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t][mt][e] += o[e];
+            }
+    const bool vec = ((p.N | p.ldy | p.kvoff) & 3) == 0;             // a lane's four columns are one aligned store
+    const int kvw = p.N - p.kvoff;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int m = mt * 16 + l15;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int nq = n0 + 16 * t + 4 * kq;
+            if (m >= p.M || nq >= p.N) continue;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = acc[t][mt][e];
+            if (p.part) {
+                float* dst = p.part + ((size_t)s * p.M + m) * p.N + nq;
+                if (vec) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+                else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) if (nq + e < p.N) dst[e] = v[e];
+                }
+                continue;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (nq + e >= p.N) continue;
+                if (p.bias) v[e] += p.bias[nq + e];
+                if (p.relu) v[e] = fmaxf(v[e], 0.0f);
+                if (v[e] > bv) { bv = v[e]; bi = nq + e; }               // columns ascend inside the lane: the lowest index of equal maxima
+            }
+            const size_t kvrow = p.kvb ? ((size_t)m * p.cap + min(p.pos[m], p.cap - 1)) * kvw : 0;
+            if (vec) {
+                if (p.kvb && nq >= p.kvoff) *reinterpret_cast<uint2*>(p.kvb + kvrow + (nq - p.kvoff)) = make_uint2(cnb_pack2(v[0], v[1]), cnb_pack2(v[2], v[3]));
+                else if (p.Y) *reinterpret_cast<float4*>(p.Y + (size_t)m * p.ldy + nq) = make_float4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int n = nq + e;
+                    if (n >= p.N) continue;
+                    if (p.kvb && n >= p.kvoff) p.kvb[kvrow + (n - p.kvoff)] = f32_to_bf16(v[e]);
+                    else if (p.Y) p.Y[(size_t)m * p.ldy + n] = v[e];
+                }
+            }
+        }
+        if (p.amv) {                                                 // (uniform) the four lanes of a row, by k_cn_select's rule
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            if (kq == 0 && m < p.M) { p.amv[(size_t)m * p.nt + blockIdx.x] = bv; p.ami[(size_t)m * p.nt + blockIdx.x] = bi; }
+        }
+    }
+}
+
 // S for a split role, from N alone: the power of two up to 8 with which ceil(N / 32) S first reaches 256 blocks
 static int cn_split_for(int N) {
     const int tiles = cdiv(N, 32);
@@ -149,7 +287,11 @@ template <class Ctx>
 static void cn_lin(Ctx* c, CnLin p, int S) {
     p.sps = cdiv(cdiv(p.K, CN_KS), S);
     const dim3 grid(cdiv(p.N, 32), S);
-    if (p.M <= 32) MIS_LAUNCH(c, k_cn_lin<1>, grid, dim3(256), p);
+    if (p.Wb) {                                                      // the bf16 decoder: 16-row tiles, M <= 16 / 32 / 64
+        if (p.M <= 16) MIS_LAUNCH(c, k_cn_lin_bf16<1>, grid, dim3(256), p);
+        else if (p.M <= 32) MIS_LAUNCH(c, k_cn_lin_bf16<2>, grid, dim3(256), p);
+        else MIS_LAUNCH(c, k_cn_lin_bf16<4>, grid, dim3(256), p);
+    } else if (p.M <= 32) MIS_LAUNCH(c, k_cn_lin<1>, grid, dim3(256), p);
     else MIS_LAUNCH(c, k_cn_lin<2>, grid, dim3(256), p);
 }
 
@@ -210,6 +352,7 @@ struct CnAttn {
     int cap; const int* capd;                                        // rows of a batch entry (capd: read from the device instead)
     const int* cnt; int cnt_add;                                     // keys of row m: cnt[m] + cnt_add, at most cap
     float* out; int ldo; int hd; float scale;
+    const bf16_t* kvb;                                               // the bf16 decoder (k_cn_attn_step_bf16): the store as bf16, same layout
 };
 
 __global__ void __launch_bounds__(256) k_cn_attn_step(CnAttn p) {
@@ -259,6 +402,83 @@ __global__ void __launch_bounds__(256) k_cn_attn_step(CnAttn p) {
         for (int w = 0; w < 4; ++w) { const float f = expf(Ms[w] - mt); l += Ls[w] * f; a += As[w][tid] * f; }
         p.out[(size_t)m * p.ldo + hh * hd + tid] = a / l;
     }
+}
+
+// k_cn_attn_step over a bf16 K | V store: the same split (a block a (row, head), 32-key tiles round-robin over four waves, online softmax per
+// wave, the four (m, l, acc) merged through LDS in wave order) and the same f32 arithmetic on the widened values - no MFMA, nothing rounded.
+// Score: the lane pair (key, half of the head) reads its half of the key row as 16-byte chunks of 8 bf16 and accumulates in ascending
+// dimension against the f32 query in LDS.  P V: the lane owns dimensions 2 lane and 2 lane + 1, one 4-byte load a key.
+__global__ void __launch_bounds__(256) k_cn_attn_step_bf16(CnAttn p) {
+    __shared__ float Qs[128], Ms[4], Ls[4], As[4][128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
+    const int m = blockIdx.x, hh = blockIdx.y, hd = p.hd, cap = p.capd ? *p.capd : p.cap, n = max(1, min(p.cnt[m] + p.cnt_add, cap));
+    const int HP = hd <= 64 ? 64 : 128, half = HP / 2;               // the head, zero-padded to 64 or 128
+    const int d0 = kh * half, d1 = min(hd, (kh + 1) * half);
+    const bool vec = ((hd | p.ld) & 7) == 0, pair = ((hd | p.ld | p.voff) & 1) == 0;
+    if (tid < 128) Qs[tid] = tid < hd ? p.q[(size_t)m * p.ldq + hh * hd + tid] : 0.0f;
+    __syncthreads();
+    const bf16_t* base = p.kvb + (size_t)m * cap * p.ld + hh * hd;
+    float m_run = -INFINITY, l_run = 0.0f, a0 = 0.0f, a1 = 0.0f;
+    for (int kb = 32 * wave; kb < n; kb += 128) {
+        const int key = kb + l31;
+        float part = 0.0f;
+        if (key < n) {
+            const bf16_t* kr = base + (size_t)key * p.ld;
+            for (int dd = d0; dd < d1; dd += 8) {                    // (columns >= d1 of the last chunk: zeros against Qs' zeros)
+                const uint4 c = pkb_chunk(kr, dd, d1, vec);
+                const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    part = fmaf(Qs[dd + 2 * e], __uint_as_float(w[e] << 16), part);
+                    part = fmaf(Qs[dd + 2 * e + 1], __uint_as_float(w[e] & 0xffff0000u), part);
+                }
+            }
+        }
+        const float other = __shfl_xor(part, 32, 64);
+        const float sc = key < n ? (kh == 0 ? part + other : other + part) * p.scale : -INFINITY;   // lower half + upper half, on both lanes
+        float mx = sc;
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        const float m_new = fmaxf(m_run, mx);                        // finite: key kb < n
+        const float alpha = expf(m_run - m_new), pr = key < n ? expf(sc - m_new) : 0.0f;
+        float ps = pr;
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) ps += __shfl_xor(ps, o, 64);
+        l_run = l_run * alpha + ps;
+        m_run = m_new;
+        a0 *= alpha; a1 *= alpha;
+        const int nk = min(32, n - kb);
+        for (int j = 0; j < nk; ++j) {                               // keys in order
+            const float pj = __shfl(pr, j, 64);
+            const bf16_t* vr = base + (size_t)(kb + j) * p.ld + p.voff;
+            if (pair) {
+                if (2 * lane < hd) {
+                    const uint32_t u = *reinterpret_cast<const uint32_t*>(vr + 2 * lane);
+                    a0 = fmaf(pj, __uint_as_float(u << 16), a0);
+                    a1 = fmaf(pj, __uint_as_float(u & 0xffff0000u), a1);
+                }
+            } else {
+                if (2 * lane < hd) a0 = fmaf(pj, bf16_to_f32(vr[2 * lane]), a0);
+                if (2 * lane + 1 < hd) a1 = fmaf(pj, bf16_to_f32(vr[2 * lane + 1]), a1);
+            }
+        }
+    }
+    if (lane == 0) { Ms[wave] = m_run; Ls[wave] = l_run; }
+    As[wave][2 * lane] = a0; As[wave][2 * lane + 1] = a1;
+    __syncthreads();
+    if (tid < hd) {
+        const float mt = fmaxf(fmaxf(Ms[0], Ms[1]), fmaxf(Ms[2], Ms[3]));    // wave 0 always holds key 0
+        float l = 0.0f, a = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const float f = expf(Ms[w] - mt); l += Ls[w] * f; a += As[w][tid] * f; }
+        p.out[(size_t)m * p.ldo + hh * hd + tid] = a / l;
+    }
+}
+
+// the cross K | V of one layer between the f32 projection and the bf16 store (k_pk_round_bf16 rounds it in), and back for mis_canary_tap
+__global__ void __launch_bounds__(256) k_cn_widen_bf16(const bf16_t* __restrict__ x, float* __restrict__ y, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = bf16_to_f32(x[i]);
 }
 
 // ============================================================================ token bookkeeping and the next input
@@ -343,8 +563,13 @@ struct mis_canary : PkEncoder {
     struct DLayer {
         const float *n1w, *n1b, *n2w, *n2b, *n3w, *n3b;
         SfLin qkv, so, cq, ckv, co, ff1, ff2;
+        bf16_t *qkv16, *so16, *cq16, *co16, *ff116, *ff216;          // dec_bf16: these six matrices live in the bf16 arena only (SfLin::w null)
     };
     std::vector<DLayer> dl;
+    bool dec_bf16 = false;                                           // mis_canary_set_decoder_dtype(MIS_BF16)
+    bf16_t* head16 = nullptr;
+    DevBuf<bf16_t> ckv16, skv16;                                     // dec_bf16: the K | V stores, in place of ckv and skv
+    DevBuf<float> ckvf;                                              // dec_bf16: one layer of cross K | V in f32, between the projection and the store
     DevBuf<float> encp, ckv, skv, x, xn, q, att, ff, part, amv, logits;
     DevBuf<int> ami, toks, st, prompt;                               // st: pos, ngen, done, plen [B] each, then done_count, Tp
     PinnedBuf<int> done_host;
@@ -422,6 +647,20 @@ extern "C" mis_status mis_canary_set_encoder_dtype(mis_canary* c, mis_dtype dtyp
     MIS_API_END
 }
 
+// f32 (the default) or bf16, before finalize, whatever the encoder's dtype; bf16 needs whole MFMA k-steps in both contraction lengths
+extern "C" mis_status mis_canary_set_decoder_dtype(mis_canary* c, mis_dtype dtype) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c, MIS_ERR_INVALID_INPUT, "null argument");
+    MIS_REQUIRE(!c->finalized, MIS_ERR_INVALID_INPUT, "set_decoder_dtype after finalize");
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "decoder dtype %d: only MIS_F32 and MIS_BF16 are implemented", (int)dtype);
+    if (dtype == MIS_BF16) {
+        MIS_REQUIRE(c->cfg.enc_output_dim % 32 == 0, MIS_ERR_INVALID_INPUT, "enc_output_dim %d: the bf16 decoder needs a multiple of 32", c->cfg.enc_output_dim);
+        MIS_REQUIRE(c->cfg.dec_inner_size % 32 == 0, MIS_ERR_INVALID_INPUT, "dec_inner_size %d: the bf16 decoder needs a multiple of 32", c->cfg.dec_inner_size);
+    }
+    c->dec_bf16 = dtype == MIS_BF16;
+    MIS_API_END
+}
+
 static const char* const CN_ATT[4] = {"q_proj", "k_proj", "v_proj", "out_proj"};
 
 extern "C" mis_status mis_canary_finalize(mis_canary* c) {
@@ -433,14 +672,23 @@ extern "C" mis_status mis_canary_finalize(mis_canary* c) {
     pk_encoder_weights(c, a);
     std::vector<float>& fh = a.fhost;
     auto lin = [&](const std::string& p, int64_t N, int64_t K, SfLin& l) { a.fvec(p + ".weight", {N, K}, N * K, l.w); a.fvec(p + ".bias", {N}, N, l.b); };
+    const bool b16 = c->dec_bf16;
+    // a matrix of the step: the f32 arena, or rounded once into the bf16 arena (and then there only); the bias is f32 in both modes
+    auto slin = [&](const std::string& p, int64_t N, int64_t K, SfLin& l, bf16_t*& wb) {
+        if (!b16) { lin(p, N, K, l); return; }
+        a.bmat(p + ".weight", N, K, wb);
+        a.fvec(p + ".bias", {N}, N, l.b);
+    };
     auto norm = [&](const std::string& p, const float*& w, const float*& b) { a.fvec(p + ".weight", {h}, h, w); a.fvec(p + ".bias", {h}, h, b); };
     // several projections over the same input as one [n h][h], bias [n h]
-    auto stacked = [&](const std::string& p, int first, int n, SfLin& l) {
-        const size_t ow = a.ftake((size_t)n * h * h, l.w), ob = a.ftake(n * h, l.b);
+    auto stacked = [&](const std::string& p, int first, int n, SfLin& l, bf16_t** wb) {      // wb null: f32 in both modes
+        const bool to16 = b16 && wb;
+        const size_t ow = to16 ? a.btake((size_t)n * h * h, *wb) : a.ftake((size_t)n * h * h, l.w), ob = a.ftake(n * h, l.b);
         for (int i = 0; i < n; ++i) {
             const HostTensor& w = c->raw.need(p + CN_ATT[first + i] + ".weight", {h, h});
             const HostTensor& bb = c->raw.need(p + CN_ATT[first + i] + ".bias", {h});
-            std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * h * h);
+            if (to16) for (int64_t j = 0; j < h * h; ++j) a.host[ow + (size_t)i * h * h + j] = f32_to_bf16(w.v[j]);
+            else std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * h * h);
             std::copy(bb.v.begin(), bb.v.end(), fh.begin() + ob + (size_t)i * h);
         }
     };
@@ -452,17 +700,17 @@ extern "C" mis_status mis_canary_finalize(mis_canary* c) {
         const std::string q = "decoder.blocks." + std::to_string(li) + ".";
         mis_canary::DLayer& l = c->dl[li];
         norm(q + "self_attn_norm", l.n1w, l.n1b);
-        stacked(q + "self_attn.", 0, 3, l.qkv);
-        lin(q + "self_attn.out_proj", h, h, l.so);
+        stacked(q + "self_attn.", 0, 3, l.qkv, &l.qkv16);
+        slin(q + "self_attn.out_proj", h, h, l.so, l.so16);
         norm(q + "cross_attn_norm", l.n2w, l.n2b);
-        stacked(q + "cross_attn.", 0, 1, l.cq);
-        stacked(q + "cross_attn.", 1, 2, l.ckv);
-        lin(q + "cross_attn.out_proj", h, h, l.co);
+        stacked(q + "cross_attn.", 0, 1, l.cq, &l.cq16);
+        stacked(q + "cross_attn.", 1, 2, l.ckv, nullptr);              // projected once a call by the f32 GEMM in both modes: stays f32
+        slin(q + "cross_attn.out_proj", h, h, l.co, l.co16);
         norm(q + "ff_norm", l.n3w, l.n3b);
-        lin(q + "ff1", inner, h, l.ff1); lin(q + "ff2", h, inner, l.ff2);
+        slin(q + "ff1", inner, h, l.ff1, l.ff116); slin(q + "ff2", h, inner, l.ff2, l.ff216);
     }
     norm("decoder.final_norm", c->fw, c->fb_);
-    lin("decoder.output_proj", V, h, c->head);
+    slin("decoder.output_proj", V, h, c->head, c->head16);
     {   // the fixed sinusoid: sin | cos interleaved, frequency 10000^(-c / h) with c the even column, all over sqrt(h); formed in double, rounded once
         const size_t o = a.ftake((size_t)CN_POS_ROWS * h, c->postab_dec);
         const double rs = 1.0 / sqrt((double)h);
@@ -477,8 +725,8 @@ extern "C" mis_status mis_canary_finalize(mis_canary* c) {
     pk_encoder_workspace(c);
     const size_t B = c->cfg.max_batch, M = B * c->Tcap;
     if (d != h) c->encp.alloc(M * h);
-    c->ckv.alloc(c->ckv_layer() * c->Ld);
-    c->skv.alloc(c->skv_layer() * c->Ld);
+    if (b16) { c->ckv16.alloc(c->ckv_layer() * c->Ld); c->skv16.alloc(c->skv_layer() * c->Ld); c->ckvf.alloc(c->ckv_layer()); }
+    else { c->ckv.alloc(c->ckv_layer() * c->Ld); c->skv.alloc(c->skv_layer() * c->Ld); }
     c->x.alloc(B * h); c->xn.alloc(B * h); c->q.alloc(B * h); c->att.alloc(B * h); c->ff.alloc(B * inner); c->part.alloc((size_t)8 * B * h);
     c->amv.alloc(B * c->NT); c->ami.alloc(B * c->NT); c->logits.alloc(B * V);
     c->st.alloc(4 * B + 2); c->prompt.alloc(B * c->cfg.max_prompt); c->toks.alloc(B * c->cfg.max_tokens);
@@ -511,6 +759,7 @@ extern "C" mis_status mis_canary_init_synthetic(mis_canary* c, uint64_t seed) {
 }
 
 // ============================================================================ the chain
+// (the bf16 decoder: the cross K/V form built is the f32 sf_gemm projection + k_pk_round_bf16 a layer, L_dec launches more in generate)
 extern "C" int mis_canary_launches(const mis_canary* c) { return c ? c->launches : 0; }
 
 extern "C" mis_status mis_canary_frames(const mis_canary* c, const int64_t* lens, int batch, int32_t* F_out, int32_t* T_out) {
@@ -538,16 +787,22 @@ static void cn_project(mis_canary* c) {
 }
 
 // K | V of every decoder layer over all B Tp frames: L_dec launches of width 2 h, rows [b Tp + t]
+// dec_bf16: each layer through the one-layer f32 buffer, rounded into the bf16 store (2 L_dec launches)
 static void cn_cross_kv(mis_canary* c) {
-    for (int li = 0; li < c->Ld; ++li)
-        sf_gemm(c, sf_lin(c->enc_out(), c->hw, c->dl[li].ckv, c->ckv.p + li * c->ckv_layer(), 2 * c->hw, c->cnt3.p, c->Tp), c->batch);
+    const size_t n = (size_t)c->batch * c->Tp * 2 * c->hw;
+    for (int li = 0; li < c->Ld; ++li) {
+        float* dst = c->dec_bf16 ? c->ckvf.p : c->ckv.p + li * c->ckv_layer();
+        sf_gemm(c, sf_lin(c->enc_out(), c->hw, c->dl[li].ckv, dst, 2 * c->hw, c->cnt3.p, c->Tp), c->batch);
+        if (c->dec_bf16) MIS_LAUNCH(c, k_pk_round_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), dst, c->ckv16.p + li * c->ckv_layer(), n);
+    }
     HIP_CHECK(hipMemcpyAsync(c->tp_dev(), &c->Tp, 4, hipMemcpyHostToDevice, c->stream));
     c->has_kv = true;
 }
 
-static CnLin cn_lin_args(const float* X, int K, const SfLin& l, int M, int N) {
+// wb: the matrix in the bf16 arena (the bf16 decoder; l.w is null then), which selects k_cn_lin_bf16 in cn_lin
+static CnLin cn_lin_args(const float* X, int K, const SfLin& l, int M, int N, const bf16_t* wb = nullptr) {
     CnLin p{};
-    p.X = X; p.ldx = K; p.W = l.w; p.bias = l.b; p.M = M; p.K = K; p.N = N;
+    p.X = X; p.ldx = K; p.W = l.w; p.Wb = wb; p.bias = l.b; p.M = M; p.K = K; p.N = N;
     return p;
 }
 
@@ -556,8 +811,9 @@ static void cn_layer(mis_canary* c, int li, int B, const float* nextw, const flo
     const mis_canary::DLayer& l = c->dl[li];
     const int h = c->hw, S = c->S_h;
     const float scale = 1.0f / sqrtf((float)c->hdd);
-    auto split = [&](const float* X, int K, const SfLin& w) {
-        CnLin p = cn_lin_args(X, K, w, B, h);
+    const bool b16 = c->dec_bf16;
+    auto split = [&](const float* X, int K, const SfLin& w, const bf16_t* wb) {
+        CnLin p = cn_lin_args(X, K, w, B, h, wb);
         p.bias = nullptr; p.part = c->part.p;
         cn_lin(c, p, S);
     };
@@ -565,31 +821,35 @@ static void cn_layer(mis_canary* c, int li, int B, const float* nextw, const flo
         CnRows r{c->x.p, c->xn.p, w.b, c->part.p, S, B, h, lw, lb};
         MIS_LAUNCH(c, k_cn_rows, dim3(B), dim3(256), r);
     };
-    float* skv = c->skv.p + li * c->skv_layer();
+    auto attn = [&](const CnAttn& a) {
+        if (b16) MIS_LAUNCH(c, k_cn_attn_step_bf16, dim3(B, c->Hd), dim3(256), a);
+        else MIS_LAUNCH(c, k_cn_attn_step, dim3(B, c->Hd), dim3(256), a);
+    };
+    float* skv = b16 ? nullptr : c->skv.p + li * c->skv_layer();
+    bf16_t* skv16 = b16 ? c->skv16.p + li * c->skv_layer() : nullptr;
     {
-        CnLin p = cn_lin_args(c->xn.p, h, l.qkv, B, 3 * h);
-        p.Y = c->q.p; p.ldy = h; p.kv = skv; p.pos = c->pos(); p.cap = c->cap; p.kvoff = h;
+        CnLin p = cn_lin_args(c->xn.p, h, l.qkv, B, 3 * h, l.qkv16);
+        p.Y = c->q.p; p.ldy = h; p.kv = skv; p.kvb = skv16; p.pos = c->pos(); p.cap = c->cap; p.kvoff = h;
         cn_lin(c, p, 1);
     }
-    CnAttn sa{c->q.p, h, skv, 2 * h, h, c->cap, nullptr, c->pos(), 1, c->att.p, h, c->hdd, scale};
-    MIS_LAUNCH(c, k_cn_attn_step, dim3(B, c->Hd), dim3(256), sa);
-    split(c->att.p, h, l.so);
+    attn(CnAttn{c->q.p, h, skv, 2 * h, h, c->cap, nullptr, c->pos(), 1, c->att.p, h, c->hdd, scale, skv16});
+    split(c->att.p, h, l.so, l.so16);
     rows(l.so, l.n2w, l.n2b);
     {
-        CnLin p = cn_lin_args(c->xn.p, h, l.cq, B, h);
+        CnLin p = cn_lin_args(c->xn.p, h, l.cq, B, h, l.cq16);
         p.Y = c->q.p; p.ldy = h;
         cn_lin(c, p, 1);
     }
-    CnAttn ca{c->q.p, h, c->ckv.p + li * c->ckv_layer(), 2 * h, h, 0, c->tp_dev(), c->cnt3.p, 0, c->att.p, h, c->hdd, scale};
-    MIS_LAUNCH(c, k_cn_attn_step, dim3(B, c->Hd), dim3(256), ca);
-    split(c->att.p, h, l.co);
+    attn(CnAttn{c->q.p, h, b16 ? nullptr : c->ckv.p + li * c->ckv_layer(), 2 * h, h, 0, c->tp_dev(), c->cnt3.p, 0, c->att.p, h, c->hdd, scale,
+                b16 ? c->ckv16.p + li * c->ckv_layer() : nullptr});
+    split(c->att.p, h, l.co, l.co16);
     rows(l.co, l.n3w, l.n3b);
     {
-        CnLin p = cn_lin_args(c->xn.p, h, l.ff1, B, c->inner);
+        CnLin p = cn_lin_args(c->xn.p, h, l.ff1, B, c->inner, l.ff116);
         p.Y = c->ff.p; p.ldy = c->inner; p.relu = 1;
         cn_lin(c, p, 1);
     }
-    split(c->ff.p, c->inner, l.ff2);
+    split(c->ff.p, c->inner, l.ff2, l.ff216);
     rows(l.ff2, nextw, nextb);
 }
 
@@ -601,7 +861,7 @@ static void cn_layers(mis_canary* c, int B) {
 }
 
 static void cn_head(mis_canary* c, int B, float* logits) {
-    CnLin p = cn_lin_args(c->xn.p, c->hw, c->head, B, c->V);
+    CnLin p = cn_lin_args(c->xn.p, c->hw, c->head, B, c->V, c->head16);
     p.Y = logits; p.ldy = c->V; p.amv = c->amv.p; p.ami = c->ami.p; p.nt = c->NT;
     cn_lin(c, p, 1);
 }
@@ -745,8 +1005,11 @@ extern "C" mis_status mis_canary_tap(mis_canary* c, int stage, float* out, int64
     const int kept = c->launches;
     if (stage >= 1) pk_encoder(c, stage > c->L ? -1 : stage);        // the chain is deterministic: recomputed from the embeddings
     if (stage == c->L + 1) cn_project(c);
+    if (stage > c->L + 1 && c->dec_bf16)                             // the bf16 store, widened
+        MIS_LAUNCH(c, k_cn_widen_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), c->ckv16.p + (stage - c->L - 2) * c->ckv_layer(), c->ckvf.p, n);
     c->launches = kept;
-    const float* src = stage == 0 ? c->emb.p : stage <= c->L ? c->h.p : stage == c->L + 1 ? c->enc_out() : c->ckv.p + (stage - c->L - 2) * c->ckv_layer();
+    const float* src = stage == 0 ? c->emb.p : stage <= c->L ? c->h.p : stage == c->L + 1 ? c->enc_out()
+                     : c->dec_bf16 ? c->ckvf.p : c->ckv.p + (stage - c->L - 2) * c->ckv_layer();
     HIP_CHECK(hipMemcpyAsync(out, src, n * 4, hipMemcpyDeviceToHost, c->stream));
     cn_sync(c);
     MIS_API_END
@@ -879,5 +1142,91 @@ extern "C" mis_status mis_debug_canary_head_argmax(int device, const float* xn, 
         if (value) value[m] = bv;
     }
     if (logits) HIP_CHECK(hipMemcpy(logits, o.p(), (size_t)M * V * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// k_cn_lin_bf16 on caller-supplied host data, as mis_debug_canary_lin: X f32 [Mrows][K] (M live rows), W bf16 bits [N][K], K % 32 == 0, bias
+// [N] or NULL, S forced by the caller.  index NULL: S = 1 is ONE launch into out [M][N]; S > 1 the partial launch and one k_cn_rows (x = 0,
+// bias; relu refused).  index [M] given: the launch as the head runs it (S = 1, pairs; out may be NULL: then no logit reaches memory), the
+// pairs combined here by k_cn_select's rule.  Every input is followed by NaNs; every output is guarded.
+extern "C" mis_status mis_debug_canary_lin_bf16(int device, const float* X, int Mrows, int M, int K, int N, const uint16_t* W, const float* bias, int relu, int S,
+                                                float* out, int32_t* index) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(X && W && (out || index) && M >= 1 && M <= 64 && Mrows >= M && K >= 32 && K % 32 == 0 && N >= 1, MIS_ERR_INVALID_INPUT,
+                "Canary bf16 lin: pointers, 1..64 live rows, K a positive multiple of 32, positive N");
+    MIS_REQUIRE(S == 1 || S == 2 || S == 4 || S == 8, MIS_ERR_INVALID_INPUT, "Canary bf16 lin: S must be 1, 2, 4 or 8");
+    MIS_REQUIRE(S == 1 || (!relu && !index && N <= CN_MAXH), MIS_ERR_INVALID_INPUT, "Canary bf16 lin: a split contraction has no ReLU, no pairs and at most %d columns", CN_MAXH);
+    MIS_REQUIRE((int64_t)Mrows * K <= CND_MAX_ELEMS && (int64_t)N * K <= CND_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Canary bf16 lin: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    CndCtx c;
+    const int nt = cdiv(N, 32);
+    DevBuf<uint32_t> dx, db;
+    DevBuf<uint16_t> dw;
+    alloc32(dx, X, (size_t)Mrows * K, F32_NAN);
+    alloc16(dw, W, (size_t)N * K, BF16_NAN);
+    std::vector<float> zero(N, 0.0f);
+    alloc32(db, bias ? bias : zero.data(), N, F32_NAN);
+    GuardedOut o, pairs;
+    o.alloc((size_t)M * N * 4, (size_t)64 * N * 4);
+    pairs.alloc((size_t)2 * M * nt * 4, 4096);
+    float* y = reinterpret_cast<float*>(o.p());
+    SfLin l{nullptr, cnd_fp(db)};
+    CnLin p = cn_lin_args(cnd_fp(dx), K, l, M, N, dw.p);
+    p.relu = relu;
+    DevBuf<float> part, xn, lw;
+    if (S == 1) {
+        p.Y = out ? y : nullptr; p.ldy = N;
+        if (index) { p.amv = reinterpret_cast<float*>(pairs.p()); p.ami = reinterpret_cast<int*>(pairs.p()) + (size_t)M * nt; p.nt = nt; }
+        cn_lin(&c, p, 1);
+    } else {
+        part.alloc((size_t)S * M * N); xn.alloc((size_t)M * N); lw.alloc(N);
+        HIP_CHECK(hipMemset(y, 0, (size_t)M * N * 4));
+        HIP_CHECK(hipMemset(lw.p, 0, (size_t)N * 4));
+        p.bias = nullptr; p.part = part.p;
+        cn_lin(&c, p, S);
+        CnRows r{y, xn.p, cnd_fp(db), part.p, S, M, N, lw.p, lw.p};
+        MIS_LAUNCH(&c, k_cn_rows, dim3(M), dim3(256), r);
+    }
+    cnd_sync(c, S == 1 ? 1 : 2);
+    o.check_guards(); pairs.check_guards();
+    if (index) {
+        std::vector<float> hv((size_t)M * nt);
+        std::vector<int> hi((size_t)M * nt);
+        HIP_CHECK(hipMemcpy(hv.data(), p.amv, hv.size() * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(hi.data(), p.ami, hi.size() * 4, hipMemcpyDeviceToHost));
+        for (int m = 0; m < M; ++m) {                                // k_cn_select's rule: tile order, ties to the lower index
+            float bv = -INFINITY; int bi = 0x7fffffff;
+            for (int t = 0; t < nt; ++t) if (hv[(size_t)m * nt + t] > bv || (hv[(size_t)m * nt + t] == bv && hi[(size_t)m * nt + t] < bi)) { bv = hv[(size_t)m * nt + t]; bi = hi[(size_t)m * nt + t]; }
+            index[m] = bi;
+        }
+    }
+    if (out) HIP_CHECK(hipMemcpy(out, y, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ONE launch of k_cn_attn_step_bf16: as mis_debug_canary_attn_step with the K | V store given as bf16 bits
+extern "C" mis_status mis_debug_canary_attn_step_bf16(int device, const float* q, const uint16_t* kv, const int32_t* cnt, int batch, int cap, int heads, int hd,
+                                                      float* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(q && kv && cnt && out && batch >= 1 && batch <= 65535 && cap >= 1 && heads >= 1 && heads <= 65535 && hd >= 1 && hd <= 128, MIS_ERR_INVALID_INPUT,
+                "Canary bf16 attention step: pointers, positive batch, cap, heads and a head size up to 128");
+    const int64_t h = (int64_t)heads * hd;
+    MIS_REQUIRE((int64_t)batch * cap * 2 * h <= CND_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Canary bf16 attention step: tensor too large");
+    for (int b = 0; b < batch; ++b) MIS_REQUIRE(cnt[b] >= 1 && cnt[b] <= cap, MIS_ERR_INVALID_INPUT, "Canary bf16 attention step: row %d has %d keys outside 1..%d", b, cnt[b], cap);
+    HIP_CHECK(hipSetDevice(device));
+    CndCtx c;
+    DevBuf<uint32_t> dq, dc;
+    DevBuf<uint16_t> dkv;
+    alloc32(dq, q, (size_t)batch * h, F32_NAN);
+    alloc16(dkv, kv, (size_t)batch * cap * 2 * h, BF16_NAN);
+    alloc32(dc, cnt, batch, 0x7FFFFFFFu);
+    GuardedOut o;
+    o.alloc((size_t)batch * h * 4, (size_t)64 * h * 4);
+    CnAttn a{cnd_fp(dq), (int)h, nullptr, (int)(2 * h), (int)h, cap, nullptr, reinterpret_cast<const int*>(dc.p), 0, reinterpret_cast<float*>(o.p()), (int)h, hd,
+             1.0f / sqrtf((float)hd), dkv.p};
+    MIS_LAUNCH(&c, k_cn_attn_step_bf16, dim3(batch, heads), dim3(256), a);
+    cnd_sync(c, 1);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), (size_t)batch * h * 4, hipMemcpyDeviceToHost));
     MIS_API_END
 }
