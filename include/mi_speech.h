@@ -1552,6 +1552,23 @@ mis_status mis_canary_tap(mis_canary*, int stage, float* out, int64_t capacity, 
  * 2..31 with conv_pad_left + conv_pad_right = conv_kernel_size - 1; 1..8 contexts, right >= 0 (att_context_style regular: one context
  * (0, 2^30), a single chunk); num_prompts 1..4096 and prompt_hidden 1..16384, or both 0; pred_rnn_layers 1 or 2; max_symbols 0..64;
  * max_seconds 1..1200.  A call's context must lie inside the distances the listed contexts cover.
+ *
+ * bf16 encoder (opt-in, mis_nemotron_set_encoder_dtype with MIS_BF16 before finalize; csrc/nemotron_encoder_bf16.h; the offline engine
+ * only).  The Conformer blocks run on v_mfma_f32_16x16x32_bf16, the chunked-limited rule included: the same tile walk, the same short
+ * table, an excluded key has weight exactly 0.  The launch counts do not change, the f32 mode keeps its bits and its resident buffers, and
+ * mis_nemotron_tap returns the same f32 residual-stream stages.  Precision contract: Parakeet's, plus the conv module's two points.
+ * f32: the residual stream; every LayerNorm statistic, the conv module's included; biases, LayerNorm parameters, bias_u / bias_v and the
+ * depthwise taps; every accumulation, the softmax and every epilogue; the front end and the stem; the prompt kernel and joint.enc; the
+ * RNN-T decode.  Rounded to bf16, to nearest even, once, at each of these points: the eight block matrices and each layer's projected
+ * distance table (projected in f32 for the widest listed context, then rounded); the operand a contraction stages; the activations
+ * between the launches of a block (the big, qkv and att buffers are bf16 in this mode); inside attention q + bias_u, q + bias_v and the
+ * probabilities in front of P V - the row sum adds the unrounded probabilities; the conv module's depthwise output, stored as bf16.  The
+ * conv module's mean and rstd are taken over the unrounded f32 depthwise outputs, and pointwise_conv2's operand load forms
+ * SiLU((x - mean) rstd w + b) in f32 from the widened bf16 x and rounds it as it is staged.  A row's output is bit-identical whatever its
+ * batch, its padding or what lies behind lens[b], NaN included.  Resident encoder weights halve: the block matrices and tables exist on
+ * the device as bf16 only, so mis_nemotron_stream_create on such a handle is refused (the stream session runs the f32 matrices).
+ * Requires hidden_size % 32 == 0 and intermediate_size % 32 == 0 (MIS_ERR_INVALID_INPUT naming the field); any dtype but MIS_F32 /
+ * MIS_BF16 and a call after finalize are refused, the handle stays usable.
  * ---------------------------------------------------------------------------------------- */
 typedef struct mis_nemotron mis_nemotron;
 typedef struct {
@@ -1570,6 +1587,8 @@ mis_status mis_nemotron_create(const mis_nemotron_config*, int device, mis_nemot
  * joint.{enc,pred}.{weight,bias}; joint.joint_net.{weight,bias} [vocab + 1, joint_hidden]; host pointers */
 mis_status mis_nemotron_set_tensor(mis_nemotron*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
 mis_status mis_nemotron_init_synthetic(mis_nemotron*, uint64_t seed);
+/* MIS_F32 (the default) or MIS_BF16: the encoder's Conformer blocks (the contract above); before finalize */
+mis_status mis_nemotron_set_encoder_dtype(mis_nemotron*, mis_dtype);
 mis_status mis_nemotron_finalize(mis_nemotron*);
 void       mis_nemotron_destroy(mis_nemotron*);
 /* kernel launches of the last call, L = num_hidden_layers, p = 1 with a prompt kernel: generate 9 + 15 L + 2 p = 2 (front end) + 4 (stem)

@@ -373,6 +373,21 @@ mis_status mis_debug_nemotron_rnnt(int device, const float* encp, const int32_t*
                                    int32_t* frames, int32_t* counts, int32_t* flags, int32_t* steps);
 mis_status mis_debug_nemotron_timing(mis_nemotron*, float* ms);
 
+/* csrc/nemotron_encoder_bf16.h: ONE launch of a kernel of the bf16 Nemotron encoder (bf16 tensors as uint16 bit patterns; guards, repeat
+ * and ms as the parakeet_*_bf16 entry points).
+ *   nemotron_attn_bf16: k_nm_attn_bf16, head sizes 1..128; the arguments of nemotron_attn with bf16 qkv and table, out bf16.
+ *   nemotron_dwconv_ln_bf16: k_nm_glu_dwconv_ln_bf16; pw bf16 [batch Tp][2 C], taps f32 [k][C], bias f32 [C] or NULL -> out bf16
+ *     [batch Tp][C], stats f32 [batch Tp][2] = mean, rstd of the unrounded outputs.
+ *   nemotron_gemm_bf16: parakeet_gemm_bf16 with the third load, 2: x bf16 [batch Tp][K] read as SiLU((x - mean) rstd lnw + lnb). */
+mis_status mis_debug_nemotron_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads, int hd,
+                                        float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp, int prow, int poff, int left,
+                                        int right, int Tcap, int ldo, uint16_t* out, int repeat, float* ms);
+mis_status mis_debug_nemotron_dwconv_ln_bf16(int device, const uint16_t* pw, const float* taps, const float* bias, const int32_t* cnt, int batch, int Tp, int C,
+                                             int k, int padl, uint16_t* out, float* stats);
+mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi, int rule, const void* x, const float* stats, const float* lnw, const float* lnb,
+                                        const uint16_t* w, const float* bias, const float* R, float ra, const int32_t* cnt, int batch, int Tp, int K, int N,
+                                        void* out, int repeat, float* ms);
+
 /* csrc/nemotron_stream.hip: ONE launch of a stream kernel on caller-supplied host data, and the device time of the last feed.
  *   nemotron_attn_stream: k_nm_attn_stream; q [streams][Tp][heads hd] holds cnt[b] queries at the absolute frames pos[b] .., ring
  *     [streams][R][2 heads hd] the projected k | v of frame f in row f % R (R % 32 == 0, R >= left + Tp + 32; the queries' own frames

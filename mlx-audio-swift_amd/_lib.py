@@ -521,6 +521,7 @@ SYMBOLS = {
     "mis_nemotron_create": (C.c_int, [C.POINTER(NemotronConfigC), C.c_int, C.POINTER(_P)]),
     "mis_nemotron_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_nemotron_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_nemotron_set_encoder_dtype": (C.c_int, [_P, C.c_int]),
     "mis_nemotron_finalize": (C.c_int, [_P]),
     "mis_nemotron_destroy": (None, [_P]),
     "mis_nemotron_launches": (C.c_int, [_P]),
@@ -745,6 +746,11 @@ DEBUG_SYMBOLS = {
     "mis_debug_nemotron_rnnt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                           _P, _P, _P, _P, _P, _P, _P]),
     "mis_debug_nemotron_timing": (C.c_int, [_P, _P]),
+    "mis_debug_nemotron_attn_bf16": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "mis_debug_nemotron_dwconv_ln_bf16": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "mis_debug_nemotron_gemm_bf16": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, _P, C.c_int, _P]),
     "mis_debug_nemotron_attn_stream": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, C.c_int,
                                                  C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "mis_debug_nemotron_rnnt_stream": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,

@@ -1,7 +1,8 @@
 // nemotron.hip - Nemotron ASR (cache-aware FastConformer + RNN-T), offline: 16 kHz samples -> NeMo log-mel -> CAUSAL depthwise-striding
 // Conv2d stem (factor 8, pad (2, 1) on both axes) -> FastConformer blocks with CHUNKED-LIMITED relative-position attention and a conv
 // module normalised by a LayerNorm over channels -> prompt conditioning -> joint.enc over every frame -> greedy RNN-T decode (embedding,
-// one or two LSTM layers, joint, arg-max) in ONE launch.  Exact f32 throughout.
+// one or two LSTM layers, joint, arg-max) in ONE launch.  Exact f32 throughout; mis_nemotron_set_encoder_dtype(MIS_BF16) before finalize
+// selects the bf16 form of the Conformer blocks (nemotron_encoder_bf16.h holds its kernels and its precision contract).
 //
 // Reference being replaced: NemotronASRModel.decode / applyPrompt (Sources/MLXAudioSTT/Models/NemotronASR/NemotronASRModel.swift :184-275),
 // NemotronASRAttentionMask, NemotronASRConvolution, NemotronASRCausalDwStridingSubsampling (NemotronASRConformer.swift),
@@ -38,6 +39,7 @@
 //
 // Launches: generate = 2 (front end) + 4 (stem) + 1 (intake) + 15 L + 2 (prompt kernel, if the model has one) + 1 (joint.enc) + 1 (decode).
 #include "nemotron_kernels.h"
+#include "nemotron_encoder_bf16.h"
 
 
 // ============================================================================ kernel B: chunked-limited attention, head sizes 65..128
@@ -352,6 +354,12 @@ extern "C" void mis_nemotron_destroy(mis_nemotron* c) {
     delete c;
 }
 
+extern "C" mis_status mis_nemotron_set_encoder_dtype(mis_nemotron* c, mis_dtype dtype) {
+    MIS_API_BEGIN
+    pk_set_encoder_dtype(c, dtype);
+    MIS_API_END
+}
+
 extern "C" mis_status mis_nemotron_set_tensor(mis_nemotron* c, const char* name, const void* data, mis_dtype dtype, const int64_t* shape, int ndim) {
     MIS_API_BEGIN
     set_tensor_check(c, name, data, shape, ndim, 4, c && c->finalized, dtype);
@@ -367,7 +375,10 @@ extern "C" mis_status mis_nemotron_finalize(mis_nemotron* c) {
     HIP_CHECK(hipSetDevice(c->device));
     const int64_t mels = c->mels, C = c->C, d = c->d, f = c->f, ck = c->ck, F3 = c->F3, H = c->H, hd = c->hd, P = c->P, J = c->J, V = c->V, NP = c->NP, PH = c->PH;
     const bool ab = c->cfg.attention_bias != 0;
-    HostArena a(c->raw);
+    // bf16 mode: the eight block matrices go to wm and relative_k_proj and the sinusoid table to wt, for nm_bf16_tables alone
+    const bool b16 = c->enc_bf16 != 0;
+    HostArena a(c->raw), wm(c->raw), wt(c->raw);
+    HostArena &am = b16 ? wm : a, &at = b16 ? wt : a;
     std::vector<float>& fh = a.fhost;
     const size_t o_win = a.ftake(NEMO_NFFT, c->window), o_twc = a.ftake(NEMO_NFFT / 2, c->twc), o_tws = a.ftake(NEMO_NFFT / 2, c->tws);
     hann_padded(&fh[o_win], NEMO_WIN, NEMO_NFFT);
@@ -388,6 +399,11 @@ extern "C" mis_status mis_nemotron_finalize(mis_nemotron* c) {
     auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l) {
         l = SfLin{};
         a.fvec(p + ".weight", {N, K}, N * K, l.w);
+        if (bias) a.fvec(p + ".bias", {N}, N, l.b);
+    };
+    auto mat = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l) {      // a block matrix; its bias stays with the f32 tensors
+        l = SfLin{};
+        am.fvec(p + ".weight", {N, K}, N * K, l.w);
         if (bias) a.fvec(p + ".bias", {N}, N, l.b);
     };
     auto norm = [&](const std::string& p, int64_t n, const float*& w, const float*& b) { a.fvec(p + ".weight", {n}, n, w); a.fvec(p + ".bias", {n}, n, b); };
@@ -415,23 +431,23 @@ extern "C" mis_status mis_nemotron_finalize(mis_nemotron* c) {
         const std::string q = "encoder.layers." + std::to_string(li) + ".";
         mis_nemotron::Layer& l = c->fc[li];
         norm(q + "norm_feed_forward1", d, l.ln1w, l.ln1b);
-        lin(q + "feed_forward1.linear1", f, d, ab, l.ff1a); lin(q + "feed_forward1.linear2", d, f, ab, l.ff1b);
+        mat(q + "feed_forward1.linear1", f, d, ab, l.ff1a); mat(q + "feed_forward1.linear2", d, f, ab, l.ff1b);
         norm(q + "norm_self_att", d, l.lnaw, l.lnab);
         {   // q, k, v over the same input as one [3 d][d]; an absent bias is zero
-            const size_t ow = a.ftake((size_t)3 * d * d, l.qkv.w), ob = a.ftake(3 * d, l.qkv.b);
+            const size_t ow = am.ftake((size_t)3 * d * d, l.qkv.w), ob = a.ftake(3 * d, l.qkv.b);
             const char* names[3] = {"q_proj", "k_proj", "v_proj"};
             for (int i = 0; i < 3; ++i) {
                 const HostTensor& w = c->raw.need(q + "self_attn." + names[i] + ".weight", {d, d});
-                std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * d * d);
+                std::copy(w.v.begin(), w.v.end(), am.fhost.begin() + ow + (size_t)i * d * d);
                 if (ab) { const HostTensor& bb = c->raw.need(q + "self_attn." + names[i] + ".bias", {d}); std::copy(bb.v.begin(), bb.v.end(), fh.begin() + ob + (size_t)i * d); }
             }
         }
-        lin(q + "self_attn.o_proj", d, d, ab, l.o);
-        a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, rk[li].w);
+        mat(q + "self_attn.o_proj", d, d, ab, l.o);
+        at.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, rk[li].w);
         a.fvec(q + "self_attn.bias_u", {H, hd}, d, l.u); a.fvec(q + "self_attn.bias_v", {H, hd}, d, l.v);
         norm(q + "norm_conv", d, l.lncw, l.lncb);
-        a.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w);
-        a.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w);
+        am.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w);
+        am.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w);
         if (ab) {
             a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d, l.pw1.b); a.fvec(q + "conv.pointwise_conv2.bias", {d}, d, l.pw2.b);
             a.fvec(q + "conv.depthwise_conv.bias", {d}, d, l.dwb);
@@ -443,20 +459,20 @@ extern "C" mis_status mis_nemotron_finalize(mis_nemotron* c) {
         }
         norm(q + "conv.norm", d, l.cnw, l.cnb);
         norm(q + "norm_feed_forward2", d, l.ln2w, l.ln2b);
-        lin(q + "feed_forward2.linear1", f, d, ab, l.ff2a); lin(q + "feed_forward2.linear2", d, f, ab, l.ff2b);
+        mat(q + "feed_forward2.linear1", f, d, ab, l.ff2a); mat(q + "feed_forward2.linear2", d, f, ab, l.ff2b);
         norm(q + "norm_out", d, l.lnow, l.lnob);
     }
     if (PH) { lin("prompt_kernel.linear0", PH, d + NP, true, c->pr0); lin("prompt_kernel.linear2", d, PH, true, c->pr2); }
     lin("joint.enc", J, d, true, c->jenc);
     // the sinusoid table by distance, the rows tab_lo .. tab_hi alone: columns interleaved sin, cos; formed in double, rounded once
     const float* tab = nullptr;
-    const size_t o_tab = a.ftake((size_t)NR * d, tab);
+    const size_t o_tab = at.ftake((size_t)NR * d, tab);
     for (int r = 0; r < NR; ++r) {
         const double dist = (double)(r + c->tab_lo);
         for (int64_t k = 0; 2 * k < d; ++k) {
             const double ang = dist * exp(-(double)(2 * k) * log(10000.0) / (double)d);
-            fh[o_tab + (size_t)r * d + 2 * k] = (float)sin(ang);
-            if (2 * k + 1 < d) fh[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
+            at.fhost[o_tab + (size_t)r * d + 2 * k] = (float)sin(ang);
+            if (2 * k + 1 < d) at.fhost[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
         }
     }
     // the decoder, checked before anything is uploaded
@@ -474,19 +490,28 @@ extern "C" mis_status mis_nemotron_finalize(mis_nemotron* c) {
     nm_pack_decoder(s, c->cfg.pred_rnn_layers, (int)P, (int)J, (int)V, c->dec, c->rnnt);
     c->fbr.alloc(2 * mels);
     HIP_CHECK(hipMemcpy(c->fbr.p, ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
-    c->ptab.alloc((size_t)c->L * NR * d);                          // each layer's relative_k_proj of the short table: one GEMM, once
-    for (int li = 0; li < c->L; ++li) {
-        float* dst = c->ptab.p + (size_t)li * NR * d;
-        sf_gemm(c, sf_lin(tab, (int)d, rk[li], dst, (int)d, nullptr, NR), 1);
-        c->fc[li].P = dst;
+    if (b16) nm_bf16_tables(c, wm, wt, tab, rk);
+    else {
+        c->ptab.alloc((size_t)c->L * NR * d);                      // each layer's relative_k_proj of the short table: one GEMM, once
+        for (int li = 0; li < c->L; ++li) {
+            float* dst = c->ptab.p + (size_t)li * NR * d;
+            sf_gemm(c, sf_lin(tab, (int)d, rk[li], dst, (int)d, nullptr, NR), 1);
+            c->fc[li].P = dst;
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipStreamSynchronize(c->stream));
     c->launches = 0;
     const size_t B = c->cfg.max_batch, M = B * Tc;
     c->pcm.alloc(B * c->maxN); c->melraw.alloc(B * c->Fcap * mels); c->feats.alloc(B * c->Fcap * mels);
     c->s0.alloc(B * c->T1cap * c->F1 * C); c->s1.alloc(B * c->T2cap * c->F2 * C); c->s2.alloc(M * F3 * C); c->emb.alloc(M * d);
-    c->h.alloc(M * d); c->stats.alloc(M * 2); c->big.alloc(M * std::max<size_t>(std::max<size_t>(f, 2 * d), PH)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d);
+    c->h.alloc(M * d); c->stats.alloc(M * 2);
+    if (b16) {                                                      // big stays as the prompt kernel's f32 buffer alone
+        c->big16.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv16.alloc(M * 3 * d); c->att16.alloc(M * d);
+        if (PH) c->big.alloc(M * PH);
+    } else {
+        c->big.alloc(M * std::max<size_t>(std::max<size_t>(f, 2 * d), PH)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d);
+    }
     if (PH) c->prm.alloc(M * d);
     c->encp.alloc(M * J);
     c->cntN.alloc(B); c->cntF.alloc(B); c->cnt1.alloc(B); c->cnt2.alloc(B); c->cnt3.alloc(B); c->lang.alloc(B);
@@ -614,6 +639,7 @@ static void nm_front_stem(mis_nemotron* c, const float* pcm, const int64_t* lens
 
 // c->emb -> the Conformer blocks -> c->h (1 + 15 L launches); stop: -1 all, 1 .. L behind that block
 static void nm_encoder(mis_nemotron* c, int stop) {
+    if (c->enc_bf16) { nm_encoder_bf16(c, stop); return; }
     const int B = c->batch, Tp = c->Tp, d = c->d, f = c->f, M = B * Tp;
     const int* cnt = c->cnt3.p;
     const size_t nd = (size_t)M * d;
@@ -909,5 +935,133 @@ extern "C" mis_status mis_debug_nemotron_rnnt(int device, const float* encp, con
     HIP_CHECK(hipMemcpy(counts, p.count, batch * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(flags, p.flag, batch * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(steps, p.steps, batch * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ---------------------------------------------------------------------------- the bf16 encoder's kernels (nemotron_encoder_bf16.h)
+namespace {
+// the ONE checked launch; then, with ms, `repeat` more of the same launch between two events: *ms = milliseconds a launch
+template <class F>
+void nmd_run(NmdCtx& c, F launch, int repeat, float* ms) {
+    launch();
+    nmd_sync(c);
+    if (!ms) return;
+    MIS_REQUIRE(repeat >= 1 && repeat <= 10000, MIS_ERR_INVALID_INPUT, "repeat %d outside 1..10000", repeat);
+    HipEvents<2> ev;
+    HIP_CHECK(hipEventRecord(ev[0], c.stream));
+    for (int r = 0; r < repeat; ++r) launch();
+    HIP_CHECK(hipEventRecord(ev[1], c.stream));
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipEventElapsedTime(ms, ev[0], ev[1]));
+    *ms /= (float)repeat;
+}
+// rows x width elements of `es` bytes out of a guarded [rows][ld] body; the columns behind width must be untouched
+void nmd_rows_out(GuardedOut& o, void* out, size_t rows, size_t width, size_t ld, size_t es) {
+    o.check_guards();
+    std::vector<uint8_t> hbuf(o.body);
+    HIP_CHECK(hipMemcpy(hbuf.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        memcpy(static_cast<uint8_t*>(out) + r * width * es, hbuf.data() + r * ld * es, width * es);
+        for (size_t i = width * es; i < ld * es; ++i)
+            MIS_REQUIRE(hbuf[r * ld * es + i] == 0xFF, MIS_ERR_GENERATION_FAILED, "the kernel wrote behind the %zu columns of row %zu", width, r);
+    }
+}
+}  // namespace
+
+// ONE launch of k_nm_attn_bf16: the arguments of mis_debug_nemotron_attn with bf16 qkv and table, head sizes 1..128; out bf16 [batch Tp][heads hd]
+extern "C" mis_status mis_debug_nemotron_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads,
+                                                   int hd, float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp, int prow, int poff,
+                                                   int left, int right, int Tcap, int ldo, uint16_t* out, int repeat, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(qkv && cnt && out && u && v && P && batch >= 1 && Tp >= 1 && heads >= 1 && hd >= 1 && hd <= 128 && Tcap >= 1 && right >= 0 && prow >= 1,
+                MIS_ERR_INVALID_INPUT, "Nemotron bf16 attention: every pointer, positive batch, Tp, heads, Tcap, prow, right >= 0 and a head size of 1..128 are required");
+    const int64_t width = (int64_t)heads * hd;
+    MIS_REQUIRE(koff >= 0 && voff >= 0 && width <= ld && koff + width <= ld && voff + width <= ld && width <= ldo && ldp >= width, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 attention: q, k and v must lie inside a row of ld columns, the output inside ldo, the table inside ldp");
+    MIS_REQUIRE((int64_t)batch * Tp * ld <= NMD_MAX_ELEMS && (int64_t)batch * Tp * ldo <= NMD_MAX_ELEMS && (int64_t)prow * ldp <= NMD_MAX_ELEMS &&
+                    batch <= 65535 && heads <= 65535 && Tp <= Tcap, MIS_ERR_INVALID_INPUT, "Nemotron bf16 attention: tensor too large (Tp <= Tcap)");
+    const NmCtx x = nm_context(left, right, Tcap);
+    MIS_REQUIRE(x.dlo + poff >= 0 && x.dhi + poff < prow, MIS_ERR_INVALID_INPUT, "Nemotron bf16 attention: the table rows %d..%d do not cover the distances %d..%d",
+                -poff, prow - 1 - poff, x.dlo, x.dhi);
+    HIP_CHECK(hipSetDevice(device));
+    NmdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint16_t> dq, dP;
+    DevBuf<uint32_t> dcnt, du, dv;
+    alloc16(dq, qkv, rows * ld, BF16_NAN); alloc16(dP, P, (size_t)prow * ldp, BF16_NAN);
+    alloc32(dcnt, cnt, batch, 0x7FFFFFFFu);
+    alloc32(du, u, width, F32_NAN); alloc32(dv, v, width, F32_NAN);
+    GuardedOut o;
+    o.alloc(rows * ldo * 2, (size_t)64 * ldo * 2);
+    NmbAttn p{dq.p, ld, koff, voff, reinterpret_cast<bf16_t*>(o.p()), ldo, nmd_ip(dcnt), Tp, hd, qscale, sdk, nmd_fp(du), nmd_fp(dv), dP.p, ldp, poff,
+              x.C, x.L, x.dlo, x.dhi};
+    nmd_run(c, [&] { nmb_attn(&c, p, heads, hd, batch); c.launches = 1; }, repeat, ms);
+    nmd_rows_out(o, out, rows, width, ldo, 2);
+    MIS_API_END
+}
+
+// ONE launch of k_nm_glu_dwconv_ln_bf16: pw bf16 [batch Tp][2 C], taps f32 [k][C], bias f32 [C] or NULL -> out bf16 [batch Tp][C], stats f32 [batch Tp][2]
+extern "C" mis_status mis_debug_nemotron_dwconv_ln_bf16(int device, const uint16_t* pw, const float* taps, const float* bias, const int32_t* cnt, int batch, int Tp,
+                                                        int C, int k, int padl, uint16_t* out, float* stats) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pw && taps && cnt && out && stats && batch >= 1 && batch <= 65535 && Tp >= 1 && C >= 1 && k >= 1 && k <= SF_DW_MAXK && padl >= 0 && padl < k &&
+                    (int64_t)batch * Tp * 2 * C <= NMD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 conv module: every pointer, positive batch, Tp, C, 1 <= k <= %d and 0 <= padl < k are required", SF_DW_MAXK);
+    HIP_CHECK(hipSetDevice(device));
+    NmdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint16_t> dpw;
+    DevBuf<uint32_t> dt, db, dc;
+    alloc16(dpw, pw, rows * 2 * C, BF16_NAN);
+    alloc32(dt, taps, (size_t)k * C, F32_NAN); alloc32(dc, cnt, batch, 0x7FFFFFFFu);
+    if (bias) alloc32(db, bias, C, F32_NAN);
+    GuardedOut o, st;
+    o.alloc(rows * C * 2, 4096); st.alloc(rows * 2 * 4, 4096);
+    nmb_glu_dwconv_ln(&c, dpw.p, nmd_fp(dt), bias ? nmd_fp(db) : nullptr, nmd_ip(dc), reinterpret_cast<bf16_t*>(o.p()), reinterpret_cast<float*>(st.p()), Tp, C, k,
+                      padl, batch);
+    nmd_sync(c);
+    o.check_guards(); st.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(stats, st.p(), st.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ONE launch of k_pk_gemm_bf16 as mis_debug_parakeet_gemm_bf16, with load 2 (PKB_LOAD_LN_SILU): x bf16 [batch Tp][K] read as
+// SiLU((x - mean) rstd lnw + lnb), stats [batch Tp][2], lnw, lnb [K]
+extern "C" mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi, int rule, const void* x, const float* stats, const float* lnw, const float* lnb,
+                                                   const uint16_t* w, const float* bias, const float* R, float ra, const int32_t* cnt, int batch, int Tp, int K,
+                                                   int N, void* out, int repeat, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(x && w && cnt && out && batch >= 1 && batch <= 65535 && Tp >= 1 && K >= 32 && K % 32 == 0 && N >= 8 && N % 8 == 0, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 GEMM: pointers, positive batch and Tp, K a multiple of 32 and N a multiple of 8 are required");
+    MIS_REQUIRE((load == PKB_LOAD_BF16 || ((load == PKB_LOAD_LN || load == PKB_LOAD_LN_SILU) && stats && lnw && lnb)) && epi >= PKB_EPI_NONE &&
+                    epi <= PKB_EPI_RES && (epi != PKB_EPI_RES || R) && (rule == PKB_TILE64 || rule == PKB_TILE32), MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 GEMM: unknown load / epilogue / rule, or a missing operand");
+    const size_t rows = (size_t)batch * Tp;
+    MIS_REQUIRE((int64_t)rows * K <= NMD_MAX_ELEMS && (int64_t)rows * N <= NMD_MAX_ELEMS && (int64_t)N * K <= NMD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 GEMM: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    NmdCtx c;
+    DevBuf<uint16_t> dxb, dw;
+    DevBuf<uint32_t> dxf, dst, dlw, dlb, dbias, dR, dcnt;
+    PkbGemm p{};
+    if (load == PKB_LOAD_LN) { alloc32(dxf, x, rows * K, F32_NAN); p.Xf = nmd_fp(dxf); }
+    else { alloc16(dxb, static_cast<const uint16_t*>(x), rows * K, BF16_NAN); p.Xb = dxb.p; }
+    if (load != PKB_LOAD_BF16) {
+        alloc32(dst, stats, rows * 2, F32_NAN); alloc32(dlw, lnw, K, F32_NAN); alloc32(dlb, lnb, K, F32_NAN);
+        p.stats = nmd_fp(dst); p.lnw = nmd_fp(dlw); p.lnb = nmd_fp(dlb);
+    }
+    alloc16(dw, w, (size_t)N * K, BF16_NAN);
+    alloc32(dcnt, cnt, batch, 0x7FFFFFFFu);
+    if (bias) { alloc32(dbias, bias, N, F32_NAN); p.bias = nmd_fp(dbias); }
+    if (epi == PKB_EPI_RES) { alloc32(dR, R, rows * N, F32_NAN); p.R = nmd_fp(dR); p.ldr = N; p.ra = ra; }
+    const size_t es = epi == PKB_EPI_RES ? 4 : 2;
+    GuardedOut o;
+    o.alloc(rows * N * es, (size_t)64 * N * es);
+    p.Yf = reinterpret_cast<float*>(o.p()); p.Yb = reinterpret_cast<bf16_t*>(o.p());
+    p.ldx = K; p.W = dw.p; p.ldy = N; p.cnt = nmd_ip(dcnt); p.Tp = Tp; p.K = K; p.N = N; p.epi = epi;
+    nmd_run(c, [&] { nmb_gemm_launch(&c, p, load, rule, batch); c.launches = 1; }, repeat, ms);
+    nmd_rows_out(o, out, rows, N, N, es);
     MIS_API_END
 }

@@ -223,6 +223,12 @@ struct mis_nemotron {
         SfLin ff1a, ff1b, qkv, o, pw1, pw2, ff2a, ff2b;
     };
     std::vector<Layer> fc;
+    // bf16 mode (nemotron_encoder_bf16.h, offline engine only): the block matrices [N][K] and the rounded tables [tab_hi - tab_lo + 1][d];
+    // the f32 matrices, ptab, qkv and att do not exist then, big only as the prompt kernel's buffer
+    int enc_bf16 = 0;
+    struct Layer16 { bf16_t *ff1a, *ff1b, *qkv, *o, *pw1, *pw2, *ff2a, *ff2b, *P; };
+    std::vector<Layer16> fc16;
+    DevBuf<bf16_t> warena, ptab16, big16, qkv16, att16;
     NmRnnt rnnt{};
     int tab_lo = 0, tab_hi = 0;                                      // the distances the projected tables hold
     // workspace (sized at finalize)

@@ -477,6 +477,8 @@ extern "C" mis_status mis_nemotron_stream_create(mis_nemotron* m, int streams, i
     MIS_REQUIRE(m && out, MIS_ERR_INVALID_INPUT, "null argument");
     MIS_REQUIRE(m->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
     MIS_REQUIRE(streams >= 1 && streams <= NM_MAX_BATCH, MIS_ERR_INVALID_INPUT, "streams %d outside 1..%d", streams, NM_MAX_BATCH);
+    MIS_REQUIRE(!m->enc_bf16, MIS_ERR_INVALID_INPUT,
+                "encoder_dtype bfloat16: a stream session runs the f32 block matrices, which are not resident in this mode (offline engine only)");
     MIS_REQUIRE(m->cfg.normalize == 0, MIS_ERR_INVALID_INPUT,
                 "normalize per_feature: a stream session requires NA mel normalization (per-utterance statistics are not frozen incrementally)");
     MIS_REQUIRE(right >= 0 && right < (1 << 20) && left >= 0 && left % (right + 1) == 0, MIS_ERR_INVALID_INPUT,

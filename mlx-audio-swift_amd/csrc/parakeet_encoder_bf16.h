@@ -38,7 +38,7 @@
 
 namespace {
 
-enum { PKB_LOAD_BF16 = 0, PKB_LOAD_LN };
+enum { PKB_LOAD_BF16 = 0, PKB_LOAD_LN, PKB_LOAD_LN_SILU };         // LN_SILU: Nemotron's pointwise_conv2 (nemotron_encoder_bf16.h)
 enum { PKB_EPI_NONE = 0, PKB_EPI_SILU, PKB_EPI_RES };               // bf16 store, bf16 store, f32 store of R + ra v
 enum { PKB_TILE64 = 0, PKB_TILE32 };
 enum { PKB_FF1A = 0, PKB_FF1B, PKB_QKV, PKB_O, PKB_PW1, PKB_PW2, PKB_FF2A, PKB_FF2B, PKB_ROLES };
@@ -63,7 +63,7 @@ static const PkbRole PKB_ROLE[PKB_ROLES] = {
 // Y[b][t][n] = epilogue(sum_k load(X)[b][t][k] W[n][k]); min(cnt[b], Tp) live rows a batch entry, the rows behind them are written as zero.
 // K % 32 == 0, N % 8 == 0, ldx % 8 == 0, ldy % 4 == 0.
 struct PkbGemm {
-    const float* Xf; const bf16_t* Xb; int ldx;              // LN load: f32 rows; else bf16 rows
+    const float* Xf; const bf16_t* Xb; int ldx;              // LN load: f32 rows; else bf16 rows (LN_SILU: bf16 rows, stats, lnw, lnb)
     const bf16_t* W; const float* bias;                      // [N][K]; bias null: none
     bf16_t* Yb; float* Yf; int ldy;                          // PKB_EPI_RES: Yf, else Yb
     const int* cnt; int Tp, K, N, epi;
@@ -100,12 +100,25 @@ __global__ void __launch_bounds__(256) k_pk_gemm_bf16(PkbGemm p) {
     const int r0 = tid >> 2, c0 = (tid & 3) * 8, ms = m0 + r0, ns = n0 + r0;
     const bool xlive = stager && ms < T, wlive = stager && ns < p.N;
     float mean = 0.0f, rstd = 0.0f;
-    if (LOAD == PKB_LOAD_LN && xlive) { mean = p.stats[2 * (row0 + ms)]; rstd = p.stats[2 * (row0 + ms) + 1]; }
+    if ((LOAD == PKB_LOAD_LN || LOAD == PKB_LOAD_LN_SILU) && xlive) { mean = p.stats[2 * (row0 + ms)]; rstd = p.stats[2 * (row0 + ms) + 1]; }
     uint4 wreg = make_uint4(0, 0, 0, 0), xreg = make_uint4(0, 0, 0, 0);
     auto load = [&](int k0) {
         if (wlive) wreg = *reinterpret_cast<const uint4*>(p.W + (size_t)ns * p.K + k0 + c0);
         if (!xlive) return;
-        if (LOAD == PKB_LOAD_LN) {                                  // (x - mean) rstd w + b in f32, as k_sf_gemm's LN load; rounded here, once
+        if constexpr (LOAD == PKB_LOAD_LN_SILU) {                   // SiLU((x - mean) rstd w + b) in f32 from the widened bf16 x; rounded here, once
+            const uint4 q = *reinterpret_cast<const uint4*>(p.Xb + (row0 + ms) * p.ldx + k0 + c0);
+            const float4* w = reinterpret_cast<const float4*>(p.lnw + k0 + c0);
+            const float4* bb = reinterpret_cast<const float4*>(p.lnb + k0 + c0);
+            const float4 w0 = w[0], w1 = w[1], b0 = bb[0], b1 = bb[1];
+            float lo[4], hi[4];
+            bf16x4_unpack(make_uint2(q.x, q.y), lo);
+            bf16x4_unpack(make_uint2(q.z, q.w), hi);
+            auto act = [&](float x, float wv, float bv) { const float v = fmaf((x - mean) * rstd, wv, bv); return v / (1.0f + expf(-v)); };
+            xreg.x = pkb_pack2(act(lo[0], w0.x, b0.x), act(lo[1], w0.y, b0.y));
+            xreg.y = pkb_pack2(act(lo[2], w0.z, b0.z), act(lo[3], w0.w, b0.w));
+            xreg.z = pkb_pack2(act(hi[0], w1.x, b1.x), act(hi[1], w1.y, b1.y));
+            xreg.w = pkb_pack2(act(hi[2], w1.z, b1.z), act(hi[3], w1.w, b1.w));
+        } else if (LOAD == PKB_LOAD_LN) {                                  // (x - mean) rstd w + b in f32, as k_sf_gemm's LN load; rounded here, once
             const float4* x = reinterpret_cast<const float4*>(p.Xf + (row0 + ms) * p.ldx + k0 + c0);
             const float4* w = reinterpret_cast<const float4*>(p.lnw + k0 + c0);
             const float4* bb = reinterpret_cast<const float4*>(p.lnb + k0 + c0);
@@ -379,7 +392,7 @@ __global__ void __launch_bounds__(256) k_pk_round_bf16(const float* __restrict__
 }
 
 // ============================================================================ host
-// f32 (the default) or bf16, before finalize; bf16 needs whole k-slabs
+// f32 (the default) or bf16, before finalize; bf16 needs whole k-slabs (any handle with cfg, finalized and enc_bf16)
 template <class Ctx>
 static void pk_set_encoder_dtype(Ctx* c, mis_dtype dtype) {
     MIS_REQUIRE(c, MIS_ERR_INVALID_INPUT, "null argument");
@@ -393,6 +406,7 @@ static void pk_set_encoder_dtype(Ctx* c, mis_dtype dtype) {
     c->enc_bf16 = dtype == MIS_BF16;
 }
 
+#ifndef PKB_NO_PARAKEET_CHAIN                                        // nemotron_encoder_bf16.h has its own tables and chain
 // finalize of bf16 mode: every layer's table projected in f32 by the f32 GEMM, as the f32 mode does, then rounded into ptab16; the f32
 // table, the relative_k_proj matrices and the projections live in buffers of this scope only
 template <class Ctx>
@@ -461,5 +475,6 @@ static void pk_encoder_bf16(Ctx* c, int stop) {
         if (stop == li + 1) return;
     }
 }
+#endif
 
 }  // namespace

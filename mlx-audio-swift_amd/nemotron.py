@@ -13,7 +13,7 @@ import ctypes as C
 import json
 import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -67,6 +67,7 @@ class NemotronConfig:
     max_batch: int = 8
     max_seconds: int = 30
     max_tokens: int = 1024
+    encoder_dtype: str = "float32"   # "bfloat16": the Conformer blocks in bf16 (csrc/nemotron_encoder_bf16.h); not part of a checkpoint
 
     @classmethod
     def from_dict(cls, d: dict, **workspace) -> "NemotronConfig":
@@ -207,28 +208,31 @@ class NemotronASR(NativeHandle):
     def __init__(self, config: NemotronConfig, device: int = 0):
         self.config, self.device = config, device
         self._create(config.to_c(), device)
+        if config.encoder_dtype != "float32":
+            self.set_encoder_dtype(config.encoder_dtype)
 
     sanitize = staticmethod(nemotron_sanitize)
 
     @classmethod
-    def from_weights(cls, config: NemotronConfig, weights: dict, device: int = 0) -> "NemotronASR":
-        """weights: the engine's names (what nemotron_sanitize returns)."""
-        m = cls(config, device)
+    def from_weights(cls, config: NemotronConfig, weights: dict, device: int = 0, encoder_dtype: str | None = None) -> "NemotronASR":
+        """weights: the engine's names (what nemotron_sanitize returns); encoder_dtype overrides the config's."""
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         for name, arr in weights.items():
             m.set_tensor(name, arr)
         m.finalize()
         return m
 
     @classmethod
-    def synthetic(cls, config: NemotronConfig, device: int = 0, seed: int = 777) -> "NemotronASR":
-        m = cls(config, device)
+    def synthetic(cls, config: NemotronConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None) -> "NemotronASR":
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         check(_lib.lib().mis_nemotron_init_synthetic(m._h, seed))
         m.finalize()
         return m
 
     @classmethod
     def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "NemotronASR":
-        """fromDirectory: config.json (Infinity / NaN scrubbed), every *.safetensors; the vocabulary of config.json, else the first *.model's."""
+        """fromDirectory: config.json (Infinity / NaN scrubbed), every *.safetensors; the vocabulary of config.json, else the first *.model's.
+        workspace: max_batch / max_seconds / max_tokens / encoder_dtype."""
         with open(os.path.join(model_dir, "config.json")) as f:
             text = f.read()
         for tok in ("-Infinity", "Infinity", "NaN"):                     # normalizedConfigData
@@ -386,7 +390,7 @@ class NemotronASR(NativeHandle):
     create_stream_session = stream_session
 
     def make_stream_session(self, language=None, chunk_ms=None, streams: int = 1, att_context_size=None) -> "NemotronStreamSession":
-        """makeStreamSession"""
+        """makeStreamSession (f32 models only: with encoder_dtype="bfloat16" the f32 block matrices the session runs are not resident)"""
         return NemotronStreamSession(self, streams, language, att_context_size, chunk_ms)
 
     def transcribe_streaming(self, audio, language=None, chunk_ms: int = 480, on_delta=None) -> ParakeetResult:
