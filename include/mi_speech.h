@@ -1566,7 +1566,9 @@ mis_status mis_canary_tap(mis_canary*, int stage, float* out, int64_t capacity, 
  * conv module's mean and rstd are taken over the unrounded f32 depthwise outputs, and pointwise_conv2's operand load forms
  * SiLU((x - mean) rstd w + b) in f32 from the widened bf16 x and rounds it as it is staged.  A row's output is bit-identical whatever its
  * batch, its padding or what lies behind lens[b], NaN included.  Resident encoder weights halve: the block matrices and tables exist on
- * the device as bf16 only, so mis_nemotron_stream_create on such a handle is refused (the stream session runs the f32 matrices).
+ * the device as bf16 only, so mis_nemotron_stream_create on such a handle is refused (an f32 stream session runs the f32 matrices).
+ * A bf16 stream session (mis_nemotron_stream_create_dtype with MIS_BF16, below) runs on such a handle and honours this contract point for
+ * point: its K | V ring and its carried conv rows are the bf16 qkv and pointwise_conv1 rows themselves, nothing is rounded a second time.
  * Requires hidden_size % 32 == 0 and intermediate_size % 32 == 0 (MIS_ERR_INVALID_INPUT naming the field); any dtype but MIS_F32 /
  * MIS_BF16 and a call after finalize are refused, the handle stays usable.
  * ---------------------------------------------------------------------------------------- */
@@ -1625,6 +1627,15 @@ mis_status mis_nemotron_tap(mis_nemotron*, int stage, float* out, int64_t capaci
  * left % (right + 1) != 0; a context outside the distances of the listed contexts; a conv pad that is not causal; max_pass_frames below C. */
 typedef struct mis_nemotron_stream mis_nemotron_stream;
 mis_status mis_nemotron_stream_create(mis_nemotron*, int streams, int left, int right, int max_pass_frames, mis_nemotron_stream** out);
+/* MIS_F32: exactly mis_nemotron_stream_create.  MIS_BF16 (csrc/nemotron_stream_bf16.h): the session's Conformer blocks run on
+ * v_mfma_f32_16x16x32_bf16 under the bf16 encoder's precision contract, on the bf16 matrices and tables of a model finalized with
+ * mis_nemotron_set_encoder_dtype(MIS_BF16) - on an f32 model it is refused (MIS_ERR_INVALID_INPUT naming encoder_dtype).  Its yardstick is
+ * the offline bf16 engine on the same model: the block taps, the prompt output, the joint.enc rows, the tokens and the absolute frames,
+ * bit for bit, for any split into feeds, any slot and any neighbours.  State per block: the ring holds bf16 K | V and the conv module
+ * carries its last conv_kernel_size - 1 bf16 pointwise_conv1 rows.  The stem, the prompt kernel, joint.enc, the decode, the launch count of
+ * a pass and every other mis_nemotron_stream_* call are the same for both kinds of session. */
+mis_status mis_nemotron_stream_create_dtype(mis_nemotron*, int streams, int left, int right, int max_pass_frames, mis_dtype dtype,
+                                            mis_nemotron_stream** out);
 void       mis_nemotron_stream_destroy(mis_nemotron_stream*);
 /* stream 0..streams-1, or -1 for all: zero state, counters 0, the prompt index of its next utterance; the other streams are untouched */
 mis_status mis_nemotron_stream_reset(mis_nemotron_stream*, int stream, int lang);

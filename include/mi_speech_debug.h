@@ -378,7 +378,9 @@ mis_status mis_debug_nemotron_timing(mis_nemotron*, float* ms);
  *   nemotron_attn_bf16: k_nm_attn_bf16, head sizes 1..128; the arguments of nemotron_attn with bf16 qkv and table, out bf16.
  *   nemotron_dwconv_ln_bf16: k_nm_glu_dwconv_ln_bf16; pw bf16 [batch Tp][2 C], taps f32 [k][C], bias f32 [C] or NULL -> out bf16
  *     [batch Tp][C], stats f32 [batch Tp][2] = mean, rstd of the unrounded outputs.
- *   nemotron_gemm_bf16: parakeet_gemm_bf16 with the third load, 2: x bf16 [batch Tp][K] read as SiLU((x - mean) rstd lnw + lnb). */
+ *   nemotron_gemm_bf16: parakeet_gemm_bf16 with the third load, 2: x bf16 [batch Tp][K] read as SiLU((x - mean) rstd lnw + lnb), and the
+ *     rules 2 / 3 / 4: the stream session's short-pass contraction k_nm_gemm_bf16_rows (csrc/nemotron_stream_bf16.h) at 64 / 32 / 16
+ *     columns a block, batch <= 64.  Its live rows have the bits of rule 0; the rows behind cnt[b] are left unwritten (0xFF bytes). */
 mis_status mis_debug_nemotron_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads, int hd,
                                         float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp, int prow, int poff, int left,
                                         int right, int Tcap, int ldo, uint16_t* out, int repeat, float* ms);
@@ -395,7 +397,13 @@ mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi, int rule,
  *   nemotron_rnnt_stream: k_nm_rnnt_stream on a pass of cnt[b] frames at pos[b] .., resumed from and stored back to state
  *     [streams][4 P + J] and ist [streams][4] = started, tokens, flag, joint evaluations (zeros: a fresh stream); the pass's tokens /
  *     frames land in [streams][cap] at index (token count - tok0[b]).
- *   nemotron_stream_timing: device milliseconds of the last feed, copies included. */
+ *   nemotron_stream_timing: device milliseconds of the last feed, copies included.
+ *   nemotron_stream_decode_timing: device milliseconds of k_nm_rnnt_stream in the last pass of the last feed (benches: the encoder / decode
+ *     split of a one-pass feed).  The first call turns the two event records on; -1 while the last feed has recorded none.
+ *   nemotron_attn_stream_bf16: k_nm_attn_stream_bf16 (csrc/nemotron_stream_bf16.h); nemotron_attn_stream's arguments with q, ring, table
+ *     and out as bf16 bit patterns, head sizes 1..128; Tp <= 16 launches 16 queries a block, above 32.
+ *   nemotron_dwconv_ln_stream_bf16: k_nm_glu_dwconv_ln_stream_bf16; nemotron_dwconv_ln_bf16's arguments (padl = k - 1) with hist_in / hist_out
+ *     bf16 [batch][k - 1][2 C]: the pointwise_conv1 rows in front of the pass (zeros: frame 0) and the ones the next pass gets. */
 mis_status mis_debug_nemotron_attn_stream(int device, const float* q, const float* ring, int R, const int32_t* cnt, const int32_t* pos, int streams, int Tp,
                                           int heads, int hd, float qscale, float sdk, const float* u, const float* v, const float* P, int ldp, int prow,
                                           int poff, int left, int right, float* out, int repeat, float* ms_out);
@@ -404,6 +412,12 @@ mis_status mis_debug_nemotron_rnnt_stream(int device, const float* encp, const i
                                           const float* const* whh, const float* const* bih, const float* const* bhh, const float* wp, const float* bp,
                                           const float* wo, const float* bo, float* state, int32_t* ist, int32_t* tokens, int32_t* frames);
 mis_status mis_debug_nemotron_stream_timing(mis_nemotron_stream*, float* ms);
+mis_status mis_debug_nemotron_stream_decode_timing(mis_nemotron_stream*, float* ms);
+mis_status mis_debug_nemotron_attn_stream_bf16(int device, const uint16_t* q, const uint16_t* ring, int R, const int32_t* cnt, const int32_t* pos, int streams,
+                                               int Tp, int heads, int hd, float qscale, float sdk, const float* u, const float* v, const uint16_t* P, int ldp,
+                                               int prow, int poff, int left, int right, uint16_t* out, int repeat, float* ms_out);
+mis_status mis_debug_nemotron_dwconv_ln_stream_bf16(int device, const uint16_t* pw, const float* taps, const float* bias, const int32_t* cnt, int batch, int Tp,
+                                                    int C, int k, int padl, const uint16_t* hist_in, uint16_t* hist_out, uint16_t* out, float* stats);
 
 /* csrc/canary.hip: the decode step's kernels on caller-supplied host data (every input followed by NaNs, every output guarded).
  *   canary_lin: k_cn_lin with S forced by the caller.  X [Mrows, K] of which the first M (1..64) rows are live, W [N, K], bias [N] or NULL.

@@ -530,6 +530,7 @@ SYMBOLS = {
     "mis_nemotron_generate": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "mis_nemotron_tap": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "mis_nemotron_stream_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "mis_nemotron_stream_create_dtype": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
     "mis_nemotron_stream_destroy": (None, [_P]),
     "mis_nemotron_stream_reset": (C.c_int, [_P, C.c_int, C.c_int]),
     "mis_nemotron_stream_feed": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
@@ -756,6 +757,10 @@ DEBUG_SYMBOLS = {
     "mis_debug_nemotron_rnnt_stream": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                                  _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mis_debug_nemotron_stream_timing": (C.c_int, [_P, _P]),
+    "mis_debug_nemotron_stream_decode_timing": (C.c_int, [_P, _P]),
+    "mis_debug_nemotron_attn_stream_bf16": (C.c_int, [C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "mis_debug_nemotron_dwconv_ln_stream_bf16": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mis_debug_encodec_encode_tap": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int32),
                                                C.POINTER(C.c_int64)]),
     "mis_debug_marvis_rope_tables": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P, _P]),

@@ -40,6 +40,7 @@
 // Launches: generate = 2 (front end) + 4 (stem) + 1 (intake) + 15 L + 2 (prompt kernel, if the model has one) + 1 (joint.enc) + 1 (decode).
 #include "nemotron_kernels.h"
 #include "nemotron_encoder_bf16.h"
+#include "nemotron_stream_bf16.h"                                  // the short-pass contraction: a rule of mis_debug_nemotron_gemm_bf16
 
 
 // ============================================================================ kernel B: chunked-limited attention, head sizes 65..128
@@ -1028,7 +1029,8 @@ extern "C" mis_status mis_debug_nemotron_dwconv_ln_bf16(int device, const uint16
 }
 
 // ONE launch of k_pk_gemm_bf16 as mis_debug_parakeet_gemm_bf16, with load 2 (PKB_LOAD_LN_SILU): x bf16 [batch Tp][K] read as
-// SiLU((x - mean) rstd lnw + lnb), stats [batch Tp][2], lnw, lnb [K]
+// SiLU((x - mean) rstd lnw + lnb), stats [batch Tp][2], lnw, lnb [K].  rule 2 / 3 / 4: k_nm_gemm_bf16_rows (nemotron_stream_bf16.h) at 64 /
+// 32 / 16 columns a block, batch <= 64; it leaves the rows behind cnt[b] unwritten (0xFF bytes in out)
 extern "C" mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi, int rule, const void* x, const float* stats, const float* lnw, const float* lnb,
                                                    const uint16_t* w, const float* bias, const float* R, float ra, const int32_t* cnt, int batch, int Tp, int K,
                                                    int N, void* out, int repeat, float* ms) {
@@ -1036,8 +1038,14 @@ extern "C" mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi
     MIS_REQUIRE(x && w && cnt && out && batch >= 1 && batch <= 65535 && Tp >= 1 && K >= 32 && K % 32 == 0 && N >= 8 && N % 8 == 0, MIS_ERR_INVALID_INPUT,
                 "Nemotron bf16 GEMM: pointers, positive batch and Tp, K a multiple of 32 and N a multiple of 8 are required");
     MIS_REQUIRE((load == PKB_LOAD_BF16 || ((load == PKB_LOAD_LN || load == PKB_LOAD_LN_SILU) && stats && lnw && lnb)) && epi >= PKB_EPI_NONE &&
-                    epi <= PKB_EPI_RES && (epi != PKB_EPI_RES || R) && (rule == PKB_TILE64 || rule == PKB_TILE32), MIS_ERR_INVALID_INPUT,
-                "Nemotron bf16 GEMM: unknown load / epilogue / rule, or a missing operand");
+                    epi <= PKB_EPI_RES && (epi != PKB_EPI_RES || R) && rule >= PKB_TILE64 && rule <= NMR_ROWS16 &&
+                    (rule < NMR_ROWS64 || batch <= NMR_MAXB), MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 GEMM: unknown load / epilogue / rule (the short-pass rules take at most %d batch entries), or a missing operand", NMR_MAXB);
+    int live = 0;
+    for (int b = 0; b < batch; ++b) {
+        MIS_REQUIRE(cnt[b] >= 0, MIS_ERR_INVALID_INPUT, "Nemotron bf16 GEMM: negative count of row %d", b);
+        live += std::min(cnt[b], Tp);
+    }
     const size_t rows = (size_t)batch * Tp;
     MIS_REQUIRE((int64_t)rows * K <= NMD_MAX_ELEMS && (int64_t)rows * N <= NMD_MAX_ELEMS && (int64_t)N * K <= NMD_MAX_ELEMS, MIS_ERR_INVALID_INPUT,
                 "Nemotron bf16 GEMM: tensor too large");
@@ -1061,7 +1069,7 @@ extern "C" mis_status mis_debug_nemotron_gemm_bf16(int device, int load, int epi
     o.alloc(rows * N * es, (size_t)64 * N * es);
     p.Yf = reinterpret_cast<float*>(o.p()); p.Yb = reinterpret_cast<bf16_t*>(o.p());
     p.ldx = K; p.W = dw.p; p.ldy = N; p.cnt = nmd_ip(dcnt); p.Tp = Tp; p.K = K; p.N = N; p.epi = epi;
-    nmd_run(c, [&] { nmb_gemm_launch(&c, p, load, rule, batch); c.launches = 1; }, repeat, ms);
+    nmd_run(c, [&] { nmr_gemm_launch(&c, p, load, rule, batch, live); c.launches = 1; }, repeat, ms);
     nmd_rows_out(o, out, rows, N, N, es);
     MIS_API_END
 }

@@ -33,7 +33,11 @@
 //
 // Launches of a pass: 9 + 16 L + 2 p = 1 (mel) + 4 (stem) + 1 (intake) + 16 L (the offline block + the ring put) + 2 p (prompt kernel) +
 // 1 (joint.enc) + 1 (decode) + 1 (mel cache).  A feed is walked in passes of at most max_pass_frames / C chunks a stream.
+//
+// bf16 sessions (mis_nemotron_stream_create_dtype with MIS_BF16 on a model finalized in bf16 mode): the 16 L block launches of a pass are
+// nemotron_stream_bf16.h's, launch for launch, and the yardstick is the offline bf16 engine; everything around the blocks is the code here.
 #include "nemotron_kernels.h"
+#include "nemotron_stream_bf16.h"
 
 #include <algorithm>
 #include <vector>
@@ -459,12 +463,15 @@ struct mis_nemotron_stream {
     NmCtx ctx{};
     size_t SS = 0, o_ring = 0, o_hist = 0, o_mel = 0, o_dec = 0;    // a stream's state: floats, and the offsets of its parts
     DevBuf<float> state, stage, win, s0, s1, s2, emb, h, stats, big, qkv, att, prm, encp, tapbuf;
+    int bf16 = 0;                                                   // the blocks of nemotron_stream_bf16.h: ring and history hold bf16, as do these
+    DevBuf<bf16_t> big16, qkv16, att16;
     DevBuf<int> ist, par, dtok, dfrm, tapfill;
     PinnedBuf<float> hstage;
     PinnedBuf<int> hpar, hist_;
     std::vector<NmsStream> st;
     int tapcap = 0, last_launches = 0;
-    HipEvents<2> ev;
+    HipEvents<4> ev;                                                // a feed's start and end; the last pass's decode launch (split timing)
+    bool split = false, split_timed = false;                        // split_timed: the last feed recorded both events
     float last_ms = 0.0f;
 };
 
@@ -472,13 +479,18 @@ static size_t nms_hist(const mis_nemotron_stream* s, int parity, int layer) {
     return s->o_hist + ((size_t)parity * s->m->L + layer) * (s->m->ck - 1) * s->m->d;
 }
 
-extern "C" mis_status mis_nemotron_stream_create(mis_nemotron* m, int streams, int left, int right, int max_pass_frames, mis_nemotron_stream** out) {
+extern "C" mis_status mis_nemotron_stream_create_dtype(mis_nemotron* m, int streams, int left, int right, int max_pass_frames, mis_dtype dtype,
+                                                       mis_nemotron_stream** out) {
     MIS_API_BEGIN
     MIS_REQUIRE(m && out, MIS_ERR_INVALID_INPUT, "null argument");
     MIS_REQUIRE(m->finalized, MIS_ERR_NOT_INITIALIZED, "model not finalized");
     MIS_REQUIRE(streams >= 1 && streams <= NM_MAX_BATCH, MIS_ERR_INVALID_INPUT, "streams %d outside 1..%d", streams, NM_MAX_BATCH);
-    MIS_REQUIRE(!m->enc_bf16, MIS_ERR_INVALID_INPUT,
-                "encoder_dtype bfloat16: a stream session runs the f32 block matrices, which are not resident in this mode (offline engine only)");
+    MIS_REQUIRE(dtype == MIS_F32 || dtype == MIS_BF16, MIS_ERR_INVALID_INPUT, "stream session dtype %d: only MIS_F32 and MIS_BF16 are implemented", (int)dtype);
+    const bool bf = dtype == MIS_BF16;
+    MIS_REQUIRE(bf || !m->enc_bf16, MIS_ERR_INVALID_INPUT,
+                "encoder_dtype bfloat16: an f32 stream session runs the f32 block matrices, which are not resident in this mode (ask for a bf16 session)");
+    MIS_REQUIRE(!bf || m->enc_bf16, MIS_ERR_INVALID_INPUT,
+                "a bf16 stream session runs the bf16 block matrices: finalize the model with encoder_dtype bfloat16 (nothing is rounded for a session)");
     MIS_REQUIRE(m->cfg.normalize == 0, MIS_ERR_INVALID_INPUT,
                 "normalize per_feature: a stream session requires NA mel normalization (per-utterance statistics are not frozen incrementally)");
     MIS_REQUIRE(right >= 0 && right < (1 << 20) && left >= 0 && left % (right + 1) == 0, MIS_ERR_INVALID_INPUT,
@@ -502,15 +514,22 @@ extern "C" mis_status mis_nemotron_stream_create(mis_nemotron* m, int streams, i
     s->sstage = (int64_t)s->maxchunks * C * 8 * NEMO_HOP + NEMO_NFFT + 8;
     const size_t B = streams, d = m->d, Lr = m->L, mels = m->mels, Cc = m->C, M = B * s->Tq;
     s->o_ring = 0;
-    s->o_hist = s->o_ring + Lr * s->R * 2 * d;
-    s->o_mel = s->o_hist + 2 * Lr * (m->ck - 1) * d;
+    s->o_hist = s->o_ring + Lr * s->R * 2 * d / (bf ? 2 : 1);       // (a bf16 session's ring takes half the floats; its history rows are
+    s->o_mel = s->o_hist + 2 * Lr * (m->ck - 1) * d;                //  2 d bf16 = d floats, as the f32 gated frames)
     s->o_dec = s->o_mel + NMS_MEL_CACHE * mels;
     s->SS = round_up(s->o_dec + 4 * m->P + m->J, 64);
     s->state.alloc(B * s->SS); s->ist.alloc(4 * B);
     s->stage.alloc(B * s->sstage); s->win.alloc(B * s->Wp * mels);
     s->s0.alloc(B * s->T1p * m->F1 * Cc); s->s1.alloc(B * s->T2p * m->F2 * Cc); s->s2.alloc(B * s->Twp * m->F3 * Cc); s->emb.alloc(B * s->Twp * d);
-    s->h.alloc(M * d); s->stats.alloc(M * 2); s->big.alloc(M * std::max<size_t>(std::max<size_t>(m->f, 2 * d), m->PH)); s->qkv.alloc(M * 3 * d);
-    s->att.alloc(M * d);
+    s->h.alloc(M * d); s->stats.alloc(M * 2);
+    s->bf16 = bf;
+    if (bf) {                                                       // ring [R][2 d] and history [ck - 1][2 d] in bf16: the f32 state's byte counts
+        s->big16.alloc(M * std::max<size_t>(m->f, 2 * d)); s->qkv16.alloc(M * 3 * d); s->att16.alloc(M * d);
+        if (m->PH) s->big.alloc(M * m->PH);
+    } else {
+        s->big.alloc(M * std::max<size_t>(std::max<size_t>(m->f, 2 * d), m->PH)); s->qkv.alloc(M * 3 * d);
+        s->att.alloc(M * d);
+    }
     if (m->PH) s->prm.alloc(M * d);
     s->encp.alloc(M * m->J);
     s->par.alloc(NMS_FIELDS * B); s->dtok.alloc(B * m->cap); s->dfrm.alloc(B * m->cap); s->tapfill.alloc(B);
@@ -522,6 +541,10 @@ extern "C" mis_status mis_nemotron_stream_create(mis_nemotron* m, int streams, i
     s->launches = 0;
     *out = s.release();
     MIS_API_END
+}
+
+extern "C" mis_status mis_nemotron_stream_create(mis_nemotron* m, int streams, int left, int right, int max_pass_frames, mis_nemotron_stream** out) {
+    return mis_nemotron_stream_create_dtype(m, streams, left, right, max_pass_frames, MIS_F32, out);
 }
 
 extern "C" void mis_nemotron_stream_destroy(mis_nemotron_stream* s) {
@@ -595,6 +618,65 @@ extern "C" mis_status mis_nemotron_stream_plan(int64_t seen, int final, int chun
     MIS_API_END
 }
 
+// Which contraction a bf16 pass takes: k_nm_gemm_bf16_rows, or k_pk_gemm_bf16 at 64 x 64.  Either gives an element the same bits, so this is
+// a matter of time alone.  The short-pass kernel's time follows its 16-row tiles, ceil(live rows / 16); the 64 x 64 rule's follows its 64-row
+// tiles, one per ceil(frames / 64) of every stream with frames, however few of the 64 rows are live.  Measured per role and pass shape, one
+// chunk and three chunks a stream (profiles/nemotron_stream_bf16/README.md): summed over a block the short-pass kernel wins wherever it
+// has no more tiles than the 64 x 64 rule (64 x 1, 16 x 14, 64 x 14 frames) and up to 11 tiles against fewer (4 streams x 44 frames), ties at
+// 22 tiles against 8 and loses from 44 against 16 on.  Hence: the short-pass kernel while its tiles are no more than the 64 x 64 rule's, or
+// no more than NMS_ROWS_TILES.  Inside it the roles that load a bf16 activation are fastest at 32 columns a block and the roles that stage a
+// LayerNorm at 64 (a block's waves share the staging arithmetic).
+constexpr int NMS_ROWS_TILES = 16;
+
+// the blocks of a bf16 session's pass on s->h: the f32 loop of nms_pass launch for launch (16 L), on nemotron_stream_bf16.h's kernels;
+// live = the pass's frames over all streams, tiles64 = the 64-row tiles they occupy stream by stream
+template <class Tap>
+static void nms_blocks_bf16(mis_nemotron_stream* s, int live, int tiles64, Tap&& tap) {
+    mis_nemotron* m = s->m;
+    const int S = s->S, d = m->d, f = m->f, Tp = s->Tq, M = S * Tp;
+    const int *cn = s->par.p + NMS_N * S, *cpos = s->par.p + NMS_POS * S;
+    bf16_t* st = reinterpret_cast<bf16_t*>(s->state.p);            // a stream's state as bf16 elements: offsets and stride double
+    const size_t ss = 2 * s->SS;
+    const bool rows = cdiv(live, 16) <= std::max(tiles64, NMS_ROWS_TILES);
+    auto stats = [&]() { MIS_LAUNCH(s, k_sf_stats, dim3(cdiv(M, 4)), dim3(256), s->h.p, s->stats.p, d, 1e-5f, M); };
+    auto gemm = [&](const PkbRole& r, const bf16_t* W, const float* bias, int N, int K, const float* lnw, const float* lnb, const bf16_t* xb, bf16_t* yb, float ra) {
+        PkbGemm p{};
+        p.W = W; p.bias = bias; p.cnt = cn; p.Tp = Tp; p.K = K; p.N = N; p.epi = r.epi; p.ldx = K; p.ldy = N;
+        if (r.load != PKB_LOAD_BF16) { p.stats = s->stats.p; p.lnw = lnw; p.lnb = lnb; }
+        if (r.load == PKB_LOAD_LN) p.Xf = s->h.p;
+        else p.Xb = xb;
+        if (r.epi == PKB_EPI_RES) { p.Yf = s->h.p; p.R = s->h.p; p.ldr = N; p.ra = ra; }
+        else p.Yb = yb;
+        nmr_gemm_launch(s, p, r.load, !rows ? PKB_TILE64 : r.load == PKB_LOAD_BF16 ? NMR_ROWS32 : NMR_ROWS64, S, live);
+    };
+    bf16_t *big = s->big16.p, *qkv = s->qkv16.p, *att = s->att16.p;
+    for (int li = 0; li < m->L; ++li) {
+        const mis_nemotron::Layer& l = m->fc[li];
+        const mis_nemotron::Layer16& w = m->fc16[li];
+        stats();
+        gemm(PKB_ROLE[PKB_FF1A], w.ff1a, l.ff1a.b, f, d, l.ln1w, l.ln1b, nullptr, big, 0.0f);
+        gemm(PKB_ROLE[PKB_FF1B], w.ff1b, l.ff1b.b, d, f, nullptr, nullptr, big, nullptr, 0.5f);
+        stats();
+        gemm(PKB_ROLE[PKB_QKV], w.qkv, l.qkv.b, 3 * d, d, l.lnaw, l.lnab, nullptr, qkv, 0.0f);
+        bf16_t* ring = st + 2 * s->o_ring + (size_t)li * s->R * 2 * d;
+        MIS_LAUNCH(s, k_nm_ring_put_bf16, dim3(Tp, S), dim3(256), qkv, cn, cpos, ring, ss, s->R, Tp, d);
+        NmbAttnS ap{qkv, 3 * d, ring, ss, s->R, 2 * d, d, att, d, cn, cpos, Tp, m->hd, 1.0f, sqrtf((float)m->hd), l.u, l.v, w.P, d, -m->tab_lo,
+                    s->ctx.C, s->ctx.L, s->ctx.dlo, s->ctx.dhi};
+        nmb_attn_stream(s, ap, m->H, m->hd, S);
+        gemm(PKB_ROLE[PKB_O], w.o, l.o.b, d, d, nullptr, nullptr, att, nullptr, 1.0f);
+        stats();
+        gemm(PKB_ROLE[PKB_PW1], w.pw1, l.pw1.b, 2 * d, d, l.lncw, l.lncb, nullptr, big, 0.0f);
+        nmb_glu_dwconv_ln_stream(s, big, l.dw, l.dwb, cn, att, s->stats.p, st + 2 * nms_hist(s, s->parity, li), st + 2 * nms_hist(s, s->parity ^ 1, li), ss, Tp, d,
+                                 m->ck, S);
+        gemm(NMB_PW2, w.pw2, l.pw2.b, d, d, l.cnw, l.cnb, att, nullptr, 1.0f);
+        stats();
+        gemm(PKB_ROLE[PKB_FF2A], w.ff2a, l.ff2a.b, f, d, l.ln2w, l.ln2b, nullptr, big, 0.0f);
+        gemm(PKB_ROLE[PKB_FF2B], w.ff2b, l.ff2b.b, d, f, nullptr, nullptr, big, nullptr, 0.5f);
+        MIS_LAUNCH(s, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), s->h.p, s->h.p, l.lnow, l.lnob, d, 1e-5f, M, cn, Tp);
+        tap(li + 1, s->h.p, d, Tp, 0);
+    }
+}
+
 // one pass over every stream that has a whole chunk ready (finished streams: whatever is left); false: nobody had work
 static bool nms_pass(mis_nemotron_stream* s) {
     mis_nemotron* m = s->m;
@@ -627,6 +709,8 @@ static bool nms_pass(mis_nemotron_stream* s) {
         x.tail0 = keep;
     }
     if (!maxwin) return false;
+    int live = 0, tiles64 = 0;                                      // the frames of the pass over all streams; their 64-row tiles, stream by stream
+    for (int b = 0; b < S; ++b) { live += par[NMS_N * S + b]; tiles64 += cdiv(par[NMS_N * S + b], 64); }
     hipStream_t q = s->stream;
     HIP_CHECK(hipMemcpyAsync(s->par.p, par, (size_t)NMS_FIELDS * S * 4, hipMemcpyHostToDevice, q));
     if (used) HIP_CHECK(hipMemcpyAsync(s->stage.p, stage, used * 4, hipMemcpyHostToDevice, q));
@@ -672,7 +756,8 @@ static bool nms_pass(mis_nemotron_stream* s) {
         p.R = hres; p.ldr = N; p.ra = ra;
         sf_gemm(s, p, S);
     };
-    for (int li = 0; li < m->L; ++li) {                            // the offline block's 15 launches + the ring put
+    if (s->bf16) nms_blocks_bf16(s, live, tiles64, tap);
+    else for (int li = 0; li < m->L; ++li) {                       // the offline block's 15 launches + the ring put
         const mis_nemotron::Layer& l = m->fc[li];
         stats(s->h.p);
         ln_lin(s->h.p, l.ln1w, l.ln1b, l.ff1a, s->big.p, f, SF_ACT_SILU);
@@ -714,7 +799,9 @@ static bool nms_pass(mis_nemotron_stream* s) {
     tap(m->L + 2, s->encp.p, m->J, Tp, 0);
     NmRnntS rp{m->rnnt, st + s->o_dec, s->SS, s->ist.p, cpos, dp + NMS_TOK0 * S};
     rp.r.encp = s->encp.p; rp.r.cnt = cn; rp.r.Tp = Tp; rp.r.tokens = s->dtok.p; rp.r.frames = s->dfrm.p;
+    if (s->split) HIP_CHECK(hipEventRecord(s->ev[2], q));
     MIS_LAUNCH(s, k_nm_rnnt_stream, dim3(S), dim3(NM_NT), rp);
+    if (s->split) { HIP_CHECK(hipEventRecord(s->ev[3], q)); s->split_timed = true; }
     MIS_LAUNCH(s, k_nm_mel_roll, dim3(NMS_MEL_CACHE, S), dim3(256), s->win.p, dp, S, st + s->o_mel, s->SS, s->Wp, m->mels);
     if (s->tapcap) { hipLaunchKernelGGL(k_nm_tap_advance, dim3(1), dim3(64), 0, q, dp, S, s->tapfill.p, 0); }
     return true;
@@ -746,6 +833,7 @@ extern "C" mis_status mis_nemotron_stream_feed(mis_nemotron_stream* s, const flo
     }
     hipStream_t q = s->stream;
     s->launches = 0;
+    s->split_timed = false;
     HIP_CHECK(hipEventRecord(s->ev[0], q));
     if (s->tapcap) hipLaunchKernelGGL(k_nm_tap_advance, dim3(1), dim3(64), 0, q, s->par.p, S, s->tapfill.p, 1);
     while (nms_pass(s)) {}
@@ -805,6 +893,17 @@ extern "C" mis_status mis_debug_nemotron_stream_timing(mis_nemotron_stream* s, f
     MIS_API_BEGIN
     MIS_REQUIRE(s && ms, MIS_ERR_INVALID_INPUT, "null argument");
     HIP_CHECK(hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
+    MIS_API_END
+}
+
+// device milliseconds of k_nm_rnnt_stream in the last pass of the last feed; -1 when that feed ran no pass or ran before the first call
+// here, which turns the two event records on
+extern "C" mis_status mis_debug_nemotron_stream_decode_timing(mis_nemotron_stream* s, float* ms) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(s && ms, MIS_ERR_INVALID_INPUT, "null argument");
+    *ms = -1.0f;
+    if (s->split_timed) HIP_CHECK(hipEventElapsedTime(ms, s->ev[2], s->ev[3]));
+    s->split = true;
     MIS_API_END
 }
 
@@ -900,5 +999,86 @@ extern "C" mis_status mis_debug_nemotron_rnnt_stream(int device, const float* en
     HIP_CHECK(hipMemcpy(frames, ob + n, n * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(state, dst.p, streams * ss * 4, hipMemcpyDeviceToHost));
     HIP_CHECK(hipMemcpy(ist, dis.p, (size_t)4 * streams * 4, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ---------------------------------------------------------------------------- the bf16 session's kernels (nemotron_stream_bf16.h)
+// ONE launch of k_nm_attn_stream_bf16: mis_debug_nemotron_attn_stream's arguments with bf16 q, ring and table, head sizes 1..128 -> out bf16
+extern "C" mis_status mis_debug_nemotron_attn_stream_bf16(int device, const uint16_t* q, const uint16_t* ring, int R, const int32_t* cnt, const int32_t* pos,
+                                                          int streams, int Tp, int heads, int hd, float qscale, float sdk, const float* u, const float* v,
+                                                          const uint16_t* P, int ldp, int prow, int poff, int left, int right, uint16_t* out, int repeat,
+                                                          float* ms_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(q && ring && cnt && pos && u && v && P && out && streams >= 1 && streams <= 65535 && Tp >= 1 && heads >= 1 && heads <= 65535 && hd >= 1 &&
+                    hd <= 128 && prow >= 1, MIS_ERR_INVALID_INPUT, "Nemotron bf16 stream attention: every pointer, positive sizes and a head size of 1..128 are required");
+    MIS_REQUIRE(right >= 0 && right < (1 << 20) && left >= 0 && left % (right + 1) == 0, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 stream attention: right >= 0, left >= 0 and left %% (right + 1) == 0 are required");
+    MIS_REQUIRE(R % 32 == 0 && R >= left + Tp + 32 && R <= (1 << 20), MIS_ERR_INVALID_INPUT, "Nemotron bf16 stream attention: R %d must be a multiple of 32 >= left + Tp + 32", R);
+    const int C = right + 1, L = left / C, w = heads * hd;
+    NmCtx x{C, L, -(C - 1), L * C + C - 1};
+    MIS_REQUIRE(x.dlo + poff >= 0 && x.dhi + poff < prow && ldp >= w, MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 stream attention: the table rows %d..%d do not cover the distances %d..%d", -poff, prow - 1 - poff, x.dlo, x.dhi);
+    for (int b = 0; b < streams; ++b)
+        MIS_REQUIRE(cnt[b] >= 0 && cnt[b] <= Tp && pos[b] >= 0 && pos[b] < (1 << 30), MIS_ERR_INVALID_INPUT, "Nemotron bf16 stream attention: stream %d count / position", b);
+    HIP_CHECK(hipSetDevice(device));
+    NmsdCtx c;
+    const size_t rows = (size_t)streams * Tp, rs = (size_t)R * 2 * w;
+    DevBuf<uint16_t> dq, dr, dP;
+    DevBuf<uint32_t> dc, dpos, du, dv;
+    alloc16(dq, q, rows * w, BF16_NAN); alloc16(dr, ring, streams * rs, BF16_NAN); alloc16(dP, P, (size_t)prow * ldp, BF16_NAN);
+    alloc32(dc, cnt, streams, 0x7FFFFFFFu); alloc32(dpos, pos, streams, 0x7FFFFFFFu); alloc32(du, u, w, F32_NAN); alloc32(dv, v, w, F32_NAN);
+    GuardedOut o;
+    o.alloc(rows * w * 2, (size_t)32 * w * 2);
+    auto fp = [](const DevBuf<uint32_t>& d) { return reinterpret_cast<const float*>(d.p); };
+    NmbAttnS p{dq.p, w, dr.p, rs, R, 2 * w, w, reinterpret_cast<bf16_t*>(o.p()), w, reinterpret_cast<const int*>(dc.p), reinterpret_cast<const int*>(dpos.p), Tp, hd,
+               qscale, sdk, fp(du), fp(dv), dP.p, ldp, poff, x.C, x.L, x.dlo, x.dhi};
+    nmb_attn_stream(&c, p, heads, hd, streams);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    MIS_REQUIRE(c.launches == 1, MIS_ERR_GENERATION_FAILED, "%d launches where one was meant", c.launches);
+    o.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+    if (repeat > 1 && ms_out) {
+        HipEvents<2> ev;
+        HIP_CHECK(hipEventRecord(ev[0], c.stream));
+        for (int i = 0; i < repeat; ++i) nmb_attn_stream(&c, p, heads, hd, streams);
+        HIP_CHECK(hipEventRecord(ev[1], c.stream));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipEventElapsedTime(ms_out, ev[0], ev[1]));
+        *ms_out /= (float)repeat;
+    }
+    MIS_API_END
+}
+
+// ONE launch of k_nm_glu_dwconv_ln_stream_bf16: mis_debug_nemotron_dwconv_ln_bf16's arguments at the causal pad (padl = k - 1 is required)
+// with hist_in / hist_out bf16 [batch][k - 1][2 C], the pointwise_conv1 rows in front of the pass and behind it
+extern "C" mis_status mis_debug_nemotron_dwconv_ln_stream_bf16(int device, const uint16_t* pw, const float* taps, const float* bias, const int32_t* cnt, int batch,
+                                                               int Tp, int C, int k, int padl, const uint16_t* hist_in, uint16_t* hist_out, uint16_t* out,
+                                                               float* stats) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(pw && taps && cnt && out && stats && hist_in && hist_out && batch >= 1 && batch <= 65535 && Tp >= 1 && C >= 1 && k >= 2 && k <= SF_DW_MAXK &&
+                    padl == k - 1 && (int64_t)batch * Tp * 2 * C <= ((int64_t)1 << 28), MIS_ERR_INVALID_INPUT,
+                "Nemotron bf16 stream conv module: every pointer, positive batch, Tp, C, 2 <= k <= %d and padl = k - 1 are required", SF_DW_MAXK);
+    for (int b = 0; b < batch; ++b) MIS_REQUIRE(cnt[b] >= 0 && cnt[b] <= Tp, MIS_ERR_INVALID_INPUT, "Nemotron bf16 stream conv module: count of row %d", b);
+    HIP_CHECK(hipSetDevice(device));
+    NmsdCtx c;
+    const size_t rows = (size_t)batch * Tp, hs = (size_t)(k - 1) * 2 * C;
+    DevBuf<uint16_t> dpw, dh;
+    DevBuf<uint32_t> dt, db, dc;
+    alloc16(dpw, pw, rows * 2 * C, BF16_NAN); alloc16(dh, hist_in, batch * hs, BF16_NAN);
+    alloc32(dt, taps, (size_t)k * C, F32_NAN); alloc32(dc, cnt, batch, 0x7FFFFFFFu);
+    if (bias) alloc32(db, bias, C, F32_NAN);
+    GuardedOut o, st, ho;
+    o.alloc(rows * C * 2, 4096); st.alloc(rows * 2 * 4, 4096); ho.alloc(batch * hs * 2, 4096);
+    nmb_glu_dwconv_ln_stream(&c, dpw.p, reinterpret_cast<const float*>(dt.p), bias ? reinterpret_cast<const float*>(db.p) : nullptr,
+                             reinterpret_cast<const int*>(dc.p), reinterpret_cast<bf16_t*>(o.p()), reinterpret_cast<float*>(st.p()), dh.p,
+                             reinterpret_cast<bf16_t*>(ho.p()), hs, Tp, C, k, batch);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    MIS_REQUIRE(c.launches == 1, MIS_ERR_GENERATION_FAILED, "%d launches where one was meant", c.launches);
+    o.check_guards(); st.check_guards(); ho.check_guards();
+    HIP_CHECK(hipMemcpy(out, o.p(), o.body, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(stats, st.p(), st.body, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hist_out, ho.p(), ho.body, hipMemcpyDeviceToHost));
     MIS_API_END
 }

@@ -18,7 +18,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._handle import NativeHandle, pack_rows, read_safetensors_dir
+from ._handle import _ENCODER_DTYPES, NativeHandle, pack_rows, read_safetensors_dir
 from .generation import AudioGenerationError, check
 from .parakeet import ParakeetResult, ParakeetToken, parakeet_sanitize
 from .sensevoice import read_sentencepiece_pieces
@@ -389,17 +389,20 @@ class NemotronASR(NativeHandle):
 
     create_stream_session = stream_session
 
-    def make_stream_session(self, language=None, chunk_ms=None, streams: int = 1, att_context_size=None) -> "NemotronStreamSession":
-        """makeStreamSession (f32 models only: with encoder_dtype="bfloat16" the f32 block matrices the session runs are not resident)"""
-        return NemotronStreamSession(self, streams, language, att_context_size, chunk_ms)
+    def make_stream_session(self, language=None, chunk_ms=None, streams: int = 1, att_context_size=None,
+                            encoder_dtype: str = "float32") -> "NemotronStreamSession":
+        """makeStreamSession.  encoder_dtype is the SESSION's: "float32" (the default) needs an f32 model, "bfloat16" one finalized with
+        encoder_dtype="bfloat16" (a session rounds nothing itself); the other pairing is refused."""
+        return NemotronStreamSession(self, streams, language, att_context_size, chunk_ms, encoder_dtype=encoder_dtype)
 
-    def transcribe_streaming(self, audio, language=None, chunk_ms: int = 480, on_delta=None) -> ParakeetResult:
+    def transcribe_streaming(self, audio, language=None, chunk_ms: int = 480, on_delta=None, encoder_dtype: str = "float32") -> ParakeetResult:
         """transcribeStreaming: the audio through a session at the model's native chunk, fed chunk_ms at a time as a live caller would;
-        on_delta receives every non-empty new fragment."""
+        on_delta receives every non-empty new fragment; encoder_dtype as make_stream_session's."""
         wave = np.asarray(audio, np.float32)
         wave = wave.mean(axis=-1, dtype=np.float32) if wave.ndim > 1 else wave
         chunk = max(1, self.config.sampling_rate * chunk_ms // 1000)
-        s = self.make_stream_session(language)
+        # (the default goes without the keyword: callers that put a session factory of their own behind make_stream_session(language) keep working)
+        s = self.make_stream_session(language) if encoder_dtype == "float32" else self.make_stream_session(language, encoder_dtype=encoder_dtype)
         start = time.perf_counter()
         for at in list(range(0, len(wave), chunk)) + [None]:
             delta = s.finish() if at is None else s.step(wave[at: at + chunk])
@@ -469,17 +472,24 @@ class NemotronStreamSession:
     return what they decoded, finish flushes a stream's tail; the transcript equals the offline generate of the whole audio at the same
     context, token for token and frame for frame.  att_context_size / chunk_ms choose the context (chunk_context); left must be a multiple
     of right + 1.  text / tokens / segments / is_finished speak of stream 0, as the reference's one-stream session; sentences(stream), raw(stream)
-    of any."""
+    of any.  encoder_dtype="bfloat16" (on a model finalized in that mode): the blocks of csrc/nemotron_stream_bf16.h, whose yardstick is the
+    offline bf16 engine of the same model."""
     _h = None
 
-    def __init__(self, model: NemotronASR, streams: int = 1, language=None, att_context_size=None, chunk_ms=None, max_pass_frames=None):
-        self.model, self.streams = model, int(streams)
+    def __init__(self, model: NemotronASR, streams: int = 1, language=None, att_context_size=None, chunk_ms=None, max_pass_frames=None,
+                 encoder_dtype: str = "float32"):
+        self.model, self.streams, self.encoder_dtype = model, int(streams), encoder_dtype
+        if encoder_dtype not in _ENCODER_DTYPES:
+            raise _bad(f"encoder_dtype {encoder_dtype!r}: only {sorted(_ENCODER_DTYPES)} are implemented")
         if att_context_size is not None and chunk_ms is not None:
             raise _bad("att_context_size and chunk_ms both choose the context: give one")
         self.context = model._context(att_context_size) if att_context_size is not None else chunk_context(chunk_ms, model.config.default_context)
         left, right = (int(v) for v in self.context)
         mp, h, cap = int(max_pass_frames or 3 * (right + 1)), C.c_void_p(), model.config.max_tokens
-        check(_lib.lib().mis_nemotron_stream_create(model._h, self.streams, left, right, mp, C.byref(h)))
+        if encoder_dtype == "float32":
+            check(_lib.lib().mis_nemotron_stream_create(model._h, self.streams, left, right, mp, C.byref(h)))
+        else:
+            check(_lib.lib().mis_nemotron_stream_create_dtype(model._h, self.streams, left, right, mp, _ENCODER_DTYPES[encoder_dtype], C.byref(h)))
         self._h, self._plan = h, (right + 1, max(1, mp // (right + 1)))
         self._out = [np.zeros((self.streams, cap), np.int32) for _ in range(2)]      # a feed's tokens and frames
         self._passes = 0
@@ -591,6 +601,12 @@ class NemotronStreamSession:
         """Device milliseconds of the last feed, copies included."""
         ms = C.c_float()
         check(_lib.lib().mis_debug_nemotron_stream_timing(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def decode_timing(self) -> float:
+        """Device milliseconds of the decode launch in the last pass of the last feed; the first call turns it on and returns -1."""
+        ms = C.c_float()
+        check(_lib.lib().mis_debug_nemotron_stream_decode_timing(self._h, C.byref(ms)))
         return float(ms.value)
 
     text = property(lambda self: self._state[0]["text"])
