@@ -1347,6 +1347,22 @@ int64_t    mis_deepfilternet_stream_hops_seen(const mis_deepfilternet_stream*, i
  * tensor missing or misshapen.  At a call, before any launch: batch outside 1..max_batch, a row longer than stride or max_seconds,
  * more frames than the workspace or max_source_positions hold, a count outside 1..the row stride, pad_to not 0 or a divisor of 16, a
  * null pointer.  A rejected call leaves the handle usable.
+ *
+ * bf16 encoder (opt-in, mis_sortformer_set_encoder_dtype with MIS_BF16 before finalize; csrc/parakeet_encoder_bf16.h for the Conformer
+ * blocks, csrc/sortformer_tf_bf16.h for the BART tower).  Both halves run on v_mfma_f32_16x16x32_bf16; front end, stem, encoder_proj +
+ * positions and the speaker head stay f32, every entry point and every tap works as in f32 mode (the taps are f32: both residual streams
+ * are), and the f32 mode keeps its bits, launch counts and buffers.  The Conformer blocks keep their 15 launches and the precision
+ * contract written under Parakeet below, unchanged.  A BART layer is 3 launches instead of 7: q | k | v, attention, and one launch for
+ * out_proj + residual + LayerNorm + fc1 + ReLU + fc2 + residual + LayerNorm.  Precision contract of the BART half.  f32: the stream g,
+ * positions, biases, LayerNorm parameters and statistics, the softmax, every accumulator and epilogue.  Rounded to bf16, to nearest even,
+ * once, at each of these points: the matrices q | k | v (packed), out_proj, fc1, fc2; g16, the copy of the stream the q | k | v
+ * contraction reads; the q | k | v store; q times head_size^-0.5 (scaled in f32, then rounded); the probabilities in front of P V - the row
+ * sum adds the unrounded ones; the attention output store; x1 = LayerNorm(g + out_proj(.)) as fc1's operand (its f32 value is kept for the
+ * residual); the ReLU hidden tile.  As in f32 mode a row's output is bit-identical whatever its batch, the longest row or the padding
+ * behind lens[b]: every output element is one accumulator over k-slabs of 32 in ascending order, tiles depend on the widths only, no float
+ * atomics.  The rounded matrices and distance tables exist on the device as bf16 only.  Requires hidden_size, intermediate_size,
+ * tf_d_model and encoder_ffn_dim multiples of 32, tf_d_model <= 256 and encoder_ffn_dim <= 1024 (MIS_ERR_INVALID_INPUT naming the field);
+ * any dtype but MIS_F32 / MIS_BF16 and a call after finalize are refused; the handle stays usable.
  * ---------------------------------------------------------------------------------------- */
 typedef struct mis_sortformer mis_sortformer;
 /* FCEncoderConfig, TFEncoderConfig, ModulesConfig (fc_d_model, tf_d_model_modules = its tf_d_model, num_speakers) and ProcessorConfig
@@ -1370,10 +1386,14 @@ mis_status mis_sortformer_create(const mis_sortformer_config*, int device, mis_s
  * missing weight and checks every shape (hidden_to_spks too, which nothing reads, as in the reference). */
 mis_status mis_sortformer_set_tensor(mis_sortformer*, const char* name, const void* data, mis_dtype, const int64_t* shape, int ndim);
 mis_status mis_sortformer_init_synthetic(mis_sortformer*, uint64_t seed);
+/* MIS_F32 (the default) or MIS_BF16: the Conformer blocks and the BART tower (the contract above); before finalize */
+mis_status mis_sortformer_set_encoder_dtype(mis_sortformer*, mis_dtype);
 mis_status mis_sortformer_finalize(mis_sortformer*);
 void       mis_sortformer_destroy(mis_sortformer*);
 /* kernel launches of the last call, with L_fc = num_hidden_layers and L_tf = encoder_layers: forward 11 + 15 L_fc + 7 L_tf,
- * forward_features 8 + 15 L_fc + 7 L_tf, encode_embeddings 4 + 15 L_fc + 7 L_tf, pre_encode 4, features 3 */
+ * forward_features 8 + 15 L_fc + 7 L_tf, encode_embeddings 4 + 15 L_fc + 7 L_tf, pre_encode 4, features 3.  bf16 mode: forward
+ * 12 + 15 L_fc + 3 L_tf = 3 (front end) + 4 (stem) + 1 (intake) + 15 L_fc + 1 (encoder_proj + positions) + 1 (its bf16 copy) + 3 L_tf +
+ * 2 (head); forward_features 9 + 15 L_fc + 3 L_tf, encode_embeddings 5 + 15 L_fc + 3 L_tf, pre_encode 4, features 3 */
 int        mis_sortformer_launches(const mis_sortformer*);
 /* F_b (pad_to applied) and T_b of rows of lens[b] samples (either output may be NULL); pad_to and a row beyond max_seconds are
  * rejected as by the calls below */

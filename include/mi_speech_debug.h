@@ -317,6 +317,15 @@ mis_status mis_debug_sortformer_intake(int device, const float* x, const int32_t
 mis_status mis_debug_sortformer_glu_dwconv(int device, const float* pw, const float* taps, const float* shift, const int32_t* cnt, int batch, int Tp, int C,
                                            int k, float* out);
 mis_status mis_debug_sortformer_peak(int device, const float* pcm, int64_t stride, const int32_t* N, int batch, int on, float* scale_out);
+/* the bf16 BART tower (csrc/sortformer_tf_bf16.h), ONE launch each on caller-supplied host data, guards as above; bf16 tensors as bits.
+ *   sortformer_tf_attn_bf16: k_sf_tf_attn_bf16, head sizes 1..64; qkv [batch Tp][ld], cnt [batch] -> out [batch Tp][heads hd].
+ *   sortformer_tf_tail_bf16: k_sf_tf_tail_bf16; att bf16 and g f32 [batch Tp][dt], cnt [batch], Wo [dt][dt], W1 [ft][dt], W2 [dt][ft] bf16,
+ *     biases and LayerNorm parameters f32; dt, ft multiples of 32 up to 256 / 1024 -> g_out f32 and g16_out bf16 [batch Tp][dt]. */
+mis_status mis_debug_sortformer_tf_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp, int heads,
+                                             int hd, float qscale, int ldo, uint16_t* out);
+mis_status mis_debug_sortformer_tf_tail_bf16(int device, const uint16_t* att, const float* g, const int32_t* cnt, int batch, int Tp, int dt, int ft, float eps,
+                                             const uint16_t* Wo, const float* bo, const float* ln1w, const float* ln1b, const uint16_t* W1, const float* b1,
+                                             const uint16_t* W2, const float* b2, const float* ln2w, const float* ln2b, float* g_out, uint16_t* g16_out);
 
 /* csrc/parakeet.hip: ONE launch of a new kernel on caller-supplied host data, and the device intervals of a generate.
  *   parakeet_attn: k_pk_attn, head sizes 65..128; arguments as mis_debug_sortformer_attn with rel = 1 (qkv [batch Tp][ld], cnt [batch],

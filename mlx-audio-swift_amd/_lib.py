@@ -484,6 +484,7 @@ SYMBOLS = {
     "mis_sortformer_create": (C.c_int, [C.POINTER(SortformerConfigC), C.c_int, C.POINTER(_P)]),
     "mis_sortformer_set_tensor": (C.c_int, [_P, C.c_char_p, _P, C.c_int, C.POINTER(C.c_int64), C.c_int]),
     "mis_sortformer_init_synthetic": (C.c_int, [_P, C.c_uint64]),
+    "mis_sortformer_set_encoder_dtype": (C.c_int, [_P, C.c_int]),
     "mis_sortformer_finalize": (C.c_int, [_P]),
     "mis_sortformer_destroy": (None, [_P]),
     "mis_sortformer_launches": (C.c_int, [_P]),
@@ -724,6 +725,9 @@ DEBUG_SYMBOLS = {
     "mis_debug_sortformer_intake": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "mis_debug_sortformer_glu_dwconv": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_sortformer_peak": (C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int, C.c_int, _P]),
+    "mis_debug_sortformer_tf_attn_bf16": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "mis_debug_sortformer_tf_tail_bf16": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                    _P, _P]),
     "mis_debug_parakeet_attn": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
                                           C.c_int, C.c_int, C.c_int, _P]),
     "mis_debug_parakeet_tdt": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,

@@ -433,8 +433,10 @@ static void pk_bf16_tables(Ctx* c) {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
 }
+#endif
 
-// c->emb -> the Conformer blocks in bf16 mode -> c->h (1 + 15 L launches, as pk_encoder)
+// c->emb -> the Conformer blocks in bf16 mode -> c->h (1 + 15 L launches, as pk_encoder).  Any handle whose fc / fc16 layers carry the
+// members read here: Parakeet's and Canary's PkEncoder, Sortformer's own (sortformer.hip).
 template <class Ctx>
 static void pk_encoder_bf16(Ctx* c, int stop) {
     const int B = c->batch, Tp = c->Tp, d = c->d, f = c->f, M = B * Tp;
@@ -454,8 +456,8 @@ static void pk_encoder_bf16(Ctx* c, int stop) {
     };
     bf16_t *big = c->big16.p, *qkv = c->qkv16.p, *att = c->att16.p;
     for (int li = 0; li < c->L; ++li) {                            // 15 launches a block
-        const PkEncoder::Layer& l = c->fc[li];
-        const PkEncoder::Layer16& w = c->fc16[li];
+        const auto& l = c->fc[li];
+        const auto& w = c->fc16[li];
         stats();
         gemm(PKB_FF1A, w.ff1a, l.ff1a.b, f, d, l.ln1w, l.ln1b, nullptr, big, 0.0f);
         gemm(PKB_FF1B, w.ff1b, l.ff1b.b, d, f, nullptr, nullptr, big, nullptr, 0.5f);
@@ -475,6 +477,5 @@ static void pk_encoder_bf16(Ctx* c, int stop) {
         if (stop == li + 1) return;
     }
 }
-#endif
 
 }  // namespace

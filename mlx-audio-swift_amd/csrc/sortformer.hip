@@ -40,6 +40,13 @@
 //
 // Launches (derived from the chain below): forward 11 + 15 L_fc + 7 L_tf; forward_features 8 + 15 L_fc + 7 L_tf;
 // encode_embeddings 4 + 15 L_fc + 7 L_tf; pre_encode 4; features 3.
+//
+// bf16 mode (opt-in, mis_sortformer_set_encoder_dtype before finalize; the f32 chain above keeps its code, bits, launches and buffers).
+// The Conformer blocks run pk_encoder_bf16 of parakeet_encoder_bf16.h on bf16 matrices, tables and big / qkv / att buffers; the BART
+// tower runs sf_tower_bf16 of sortformer_tf_bf16.h, three launches a layer, behind ONE k_pk_round_bf16 of the projection.  Front end,
+// stem, projection + positions and the head stay on k_sf_gemm; the streams h and g are f32 in both modes, so the taps are too.  The
+// rounded matrices and tables exist on the device as bf16 only.  Launches: forward 12 + 15 L_fc + 3 L_tf; forward_features 9 + ...;
+// encode_embeddings 5 + ...; pre_encode 4; features 3.  The precision contracts stand in the two headers and in mi_speech.h.
 #include "common.h"
 #define AUDIO_FRONT_NEMO_KERNELS
 #include "audio_front.h"
@@ -47,6 +54,9 @@
 #include "host_weights.h"
 #include "step_loop.h"
 #include "sortformer_kernels.h"     // every k_sf_* kernel described above but k_sf_peak, and sf_gemm / sf_lin / sf_attn
+#define PKB_NO_PARAKEET_CHAIN       // the tables are projected in finalize below
+#include "parakeet_encoder_bf16.h"  // bf16 mode: k_pk_gemm_bf16, k_pk_attn_bf16, k_pk_glu_dwconv_bf16, k_pk_round_bf16, pk_encoder_bf16
+#include "sortformer_tf_bf16.h"     // bf16 mode: k_sf_tf_attn_bf16, k_sf_tf_tail_bf16, sf_tower_bf16
 
 #include <math.h>
 #include <string.h>
@@ -75,6 +85,8 @@ struct SfFcLayer {
     SfLin ff1a, ff1b, qkv, o, pw1, pw2, ff2a, ff2b;
 };
 struct SfTfLayer { SfLin qkv, o, fc1, fc2; const float *ln1w, *ln1b, *ln2w, *ln2b; };
+// bf16 mode: the matrices [N][K] and the rounded table [2 Tcap - 1][d] (the SfLin::w of these are null then; the biases stay f32)
+struct SfFcLayer16 { bf16_t *ff1a, *ff1b, *qkv, *o, *pw1, *pw2, *ff2a, *ff2b, *P; };
 
 struct mis_sortformer {
     int device = 0;
@@ -102,6 +114,11 @@ struct mis_sortformer {
     bool timed = false;
     bool has_emb = false;        // the last call left the stem's embeddings of ITS rows in emb
     bool timed_done = false;     // the last call was a timed forward: all five events are recorded
+    // bf16 mode: big / qkv / att / gq / ga / gf are not allocated, these are
+    bool enc_bf16 = false;
+    std::vector<SfFcLayer16> fc16;
+    std::vector<SfTfLayer16> tf16;
+    DevBuf<bf16_t> warena, ptab16, big16, qkv16, att16, g16, gq16, ga16;
 };
 
 static inline int sf_half(int t) { return t >= 1 ? (t - 1) / 2 + 1 : 0; }
@@ -188,13 +205,25 @@ extern "C" mis_status mis_sortformer_set_tensor(mis_sortformer* c, const char* n
     MIS_API_END
 }
 
+// MIS_F32 (the default) or MIS_BF16, before finalize.  Refused, the handle left as it was: another dtype, a finalized handle, and for
+// MIS_BF16 widths the bf16 kernels do not serve (whole k-slabs of 32 everywhere; the tower inside the tail's LDS tile).
+extern "C" mis_status mis_sortformer_set_encoder_dtype(mis_sortformer* c, mis_dtype dtype) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(c, MIS_ERR_INVALID_INPUT, "null argument");
+    if (dtype == MIS_BF16 && !c->finalized) sft_check(c->cfg);
+    pk_set_encoder_dtype(c, dtype);
+    MIS_API_END
+}
+
 extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
     MIS_API_BEGIN
     MIS_REQUIRE(c && !c->finalized, MIS_ERR_INVALID_INPUT, "bad handle");
     HIP_CHECK(hipSetDevice(c->device));
     const int64_t mels = c->mels, C = c->C, d = c->d, f = c->f, ck = c->ck, dt = c->dt, ft = c->ft, S = c->S, F3 = c->F3, H = c->H, hd = c->hd;
-    const bool ab = c->cfg.attention_bias != 0, kb = c->cfg.k_proj_bias != 0;
+    const bool ab = c->cfg.attention_bias != 0, kb = c->cfg.k_proj_bias != 0, b16 = c->enc_bf16;
     HostArena a(c->raw);
+    HostArena tonly(c->raw);                                 // bf16 mode: the f32 sinusoid table and relative_k_proj, for the projection below only
+    HostArena& ta = b16 ? tonly : a;
     std::vector<float>& fh = a.fhost;
     // ---- front end tables: window 400 -> 512, FFT twiddles, slaney filters [257][mels] and each filter's bin range
     const size_t o_win = a.ftake(NEMO_NFFT, c->window), o_twc = a.ftake(NEMO_NFFT / 2, c->twc), o_tws = a.ftake(NEMO_NFFT / 2, c->tws);
@@ -208,19 +237,28 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
     c->Fcap = sf_frames(c->maxN, 16); c->T1cap = sf_half(c->Fcap); c->T2cap = sf_half(c->T1cap); c->Tcap = sf_half(c->T2cap);
     const int Tc = c->Tcap, NP = 2 * Tc - 1;
     // ---- weights; an absent bias stays nullptr
-    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l) {
+    // a matrix of the two encoders: the f32 arena, or (bf16 mode, wb given) rounded once into the bf16 arena
+    auto mat = [&](const std::string& name, std::initializer_list<int64_t> shape, int64_t n, const float*& wf, bf16_t** wb) {
+        if (!(b16 && wb)) { a.fvec(name, shape, n, wf); return; }
+        const HostTensor& t = c->raw.need(name, shape);
+        const size_t off = a.btake((size_t)n, *wb);
+        for (int64_t i = 0; i < n; ++i) a.host[off + i] = f32_to_bf16(t.v[i]);
+    };
+    auto lin = [&](const std::string& p, int64_t N, int64_t K, bool bias, SfLin& l, bf16_t** wb = nullptr) {
         l = SfLin{};
-        a.fvec(p + ".weight", {N, K}, N * K, l.w);
+        mat(p + ".weight", {N, K}, N * K, l.w, wb);
         if (bias) a.fvec(p + ".bias", {N}, N, l.b);
     };
     // three linears over the same input as one [N0 + N1 + N2][K]; an absent bias is zero
-    auto lin3 = [&](const std::string& p, const char* n0, const char* n1, const char* n2, int64_t N, bool b0, bool b1, bool b2, SfLin& l) {
-        const size_t ow = a.ftake((size_t)3 * N * N, l.w), ob = a.ftake(3 * N, l.b);
+    auto lin3 = [&](const std::string& p, const char* n0, const char* n1, const char* n2, int64_t N, bool b0, bool b1, bool b2, SfLin& l, bf16_t*& wb) {
+        l = SfLin{};
+        const size_t ow = b16 ? a.btake((size_t)3 * N * N, wb) : a.ftake((size_t)3 * N * N, l.w), ob = a.ftake(3 * N, l.b);
         const char* names[3] = {n0, n1, n2};
         const bool has[3] = {b0, b1, b2};
         for (int i = 0; i < 3; ++i) {
             const HostTensor& w = c->raw.need(p + names[i] + ".weight", {N, N});
-            std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * N * N);
+            if (b16) for (int64_t j = 0; j < N * N; ++j) a.host[ow + (size_t)i * N * N + j] = f32_to_bf16(w.v[j]);
+            else std::copy(w.v.begin(), w.v.end(), fh.begin() + ow + (size_t)i * N * N);
             if (has[i]) { const HostTensor& bb = c->raw.need(p + names[i] + ".bias", {N}); std::copy(bb.v.begin(), bb.v.end(), fh.begin() + ob + (size_t)i * N); }
         }
     };
@@ -246,20 +284,22 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
             fh[ow + (n * F3 + fq) * C + ch] = w.v[n * C * F3 + ch * F3 + fq];
     }
     c->fc.assign(c->L, SfFcLayer{});
+    c->fc16.assign(c->L, SfFcLayer16{});
     std::vector<SfLin> rk(c->L);                         // relative_k_proj: used once, below
     for (int li = 0; li < c->L; ++li) {
         const std::string q = "fc_encoder.layers." + std::to_string(li) + ".";
         SfFcLayer& l = c->fc[li];
+        SfFcLayer16& l16 = c->fc16[li];
         norm(q + "norm_feed_forward1", d, l.ln1w, l.ln1b);
-        lin(q + "feed_forward1.linear1", f, d, true, l.ff1a); lin(q + "feed_forward1.linear2", d, f, true, l.ff1b);
+        lin(q + "feed_forward1.linear1", f, d, true, l.ff1a, &l16.ff1a); lin(q + "feed_forward1.linear2", d, f, true, l.ff1b, &l16.ff1b);
         norm(q + "norm_self_att", d, l.lnaw, l.lnab);
-        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", d, ab, ab, ab, l.qkv);
-        lin(q + "self_attn.o_proj", d, d, ab, l.o);
-        a.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, rk[li].w);
+        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", d, ab, ab, ab, l.qkv, l16.qkv);
+        lin(q + "self_attn.o_proj", d, d, ab, l.o, &l16.o);
+        ta.fvec(q + "self_attn.relative_k_proj.weight", {d, d}, d * d, rk[li].w);
         a.fvec(q + "self_attn.bias_u", {H, hd}, d, l.u); a.fvec(q + "self_attn.bias_v", {H, hd}, d, l.v);
         norm(q + "norm_conv", d, l.lncw, l.lncb);
-        a.fvec(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w); a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d, l.pw1.b);
-        a.fvec(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w); a.fvec(q + "conv.pointwise_conv2.bias", {d}, d, l.pw2.b);
+        mat(q + "conv.pointwise_conv1.weight", {2 * d, 1, d}, 2 * d * d, l.pw1.w, &l16.pw1); a.fvec(q + "conv.pointwise_conv1.bias", {2 * d}, 2 * d, l.pw1.b);
+        mat(q + "conv.pointwise_conv2.weight", {d, 1, d}, d * d, l.pw2.w, &l16.pw2); a.fvec(q + "conv.pointwise_conv2.bias", {d}, d, l.pw2.b);
         // inference BatchNorm folded into the depthwise taps and a shift
         const HostTensor& dw = c->raw.need(q + "conv.depthwise_conv.weight", {d, ck, 1});
         const HostTensor& dwb = c->raw.need(q + "conv.depthwise_conv.bias", {d});
@@ -268,19 +308,21 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
         const size_t o_dw = a.ftake((size_t)ck * d, l.dw), o_sh = a.ftake(d, l.dwshift);
         fold_bn_dwconv(&fh[o_dw], &fh[o_sh], dw.v.data(), dwb.v.data(), bw.v.data(), bb.v.data(), bm.v.data(), bv.v.data(), d, ck);
         norm(q + "norm_feed_forward2", d, l.ln2w, l.ln2b);
-        lin(q + "feed_forward2.linear1", f, d, true, l.ff2a); lin(q + "feed_forward2.linear2", d, f, true, l.ff2b);
+        lin(q + "feed_forward2.linear1", f, d, true, l.ff2a, &l16.ff2a); lin(q + "feed_forward2.linear2", d, f, true, l.ff2b, &l16.ff2b);
         norm(q + "norm_out", d, l.lnow, l.lnob);
     }
     const int64_t msp = c->cfg.max_source_positions;
     a.fvec("tf_encoder.embed_positions.weight", {msp, dt}, msp * dt, c->pos);
     c->tf.assign(c->Lt, SfTfLayer{});
+    c->tf16.assign(c->Lt, SfTfLayer16{});
     for (int li = 0; li < c->Lt; ++li) {
         const std::string q = "tf_encoder.layers." + std::to_string(li) + ".";
         SfTfLayer& l = c->tf[li];
-        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", dt, true, kb, true, l.qkv);
-        lin(q + "self_attn.out_proj", dt, dt, true, l.o);
+        SfTfLayer16& l16 = c->tf16[li];
+        lin3(q + "self_attn.", "q_proj", "k_proj", "v_proj", dt, true, kb, true, l.qkv, l16.qkv);
+        lin(q + "self_attn.out_proj", dt, dt, true, l.o, &l16.o);
         norm(q + "self_attn_layer_norm", dt, l.ln1w, l.ln1b);
-        lin(q + "fc1", ft, dt, true, l.fc1); lin(q + "fc2", dt, ft, true, l.fc2);
+        lin(q + "fc1", ft, dt, true, l.fc1, &l16.fc1); lin(q + "fc2", dt, ft, true, l.fc2, &l16.fc2);
         norm(q + "final_layer_norm", dt, l.ln2w, l.ln2b);
     }
     const std::string SM = "sortformer_modules.";
@@ -289,26 +331,32 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
     c->raw.need(SM + "hidden_to_spks.weight", {S, 2 * dt}); c->raw.need(SM + "hidden_to_spks.bias", {S});   // loaded and checked, unused
     // ---- the sinusoid table by distance: row d + Tcap - 1, columns interleaved sin, cos; formed in double, rounded once
     const float* tab = nullptr;
-    const size_t o_tab = a.ftake((size_t)NP * d, tab);
+    const size_t o_tab = ta.ftake((size_t)NP * d, tab);
     for (int r = 0; r < NP; ++r) {
         const double dist = (double)(r - (Tc - 1));
         for (int64_t k = 0; 2 * k < d; ++k) {
             const double ang = dist * exp(-(double)(2 * k) * log(10000.0) / (double)d);
-            fh[o_tab + (size_t)r * d + 2 * k] = (float)sin(ang);
-            if (2 * k + 1 < d) fh[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
+            ta.fhost[o_tab + (size_t)r * d + 2 * k] = (float)sin(ang);
+            if (2 * k + 1 < d) ta.fhost[o_tab + (size_t)r * d + 2 * k + 1] = (float)cos(ang);
         }
     }
     // ---- upload: every pointer bound above now addresses the device arena
-    DevBuf<bf16_t> none;
-    a.upload(none, c->farena);
+    a.upload(c->warena, c->farena);
     c->fbr.alloc(2 * mels);
     HIP_CHECK(hipMemcpy(c->fbr.p, ranges.data(), 2 * mels * sizeof(int), hipMemcpyHostToDevice));
-    // each layer's relative_k_proj of the table: one GEMM, once
-    c->ptab.alloc((size_t)c->L * NP * d);
+    // each layer's relative_k_proj of the table: one GEMM, once; bf16 mode rounds the f32 projection into ptab16 and keeps nothing in f32
+    const size_t per = (size_t)NP * d;
+    DevBuf<bf16_t> none;
+    DevBuf<float> tdev, proj;
+    if (b16) { tonly.upload(none, tdev); proj.alloc(per); c->ptab16.alloc(c->L * per); }
+    else c->ptab.alloc(c->L * per);
     for (int li = 0; li < c->L; ++li) {
-        float* dst = c->ptab.p + (size_t)li * NP * d;
+        float* dst = b16 ? proj.p : c->ptab.p + li * per;
         sf_gemm(c, sf_lin(tab, (int)d, rk[li], dst, (int)d, nullptr, NP), 1);
-        c->fc[li].P = dst;
+        if (b16) {
+            MIS_LAUNCH(c, k_pk_round_bf16, dim3((unsigned)((per + 255) / 256)), dim3(256), dst, c->ptab16.p + li * per, per);
+            c->fc16[li].P = c->ptab16.p + li * per;
+        } else c->fc[li].P = dst;
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -317,8 +365,15 @@ extern "C" mis_status mis_sortformer_finalize(mis_sortformer* c) {
     const size_t B = c->cfg.max_batch, M = B * Tc;
     c->pcm.alloc(B * c->maxN); c->scale.alloc(B); c->melraw.alloc(B * c->Fcap * mels); c->feats.alloc(B * c->Fcap * mels);
     c->s0.alloc(B * c->T1cap * c->F1 * C); c->s1.alloc(B * c->T2cap * c->F2 * C); c->s2.alloc(M * F3 * C); c->emb.alloc(M * d);
-    c->h.alloc(M * d); c->x.alloc(M * d); c->stats.alloc(M * 2); c->big.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d);
-    c->g.alloc(M * dt); c->gx.alloc(M * dt); c->gq.alloc(M * 3 * dt); c->ga.alloc(M * dt); c->gf.alloc(M * ft); c->probs.alloc(M * S);
+    c->h.alloc(M * d); c->x.alloc(M * d); c->stats.alloc(M * 2);
+    c->g.alloc(M * dt); c->gx.alloc(M * dt); c->probs.alloc(M * S);
+    if (b16) {
+        c->big16.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv16.alloc(M * 3 * d); c->att16.alloc(M * d);
+        c->g16.alloc(M * dt); c->gq16.alloc(M * 3 * dt); c->ga16.alloc(M * dt);
+    } else {
+        c->big.alloc(M * std::max<size_t>(f, 2 * d)); c->qkv.alloc(M * 3 * d); c->att.alloc(M * d);
+        c->gq.alloc(M * 3 * dt); c->ga.alloc(M * dt); c->gf.alloc(M * ft);
+    }
     c->cntN.alloc(B); c->cntF0.alloc(B); c->cntF.alloc(B); c->cnt1.alloc(B); c->cnt2.alloc(B); c->cnt3.alloc(B);
     c->raw.clear();
     c->finalized = true;
@@ -452,12 +507,10 @@ static void sf_stem(mis_sortformer* c) {
     c->has_emb = true;
 }
 
-// c->emb -> Conformer blocks -> projection -> BART layers -> c->probs.  stop: -1 everything; 1 .. L behind that block (c->h);
-// L + 1 behind the projection, L + 2 .. L + 1 + Lt behind that BART layer (c->g).
-static void sf_encoder(mis_sortformer* c, int stop) {
-    const int B = c->batch, Tp = c->Tp, d = c->d, f = c->f, dt = c->dt, ft = c->ft, M = B * Tp, L = c->L;
+// the f32 Conformer half: c->emb -> c->h, 1 + 15 L launches; returns behind block `stop`
+static void sf_conformer(mis_sortformer* c, int stop) {
+    const int B = c->batch, Tp = c->Tp, d = c->d, f = c->f, M = B * Tp, L = c->L;
     const int* cnt = c->cnt3.p;
-    hipStream_t s = c->stream;
     const size_t nd = (size_t)M * d;
     MIS_LAUNCH(c, k_sf_intake, dim3((unsigned)((nd + 255) / 256)), dim3(256), c->emb.p, c->h.p, cnt, Tp, d,
               c->cfg.scale_input ? sqrtf((float)d) : 1.0f, nd);
@@ -492,6 +545,17 @@ static void sf_encoder(mis_sortformer* c, int stop) {
         MIS_LAUNCH(c, k_sf_ln, dim3(cdiv(M, 4)), dim3(256), c->h.p, c->h.p, l.lnow, l.lnob, d, 1e-5f, M, cnt, Tp);
         if (stop == li + 1) return;
     }
+}
+
+// c->emb -> Conformer blocks -> projection -> BART layers -> c->probs.  stop: -1 everything; 1 .. L behind that block (c->h);
+// L + 1 behind the projection, L + 2 .. L + 1 + Lt behind that BART layer (c->g).
+static void sf_encoder(mis_sortformer* c, int stop) {
+    const int B = c->batch, Tp = c->Tp, d = c->d, dt = c->dt, ft = c->ft, M = B * Tp, L = c->L;
+    const int* cnt = c->cnt3.p;
+    hipStream_t s = c->stream;
+    if (c->enc_bf16) pk_encoder_bf16(c, stop);
+    else sf_conformer(c, stop);
+    if (stop >= 1 && stop <= L) return;
     if (c->timed) HIP_CHECK(hipEventRecord(c->ev[3], s));
     {   // encoder_proj + embed_positions[0 .. T)
         SfGemm p = sf_lin(c->h.p, d, c->proj, c->g.p, dt, cnt, Tp);
@@ -500,7 +564,11 @@ static void sf_encoder(mis_sortformer* c, int stop) {
     }
     if (stop == L + 1) return;
     const float eps = c->cfg.layer_norm_eps;
-    for (int li = 0; li < c->Lt; ++li) {                           // 7 launches a layer
+    if (c->enc_bf16) {                                             // 1 + 3 launches a layer
+        sf_tower_bf16(c, stop);
+        if (stop >= L + 2) return;
+    }
+    for (int li = 0; li < c->Lt && !c->enc_bf16; ++li) {           // 7 launches a layer
         const SfTfLayer& l = c->tf[li];
         sf_gemm(c, sf_lin(c->g.p, dt, l.qkv, c->gq.p, 3 * dt, cnt, Tp), B);
         SfAttn ap{c->gq.p, 3 * dt, dt, 2 * dt, c->ga.p, dt, cnt, Tp, c->hdt, powf((float)c->hdt, -0.5f), 1.0f, nullptr, nullptr, nullptr, 0, 0};
@@ -909,5 +977,73 @@ extern "C" mis_status mis_debug_sortformer_peak(int device, const float* pcm, in
     sfd_sync(c);
     o.check_guards();
     HIP_CHECK(hipMemcpy(scale_out, o.p(), o.body, hipMemcpyDeviceToHost));
+    MIS_API_END
+}
+
+// ---------------------------------------------------------------------------- the bf16 tower's kernels (sortformer_tf_bf16.h)
+// ONE launch of k_sf_tf_attn_bf16: qkv bf16 bits [batch Tp][ld] (q at column h hd, k at koff + h hd, v at voff + h hd), cnt [batch], head sizes
+// 1..64 -> out bf16 bits [batch Tp][heads hd] taken from rows of ldo columns
+extern "C" mis_status mis_debug_sortformer_tf_attn_bf16(int device, const uint16_t* qkv, int ld, int koff, int voff, const int32_t* cnt, int batch, int Tp,
+                                                        int heads, int hd, float qscale, int ldo, uint16_t* out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(qkv && cnt && out && batch >= 1 && batch <= 65535 && Tp >= 1 && heads >= 1 && hd >= 1 && hd <= 64, MIS_ERR_INVALID_INPUT,
+                "Sortformer bf16 tower attention: qkv, cnt, out, positive batch, Tp, heads and a head size of 1..64 (two slabs of 32) are required");
+    const int64_t width = (int64_t)heads * hd;
+    MIS_REQUIRE(koff >= 0 && voff >= 0 && width <= ld && koff + width <= ld && voff + width <= ld && width <= ldo, MIS_ERR_INVALID_INPUT,
+                "Sortformer bf16 tower attention: q, k and v must lie inside a row of ld columns, the output inside ldo");
+    MIS_REQUIRE((int64_t)batch * Tp * ld <= SFD_MAX_ELEMS && (int64_t)batch * Tp * ldo <= SFD_MAX_ELEMS && cdiv(heads, 4) <= 65535, MIS_ERR_INVALID_INPUT,
+                "Sortformer bf16 tower attention: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    const size_t rows = (size_t)batch * Tp;
+    DevBuf<uint16_t> dq;
+    DevBuf<uint32_t> dcnt;
+    alloc16(dq, qkv, rows * ld, BF16_NAN);
+    sfd_counts(dcnt, cnt, batch);
+    GuardedOut o;
+    o.alloc(rows * ldo * 2, (size_t)16 * ldo * 2);                 // a guard is one 16-query tile of output
+    sft_attn(&c, SftAttn{dq.p, ld, koff, voff, reinterpret_cast<bf16_t*>(o.p()), ldo, sfd_ip(dcnt), Tp, hd, heads, qscale}, batch);
+    sfd_sync(c);
+    o.check_guards();
+    std::vector<uint16_t> h(rows * ldo);
+    HIP_CHECK(hipMemcpy(h.data(), o.p(), o.body, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; ++r) {
+        memcpy(out + r * width, h.data() + r * ldo, width * 2);
+        for (size_t k = width; k < (size_t)ldo; ++k)
+            MIS_REQUIRE(h[r * ldo + k] == 0xFFFFu, MIS_ERR_GENERATION_FAILED, "the kernel wrote column %zu of row %zu behind its %lld columns", k, r, (long long)width);
+    }
+    MIS_API_END
+}
+
+// ONE launch of k_sf_tf_tail_bf16: att bf16 bits and g f32 [batch Tp][dt], cnt [batch]; Wo [dt][dt], W1 [ft][dt], W2 [dt][ft] bf16 bits; bo, ln1w,
+// ln1b, b2, ln2w, ln2b [dt] and b1 [ft] f32 -> g_out f32 and g16_out bf16 bits [batch Tp][dt].  dt, ft multiples of 32 up to 256 / 1024.
+extern "C" mis_status mis_debug_sortformer_tf_tail_bf16(int device, const uint16_t* att, const float* g, const int32_t* cnt, int batch, int Tp, int dt, int ft,
+                                                        float eps, const uint16_t* Wo, const float* bo, const float* ln1w, const float* ln1b,
+                                                        const uint16_t* W1, const float* b1, const uint16_t* W2, const float* b2, const float* ln2w,
+                                                        const float* ln2b, float* g_out, uint16_t* g16_out) {
+    MIS_API_BEGIN
+    MIS_REQUIRE(att && g && cnt && Wo && bo && ln1w && ln1b && W1 && b1 && W2 && b2 && ln2w && ln2b && g_out && g16_out && batch >= 1 && batch <= 65535 && Tp >= 1,
+                MIS_ERR_INVALID_INPUT, "Sortformer bf16 tower tail: every pointer and positive batch and Tp are required");
+    MIS_REQUIRE(dt >= 32 && dt % 32 == 0 && dt <= SFT_DT_MAX && ft >= 32 && ft % 32 == 0 && ft <= SFT_FT_MAX, MIS_ERR_INVALID_INPUT,
+                "Sortformer bf16 tower tail: dt and ft must be multiples of 32 up to %d / %d (the LDS tile)", SFT_DT_MAX, SFT_FT_MAX);
+    MIS_REQUIRE((int64_t)batch * Tp * dt <= SFD_MAX_ELEMS, MIS_ERR_INVALID_INPUT, "Sortformer bf16 tower tail: tensor too large");
+    HIP_CHECK(hipSetDevice(device));
+    SfdCtx c;
+    const size_t n = (size_t)batch * Tp * dt;
+    DevBuf<uint16_t> da, dwo, dw1, dw2;
+    DevBuf<uint32_t> dg, dcnt, dbo, dl1w, dl1b, db1, db2, dl2w, dl2b;
+    alloc16(da, att, n, BF16_NAN); alloc16(dwo, Wo, (size_t)dt * dt, BF16_NAN); alloc16(dw1, W1, (size_t)ft * dt, BF16_NAN); alloc16(dw2, W2, (size_t)dt * ft, BF16_NAN);
+    sfd_f32(dg, g, n); sfd_counts(dcnt, cnt, batch);
+    sfd_f32(dbo, bo, dt); sfd_f32(dl1w, ln1w, dt); sfd_f32(dl1b, ln1b, dt); sfd_f32(db1, b1, ft); sfd_f32(db2, b2, dt); sfd_f32(dl2w, ln2w, dt); sfd_f32(dl2b, ln2b, dt);
+    GuardedOut of, ob;
+    of.alloc(n * 4, (size_t)16 * dt * 4);                          // a guard is one 16-row tile of output
+    ob.alloc(n * 2, (size_t)16 * dt * 2);
+    sft_tail(&c, SftTail{da.p, sfd_fp(dg), sfd_out(of), reinterpret_cast<bf16_t*>(ob.p()), sfd_ip(dcnt), Tp, dt, ft, eps, dwo.p, dw1.p, dw2.p, sfd_fp(dbo),
+                         sfd_fp(db1), sfd_fp(db2), sfd_fp(dl1w), sfd_fp(dl1b), sfd_fp(dl2w), sfd_fp(dl2b)}, batch);
+    sfd_sync(c);
+    of.check_guards();
+    ob.check_guards();
+    HIP_CHECK(hipMemcpy(g_out, of.p(), of.body, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(g16_out, ob.p(), ob.body, hipMemcpyDeviceToHost));
     MIS_API_END
 }

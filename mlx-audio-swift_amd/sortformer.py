@@ -9,7 +9,7 @@ import json
 import math
 import os
 import time
-from dataclasses import dataclass, field, fields
+from dataclasses import dataclass, field, fields, replace
 
 import numpy as np
 
@@ -88,7 +88,8 @@ class ProcessorConfig:
 @dataclass
 class SortformerConfig:
     """SortformerConfig (SortformerConfig.swift:191-217).  A nested config that is absent is decoded from the top-level dictionary (the
-    flat-config fallback).  max_batch / max_seconds size the engine's workspace and are not part of a checkpoint."""
+    flat-config fallback).  max_batch / max_seconds size the engine's workspace and encoder_dtype selects its arithmetic; none of the
+    three is part of a checkpoint."""
     model_type: str = "sortformer"
     num_speakers: int = 4
     fc_encoder_config: FCEncoderConfig = field(default_factory=FCEncoderConfig)
@@ -97,6 +98,7 @@ class SortformerConfig:
     processor_config: ProcessorConfig = field(default_factory=ProcessorConfig)
     max_batch: int = 8
     max_seconds: int = 90
+    encoder_dtype: str = "float32"   # "bfloat16": both encoders in bf16 (csrc/parakeet_encoder_bf16.h, csrc/sortformer_tf_bf16.h)
 
     @classmethod
     def from_dict(cls, d: dict, **workspace) -> "SortformerConfig":
@@ -393,49 +395,59 @@ class SortformerModel(NativeHandle):
     def __init__(self, config: SortformerConfig, device: int = 0):
         self.config, self.device = config, device
         self._create(config.to_c(), device)
+        if config.encoder_dtype != "float32":
+            self.set_encoder_dtype(config.encoder_dtype)
 
     sanitize = staticmethod(sortformer_sanitize)
     preds_to_segments = staticmethod(preds_to_segments)
     maybe_compress_state = staticmethod(maybe_compress_state)
 
     @classmethod
-    def from_weights(cls, config: SortformerConfig, weights: dict, device: int = 0) -> "SortformerModel":
-        """weights: sanitized names (what sortformer_sanitize returns)."""
-        m = cls(config, device)
+    def from_weights(cls, config: SortformerConfig, weights: dict, device: int = 0, encoder_dtype: str | None = None) -> "SortformerModel":
+        """weights: sanitized names (what sortformer_sanitize returns); encoder_dtype overrides the config's."""
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         for name, arr in weights.items():
             m.set_tensor(name, arr)
         m.finalize()
         return m
 
     @classmethod
-    def synthetic(cls, config: SortformerConfig, device: int = 0, seed: int = 777) -> "SortformerModel":
-        m = cls(config, device)
+    def synthetic(cls, config: SortformerConfig, device: int = 0, seed: int = 777, encoder_dtype: str | None = None) -> "SortformerModel":
+        m = cls(replace(config, encoder_dtype=encoder_dtype) if encoder_dtype else config, device)
         check(_lib.lib().mis_sortformer_init_synthetic(m._h, seed))
         m.finalize()
         return m
 
     @classmethod
-    def from_model_directory(cls, model_dir: str, device: int = 0, **workspace) -> "SortformerModel":
-        """fromModelDirectory (:1406-1432): config.json, every *.safetensors; keys the model does not have are rejected."""
+    def from_model_directory(cls, model_dir: str, device: int = 0, encoder_dtype: str | None = None, **workspace) -> "SortformerModel":
+        """fromModelDirectory (:1406-1432): config.json, every *.safetensors; keys the model does not have are rejected.
+        workspace: max_batch / max_seconds / encoder_dtype; the encoder_dtype argument overrides it."""
         with open(os.path.join(model_dir, "config.json")) as f:
             config = SortformerConfig.from_dict(json.load(f), **workspace)
         weights = sortformer_sanitize(read_safetensors_dir(model_dir, missing_code=(2, f"No safetensors files found in {model_dir}")))
         unknown = sorted(set(weights) - sortformer_expected_keys(config))
         if unknown:
             raise AudioGenerationError(3, f"Sortformer checkpoint: unused keys {unknown[:4]}")
-        return cls.from_weights(config, weights, device)
+        return cls.from_weights(config, weights, device, encoder_dtype)
 
     @classmethod
-    def from_pretrained(cls, path: str, device: int = 0, **workspace) -> "SortformerModel":
+    def from_pretrained(cls, path: str, device: int = 0, encoder_dtype: str | None = None, **workspace) -> "SortformerModel":
         """Local directories only: nothing is downloaded."""
         if not os.path.isdir(path):
             raise AudioGenerationError(3, f"Sortformer: {path} is not a local model directory")
-        return cls.from_model_directory(path, device, **workspace)
+        return cls.from_model_directory(path, device, encoder_dtype, **workspace)
 
     # -- sizes ---------------------------------------------------------------------------------------
     @property
     def launches(self) -> int:
         return int(_lib.lib().mis_sortformer_launches(self._h))
+
+    @property
+    def expected_launches(self) -> dict:
+        """launches of a call as include/mi_speech.h documents them, in this model's encoder_dtype"""
+        L, Lt = self.config.fc_encoder_config.num_hidden_layers, self.config.tf_encoder_config.encoder_layers
+        chain = 15 * L + (7 * Lt if self.config.encoder_dtype == "float32" else 1 + 3 * Lt)
+        return dict(forward=11 + chain, forward_features=8 + chain, encode_embeddings=4 + chain, pre_encode=4, features=3)
 
     @property
     def frame_duration(self) -> np.float32:

@@ -3,7 +3,12 @@
 compression modes; median of 5 runs after 2 warm-ups; wall-clock, the device intervals of the forward call (front end / stem /
 Conformer / BART + head) and launches per call.
 
-    python tools/bench_sortformer.py [--out profiles/sortformer/bench.jsonl]"""
+    python tools/bench_sortformer.py [--out profiles/sortformer/bench.jsonl]
+
+--encoder-dtype bfloat16 (or both) -> profiles/sortformer_bf16/bench.jsonl: f32 mode and bf16 mode of the same build in ONE process, the two
+models alive side by side and their runs alternating (median of 7 after 3 warm-ups each).  Offline: generate_batch of 10 s x 1 / 8 / 32 and of
+one 119 s row (the longest max_source_positions 1500 admits).  Streaming: encode_embeddings alone at the frame counts generate_stream's steps
+reach with the default cache 188, FIFO 188 and 5 s chunks: 63 (the first chunk), 251, 439 (cache and FIFO full)."""
 import argparse
 import json
 import os
@@ -36,13 +41,67 @@ def median_of(fn, runs=5, warm=2):
     return statistics.median(wall), extra
 
 
+def alternating(fns, runs=7, warm=3):
+    """{name: (median wall ms, the last run's return)} of callables run in turn, so that drift of the machine meets all of them alike"""
+    wall, extra = {k: [] for k in fns}, {}
+    for i in range(warm + runs):
+        for k, fn in fns.items():
+            t0 = time.perf_counter()
+            extra[k] = fn()
+            if i >= warm:
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: (statistics.median(wall[k]), extra[k]) for k in fns}
+
+
+def compare_dtypes(dtypes):
+    rows = []
+
+    def pair(case, make, fields, **tags):
+        res = alternating(make)
+        for dt, (ms, extra) in res.items():
+            rows.append(dict(case=case, encoder_dtype=dt, wall_ms=ms, **tags, **fields(extra)))
+        if len(res) == 2:
+            rows.append(dict(case=case + "_ratio", f32_over_bf16_wall=res["float32"][0] / res["bfloat16"][0], **tags))
+
+    for batch, seconds in ((1, 10), (8, 10), (32, 10), (1, 119)):
+        models = {dt: mas.SortformerModel.synthetic(mas.SortformerConfig(max_batch=batch, max_seconds=seconds + 1), encoder_dtype=dt) for dt in dtypes}
+        audio = [wave(b, seconds) for b in range(batch)]
+        for m in models.values():
+            m.enable_timing()
+
+        def call(m):
+            m.generate_batch(audio)
+            return m.timing(), m.launches
+
+        pair("generate", {dt: (lambda m=m: call(m)) for dt, m in models.items()},
+             lambda e: dict(front_ms=e[0][0], stem_ms=e[0][1], conformer_ms=e[0][2], bart_head_ms=e[0][3], launches=e[1]), batch=batch, seconds=seconds)
+        for m in models.values():
+            m.close()
+    models = {dt: mas.SortformerModel.synthetic(mas.SortformerConfig(max_batch=1, max_seconds=60), encoder_dtype=dt) for dt in dtypes}
+    rng = np.random.default_rng(5)
+    for T in (63, 251, 439):
+        emb = rng.standard_normal((1, T, 512)).astype(np.float32)
+
+        def step(m):
+            m.encode_embeddings(emb)
+            return m.launches
+
+        pair("encode_embeddings", {dt: (lambda m=m: step(m)) for dt, m in models.items()}, lambda e: dict(launches=e), frames=T)
+    for m in models.values():
+        m.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sortformer", "bench.jsonl"))
+    ap.add_argument("--encoder-dtype", choices=("float32", "bfloat16", "both"), default="float32")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    bf16 = args.encoder_dtype != "float32"
+    args.out = args.out or os.path.join(ROOT, "profiles", "sortformer_bf16" if bf16 else "sortformer", "bench.jsonl")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    rows = []
-    for batch, seconds in ((1, 10), (8, 10), (32, 10), (1, 90)):
+    rows = compare_dtypes(("float32", "bfloat16") if args.encoder_dtype == "both" else ("bfloat16",)) if bf16 else []
+    for batch, seconds in () if bf16 else ((1, 10), (8, 10), (32, 10), (1, 90)):
         m = mas.SortformerModel.synthetic(mas.SortformerConfig(max_batch=batch, max_seconds=seconds + 1))
         m.enable_timing()
         audio = [wave(b, seconds) for b in range(batch)]
@@ -55,7 +114,7 @@ def main():
         rows.append(dict(case="generate", batch=batch, seconds=seconds, wall_ms=ms, front_ms=dev[0], stem_ms=dev[1], conformer_ms=dev[2],
                          bart_head_ms=dev[3], launches=launches, audio_seconds_per_second=batch * seconds / (ms / 1e3)))
         m.close()
-    for aosc in (False, True):
+    for aosc in () if bf16 else (False, True):
         cfg = mas.SortformerConfig(max_batch=1, max_seconds=91, modules_config=mas.ModulesConfig(use_aosc=aosc))
         m = mas.SortformerModel.synthetic(cfg)
         audio = wave(3, 90)
